@@ -23,7 +23,11 @@ per-system energies are exchanged with ONE RCCL all_gather per step.
 (rank r on GPU r, RCCL); on a box with fewer than N GPUs the ranks share device 0 over gloo (a smoke test of the N > 1 code path,
 labelled as such in `config.parallelism`).
 
-Prints ONE JSON line (rank 0) with the driver's fields plus
+A plain run (`--gpus 1 --steps K --warmup W`) does only what its headline figure needs: set-up, W warm-up steps, exactly K timed steps
+in this one process, and ONE JSON line (rank 0) with the driver's fields (`metric`, `value`, `unit`, `ms_per_step`, `higher_is_better`,
+`dtype`, ...), `config`, `ranks` and `energies`.  `--dump-outputs DIR` then writes what the last timed step computed as DIR/<name>.npy.
+`--full` adds everything else the benchmark measures or checks (the median of 3 fresh processes, the HBM calibration, the instrumented and
+isolated passes, the CPU oracle, the other configurations); its line carries in addition
   `stats`        per-step GPU time from HIP events: median / min / max (the reference protocol reports the median, benchmarks/utils.py:170-240);
                  `value` itself is the contract's wall-clock figure over exactly K steps
   `kernels`      every timed kernel: average in the timed (two-stream) region, isolated median from an untimed serial pass, SURVEY 8(d)
@@ -31,6 +35,7 @@ Prints ONE JSON line (rank 0) with the driver's fields plus
   `roofline`     the entry of the dominant kernel (largest isolated time)
   `cpu_baseline` the CPU oracle on the host: 1 thread on a bounded sample box (same density / cutoffs / spline order), and the
                  all-core OpenMP build on the FULL 100k-atom step (`--cpu-full-size` adds the 1-thread full-size leg, ~1 min)
+  `configs`      BASELINE configs 2 - 5, the reference's benchmark rows and the headline step two more ways, each from a child process
 Other workloads: `--workload c2|c3|c4` (BASELINE.json's single-GPU configurations, same JSON shape: `config.workload`, `roofline` of that
 configuration's dominant kernel, `cpu_baseline`), `--workload c5` (BASELINE config 5 shard) and `--workload ref-nlist|ref-d3|ref-pme` (the reference's own published
 benchmark configurations, BASELINE.md, with its warm-up / median protocol).
@@ -839,7 +844,7 @@ def extra_records(env):
     reported mode)."""
     out = {}
     t0 = time.perf_counter()
-    d, err = _child(["--workload", "c5", "--steps", "20", "--warmup", "3", "--processes", "1"], env)
+    d, err = _child(["--workload", "c5", "--steps", "20", "--warmup", "3", "--processes", "1", "--full"], env)
     if d is None:
         out["c5"] = {"error": err}
     else:
@@ -861,7 +866,7 @@ def extra_records(env):
                                  ("headline_graph_replay", {"BENCH_GRAPH": "1", "BENCH_CALIB": "0"},
                                   "the headline step captured once into a HIP graph (both streams) and replayed: one fresh process")):
         t0 = time.perf_counter()
-        d, err = _child(["--steps", "100", "--warmup", "10", "--processes", "1", "--cpu-sample", "0"], dict(env, BENCH_CONFIGS="0", **extra_env))
+        d, err = _child(["--steps", "100", "--warmup", "10", "--processes", "1", "--cpu-sample", "0", "--full"], dict(env, BENCH_CONFIGS="0", **extra_env))
         out[key] = ({"error": err} if d is None else
                     {"ms_per_step": d["ms_per_step"], "value": d["value"], "unit": d["unit"], "steps": d["steps"], "what": what,
                      "list_fill_40bohr_isolated_median_ms": (d.get("kernels", {}).get("nl_query_matrix_f32") or {}).get("isolated_median_ms"),
@@ -995,6 +1000,34 @@ def ref_pme(device):
                      "speedup_vs_reference_h100": h100[n] / med})
     return {"metric": "pme_reciprocal_space median ms (reference benchmark configuration: energies only, order 4, fp32)", "unit": "ms", "rows": rows,
             "source": "BASELINE.md / docs/benchmarks/benchmark_results/electrostatics_benchmark_pme_nvalchemiops_h100-80gb-hbm3.csv"}
+
+
+# ---- --dump-outputs: what the last timed step computed, for output-by-output comparison of two builds ---------------------------------
+def step_outputs(out):
+    """{name: tensor} of what a headline / config-5 step returns to its caller: PME per-atom energies and forces (fp64), D3 energy per system
+    and forces (fp32), the per-atom neighbour counts of both lists (int32; CSR format: the D3 list's row pointer)."""
+    e_pme, f_pme, e_d3, f_d3, num, nptr = out
+    return {"pme_energies": e_pme, "pme_forces": f_pme, "d3_energy": e_d3, "d3_forces": f_d3, "pme_num_neighbors": num,
+            ("d3_num_neighbors" if D3_FORMAT == "matrix" else "d3_neighbor_ptr"): nptr}
+
+
+CONFIG_OUTPUTS = {"c2": ("num_neighbors",), "c3": ("num_neighbors", "d3_energy", "d3_forces", "d3_virial"),
+                  "c4": ("num_neighbors", "pme_energies", "pme_forces")}
+
+
+def dump_outputs(directory, named, limit_bytes=64 << 20):
+    """Write every tensor as `directory/<name>.npy`: floating point as float32 / float64, integers (counts: exact) as float64.  An output
+    larger than its share of `limit_bytes` is written as a fixed sample of its rows (seed 0, sorted; the row indices go beside it)."""
+    os.makedirs(directory, exist_ok=True)
+    share = limit_bytes // max(len(named), 1) // 2  # room for the row indices of a sampled output
+    for name, t in named.items():
+        a = t.detach().cpu().numpy()
+        a = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+        if a.nbytes > share and a.ndim >= 1:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=max(1, share * a.shape[0] // a.nbytes), replace=False))
+            np.save(os.path.join(directory, f"{name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 # ---- the other BASELINE.json configurations as driver-parseable lines (VERDICT r3 next #4) ---------------------------------------------
@@ -1249,6 +1282,8 @@ def run_config(name, device, args):
     cfg = {"c2": config_c2, "c3": config_c3, "c4": config_c4}[name](device, args)
     calibration = hbm_calibration(device, gib=1.0) if os.environ.get("BENCH_CALIB", "1") != "0" else None
     out, elapsed, step_ms, kernels, timed_names, n_instr = _timed_steps(cfg["step"], args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(zip(CONFIG_OUTPUTS[name], out if isinstance(out, tuple) else (out,))))
     rows = _config_rows(kernels, cfg["acct"], name)
     for kname, r in rows.items():
         in_timed = kname in timed_names
@@ -1363,10 +1398,10 @@ def self_launch(n: int) -> int:
 
 
 def fresh_processes(args) -> int:
-    """The headline line as the MEDIAN of `args.processes` fresh processes.  Every child is this script with
+    """The headline line as the MEDIAN of `args.processes` fresh processes (`--full` runs 3).  Every child is this script with
     `--processes 1 --cpu-sample 0`: W warm-up + exactly K timed steps, barrier / synchronize on both sides, one JSON line.  This parent never
     touches the GPU; it prints the child line with the median ms_per_step, adds `processes` (every child's step time, list-fill state and
-    calibration) and runs the CPU baseline once."""
+    calibration) and, with `--full`, runs the CPU baseline once."""
     argv = [a for a in sys.argv[1:]]
     for flag in ("--processes", "--cpu-sample"):
         while flag in argv:
@@ -1386,19 +1421,20 @@ def fresh_processes(args) -> int:
     res = lines[pick]
 
     def state(d):
-        k = d["kernels"].get("nl_query_matrix_f32", {})
+        kernels = d.get("kernels", {})  # only a --full child carries the kernel table
+        k = kernels.get("nl_query_matrix_f32", {})
         return {"ms_per_step": d["ms_per_step"], "value": d["value"], "list_fill_40bohr_isolated_median_ms": k.get("isolated_median_ms"),
-                "list_fill_40bohr_in_step_ms": k.get("avg_ms_timed_region"), "d3_cn_in_step_ms": d["kernels"].get("d3_cn", {}).get("avg_ms_timed_region"),
+                "list_fill_40bohr_in_step_ms": k.get("avg_ms_timed_region"), "d3_cn_in_step_ms": kernels.get("d3_cn", {}).get("avg_ms_timed_region"),
                 "calibration_fill_GBps": (d.get("calibration") or {}).get("fill_GBps")}
 
     res["processes"] = {"count": len(lines), "reported": f"process {pick + 1} of {len(lines)} (median ms_per_step)", "seconds_all": time.perf_counter() - t_children,
                         "each": [state(d) for d in lines],
                         "note": "fresh processes run one after the other; the list fill is in one of two states for the life of a process "
                                 "(placement of its row buffers by the driver: DESIGN.md 3.3), so the line is the median process, not a coin flip"}
-    if args.cpu_sample > 0:
+    if args.full and args.cpu_sample > 0:
         res["cpu_baseline"] = cpu_baseline(args.cpu_sample, args.cpu_full_size)
         add_parity(res)
-    if args.workload == "headline" and os.environ.get("BENCH_CONFIGS", "1") != "0":
+    if args.full and args.workload == "headline" and os.environ.get("BENCH_CONFIGS", "1") != "0":
         res["configs"] = compact_configs()
     print(json.dumps(res), flush=True)
     return 0
@@ -1407,7 +1443,7 @@ def fresh_processes(args) -> int:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=250, help="timed steps (default 250: > 1 s of GPU time)")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 250: > 1 s of GPU time; 100 for --workload c2 / c3 / c4)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--atoms", type=int, default=100000)
     ap.add_argument("--cpu-sample", type=int, default=6912, help="atoms in the CPU-baseline sample box (0 = skip the CPU baseline)")
@@ -1423,9 +1459,17 @@ def main():
     ap.add_argument("--overlap", type=int, default=1, choices=[0, 1, 2, 3, 4, 5], help="1 (default): PME and D3 branches on two HIP streams; 0: one stream, per-stage times; 2 - 4: tuning aids; 5: three streams (reciprocal half, real-space half, dispersion)")
     ap.add_argument("--processes", type=int, default=0,
                     help="headline, 1 GPU: run the timed region in this many FRESH processes one after the other and report the one with the median "
-                         "ms_per_step (default 3; 1 = time in this process).  The 40-Bohr list fill has two states that are fixed for the life of a "
+                         "ms_per_step (default 1; 3 with --full).  The 40-Bohr list fill has two states that are fixed for the life of a "
                          "process (0.82 / 1.13 ms: a property of where the driver places the row buffers, DESIGN.md 3.3): one process is a coin flip")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: median of fresh processes, HBM calibration, instrumented + isolated passes (per-kernel "
+                         "table, roofline, stats), CPU oracle baseline + parity, the other configurations (`configs`); off: set-up, warm-up, the timed "
+                         "steps and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if args.steps is None and args.workload not in ("c2", "c3", "c4"):
+        args.steps = 250
     global VIRIAL, OVERLAP, D3_FORMAT
     VIRIAL = not args.no_virial
     D3_FORMAT = args.d3_format
@@ -1433,8 +1477,10 @@ def main():
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
+    if args.dump_outputs and args.workload not in ("headline", "c2", "c3", "c4", "c5"):
+        raise SystemExit("--dump-outputs: the timed-step workloads only (headline, c2 - c5)")
     if args.processes == 0:
-        args.processes = 3 if (args.workload == "headline" and args.gpus == 1 and "WORLD_SIZE" not in os.environ
+        args.processes = 3 if (args.full and args.workload == "headline" and args.gpus == 1 and "WORLD_SIZE" not in os.environ
                                and os.environ.get("BENCH_GRAPH") != "1") else 1
     if args.processes > 1:
         sys.exit(fresh_processes(args))
@@ -1477,7 +1523,7 @@ def main():
     if args.workload in ("c2", "c3", "c4"):
         if world > 1:
             raise SystemExit("c2 / c3 / c4 are BASELINE.json's single-GPU configurations")
-        if args.steps == 250:
+        if args.steps is None:
             args.steps = 100
         run_config(args.workload, device, args)
         return
@@ -1503,7 +1549,8 @@ def main():
         torch.cuda.synchronize()
 
     # this box's own HBM rates, measured before the timed region (not part of it)
-    calibration = hbm_calibration(device, gib=float(os.environ.get("BENCH_CALIB_GIB", "4"))) if os.environ.get("BENCH_CALIB", "1") != "0" else None
+    calibration = (hbm_calibration(device, gib=float(os.environ.get("BENCH_CALIB_GIB", "4")))
+                   if args.full and os.environ.get("BENCH_CALIB", "1") != "0" else None)
     for _ in range(args.warmup):
         out = step()
     barrier()
@@ -1536,22 +1583,23 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
     else:
-        # (1) instrumented pass, NOT the timed region: the same two-stream step with every kernel bracketed by HIP events (the per-kernel
-        # in-step table) and one event per step (`stats`).  An event record is a packet of its own in the stream -- ~5 us of bubble on either
-        # side of a kernel, ~25 brackets per step -- so the timed region below carries ONE bracket, the dominant kernel's (round 6).
-        C.lib().mi_timing_select(None)
-        C.lib().mi_timing_enable(1)
-        for _ in range(max(5, min(args.steps, 50))):
+        if args.full:
+            # (1) instrumented pass (--full), NOT the timed region: the same two-stream step with every kernel bracketed by HIP events (the
+            # per-kernel in-step table) and one event per step (`stats`).  An event record is a packet of its own in the stream -- ~5 us of
+            # bubble on either side of a kernel, ~25 brackets per step -- so the timed region below carries ONE bracket, the dominant kernel's (round 6).
+            C.lib().mi_timing_select(None)
+            C.lib().mi_timing_enable(1)
+            for _ in range(max(5, min(args.steps, 50))):
+                e = torch.cuda.Event(enable_timing=True)
+                e.record()
+                step_events.append(e)
+                out = step(records if len(records) < 32 else None)
             e = torch.cuda.Event(enable_timing=True)
             e.record()
             step_events.append(e)
-            out = step(records if len(records) < 32 else None)
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        step_events.append(e)
-        barrier()
-        C.lib().mi_timing_enable(0)
-        instrumented = kernel_report()
+            barrier()
+            C.lib().mi_timing_enable(0)
+            instrumented = kernel_report()
         # (2) which kernel is the dominant one?  the one with the most work: largest median duration in a short serialised pass
         saved, OVERLAP = OVERLAP, 0
         C.lib().mi_timing_enable(1)
@@ -1563,7 +1611,8 @@ def main():
         probe = kernel_report()
         dominant = max(probe.items(), key=lambda kv: kv[1][2])[0] if probe else None
         # (3) THE timed region: exactly `steps` steps between two barriers, wall clock; the dominant kernel's launches are the only ones
-        # bracketed (its average duration inside this region is `roofline.achieved`'s denominator)
+        # bracketed (its average duration inside this region is `roofline.achieved`'s denominator).  A plain run keeps this protocol, so its
+        # `ms_per_step` is measured as before: the two-stream step without that one bracket ran 0.6 - 1.3 % slower on MI355X
         C.lib().mi_timing_select(dominant.encode() if dominant else None)
         C.lib().mi_timing_enable(1)
         barrier()
@@ -1574,6 +1623,8 @@ def main():
         elapsed = time.perf_counter() - t0
         C.lib().mi_timing_enable(0)
         C.lib().mi_timing_select(None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(out))
     rank_ms = [elapsed / args.steps * 1e3]
     if world > 1:
         mine = torch.tensor([elapsed], dtype=torch.float64, device=device)
@@ -1584,7 +1635,7 @@ def main():
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(tt.item())
     kernels = kernel_report()  # the timed region's records: the dominant kernel only
-    if not graph_mode:
+    if args.full and not graph_mode:
         timed_only = kernels
         kernels = dict(instrumented)
         kernels.update(timed_only)  # the dominant kernel's row carries its launches INSIDE the timed region
@@ -1594,7 +1645,7 @@ def main():
     # move when a profiler changes the overlap); the isolated figures are the ones comparable across runs and with
     # profiles/*kernel_stats*_serial.csv.  They do not enter `value`.
     isolated, serial_ms = {}, []
-    if not graph_mode:
+    if args.full and not graph_mode:
         saved, OVERLAP = OVERLAP, 0
         C.lib().mi_timing_enable(1)
         sev = []
@@ -1627,7 +1678,7 @@ def main():
     if rank == 0:
         total_atoms = args.atoms * world
         value = total_atoms * args.steps / elapsed
-        rows = kernel_table(kernels, isolated, args.atoms, pairs_d3, args.workload)
+        rows = kernel_table(kernels, isolated, args.atoms, pairs_d3, args.workload) if args.full else {}
         n_instr = max(len(step_events) - 1, 1)
         for name, r in rows.items():  # where each row's in-step figures come from, and its launches per step
             in_timed = graph_mode or name in timed_only
@@ -1651,22 +1702,11 @@ def main():
                        "parallelism": par, "ranks": world, "backend": backend,
                        "devices": ([f"{i[2]} #{i[0]} {i[1]}" for i in ident] if world > 1 else [torch.cuda.get_device_name(device)]),
                        "real_space_divide": "hardware rcp/rsq + Newton (EW_IEEE_DIV=0 build of csrc/ewald.hip)"},
-            "stats": ({"step_ms_median": statistics.median(step_ms), "step_ms_min": min(step_ms), "step_ms_max": max(step_ms),
-                       "value_at_median": total_atoms / statistics.median(step_ms) * 1e3, "timed_region_s": elapsed,
-                       "overlap": OVERLAP,
-                       "step_ms_median_serial_untimed": statistics.median(serial_ms) if serial_ms else None,
-                       "note": "per-step GPU time between HIP events on rank 0's main stream in the INSTRUMENTED pass that precedes the timed region (every kernel "
-                               "bracketed: ~0.1 ms of event bubbles per step); `value` is the wall-clock figure over exactly `steps` steps with one bracket per step"}
-                      if step_ms else None),
-            "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
             "ranks": {"ms_per_step": [round(x, 4) for x in rank_ms], "imbalance_max_over_min": max(rank_ms) / max(min(rank_ms), 1e-9),
                       "all_gather_us_median": statistics.median(gather_us) if gather_us else None,
                       "note": "wall-clock per step of every rank over the timed region (`value` uses the slowest); the all_gather figure is rank 0's "
-                              "GPU time between the events around the one collective of a step"},
+                              "GPU time between the events around the one collective of a step (--full only)"},
             "energies": {"e_d3_Ha": float(e_d3[0].item()), "e_pme": float(e_pme.sum().item())},
-            "roofline": roofline_of(rows),
-            "calibration": calibration,
-            "kernels": rows,
         }
         result["config"]["d3_list_buffers"] = (
             {"selection": "nvalchemiops.neighborlist.tuned_neighbor_buffers: fastest of the candidate allocations by a trial search at set-up (untimed)",
@@ -1677,6 +1717,22 @@ def main():
         result["config"]["d3_search_cn"] = (
             "on: the 40-Bohr search also sums the DFT-D3 coordination numbers over its hits (D3SearchContext attached to the list buffers at set-up); "
             "dftd3 adopts them after a device-side fingerprint check of positions / species / cell / k1 and skips its CN pass" if SEARCH_CN else "off")
+        if not args.full:
+            print(json.dumps(result), flush=True)
+    if rank == 0 and args.full:
+        result.update({
+            "stats": ({"step_ms_median": statistics.median(step_ms), "step_ms_min": min(step_ms), "step_ms_max": max(step_ms),
+                       "value_at_median": total_atoms / statistics.median(step_ms) * 1e3, "timed_region_s": elapsed,
+                       "overlap": OVERLAP,
+                       "step_ms_median_serial_untimed": statistics.median(serial_ms) if serial_ms else None,
+                       "note": "per-step GPU time between HIP events on rank 0's main stream in the INSTRUMENTED pass that precedes the timed region (every kernel "
+                               "bracketed: ~0.1 ms of event bubbles per step); `value` is the wall-clock figure over exactly `steps` steps with one bracket per step"}
+                      if step_ms else None),
+            "stage_ms": {k: round(v, 4) for k, v in stage_ms.items()},
+            "roofline": roofline_of(rows),
+            "calibration": calibration,
+            "kernels": rows,
+        })
         # bytes the step's timed kernels really move per step (design bytes where they differ from the 8(d) formula, else the formula's)
         # against the ~6.3 TB/s the guide gives as achievable: the whole step's distance from an HBM floor, not one kernel's
         moved = sum((r.get("design_bytes") or r.get("algorithmic_bytes") or 0.0) * r["launches_per_step"] for r in rows.values())

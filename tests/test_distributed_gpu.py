@@ -164,7 +164,7 @@ def test_bench_launches_its_own_ranks(workload):
     """`python bench.py --gpus 2` with no launcher and no WORLD_SIZE: two ranks (sharing the device over gloo on a 1-GPU box), n_gpus 2."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     extra = ["--atoms", "20000"] if workload == "headline" else ["--workload", "c5", "--systems", "4"]
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--cpu-sample", "0"] + extra,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--full"] + extra,
                        capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

@@ -15,7 +15,7 @@ PY
 }
 for r in $(seq $ROUNDS); do
   for v in 0 1; do
-    NVALCHEMIOPS_D3_CHAIN_RECORDS=$v timeout 400 python bench.py --processes 1 --steps 50 --warmup 10 --cpu-sample 0 > /tmp/ab.json 2>/tmp/ab.err
+    NVALCHEMIOPS_D3_CHAIN_RECORDS=$v timeout 400 python bench.py --full --processes 1 --steps 50 --warmup 10 --cpu-sample 0 > /tmp/ab.json 2>/tmp/ab.err
     echo "headline records $v: $(py /tmp/ab.json)" | tee -a $OUT
     NVALCHEMIOPS_D3_CHAIN_RECORDS=$v timeout 300 python bench.py --workload c3 --steps 200 --warmup 20 --cpu-sample 0 > /tmp/ab.json 2>/tmp/ab.err
     echo "c3 records $v: $(py /tmp/ab.json)" | tee -a $OUT

@@ -21,7 +21,7 @@ for r in $(seq $ROUNDS); do
 done
 for r in 1 2; do
   for t in 0 1; do
-    NVALCHEMIOPS_EWALD_TRUST_FULL_LISTS=$t timeout 400 python bench.py --processes 1 --steps 50 --warmup 10 --cpu-sample 0 > /tmp/ab.json 2>/tmp/ab.err
+    NVALCHEMIOPS_EWALD_TRUST_FULL_LISTS=$t timeout 400 python bench.py --full --processes 1 --steps 50 --warmup 10 --cpu-sample 0 > /tmp/ab.json 2>/tmp/ab.err
     echo "headline trust $t: $(py /tmp/ab.json)" | tee -a $OUT
   done
 done
