@@ -295,6 +295,18 @@ int mi_ewald_real_listed(const void* positions, const void* charges, const void*
                          int dtype, const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors,
                          int mask_value, int flags, double* energies, void* forces, double* charge_grads, void* scratch, size_t scratch_bytes,
                          const int32_t* search_num_neighbors, int verify_stride, int verify_phase, void* stream);
+/* mi_ewald_real_listed plus the virial of the listed entries, in the same owner pass: every stored entry e = (i -> j) contributes
+ * fm_e r_a r_b (fm_e = 1/2 q_i q_j (erfc(a r)/r^3 + 2a/sqrt(pi) exp(-a^2 r^2)/r^2), r = r_j - r_i + S.cell), i.e. -dE/d(strain) of its energy
+ * 1/2 q_i q_j erfc(a r)/r under x -> (I + eps) x with the unit shifts held fixed; per entry, so any list (full, half, asymmetric) is covered.
+ * Each row's wave sums the six components {xx, yy, zz, xy, xz, yz} in fp64 and stores them in row_virial [n_atoms][6] (workspace, no
+ * atomics); a fold pass writes virial_partial [n_systems][mi_ewald_virial_blocks()][6] (every entry, float64), the caller sums the block
+ * dimension.  Energies, forces and charge gradients are those of mi_ewald_real_listed (same arithmetic).  n_systems > 1 needs batch_idx. */
+int mi_ewald_real_virial(const void* positions, const void* charges, const void* cell, const void* alpha, const int32_t* batch_idx, int n_atoms,
+                         int n_systems, int dtype, const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors,
+                         int mask_value, int flags, double* energies, void* forces, double* charge_grads, void* scratch, size_t scratch_bytes,
+                         const int32_t* search_num_neighbors, int verify_stride, int verify_phase, double* row_virial, double* virial_partial,
+                         void* stream);
+int mi_ewald_virial_blocks(void);
 
 /* Explicit-k reciprocal-space Ewald.  Replaces `alchemiops::_[batch_]ewald_reciprocal_space_energy[_forces
  * [_charge_grad]]` (ewald.py:1365-2318; kernels ewald_kernels.py:1496-2480).  Two passes, no [K,N] phase tables:
@@ -304,6 +316,13 @@ int mi_ewald_real_listed(const void* positions, const void* charges, const void*
  *                                E_i = q phi/2 - a q^2/sqrt(pi) - pi q Q/(2a^2), F_i = q kforce_i, dE/dq_i = phi - 2a q/sqrt(pi) - pi Q/a^2
  * k_vectors [n_systems,n_k,3] in `dtype` (half-space set); system_ptr [n_systems+1] atom ranges (NULL: one system);
  * total_charge NULL in the gather = no self/background corrections (used by the adjoint).  Any output pointer may be NULL.  */
+/* Virial of the explicit-k reciprocal sum from mi_ewald_structure_factors' output (S_k = G_k sum_j q_j exp(i k.r_j)): E_k = |S_k|^2 / (2 G_k),
+ * W[a][b] = sum_k E_k (delta_ab - 2 (1/k^2 + 1/(4 alpha^2)) k_a k_b) over the caller's half-space set (k_vectors [n_systems,n_k,3] in `dtype`,
+ * reciprocal vectors of `cell`).  partial [n_systems][mi_ewald_recip_virial_blocks()][6] float64 {xx, yy, zz, xy, xz, yz}, every entry
+ * written; the caller folds the blocks and adds the background term.                                                                          */
+int mi_ewald_recip_virial(const double* structure_factors, const void* k_vectors, const void* cell, const void* alpha, int n_systems, int n_k,
+                          int dtype, double* partial, void* stream);
+int mi_ewald_recip_virial_blocks(void);
 int mi_ewald_structure_factors(const void* positions, const void* weights /*[n_atoms] dtype*/, const void* k_vectors, const void* cell,
                                const void* alpha, const int32_t* system_ptr, int n_atoms, int n_systems, int n_k,
                                int max_atoms_per_system, int dtype, double* structure_factors /*[n_systems,n_k,2]*/,
@@ -552,6 +571,15 @@ int mi_pme_solve_tabled(const void* mesh, const void* recip_cell, const void* al
 int mi_pme_convolve_bwd(const void* spec, const void* weight_spec, int n_channels, const void* recip_cell, const void* alpha, const void* volume,
                         int n_systems, int nx, int ny, int nz, int order, int dtype, void* conv_out, double* partial, void* stream);
 int mi_pme_convolve_bwd_blocks(void);
+/* Virial of the mesh sum from the charge spectrum `spec` [B,nx,ny,nzr] (the unscaled R2C of the spread charges, as the k-space step holds it):
+ *   W[a][b] = sum_m h_m E_m (delta_ab - 2 (1/k^2 + 1/(4 alpha^2)) k_a k_b),  E_m = G(k_m) |spec_m|^2 / sf2_m,  h = 1 on kz = 0 and the
+ * Nyquist plane, else 2 -- -dE/d(strain) at fixed alpha, mesh and order.  k from recip_cell (2 pi cell^-1), or from the caller's k_vectors
+ * [(B,)nx,ny,nzr,3] and k_squared [(B,)nx,ny,nzr] (both or neither; k_batched = 1: with the leading system dimension).  Six sums {xx, yy, zz,
+ * xy, xz, yz} per system and block: partial [n_systems][mi_pme_virial_blocks()][6] float64, every entry written, the caller folds the blocks.
+ * total_charge [n_systems] in `dtype` (NULL: left out): the background term -pi Q^2 / (2 alpha^2 V) joins the diagonal (it scales as 1/V).     */
+int mi_pme_virial(const void* spec, const void* recip_cell, const void* alpha, const void* volume, int n_systems, int nx, int ny, int nz, int order,
+                  int dtype, const void* k_vectors, const void* k_squared, int k_batched, const void* total_charge, double* partial, void* stream);
+int mi_pme_virial_blocks(void);
 
 int mi_pme_gather_finish(const void* positions, const void* charges, const int32_t* batch_idx, const void* cell_inv_t,
                          const void* meshes /*[B,(1|4),nx,ny,nz] real*/, const void* alpha, const void* volume,

@@ -116,14 +116,19 @@ __global__ void ewald_pack_kernel(const T* __restrict__ pos, const T* __restrict
 // The look-ups run in `vblocks` blocks of their own at the FRONT of the grid, 16 lanes per sampled row: done by the sampled row's own wave
 // they cost 0.020 ms at stride 64 (four dependent loads in front of the pair loop keep the wave's whole block resident 2.5 x as long, and
 // this kernel lives off its occupancy); as 1 / 64 of the rows x 1 / 16 of a block each they are not measurable.
-template <class T, bool CSR, bool REC, bool TRUST = false>
+//
+// VIR: also the per-row virial W_i[a][b] = sum_e fm_e r_a r_b (fm_e the force magnitude below, r the pair vector: -dE/d(strain) of the
+// row's entries, any list) -- six fp64 sums per wave, written by lane 0 with plain stores into vrow[i][0..5] = {xx, yy, zz, xy, xz, yz};
+// ew_virial_fold_kernel folds the rows per system.  VIR = false is the instantiation set of before, unchanged.
+template <class T, bool CSR, bool REC, bool TRUST = false, bool VIR = false>
 __global__ __launch_bounds__(256) void ewald_real_kernel(const T* __restrict__ pos, const T* __restrict__ q, const T* __restrict__ cell,
                                                          const T* __restrict__ alpha, const int* __restrict__ batch_idx, int N,
                                                          const int* __restrict__ idx, const int* __restrict__ ush, const int* __restrict__ nptr,
                                                          int M, int mask_value, int flags, double* __restrict__ energies,
                                                          T* __restrict__ forces, double* __restrict__ cgrad,
                                                          unsigned long long* __restrict__ sym, const typename Vec4<T>::type* __restrict__ rec,
-                                                         const int* __restrict__ snum = nullptr, int vblocks = 0, int vshift = 0, int vphase = 0) {
+                                                         const int* __restrict__ snum = nullptr, int vblocks = 0, int vshift = 0, int vphase = 0,
+                                                         double* __restrict__ vrow = nullptr) {
   static_assert(!(TRUST && CSR), "the trusted form describes a padded matrix");
   const int lane = threadIdx.x & (MI_WAVE - 1);
   if (TRUST && (int)blockIdx.x < vblocks) {  // ---- sampled mirror look-ups: sample k is row (k << vshift) + ((-vphase) mod stride)
@@ -171,6 +176,7 @@ __global__ __launch_bounds__(256) void ewald_real_kernel(const T* __restrict__ p
   double eacc = 0.0, cgi = 0.0;
   T fx = 0, fy = 0, fz = 0;
   unsigned long long hf = 0, hr = 0;
+  double vxx = 0.0, vyy = 0.0, vzz = 0.0, vxy = 0.0, vxz = 0.0, vyz = 0.0;
   if (TRUST) {
     const int cnt_i = __builtin_amdgcn_readfirstlane(snum[i]);
     end = beg + (cnt_i < M ? cnt_i : M);
@@ -209,9 +215,23 @@ __global__ __launch_bounds__(256) void ewald_real_kernel(const T* __restrict__ p
       fx -= fmt * sx; fy -= fmt * sy; fz -= fmt * sz;
     }
     if (wc) cgi += qj * (0.5 * pot);
+    if (VIR) {
+      const double rinv2 = rinv * rinv;
+      const double fv = (0.5 * qi * qj) * (pot * rinv2 + two_over_sqrt_pi * al * ex * rinv2);  // the force code's fm, kept in fp64
+      const double dx = (double)sx, dy = (double)sy, dz = (double)sz;
+      vxx += fv * (dx * dx); vyy += fv * (dy * dy); vzz += fv * (dz * dz);
+      vxy += fv * (dx * dy); vxz += fv * (dx * dz); vyz += fv * (dy * dz);
+    }
   }
   eacc = wave_sum(eacc);
   if (lane == 0) energies[i] = eacc;
+  if (VIR) {
+    vxx = wave_sum(vxx); vyy = wave_sum(vyy); vzz = wave_sum(vzz); vxy = wave_sum(vxy); vxz = wave_sum(vxz); vyz = wave_sum(vyz);
+    if (lane == 0) {
+      double* o = vrow + 6 * (size_t)i;
+      o[0] = vxx; o[1] = vyy; o[2] = vzz; o[3] = vxy; o[4] = vxz; o[5] = vyz;
+    }
+  }
   if (wf) {
     fx = wave_sum(fx); fy = wave_sum(fy); fz = wave_sum(fz);
     if (lane == 0) { forces[3 * (size_t)i] = T(2) * fx; forces[3 * (size_t)i + 1] = T(2) * fy; forces[3 * (size_t)i + 2] = T(2) * fz; }
@@ -384,6 +404,28 @@ __global__ __launch_bounds__(EW_BWD_SLOTS) void ew_bwd_reduce_kernel(const doubl
       else if (galpha) galpha[s] += v;
     }
   }
+}
+
+// per-system fold of the per-row virials of ewald_real_kernel<..., VIR = true>: block (x, s) sums the rows r = x*256 + t + k*EW_VIR_BLOCKS*256 of
+// system s in a fixed order and writes partial[s][x][0..5] with plain stores; the caller folds the EW_VIR_BLOCKS rows (deterministic, no atomics).
+// A batch reads batch_idx once per (row, system): n_systems * n_atoms int loads, L2-resident for the batches this is used with.
+#define EW_VIR_BLOCKS 64
+__global__ __launch_bounds__(256) void ew_virial_fold_kernel(const double* __restrict__ vrow, const int* __restrict__ batch_idx, int N,
+                                                             double* __restrict__ partial) {
+  const int s = blockIdx.y;
+  double a[6] = {0, 0, 0, 0, 0, 0};
+  for (long long r = (long long)blockIdx.x * 256 + threadIdx.x; r < N; r += (long long)EW_VIR_BLOCKS * 256) {
+    if (batch_idx && batch_idx[r] != s) continue;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) a[k] += vrow[6 * r + k];
+  }
+  __shared__ double part[256 / MI_WAVE][6];
+  const int lane = threadIdx.x & (MI_WAVE - 1), wave = threadIdx.x / MI_WAVE;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { const double t = wave_sum(a[k]); if (lane == 0) part[wave][k] = t; }
+  __syncthreads();
+  if (threadIdx.x < 6)
+    partial[((size_t)s * EW_VIR_BLOCKS + blockIdx.x) * 6 + threadIdx.x] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
 }
 
 // general adjoint for lists that are not symmetric: entry (i -> j) belongs to E_i only, so it carries weight g_i to BOTH ends
@@ -632,6 +674,42 @@ __global__ __launch_bounds__(256) void ewald_recip_gather_kernel(const T* __rest
 
 // kk_i = sum_k k (w_i . k) (S_re cos + S_im sin)(k.r_i): the position derivative of sum_i w_i . kf_i[S] at fixed S -- one of the terms of
 // the adjoint of the explicit FORCES (nvalchemiops/interactions/electrostatics/ewald.py `_recip_outputs_adjoint`)
+// virial of the explicit-k reciprocal sum from the structure factors of ewald_sf_kernel (S = G sum_j q_j exp(i k.r_j)): the k-th term of
+// the energy is E_k = |S_k|^2 / (2 G_k) and, under x -> (I + eps) x with the k set following the cell (k -> (I + eps)^-T k),
+//   W[a][b] = sum_k E_k (delta_ab - 2 (1/k^2 + 1/(4 alpha^2)) k_a k_b)       (six sums {xx, yy, zz, xy, xz, yz}; background on the host)
+// Block (x, b) strides k = x*256 + t over system b and writes partial[b][x][0..5] (no atomics; the caller folds the blocks).
+#define EK_VIR_BLOCKS 32
+template <class T>
+__global__ __launch_bounds__(256) void ewald_recip_virial_kernel(const double* __restrict__ sf, const T* __restrict__ kvec, const T* __restrict__ cell,
+                                                                 const T* __restrict__ alpha, int K, double* __restrict__ partial) {
+  const int b = blockIdx.y;
+  const T* cm = cell + 9 * (size_t)b;
+  const double vol = fabs((double)(cm[0] * (cm[4] * cm[8] - cm[5] * cm[7]) - cm[1] * (cm[3] * cm[8] - cm[5] * cm[6]) +
+                                   cm[2] * (cm[3] * cm[7] - cm[4] * cm[6])));
+  const double al = alpha[b], c4 = 0.25 / (al * al);
+  double a[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = blockIdx.x * 256 + threadIdx.x; k < K; k += EK_VIR_BLOCKS * 256) {
+    const T* kv = kvec + 3 * ((size_t)b * K + k);
+    const double kx = kv[0], ky = kv[1], kz = kv[2];
+    const double k2 = kx * kx + ky * ky + kz * kz;
+    if (k2 < 1e-10) continue;  // no term in the forward either (ewald_sf_kernel)
+    const double green = exp(-k2 * c4) / k2 * (8.0 * M_PI) / vol;
+    if (!(green > 0.0)) continue;
+    const double sre = sf[2 * ((size_t)b * K + k)], sim = sf[2 * ((size_t)b * K + k) + 1];
+    const double e = 0.5 * (sre * sre + sim * sim) / green;
+    const double c = -2.0 * e * (1.0 / k2 + c4);
+    a[0] += e + c * kx * kx; a[1] += e + c * ky * ky; a[2] += e + c * kz * kz;
+    a[3] += c * kx * ky; a[4] += c * kx * kz; a[5] += c * ky * kz;
+  }
+  __shared__ double part[256 / MI_WAVE][6];
+  const int lane = threadIdx.x & (MI_WAVE - 1), wave = threadIdx.x / MI_WAVE;
+#pragma unroll
+  for (int q = 0; q < 6; ++q) { const double t = wave_sum(a[q]); if (lane == 0) part[wave][q] = t; }
+  __syncthreads();
+  if (threadIdx.x < 6)
+    partial[((size_t)b * EK_VIR_BLOCKS + blockIdx.x) * 6 + threadIdx.x] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+}
+
 template <class T>
 __global__ __launch_bounds__(256) void ewald_recip_gather_kk_kernel(const T* __restrict__ pos, const T* __restrict__ kvec, const int* __restrict__ batch_idx,
                                                                     const double* __restrict__ sf, const double* __restrict__ wvec, int n_atoms, int K,
@@ -945,11 +1023,12 @@ extern "C" int mi_ewald_real(const void* positions, const void* charges, const v
   return mi_ewald_real_listed(positions, charges, cell, alpha, batch_idx, n_atoms, dtype, idx_j, unit_shifts, neighbor_ptr, max_neighbors, mask_value, flags,
                               energies, forces, charge_grads, scratch, scratch_bytes, nullptr, 0, 0, stream);
 }
-extern "C" int mi_ewald_real_listed(const void* positions, const void* charges, const void* cell, const void* alpha, const int32_t* batch_idx,
-                                    int n_atoms, int dtype, const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr,
-                                    int max_neighbors, int mask_value, int flags, double* energies, void* forces, double* charge_grads,
-                                    void* scratch, size_t scratch_bytes, const int32_t* search_num_neighbors, int verify_stride, int verify_phase,
-                                    void* stream) {
+// mi_ewald_real_listed, and with `vrow` != NULL (n_atoms x 6 doubles) the VIR instantiations of the owner pass (mi_ewald_real_virial)
+static int ewald_real_impl(const void* positions, const void* charges, const void* cell, const void* alpha, const int32_t* batch_idx,
+                           int n_atoms, int dtype, const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr,
+                           int max_neighbors, int mask_value, int flags, double* energies, void* forces, double* charge_grads,
+                           void* scratch, size_t scratch_bytes, const int32_t* search_num_neighbors, int verify_stride, int verify_phase,
+                           double* vrow, void* stream) {
   MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
   if (n_atoms <= 0) return MI_OK;
   MI_REQUIRE(positions && charges && cell && alpha && idx_j && unit_shifts && energies, "null pointer");
@@ -958,25 +1037,27 @@ extern "C" int mi_ewald_real_listed(const void* positions, const void* charges, 
   hipStream_t st = (hipStream_t)stream;
   const int blocks = mi_blocks(n_atoms, 4);
   const bool csr = neighbor_ptr != nullptr;
-#define MI_EW(T_, CSR_)                                                                                                                        \
+#define MI_EW_V(T_, CSR_, VIR_)                                                                                                                \
   do {                                                                                                                                         \
     if (rec) {                                                                                                                                 \
       ewald_pack_kernel<T_><<<mi_blocks(n_atoms, 256), 256, 0, st>>>((const T_*)positions, (const T_*)charges, n_atoms, (Vec4<T_>::type*)rec, sym);  \
       if (!CSR_ && trusted)                                                                                                                    \
-        ewald_real_kernel<T_, false, true, true><<<blocks + vblocks, 256, 0, st>>>((const T_*)positions, (const T_*)charges, (const T_*)cell, (const T_*)alpha, \
+        ewald_real_kernel<T_, false, true, true, VIR_><<<blocks + vblocks, 256, 0, st>>>((const T_*)positions, (const T_*)charges, (const T_*)cell, (const T_*)alpha, \
                                                                 batch_idx, n_atoms, idx_j, unit_shifts, neighbor_ptr, max_neighbors, mask_value,  \
                                                                 flags, energies, (T_*)forces, charge_grads, sym, (const Vec4<T_>::type*)rec,   \
-                                                                search_num_neighbors, vblocks, vshift, verify_phase);                           \
+                                                                search_num_neighbors, vblocks, vshift, verify_phase, vrow);                     \
       else                                                                                                                                     \
-      ewald_real_kernel<T_, CSR_, true><<<blocks, 256, 0, st>>>((const T_*)positions, (const T_*)charges, (const T_*)cell, (const T_*)alpha,   \
+      ewald_real_kernel<T_, CSR_, true, false, VIR_><<<blocks, 256, 0, st>>>((const T_*)positions, (const T_*)charges, (const T_*)cell, (const T_*)alpha, \
                                                                 batch_idx, n_atoms, idx_j, unit_shifts, neighbor_ptr, max_neighbors, mask_value,  \
-                                                                flags, energies, (T_*)forces, charge_grads, sym, (const Vec4<T_>::type*)rec);  \
+                                                                flags, energies, (T_*)forces, charge_grads, sym, (const Vec4<T_>::type*)rec,   \
+                                                                nullptr, 0, 0, 0, vrow);                                                        \
     } else {                                                                                                                                   \
-      ewald_real_kernel<T_, CSR_, false><<<blocks, 256, 0, st>>>((const T_*)positions, (const T_*)charges, (const T_*)cell, (const T_*)alpha,  \
+      ewald_real_kernel<T_, CSR_, false, false, VIR_><<<blocks, 256, 0, st>>>((const T_*)positions, (const T_*)charges, (const T_*)cell, (const T_*)alpha, \
                                                                  batch_idx, n_atoms, idx_j, unit_shifts, neighbor_ptr, max_neighbors, mask_value, \
-                                                                 flags, energies, (T_*)forces, charge_grads, sym, nullptr);                    \
+                                                                 flags, energies, (T_*)forces, charge_grads, sym, nullptr, nullptr, 0, 0, 0, vrow); \
     }                                                                                                                                          \
   } while (0)
+#define MI_EW(T_, CSR_) do { if (vrow) MI_EW_V(T_, CSR_, true); else MI_EW_V(T_, CSR_, false); } while (0)
 #define MI_EWS(T_, CSR_)                                                                                                                         \
   do {                                                                                                                                           \
     ewald_fixup_zero_kernel<T_><<<mi_blocks(n_atoms, 256), 256, 0, st>>>(sym, (T_*)forces, nullptr, charge_grads, n_atoms);                      \
@@ -1012,7 +1093,35 @@ extern "C" int mi_ewald_real_listed(const void* positions, const void* charges, 
     MI_LAUNCH_CHECK();
   }
 #undef MI_EW
+#undef MI_EW_V
 #undef MI_EWS
+  return MI_OK;
+}
+extern "C" int mi_ewald_real_listed(const void* positions, const void* charges, const void* cell, const void* alpha, const int32_t* batch_idx,
+                                    int n_atoms, int dtype, const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr,
+                                    int max_neighbors, int mask_value, int flags, double* energies, void* forces, double* charge_grads,
+                                    void* scratch, size_t scratch_bytes, const int32_t* search_num_neighbors, int verify_stride, int verify_phase,
+                                    void* stream) {
+  return ewald_real_impl(positions, charges, cell, alpha, batch_idx, n_atoms, dtype, idx_j, unit_shifts, neighbor_ptr, max_neighbors, mask_value, flags,
+                         energies, forces, charge_grads, scratch, scratch_bytes, search_num_neighbors, verify_stride, verify_phase, nullptr, stream);
+}
+
+extern "C" int mi_ewald_virial_blocks(void) { return EW_VIR_BLOCKS; }
+extern "C" int mi_ewald_real_virial(const void* positions, const void* charges, const void* cell, const void* alpha, const int32_t* batch_idx,
+                                    int n_atoms, int n_systems, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
+                                    const int32_t* neighbor_ptr, int max_neighbors, int mask_value, int flags, double* energies, void* forces,
+                                    double* charge_grads, void* scratch, size_t scratch_bytes, const int32_t* search_num_neighbors,
+                                    int verify_stride, int verify_phase, double* row_virial, double* virial_partial, void* stream) {
+  MI_REQUIRE(n_systems >= 1 && (n_systems == 1 || batch_idx), "batch_idx is required for more than one system");
+  if (n_atoms <= 0) return MI_OK;
+  MI_REQUIRE(row_virial && virial_partial, "null pointer");
+  const int rc = ewald_real_impl(positions, charges, cell, alpha, batch_idx, n_atoms, dtype, idx_j, unit_shifts, neighbor_ptr, max_neighbors, mask_value,
+                                 flags, energies, forces, charge_grads, scratch, scratch_bytes, search_num_neighbors, verify_stride, verify_phase,
+                                 row_virial, stream);
+  if (rc != MI_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  ew_virial_fold_kernel<<<dim3(EW_VIR_BLOCKS, n_systems), 256, 0, st>>>(row_virial, n_systems > 1 ? batch_idx : nullptr, n_atoms, virial_partial);
+  MI_LAUNCH_CHECK();
   return MI_OK;
 }
 
@@ -1150,6 +1259,26 @@ extern "C" int mi_ewald_recip_gather_kk(const void* positions, const void* k_vec
   else
     ewald_recip_gather_kk_kernel<double><<<blocks, 256, 0, st>>>((const double*)positions, (const double*)k_vectors, batch_idx, structure_factors,
                                                                  weights, n_atoms, n_k, out);
+  MI_LAUNCH_CHECK();
+  return MI_OK;
+}
+
+extern "C" int mi_ewald_recip_virial_blocks(void) { return EK_VIR_BLOCKS; }
+extern "C" int mi_ewald_recip_virial(const double* structure_factors, const void* k_vectors, const void* cell, const void* alpha, int n_systems, int n_k,
+                                     int dtype, double* partial, void* stream) {
+  MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
+  MI_REQUIRE(n_systems >= 1 && partial && cell && alpha && (n_k == 0 || (structure_factors && k_vectors)), "null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (n_k <= 0) {
+    MI_HIP_CHECK(hipMemsetAsync(partial, 0, sizeof(double) * 6 * EK_VIR_BLOCKS * (size_t)n_systems, st));
+    return MI_OK;
+  }
+  if (dtype == MI_F32)
+    ewald_recip_virial_kernel<float><<<dim3(EK_VIR_BLOCKS, n_systems), 256, 0, st>>>(structure_factors, (const float*)k_vectors, (const float*)cell,
+                                                                                     (const float*)alpha, n_k, partial);
+  else
+    ewald_recip_virial_kernel<double><<<dim3(EK_VIR_BLOCKS, n_systems), 256, 0, st>>>(structure_factors, (const double*)k_vectors, (const double*)cell,
+                                                                                      (const double*)alpha, n_k, partial);
   MI_LAUNCH_CHECK();
   return MI_OK;
 }

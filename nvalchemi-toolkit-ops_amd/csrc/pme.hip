@@ -955,6 +955,61 @@ __global__ __launch_bounds__(256) void pme_convolve_bwd_kernel(const Cplx<T>* __
     partial[((size_t)b * gridDim.x + blockIdx.x) * PME_BWD_SUMS + threadIdx.x] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
 }
 
+// ---- virial of the mesh sum (forward only) ---------------------------------------------------------------------------------------------
+// The mesh energy is E = sum_m h_m G(k_m) |rho_hat_m|^2 / sf2_m over the half spectrum (h as above).  Under x -> (I + eps) x the spread and
+// the gather see fractional coordinates only, so rho_hat and sf2 do not move; k_m = 2 pi cell^-1 m follows the cell and V grows by det(I+eps):
+//   W[a][b] = -dE/deps[a][b] = sum_m E_m (delta_ab - 2 (1/k^2 + 1/(4 alpha^2)) k_a k_b)
+// Six sums {xx, yy, zz, xy, xz, yz}, laid out like mi_pme_convolve_bwd's: partial[b][block][6], every entry written, the caller folds.
+// k from `recip` (as pme_convolve_kernel evaluates it) or from the caller's arrays (kvec_in / k2_in, shared or per system).
+#define PME_VIR_BLOCKS 256
+template <class T>
+__global__ __launch_bounds__(256) void pme_virial_kernel(const Cplx<T>* __restrict__ spec, const T* __restrict__ recip, const T* __restrict__ alpha,
+                                                         const T* __restrict__ volume, int nx, int ny, int nz, int order,
+                                                         const T* __restrict__ kvec_in, const T* __restrict__ k2_in, int k_batched,
+                                                         const T* __restrict__ qtot, double* __restrict__ partial) {
+  const int b = blockIdx.y;
+  const int nzr = nz / 2 + 1;
+  const size_t per = (size_t)nx * ny * nzr;
+  const T* R = recip + 9 * (size_t)b;
+  const T al = alpha[b], vol = volume[b];
+  const double c4 = 1.0 / (4.0 * (double)al * (double)al);
+  double acc[6] = {0, 0, 0, 0, 0, 0};
+  for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x; r < per; r += (size_t)gridDim.x * blockDim.x) {
+    const int k = (int)(r % nzr), j = (int)((r / nzr) % ny), i = (int)(r / ((size_t)nzr * ny));
+    const int mx = miller_of(i, nx), my = miller_of(j, ny), mz = k;
+    const T m[3] = {(T)mx, (T)my, (T)mz};
+    T kv[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) kv[c] = m[0] * R[3 * c] + m[1] * R[3 * c + 1] + m[2] * R[3 * c + 2];
+    T k2 = kv[0] * kv[0] + kv[1] * kv[1] + kv[2] * kv[2];
+    if (!(k2 > T(1e-12))) k2 = T(1e-12);
+    const size_t kidx = (k_batched ? (size_t)b * per : 0) + r;
+    if (k2_in) k2 = k2_in[kidx];
+    if (kvec_in) { kv[0] = kvec_in[3 * kidx]; kv[1] = kvec_in[3 * kidx + 1]; kv[2] = kvec_in[3 * kidx + 2]; }
+    const T G = green_of(k2, al, vol, i == 0 && j == 0 && k == 0);
+    if (G == T(0)) continue;  // origin and masked modes: no energy, no virial
+    const T sf2 = sf_sq_of<T>(mx, my, mz, nx, ny, nz, order);
+    const Cplx<T> v = spec[(size_t)b * per + r];
+    const double h = (k == 0 || (2 * k == nz)) ? 1.0 : 2.0;
+    const double e = h * ((double)v.re * (double)v.re + (double)v.im * (double)v.im) * ((double)G / (double)sf2);
+    const double c = -2.0 * e * (1.0 / (double)k2 + c4);
+    const double kx = kv[0], ky = kv[1], kz = kv[2];
+    acc[0] += e + c * kx * kx; acc[1] += e + c * ky * ky; acc[2] += e + c * kz * kz;
+    acc[3] += c * kx * ky; acc[4] += c * kx * kz; acc[5] += c * ky * kz;
+  }
+  __shared__ double part[4][6];
+  const int lane = threadIdx.x & (MI_WAVE - 1), wave = threadIdx.x / MI_WAVE;
+#pragma unroll
+  for (int q = 0; q < 6; ++q) { const double t = wave_sum(acc[q]); if (lane == 0) part[wave][q] = t; }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    double v = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+    // background term -pi Q^2 / (2 alpha^2 V): it scales as 1/V, so it adds E_bg to the diagonal (block 0 of each system)
+    if (qtot && blockIdx.x == 0 && threadIdx.x < 3) { const double Q = (double)qtot[b]; v -= M_PI * Q * Q / (2.0 * (double)al * (double)al * (double)vol); }
+    partial[((size_t)b * gridDim.x + blockIdx.x) * 6 + threadIdx.x] = v;
+  }
+}
+
 template <class T>
 __global__ void pme_corrections_kernel(const T* __restrict__ raw, const T* __restrict__ q, const int* __restrict__ batch_idx,
                                        const T* __restrict__ vol, const T* __restrict__ alpha, const T* __restrict__ qtot, int N,
@@ -1456,6 +1511,24 @@ int mi_pme_convolve_bwd(const void* spec, const void* weight_spec, int n_channel
   return MI_OK;
 }
 int mi_pme_convolve_bwd_blocks(void) { return PME_BWD_BLOCKS; }
+
+int mi_pme_virial(const void* spec, const void* recip_cell, const void* alpha, const void* volume, int n_systems, int nx, int ny, int nz, int order,
+                  int dtype, const void* k_vectors, const void* k_squared, int k_batched, const void* total_charge,
+                  double* partial /*[n_systems][mi_pme_virial_blocks()][6]*/, void* stream) {
+  MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
+  MI_REQUIRE(spec && recip_cell && alpha && volume && partial && n_systems >= 1 && nx > 0 && ny > 0 && nz > 0, "null pointer");
+  MI_REQUIRE((k_vectors == nullptr) == (k_squared == nullptr), "k_vectors and k_squared are given together or not at all");
+  order = decode_order(order).sf_exponent;
+  hipStream_t st = (hipStream_t)stream;
+  mi_timing_begin("pme_virial", stream);
+  MI_DISPATCH_T(dtype, (pme_virial_kernel<T_><<<dim3(PME_VIR_BLOCKS, n_systems), 256, 0, st>>>(
+                           (const Cplx<T_>*)spec, (const T_*)recip_cell, (const T_*)alpha, (const T_*)volume, nx, ny, nz, order,
+                           (const T_*)k_vectors, (const T_*)k_squared, k_batched, (const T_*)total_charge, partial)));
+  mi_timing_end(stream);
+  MI_LAUNCH_CHECK();
+  return MI_OK;
+}
+int mi_pme_virial_blocks(void) { return PME_VIR_BLOCKS; }
 
 /* ---- fused mesh solve ------------------------------------------------------------------------------------------------------------------ */
 int mi_pme_solve_supported(int n_systems, int nx, int ny, int nz, int dtype) {

@@ -69,6 +69,17 @@ def lib() -> ctypes.CDLL:
             L.mi_d3_workspace_bytes_packed.argtypes = [ctypes.c_int] * 4
             L.mi_d3_workspace_bytes_entries.restype = ctypes.c_size_t
             L.mi_d3_workspace_bytes_entries.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong]
+        # the virial entry points (forward-only -dE/d(strain) of the Ewald / PME sums)
+        vp, i, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+        L.mi_ewald_real_virial.restype = i
+        L.mi_ewald_real_virial.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, i, i, i, vp, vp, vp, vp, sz, vp, i, i, vp, vp, vp]
+        L.mi_ewald_recip_virial.restype = i
+        L.mi_ewald_recip_virial.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp]
+        L.mi_pme_virial.restype = i
+        L.mi_pme_virial.argtypes = [vp, vp, vp, vp, i, i, i, i, i, i, vp, vp, i, vp, vp, vp]
+        for name in ("mi_ewald_virial_blocks", "mi_ewald_recip_virial_blocks", "mi_pme_virial_blocks"):
+            getattr(L, name).restype = i
+            getattr(L, name).argtypes = []
         _LIB = L
     return _LIB
 
@@ -83,6 +94,12 @@ def ewald_scratch_bytes(n_atoms: int, dtype: int) -> int:
     L = lib()
     L.mi_ewald_real_scratch_bytes.restype = ctypes.c_size_t
     return int(L.mi_ewald_real_scratch_bytes(int(n_atoms), int(dtype)))
+
+
+def fold_virial(partial: torch.Tensor) -> torch.Tensor:
+    """[B, blocks, 6] float64 block partials {xx, yy, zz, xy, xz, yz} of a virial entry point -> symmetric [B, 3, 3] float64 (fixed-order sum)."""
+    xx, yy, zz, xy, xz, yz = partial.sum(1).unbind(-1)
+    return torch.stack((xx, xy, xz, xy, yy, yz, xz, yz, zz), dim=-1).reshape(-1, 3, 3)
 
 
 def check(rc: int, what: str) -> None:

@@ -1271,7 +1271,60 @@ def _pme_fused_autograd(ctx, g_e, g_f, g_cg, *g_kept):
 pme_fused_op.register_autograd(_pme_fused_autograd, setup_context=_pme_fused_setup)
 
 
+# =====================================================================================================================================
+# virials of the Ewald / PME sums (forward only)
+# =====================================================================================================================================
+# The `*_with_virial` functions return their sibling's outputs unchanged; when those go through autograd or a torch.compile trace, the virial
+# comes from these ops: the same virial kernels on detached inputs.  The virial has no adjoint in this build: a loss that depends on it raises
+# at backward (never a silent zero).
+def _virial_no_adjoint(op):
+    def backward(ctx, *grads):
+        raise NotImplementedError(f"{op}: the virial is not differentiable in this build (training on stress is not supported); "
+                                  "differentiate the energies, forces or charge gradients instead")
+    return backward
+
+
+def _ewald_real_virial(positions: Tensor, charges: Tensor, cells: Tensor, alpha: Tensor, batch_idx: Optional[Tensor], neighbor_list: Optional[Tensor],
+                       neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor], neighbor_matrix: Optional[Tensor],
+                       neighbor_matrix_shifts: Optional[Tensor], mask_value: int, num_systems: int) -> Tensor:
+    from nvalchemiops.interactions.electrostatics.ewald import _real_virial
+
+    return _real_virial(positions.detach(), charges.detach(), cells.detach(), alpha.detach(), neighbor_list, neighbor_ptr, neighbor_shifts,
+                        neighbor_matrix, neighbor_matrix_shifts, int(mask_value), batch_idx, int(num_systems))
+
+
+def _ewald_recip_virial(positions: Tensor, charges: Tensor, cells: Tensor, k_vectors: Tensor, alpha: Tensor, batch_idx: Optional[Tensor]) -> Tensor:
+    from nvalchemiops.interactions.electrostatics.ewald import _recip_virial_only
+
+    return _recip_virial_only(positions.detach(), charges.detach(), cells.detach(), k_vectors.detach(), alpha.detach(), batch_idx)
+
+
+def _pme_recip_virial(positions: Tensor, charges: Tensor, cells: Tensor, alpha: Tensor, batch_idx: Optional[Tensor], nx: int, ny: int, nz: int,
+                      spline_order: int, k_vectors: Optional[Tensor], k_squared: Optional[Tensor]) -> Tensor:
+    from nvalchemiops.interactions.electrostatics.pme import _pme_virial_only
+
+    return _pme_virial_only(positions.detach(), charges.detach(), cells.detach(), alpha.detach(), batch_idx, (int(nx), int(ny), int(nz)), int(spline_order),
+                            None if k_vectors is None else k_vectors.detach(), None if k_squared is None else k_squared.detach())
+
+
+def _noop_virial_setup(ctx, inputs, output):
+    pass
+
+
+ewald_real_virial_op = torch.library.custom_op("nvalchemiops::ewald_real_space_virial", _ewald_real_virial, mutates_args=())
+ewald_real_virial_op.register_fake(lambda positions, *rest: positions.new_empty((int(rest[-1]), 3, 3)))
+ewald_real_virial_op.register_autograd(_virial_no_adjoint("nvalchemiops::ewald_real_space_virial"), setup_context=_noop_virial_setup)
+ewald_recip_virial_op = torch.library.custom_op("nvalchemiops::ewald_reciprocal_space_virial", _ewald_recip_virial, mutates_args=())
+ewald_recip_virial_op.register_fake(lambda positions, charges, cells, *rest: positions.new_empty((cells.reshape(-1, 3, 3).shape[0], 3, 3)))
+ewald_recip_virial_op.register_autograd(_virial_no_adjoint("nvalchemiops::ewald_reciprocal_space_virial"), setup_context=_noop_virial_setup)
+pme_recip_virial_op = torch.library.custom_op("nvalchemiops::pme_reciprocal_space_virial", _pme_recip_virial, mutates_args=())
+pme_recip_virial_op.register_fake(lambda positions, charges, cells, alpha, batch_idx, *rest:
+                                  positions.new_empty((cells.reshape(-1, 3, 3).shape[0] if batch_idx is not None else 1, 3, 3)))
+pme_recip_virial_op.register_autograd(_virial_no_adjoint("nvalchemiops::pme_reciprocal_space_virial"), setup_context=_noop_virial_setup)
+
+
 __all__ = ["spline_spread_op", "batch_spline_spread_op", "spline_gather_op", "batch_spline_gather_op", "spline_gather_vec3_op",
            "batch_spline_gather_vec3_op", "spline_gather_gradient_op", "batch_spline_gather_gradient_op", "pme_green_structure_factor_op",
            "batch_pme_green_structure_factor_op", "pme_energy_corrections_op", "batch_pme_energy_corrections_op",
-           "pme_energy_corrections_with_charge_grad_op", "batch_pme_energy_corrections_with_charge_grad_op", "REAL_OPS", "real_space_op", "RECIPROCAL_OPS", "reciprocal_space_op", "COULOMB_OPS", "coulomb_op"]
+           "pme_energy_corrections_with_charge_grad_op", "batch_pme_energy_corrections_with_charge_grad_op", "REAL_OPS", "real_space_op", "RECIPROCAL_OPS", "reciprocal_space_op", "COULOMB_OPS", "coulomb_op",
+           "ewald_real_virial_op", "ewald_recip_virial_op", "pme_recip_virial_op"]

@@ -62,8 +62,10 @@ def _real_space_inputs(positions, charges, cell, alpha, neighbor_list, neighbor_
                 nptr=nptr, m=m, n_entries=n_entries)
 
 
-def _real_space_launch(p, mask_value: int, compute_forces: bool, compute_charge_gradients: bool):
-    """One launch of the real-space family: (float64 energies, forces in the input dtype | None, float64 charge gradients | None)."""
+def _real_space_launch(p, mask_value: int, compute_forces: bool, compute_charge_gradients: bool, virial_systems: int = 0):
+    """One launch of the real-space family: (float64 energies, forces in the input dtype | None, float64 charge gradients | None).
+    virial_systems > 0: the same owner pass also sums the virial of the listed entries (`mi_ewald_real_virial`) and a fourth item, the
+    float64 [virial_systems, 3, 3] virial, is returned."""
     pos = p["pos"]
     n, dev, dt = pos.shape[0], pos.device, pos.dtype
     energies = torch.empty(n, dtype=torch.float64, device=dev)
@@ -74,6 +76,21 @@ def _real_space_launch(p, mask_value: int, compute_forces: bool, compute_charge_
     nbytes = C.ewald_scratch_bytes(n, C.dtype_code(dt))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     counts = p.get("counts")
+    if virial_systems:
+        trusted = counts is not None and not (0 <= int(mask_value) < n)
+        stride, phase = 0, 0
+        if trusted:
+            from nvalchemiops.neighborlist import _engine as E
+
+            stride, phase = E.verify_args()
+        vrow = torch.empty((n, 6), dtype=torch.float64, device=dev)
+        vpart = torch.empty((int(virial_systems), int(C.lib().mi_ewald_virial_blocks()), 6), dtype=torch.float64, device=dev)
+        rc = C.lib().mi_ewald_real_virial(C.ptr(pos), C.ptr(p["q"]), C.ptr(p["cells"]), C.ptr(p["alpha"]), C.ptr(p["bi"]), n, int(virial_systems),
+                                          C.dtype_code(dt), C.ptr(p["idx"]), C.ptr(p["sh"]), C.ptr(p["nptr"]), int(p["m"]), int(mask_value), flags,
+                                          C.ptr(energies), C.ptr(forces), C.ptr(cgrads), C.ptr(scratch), ctypes.c_size_t(nbytes),
+                                          C.ptr(counts if trusted else None), int(stride), int(phase), C.ptr(vrow), C.ptr(vpart), C.stream_of(pos))
+        C.check(rc, "mi_ewald_real_virial")
+        return energies, forces, cgrads, C.fold_virial(vpart)
     # (a mask_value that is an atom's index would turn stored entries into padding: the list as the reference reads it is then not the search's list)
     if counts is not None and not (0 <= int(mask_value) < n):
         from nvalchemiops.neighborlist import _engine as E
@@ -157,6 +174,75 @@ def ewald_real_space(positions: torch.Tensor, charges: torch.Tensor, cell: torch
     if compute_charge_gradients:
         out += (cgrads.to(dt),)
     return out if len(out) > 1 else out[0]
+
+
+def _with_virial(out, virial):
+    """A sibling's result (one tensor or a tuple) with the virial appended."""
+    return (out if isinstance(out, tuple) else (out,)) + (virial,)
+
+
+def _real_virial(positions, charges, cell, alpha, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts,
+                 mask_value, batch_idx, num_systems: int) -> torch.Tensor:
+    """The real-space virial alone, [num_systems, 3, 3] in the positions dtype (no autograd graph): the `nvalchemiops::ewald_real_space_virial`
+    op behind `ewald_real_space_with_virial` when its energies go through the sibling's autograd / torch.compile path."""
+    n, dev, dt = positions.shape[0], positions.device, positions.dtype
+    p = _real_space_inputs(positions, charges, cell, alpha, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts,
+                           batch_idx)
+    if n == 0 or p["n_entries"] == 0:
+        return torch.zeros((num_systems, 3, 3), dtype=dt, device=dev)
+    return _real_space_launch(p, mask_value, False, False, virial_systems=num_systems)[3].to(dt)
+
+
+@C.traceable
+def ewald_real_space_with_virial(positions: torch.Tensor, charges: torch.Tensor, cell: torch.Tensor, alpha: torch.Tensor,
+                                 neighbor_list: torch.Tensor | None = None, neighbor_ptr: torch.Tensor | None = None,
+                                 neighbor_shifts: torch.Tensor | None = None, neighbor_matrix: torch.Tensor | None = None,
+                                 neighbor_matrix_shifts: torch.Tensor | None = None, mask_value: int = -1, batch_idx: torch.Tensor | None = None,
+                                 compute_forces: bool = False, compute_charge_gradients: bool = False):
+    """`ewald_real_space` plus the virial W_s[a][b] = -dE_s/d eps[a][b] of the listed entries under x -> (I + eps) x (positions and cell rows,
+    unit shifts fixed): sum over stored entries (i -> j) of fm_ij r_a r_b, fm_ij = 1/2 q_i q_j (erfc(a r)/r^3 + 2a/sqrt(pi) exp(-a^2 r^2)/r^2).
+    Per entry, so any list (full, half, asymmetric, CSR or padded) gives the virial of exactly the energies returned.  The virial is summed in
+    the same owner pass as the energies (fp64, no atomics) and returned as [num_systems, 3, 3] in the positions dtype, num_systems = 1 without
+    batch_idx.  Returns the sibling's result with the virial appended: ``(energies, virial)`` | ``(energies, forces, virial)`` | ...
+    Under autograd / torch.compile the energies, forces and charge gradients are the sibling's (same gradients); the virial has no adjoint
+    (a loss on it raises NotImplementedError at backward)."""
+    if neighbor_list is None and neighbor_matrix is None:
+        raise ValueError("Either neighbor_list or neighbor_matrix must be provided")
+    if neighbor_list is not None and neighbor_ptr is None:
+        raise ValueError("neighbor_ptr is required when using neighbor_list format")
+    n, dev, dt = positions.shape[0], positions.device, positions.dtype
+    nsys = cell.reshape(-1, 3, 3).shape[0] if batch_idx is not None else 1
+    alpha_t = alpha if isinstance(alpha, torch.Tensor) else torch.full((1,), float(alpha), dtype=dt, device=dev)
+    if n == 0 or C.tracing() or (torch.is_grad_enabled() and any(t.requires_grad for t in (positions, charges, cell, alpha_t))):
+        out = ewald_real_space(positions, charges, cell, alpha, neighbor_list=neighbor_list, neighbor_ptr=neighbor_ptr, neighbor_shifts=neighbor_shifts,
+                               neighbor_matrix=neighbor_matrix, neighbor_matrix_shifts=neighbor_matrix_shifts, mask_value=mask_value,
+                               batch_idx=batch_idx, compute_forces=compute_forces, compute_charge_gradients=compute_charge_gradients)
+        if n == 0:
+            return _with_virial(out, torch.zeros((nsys, 3, 3), dtype=dt, device=dev))
+        from nvalchemiops import _eops
+
+        cells = cell.reshape(-1, 3, 3)
+        al = alpha_t.to(dt).reshape(-1)
+        if al.shape[0] == 1 and cells.shape[0] > 1:
+            al = al.expand(cells.shape[0])
+        vir = _eops.ewald_real_virial_op(positions, charges.to(dt), cells.to(dt), al, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
+                                         neighbor_matrix, neighbor_matrix_shifts, int(mask_value), nsys)
+        return _with_virial(out, vir)
+    p = _real_space_inputs(positions, charges, cell, alpha_t, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts,
+                           batch_idx)
+    if p["n_entries"] == 0:
+        energies = torch.zeros(n, dtype=torch.float64, device=dev)
+        forces = torch.zeros((n, 3), dtype=dt, device=dev) if compute_forces else None
+        cgrads = torch.zeros(n, dtype=torch.float64, device=dev) if compute_charge_gradients else None
+        virial = torch.zeros((nsys, 3, 3), dtype=torch.float64, device=dev)
+    else:
+        energies, forces, cgrads, virial = _real_space_launch(p, mask_value, compute_forces, compute_charge_gradients, virial_systems=nsys)
+    out = (energies.to(dt),)
+    if compute_forces:
+        out += (forces,)
+    if compute_charge_gradients:
+        out += (cgrads.to(dt),)
+    return out + (virial.to(dt),)
 
 
 def _prepare_alpha(alpha, num_systems: int, dtype: torch.dtype, device: torch.device) -> torch.Tensor:
@@ -426,6 +512,67 @@ def ewald_reciprocal_space(positions: torch.Tensor, charges: torch.Tensor, cell:
     return out if len(out) > 1 else out[0]
 
 
+def _recip_virial(p, sf, tq) -> torch.Tensor:
+    """float64 [B, 3, 3] virial of the explicit-k reciprocal sum from its structure factors (`mi_ewald_recip_virial`), plus the background
+    term: its energy sum_i -pi q_i (Q/V) / (2 alpha^2) = -pi Q (Q/V) / (2 alpha^2) scales as 1/V, so it adds E_bg * I (the self term is
+    strain-free).  `tq` = Q/V as the forward used it (0 for fewer than two k-vectors)."""
+    n_sys, n_k, dev = p["n_sys"], p["n_k"], p["pos"].device
+    nblk = int(C.lib().mi_ewald_recip_virial_blocks())
+    part = torch.empty((n_sys, nblk, 6), dtype=torch.float64, device=dev)
+    C.check(C.lib().mi_ewald_recip_virial(C.ptr(sf), C.ptr(p["kv"]), C.ptr(p["cells"]), C.ptr(p["al"]), n_sys, n_k, C.dtype_code(p["pos"].dtype),
+                                          C.ptr(part), C.stream_of(p["pos"])), "mi_ewald_recip_virial")
+    w = C.fold_virial(part)
+    qsum = _seg(p["q"].to(torch.float64), p["bi"], n_sys)
+    al64 = p["al"].to(torch.float64)
+    e_bg = -math.pi * qsum * tq / (2.0 * al64 * al64)
+    return w + e_bg.reshape(-1, 1, 1) * torch.eye(3, dtype=torch.float64, device=dev)
+
+
+def _recip_virial_only(positions, charges, cell, k_vectors, alpha, batch_idx) -> torch.Tensor:
+    """The explicit-k reciprocal virial alone, [B, 3, 3] in the positions dtype (the `nvalchemiops::ewald_reciprocal_space_virial` op)."""
+    cells, n_sys = _prepare_cell(cell)
+    k3 = k_vectors if k_vectors.dim() == 3 else k_vectors.unsqueeze(0)
+    if positions.shape[0] == 0 or k3.shape[1] == 0:
+        return torch.zeros((n_sys, 3, 3), dtype=positions.dtype, device=positions.device)
+    p = _recip_inputs(positions, charges, cells, k_vectors, alpha, batch_idx)
+    sf, tq = _structure_factors(p["pos"], p["q"], p["kv"], p["cells"], p["al"], p["sptr"], p["n_sys"], p["n_k"], p["max_atoms"])
+    return _recip_virial(p, sf, tq).to(positions.dtype)
+
+
+@C.traceable
+def ewald_reciprocal_space_with_virial(positions: torch.Tensor, charges: torch.Tensor, cell: torch.Tensor, k_vectors: torch.Tensor,
+                                       alpha: torch.Tensor, batch_idx: torch.Tensor | None = None, compute_forces: bool = False,
+                                       compute_charge_gradients: bool = False):
+    """`ewald_reciprocal_space` plus the virial W_s = -dE_s/d eps (positions and cell rows strained, the caller's k-vectors taken as reciprocal
+    vectors of `cell` that follow it): W[a][b] = sum_k E_k (delta_ab - 2 (1/k^2 + 1/(4 alpha^2)) k_a k_b) + E_bg delta_ab, E_k the k-th share of
+    the energy.  One reduction pass over the structure factors the forward already forms.  Returns the sibling's result with the
+    [num_systems, 3, 3] virial (positions dtype) appended; under autograd / torch.compile the other outputs are the sibling's and the virial
+    has no adjoint (NotImplementedError at backward)."""
+    dt, dev = positions.dtype, positions.device
+    if positions.shape[0] > 0:
+        C.require_device(positions, charges, cell, k_vectors, batch_idx)
+    cells, n_sys = _prepare_cell(cell)
+    al_in = _prepare_alpha(alpha, n_sys, dt, dev)
+    if C.tracing() or (torch.is_grad_enabled() and any(t.requires_grad for t in (positions, charges, k_vectors, cells, al_in))):
+        out = ewald_reciprocal_space(positions, charges, cell, k_vectors, alpha, batch_idx=batch_idx, compute_forces=compute_forces,
+                                     compute_charge_gradients=compute_charge_gradients)
+        from nvalchemiops import _eops
+
+        vir = _eops.ewald_recip_virial_op(positions, charges.to(dt), cells.to(dt), k_vectors.to(dt), al_in, batch_idx)
+        return _with_virial(out, vir)
+    n = positions.shape[0]
+    k3 = k_vectors if k_vectors.dim() == 3 else k_vectors.unsqueeze(0)
+    if n == 0 or k3.shape[1] == 0:
+        out = _recip_forward(positions, charges, cells, k_vectors, al_in, batch_idx, compute_forces, compute_charge_gradients)
+        return out + (torch.zeros((n_sys, 3, 3), dtype=dt, device=dev),)
+    p = _recip_inputs(positions, charges, cells, k_vectors, al_in, batch_idx)
+    sf, tq = _structure_factors(p["pos"], p["q"], p["kv"], p["cells"], p["al"], p["sptr"], p["n_sys"], p["n_k"], p["max_atoms"])
+    res = _recip_gather(p["pos"], p["q"], p["kv"], p["al"], p["bi"], sf, tq, p["n_k"], energies=True, forces=compute_forces,
+                        cgrads=compute_charge_gradients)
+    out = (res["energies"].to(dt),) + ((res["forces"],) if compute_forces else ()) + ((res["cgrads"].to(dt),) if compute_charge_gradients else ())
+    return out + (_recip_virial(p, sf, tq).to(dt),)
+
+
 @C.eager
 def ewald_summation(positions: torch.Tensor, charges: torch.Tensor, cell: torch.Tensor, alpha=None, k_vectors: torch.Tensor | None = None,
                     k_cutoff: float | None = None, batch_idx: torch.Tensor | None = None, neighbor_list: torch.Tensor | None = None,
@@ -457,4 +604,37 @@ def ewald_summation(positions: torch.Tensor, charges: torch.Tensor, cell: torch.
     return rs + rec
 
 
-__all__ = ["ewald_real_space", "ewald_reciprocal_space", "ewald_summation"]
+@C.eager
+def ewald_summation_with_virial(positions: torch.Tensor, charges: torch.Tensor, cell: torch.Tensor, alpha=None, k_vectors: torch.Tensor | None = None,
+                                k_cutoff: float | None = None, batch_idx: torch.Tensor | None = None, neighbor_list: torch.Tensor | None = None,
+                                neighbor_ptr: torch.Tensor | None = None, neighbor_shifts: torch.Tensor | None = None,
+                                neighbor_matrix: torch.Tensor | None = None, neighbor_matrix_shifts: torch.Tensor | None = None,
+                                mask_value: int | None = None, compute_forces: bool = False, accuracy: float = 1e-6):
+    """`ewald_summation` plus the total electrostatic virial [num_systems, 3, 3] (real-space + reciprocal + background; see
+    `ewald_real_space_with_virial` / `ewald_reciprocal_space_with_virial`): (energies, virial) | (energies, forces, virial)."""
+    from nvalchemiops.interactions.electrostatics.k_vectors import generate_k_vectors_ewald_summation
+    from nvalchemiops.interactions.electrostatics.parameters import estimate_ewald_parameters
+
+    cells, n_sys = _prepare_cell(cell)
+    if alpha is None or (k_cutoff is None and k_vectors is None):
+        params = estimate_ewald_parameters(positions, cells, batch_idx, accuracy)
+        if alpha is None:
+            alpha = params.alpha
+        if k_cutoff is None:
+            k_cutoff = params.reciprocal_space_cutoff
+    alpha_t = _prepare_alpha(alpha, n_sys, positions.dtype, positions.device)
+    if k_vectors is None:
+        k_vectors = generate_k_vectors_ewald_summation(cells, k_cutoff)
+    if mask_value is None:
+        mask_value = positions.shape[0]
+    rs = ewald_real_space_with_virial(positions, charges, cells, alpha_t, neighbor_list=neighbor_list, neighbor_ptr=neighbor_ptr,
+                                      neighbor_shifts=neighbor_shifts, neighbor_matrix=neighbor_matrix, neighbor_matrix_shifts=neighbor_matrix_shifts,
+                                      mask_value=mask_value, batch_idx=batch_idx, compute_forces=compute_forces)
+    rec = ewald_reciprocal_space_with_virial(positions, charges, cells, k_vectors, alpha_t, batch_idx=batch_idx, compute_forces=compute_forces)
+    if compute_forces:
+        return rs[0] + rec[0], rs[1] + rec[1], rs[-1] + rec[-1]
+    return rs[0] + rec[0], rs[-1] + rec[-1]
+
+
+__all__ = ["ewald_real_space", "ewald_reciprocal_space", "ewald_summation", "ewald_real_space_with_virial", "ewald_reciprocal_space_with_virial",
+           "ewald_summation_with_virial"]

@@ -22,7 +22,7 @@ import os
 import torch
 
 from nvalchemiops import _capi as C
-from nvalchemiops.interactions.electrostatics.ewald import _real_space_inputs, _real_space_launch, ewald_real_space
+from nvalchemiops.interactions.electrostatics.ewald import _real_space_inputs, _real_space_launch, _with_virial, ewald_real_space
 from nvalchemiops.interactions.electrostatics.parameters import (estimate_pme_mesh_dimensions, estimate_pme_parameters,
                                                                  mesh_spacing_to_dimensions)
 from nvalchemiops.spline import _launch_spread, spline_gather, spline_gather_vec3, spline_spread
@@ -923,5 +923,168 @@ def particle_mesh_ewald(positions: torch.Tensor, charges: torch.Tensor, cell: to
     return real + recip
 
 
+# ---- virial (forward only) -------------------------------------------------------------------------------------------------------------
+def _pme_virial(spec, recip, al, vol, qtot, nsys, dims, spline_order, k_vectors=None, k_squared=None) -> torch.Tensor:
+    """float64 [nsys, 3, 3] virial of the reciprocal sum from the charge spectrum the k-space step left (`mi_pme_virial`: one pass over the
+    half spectrum, block partials folded here), the background term -pi Q^2 / (2 alpha^2 V) * I included by the same kernel (it scales as
+    1/V; the self term is strain-free).  k from 2 pi cell^-1, or the caller's k_vectors / k_squared when both are given (as the forward read
+    them)."""
+    nx, ny, nz = dims
+    dt, dev = recip.dtype, recip.device
+    kv = k2 = None
+    k_batched = 0
+    if k_vectors is not None and k_squared is not None:
+        half = (nx, ny, nz // 2 + 1)
+        k2 = k_squared.detach().to(dt).contiguous()
+        kv = k_vectors.detach().to(dt).contiguous()
+        if tuple(k2.shape[-3:]) != half or k2.dim() not in (3, 4) or (k2.dim() == 4 and k2.shape[0] not in (1, nsys)):
+            raise ValueError(f"k_squared must have shape {half} or (B, {nx}, {ny}, {nz // 2 + 1}) with B in (1, {nsys}) -- the rfft half grid of "
+                             f"generate_k_vectors_pme -- got {tuple(k_squared.shape)}")
+        if tuple(kv.shape[-4:]) != half + (3,) or kv.dim() not in (4, 5) or (kv.dim() == 5 and kv.shape[0] not in (1, nsys)):
+            raise ValueError(f"k_vectors must have shape {half + (3,)} or (B,) + that with B in (1, {nsys}), got {tuple(k_vectors.shape)}")
+        k_batched = int(k2.dim() == 4 and k2.shape[0] == nsys and nsys > 1)
+        if k_batched != int(kv.dim() == 5 and kv.shape[0] == nsys and nsys > 1):
+            raise ValueError("k_vectors and k_squared must both be shared by all systems or both carry the batch dimension")
+    part = torch.empty((nsys, int(C.lib().mi_pme_virial_blocks()), 6), dtype=torch.float64, device=dev)
+    C.check(C.lib().mi_pme_virial(C.ptr(spec), C.ptr(recip), C.ptr(al), C.ptr(vol), nsys, nx, ny, nz, C.spline_order_arg(spline_order), C.dtype_code(dt),
+                                  C.ptr(kv), C.ptr(k2), k_batched, C.ptr(qtot.contiguous()), C.ptr(part), C.stream_of(recip)), "mi_pme_virial")
+    return C.fold_virial(part)
+
+
+def _pme_virial_only(positions, charges, cells, alpha, batch_idx, dims, spline_order, k_vectors=None, k_squared=None) -> torch.Tensor:
+    """The reciprocal virial alone, [nsys, 3, 3] in the positions dtype (the `nvalchemiops::pme_reciprocal_space_virial` op): spread and
+    k-space step with the charge spectrum kept, no gather."""
+    dt, dev = positions.dtype, positions.device
+    batched = batch_idx is not None
+    cells = cells if cells.dim() == 3 else cells.unsqueeze(0)
+    nsys = cells.shape[0] if batched else 1
+    if positions.shape[0] == 0:
+        return torch.zeros((nsys, 3, 3), dtype=dt, device=dev)
+    C.require_device(positions, charges, cells, batch_idx)
+    code = C.dtype_code(dt)
+    bi = None if batch_idx is None else C.i32(batch_idx)
+    al = alpha.to(dt).reshape(-1)
+    if al.shape[0] == 1 and cells.shape[0] > 1:
+        al = al.expand(cells.shape[0])
+    have_k = k_vectors is not None and k_squared is not None
+    spec, _, _, recip, vol, qtot, al, _ = _reciprocal_front(positions.contiguous(), charges.to(dt).contiguous(), cells.to(dt).contiguous(), al.contiguous(),
+                                                            tuple(int(v) for v in dims), int(spline_order), bi, nsys, batched, False,
+                                                            k_vectors if have_k else None, k_squared if have_k else None, code, need_spec=True)
+    return _pme_virial(spec, recip, al, vol, qtot, nsys, dims, spline_order, k_vectors if have_k else None, k_squared if have_k else None).to(dt)
+
+
+@C.traceable
+def pme_reciprocal_space_with_virial(positions: torch.Tensor, charges: torch.Tensor, cell: torch.Tensor, alpha: float | torch.Tensor,
+                                     mesh_dimensions: tuple[int, int, int] | None = None, mesh_spacing: float | None = None, spline_order: int = 4,
+                                     batch_idx: torch.Tensor | None = None, k_vectors: torch.Tensor | None = None,
+                                     k_squared: torch.Tensor | None = None, compute_forces: bool = False, compute_charge_gradients: bool = False):
+    """`pme_reciprocal_space` plus the virial W_s = -dE_s/d eps (positions and cell rows strained; alpha, mesh and spline order fixed):
+    W[a][b] = sum_m E_m (delta_ab - 2 (1/k^2 + 1/(4 alpha^2)) k_a k_b) over the half spectrum (E_m the mode's share of the mesh energy, B-spline
+    moduli included) + E_bg delta_ab.  One reduction pass over the charge spectrum the k-space step already holds (fused mesh solve, hipFFT or
+    dense DFT), k from the cell or from the caller's k_vectors / k_squared.  Returns the sibling's result with the [num_systems, 3, 3] virial
+    (positions dtype) appended; under autograd / torch.compile the other outputs are the sibling's and the virial has no adjoint."""
+    spline_order = C.resolve_spline_order(spline_order)
+    cells, num_systems = _prepare_cell(cell)
+    n, dev, dt = positions.shape[0], positions.device, positions.dtype
+    nsys = num_systems if batch_idx is not None else 1
+    composed = C.tracing() or (torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (positions, charges, cell, alpha)))
+    if mesh_dimensions is None:
+        if mesh_spacing is None:
+            raise ValueError("Either mesh_dimensions or mesh_spacing must be provided")
+        lengths = torch.norm(cells[0], dim=1)
+        mesh_dimensions = tuple(int(torch.ceil(length / mesh_spacing).item()) for length in lengths)
+    mesh_dimensions = tuple(int(v) for v in mesh_dimensions)
+    if n == 0 or composed:
+        out = pme_reciprocal_space(positions, charges, cell, alpha, mesh_dimensions=mesh_dimensions, spline_order=spline_order, batch_idx=batch_idx,
+                                   k_vectors=k_vectors, k_squared=k_squared, compute_forces=compute_forces,
+                                   compute_charge_gradients=compute_charge_gradients)
+        if n == 0:
+            return _with_virial(out, torch.zeros((nsys, 3, 3), dtype=dt, device=dev))
+        from nvalchemiops import _eops
+
+        have_k = k_vectors is not None and k_squared is not None
+        vir = _eops.pme_recip_virial_op(positions, charges.to(dt), cells.to(dt), _traceable_alpha(alpha, num_systems, dt, dev), batch_idx, *mesh_dimensions,
+                                        int(spline_order), k_vectors if have_k else None, k_squared if have_k else None)
+        return _with_virial(out, vir)
+    C.require_device(positions, charges, cell, batch_idx)
+    C.dtype_code(dt)
+    alpha_t = _prepare_alpha(alpha, num_systems, torch.float64, dev)
+    bi = None if batch_idx is None else C.i32(batch_idx)
+    pos = positions.detach().contiguous()
+    q = charges.detach().to(dt).contiguous()
+    cells_t = cells.detach().to(dt).contiguous()
+    have_k = k_vectors is not None and k_squared is not None
+    keep = {}
+    energies, forces, cgrads = _reciprocal_fused(pos, q, cells_t, alpha_t, mesh_dimensions, spline_order, bi, compute_forces, compute_charge_gradients,
+                                                 k_vectors=k_vectors if have_k else None, k_squared=k_squared if have_k else None, keep=keep)
+    virial = _pme_virial(keep["spec"], keep["recip"], keep["alpha"], keep["vol"], keep["qtot"], nsys, mesh_dimensions, spline_order,
+                         k_vectors if have_k else None, k_squared if have_k else None)
+    out = (energies,) + ((forces,) if compute_forces else ()) + ((cgrads,) if compute_charge_gradients else ())
+    return out + (virial.to(dt),)
+
+
+@C.traceable
+def particle_mesh_ewald_with_virial(positions: torch.Tensor, charges: torch.Tensor, cell: torch.Tensor, alpha: float | torch.Tensor | None = None,
+                                    mesh_spacing: float | None = None, mesh_dimensions: tuple[int, int, int] | None = None, spline_order: int = 4,
+                                    batch_idx: torch.Tensor | None = None, k_vectors: torch.Tensor | None = None, k_squared: torch.Tensor | None = None,
+                                    neighbor_list: torch.Tensor | None = None, neighbor_ptr: torch.Tensor | None = None,
+                                    neighbor_shifts: torch.Tensor | None = None, neighbor_matrix: torch.Tensor | None = None,
+                                    neighbor_matrix_shifts: torch.Tensor | None = None, mask_value: int | None = None, compute_forces: bool = False,
+                                    compute_charge_gradients: bool = False, accuracy: float = 1e-6):
+    """`particle_mesh_ewald` plus the total electrostatic virial [num_systems, 3, 3] (positions dtype, fp64 sums): the real-space virial from
+    the same owner pass as the real-space energies and the reciprocal virial from the charge spectrum of the same k-space step
+    (`ewald_real_space_with_virial`, `pme_reciprocal_space_with_virial`).  W_s = -dE_s/d eps with alpha, mesh and order fixed; it adds to
+    `dftd3(..., compute_virial=True)`'s virial (same convention).  Returns the sibling's result with the virial appended."""
+    spline_order = C.resolve_spline_order(spline_order)
+    num_atoms = positions.shape[0]
+    cells, num_systems = _prepare_cell(cell)
+    nsys = num_systems if batch_idx is not None else 1
+    if alpha is None:
+        est = estimate_pme_parameters(positions, cells, batch_idx, accuracy)
+        alpha = est.alpha
+        if mesh_dimensions is None and mesh_spacing is None:
+            mesh_dimensions = tuple(est.mesh_dimensions)
+    wants_grad = C.tracing() or (torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (positions, charges, cell, alpha)))
+    plain_alpha = isinstance(alpha, (int, float)) and not C.tracing()
+    alpha_in = alpha
+    alpha = (_traceable_alpha if (wants_grad and not plain_alpha) else _prepare_alpha)(alpha, num_systems, positions.dtype, positions.device)
+    if mask_value is None:
+        mask_value = num_atoms
+    if mesh_dimensions is None:
+        if mesh_spacing is not None:
+            mesh_dimensions = mesh_spacing_to_dimensions(cells, mesh_spacing)
+        else:
+            mesh_dimensions = estimate_pme_mesh_dimensions(cells, alpha, accuracy)
+    mesh_dimensions = tuple(int(v) for v in mesh_dimensions)
+    if not wants_grad and num_atoms > 0 and (k_vectors is None or k_squared is None):
+        # the sibling's inference step (real-space owner pass -> reciprocal pipeline adding it in the gather epilogue) with the virial flag on
+        # the owner pass and the charge spectrum of the k-space step kept for one more reduction
+        p = _real_space_inputs(positions, charges, cells, alpha, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                               neighbor_matrix_shifts, batch_idx)
+        if p["n_entries"] > 0:
+            add_e, add_f, add_cg, w_real = _real_space_launch(p, mask_value, compute_forces, compute_charge_gradients, virial_systems=nsys)
+            keep = {}
+            energies, forces, cgrads = _reciprocal_fused(p["pos"], p["q"], p["cells"], p["alpha"], mesh_dimensions, spline_order, p["bi"],
+                                                         compute_forces, compute_charge_gradients, add=(add_e, add_f, add_cg), keep=keep)
+            w_recip = _pme_virial(keep["spec"], keep["recip"], keep["alpha"], keep["vol"], keep["qtot"], nsys, mesh_dimensions, spline_order)
+            out = (energies,) + ((forces,) if compute_forces else ()) + ((cgrads,) if compute_charge_gradients else ())
+            return out + ((w_real + w_recip).to(positions.dtype),)
+    out = particle_mesh_ewald(positions, charges, cell, alpha=alpha_in, mesh_spacing=mesh_spacing, mesh_dimensions=mesh_dimensions,
+                              spline_order=spline_order, batch_idx=batch_idx, k_vectors=k_vectors, k_squared=k_squared, neighbor_list=neighbor_list,
+                              neighbor_ptr=neighbor_ptr, neighbor_shifts=neighbor_shifts, neighbor_matrix=neighbor_matrix,
+                              neighbor_matrix_shifts=neighbor_matrix_shifts, mask_value=mask_value, compute_forces=compute_forces,
+                              compute_charge_gradients=compute_charge_gradients, accuracy=accuracy)
+    # the sibling's outputs (autograd node, composition or trace) as they are; the virial beside them from the two forward-only virial ops
+    from nvalchemiops import _eops
+
+    dt = positions.dtype
+    have_k = k_vectors is not None and k_squared is not None
+    w_real = _eops.ewald_real_virial_op(positions, charges.to(dt), cells.to(dt), alpha.to(dt), batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
+                                        neighbor_matrix, neighbor_matrix_shifts, int(mask_value), nsys)
+    w_recip = _eops.pme_recip_virial_op(positions, charges.to(dt), cells.to(dt), alpha.to(dt), batch_idx, *mesh_dimensions, int(spline_order),
+                                        k_vectors if have_k else None, k_squared if have_k else None)
+    return _with_virial(out, w_real + w_recip)
+
+
 __all__ = ["particle_mesh_ewald", "pme_reciprocal_space", "pme_green_structure_factor", "pme_energy_corrections",
-           "pme_energy_corrections_with_charge_grad"]
+           "pme_energy_corrections_with_charge_grad", "particle_mesh_ewald_with_virial", "pme_reciprocal_space_with_virial"]
