@@ -465,6 +465,41 @@ int mi_spline_spread_grad(const void* positions, const void* vec /*[n_atoms,3]*/
                           int n_atoms, int n_systems, int nx, int ny, int nz, int order, int dtype, void* mesh /*[B,nx,ny,nz]*/,
                           void* stream);
 
+/* ---- multi-channel spread / gather: values[n_atoms, C] (row major) <-> mesh[n_systems, C, nx, ny, nz] (planar channels) -------------
+ * Replace alchemiops::_[batch_]spline_spread_channels / _gather_channels (spline.py:2202-2580; kernels :1053-1330): the multipole path,
+ * C = 9 for L_max = 2.  The channels share stencil, tile and 1-D weights; only the per-atom value differs, so the tile path runs the key
+ * kernel and the counting sort ONCE and accumulates a block of channels per box kernel (as many LDS boxes as fit 48 KiB, at most 9),
+ * box + reduce once per block; the atomic path evaluates the weights once and loops over the channels.  Weight thresholds are those of
+ * mi_spline_spread (w > 0, batched: w > 1e-8), any C >= 1.  Unlike mi_spline_spread the call WRITES the whole mesh on either path (the
+ * atomic path zero-fills it first): the caller's mesh may be uninitialised.  Tiles run when `workspace` holds
+ * mi_spline_spread_channels_workspace_bytes_for(...) bytes and the mesh tiles (mi_spline_spread_is_tiled); NULL selects the atomic path. */
+size_t mi_spline_spread_channels_workspace_bytes_for(int n_atoms, int n_systems, int nx, int ny, int nz, int order, int n_channels, int dtype);
+int mi_spline_spread_channels(const void* positions, const void* values /*[n_atoms,C]*/, const int32_t* batch_idx, const void* cell_inv_t,
+                              int n_atoms, int n_systems, int n_channels, int nx, int ny, int nz, int order, int batched, int dtype,
+                              void* mesh /*[n_systems,C,nx,ny,nz]*/, void* workspace, size_t workspace_bytes, void* stream);
+/* out[i][c] = sum_g mesh[c][g] w_i(g), weights <= 1e-8 skipped: per channel the very operations of mi_spline_gather, in its order, so
+ * a channel equals the scalar gather of its plane bit for bit.                                                                        */
+int mi_spline_gather_channels(const void* positions, const void* mesh /*[n_systems,C,nx,ny,nz]*/, const int32_t* batch_idx,
+                              const void* cell_inv_t, int n_atoms, int n_systems, int n_channels, int nx, int ny, int nz, int order, int dtype,
+                              void* out /*[n_atoms,C]*/, void* stream);
+/* out[i][a] = sum_c coef[i][c] sum_g mesh[c][g] d w_i(g) / d frac_a: mi_spline_gather_grad over the channels, weighted per atom and
+ * channel -- the position / cell branch of both adjoints (spread: mesh = grad_mesh, coef = values; gather: mesh = mesh, coef = grad_out). */
+int mi_spline_gather_channels_frac_grad(const void* positions, const void* mesh /*[n_systems,C,nx,ny,nz]*/, const void* coef /*[n_atoms,C]*/,
+                                        const int32_t* batch_idx, const void* cell_inv_t, int n_atoms, int n_systems, int n_channels, int nx,
+                                        int ny, int nz, int order, int dtype, void* out /*[n_atoms,3]*/, void* stream);
+
+/* ---- multipole basis functions (csrc/multipole.hip), float64, L_max in {0, 1, 2} -> 1 / 4 / 9 components -------------------------
+ * Host-callable counterparts of the reference's math/spherical_harmonics.py and math/gto.py wrappers (eval_*_pytorch).  Real
+ * orthonormal harmonics of r / |r| in the order [Y00, Y1-1 (y), Y10 (z), Y1+1 (x), Y2-2 (xy), Y2-1 (yz), Y20, Y2+1 (xz), Y2+2 (x^2-y^2)],
+ * 1 / r = rsqrt(r^2 + 1e-30).  out is row-major [n, components]; the gradient [n, components, 3] is d Y_lm(r / |r|) / d r.
+ *   mi_gto_density   sqrt(4 pi) / (2 pi sigma^2)^(3/2) Y_lm(r^) exp(-r^2 / (2 sigma^2))
+ *   mi_gto_fourier   exp(-k^2 sigma^2 / 2) x {1 (L = 0, real), (1/2) sqrt(4 pi) Y_1m(k^) (L = 1, imaginary), -(1/4) sqrt(4 pi) Y_2m(k^)
+ *                    (L = 2, real)}; the other part is written as zero.                                                             */
+int mi_sph_harm(const double* positions /*[n,3]*/, int n, int l_max, double* out, void* stream);
+int mi_sph_harm_grad(const double* positions /*[n,3]*/, int n, int l_max, double* out, void* stream);
+int mi_gto_density(const double* positions /*[n,3]*/, int n, double sigma, int l_max, double* out, void* stream);
+int mi_gto_fourier(const double* k_vectors /*[n,3]*/, int n, double sigma, int l_max, double* out_real, double* out_imag, void* stream);
+
 /* ---- FFT plans (csrc/fft.cpp: hipFFT on rocFFT) ------------------------------------------------------------------------
  * 3-D real <-> complex transforms over a batch of contiguous meshes: real [batch][nx][ny][nz], complex [batch][nx][ny][nz/2+1]
  * interleaved.  Replace torch.fft.rfftn(norm="backward") / irfftn(norm="forward") of `_pme_reciprocal_space_impl` (pme.py:1398,

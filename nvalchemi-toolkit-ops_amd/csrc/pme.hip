@@ -191,7 +191,7 @@ struct SpLayout { size_t keys_in, vals_out, bin_start, lo3, theta, bins, boxes, 
 // give the size every run fits in (mi_spline_spread_workspace_bytes); an actual (order, dtype) gives the exact size
 // (mi_spline_spread_workspace_bytes_for): (e + order - 1)^3 values of the mesh dtype per tile instead of (e + 5)^3 doubles -- a 256^3 fp32
 // order-4 mesh needs 178 MB of boxes instead of 576.  All other offsets do not depend on either.
-static SpLayout sp_layout(int N, int B, int nx, int ny, int nz, int order = MI_MAX_ORDER, size_t elem_bytes = sizeof(double)) {
+static SpLayout sp_layout(int N, int B, int nx, int ny, int nz, int order = MI_MAX_ORDER, size_t elem_bytes = sizeof(double), int box_channels = 1) {
   SpLayout L;
   size_t o = 0;
   auto take = [&](size_t b) { size_t at = o; o += mi_align(b); return at; };
@@ -205,7 +205,8 @@ static SpLayout sp_layout(int N, int B, int nx, int ny, int nz, int order = MI_M
   L.bins = take(sizeof(int) * bs_scratch_ints(L.nbins + 1));  // counting-sort counters (binsort.h)
   // per-tile accumulation boxes of the two-phase spread: (e + order - 1)^3 points per tile
   if (order < 1 || order > MI_MAX_ORDER) order = MI_MAX_ORDER;
-  L.boxes = take(elem_bytes * (size_t)L.nbins * (e.ex + order - 1) * (e.ey + order - 1) * (e.ez + order - 1));
+  // (box_channels: the channels of one block of the multi-channel spread, spread_box_channels_kernel)
+  L.boxes = take(elem_bytes * (size_t)box_channels * (size_t)L.nbins * (e.ex + order - 1) * (e.ey + order - 1) * (e.ez + order - 1));
   L.total = o;
   return L;
 }
@@ -346,6 +347,150 @@ __global__ __launch_bounds__(256) void spread_box_reduce_kernel(const T* __restr
         const int sz = dz ? (tz == 0 ? nbz - 1 : tz - 1) : tz, pz = lz + dz * e.ez;
         const size_t tile = (((size_t)s * nbx + sx) * nby + sy) * nbz + sz;
         acc += boxes[tile * box_n + ((size_t)px * byn + py) * bzn + pz];
+      }
+    }
+  }
+  mesh[g] = acc;
+}
+
+// ---- multi-channel spread (values[N, C] -> mesh[B, C, nx, ny, nz]) ------------------------------------------------------------------
+// The channels of a multipole spread share the stencil, the tile and the 3 x order 1-D weights of every atom; only the per-atom value
+// differs.  Atomic path: the scalar kernel's thread mapping, weights once, a loop over the channels around the atomic add.
+template <class T>
+__global__ __launch_bounds__(256) void spline_spread_channels_kernel(const T* __restrict__ pos, const T* __restrict__ values,
+                                                                     const int* __restrict__ batch_idx, const T* __restrict__ cit, int N, int C,
+                                                                     int nx, int ny, int nz, int order, int batched, T* __restrict__ mesh) {
+  const int tpa = order * order;
+  const int apb = blockDim.x / tpa;  // atoms per block
+  const int la = threadIdx.x / tpa, col = threadIdx.x - la * tpa;
+  const int i = blockIdx.x * apb + la;
+  if (la >= apb || i >= N) return;
+  const int s = batch_idx ? batch_idx[i] : 0;
+  const Stencil<T> st = make_stencil(pos + 3 * (size_t)i, cit + 9 * (size_t)s, nx, ny, nz, order);
+  const int tx = col / order, ty = col - tx * order;
+  const T wx = weight_1d(st, 0, tx, order), wy = weight_1d(st, 1, ty, order);
+  const int gx = wrap_idx(st.base[0] + tx + st.off0[0], nx), gy = wrap_idx(st.base[1] + ty + st.off0[1], ny);
+  const size_t plane = (size_t)nx * ny * nz;
+  T* row = mesh + (size_t)s * C * plane + ((size_t)gx * ny + gy) * nz;
+  const T* vals = values + (size_t)i * C;
+  const T thr = batched ? T(1e-8) : T(0);  // the scalar kernel's thresholds (spline.py:548 / :820), not :1107's
+  for (int tz = 0; tz < order; ++tz) {
+    const T wz = weight_1d(st, 2, tz, order);
+    const T w = wx * wy * wz;
+    if (w > thr) {
+      T* p = row + wrap_idx(st.base[2] + tz + st.off0[2], nz);
+      for (int c = 0; c < C; ++c) atomicAdd(p + (size_t)c * plane, vals[c] * w);
+    }
+  }
+}
+
+// Tile path: key kernel and counting sort run once per call; the box kernel below accumulates a BLOCK of channels into LDS boxes from one
+// staging of the chunk's weights, and the reduce writes that block's mesh planes.  The channel block is what keeps three thread blocks on
+// a CU: the boxes of one block of channels take at most SPC_LDS_BYTES of the CU's 160 KiB (fp64, order 6: 2 x 17.6 KB; fp32, order 4: 9 x
+// 5.3 KB).  The host runs box + reduce once per channel block, so the box scratch is sized for one block, not for C channels.
+#define SPC_LDS_BYTES 49152
+#define SPC_MAX_BLOCK 9
+constexpr int spc_block_max(int order, size_t elem_bytes) {
+  const size_t box = (size_t)(SP_T + order - 1) * (SP_T + order - 1) * (SP_T + order - 1) * elem_bytes;
+  const int m = (int)(SPC_LDS_BYTES / box);
+  return m < 1 ? 1 : (m > SPC_MAX_BLOCK ? SPC_MAX_BLOCK : m);
+}
+struct SpcPlan { int nblk, cb; };  // number of channel blocks and channels per block (the last block may hold fewer)
+static SpcPlan spc_plan(int C, int order, size_t elem_bytes) {
+  const int m = spc_block_max(order, elem_bytes);
+  const int nblk = (C + m - 1) / m;
+  return SpcPlan{nblk, (C + nblk - 1) / nblk};  // 9 channels at a limit of 4: three blocks of 3, not 4 + 4 + 1
+}
+static bool spc_tiled_ok(int nx, int ny, int nz, int B, int order, int C, size_t elem_bytes) {
+  return sp_tiled_ok(nx, ny, nz, B, order) && (long long)B * spc_plan(C, order, elem_bytes).cb <= 65535;  // grid.z of the reduce
+}
+
+template <class T, int ORDER>
+__global__ __launch_bounds__(256) void spread_box_channels_kernel(const T* __restrict__ values, int C, int c0, int cb,
+                                                                  const int* __restrict__ atom_of, const int* __restrict__ bin_start,
+                                                                  const int4* __restrict__ lo3, const T* __restrict__ theta_all, int N, int nx, int ny,
+                                                                  int nz, int batched, SpTile e, T* __restrict__ boxes) {
+  constexpr int order = ORDER, H = ORDER - 1, CBM = spc_block_max(ORDER, sizeof(T));
+  __shared__ T box[CBM * (SP_T + H) * (SP_T + H) * (SP_T + H)];  // [cb][box_n]
+  __shared__ T wl[SPB_CHUNK][3][ORDER];
+  __shared__ int lo_s[SPB_CHUNK][3];
+  __shared__ T val_s[SPB_CHUNK][CBM];
+  const int nbx = nx / e.ex, nby = ny / e.ey, nbz = nz / e.ez;
+  const int bxn = e.ex + H, byn = e.ey + H, bzn = e.ez + H, box_n = bxn * byn * bzn;
+  int b = blockIdx.x;
+  const int bz = b % nbz; b /= nbz;
+  const int by = b % nby; b /= nby;
+  const int bx = b % nbx;
+  const int org[3] = {bx * e.ex, by * e.ey, bz * e.ez};
+  for (int k = threadIdx.x; k < cb * box_n; k += blockDim.x) box[k] = T(0);
+  const int tpa = order * order;
+  const T thr = batched ? T(1e-8) : T(0);
+  const int beg = bin_start[blockIdx.x], end = bin_start[blockIdx.x + 1];
+  for (int a0 = beg; a0 < end; a0 += SPB_CHUNK) {
+    const int nc = end - a0 < SPB_CHUNK ? end - a0 : SPB_CHUNK;
+    __syncthreads();  // boxes zeroed / previous chunk consumed
+    if (threadIdx.x < 3 * nc) {  // one thread per (atom, axis), as in spread_box_kernel
+      const int a = threadIdx.x / 3, d = threadIdx.x - 3 * a;
+      const int i = atom_of[a0 + a];
+      const int4 lo = lo3[i];
+      const T theta = theta_all[(size_t)d * N + i];
+      const int off0 = (int)floor(theta - (T)(order - 2) * T(0.5));
+      lo_s[a][d] = (d == 0 ? lo.x : (d == 1 ? lo.y : lo.z)) - org[d];
+#pragma unroll
+      for (int t = 0; t < order; ++t) {
+        const T u = (T)order * T(0.5) + theta - (T)(t + off0);
+        wl[a][d][t] = (u < T(0) || u >= (T)order) ? T(0) : bspline_weight(u, order);
+      }
+    }
+    for (int k = threadIdx.x; k < nc * cb; k += blockDim.x) {
+      const int a = k / cb, c = k - a * cb;
+      val_s[a][c] = values[(size_t)atom_of[a0 + a] * C + c0 + c];
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < nc * tpa; t += blockDim.x) {
+      const int a = t / tpa, col = t - a * tpa;
+      const int tx = col / order, ty = col - tx * order;
+      const T wxy = wl[a][0][tx] * wl[a][1][ty];
+      T* row = box + ((lo_s[a][0] + tx) * byn + lo_s[a][1] + ty) * bzn + lo_s[a][2];  // box coordinates need no wrap
+#pragma unroll
+      for (int tz = 0; tz < order; ++tz) {
+        const T w = wxy * wl[a][2][tz];
+        if (w > thr)
+          for (int c = 0; c < cb; ++c) atomicAdd(row + c * box_n + tz, val_s[a][c] * w);
+      }
+    }
+  }
+  __syncthreads();
+  T* out = boxes + (size_t)blockIdx.x * cb * box_n;  // [tile][cb][box_n]
+  for (int k = threadIdx.x; k < cb * box_n; k += blockDim.x) out[k] = box[k];
+}
+// spread_box_reduce_kernel for one block of channels: grid.z = system * cb + channel of the block
+template <class T>
+__global__ __launch_bounds__(256) void spread_box_reduce_channels_kernel(const T* __restrict__ boxes, int nx, int ny, int nz, int C, int c0, int cb,
+                                                                        int order, SpTile e, T* __restrict__ mesh) {
+  const unsigned yz = blockIdx.x * blockDim.x + threadIdx.x;
+  if (yz >= (unsigned)ny * (unsigned)nz) return;
+  const int y = (int)(yz / (unsigned)nz), z = (int)(yz - (unsigned)y * (unsigned)nz), x = (int)blockIdx.y;
+  const int s = (int)blockIdx.z / cb, c = (int)blockIdx.z - s * cb;
+  const size_t g = (((size_t)s * C + c0 + c) * nx + x) * ((size_t)ny * nz) + yz;
+  const int H = order - 1;
+  const int nbx = nx / e.ex, nby = ny / e.ey, nbz = nz / e.ez;
+  const int bxn = e.ex + H, byn = e.ey + H, bzn = e.ez + H;
+  const size_t box_n = (size_t)bxn * byn * bzn;
+  const int tx = x / e.ex, ty = y / e.ey, tz = z / e.ez;
+  const int lx = x - tx * e.ex, ly = y - ty * e.ey, lz = z - tz * e.ez;
+  T acc = T(0);
+  for (int dx = 0; dx < 2; ++dx) {
+    if (dx && lx >= H) break;
+    const int sx = dx ? (tx == 0 ? nbx - 1 : tx - 1) : tx, px = lx + dx * e.ex;
+    for (int dy = 0; dy < 2; ++dy) {
+      if (dy && ly >= H) break;
+      const int sy = dy ? (ty == 0 ? nby - 1 : ty - 1) : ty, py = ly + dy * e.ey;
+      for (int dz = 0; dz < 2; ++dz) {
+        if (dz && lz >= H) break;
+        const int sz = dz ? (tz == 0 ? nbz - 1 : tz - 1) : tz, pz = lz + dz * e.ez;
+        const size_t tile = (((size_t)s * nbx + sx) * nby + sy) * nbz + sz;
+        acc += boxes[(tile * cb + c) * box_n + ((size_t)px * byn + py) * bzn + pz];
       }
     }
   }
@@ -499,6 +644,120 @@ __global__ __launch_bounds__(128) void spline_gather_grad_kernel(const T* __rest
         gz += v * wxy * d1[2][tz];
       }
     }
+  out[3 * (size_t)i] = gx; out[3 * (size_t)i + 1] = gy; out[3 * (size_t)i + 2] = gz;
+}
+
+// ---- multi-channel gathers (mesh[B, C, nx, ny, nz] -> out[N, C]) -------------------------------------------------------------------
+// One thread per atom: stencil, wrapped z indices and z weights once, SGC_BLOCK channel accumulators, a loop over channel blocks for larger
+// C.  The body is spline_gather_kernel<T, 1>'s, statement for statement (run-time order, the same loop nest, wxy = wx * wy, w = wxy * wz,
+// the w > 1e-8 test, acc += mesh * w), with the channel loop around the accumulation only: a channel must equal the scalar gather of its
+// plane bit for bit, and the compiler contracts / packs the fp32 stencil arithmetic differently once the loops are unrolled over a
+// compile-time order (tests/test_spline_channels_gpu.py asserts the equality for every order, dtype and channel count).
+#define SGC_BLOCK 5
+template <class T, bool FULL>
+__device__ __forceinline__ void gather_channel_block(const Stencil<T>& st, const T* __restrict__ wz, const int* __restrict__ gz, const T* __restrict__ m0,
+                                                     size_t plane, int nc, int nx, int ny, int nz, int order, T* __restrict__ out) {
+  T acc[SGC_BLOCK];
+#pragma unroll
+  for (int c = 0; c < SGC_BLOCK; ++c) acc[c] = T(0);
+  for (int tx = 0; tx < order; ++tx) {
+    const T wx = weight_1d(st, 0, tx, order);
+    const int gx = wrap_idx(st.base[0] + tx + st.off0[0], nx);
+    for (int ty = 0; ty < order; ++ty) {
+      const T wxy = wx * weight_1d(st, 1, ty, order);
+      const int gy = wrap_idx(st.base[1] + ty + st.off0[1], ny);
+      const T* row = m0 + ((size_t)gx * ny + gy) * nz;
+      for (int tz = 0; tz < order; ++tz) {
+        const T w = wxy * wz[tz];
+        if (w > T(1e-8)) {
+#pragma unroll
+          for (int c = 0; c < SGC_BLOCK; ++c)
+            if (FULL || c < nc) acc[c] += row[(size_t)c * plane + gz[tz]] * w;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < SGC_BLOCK; ++c)
+    if (FULL || c < nc) out[c] = acc[c];
+}
+template <class T>
+__global__ __launch_bounds__(128) void spline_gather_channels_kernel(const T* __restrict__ pos, const T* __restrict__ mesh,
+                                                                     const int* __restrict__ batch_idx, const T* __restrict__ cit, int N, int C, int nx,
+                                                                     int ny, int nz, int order, T* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const int s = batch_idx ? batch_idx[i] : 0;
+  const Stencil<T> st = make_stencil(pos + 3 * (size_t)i, cit + 9 * (size_t)s, nx, ny, nz, order);
+  T wz[MI_MAX_ORDER];
+  int gz[MI_MAX_ORDER];
+  for (int t = 0; t < order; ++t) { wz[t] = weight_1d(st, 2, t, order); gz[t] = wrap_idx(st.base[2] + t + st.off0[2], nz); }
+  const size_t plane = (size_t)nx * ny * nz;
+  const T* m0 = mesh + (size_t)s * C * plane;
+  T* o = out + (size_t)i * C;
+  int c0 = 0;
+  for (; c0 + SGC_BLOCK <= C; c0 += SGC_BLOCK) gather_channel_block<T, true>(st, wz, gz, m0 + (size_t)c0 * plane, plane, SGC_BLOCK, nx, ny, nz, order, o + c0);
+  if (c0 < C) gather_channel_block<T, false>(st, wz, gz, m0 + (size_t)c0 * plane, plane, C - c0, nx, ny, nz, order, o + c0);
+}
+
+// out[i][a] = sum_c coef[i][c] sum_g mesh[c][g] dW_i(g) / dfrac_a: spline_gather_grad_kernel on the per-atom combination of the channel
+// planes.  Weights and derivative weights (times the mesh dimension) once per atom; the channels enter only through v = sum_c coef_c mesh_c.
+template <class T, int ORDER>
+__global__ __launch_bounds__(128) void spline_gather_channels_frac_grad_kernel(const T* __restrict__ pos, const T* __restrict__ mesh,
+                                                                               const T* __restrict__ coef, const int* __restrict__ batch_idx,
+                                                                               const T* __restrict__ cit, int N, int C, int nx, int ny, int nz,
+                                                                               T* __restrict__ out) {
+  constexpr int order = ORDER;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const int s = batch_idx ? batch_idx[i] : 0;
+  const Stencil<T> st = make_stencil(pos + 3 * (size_t)i, cit + 9 * (size_t)s, nx, ny, nz, order);
+  T w1[2][ORDER], d1[2][ORDER];  // y and z tables; the x pair is evaluated inside the (rolled) outer loop
+  int gi[2][ORDER];
+  const int dims[3] = {nx, ny, nz};
+#pragma unroll
+  for (int d = 1; d < 3; ++d)
+#pragma unroll
+    for (int t = 0; t < order; ++t) {
+      const T u = (T)order * T(0.5) + st.theta[d] - (T)(t + st.off0[d]);
+      const bool in = !(u < T(0) || u >= (T)order);
+      w1[d - 1][t] = in ? bspline_weight(u, order) : T(0);
+      d1[d - 1][t] = in ? bspline_deriv(u, order) * (T)dims[d] : T(0);
+      gi[d - 1][t] = wrap_idx(st.base[d] + t + st.off0[d], dims[d]);
+    }
+  const size_t plane = (size_t)nx * ny * nz;
+  const T* m0 = mesh + (size_t)s * C * plane;
+  const T* cf = coef + (size_t)i * C;
+  T gx = 0, gy = 0, gz = 0;
+  for (int c0 = 0; c0 < C; c0 += SGC_BLOCK) {
+    const int nc = C - c0 < SGC_BLOCK ? C - c0 : SGC_BLOCK;
+    T k[SGC_BLOCK];
+#pragma unroll
+    for (int c = 0; c < SGC_BLOCK; ++c) k[c] = c < nc ? cf[c0 + c] : T(0);
+    const T* mb = m0 + (size_t)c0 * plane;
+#pragma unroll 1
+    for (int tx = 0; tx < order; ++tx) {
+      const T u = (T)order * T(0.5) + st.theta[0] - (T)(tx + st.off0[0]);
+      const bool in = !(u < T(0) || u >= (T)order);
+      const T wx = in ? bspline_weight(u, order) : T(0), dx = in ? bspline_deriv(u, order) * (T)nx : T(0);
+      const int ix = wrap_idx(st.base[0] + tx + st.off0[0], nx);
+#pragma unroll
+      for (int ty = 0; ty < order; ++ty) {
+        const T* row = mb + ((size_t)ix * ny + gi[0][ty]) * nz;
+        const T wxy = wx * w1[0][ty], dxy = dx * w1[0][ty], xdy = wx * d1[0][ty];
+#pragma unroll
+        for (int tz = 0; tz < order; ++tz) {
+          T v = T(0);
+#pragma unroll
+          for (int c = 0; c < SGC_BLOCK; ++c)
+            if (c < nc) v += k[c] * row[(size_t)c * plane + gi[1][tz]];
+          gx += v * dxy * w1[1][tz];
+          gy += v * xdy * w1[1][tz];
+          gz += v * wxy * d1[1][tz];
+        }
+      }
+    }
+  }
   out[3 * (size_t)i] = gx; out[3 * (size_t)i + 1] = gy; out[3 * (size_t)i + 2] = gz;
 }
 
@@ -1251,6 +1510,39 @@ static int solve_launch(const void* mesh, const void* recip_cell, const void* al
     }                                                    \
   } while (0)
 
+namespace {
+// multi-channel tile spread: key + counting sort ONCE, then box + reduce per block of channels (mesh [B, C, nx, ny, nz])
+template <class T>
+int spread_channels_tiled(const T* pos, const T* values, const int* batch_idx, const T* cit, int N, int B, int C, int nx, int ny, int nz, int order,
+                          int batched, T* mesh, char* ws, hipStream_t st) {
+  const SpcPlan plan = spc_plan(C, order, sizeof(T));
+  const SpLayout L = sp_layout(N, B, nx, ny, nz, order, sizeof(T), plan.cb);
+  const SpTile e = sp_tile(nx, ny, nz);
+  int* keys_in = reinterpret_cast<int*>(ws + L.keys_in);
+  int* vals_out = reinterpret_cast<int*>(ws + L.vals_out) + 4;
+  int* bin_start = reinterpret_cast<int*>(ws + L.bin_start);
+  int4* lo3 = reinterpret_cast<int4*>(ws + L.lo3);
+  T* theta = reinterpret_cast<T*>(ws + L.theta);
+  const BsScratch bins = bs_carve(reinterpret_cast<int*>(ws + L.bins), L.nbins + 1);
+  MI_HIP_CHECK(bs_clear(bins, st));
+  int* incoherent = bins.fill + L.nbins;
+  spread_key_kernel<T><<<mi_blocks(N, 256), 256, 0, st>>>(pos, batch_idx, cit, N, nx, ny, nz, order, e, keys_in, bins.count, lo3, theta, incoherent);
+  MI_LAUNCH_CHECK();
+  MI_HIP_CHECK(bs_sort(bins, keys_in, N, nullptr, vals_out, bin_start, st));
+  T* boxes = reinterpret_cast<T*>(ws + L.boxes);
+  for (int c0 = 0; c0 < C; c0 += plan.cb) {
+    const int cb = C - c0 < plan.cb ? C - c0 : plan.cb;
+    MI_DISPATCH_ORDER(order, (spread_box_channels_kernel<T, O_><<<(int)L.nbins, 256, 0, st>>>(values, C, c0, cb, vals_out, bin_start, lo3, theta, N, nx, ny,
+                                                                                             nz, batched, e, boxes)));
+    MI_LAUNCH_CHECK();
+    spread_box_reduce_channels_kernel<T><<<dim3((unsigned)mi_blocks((long long)ny * nz, 256), (unsigned)nx, (unsigned)(B * cb)), 256, 0, st>>>(
+        boxes, nx, ny, nz, C, c0, cb, order, e, mesh);
+    MI_LAUNCH_CHECK();
+  }
+  return MI_OK;
+}
+}  // namespace
+
 // `order` arguments of the C ABI: low byte = spline order; MI_SPLINE_REFERENCE_ORDERS + order >= 5 selects the reference's evaluation of
 // those orders -- identically ZERO weights (spline.py:150-193 implements orders 1-4 only) and the structure-factor exponent capped at 4
 // (pme_kernels.py:213-225).  Without the flag orders 5 and 6 are the true cardinal B-splines.
@@ -1383,6 +1675,96 @@ int mi_spline_gather(const void* positions, const void* mesh, const int32_t* bat
   MI_DISPATCH_T(dtype, (spline_gather_kernel<T_, 1><<<mi_blocks(n_atoms, 128), 128, 0, st>>>((const T_*)positions, nullptr, (const T_*)mesh, batch_idx,
                                                                                              (const T_*)cell_inv_t, n_atoms, nx, ny, nz, order,
                                                                                              (T_*)out)));
+  mi_timing_end(stream);
+  MI_LAUNCH_CHECK();
+  return MI_OK;
+}
+
+/* ---- multi-channel spread / gather (values[N, C] <-> mesh[B, C, nx, ny, nz]) ---- */
+size_t mi_spline_spread_channels_workspace_bytes_for(int n_atoms, int n_systems, int nx, int ny, int nz, int order, int n_channels, int dtype) {
+  if (n_atoms < 0 || n_systems < 1 || nx <= 0 || ny <= 0 || nz <= 0 || n_channels < 1 || (dtype != MI_F32 && dtype != MI_F64)) return 0;
+  const OrderArg oa = decode_order(order);
+  if (oa.order < 1 || oa.order > MI_MAX_ORDER) return 0;
+  if (oa.ref_zero || !spc_tiled_ok(nx, ny, nz, n_systems, oa.order, n_channels, dtype_bytes(dtype))) return 256;  // the atomic kernel needs no scratch
+  return sp_layout(n_atoms, n_systems, nx, ny, nz, oa.order, dtype_bytes(dtype), spc_plan(n_channels, oa.order, dtype_bytes(dtype)).cb).total;
+}
+
+int mi_spline_spread_channels(const void* positions, const void* values, const int32_t* batch_idx, const void* cell_inv_t, int n_atoms,
+                              int n_systems, int n_channels, int nx, int ny, int nz, int order, int batched, int dtype, void* mesh, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
+  const OrderArg oa = decode_order(order);
+  order = oa.order;
+  MI_REQUIRE(order >= 1 && order <= MI_MAX_ORDER, "spline order must be 1..6");
+  MI_REQUIRE(nx > 0 && ny > 0 && nz > 0 && n_systems >= 1, "mesh dimensions");
+  MI_REQUIRE(n_channels >= 1, "n_channels must be >= 1");
+  if (n_atoms <= 0) return MI_OK;
+  MI_REQUIRE(positions && values && cell_inv_t && mesh, "null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t mesh_bytes = (size_t)n_systems * n_channels * nx * ny * nz * dtype_bytes(dtype);
+  if (oa.ref_zero) {  // all weights are zero: nothing is spread
+    MI_HIP_CHECK(hipMemsetAsync(mesh, 0, mesh_bytes, st));
+    return MI_OK;
+  }
+  mi_timing_begin("spline_spread_channels", stream);
+  int rc = MI_OK;
+  if (workspace && spc_tiled_ok(nx, ny, nz, n_systems, order, n_channels, dtype_bytes(dtype)) &&
+      workspace_bytes >= sp_layout(n_atoms, n_systems, nx, ny, nz, order, dtype_bytes(dtype), spc_plan(n_channels, order, dtype_bytes(dtype)).cb).total) {
+    MI_DISPATCH_T(dtype, rc = spread_channels_tiled<T_>((const T_*)positions, (const T_*)values, batch_idx, (const T_*)cell_inv_t, n_atoms, n_systems,
+                                                        n_channels, nx, ny, nz, order, batched, (T_*)mesh, (char*)workspace, st));
+  } else {
+    // the atomic kernel adds into a zeroed mesh; the call clears it itself, so the caller's mesh may be uninitialised on either path
+    hipError_t he = hipMemsetAsync(mesh, 0, mesh_bytes, st);
+    if (he != hipSuccess) { mi_timing_end(stream); MI_HIP_CHECK(he); }
+    const int apb = 256 / (order * order);
+    MI_DISPATCH_T(dtype, (spline_spread_channels_kernel<T_><<<mi_blocks(n_atoms, apb), 256, 0, st>>>(
+                             (const T_*)positions, (const T_*)values, batch_idx, (const T_*)cell_inv_t, n_atoms, n_channels, nx, ny, nz, order, batched,
+                             (T_*)mesh)));
+  }
+  mi_timing_end(stream);
+  if (rc != MI_OK) return rc;
+  MI_LAUNCH_CHECK();
+  return MI_OK;
+}
+
+int mi_spline_gather_channels(const void* positions, const void* mesh, const int32_t* batch_idx, const void* cell_inv_t, int n_atoms, int n_systems,
+                              int n_channels, int nx, int ny, int nz, int order, int dtype, void* out, void* stream) {
+  MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
+  const OrderArg oa = decode_order(order);
+  order = oa.order;
+  MI_REQUIRE(order >= 1 && order <= MI_MAX_ORDER, "spline order must be 1..6");
+  MI_REQUIRE(nx > 0 && ny > 0 && nz > 0 && n_systems >= 1, "mesh dimensions");
+  MI_REQUIRE(n_channels >= 1, "n_channels must be >= 1");
+  if (n_atoms <= 0) return MI_OK;
+  MI_REQUIRE(positions && mesh && cell_inv_t && out, "null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (oa.ref_zero) { MI_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)n_atoms * n_channels * dtype_bytes(dtype), st)); return MI_OK; }
+  mi_timing_begin("spline_gather_channels", stream);
+  MI_DISPATCH_T(dtype, (spline_gather_channels_kernel<T_><<<mi_blocks(n_atoms, 128), 128, 0, st>>>((const T_*)positions, (const T_*)mesh, batch_idx,
+                                                                                                   (const T_*)cell_inv_t, n_atoms, n_channels, nx, ny, nz,
+                                                                                                   order, (T_*)out)));
+  mi_timing_end(stream);
+  MI_LAUNCH_CHECK();
+  return MI_OK;
+}
+
+int mi_spline_gather_channels_frac_grad(const void* positions, const void* mesh, const void* coef, const int32_t* batch_idx, const void* cell_inv_t,
+                                        int n_atoms, int n_systems, int n_channels, int nx, int ny, int nz, int order, int dtype, void* out,
+                                        void* stream) {
+  MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
+  const OrderArg oa = decode_order(order);
+  order = oa.order;
+  MI_REQUIRE(order >= 1 && order <= MI_MAX_ORDER, "spline order must be 1..6");
+  MI_REQUIRE(nx > 0 && ny > 0 && nz > 0 && n_systems >= 1, "mesh dimensions");
+  MI_REQUIRE(n_channels >= 1, "n_channels must be >= 1");
+  if (n_atoms <= 0) return MI_OK;
+  MI_REQUIRE(positions && mesh && coef && cell_inv_t && out, "null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (oa.ref_zero) { MI_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)n_atoms * 3 * dtype_bytes(dtype), st)); return MI_OK; }
+  mi_timing_begin("spline_gather_channels_frac_grad", stream);
+  MI_DISPATCH_ORDER(order, MI_DISPATCH_T(dtype, (spline_gather_channels_frac_grad_kernel<T_, O_><<<mi_blocks(n_atoms, 128), 128, 0, st>>>(
+                                                    (const T_*)positions, (const T_*)mesh, (const T_*)coef, batch_idx, (const T_*)cell_inv_t, n_atoms,
+                                                    n_channels, nx, ny, nz, (T_*)out))));
   mi_timing_end(stream);
   MI_LAUNCH_CHECK();
   return MI_OK;

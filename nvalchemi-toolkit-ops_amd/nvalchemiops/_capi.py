@@ -80,6 +80,20 @@ def lib() -> ctypes.CDLL:
         for name in ("mi_ewald_virial_blocks", "mi_ewald_recip_virial_blocks", "mi_pme_virial_blocks"):
             getattr(L, name).restype = i
             getattr(L, name).argtypes = []
+        # multi-channel spline entry points and the multipole basis functions (nvalchemiops.math)
+        L.mi_spline_spread_channels_workspace_bytes_for.restype = sz
+        L.mi_spline_spread_channels_workspace_bytes_for.argtypes = [i] * 8
+        L.mi_spline_spread_channels.restype = i
+        L.mi_spline_spread_channels.argtypes = [vp, vp, vp, vp] + [i] * 9 + [vp, vp, sz, vp]
+        L.mi_spline_gather_channels.restype = i
+        L.mi_spline_gather_channels.argtypes = [vp, vp, vp, vp] + [i] * 8 + [vp, vp]
+        L.mi_spline_gather_channels_frac_grad.restype = i
+        L.mi_spline_gather_channels_frac_grad.argtypes = [vp, vp, vp, vp, vp] + [i] * 8 + [vp, vp]
+        dbl = ctypes.c_double
+        for name, args in (("mi_sph_harm", [vp, i, i, vp, vp]), ("mi_sph_harm_grad", [vp, i, i, vp, vp]), ("mi_gto_density", [vp, i, dbl, i, vp, vp]),
+                           ("mi_gto_fourier", [vp, i, dbl, i, vp, vp, vp])):
+            getattr(L, name).restype = i
+            getattr(L, name).argtypes = args
         _LIB = L
     return _LIB
 

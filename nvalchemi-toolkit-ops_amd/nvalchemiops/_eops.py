@@ -208,7 +208,7 @@ def _coordinate_grads(weight, gfrac, pos, cit, bi):
     Elementwise contractions + reductions: a per-atom batched 3x3 GEMM (einsum) was 11 % of the GPU time of a PME training step, and the
     [3,N] x [N,3] GEMM formulation of the cell term is worse still (rocBLAS runs a K = N fp64 product with a 3x3 result in one workgroup:
     5 ms at 100k atoms).  Batch: nine per-system segment sums (`seg_sum`), not one same-address atomic per atom."""
-    wg = gfrac * weight.unsqueeze(-1)
+    wg = gfrac if weight is None else gfrac * weight.unsqueeze(-1)  # (None: the weights are inside gfrac already, channel ops below)
     if bi is None:  # single system: cit is [1,3,3]
         return (wg.unsqueeze(-1) * cit[0]).sum(1), (wg.unsqueeze(-1) * pos.unsqueeze(-2)).sum(0, keepdim=True)
     gpos = (wg.unsqueeze(-1) * cit[bi.long()]).sum(1)
@@ -374,6 +374,184 @@ def _gather_backward(batched):
 
 spline_gather_op = _op("_spline_gather", _spline_gather, _spline_gather_fake, _gather_backward(False), _gather_setup(False))
 batch_spline_gather_op = _op("_batch_spline_gather", _batch_spline_gather, _batch_spline_gather_fake, _gather_backward(True), _gather_setup(True))
+
+
+# ---- multi-channel spread / gather: values[N, C] <-> mesh[(B,) C, nx, ny, nz] (reference ops spline.py:2202-2580) ---------------------------
+# One fused launch sequence per call (csrc/pme.hip: mi_spline_spread_channels / _gather_channels) instead of C scalar ops; argument lists
+# are the reference's plus the optional `cell_inv_t` the scalar ops here carry.  Adjoints: the two ops are each other's (values / mesh
+# branches, built from the ops themselves so they can be differentiated again); positions and cell come from the channel-weighted
+# fractional gradient, an op of its own whose derivative is refused like `frac_grad_op`'s.
+def _channels_impl(positions, batch_idx, cit):
+    C.require_device(positions, cit)  # the ops are reachable from a trace over tensors that are not on the device: refuse, never dereference
+    pos = positions.detach().contiguous()
+    return pos, (None if batch_idx is None else C.i32(batch_idx)), cit.detach().to(pos.dtype).contiguous()
+
+
+def _frac_grad_channels(positions: Tensor, mesh: Tensor, coef: Tensor, batch_idx: Optional[Tensor], cell_inv_t: Tensor, spline_order: int) -> Tensor:
+    from nvalchemiops.spline import _launch_gather_channels
+
+    pos, bi, cit = _channels_impl(positions, batch_idx, cell_inv_t)
+    if pos.shape[0] == 0 or mesh.shape[1] == 0:
+        return pos.new_zeros((pos.shape[0], 3))
+    return _launch_gather_channels(pos, mesh.detach().to(pos.dtype).contiguous(), cit, bi, int(spline_order), coef=coef.detach().to(pos.dtype).contiguous())
+
+
+frac_grad_channels_op = torch.library.custom_op("nvalchemiops::spline_gather_channels_frac_grad", _frac_grad_channels, mutates_args=())
+frac_grad_channels_op.register_fake(lambda positions, mesh, coef, batch_idx, cell_inv_t, spline_order: positions.new_empty((positions.shape[0], 3)))
+frac_grad_channels_op.register_autograd(lambda ctx, g: (_ for _ in ()).throw(NotImplementedError(_SECOND_ORDER.format(
+    op="nvalchemiops::spline_gather_channels_frac_grad", what="position / cell gradient"))), setup_context=lambda ctx, inputs, output: None)
+
+
+def _spread_channels_run(positions, values, batch_idx, cit, nsys, dims, order):
+    from nvalchemiops.spline import _launch_spread_channels
+
+    pos, bi, c = _channels_impl(positions, batch_idx, cit)
+    if pos.shape[0] == 0 or values.shape[1] == 0:
+        return pos.new_zeros((nsys, values.shape[1]) + tuple(dims))
+    return _launch_spread_channels(pos, values.detach().to(pos.dtype).contiguous(), c, bi, nsys, dims, int(order), bi is not None)
+
+
+def _gather_channels_run(positions, mesh, batch_idx, cit, order):
+    from nvalchemiops.spline import _launch_gather_channels
+
+    pos, bi, c = _channels_impl(positions, batch_idx, cit)
+    if pos.shape[0] == 0 or mesh.shape[1] == 0:
+        return pos.new_zeros((pos.shape[0], mesh.shape[1]))
+    return _launch_gather_channels(pos, mesh.detach().to(pos.dtype).contiguous(), c, bi, int(order))
+
+
+def _batch_cit(cell, cell_inv_t, dtype, nsys):
+    cit = _cit(cell, cell_inv_t, dtype)
+    return cit.expand(nsys, 3, 3) if cit.shape[0] == 1 and nsys > 1 else cit
+
+
+def _spline_spread_channels(positions: Tensor, values: Tensor, cell: Tensor, num_channels: int, mesh_nx: int, mesh_ny: int, mesh_nz: int,
+                            spline_order: int, cell_inv_t: Optional[Tensor] = None) -> Tensor:
+    return _spread_channels_run(positions, values, None, _cit(cell, cell_inv_t, positions.dtype), 1, (mesh_nx, mesh_ny, mesh_nz), spline_order)[0]
+
+
+def _spline_spread_channels_fake(positions, values, cell, num_channels, mesh_nx, mesh_ny, mesh_nz, spline_order, cell_inv_t=None):
+    return positions.new_empty((num_channels, mesh_nx, mesh_ny, mesh_nz))
+
+
+def _batch_spline_spread_channels(positions: Tensor, values: Tensor, batch_idx: Tensor, cell: Tensor, num_systems: int, num_channels: int,
+                                  mesh_nx: int, mesh_ny: int, mesh_nz: int, spline_order: int, cell_inv_t: Optional[Tensor] = None) -> Tensor:
+    return _spread_channels_run(positions, values, batch_idx, _batch_cit(cell, cell_inv_t, positions.dtype, num_systems), num_systems,
+                                (mesh_nx, mesh_ny, mesh_nz), spline_order)
+
+
+def _batch_spline_spread_channels_fake(positions, values, batch_idx, cell, num_systems, num_channels, mesh_nx, mesh_ny, mesh_nz, spline_order,
+                                       cell_inv_t=None):
+    return positions.new_empty((num_systems, num_channels, mesh_nx, mesh_ny, mesh_nz))
+
+
+def _spline_gather_channels(positions: Tensor, mesh: Tensor, cell: Tensor, spline_order: int, cell_inv_t: Optional[Tensor] = None) -> Tensor:
+    return _gather_channels_run(positions, mesh.unsqueeze(0), None, _cit(cell, cell_inv_t, positions.dtype), spline_order)
+
+
+def _spline_gather_channels_fake(positions, mesh, cell, spline_order, cell_inv_t=None):
+    return positions.new_empty((positions.shape[0], mesh.shape[0]))
+
+
+def _batch_spline_gather_channels(positions: Tensor, mesh: Tensor, batch_idx: Tensor, cell: Tensor, spline_order: int,
+                                  cell_inv_t: Optional[Tensor] = None) -> Tensor:
+    return _gather_channels_run(positions, mesh, batch_idx, _batch_cit(cell, cell_inv_t, positions.dtype, mesh.shape[0]), spline_order)
+
+
+def _batch_spline_gather_channels_fake(positions, mesh, batch_idx, cell, spline_order, cell_inv_t=None):
+    return positions.new_empty((positions.shape[0], mesh.shape[1]))
+
+
+def _channel_coordinate_grads(positions, mesh5, coef, batch_idx, cit, cell, cell_inv_t, order, need_cell):
+    """Position / cell_inv_t / cell gradients shared by both adjoints: gfrac_i = sum_c coef_ic sum_g mesh_c[g] dW_i(g)/dfrac, then the
+    chain rule of `_coordinate_grads` (the per-atom weights are inside gfrac already)."""
+    gfrac = frac_grad_channels_op(positions, mesh5, coef, batch_idx, cit, order)
+    gpos, gc = _coordinate_grads(None, gfrac, positions.detach(), cit.detach(), batch_idx)
+    gcit = _like_cell_inv_t(gc if (cell_inv_t is None or cell_inv_t.reshape(-1, 3, 3).shape[0] == gc.shape[0]) else gc.sum(0, keepdim=True), cell_inv_t)
+    return gpos, gcit, _cell_grad_without_cit(gc, cit, cell, cell_inv_t, need_cell)
+
+
+def _spread_channels_setup(batched):
+    def setup(ctx, inputs, output):
+        if batched:
+            positions, values, batch_idx, cell, num_systems, _, _, _, _, order, cell_inv_t = inputs
+        else:
+            positions, values, cell, _, _, _, _, order, cell_inv_t = inputs
+            batch_idx, num_systems = None, 1
+        ctx.save_for_backward(positions, values, cell, cell_inv_t, batch_idx)
+        ctx.order, ctx.nsys = order, num_systems
+    return setup
+
+
+def _spread_channels_backward(batched):
+    def backward(ctx, gmesh):
+        positions, values, cell, cell_inv_t, batch_idx = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g = gmesh.contiguous()
+        gvals = gpos = gcit = gcell = None
+        ci, cell_i = (10, 3) if batched else (8, 2)
+        if need[1]:  # d/dvalues = gather_channels(grad_mesh): the gather op, so this branch can be differentiated again
+            if batched:
+                gvals = torch.ops.alchemiops._batch_spline_gather_channels(positions, g, batch_idx, cell, ctx.order, cell_inv_t)
+            else:
+                gvals = torch.ops.alchemiops._spline_gather_channels(positions, g, cell, ctx.order, cell_inv_t)
+        if need[0] or _n(need, ci) or (cell_inv_t is None and need[cell_i]):
+            cit = _batch_cit(cell, cell_inv_t, positions.dtype, ctx.nsys if batched else 1)
+            gpos, gcit, gcell = _channel_coordinate_grads(positions, g if batched else g.unsqueeze(0), values.to(positions.dtype), batch_idx, cit, cell,
+                                                          cell_inv_t, ctx.order, need[cell_i])
+        gpos = gpos if need[0] else None
+        if batched:
+            return _fit(need, (gpos, gvals, None, gcell, None, None, None, None, None, None, gcit if _n(need, ci) else None))
+        return _fit(need, (gpos, gvals, gcell, None, None, None, None, None, gcit if _n(need, ci) else None))
+    return backward
+
+
+def _gather_channels_setup(batched):
+    def setup(ctx, inputs, output):
+        if batched:
+            positions, mesh, batch_idx, cell, order, cell_inv_t = inputs
+        else:
+            positions, mesh, cell, order, cell_inv_t = inputs
+            batch_idx = None
+        ctx.save_for_backward(positions, mesh, cell, cell_inv_t, batch_idx)
+        ctx.order = order
+    return setup
+
+
+def _gather_channels_backward(batched):
+    def backward(ctx, gout):
+        positions, mesh, cell, cell_inv_t, batch_idx = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        nsys = mesh.shape[0] if batched else 1
+        g = gout.contiguous()
+        nch = mesh.shape[-4]
+        nx, ny, nz = mesh.shape[-3:]
+        gmesh = gpos = gcit = gcell = None
+        ci, cell_i = (5, 3) if batched else (4, 2)
+        if need[1]:  # d/dmesh = spread_channels(grad_out): the spread op, differentiable again
+            if batched:
+                gmesh = torch.ops.alchemiops._batch_spline_spread_channels(positions, g, batch_idx, cell, nsys, nch, nx, ny, nz, ctx.order, cell_inv_t)
+            else:
+                gmesh = torch.ops.alchemiops._spline_spread_channels(positions, g, cell, nch, nx, ny, nz, ctx.order, cell_inv_t)
+        if need[0] or _n(need, ci) or (cell_inv_t is None and need[cell_i]):
+            cit = _batch_cit(cell, cell_inv_t, positions.dtype, nsys)
+            gpos, gcit, gcell = _channel_coordinate_grads(positions, mesh if batched else mesh.unsqueeze(0), g.to(positions.dtype), batch_idx, cit, cell,
+                                                          cell_inv_t, ctx.order, need[cell_i])
+        gpos = gpos if need[0] else None
+        if batched:
+            return _fit(need, (gpos, gmesh, None, gcell, None, gcit if _n(need, ci) else None))
+        return _fit(need, (gpos, gmesh, gcell, None, gcit if _n(need, ci) else None))
+    return backward
+
+
+spline_spread_channels_op = _op("_spline_spread_channels", _spline_spread_channels, _spline_spread_channels_fake, _spread_channels_backward(False),
+                                _spread_channels_setup(False))
+batch_spline_spread_channels_op = _op("_batch_spline_spread_channels", _batch_spline_spread_channels, _batch_spline_spread_channels_fake,
+                                      _spread_channels_backward(True), _spread_channels_setup(True))
+spline_gather_channels_op = _op("_spline_gather_channels", _spline_gather_channels, _spline_gather_channels_fake, _gather_channels_backward(False),
+                                _gather_channels_setup(False))
+batch_spline_gather_channels_op = _op("_batch_spline_gather_channels", _batch_spline_gather_channels, _batch_spline_gather_channels_fake,
+                                      _gather_channels_backward(True), _gather_channels_setup(True))
 
 
 # ---- gather_vec3: out_i[c] = q_i sum_g mesh[g, c] w_i(g) -------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """B-spline charge spreading / gathering -- drop-in for the scalar-channel part of nvalchemiops/spline.py
 (`spline_spread` :2581, `spline_gather` :2640, `spline_gather_vec3` :2684; ops `alchemiops::_[batch_]spline_*` :1500-2107).
 
-HIP kernels in csrc/pme.hip behind `mi_spline_spread / _gather / _gather_vec3`.  Orders 1-4 reproduce the reference's
+HIP kernels in csrc/pme.hip behind `mi_spline_spread / _gather / _gather_vec3` and, for the multi-channel (multipole) forms
+`spline_spread_channels` / `spline_gather_channels` (:2788, :2863; ops :2202-2580), `mi_spline_spread_channels / _gather_channels`.  Orders 1-4 reproduce the reference's
 piecewise polynomials; orders 5 and 6 are true cardinal B-splines (the reference evaluates them as zero: SURVEY F2) unless
 `reference_spline_orders()` / `set_reference_spline_orders(True)` asks for the reference's evaluation.
 """
@@ -217,27 +218,92 @@ def spline_gather_gradient(positions: torch.Tensor, charges: torch.Tensor, mesh:
     return -charges.detach().to(pos.dtype).unsqueeze(-1) * torch.einsum("na,nab->nb", gfrac, cit_i)
 
 
+def _launch_spread_channels(pos, vals, cit, bi, nsys, dims, order, batched):
+    """mesh[nsys, C, nx, ny, nz] = spread of vals[N, C] at `pos` in ONE library call (`mi_spline_spread_channels`): key kernel and counting
+    sort once, box + reduce per block of channels on the tile path; weights once and a loop over the channels on the atomic path.  The
+    path follows `_SPREAD_PATH` exactly as `_launch_spread` does; the library writes the whole mesh on either path."""
+    import ctypes
+
+    nx, ny, nz = (int(v) for v in dims)
+    n, nch = pos.shape[0], vals.shape[1]
+    oarg, dt = C.spline_order_arg(order), C.dtype_code(pos.dtype)
+    if _SPREAD_PATH == "auto":
+        tiled = bool(C.lib().mi_spline_spread_prefers_tiles(n, nsys, nx, ny, nz, oarg))
+    else:
+        tiled = _SPREAD_PATH == "tile" and bool(C.lib().mi_spline_spread_is_tiled(nsys, nx, ny, nz, oarg))
+    mesh = torch.empty((nsys, nch, nx, ny, nz), dtype=pos.dtype, device=pos.device)
+    ws_bytes = int(C.lib().mi_spline_spread_channels_workspace_bytes_for(n, nsys, nx, ny, nz, oarg, nch, dt)) if tiled else 0
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=pos.device) if tiled else None
+    rc = C.lib().mi_spline_spread_channels(C.ptr(pos), C.ptr(vals), C.ptr(bi), C.ptr(cit), n, nsys, nch, nx, ny, nz, oarg, int(batched), dt,
+                                           C.ptr(mesh), C.ptr(ws), ctypes.c_size_t(ws_bytes), C.stream_of(pos))
+    C.check(rc, "mi_spline_spread_channels")
+    return mesh
+
+
+def _launch_gather_channels(pos, mesh, cit, bi, order, coef=None):
+    """out[N, C] = gather of mesh[B, C, nx, ny, nz]; with `coef`[N, C] the channel-weighted fractional-coordinate gradient [N, 3]."""
+    nch = mesh.shape[1]
+    nx, ny, nz = mesh.shape[-3:]
+    n = pos.shape[0]
+    if coef is None:
+        out = torch.empty((n, nch), dtype=pos.dtype, device=pos.device)
+        rc = C.lib().mi_spline_gather_channels(C.ptr(pos), C.ptr(mesh), C.ptr(bi), C.ptr(cit), n, cit.shape[0], nch, nx, ny, nz, C.spline_order_arg(order),
+                                               C.dtype_code(pos.dtype), C.ptr(out), C.stream_of(pos))
+        C.check(rc, "mi_spline_gather_channels")
+        return out
+    out = torch.empty((n, 3), dtype=pos.dtype, device=pos.device)
+    rc = C.lib().mi_spline_gather_channels_frac_grad(C.ptr(pos), C.ptr(mesh), C.ptr(coef), C.ptr(bi), C.ptr(cit), n, cit.shape[0], nch, nx, ny, nz,
+                                                     C.spline_order_arg(order), C.dtype_code(pos.dtype), C.ptr(out), C.stream_of(pos))
+    C.check(rc, "mi_spline_gather_channels_frac_grad")
+    return out
+
+
 @C.traceable
 def spline_spread_channels(positions: torch.Tensor, values: torch.Tensor, cell: torch.Tensor, mesh_dims: tuple[int, int, int],
                            spline_order: int = 4, batch_idx: torch.Tensor | None = None) -> torch.Tensor:
-    """values[N, C] -> mesh[(B,) C, nx, ny, nz] (spline.py:2788-2860).  One tile-owned scalar spread per channel -- the channels
-    share nothing but the per-atom weights, and the multipole path that uses many channels is outside this build's hot path."""
-    chans = [spline_spread(positions, values[:, ch], cell, mesh_dims, spline_order, batch_idx) for ch in range(values.shape[1])]
-    if not chans:
-        lead = () if batch_idx is None else ((cell.shape[0] if cell.dim() == 3 else int(batch_idx.max().item()) + 1),)
-        return torch.zeros(lead + (0,) + tuple(int(v) for v in mesh_dims), dtype=positions.dtype, device=positions.device)
-    return torch.stack(chans, dim=0 if batch_idx is None else 1)
+    """values[N, C] -> mesh[(B,) C, nx, ny, nz] (spline.py:2788-2860), e.g. the 9 multipole channels of L_max = 2.  One fused launch
+    sequence for all channels: they share the stencil, the mesh tile and the 1-D weights of every atom (`mi_spline_spread_channels`).
+    Differentiable w.r.t. positions, values and cell (`alchemiops::_[batch_]spline_spread_channels`)."""
+    spline_order = C.resolve_spline_order(spline_order)
+    nx, ny, nz = (int(v) for v in mesh_dims)
+    nch = values.shape[1]
+    if nch == 0 or positions.shape[0] == 0:
+        lead = () if batch_idx is None else ((cell.shape[0] if cell.dim() == 3 else (int(batch_idx.max().item()) + 1 if batch_idx.numel() else 1)),)
+        return torch.zeros(lead + (nch, nx, ny, nz), dtype=positions.dtype, device=positions.device)
+    if not C.tracing():  # (inside a trace the op itself refuses tensors off the device, at run time)
+        C.require_device(positions, values, cell)
+    if C.tracing() or _wants_grad(positions, values, cell):
+        c, cit, nsys = _op_inputs(positions, cell, batch_idx, None)
+        if batch_idx is None:
+            return torch.ops.alchemiops._spline_spread_channels(positions, values.to(positions.dtype), c[0], nch, nx, ny, nz, int(spline_order), cit)
+        return torch.ops.alchemiops._batch_spline_spread_channels(positions, values.to(positions.dtype), batch_idx, c, nsys, nch, nx, ny, nz,
+                                                                  int(spline_order), cit)
+    pos, c, cit, bi = _prep(positions, cell, batch_idx, None)
+    nsys = c.shape[0] if bi is not None else 1
+    vals = values.detach().to(pos.dtype).contiguous()
+    mesh = _launch_spread_channels(pos, vals, cit, bi, nsys, (nx, ny, nz), int(spline_order), bi is not None)
+    return mesh if bi is not None else mesh[0]
 
 
 @C.traceable
 def spline_gather_channels(positions: torch.Tensor, mesh: torch.Tensor, cell: torch.Tensor, spline_order: int = 4,
                            batch_idx: torch.Tensor | None = None) -> torch.Tensor:
-    """mesh[(B,) C, nx, ny, nz] -> values[N, C] (spline.py:2863-2910); one scalar gather per channel."""
+    """mesh[(B,) C, nx, ny, nz] -> values[N, C] (spline.py:2863-2910): one kernel for all channels, each channel bit-identical to
+    `spline_gather` of its plane.  Differentiable w.r.t. positions, mesh and cell (`alchemiops::_[batch_]spline_gather_channels`)."""
+    spline_order = C.resolve_spline_order(spline_order)
     nch = mesh.shape[0] if batch_idx is None else mesh.shape[1]
-    cols = [spline_gather(positions, mesh[ch] if batch_idx is None else mesh[:, ch], cell, spline_order, batch_idx) for ch in range(nch)]
-    if not cols:
-        return torch.zeros((positions.shape[0], 0), dtype=positions.dtype, device=positions.device)
-    return torch.stack(cols, dim=1)
+    if nch == 0 or positions.shape[0] == 0:
+        return torch.zeros((positions.shape[0], nch), dtype=positions.dtype, device=positions.device)
+    if not C.tracing():
+        C.require_device(positions, mesh, cell)
+    if C.tracing() or _wants_grad(positions, mesh, cell):
+        c, cit, _ = _op_inputs(positions, cell, batch_idx, None)
+        if batch_idx is None:
+            return torch.ops.alchemiops._spline_gather_channels(positions, mesh.to(positions.dtype), c[0], int(spline_order), cit)
+        return torch.ops.alchemiops._batch_spline_gather_channels(positions, mesh.to(positions.dtype), batch_idx, c, int(spline_order), cit)
+    pos, c, cit, bi = _prep(positions, cell, batch_idx, None)
+    m = mesh.detach().to(pos.dtype).contiguous()
+    return _launch_gather_channels(pos, m if bi is not None else m.unsqueeze(0), cit, bi, int(spline_order))
 
 
 def _bspline_modulus_sq(n: int, order: int, device) -> torch.Tensor:
