@@ -260,6 +260,28 @@ int mi_d3_packed_cn(const void* positions, const int32_t* numbers, int n_atoms, 
                     void* workspace, size_t workspace_bytes, const void* packed_list, size_t packed_bytes, const void* cn_block, size_t cn_bytes,
                     int verify_stride, int verify_phase, void* stream);
 
+/* ---- DFT-D3 three-body (Axilrod-Teller-Muto) term --------------------------------------------------
+ * No reference counterpart (its dftd3 is two-body only).  For every unordered triple of distinct atom images A, B, C whose three distances
+ * are all < three_body_cutoff:  E_ABC = s9 sqrt(C6_AB C6_AC C6_BC) ang fdamp,  ang = (3 cosA cosB cosC + 1) / (r_AB r_AC r_BC)^3,
+ * fdamp = 1 / (1 + 6 (R0_AB R0_AC R0_BC / (r_AB r_AC r_BC))^(alpha / 3)),  R0_XY = a1 sqrt(3 r4r2_X r4r2_Y) + a2,  C6_XY = mi_d3's own
+ * interpolation with mi_d3's coordination numbers (summed over ALL stored entries of the list).  Outputs are the three-body contribution
+ * alone, in mi_d3's units, dtypes and virial convention, so they add to mi_d3's: energy per system (each triple once per unit cell),
+ * forces = -dE/dr including the path through the coordination numbers, virial.  params->s6 / s8 / s5_* are not used.
+ * The list (either layout, as for mi_d3) must be a FULL list (every pair stored in both rows) with a cutoff >= three_body_cutoff; entries
+ * beyond three_body_cutoff only count for the coordination numbers.  Reads the caller's arrays: there is no packed-companion variant.
+ * After the call the n_atoms uint32 at byte mi_d3_atm_visits_offset(...) of the workspace hold, per centre atom, the number of triangles
+ * visited from it (each triangle is visited from its three vertices; a diagnostic for benchmarks).  mi_d3_atm_tile(): neighbours inside
+ * three_body_cutoff a row may have before the triple pass works tile by tile (results do not depend on it).                              */
+size_t mi_d3_atm_workspace_bytes(int n_atoms, int n_systems, int nz);
+size_t mi_d3_atm_visits_offset(int n_atoms, int n_systems, int nz);
+int mi_d3_atm_tile(void);
+int mi_d3_atm(const void* positions, const int32_t* numbers, int n_atoms, int dtype,
+              const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr /* NULL => matrix layout */,
+              int max_neighbors, int fill_value, const void* cell, const int32_t* batch_idx, int n_systems,
+              const mi_d3_params* params /* [host] */, float s9, float alpha, float three_body_cutoff, int compute_virial,
+              float* energy /*[n_systems]*/, float* forces /*[n_atoms,3]*/, float* virial /*[n_systems,3,3] or NULL*/,
+              void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Ewald real space -----------------------------------------------------------------------
  * Replaces the 12 alchemiops::_[batch_]ewald_real_space_* ops (ewald.py:263-1365; kernels
  * ewald_kernels.py:266-1495): erfc(A&S 7.1.26)-damped pair sum over the stored neighbour entries.

@@ -1611,6 +1611,8 @@ int d3_impl(const T* pos, const int* numbers, int N, const int* idx, const int* 
   return MI_OK;
 }
 
+#include "d3_atm.h"  // the three-body (Axilrod-Teller-Muto) term: triple pass + driver, on the kernels above
+
 }  // namespace
 
 extern "C" {
@@ -1700,6 +1702,43 @@ int mi_d3_packed_cn(const void* positions, const int32_t* numbers, int n_atoms, 
   return d3_entry(positions, numbers, n_atoms, dtype, neighbor_matrix, neighbor_matrix_shifts, nullptr, max_neighbors, 0, fill_value, cell, batch_idx,
                   n_systems, params, compute_virial, energy, forces, coord_num, virial, workspace, workspace_bytes, stream, packed_list, cn_block,
                   verify_stride, verify_phase);
+}
+
+size_t mi_d3_atm_workspace_bytes(int n_atoms, int n_systems, int nz) {
+  if (n_atoms < 0 || nz < 1 || n_systems < 1) return 0;
+  return d3_atm_layout(n_atoms, nz, MI_F64, n_systems).total;  // sized for the wider dtype
+}
+
+size_t mi_d3_atm_visits_offset(int n_atoms, int n_systems, int nz) {
+  if (n_atoms < 0 || nz < 1 || n_systems < 1) return 0;
+  return d3_atm_layout(n_atoms, nz, MI_F64, n_systems).visits;
+}
+
+int mi_d3_atm_tile(void) { return D3_ATM_TILE; }
+
+int mi_d3_atm(const void* positions, const int32_t* numbers, int n_atoms, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
+              const int32_t* neighbor_ptr, int max_neighbors, int fill_value, const void* cell, const int32_t* batch_idx, int n_systems,
+              const mi_d3_params* params, float s9, float alpha, float three_body_cutoff, int compute_virial, float* energy, float* forces,
+              float* virial, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
+  MI_REQUIRE(n_atoms >= 0 && n_systems >= 1, "sizes");
+  if (n_atoms == 0) return MI_OK;
+  MI_REQUIRE(positions && numbers && idx_j && params && energy && forces && workspace, "null pointer");
+  MI_REQUIRE(params->rcov && params->r4r2 && params->c6ab && params->cn_ref && params->nz >= 2, "D3 parameter tables");
+  MI_REQUIRE(!compute_virial || virial, "virial output");
+  MI_REQUIRE(three_body_cutoff > 0.0f && alpha > 0.0f, "three_body_cutoff and alpha must be positive");
+  MI_REQUIRE(neighbor_ptr != nullptr || max_neighbors > 0, "max_neighbors");
+  // the layout is laid out for the wider dtype whatever `dtype` is, so that mi_d3_atm_visits_offset does not depend on it
+  const D3AtmLayout L = d3_atm_layout(n_atoms, params->nz, MI_F64, n_systems);
+  if (workspace_bytes < L.total) { mi_set_error("workspace too small: %zu < %zu", workspace_bytes, L.total); return MI_EWORKSPACE; }
+  hipStream_t st = (hipStream_t)stream;
+  const bool csr = neighbor_ptr != nullptr;
+#define MI_D3_ATM_CALL(T_, CSR_)                                                                                                                  \
+  return d3_atm_impl<T_, CSR_>((const T_*)positions, numbers, n_atoms, idx_j, unit_shifts, neighbor_ptr, max_neighbors, fill_value, (const T_*)cell, \
+                               batch_idx, n_systems, params, s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial, (char*)workspace, L, st)
+  if (dtype == MI_F32) { if (csr) MI_D3_ATM_CALL(float, true); else MI_D3_ATM_CALL(float, false); }
+  else { if (csr) MI_D3_ATM_CALL(double, true); else MI_D3_ATM_CALL(double, false); }
+#undef MI_D3_ATM_CALL
 }
 
 }  // extern "C"

@@ -69,6 +69,16 @@ def lib() -> ctypes.CDLL:
             L.mi_d3_workspace_bytes_packed.argtypes = [ctypes.c_int] * 4
             L.mi_d3_workspace_bytes_entries.restype = ctypes.c_size_t
             L.mi_d3_workspace_bytes_entries.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong]
+        if hasattr(L, "mi_d3_atm"):  # the three-body (Axilrod-Teller-Muto) term
+            for name in ("mi_d3_atm_workspace_bytes", "mi_d3_atm_visits_offset"):
+                getattr(L, name).restype = ctypes.c_size_t
+                getattr(L, name).argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+            L.mi_d3_atm_tile.restype = ctypes.c_int
+            L.mi_d3_atm_tile.argtypes = []
+            L.mi_d3_atm.restype = ctypes.c_int
+            L.mi_d3_atm.argtypes = ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_float,
+                                     ctypes.c_float, ctypes.c_float, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_size_t, ctypes.c_void_p])
         # the virial entry points (forward-only -dE/d(strain) of the Ewald / PME sums)
         vp, i, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
         L.mi_ewald_real_virial.restype = i

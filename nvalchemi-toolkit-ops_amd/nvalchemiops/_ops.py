@@ -5,6 +5,7 @@ need an opaque, mutation-annotated op -- finds the same ops as in the reference:
     nvalchemiops::build_cell_list / ::query_cell_list               (cell_list.py:725-736, 892-895)
     nvalchemiops::batch_build_cell_list / ::batch_query_cell_list   (batch_cell_list.py:739-749, 915-918)
     nvalchemiops::dftd3_nm / ::dftd3_nl                             (dftd3.py:1792-1795, 2125-2128)
+    nvalchemiops::dftd3_atm_nm / ::dftd3_atm_nl                     (this build's own: the three-body term, same shape as the two above)
 
     nvalchemiops::_cell_list_needs_rebuild / ::_neighbor_list_needs_rebuild   (rebuild_detection.py:258, :386)
 
@@ -124,6 +125,41 @@ def _dftd3_nl_op(positions: torch.Tensor, numbers: torch.Tensor, idx_j: torch.Te
         _d3._launch(positions, numbers, C.i32(idx_j), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, energy.shape[0],
                     (covalent_radii, r4r2, c6_reference, coord_num_ref), _d3_scalars(a1, a2, s6, s8, k1, k3, s5_smoothing_on, s5_smoothing_off),
                     compute_virial, energy, forces, coord_num, virial)
+
+
+@torch.library.custom_op("nvalchemiops::dftd3_atm_nm", mutates_args=("energy", "forces", "virial"))
+def _dftd3_atm_nm_op(positions: torch.Tensor, numbers: torch.Tensor, neighbor_matrix: torch.Tensor, covalent_radii: torch.Tensor,
+                     r4r2: torch.Tensor, c6_reference: torch.Tensor, coord_num_ref: torch.Tensor, a1: float, a2: float,
+                     three_body_cutoff: float, energy: torch.Tensor, forces: torch.Tensor, virial: torch.Tensor, s9: float = 1.0,
+                     alpha: float = 16.0, k1: float = 16.0, k3: float = -4.0, fill_value: int | None = None,
+                     batch_idx: torch.Tensor | None = None, cell: torch.Tensor | None = None,
+                     neighbor_matrix_shifts: torch.Tensor | None = None, compute_virial: bool = False) -> None:
+    """The three-body (Axilrod-Teller-Muto) term on a padded matrix (`mi_d3_atm`; no reference counterpart), mutating like `dftd3_nm`."""
+    n = positions.shape[0]
+    if n == 0:
+        return
+    C.require_device(positions, numbers, neighbor_matrix, batch_idx, energy, forces)
+    nm = C.i32(neighbor_matrix)
+    with _device_of(positions):
+        _d3._launch_atm(positions, numbers, nm, neighbor_matrix_shifts, None, nm.shape[1], n if fill_value is None else fill_value, cell,
+                        batch_idx, energy.shape[0], (covalent_radii, r4r2, c6_reference, coord_num_ref), _d3.atm_scalars(a1, a2, k1, k3), s9,
+                        alpha, three_body_cutoff, compute_virial, energy, forces, virial)
+
+
+@torch.library.custom_op("nvalchemiops::dftd3_atm_nl", mutates_args=("energy", "forces", "virial"))
+def _dftd3_atm_nl_op(positions: torch.Tensor, numbers: torch.Tensor, idx_j: torch.Tensor, neighbor_ptr: torch.Tensor,
+                     covalent_radii: torch.Tensor, r4r2: torch.Tensor, c6_reference: torch.Tensor, coord_num_ref: torch.Tensor, a1: float,
+                     a2: float, three_body_cutoff: float, energy: torch.Tensor, forces: torch.Tensor, virial: torch.Tensor, s9: float = 1.0,
+                     alpha: float = 16.0, k1: float = 16.0, k3: float = -4.0, batch_idx: torch.Tensor | None = None,
+                     cell: torch.Tensor | None = None, unit_shifts: torch.Tensor | None = None, compute_virial: bool = False) -> None:
+    """The three-body term on a CSR list (`mi_d3_atm`), mutating like `dftd3_nl`."""
+    if positions.shape[0] == 0:
+        return
+    C.require_device(positions, numbers, idx_j, neighbor_ptr, batch_idx, energy, forces)
+    with _device_of(positions):
+        _d3._launch_atm(positions, numbers, C.i32(idx_j), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, energy.shape[0],
+                        (covalent_radii, r4r2, c6_reference, coord_num_ref), _d3.atm_scalars(a1, a2, k1, k3), s9, alpha, three_body_cutoff,
+                        compute_virial, energy, forces, virial)
 
 
 # ---- this build's own ops behind the high-level entry points -----------------------------------------------------------------

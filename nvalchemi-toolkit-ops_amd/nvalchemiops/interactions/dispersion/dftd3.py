@@ -1,4 +1,4 @@
-"""DFT-D3(BJ) two-body dispersion -- drop-in for interactions/dispersion/dftd3.py of the reference
+"""DFT-D3(BJ) dispersion: the two-body term `dftd3` -- drop-in for interactions/dispersion/dftd3.py of the reference
 (`D3Parameters` :146-332, `dftd3` :2468-2874; ops `nvalchemiops::dftd3_nm` :1792, `::dftd3_nl` :2125).
 
 Energies [num_systems], forces [N,3], coordination numbers [N] and (optionally) virials [num_systems,3,3], all
@@ -6,6 +6,9 @@ float32, from a FULL neighbour list given either as a padded neighbour matrix or
 `neighbor_ptr`).  The three passes (CN; C6 interpolation + BJ damping + energy + direct force + dE/dCN; chain-rule
 force) run as hand-written HIP kernels (csrc/d3.hip) behind `mi_d3` of the C ABI.  As in the reference, positions
 and cell are detached: explicit forces are returned, there is no autograd through D3.
+
+`dftd3_atm` adds what the reference leaves out ("Two-body only", dftd3.py:119): the three-body Axilrod-Teller-Muto term, returned on its
+own so that a caller adds it to `dftd3`'s outputs (`mi_d3_atm`, csrc/d3_atm.h).
 """
 from __future__ import annotations
 
@@ -125,18 +128,11 @@ def _launch(positions, numbers, idx, shifts, nptr, max_neighbors, fill_value, ce
     C.check(rc, "mi_d3")
 
 
-@C.hybrid
-def dftd3(positions: torch.Tensor, numbers: torch.Tensor, a1: float, a2: float, s8: float, k1: float = 16.0, k3: float = -4.0,
-          s6: float = 1.0, s5_smoothing_on: float = 1e10, s5_smoothing_off: float = 1e10, fill_value: int | None = None,
-          d3_params: D3Parameters | dict[str, torch.Tensor] | None = None, covalent_radii: torch.Tensor | None = None,
-          r4r2: torch.Tensor | None = None, c6_reference: torch.Tensor | None = None, coord_num_ref: torch.Tensor | None = None,
-          batch_idx: torch.Tensor | None = None, cell: torch.Tensor | None = None, neighbor_matrix: torch.Tensor | None = None,
-          neighbor_matrix_shifts: torch.Tensor | None = None, neighbor_list: torch.Tensor | None = None,
-          neighbor_ptr: torch.Tensor | None = None, unit_shifts: torch.Tensor | None = None, compute_virial: bool = False,
-          num_systems: int | None = None, device: str | None = None):
-    """Returns ``(energy[num_systems], forces[N,3], coord_num[N])`` (+ ``virial[num_systems,3,3]`` if ``compute_virial``).
-
-    Validation, parameter resolution, num_systems inference and empty-input behaviour follow dftd3.py:2668-2804."""
+def _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial, missing_functional,
+                       d3_params, covalent_radii, r4r2, c6_reference, coord_num_ref):
+    """Argument validation and parameter resolution shared by `dftd3` and `dftd3_atm` (dftd3.py:2668-2757): the same checks in the same
+    order with the same messages.  `missing_functional`: the message to raise when a required functional parameter is None, or None.
+    Returns (use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref))."""
     use_matrix, use_list = neighbor_matrix is not None, neighbor_list is not None
     if use_matrix and use_list:
         raise ValueError("Cannot provide both neighbor_matrix and neighbor_list. Please provide only one neighbor representation format.")
@@ -149,9 +145,8 @@ def dftd3(positions: torch.Tensor, numbers: torch.Tensor, a1: float, a2: float, 
     if use_list and neighbor_ptr is None:
         raise ValueError("neighbor_ptr must be provided when using neighbor_list format. "
                          "Obtain it from the neighbor list API by setting return_neighbor_list=True.")
-    if a1 is None or a2 is None or s8 is None:
-        raise ValueError("Functional parameters a1, a2, and s8 must be provided. "
-                         "These are functional-dependent parameters required for DFT-D3(BJ) calculations.")
+    if missing_functional:
+        raise ValueError(missing_functional)
     if compute_virial:
         need = "Virial computation requires periodic boundary conditions. "
         if cell is None:
@@ -178,6 +173,29 @@ def dftd3(positions: torch.Tensor, numbers: torch.Tensor, a1: float, a2: float, 
         r4r2 = src["r4r2"] if r4r2 is None else r4r2
         c6_reference = src["c6ab"] if c6_reference is None else c6_reference
         coord_num_ref = src["cn_ref"] if coord_num_ref is None else coord_num_ref
+
+    return use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref)
+
+
+@C.hybrid
+def dftd3(positions: torch.Tensor, numbers: torch.Tensor, a1: float, a2: float, s8: float, k1: float = 16.0, k3: float = -4.0,
+          s6: float = 1.0, s5_smoothing_on: float = 1e10, s5_smoothing_off: float = 1e10, fill_value: int | None = None,
+          d3_params: D3Parameters | dict[str, torch.Tensor] | None = None, covalent_radii: torch.Tensor | None = None,
+          r4r2: torch.Tensor | None = None, c6_reference: torch.Tensor | None = None, coord_num_ref: torch.Tensor | None = None,
+          batch_idx: torch.Tensor | None = None, cell: torch.Tensor | None = None, neighbor_matrix: torch.Tensor | None = None,
+          neighbor_matrix_shifts: torch.Tensor | None = None, neighbor_list: torch.Tensor | None = None,
+          neighbor_ptr: torch.Tensor | None = None, unit_shifts: torch.Tensor | None = None, compute_virial: bool = False,
+          num_systems: int | None = None, device: str | None = None):
+    """Returns ``(energy[num_systems], forces[N,3], coord_num[N])`` (+ ``virial[num_systems,3,3]`` if ``compute_virial``).
+
+    Validation, parameter resolution, num_systems inference and empty-input behaviour follow dftd3.py:2668-2804."""
+    missing = None
+    if a1 is None or a2 is None or s8 is None:
+        missing = ("Functional parameters a1, a2, and s8 must be provided. "
+                   "These are functional-dependent parameters required for DFT-D3(BJ) calculations.")
+    use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref) = _check_and_resolve(
+        neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial, missing, d3_params, covalent_radii,
+        r4r2, c6_reference, coord_num_ref)
 
     n, dev = positions.size(0), positions.device
     f32 = dict(dtype=torch.float32, device=dev)
@@ -228,3 +246,123 @@ def dftd3(positions: torch.Tensor, numbers: torch.Tensor, a1: float, a2: float, 
         _launch(positions, numbers, idx_j, unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, num_systems, tables, scalars,
                 compute_virial, energy, forces, coord_num, virial)
     return (energy, forces, coord_num, virial) if compute_virial else (energy, forces, coord_num)
+
+
+def atm_tile() -> int:
+    """Neighbours inside ``three_body_cutoff`` a row may have before the triple pass of `dftd3_atm` works tile by tile."""
+    return int(C.lib().mi_d3_atm_tile())
+
+
+def _launch_atm(positions, numbers, idx, shifts, nptr, max_neighbors, fill_value, cell, batch_idx, num_systems, tables, scalars, s9, alpha,
+                three_body_cutoff, compute_virial, energy, forces, virial, want_visits=False):
+    """One `mi_d3_atm` call on the caller's arrays.  `want_visits`: return the per-centre triangle-visit counts the triple pass leaves in
+    its workspace (a diagnostic for tools/atm_bench.py)."""
+    dev = positions.device
+    n = positions.shape[0]
+    pos = positions.detach().contiguous()
+    code = C.dtype_code(pos.dtype)
+    f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+    rcov, r4r2, c6ab, cnref = (f32(t) for t in tables)
+    if c6ab.shape[-1] != 5 or c6ab.shape[-2] != 5:
+        raise ValueError("this build supports the standard 5x5 CN interpolation mesh only")
+    par = C.MiD3Params(rcov=rcov.data_ptr(), r4r2=r4r2.data_ptr(), c6ab=c6ab.data_ptr(), cn_ref=cnref.data_ptr(), nz=rcov.shape[0],
+                       **{k: float(v) for k, v in scalars.items()})
+    periodic = cell is not None and shifts is not None
+    cell_t = cell.detach().to(dtype=pos.dtype, device=dev).reshape(-1, 3, 3).contiguous() if periodic else None
+    sh = C.i32(shifts.to(dev)) if periodic else None
+    bi = None if batch_idx is None else C.i32(batch_idx)
+    L = C.lib()
+    if not hasattr(L, "mi_d3_atm"):
+        raise C.NativeLibraryError("libnvalchemiops_hip.so does not export mi_d3_atm: rebuild it (build_native.py)")
+    ws_bytes = int(L.mi_d3_atm_workspace_bytes(n, num_systems, rcov.shape[0]))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    z = C.i32(numbers)  # converted tensors stay referenced until the launch is enqueued
+    rc = L.mi_d3_atm(C.ptr(pos), C.ptr(z), n, code, C.ptr(idx), C.ptr(sh), C.ptr(nptr), int(max_neighbors), int(fill_value), C.ptr(cell_t),
+                     C.ptr(bi), int(num_systems), ctypes.byref(par), float(s9), float(alpha), float(three_body_cutoff), int(bool(compute_virial)),
+                     C.ptr(energy), C.ptr(forces), C.ptr(virial if compute_virial else None), C.ptr(ws), ctypes.c_size_t(ws_bytes),
+                     C.stream_of(pos))
+    C.check(rc, "mi_d3_atm")
+    if want_visits:
+        off = int(L.mi_d3_atm_visits_offset(n, num_systems, rcov.shape[0]))
+        return ws[off:off + 4 * n].view(torch.int32).clone()
+    return None
+
+
+@C.hybrid
+def dftd3_atm(positions: torch.Tensor, numbers: torch.Tensor, a1: float, a2: float, three_body_cutoff: float, s9: float = 1.0,
+              alpha: float = 16.0, k1: float = 16.0, k3: float = -4.0, fill_value: int | None = None,
+              d3_params: D3Parameters | dict[str, torch.Tensor] | None = None, covalent_radii: torch.Tensor | None = None,
+              r4r2: torch.Tensor | None = None, c6_reference: torch.Tensor | None = None, coord_num_ref: torch.Tensor | None = None,
+              batch_idx: torch.Tensor | None = None, cell: torch.Tensor | None = None, neighbor_matrix: torch.Tensor | None = None,
+              neighbor_matrix_shifts: torch.Tensor | None = None, neighbor_list: torch.Tensor | None = None,
+              neighbor_ptr: torch.Tensor | None = None, unit_shifts: torch.Tensor | None = None, compute_virial: bool = False,
+              num_systems: int | None = None):
+    """Three-body (Axilrod-Teller-Muto) dispersion of DFT-D3: returns ``(energy[num_systems], forces[N,3])`` (+ ``virial[num_systems,3,3]``
+    if ``compute_virial``) of the three-body term ALONE, float32, in the units and the virial convention of `dftd3`, so that a caller adds
+    them to `dftd3`'s outputs.
+
+    For every unordered triple of distinct atom images A, B, C whose three distances are all ``< three_body_cutoff``::
+
+        E_ABC = s9 * sqrt(C6_AB C6_AC C6_BC) * (3 cosA cosB cosC + 1) / (r_AB r_AC r_BC)^3 / (1 + 6 (R0_AB R0_AC R0_BC / (r_AB r_AC r_BC))^(alpha/3))
+
+    with ``R0_XY = a1 sqrt(3 r4r2_X r4r2_Y) + a2`` and C6_XY the coordination-number interpolation of `dftd3`, evaluated with the
+    coordination numbers `dftd3` returns for the same list (summed over ALL its entries).  A triple counts once per unit cell; forces
+    include the path through the coordination numbers.  ``alpha = 16`` is the original D3 damping exponent (some codes use 14).
+
+    Requirements on the list: it is a FULL list (every pair stored in both rows: what ``neighbor_list()`` / ``cell_list()`` return without
+    ``half_fill``) and its cutoff is at least ``three_body_cutoff``.  Entries beyond ``three_body_cutoff`` are part of no triple (they still
+    count for the coordination numbers).  A periodic list may hold an atom's own images and several images of one neighbour: those are
+    distinct vertices.  Argument names, parameter resolution, validation, ``num_systems`` inference and empty-input behaviour are `dftd3`'s."""
+    missing = None
+    if a1 is None or a2 is None:
+        missing = ("Functional parameters a1 and a2 must be provided. "
+                   "These are functional-dependent parameters required for DFT-D3(BJ) calculations.")
+    elif three_body_cutoff is None:
+        missing = "three_body_cutoff must be provided: the distance below which all three sides of a triple must lie."
+    elif not three_body_cutoff > 0:
+        missing = f"three_body_cutoff must be positive, got {three_body_cutoff}"
+    elif not alpha > 0:
+        missing = f"alpha must be positive, got {alpha}"
+    use_matrix, use_list, tables = _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell,
+                                                      compute_virial, missing, d3_params, covalent_radii, r4r2, c6_reference, coord_num_ref)
+    n, dev = positions.size(0), positions.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    if n == 0:
+        nsys = 1 if (batch_idx is None or batch_idx.numel() == 0) else int(batch_idx.max().item()) + 1
+        out = (torch.zeros(nsys, **f32), torch.zeros((0, 3), **f32))
+        return out + (torch.zeros((0, 3, 3), **f32),) if compute_virial else out
+    if num_systems is None:
+        if batch_idx is None:
+            num_systems = 1
+        elif cell is not None:
+            num_systems = cell.size(0)
+        else:
+            num_systems = int(batch_idx.max().item()) + 1
+    energy = torch.empty(num_systems, **f32)  # written for every system inside mi_d3_atm
+    forces = torch.empty((n, 3), **f32)
+    virial = torch.empty((num_systems, 3, 3), **f32) if compute_virial else torch.zeros((0, 3, 3), **f32)
+    if C.tracing():
+        if use_matrix:
+            torch.ops.nvalchemiops.dftd3_atm_nm(positions, numbers, neighbor_matrix, tables[0], tables[1], tables[2], tables[3], a1, a2,
+                                                three_body_cutoff, energy, forces, virial, s9, alpha, k1, k3, fill_value, batch_idx, cell,
+                                                neighbor_matrix_shifts, compute_virial)
+        else:
+            torch.ops.nvalchemiops.dftd3_atm_nl(positions, numbers, neighbor_list[1], neighbor_ptr, tables[0], tables[1], tables[2], tables[3],
+                                                a1, a2, three_body_cutoff, energy, forces, virial, s9, alpha, k1, k3, batch_idx, cell, unit_shifts,
+                                                compute_virial)
+        return (energy, forces, virial) if compute_virial else (energy, forces)
+    C.require_device(positions, numbers, neighbor_matrix, neighbor_list, neighbor_ptr, batch_idx)
+    scalars = atm_scalars(a1, a2, k1, k3)
+    if use_matrix:
+        nm = C.i32(neighbor_matrix)
+        _launch_atm(positions, numbers, nm, neighbor_matrix_shifts, None, nm.size(1), n if fill_value is None else fill_value, cell, batch_idx,
+                    num_systems, tables, scalars, s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial)
+    else:
+        _launch_atm(positions, numbers, C.i32(neighbor_list[1]), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, num_systems, tables,
+                    scalars, s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial)
+    return (energy, forces, virial) if compute_virial else (energy, forces)
+
+
+def atm_scalars(a1, a2, k1, k3):
+    """`mi_d3_params` scalars of a three-body call: the two-body-only ones (s6, s8, the S5 window) are not read."""
+    return dict(a1=a1, a2=a2, s6=0.0, s8=0.0, k1=k1, k3=k3, s5_on=1e10, s5_off=1e10)
