@@ -260,6 +260,35 @@ int mi_d3_packed_cn(const void* positions, const int32_t* numbers, int n_atoms, 
                     void* workspace, size_t workspace_bytes, const void* packed_list, size_t packed_bytes, const void* cn_block, size_t cn_bytes,
                     int verify_stride, int verify_phase, void* stream);
 
+/* ---- DFT-D3 with zero damping: D3(0) and D3M(0) ----------------------------------------------------
+ * No reference counterpart (its dftd3 has the BJ damping only).  mi_d3 with the damping function of the original D3 parametrisation:
+ *   E_ij = -C6_ij(CN_i, CN_j) [s6 f_6(r) / r^6 + s8 q f_8(r) / r^8] sw(r),   q = 3 r4r2_i r4r2_j,
+ *   f_n(r) = 1 / (1 + 6 (r / (rs_n R0) + beta R0)^(-alpha_n)),   alpha_6 = alpha, alpha_8 = alpha + 2,   R0 = r0ab[Z_i, Z_j]
+ * (beta = 0: D3(0); beta != 0: the modified form D3M(0)).  Everything else -- the coordination numbers, the C6 interpolation, the 1/2 per
+ * stored directed pair, the c6 < 1e-12 skip, the s5 switch, forces including the path through the coordination numbers, the virial, the
+ * outputs and the workspace (mi_d3_workspace_bytes*: the species-pair constants reuse the room the BJ ones take) -- is mi_d3's.
+ * params->a1 / a2 are ignored.  r0ab is the symmetric [nz,nz] table of pair cutoff radii in Bohr (device memory, float32; row / column 0
+ * is padding); a pair whose entry is <= 0 contributes nothing (energy, force, virial and dE/dCN are zero for it).  alpha == 14 takes the
+ * powers by repeated squaring, any other exponent one log2 / exp2 pair per power.  A close contact (x^-alpha overflowing fp32) gives f = 0
+ * and a zero derivative, not a NaN.  Requires rs6 > 0, rs8 > 0, alpha > 0.                                                               */
+typedef struct {
+  float rs6, rs8, alpha, beta;
+  const float* r0ab; /* [nz,nz] */
+} mi_d3_zero_params;
+
+int mi_d3_zero(const void* positions, const int32_t* numbers, int n_atoms, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
+               const int32_t* neighbor_ptr, int max_neighbors, long long n_list_entries, int fill_value, const void* cell,
+               const int32_t* batch_idx, int n_systems, const mi_d3_params* params /* [host] */, const mi_d3_zero_params* zero /* [host] */,
+               int compute_virial, float* energy, float* forces, float* coord_num, float* virial, void* workspace, size_t workspace_bytes,
+               void* stream);
+
+/* mi_d3_packed_cn (companion, adoption of the search's coordination numbers, sampled check: all as described there) with zero damping.  */
+int mi_d3_zero_packed_cn(const void* positions, const int32_t* numbers, int n_atoms, int dtype, const int32_t* neighbor_matrix,
+                         const int32_t* neighbor_matrix_shifts, int max_neighbors, int fill_value, const void* cell, const int32_t* batch_idx,
+                         int n_systems, const mi_d3_params* params, const mi_d3_zero_params* zero, int compute_virial, float* energy,
+                         float* forces, float* coord_num, float* virial, void* workspace, size_t workspace_bytes, const void* packed_list,
+                         size_t packed_bytes, const void* cn_block, size_t cn_bytes, int verify_stride, int verify_phase, void* stream);
+
 /* ---- DFT-D3 three-body (Axilrod-Teller-Muto) term --------------------------------------------------
  * No reference counterpart (its dftd3 is two-body only).  For every unordered triple of distinct atom images A, B, C whose three distances
  * are all < three_body_cutoff:  E_ABC = s9 sqrt(C6_AB C6_AC C6_BC) ang fdamp,  ang = (3 cosA cosB cosC + 1) / (r_AB r_AC r_BC)^3,
@@ -281,6 +310,17 @@ int mi_d3_atm(const void* positions, const int32_t* numbers, int n_atoms, int dt
               const mi_d3_params* params /* [host] */, float s9, float alpha, float three_body_cutoff, int compute_virial,
               float* energy /*[n_systems]*/, float* forces /*[n_atoms,3]*/, float* virial /*[n_systems,3,3] or NULL*/,
               void* workspace, size_t workspace_bytes, void* stream);
+
+/* mi_d3_atm with the radii zero damping conventionally pairs it with: R0_XY = rs9 r0ab[Z_X, Z_Y] (rs9 = 4/3 by convention; r0ab as for
+ * mi_d3_zero: symmetric [nz,nz], Bohr, device memory, float32) instead of a1 sqrt(3 r4r2_X r4r2_Y) + a2.  params->a1 / a2 are ignored.  A
+ * triple with a pair whose r0ab entry is <= 0 contributes nothing.  Everything else -- arguments, outputs, list requirements, workspace
+ * (mi_d3_atm_workspace_bytes), the visit counters -- is mi_d3_atm's.  Requires rs9 > 0.                                                 */
+int mi_d3_zero_atm(const void* positions, const int32_t* numbers, int n_atoms, int dtype,
+                   const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr /* NULL => matrix layout */,
+                   int max_neighbors, int fill_value, const void* cell, const int32_t* batch_idx, int n_systems,
+                   const mi_d3_params* params /* [host] */, float s9, float alpha, float three_body_cutoff, float rs9,
+                   const float* r0ab /* [nz,nz] */, int compute_virial, float* energy, float* forces, float* virial,
+                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Ewald real space -----------------------------------------------------------------------
  * Replaces the 12 alchemiops::_[batch_]ewald_real_space_* ops (ewald.py:263-1365; kernels

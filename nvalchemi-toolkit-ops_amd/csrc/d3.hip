@@ -18,6 +18,8 @@
 //   * cn / chain walks: 8 waves per block in lock-step (one barrier per trip) so that consecutive atoms share the cache lines
 //     their gathers pull into L1; all walks are software-pipelined three deep with predicated (not branched) validity.
 //   * per-system energy / virial: per-atom values, fp64 slab sums, one atomic per system change per wave, rounded once.
+//   * zero damping, D3(0) / D3M(0) (mi_d3_zero*; no reference counterpart): a compile-time damping kind of the energy pass (DAMP) and of the
+//     triple pass (d3_atm.h); every other kernel is shared.  See D3ZeroSpec and the damping block of d3_energy_body.
 #include <type_traits>
 #include <mutex>
 
@@ -96,10 +98,31 @@ __device__ __forceinline__ float d3_crec_value(float w, const D3CRec& f) { retur
 
 struct D3Species;
 __device__ __forceinline__ int d3_species_count(const D3Species* info);
+// Zero damping (mi_d3_zero): f_n(r) = 1 / (1 + 6 x_n^-alpha_n), x_n = r / (rs_n R0) + beta R0, R0 = r0ab[Z_i, Z_j].  The pair loop never sees
+// R0 itself: the table kernels turn every species pair's radius into D3ZeroPair = {1 / (rs6 R0), 1 / (rs8 R0), beta R0}, so x_n is ONE fma and
+// the derivative alpha_n f (1 - f) / (r + beta rs_n R0^2) = alpha_n f (1 - f) (1 / (rs_n R0)) / x_n needs nothing else.  R0 <= 0 (padding row /
+// column, an element the table does not cover) is stored as zeros in both reciprocals: the pair then contributes nothing.
+// `r0ab` == NULL: BJ damping, the tables carry zeros where these values would go.
+struct D3ZeroSpec { const float* r0ab; float irs6, irs8, beta; };  // irs_n = 1 / rs_n
+struct D3ZeroPair { float i6, i8, bR; };
+__device__ __forceinline__ D3ZeroPair d3_zero_pair(const D3ZeroSpec& Z, int zi, int zj, int nz) {
+  const float R0 = Z.r0ab[(size_t)zi * nz + zj];
+  const bool ok = R0 > 0.0f;  // (false for NaN)
+  D3ZeroPair p;
+  p.i6 = ok ? Z.irs6 / R0 : 0.0f; p.i8 = ok ? Z.irs8 / R0 : 0.0f; p.bR = ok ? Z.beta * R0 : 0.0f;
+  return p;
+}
+// where the three values ride in the 25-entry {c6, cn_ref_i, cn_ref_j, w} tables of the general interpolation (MODE 0 / 1): the spare w of
+// entries 0, 1, 2 of the species pair
+__device__ __forceinline__ float d3_zero_w(const D3ZeroSpec& Z, int zi, int zj, int nz, int pq) {
+  if (Z.r0ab == nullptr || pq > 2) return 0.0f;
+  const D3ZeroPair p = d3_zero_pair(Z, zi, zj, nz);
+  return pq == 0 ? p.i6 : (pq == 1 ? p.i8 : p.bR);
+}
 // (round 6: the blocks behind the atom and companion-check blocks of d3_pack_atoms_kernel; a launch of its own before)
-struct D3Tables { const float* c6ab; const float* cnref; int nz; const D3Species* info; float4* tab; int first_block; };
+struct D3Tables { const float* c6ab; const float* cnref; int nz; const D3Species* info; float4* tab; int first_block; D3ZeroSpec zero; };
 __device__ __forceinline__ void d3_pack_tables_body(const float* __restrict__ c6ab, const float* __restrict__ cnref, int nz, const D3Species* __restrict__ info,
-                                      float4* __restrict__ tab, long long vblock) {
+                                      float4* __restrict__ tab, long long vblock, const D3ZeroSpec& zero) {
   if (d3_species_count(info) <= 16) return;  // the global table is only read by the > 16 species variant of the energy pass
   const long long t = vblock * blockDim.x + threadIdx.x;
   const long long total = (long long)nz * nz * 25;
@@ -110,7 +133,7 @@ __device__ __forceinline__ void d3_pack_tables_body(const float* __restrict__ c6
   const float c6 = c6ab[t];
   const float ci = cnref[t];
   const float cj = cnref[(((long long)zj * nz + zi) * 5 + q) * 5 + p];
-  tab[t] = make_float4(c6, ci, cj, 0.0f);
+  tab[t] = make_float4(c6, ci, cj, d3_zero_w(zero, zi, zj, nz, pq));
 }
 
 template <class T> struct PairGeom { float r, rinv, rx, ry, rz; bool ok; };
@@ -239,7 +262,7 @@ __global__ void d3_pack_atoms_kernel(const T* __restrict__ pos, const int* __res
                                      const int* __restrict__ inv, typename Vec4<T>::type* __restrict__ apos_s, float4* __restrict__ aaux_s,
                                      typename Vec4<T>::type* __restrict__ acn, D3Guard G, D3Tables TB, float4* __restrict__ crec) {
   if ((int)blockIdx.x >= TB.first_block) {  // ---- the global species-pair table (only built for > 16 species)
-    d3_pack_tables_body(TB.c6ab, TB.cnref, TB.nz, TB.info, TB.tab, (long long)blockIdx.x - TB.first_block);
+    d3_pack_tables_body(TB.c6ab, TB.cnref, TB.nz, TB.info, TB.tab, (long long)blockIdx.x - TB.first_block, TB.zero);
     return;
   }
   if ((int)blockIdx.x >= G.atom_blocks) {  // ---- sampled check of the packed companion (block-uniform branch)
@@ -650,7 +673,7 @@ __device__ __forceinline__ void d3_s5(float r, float on, float off, float inv_w,
 
 struct D3Species { int S; int factorized; int pad[2]; };
 __device__ __forceinline__ int d3_species_count(const D3Species* info) { return info->S; }
-#define D3_FROW 44  // factorised block per partner species: 5 c6 rows x 8 floats (b = 0..4 used) + {q, r0^6, r0^8, 0} of the BJ damping
+#define D3_FROW 44  // factorised block per partner species: 5 c6 rows x 8 floats (b = 0..4 used) + {q, r0^6, r0^8, 0} of the BJ damping (zero damping: D3ZeroPair)
 
 __global__ void d3_mark_species_kernel(const int* __restrict__ numbers, int N, int nz, int* __restrict__ present) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -669,7 +692,7 @@ __global__ void d3_mark_species_kernel(const int* __restrict__ numbers, int N, i
 __global__ void d3_compact_species_kernel(const int* __restrict__ present, const float* __restrict__ c6ab, const float* __restrict__ cnref, int nz,
                                           int* __restrict__ smap, D3Species* __restrict__ info, float4* __restrict__ ctab,
                                           float* __restrict__ ftab, float* __restrict__ fcr, float k3, const float* __restrict__ r4r2,
-                                          float a1, float a2, const float* __restrict__ rcov, float* __restrict__ crc) {
+                                          float a1, float a2, const float* __restrict__ rcov, float* __restrict__ crc, D3ZeroSpec zero) {
   __shared__ int zlist[D3_SMAX];
   __shared__ int count;
   __shared__ int fact_ok;
@@ -691,7 +714,7 @@ __global__ void d3_compact_species_kernel(const int* __restrict__ present, const
     const int pq = k % 25, p = pq / 5, q = pq % 5, sj = (k / 25) % S, si = k / (25 * S);
     const int zi = zlist[si], zj = zlist[sj];
     const size_t a = ((size_t)zi * nz + zj) * 25 + pq, b = (((size_t)zj * nz + zi) * 5 + q) * 5 + p;
-    ctab[k] = make_float4(c6ab[a], cnref[a], cnref[b], 0.0f);
+    ctab[k] = make_float4(c6ab[a], cnref[a], cnref[b], d3_zero_w(zero, zi, zj, nz, pq));
     ftab[((size_t)si * S + sj) * D3_FROW + p * 8 + q] = c6ab[a];
     const size_t dii = ((size_t)zi * nz + zi) * 25 + p * 6, djj = ((size_t)zj * nz + zj) * 25 + q * 6;  // (p,p) / (q,q) entries
     const bool valid = c6ab[a] != 0.0f, rect = (c6ab[dii] != 0.0f) && (c6ab[djj] != 0.0f);
@@ -706,6 +729,11 @@ __global__ void d3_compact_species_kernel(const int* __restrict__ present, const
     const float q = 3.0f * r4r2[zlist[k / S]] * r4r2[zlist[k % S]];
     const float r0 = a1 * sqrtf(q) + a2, r02 = r0 * r0, r04 = r02 * r02;
     float* d = ftab + (size_t)k * D3_FROW + 40;
+    if (zero.r0ab != nullptr) {  // zero damping: the same four floats carry {q, 1 / (rs6 R0), 1 / (rs8 R0), beta R0} (D3ZeroPair)
+      const D3ZeroPair zp = d3_zero_pair(zero, zlist[k / S], zlist[k % S], nz);
+      d[0] = q; d[1] = zp.i6; d[2] = zp.i8; d[3] = zp.bR;
+      continue;
+    }
     d[0] = q; d[1] = r04 * r02; d[2] = r04 * r04; d[3] = 0.0f;
   }
   for (int si = threadIdx.x; si < S; si += blockDim.x) {
@@ -905,7 +933,11 @@ __host__ __device__ constexpr int d3_wave_f4(int mode) { return mode == 1 ? D3_S
 // ---- pass 2: energy, direct force, dE/dCN ------------------------------------------------------------
 // MODE 0: global [nz,nz,25] table (> 16 species); 1: general 25-term interpolation from the LDS-staged compact table;
 // 2: factorised interpolation.  All three are launched; the two that do not match the device-side species info exit at once.
-template <class T, bool CSR, int MODE, bool PK>
+// DAMP 0: Becke-Johnson rational damping (mi_d3); 1: zero damping (mi_d3_zero; D3ZeroSpec above, P.a1 then carries alpha and P.a2 is unused).
+// Everything outside the damping block is shared; the DAMP 0 instantiations are the code they were before the parameter existed.
+#define D3_DAMP_BJ 0
+#define D3_DAMP_ZERO 1
+template <class T, bool CSR, int MODE, bool PK, int DAMP>
 __device__ __forceinline__ void d3_energy_body(const T* __restrict__ pos, const int* __restrict__ numbers, int N, const int* __restrict__ idx,
                                                         const int* __restrict__ ush, const int* __restrict__ nptr, int M, int fill_value,
                                                         const T* __restrict__ cell, const int* __restrict__ batch_idx, D3Dev P,
@@ -1021,9 +1053,47 @@ __device__ __forceinline__ void d3_energy_body(const T* __restrict__ pos, const 
         d3_c6(cn_i, a0.x, LDS ? my_tab + (code & 0xff) * 25 : tab_i + (size_t)(code >> 8) * 25, P.k3, c6, dci);
       }
       valid = valid && !(c6 < 1e-12f);
-      // `_bj_damping` (dftd3.py:648-687)
+      float q, zi6 = 0.0f, zi8 = 0.0f, zbR = 0.0f;  // zero damping: D3ZeroPair of the species pair
+      if constexpr (DAMP == D3_DAMP_ZERO) {
+        if (MODE == 2) {  // the four floats behind the c6 rows
+          const float4 zp = *reinterpret_cast<const float4*>(my_f + code * D3_FROW + 40);
+          q = zp.x; zi6 = zp.y; zi8 = zp.z; zbR = zp.w;
+        } else {  // the spare word of the first three table entries of the pair (LDS-staged or global, like the c6 they sit next to)
+          const float4* __restrict__ t25 = LDS ? my_tab + (code & 0xff) * 25 : tab_i + (size_t)(code >> 8) * 25;
+          q = 3.0f * r4r2_i * r4r2_j;
+          zi6 = t25[0].w; zi8 = t25[1].w; zbR = t25[2].w;
+        }
+        valid = valid && zi6 > 0.0f;  // r0ab <= 0: the pair contributes nothing
+      }
       const float r = valid ? g.r : 1.0f;
-      float q, r06, r08;
+      float damp, dEdr;
+      if constexpr (DAMP == D3_DAMP_ZERO) {
+        // f_n = 1 / (1 + 6 x_n^-alpha_n),  x_n = r / (rs_n R0) + beta R0;  damp = s6 f_6 / r^6 + s8 q f_8 / r^8
+        // df_n/dr = alpha_n f_n (1 - f_n) / (rs_n R0 x_n): a close contact overflows x^-alpha to +inf, f becomes an exact 0 and so does
+        // its derivative (0 * finite; 1 / x_n <= 1e13 rs_n R0 because r >= 1e-12) -- no inf * 0 anywhere.  f_n / r^n is formed under a
+        // select, so that an overflowed 1 / r^n (r < 4e-7 Bohr) next to f_n = 0 is a zero as well.  Lanes that are not `valid` may hold
+        // NaN here (x = 0); the selects below drop them.
+        const float x6 = fmaf(r, zi6, zbR), x8 = fmaf(r, zi8, zbR);
+        const float xi6 = D3_RCP(x6), xi8 = D3_RCP(x8);
+        const float al6 = P.a1, al8 = P.a1 + 2.0f;
+        float p6, p8;  // x_6^-alpha, x_8^-(alpha + 2)
+        if (al6 == 14.0f) {  // kernel-uniform: the usual exponents 14 / 16 by squaring
+          const float a2_ = xi6 * xi6, a4_ = a2_ * a2_, a8_ = a4_ * a4_;
+          const float b2_ = xi8 * xi8, b4_ = b2_ * b2_, b8_ = b4_ * b4_;
+          p6 = a8_ * a4_ * a2_; p8 = b8_ * b8_;
+        } else {  // any other exponent: one log2 / exp2 pair per power
+          p6 = __builtin_amdgcn_exp2f(-al6 * __builtin_amdgcn_logf(x6));
+          p8 = __builtin_amdgcn_exp2f(-al8 * __builtin_amdgcn_logf(x8));
+        }
+        const float f6 = D3_RCP(fmaf(6.0f, p6, 1.0f)), f8 = D3_RCP(fmaf(6.0f, p8, 1.0f));
+        const float rinv = D3_RCP(r), ri2 = rinv * rinv, ri6 = ri2 * ri2 * ri2, ri8 = ri6 * ri2;
+        const float t6 = f6 > 0.0f ? P.s6 * (f6 * ri6) : 0.0f, t8 = f8 > 0.0f ? (P.s8 * q) * (f8 * ri8) : 0.0f;
+        damp = t6 + t8;
+        const float g6 = fmaf(al6 * (1.0f - f6), zi6 * xi6, -6.0f * rinv), g8 = fmaf(al8 * (1.0f - f8), zi8 * xi8, -8.0f * rinv);
+        dEdr = -c6 * fmaf(t6, g6, t8 * g8);
+      } else {
+      // `_bj_damping` (dftd3.py:648-687)
+      float r06, r08;
       if (MODE == 2) {  // species-pair constants staged with the c6 rows
         const float4 bj = *reinterpret_cast<const float4*>(my_f + code * D3_FROW + 40);
         q = bj.x; r06 = bj.y; r08 = bj.z;
@@ -1035,13 +1105,14 @@ __device__ __forceinline__ void d3_energy_body(const T* __restrict__ pos, const 
       }
       const float r2 = r * r, r4 = r2 * r2, r6 = r4 * r2, r8 = r4 * r4;
       const float i6 = D3_RCP(r6 + r06), i8 = D3_RCP(r8 + r08);
-      const float damp = P.s6 * i6 + P.s8 * q * i8;
+      damp = P.s6 * i6 + P.s8 * q * i8;
       // `_dispersion_energy_force` (dftd3.py:690-731)
-      const float eij = -c6 * damp;
       const float r5 = r4 * r, r7 = r6 * r;
       const float d6 = -6.0f * P.s6 * r5 * i6 * i6;
       const float d8 = -8.0f * P.s8 * q * r7 * i8 * i8;
-      const float dEdr = -c6 * (d6 + d8);
+      dEdr = -c6 * (d6 + d8);
+      }
+      const float eij = -c6 * damp;
       float sw, dsw;
       d3_s5(r, P.s5_on, P.s5_off, P.inv_w, sw, dsw);
       const float esw = valid ? eij * sw : 0.0f;
@@ -1049,6 +1120,10 @@ __device__ __forceinline__ void d3_energy_body(const T* __restrict__ pos, const 
       const float fx = dEsw * (g.rx * g.rinv), fy = dEsw * (g.ry * g.rinv), fz = dEsw * (g.rz * g.rinv);
       Fx += (double)fx; Fy += (double)fy; Fz += (double)fz;
       E += (double)esw;
+      // dE_ij/dCN_i.  The BJ path keeps the reference's form, which leaves the switch out of this term (dftd3.py:1116: with the S5 window on, its
+      // forces are not the exact gradient of its energy); the zero-damping path differentiates the energy it returns, -C6 damp sw
+      if constexpr (DAMP == D3_DAMP_ZERO) dacc += valid ? (double)(-(damp * sw) * dci) : 0.0;
+      else
       dacc += valid ? (double)(-damp * dci) : 0.0;
       if (want_virial) {
         V[0] += fx * g.rx; V[1] += fx * g.ry; V[2] += fx * g.rz;
@@ -1093,10 +1168,10 @@ __device__ __forceinline__ void d3_energy_body(const T* __restrict__ pos, const 
 
 #define D3_ENERGY_PARAMS const T* __restrict__ pos, const int* __restrict__ numbers, int N, const int* __restrict__ idx, const int* __restrict__ ush, const int* __restrict__ nptr, int M, int fill_value, const T* __restrict__ cell, const int* __restrict__ batch_idx, D3Dev P, const float* __restrict__ cn, int want_virial, const int* __restrict__ smap, const D3Species* __restrict__ sinfo, const float4* __restrict__ ctab, const float* __restrict__ ftab, const float* __restrict__ fcr, const typename Vec4<T>::type* __restrict__ apos, const float4* __restrict__ aaux, const float4* __restrict__ aw, float* __restrict__ dEdCN, float* __restrict__ forces, float* __restrict__ e_atom, double* __restrict__ v_atom, const unsigned* __restrict__ pk, const int* __restrict__ pk_flag, const int* __restrict__ inv, const typename Vec4<T>::type* __restrict__ apos_s, const float4* __restrict__ aaux_s, const float4* __restrict__ aw_s, float* __restrict__ dEdCN_s
 #define D3_ENERGY_ARGS pos, numbers, N, idx, ush, nptr, M, fill_value, cell, batch_idx, P, cn, want_virial, smap, sinfo, ctab, ftab, fcr, apos, aaux, aw, dEdCN, forces, e_atom, v_atom, pk, pk_flag, inv, apos_s, aaux_s, aw_s, dEdCN_s, lds_buf
-template <class T, bool CSR, int MODE, bool PK>
+template <class T, bool CSR, int MODE, bool PK, int DAMP>
 __global__ __launch_bounds__(256) void d3_energy_kernel(D3_ENERGY_PARAMS) {
   __shared__ float4 lds_buf[4 * d3_wave_f4(MODE)];
-  d3_energy_body<T, CSR, MODE, PK>(D3_ENERGY_ARGS);
+  d3_energy_body<T, CSR, MODE, PK, DAMP>(D3_ENERGY_ARGS);
 }
 // the fp32 factorised variant is latency-bound once its contraction is cheap (gathers from L2): it fits the register budget of
 // D3_ENERGY_WAVES waves per SIMD without spilling, the other variants would spill under that cap
@@ -1104,10 +1179,10 @@ __global__ __launch_bounds__(256) void d3_energy_kernel(D3_ENERGY_PARAMS) {
 #define D3_ENERGY_WAVES 8  // 63 VGPRs / 78 SGPRs, no scratch (same-box A/B: 5 waves 1.09 ms, 6 waves 0.94, 7 / 8 waves 0.92)
 #endif
 // (the plain-list variants need a few registers more for their decoded pipeline steps: 7 waves / SIMD without scratch instead of 8 with 5-7 spills)
-template <class T, bool CSR, int MODE, bool PK>
+template <class T, bool CSR, int MODE, bool PK, int DAMP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PK ? D3_ENERGY_WAVES : D3_ENERGY_WAVES - 1, PK ? D3_ENERGY_WAVES : D3_ENERGY_WAVES - 1))) void d3_energy_kernel_w5(D3_ENERGY_PARAMS) {
   __shared__ float4 lds_buf[4 * d3_wave_f4(MODE)];
-  d3_energy_body<T, CSR, MODE, PK>(D3_ENERGY_ARGS);
+  d3_energy_body<T, CSR, MODE, PK, DAMP>(D3_ENERGY_ARGS);
 }
 // Everything but the common case in ONE launch behind the packed factorised variant: the packed general / global-table variants and the
 // three plain-list variants (the bodies select themselves on the device-side species info and the packed-list flag; all but at most one
@@ -1116,18 +1191,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PK ? D3_ENE
 // leave at once when the main variant (packed list, factorised interpolation) has done the work -- the common case, where this launch used
 // to cost the dependent chain 14 - 16 us for tens of thousands of blocks that each ran five body prologues.
 #define D3_FALLBACK_GRID 2048
-template <class T, bool CSR>
+template <class T, bool CSR, int DAMP>
 __global__ __launch_bounds__(256) void d3_energy_fallback_kernel(D3_ENERGY_PARAMS, const unsigned* __restrict__ pk_packed, int n_blocks) {
   __shared__ float4 lds_buf[4 * d3_wave_f4(1)];  // one buffer for all bodies (the general form's is the largest): at most one of them works
   if (sinfo->S <= D3_SMAX && sinfo->factorized && *pk_flag == 0) return;  // d3_energy_body<T, CSR, 2, true> took this call
   for (int vb = blockIdx.x; vb < n_blocks; vb += gridDim.x) {
-    d3_energy_body<T, CSR, 1, true>(pos, numbers, N, idx, ush, nptr, M, fill_value, cell, batch_idx, P, cn, want_virial, smap, sinfo, ctab, ftab, fcr, apos, aaux,
+    d3_energy_body<T, CSR, 1, true, DAMP>(pos, numbers, N, idx, ush, nptr, M, fill_value, cell, batch_idx, P, cn, want_virial, smap, sinfo, ctab, ftab, fcr, apos, aaux,
                                     aw, dEdCN, forces, e_atom, v_atom, pk_packed, pk_flag, inv, apos_s, aaux_s, aw_s, dEdCN_s, lds_buf, vb);
-    d3_energy_body<T, CSR, 0, true>(pos, numbers, N, idx, ush, nptr, M, fill_value, cell, batch_idx, P, cn, want_virial, smap, sinfo, ctab, ftab, fcr, apos, aaux,
+    d3_energy_body<T, CSR, 0, true, DAMP>(pos, numbers, N, idx, ush, nptr, M, fill_value, cell, batch_idx, P, cn, want_virial, smap, sinfo, ctab, ftab, fcr, apos, aaux,
                                     aw, dEdCN, forces, e_atom, v_atom, pk_packed, pk_flag, inv, apos_s, aaux_s, aw_s, dEdCN_s, lds_buf, vb);
-    d3_energy_body<T, CSR, 2, false>(D3_ENERGY_ARGS, vb);
-    d3_energy_body<T, CSR, 1, false>(D3_ENERGY_ARGS, vb);
-    d3_energy_body<T, CSR, 0, false>(D3_ENERGY_ARGS, vb);
+    d3_energy_body<T, CSR, 2, false, DAMP>(D3_ENERGY_ARGS, vb);
+    d3_energy_body<T, CSR, 1, false, DAMP>(D3_ENERGY_ARGS, vb);
+    d3_energy_body<T, CSR, 0, false, DAMP>(D3_ENERGY_ARGS, vb);
   }
 }
 #undef D3_ENERGY_ARGS
@@ -1428,11 +1503,11 @@ static void d3_order_publish(const int* d_count, int* h_slot, hipStream_t st) {
   if (h_slot) (void)hipMemcpyAsync(h_slot, d_count, 2 * sizeof(int), hipMemcpyDeviceToHost, st);
 }
 
-template <class T, bool CSR>
+template <class T, bool CSR, int DAMP>
 int d3_impl(const T* pos, const int* numbers, int N, const int* idx, const int* ush, const int* nptr, int M, int fill_value, const T* cell,
             const int* batch_idx, int B, const mi_d3_params* hp, int want_virial, float* energy, float* forces, float* cn, float* virial,
             char* ws, const D3Layout& L, unsigned* pk, long long n_entries, const unsigned* pre, const void* cn_block, int verify_stride, int verify_phase,
-            hipStream_t st) {
+            const mi_d3_zero_params* zp /* DAMP == D3_DAMP_ZERO only */, hipStream_t st) {
   // `pk` (optional, [N*M] words + one flag word in front): packed copy of a periodic padded list, see d3_fetch_pk
   int* pk_flag = nullptr;
   if (pk) { pk_flag = reinterpret_cast<int*>(pk); pk += 64; }
@@ -1482,6 +1557,11 @@ int d3_impl(const T* pos, const int* numbers, int N, const int* idx, const int* 
   D3Dev P;
   P.rcov = hp->rcov; P.r4r2 = hp->r4r2; P.tab = tab; P.nz = hp->nz;
   P.a1 = hp->a1; P.a2 = hp->a2; P.s6 = hp->s6; P.s8 = hp->s8; P.k1 = hp->k1; P.k3 = hp->k3; P.s5_on = hp->s5_on; P.s5_off = hp->s5_off;
+  D3ZeroSpec zero{nullptr, 0.0f, 0.0f, 0.0f};
+  if constexpr (DAMP == D3_DAMP_ZERO) {  // the energy kernels read alpha where the BJ ones read a1; rs6 / rs8 / beta only reach the table kernels
+    P.a1 = zp->alpha; P.a2 = 0.0f;
+    zero = D3ZeroSpec{zp->r0ab, 1.0f / zp->rs6, 1.0f / zp->rs8, zp->beta};
+  }
   // inv_w in double on the host, then cast (dftd3.py:1983-1986)
   P.inv_w = (hp->s5_off > hp->s5_on) ? (float)(1.0 / ((double)hp->s5_off - (double)hp->s5_on)) : 0.0f;
   const char* crec_env = getenv("NVALCHEMIOPS_D3_CHAIN_RECORDS");  // "0": the two-gather chain walk (A/B, tests); read per call like NVALCHEMIOPS_D3_SORT
@@ -1515,7 +1595,7 @@ int d3_impl(const T* pos, const int* numbers, int N, const int* idx, const int* 
   d3_mark_species_kernel<<<mi_blocks(N, 256), 256, 0, st>>>(numbers, N, hp->nz, present);
   MI_LAUNCH_CHECK();
   d3_compact_species_kernel<<<1, 256, 0, st>>>(present, hp->c6ab, hp->cn_ref, hp->nz, smap, sinfo, ctab, ftab, fcr, hp->k3, hp->r4r2, hp->a1, hp->a2, hp->rcov,
-                                               reinterpret_cast<float*>(ws + L.crc));
+                                               reinterpret_cast<float*>(ws + L.crc), zero);
   MI_LAUNCH_CHECK();
   const long long nt = (long long)hp->nz * hp->nz * 25;
   // the search's coordination numbers are taken only in the caller's atom order (the spatial order's CN pass writes its place-coded list anyway)
@@ -1529,7 +1609,7 @@ int d3_impl(const T* pos, const int* numbers, int N, const int* idx, const int* 
     // one wave per sampled row; one block at least: it also forwards the header flag
     verify_blocks = verify_stride > 0 ? mi_blocks(((long long)N + verify_stride - 1) / verify_stride, 4) : 1;
   }
-  const D3Tables TB{hp->c6ab, hp->cn_ref, hp->nz, sinfo, tab, G.atom_blocks + verify_blocks};  // (its blocks leave at once unless > 16 species are present)
+  const D3Tables TB{hp->c6ab, hp->cn_ref, hp->nz, sinfo, tab, G.atom_blocks + verify_blocks, zero};  // (its blocks leave at once unless > 16 species are present)
   d3_pack_atoms_kernel<T><<<G.atom_blocks + verify_blocks + mi_blocks(nt, 256), 256, 0, st>>>(pos, numbers, N, hp->rcov, hp->r4r2, smap, hp->nz, apos, aaux, forces, cn,
                                                                                               dEdCN, e_atom, want_virial ? v_atom : nullptr, inv, apos_s, aaux_s, acn, G, TB, P.crec);
   MI_LAUNCH_CHECK();
@@ -1572,10 +1652,10 @@ int d3_impl(const T* pos, const int* numbers, int N, const int* idx, const int* 
     constexpr bool PK_ = decltype(packed)::value;
     const unsigned* pk_in = PK_ ? pk : nullptr;
     if constexpr (MODE_ == 2 && sizeof(T) == 4)
-      d3_energy_kernel_w5<T, CSR, MODE_, PK_><<<blocks, 256, 0, st>>>(pos, numbers, N, idx, ush, nptr, M, fill_value, cell, batch_idx, P, cn, want_virial,
+      d3_energy_kernel_w5<T, CSR, MODE_, PK_, DAMP><<<blocks, 256, 0, st>>>(pos, numbers, N, idx, ush, nptr, M, fill_value, cell, batch_idx, P, cn, want_virial,
                                                                      smap, sinfo, ctab, ftab, fcr, apos, aaux, aw, dEdCN, forces, e_atom, v_atom, pk_in, pk_flag, inv, apos_s, aaux_s, aw_s, dEdCN_s);
     else
-      d3_energy_kernel<T, CSR, MODE_, PK_><<<blocks, 256, 0, st>>>(pos, numbers, N, idx, ush, nptr, M, fill_value, cell, batch_idx, P, cn, want_virial,
+      d3_energy_kernel<T, CSR, MODE_, PK_, DAMP><<<blocks, 256, 0, st>>>(pos, numbers, N, idx, ush, nptr, M, fill_value, cell, batch_idx, P, cn, want_virial,
                                                                   smap, sinfo, ctab, ftab, fcr, apos, aaux, aw, dEdCN, forces, e_atom, v_atom, pk_in, pk_flag, inv, apos_s, aaux_s, aw_s, dEdCN_s);
   };
   using Plain = std::integral_constant<bool, false>;
@@ -1590,7 +1670,7 @@ int d3_impl(const T* pos, const int* numbers, int N, const int* idx, const int* 
   if (pk) {
     MI_TIMED("d3_energy", st, (launch_energy(std::integral_constant<int, 2>{}, Packed{})));
     MI_LAUNCH_CHECK();
-    d3_energy_fallback_kernel<T, CSR><<<blocks < D3_FALLBACK_GRID ? blocks : D3_FALLBACK_GRID, 256, 0, st>>>(
+    d3_energy_fallback_kernel<T, CSR, DAMP><<<blocks < D3_FALLBACK_GRID ? blocks : D3_FALLBACK_GRID, 256, 0, st>>>(
         pos, numbers, N, idx, ush, nptr, M, fill_value, cell, batch_idx, P, cn, want_virial, smap, sinfo, ctab, ftab, fcr, apos, aaux, aw, dEdCN, forces, e_atom,
         v_atom, nullptr, pk_flag, inv, apos_s, aaux_s, aw_s, dEdCN_s, pk, blocks);
   } else { MI_TIMED("d3_energy", st, (launch_modes(Plain{}))); }
@@ -1637,13 +1717,16 @@ static int d3_entry(const void* positions, const int32_t* numbers, int n_atoms, 
           const int32_t* neighbor_ptr, int max_neighbors, long long n_list_entries, int fill_value, const void* cell,
           const int32_t* batch_idx, int n_systems,
           const mi_d3_params* params, int compute_virial, float* energy, float* forces, float* coord_num, float* virial, void* workspace,
-          size_t workspace_bytes, void* stream, const void* packed_list, const void* cn_block = nullptr, int verify_stride = 64, int verify_phase = 0) {
+          size_t workspace_bytes, void* stream, const void* packed_list, const void* cn_block = nullptr, int verify_stride = 64, int verify_phase = 0,
+          const mi_d3_zero_params* zero = nullptr /* zero damping instead of BJ (mi_d3_zero*) */, bool want_zero = false) {
+  MI_REQUIRE(!want_zero || zero != nullptr, "zero-damping parameters");
   MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
   MI_REQUIRE(n_atoms >= 0 && n_systems >= 1, "sizes");
   if (n_atoms == 0) return MI_OK;
   MI_REQUIRE(positions && numbers && idx_j && params && energy && forces && coord_num && workspace, "null pointer");
   MI_REQUIRE(params->rcov && params->r4r2 && params->c6ab && params->cn_ref && params->nz >= 2, "D3 parameter tables");
   MI_REQUIRE(!compute_virial || virial, "virial output");
+  MI_REQUIRE(!zero || (zero->r0ab && zero->rs6 > 0.0f && zero->rs8 > 0.0f && zero->alpha > 0.0f), "zero damping: r0ab table, rs6 > 0, rs8 > 0, alpha > 0");
   D3Layout L = d3_layout(n_atoms, params->nz, dtype, n_systems);
   if (workspace_bytes < L.total) { mi_set_error("workspace too small: %zu < %zu", workspace_bytes, L.total); return MI_EWORKSPACE; }
   hipStream_t st = (hipStream_t)stream;
@@ -1659,12 +1742,16 @@ static int d3_entry(const void* positions, const int32_t* numbers, int n_atoms, 
   if (cell && unit_shifts && n_entries > 0 && n_atoms < D3_PK_MAX_ATOMS &&
       workspace_bytes >= mi_d3_workspace_bytes_entries(n_atoms, n_systems, params->nz, n_entries))
     pk = reinterpret_cast<unsigned*>((char*)workspace + ((mi_d3_workspace_bytes(n_atoms, n_systems, params->nz) + 255) & ~(size_t)255));
-#define MI_D3_CALL(T_, CSR_)                                                                                                              \
-  return d3_impl<T_, CSR_>((const T_*)positions, numbers, n_atoms, idx_j, unit_shifts, neighbor_ptr, max_neighbors, fill_value, (const T_*)cell, \
+#define MI_D3_CALL(T_, CSR_, DAMP_)                                                                                                       \
+  return d3_impl<T_, CSR_, DAMP_>((const T_*)positions, numbers, n_atoms, idx_j, unit_shifts, neighbor_ptr, max_neighbors, fill_value, (const T_*)cell, \
                            batch_idx, n_systems, params, compute_virial, energy, forces, coord_num, virial, (char*)workspace, L, pk, n_entries,      \
-                           (const unsigned*)packed_list, cn_block, verify_stride, verify_phase, st)
-  if (dtype == MI_F32) { if (csr) MI_D3_CALL(float, true); else MI_D3_CALL(float, false); }
-  else { if (csr) MI_D3_CALL(double, true); else MI_D3_CALL(double, false); }
+                           (const unsigned*)packed_list, cn_block, verify_stride, verify_phase, zero, st)
+  if (zero) {
+    if (dtype == MI_F32) { if (csr) MI_D3_CALL(float, true, D3_DAMP_ZERO); else MI_D3_CALL(float, false, D3_DAMP_ZERO); }
+    else { if (csr) MI_D3_CALL(double, true, D3_DAMP_ZERO); else MI_D3_CALL(double, false, D3_DAMP_ZERO); }
+  }
+  if (dtype == MI_F32) { if (csr) MI_D3_CALL(float, true, D3_DAMP_BJ); else MI_D3_CALL(float, false, D3_DAMP_BJ); }
+  else { if (csr) MI_D3_CALL(double, true, D3_DAMP_BJ); else MI_D3_CALL(double, false, D3_DAMP_BJ); }
 #undef MI_D3_CALL
 }
 
@@ -1704,6 +1791,30 @@ int mi_d3_packed_cn(const void* positions, const int32_t* numbers, int n_atoms, 
                   verify_stride, verify_phase);
 }
 
+int mi_d3_zero(const void* positions, const int32_t* numbers, int n_atoms, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
+               const int32_t* neighbor_ptr, int max_neighbors, long long n_list_entries, int fill_value, const void* cell,
+               const int32_t* batch_idx, int n_systems, const mi_d3_params* params, const mi_d3_zero_params* zero, int compute_virial,
+               float* energy, float* forces, float* coord_num, float* virial, void* workspace, size_t workspace_bytes, void* stream) {
+  return d3_entry(positions, numbers, n_atoms, dtype, idx_j, unit_shifts, neighbor_ptr, max_neighbors, n_list_entries, fill_value, cell, batch_idx,
+                  n_systems, params, compute_virial, energy, forces, coord_num, virial, workspace, workspace_bytes, stream, nullptr, nullptr, 64, 0,
+                  zero, true);
+}
+
+int mi_d3_zero_packed_cn(const void* positions, const int32_t* numbers, int n_atoms, int dtype, const int32_t* neighbor_matrix,
+                         const int32_t* neighbor_matrix_shifts, int max_neighbors, int fill_value, const void* cell, const int32_t* batch_idx,
+                         int n_systems, const mi_d3_params* params, const mi_d3_zero_params* zero, int compute_virial, float* energy, float* forces,
+                         float* coord_num, float* virial, void* workspace, size_t workspace_bytes, const void* packed_list, size_t packed_bytes,
+                         const void* cn_block, size_t cn_bytes, int verify_stride, int verify_phase, void* stream) {
+  MI_REQUIRE(packed_list != nullptr, "packed_list");
+  MI_REQUIRE(max_neighbors > 0 && packed_bytes >= 256 + sizeof(unsigned) * (size_t)n_atoms * (size_t)max_neighbors,
+             "packed_bytes: mi_nl_packed_bytes(n_atoms, max_neighbors)");
+  MI_REQUIRE(!cn_block || cn_bytes >= MI_CN_HEADER_BYTES + sizeof(float) * (size_t)n_atoms, "cn_bytes: mi_nl_cn_bytes(n_atoms)");
+  MI_REQUIRE(verify_stride >= 0 && verify_phase >= 0, "verify_stride / verify_phase");
+  return d3_entry(positions, numbers, n_atoms, dtype, neighbor_matrix, neighbor_matrix_shifts, nullptr, max_neighbors, 0, fill_value, cell, batch_idx,
+                  n_systems, params, compute_virial, energy, forces, coord_num, virial, workspace, workspace_bytes, stream, packed_list, cn_block,
+                  verify_stride, verify_phase, zero, true);
+}
+
 size_t mi_d3_atm_workspace_bytes(int n_atoms, int n_systems, int nz) {
   if (n_atoms < 0 || nz < 1 || n_systems < 1) return 0;
   return d3_atm_layout(n_atoms, nz, MI_F64, n_systems).total;  // sized for the wider dtype
@@ -1716,10 +1827,10 @@ size_t mi_d3_atm_visits_offset(int n_atoms, int n_systems, int nz) {
 
 int mi_d3_atm_tile(void) { return D3_ATM_TILE; }
 
-int mi_d3_atm(const void* positions, const int32_t* numbers, int n_atoms, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
+static int d3_atm_entry(const void* positions, const int32_t* numbers, int n_atoms, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
               const int32_t* neighbor_ptr, int max_neighbors, int fill_value, const void* cell, const int32_t* batch_idx, int n_systems,
               const mi_d3_params* params, float s9, float alpha, float three_body_cutoff, int compute_virial, float* energy, float* forces,
-              float* virial, void* workspace, size_t workspace_bytes, void* stream) {
+              float* virial, void* workspace, size_t workspace_bytes, void* stream, bool zero, float rs9, const float* r0ab) {
   MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
   MI_REQUIRE(n_atoms >= 0 && n_systems >= 1, "sizes");
   if (n_atoms == 0) return MI_OK;
@@ -1728,17 +1839,39 @@ int mi_d3_atm(const void* positions, const int32_t* numbers, int n_atoms, int dt
   MI_REQUIRE(!compute_virial || virial, "virial output");
   MI_REQUIRE(three_body_cutoff > 0.0f && alpha > 0.0f, "three_body_cutoff and alpha must be positive");
   MI_REQUIRE(neighbor_ptr != nullptr || max_neighbors > 0, "max_neighbors");
+  MI_REQUIRE(!zero || (r0ab != nullptr && rs9 > 0.0f), "zero damping: r0ab table, rs9 > 0");
   // the layout is laid out for the wider dtype whatever `dtype` is, so that mi_d3_atm_visits_offset does not depend on it
   const D3AtmLayout L = d3_atm_layout(n_atoms, params->nz, MI_F64, n_systems);
   if (workspace_bytes < L.total) { mi_set_error("workspace too small: %zu < %zu", workspace_bytes, L.total); return MI_EWORKSPACE; }
   hipStream_t st = (hipStream_t)stream;
   const bool csr = neighbor_ptr != nullptr;
-#define MI_D3_ATM_CALL(T_, CSR_)                                                                                                                  \
-  return d3_atm_impl<T_, CSR_>((const T_*)positions, numbers, n_atoms, idx_j, unit_shifts, neighbor_ptr, max_neighbors, fill_value, (const T_*)cell, \
-                               batch_idx, n_systems, params, s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial, (char*)workspace, L, st)
-  if (dtype == MI_F32) { if (csr) MI_D3_ATM_CALL(float, true); else MI_D3_ATM_CALL(float, false); }
-  else { if (csr) MI_D3_ATM_CALL(double, true); else MI_D3_ATM_CALL(double, false); }
+#define MI_D3_ATM_CALL(T_, CSR_, DAMP_)                                                                                                                  \
+  return d3_atm_impl<T_, CSR_, DAMP_>((const T_*)positions, numbers, n_atoms, idx_j, unit_shifts, neighbor_ptr, max_neighbors, fill_value, (const T_*)cell, \
+                               batch_idx, n_systems, params, s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial, (char*)workspace, L, rs9, r0ab, st)
+  if (zero) {
+    if (dtype == MI_F32) { if (csr) MI_D3_ATM_CALL(float, true, D3_DAMP_ZERO); else MI_D3_ATM_CALL(float, false, D3_DAMP_ZERO); }
+    else { if (csr) MI_D3_ATM_CALL(double, true, D3_DAMP_ZERO); else MI_D3_ATM_CALL(double, false, D3_DAMP_ZERO); }
+  }
+  if (dtype == MI_F32) { if (csr) MI_D3_ATM_CALL(float, true, D3_DAMP_BJ); else MI_D3_ATM_CALL(float, false, D3_DAMP_BJ); }
+  else { if (csr) MI_D3_ATM_CALL(double, true, D3_DAMP_BJ); else MI_D3_ATM_CALL(double, false, D3_DAMP_BJ); }
 #undef MI_D3_ATM_CALL
+}
+
+
+int mi_d3_atm(const void* positions, const int32_t* numbers, int n_atoms, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
+              const int32_t* neighbor_ptr, int max_neighbors, int fill_value, const void* cell, const int32_t* batch_idx, int n_systems,
+              const mi_d3_params* params, float s9, float alpha, float three_body_cutoff, int compute_virial, float* energy, float* forces,
+              float* virial, void* workspace, size_t workspace_bytes, void* stream) {
+  return d3_atm_entry(positions, numbers, n_atoms, dtype, idx_j, unit_shifts, neighbor_ptr, max_neighbors, fill_value, cell, batch_idx, n_systems, params,
+                      s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial, workspace, workspace_bytes, stream, false, 0.0f, nullptr);
+}
+
+int mi_d3_zero_atm(const void* positions, const int32_t* numbers, int n_atoms, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
+                   const int32_t* neighbor_ptr, int max_neighbors, int fill_value, const void* cell, const int32_t* batch_idx, int n_systems,
+                   const mi_d3_params* params, float s9, float alpha, float three_body_cutoff, float rs9, const float* r0ab, int compute_virial,
+                   float* energy, float* forces, float* virial, void* workspace, size_t workspace_bytes, void* stream) {
+  return d3_atm_entry(positions, numbers, n_atoms, dtype, idx_j, unit_shifts, neighbor_ptr, max_neighbors, fill_value, cell, batch_idx, n_systems, params,
+                      s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial, workspace, workspace_bytes, stream, true, rs9, r0ab);
 }
 
 }  // extern "C"

@@ -15,6 +15,14 @@
 // of the explicit virial, the FULL explicit force on the centre and the FULL dE/dC6_ij dC6_ij/dCN_i + dE/dC6_ik dC6_ik/dCN_i to the
 // centre's dE/dCN -- complete without a write to j or k.  fp32 per-triple arithmetic, fp64 accumulation, as in the two-body passes.
 // Rows with more kept entries than a tile holds are processed tile pair by tile pair (the row is streamed again per staged tile).
+//
+// DAMP (compile-time, as in the two-body energy pass): D3_DAMP_BJ takes the radii from the BJ parameters as above; D3_DAMP_ZERO
+// (mi_d3_zero_atm) takes R0_XY = rs9 r0ab[Z_X, Z_Y] from the table of pair cutoff radii.  The radius of a species pair rides where its c6
+// does: the table kernels are run with D3ZeroSpec{r0ab, 1, 1, rs9}, whose third value per pair (D3ZeroPair::bR = "beta R0") IS rs9 R0 -- the
+// fourth float behind the factorised c6 rows (in LDS with them for <= D3_ATM_LDS_S species, through L1 otherwise), the spare word of entry 2
+// of the 25-entry tables (MODE 0 / 1).  So the centre-neighbour radius is staged per tile slot as before and the neighbour-neighbour
+// radius is one more read next to the c6 of that pair, indexed by the two species codes the tile already holds; no argument and no LDS is
+// added.  A pair whose radius is <= 0 is stored as 0 and takes every triple it is part of out (its sqrt(C6) is staged / taken as 0).
 #pragma once
 
 #define D3_ATM_TILE 320   // staged records per LDS tile; two tiles + the species table = 40 KB per block: four blocks (16 waves) per CU
@@ -56,7 +64,14 @@ __device__ __forceinline__ float d3_atm_c6_jk(const float (*tp)[D3_ATM_TILE], in
   }
 }
 
-template <class T, bool CSR, int MODE>
+// rs9 r0ab of the pair of two species codes (D3_DAMP_ZERO), from the table the c6 of that pair is read from
+template <int MODE>
+__device__ __forceinline__ float d3_atm_radius(int cp, int cq, int S, int nz, const float* ft, const float4* __restrict__ t25base) {
+  if constexpr (MODE == 2) return ft[(size_t)(cp * S + cq) * D3_FROW + 43];
+  else return t25base[(size_t)(cp * (MODE == 1 ? S : nz) + cq) * 25 + 2].w;
+}
+
+template <class T, bool CSR, int MODE, int DAMP>
 __global__ __launch_bounds__(D3_ATM_WAVES * MI_WAVE) void d3_atm_kernel(
     const T* __restrict__ pos, const int* __restrict__ numbers, int N, const int* __restrict__ idx, const int* __restrict__ ush,
     const int* __restrict__ nptr, int M, int fill_value, const T* __restrict__ cell, const int* __restrict__ batch_idx, D3Dev P, D3Atm A,
@@ -131,10 +146,17 @@ __global__ __launch_bounds__(D3_ATM_WAVES * MI_WAVE) void d3_atm_kernel(
           d3_c6(cn_i, ax.x, t25base + (size_t)(si * (MODE == 1 ? S : P.nz) + cj) * 25, P.k3, c6, dci);
         }
         if (mine) {
-          const bool live = !(c6 < 1e-12f);  // a triple with any C6 < 1e-12 contributes nothing: sqrt(C6) = 0 zeroes every term of it
+          bool live = !(c6 < 1e-12f);  // a triple with any C6 < 1e-12 contributes nothing: sqrt(C6) = 0 zeroes every term of it
+          float r0z = 0.0f;
+          if constexpr (DAMP == D3_DAMP_ZERO) {
+            r0z = d3_atm_radius<MODE>(si, cj, S, P.nz, ftab, t25base);
+            live = live && r0z > 0.0f;  // no radius for this pair: likewise
+          }
           tile[ATM_RX][slot] = g.rx; tile[ATM_RY][slot] = g.ry; tile[ATM_RZ][slot] = g.rz;
           tile[ATM_SC][slot] = live ? D3_SQRT(c6) : 0.0f;
           tile[ATM_G][slot] = live ? dci * D3_RCP(c6) : 0.0f;
+          if constexpr (DAMP == D3_DAMP_ZERO) tile[ATM_R0][slot] = r0z;
+          else
           tile[ATM_R0][slot] = P.a1 * D3_SQRT(3.0f * r4r2_i * ax.y) + P.a2;
           tile[ATM_H][slot] = D3_SQRT(1.73205081f * ax.y);  // h_j h_k = sqrt(3 r4r2_j r4r2_k)
           tile[ATM_CODE][slot] = __int_as_float(cj);
@@ -168,7 +190,12 @@ __global__ __launch_bounds__(D3_ATM_WAVES * MI_WAVE) void d3_atm_kernel(
         if (!(c < A.rc2) || c < 1e-24f) continue;
         ++visits;
         const float c6jk = d3_atm_c6_jk<MODE>(tp, p, tq, q, S, P.nz, ft, t25base, P.k3);
-        const float sjk = c6jk < 1e-12f ? 0.0f : D3_SQRT(c6jk);
+        float sjk = c6jk < 1e-12f ? 0.0f : D3_SQRT(c6jk);
+        float r0jk = 0.0f;
+        if constexpr (DAMP == D3_DAMP_ZERO) {
+          r0jk = d3_atm_radius<MODE>(__float_as_int(tp[ATM_CODE][p]), __float_as_int(tq[ATM_CODE][q]), S, P.nz, ft, t25base);
+          sjk = r0jk > 0.0f ? sjk : 0.0f;
+        }
         const float b = qx * qx + qy * qy + qz * qz;
         // a + b - c = 2 r_ij.r_ik etc.: the three factors as dot products, not as differences of squared lengths
         const float x = 2.0f * (px * qx + py * qy + pz * qz), y = -2.0f * (px * jx + py * jy + pz * jz), z = 2.0f * (qx * jx + qy * jy + qz * jz);
@@ -176,7 +203,10 @@ __global__ __launch_bounds__(D3_ATM_WAVES * MI_WAVE) void d3_atm_kernel(
         const float pinv3 = pinv * pinv * pinv, k5 = 0.375f * pinv3 * pinv * pinv;
         const float yz = y * z, xz = x * z, xy = x * y, nn = xy * z;
         const float ang = fmaf(k5, nn, pinv3);
-        const float r0 = r0p * tq[ATM_R0][q] * fmaf(P.a1, hp * tq[ATM_H][q], P.a2);
+        float r0;
+        if constexpr (DAMP == D3_DAMP_ZERO) r0 = r0p * tq[ATM_R0][q] * r0jk;
+        else
+        r0 = r0p * tq[ATM_R0][q] * fmaf(P.a1, hp * tq[ATM_H][q], P.a2);
         // (R0 / P)^(alpha / 3) with a runtime exponent: one log2 / exp2 pair per triple
         const float t = __builtin_amdgcn_exp2f(alpha3 * __builtin_amdgcn_logf(r0 * pinv));
         const float fd = D3_RCP(fmaf(6.0f, t, 1.0f));
@@ -258,10 +288,10 @@ D3AtmLayout d3_atm_layout(int N, int nz, int dtype, int B) {
   return L;
 }
 
-template <class T, bool CSR>
+template <class T, bool CSR, int DAMP>
 int d3_atm_impl(const T* pos, const int* numbers, int N, const int* idx, const int* ush, const int* nptr, int M, int fill_value, const T* cell,
                 const int* batch_idx, int B, const mi_d3_params* hp, float s9, float alpha, float cutoff, int want_virial, float* energy,
-                float* forces, float* virial, char* ws, const D3AtmLayout& LA, hipStream_t st) {
+                float* forces, float* virial, char* ws, const D3AtmLayout& LA, float rs9, const float* r0ab /* D3_DAMP_ZERO only */, hipStream_t st) {
   const D3Layout& L = LA.base;
   int* gflag = reinterpret_cast<int*>(ws + L.guard + sizeof(unsigned long long) * MI_CN_SLOTS);
   float* dEdCN = reinterpret_cast<float*>(ws + L.dEdCN);
@@ -287,6 +317,8 @@ int d3_atm_impl(const T* pos, const int* numbers, int N, const int* idx, const i
   P.rcov = hp->rcov; P.r4r2 = hp->r4r2; P.tab = tab; P.nz = hp->nz;
   P.a1 = hp->a1; P.a2 = hp->a2; P.s6 = hp->s6; P.s8 = hp->s8; P.k1 = hp->k1; P.k3 = hp->k3; P.s5_on = hp->s5_on; P.s5_off = hp->s5_off;
   P.inv_w = 0.0f;
+  // D3_DAMP_ZERO: every table carries rs9 r0ab of its species pair in the "beta R0" place (see the head of this file)
+  const D3ZeroSpec zero = DAMP == D3_DAMP_ZERO ? D3ZeroSpec{r0ab, 1.0f, 1.0f, rs9} : D3ZeroSpec{nullptr, 0.0f, 0.0f, 0.0f};
   P.crec = nullptr;  // the chain pass then runs its plain-array form on the three-body dE/dCN
   P.crc = reinterpret_cast<const float*>(ws + L.crc);
   P.cflag = gflag + 4;
@@ -295,12 +327,12 @@ int d3_atm_impl(const T* pos, const int* numbers, int N, const int* idx, const i
   d3_mark_species_kernel<<<mi_blocks(N, 256), 256, 0, st>>>(numbers, N, hp->nz, present);
   MI_LAUNCH_CHECK();
   d3_compact_species_kernel<<<1, 256, 0, st>>>(present, hp->c6ab, hp->cn_ref, hp->nz, smap, sinfo, ctab, ftab, fcr, hp->k3, hp->r4r2, hp->a1, hp->a2, hp->rcov,
-                                               reinterpret_cast<float*>(ws + L.crc));
+                                               reinterpret_cast<float*>(ws + L.crc), zero);
   MI_LAUNCH_CHECK();
   const long long nt = (long long)hp->nz * hp->nz * 25;
   D3Guard G{};
   G.atom_blocks = mi_blocks(N, 256);
-  const D3Tables TB{hp->c6ab, hp->cn_ref, hp->nz, sinfo, tab, G.atom_blocks};
+  const D3Tables TB{hp->c6ab, hp->cn_ref, hp->nz, sinfo, tab, G.atom_blocks, zero};
   d3_pack_atoms_kernel<T><<<G.atom_blocks + mi_blocks(nt, 256), 256, 0, st>>>(pos, numbers, N, hp->rcov, hp->r4r2, smap, hp->nz, apos, aaux, forces, cn, dEdCN, e_atom,
                                                                             want_virial ? v_atom : nullptr, nullptr, apos_s, aaux_s, acn, G, TB, nullptr);
   MI_LAUNCH_CHECK();
@@ -314,7 +346,7 @@ int d3_atm_impl(const T* pos, const int* numbers, int N, const int* idx, const i
   const D3Atm A{s9, alpha, cutoff * cutoff, reinterpret_cast<unsigned*>(ws + LA.visits)};
   auto launch = [&](auto mode) {
     constexpr int MODE_ = decltype(mode)::value;
-    d3_atm_kernel<T, CSR, MODE_><<<N, D3_ATM_WAVES * MI_WAVE, 0, st>>>(pos, numbers, N, idx, ush, nptr, M, fill_value, cell, batch_idx, P, A, cn, want_virial, smap,
+    d3_atm_kernel<T, CSR, MODE_, DAMP><<<N, D3_ATM_WAVES * MI_WAVE, 0, st>>>(pos, numbers, N, idx, ush, nptr, M, fill_value, cell, batch_idx, P, A, cn, want_virial, smap,
                                                                     sinfo, ctab, ftab, fcr, apos, aaux, aw, dEdCN, forces, e_atom, v_atom);
   };
   MI_TIMED("d3_atm_triples", st, (launch(std::integral_constant<int, 2>{}), launch(std::integral_constant<int, 1>{}), launch(std::integral_constant<int, 0>{})));

@@ -32,6 +32,11 @@ class MiD3Params(ctypes.Structure):
                 ("k1", ctypes.c_float), ("k3", ctypes.c_float), ("s5_on", ctypes.c_float), ("s5_off", ctypes.c_float)]
 
 
+class MiD3ZeroParams(ctypes.Structure):
+    """`mi_d3_zero_params` of include/nvalchemiops_hip.h: the zero-damping parameters and the pair cutoff radii r0ab[nz,nz]."""
+    _fields_ = [("rs6", ctypes.c_float), ("rs8", ctypes.c_float), ("alpha", ctypes.c_float), ("beta", ctypes.c_float), ("r0ab", ctypes.c_void_p)]
+
+
 class MiNlCnRequest(ctypes.Structure):
     """`mi_nl_cn_request` of include/nvalchemiops_hip.h: what a search needs to sum DFT-D3 coordination numbers over the list it writes."""
     _fields_ = [("numbers", ctypes.c_void_p), ("covalent_radii", ctypes.c_void_p), ("nz", ctypes.c_int), ("k1", ctypes.c_float)]
@@ -79,6 +84,12 @@ def lib() -> ctypes.CDLL:
             L.mi_d3_atm.argtypes = ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_float,
                                      ctypes.c_float, ctypes.c_float, ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_size_t, ctypes.c_void_p])
+        if hasattr(L, "mi_d3_zero_atm"):  # ... with the radii of the zero damping: mi_d3_atm's arguments + rs9 + the r0ab table
+            L.mi_d3_zero_atm.restype = ctypes.c_int
+            L.mi_d3_zero_atm.argtypes = ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_float,
+                                          ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4
+                                         + [ctypes.c_size_t, ctypes.c_void_p])
         # the virial entry points (forward-only -dE/d(strain) of the Ewald / PME sums)
         vp, i, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
         L.mi_ewald_real_virial.restype = i

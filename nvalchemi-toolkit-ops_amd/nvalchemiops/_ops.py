@@ -6,6 +6,8 @@ need an opaque, mutation-annotated op -- finds the same ops as in the reference:
     nvalchemiops::batch_build_cell_list / ::batch_query_cell_list   (batch_cell_list.py:739-749, 915-918)
     nvalchemiops::dftd3_nm / ::dftd3_nl                             (dftd3.py:1792-1795, 2125-2128)
     nvalchemiops::dftd3_atm_nm / ::dftd3_atm_nl                     (this build's own: the three-body term, same shape as the two above)
+    nvalchemiops::dftd3_zero_nm / ::dftd3_zero_nl                   (this build's own: zero damping, D3(0) / D3M(0); same shape again)
+    nvalchemiops::dftd3_zero_atm_nm / ::dftd3_zero_atm_nl           (this build's own: the three-body term with the radii of the zero damping)
 
     nvalchemiops::_cell_list_needs_rebuild / ::_neighbor_list_needs_rebuild   (rebuild_detection.py:258, :386)
 
@@ -127,6 +129,45 @@ def _dftd3_nl_op(positions: torch.Tensor, numbers: torch.Tensor, idx_j: torch.Te
                     compute_virial, energy, forces, coord_num, virial)
 
 
+@torch.library.custom_op("nvalchemiops::dftd3_zero_nm", mutates_args=("energy", "forces", "coord_num", "virial"))
+def _dftd3_zero_nm_op(positions: torch.Tensor, numbers: torch.Tensor, neighbor_matrix: torch.Tensor, covalent_radii: torch.Tensor,
+                      r4r2: torch.Tensor, c6_reference: torch.Tensor, coord_num_ref: torch.Tensor, cutoff_radii: torch.Tensor, rs6: float,
+                      s8: float, energy: torch.Tensor, forces: torch.Tensor, coord_num: torch.Tensor, virial: torch.Tensor, rs8: float = 1.0,
+                      alpha: float = 14.0, beta: float = 0.0, k1: float = 16.0, k3: float = -4.0, s6: float = 1.0,
+                      s5_smoothing_on: float = 1e10, s5_smoothing_off: float = 1e10, fill_value: int | None = None,
+                      batch_idx: torch.Tensor | None = None, cell: torch.Tensor | None = None,
+                      neighbor_matrix_shifts: torch.Tensor | None = None, compute_virial: bool = False, device: str | None = None) -> None:
+    """`dftd3_nm` with zero damping (`mi_d3_zero`; no reference counterpart), mutating like it."""
+    n = positions.shape[0]
+    if n == 0:
+        return
+    C.require_device(positions, numbers, neighbor_matrix, batch_idx, energy, forces, coord_num)
+    nm = C.i32(neighbor_matrix)
+    with _device_of(positions):
+        _d3._launch(positions, numbers, nm, neighbor_matrix_shifts, None, nm.shape[1], n if fill_value is None else fill_value, cell, batch_idx,
+                    energy.shape[0], (covalent_radii, r4r2, c6_reference, coord_num_ref),
+                    _d3.zero_scalars(s6, s8, k1, k3, s5_smoothing_on, s5_smoothing_off), compute_virial, energy, forces, coord_num, virial,
+                    zero=(rs6, rs8, alpha, beta, cutoff_radii))
+
+
+@torch.library.custom_op("nvalchemiops::dftd3_zero_nl", mutates_args=("energy", "forces", "coord_num", "virial"))
+def _dftd3_zero_nl_op(positions: torch.Tensor, numbers: torch.Tensor, idx_j: torch.Tensor, neighbor_ptr: torch.Tensor,
+                      covalent_radii: torch.Tensor, r4r2: torch.Tensor, c6_reference: torch.Tensor, coord_num_ref: torch.Tensor,
+                      cutoff_radii: torch.Tensor, rs6: float, s8: float, energy: torch.Tensor, forces: torch.Tensor, coord_num: torch.Tensor,
+                      virial: torch.Tensor, rs8: float = 1.0, alpha: float = 14.0, beta: float = 0.0, k1: float = 16.0, k3: float = -4.0,
+                      s6: float = 1.0, s5_smoothing_on: float = 1e10, s5_smoothing_off: float = 1e10, batch_idx: torch.Tensor | None = None,
+                      cell: torch.Tensor | None = None, unit_shifts: torch.Tensor | None = None, compute_virial: bool = False,
+                      device: str | None = None) -> None:
+    """`dftd3_nl` with zero damping (`mi_d3_zero`), mutating like it."""
+    if positions.shape[0] == 0:
+        return
+    C.require_device(positions, numbers, idx_j, neighbor_ptr, batch_idx, energy, forces, coord_num)
+    with _device_of(positions):
+        _d3._launch(positions, numbers, C.i32(idx_j), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, energy.shape[0],
+                    (covalent_radii, r4r2, c6_reference, coord_num_ref), _d3.zero_scalars(s6, s8, k1, k3, s5_smoothing_on, s5_smoothing_off),
+                    compute_virial, energy, forces, coord_num, virial, zero=(rs6, rs8, alpha, beta, cutoff_radii))
+
+
 @torch.library.custom_op("nvalchemiops::dftd3_atm_nm", mutates_args=("energy", "forces", "virial"))
 def _dftd3_atm_nm_op(positions: torch.Tensor, numbers: torch.Tensor, neighbor_matrix: torch.Tensor, covalent_radii: torch.Tensor,
                      r4r2: torch.Tensor, c6_reference: torch.Tensor, coord_num_ref: torch.Tensor, a1: float, a2: float,
@@ -160,6 +201,42 @@ def _dftd3_atm_nl_op(positions: torch.Tensor, numbers: torch.Tensor, idx_j: torc
         _d3._launch_atm(positions, numbers, C.i32(idx_j), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, energy.shape[0],
                         (covalent_radii, r4r2, c6_reference, coord_num_ref), _d3.atm_scalars(a1, a2, k1, k3), s9, alpha, three_body_cutoff,
                         compute_virial, energy, forces, virial)
+
+
+@torch.library.custom_op("nvalchemiops::dftd3_zero_atm_nm", mutates_args=("energy", "forces", "virial"))
+def _dftd3_zero_atm_nm_op(positions: torch.Tensor, numbers: torch.Tensor, neighbor_matrix: torch.Tensor, covalent_radii: torch.Tensor,
+                          r4r2: torch.Tensor, c6_reference: torch.Tensor, coord_num_ref: torch.Tensor, cutoff_radii: torch.Tensor,
+                          three_body_cutoff: float, energy: torch.Tensor, forces: torch.Tensor, virial: torch.Tensor, rs9: float = 4.0 / 3.0,
+                          s9: float = 1.0, alpha: float = 16.0, k1: float = 16.0, k3: float = -4.0, fill_value: int | None = None,
+                          batch_idx: torch.Tensor | None = None, cell: torch.Tensor | None = None,
+                          neighbor_matrix_shifts: torch.Tensor | None = None, compute_virial: bool = False) -> None:
+    """`dftd3_atm_nm` with the radii of the zero damping (`mi_d3_zero_atm`), mutating like it."""
+    n = positions.shape[0]
+    if n == 0:
+        return
+    C.require_device(positions, numbers, neighbor_matrix, batch_idx, energy, forces)
+    nm = C.i32(neighbor_matrix)
+    with _device_of(positions):
+        _d3._launch_atm(positions, numbers, nm, neighbor_matrix_shifts, None, nm.shape[1], n if fill_value is None else fill_value, cell,
+                        batch_idx, energy.shape[0], (covalent_radii, r4r2, c6_reference, coord_num_ref), _d3.atm_scalars(0.0, 0.0, k1, k3), s9,
+                        alpha, three_body_cutoff, compute_virial, energy, forces, virial, zero=(rs9, cutoff_radii))
+
+
+@torch.library.custom_op("nvalchemiops::dftd3_zero_atm_nl", mutates_args=("energy", "forces", "virial"))
+def _dftd3_zero_atm_nl_op(positions: torch.Tensor, numbers: torch.Tensor, idx_j: torch.Tensor, neighbor_ptr: torch.Tensor,
+                          covalent_radii: torch.Tensor, r4r2: torch.Tensor, c6_reference: torch.Tensor, coord_num_ref: torch.Tensor,
+                          cutoff_radii: torch.Tensor, three_body_cutoff: float, energy: torch.Tensor, forces: torch.Tensor,
+                          virial: torch.Tensor, rs9: float = 4.0 / 3.0, s9: float = 1.0, alpha: float = 16.0, k1: float = 16.0,
+                          k3: float = -4.0, batch_idx: torch.Tensor | None = None, cell: torch.Tensor | None = None,
+                          unit_shifts: torch.Tensor | None = None, compute_virial: bool = False) -> None:
+    """`dftd3_atm_nl` with the radii of the zero damping (`mi_d3_zero_atm`), mutating like it."""
+    if positions.shape[0] == 0:
+        return
+    C.require_device(positions, numbers, idx_j, neighbor_ptr, batch_idx, energy, forces)
+    with _device_of(positions):
+        _d3._launch_atm(positions, numbers, C.i32(idx_j), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, energy.shape[0],
+                        (covalent_radii, r4r2, c6_reference, coord_num_ref), _d3.atm_scalars(0.0, 0.0, k1, k3), s9, alpha, three_body_cutoff,
+                        compute_virial, energy, forces, virial, zero=(rs9, cutoff_radii))
 
 
 # ---- this build's own ops behind the high-level entry points -----------------------------------------------------------------

@@ -7,6 +7,11 @@ float32, from a FULL neighbour list given either as a padded neighbour matrix or
 force) run as hand-written HIP kernels (csrc/d3.hip) behind `mi_d3` of the C ABI.  As in the reference, positions
 and cell are detached: explicit forces are returned, there is no autograd through D3.
 
+`dftd3_zero` is `dftd3` with the zero damping of the original D3 parametrisation, D3(0) / D3M(0), instead of the Becke-Johnson one
+(`mi_d3_zero`: the same three passes with another damping block in the energy pass; the pair cutoff radii are a table the caller supplies).
+
+`dftd3_zero_atm` is `dftd3_atm` with the radii of that table (`mi_d3_zero_atm`).
+
 `dftd3_atm` adds what the reference leaves out ("Two-body only", dftd3.py:119): the three-body Axilrod-Teller-Muto term, returned on its
 own so that a caller adds it to `dftd3`'s outputs (`mi_d3_atm`, csrc/d3_atm.h).
 """
@@ -75,8 +80,10 @@ _LIB_OVERRIDE = None  # tests only: a ctypes handle of the IEEE-arithmetic build
 
 
 def _launch(positions, numbers, idx, shifts, nptr, max_neighbors, fill_value, cell, batch_idx, num_systems, tables, scalars,
-            compute_virial, energy, forces, coord_num, virial, packed=None) -> None:
-    """`packed`: the companion record the neighbour search left next to (idx, shifts) (`neighborlist/_engine.py`: `.words`, and `.cn` when the
+            compute_virial, energy, forces, coord_num, virial, packed=None, zero=None) -> None:
+    """`zero`: None (BJ damping, `mi_d3*`) or (rs6, rs8, alpha, beta, cutoff_radii[nz,nz]) for the zero damping (`mi_d3_zero*`; scalars' a1 / a2
+    are then ignored).
+    `packed`: the companion record the neighbour search left next to (idx, shifts) (`neighborlist/_engine.py`: `.words`, and `.cn` when the
     search also summed the coordination numbers), already validated by the caller against tensor identity / versions; the passes then stream
     4 B/slot (`mi_d3_packed_cn`), the CN pass is skipped when the device-side fingerprint check lets the search's numbers in, and every call
     re-derives a rotating sample of the companion's rows from (idx, shifts) on the device before trusting it."""
@@ -90,6 +97,11 @@ def _launch(positions, numbers, idx, shifts, nptr, max_neighbors, fill_value, ce
         raise ValueError("this build supports the standard 5x5 CN interpolation mesh only")
     par = C.MiD3Params(rcov=rcov.data_ptr(), r4r2=r4r2.data_ptr(), c6ab=c6ab.data_ptr(), cn_ref=cnref.data_ptr(), nz=rcov.shape[0],
                        **{k: float(v) for k, v in scalars.items()})
+    zargs, tag = (), ""
+    if zero is not None:
+        r0ab = f32(zero[4])  # stays referenced until the launch is enqueued, like the other tables
+        zpar = C.MiD3ZeroParams(rs6=float(zero[0]), rs8=float(zero[1]), alpha=float(zero[2]), beta=float(zero[3]), r0ab=r0ab.data_ptr())
+        zargs, tag = (ctypes.byref(zpar),), "_zero"
     periodic = cell is not None and shifts is not None
     cell_t = cell.detach().to(dtype=pos.dtype, device=dev).reshape(-1, 3, 3).contiguous() if periodic else None
     sh = C.i32(shifts.to(dev)) if periodic else None
@@ -101,6 +113,8 @@ def _launch(positions, numbers, idx, shifts, nptr, max_neighbors, fill_value, ce
     pack = periodic and mode != "0" and (nptr is None or mode == "2")
     n_entries = (idx.shape[0] if nptr is not None else n * int(max_neighbors)) if pack else 0
     L = _LIB_OVERRIDE or C.lib()
+    if zero is not None and not hasattr(L, "mi_d3_zero"):
+        raise C.NativeLibraryError("libnvalchemiops_hip.so does not export mi_d3_zero: rebuild it (build_native.py)")
     ws_bytes = int(C.lib().mi_d3_workspace_bytes_entries(n, num_systems, rcov.shape[0], int(n_entries)))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     vir = virial if compute_virial else None
@@ -111,28 +125,36 @@ def _launch(positions, numbers, idx, shifts, nptr, max_neighbors, fill_value, ce
         words = packed.words
         cn = packed.cn if os.environ.get("NVALCHEMIOPS_D3_SEARCH_CN", "1") != "0" else None  # (A/B switch: "0" ignores the search's coordination numbers)
         stride, phase = E.verify_args()
-        rc = L.mi_d3_packed_cn(C.ptr(pos), C.ptr(z), n, code, C.ptr(idx), C.ptr(sh), int(max_neighbors), int(fill_value), C.ptr(cell_t), C.ptr(bi),
-                               int(num_systems), ctypes.byref(par), int(bool(compute_virial)), C.ptr(energy), C.ptr(forces), C.ptr(coord_num),
-                               C.ptr(vir), C.ptr(ws), ctypes.c_size_t(ws_bytes), C.ptr(words), ctypes.c_size_t(words.numel() * words.element_size()),
-                               C.ptr(cn), ctypes.c_size_t(cn.numel() if cn is not None else 0), int(stride), int(phase), C.stream_of(pos))
+        fn = L.mi_d3_packed_cn if zero is None else L.mi_d3_zero_packed_cn
+        rc = fn(C.ptr(pos), C.ptr(z), n, code, C.ptr(idx), C.ptr(sh), int(max_neighbors), int(fill_value), C.ptr(cell_t), C.ptr(bi),
+                int(num_systems), ctypes.byref(par), *zargs, int(bool(compute_virial)), C.ptr(energy), C.ptr(forces), C.ptr(coord_num),
+                C.ptr(vir), C.ptr(ws), ctypes.c_size_t(ws_bytes), C.ptr(words), ctypes.c_size_t(words.numel() * words.element_size()),
+                C.ptr(cn), ctypes.c_size_t(cn.numel() if cn is not None else 0), int(stride), int(phase), C.stream_of(pos))
         if rc != 0 and _LIB_OVERRIDE is not None:
-            raise C.NativeLibraryError(f"mi_d3_packed_cn (override library) failed with code {rc}")
-        C.check(rc, "mi_d3_packed_cn")
+            raise C.NativeLibraryError(f"mi_d3{tag}_packed_cn (override library) failed with code {rc}")
+        C.check(rc, f"mi_d3{tag}_packed_cn")
         return
-    rc = L.mi_d3(C.ptr(pos), C.ptr(z), n, code, C.ptr(idx), C.ptr(sh), C.ptr(nptr), int(max_neighbors),
-                 ctypes.c_longlong(idx.shape[0] if nptr is not None else 0), int(fill_value),  # CSR: the entry count (packing is decided by the workspace size)
-                 C.ptr(cell_t), C.ptr(bi), int(num_systems), ctypes.byref(par), int(bool(compute_virial)), C.ptr(energy), C.ptr(forces),
-                 C.ptr(coord_num), C.ptr(vir), C.ptr(ws), ctypes.c_size_t(ws_bytes), C.stream_of(pos))
+    fn = L.mi_d3 if zero is None else L.mi_d3_zero
+    rc = fn(C.ptr(pos), C.ptr(z), n, code, C.ptr(idx), C.ptr(sh), C.ptr(nptr), int(max_neighbors),
+            ctypes.c_longlong(idx.shape[0] if nptr is not None else 0), int(fill_value),  # CSR: the entry count (packing is decided by the workspace size)
+            C.ptr(cell_t), C.ptr(bi), int(num_systems), ctypes.byref(par), *zargs, int(bool(compute_virial)), C.ptr(energy), C.ptr(forces),
+            C.ptr(coord_num), C.ptr(vir), C.ptr(ws), ctypes.c_size_t(ws_bytes), C.stream_of(pos))
     if rc != 0 and _LIB_OVERRIDE is not None:
-        raise C.NativeLibraryError(f"mi_d3 (override library) failed with code {rc}")
-    C.check(rc, "mi_d3")
+        raise C.NativeLibraryError(f"mi_d3{tag} (override library) failed with code {rc}")
+    C.check(rc, f"mi_d3{tag}")
+
+
+_NO_RADII = object()  # `_check_and_resolve(cutoff_radii=...)`: the caller has no use for a table of pair cutoff radii
 
 
 def _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial, missing_functional,
-                       d3_params, covalent_radii, r4r2, c6_reference, coord_num_ref):
-    """Argument validation and parameter resolution shared by `dftd3` and `dftd3_atm` (dftd3.py:2668-2757): the same checks in the same
-    order with the same messages.  `missing_functional`: the message to raise when a required functional parameter is None, or None.
-    Returns (use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref))."""
+                       d3_params, covalent_radii, r4r2, c6_reference, coord_num_ref, cutoff_radii=_NO_RADII):
+    """Argument validation and parameter resolution shared by `dftd3`, `dftd3_zero` and `dftd3_atm` (dftd3.py:2668-2757): the same checks in
+    the same order with the same messages.  `missing_functional`: the message to raise when a required functional parameter is None, or None.
+    Returns (use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref)).
+    `cutoff_radii` given (a tensor or None; zero damping): the pair cutoff radii r0ab[Z+1, Z+1] are resolved as well -- explicit tensor, else
+    key "r0ab" of a `d3_params` dict (`D3Parameters` does not carry them) -- and checked against rcov's length; they are appended to the
+    returned tuple of tables."""
     use_matrix, use_list = neighbor_matrix is not None, neighbor_list is not None
     if use_matrix and use_list:
         raise ValueError("Cannot provide both neighbor_matrix and neighbor_list. Please provide only one neighbor representation format.")
@@ -174,7 +196,21 @@ def _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, n
         c6_reference = src["c6ab"] if c6_reference is None else c6_reference
         coord_num_ref = src["cn_ref"] if coord_num_ref is None else coord_num_ref
 
-    return use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref)
+    if cutoff_radii is _NO_RADII:
+        return use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref)
+    if cutoff_radii is None and isinstance(d3_params, dict):
+        cutoff_radii = d3_params.get("r0ab")
+    if cutoff_radii is None:
+        raise RuntimeError("DFT-D3 zero-damping pair cutoff radii must be explicitly provided. Either supply cutoff_radii (r0ab[max_Z+1, max_Z+1], "
+                           'in Bohr) or provide a d3_params dictionary with the key "r0ab"; a D3Parameters instance does not carry them.')
+    if not isinstance(cutoff_radii, torch.Tensor):
+        raise TypeError(f"Parameter 'cutoff_radii' must be a torch.Tensor, got {type(cutoff_radii)}")
+    if cutoff_radii.dtype not in _FLOAT_TYPES:
+        raise TypeError(f"Parameter 'cutoff_radii' must be float32 or float64, got {cutoff_radii.dtype}")
+    nz = covalent_radii.size(0)
+    if tuple(cutoff_radii.shape) != (nz, nz):
+        raise ValueError(f"cutoff_radii must have shape [{nz}, {nz}] to match rcov, got {tuple(cutoff_radii.shape)}")
+    return use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref, cutoff_radii)
 
 
 @C.hybrid
@@ -248,15 +284,106 @@ def dftd3(positions: torch.Tensor, numbers: torch.Tensor, a1: float, a2: float, 
     return (energy, forces, coord_num, virial) if compute_virial else (energy, forces, coord_num)
 
 
+@C.hybrid
+def dftd3_zero(positions: torch.Tensor, numbers: torch.Tensor, rs6: float, s8: float, rs8: float = 1.0, alpha: float = 14.0, beta: float = 0.0,
+               k1: float = 16.0, k3: float = -4.0, s6: float = 1.0, s5_smoothing_on: float = 1e10, s5_smoothing_off: float = 1e10,
+               fill_value: int | None = None, d3_params: D3Parameters | dict[str, torch.Tensor] | None = None,
+               covalent_radii: torch.Tensor | None = None, r4r2: torch.Tensor | None = None, c6_reference: torch.Tensor | None = None,
+               coord_num_ref: torch.Tensor | None = None, cutoff_radii: torch.Tensor | None = None, batch_idx: torch.Tensor | None = None,
+               cell: torch.Tensor | None = None, neighbor_matrix: torch.Tensor | None = None,
+               neighbor_matrix_shifts: torch.Tensor | None = None, neighbor_list: torch.Tensor | None = None,
+               neighbor_ptr: torch.Tensor | None = None, unit_shifts: torch.Tensor | None = None, compute_virial: bool = False,
+               num_systems: int | None = None, device: str | None = None):
+    """DFT-D3 with zero damping, D3(0) and its modified form D3M(0): returns what `dftd3` returns, ``(energy[num_systems], forces[N,3],
+    coord_num[N])`` (+ ``virial[num_systems,3,3]`` if ``compute_virial``), float32, with the pair energy::
+
+        E_ij = -C6_ij(CN_i, CN_j) * (s6 f_6(r) / r^6 + s8 * 3 r4r2_i r4r2_j * f_8(r) / r^8) * sw(r)
+        f_n(r) = 1 / (1 + 6 (r / (rs_n R0) + beta R0)^(-alpha_n)),   alpha_6 = alpha, alpha_8 = alpha + 2,   R0 = cutoff_radii[Z_i, Z_j]
+
+    ``beta = 0`` is D3(0), ``beta != 0`` D3M(0).  ``cutoff_radii`` is the symmetric table of pair cutoff radii r0ab[max_Z+1, max_Z+1] in Bohr
+    (index 0 = padding; float32 or float64, cast to float32 like the other tables), given explicitly or as key ``"r0ab"`` of a ``d3_params``
+    dict; a `D3Parameters` instance does not carry it.  A pair whose entry is <= 0 contributes nothing.  Coordination numbers, C6
+    interpolation, the half per stored directed pair, the S5 switch, the force / virial conventions, argument validation, ``num_systems``
+    inference and empty-input behaviour are `dftd3`'s; so is the use of what a neighbour search of this package left next to its matrix
+    (packed companion, coordination numbers)."""
+    missing = None
+    if rs6 is None or s8 is None:
+        missing = ("Functional parameters rs6 and s8 must be provided. "
+                   "These are functional-dependent parameters required for DFT-D3 zero-damping calculations.")
+    elif not alpha > 0:
+        missing = f"alpha must be positive, got {alpha}"
+    elif not (rs6 > 0 and rs8 > 0):
+        missing = f"rs6 and rs8 must be positive, got rs6={rs6}, rs8={rs8}"
+    use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref, cutoff_radii) = _check_and_resolve(
+        neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial, missing, d3_params, covalent_radii,
+        r4r2, c6_reference, coord_num_ref, cutoff_radii=cutoff_radii)
+
+    n, dev = positions.size(0), positions.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    if n == 0:
+        nsys = 1 if (batch_idx is None or batch_idx.numel() == 0) else int(batch_idx.max().item()) + 1
+        out = (torch.zeros(nsys, **f32), torch.zeros((0, 3), **f32), torch.zeros((0,), **f32))
+        return out + (torch.zeros((0, 3, 3), **f32),) if compute_virial else out
+    if num_systems is None:
+        if batch_idx is None:
+            num_systems = 1
+        elif cell is not None:
+            num_systems = cell.size(0)
+        else:
+            num_systems = int(batch_idx.max().item()) + 1
+    energy = torch.empty(num_systems, **f32)  # zeroed inside mi_d3_zero
+    forces = torch.empty((n, 3), **f32)
+    coord_num = torch.empty(n, **f32)
+    virial = torch.empty((num_systems, 3, 3), **f32) if compute_virial else torch.zeros((0, 3, 3), **f32)
+    if C.tracing():  # torch.compile: one mutating custom op per call, as for `dftd3`
+        if use_matrix:
+            torch.ops.nvalchemiops.dftd3_zero_nm(positions, numbers, neighbor_matrix, covalent_radii, r4r2, c6_reference, coord_num_ref,
+                                                 cutoff_radii, rs6, s8, energy, forces, coord_num, virial, rs8, alpha, beta, k1, k3, s6,
+                                                 s5_smoothing_on, s5_smoothing_off, fill_value, batch_idx, cell, neighbor_matrix_shifts,
+                                                 compute_virial, None)
+        else:
+            torch.ops.nvalchemiops.dftd3_zero_nl(positions, numbers, neighbor_list[1], neighbor_ptr, covalent_radii, r4r2, c6_reference,
+                                                 coord_num_ref, cutoff_radii, rs6, s8, energy, forces, coord_num, virial, rs8, alpha, beta, k1,
+                                                 k3, s6, s5_smoothing_on, s5_smoothing_off, batch_idx, cell, unit_shifts, compute_virial, None)
+        return (energy, forces, coord_num, virial) if compute_virial else (energy, forces, coord_num)
+    C.require_device(positions, numbers, neighbor_matrix, neighbor_list, neighbor_ptr, batch_idx)
+    scalars = zero_scalars(s6, s8, k1, k3, s5_smoothing_on, s5_smoothing_off)
+    tables = (covalent_radii, r4r2, c6_reference, coord_num_ref)
+    zero = (rs6, rs8, alpha, beta, cutoff_radii)
+    if use_matrix:
+        nm = C.i32(neighbor_matrix)
+        fill = n if fill_value is None else fill_value
+        packed = None
+        if nm is neighbor_matrix and cell is not None and neighbor_matrix_shifts is not None and int(fill) >= n:
+            from nvalchemiops.neighborlist import _engine as E
+
+            # exactly `dftd3`'s route: the companion and the search-side coordination numbers know nothing about the damping
+            packed = E.packed_companion(nm, neighbor_matrix_shifts, fill)
+            E.learn_dftd3_context(nm, numbers, covalent_radii, k1)
+        _launch(positions, numbers, nm, neighbor_matrix_shifts, None, nm.size(1), fill, cell,
+                batch_idx, num_systems, tables, scalars, compute_virial, energy, forces, coord_num, virial, packed=packed, zero=zero)
+    else:
+        idx_j = C.i32(neighbor_list[1])
+        _launch(positions, numbers, idx_j, unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, num_systems, tables, scalars,
+                compute_virial, energy, forces, coord_num, virial, zero=zero)
+    return (energy, forces, coord_num, virial) if compute_virial else (energy, forces, coord_num)
+
+
+def zero_scalars(s6, s8, k1, k3, on, off):
+    """`mi_d3_params` scalars of a zero-damping call: a1 / a2 are not read."""
+    return dict(a1=0.0, a2=0.0, s6=s6, s8=s8, k1=k1, k3=k3, s5_on=on, s5_off=off)
+
+
 def atm_tile() -> int:
     """Neighbours inside ``three_body_cutoff`` a row may have before the triple pass of `dftd3_atm` works tile by tile."""
     return int(C.lib().mi_d3_atm_tile())
 
 
 def _launch_atm(positions, numbers, idx, shifts, nptr, max_neighbors, fill_value, cell, batch_idx, num_systems, tables, scalars, s9, alpha,
-                three_body_cutoff, compute_virial, energy, forces, virial, want_visits=False):
+                three_body_cutoff, compute_virial, energy, forces, virial, want_visits=False, zero=None):
     """One `mi_d3_atm` call on the caller's arrays.  `want_visits`: return the per-centre triangle-visit counts the triple pass leaves in
-    its workspace (a diagnostic for tools/atm_bench.py)."""
+    its workspace (a diagnostic for tools/atm_bench.py).  `zero`: None, or (rs9, cutoff_radii[nz,nz]) for the radii of the zero damping
+    (`mi_d3_zero_atm`; scalars' a1 / a2 are then ignored)."""
     dev = positions.device
     n = positions.shape[0]
     pos = positions.detach().contiguous()
@@ -277,11 +404,21 @@ def _launch_atm(positions, numbers, idx, shifts, nptr, max_neighbors, fill_value
     ws_bytes = int(L.mi_d3_atm_workspace_bytes(n, num_systems, rcov.shape[0]))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     z = C.i32(numbers)  # converted tensors stay referenced until the launch is enqueued
-    rc = L.mi_d3_atm(C.ptr(pos), C.ptr(z), n, code, C.ptr(idx), C.ptr(sh), C.ptr(nptr), int(max_neighbors), int(fill_value), C.ptr(cell_t),
-                     C.ptr(bi), int(num_systems), ctypes.byref(par), float(s9), float(alpha), float(three_body_cutoff), int(bool(compute_virial)),
-                     C.ptr(energy), C.ptr(forces), C.ptr(virial if compute_virial else None), C.ptr(ws), ctypes.c_size_t(ws_bytes),
-                     C.stream_of(pos))
-    C.check(rc, "mi_d3_atm")
+    if zero is not None:
+        if not hasattr(L, "mi_d3_zero_atm"):
+            raise C.NativeLibraryError("libnvalchemiops_hip.so does not export mi_d3_zero_atm: rebuild it (build_native.py)")
+        r0ab = f32(zero[1])
+        rc = L.mi_d3_zero_atm(C.ptr(pos), C.ptr(z), n, code, C.ptr(idx), C.ptr(sh), C.ptr(nptr), int(max_neighbors), int(fill_value), C.ptr(cell_t),
+                              C.ptr(bi), int(num_systems), ctypes.byref(par), float(s9), float(alpha), float(three_body_cutoff), float(zero[0]),
+                              C.ptr(r0ab), int(bool(compute_virial)), C.ptr(energy), C.ptr(forces), C.ptr(virial if compute_virial else None),
+                              C.ptr(ws), ctypes.c_size_t(ws_bytes), C.stream_of(pos))
+        C.check(rc, "mi_d3_zero_atm")
+    else:
+        rc = L.mi_d3_atm(C.ptr(pos), C.ptr(z), n, code, C.ptr(idx), C.ptr(sh), C.ptr(nptr), int(max_neighbors), int(fill_value), C.ptr(cell_t),
+                         C.ptr(bi), int(num_systems), ctypes.byref(par), float(s9), float(alpha), float(three_body_cutoff), int(bool(compute_virial)),
+                         C.ptr(energy), C.ptr(forces), C.ptr(virial if compute_virial else None), C.ptr(ws), ctypes.c_size_t(ws_bytes),
+                         C.stream_of(pos))
+        C.check(rc, "mi_d3_atm")
     if want_visits:
         off = int(L.mi_d3_atm_visits_offset(n, num_systems, rcov.shape[0]))
         return ws[off:off + 4 * n].view(torch.int32).clone()
@@ -360,6 +497,72 @@ def dftd3_atm(positions: torch.Tensor, numbers: torch.Tensor, a1: float, a2: flo
     else:
         _launch_atm(positions, numbers, C.i32(neighbor_list[1]), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, num_systems, tables,
                     scalars, s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial)
+    return (energy, forces, virial) if compute_virial else (energy, forces)
+
+
+@C.hybrid
+def dftd3_zero_atm(positions: torch.Tensor, numbers: torch.Tensor, three_body_cutoff: float, cutoff_radii: torch.Tensor | None = None,
+                   rs9: float = 4.0 / 3.0, s9: float = 1.0, alpha: float = 16.0, k1: float = 16.0, k3: float = -4.0,
+                   fill_value: int | None = None, d3_params: D3Parameters | dict[str, torch.Tensor] | None = None,
+                   covalent_radii: torch.Tensor | None = None, r4r2: torch.Tensor | None = None, c6_reference: torch.Tensor | None = None,
+                   coord_num_ref: torch.Tensor | None = None, batch_idx: torch.Tensor | None = None, cell: torch.Tensor | None = None,
+                   neighbor_matrix: torch.Tensor | None = None, neighbor_matrix_shifts: torch.Tensor | None = None,
+                   neighbor_list: torch.Tensor | None = None, neighbor_ptr: torch.Tensor | None = None,
+                   unit_shifts: torch.Tensor | None = None, compute_virial: bool = False, num_systems: int | None = None):
+    """The three-body (Axilrod-Teller-Muto) term as it is paired with zero damping: `dftd3_atm` with the radii taken from the table of pair
+    cutoff radii, ``R0_XY = rs9 * cutoff_radii[Z_X, Z_Y]`` (``rs9 = 4/3`` by convention), instead of ``a1 sqrt(3 r4r2_X r4r2_Y) + a2``.
+    ``cutoff_radii`` is resolved as in `dftd3_zero` (explicit, or key ``"r0ab"`` of a ``d3_params`` dict); a triple with a pair whose entry
+    is <= 0 contributes nothing.  The remaining arguments, the list requirements and the outputs -- ``(energy[num_systems], forces[N,3])``
+    (+ ``virial[num_systems,3,3]``) of the three-body term alone, to be added to `dftd3_zero`'s -- are `dftd3_atm`'s."""
+    missing = None
+    if three_body_cutoff is None:
+        missing = "three_body_cutoff must be provided: the distance below which all three sides of a triple must lie."
+    elif not three_body_cutoff > 0:
+        missing = f"three_body_cutoff must be positive, got {three_body_cutoff}"
+    elif not alpha > 0:
+        missing = f"alpha must be positive, got {alpha}"
+    elif not rs9 > 0:
+        missing = f"rs9 must be positive, got {rs9}"
+    use_matrix, use_list, tables = _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell,
+                                                      compute_virial, missing, d3_params, covalent_radii, r4r2, c6_reference, coord_num_ref,
+                                                      cutoff_radii=cutoff_radii)
+    tables, cutoff_radii = tables[:4], tables[4]
+    n, dev = positions.size(0), positions.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    if n == 0:
+        nsys = 1 if (batch_idx is None or batch_idx.numel() == 0) else int(batch_idx.max().item()) + 1
+        out = (torch.zeros(nsys, **f32), torch.zeros((0, 3), **f32))
+        return out + (torch.zeros((0, 3, 3), **f32),) if compute_virial else out
+    if num_systems is None:
+        if batch_idx is None:
+            num_systems = 1
+        elif cell is not None:
+            num_systems = cell.size(0)
+        else:
+            num_systems = int(batch_idx.max().item()) + 1
+    energy = torch.empty(num_systems, **f32)  # written for every system inside mi_d3_zero_atm
+    forces = torch.empty((n, 3), **f32)
+    virial = torch.empty((num_systems, 3, 3), **f32) if compute_virial else torch.zeros((0, 3, 3), **f32)
+    if C.tracing():
+        if use_matrix:
+            torch.ops.nvalchemiops.dftd3_zero_atm_nm(positions, numbers, neighbor_matrix, tables[0], tables[1], tables[2], tables[3], cutoff_radii,
+                                                     three_body_cutoff, energy, forces, virial, rs9, s9, alpha, k1, k3, fill_value, batch_idx,
+                                                     cell, neighbor_matrix_shifts, compute_virial)
+        else:
+            torch.ops.nvalchemiops.dftd3_zero_atm_nl(positions, numbers, neighbor_list[1], neighbor_ptr, tables[0], tables[1], tables[2],
+                                                     tables[3], cutoff_radii, three_body_cutoff, energy, forces, virial, rs9, s9, alpha, k1, k3,
+                                                     batch_idx, cell, unit_shifts, compute_virial)
+        return (energy, forces, virial) if compute_virial else (energy, forces)
+    C.require_device(positions, numbers, neighbor_matrix, neighbor_list, neighbor_ptr, batch_idx)
+    scalars = atm_scalars(0.0, 0.0, k1, k3)
+    zero = (rs9, cutoff_radii)
+    if use_matrix:
+        nm = C.i32(neighbor_matrix)
+        _launch_atm(positions, numbers, nm, neighbor_matrix_shifts, None, nm.size(1), n if fill_value is None else fill_value, cell, batch_idx,
+                    num_systems, tables, scalars, s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial, zero=zero)
+    else:
+        _launch_atm(positions, numbers, C.i32(neighbor_list[1]), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, num_systems, tables,
+                    scalars, s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial, zero=zero)
     return (energy, forces, virial) if compute_virial else (energy, forces)
 
 
