@@ -177,6 +177,57 @@ def require_device(*tensors: torch.Tensor | None) -> torch.device:
     return dev
 
 
+def check_per_atom(n: int, **named: torch.Tensor | None) -> None:
+    """`numbers`, `charges`, `batch_idx`, ...: one entry per atom.  The kernels index them with the atom index, so a shorter tensor is an
+    out-of-bounds device read (and a longer one a misunderstanding): ValueError.  Host-side shape reads only."""
+    for name, t in named.items():
+        if t is not None and (t.dim() == 0 or t.shape[0] != n):
+            raise ValueError(f"{name} must have one entry per atom: expected shape [{n}], got {tuple(t.shape)}")
+
+
+def check_neighbor_data(n: int, *, neighbor_matrix=None, neighbor_matrix_shifts=None, neighbor_list=None, idx_j=None, neighbor_ptr=None,
+                        neighbor_shifts=None, shifts_name: str = "neighbor_shifts", short_ptr_ok: bool = False, cell=None, num_systems=None,
+                        alpha=None, **per_atom) -> None:
+    """Neighbour data against the number of atoms `n`, before anything is launched.  The kernels receive bare pointers plus `n`, the row
+    width and the entry count, so every disagreement checked here would be an out-of-bounds device read:
+
+      neighbor_matrix [n, M] with neighbor_matrix_shifts [n, M, 3];
+      neighbor_list [2, P] (or its second row `idx_j` [P]) with neighbor_ptr [n + 1] and shifts [P, 3]
+        (`short_ptr_ok`: cut-off Coulomb defines a shorter neighbor_ptr as "the remaining rows are empty");
+      `per_atom` tensors (numbers, charges, batch_idx) of length n;
+      cell [B, 3, 3] against `num_systems` and a tensor `alpha` of more than one value.
+
+    Host-side shape reads only (no device sync; TorchDynamo traces them as shape guards).  Values -- indices inside [0, n), a
+    monotonic neighbor_ptr -- are NOT checked: that would need a device pass."""
+    check_per_atom(n, **per_atom)
+    if neighbor_matrix is not None:
+        if neighbor_matrix.dim() != 2 or neighbor_matrix.shape[0] != n:
+            raise ValueError(f"neighbor_matrix must have shape [{n}, max_neighbors], got {tuple(neighbor_matrix.shape)}")
+        want = (n, neighbor_matrix.shape[1], 3)
+        if neighbor_matrix_shifts is not None and tuple(neighbor_matrix_shifts.shape) != want:
+            raise ValueError(f"neighbor_matrix_shifts must have shape {list(want)} to match neighbor_matrix, got {tuple(neighbor_matrix_shifts.shape)}")
+    if neighbor_list is not None:
+        if neighbor_list.dim() != 2 or neighbor_list.shape[0] != 2:
+            raise ValueError(f"neighbor_list must have shape [2, num_pairs], got {tuple(neighbor_list.shape)}")
+        idx_j = neighbor_list[1]
+    if idx_j is not None:
+        if idx_j.dim() != 1:
+            raise ValueError(f"idx_j must have shape [num_pairs], got {tuple(idx_j.shape)}")
+        if neighbor_ptr is not None and (neighbor_ptr.dim() != 1 or (neighbor_ptr.shape[0] > n + 1 if short_ptr_ok else neighbor_ptr.shape[0] != n + 1)):
+            raise ValueError(f"neighbor_ptr must have shape [{n + 1}] (num_atoms + 1), got {tuple(neighbor_ptr.shape)}")
+        want = (idx_j.shape[0], 3)
+        if neighbor_shifts is not None and tuple(neighbor_shifts.shape) != want:
+            raise ValueError(f"{shifts_name} must have shape {list(want)} to match neighbor_list, got {tuple(neighbor_shifts.shape)}")
+    if cell is not None:
+        if cell.dim() not in (2, 3) or tuple(cell.shape[-2:]) != (3, 3):
+            raise ValueError(f"cell must have shape [3, 3] or [num_systems, 3, 3], got {tuple(cell.shape)}")
+        n_cells = cell.shape[0] if cell.dim() == 3 else 1
+        if num_systems is not None and n_cells != int(num_systems):
+            raise ValueError(f"cell must have shape [{int(num_systems)}, 3, 3] (one per system), got {tuple(cell.shape)}")
+        if isinstance(alpha, torch.Tensor) and alpha.numel() > 1 and alpha.numel() != n_cells:
+            raise ValueError(f"alpha has {alpha.numel()} values but there are {n_cells} systems")  # the reference's message (ewald.py:230)
+
+
 SPLINE_REFERENCE_ORDERS = 0x100  # MI_SPLINE_REFERENCE_ORDERS of include/nvalchemiops_hip.h
 _REFERENCE_SPLINE_ORDERS = os.environ.get("NVALCHEMIOPS_REFERENCE_SPLINE_ORDERS", "0") not in ("", "0")  # process default
 # context-local override (`with nvalchemiops.spline.reference_spline_orders():`): a contextvars.ContextVar, so the setting belongs to the

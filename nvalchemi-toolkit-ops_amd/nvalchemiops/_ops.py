@@ -247,6 +247,8 @@ def _neighbor_search_op(positions: torch.Tensor, cell: torch.Tensor, pbc: torch.
                         num_neighbors: torch.Tensor, origin: torch.Tensor | None = None) -> None:
     """The fused search (`mi_nl_neighbors`, mode matrix) into caller-owned outputs; `flags` = the NL_* bits of include/nvalchemiops_hip.h.
     Inputs are canonical already (`_engine.canon_geometry`): positions [N,3] f32/f64, cell [B,3,3] same dtype, pbc [B,3] bool."""
+    C.check_per_atom(positions.shape[0], batch_idx=batch_idx)
+    E.check_outputs(positions.shape[0], positions.device, neighbor_matrix, neighbor_matrix_shifts, num_neighbors)
     C.require_device(positions, cell, pbc, batch_idx, neighbor_matrix, neighbor_matrix_shifts, num_neighbors, origin)
     pos, c, p = E.canon_geometry(positions, cell, pbc)
     with _device_of(pos):

@@ -148,13 +148,16 @@ _NO_RADII = object()  # `_check_and_resolve(cutoff_radii=...)`: the caller has n
 
 
 def _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial, missing_functional,
-                       d3_params, covalent_radii, r4r2, c6_reference, coord_num_ref, cutoff_radii=_NO_RADII):
+                       d3_params, covalent_radii, r4r2, c6_reference, coord_num_ref, atoms, cutoff_radii=_NO_RADII):
     """Argument validation and parameter resolution shared by `dftd3`, `dftd3_zero` and `dftd3_atm` (dftd3.py:2668-2757): the same checks in
     the same order with the same messages.  `missing_functional`: the message to raise when a required functional parameter is None, or None.
     Returns (use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref)).
     `cutoff_radii` given (a tensor or None; zero damping): the pair cutoff radii r0ab[Z+1, Z+1] are resolved as well -- explicit tensor, else
     key "r0ab" of a `d3_params` dict (`D3Parameters` does not carry them) -- and checked against rcov's length; they are appended to the
-    returned tuple of tables."""
+    returned tuple of tables.
+    `atoms` = (positions, numbers, batch_idx, num_systems) of the call: neighbour data, per-atom tensors and cells are checked against
+    the number of atoms and systems, and the tables against rcov's length (`_capi.check_neighbor_data`; host-side shape reads, before the
+    device check and before any launch -- the kernels see bare pointers and these integers)."""
     use_matrix, use_list = neighbor_matrix is not None, neighbor_list is not None
     if use_matrix and use_list:
         raise ValueError("Cannot provide both neighbor_matrix and neighbor_list. Please provide only one neighbor representation format.")
@@ -196,6 +199,21 @@ def _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, n
         c6_reference = src["c6ab"] if c6_reference is None else c6_reference
         coord_num_ref = src["cn_ref"] if coord_num_ref is None else coord_num_ref
 
+    positions, numbers, batch_idx, num_systems = atoms
+    nz = covalent_radii.size(0)
+    if tuple(r4r2.shape) != (nz,):
+        raise ValueError(f"r4r2 must have shape [{nz}] to match rcov, got {tuple(r4r2.shape)}")
+    if c6_reference.dim() != 4 or tuple(c6_reference.shape[:2]) != (nz, nz):
+        raise ValueError(f"c6ab must have shape {(nz, nz, 5, 5)}, got {tuple(c6_reference.shape)}")
+    if tuple(coord_num_ref.shape) != tuple(c6_reference.shape):
+        raise ValueError(f"cn_ref must have shape {tuple(c6_reference.shape)}, got {tuple(coord_num_ref.shape)}")
+    shifts = neighbor_matrix_shifts if use_matrix else unit_shifts
+    if num_systems is None and batch_idx is None:
+        num_systems = 1
+    if positions.size(0) > 0:  # (no atoms: nothing is launched, and the reference's empty-input contract reads batch_idx on its own)
+        C.check_neighbor_data(positions.size(0), neighbor_matrix=neighbor_matrix, neighbor_matrix_shifts=neighbor_matrix_shifts,
+                              neighbor_list=neighbor_list, neighbor_ptr=neighbor_ptr, neighbor_shifts=unit_shifts, shifts_name="unit_shifts",
+                              cell=cell if shifts is not None else None, num_systems=num_systems, numbers=numbers, batch_idx=batch_idx)
     if cutoff_radii is _NO_RADII:
         return use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref)
     if cutoff_radii is None and isinstance(d3_params, dict):
@@ -231,7 +249,7 @@ def dftd3(positions: torch.Tensor, numbers: torch.Tensor, a1: float, a2: float, 
                    "These are functional-dependent parameters required for DFT-D3(BJ) calculations.")
     use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref) = _check_and_resolve(
         neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial, missing, d3_params, covalent_radii,
-        r4r2, c6_reference, coord_num_ref)
+        r4r2, c6_reference, coord_num_ref, (positions, numbers, batch_idx, num_systems))
 
     n, dev = positions.size(0), positions.device
     f32 = dict(dtype=torch.float32, device=dev)
@@ -316,7 +334,7 @@ def dftd3_zero(positions: torch.Tensor, numbers: torch.Tensor, rs6: float, s8: f
         missing = f"rs6 and rs8 must be positive, got rs6={rs6}, rs8={rs8}"
     use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref, cutoff_radii) = _check_and_resolve(
         neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial, missing, d3_params, covalent_radii,
-        r4r2, c6_reference, coord_num_ref, cutoff_radii=cutoff_radii)
+        r4r2, c6_reference, coord_num_ref, (positions, numbers, batch_idx, num_systems), cutoff_radii=cutoff_radii)
 
     n, dev = positions.size(0), positions.device
     f32 = dict(dtype=torch.float32, device=dev)
@@ -461,7 +479,8 @@ def dftd3_atm(positions: torch.Tensor, numbers: torch.Tensor, a1: float, a2: flo
     elif not alpha > 0:
         missing = f"alpha must be positive, got {alpha}"
     use_matrix, use_list, tables = _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell,
-                                                      compute_virial, missing, d3_params, covalent_radii, r4r2, c6_reference, coord_num_ref)
+                                                      compute_virial, missing, d3_params, covalent_radii, r4r2, c6_reference, coord_num_ref,
+                                                      (positions, numbers, batch_idx, num_systems))
     n, dev = positions.size(0), positions.device
     f32 = dict(dtype=torch.float32, device=dev)
     if n == 0:
@@ -525,7 +544,7 @@ def dftd3_zero_atm(positions: torch.Tensor, numbers: torch.Tensor, three_body_cu
         missing = f"rs9 must be positive, got {rs9}"
     use_matrix, use_list, tables = _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell,
                                                       compute_virial, missing, d3_params, covalent_radii, r4r2, c6_reference, coord_num_ref,
-                                                      cutoff_radii=cutoff_radii)
+                                                      (positions, numbers, batch_idx, num_systems), cutoff_radii=cutoff_radii)
     tables, cutoff_radii = tables[:4], tables[4]
     n, dev = positions.size(0), positions.device
     f32 = dict(dtype=torch.float32, device=dev)

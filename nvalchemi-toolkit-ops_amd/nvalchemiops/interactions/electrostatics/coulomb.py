@@ -52,8 +52,15 @@ def _force_adjoint(pos, q, cells, bi, idx, sh, nptr, m, fill_value, cutoff, alph
     return gpos, gq, gcell
 
 
-def _lists(n, dev, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, fill_value, want_forces):
-    """(idx, shifts, row pointer | None, row width, fill value, energy prefactor) of either neighbour format."""
+def _lists(n, dev, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, fill_value, want_forces, atoms):
+    """(idx, shifts, row pointer | None, row width, fill value, energy prefactor) of either neighbour format.  Every launch of this module
+    comes through here, so this is where `atoms` = (positions, charges, cell, batch_idx) and the neighbour data are checked: shapes
+    first (`_capi.check_neighbor_data`; a neighbor_ptr SHORTER than N + 1 stays legal, see below), then the device."""
+    positions, charges, cell, batch_idx = atoms
+    C.check_neighbor_data(n, neighbor_matrix=neighbor_matrix, neighbor_matrix_shifts=neighbor_matrix_shifts, neighbor_list=neighbor_list,
+                          neighbor_ptr=neighbor_ptr, neighbor_shifts=neighbor_shifts, short_ptr_ok=True, charges=charges, batch_idx=batch_idx)
+    if n > 0:
+        C.require_device(positions, charges, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx)
     if neighbor_list is not None:
         idx, sh, nptr, m, fv = C.i32(neighbor_list[1]), C.i32(neighbor_shifts), C.i32(neighbor_ptr), 0, 0
         if nptr.numel() < n + 1:
@@ -73,7 +80,7 @@ def _forward(positions, charges, cell, batch_idx, neighbor_list, neighbor_ptr, n
     (nvalchemiops/_eops.py) and of the plain eager call."""
     n, dev = positions.shape[0], positions.device
     idx, sh, nptr, m, fv, epref = _lists(n, dev, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, fill_value,
-                                         want_forces)
+                                         want_forces, (positions, charges, cell, batch_idx))
     if n == 0 or idx.numel() == 0:
         return torch.zeros(n, dtype=torch.float64, device=dev), (torch.zeros((n, 3), dtype=torch.float64, device=dev) if want_forces else None)
     bi = None if batch_idx is None else C.i32(batch_idx)
@@ -85,7 +92,7 @@ def _backward(positions, charges, cell, batch_idx, neighbor_list, neighbor_ptr, 
               fill_value, cutoff, alpha, want_forces, grad_energies):
     n, dev = positions.shape[0], positions.device
     idx, sh, nptr, m, fv, epref = _lists(n, dev, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, fill_value,
-                                         want_forces)
+                                         want_forces, (positions, charges, cell, batch_idx))
     cells = cell.detach().reshape(-1, 3, 3).contiguous()
     if n == 0 or idx.numel() == 0:  # nothing stored: zero gradients, as the reference's tape gives (test_coulomb.py:964-996, :1954-2175)
         return torch.zeros((n, 3), dtype=torch.float64, device=dev), torch.zeros(n, dtype=torch.float64, device=dev), torch.zeros_like(cells)
@@ -97,7 +104,7 @@ def _backward(positions, charges, cell, batch_idx, neighbor_list, neighbor_ptr, 
 def _forces_backward(positions, charges, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts,
                      fill_value, cutoff, alpha, grad_forces):
     n, dev = positions.shape[0], positions.device
-    idx, sh, nptr, m, fv, _ = _lists(n, dev, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, fill_value, True)
+    idx, sh, nptr, m, fv, _ = _lists(n, dev, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, fill_value, True, (positions, charges, cell, batch_idx))
     cells = cell.detach().reshape(-1, 3, 3).contiguous()
     if n == 0 or idx.numel() == 0:
         return torch.zeros((n, 3), dtype=torch.float64, device=dev), torch.zeros(n, dtype=torch.float64, device=dev), torch.zeros_like(cells)
@@ -117,8 +124,6 @@ def _run(positions, charges, cell, cutoff, alpha, neighbor_list, neighbor_ptr, n
     if use_list and neighbor_ptr is None:
         raise ValueError("neighbor_ptr is required when using neighbor_list format")
     n = positions.shape[0]
-    if n > 0:
-        C.require_device(positions, charges, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx)
     pos = positions.to(torch.float64)
     q = charges.to(torch.float64)
     cells = cell.to(torch.float64).reshape(-1, 3, 3)

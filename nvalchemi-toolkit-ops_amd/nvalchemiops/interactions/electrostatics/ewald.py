@@ -34,6 +34,10 @@ def _real_space_inputs(positions, charges, cell, alpha, neighbor_list, neighbor_
         raise ValueError("neighbor_ptr is required when using neighbor_list format")
     dev, dt = positions.device, positions.dtype
     C.dtype_code(dt)
+    # shapes against the number of atoms / systems, before the device check and before anything is launched: the kernels see bare pointers
+    C.check_neighbor_data(positions.shape[0], neighbor_matrix=neighbor_matrix, neighbor_matrix_shifts=neighbor_matrix_shifts,
+                          neighbor_list=neighbor_list, neighbor_ptr=neighbor_ptr, neighbor_shifts=neighbor_shifts, cell=cell, alpha=alpha,
+                          charges=charges, batch_idx=batch_idx)
     C.require_device(positions, charges, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx)
     alpha_in = alpha if isinstance(alpha, torch.Tensor) else torch.tensor([float(alpha)], device=dev)
     alpha_in = alpha_in.to(device=dev, dtype=dt).reshape(-1)

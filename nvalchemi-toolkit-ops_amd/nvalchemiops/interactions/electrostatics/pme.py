@@ -33,7 +33,13 @@ TWOPI = 2.0 * math.pi
 @functools.lru_cache(maxsize=64)
 def _alpha_constant(value: float, num_systems: int, dtype: torch.dtype, device: torch.device) -> torch.Tensor:
     # a Python-float alpha becomes the same read-only device tensor on every call of an MD loop: no fill kernel per step
-    return torch.full((num_systems,), value, dtype=dtype, device=device)
+    t = torch.full((num_systems,), value, dtype=dtype, device=device)
+    if t.is_cuda:
+        # the fill is enqueued on the stream that is current NOW, but the cached tensor is handed to every later caller on whatever stream
+        # is current THEN, and a caller who passed a Python float has nothing to wait on: the filling stream is waited for once, at
+        # creation (as `_solve_tables` does); afterwards the block is read-only and any stream may use it
+        torch.cuda.current_stream(t.device).synchronize()
+    return t
 
 
 def _prepare_alpha(alpha: float | torch.Tensor, num_systems: int, dtype: torch.dtype, device: torch.device) -> torch.Tensor:
@@ -88,7 +94,7 @@ def pme_green_structure_factor(k_squared: torch.Tensor, mesh_dimensions: tuple[i
     spline_order = C.resolve_spline_order(spline_order)
     nx, ny, nz = (int(v) for v in mesh_dimensions)
     dt, dev = k_squared.dtype, k_squared.device
-    cells = cell if cell.dim() == 3 else cell.unsqueeze(0)
+    cells = (cell if cell.dim() == 3 else cell.unsqueeze(0)).to(dt)  # the volume below is computed in the dtype of the call, whatever the cell's own
     nsys = cells.shape[0] if batch_idx is not None else 1
     if C.tracing() or (torch.is_grad_enabled() and any(t.requires_grad for t in (k_squared, alpha, cell))):
         from nvalchemiops import _eops  # noqa: F401
@@ -122,7 +128,7 @@ def _total_charge(charges: torch.Tensor, batch_idx, num_systems: int) -> torch.T
 def _corrections(raw, charges, cell, alpha, batch_idx, want_cg):
     C.require_device(raw, charges, cell)
     dt, dev = raw.dtype, raw.device
-    cells = cell if cell.dim() == 3 else cell.unsqueeze(0)
+    cells = (cell if cell.dim() == 3 else cell.unsqueeze(0)).to(dt)  # the volume below is computed in the dtype of the call, whatever the cell's own
     nsys = cells.shape[0] if batch_idx is not None else 1
     if C.tracing() or (torch.is_grad_enabled() and any(t.requires_grad for t in (raw, charges, cell, alpha))):
         from nvalchemiops import _eops  # noqa: F401

@@ -256,6 +256,43 @@ def canon_geometry(positions: torch.Tensor, cell: torch.Tensor, pbc: torch.Tenso
     return pos, cell, pbc.contiguous()
 
 
+def check_outputs(n, dev, nm, nsh, num, which="", width=None):
+    """Caller-supplied output buffers go to the kernel as raw pointers (rows written at i * M + slot, whole rows padded): anything but
+    int32 / contiguous / the positions' device / N rows / matching widths would be an out-of-bounds device write, so it is an error here.
+    The package's one rule for `neighbor_matrix` / `neighbor_matrix_shifts` / `num_neighbors` (None = allocated by the entry point);
+    `width`: the row width the entry point will allocate the matrix with when the caller gave only the other two.  Host-side shape reads
+    only, before the device check and before any launch."""
+    m = (nm.shape[1] if nm.dim() == 2 else -1) if nm is not None else (-1 if width is None else int(width))
+    for name, t, shape in ((f"neighbor_matrix{which}", nm, (n, m)), (f"num_neighbors{which}", num, (n,)),
+                           (f"neighbor_matrix_shifts{which}", nsh, (n, m, 3))):
+        if t is None:
+            continue
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev or tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be a contiguous int32 tensor of shape {shape} on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}"
+                             f"{'' if t.is_contiguous() else ' (non-contiguous)'}")
+
+
+def check_cache(n, n_systems, dev, cells_per_dimension, atom_periodic_shifts, atom_to_cell_mapping, atoms_per_cell_count,
+                cell_atom_start_indices, cell_atom_list):
+    """The cell-list cache tensors `mi_nl_build_cell_cache` fills through raw pointers: int32, contiguous, on the positions' device and long
+    enough for N atoms, `n_systems` grids and the cell capacity (= atoms_per_cell_count.shape[0]); larger buffers are fine.  Same rule and
+    place in the call as `check_outputs`."""
+    cap = atoms_per_cell_count.shape[0] if atoms_per_cell_count.dim() == 1 else -1
+    for name, t, ok, want in (
+            ("cells_per_dimension", cells_per_dimension, cells_per_dimension.numel() >= 3 * n_systems, f"[{n_systems}, 3] or [3]"),
+            ("atom_periodic_shifts", atom_periodic_shifts, atom_periodic_shifts.dim() == 2 and atom_periodic_shifts.shape[0] >= n
+             and atom_periodic_shifts.shape[1] == 3, f"[{n}, 3]"),
+            ("atom_to_cell_mapping", atom_to_cell_mapping, atom_to_cell_mapping.dim() == 2 and atom_to_cell_mapping.shape[0] >= n
+             and atom_to_cell_mapping.shape[1] == 3, f"[{n}, 3]"),
+            ("atoms_per_cell_count", atoms_per_cell_count, cap >= n_systems, f"[max_total_cells >= {n_systems}]"),
+            ("cell_atom_start_indices", cell_atom_start_indices, cell_atom_start_indices.dim() == 1 and cell_atom_start_indices.shape[0] >= cap,
+             f"[{cap}] to match atoms_per_cell_count"),
+            ("cell_atom_list", cell_atom_list, cell_atom_list.dim() == 1 and cell_atom_list.shape[0] >= n, f"[{n}]")):
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.device != dev or not ok:
+            raise ValueError(f"{name} must be a contiguous int32 tensor of shape {want} (or longer) on {dev}, got {t.dtype} {tuple(t.shape)} "
+                             f"on {t.device}{'' if t.is_contiguous() else ' (non-contiguous)'}")
+
+
 def run(pos, cell, pbc, batch_idx, cutoff, mode, flags, *, nm=None, nsh=None, num=None, max_neighbors=0, fill_value=0,
         nptr=None, list_ij=None, list_sh=None, n_pairs=0, ws=None, origin=None):
     n = pos.shape[0]

@@ -42,6 +42,10 @@ def batch_build_cell_list(positions, cutoff, cell, pbc, batch_idx, cells_per_dim
                                                      atom_periodic_shifts, atom_to_cell_mapping, atoms_per_cell_count,
                                                      cell_atom_start_indices, cell_atom_list)
         return
+    n = positions.shape[0]
+    C.check_per_atom(n, batch_idx=batch_idx)
+    E.check_cache(n, cell.shape[0] if cell.ndim == 3 else 1, positions.device, cells_per_dimension, atom_periodic_shifts, atom_to_cell_mapping,
+                  atoms_per_cell_count, cell_atom_start_indices, cell_atom_list)
     C.require_device(positions, cell, pbc, batch_idx)
     pos, c, p = E.canon_geometry(positions, cell, pbc)
     _build_cache(pos, c, p, C.i32(batch_idx), cutoff, cells_per_dimension, atom_periodic_shifts, atom_to_cell_mapping,
@@ -62,6 +66,8 @@ def batch_query_cell_list(positions, cell, pbc, cutoff, batch_idx, cells_per_dim
                                                      cell_atom_start_indices, cell_atom_list, neighbor_matrix, neighbor_matrix_shifts,
                                                      num_neighbors, half_fill)
         return
+    C.check_per_atom(positions.shape[0], batch_idx=batch_idx)
+    E.check_outputs(positions.shape[0], positions.device, neighbor_matrix, neighbor_matrix_shifts, num_neighbors)
     C.require_device(positions, cell, pbc, batch_idx, neighbor_matrix, neighbor_matrix_shifts, num_neighbors)
     pos, c, p = E.canon_geometry(positions, cell, pbc)
     E.neighbor_matrix(pos, c, p, C.i32(batch_idx), cutoff, neighbor_matrix.shape[1], 0, half_fill, neighbor_matrix,
@@ -81,18 +87,26 @@ def batch_cell_list(positions: torch.Tensor, cutoff: float, cell: torch.Tensor, 
     total_atoms = positions.shape[0]
     if total_atoms <= 0 or cutoff <= 0:
         return _empty_result(total_atoms, -1, return_neighbor_list, positions.device)  # -1: batch_cell_list.py:1369
-    if not C.tracing():
-        C.require_device(positions, cell, pbc, batch_idx)
     if max_neighbors is None and neighbor_matrix is None:
         max_neighbors = estimate_max_neighbors(cutoff)
+    C.check_per_atom(total_atoms, batch_idx=batch_idx)
+    E.check_outputs(total_atoms, positions.device, neighbor_matrix, neighbor_matrix_shifts, num_neighbors, width=max_neighbors)
+    cache = (cells_per_dimension, neighbor_search_radius, atom_periodic_shifts, atom_to_cell_mapping, atoms_per_cell_count,
+             cell_atom_start_indices, cell_atom_list)
+    refresh = all(t is not None for t in cache)
+    if refresh:
+        E.check_cache(total_atoms, cell.shape[0] if cell.ndim == 3 else 1, positions.device, *cache[:1], *cache[2:])
+    if not C.tracing():
+        C.require_device(positions, cell, pbc, batch_idx)
     if fill_value is None:
         fill_value = total_atoms
     pos, c, p = E.canon_geometry(positions, cell, pbc)
     bi = C.i32(batch_idx)
-    cache = (cells_per_dimension, neighbor_search_radius, atom_periodic_shifts, atom_to_cell_mapping, atoms_per_cell_count,
-             cell_atom_start_indices, cell_atom_list)
-    if all(t is not None for t in cache):
-        batch_build_cell_list(pos, cutoff, c, p, bi, *cache)
+    if refresh:  # (checked above: straight to the launch)
+        if C.tracing():
+            batch_build_cell_list(pos, cutoff, c, p, bi, *cache)
+        else:
+            _build_cache(pos, c, p, bi, cutoff, cache[0], *cache[2:])
     return _search(pos, c, p, bi, cutoff, max_neighbors, half_fill, fill_value, return_neighbor_list, neighbor_matrix,
                    neighbor_matrix_shifts, num_neighbors)
 

@@ -37,6 +37,8 @@ def batch_naive_neighbor_list(positions: torch.Tensor, cutoff: float, batch_idx:
     if max_neighbors is None and (neighbor_matrix is None or (neighbor_matrix_shifts is None and periodic) or num_neighbors is None):
         max_neighbors = estimate_max_neighbors(cutoff)
     i32 = dict(dtype=torch.int32, device=dev)
+    C.check_per_atom(n, batch_idx=batch_idx)
+    E.check_outputs(n, dev, neighbor_matrix, neighbor_matrix_shifts if periodic else None, num_neighbors, width=max_neighbors)
     if neighbor_matrix is None:
         neighbor_matrix = torch.empty((n, max_neighbors), **i32)
     m = neighbor_matrix.shape[1]

@@ -60,6 +60,8 @@ def build_cell_list(positions, cutoff, cell, pbc, cells_per_dimension, neighbor_
         torch.ops.nvalchemiops.build_cell_list(positions, cutoff, cell, pbc, cells_per_dimension, neighbor_search_radius, atom_periodic_shifts,
                                                atom_to_cell_mapping, atoms_per_cell_count, cell_atom_start_indices, cell_atom_list)
         return
+    E.check_cache(positions.shape[0], 1, positions.device, cells_per_dimension, atom_periodic_shifts, atom_to_cell_mapping, atoms_per_cell_count,
+                  cell_atom_start_indices, cell_atom_list)
     C.require_device(positions, cell, pbc)
     pos, c, p = E.canon_geometry(positions, cell, pbc)
     _build_cache(pos, c, p, None, cutoff, cells_per_dimension, atom_periodic_shifts, atom_to_cell_mapping, atoms_per_cell_count,
@@ -79,6 +81,7 @@ def query_cell_list(positions, cutoff, cell, pbc, cells_per_dimension, neighbor_
                                                atom_to_cell_mapping, atoms_per_cell_count, cell_atom_start_indices, cell_atom_list,
                                                neighbor_matrix, neighbor_matrix_shifts, num_neighbors, half_fill)
         return
+    E.check_outputs(positions.shape[0], positions.device, neighbor_matrix, neighbor_matrix_shifts, num_neighbors)
     C.require_device(positions, cell, pbc, neighbor_matrix, neighbor_matrix_shifts, num_neighbors)
     pos, c, p = E.canon_geometry(positions, cell, pbc)
     E.neighbor_matrix(pos, c, p, None, cutoff, neighbor_matrix.shape[1], 0, half_fill, neighbor_matrix, neighbor_matrix_shifts,
@@ -132,16 +135,23 @@ def cell_list(positions: torch.Tensor, cutoff: float, cell: torch.Tensor, pbc: t
         fill_value = total_atoms
     if total_atoms <= 0 or cutoff <= 0:
         return _empty_result(total_atoms, fill_value, return_neighbor_list, positions.device)
+    if max_neighbors is None and (neighbor_matrix is None or neighbor_matrix_shifts is None or num_neighbors is None):
+        max_neighbors = estimate_max_neighbors(cutoff)
+    E.check_outputs(total_atoms, positions.device, neighbor_matrix, neighbor_matrix_shifts, num_neighbors, width=max_neighbors)
+    cache = (cells_per_dimension, neighbor_search_radius, atom_periodic_shifts, atom_to_cell_mapping, atoms_per_cell_count,
+             cell_atom_start_indices, cell_atom_list)
+    refresh = all(t is not None for t in cache)
+    if refresh:
+        E.check_cache(total_atoms, 1, positions.device, *cache[:1], *cache[2:])
     if not C.tracing():
         C.require_device(positions, cell, pbc)
     pos, c, p = E.canon_geometry(positions, cell, pbc)
-    if max_neighbors is None and (neighbor_matrix is None or neighbor_matrix_shifts is None or num_neighbors is None):
-        max_neighbors = estimate_max_neighbors(cutoff)
-    cache = (cells_per_dimension, neighbor_search_radius, atom_periodic_shifts, atom_to_cell_mapping, atoms_per_cell_count,
-             cell_atom_start_indices, cell_atom_list)
-    if all(t is not None for t in cache):
-        # caller-owned cache: refresh it in the reference's format (cell_list.py:1394-1417)
-        build_cell_list(pos, cutoff, c, p, *cache)
+    if refresh:
+        # caller-owned cache: refresh it in the reference's format (cell_list.py:1394-1417); checked above, so straight to the launch
+        if C.tracing():
+            build_cell_list(pos, cutoff, c, p, *cache)
+        else:
+            _build_cache(pos, c, p, None, cutoff, cache[0], *cache[2:])
     return _search(pos, c, p, None, cutoff, max_neighbors, half_fill, fill_value, return_neighbor_list, neighbor_matrix,
                    neighbor_matrix_shifts, num_neighbors)
 

@@ -50,6 +50,7 @@ def naive_neighbor_list(positions: torch.Tensor, cutoff: float, cell: torch.Tens
     if fill_value is None:
         fill_value = n
     i32 = dict(dtype=torch.int32, device=dev)
+    E.check_outputs(n, dev, neighbor_matrix, neighbor_matrix_shifts if periodic else None, num_neighbors, width=max_neighbors)
     if cutoff <= 0 or n == 0:
         if neighbor_matrix is None:
             neighbor_matrix = torch.full((n, max_neighbors), fill_value, **i32)

@@ -196,6 +196,17 @@ def test_query_api_and_preallocated_buffers():
     assert np.array_equal(_pairs(nm, num, sh), O.canonical_pairs(onm, onum, osh))
     a, b, c = cell_list(tp, 3.0, tc, pbc, neighbor_matrix=nm, neighbor_matrix_shifts=sh, num_neighbors=num)
     assert a.data_ptr() == nm.data_ptr() and b.data_ptr() == num.data_ptr()
+    assert c.data_ptr() == sh.data_ptr()
+    # ... and so do the naive and the batched forms (tests/test_arg_layouts_gpu.py goes through every search entry point)
+    from nvalchemiops.neighborlist import batch_cell_list, batch_naive_neighbor_list, naive_neighbor_list
+
+    bi = torch.zeros(600, dtype=torch.int32, device=DEV)
+    for out in (naive_neighbor_list(tp, 3.0, cell=tc, pbc=pbc, neighbor_matrix=nm, neighbor_matrix_shifts=sh, num_neighbors=num),
+                batch_cell_list(tp, 3.0, tc[None], pbc[None], bi, neighbor_matrix=nm, neighbor_matrix_shifts=sh, num_neighbors=num),
+                batch_naive_neighbor_list(tp, 3.0, batch_idx=bi, cell=tc[None], pbc=pbc[None], neighbor_matrix=nm, neighbor_matrix_shifts=sh,
+                                          num_neighbors=num)):
+        assert [t.data_ptr() for t in out] == [nm.data_ptr(), num.data_ptr(), sh.data_ptr()]
+        assert np.array_equal(_pairs(nm, num, sh), O.canonical_pairs(onm, onum, osh))
 
 
 def test_empty_and_tiny_inputs():
