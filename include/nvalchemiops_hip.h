@@ -370,6 +370,43 @@ int mi_ewald_real_virial(const void* positions, const void* charges, const void*
                          void* stream);
 int mi_ewald_virial_blocks(void);
 
+/* Gaussian-smeared charges: the short-ranged pair correction that, added to a point-charge Ewald / PME / Coulomb energy, gives the energy of
+ * Gaussian charge clouds of per-atom width sigma_i (sigma_i <= 0: point charge).  s = max(sigma, 0)^2, g_ij = sqrt(2 (s_i + s_j)), x = r / g_ij:
+ *     energies[i] = -1/2 sum_{entries (i, j, S) of row i} q_i q_j erfc(x) / r,        r = r_j - r_i + S . cell
+ * over a FULL (symmetric) list -- padded matrix (neighbor_ptr == NULL; entries equal to mask_value or outside [0, n_atoms) are padding) or CSR.
+ * Entries with r <= 1e-8 or x >= 6 (erfc(6) = 2.2e-17) are skipped, and so are pairs of two point charges.  A half list is not detected.
+ * The row owner writes every output (no atomics, deterministic).  Pair vector and r^2 in the positions dtype, everything else fp64 (libm erfc).
+ * weights [n_atoms] float64 or NULL (all ones): entry weight w = (g_i + g_j) / 2 -- the outputs are then the derivatives of
+ * L = sum_i g_i energies[i]:
+ *   MI_GC_FORCES       forces [n_atoms][3] (positions dtype)  = -dL/dr_i = 2 sum_row w fm r,
+ *                      fm = 1/2 q_i q_j (erfc(x)/r^3 + 2/(sqrt(pi) g_ij) exp(-x^2)/r^2)
+ *   MI_GC_CHARGE_GRAD  charge_grads [n_atoms] float64         = dL/dq_i = -sum_row w q_j erfc(x)/r
+ *   MI_GC_SIGMA_GRAD   sigma_grads [n_atoms] float64          = dL/dsigma_i = -(4/sqrt(pi)) q_i sigma_i sum_row w q_j exp(-x^2)/g_ij^3
+ *   MI_GC_VIRIAL       system_partial[s][b][0..5] = block partials of -sum_entries w fm r_a r_b, {xx, yy, zz, xy, xz, yz}
+ *   MI_GC_CELL_GRAD    system_partial[s][b][0..8] = block partials of dL/dcell[a][b] = sum_entries w fm S_a r_b (row-major; not with MI_GC_VIRIAL)
+ * system_partial is [n_systems][mi_gaussian_charges_blocks()][mi_gaussian_charges_row_words()] float64; the caller sums the block dimension.
+ * energies may be NULL (adjoint use).  cell NULL: non-periodic, unit_shifts must be NULL too.  unit_shifts NULL with a cell: all zero.
+ * scratch: mi_gaussian_charges_scratch_bytes(n_atoms, dtype) bytes ({x, y, z, q, sigma} records + per-row tensors), contents undefined.
+ * Self and neutralising-background terms are not part of this entry point (O(N), see nvalchemiops/interactions/electrostatics/gaussian.py). */
+#define MI_GC_FORCES 1
+#define MI_GC_CHARGE_GRAD 2
+#define MI_GC_SIGMA_GRAD 4
+#define MI_GC_VIRIAL 8
+#define MI_GC_CELL_GRAD 16
+size_t mi_gaussian_charges_scratch_bytes(int n_atoms, int dtype);
+int mi_gaussian_charges_blocks(void);
+int mi_gaussian_charges_row_words(void);
+/* The per-system sums of the background term, in a fixed order (no atomics: bit-reproducible, unlike mi_segment_sum, whose one atomic per
+ * wave leaves the last bit to the arrival order): partial [n_systems][mi_gaussian_charges_blocks()][3] float64 = block partials of
+ * {sum q, sum q s, sum g q s} over each system's atoms, s = max(sigma, 0)^2, g = weights or 1 (NULL); the caller sums the block dimension. */
+int mi_gaussian_charges_system_sums(const void* charges, const void* sigma, const double* weights, const int32_t* batch_idx, int n_atoms,
+                                    int n_systems, int dtype, double* partial, void* stream);
+int mi_gaussian_charges(const void* positions, const void* charges, const void* sigma, const void* cell /*[n_systems,3,3] or NULL*/,
+                        const int32_t* batch_idx, const double* weights, int n_atoms, int n_systems, int dtype, const int32_t* idx_j,
+                        const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors, int mask_value, int flags, double* energies,
+                        void* forces, double* charge_grads, double* sigma_grads, double* system_partial, void* scratch, size_t scratch_bytes,
+                        void* stream);
+
 /* Explicit-k reciprocal-space Ewald.  Replaces `alchemiops::_[batch_]ewald_reciprocal_space_energy[_forces
  * [_charge_grad]]` (ewald.py:1365-2318; kernels ewald_kernels.py:1496-2480).  Two passes, no [K,N] phase tables:
  *   mi_ewald_structure_factors : S[b][k] = 8pi/V exp(-k^2/4a^2)/k^2 * sum_j w_j exp(i k.r_j) (interleaved re,im; k^2<1e-10 -> 0)

@@ -31,6 +31,7 @@ SOURCES = {
     # costs v_mov's to pair the operands -- the energy pass is VALU-issue-bound
     "d3.hip": ["-fno-hip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize"] + os.environ.get("MI_D3_EXTRA_FLAGS", "").split(),
     "ewald.hip": os.environ.get("MI_EWALD_EXTRA_FLAGS", "").split(),
+    "gaussian.hip": [],  # Gaussian-smeared charge correction (mi_gaussian_charges): fp64 pair math with libm erfc
     "pme.hip": os.environ.get("MI_PME_EXTRA_FLAGS", "").split(),
     "dft.hip": [],  # dense DFT of any mesh size: the transform of last resort behind the self-tested hipFFT plans
     "calib.hip": [],

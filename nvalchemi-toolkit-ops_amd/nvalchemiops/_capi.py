@@ -115,6 +115,16 @@ def lib() -> ctypes.CDLL:
                            ("mi_gto_fourier", [vp, i, dbl, i, vp, vp, vp])):
             getattr(L, name).restype = i
             getattr(L, name).argtypes = args
+        # Gaussian-smeared charge correction (nvalchemiops/interactions/electrostatics/gaussian.py)
+        L.mi_gaussian_charges.restype = i
+        L.mi_gaussian_charges.argtypes = [vp] * 6 + [i, i, i, vp, vp, vp, i, i, i] + [vp] * 6 + [sz, vp]
+        L.mi_gaussian_charges_system_sums.restype = i
+        L.mi_gaussian_charges_system_sums.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp]
+        L.mi_gaussian_charges_scratch_bytes.restype = sz
+        L.mi_gaussian_charges_scratch_bytes.argtypes = [i, i]
+        for name in ("mi_gaussian_charges_blocks", "mi_gaussian_charges_row_words"):
+            getattr(L, name).restype = i
+            getattr(L, name).argtypes = []
         _LIB = L
     return _LIB
 

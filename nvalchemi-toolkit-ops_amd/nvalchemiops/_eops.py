@@ -1501,7 +1501,89 @@ pme_recip_virial_op.register_fake(lambda positions, charges, cells, alpha, batch
 pme_recip_virial_op.register_autograd(_virial_no_adjoint("nvalchemiops::pme_reciprocal_space_virial"), setup_context=_noop_virial_setup)
 
 
-__all__ = ["spline_spread_op", "batch_spline_spread_op", "spline_gather_op", "batch_spline_gather_op", "spline_gather_vec3_op",
+# =====================================================================================================================================
+# Gaussian-smeared charge correction: one op with optional tensors (single / batch, list / matrix, with / without a cell)
+# =====================================================================================================================================
+# Outputs are always the five of the public function; the ones not asked for are empty [0] tensors.  The energies are differentiable w.r.t.
+# positions, charges, sigma and cell: the backward op runs the forward kernel with the incoming gradient as per-atom weights.
+_GC_NAME = f"{_NS}::_gaussian_charge_correction"
+_GC_OUTPUTS = ("energies", "forces", "charge_gradients", "sigma_gradients", "virial")
+
+
+def _gaussian_fwd(positions: Tensor, charges: Tensor, sigma: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor],
+                  neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
+                  neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int, self_energy: bool,
+                  neutralizing_background: bool, compute_forces: bool, compute_charge_gradients: bool, compute_sigma_gradients: bool,
+                  compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from nvalchemiops.interactions.electrostatics.gaussian import _forward
+
+    out = _forward(positions, charges, sigma, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts,
+                   int(mask_value), self_energy, neutralizing_background, compute_forces, compute_charge_gradients, compute_sigma_gradients,
+                   compute_virial)
+    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
+
+
+def _gaussian_fwd_fake(positions, charges, sigma, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                       neighbor_matrix_shifts, mask_value, self_energy, neutralizing_background, compute_forces, compute_charge_gradients,
+                       compute_sigma_gradients, compute_virial):
+    n = positions.shape[0]
+    nsys = cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1
+    empty = lambda: positions.new_empty((0,))  # noqa: E731
+    return (positions.new_empty((n,)), positions.new_empty((n, 3)) if compute_forces else empty(),
+            positions.new_empty((n,)) if compute_charge_gradients else empty(), positions.new_empty((n,)) if compute_sigma_gradients else empty(),
+            positions.new_empty((nsys, 3, 3)) if compute_virial else empty())
+
+
+def _gaussian_bwd(positions: Tensor, charges: Tensor, sigma: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor],
+                  neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
+                  neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int, self_energy: bool,
+                  neutralizing_background: bool, grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Float64 (dL/dpositions, dL/dcharges, dL/dsigma, dL/dcell [B,3,3] or [0]) for L = sum_i g_i E_i."""
+    from nvalchemiops.interactions.electrostatics.gaussian import _adjoint
+
+    gpos, gq, gs, gcell = _adjoint(positions, charges, sigma, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                                   neighbor_matrix_shifts, int(mask_value), self_energy, neutralizing_background, grad_energies)
+    return gpos, gq, gs, (gcell if gcell is not None else gpos.new_empty((0,)))
+
+
+def _gaussian_bwd_fake(positions, charges, sigma, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                       neighbor_matrix_shifts, mask_value, self_energy, neutralizing_background, grad_energies):
+    n, f64 = positions.shape[0], dict(dtype=torch.float64)
+    nsys = cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1
+    return (positions.new_empty((n, 3), **f64), positions.new_empty((n,), **f64), positions.new_empty((n,), **f64),
+            positions.new_empty((nsys, 3, 3), **f64) if cell is not None else positions.new_empty((0,), **f64))
+
+
+gaussian_bwd_op = torch.library.custom_op("nvalchemiops::gaussian_charge_correction_backward", _gaussian_bwd, mutates_args=())
+gaussian_bwd_op.register_fake(_gaussian_bwd_fake)
+gaussian_bwd_op.register_autograd(lambda ctx, *g: (_ for _ in ()).throw(NotImplementedError(_SECOND_ORDER.format(
+    op="nvalchemiops::gaussian_charge_correction_backward", what="gradient"))), setup_context=lambda ctx, inputs, output: None)
+
+
+def _gaussian_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:10])
+    ctx.mask, ctx.self_energy, ctx.background = inputs[10], inputs[11], inputs[12]
+    ctx.set_materialize_grads(False)
+
+
+def _gaussian_backward(ctx, g_e, *g_explicit):
+    for what, g in zip(_GC_OUTPUTS[1:], g_explicit):
+        if g is not None:
+            raise NotImplementedError(_SECOND_ORDER.format(op=_GC_NAME, what=what))
+    need = ctx.needs_input_grad
+    if g_e is None:
+        return (None,) * len(need)
+    saved = ctx.saved_tensors
+    positions, charges, sigma, cell = saved[:4]
+    gpos, gq, gs, gcell = gaussian_bwd_op(*saved, int(ctx.mask), bool(ctx.self_energy), bool(ctx.background), g_e)
+    return (gpos.to(positions.dtype) if need[0] else None, gq.to(charges.dtype) if need[1] else None, gs.to(sigma.dtype) if need[2] else None,
+            gcell.reshape(cell.shape).to(cell.dtype) if (cell is not None and need[3]) else None) + (None,) * (len(need) - 4)
+
+
+gaussian_charge_correction_op = _op("_gaussian_charge_correction", _gaussian_fwd, _gaussian_fwd_fake, _gaussian_backward, _gaussian_setup)
+
+
+__all__ = ["gaussian_charge_correction_op", "gaussian_bwd_op", "spline_spread_op", "batch_spline_spread_op", "spline_gather_op", "batch_spline_gather_op", "spline_gather_vec3_op",
            "batch_spline_gather_vec3_op", "spline_gather_gradient_op", "batch_spline_gather_gradient_op", "pme_green_structure_factor_op",
            "batch_pme_green_structure_factor_op", "pme_energy_corrections_op", "batch_pme_energy_corrections_op",
            "pme_energy_corrections_with_charge_grad_op", "batch_pme_energy_corrections_with_charge_grad_op", "REAL_OPS", "real_space_op", "RECIPROCAL_OPS", "reciprocal_space_op", "COULOMB_OPS", "coulomb_op",
