@@ -407,6 +407,48 @@ int mi_gaussian_charges(const void* positions, const void* charges, const void* 
                         void* forces, double* charge_grads, double* sigma_grads, double* system_partial, void* scratch, size_t scratch_bytes,
                         void* stream);
 
+/* Charge equilibration (csrc/qeq.hip; driver: nvalchemiops/interactions/electrostatics/qeq.py): the real-space Hessian of the Gaussian-charge
+ * electrostatic energy as a stored sparse operator over the caller's FULL list, its product, and the vector kernels of a batched projected
+ * conjugate-gradient solve of  min_q sum chi_i q_i + 1/2 sum J_i q_i^2 + E_el(q),  sum_{i in s} q_i = Q_s.  All arithmetic is fp64; only the
+ * pair vector and r are formed in the positions dtype.  No atomics anywhere: every per-system sum is a fixed-order fold into
+ * mi_qeq_blocks() block partials that the next kernel sums itself, so these entry points are bit-reproducible (a periodic solve also calls the
+ * reciprocal-space entry points, which are not).  Nothing synchronises with the host.  n_systems <= 65535 wherever per-system sums are formed
+ * (one grid row per system; every block scans batch_idx: O(n_atoms n_systems) index reads per launch).
+ *
+ * mi_qeq_pair_coefficients (once per geometry): for every slot e of the list layout -- padded matrix [n_atoms][max_neighbors]
+ *   (neighbor_ptr == NULL) or CSR -- with row i, neighbour j, unit shift S, r = |r_j - r_i + S . cell|, g_ij = sqrt(2 (s_i + s_j)), s = max(sigma, 0)^2:
+ *     coefficients[e] = [erfc_AS(alpha_s r) - erfc(r / g_ij)] / r   with a cell (erfc_AS: the polynomial of mi_ewald_real; erfc: libm, as mi_gaussian_charges)
+ *     coefficients[e] = [1 - erfc(r / g_ij)] / r                    cell == NULL (alpha is not read; unit_shifts must be NULL)
+ *     neighbors[e]    = j
+ *   r <= 1e-8: no contribution.  The erfc(r / g_ij) term is dropped for r / g_ij >= 6 and for two point charges, as mi_gaussian_charges does.
+ *   Padding (matrix entries equal to mask_value, any index outside [0, n_atoms)) and entries without contribution get coefficient 0 and
+ *   neighbors[e] = i, so neighbors[] is always safe to gather with.  12 bytes per slot.
+ *     diagonal[i]     = hardness[i] + [sigma_i > 0] / (sqrt(pi) sigma_i)
+ *   sigma, cell [n_systems,3,3], alpha [n_systems] in the positions dtype; hardness float64.  batch_idx is read only with a cell and n_systems > 1.
+ * mi_qeq_apply:  y[i] = (y_in ? y_in[i] : 0) + diagonal[i] x[i] + sum_{slots e of row i} coefficients[e] x[neighbors[e]]   (one wave64 per row;
+ *   y_in may be y, x must not be).  partial (may be NULL): [n_systems][mi_qeq_blocks()][2] block partials of {sum_i y_i, sum_i x_i y_i} per system.
+ * State of a solve: [n_systems][mi_qeq_state_words()] float64 = {r.r, b.b, done, iterations, alpha, beta, -, -}; every kernel reads state_in
+ *   and writes state_out (two buffers used alternately; a fresh solve starts from zeros).  counts [n_systems] float64 = atoms per system.
+ * mi_qeq_cg_update(mode 0): from partial_y = the partials of y = H p:  w = y - mean_s(y),  alpha_s = r.r / p.y,  q += alpha p,  r -= alpha w,
+ *   partial_rr [n_systems][mi_qeq_blocks()] = block partials of the new r.r.  A done system, or one with p.y <= 0 (then marked done), is not touched.
+ *   mode 1 (set-up): r = -(y - mean_s(y)) for y = chi + H q0; q and p are not used.
+ * mi_qeq_cg_direction(mode 0): beta_s = r.r_new / r.r_old,  p = r + beta p,  iterations += 1,  done = r.r_new <= tolerance^2 b.b; done systems
+ *   are frozen.  mode 1 (set-up): b.b = r.r, p = r, iterations = 0, done at once when b.b == 0 (also one-atom and empty systems).
+ *   mode 2 (restart, warm start): as mode 1 but b.b is kept from state_in. */
+int mi_qeq_blocks(void);
+int mi_qeq_state_words(void);
+int mi_qeq_pair_coefficients(const void* positions, const void* sigma, const double* hardness, const void* cell /*[n_systems,3,3] or NULL*/,
+                             const void* alpha /*[n_systems], NULL without a cell*/, const int32_t* batch_idx, int n_atoms, int n_systems, int dtype,
+                             const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors, int mask_value,
+                             double* coefficients, int32_t* neighbors, double* diagonal, void* stream);
+int mi_qeq_apply(const double* coefficients, const int32_t* neighbors, const double* diagonal, const double* x, const double* y_in,
+                 const int32_t* batch_idx, int n_atoms, int n_systems, const int32_t* neighbor_ptr, int max_neighbors, double* y, double* partial,
+                 void* stream);
+int mi_qeq_cg_update(const double* y, const double* partial_y, const double* counts, const int32_t* batch_idx, int n_atoms, int n_systems, int mode,
+                     double* q, double* r, const double* p, const double* state_in, double* state_out, double* partial_rr, void* stream);
+int mi_qeq_cg_direction(const double* partial_rr, const int32_t* batch_idx, int n_atoms, int n_systems, int mode, double tolerance, const double* r,
+                        double* p, const double* state_in, double* state_out, void* stream);
+
 /* Explicit-k reciprocal-space Ewald.  Replaces `alchemiops::_[batch_]ewald_reciprocal_space_energy[_forces
  * [_charge_grad]]` (ewald.py:1365-2318; kernels ewald_kernels.py:1496-2480).  Two passes, no [K,N] phase tables:
  *   mi_ewald_structure_factors : S[b][k] = 8pi/V exp(-k^2/4a^2)/k^2 * sum_j w_j exp(i k.r_j) (interleaved re,im; k^2<1e-10 -> 0)

@@ -125,6 +125,18 @@ def lib() -> ctypes.CDLL:
         for name in ("mi_gaussian_charges_blocks", "mi_gaussian_charges_row_words"):
             getattr(L, name).restype = i
             getattr(L, name).argtypes = []
+        # charge equilibration (nvalchemiops/interactions/electrostatics/qeq.py)
+        L.mi_qeq_pair_coefficients.restype = i
+        L.mi_qeq_pair_coefficients.argtypes = [vp] * 6 + [i, i, i, vp, vp, vp, i, i, vp, vp, vp, vp]
+        L.mi_qeq_apply.restype = i
+        L.mi_qeq_apply.argtypes = [vp] * 6 + [i, i, vp, i, vp, vp, vp]
+        L.mi_qeq_cg_update.restype = i
+        L.mi_qeq_cg_update.argtypes = [vp] * 4 + [i, i, i] + [vp] * 7
+        L.mi_qeq_cg_direction.restype = i
+        L.mi_qeq_cg_direction.argtypes = [vp, vp, i, i, i, dbl, vp, vp, vp, vp, vp]
+        for name in ("mi_qeq_blocks", "mi_qeq_state_words"):
+            getattr(L, name).restype = i
+            getattr(L, name).argtypes = []
         _LIB = L
     return _LIB
 

@@ -7,6 +7,7 @@ from nvalchemiops.interactions.electrostatics.k_vectors import generate_k_vector
 from nvalchemiops.interactions.electrostatics.parameters import (EwaldParameters, PMEParameters, estimate_ewald_parameters,
                                                                  estimate_pme_mesh_dimensions, estimate_pme_parameters,
                                                                  mesh_spacing_to_dimensions)
+from nvalchemiops.interactions.electrostatics.qeq import ChargeEquilibrationError, ChargeEquilibrationResult, charge_equilibration
 from nvalchemiops.interactions.electrostatics.pme import (particle_mesh_ewald, pme_energy_corrections,
                                                           particle_mesh_ewald_with_virial, pme_energy_corrections_with_charge_grad,
                                                           pme_green_structure_factor, pme_reciprocal_space, pme_reciprocal_space_with_virial)
@@ -16,5 +17,5 @@ __all__ = [
     "pme_energy_corrections_with_charge_grad", "generate_k_vectors_pme", "estimate_pme_parameters", "estimate_ewald_parameters",
     "estimate_pme_mesh_dimensions", "mesh_spacing_to_dimensions", "PMEParameters", "EwaldParameters", "ewald_reciprocal_space", "ewald_summation", "generate_k_vectors_ewald_summation",
     "ewald_real_space_with_virial", "pme_reciprocal_space_with_virial", "particle_mesh_ewald_with_virial", "ewald_reciprocal_space_with_virial",
-    "ewald_summation_with_virial", "gaussian_charge_correction",
+    "ewald_summation_with_virial", "gaussian_charge_correction", "charge_equilibration", "ChargeEquilibrationError", "ChargeEquilibrationResult",
 ]
