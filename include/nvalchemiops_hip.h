@@ -322,6 +322,47 @@ int mi_d3_zero_atm(const void* positions, const int32_t* numbers, int n_atoms, i
                    const float* r0ab /* [nz,nz] */, int compute_virial, float* energy, float* forces, float* virial,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- DFT-D4 two-body dispersion (csrc/d4.hip) -------------------------------------------------------------------------------------
+ * No reference counterpart.  The D4 two-body energy with Becke-Johnson damping and a C6 that depends on each atom's coordination number
+ * AND partial charge, over the entries (i, j, S) of a FULL list in either layout of mi_d3 (r = r_j - r_i + S . cell).  Tables are indexed
+ * by Z (index 0 = padding), element Z has n_ref[Z] <= 7 references a with cn_ref[Z,a], q_ref[Z,a], ngw[Z,a] in {1,2,3}:
+ *   CN_i    = sum_row delta(Z_i,Z_j) 1/2 (1 + erf(-k_cn (r / (rcov_i + rcov_j) - 1))),  delta = k4 exp(-(|en_i - en_j| + k5)^2 / k6);
+ *             with cn_cutoff > 0 entries with r >= cn_cutoff do not count (hard cut), cn_cutoff <= 0: every stored entry counts
+ *   g_a     = sum_{s=1..ngw_a} exp(-wf s (CN_i - cn_ref_a)^2),   W_a = g_a / sum_b g_b          (evaluated max-shifted: never 0/0)
+ *   zeta_a  = exp(ga (1 - exp(gc gam[Z] (1 - (zeff[Z] + q_ref_a) / (zeff[Z] + q_i)))))   if zeff[Z] + q_i > 0,  else exp(ga)
+ *   w_i[a]  = W_a zeta_a,   C6_ij = sum_ab w_i[a] c6_ref[Z_i,Z_j,a,b] w_j[b]              (c6_ref[A,B,a,b] = c6_ref[B,A,b,a] is required)
+ *   E       = 1/2 sum_entries -C6_ij (s6 / (r^6 + R0^6) + s8 Q / (r^8 + R0^8)),   Q = 3 r4r2_i r4r2_j,  R0 = a1 sqrt(Q) + a2
+ * Table entries with reference index >= n_ref[Z] are never used, whatever they hold.  Atoms with Z <= 0, Z >= nz or n_ref[Z] = 0 are
+ * padding: part of no pair and of no CN, their force, CN and dE/dq are 0.  Entries with r <= 1e-8 contribute nothing.
+ * Outputs (float32 whatever `dtype`): energy per system, forces at fixed charges including the path through the coordination numbers,
+ * coord_num, charge_grad = dE/dq_i, virial = -dE/d(strain) (needs cell and unit_shifts).  No atomics: two identical calls give
+ * bit-identical outputs.  mi_d4_species_slots(): distinct species of one call whose contracted C6 vectors a wave holds in LDS at once;
+ * with more species present a row is walked once per group of that many (same results).  n_list_entries is accepted for symmetry with
+ * mi_d3 and not read.                                                                                                                   */
+typedef struct {
+  const float* rcov;     /* [nz]          used as given                     */
+  const float* en;       /* [nz]          electronegativities               */
+  const float* r4r2;     /* [nz]                                            */
+  const float* zeff;     /* [nz]          effective nuclear charges         */
+  const float* gam;      /* [nz]          chemical hardnesses               */
+  const int32_t* n_ref;  /* [nz]          references per element, 0 ... 7   */
+  const int32_t* ngw;    /* [nz,7]        Gaussian weights per reference    */
+  const float* cn_ref;   /* [nz,7]                                          */
+  const float* q_ref;    /* [nz,7]                                          */
+  const float* c6_ref;   /* [nz,nz,7,7]                                     */
+  int nz;                /* max_Z + 1                                       */
+  float a1, a2, s6, s8, k_cn, k4, k5, k6, wf, ga, gc;
+  float cn_cutoff;       /* <= 0: none                                      */
+} mi_d4_params;
+size_t mi_d4_workspace_bytes(int n_atoms, int n_systems, int nz);
+int mi_d4_species_slots(void);
+int mi_d4(const void* positions, const int32_t* numbers, int n_atoms, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
+          const int32_t* neighbor_ptr /* NULL => matrix layout */, int max_neighbors, long long n_list_entries, int fill_value,
+          const void* cell, const int32_t* batch_idx, int n_systems, const mi_d4_params* params /* [host] */,
+          const float* charges /* [n_atoms] */, int compute_virial, float* energy /*[n_systems]*/, float* forces /*[n_atoms,3]*/,
+          float* coord_num /*[n_atoms]*/, float* charge_grad /*[n_atoms]*/, float* virial /*[n_systems,3,3] or NULL*/,
+          void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Ewald real space -----------------------------------------------------------------------
  * Replaces the 12 alchemiops::_[batch_]ewald_real_space_* ops (ewald.py:263-1365; kernels
  * ewald_kernels.py:266-1495): erfc(A&S 7.1.26)-damped pair sum over the stored neighbour entries.

@@ -33,6 +33,7 @@ SOURCES = {
     "ewald.hip": os.environ.get("MI_EWALD_EXTRA_FLAGS", "").split(),
     "gaussian.hip": [],  # Gaussian-smeared charge correction (mi_gaussian_charges): fp64 pair math with libm erfc
     "qeq.hip": [],  # charge equilibration (mi_qeq_*): stored pair operator, its product and the CG vector kernels, all fp64
+    "d4.hip": [],  # DFT-D4 two-body dispersion (mi_d4): fp32 pair math with IEEE divide / sqrt and libm erff / expf, fp64 sums
     "pme.hip": os.environ.get("MI_PME_EXTRA_FLAGS", "").split(),
     "dft.hip": [],  # dense DFT of any mesh size: the transform of last resort behind the self-tested hipFFT plans
     "calib.hip": [],

@@ -37,6 +37,13 @@ class MiD3ZeroParams(ctypes.Structure):
     _fields_ = [("rs6", ctypes.c_float), ("rs8", ctypes.c_float), ("alpha", ctypes.c_float), ("beta", ctypes.c_float), ("r0ab", ctypes.c_void_p)]
 
 
+class MiD4Params(ctypes.Structure):
+    """`mi_d4_params` of include/nvalchemiops_hip.h: the D4 element tables (device pointers) and the scalars of the model."""
+    _fields_ = ([(name, ctypes.c_void_p) for name in ("rcov", "en", "r4r2", "zeff", "gam", "n_ref", "ngw", "cn_ref", "q_ref", "c6_ref")]
+                + [("nz", ctypes.c_int)]
+                + [(name, ctypes.c_float) for name in ("a1", "a2", "s6", "s8", "k_cn", "k4", "k5", "k6", "wf", "ga", "gc", "cn_cutoff")])
+
+
 class MiNlCnRequest(ctypes.Structure):
     """`mi_nl_cn_request` of include/nvalchemiops_hip.h: what a search needs to sum DFT-D3 coordination numbers over the list it writes."""
     _fields_ = [("numbers", ctypes.c_void_p), ("covalent_radii", ctypes.c_void_p), ("nz", ctypes.c_int), ("k1", ctypes.c_float)]
@@ -90,8 +97,15 @@ def lib() -> ctypes.CDLL:
                                           ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_float,
                                           ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4
                                          + [ctypes.c_size_t, ctypes.c_void_p])
-        # the virial entry points (forward-only -dE/d(strain) of the Ewald / PME sums)
         vp, i, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+        if hasattr(L, "mi_d4"):  # DFT-D4 two-body dispersion (nvalchemiops/interactions/dispersion/dftd4.py)
+            L.mi_d4_workspace_bytes.restype = sz
+            L.mi_d4_workspace_bytes.argtypes = [i, i, i]
+            L.mi_d4_species_slots.restype = i
+            L.mi_d4_species_slots.argtypes = []
+            L.mi_d4.restype = i
+            L.mi_d4.argtypes = [vp, vp, i, i, vp, vp, vp, i, ctypes.c_longlong, i, vp, vp, i, vp, vp, i] + [vp] * 6 + [sz, vp]
+        # the virial entry points (forward-only -dE/d(strain) of the Ewald / PME sums)
         L.mi_ewald_real_virial.restype = i
         L.mi_ewald_real_virial.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, i, i, i, vp, vp, vp, vp, sz, vp, i, i, vp, vp, vp]
         L.mi_ewald_recip_virial.restype = i

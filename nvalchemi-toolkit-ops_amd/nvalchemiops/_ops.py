@@ -8,6 +8,7 @@ need an opaque, mutation-annotated op -- finds the same ops as in the reference:
     nvalchemiops::dftd3_atm_nm / ::dftd3_atm_nl                     (this build's own: the three-body term, same shape as the two above)
     nvalchemiops::dftd3_zero_nm / ::dftd3_zero_nl                   (this build's own: zero damping, D3(0) / D3M(0); same shape again)
     nvalchemiops::dftd3_zero_atm_nm / ::dftd3_zero_atm_nl           (this build's own: the three-body term with the radii of the zero damping)
+    nvalchemiops::dftd4_nm / ::dftd4_nl                             (this build's own: DFT-D4 two-body dispersion; forward only)
 
     nvalchemiops::_cell_list_needs_rebuild / ::_neighbor_list_needs_rebuild   (rebuild_detection.py:258, :386)
 
@@ -39,6 +40,7 @@ from nvalchemiops.neighborlist import naive as _naive
 from nvalchemiops.neighborlist import rebuild_detection as _rd
 
 _d3 = importlib.import_module("nvalchemiops.interactions.dispersion.dftd3")
+_d4 = importlib.import_module("nvalchemiops.interactions.dispersion.dftd4")
 _bcl = importlib.import_module("nvalchemiops.neighborlist.batch_cell_list")
 _cl = importlib.import_module("nvalchemiops.neighborlist.cell_list")
 
@@ -237,6 +239,44 @@ def _dftd3_zero_atm_nl_op(positions: torch.Tensor, numbers: torch.Tensor, idx_j:
         _d3._launch_atm(positions, numbers, C.i32(idx_j), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, energy.shape[0],
                         (covalent_radii, r4r2, c6_reference, coord_num_ref), _d3.atm_scalars(0.0, 0.0, k1, k3), s9, alpha, three_body_cutoff,
                         compute_virial, energy, forces, virial, zero=(rs9, cutoff_radii))
+
+
+@torch.library.custom_op("nvalchemiops::dftd4_nm", mutates_args=("energy", "forces", "coord_num", "charge_grad", "virial"))
+def _dftd4_nm_op(positions: torch.Tensor, numbers: torch.Tensor, charges: torch.Tensor, neighbor_matrix: torch.Tensor, rcov: torch.Tensor,
+                 en: torch.Tensor, r4r2: torch.Tensor, zeff: torch.Tensor, gam: torch.Tensor, n_ref: torch.Tensor, ngw: torch.Tensor,
+                 cn_ref: torch.Tensor, q_ref: torch.Tensor, c6_ref: torch.Tensor, a1: float, a2: float, s8: float, energy: torch.Tensor,
+                 forces: torch.Tensor, coord_num: torch.Tensor, charge_grad: torch.Tensor, virial: torch.Tensor, s6: float = 1.0,
+                 cn_cutoff: float | None = None, wf: float = 6.0, ga: float = 3.0, gc: float = 2.0, k_cn: float = 7.5,
+                 fill_value: int | None = None, batch_idx: torch.Tensor | None = None, cell: torch.Tensor | None = None,
+                 neighbor_matrix_shifts: torch.Tensor | None = None, compute_virial: bool = False) -> None:
+    """DFT-D4 two-body dispersion on a padded matrix (`mi_d4`; no reference counterpart), mutating like `dftd3_nm`.  No autograd."""
+    n = positions.shape[0]
+    if n == 0:
+        return
+    C.require_device(positions, numbers, charges, neighbor_matrix, batch_idx, energy, forces, coord_num, charge_grad)
+    nm = C.i32(neighbor_matrix)
+    with _device_of(positions):
+        _d4._launch(positions, numbers, charges, nm, neighbor_matrix_shifts, None, nm.shape[1], n if fill_value is None else fill_value, cell,
+                    batch_idx, energy.shape[0], (rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref),
+                    _d4.d4_scalars(a1, a2, s6, s8, k_cn, wf, ga, gc, cn_cutoff), compute_virial, energy, forces, coord_num, charge_grad, virial)
+
+
+@torch.library.custom_op("nvalchemiops::dftd4_nl", mutates_args=("energy", "forces", "coord_num", "charge_grad", "virial"))
+def _dftd4_nl_op(positions: torch.Tensor, numbers: torch.Tensor, charges: torch.Tensor, idx_j: torch.Tensor, neighbor_ptr: torch.Tensor,
+                 rcov: torch.Tensor, en: torch.Tensor, r4r2: torch.Tensor, zeff: torch.Tensor, gam: torch.Tensor, n_ref: torch.Tensor,
+                 ngw: torch.Tensor, cn_ref: torch.Tensor, q_ref: torch.Tensor, c6_ref: torch.Tensor, a1: float, a2: float, s8: float,
+                 energy: torch.Tensor, forces: torch.Tensor, coord_num: torch.Tensor, charge_grad: torch.Tensor, virial: torch.Tensor,
+                 s6: float = 1.0, cn_cutoff: float | None = None, wf: float = 6.0, ga: float = 3.0, gc: float = 2.0, k_cn: float = 7.5,
+                 batch_idx: torch.Tensor | None = None, cell: torch.Tensor | None = None, unit_shifts: torch.Tensor | None = None,
+                 compute_virial: bool = False) -> None:
+    """DFT-D4 two-body dispersion on a CSR list (`mi_d4`), mutating like `dftd3_nl`.  No autograd."""
+    if positions.shape[0] == 0:
+        return
+    C.require_device(positions, numbers, charges, idx_j, neighbor_ptr, batch_idx, energy, forces, coord_num, charge_grad)
+    with _device_of(positions):
+        _d4._launch(positions, numbers, charges, C.i32(idx_j), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, energy.shape[0],
+                    (rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref), _d4.d4_scalars(a1, a2, s6, s8, k_cn, wf, ga, gc, cn_cutoff),
+                    compute_virial, energy, forces, coord_num, charge_grad, virial)
 
 
 # ---- this build's own ops behind the high-level entry points -----------------------------------------------------------------
