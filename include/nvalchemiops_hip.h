@@ -363,6 +363,34 @@ int mi_d4(const void* positions, const int32_t* numbers, int n_atoms, int dtype,
           float* coord_num /*[n_atoms]*/, float* charge_grad /*[n_atoms]*/, float* virial /*[n_systems,3,3] or NULL*/,
           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- DFT-D4 three-body (Axilrod-Teller-Muto) term (csrc/d4_atm.h) --------------------------------------------------------------------
+ * No reference counterpart.  For every unordered triple of distinct atom images A, B, C whose three distances are all
+ * < three_body_cutoff:
+ *   E_ABC  = s9 sqrt(C6_AB C6_AC C6_BC) ang fdamp
+ *   ang    = 0.375 (a + b - c)(a + c - b)(b + c - a) / P^5 + 1 / P^3        a, b, c squared sides, P product of the sides
+ *   fdamp  = 1 / (1 + 6 (R0_AB R0_AC R0_BC / P)^(alpha / 3)),               R0_XY = a1 sqrt(3 r4r2_X r4r2_Y) + a2
+ *   C6_XY  = sum_ab w_X[a] c6_ref[Z_X,Z_Y,a,b] w_Y[b],                      w_X[a] = W_a(CN_X) zeta_a(q = 0)
+ * W_a, zeta_a, the coordination number (erf count, electronegativity factor, optional hard cn_cutoff) and the padding rules (Z <= 0,
+ * Z >= nz, n_ref[Z] = 0; table entries beyond n_ref are never read) are exactly mi_d4's.  The charge scaling is evaluated at q = 0 for
+ * every atom -- D4's definition of the term -- so there is no charges argument and no dE/dq output; zeta_a(0) is not 1: it depends on q_ref,
+ * zeff, gam, ga and gc.  CN is summed over ALL stored entries of the list (subject to cn_cutoff); entries beyond three_body_cutoff only
+ * count for CN.  A triple with any C6 < 1e-12 contributes nothing.  Each triple counts once per unit cell.
+ * Outputs are the three-body contribution alone, float32, to be ADDED to mi_d4's: energy per system, forces = -dE/dr including the path
+ * through the coordination numbers, virial in mi_d4's convention (needs cell and unit_shifts).  params->s6 / s8 are not used.  The list
+ * (either layout) must be a FULL list with a cutoff >= three_body_cutoff.  No atomics: two identical calls give bit-identical outputs.
+ * Requires finite three_body_cutoff > 0, alpha > 0 and s9.  After the call the n_atoms uint32 at byte mi_d4_atm_visits_offset(...) of the
+ * workspace hold, per centre atom, the number of triangles visited from it (each triangle is visited from its three vertices; a diagnostic
+ * for benchmarks).  mi_d4_atm_tile(): neighbours inside three_body_cutoff a row may have before the triple pass works tile by tile
+ * (results do not depend on it).  More species in one call than mi_d4_species_slots(): same results, slower.                            */
+size_t mi_d4_atm_workspace_bytes(int n_atoms, int n_systems, int nz);
+size_t mi_d4_atm_visits_offset(int n_atoms, int n_systems, int nz);
+int mi_d4_atm_tile(void);
+int mi_d4_atm(const void* positions, const int32_t* numbers, int n_atoms, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
+              const int32_t* neighbor_ptr /* NULL => matrix layout */, int max_neighbors, int fill_value, const void* cell,
+              const int32_t* batch_idx, int n_systems, const mi_d4_params* params /* [host] */, float s9, float alpha,
+              float three_body_cutoff, int compute_virial, float* energy /*[n_systems]*/, float* forces /*[n_atoms,3]*/,
+              float* virial /*[n_systems,3,3] or NULL*/, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Ewald real space -----------------------------------------------------------------------
  * Replaces the 12 alchemiops::_[batch_]ewald_real_space_* ops (ewald.py:263-1365; kernels
  * ewald_kernels.py:266-1495): erfc(A&S 7.1.26)-damped pair sum over the stored neighbour entries.

@@ -501,6 +501,8 @@ int d4_impl(const T* positions, const int32_t* numbers, int N, const int32_t* id
   return MI_OK;
 }
 
+#include "d4_atm.h"  // the three-body term: the triple pass and its driver, on the kernels above
+
 }  // namespace
 
 extern "C" int mi_d4_species_slots(void) { return D4_SLOTS; }
@@ -540,4 +542,51 @@ extern "C" int mi_d4(const void* positions, const int32_t* numbers, int n_atoms,
   if (dtype == MI_F32) { if (csr) MI_D4_CALL(float, true); else MI_D4_CALL(float, false); }
   else { if (csr) MI_D4_CALL(double, true); else MI_D4_CALL(double, false); }
 #undef MI_D4_CALL
+}
+
+// ---- the three-body (Axilrod-Teller-Muto) term: csrc/d4_atm.h -----------------------------------------------------------------------------
+extern "C" size_t mi_d4_atm_workspace_bytes(int n_atoms, int n_systems, int nz) {
+  if (n_atoms < 0 || nz < 1 || n_systems < 1) return 0;
+  return d4_atm_layout(n_atoms, n_systems, nz).total;
+}
+
+extern "C" size_t mi_d4_atm_visits_offset(int n_atoms, int n_systems, int nz) {
+  if (n_atoms < 0 || nz < 1 || n_systems < 1) return 0;
+  return d4_atm_layout(n_atoms, n_systems, nz).visits;
+}
+
+extern "C" int mi_d4_atm_tile(void) { return D4_ATM_TILE; }
+
+extern "C" int mi_d4_atm(const void* positions, const int32_t* numbers, int n_atoms, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
+                         const int32_t* neighbor_ptr, int max_neighbors, int fill_value, const void* cell, const int32_t* batch_idx, int n_systems,
+                         const mi_d4_params* params, float s9, float alpha, float three_body_cutoff, int compute_virial, float* energy,
+                         float* forces, float* virial, void* workspace, size_t workspace_bytes, void* stream) {
+  MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
+  MI_REQUIRE(n_atoms >= 0 && n_systems >= 1, "sizes");
+  MI_REQUIRE(neighbor_ptr || max_neighbors >= 0, "max_neighbors must not be negative");
+  MI_REQUIRE(n_systems == 1 || batch_idx, "batch_idx is required for more than one system");
+  MI_REQUIRE(std::isfinite(three_body_cutoff) && three_body_cutoff > 0.0f && std::isfinite(alpha) && alpha > 0.0f,
+             "three_body_cutoff and alpha must be positive and finite");
+  MI_REQUIRE(std::isfinite(s9), "s9 must be finite");
+  if (n_atoms == 0) return MI_OK;
+  MI_REQUIRE(positions && numbers && params && energy && forces && workspace, "null pointer");
+  MI_REQUIRE(idx_j || neighbor_ptr || max_neighbors == 0, "idx_j is NULL (only a CSR list without entries has none)");
+  MI_REQUIRE(params->rcov && params->en && params->r4r2 && params->zeff && params->gam && params->n_ref && params->ngw && params->cn_ref &&
+                 params->q_ref && params->c6_ref && params->nz >= 2,
+             "D4 parameter tables");
+  MI_REQUIRE(params->k6 > 0.0f, "k6 must be positive");
+  MI_REQUIRE(!compute_virial || (virial && cell && unit_shifts), "virial needs its output, a cell and unit shifts");
+  MI_REQUIRE(!unit_shifts || cell, "unit_shifts without a cell");
+  const D4AtmLayout L = d4_atm_layout(n_atoms, n_systems, params->nz);
+  if (workspace_bytes < L.total) { mi_set_error("workspace too small: %zu < %zu", workspace_bytes, L.total); return MI_EWORKSPACE; }
+  MI_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const int32_t* bi = n_systems > 1 ? batch_idx : nullptr;  // one system: every atom belongs to system 0 and the batch index is not read
+  const bool csr = neighbor_ptr != nullptr;
+#define MI_D4_ATM_CALL(T_, CSR_)                                                                                                                       \
+  return d4_atm_impl<T_, CSR_>((const T_*)positions, numbers, n_atoms, idx_j, unit_shifts, neighbor_ptr, max_neighbors, fill_value, (const T_*)cell, bi, \
+                               n_systems, params, s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial, (char*)workspace, L, st)
+  if (dtype == MI_F32) { if (csr) MI_D4_ATM_CALL(float, true); else MI_D4_ATM_CALL(float, false); }
+  else { if (csr) MI_D4_ATM_CALL(double, true); else MI_D4_ATM_CALL(double, false); }
+#undef MI_D4_ATM_CALL
 }

@@ -105,6 +105,15 @@ def lib() -> ctypes.CDLL:
             L.mi_d4_species_slots.argtypes = []
             L.mi_d4.restype = i
             L.mi_d4.argtypes = [vp, vp, i, i, vp, vp, vp, i, ctypes.c_longlong, i, vp, vp, i, vp, vp, i] + [vp] * 6 + [sz, vp]
+        if hasattr(L, "mi_d4_atm"):  # ... and its three-body (Axilrod-Teller-Muto) term: mi_d3_atm's argument list with the D4 tables
+            for name in ("mi_d4_atm_workspace_bytes", "mi_d4_atm_visits_offset"):
+                getattr(L, name).restype = sz
+                getattr(L, name).argtypes = [i, i, i]
+            L.mi_d4_atm_tile.restype = i
+            L.mi_d4_atm_tile.argtypes = []
+            L.mi_d4_atm.restype = i
+            L.mi_d4_atm.argtypes = ([vp, vp, i, i, vp, vp, vp, i, i, vp, vp, i, vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, i] + [vp] * 4
+                                    + [sz, vp])
         # the virial entry points (forward-only -dE/d(strain) of the Ewald / PME sums)
         L.mi_ewald_real_virial.restype = i
         L.mi_ewald_real_virial.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, i, i, i, vp, vp, vp, vp, sz, vp, i, i, vp, vp, vp]

@@ -9,6 +9,7 @@ need an opaque, mutation-annotated op -- finds the same ops as in the reference:
     nvalchemiops::dftd3_zero_nm / ::dftd3_zero_nl                   (this build's own: zero damping, D3(0) / D3M(0); same shape again)
     nvalchemiops::dftd3_zero_atm_nm / ::dftd3_zero_atm_nl           (this build's own: the three-body term with the radii of the zero damping)
     nvalchemiops::dftd4_nm / ::dftd4_nl                             (this build's own: DFT-D4 two-body dispersion; forward only)
+    nvalchemiops::dftd4_atm_nm / ::dftd4_atm_nl                     (this build's own: the DFT-D4 three-body term; forward only)
 
     nvalchemiops::_cell_list_needs_rebuild / ::_neighbor_list_needs_rebuild   (rebuild_detection.py:258, :386)
 
@@ -277,6 +278,64 @@ def _dftd4_nl_op(positions: torch.Tensor, numbers: torch.Tensor, charges: torch.
         _d4._launch(positions, numbers, charges, C.i32(idx_j), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, energy.shape[0],
                     (rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref), _d4.d4_scalars(a1, a2, s6, s8, k_cn, wf, ga, gc, cn_cutoff),
                     compute_virial, energy, forces, coord_num, charge_grad, virial)
+
+
+_D4_ATM_OUT = ("energy", "forces", "virial")
+
+
+@torch.library.custom_op("nvalchemiops::dftd4_atm_nm", mutates_args=_D4_ATM_OUT)
+def _dftd4_atm_nm_op(positions: torch.Tensor, numbers: torch.Tensor, neighbor_matrix: torch.Tensor, rcov: torch.Tensor, en: torch.Tensor,
+                     r4r2: torch.Tensor, zeff: torch.Tensor, gam: torch.Tensor, n_ref: torch.Tensor, ngw: torch.Tensor, cn_ref: torch.Tensor,
+                     q_ref: torch.Tensor, c6_ref: torch.Tensor, a1: float, a2: float, three_body_cutoff: float, energy: torch.Tensor,
+                     forces: torch.Tensor, virial: torch.Tensor, s9: float = 1.0, alpha: float = 16.0, cn_cutoff: float | None = None,
+                     wf: float = 6.0, ga: float = 3.0, gc: float = 2.0, k_cn: float = 7.5, fill_value: int | None = None,
+                     batch_idx: torch.Tensor | None = None, cell: torch.Tensor | None = None,
+                     neighbor_matrix_shifts: torch.Tensor | None = None, compute_virial: bool = False) -> None:
+    """The DFT-D4 three-body term on a padded matrix (`mi_d4_atm`; no reference counterpart), mutating like `dftd4_nm`.  No autograd."""
+    n = positions.shape[0]
+    if n == 0:
+        return
+    C.require_device(positions, numbers, neighbor_matrix, batch_idx, energy, forces)
+    nm = C.i32(neighbor_matrix)
+    with _device_of(positions):
+        _d4._launch_atm(positions, numbers, nm, neighbor_matrix_shifts, None, nm.shape[1], n if fill_value is None else fill_value, cell,
+                        batch_idx, energy.shape[0], (rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref),
+                        _d4.d4_scalars(a1, a2, 0.0, 0.0, k_cn, wf, ga, gc, cn_cutoff), s9, alpha, three_body_cutoff, compute_virial, energy,
+                        forces, virial)
+
+
+@torch.library.custom_op("nvalchemiops::dftd4_atm_nl", mutates_args=_D4_ATM_OUT)
+def _dftd4_atm_nl_op(positions: torch.Tensor, numbers: torch.Tensor, idx_j: torch.Tensor, neighbor_ptr: torch.Tensor, rcov: torch.Tensor,
+                     en: torch.Tensor, r4r2: torch.Tensor, zeff: torch.Tensor, gam: torch.Tensor, n_ref: torch.Tensor, ngw: torch.Tensor,
+                     cn_ref: torch.Tensor, q_ref: torch.Tensor, c6_ref: torch.Tensor, a1: float, a2: float, three_body_cutoff: float,
+                     energy: torch.Tensor, forces: torch.Tensor, virial: torch.Tensor, s9: float = 1.0, alpha: float = 16.0,
+                     cn_cutoff: float | None = None, wf: float = 6.0, ga: float = 3.0, gc: float = 2.0, k_cn: float = 7.5,
+                     batch_idx: torch.Tensor | None = None, cell: torch.Tensor | None = None, unit_shifts: torch.Tensor | None = None,
+                     compute_virial: bool = False) -> None:
+    """The DFT-D4 three-body term on a CSR list (`mi_d4_atm`), mutating like `dftd4_nl`.  No autograd."""
+    if positions.shape[0] == 0:
+        return
+    C.require_device(positions, numbers, idx_j, neighbor_ptr, batch_idx, energy, forces)
+    with _device_of(positions):
+        _d4._launch_atm(positions, numbers, C.i32(idx_j), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, energy.shape[0],
+                        (rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref),
+                        _d4.d4_scalars(a1, a2, 0.0, 0.0, k_cn, wf, ga, gc, cn_cutoff), s9, alpha, three_body_cutoff, compute_virial, energy,
+                        forces, virial)
+
+
+# shape-only implementations: the two ops write into caller-owned outputs and return nothing, so a fake run has nothing to do
+@_dftd4_atm_nm_op.register_fake
+def _(positions, numbers, neighbor_matrix, rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref, a1, a2, three_body_cutoff, energy,
+      forces, virial, s9=1.0, alpha=16.0, cn_cutoff=None, wf=6.0, ga=3.0, gc=2.0, k_cn=7.5, fill_value=None, batch_idx=None, cell=None,
+      neighbor_matrix_shifts=None, compute_virial=False):
+    return None
+
+
+@_dftd4_atm_nl_op.register_fake
+def _(positions, numbers, idx_j, neighbor_ptr, rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref, a1, a2, three_body_cutoff, energy,
+      forces, virial, s9=1.0, alpha=16.0, cn_cutoff=None, wf=6.0, ga=3.0, gc=2.0, k_cn=7.5, batch_idx=None, cell=None, unit_shifts=None,
+      compute_virial=False):
+    return None
 
 
 # ---- this build's own ops behind the high-level entry points -----------------------------------------------------------------

@@ -1,9 +1,11 @@
-"""DFT-D4 dispersion: the two-body term `dftd4`, with a C6 that depends on each atom's coordination number and partial charge.
+"""DFT-D4 dispersion: the two-body term `dftd4`, with a C6 that depends on each atom's coordination number and partial charge, and the
+three-body (Axilrod-Teller-Muto) term `dftd4_atm`, whose C6 is the same contraction at zero charge.
 
 The reference package has no counterpart (its dispersion is DFT-D3(BJ), two-body).  Energies [num_systems], forces [N,3], coordination
 numbers [N], dE/dq [N] and (optionally) virials [num_systems,3,3], all float32, from a FULL neighbour list given either as a padded
 neighbour matrix or as CSR, exactly as for `dftd3`.  The passes (pack, CN, weights, energy, chain, fold) are hand-written HIP kernels
 (csrc/d4.hip) behind `mi_d4` of the C ABI; the model they evaluate is stated in include/nvalchemiops_hip.h and in `dftd4`'s docstring.
+`dftd4_atm` (`mi_d4_atm`, csrc/d4_atm.h) reuses those passes around one triple kernel and returns its term alone, to be added.
 No element tables ship with the package: like the c6 tables of `dftd3` they are the caller's (`D4Parameters`).
 """
 from __future__ import annotations
@@ -190,8 +192,9 @@ def dftd4(positions: torch.Tensor, numbers: torch.Tensor, charges: torch.Tensor,
     List layouts, argument validation and its messages, ``num_systems`` inference and the empty-input contract are `dftd3`'s.  CPU tensors
     raise ``NativeLibraryError``: there is no fallback.
 
-    Out of scope: D4's three-body term (it needs charge-free C6 values and cannot go through `dftd3_atm`), the neighbour search's packed
-    companion and search-side coordination numbers, zero damping, and element tables (`D4Parameters` holds the caller's)."""
+    D4's three-body term is `dftd4_atm` (charge-free C6 values: it cannot go through `dftd3_atm`); every published D4 parametrisation is
+    fitted with it switched on (s9 = 1), so a DFT-D4 energy is the sum of the two.  Out of scope: the neighbour search's packed companion
+    and search-side coordination numbers, zero damping, and element tables (`D4Parameters` holds the caller's)."""
     missing = None
     if a1 is None or a2 is None or s8 is None:
         missing = ("Functional parameters a1, a2, and s8 must be provided. "
@@ -267,4 +270,171 @@ def dftd4(positions: torch.Tensor, numbers: torch.Tensor, charges: torch.Tensor,
     return run()
 
 
-__all__ = ["D4Parameters", "dftd4", "species_slots"]
+def atm_tile() -> int:
+    """Neighbours inside ``three_body_cutoff`` a row may have before the triple pass of `dftd4_atm` works tile by tile."""
+    return int(C.lib().mi_d4_atm_tile())
+
+
+def _launch_atm(positions, numbers, idx, shifts, nptr, max_neighbors, fill_value, cell, batch_idx, num_systems, tables, scalars, s9, alpha,
+                three_body_cutoff, compute_virial, energy, forces, virial, want_visits=False):
+    """One `mi_d4_atm` call on the caller's arrays (`tables`, `scalars`: as for `_launch`; s6 / s8 are not read).  `want_visits`: return the
+    per-centre triangle-visit counts the triple pass leaves in its workspace (a diagnostic for tools/d4_atm_bench.py)."""
+    dev = positions.device
+    n = positions.shape[0]
+    pos = positions.detach().contiguous()
+    code = C.dtype_code(pos.dtype)
+    f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+    named = dict(zip(_TABLES, tables))
+    conv = {k: (C.i32(named[k].detach().to(dev)) if k in _INT_TABLES else f32(named[k])) for k in _TABLES}  # stay referenced until the launch is enqueued
+    L = C.lib()
+    if not hasattr(L, "mi_d4_atm"):
+        raise C.NativeLibraryError("libnvalchemiops_hip.so does not export mi_d4_atm: rebuild it (build_native.py)")
+    nz = conv["rcov"].shape[0]
+    par = C.MiD4Params(**{k: conv[k].data_ptr() for k in _TABLES}, nz=nz, **{k: float(v) for k, v in scalars.items()})
+    periodic = cell is not None and shifts is not None
+    cell_t = cell.detach().to(dtype=pos.dtype, device=dev).reshape(-1, 3, 3).contiguous() if periodic else None
+    sh = C.i32(shifts.to(dev)) if periodic else None
+    bi = None if batch_idx is None else C.i32(batch_idx)
+    z = C.i32(numbers)
+    ws_bytes = int(L.mi_d4_atm_workspace_bytes(n, int(num_systems), nz))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    rc = L.mi_d4_atm(C.ptr(pos), C.ptr(z), n, code, C.ptr(idx), C.ptr(sh), C.ptr(nptr), int(max_neighbors), int(fill_value), C.ptr(cell_t),
+                     C.ptr(bi), int(num_systems), ctypes.byref(par), float(s9), float(alpha), float(three_body_cutoff), int(bool(compute_virial)),
+                     C.ptr(energy), C.ptr(forces), C.ptr(virial if compute_virial else None), C.ptr(ws), ctypes.c_size_t(ws_bytes),
+                     C.stream_of(pos))
+    C.check(rc, "mi_d4_atm")
+    if want_visits:
+        off = int(L.mi_d4_atm_visits_offset(n, int(num_systems), nz))
+        return ws[off:off + 4 * n].view(torch.int32).clone()
+    return None
+
+
+class _D4AtmEnergy(torch.autograd.Function):
+    """`energy` of `dftd4_atm` with `dftd4`'s hand-written first-order adjoint: d(sum_s g_s E_s)/d(positions) = -g[batch] forces."""
+
+    @staticmethod
+    def forward(ctx, positions, batch_idx, run):
+        out = run()
+        ctx.save_for_backward(out[1])
+        ctx.batch_idx = batch_idx
+        ctx.dtype = positions.dtype
+        ctx.mark_non_differentiable(*out[1:])
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, *_unused):
+        (forces,) = ctx.saved_tensors
+        ga = g.expand(forces.shape[0]) if ctx.batch_idx is None else g[ctx.batch_idx.long()]
+        return (-ga[:, None] * forces).to(ctx.dtype), None, None
+
+
+@C.hybrid
+def dftd4_atm(positions: torch.Tensor, numbers: torch.Tensor, a1: float, a2: float, three_body_cutoff: float, s9: float = 1.0,
+              alpha: float = 16.0, *, d4_params: D4Parameters | dict[str, torch.Tensor] | None = None, cn_cutoff: float | None = None,
+              wf: float = 6.0, ga: float = 3.0, gc: float = 2.0, k_cn: float = 7.5, fill_value: int | None = None,
+              batch_idx: torch.Tensor | None = None, cell: torch.Tensor | None = None, neighbor_matrix: torch.Tensor | None = None,
+              neighbor_matrix_shifts: torch.Tensor | None = None, neighbor_list: torch.Tensor | None = None,
+              neighbor_ptr: torch.Tensor | None = None, unit_shifts: torch.Tensor | None = None, compute_virial: bool = False,
+              num_systems: int | None = None):
+    """Three-body (Axilrod-Teller-Muto) dispersion of DFT-D4: returns ``(energy[num_systems], forces[N,3])`` (+ ``virial[num_systems,3,3]``
+    if ``compute_virial``) of the three-body term ALONE, float32, in the units and the virial convention of `dftd4`, so that a caller adds
+    them to `dftd4`'s outputs.
+
+    For every unordered triple of distinct atom images A, B, C whose three distances are all ``< three_body_cutoff``::
+
+        E_ABC  = s9 sqrt(C6_AB C6_AC C6_BC) ang fdamp
+        ang    = 0.375 (a+b-c)(a+c-b)(b+c-a)/P^5 + 1/P^3           a, b, c squared sides, P product of the sides
+        fdamp  = 1 / (1 + 6 (R0_AB R0_AC R0_BC / P)^(alpha/3))     R0_XY = a1 sqrt(3 r4r2_X r4r2_Y) + a2
+        C6_XY  = sum_ab w_X[a] c6_ref[Z_X,Z_Y,a,b] w_Y[b]          w_X[a] = W_a(CN_X) zeta_a(q = 0)
+
+    ``W_a``, ``zeta_a``, the coordination number (erf count, electronegativity factor, optional hard ``cn_cutoff``) and the padding rules
+    (Z <= 0, Z > max_Z, ``n_ref[Z] = 0``; table entries beyond ``n_ref`` are never read) are exactly `dftd4`'s.  The charge scaling is
+    evaluated at q = 0 for every atom -- D4's definition of the term -- so there is no ``charges`` argument and no dE/dq output; note that
+    zeta_a(0) is not 1: it still depends on ``q_ref``, ``zeff``, ``gam``, ``ga`` and ``gc``.  The coordination numbers are summed over ALL
+    stored entries of the list (subject to ``cn_cutoff``); entries beyond ``three_body_cutoff`` only count for them.  A triple with any
+    C6 < 1e-12 contributes nothing.  A triple counts once per unit cell; forces include the path through the coordination numbers.
+
+    Requirements on the list: it is a FULL list (every pair stored in both rows) and its cutoff is at least ``three_body_cutoff``.  A
+    periodic list may hold an atom's own images and several images of one neighbour: those are distinct vertices.
+
+    Validation order and messages, list layouts, ``num_systems`` inference and the empty-input contract are `dftd4`'s.  CPU tensors raise
+    ``NativeLibraryError``: there is no fallback.  If ``positions`` requires grad, ``energy`` carries the same hand-written first-order
+    adjoint as `dftd4` (grad_positions = -g[batch] forces, in the input's dtype); differentiating twice raises.  Gradients with respect to
+    ``cell`` are out of scope (use ``virial``).  Under ``torch.compile`` the call is one mutating custom op per layout
+    (``nvalchemiops::dftd4_atm_nm`` / ``::dftd4_atm_nl``); there is no autograd on that path.
+
+    Out of scope: a charge-dependent three-body C6 and its dE/dq, zero damping, the packed companion and element tables."""
+    missing = None
+    if a1 is None or a2 is None:
+        missing = ("Functional parameters a1 and a2 must be provided. "
+                   "These are functional-dependent parameters required for DFT-D4 calculations.")
+    elif three_body_cutoff is None:
+        missing = "three_body_cutoff must be provided: the distance below which all three sides of a triple must lie."
+    elif not three_body_cutoff > 0:
+        missing = f"three_body_cutoff must be positive, got {three_body_cutoff}"
+    elif not alpha > 0:
+        missing = f"alpha must be positive, got {alpha}"
+    if d4_params is None:
+        tables = None
+    elif isinstance(d4_params, D4Parameters):
+        tables = tuple(getattr(d4_params, k) for k in _TABLES)
+    else:
+        checked = D4Parameters(**{k: d4_params[k] for k in _TABLES})
+        tables = tuple(getattr(checked, k) for k in _TABLES)
+    atoms = (positions, numbers, batch_idx, num_systems)
+    if tables is None:  # the list checks come first, as in `dftd4`; then the missing tables are reported
+        try:
+            _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial, missing,
+                               None, None, None, None, None, atoms)
+        except RuntimeError:
+            pass
+        raise RuntimeError("DFT-D4 parameters must be explicitly provided: pass d4_params, a D4Parameters instance or a dictionary with its "
+                           "ten tables (rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref).")
+    use_matrix, use_list, _ = _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell,
+                                                 compute_virial, missing, None, tables[0], tables[2], tables[9], tables[9], atoms)
+    n, dev = positions.size(0), positions.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    if n == 0:
+        nsys = 1 if (batch_idx is None or batch_idx.numel() == 0) else int(batch_idx.max().item()) + 1
+        out = (torch.zeros(nsys, **f32), torch.zeros((0, 3), **f32))
+        return out + (torch.zeros((0, 3, 3), **f32),) if compute_virial else out
+    if num_systems is None:
+        if batch_idx is None:
+            num_systems = 1
+        elif cell is not None:
+            num_systems = cell.size(0)
+        else:
+            num_systems = int(batch_idx.max().item()) + 1
+    energy = torch.empty(num_systems, **f32)  # written for every system inside mi_d4_atm
+    forces = torch.empty((n, 3), **f32)
+    virial = torch.empty((num_systems, 3, 3), **f32) if compute_virial else torch.zeros((0, 3, 3), **f32)
+    if C.tracing():  # torch.compile: one mutating custom op per call, as for `dftd4`; no autograd on this path
+        if use_matrix:
+            torch.ops.nvalchemiops.dftd4_atm_nm(positions, numbers, neighbor_matrix, *tables, a1, a2, three_body_cutoff, energy, forces, virial,
+                                                s9, alpha, cn_cutoff, wf, ga, gc, k_cn, fill_value, batch_idx, cell, neighbor_matrix_shifts,
+                                                compute_virial)
+        else:
+            torch.ops.nvalchemiops.dftd4_atm_nl(positions, numbers, neighbor_list[1], neighbor_ptr, *tables, a1, a2, three_body_cutoff, energy,
+                                                forces, virial, s9, alpha, cn_cutoff, wf, ga, gc, k_cn, batch_idx, cell, unit_shifts,
+                                                compute_virial)
+        return (energy, forces, virial) if compute_virial else (energy, forces)
+    C.require_device(positions, numbers, neighbor_matrix, neighbor_list, neighbor_ptr, batch_idx)
+    scalars = d4_scalars(a1, a2, 0.0, 0.0, k_cn, wf, ga, gc, cn_cutoff)
+
+    def run():
+        if use_matrix:
+            nm = C.i32(neighbor_matrix)
+            _launch_atm(positions, numbers, nm, neighbor_matrix_shifts, None, nm.size(1), n if fill_value is None else fill_value, cell,
+                        batch_idx, num_systems, tables, scalars, s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial)
+        else:
+            _launch_atm(positions, numbers, C.i32(neighbor_list[1]), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, num_systems,
+                        tables, scalars, s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial)
+        return (energy, forces, virial) if compute_virial else (energy, forces)
+
+    if torch.is_grad_enabled() and positions.requires_grad:
+        return _D4AtmEnergy.apply(positions, batch_idx, run)
+    return run()
+
+
+__all__ = ["D4Parameters", "atm_tile", "dftd4", "dftd4_atm", "species_slots"]
