@@ -337,8 +337,10 @@ int mi_d3_zero_atm(const void* positions, const int32_t* numbers, int n_atoms, i
  * Outputs (float32 whatever `dtype`): energy per system, forces at fixed charges including the path through the coordination numbers,
  * coord_num, charge_grad = dE/dq_i, virial = -dE/d(strain) (needs cell and unit_shifts).  No atomics: two identical calls give
  * bit-identical outputs.  mi_d4_species_slots(): distinct species of one call whose contracted C6 vectors a wave holds in LDS at once;
- * with more species present a row is walked once per group of that many (same results).  n_list_entries is accepted for symmetry with
- * mi_d3 and not read.                                                                                                                   */
+ * with more species present a row is walked once per group of that many (same results).  mi_d4_fold_blocks(): blocks of 256 threads per
+ * system in the fixed-order fold of the per-row energies and virials (mi_d4 and mi_d4_atm): a block takes the rows
+ * x*256 + t + k*256*mi_d4_fold_blocks(), so systems beyond 256*mi_d4_fold_blocks() atoms make a second trip.  n_list_entries is accepted
+ * for symmetry with mi_d3 and not read.                                                                                                 */
 typedef struct {
   const float* rcov;     /* [nz]          used as given                     */
   const float* en;       /* [nz]          electronegativities               */
@@ -356,6 +358,7 @@ typedef struct {
 } mi_d4_params;
 size_t mi_d4_workspace_bytes(int n_atoms, int n_systems, int nz);
 int mi_d4_species_slots(void);
+int mi_d4_fold_blocks(void);
 int mi_d4(const void* positions, const int32_t* numbers, int n_atoms, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
           const int32_t* neighbor_ptr /* NULL => matrix layout */, int max_neighbors, long long n_list_entries, int fill_value,
           const void* cell, const int32_t* batch_idx, int n_systems, const mi_d4_params* params /* [host] */,

@@ -506,6 +506,7 @@ int d4_impl(const T* positions, const int32_t* numbers, int N, const int32_t* id
 }  // namespace
 
 extern "C" int mi_d4_species_slots(void) { return D4_SLOTS; }
+extern "C" int mi_d4_fold_blocks(void) { return D4_FOLD_BLOCKS; }
 
 extern "C" size_t mi_d4_workspace_bytes(int n_atoms, int n_systems, int nz) {
   if (n_atoms < 0 || nz < 1 || n_systems < 1) return 0;

@@ -103,6 +103,8 @@ def lib() -> ctypes.CDLL:
             L.mi_d4_workspace_bytes.argtypes = [i, i, i]
             L.mi_d4_species_slots.restype = i
             L.mi_d4_species_slots.argtypes = []
+            L.mi_d4_fold_blocks.restype = i
+            L.mi_d4_fold_blocks.argtypes = []
             L.mi_d4.restype = i
             L.mi_d4.argtypes = [vp, vp, i, i, vp, vp, vp, i, ctypes.c_longlong, i, vp, vp, i, vp, vp, i] + [vp] * 6 + [sz, vp]
         if hasattr(L, "mi_d4_atm"):  # ... and its three-body (Axilrod-Teller-Muto) term: mi_d3_atm's argument list with the D4 tables

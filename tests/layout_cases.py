@@ -1,0 +1,231 @@
+"""The fixtures of the layout sweeps of `dftd4`, `dftd4_atm`, `gaussian_charge_correction` and `charge_equilibration`
+(tests/test_arg_layouts_gpu.py), in one place and free of any device, so that the CPU suite can check on exactly these inputs the condition
+that makes such a sweep worth running (tests/test_layout_sensitivity_cpu.py): a tensor argument that the entry point misreads by one row
+must move the result far beyond the bar the sweep applies.  Every reference is computed once and never modified.
+
+    system(n, seed, box)        the lattice builder of the layout tests: float32 values throughout, so float32 <-> float64 variants are equal-valued
+    d4(batch, compact)          the D4 fixtures: 130 atoms in a 24 Bohr triclinic box / 70 + 60 atoms in boxes 24 and 22 (compact blocks) /
+                                a compact block of 130 atoms in a box of 22 for the table sweeps of `dftd4_atm`
+    gaussian(dtype, batch)      130 atoms in the 12 Bohr box / 70 + 60 in boxes 12 and 11, widths in [0.3, 0.8], two point atoms per system
+    qeq_cluster(), qeq_periodic()   two clusters (no cell) / two periodic systems with their own k-vectors and alpha
+
+Why the D4 fixture is not the 12 Bohr box of the other sweeps: there the coordination numbers reach 18 while the `cn_ref` of
+`d4_test_tables` lie in [0, 1]; every Gaussian weight saturates on the reference nearest to 1, and rolling `ngw` by one row moves the
+float64 restatement by only 3.6 x the bar.  At 24 Bohr the coordination numbers stay inside the range of the references.
+"""
+import functools
+
+import numpy as np
+import torch
+
+from tests import d4_atm_cases as K3
+from tests import d4_atm_reference as R3
+from tests import d4_cases as K
+from tests import d4_reference as R
+from tests import gaussian_reference as GR
+from tests import qeq_reference as QR
+from tests import systems as S
+
+N, NA, NB = 130, 70, 60
+F64 = torch.float64
+
+
+def system(n, seed, box):
+    """The first n sites of a jittered FCC lattice (no unphysical contacts) sheared into the triclinic cell `random_box` uses; neutral
+    +-1 charges; Z drawn from 4 species.  Every value is a float32 number, so float32 <-> float64 variants are equal-valued."""
+    pos, cell, q, _ = S.fcc_box(n, a=box / 4.0, jitter=0.05, seed=seed, dtype=np.float32)
+    tri = np.array([[box, 0.0, 0.0], [0.25 * box, 0.9 * box, 0.0], [0.1 * box, -0.2 * box, 1.1 * box]])
+    pos = ((pos.astype(np.float64) / float(cell[0, 0])) @ tri).astype(np.float32)
+    z = np.random.default_rng(seed).choice(np.array([1, 6, 8, 17], np.int32), n)
+    return pos, tri.astype(np.float32), q.astype(np.float32), z
+
+
+def compact_system(n, seed, box):
+    """As `system`, but the n sites of the 256-site lattice NEAREST TO THE CENTRE of the cell: a compact block, whose atoms have their
+    full shells of (unlike) neighbours, where the first n sites are one or two slabs."""
+    pos, cell, q, _ = S.fcc_box(256, a=box / 4.0, jitter=0.05, seed=seed, dtype=np.float32)
+    tri = np.array([[box, 0.0, 0.0], [0.25 * box, 0.9 * box, 0.0], [0.1 * box, -0.2 * box, 1.1 * box]])
+    pos = (pos.astype(np.float64) / float(cell[0, 0])) @ tri
+    sel = np.sort(np.argsort(np.linalg.norm(pos - np.full(3, 0.5) @ tri, axis=1), kind="stable")[:n])
+    z = np.random.default_rng(seed).choice(np.array([1, 6, 8, 17], np.int32), n)
+    return pos[sel].astype(np.float32), tri.astype(np.float32), q[sel].astype(np.float32), z
+
+
+def _join(parts):
+    """[(pos, cell, q, z), ...] -> pos, cells [B, 3, 3], q, z, batch_idx (None for one system)."""
+    bi = None if len(parts) == 1 else np.concatenate([np.full(len(p[0]), k, np.int32) for k, p in enumerate(parts)])
+    return np.concatenate([p[0] for p in parts]), np.stack([p[1] for p in parts]), np.concatenate([p[2] for p in parts]), np.concatenate([p[3] for p in parts]), bi
+
+
+# ---- dftd4 / dftd4_atm -------------------------------------------------------------------------------------------------------------------
+
+D4_RC, D4_RC3 = 9.0, 7.0
+D4_KEYS = ("energy", "forces", "cn", "charge_grad", "virial")
+D4_EXTRA = {"energy": 0.0, "forces": 5e-6, "cn": 0.0, "charge_grad": 5e-6, "virial": 2e-7}  # tests/test_d4_gpu.py::EXTRA
+ATM_KEYS = ("energy", "forces", "virial")
+
+
+@functools.lru_cache(maxsize=None)
+def d4(batch=False, compact=False):
+    """single: `system(130, 7, 24.0)`.  batch: 70 + 60 atoms in boxes 24 and 22, as compact blocks -- as the first sites of the lattice
+    (slabs: largest coordination number 0.04) rolled `en` moves the restatement of `dftd4` by 0.45 bars and that of `dftd4_atm` by 0.05.
+    compact: one compact block of 130 atoms in a box of 22, the fixture the table sweeps of `dftd4_atm` run on besides the single
+    system, on which rolled `en` moves the three-body term by 66 bars only."""
+    assert not (batch and compact)
+    parts = [compact_system(NA, 8, 24.0), compact_system(NB, 9, 22.0)] if batch else [compact_system(N, 7, 22.0) if compact else system(N, 7, 24.0)]
+    pos, cell, q, z, bi = _join(parts)
+    return dict(pos=pos, cell=cell, q=(0.3 * q.astype(np.float64)).astype(np.float32), z=z, batch_idx=bi, tables=R.d4_test_tables(17))
+
+
+def d4_reference(batch=False, compact=False, work_dtype=F64, **replace):
+    """The restatement of `dftd4` on the fixture, with `q=` or single tables (`ngw=`, ...) replaced."""
+    c = d4(batch, compact)
+    tables = {**c["tables"], **{k: v for k, v in replace.items() if k != "q"}}
+    return R.reference(c["pos"], c["z"], replace.get("q", c["q"]), tables, list_cutoff=D4_RC, cell=c["cell"], batch_idx=c["batch_idx"],
+                       work_dtype=work_dtype, **K.BJ)
+
+
+@functools.lru_cache(maxsize=None)
+def d4_references(batch=False, compact=False):
+    return d4_reference(batch, compact), d4_reference(batch, compact, torch.float32)
+
+
+def d4_atm_reference(batch=False, compact=False, work_dtype=F64, **replace):
+    """The restatement of `dftd4_atm` on the fixture at s9 = 1 (the term is linear in s9)."""
+    c = d4(batch, compact)
+    return R3.reference(c["pos"], c["z"], {**c["tables"], **replace}, K3.BJ["a1"], K3.BJ["a2"], D4_RC, three_body_cutoff=D4_RC3, s9=1.0,
+                        cell=c["cell"], batch_idx=c["batch_idx"], work_dtype=work_dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def d4_atm_unit_references(batch=False, compact=False):
+    return d4_atm_reference(batch, compact), d4_atm_reference(batch, compact, torch.float32)
+
+
+def d4_atm_s9(batch=False, compact=False):
+    """The smallest power of ten `tests/d4_atm_cases.lifted` accepts for the fixture's restatement (the rule of every `dftd4_atm` case)."""
+    r64, s9 = d4_atm_unit_references(batch, compact)[0], 1.0
+    while not K3.lifted(r64, s9):
+        s9 *= 10.0
+        assert s9 <= 1e12
+    return s9
+
+
+def d4_atm_references(batch=False, compact=False):
+    s9 = d4_atm_s9(batch, compact)
+    return tuple(K3._scaled(r, s9) for r in d4_atm_unit_references(batch, compact))
+
+
+def d4_bar(r64, r32, key, extra=D4_EXTRA):
+    """The elementwise bar tests/test_d4_gpu.py::_bars and tests/test_d4_atm_gpu.py::_bars apply to the quantity `key`."""
+    ref = r64[key]
+    dev32 = np.abs(r32[key] - ref).max() if ref.size else 0.0
+    return 4.0 * np.maximum(dev32, 1e-6 + 1e-6 * np.abs(ref) + extra[key] * (np.abs(ref).max() if ref.size else 0.0))
+
+
+# ---- gaussian_charge_correction ----------------------------------------------------------------------------------------------------------
+
+GC_RC = 7.0  # the cutoff of tests/test_gaussian_charges_gpu.py
+GC_NAMES = ("energies", "forces", "charge_grads", "sigma_grads", "virial")
+
+
+@functools.lru_cache(maxsize=None)
+def gaussian(batch=False):
+    """The box of the layout tests with charges 0.5 q + 0.125 (a charged cell: the background term and its per-system sums take part),
+    widths in [0.3, 0.8] and two point atoms (sigma = 0) per system; all float32 numbers."""
+    parts = [system(NA, 8, 12.0), system(NB, 9, 11.0)] if batch else [system(N, 7, 12.0)]
+    pos, cell, q, _, bi = _join(parts)
+    g = np.random.default_rng(17 + batch)
+    sigma = g.uniform(0.3, 0.8, len(pos)).astype(np.float32)
+    off = 0
+    for p in parts:
+        sigma[off + g.choice(len(p[0]), 2, replace=False)] = 0.0
+        off += len(p[0])
+    return dict(pos=pos, cell=cell, q=(0.5 * q + 0.125).astype(np.float32), sigma=sigma, batch_idx=bi)
+
+
+def _entries(pos, cells, bi, cutoff):
+    """(i, j, S) of the full list with this cutoff, system by system (images up to +-1: the boxes are wider than the cutoff)."""
+    bi = np.zeros(len(pos), np.int64) if bi is None else bi
+    out = []
+    for s, cell in enumerate(cells):
+        sel = np.nonzero(bi == s)[0]
+        i, j, sh = GR.brute_force_entries(pos[sel].astype(np.float64), cell.astype(np.float64), cutoff, 1)
+        out.append((torch.as_tensor(sel)[i], torch.as_tensor(sel)[j], sh))
+    return tuple(torch.cat([o[k] for o in out]) for k in range(3))
+
+
+def gaussian_reference(batch=False, distance_dtype=F64, **replace):
+    c = {**gaussian(batch), **replace}
+    t = lambda a: torch.as_tensor(np.asarray(a, np.float64))  # noqa: E731
+    bi = None if c["batch_idx"] is None else torch.as_tensor(c["batch_idx"])
+    ent = _entries(c["pos"], c["cell"], c["batch_idx"], GC_RC)
+    return GR.evaluate(t(c["pos"]), t(c["q"]), t(c["sigma"]), t(c["cell"]), *ent, batch_idx=bi, distance_dtype=distance_dtype)
+
+
+# ---- charge_equilibration ----------------------------------------------------------------------------------------------------------------
+
+QEQ_TOL = 1e-10
+
+
+def _f32(a):
+    return np.asarray(a, np.float32).astype(np.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def qeq_cluster(sizes=(37, 33), seed=71):
+    """Clusters with all-pairs full lists (`systems.clusters`, the recipe tests/test_qeq_gpu.py::_cluster uses), float32 numbers in
+    float64 arrays."""
+    g, pos, bi, ii, jj, sigma = S.clusters(sizes, seed)
+    n = len(pos)
+    i, j = torch.as_tensor(ii), torch.as_tensor(jj)
+    return dict(n=n, nsys=len(sizes), pos=_f32(pos), cell=None, batch_idx=bi, sigma=_f32(sigma),
+                chi=_f32(g.normal(size=n)), hard=_f32(g.uniform(1.0, 2.0, n)), q0=_f32(g.uniform(-0.2, 0.2, n)), total=_f32([1.5, -0.25]),
+                ent=(i, j, torch.zeros((i.shape[0], 3), dtype=torch.long)), width=max(sizes) + 1)
+
+
+@functools.lru_cache(maxsize=None)
+def qeq_periodic(same_cell=False):
+    """40 atoms in a triclinic box 9 (charged) and 55 atoms in a cubic box 10 (neutral), cutoff 6 (the recipe of
+    tests/test_qeq_gpu.py::_periodic_batch), with the half-space k-vectors of cutoff 3.2 and one alpha per system.  `same_cell`: both
+    systems in the triclinic box, for the stride-0 expansion of `cell`."""
+    from nvalchemiops.interactions.electrostatics import generate_k_vectors_ewald_summation
+
+    g = np.random.default_rng(72)
+    tri = lambda b: np.array([[b, 0, 0], [0.2 * b, 0.9 * b, 0], [0.1 * b, -0.15 * b, 1.1 * b]])  # noqa: E731
+    cells = _f32(np.stack([tri(9.0), tri(9.0) if same_cell else np.eye(3) * 10.0]))
+    pos = _f32(np.concatenate([g.uniform(0, 1, (40, 3)) @ cells[0], g.uniform(0, 1, (55, 3)) @ cells[1]]))
+    bi = np.array([0] * 40 + [1] * 55, np.int32)
+    ent = _entries(pos, cells, bi, 6.0)
+    n = 95
+    sigma = g.uniform(0.3, 0.8, n)
+    sigma[[5, 60]] = 0.0
+    # (the package's own generator, pure torch, as tests/test_qeq_gpu.py uses it: the k-vectors are an INPUT of the solve and of the dense
+    # restatement alike, so which set they are does not enter the comparison)
+    kv = generate_k_vectors_ewald_summation(torch.as_tensor(cells), 3.2)
+    return dict(n=n, nsys=2, pos=pos, cell=cells, batch_idx=bi, sigma=_f32(sigma), chi=_f32(g.normal(size=n)), hard=_f32(g.uniform(1.0, 2.0, n)),
+                q0=_f32(g.uniform(-0.2, 0.2, n)), total=_f32([1.25, 0.0]), alpha=_f32([0.45, 0.42]), kv=kv.numpy(), ent=ent,
+                width=int(torch.bincount(ent[0]).max()) + 5)
+
+
+def qeq_dense(c, device="cpu", **replace):
+    """(H, chi, per-system totals, batch_idx) of the dense float64 restatement of a QEq fixture on `device`, with arguments replaced."""
+    c = {**c, **replace}
+    t = lambda a: None if a is None else torch.as_tensor(np.asarray(a), device=device)  # noqa: E731
+    ent = tuple(e.to(device) for e in c["ent"])
+    periodic = c["cell"] is not None
+    h = QR.dense_operator(t(c["pos"]), t(c["sigma"]), t(c["hard"]), t(c["cell"]), t(c["alpha"]) if periodic else None, t(c["kv"]) if periodic else None,
+                          *ent, batch_idx=t(c["batch_idx"]), **(dict(erfc_lr=QR.erfc_as) if periodic else {}))
+    return h, t(c["chi"]), t(c["total"]), t(c["batch_idx"])
+
+
+def qeq_charge_bound(h, chi, total, bi, nsys, tol=QEQ_TOL):
+    """Per system: the bound tests/test_qeq_gpu.py::_check_solution derives from the dense operator for |q - q_ref|,
+    10 tol ||b|| / lambda_min + 1e-14, b the projected gradient at the uniform start."""
+    counts = torch.bincount(bi.long(), minlength=nsys).to(F64)
+    b_norm = QR.projected_residual(h, chi, (total / counts)[bi.long()], bi, nsys)
+    out = []
+    for s in range(nsys):
+        m = torch.nonzero(bi == s).flatten()
+        out.append(10.0 * tol * float(b_norm[s]) / float(torch.linalg.eigvalsh(h[m][:, m]).min()) + 1e-14)
+    return out

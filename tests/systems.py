@@ -66,6 +66,27 @@ def molecule(n_atoms=512, density=0.05, min_dist=1.0, seed=2000, dtype=np.float3
     return pts.astype(dtype), numbers.astype(np.int32), side
 
 
+def clusters(sizes, seed):
+    """Clusters for charge equilibration without a cell: `sizes` sets of sites of a 6 x 6 x 6 grid (spacing 1.6, jitter 0.3), each with the
+    all-pairs FULL list of its own atoms.  Returns (generator, positions [N,3], batch_idx [N], i [P], j [P], sigma [N]); sigma in
+    [0.3, 0.8] with two point charges (sigma = 0) when N > 8.  The caller draws what else it needs from the generator."""
+    g = np.random.default_rng(seed)
+    pos, bi, ii, jj = [], [], [], []
+    off = 0
+    for b, nb in enumerate(sizes):
+        grid = np.array([(a, c, d) for a in range(6) for c in range(6) for d in range(6)], dtype=float)
+        pos.append(grid[g.choice(216, nb, replace=False)] * 1.6 + g.uniform(-0.3, 0.3, (nb, 3)))
+        bi += [b] * nb
+        a, c = np.nonzero(~np.eye(nb, dtype=bool))
+        ii.append(a + off)
+        jj.append(c + off)
+        off += nb
+    sigma = g.uniform(0.3, 0.8, off)
+    if off > 8:
+        sigma[[2, off - 3]] = 0.0
+    return g, np.concatenate(pos), np.array(bi, dtype=np.int32), np.concatenate(ii), np.concatenate(jj), sigma
+
+
 def d3_test_tables(z_max: int = 17, seed: int | None = None):
     """Analytic test tables of the reference's own test-suite (test/interactions/dispersion/conftest.py:38-160):
     c6ab = 10 Zi Zj (1 + 0.1p + 0.1q), cn_ref = (p/4) cnmax[Zi].  For z_max > 17 (benchmarks) the element

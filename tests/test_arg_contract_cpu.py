@@ -322,11 +322,196 @@ def test_coulomb_inputs_are_checked_against_each_other(entry):
         call(pos, q, cells, 3.0, 0.2, neighbor_list=lst, neighbor_ptr=ptr[:2], neighbor_shifts=lsh)
 
 
+def _d4_tables(nz=6):
+    r, ones = torch.rand, lambda *s: torch.ones(s, dtype=I32)  # noqa: E731
+    return dict(rcov=r(nz), en=r(nz), r4r2=r(nz), zeff=r(nz), gam=r(nz), n_ref=ones(nz), ngw=ones(nz, 7), cn_ref=r(nz, 7), q_ref=r(nz, 7),
+                c6_ref=r(nz, nz, 7, 7))
+
+
+# every D4 table with ONE wrong dimension (the kernels index them with Z < nz = len(rcov) and a reference index < 7)
+BAD_D4_TABLES = [
+    ("rcov", lambda: torch.rand(6, 1)), ("en", lambda: torch.rand(5)), ("r4r2", lambda: torch.rand(5)), ("zeff", lambda: torch.rand(5)),
+    ("gam", lambda: torch.rand(5)), ("n_ref", lambda: torch.ones(5, dtype=I32)), ("ngw", lambda: torch.ones((6, 6), dtype=I32)),
+    ("ngw", lambda: torch.ones((5, 7), dtype=I32)), ("cn_ref", lambda: torch.rand(6, 6)), ("cn_ref", lambda: torch.rand(5, 7)),
+    ("q_ref", lambda: torch.rand(6, 6)), ("q_ref", lambda: torch.rand(5, 7)), ("c6_ref", lambda: torch.rand(6, 5, 7, 7)),
+    ("c6_ref", lambda: torch.rand(5, 6, 7, 7)), ("c6_ref", lambda: torch.rand(6, 6, 6, 7)), ("c6_ref", lambda: torch.rand(6, 6, 7, 6)),
+]
+
+
+def _d4_calls():
+    from nvalchemiops.interactions.dispersion import dftd4, dftd4_atm
+
+    return {"dftd4": lambda pos, z, q, **kw: dftd4(pos, z, q, a1=0.4, a2=4.0, s8=0.8, **kw),
+            "dftd4_atm": lambda pos, z, q, **kw: dftd4_atm(pos, z, a1=0.4, a2=4.0, three_body_cutoff=6.0, **kw)}
+
+
+@pytest.mark.parametrize("entry", ["dftd4", "dftd4_atm"])
+def test_dftd4_inputs_are_checked_against_each_other(entry):
+    from nvalchemiops.interactions.dispersion import D4Parameters
+
+    call = _d4_calls()[entry]
+    pos, cell, _, bi = _geometry()
+    z, q = torch.ones(N, dtype=I32), torch.rand(N)
+    nm, nsh, lst, ptr, lsh = _neighbour_inputs()
+    t = _d4_tables()
+    cells = cell[None]
+    cases = [
+        ("neighbor_matrix", dict(neighbor_matrix=nm[:-1])),
+        ("neighbor_matrix", dict(neighbor_matrix=torch.full((N + 1, M), N, dtype=I32))),
+        ("neighbor_matrix_shifts", dict(neighbor_matrix=nm, neighbor_matrix_shifts=torch.zeros((N, M + 1, 3), dtype=I32), cell=cells)),
+        ("neighbor_matrix_shifts", dict(neighbor_matrix=nm, neighbor_matrix_shifts=torch.zeros((N, M - 1, 3), dtype=I32), cell=cells)),
+        ("neighbor_matrix_shifts", dict(neighbor_matrix=nm, neighbor_matrix_shifts=torch.zeros((N, M, 2), dtype=I32), cell=cells)),
+        ("neighbor_matrix_shifts", dict(neighbor_matrix=nm, neighbor_matrix_shifts=torch.zeros((N - 1, M, 3), dtype=I32), cell=cells)),
+        ("neighbor_matrix_shifts", dict(neighbor_matrix=nm, neighbor_matrix_shifts=torch.zeros((N, M), dtype=I32), cell=cells)),
+        ("unit_shifts", dict(neighbor_list=lst, neighbor_ptr=ptr, unit_shifts=lsh[:-1], cell=cells)),
+        ("unit_shifts", dict(neighbor_list=lst, neighbor_ptr=ptr, unit_shifts=torch.zeros((7, 2), dtype=I32), cell=cells)),
+        ("neighbor_ptr", dict(neighbor_list=lst, neighbor_ptr=ptr[:-1])),
+        ("neighbor_ptr", dict(neighbor_list=lst, neighbor_ptr=torch.zeros((N + 2,), dtype=I32))),
+        ("neighbor_list", dict(neighbor_list=torch.zeros((7, 2), dtype=I32), neighbor_ptr=ptr)),
+        ("batch_idx", dict(neighbor_matrix=nm, batch_idx=bi[:-1])),
+        ("batch_idx", dict(neighbor_list=lst, neighbor_ptr=ptr, batch_idx=bi[:-1])),
+        ("cell must have shape", dict(neighbor_matrix=nm, neighbor_matrix_shifts=nsh, batch_idx=bi, num_systems=3, cell=cells.repeat(2, 1, 1))),
+        ("cell must have shape", dict(neighbor_matrix=nm, neighbor_matrix_shifts=nsh, cell=cells.repeat(2, 1, 1))),
+        ("cell must have shape", dict(neighbor_list=lst, neighbor_ptr=ptr, unit_shifts=lsh, cell=cells.repeat(2, 1, 1))),
+        ("cell must have shape", dict(neighbor_matrix=nm, neighbor_matrix_shifts=nsh, cell=torch.zeros(3, 2))),
+    ]
+    for match, kw in cases:
+        for params in (t, D4Parameters(**t)):
+            with pytest.raises(ValueError, match=match):
+                call(pos, z, q, d4_params=params, **kw)
+    for lists in (dict(neighbor_matrix=nm), dict(neighbor_list=lst, neighbor_ptr=ptr)):
+        with pytest.raises(ValueError, match="numbers"):
+            call(pos, z[:-1], q, d4_params=t, **lists)
+        if entry == "dftd4":
+            with pytest.raises(ValueError, match="charges"):
+                call(pos, z, q[:-1], d4_params=t, **lists)
+    for name, make in BAD_D4_TABLES:
+        with pytest.raises(ValueError, match=f"^{name} must"):
+            call(pos, z, q, d4_params={**t, name: make()}, neighbor_matrix=nm)
+    with pytest.raises(ValueError, match="to match rcov"):  # every table against a shorter rcov
+        call(pos, z, q, d4_params={**t, "rcov": torch.rand(5)}, neighbor_matrix=nm)
+
+
+def _gaussian_calls():
+    from nvalchemiops.interactions.electrostatics import gaussian_charge_correction as gcc
+
+    everything = dict(compute_forces=True, compute_charge_gradients=True, compute_sigma_gradients=True)
+    return {"energies": gcc, "all_outputs": lambda *a, **k: gcc(*a, **everything, compute_virial=len(a) > 3, **k),  # (the virial needs the cell)
+            "autograd": lambda pos, q, *a, **k: gcc(pos.clone().requires_grad_(True), q.clone().requires_grad_(True), *a, **k)}
+
+
+def _periodic_list_cases(shifts_name):
+    """The list disagreements of a periodic call whose CSR shifts are called `shifts_name`: (message, list kwargs)."""
+    nm, nsh, lst, ptr, lsh = _neighbour_inputs()
+    z = lambda *s: torch.zeros(s, dtype=I32)  # noqa: E731
+    return [
+        ("neighbor_matrix", dict(neighbor_matrix=nm[:-1], neighbor_matrix_shifts=nsh[:-1])),
+        ("neighbor_matrix", dict(neighbor_matrix=torch.full((N + 1, M), N, dtype=I32), neighbor_matrix_shifts=z(N + 1, M, 3))),
+        ("neighbor_matrix", dict(neighbor_matrix=torch.full((N * M,), N, dtype=I32), neighbor_matrix_shifts=nsh)),
+        ("neighbor_matrix_shifts", dict(neighbor_matrix=nm, neighbor_matrix_shifts=z(N, M + 1, 3))),
+        ("neighbor_matrix_shifts", dict(neighbor_matrix=nm, neighbor_matrix_shifts=z(N, M - 1, 3))),
+        ("neighbor_matrix_shifts", dict(neighbor_matrix=nm, neighbor_matrix_shifts=z(N, M, 2))),
+        ("neighbor_matrix_shifts", dict(neighbor_matrix=nm, neighbor_matrix_shifts=nsh[:-1])),
+        (shifts_name, dict(neighbor_list=lst, neighbor_ptr=ptr, **{shifts_name: lsh[:-1]})),
+        (shifts_name, dict(neighbor_list=lst, neighbor_ptr=ptr, **{shifts_name: z(7, 2)})),
+        ("neighbor_ptr", dict(neighbor_list=lst, neighbor_ptr=ptr[:-1], **{shifts_name: lsh})),
+        ("neighbor_ptr", dict(neighbor_list=lst, neighbor_ptr=z(N + 2), **{shifts_name: lsh})),
+        ("neighbor_list", dict(neighbor_list=z(7, 2), neighbor_ptr=ptr, **{shifts_name: z(7, 3)})),
+    ]
+
+
+@pytest.mark.parametrize("entry", ["energies", "all_outputs", "autograd"])
+def test_gaussian_charge_correction_inputs_are_checked_against_each_other(entry):
+    call = _gaussian_calls()[entry]
+    pos, cell, _, bi = _geometry()
+    q, s = torch.rand(N), torch.rand(N) + 0.3
+    nm, nsh, lst, ptr, lsh = _neighbour_inputs()
+    cells = cell[None]
+    good = dict(neighbor_matrix=nm, neighbor_matrix_shifts=nsh)
+    for match, kw in _periodic_list_cases("neighbor_shifts"):
+        with pytest.raises(ValueError, match=match):
+            call(pos, q, s, cells, **kw)
+    for lists in (good, dict(neighbor_list=lst, neighbor_ptr=ptr, neighbor_shifts=lsh)):
+        with pytest.raises(ValueError, match="charges"):
+            call(pos, q[:-1], s, cells, **lists)
+        with pytest.raises(ValueError, match="sigma"):
+            call(pos, q, s[:-1], cells, **lists)
+        with pytest.raises(ValueError, match="sigma"):
+            call(pos, q, s[:, None].expand(N, 2), cells, **lists)
+        with pytest.raises(ValueError, match="batch_idx"):
+            call(pos, q, s, cells.repeat(B, 1, 1), batch_idx=bi[:-1], **lists)
+        with pytest.raises(ValueError, match="cell must have shape"):
+            call(pos, q, s, torch.zeros(3, 2), **lists)
+    # without a cell: the same list checks, and no shifts
+    with pytest.raises(ValueError, match="neighbor_matrix"):
+        call(pos, q, s, neighbor_matrix=nm[:-1])
+    with pytest.raises(ValueError, match="neighbor_ptr"):
+        call(pos, q, s, neighbor_list=lst, neighbor_ptr=ptr[:-1])
+    with pytest.raises(ValueError, match="need a cell"):
+        call(pos, q, s, **good)
+
+
+def _qeq_calls():
+    from nvalchemiops.interactions.electrostatics import charge_equilibration as qeq
+
+    return {"pme": lambda *a, **k: qeq(*a, reciprocal="pme", **{"alpha": 0.4, "mesh_dimensions": (8, 8, 8), **k}),
+            "ewald": lambda *a, **k: qeq(*a, reciprocal="ewald", **{"alpha": 0.4, "k_cutoff": 2.0, **k}),
+            "ewald_info_autograd": lambda pos, chi, *a, **k: qeq(pos, chi.clone().requires_grad_(True), *a, reciprocal="ewald", return_info=True,
+                                                                 **{"alpha": 0.4, "k_cutoff": 2.0, **k})}
+
+
+@pytest.mark.parametrize("entry", ["pme", "ewald", "ewald_info_autograd"])
+def test_charge_equilibration_inputs_are_checked_against_each_other(entry):
+    from nvalchemiops.interactions.electrostatics import charge_equilibration as qeq
+
+    call = _qeq_calls()[entry]
+    pos, cell, _, bi = _geometry()
+    chi, hard, s, q0 = torch.rand(N), torch.rand(N) + 1.0, torch.rand(N) + 0.3, torch.zeros(N)
+    nm, nsh, lst, ptr, lsh = _neighbour_inputs()
+    cells, cellb = cell[None], cell[None].repeat(B, 1, 1)
+    for match, kw in _periodic_list_cases("neighbor_shifts"):
+        with pytest.raises(ValueError, match=match):
+            call(pos, chi, hard, s, cells, **kw)
+    for lists in (dict(neighbor_matrix=nm, neighbor_matrix_shifts=nsh), dict(neighbor_list=lst, neighbor_ptr=ptr, neighbor_shifts=lsh)):
+        for name, args in (("electronegativity", (chi[:-1], hard, s)), ("hardness", (chi, hard[:-1], s)), ("sigma", (chi, hard, s[:-1])),
+                           ("electronegativity", (chi[:, None].expand(N, 2), hard, s)), ("hardness", (chi, hard[:, None].expand(N, 2), s))):
+            with pytest.raises(ValueError, match=name):
+                call(pos, *args, cells, **lists)
+        with pytest.raises(ValueError, match="initial_charges"):
+            call(pos, chi, hard, s, cells, initial_charges=q0[:-1], **lists)
+        with pytest.raises(ValueError, match="batch_idx"):
+            call(pos, chi, hard, s, cellb, batch_idx=bi[:-1], **lists)
+        with pytest.raises(ValueError, match="batch_idx is required"):
+            call(pos, chi, hard, s, cellb, **lists)
+        with pytest.raises(ValueError, match="cell must have shape"):
+            call(pos, chi, hard, s, cellb, batch_idx=bi, num_systems=3, **lists)
+        with pytest.raises(ValueError, match="cell must have shape"):
+            call(pos, chi, hard, s, torch.zeros(3, 2), **lists)
+        with pytest.raises(ValueError, match="total_charge"):
+            call(pos, chi, hard, s, cellb, batch_idx=bi, total_charge=torch.zeros(3), **lists)
+        with pytest.raises(ValueError, match="total_charge"):
+            call(pos, chi, hard, s, cells, total_charge=torch.zeros(2), **lists)
+        with pytest.raises(ValueError, match="alpha has 3 values but there are 2 systems"):
+            call(pos, chi, hard, s, cellb, batch_idx=bi, alpha=torch.tensor([0.4, 0.4, 0.4]), **lists)
+    # clusters: no cell, the number of systems from num_systems or the length of total_charge
+    for match, kw in (("neighbor_matrix", dict(neighbor_matrix=nm[:-1])), ("neighbor_ptr", dict(neighbor_list=lst, neighbor_ptr=ptr[:-1])),
+                      ("neighbor_list", dict(neighbor_list=torch.zeros((7, 2), dtype=I32), neighbor_ptr=ptr)),
+                      ("need a cell", dict(neighbor_matrix=nm, neighbor_matrix_shifts=nsh)),
+                      ("batch_idx", dict(neighbor_matrix=nm, batch_idx=bi[:-1], num_systems=B)),
+                      ("batch_idx is required", dict(neighbor_matrix=nm, total_charge=torch.zeros(B))),
+                      ("total_charge", dict(neighbor_matrix=nm, batch_idx=bi, num_systems=B, total_charge=torch.zeros(3))),
+                      ("initial_charges", dict(neighbor_matrix=nm, initial_charges=q0[:-1]))):
+        with pytest.raises(ValueError, match=match):
+            qeq(pos, chi, hard, s, **kw)
+    with pytest.raises(ValueError, match="hardness"):
+        qeq(pos, chi, hard[:-1], s, neighbor_matrix=nm)
+
+
 def test_well_formed_cpu_arguments_stop_at_the_device_check():
     """The control: the same calls with consistent shapes get past every shape check and are refused for being on the CPU (still without a
     library call) -- so the ValueErrors above are about the mismatch, not about something else in the fixture."""
     from nvalchemiops import _capi as C
-    from nvalchemiops.interactions.electrostatics import ewald_real_space
+    from nvalchemiops.interactions.electrostatics import charge_equilibration, ewald_real_space
     from nvalchemiops.interactions.electrostatics.coulomb import coulomb_energy
     from nvalchemiops.neighborlist import build_cell_list, cell_list
 
@@ -338,6 +523,16 @@ def test_well_formed_cpu_arguments_stop_at_the_device_check():
              lambda: ewald_real_space(pos, q, cell[None], torch.tensor([0.3]), neighbor_list=lst, neighbor_ptr=ptr, neighbor_shifts=lsh),
              lambda: coulomb_energy(pos, q, cell[None], 3.0, 0.2, neighbor_matrix=nm, neighbor_matrix_shifts=nsh)]
     calls += [lambda c=c: c(pos, z, d3_params=_tables(), neighbor_matrix=nm, neighbor_matrix_shifts=nsh, cell=cell[None]) for c in _d3_calls().values()]
+    calls += [lambda c=c: c(pos, z, q, d4_params=_d4_tables(), neighbor_matrix=nm, neighbor_matrix_shifts=nsh, cell=cell[None]) for c in _d4_calls().values()]
+    calls += [lambda c=c: c(pos, z, q, d4_params=_d4_tables(), neighbor_list=lst, neighbor_ptr=ptr, unit_shifts=lsh, cell=cell[None])
+              for c in _d4_calls().values()]
+    s, hard = torch.rand(N) + 0.3, torch.rand(N) + 1.0
+    calls += [lambda c=c: c(pos, q, s, cell[None], neighbor_matrix=nm, neighbor_matrix_shifts=nsh) for c in _gaussian_calls().values()]
+    calls += [lambda c=c: c(pos, q, s, cell[None].repeat(B, 1, 1), neighbor_list=lst, neighbor_ptr=ptr, neighbor_shifts=lsh, batch_idx=bi)
+              for c in _gaussian_calls().values()]
+    calls += [lambda c=c: c(pos, q, hard, s, cell[None].repeat(B, 1, 1), neighbor_matrix=nm, neighbor_matrix_shifts=nsh, batch_idx=bi,
+                            total_charge=torch.zeros(B), initial_charges=torch.zeros(N), alpha=torch.tensor([0.4, 0.4])) for c in _qeq_calls().values()]
+    calls.append(lambda: charge_equilibration(pos, q, hard, s, neighbor_list=lst, neighbor_ptr=ptr, batch_idx=bi, total_charge=torch.zeros(B)))
     for call in calls:
         with pytest.raises(C.NativeLibraryError, match="ROCm devices only"):
             call()

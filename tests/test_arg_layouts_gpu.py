@@ -30,6 +30,11 @@ Which variant goes to which argument (no tensor argument of a listed entry point
     neighbor_matrix_shifts, unit/neighbor_shifts      x   x   x   x   -   -   x   -
     neighbor_list [2,P]                               x   x   x   x   -   -   x   -
     D3 tables rcov, r4r2, c6ab, cn_ref, r0ab          x   x   x   T(c6ab, cn_ref, r0ab)  -   -   -   x
+    D4 tables rcov, en, r4r2, zeff, gam, cn_ref,
+      q_ref, c6_ref                                   x   x   x   T(cn_ref, q_ref, c6_ref) -   -   -   x
+    D4 tables n_ref, ngw                              x   x   x   T(ngw)  -   -   x   -
+    sigma, electronegativity, hardness,
+      initial_charges, total_charge [B]               x   x   x   -   -   -   -   x
     meshes, k_squared                                 x   x   x   x   -   -   -   x*     (* not k_squared)
 
 `flt` goes to every float argument but the one whose dtype IS the dtype of the call and of its outputs: positions, and where there are
@@ -40,7 +45,15 @@ canonical tensor (`_variant` asserts it), index tensors are padded with 0 (a val
 box).  A code path that ignored strides or dtype would read wrong values but stay inside the allocation: nothing here can cause an
 out-of-bounds access, even against a broken library.  Everything that COULD go out of bounds is in tests/test_arg_contract_cpu.py, behind
 a launch guard.  Shapes: 130 atoms (more than two waves, no multiple of 64) in a triclinic cell of 12 Bohr, a batch of 70 + 60 atoms,
-cutoff 5 Bohr (20 - 60 neighbours), meshes (12, 10, 14) and (16, 8, 24), tables with 4 species present."""
+cutoff 5 Bohr (20 - 60 neighbours), meshes (12, 10, 14) and (16, 8, 24), tables with 4 species present.  `dftd4`, `dftd4_atm`,
+`gaussian_charge_correction` and `charge_equilibration` have fixtures of their own (tests/layout_cases.py, which says why);
+tests/test_layout_sensitivity_cpu.py checks without a GPU that an argument of theirs read one row off moves the result by 100 bars.
+
+MEASURED on one MI355X for those four ops (variants run, all in one run; every sweep prints its line under `pytest -s`): dftd4 single
+system 69 (matrix, `D4Parameters`) + 73 (CSR, tables as a dict) + 11 (float64 positions), batch 75 + 78 + 12; dftd4_atm 65 + 69 + 11,
+44 + 44 (the tables on the compact block) and 71 + 74 + 12; gaussian_charge_correction 25 (matrix) + 29 (CSR) single, 31 + 34 batch, in float32 and in float64; charge_equilibration
+33 + 37 (cluster batch), 50 + 54 (periodic Ewald batch) + 1 (stride-0 cell).  Worst |variant - canonical| / bar: 0 in every sweep, the
+periodic solves included: every variant gave the bits of the canonical call."""
 import functools
 import re
 import types
@@ -50,14 +63,19 @@ import pytest
 import torch
 
 from oracle import oracle as O
+from tests import layout_cases as LC
 from tests import systems as S
 from tests import test_coulomb_gpu as TC
 from tests import test_d3_atm_gpu as TATM
 from tests import test_d3_gpu as TD3
 from tests import test_d3_zero_atm_gpu as TZA
 from tests import test_d3_zero_gpu as TZ
+from tests import test_d4_atm_gpu as TD4A
+from tests import test_d4_gpu as TD4
+from tests import test_gaussian_charges_gpu as TG
 from tests import test_math_gpu as TM
 from tests import test_pme_gpu as TP
+from tests import test_qeq_gpu as TQ
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -81,14 +99,7 @@ def _t(a, dtype=None):
 
 # ---- systems (tests/systems.py) ----------------------------------------------------------------------------------------------------------
 
-def _system(n, seed, box):
-    """The first n sites of a jittered FCC lattice (no unphysical contacts) sheared into the triclinic cell `random_box` uses; neutral
-    +-1 charges; Z drawn from 4 species.  Every value is a float32 number, so float32 <-> float64 variants are equal-valued."""
-    pos, cell, q, _ = S.fcc_box(n, a=box / 4.0, jitter=0.05, seed=seed, dtype=np.float32)
-    tri = np.array([[box, 0.0, 0.0], [0.25 * box, 0.9 * box, 0.0], [0.1 * box, -0.2 * box, 1.1 * box]])
-    pos = ((pos.astype(np.float64) / float(cell[0, 0])) @ tri).astype(np.float32)
-    z = np.random.default_rng(seed).choice(np.array([1, 6, 8, 17], np.int32), n)
-    return pos, tri.astype(np.float32), q.astype(np.float32), z
+_system = LC.system  # the lattice builder, in tests/layout_cases.py so that the CPU suite can build the same fixtures
 
 
 @functools.lru_cache(maxsize=None)
@@ -194,9 +205,16 @@ CELLB = "off row F flt"       # [B, 3, 3]
 TAB = "off col row flt"
 
 
+def _same_values(a, b):
+    """torch.equal, with NaN equal to NaN (the D4 tables hold NaN in the entries no kernel may read)."""
+    if not a.dtype.is_floating_point:
+        return torch.equal(a, b)
+    return torch.equal(torch.isnan(a), torch.isnan(b)) and torch.equal(torch.nan_to_num(a), torch.nan_to_num(b))
+
+
 def _variant(t, kind):
     v = KINDS[kind](t)
-    assert v.shape == t.shape and torch.equal(v.to(t.dtype), t), kind
+    assert v.shape == t.shape and _same_values(v.to(t.dtype), t), kind
     assert v.dtype != t.dtype or v.stride() != t.stride() or v.storage_offset() != 0, f"{kind}: not a different layout"
     behind = v.untyped_storage().nbytes() - v.storage_offset() * v.element_size()
     assert behind >= t.numel() * t.element_size(), f"{kind}: the storage behind the pointer is shorter than the canonical tensor"
@@ -568,6 +586,124 @@ def test_dftd3_family(name, batch):
     _sweep(f"{name} matrix f64", call, k64, dict(positions=POS, cell=splan["cell"], neighbor_matrix="off i64", neighbor_matrix_shifts="off i64"), close)
 
 
+# ---- DFT-D4 (its own fixture: tests/layout_cases.py says why) ------------------------------------------------------------------------------
+
+RC4, RC43, M4 = LC.D4_RC, LC.D4_RC3, 128
+_WORST = [0.0]  # largest error / bar of the sweep in progress (the closeness functions of the four newer ops record it)
+
+
+def _count(plan):
+    return sum(len(kinds.split()) for kinds in plan.values())
+
+
+def _swept(what, call, kw, plan, close, ref=None, shared=()):
+    """`_sweep` (+ `_sweep_shared` for the arguments in `shared`); prints the number of variants run and the worst error / bar among them."""
+    _WORST[0] = 0.0
+    ref = _sweep(what, call, kw, plan, close, ref=ref)
+    if shared:
+        _sweep_shared(what, call, kw, shared, close)
+    print(f"[layouts] {what:44s} {_count(plan) + len(shared):3d} variants, worst error / bar {_WORST[0]:.3g}")
+    return ref
+
+
+def _close_bars(bars, keys):
+    """Elementwise |variant - canonical| <= the bar of tests/test_d4_gpu.py::_bars / tests/test_d4_atm_gpu.py::_bars for that output."""
+    def close(o, r, what, i):
+        err, bar = np.abs(o.detach().cpu().numpy().astype(np.float64) - r.astype(np.float64)), bars[keys[i]][0]
+        _WORST[0] = max(_WORST[0], float((err / bar).max()) if err.size else 0.0)
+        assert (err <= bar).all(), f"{what}: max err {err.max():.3e}, worst err / bar {(err / bar).max():.3g}"
+    return close
+
+
+@functools.lru_cache(maxsize=None)
+def _d4fx(batch, dtype_name="float32", compact=False):
+    """A D4 fixture of tests/layout_cases.py on the device with both list layouts (cutoff 9 Bohr); tables and charges are float32."""
+    from nvalchemiops.neighborlist import batch_cell_list, cell_list
+
+    c, dt = LC.d4(batch, compact), np.dtype(dtype_name).type
+    f = types.SimpleNamespace(batch=batch, n=len(c["pos"]), c=c)
+    f.P, f.C, f.Q, f.Zt = _t(c["pos"].astype(dt)), _t(c["cell"].astype(dt)), _t(c["q"]), _t(c["z"])
+    f.BI = None if not batch else _t(c["batch_idx"])
+    pbc = torch.ones((f.C.shape[0], 3), dtype=torch.bool, device=DEV)
+    if not batch:
+        f.nm, f.num, f.sh = cell_list(f.P, RC4, f.C[0], pbc[0], max_neighbors=M4)
+        f.lst, f.ptr, f.lsh = cell_list(f.P, RC4, f.C[0], pbc[0], max_neighbors=M4, return_neighbor_list=True)
+    else:
+        f.nm, f.num, f.sh = batch_cell_list(f.P, RC4, f.C, pbc, f.BI, max_neighbors=M4)
+        f.lst, f.ptr, f.lsh = batch_cell_list(f.P, RC4, f.C, pbc, f.BI, max_neighbors=M4, return_neighbor_list=True)
+    assert 8 <= int(f.num.max()) <= M4, "the rows of the neighbour matrix must hold every neighbour inside the list cutoff"
+    f.tabs = {k: _t(c["tables"][k]) for k in LC.R.TABLE_KEYS}
+    return f
+
+
+D4_TPLAN = dict(rcov=TAB, en=TAB, r4r2=TAB, zeff=TAB, gam=TAB, n_ref=IDX, ngw=MAT, cn_ref=TAB + " T", q_ref=TAB + " T", c6_ref=TAB + " T")
+
+
+def _d4_call(name, as_params, s9=None):
+    from nvalchemiops.interactions.dispersion import D4Parameters, dftd4, dftd4_atm
+
+    def call(positions, numbers, **a):
+        tab = {k: a.pop(k) for k in LC.R.TABLE_KEYS}
+        params = D4Parameters(**tab) if as_params else tab
+        if name == "dftd4":
+            return dftd4(positions, numbers, a.pop("charges"), **TD4.BJ, d4_params=params, compute_virial=True, **a)
+        return dftd4_atm(positions, numbers, **TD4A.BJ, three_body_cutoff=RC43, s9=s9, d4_params=params, compute_virial=True, **a)
+    return call
+
+
+@pytest.mark.parametrize("name", ["dftd4", "dftd4_atm"])
+@pytest.mark.parametrize("batch", [False, True])
+@_collecting
+def test_dftd4_family(name, batch):
+    """Matrix layout with the tables as a `D4Parameters`, CSR with the tables as a dict; every argument in both."""
+    f = _d4fx(batch)
+    if name == "dftd4":
+        r64, r32 = LC.d4_references(batch)
+        bars, keys, judge, s9 = TD4._bars(r64, r32), TD4.KEYS, TD4._judge, None
+        assert all(np.array_equal(bars[k][0], LC.d4_bar(r64, r32, k)) for k in keys)  # the bar the CPU suite measured the fixture against
+    else:
+        s9 = LC.d4_atm_s9(batch)
+        assert (batch or s9 == 10.0) and RC43 <= RC4
+        r64, r32 = LC.d4_atm_references(batch)
+        bars, keys, judge = TD4A._bars(r64, r32), TD4A.KEYS, TD4A._judge
+    close = _close_bars(bars, keys)
+    sysk = dict(positions=f.P, numbers=f.Zt, cell=f.C, **f.tabs)
+    splan = dict(positions=POS, numbers=IDX, cell=CELLB if batch else CELL1, **D4_TPLAN)
+    if name == "dftd4":
+        sysk["charges"], splan["charges"] = f.Q, VEC
+    if batch:
+        sysk["batch_idx"], splan["batch_idx"] = f.BI, IDX
+    tag = f"{name}{' batch' if batch else ''}"
+    mk = dict(sysk, neighbor_matrix=f.nm, neighbor_matrix_shifts=f.sh)
+    ref = _tuple(_d4_call(name, True, s9)(**mk))
+    judge(f"layouts {tag} matrix", ref, r64, r32)  # the canonical call against the op's own reference, at its own module's bar
+    _swept(f"{tag} matrix, D4Parameters", _d4_call(name, True, s9), mk, dict(splan, neighbor_matrix=MAT, neighbor_matrix_shifts=MAT), close, ref=ref,
+           shared=("cell",) if batch else ())
+    ck = dict(sysk, neighbor_list=f.lst, neighbor_ptr=f.ptr, unit_shifts=f.lsh)
+    csr = _tuple(_d4_call(name, False, s9)(**ck))
+    judge(f"layouts {tag} csr", csr, r64, r32)
+    _swept(f"{tag} csr, tables as a dict", _d4_call(name, False, s9), ck, dict(splan, neighbor_list=MAT, neighbor_ptr=IDX, unit_shifts=MAT), close, ref=csr)
+    # float64 positions and cell with the float32 tables and charges of the calls above (D4 outputs are float32 whatever the positions' dtype)
+    g = _d4fx(batch, "float64")
+    k64 = dict(sysk, positions=g.P, cell=g.C, neighbor_matrix=g.nm, neighbor_matrix_shifts=g.sh)
+    r = _tuple(_d4_call(name, True, s9)(**k64))
+    judge(f"layouts {tag} matrix f64", r, r64, r32)
+    _swept(f"{tag} matrix f64", _d4_call(name, True, s9), k64, dict(positions=POS, cell=splan["cell"], neighbor_matrix="off i64", neighbor_matrix_shifts="off i64"),
+           close, ref=r)
+    if name == "dftd4_atm" and not batch:
+        # The tables once more on the compact 130-atom block: on the single system above rolled `en` moves the three-body term by 66 bars
+        # only, on this one every table moves it by more than 100 (tests/test_layout_sensitivity_cpu.py).
+        f, s9 = _d4fx(False, compact=True), LC.d4_atm_s9(False, True)
+        r64, r32 = LC.d4_atm_references(False, True)
+        close = _close_bars(TD4A._bars(r64, r32), keys)
+        sysk = dict(positions=f.P, numbers=f.Zt, cell=f.C, **f.tabs)
+        for label, as_params, lists in (("matrix, D4Parameters", True, dict(neighbor_matrix=f.nm, neighbor_matrix_shifts=f.sh)),
+                                        ("csr, tables as a dict", False, dict(neighbor_list=f.lst, neighbor_ptr=f.ptr, unit_shifts=f.lsh))):
+            ref = _tuple(_d4_call(name, as_params, s9)(**sysk, **lists))
+            judge(f"layouts {name} compact {label}", ref, r64, r32)
+            _swept(f"{name} compact {label}", _d4_call(name, as_params, s9), dict(sysk, **lists), D4_TPLAN, close, ref=ref)
+
+
 # ==== electrostatics ======================================================================================================================
 
 @pytest.fixture(params=["tile", "auto"])
@@ -749,6 +885,140 @@ def test_pme_green_structure_factor_and_corrections(dtype):
     _sweep_shared("pme_energy_corrections_with_charge_grad batch", lambda **a: pme_energy_corrections_with_charge_grad(**a), bkw, ("cell", "alpha"), close)
 
 
+# ---- Gaussian-smeared charges and charge equilibration --------------------------------------------------------------------------------------
+
+MG = 192
+
+
+@functools.lru_cache(maxsize=None)
+def _gfx(dtype_name, batch):
+    """The Gaussian fixture of tests/layout_cases.py on the device (cutoff 7 Bohr: 90 - 130 neighbours) and its reference, computed once."""
+    from nvalchemiops.neighborlist import batch_cell_list, cell_list
+
+    c, dt = LC.gaussian(batch), np.dtype(dtype_name).type
+    f = types.SimpleNamespace(batch=batch, n=len(c["pos"]), tdtype=F32 if dt == np.float32 else F64)
+    f.P, f.C, f.Q, f.S = (_t(c[k].astype(dt)) for k in ("pos", "cell", "q", "sigma"))
+    f.BI = None if not batch else _t(c["batch_idx"])
+    pbc = torch.ones((f.C.shape[0], 3), dtype=torch.bool, device=DEV)
+    if not batch:
+        f.nm, f.num, f.sh = cell_list(f.P, LC.GC_RC, f.C[0], pbc[0], max_neighbors=MG)
+        f.lst, f.ptr, f.lsh = cell_list(f.P, LC.GC_RC, f.C[0], pbc[0], max_neighbors=MG, return_neighbor_list=True)
+    else:
+        f.nm, f.num, f.sh = batch_cell_list(f.P, LC.GC_RC, f.C, pbc, f.BI, max_neighbors=MG)
+        f.lst, f.ptr, f.lsh = batch_cell_list(f.P, LC.GC_RC, f.C, pbc, f.BI, max_neighbors=MG, return_neighbor_list=True)
+    assert 64 < int(f.num.max()) <= MG
+    f.rel = 1e-11 if dt == np.float64 else 1e-6  # tests/test_gaussian_charges_gpu.py: test_parity_fp64_matrix_and_csr / test_fp32_inputs
+    f.ref = TG._ref(f.P, f.Q, f.S, f.C, TG.R.entries_from_matrix(f.nm, f.sh, f.n), batch_idx=f.BI, distance_dtype=f.tdtype)
+    return f
+
+
+def _close_gaussian(rel):
+    def close(o, r, what, i):
+        _WORST[0] = max(_WORST[0], TG._close(o, r, what, rel) / rel)
+    return close
+
+
+@DTYPES
+@pytest.mark.parametrize("batch", [False, True])
+@_collecting
+def test_gaussian_charge_correction(dtype, batch):
+    from nvalchemiops.interactions.electrostatics import gaussian_charge_correction as gcc
+
+    f = _gfx(dtype, batch)
+    close = _close_gaussian(f.rel)
+    call = lambda positions, charges, sigma, cell, **a: gcc(positions, charges, sigma, cell, **a, **TG.ALL)  # noqa: E731
+    sysk = dict(positions=f.P, charges=f.Q, sigma=f.S, cell=f.C)
+    splan = dict(positions=POS, charges=VEC, sigma=VEC, cell=CELLB if batch else CELL1)
+    if batch:
+        sysk["batch_idx"], splan["batch_idx"] = f.BI, IDX
+    tag = f"gaussian {dtype}{' batch' if batch else ''}"
+    for label, lists, lplan in (("matrix", dict(neighbor_matrix=f.nm, neighbor_matrix_shifts=f.sh, mask_value=f.n), dict(neighbor_matrix=MAT, neighbor_matrix_shifts=MAT)),
+                                ("csr", dict(neighbor_list=f.lst, neighbor_ptr=f.ptr, neighbor_shifts=f.lsh), dict(neighbor_list=MAT, neighbor_ptr=IDX, neighbor_shifts=MAT))):
+        ref = _tuple(call(**sysk, **lists))
+        assert len(ref) == 5
+        for name, o in zip(TG.NAMES, ref):  # the canonical call against the float64 restatement, at the module's bar
+            assert o.dtype == f.tdtype
+            TG._close(o, f.ref[name], f"{tag} {label} {name} vs the restatement", f.rel)
+        _swept(f"{tag} {label}", call, dict(sysk, **lists), dict(splan, **lplan), close, ref=ref, shared=("cell",) if batch and label == "matrix" else ())
+
+
+def _qeq_lists(c):
+    nm, sh = TQ._lists(*c["ent"], c["n"], c["width"], c["n"])
+    lst, ptr, lsh = TQ._csr(nm, sh, c["n"])
+    return nm, sh, lst, ptr, lsh
+
+
+def _exact(o, r, what, i):
+    assert np.array_equal(o.detach().cpu().numpy(), r), f"{what}: not bit-identical to the canonical call (max difference {np.abs(o.detach().cpu().numpy() - r).max():.3e})"
+
+
+@_collecting
+def test_charge_equilibration_cluster_batch():
+    """No cell: the solve is free of atomics, so every variant gives the BITS of the canonical call -- charges, chemical potentials,
+    iteration counts -- from a warm start and per-system total charges."""
+    from nvalchemiops.interactions.electrostatics import charge_equilibration as qeq
+
+    c = LC.qeq_cluster()
+    nm, sh, lst, ptr, lsh = _qeq_lists(c)
+    h, chi, total, bi = LC.qeq_dense(c, DEV)
+
+    def call(positions, electronegativity, hardness, sigma, **a):
+        out = qeq(positions, electronegativity, hardness, sigma, tolerance=LC.QEQ_TOL, return_info=True, **a)
+        return out.charges, out.chemical_potential, out.iterations
+
+    sysk = dict(positions=_t(c["pos"]), electronegativity=chi, hardness=_t(c["hard"]), sigma=_t(c["sigma"]), initial_charges=_t(c["q0"]), total_charge=total,
+                batch_idx=bi)
+    splan = dict(positions=POS, electronegativity=VEC, hardness=VEC, sigma=VEC, initial_charges=VEC, total_charge=VEC, batch_idx=IDX)
+    for label, lists, lplan in (("matrix", dict(neighbor_matrix=nm, mask_value=c["n"]), dict(neighbor_matrix=MAT)),
+                                ("csr", dict(neighbor_list=lst, neighbor_ptr=ptr), dict(neighbor_list=MAT, neighbor_ptr=IDX))):
+        out = qeq(sysk["positions"], chi, sysk["hardness"], sysk["sigma"], tolerance=LC.QEQ_TOL, return_info=True,
+                  **{k: sysk[k] for k in ("initial_charges", "total_charge", "batch_idx")}, **lists)
+        TQ._check_solution(out, h, chi, total, bi, c["nsys"], LC.QEQ_TOL, 200, f"layouts cluster batch {label}")
+        assert int(out.iterations.min()) > 0
+        _swept(f"charge_equilibration cluster {label}", call, dict(sysk, **lists), dict(splan, **lplan), _exact,
+               ref=(out.charges, out.chemical_potential, out.iterations))
+
+
+@pytest.mark.parametrize("same_cell", [False, True], ids=["two_cells", "x0"])
+@_collecting
+def test_charge_equilibration_periodic_ewald_batch(same_cell):
+    """reciprocal="ewald" with given k-vectors and one alpha per system.  Reciprocal space adds with atomics in arrival order, so a variant
+    is within TWICE the bound `_check_solution` derives from the dense operator for the distance of a converged solve to the exact charges
+    (each of the two calls is within once of them); chemical potentials within ||H|| times that.  `x0`: both systems in the same cell, which
+    is then a stride-0 expansion."""
+    from nvalchemiops.interactions.electrostatics import charge_equilibration as qeq
+
+    c = LC.qeq_periodic(same_cell)
+    nm, sh, lst, ptr, lsh = _qeq_lists(c)
+    h, chi, total, bi = LC.qeq_dense(c, DEV)
+    bound = torch.tensor(LC.qeq_charge_bound(h, chi, total, bi, c["nsys"]), dtype=F64, device=DEV)
+    hmax = torch.stack([torch.linalg.eigvalsh(h[bi == s][:, bi == s]).abs().max() for s in range(c["nsys"])])
+    bars = ((2.0 * bound)[bi.long()].cpu().numpy(), (2.0 * bound * hmax).cpu().numpy())
+
+    def close(o, r, what, i):
+        err = np.abs(o.detach().cpu().numpy() - r)
+        _WORST[0] = max(_WORST[0], float((err / bars[i]).max()))
+        assert (err <= bars[i]).all(), f"{what}: max err {err.max():.3e}, worst err / bar {(err / bars[i]).max():.3g}"
+
+    def call(positions, electronegativity, hardness, sigma, cell, **a):
+        out = qeq(positions, electronegativity, hardness, sigma, cell, reciprocal="ewald", tolerance=LC.QEQ_TOL, return_info=True, **a)
+        return out.charges, out.chemical_potential
+
+    sysk = dict(positions=_t(c["pos"]), electronegativity=chi, hardness=_t(c["hard"]), sigma=_t(c["sigma"]), cell=_t(c["cell"]), initial_charges=_t(c["q0"]),
+                total_charge=total, alpha=_t(c["alpha"]), k_vectors=_t(c["kv"]), batch_idx=bi)
+    splan = dict(positions=POS, electronegativity=VEC, hardness=VEC, sigma=VEC, cell=CELLB, initial_charges=VEC, total_charge=VEC, alpha=VEC, k_vectors=POS,
+                 batch_idx=IDX)
+    for label, lists, lplan in (("matrix", dict(neighbor_matrix=nm, neighbor_matrix_shifts=sh, mask_value=c["n"]), dict(neighbor_matrix=MAT, neighbor_matrix_shifts=MAT)),
+                                ("csr", dict(neighbor_list=lst, neighbor_ptr=ptr, neighbor_shifts=lsh), dict(neighbor_list=MAT, neighbor_ptr=IDX, neighbor_shifts=MAT))):
+        if same_cell and label == "csr":
+            continue  # (the whole plan runs on the two-cell batch; here only `cell` is swept, once)
+        a = {k: v for k, v in sysk.items() if k not in ("positions", "electronegativity", "hardness", "sigma", "cell")}
+        out = qeq(sysk["positions"], chi, sysk["hardness"], sysk["sigma"], sysk["cell"], reciprocal="ewald", tolerance=LC.QEQ_TOL, return_info=True, **a, **lists)
+        TQ._check_solution(out, h, chi, total, bi, c["nsys"], LC.QEQ_TOL, 200, f"layouts periodic ewald batch {label}")
+        _swept(f"charge_equilibration ewald {'x0 ' if same_cell else ''}{label}", call, dict(sysk, **lists), {} if same_cell else dict(splan, **lplan), close,
+               ref=(out.charges, out.chemical_potential), shared=("cell",) if same_cell else ())
+
+
 # ==== splines =============================================================================================================================
 
 MESH = "off col row T flt"
@@ -880,11 +1150,18 @@ def test_gradient_layouts(dtype, spread_path):
     if dtype == "float64":  # (the cut-off Coulomb ops compute in float64: their 1e-11 bar is a float64 bar)
         ops["coulomb_energy"] = lambda p, q, c: coulomb_energy(p, q, c, 4.5, 0.3, **nb)
         ops["coulomb_energy_forces"] = lambda p, q, c: coulomb_energy_forces(p, q, c, 4.5, 0.3, **nb)
+    _check_gradient_layouts({name: (op, (f.P, f.Q, f.C), ("positions", "charges", "cell"), CLOSE_COULOMB if name.startswith("coulomb") else close)
+                             for name, op in ops.items()})
+
+
+def _check_gradient_layouts(ops):
+    """ops: name -> (op(*leaves) -> output(s), the tensors to differentiate with respect to, their names, closeness).  Every grad-output
+    layout against the canonical (contiguous) backward of the same op."""
     fails = []
-    for name, op in ops.items():
-        def grads(layout, op=op):
-            p, q, c = (t.clone().requires_grad_(True) for t in (f.P, f.Q, f.C))
-            outs = _tuple(op(p, q, c))
+    for name, (op, inputs, args, close) in ops.items():
+        def grads(layout, op=op, inputs=inputs):
+            leaves = [t.clone().requires_grad_(True) for t in inputs]
+            outs = _tuple(op(*leaves))
             gs = []
             for i, o in enumerate(outs):
                 w = _t(np.random.default_rng(9 + i).uniform(0.5, 1.5, tuple(o.shape)).astype(np.float32)).to(o.dtype)
@@ -897,17 +1174,69 @@ def test_gradient_layouts(dtype, spread_path):
                 elif layout != "contiguous":
                     w = _variant(w, layout)
                 gs.append(w)
-            return torch.autograd.grad(outs, (p, q, c), grad_outputs=gs, allow_unused=True)
+            return torch.autograd.grad(outs, leaves, grad_outputs=gs, allow_unused=True)
 
-        def one(name=name, grads=grads):
+        def one(name=name, grads=grads, args=args, close=close):
             ref_w, ref_1 = grads("contiguous"), grads("ones")
             for layout, ref in (("x0", ref_1), ("row", ref_w), ("T", ref_w), ("off", ref_w)):
-                for gt, rf, arg in zip(grads(layout), ref, ("positions", "charges", "cell")):
+                for gt, rf, arg in zip(grads(layout), ref, args):
                     assert (gt is None) == (rf is None), f"{name} grad output {layout}: d/d{arg}"
                     if rf is not None:
-                        (CLOSE_COULOMB if name.startswith("coulomb") else close)(gt, rf.cpu().numpy(), f"{name} grad output {layout}: d/d{arg}", 0)
+                        close(gt, rf.cpu().numpy(), f"{name} grad output {layout}: d/d{arg}", args.index(arg))
         _guarded(one, name, fails)
     assert not fails, "\n".join(fails)
+
+
+@DTYPES
+def test_gradient_layouts_of_the_dispersion_and_charge_ops(dtype):
+    """The same for the four adjoint paths of `gaussian_charge_correction` (energies, with respect to positions, charges, sigma and cell),
+    `dftd4` (positions and charges) and `dftd4_atm` (positions) on the two-system batch -- so that the [B] grad output has a layout -- and
+    the charges of `charge_equilibration` on the cluster batch (positions, chi, hardness, sigma, total charge; float64 only).  Each against
+    its own contiguous backward: `dftd4`, `dftd4_atm` and the solver part of the cluster solve (chi, hardness, total charge) are free of
+    atomics, so the bits must be equal; the Gaussian energies, and the position and sigma gradients of the solve, at their modules' bars."""
+    from nvalchemiops.interactions.dispersion import dftd4, dftd4_atm
+    from nvalchemiops.interactions.electrostatics import charge_equilibration as qeq, gaussian_charge_correction as gcc
+
+    ops = {}
+    for batch in (False, True):
+        g = _gfx(dtype, batch)
+        bkw = dict(batch_idx=g.BI) if batch else {}
+        ops[f"gaussian_charge_correction{' batch' if batch else ''}"] = (
+            lambda p, q, s, c, g=g, bkw=bkw: gcc(p, q, s, c, neighbor_matrix=g.nm, neighbor_matrix_shifts=g.sh, mask_value=g.n, **bkw),
+            (g.P, g.Q, g.S, g.C), ("positions", "charges", "sigma", "cell"), lambda o, r, what, i, g=g: TG._close(o, r, what, g.rel))
+        ops[f"gaussian_charge_correction csr{' batch' if batch else ''}"] = (
+            lambda p, q, s, c, g=g, bkw=bkw: gcc(p, q, s, c, neighbor_list=g.lst, neighbor_ptr=g.ptr, neighbor_shifts=g.lsh, **bkw),
+            (g.P, g.Q, g.S, g.C), ("positions", "charges", "sigma", "cell"), lambda o, r, what, i, g=g: TG._close(o, r, what, g.rel))
+    f = _d4fx(True, dtype)
+    params = TD4._params(f.c["tables"])
+    lists = dict(neighbor_matrix=f.nm, neighbor_matrix_shifts=f.sh, cell=f.C, batch_idx=f.BI)
+    ops["dftd4 batch"] = (lambda p, q: dftd4(p, f.Zt, q, **TD4.BJ, d4_params=params, **lists)[0], (f.P, f.Q.to(f.P.dtype)), ("positions", "charges"), _exact)
+    s9 = LC.d4_atm_s9(True)
+    ops["dftd4_atm batch"] = (lambda p: dftd4_atm(p, f.Zt, **TD4A.BJ, three_body_cutoff=RC43, s9=s9, d4_params=params, **lists)[0], (f.P,), ("positions",), _exact)
+    if dtype == "float64":
+        c = LC.qeq_cluster()
+        nm, _, _, _, _ = _qeq_lists(c)
+        bi = _t(c["batch_idx"])
+        solve = lambda p, chi, j, s, tot: qeq(p, chi, j, s, total_charge=tot, batch_idx=bi, neighbor_matrix=nm, mask_value=c["n"], tolerance=1e-12)  # noqa: E731
+        inputs = tuple(_t(c[k]) for k in ("pos", "chi", "hard", "sigma", "total"))
+        # chi, hardness and total charge come out of the solver's own kernels (no atomics): equal bits.  The gradients with respect to
+        # positions and sigma are assembled by the adjoints of the public energy functions, which add with atomics (measured: 1.1e-16
+        # between two equal backward passes): those two at the relative bars of tests/test_qeq_gpu.py::GRAD_BARS.  The bars are relative
+        # to the largest component of the gradient of a loss with random weights: for the stride-0 layout (every weight 1) the loss is
+        # sum_i q_i = sum_s Q_s, whose gradient with respect to positions and sigma is zero up to rounding and gives no scale.
+        leaves = [t.clone().requires_grad_(True) for t in inputs]
+        w = _t(np.random.default_rng(9).uniform(0.5, 1.5, c["n"]).astype(np.float32)).to(F64)
+        scale = [float(g.abs().max()) for g in torch.autograd.grad((w * solve(*leaves)).sum(), leaves)]
+        rel = {0: TQ.GRAD_BARS["cluster"]["pos"], 3: TQ.GRAD_BARS["cluster"]["sigma"]}
+
+        def close_qeq(o, r, what, i):
+            if i not in rel:
+                return _exact(o, r, what, i)
+            err = np.abs(o.detach().cpu().numpy() - r).max()
+            assert err <= rel[i] * scale[i], f"{what}: max err {err:.3e} on {scale[i]:.3e}"
+
+        ops["charge_equilibration cluster batch"] = (solve, inputs, ("positions", "chi", "hardness", "sigma", "total_charge"), close_qeq)
+    _check_gradient_layouts(ops)
 
 
 # ==== caller-owned output buffers =========================================================================================================

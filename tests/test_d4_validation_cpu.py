@@ -34,6 +34,7 @@ def test_exports():
     assert {"dftd3", "dftd3_atm", "dftd3_zero", "dftd3_zero_atm", "D3Parameters"} <= set(D.__all__)
     lib = _capi.lib()
     assert species_slots() == lib.mi_d4_species_slots() >= 1
+    assert lib.mi_d4_fold_blocks() == 64  # tests/test_fold_sizes_gpu.py sizes its systems by it, beside mi_qeq_blocks / mi_gaussian_charges_blocks
     assert lib.mi_d4_workspace_bytes(1000, 2, 20) > lib.mi_d4_workspace_bytes(10, 2, 20) > 0 and lib.mi_d4_workspace_bytes(-1, 1, 20) == 0
     assert hasattr(torch.ops.nvalchemiops, "dftd4_nm") and hasattr(torch.ops.nvalchemiops, "dftd4_nl")
 

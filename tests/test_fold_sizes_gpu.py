@@ -1,0 +1,240 @@
+"""Sizes beyond one trip of the per-system folds of `dftd4`, `dftd4_atm`, `gaussian_charge_correction` and `charge_equilibration`.
+
+Every per-system sum of these ops is a fixed-order fold on a grid of (blocks, systems) blocks of 256 threads, each looping
+`r += blocks * 256` over ALL N rows and keeping those of its system: `d4_fold_kernel` (also `dftd4_atm`'s), `gc_fold_kernel`,
+`gc_system_sums_kernel`, `qeq_fold_kernel`, `qeq_cg_update_kernel`, `qeq_cg_direction_kernel`.  The parity modules stop at a few hundred
+atoms; the second trip of these loops (N > 256 * blocks = 16 384) and the batched form at that size are compared here.
+
+No large reference is needed.  These ops take the pairs from the list, so K copies of a small system with the small list repeated
+blockwise (indices + k n0, fill value N) are K independent systems, even at identical positions; the small call is judged against its
+float64 reference in the same test.  K is the smallest number of copies with K n0 >= 1.5 * 256 * blocks (the second trip holds at least
+a third of the rows) and K n0 no multiple of 64.
+
+  (a) all copies as ONE system (periodic: one shared cell).  Per-atom outputs equal the tiled small call's bit for bit: the kernels are
+      owner-computes with fixed-order sums and a row's arithmetic does not depend on N.  Per-system outputs:
+      |X_big - K X_small| <= 2^-22 max|X_big| -- two float32 roundings with a factor 2; the float64 reordering error is negligible.  One
+      lost row of 24 640 is 4e-5.
+  (b) the copies as a BATCH of K systems (periodic: K cells, and once more as a stride-0 expansion of one cell).  Every system's energy
+      and virial within 2^-22 max|X_small| of the small call's, per-atom outputs bit-identical again.
+  Gaussian background term: the per-system charge sum feeds every atom.  In (a) Q = K Q_small, so the expectation is the small call
+      without background plus K x (K^2 x for the virial) the closed-form background part of the small system, compared with the
+      module's rel = 1e-11 `_close`, as are the per-atom outputs of (b) with the background switched on.
+  charge_equilibration (cluster): the operator is block-diagonal with identical blocks, so the exact solution is the small dense KKT
+      solution tiled:  max|q - q_ref| <= sqrt(K) (10 tol ||b_small|| / lambda_min + 1e-14) for the single system (||b|| grows as sqrt(K)),
+      without the sqrt(K) per system of the batch -- `_check_solution`'s bound with the small block's spectrum; tol = 1e-10.
+
+MEASURED on one MI355X (each test prints its figures under `pytest -s`; matrix and CSR agree to the digits shown).  Per-atom outputs:
+bit-identical wherever that is asserted.  Worst |X_big - K X_small| / bar as ONE system:
+  dftd4      molecule70 (K 353, N 24 710)      E 0.215                 triclinic_f32 (K 1366, N 24 588)  E 0.352  V 0.107
+  dftd4_atm  molecule70                        E 0.104                 triclinic_f32                     E 0.148  V 0.052
+  gaussian   300 atoms (K 82, N 24 600)        V 8.7e-10 (without background); with background, relative to max|ref| against the bar
+             1e-11: energies 1.4e-16, forces 0, charge gradients 3.1e-16, sigma gradients 2.1e-16, virial 3.6e-16
+As a BATCH of K systems: every energy and virial of dftd4 and dftd4_atm EQUAL to the small call's (error 0), with K cells and with the
+stride-0 cell; gaussian virial 3.6e-15 and 5.3e-15 absolute (1.1e-9 and 1.8e-9 of the bar).
+  charge_equilibration  60 atoms (K 410, N 24 600): max|q - q_ref| 2.9e-11 as one system (bar 1.3e-7) and in the worst system of the batch
+             (bar 6.2e-9); 19 iterations in the small call, the single system and all 410 systems of the batch."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from tests import d4_atm_cases as K3
+from tests import d4_cases as K4
+from tests import qeq_reference as QR
+from tests import test_d4_atm_gpu as TD4A
+from tests import test_d4_gpu as TD4
+from tests import test_gaussian_charges_gpu as TG
+from tests import test_qeq_gpu as TQ
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+F64 = torch.float64
+FOLD = 2.0 ** -22
+
+
+def _copies(n0, blocks):
+    k = math.ceil(1.5 * 256 * blocks / n0)
+    while (k * n0) % 64 == 0:
+        k += 1
+    assert 3 * (k * n0 - 256 * blocks) >= k * n0, "the second trip must hold at least a third of the rows"
+    return k
+
+
+def _tile_matrix(nm, sh, k):
+    """[n0, M] with fill value n0 -> [k n0, M] with fill value k n0: block b holds the small list shifted by b n0."""
+    n0 = nm.shape[0]
+    off = (torch.arange(k, device=nm.device, dtype=nm.dtype) * n0)[:, None, None]
+    big = torch.where(nm[None] == n0, torch.full_like(nm[None], k * n0), nm[None] + off).reshape(k * n0, -1).contiguous()
+    return big, None if sh is None else sh.repeat(k, 1, 1).contiguous()
+
+
+def _tile_csr(lst, ptr, lsh, k):
+    n0, p0 = ptr.shape[0] - 1, lst.shape[1]
+    off = torch.arange(k, device=lst.device, dtype=lst.dtype)
+    big = (lst[:, None, :] + (off * n0)[None, :, None]).reshape(2, k * p0).contiguous()
+    bptr = torch.cat([(ptr[None, :-1] + (off * p0)[:, None]).reshape(-1), ptr.new_tensor([k * p0])]).contiguous()
+    return big, bptr, None if lsh is None else lsh.repeat(k, 1).contiguous()
+
+
+def _fold_close(big, small_times_k, scale, what):
+    err = float((big.double() - small_times_k.double()).abs().max())
+    bar = FOLD * float(scale.double().abs().max())
+    print(f"[fold] {what:58s} max error {err:.3e}  bar {bar:.3e}  error / bar {err / bar if bar else 0.0:.3g}")
+    assert err <= bar, f"{what}: {err:.3e} > {bar:.3e}"
+
+
+def _bitwise(big, small, k, what):
+    assert torch.equal(big, small.repeat((k,) + (1,) * (small.dim() - 1))), f"{what}: per-atom output differs from the tiled small call's"
+
+
+# ---- dftd4 / dftd4_atm ---------------------------------------------------------------------------------------------------------------------
+
+def _d4_blocks():
+    from nvalchemiops import _capi as C
+
+    return int(C.lib().mi_d4_fold_blocks())
+
+
+@pytest.mark.parametrize("name", ["molecule70", "triclinic_f32"])
+@pytest.mark.parametrize("op", ["dftd4", "dftd4_atm"])
+def test_d4_copies_as_one_system_and_as_a_batch(op, name):
+    from nvalchemiops.interactions.dispersion import dftd4, dftd4_atm
+
+    if op == "dftd4":
+        c, args, kw, m, l, _ = TD4._inputs(name)
+        fn, judge, refs, per_atom = dftd4, TD4._judge, K4.references(name), (1, 2, 3)
+    else:
+        c, args, kw, m, l, _ = TD4A._inputs(name)
+        fn, judge, refs, per_atom = dftd4_atm, TD4A._judge, K3.references(name), (1,)
+    n0, periodic = len(c["pos"]), c["cell"] is not None
+    k = _copies(n0, _d4_blocks())
+    n = k * n0
+    assert n > 256 * _d4_blocks() and n % 64 != 0
+    big_args = tuple(a.repeat((k,) + (1,) * (a.dim() - 1)) for a in args)
+    bi = torch.arange(k, device=DEV, dtype=torch.int32).repeat_interleave(n0)
+    nm, sh = _tile_matrix(m["neighbor_matrix"], m.get("neighbor_matrix_shifts"), k)
+    lst, ptr, lsh = _tile_csr(l["neighbor_list"], l["neighbor_ptr"], l.get("unit_shifts"), k)
+    layouts = (("matrix", m, dict(neighbor_matrix=nm, **(dict(neighbor_matrix_shifts=sh) if periodic else {}))),
+               ("csr", l, dict(neighbor_list=lst, neighbor_ptr=ptr, **(dict(unit_shifts=lsh) if periodic else {}))))
+    for tag, small_lists, big_lists in layouts:
+        small = fn(*args, **kw, **small_lists)
+        judge(f"fold sizes {op} {name} {tag}: the small call", small, *refs)
+        per_system = (0, len(small) - 1) if periodic else (0,)
+        # (a) one system of K n0 atoms
+        one = fn(*big_args, **kw, **big_lists)
+        for i in per_atom:
+            _bitwise(one[i], small[i], k, f"{op} {name} {tag} one system, output {i}")
+        for i in per_system:
+            _fold_close(one[i], k * small[i].double(), one[i], f"{op} {name} {tag} one system of {n} atoms, output {i}")
+        # (b) a batch of K systems
+        cells = [None]
+        if periodic:
+            full = kw["cell"].repeat(k, 1, 1).contiguous()
+            cells = [full, kw["cell"][:1].expand(k, 3, 3)]
+            assert cells[1].stride(0) == 0
+        for cell in cells:
+            bkw = dict(kw, batch_idx=bi, num_systems=k, **({} if cell is None else dict(cell=cell)))
+            many = fn(*big_args, **bkw, **big_lists)
+            for i in per_atom:
+                _bitwise(many[i], small[i], k, f"{op} {name} {tag} batch, output {i}")
+            for i in per_system:
+                assert many[i].shape[0] == k
+                _fold_close(many[i], small[i].double().expand_as(many[i]), small[i],
+                            f"{op} {name} {tag} batch of {k}{'' if cell is None or cell.stride(0) else ' (stride-0 cell)'}, output {i}")
+
+
+# ---- gaussian_charge_correction --------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("fmt", ["matrix", "list"])
+def test_gaussian_copies_as_one_system_and_as_a_batch(fmt):
+    from nvalchemiops import _capi as C
+    from nvalchemiops.interactions.electrostatics import gaussian_charge_correction as gcc
+
+    f = TG._single()
+    n0, blocks = f["n"], int(C.lib().mi_gaussian_charges_blocks())
+    k = _copies(n0, blocks)
+    n = k * n0
+    assert n > 256 * blocks and n % 64 != 0
+    P, Q, S = (f[x].repeat((k,) + (1,) * (f[x].dim() - 1)) for x in ("P", "Q", "S"))
+    if fmt == "matrix":
+        nm, sh = _tile_matrix(f["nm"], f["sh"], k)
+        big = dict(neighbor_matrix=nm, neighbor_matrix_shifts=sh, mask_value=n)
+    else:
+        lst, ptr, lsh = _tile_csr(f["nl"], f["ptr"], f["lsh"], k)
+        big = dict(neighbor_list=lst, neighbor_ptr=ptr, neighbor_shifts=lsh)
+    small = gcc(f["P"], f["Q"], f["S"], f["C"], **TG._fmt_kw(f, fmt), **TG.ALL)
+    for name, o in zip(TG.NAMES, small):
+        TG._close(o, f["ref"][name], f"fold sizes gaussian {fmt}: the small call, {name}")
+    plain = gcc(f["P"], f["Q"], f["S"], f["C"], **TG._fmt_kw(f, fmt), neutralizing_background=False, **TG.ALL)
+    # the closed-form background part of the small system: (2 pi / V) Q q_i s_i and its derivatives
+    s = torch.clamp(f["S"], min=0.0) ** 2
+    pref = 2.0 * math.pi / float(torch.linalg.det(f["C"][0]).abs())
+    qsum, qssum = f["Q"].sum(), (f["Q"] * s).sum()
+    bg = (pref * qsum * f["Q"] * s, None, pref * qssum + pref * qsum * s, 2.0 * pref * qsum * f["Q"] * torch.clamp(f["S"], min=0.0),
+          (pref * qsum * qssum) * torch.eye(3, dtype=F64, device=DEV)[None])
+    # (a) one system: without background bit for bit and the virial fold; with background the expectation above
+    one = gcc(P, Q, S, f["C"], **big, neutralizing_background=False, **TG.ALL)
+    for i in range(4):
+        _bitwise(one[i], plain[i], k, f"gaussian {fmt} one system without background, {TG.NAMES[i]}")
+    _fold_close(one[4], k * plain[4], one[4], f"gaussian {fmt} one system of {n} atoms without background, virial")
+    one = gcc(P, Q, S, f["C"], **big, **TG.ALL)
+    for i, name in enumerate(TG.NAMES):
+        want = plain[i] if bg[i] is None else plain[i] + k * bg[i]
+        want = want.repeat((k,) + (1,) * (want.dim() - 1)) if i < 4 else k * plain[4] + k * k * bg[4]
+        print(f"[fold] gaussian {fmt} one system with background, {name:13s} relative error {TG._close(one[i], want, f'gaussian {fmt} one system, {name}'):.3e}  (bar 1e-11)")
+    # (b) a batch of K systems: K cells, and one cell as a stride-0 expansion
+    bi = torch.arange(k, device=DEV, dtype=torch.int32).repeat_interleave(n0)
+    for cell in (f["C"].repeat(k, 1, 1).contiguous(), f["C"][:1].expand(k, 3, 3)):
+        label = f"gaussian {fmt} batch of {k}{'' if cell.stride(0) else ' (stride-0 cell)'}"
+        many = gcc(P, Q, S, cell, batch_idx=bi, **big, neutralizing_background=False, **TG.ALL)
+        for i in range(4):
+            _bitwise(many[i], plain[i], k, f"{label} without background, {TG.NAMES[i]}")
+        _fold_close(many[4], plain[4].expand_as(many[4]), plain[4], f"{label} without background, virial")
+        many = gcc(P, Q, S, cell, batch_idx=bi, **big, **TG.ALL)
+        for i in range(4):
+            TG._close(many[i], small[i].repeat((k,) + (1,) * (small[i].dim() - 1)), f"{label}, {TG.NAMES[i]}")
+        _fold_close(many[4], small[4].expand_as(many[4]), small[4], f"{label}, virial")
+
+
+# ---- charge_equilibration ------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("fmt", ["matrix", "csr"])
+def test_charge_equilibration_copies_as_one_system_and_as_a_batch(fmt):
+    from nvalchemiops import _capi as C
+    from nvalchemiops.interactions.electrostatics import charge_equilibration as qeq
+
+    tol, total, max_iterations = 1e-10, -0.7, 200
+    f = TQ._cluster((60,), 33)
+    n0, blocks = f["n"], int(C.lib().mi_qeq_blocks())
+    k = _copies(n0, blocks)
+    n = k * n0
+    assert n > 256 * blocks and n % 64 != 0
+    h = QR.dense_operator(f["pos"], f["sigma"], f["hard"], None, None, None, *f["ent"])
+    out = qeq(f["pos"], f["chi"], f["hard"], f["sigma"], total_charge=total, tolerance=tol, return_info=True, **TQ._kw(f, fmt, shifts=False))
+    q_ref, _ = TQ._check_solution(out, h, f["chi"], total, None, 1, tol, max_iterations, f"fold sizes qeq {fmt}: the small call")
+    b_norm = float(QR.projected_residual(h, f["chi"], torch.full((n0,), total / n0, dtype=F64, device=DEV))[0])
+    dq = 10.0 * tol * b_norm / float(torch.linalg.eigvalsh(h).min()) + 1e-14
+    pos, chi, hard, sigma = (f[x].repeat((k,) + (1,) * (f[x].dim() - 1)) for x in ("pos", "chi", "hard", "sigma"))
+    if fmt == "matrix":
+        nm, _ = _tile_matrix(f["nm"], None, k)
+        big = dict(neighbor_matrix=nm, mask_value=n)
+    else:
+        lst, ptr, _ = _tile_csr(f["nl"], f["ptr"], None, k)
+        big = dict(neighbor_list=lst, neighbor_ptr=ptr)
+    want = q_ref.repeat(k)
+    # one system of K n0 atoms with total charge K Q
+    one = qeq(pos, chi, hard, sigma, total_charge=k * total, tolerance=tol, max_iterations=max_iterations, return_info=True, **big)
+    err = float((one.charges - want).abs().max())
+    print(f"[fold] qeq {fmt} one system of {n} atoms: max|q - q_ref| {err:.3e}  bar {math.sqrt(k) * dq:.3e}  iterations {one.iterations.tolist()}")
+    assert err <= math.sqrt(k) * dq
+    assert abs(float(one.charges.sum()) - k * total) <= 1e-12 * n and int(one.iterations[0]) <= max_iterations
+    # a batch of K systems
+    bi = torch.arange(k, device=DEV, dtype=torch.int32).repeat_interleave(n0)
+    many = qeq(pos, chi, hard, sigma, total_charge=torch.full((k,), total, dtype=F64, device=DEV), batch_idx=bi, tolerance=tol,
+               max_iterations=max_iterations, return_info=True, **big)
+    err = (many.charges - want).abs().reshape(k, n0).max(1).values
+    print(f"[fold] qeq {fmt} batch of {k}: worst system max|q - q_ref| {float(err.max()):.3e}  bar {dq:.3e}  iterations {int(many.iterations.min())} - "
+          f"{int(many.iterations.max())}")
+    assert bool((err <= dq).all())
+    assert bool(((many.charges.reshape(k, n0).sum(1) - total).abs() <= 1e-12 * n0).all()) and bool((many.iterations <= max_iterations).all())

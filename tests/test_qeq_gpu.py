@@ -20,6 +20,7 @@ import torch
 
 from tests import gaussian_reference as GR
 from tests import qeq_reference as R
+from tests import systems as SY
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -236,28 +237,15 @@ def test_product_is_the_sum_of_the_public_charge_gradients(fmt):
 # ---- solves ----------------------------------------------------------------------------------------------------------------------------
 def _cluster(sizes, seed):
     """Clusters side by side (far apart is not needed: the all-pairs lists do not connect them), all-pairs FULL list per cluster."""
-    g = np.random.default_rng(seed)
-    pos, bi, ii, jj = [], [], [], []
-    off = 0
-    for b, nb in enumerate(sizes):
-        grid = np.array([(a, c, d) for a in range(6) for c in range(6) for d in range(6)], dtype=float)
-        pos.append(grid[g.choice(216, nb, replace=False)] * 1.6 + g.uniform(-0.3, 0.3, (nb, 3)))
-        bi += [b] * nb
-        a, c = np.nonzero(~np.eye(nb, dtype=bool))
-        ii.append(a + off)
-        jj.append(c + off)
-        off += nb
-    n = off
-    i, j = torch.as_tensor(np.concatenate(ii)), torch.as_tensor(np.concatenate(jj))
-    S = torch.zeros((i.shape[0], 3), dtype=torch.long)
+    g, pos, bi, ii, jj, sigma = SY.clusters(sizes, seed)  # (the recipe, shared with tests/layout_cases.py)
+    n = len(pos)
+    i, j = torch.as_tensor(ii), torch.as_tensor(jj)
+    S_ = torch.zeros((i.shape[0], 3), dtype=torch.long)
     m = max(max(sizes) - 1, 1) + 2
-    nm, sh = _lists(i, j, S, n, m, n)
+    nm, sh = _lists(i, j, S_, n, m, n)
     nl, ptr, lsh = _csr(nm, sh, n)
-    sigma = g.uniform(0.3, 0.8, n)
-    if n > 8:
-        sigma[[2, n - 3]] = 0.0
-    return dict(n=n, nsys=len(sizes), pos=_t(np.concatenate(pos)), bi=_t(np.array(bi, dtype=np.int32)), sigma=_t(sigma), chi=_t(g.normal(size=n)),
-                hard=_t(g.uniform(1.0, 2.0, n)), nm=nm, sh=sh, nl=nl, ptr=ptr, lsh=lsh, ent=(i.to(DEV), j.to(DEV), S.to(DEV)))
+    return dict(n=n, nsys=len(sizes), pos=_t(pos), bi=_t(bi), sigma=_t(sigma), chi=_t(g.normal(size=n)),
+                hard=_t(g.uniform(1.0, 2.0, n)), nm=nm, sh=sh, nl=nl, ptr=ptr, lsh=lsh, ent=(i.to(DEV), j.to(DEV), S_.to(DEV)))
 
 
 def _check_solution(out, h, chi, total, bi, nsys, tol, max_iterations, what):
