@@ -2,19 +2,10 @@
 // namespace: the coordination-number pass, the species compaction, the chain-rule pass and the per-system reduction are the two-body
 // code's own kernels (the chain pass is linear in dE/dCN, so it runs unchanged on the three-body dE/dCN).
 //
-// For every unordered triple of distinct atom images A, B, C with all three distances below `cutoff`:
-//   C9 = sqrt(C6_AB C6_AC C6_BC),  R0_XY = a1 sqrt(3 r4r2_X r4r2_Y) + a2,  a, b, c = r_AB^2, r_AC^2, r_BC^2,  P = r_AB r_AC r_BC
-//   ang = 0.375 (a + b - c)(a + c - b)(b + c - a) / P^5 + 1 / P^3,   fdamp = 1 / (1 + 6 (R0_AB R0_AC R0_BC / P)^(alpha / 3))
-//   E_ABC = s9 C9 ang fdamp
-// Owner-computes, no atomics: ONE BLOCK OF FOUR WAVES PER CENTRE ATOM i.  Seen from i the vector between two of its neighbours is
-// r_ik - r_ij with the unit shifts already applied, so a triangle needs no look-up of the j-k pair in anybody's row.  The block streams
-// row i, keeps the entries inside the cutoff and stages one record per kept entry in LDS (structure of arrays: displacement, sqrt(C6_ij),
-// dC6_ij/dCN_i / C6_ij, R0_ij, sqrt(sqrt(3) r4r2_j), species code, and either the five factorised Gaussian weights of j or CN_j).  Waves then
-// take rows p of the triangle (p, q > p) of staged records: record p is wave-uniform (LDS broadcast), lanes take consecutive q -- no integer
-// division, conflict-free LDS reads.  Every triangle is visited from each of its three vertices; a visit adds ONE THIRD of the energy and
-// of the explicit virial, the FULL explicit force on the centre and the FULL dE/dC6_ij dC6_ij/dCN_i + dE/dC6_ik dC6_ik/dCN_i to the
-// centre's dE/dCN -- complete without a write to j or k.  fp32 per-triple arithmetic, fp64 accumulation, as in the two-body passes.
-// Rows with more kept entries than a tile holds are processed tile pair by tile pair (the row is streamed again per staged tile).
+// The triple pass itself -- the triangle, its schedule, the ordinal staging, the per-triple arithmetic, the accumulators and the block
+// reduction -- is csrc/atm_core.h's, shared with the DFT-D4 kernel; read the algorithm there.  This file keeps what is D3's: the record
+// tail (the five factorised Gaussian weights of j, or CN_j), C6_jk from the three table MODEs, the radii of the two DAMPs, the fp32
+// outputs with a 3x3 per-atom virial, the workspace layout and the host driver.  R0_XY = a1 sqrt(3 r4r2_X r4r2_Y) + a2 with D3_DAMP_BJ.
 //
 // DAMP (compile-time, as in the two-body energy pass): D3_DAMP_BJ takes the radii from the BJ parameters as above; D3_DAMP_ZERO
 // (mi_d3_zero_atm) takes R0_XY = rs9 r0ab[Z_X, Z_Y] from the table of pair cutoff radii.  The radius of a species pair rides where its c6
@@ -24,16 +15,14 @@
 // radius is one more read next to the c6 of that pair, indexed by the two species codes the tile already holds; no argument and no LDS is
 // added.  A pair whose radius is <= 0 is stored as 0 and takes every triple it is part of out (its sqrt(C6) is staged / taken as 0).
 #pragma once
+#include "atm_core.h"
 
 #define D3_ATM_TILE 320   // staged records per LDS tile; two tiles + the species table = 40 KB per block: four blocks (16 waves) per CU
 #define D3_ATM_REC 13     // floats per record
-#define D3_ATM_WAVES 4
 #define D3_ATM_LDS_S 6    // factorised form: up to this many species keep the whole [S][S] c6 table in LDS (6.2 KB); more read it through L1
 #define D3_ATM_E12 6.14421235e-06f  // e^-12: the reference's cut on a Gaussian weight relative to the dominant one
 
-enum { ATM_RX = 0, ATM_RY, ATM_RZ, ATM_SC, ATM_G, ATM_R0, ATM_H, ATM_CODE, ATM_V0 };
-
-struct D3Atm { float s9, alpha, rc2; unsigned* visits; };
+struct D3AtmMath { static __device__ __forceinline__ float rcp(float x) { return D3_RCP(x); } };  // (the IEEE divide in the test library)
 
 // C6 of the pair (record p, record q) of two staged neighbours: no derivative (the visits from j and from k carry it)
 template <int MODE>
@@ -45,11 +34,11 @@ __device__ __forceinline__ float d3_atm_c6_jk(const float (*tp)[D3_ATM_TILE], in
     float w = 0.0f, z = 0.0f;
 #pragma unroll
     for (int a = 0; a < 5; ++a) {
-      const float va = tp[ATM_V0 + a][p];  // wave-uniform
+      const float va = tp[ATM_TAIL + a][p];  // wave-uniform
       if (__builtin_amdgcn_readfirstlane(__float_as_int(va)) == 0) continue;
 #pragma unroll
       for (int b = 0; b < 5; ++b) {
-        float L = va * tq[ATM_V0 + b][q];
+        float L = va * tq[ATM_TAIL + b][q];
         L = L >= D3_ATM_E12 ? L : 0.0f;
         w += L;
         z = fmaf(L, rows[a * 8 + b], z);
@@ -59,7 +48,7 @@ __device__ __forceinline__ float d3_atm_c6_jk(const float (*tp)[D3_ATM_TILE], in
   } else {
     const float4* t25 = t25base + (size_t)(cp * (MODE == 1 ? S : nz) + cq) * 25;
     float c6, dci;
-    d3_c6(tp[ATM_V0][p], tq[ATM_V0][q], t25, k3, c6, dci);
+    d3_c6(tp[ATM_TAIL][p], tq[ATM_TAIL][q], t25, k3, c6, dci);
     return c6;
   }
 }
@@ -72,18 +61,17 @@ __device__ __forceinline__ float d3_atm_radius(int cp, int cq, int S, int nz, co
 }
 
 template <class T, bool CSR, int MODE, int DAMP>
-__global__ __launch_bounds__(D3_ATM_WAVES * MI_WAVE) void d3_atm_kernel(
+__global__ __launch_bounds__(ATM_WAVES * MI_WAVE) void d3_atm_kernel(
     const T* __restrict__ pos, const int* __restrict__ numbers, int N, const int* __restrict__ idx, const int* __restrict__ ush,
-    const int* __restrict__ nptr, int M, int fill_value, const T* __restrict__ cell, const int* __restrict__ batch_idx, D3Dev P, D3Atm A,
+    const int* __restrict__ nptr, int M, int fill_value, const T* __restrict__ cell, const int* __restrict__ batch_idx, D3Dev P, AtmParams A,
     const float* __restrict__ cn, int want_virial, const int* __restrict__ smap, const D3Species* __restrict__ sinfo,
     const float4* __restrict__ ctab, const float* __restrict__ ftab, const float* __restrict__ fcr,
     const typename Vec4<T>::type* __restrict__ apos, const float4* __restrict__ aaux, const float4* __restrict__ aw,
     float* __restrict__ dEdCN, float* __restrict__ forces, float* __restrict__ e_atom, double* __restrict__ v_atom) {
-  __shared__ float tileA[D3_ATM_REC][D3_ATM_TILE];
-  __shared__ float tileB[D3_ATM_REC][D3_ATM_TILE];
+  __shared__ float tiles[2][D3_ATM_REC][D3_ATM_TILE];
   __shared__ float ft_lds[MODE == 2 ? D3_ATM_LDS_S * D3_ATM_LDS_S * D3_FROW : 1];
-  __shared__ double red[D3_ATM_WAVES][12];
-  __shared__ int cnt_sh[2][D3_ATM_WAVES];
+  __shared__ double red[ATM_WAVES][12];
+  __shared__ int cnt_sh[2][ATM_WAVES];
   const int S = sinfo->S;
   const int want_mode = S > D3_SMAX ? 0 : (sinfo->factorized ? 2 : 1);
   if (want_mode != MODE) return;  // all three variants are launched, as for the two-body energy pass
@@ -116,20 +104,15 @@ __global__ __launch_bounds__(D3_ATM_WAVES * MI_WAVE) void d3_atm_kernel(
   // Returns the number of kept entries of the whole row.  Block-cooperative; ends with a barrier.
   auto stage = [&](float (*tile)[D3_ATM_TILE], int k_lo) -> int {
     int running = 0, par = 0;
-    for (long long e0 = beg; e0 < end; e0 += D3_ATM_WAVES * MI_WAVE, par ^= 1) {
+    for (long long e0 = beg; e0 < end; e0 += ATM_WAVES * MI_WAVE, par ^= 1) {
       const D3Step s = d3_fetch<false>(idx, ush3, e0 + threadIdx.x, end, periodic);
       const bool v = s.in && ((unsigned)s.j < jlim);
       const int j = v ? s.j : i;
       const auto pj = apos[j];
       const PairGeom<T> g = d3_geom<T>(pj, pix, piy, piz, s.sh, cm, periodic);
       const bool keep = v && !(pj.w < (T)0) && g.ok && (g.r * g.r < A.rc2);
-      const unsigned long long m = __ballot(keep);
-      if (lane == 0) cnt_sh[par][wave] = (int)__popcll(m);
-      __syncthreads();  // (cnt_sh is double-buffered: one barrier per trip)
-      int before = 0, total = 0;
-#pragma unroll
-      for (int w = 0; w < D3_ATM_WAVES; ++w) { const int c = cnt_sh[par][w]; before += w < wave ? c : 0; total += c; }
-      const int slot = running + before + (int)__popcll(m & lanemask_lt()) - k_lo;
+      int total;
+      const int slot = atm_stage_slot(keep, cnt_sh, par, running, k_lo, lane, wave, total);
       const bool mine = keep && slot >= 0 && slot < D3_ATM_TILE;
       if (__any(mine)) {
         const int jj = mine ? j : i;
@@ -161,7 +144,7 @@ __global__ __launch_bounds__(D3_ATM_WAVES * MI_WAVE) void d3_atm_kernel(
           tile[ATM_H][slot] = D3_SQRT(1.73205081f * ax.y);  // h_j h_k = sqrt(3 r4r2_j r4r2_k)
           tile[ATM_CODE][slot] = __int_as_float(cj);
 #pragma unroll
-          for (int b = 0; b < 5; ++b) tile[ATM_V0 + b][slot] = vj[b];
+          for (int b = 0; b < 5; ++b) tile[ATM_TAIL + b][slot] = vj[b];
         }
       }
       running += total;
@@ -170,15 +153,11 @@ __global__ __launch_bounds__(D3_ATM_WAVES * MI_WAVE) void d3_atm_kernel(
     return running;
   };
 
-  double Fx = 0, Fy = 0, Fz = 0, E = 0, dacc = 0;
-  float V[6] = {0, 0, 0, 0, 0, 0};  // xx xy xz yy yz zz: fp32 lane partials flushed into fp64 once per row of the triangle
-  double V6[6] = {0, 0, 0, 0, 0, 0};
-  unsigned visits = 0;
-  const float alpha3 = A.alpha * (1.0f / 3.0f);
+  AtmAcc acc;
 
   // all pairs (p in tile tp, q in tile tq); same tile: q > p
   auto pairs = [&](const float (*tp)[D3_ATM_TILE], int np, const float (*tq)[D3_ATM_TILE], int nq, bool same) {
-    for (int p = wave; p < np; p += D3_ATM_WAVES) {
+    for (int p = wave; p < np; p += ATM_WAVES) {
       const float px = tp[ATM_RX][p], py = tp[ATM_RY][p], pz = tp[ATM_RZ][p];  // wave-uniform: LDS broadcasts
       const float scp = tp[ATM_SC][p], gp = tp[ATM_G][p], r0p = tp[ATM_R0][p], hp = tp[ATM_H][p];
       const float a = px * px + py * py + pz * pz;
@@ -188,82 +167,26 @@ __global__ __launch_bounds__(D3_ATM_WAVES * MI_WAVE) void d3_atm_kernel(
         const float jx = qx - px, jy = qy - py, jz = qz - pz;  // r_jk
         const float c = jx * jx + jy * jy + jz * jz;
         if (!(c < A.rc2) || c < 1e-24f) continue;
-        ++visits;
+        ++acc.visits;
         const float c6jk = d3_atm_c6_jk<MODE>(tp, p, tq, q, S, P.nz, ft, t25base, P.k3);
         float sjk = c6jk < 1e-12f ? 0.0f : D3_SQRT(c6jk);
-        float r0jk = 0.0f;
-        if constexpr (DAMP == D3_DAMP_ZERO) {
-          r0jk = d3_atm_radius<MODE>(__float_as_int(tp[ATM_CODE][p]), __float_as_int(tq[ATM_CODE][q]), S, P.nz, ft, t25base);
-          sjk = r0jk > 0.0f ? sjk : 0.0f;
-        }
-        const float b = qx * qx + qy * qy + qz * qz;
-        // a + b - c = 2 r_ij.r_ik etc.: the three factors as dot products, not as differences of squared lengths
-        const float x = 2.0f * (px * qx + py * qy + pz * qz), y = -2.0f * (px * jx + py * jy + pz * jz), z = 2.0f * (qx * jx + qy * jy + qz * jz);
-        const float pinv = __builtin_amdgcn_rsqf(a * b * c);
-        const float pinv3 = pinv * pinv * pinv, k5 = 0.375f * pinv3 * pinv * pinv;
-        const float yz = y * z, xz = x * z, xy = x * y, nn = xy * z;
-        const float ang = fmaf(k5, nn, pinv3);
         float r0;
-        if constexpr (DAMP == D3_DAMP_ZERO) r0 = r0p * tq[ATM_R0][q] * r0jk;
-        else
-        r0 = r0p * tq[ATM_R0][q] * fmaf(P.a1, hp * tq[ATM_H][q], P.a2);
-        // (R0 / P)^(alpha / 3) with a runtime exponent: one log2 / exp2 pair per triple
-        const float t = __builtin_amdgcn_exp2f(alpha3 * __builtin_amdgcn_logf(r0 * pinv));
-        const float fd = D3_RCP(fmaf(6.0f, t, 1.0f));
-        const float c9 = A.s9 * scp * tq[ATM_SC][q] * sjk;
-        const float e = c9 * ang * fd;
-        // dE/da = C9 fd (k5 dN/da + B0 / a),  B0 = ang fd t alpha - (2.5 k5 N + 1.5 / P^3); likewise b, c
-        const float b0 = ang * fd * t * A.alpha - fmaf(2.5f * k5, nn, 1.5f * pinv3);
-        const float cf = c9 * fd;
-        const float dEda = cf * fmaf(k5, yz + xz - xy, b0 * inva);
-        const float dEdb = cf * fmaf(k5, yz - xz + xy, b0 * D3_RCP(b));
-        E += (double)e;
-        dacc += (double)(0.5f * e * (gp + tq[ATM_G][q]));
-        const float fx = 2.0f * (dEda * px + dEdb * qx), fy = 2.0f * (dEda * py + dEdb * qy), fz = 2.0f * (dEda * pz + dEdb * qz);
-        Fx += (double)fx; Fy += (double)fy; Fz += (double)fz;
-        if (want_virial) {
-          const float dEdc = cf * fmaf(k5, xz + xy - yz, b0 * D3_RCP(c));
-          const float ax = dEda * px, ay = dEda * py, az = dEda * pz, bx = dEdb * qx, by = dEdb * qy, bz = dEdb * qz;
-          const float cx = dEdc * jx, cy = dEdc * jy, cz = dEdc * jz;
-          V[0] += ax * px + bx * qx + cx * jx; V[1] += ax * py + bx * qy + cx * jy; V[2] += ax * pz + bx * qz + cx * jz;
-          V[3] += ay * py + by * qy + cy * jy; V[4] += ay * pz + by * qz + cy * jz; V[5] += az * pz + bz * qz + cz * jz;
+        if constexpr (DAMP == D3_DAMP_ZERO) {
+          const float r0jk = d3_atm_radius<MODE>(__float_as_int(tp[ATM_CODE][p]), __float_as_int(tq[ATM_CODE][q]), S, P.nz, ft, t25base);
+          sjk = r0jk > 0.0f ? sjk : 0.0f;
+          r0 = r0p * tq[ATM_R0][q] * r0jk;
+        } else {
+          r0 = r0p * tq[ATM_R0][q] * fmaf(P.a1, hp * tq[ATM_H][q], P.a2);
         }
+        atm_triple<D3AtmMath>(px, py, pz, a, inva, scp, gp, qx, qy, qz, tq[ATM_SC][q], tq[ATM_G][q], sjk, r0, A, acc, want_virial);
       }
-      if (want_virial) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) { V6[k] += (double)V[k]; V[k] = 0.0f; }
-      }
+      if (want_virial) acc.flush_row();
     }
   };
 
-  const int n = stage(tileA, 0);
-  const int ntiles = (n + D3_ATM_TILE - 1) / D3_ATM_TILE;
-  for (int tp = 0; tp < ntiles; ++tp) {
-    if (tp > 0) { __syncthreads(); stage(tileA, tp * D3_ATM_TILE); }
-    const int np = min(D3_ATM_TILE, n - tp * D3_ATM_TILE);
-    pairs(tileA, np, tileA, np, true);
-    for (int tq = tp + 1; tq < ntiles; ++tq) {
-      __syncthreads();  // the waves are done with the previous B tile
-      stage(tileB, tq * D3_ATM_TILE);
-      pairs(tileA, np, tileB, min(D3_ATM_TILE, n - tq * D3_ATM_TILE), false);
-    }
-  }
-
-  double r12[12] = {E, Fx, Fy, Fz, dacc, V6[0], V6[1], V6[2], V6[3], V6[4], V6[5], (double)visits};
-#pragma unroll
-  for (int k = 0; k < 12; ++k) {
-    if (k >= 5 && k < 11 && !want_virial) continue;
-    const double s = wave_sum(r12[k]);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < 12) {
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < D3_ATM_WAVES; ++w) s += red[w][threadIdx.x];
-    red[0][threadIdx.x] = s;
-  }
-  __syncthreads();
+  atm_tile_pairs(stage, pairs, tiles);
+  const double r12[12] = {acc.E, acc.Fx, acc.Fy, acc.Fz, acc.dacc, acc.V6[0], acc.V6[1], acc.V6[2], acc.V6[3], acc.V6[4], acc.V6[5], (double)acc.visits};
+  atm_block_reduce(r12, red, lane, wave, want_virial);
   if (threadIdx.x == 0) {
     forces[3 * (size_t)i] = (float)red[0][1]; forces[3 * (size_t)i + 1] = (float)red[0][2]; forces[3 * (size_t)i + 2] = (float)red[0][3];
     dEdCN[i] = (float)red[0][4];
@@ -271,8 +194,8 @@ __global__ __launch_bounds__(D3_ATM_WAVES * MI_WAVE) void d3_atm_kernel(
     if (A.visits) A.visits[i] = (unsigned)red[0][11];
   }
   if (want_virial && threadIdx.x < 9) {
-    const int r = threadIdx.x / 3, c = threadIdx.x - 3 * r, lo = r < c ? r : c, hi2 = r < c ? c : r;
-    const int m = lo == 0 ? hi2 : (lo == 1 ? hi2 + 2 : 5);  // row-major (r, c) -> index in {xx, xy, xz, yy, yz, zz}
+    const int r = threadIdx.x / 3, c = threadIdx.x - 3 * r;
+    const int m = r == c ? r : r + c + 2;  // row-major (r, c) -> index in {xx, yy, zz, xy, xz, yz}
     // per edge dE/dr / r = 2 dE/d(r^2); a third of the triangle's -sum_edges (dE/dr / r) r (x) r per visit
     v_atom[9 * (size_t)i + threadIdx.x] = -(2.0 / 3.0) * red[0][5 + m];
   }
@@ -343,10 +266,10 @@ int d3_atm_impl(const T* pos, const int* numbers, int N, const int* idx, const i
                                 nullptr, W, nullptr, 0)));
   MI_LAUNCH_CHECK();
   // 2. triples
-  const D3Atm A{s9, alpha, cutoff * cutoff, reinterpret_cast<unsigned*>(ws + LA.visits)};
+  const AtmParams A{s9, alpha, cutoff * cutoff, reinterpret_cast<unsigned*>(ws + LA.visits)};
   auto launch = [&](auto mode) {
     constexpr int MODE_ = decltype(mode)::value;
-    d3_atm_kernel<T, CSR, MODE_, DAMP><<<N, D3_ATM_WAVES * MI_WAVE, 0, st>>>(pos, numbers, N, idx, ush, nptr, M, fill_value, cell, batch_idx, P, A, cn, want_virial, smap,
+    d3_atm_kernel<T, CSR, MODE_, DAMP><<<N, ATM_WAVES * MI_WAVE, 0, st>>>(pos, numbers, N, idx, ush, nptr, M, fill_value, cell, batch_idx, P, A, cn, want_virial, smap,
                                                                     sinfo, ctab, ftab, fcr, apos, aaux, aw, dEdCN, forces, e_atom, v_atom);
   };
   MI_TIMED("d3_atm_triples", st, (launch(std::integral_constant<int, 2>{}), launch(std::integral_constant<int, 1>{}), launch(std::integral_constant<int, 0>{})));

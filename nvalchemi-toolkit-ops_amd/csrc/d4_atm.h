@@ -3,18 +3,15 @@
 // the chain-rule pass (linear in dE/dCN, so it runs unchanged on the three-body dE/dCN) and the fixed-order fold are the two-body code's
 // own kernels, launched exactly as mi_d4 launches them.
 //
-// For every unordered triple of distinct atom images A, B, C with all three distances below `cutoff`:
+// The triangle energy is atm_core.h's E_ABC, with D4's pair coefficients and the BJ radii (a triple with any C6 < 1e-12 contributes nothing):
 //   C6_XY = sum_ab w_X[a] c6_ref[Z_X, Z_Y, a, b] w_Y[b],   w_X[a] = W_a(CN_X) zeta_a(q = 0)       (the weight kernel on a zeroed charge array)
-//   C9 = sqrt(C6_AB C6_AC C6_BC),  R0_XY = a1 sqrt(3 r4r2_X r4r2_Y) + a2,  a, b, c = r_AB^2, r_AC^2, r_BC^2,  P = r_AB r_AC r_BC
-//   ang = 0.375 (a + b - c)(a + c - b)(b + c - a) / P^5 + 1 / P^3,   fdamp = 1 / (1 + 6 (R0_AB R0_AC R0_BC / P)^(alpha / 3))
-//   E_ABC = s9 C9 ang fdamp                                                                        (nothing if any C6 < 1e-12)
-// Execution shape (csrc/d3_atm.h's): owner-computes, no atomics, ONE BLOCK OF FOUR WAVES PER CENTRE ATOM i.  The block streams row i, keeps
-// the entries inside the cutoff and stages one record of 16 floats per kept entry in LDS (structure of arrays: displacement, sqrt(C6_ij),
-// dC6_ij/dCN_i / C6_ij, R0_ij, sqrt(sqrt(3) r4r2_j), species code, the neighbour's eight weights).  Waves then take rows p of the triangle
-// (p, q > p) of staged records: record p is wave-uniform (LDS broadcast), lanes take consecutive q.  Every triangle is visited from each of
-// its three vertices; a visit adds ONE THIRD of the energy and of the explicit virial, the FULL explicit force on the centre and
-// 1/2 E (g_ij + g_ik) to the centre's dE/dCN.  fp32 per-triple arithmetic, fp64 accumulators, one block reduction.  Rows with more kept
-// entries than a tile holds are processed tile pair by tile pair (the row is streamed again per staged tile).
+//   R0_XY = a1 sqrt(3 r4r2_X r4r2_Y) + a2
+// The triple pass -- the triangle, its schedule, the ordinal staging, the tile-pair loop and the block reduction -- is csrc/atm_core.h's,
+// shared with the DFT-D3 kernel; read the algorithm there.  This file keeps what is D4's: the record tail (the neighbour's eight weights; 16
+// floats per record), C6_ij and C6_jk from the `ctr` and `strip` contractions, the fp64 row words written through pointers parked in LDS,
+// the workspace layout and the host driver -- and ITS OWN TEXT of the accumulators and of the per-triple arithmetic, which is atm_core.h's
+// atm_triple line for line: d4.hip is built with the SLP vectoriser on, and through AtmAcc / atm_triple it packed the visit's products
+// differently (forces moved in the last bit, the pass ran 0.5 - 1.9 % slower).  A fix to the arithmetic goes into both places.
 //
 // The C6 values, the energy pass's contraction applied twice:
 //   centre      the block contracts w_i and dw_i/dCN with cc6[c_i, t, :, :] once for the first D4_SLOTS species t (LDS `ctr`); C6_ij and its
@@ -27,14 +24,10 @@
 // Block-uniform values that are needed only while staging (the cell, the centre's position) or only in the last lines (the output
 // pointers) are parked in LDS: held in scalar registers through every loop they made the kernel spill SGPRs.
 #pragma once
+#include "atm_core.h"
 
 #define D4_ATM_TILE 288   // staged records per LDS tile
 #define D4_ATM_REC 16     // floats per record
-#define D4_ATM_WAVES 4
-
-enum { D4A_RX = 0, D4A_RY, D4A_RZ, D4A_SC, D4A_G, D4A_R0, D4A_H, D4A_CODE, D4A_W0 };
-
-struct D4Atm { float s9, alpha, rc2; unsigned* visits; };
 
 // a wave's own LDS writes become visible to its own later reads (the strip is private to the wave: no block barrier)
 __device__ __forceinline__ void d4_atm_wave_sync() {
@@ -57,18 +50,18 @@ __device__ __forceinline__ void d4_atm_direct(const float* __restrict__ c, const
 }
 
 template <class T, bool CSR, bool VIR>
-__global__ __launch_bounds__(D4_ATM_WAVES * MI_WAVE) void d4_atm_kernel(const D4Rec<T>* __restrict__ rec, int N, const int* __restrict__ idx,
+__global__ __launch_bounds__(ATM_WAVES * MI_WAVE) void d4_atm_kernel(const D4Rec<T>* __restrict__ rec, int N, const int* __restrict__ idx,
                                                                         const int* __restrict__ ush, const int* __restrict__ nptr, int M,
                                                                         int fill_value, const T* __restrict__ cell, const int* __restrict__ batch_idx,
                                                                         const int* __restrict__ info, const float* __restrict__ ptab,
                                                                         const float* __restrict__ cc6, const float* __restrict__ wrec, D4Scalars P,
-                                                                        D4Atm A, double* __restrict__ row,
+                                                                        AtmParams A, double* __restrict__ row,
                                                                         double* __restrict__ dEdCN, double* __restrict__ fdir) {
   __shared__ __attribute__((aligned(16))) float tiles[2][D4_ATM_REC][D4_ATM_TILE];
   __shared__ __attribute__((aligned(16))) float ctr[D4_SLOTS][16];                  // [slot][k = 0 (w_i), 1 (dw_i/dCN)][8]
-  __shared__ __attribute__((aligned(16))) float strip[D4_ATM_WAVES][D4_SLOTS * 8];  // per wave: [slot][8] of its current row p
-  __shared__ double red[D4_ATM_WAVES][12];
-  __shared__ int cnt_sh[2][D4_ATM_WAVES];
+  __shared__ __attribute__((aligned(16))) float strip[ATM_WAVES][D4_SLOTS * 8];  // per wave: [slot][8] of its current row p
+  __shared__ double red[ATM_WAVES][12];
+  __shared__ int cnt_sh[2][ATM_WAVES];
   __shared__ void* out_sh[4];  // the output pointers, parked for the block's last lines (scalar registers again)
   __shared__ T geo[12];  // the cell of the centre's system (zero without shifts) and the centre's position
   const int i = blockIdx.x;
@@ -123,7 +116,7 @@ __global__ __launch_bounds__(D4_ATM_WAVES * MI_WAVE) void d4_atm_kernel(const D4
   // Returns the number of kept entries of the whole row.  Block-cooperative; ends with a barrier.
   auto stage = [&](float (*tile)[D4_ATM_TILE], int k_lo) -> int {
     int running = 0, par = 0;
-    for (int e0 = 0; e0 < len; e0 += D4_ATM_WAVES * MI_WAVE, par ^= 1) {
+    for (int e0 = 0; e0 < len; e0 += ATM_WAVES * MI_WAVE, par ^= 1) {
       const int e = e0 + (int)threadIdx.x;
       bool keep = false;
       int j = i, cj = -1;
@@ -144,13 +137,8 @@ __global__ __launch_bounds__(D4_ATM_WAVES * MI_WAVE) void d4_atm_kernel(const D4
           }
         }
       }
-      const unsigned long long m = __ballot(keep);
-      if (lane == 0) cnt_sh[par][wave] = (int)__popcll(m);
-      __syncthreads();  // (cnt_sh is double-buffered: one barrier per trip)
-      int before = 0, total = 0;
-#pragma unroll
-      for (int w = 0; w < D4_ATM_WAVES; ++w) { const int c = cnt_sh[par][w]; before += w < wave ? c : 0; total += c; }
-      const int slot = running + before + (int)__popcll(m & lanemask_lt()) - k_lo;
+      int total;
+      const int slot = atm_stage_slot(keep, cnt_sh, par, running, k_lo, lane, wave, total);
       if (keep && slot >= 0 && slot < D4_ATM_TILE) {
         const float4* wj4 = reinterpret_cast<const float4*>(wrec + D4_WREC * (size_t)j);
         const float4 wa = wj4[0], wb = wj4[1];
@@ -166,14 +154,14 @@ __global__ __launch_bounds__(D4_ATM_WAVES * MI_WAVE) void d4_atm_kernel(const D4
           d4_atm_direct(cc6 + ((size_t)ci * S + cj) * 56, wi, wi + 8, wj, c6, dci);
         }
         const bool live = !(c6 < 1e-12f);  // a triple with any C6 < 1e-12 contributes nothing: sqrt(C6) = 0 zeroes every term of it
-        tile[D4A_RX][slot] = rx; tile[D4A_RY][slot] = ry; tile[D4A_RZ][slot] = rz;
-        tile[D4A_SC][slot] = live ? sqrtf(c6) : 0.0f;
-        tile[D4A_G][slot] = live ? dci / c6 : 0.0f;
-        tile[D4A_R0][slot] = P.a1 * sqrtf(ptab[D4_PAIR * ((size_t)ci * S + cj) + 2]) + P.a2;
-        tile[D4A_H][slot] = sqrtf(sqrtf(ptab[D4_PAIR * ((size_t)cj * S + cj) + 2]));  // h_j h_k = sqrt(3 r4r2_j r4r2_k)
-        tile[D4A_CODE][slot] = __int_as_float(cj);
-        tile[D4A_W0 + 0][slot] = wa.x; tile[D4A_W0 + 1][slot] = wa.y; tile[D4A_W0 + 2][slot] = wa.z; tile[D4A_W0 + 3][slot] = wa.w;
-        tile[D4A_W0 + 4][slot] = wb.x; tile[D4A_W0 + 5][slot] = wb.y; tile[D4A_W0 + 6][slot] = wb.z; tile[D4A_W0 + 7][slot] = wb.w;
+        tile[ATM_RX][slot] = rx; tile[ATM_RY][slot] = ry; tile[ATM_RZ][slot] = rz;
+        tile[ATM_SC][slot] = live ? sqrtf(c6) : 0.0f;
+        tile[ATM_G][slot] = live ? dci / c6 : 0.0f;
+        tile[ATM_R0][slot] = P.a1 * sqrtf(ptab[D4_PAIR * ((size_t)ci * S + cj) + 2]) + P.a2;
+        tile[ATM_H][slot] = sqrtf(sqrtf(ptab[D4_PAIR * ((size_t)cj * S + cj) + 2]));  // h_j h_k = sqrt(3 r4r2_j r4r2_k)
+        tile[ATM_CODE][slot] = __int_as_float(cj);
+        tile[ATM_TAIL + 0][slot] = wa.x; tile[ATM_TAIL + 1][slot] = wa.y; tile[ATM_TAIL + 2][slot] = wa.z; tile[ATM_TAIL + 3][slot] = wa.w;
+        tile[ATM_TAIL + 4][slot] = wb.x; tile[ATM_TAIL + 5][slot] = wb.y; tile[ATM_TAIL + 6][slot] = wb.z; tile[ATM_TAIL + 7][slot] = wb.w;
       }
       running += total;
     }
@@ -190,12 +178,12 @@ __global__ __launch_bounds__(D4_ATM_WAVES * MI_WAVE) void d4_atm_kernel(const D4
 
   // all pairs (p in tile tp, q in tile tq); same tile: q > p
   auto pairs = [&](const float (*tp)[D4_ATM_TILE], int np, const float (*tq)[D4_ATM_TILE], int nq, bool same) {
-    for (int p = wave; p < np; p += D4_ATM_WAVES) {
+    for (int p = wave; p < np; p += ATM_WAVES) {
       const int q0 = same ? p + 1 : 0;
       if (q0 >= nq) continue;  // (wave-uniform)
-      const float px = tp[D4A_RX][p], py = tp[D4A_RY][p], pz = tp[D4A_RZ][p];  // wave-uniform: LDS broadcasts
-      const float scp = tp[D4A_SC][p], gp = tp[D4A_G][p], r0p = tp[D4A_R0][p], hp = tp[D4A_H][p];
-      const int cp = __float_as_int(tp[D4A_CODE][p]);
+      const float px = tp[ATM_RX][p], py = tp[ATM_RY][p], pz = tp[ATM_RZ][p];  // wave-uniform: LDS broadcasts
+      const float scp = tp[ATM_SC][p], gp = tp[ATM_G][p], r0p = tp[ATM_R0][p], hp = tp[ATM_H][p];
+      const int cp = __float_as_int(tp[ATM_CODE][p]);
       // the wave's strip: v_t[b] = sum_a w_p[a] c6[c_p, t, a, b] for the species in the slots; lane (tl, b) of trip k takes t = 8 k + tl
       d4_atm_wave_sync();  // the readers of the previous row are done
       for (int k = 0; 8 * k < ns; ++k) {
@@ -204,7 +192,7 @@ __global__ __launch_bounds__(D4_ATM_WAVES * MI_WAVE) void d4_atm_kernel(const D4
         if (t < ns) {
           const float* c = cc6 + ((size_t)cp * S + t) * 56 + b;
 #pragma unroll
-          for (int a = 0; a < D4_REFS; ++a) o = fmaf(tp[D4A_W0 + a][p], c[8 * a], o);
+          for (int a = 0; a < D4_REFS; ++a) o = fmaf(tp[ATM_TAIL + a][p], c[8 * a], o);
         }
         mine[t * 8 + b] = o;
       }
@@ -212,15 +200,15 @@ __global__ __launch_bounds__(D4_ATM_WAVES * MI_WAVE) void d4_atm_kernel(const D4
       const float a = px * px + py * py + pz * pz;
       const float inva = __builtin_amdgcn_rcpf(a);
       for (int q = q0 + lane; q < nq; q += MI_WAVE) {
-        const float qx = tq[D4A_RX][q], qy = tq[D4A_RY][q], qz = tq[D4A_RZ][q];
+        const float qx = tq[ATM_RX][q], qy = tq[ATM_RY][q], qz = tq[ATM_RZ][q];
         const float jx = qx - px, jy = qy - py, jz = qz - pz;  // r_jk
         const float c = jx * jx + jy * jy + jz * jz;
         if (!(c < A.rc2) || c < 1e-24f) continue;
         ++visits;
-        const int cq = __float_as_int(tq[D4A_CODE][q]);
+        const int cq = __float_as_int(tq[ATM_CODE][q]);
         float wq[8];
 #pragma unroll
-        for (int b = 0; b < 8; ++b) wq[b] = tq[D4A_W0 + b][q];
+        for (int b = 0; b < 8; ++b) wq[b] = tq[ATM_TAIL + b][q];
         float c6jk;
         if (cq < D4_SLOTS) {
           const float4* sv = reinterpret_cast<const float4*>(mine + cq * 8);
@@ -229,7 +217,7 @@ __global__ __launch_bounds__(D4_ATM_WAVES * MI_WAVE) void d4_atm_kernel(const D4
         } else {
           float unused, wp[D4_REFS];
 #pragma unroll
-          for (int a = 0; a < D4_REFS; ++a) wp[a] = tp[D4A_W0 + a][p];
+          for (int a = 0; a < D4_REFS; ++a) wp[a] = tp[ATM_TAIL + a][p];
           d4_atm_direct(cc6 + ((size_t)cp * S + cq) * 56, wp, nullptr, wq, c6jk, unused);
         }
         const float sjk = c6jk < 1e-12f ? 0.0f : __builtin_amdgcn_sqrtf(c6jk);
@@ -240,11 +228,11 @@ __global__ __launch_bounds__(D4_ATM_WAVES * MI_WAVE) void d4_atm_kernel(const D4
         const float pinv3 = pinv * pinv * pinv, k5 = 0.375f * pinv3 * pinv * pinv;
         const float yz = y * z, xz = x * z, xy = x * y, nn = xy * z;
         const float ang = fmaf(k5, nn, pinv3);
-        const float r0 = r0p * tq[D4A_R0][q] * fmaf(P.a1, hp * tq[D4A_H][q], P.a2);
+        const float r0 = r0p * tq[ATM_R0][q] * fmaf(P.a1, hp * tq[ATM_H][q], P.a2);
         // (R0 / P)^(alpha / 3) with a runtime exponent: one log2 / exp2 pair per triple
         const float t = __builtin_amdgcn_exp2f(alpha3 * __builtin_amdgcn_logf(r0 * pinv));
         const float fd = __builtin_amdgcn_rcpf(fmaf(6.0f, t, 1.0f));
-        const float c9 = A.s9 * scp * tq[D4A_SC][q] * sjk;
+        const float c9 = A.s9 * scp * tq[ATM_SC][q] * sjk;
         const float e = c9 * ang * fd;
         // dE/da = C9 fd (k5 dN/da + B0 / a),  B0 = ang fd t alpha - (2.5 k5 N + 1.5 / P^3); likewise b, c
         const float b0 = ang * fd * t * A.alpha - fmaf(2.5f * k5, nn, 1.5f * pinv3);
@@ -252,7 +240,7 @@ __global__ __launch_bounds__(D4_ATM_WAVES * MI_WAVE) void d4_atm_kernel(const D4
         const float dEda = cf * fmaf(k5, yz + xz - xy, b0 * inva);
         const float dEdb = cf * fmaf(k5, yz - xz + xy, b0 * __builtin_amdgcn_rcpf(b));
         E += (double)e;
-        dacc += (double)(0.5f * e * (gp + tq[D4A_G][q]));
+        dacc += (double)(0.5f * e * (gp + tq[ATM_G][q]));
         const float fx = 2.0f * (dEda * px + dEdb * qx), fy = 2.0f * (dEda * py + dEdb * qy), fz = 2.0f * (dEda * pz + dEdb * qz);
         Fx += (double)fx; Fy += (double)fy; Fz += (double)fz;
         if constexpr (VIR) {
@@ -270,32 +258,9 @@ __global__ __launch_bounds__(D4_ATM_WAVES * MI_WAVE) void d4_atm_kernel(const D4
     }
   };
 
-  // tile pairs (tp, tq >= tp): the p tile in `tiles[0]`, another q tile in `tiles[1]`; one copy of the staging and of the triangle loops
-  for (int tp = 0, ntiles = 1; tp < ntiles; ++tp) {
-    for (int tq = tp; tq < ntiles; ++tq) {
-      const int w = tq == tp ? 0 : 1;
-      __syncthreads();  // the waves are done with the tile that is staged over
-      const int n = stage(tiles[w], tq * D4_ATM_TILE);
-      ntiles = (n + D4_ATM_TILE - 1) / D4_ATM_TILE;  // (the same number every time: 0 ends both loops)
-      pairs(tiles[0], min(D4_ATM_TILE, n - tp * D4_ATM_TILE), tiles[w], min(D4_ATM_TILE, n - tq * D4_ATM_TILE), w == 0);
-    }
-  }
-
-  double r12[12] = {E, Fx, Fy, Fz, dacc, V6[0], V6[1], V6[2], V6[3], V6[4], V6[5], (double)visits};
-#pragma unroll
-  for (int k = 0; k < 12; ++k) {
-    if (k >= 5 && k < 11 && !VIR) continue;
-    const double s = wave_sum(r12[k]);
-    if (lane == 0) red[wave][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < 12 && (VIR || threadIdx.x < 5 || threadIdx.x == 11)) {  // (the virial words are only written with VIR)
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < D4_ATM_WAVES; ++w) s += red[w][threadIdx.x];
-    red[0][threadIdx.x] = s;
-  }
-  __syncthreads();
+  atm_tile_pairs(stage, pairs, tiles);
+  const double r12[12] = {E, Fx, Fy, Fz, dacc, V6[0], V6[1], V6[2], V6[3], V6[4], V6[5], (double)visits};
+  atm_block_reduce(r12, red, lane, wave, VIR);
   if (threadIdx.x == 0) {
     double* o = static_cast<double*>(out_sh[0]);
     double* dcn_o = static_cast<double*>(out_sh[1]);
@@ -366,12 +331,12 @@ int d4_atm_impl(const T* positions, const int32_t* numbers, int N, const int32_t
   MI_TIMED("d4_atm_weights", st, (d4_weights_kernel<<<per_atom, 256, 0, st>>>(numbers, q0, N, nz, q->n_ref, q->ngw, q->cn_ref, q->q_ref, q->zeff,
                                                                              q->gam, P, cn64, wrec)));
   // 2. triples
-  const D4Atm A{s9, alpha, cutoff * cutoff, visits};
+  const AtmParams A{s9, alpha, cutoff * cutoff, visits};
   MI_TIMED("d4_atm_triples", st, {
     if (want_virial)
-      d4_atm_kernel<T, CSR, true><<<N, D4_ATM_WAVES * MI_WAVE, 0, st>>>(rec, N, idx, ush, nptr, M, fill_value, cell, bi, info, ptab, cc6, wrec, P, A, row, dEdCN, fdir);
+      d4_atm_kernel<T, CSR, true><<<N, ATM_WAVES * MI_WAVE, 0, st>>>(rec, N, idx, ush, nptr, M, fill_value, cell, bi, info, ptab, cc6, wrec, P, A, row, dEdCN, fdir);
     else
-      d4_atm_kernel<T, CSR, false><<<N, D4_ATM_WAVES * MI_WAVE, 0, st>>>(rec, N, idx, ush, nptr, M, fill_value, cell, bi, info, ptab, cc6, wrec, P, A, row, dEdCN, fdir);
+      d4_atm_kernel<T, CSR, false><<<N, ATM_WAVES * MI_WAVE, 0, st>>>(rec, N, idx, ush, nptr, M, fill_value, cell, bi, info, ptab, cc6, wrec, P, A, row, dEdCN, fdir);
   });
   MI_LAUNCH_CHECK();
   // 3. chain rule through the coordination numbers, over the whole list; 4. per-system sums

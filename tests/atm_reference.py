@@ -42,6 +42,32 @@ def lattice_box(n=(4, 5, 5), a=4.2, jitter=0.25, seed=3, triclinic=True, dtype=n
     return pos.astype(dtype), cell.astype(dtype)
 
 
+def centre_and_shell(m, radius=19.0, jitter=0.2, seed=29):
+    """Test system with ONE long row: atom 0 at the origin and m atoms on a Fibonacci sphere of `radius` Bohr around it, every coordinate
+    moved by up to +-jitter.  With a three-body cutoff just above the radius the centre keeps all m, a shell atom only its cap of the
+    sphere -- a row of many LDS tiles of the triple pass at a cost the float64 restatement can pay (a cluster in which EVERY row is that
+    long costs it m^3 / 6 triples).  Returns positions [m + 1, 3], float32."""
+    k = np.arange(m) + 0.5
+    ct = 1.0 - 2.0 * k / m
+    st = np.sqrt(1.0 - ct * ct)
+    phi = k * np.pi * (3.0 - np.sqrt(5.0))
+    shell = radius * np.stack([st * np.cos(phi), st * np.sin(phi), ct], 1) + np.random.default_rng(seed).uniform(-jitter, jitter, (m, 3))
+    return np.concatenate([np.zeros((1, 3)), shell]).astype(np.float32)
+
+
+def kept_and_triples(pos, cutoff):
+    """Of a free system, from numpy distances: (entries each row keeps inside `cutoff` [N], shell pairs of atom 0 = pairs of its kept
+    entries that are themselves closer than `cutoff`, unordered triples with all three sides inside `cutoff`, the smallest |distance -
+    cutoff| of any pair -- a float32 kernel and this count agree only while that is far above float32 rounding)."""
+    pos = np.asarray(pos, np.float64)
+    d = np.linalg.norm(pos[:, None, :] - pos[None, :, :], axis=2)
+    a = ((d < cutoff) & (d > 0)).astype(np.float64)  # (counts below 2^53: exact in float64, and a BLAS product)
+    on0 = a[0] > 0
+    pairs0 = int(a[np.ix_(on0, on0)].sum()) // 2
+    triples = int(round(((a @ a) * a).sum())) // 6
+    return a.sum(1).astype(np.int64), pairs0, triples, float(np.abs(d - cutoff).min())
+
+
 def enumerate_pairs(pos, cell, cutoff):
     """All ordered pairs (i, j, integer shift) with 1e-12 <= |r_j + shift.cell - r_i| < cutoff, i's image in the home cell; sorted by i.
     `cell` None: free space (shift 0)."""
@@ -105,7 +131,7 @@ def c6_interpolate(cn_x, cn_y, zx, zy, c6ab, cn_ref, k3):
 
 
 def _system(pos, numbers, tables, cell, a1, a2, list_cutoff, three_body_cutoff, s9, alpha, k1, k3, s6, s8, term, wd, chunk):
-    """One system: (energy, forces[N,3], virial[3,3] or None, cn[N]) as float64 numpy."""
+    """One system: (energy, forces[N,3], virial[3,3] or None, cn[N]) as float64 numpy, and the number of triples enumerated (term "atm")."""
     f64 = torch.float64
     n = len(pos)
     z = torch.as_tensor(np.asarray(numbers), dtype=torch.long)
@@ -141,6 +167,7 @@ def _system(pos, numbers, tables, cell, a1, a2, list_cutoff, three_body_cutoff, 
         return a1 * torch.sqrt(3.0 * r4r2[za] * r4r2[zb]) + a2
 
     total = torch.zeros((), dtype=f64)
+    triples = 0
     if term == "two_body":
         c6 = c6_interpolate(cn[tli], cn[tlj], z[tli], z[tlj], c6ab, cn_ref, k3)
         q = 3.0 * r4r2[z[tli]] * r4r2[z[tlj]]
@@ -172,6 +199,7 @@ def _system(pos, numbers, tables, cell, a1, a2, list_cutoff, three_body_cutoff, 
         vp = np.concatenate(vp) if vp else np.zeros(0, np.int64)
         vq = np.concatenate(vq) if vq else np.zeros(0, np.int64)
         weight = 1.0 if free else 1.0 / 3.0
+        triples = len(vp) if free else len(vp) // 3  # (periodic: every triple is enumerated from each of its three vertices)
         tti, ttj = torch.as_tensor(ti), torch.as_tensor(tj)
         total_val = 0.0
         for lo in range(0, max(len(vp), 1), chunk):
@@ -205,7 +233,7 @@ def _system(pos, numbers, tables, cell, a1, a2, list_cutoff, three_body_cutoff, 
     if cell is not None:
         virial = -eps.grad.numpy() if eps.grad is not None else np.zeros((3, 3))
         virial = 0.5 * (virial + virial.T)
-    return float(total.detach()), forces, virial, cn64.detach().numpy()
+    return float(total.detach()), forces, virial, cn64.detach().numpy(), triples
 
 
 def _np_vectors(pos, cell, i, j, s):
@@ -218,7 +246,8 @@ def _np_vectors(pos, cell, i, j, s):
 
 def reference(pos, numbers, tables, a1, a2, list_cutoff, three_body_cutoff=None, s9=1.0, alpha=16.0, k1=16.0, k3=-4.0, s6=1.0, s8=0.0,
               cell=None, batch_idx=None, term="atm", work_dtype=torch.float64, chunk=1_000_000):
-    """Returns dict(energy[B], forces[N,3], virial[B,3,3] (periodic only, else None), cn[N]) as float64 numpy arrays.
+    """Returns dict(energy[B], forces[N,3], virial[B,3,3] (periodic only, else None), cn[N]) as float64 numpy arrays, and `triples`: the
+    unordered triples the three-body term summed over (0 for term "two_body").
     `cell`: None, [3,3] or [B,3,3]; `batch_idx`: None or [N] (systems are evaluated one by one)."""
     pos = np.asarray(pos, np.float64)
     numbers = np.asarray(numbers)
@@ -230,16 +259,18 @@ def reference(pos, numbers, tables, a1, a2, list_cutoff, three_body_cutoff=None,
     forces = np.zeros((n, 3))
     cn = np.zeros(n)
     virial = None if cells is None else np.zeros((nsys, 3, 3))
+    triples = 0
     for s in range(nsys):
         sel = np.nonzero(bi == s)[0]
         if len(sel) == 0:
             continue
-        e, f, v, c = _system(pos[sel], numbers[sel], tables, None if cells is None else cells[s], a1, a2, list_cutoff,
-                             three_body_cutoff if three_body_cutoff is not None else list_cutoff, s9, alpha, k1, k3, s6, s8, term, work_dtype,
-                             chunk)
+        e, f, v, c, k = _system(pos[sel], numbers[sel], tables, None if cells is None else cells[s], a1, a2, list_cutoff,
+                                three_body_cutoff if three_body_cutoff is not None else list_cutoff, s9, alpha, k1, k3, s6, s8, term, work_dtype,
+                                chunk)
         energy[s] = e
         forces[sel] = f
         cn[sel] = c
+        triples += k
         if virial is not None:
             virial[s] = v
-    return dict(energy=energy, forces=forces, virial=virial, cn=cn)
+    return dict(energy=energy, forces=forces, virial=virial, cn=cn, triples=triples)

@@ -195,12 +195,14 @@ def _system_atm(pos, numbers, tables, r0ab, cell, rs9, s9, alpha, list_cutoff, t
     if cell is not None:
         virial = -eps.grad.numpy() if eps.grad is not None else np.zeros((3, 3))
         virial = 0.5 * (virial + virial.T)
-    return total_val, forces, virial, cn64.detach().numpy()
+    triples = len(vp) if free else len(vp) // 3
+    return total_val, forces, virial, cn64.detach().numpy(), triples
 
 
 def reference(pos, numbers, tables, r0ab, rs6, s8, list_cutoff, rs8=1.0, alpha=None, beta=0.0, k1=16.0, k3=-4.0, s6=1.0, s5_on=1e10,
               s5_off=1e10, cell=None, batch_idx=None, term="two_body", work_dtype=torch.float64, three_body_cutoff=None, rs9=4.0 / 3.0, s9=1.0):
-    """Returns dict(energy[B], forces[N,3], virial[B,3,3] (periodic only, else None), cn[N]) as float64 numpy arrays.
+    """Returns dict(energy[B], forces[N,3], virial[B,3,3] (periodic only, else None), cn[N]) as float64 numpy arrays, and `triples`: the
+    unordered triples the three-body term enumerated (0 for term "two_body").
     `cell`: None, [3,3] or [B,3,3]; `batch_idx`: None or [N] (systems are evaluated one by one).  `alpha` defaults to 14 for the two-body
     term and to 16 for the three-body term, as in the package; rs6 / s8 / rs8 / beta / s6 / the S5 window are not read for term="atm"."""
     if term not in ("two_body", "atm"):
@@ -217,14 +219,16 @@ def reference(pos, numbers, tables, r0ab, rs6, s8, list_cutoff, rs8=1.0, alpha=N
     forces = np.zeros((n, 3))
     cn = np.zeros(n)
     virial = None if cells is None else np.zeros((nsys, 3, 3))
+    triples = 0
     for s in range(nsys):
         sel = np.nonzero(bi == s)[0]
         if len(sel) == 0:
             continue
         cs = None if cells is None else cells[s]
         if term == "atm":
-            e, f, v, c = _system_atm(pos[sel], numbers[sel], tables, r0ab, cs, rs9, s9, alpha, list_cutoff,
-                                     three_body_cutoff if three_body_cutoff is not None else list_cutoff, k1, k3, work_dtype)
+            e, f, v, c, k = _system_atm(pos[sel], numbers[sel], tables, r0ab, cs, rs9, s9, alpha, list_cutoff,
+                                        three_body_cutoff if three_body_cutoff is not None else list_cutoff, k1, k3, work_dtype)
+            triples += k
         else:
             e, f, v, c = _system(pos[sel], numbers[sel], tables, r0ab, cs, rs6, rs8, s6, s8, alpha, beta, list_cutoff, k1, k3, s5_on, s5_off,
                                  work_dtype)
@@ -233,4 +237,4 @@ def reference(pos, numbers, tables, r0ab, rs6, s8, list_cutoff, rs8=1.0, alpha=N
         cn[sel] = c
         if virial is not None:
             virial[s] = v
-    return dict(energy=energy, forces=forces, virial=virial, cn=cn)
+    return dict(energy=energy, forces=forces, virial=virial, cn=cn, triples=triples)

@@ -39,6 +39,8 @@ ABOVE_RULE = {"cn_cutoff": 10.0}  # the feature request's value, this factor abo
 ZERO = ("molecule1", "molecule2")  # fewer than three atoms: every output is exactly 0
 PARITY = tuple(n for n in RC3 if n not in ZERO)
 NAMES = tuple(RC3)
+# one row of three LDS tiles (`_shell`), judged by a test of its own; s9 by the rule above
+RC3["shell"], S9["shell"] = 20.0, 1.0
 
 
 def dense_atoms():
@@ -59,9 +61,19 @@ def _dense():
     return dict(pos=pos, z=z, tables=K.R.d4_test_tables(17), cell=None, batch_idx=None, rc=rc, kw={})
 
 
+def _shell():
+    """A centre atom and a shell of 2 tiles + 8 atoms at 19 Bohr (`atm_reference.centre_and_shell`): the centre's row stages three tiles,
+    every other row less than one; the list (cutoff 40) holds everybody."""
+    from nvalchemiops.interactions.dispersion.dftd4 import atm_tile
+
+    pos = K.A.centre_and_shell(2 * atm_tile() + 8)
+    z = np.random.default_rng(29).choice(np.array((1, 6, 8), np.int32), len(pos))
+    return dict(pos=pos, z=z, tables=K.R.d4_test_tables(17), cell=None, batch_idx=None, rc=40.0, kw={})
+
+
 @functools.lru_cache(maxsize=None)
 def case(name):
-    c = dict(_dense() if name == "dense" else K.case(name))
+    c = dict(_dense() if name == "dense" else _shell() if name == "shell" else K.case(name))
     c.pop("q", None)  # the three-body term takes no charges
     c["rc3"], c["s9"] = RC3[name], S9[name]
     return c

@@ -19,6 +19,7 @@ CSR agree to the digits shown; the full table with max|ref| is in DESIGN.md sect
   batch of three              E 3.6e-10 | 7.5e-10 | 0.000  F 2.3e-10 | 1.1e-10 | 0.000  V 1.5e-9 | 1.5e-9 | 0.000
   dense row, 343 staged       E 1.5e-7 | 1.4e-8 | 0.001    F 1.5e-8 | 2.1e-8 | 0.004
   renumbered 80-atom box      E 1.5e-10 | 2.8e-9 | 0.001   F 4.7e-10 | 2.5e-10 | 0.000  V 5.0e-9 | 3.3e-9 | 0.001
+  three-tile row, 648 staged  E 1.5e-7 | 3.0e-7 | 0.035    F 7.2e-9 | 5.1e-9 | 0.001
 The float32 deviation never exceeds `dftd3`'s bar on these systems, so every bar is 4 x `dftd3`'s."""
 import numpy as np
 import pytest
@@ -284,6 +285,53 @@ def test_dense_row_needs_more_than_one_lds_tile():
     r64, r32 = _references(pos, z, t, rc, rc)
     _judge(f"dense row ({widest} staged) matrix", dftd3_atm(_t(pos), _t(z), three_body_cutoff=rc, d3_params=_params(t), **BJ, **m), r64, r32)
     _judge(f"dense row ({widest} staged) csr", dftd3_atm(_t(pos), _t(z), three_body_cutoff=rc, d3_params=_params(t), **BJ, **l), r64, r32)
+
+
+def _visits(pos, z, t, lists, rc3, scalars, zero=None):
+    """Per-centre triangle-visit counters of one triple pass on the matrix list (`want_visits`)."""
+    import importlib
+
+    from nvalchemiops import _capi as C
+
+    D3 = importlib.import_module("nvalchemiops.interactions.dispersion.dftd3")  # (the package re-exports a function of the same name)
+    n = len(pos)
+    nm = C.i32(lists["neighbor_matrix"])
+    f32 = dict(dtype=torch.float32, device=DEV)
+    tables = tuple(_t(t[k]) for k in ("rcov", "r4r2", "c6ab", "cn_ref"))
+    return D3._launch_atm(positions=_t(pos), numbers=_t(z), idx=nm, shifts=None, nptr=None, max_neighbors=nm.shape[1], fill_value=n, cell=None,
+                          batch_idx=None, num_systems=1, tables=tables, scalars=scalars, s9=1.0, alpha=16.0, three_body_cutoff=rc3,
+                          compute_virial=False, energy=torch.empty(1, **f32), forces=torch.empty((n, 3), **f32),
+                          virial=torch.zeros((0, 3, 3), **f32), want_visits=True, zero=zero).cpu().numpy()
+
+
+def shell_system():
+    """A centre atom whose row stages THREE tiles (`atm_reference.centre_and_shell` with 2 tiles + 8 shell atoms, three-body cutoff 20, list
+    cutoff 40: everybody is listed) while every other row stages less than one: all six tile pairs of the long row, (1, 2) among them.
+    Returns (pos, z, tile, pairs among the centre's kept entries, triples), the last two counted from numpy distances."""
+    from nvalchemiops.interactions.dispersion.dftd3 import atm_tile
+
+    tile = atm_tile()
+    pos = R.centre_and_shell(2 * tile + 8)
+    kept, pairs0, triples, margin = R.kept_and_triples(pos, 20.0)
+    assert kept[0] > 2 * tile and kept[1:].max() < tile, (kept[0], kept[1:].max(), tile)
+    assert margin > 2e-5, "no pair within float32 rounding (ulp(20) = 1.9e-6, a few per distance) of the cutoff: the counts below are exact"
+    return pos, _zs(len(pos), 29, (1, 6, 8)), tile, pairs0, triples
+
+
+def test_row_of_three_lds_tiles_runs_every_tile_pair_once():
+    from nvalchemiops.interactions.dispersion import dftd3_atm
+    from nvalchemiops.interactions.dispersion.dftd3 import atm_scalars
+
+    pos, z, tile, pairs0, triples = shell_system()
+    t = S.d3_test_tables(17)
+    m, l, widest = _lists(pos, None, 40.0)
+    assert widest == len(pos) - 1
+    r64, r32 = _references(pos, z, t, 40.0, 20.0)
+    assert r64["triples"] == triples
+    _judge("three-tile row matrix", dftd3_atm(_t(pos), _t(z), three_body_cutoff=20.0, d3_params=_params(t), **BJ, **m), r64, r32)
+    _judge("three-tile row csr", dftd3_atm(_t(pos), _t(z), three_body_cutoff=20.0, d3_params=_params(t), **BJ, **l), r64, r32)
+    visits = _visits(pos, z, t, m, 20.0, atm_scalars(BJ["a1"], BJ["a2"], 16.0, -4.0))
+    assert visits[0] == pairs0 and int(visits.sum()) == 3 * r64["triples"], (visits[0], pairs0, int(visits.sum()), 3 * r64["triples"])
 
 
 # ---- invariances ---------------------------------------------------------------------------------------------------------------------

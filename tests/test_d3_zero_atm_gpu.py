@@ -189,6 +189,24 @@ def test_dense_row_needs_more_than_one_lds_tile():
     _judge(f"dense row ({n - 1} staged) csr", dftd3_zero_atm(_t(pos), _t(z), rc, d3_params=_params(t, r0ab), **l), r64, r32)
 
 
+def test_row_of_three_lds_tiles_runs_every_tile_pair_once():
+    """The system of tests/test_d3_atm_gpu.py's test of the same name with the table radii of this file's dense test."""
+    from nvalchemiops.interactions.dispersion import dftd3_zero_atm
+    from nvalchemiops.interactions.dispersion.dftd3 import atm_scalars
+    from tests.test_d3_atm_gpu import _visits, shell_system
+
+    pos, z, tile, pairs0, triples = shell_system()
+    t, r0ab = _tables()
+    m, l = _lists(pos, None, 40.0)
+    assert int((m["neighbor_matrix"] < len(pos)).sum(1).min()) == len(pos) - 1
+    r64, r32 = _references(pos, z, t, r0ab, 40.0, 20.0)
+    _judge("three-tile row matrix", dftd3_zero_atm(_t(pos), _t(z), 20.0, d3_params=_params(t, r0ab), **m), r64, r32)
+    _judge("three-tile row csr", dftd3_zero_atm(_t(pos), _t(z), 20.0, d3_params=_params(t, r0ab), **l), r64, r32)
+    visits = _visits(pos, z, t, m, 20.0, atm_scalars(0.0, 0.0, 16.0, -4.0), zero=(4.0 / 3.0, _t(r0ab)))
+    assert r64["triples"] == triples
+    assert visits[0] == pairs0 and int(visits.sum()) == 3 * r64["triples"], (visits[0], pairs0, int(visits.sum()), 3 * r64["triples"])
+
+
 def test_renumbering_and_dftd3_atm_untouched():
     from nvalchemiops.interactions.dispersion import dftd3_atm, dftd3_zero_atm
 

@@ -285,6 +285,34 @@ def test_visit_counters_of_a_molecule_count_every_triple_three_times():
         assert visits.shape == (n,) and int(visits.sum()) == 3 * r64["triples"] > 0
 
 
+def test_row_of_three_lds_tiles_runs_every_tile_pair_once():
+    """`shell` (tests/d4_atm_cases.py): the centre's row stages three tiles -- all six tile pairs, (1, 2) among them -- every other row less
+    than one.  Both layouts at the module's bars, and the visit counters: the centre's equal the pairs among its kept entries, their sum is
+    3 x the triples the restatement enumerates, so no tile pair is dropped or run twice."""
+    from nvalchemiops import _capi as C
+    from nvalchemiops.interactions.dispersion.dftd4 import atm_tile
+    import importlib
+
+    D4 = importlib.import_module("nvalchemiops.interactions.dispersion.dftd4")
+    c, outs, r64, bars, widest = _both_layouts("shell", max_neighbors=len(K3.case("shell")["pos"]) + 8)
+    n, tile = len(c["pos"]), atm_tile()
+    kept, pairs0, triples, margin = K3.K.A.kept_and_triples(c["pos"], c["rc3"])
+    assert widest == n - 1 and kept[0] > 2 * tile and kept[1:].max() < tile, (widest, kept[0], kept[1:].max(), tile)
+    assert margin > 2e-5, "no pair within float32 rounding (ulp(20) = 1.9e-6, a few per distance) of the cutoff: the counts below are exact"
+    assert r64["triples"] == triples and r64["kept"] == kept[0]
+    _, args, kw, m, _, _ = _inputs("shell", max_neighbors=n + 8)
+    p = kw["d4_params"]
+    tables = tuple(getattr(p, k) for k in K3.K.R.TABLE_KEYS)
+    scalars = D4.d4_scalars(BJ["a1"], BJ["a2"], 0.0, 0.0, 7.5, 6.0, 3.0, 2.0, None)
+    f32 = dict(dtype=torch.float32, device=DEV)
+    nm = C.i32(m["neighbor_matrix"])
+    visits = D4._launch_atm(positions=args[0], numbers=args[1], idx=nm, shifts=None, nptr=None, max_neighbors=nm.shape[1], fill_value=n, cell=None,
+                            batch_idx=None, num_systems=1, tables=tables, scalars=scalars, s9=c["s9"], alpha=16.0, three_body_cutoff=c["rc3"],
+                            compute_virial=False, energy=torch.empty(1, **f32), forces=torch.empty((n, 3), **f32),
+                            virial=torch.zeros((0, 3, 3), **f32), want_visits=True).cpu().numpy()
+    assert visits[0] == pairs0 and int(visits.sum()) == 3 * r64["triples"], (visits[0], pairs0, int(visits.sum()), 3 * r64["triples"])
+
+
 # ---- autograd -------------------------------------------------------------------------------------------------------------------------------
 
 def test_backward_gives_minus_forces_and_differentiating_twice_raises():

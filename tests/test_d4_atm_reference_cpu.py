@@ -170,3 +170,21 @@ def test_cases_hold_one_and_seven_reference_elements_and_a_row_longer_than_a_til
     assert len(d["pos"]) == tile + 24 and kept.max() == r64["kept"] > tile, (kept.max(), tile)
     assert kept.min() < tile, "rows of one tile and rows of two tiles in the same call"
     assert (d["z"] == R.ONE_REF_Z).any() and (d["z"] == R.SEVEN_REF_Z).any()
+
+
+def test_shell_case_holds_one_row_of_three_tiles_and_its_s9_follows_the_rule():
+    """`shell` is judged by a GPU test of its own (it is not in PARITY); its conditions, as for `dense`.  The restatement of this system
+    (585 atoms at a tile of 288, 1.6e6 triples) takes 5.6 s for float64 + float32 together on 16 CPU threads, so both are used."""
+    from nvalchemiops.interactions.dispersion.dftd4 import atm_tile
+
+    d = K3.case("shell")
+    r64, r32 = K3.unit_references("shell")
+    tile = atm_tile()
+    kept, pairs0, triples, margin = A.kept_and_triples(d["pos"], d["rc3"])
+    assert len(d["pos"]) == 2 * tile + 9 and kept[0] == r64["kept"] > 2 * tile and kept[1:].max() < tile, (kept[0], kept[1:].max(), tile)
+    assert r64["triples"] == triples and pairs0 > 0
+    assert margin > 2e-5, "no pair within float32 rounding of the cutoff (ulp(20) = 1.9e-6, a few per distance)"
+    assert d["s9"] == K3.smallest_s9("shell") and K3.lifted(r64, d["s9"])
+    for k in ("energy", "forces"):
+        assert (np.abs(r32[k] - r64[k]) <= K3.d3_bar(r64[k], k)).all(), k
+    assert (d["z"] == R.ONE_REF_Z).any() and (d["z"] == R.SEVEN_REF_Z).any()

@@ -1,4 +1,4 @@
-"""VGPRs / spills / occupancy of every kernel in one csrc/*.hip file, from hipcc's -Rpass-analysis=kernel-resource-usage remarks
+"""VGPRs / SGPRs / spills / scratch / occupancy of every kernel in one csrc/*.hip file, from hipcc's -Rpass-analysis=kernel-resource-usage remarks
 (cross-compiles for gfx950, no GPU needed).  Usage: python tools/kernel_resources.py nvalchemi-toolkit-ops_amd/csrc/d3.hip [name-filter]"""
 import os
 import re
@@ -34,4 +34,5 @@ for r_ in rows:
     if flt in r_["name"]:
         short = re.sub(r"^_ZN12_GLOBAL__N_1\d+", "", r_["name"])[:70]
         print(f"{short:70s} VGPR {r_.get('VGPRs'):>4s} AGPR {r_.get('AGPRs', '-'):>3s} spill {r_.get('VGPRs Spill'):>3s} "
+              f"SGPR {r_.get('TotalSGPRs', r_.get('SGPRs', '-')):>4s} spill {r_.get('SGPRs Spill', '-'):>3s} scratch {r_.get('ScratchSize [bytes/lane]', '-'):>3s} "
               f"LDS {r_.get('LDS Size [bytes/block]', '-'):>6s} occ {r_.get('Occupancy [waves/SIMD]')}")
