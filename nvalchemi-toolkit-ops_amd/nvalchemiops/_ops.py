@@ -42,6 +42,7 @@ from nvalchemiops.neighborlist import rebuild_detection as _rd
 
 _d3 = importlib.import_module("nvalchemiops.interactions.dispersion.dftd3")
 _d4 = importlib.import_module("nvalchemiops.interactions.dispersion.dftd4")
+_disp = importlib.import_module("nvalchemiops.interactions.dispersion._call")
 _bcl = importlib.import_module("nvalchemiops.neighborlist.batch_cell_list")
 _cl = importlib.import_module("nvalchemiops.neighborlist.cell_list")
 
@@ -94,10 +95,6 @@ def _device_of(t: torch.Tensor):
     return torch.cuda.device(t.device)
 
 
-def _d3_scalars(a1, a2, s6, s8, k1, k3, on, off):
-    return dict(a1=a1, a2=a2, s6=s6, s8=s8, k1=k1, k3=k3, s5_on=on, s5_off=off)
-
-
 @torch.library.custom_op("nvalchemiops::dftd3_nm", mutates_args=("energy", "forces", "coord_num", "virial"))
 def _dftd3_nm_op(positions: torch.Tensor, numbers: torch.Tensor, neighbor_matrix: torch.Tensor, covalent_radii: torch.Tensor,
                  r4r2: torch.Tensor, c6_reference: torch.Tensor, coord_num_ref: torch.Tensor, a1: float, a2: float, s8: float,
@@ -109,11 +106,10 @@ def _dftd3_nm_op(positions: torch.Tensor, numbers: torch.Tensor, neighbor_matrix
     if n == 0:
         return
     C.require_device(positions, numbers, neighbor_matrix, batch_idx, energy, forces, coord_num)
-    nm = C.i32(neighbor_matrix)
     with _device_of(positions):
-        _d3._launch(positions, numbers, nm, neighbor_matrix_shifts, None, nm.shape[1], n if fill_value is None else fill_value, cell, batch_idx,
+        _d3._launch(positions, numbers, *_disp.list_args(n, neighbor_matrix, neighbor_matrix_shifts, fill_value), cell, batch_idx,
                     energy.shape[0], (covalent_radii, r4r2, c6_reference, coord_num_ref),
-                    _d3_scalars(a1, a2, s6, s8, k1, k3, s5_smoothing_on, s5_smoothing_off), compute_virial, energy, forces, coord_num, virial)
+                    _d3.d3_scalars(a1, a2, s6, s8, k1, k3, s5_smoothing_on, s5_smoothing_off), compute_virial, energy, forces, coord_num, virial)
 
 
 @torch.library.custom_op("nvalchemiops::dftd3_nl", mutates_args=("energy", "forces", "coord_num", "virial"))
@@ -127,8 +123,9 @@ def _dftd3_nl_op(positions: torch.Tensor, numbers: torch.Tensor, idx_j: torch.Te
         return
     C.require_device(positions, numbers, idx_j, neighbor_ptr, batch_idx, energy, forces, coord_num)
     with _device_of(positions):
-        _d3._launch(positions, numbers, C.i32(idx_j), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, energy.shape[0],
-                    (covalent_radii, r4r2, c6_reference, coord_num_ref), _d3_scalars(a1, a2, s6, s8, k1, k3, s5_smoothing_on, s5_smoothing_off),
+        _d3._launch(positions, numbers, *_disp.list_args(0, idx_j=idx_j, neighbor_ptr=neighbor_ptr, unit_shifts=unit_shifts), cell,
+                    batch_idx, energy.shape[0], (covalent_radii, r4r2, c6_reference, coord_num_ref),
+                    _d3.d3_scalars(a1, a2, s6, s8, k1, k3, s5_smoothing_on, s5_smoothing_off),
                     compute_virial, energy, forces, coord_num, virial)
 
 
@@ -145,9 +142,8 @@ def _dftd3_zero_nm_op(positions: torch.Tensor, numbers: torch.Tensor, neighbor_m
     if n == 0:
         return
     C.require_device(positions, numbers, neighbor_matrix, batch_idx, energy, forces, coord_num)
-    nm = C.i32(neighbor_matrix)
     with _device_of(positions):
-        _d3._launch(positions, numbers, nm, neighbor_matrix_shifts, None, nm.shape[1], n if fill_value is None else fill_value, cell, batch_idx,
+        _d3._launch(positions, numbers, *_disp.list_args(n, neighbor_matrix, neighbor_matrix_shifts, fill_value), cell, batch_idx,
                     energy.shape[0], (covalent_radii, r4r2, c6_reference, coord_num_ref),
                     _d3.zero_scalars(s6, s8, k1, k3, s5_smoothing_on, s5_smoothing_off), compute_virial, energy, forces, coord_num, virial,
                     zero=(rs6, rs8, alpha, beta, cutoff_radii))
@@ -166,8 +162,9 @@ def _dftd3_zero_nl_op(positions: torch.Tensor, numbers: torch.Tensor, idx_j: tor
         return
     C.require_device(positions, numbers, idx_j, neighbor_ptr, batch_idx, energy, forces, coord_num)
     with _device_of(positions):
-        _d3._launch(positions, numbers, C.i32(idx_j), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, energy.shape[0],
-                    (covalent_radii, r4r2, c6_reference, coord_num_ref), _d3.zero_scalars(s6, s8, k1, k3, s5_smoothing_on, s5_smoothing_off),
+        _d3._launch(positions, numbers, *_disp.list_args(0, idx_j=idx_j, neighbor_ptr=neighbor_ptr, unit_shifts=unit_shifts), cell,
+                    batch_idx, energy.shape[0], (covalent_radii, r4r2, c6_reference, coord_num_ref),
+                    _d3.zero_scalars(s6, s8, k1, k3, s5_smoothing_on, s5_smoothing_off),
                     compute_virial, energy, forces, coord_num, virial, zero=(rs6, rs8, alpha, beta, cutoff_radii))
 
 
@@ -183,10 +180,9 @@ def _dftd3_atm_nm_op(positions: torch.Tensor, numbers: torch.Tensor, neighbor_ma
     if n == 0:
         return
     C.require_device(positions, numbers, neighbor_matrix, batch_idx, energy, forces)
-    nm = C.i32(neighbor_matrix)
     with _device_of(positions):
-        _d3._launch_atm(positions, numbers, nm, neighbor_matrix_shifts, None, nm.shape[1], n if fill_value is None else fill_value, cell,
-                        batch_idx, energy.shape[0], (covalent_radii, r4r2, c6_reference, coord_num_ref), _d3.atm_scalars(a1, a2, k1, k3), s9,
+        _d3._launch_atm(positions, numbers, *_disp.list_args(n, neighbor_matrix, neighbor_matrix_shifts, fill_value), cell, batch_idx,
+                        energy.shape[0], (covalent_radii, r4r2, c6_reference, coord_num_ref), _d3.atm_scalars(a1, a2, k1, k3), s9,
                         alpha, three_body_cutoff, compute_virial, energy, forces, virial)
 
 
@@ -201,8 +197,9 @@ def _dftd3_atm_nl_op(positions: torch.Tensor, numbers: torch.Tensor, idx_j: torc
         return
     C.require_device(positions, numbers, idx_j, neighbor_ptr, batch_idx, energy, forces)
     with _device_of(positions):
-        _d3._launch_atm(positions, numbers, C.i32(idx_j), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, energy.shape[0],
-                        (covalent_radii, r4r2, c6_reference, coord_num_ref), _d3.atm_scalars(a1, a2, k1, k3), s9, alpha, three_body_cutoff,
+        _d3._launch_atm(positions, numbers, *_disp.list_args(0, idx_j=idx_j, neighbor_ptr=neighbor_ptr, unit_shifts=unit_shifts), cell,
+                        batch_idx, energy.shape[0], (covalent_radii, r4r2, c6_reference, coord_num_ref),
+                        _d3.atm_scalars(a1, a2, k1, k3), s9, alpha, three_body_cutoff,
                         compute_virial, energy, forces, virial)
 
 
@@ -218,10 +215,9 @@ def _dftd3_zero_atm_nm_op(positions: torch.Tensor, numbers: torch.Tensor, neighb
     if n == 0:
         return
     C.require_device(positions, numbers, neighbor_matrix, batch_idx, energy, forces)
-    nm = C.i32(neighbor_matrix)
     with _device_of(positions):
-        _d3._launch_atm(positions, numbers, nm, neighbor_matrix_shifts, None, nm.shape[1], n if fill_value is None else fill_value, cell,
-                        batch_idx, energy.shape[0], (covalent_radii, r4r2, c6_reference, coord_num_ref), _d3.atm_scalars(0.0, 0.0, k1, k3), s9,
+        _d3._launch_atm(positions, numbers, *_disp.list_args(n, neighbor_matrix, neighbor_matrix_shifts, fill_value), cell, batch_idx,
+                        energy.shape[0], (covalent_radii, r4r2, c6_reference, coord_num_ref), _d3.atm_scalars(0.0, 0.0, k1, k3), s9,
                         alpha, three_body_cutoff, compute_virial, energy, forces, virial, zero=(rs9, cutoff_radii))
 
 
@@ -237,8 +233,9 @@ def _dftd3_zero_atm_nl_op(positions: torch.Tensor, numbers: torch.Tensor, idx_j:
         return
     C.require_device(positions, numbers, idx_j, neighbor_ptr, batch_idx, energy, forces)
     with _device_of(positions):
-        _d3._launch_atm(positions, numbers, C.i32(idx_j), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, energy.shape[0],
-                        (covalent_radii, r4r2, c6_reference, coord_num_ref), _d3.atm_scalars(0.0, 0.0, k1, k3), s9, alpha, three_body_cutoff,
+        _d3._launch_atm(positions, numbers, *_disp.list_args(0, idx_j=idx_j, neighbor_ptr=neighbor_ptr, unit_shifts=unit_shifts), cell,
+                        batch_idx, energy.shape[0], (covalent_radii, r4r2, c6_reference, coord_num_ref),
+                        _d3.atm_scalars(0.0, 0.0, k1, k3), s9, alpha, three_body_cutoff,
                         compute_virial, energy, forces, virial, zero=(rs9, cutoff_radii))
 
 
@@ -255,10 +252,9 @@ def _dftd4_nm_op(positions: torch.Tensor, numbers: torch.Tensor, charges: torch.
     if n == 0:
         return
     C.require_device(positions, numbers, charges, neighbor_matrix, batch_idx, energy, forces, coord_num, charge_grad)
-    nm = C.i32(neighbor_matrix)
     with _device_of(positions):
-        _d4._launch(positions, numbers, charges, nm, neighbor_matrix_shifts, None, nm.shape[1], n if fill_value is None else fill_value, cell,
-                    batch_idx, energy.shape[0], (rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref),
+        _d4._launch(positions, numbers, charges, *_disp.list_args(n, neighbor_matrix, neighbor_matrix_shifts, fill_value), cell, batch_idx,
+                    energy.shape[0], (rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref),
                     _d4.d4_scalars(a1, a2, s6, s8, k_cn, wf, ga, gc, cn_cutoff), compute_virial, energy, forces, coord_num, charge_grad, virial)
 
 
@@ -275,8 +271,9 @@ def _dftd4_nl_op(positions: torch.Tensor, numbers: torch.Tensor, charges: torch.
         return
     C.require_device(positions, numbers, charges, idx_j, neighbor_ptr, batch_idx, energy, forces, coord_num, charge_grad)
     with _device_of(positions):
-        _d4._launch(positions, numbers, charges, C.i32(idx_j), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, energy.shape[0],
-                    (rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref), _d4.d4_scalars(a1, a2, s6, s8, k_cn, wf, ga, gc, cn_cutoff),
+        _d4._launch(positions, numbers, charges, *_disp.list_args(0, idx_j=idx_j, neighbor_ptr=neighbor_ptr, unit_shifts=unit_shifts), cell,
+                    batch_idx, energy.shape[0], (rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref),
+                    _d4.d4_scalars(a1, a2, s6, s8, k_cn, wf, ga, gc, cn_cutoff),
                     compute_virial, energy, forces, coord_num, charge_grad, virial)
 
 
@@ -296,10 +293,9 @@ def _dftd4_atm_nm_op(positions: torch.Tensor, numbers: torch.Tensor, neighbor_ma
     if n == 0:
         return
     C.require_device(positions, numbers, neighbor_matrix, batch_idx, energy, forces)
-    nm = C.i32(neighbor_matrix)
     with _device_of(positions):
-        _d4._launch_atm(positions, numbers, nm, neighbor_matrix_shifts, None, nm.shape[1], n if fill_value is None else fill_value, cell,
-                        batch_idx, energy.shape[0], (rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref),
+        _d4._launch_atm(positions, numbers, *_disp.list_args(n, neighbor_matrix, neighbor_matrix_shifts, fill_value), cell, batch_idx,
+                        energy.shape[0], (rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref),
                         _d4.d4_scalars(a1, a2, 0.0, 0.0, k_cn, wf, ga, gc, cn_cutoff), s9, alpha, three_body_cutoff, compute_virial, energy,
                         forces, virial)
 
@@ -317,8 +313,8 @@ def _dftd4_atm_nl_op(positions: torch.Tensor, numbers: torch.Tensor, idx_j: torc
         return
     C.require_device(positions, numbers, idx_j, neighbor_ptr, batch_idx, energy, forces)
     with _device_of(positions):
-        _d4._launch_atm(positions, numbers, C.i32(idx_j), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, energy.shape[0],
-                        (rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref),
+        _d4._launch_atm(positions, numbers, *_disp.list_args(0, idx_j=idx_j, neighbor_ptr=neighbor_ptr, unit_shifts=unit_shifts), cell,
+                        batch_idx, energy.shape[0], (rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref),
                         _d4.d4_scalars(a1, a2, 0.0, 0.0, k_cn, wf, ga, gc, cn_cutoff), s9, alpha, three_body_cutoff, compute_virial, energy,
                         forces, virial)
 

@@ -24,8 +24,9 @@ from dataclasses import dataclass
 import torch
 
 from nvalchemiops import _capi as C
+from nvalchemiops.interactions.dispersion import _call as K
 
-_FLOAT_TYPES = (torch.float32, torch.float64)
+_FLOAT_TYPES = K.FLOAT_TYPES
 
 
 @dataclass
@@ -87,25 +88,15 @@ def _launch(positions, numbers, idx, shifts, nptr, max_neighbors, fill_value, ce
     search also summed the coordination numbers), already validated by the caller against tensor identity / versions; the passes then stream
     4 B/slot (`mi_d3_packed_cn`), the CN pass is skipped when the device-side fingerprint check lets the search's numbers in, and every call
     re-derives a rotating sample of the companion's rows from (idx, shifts) on the device before trusting it."""
-    dev = positions.device
     n = positions.shape[0]
-    pos = positions.detach().contiguous()
-    code = C.dtype_code(pos.dtype)
-    f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731  (dftd3.py:1912-1915)
-    rcov, r4r2, c6ab, cnref = (f32(t) for t in tables)
-    if c6ab.shape[-1] != 5 or c6ab.shape[-2] != 5:
-        raise ValueError("this build supports the standard 5x5 CN interpolation mesh only")
-    par = C.MiD3Params(rcov=rcov.data_ptr(), r4r2=r4r2.data_ptr(), c6ab=c6ab.data_ptr(), cn_ref=cnref.data_ptr(), nz=rcov.shape[0],
-                       **{k: float(v) for k, v in scalars.items()})
+    pos, code, z, cell_t, sh, bi = K.prelude(positions, numbers, shifts, cell, batch_idx)
+    par, keep = K.d3_struct(pos.device, tables, scalars)
     zargs, tag = (), ""
     if zero is not None:
-        r0ab = f32(zero[4])  # stays referenced until the launch is enqueued, like the other tables
+        r0ab = K.f32_on(zero[4], pos.device)  # stays referenced until the launch is enqueued, like the other tables
         zpar = C.MiD3ZeroParams(rs6=float(zero[0]), rs8=float(zero[1]), alpha=float(zero[2]), beta=float(zero[3]), r0ab=r0ab.data_ptr())
         zargs, tag = (ctypes.byref(zpar),), "_zero"
-    periodic = cell is not None and shifts is not None
-    cell_t = cell.detach().to(dtype=pos.dtype, device=dev).reshape(-1, 3, 3).contiguous() if periodic else None
-    sh = C.i32(shifts.to(dev)) if periodic else None
-    bi = None if batch_idx is None else C.i32(batch_idx)
+    periodic = sh is not None
     # a periodic padded matrix is streamed by all three passes: the larger workspace lets the CN pass leave a 4 B/slot copy for the others
     # NVALCHEMIOPS_D3_PACKED_LIST: "1" (default) padded matrix only; "0" never (A/B on one box); "2" also CSR lists -- measured neutral
     # there (unaligned rows make the CN pass's extra write cost what the other two passes gain), so it is not the default
@@ -115,10 +106,9 @@ def _launch(positions, numbers, idx, shifts, nptr, max_neighbors, fill_value, ce
     L = _LIB_OVERRIDE or C.lib()
     if zero is not None and not hasattr(L, "mi_d3_zero"):
         raise C.NativeLibraryError("libnvalchemiops_hip.so does not export mi_d3_zero: rebuild it (build_native.py)")
-    ws_bytes = int(C.lib().mi_d3_workspace_bytes_entries(n, num_systems, rcov.shape[0], int(n_entries)))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws_bytes = int(C.lib().mi_d3_workspace_bytes_entries(n, num_systems, par.nz, int(n_entries)))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos.device)
     vir = virial if compute_virial else None
-    z = C.i32(numbers)  # converted tensors stay referenced until the launch is enqueued (the allocator may otherwise reuse their blocks)
     if packed is not None and periodic and nptr is None and mode != "0":
         from nvalchemiops.neighborlist import _engine as E
 
@@ -144,91 +134,37 @@ def _launch(positions, numbers, idx, shifts, nptr, max_neighbors, fill_value, ce
     C.check(rc, f"mi_d3{tag}")
 
 
-_NO_RADII = object()  # `_check_and_resolve(cutoff_radii=...)`: the caller has no use for a table of pair cutoff radii
+_NO_RADII = object()  # `_check_d3(cutoff_radii=...)`: the caller has no use for a table of pair cutoff radii
 
 
-def _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial, missing_functional,
-                       d3_params, covalent_radii, r4r2, c6_reference, coord_num_ref, atoms, cutoff_radii=_NO_RADII):
-    """Argument validation and parameter resolution shared by `dftd3`, `dftd3_zero` and `dftd3_atm` (dftd3.py:2668-2757): the same checks in
-    the same order with the same messages.  `missing_functional`: the message to raise when a required functional parameter is None, or None.
-    Returns (use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref)).
-    `cutoff_radii` given (a tensor or None; zero damping): the pair cutoff radii r0ab[Z+1, Z+1] are resolved as well -- explicit tensor, else
-    key "r0ab" of a `d3_params` dict (`D3Parameters` does not carry them) -- and checked against rcov's length; they are appended to the
-    returned tuple of tables.
-    `atoms` = (positions, numbers, batch_idx, num_systems) of the call: neighbour data, per-atom tensors and cells are checked against
-    the number of atoms and systems, and the tables against rcov's length (`_capi.check_neighbor_data`; host-side shape reads, before the
-    device check and before any launch -- the kernels see bare pointers and these integers)."""
-    use_matrix, use_list = neighbor_matrix is not None, neighbor_list is not None
-    if use_matrix and use_list:
-        raise ValueError("Cannot provide both neighbor_matrix and neighbor_list. Please provide only one neighbor representation format.")
-    if not use_matrix and not use_list:
-        raise ValueError("Must provide either neighbor_matrix or neighbor_list.")
-    if use_matrix and unit_shifts is not None:
-        raise ValueError("unit_shifts is for neighbor_list format. Use neighbor_matrix_shifts for neighbor_matrix format.")
-    if use_list and neighbor_matrix_shifts is not None:
-        raise ValueError("neighbor_matrix_shifts is for neighbor_matrix format. Use unit_shifts for neighbor_list format.")
-    if use_list and neighbor_ptr is None:
-        raise ValueError("neighbor_ptr must be provided when using neighbor_list format. "
-                         "Obtain it from the neighbor list API by setting return_neighbor_list=True.")
-    if missing_functional:
-        raise ValueError(missing_functional)
-    if compute_virial:
-        need = "Virial computation requires periodic boundary conditions. "
-        if cell is None:
-            raise ValueError(need + "Please provide unit cell parameters (cell) and shifts (neighbor_matrix_shifts or unit_shifts) "
-                             "when compute_virial=True or when passing a virial tensor.")
-        if use_matrix and neighbor_matrix_shifts is None:
-            raise ValueError(need + "Please provide neighbor_matrix_shifts along with cell when using neighbor_matrix format "
-                             "and compute_virial=True or passing a virial tensor.")
-        if use_list and unit_shifts is None:
-            raise ValueError(need + "Please provide unit_shifts along with cell when using neighbor_list format "
-                             "and compute_virial=True or passing a virial tensor.")
-    # explicit tensors win over d3_params entries (dftd3.py:2727-2757)
-    explicit = (covalent_radii, r4r2, c6_reference, coord_num_ref)
-    if any(t is None for t in explicit):
-        if d3_params is None:
-            raise RuntimeError("DFT-D3 parameters must be explicitly provided. Either supply all individual parameters "
-                               "(covalent_radii, r4r2, c6_reference, coord_num_ref), provide a D3Parameters instance, "
-                               "or provide a d3_params dictionary. See the function docstring for details.")
-        if isinstance(d3_params, D3Parameters):
-            src = {"rcov": d3_params.rcov, "r4r2": d3_params.r4r2, "c6ab": d3_params.c6ab, "cn_ref": d3_params.cn_ref}
-        else:
-            src = d3_params
-        covalent_radii = src["rcov"] if covalent_radii is None else covalent_radii
-        r4r2 = src["r4r2"] if r4r2 is None else r4r2
-        c6_reference = src["c6ab"] if c6_reference is None else c6_reference
-        coord_num_ref = src["cn_ref"] if coord_num_ref is None else coord_num_ref
-
-    positions, numbers, batch_idx, num_systems = atoms
-    nz = covalent_radii.size(0)
-    if tuple(r4r2.shape) != (nz,):
-        raise ValueError(f"r4r2 must have shape [{nz}] to match rcov, got {tuple(r4r2.shape)}")
-    if c6_reference.dim() != 4 or tuple(c6_reference.shape[:2]) != (nz, nz):
-        raise ValueError(f"c6ab must have shape {(nz, nz, 5, 5)}, got {tuple(c6_reference.shape)}")
-    if tuple(coord_num_ref.shape) != tuple(c6_reference.shape):
-        raise ValueError(f"cn_ref must have shape {tuple(c6_reference.shape)}, got {tuple(coord_num_ref.shape)}")
-    shifts = neighbor_matrix_shifts if use_matrix else unit_shifts
-    if num_systems is None and batch_idx is None:
-        num_systems = 1
-    if positions.size(0) > 0:  # (no atoms: nothing is launched, and the reference's empty-input contract reads batch_idx on its own)
-        C.check_neighbor_data(positions.size(0), neighbor_matrix=neighbor_matrix, neighbor_matrix_shifts=neighbor_matrix_shifts,
-                              neighbor_list=neighbor_list, neighbor_ptr=neighbor_ptr, neighbor_shifts=unit_shifts, shifts_name="unit_shifts",
-                              cell=cell if shifts is not None else None, num_systems=num_systems, numbers=numbers, batch_idx=batch_idx)
+def _check_d3(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial, missing_functional,
+              d3_params, covalent_radii, r4r2, c6_reference, coord_num_ref, positions, numbers, batch_idx, num_systems, cutoff_radii=_NO_RADII):
+    """Argument validation and parameter resolution of the four D3 operators (dftd3.py:2668-2757): the same checks in the same order with
+    the same messages -- list format, tables, per-atom / neighbour data and, with `cutoff_radii` given (a tensor or None; zero damping),
+    the pair cutoff radii.  Returns (use_matrix, (rcov, r4r2, c6ab, cn_ref)[, cutoff_radii])."""
+    use_matrix = K.check_lists(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial,
+                               missing_functional)
+    tables = K.d3_tables(d3_params, covalent_radii, r4r2, c6_reference, coord_num_ref)
+    K.check_atoms(positions, numbers, batch_idx, num_systems, neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts,
+                  cell)
     if cutoff_radii is _NO_RADII:
-        return use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref)
-    if cutoff_radii is None and isinstance(d3_params, dict):
-        cutoff_radii = d3_params.get("r0ab")
-    if cutoff_radii is None:
-        raise RuntimeError("DFT-D3 zero-damping pair cutoff radii must be explicitly provided. Either supply cutoff_radii (r0ab[max_Z+1, max_Z+1], "
-                           'in Bohr) or provide a d3_params dictionary with the key "r0ab"; a D3Parameters instance does not carry them.')
-    if not isinstance(cutoff_radii, torch.Tensor):
-        raise TypeError(f"Parameter 'cutoff_radii' must be a torch.Tensor, got {type(cutoff_radii)}")
-    if cutoff_radii.dtype not in _FLOAT_TYPES:
-        raise TypeError(f"Parameter 'cutoff_radii' must be float32 or float64, got {cutoff_radii.dtype}")
-    nz = covalent_radii.size(0)
-    if tuple(cutoff_radii.shape) != (nz, nz):
-        raise ValueError(f"cutoff_radii must have shape [{nz}, {nz}] to match rcov, got {tuple(cutoff_radii.shape)}")
-    return use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref, cutoff_radii)
+        return use_matrix, tables
+    return use_matrix, tables, K.d3_cutoff_radii(d3_params, cutoff_radii, tables[0].size(0))
+
+
+def _two_body(positions, numbers, lists, neighbor_matrix, cell, batch_idx, num_systems, tables, scalars, k1, compute_virial, out,
+              zero=None) -> None:
+    """The eager launch of `dftd3` / `dftd3_zero` on `lists` = `K.list_args(...)`, with what a neighbour search of this package left next to
+    its matrix: the companion and the search-side coordination numbers know nothing about the damping."""
+    idx, shifts, fill = lists[0], lists[1], lists[4]
+    packed = None
+    if idx is neighbor_matrix and cell is not None and shifts is not None and int(fill) >= positions.size(0):
+        from nvalchemiops.neighborlist import _engine as E
+
+        # valid only while matrix and shifts are provably what the search wrote (tensor identity + version counters); else None
+        packed = E.packed_companion(idx, shifts, fill)
+        E.learn_dftd3_context(idx, numbers, tables[0], k1)  # "auto" policy: the next search into this buffer also sums the CNs
+    _launch(positions, numbers, *lists, cell, batch_idx, num_systems, tables, scalars, compute_virial, *out, packed=packed, zero=zero)
 
 
 @C.hybrid
@@ -247,27 +183,13 @@ def dftd3(positions: torch.Tensor, numbers: torch.Tensor, a1: float, a2: float, 
     if a1 is None or a2 is None or s8 is None:
         missing = ("Functional parameters a1, a2, and s8 must be provided. "
                    "These are functional-dependent parameters required for DFT-D3(BJ) calculations.")
-    use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref) = _check_and_resolve(
+    use_matrix, (covalent_radii, r4r2, c6_reference, coord_num_ref) = _check_d3(
         neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial, missing, d3_params, covalent_radii,
-        r4r2, c6_reference, coord_num_ref, (positions, numbers, batch_idx, num_systems))
-
-    n, dev = positions.size(0), positions.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    if n == 0:
-        nsys = 1 if (batch_idx is None or batch_idx.numel() == 0) else int(batch_idx.max().item()) + 1
-        out = (torch.zeros(nsys, **f32), torch.zeros((0, 3), **f32), torch.zeros((0,), **f32))
-        return out + (torch.zeros((0, 3, 3), **f32),) if compute_virial else out
-    if num_systems is None:
-        if batch_idx is None:
-            num_systems = 1
-        elif cell is not None:
-            num_systems = cell.size(0)
-        else:
-            num_systems = int(batch_idx.max().item()) + 1
-    energy = torch.empty(num_systems, **f32)  # zeroed inside mi_d3
-    forces = torch.empty((n, 3), **f32)
-    coord_num = torch.empty(n, **f32)
-    virial = torch.empty((num_systems, 3, 3), **f32) if compute_virial else torch.zeros((0, 3, 3), **f32)
+        r4r2, c6_reference, coord_num_ref, positions, numbers, batch_idx, num_systems)
+    if positions.size(0) == 0:
+        return K.empty_result(positions, batch_idx, 1, compute_virial)
+    num_systems = K.infer_num_systems(num_systems, batch_idx, cell)
+    out = energy, forces, coord_num, virial = K.allocate(positions, num_systems, 1, compute_virial)
     if C.tracing():
         # torch.compile: the reference's own seam -- one mutating custom op per call (dftd3.py:1792-1796 / :2125-2128, called from
         # :2806-2870); the conversions the eager path does below happen inside the op
@@ -279,27 +201,12 @@ def dftd3(positions: torch.Tensor, numbers: torch.Tensor, a1: float, a2: float, 
             torch.ops.nvalchemiops.dftd3_nl(positions, numbers, neighbor_list[1], neighbor_ptr, covalent_radii, r4r2, c6_reference,
                                             coord_num_ref, a1, a2, s8, energy, forces, coord_num, virial, k1, k3, s6, s5_smoothing_on,
                                             s5_smoothing_off, batch_idx, cell, unit_shifts, compute_virial, None)
-        return (energy, forces, coord_num, virial) if compute_virial else (energy, forces, coord_num)
-    C.require_device(positions, numbers, neighbor_matrix, neighbor_list, neighbor_ptr, batch_idx)
-    scalars = dict(a1=a1, a2=a2, s6=s6, s8=s8, k1=k1, k3=k3, s5_on=s5_smoothing_on, s5_off=s5_smoothing_off)
-    tables = (covalent_radii, r4r2, c6_reference, coord_num_ref)
-    if use_matrix:
-        nm = C.i32(neighbor_matrix)
-        fill = n if fill_value is None else fill_value
-        packed = None
-        if nm is neighbor_matrix and cell is not None and neighbor_matrix_shifts is not None and int(fill) >= n:
-            from nvalchemiops.neighborlist import _engine as E
-
-            # valid only while matrix and shifts are provably what the search wrote (tensor identity + version counters); else None
-            packed = E.packed_companion(nm, neighbor_matrix_shifts, fill)
-            E.learn_dftd3_context(nm, numbers, covalent_radii, k1)  # "auto" policy: the next search into this buffer also sums the CNs
-        _launch(positions, numbers, nm, neighbor_matrix_shifts, None, nm.size(1), fill, cell,
-                batch_idx, num_systems, tables, scalars, compute_virial, energy, forces, coord_num, virial, packed=packed)
     else:
-        idx_j = C.i32(neighbor_list[1])
-        _launch(positions, numbers, idx_j, unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, num_systems, tables, scalars,
-                compute_virial, energy, forces, coord_num, virial)
-    return (energy, forces, coord_num, virial) if compute_virial else (energy, forces, coord_num)
+        C.require_device(positions, numbers, neighbor_matrix, neighbor_list, neighbor_ptr, batch_idx)
+        lists = K.list_args(positions.size(0), neighbor_matrix, neighbor_matrix_shifts, fill_value, neighbor_list, neighbor_ptr, unit_shifts)
+        _two_body(positions, numbers, lists, neighbor_matrix, cell, batch_idx, num_systems, (covalent_radii, r4r2, c6_reference, coord_num_ref),
+                  d3_scalars(a1, a2, s6, s8, k1, k3, s5_smoothing_on, s5_smoothing_off), k1, compute_virial, out)
+    return K.select(out, compute_virial)
 
 
 @C.hybrid
@@ -332,28 +239,15 @@ def dftd3_zero(positions: torch.Tensor, numbers: torch.Tensor, rs6: float, s8: f
         missing = f"alpha must be positive, got {alpha}"
     elif not (rs6 > 0 and rs8 > 0):
         missing = f"rs6 and rs8 must be positive, got rs6={rs6}, rs8={rs8}"
-    use_matrix, use_list, (covalent_radii, r4r2, c6_reference, coord_num_ref, cutoff_radii) = _check_and_resolve(
+    use_matrix, (covalent_radii, r4r2, c6_reference, coord_num_ref), cutoff_radii = _check_d3(
         neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial, missing, d3_params, covalent_radii,
-        r4r2, c6_reference, coord_num_ref, (positions, numbers, batch_idx, num_systems), cutoff_radii=cutoff_radii)
-
-    n, dev = positions.size(0), positions.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    if n == 0:
-        nsys = 1 if (batch_idx is None or batch_idx.numel() == 0) else int(batch_idx.max().item()) + 1
-        out = (torch.zeros(nsys, **f32), torch.zeros((0, 3), **f32), torch.zeros((0,), **f32))
-        return out + (torch.zeros((0, 3, 3), **f32),) if compute_virial else out
-    if num_systems is None:
-        if batch_idx is None:
-            num_systems = 1
-        elif cell is not None:
-            num_systems = cell.size(0)
-        else:
-            num_systems = int(batch_idx.max().item()) + 1
-    energy = torch.empty(num_systems, **f32)  # zeroed inside mi_d3_zero
-    forces = torch.empty((n, 3), **f32)
-    coord_num = torch.empty(n, **f32)
-    virial = torch.empty((num_systems, 3, 3), **f32) if compute_virial else torch.zeros((0, 3, 3), **f32)
-    if C.tracing():  # torch.compile: one mutating custom op per call, as for `dftd3`
+        r4r2, c6_reference, coord_num_ref, positions, numbers, batch_idx, num_systems, cutoff_radii=cutoff_radii)
+    if positions.size(0) == 0:
+        return K.empty_result(positions, batch_idx, 1, compute_virial)
+    num_systems = K.infer_num_systems(num_systems, batch_idx, cell)
+    out = energy, forces, coord_num, virial = K.allocate(positions, num_systems, 1, compute_virial)
+    if C.tracing():
+        # torch.compile: one mutating custom op per call, as for `dftd3`
         if use_matrix:
             torch.ops.nvalchemiops.dftd3_zero_nm(positions, numbers, neighbor_matrix, covalent_radii, r4r2, c6_reference, coord_num_ref,
                                                  cutoff_radii, rs6, s8, energy, forces, coord_num, virial, rs8, alpha, beta, k1, k3, s6,
@@ -363,33 +257,23 @@ def dftd3_zero(positions: torch.Tensor, numbers: torch.Tensor, rs6: float, s8: f
             torch.ops.nvalchemiops.dftd3_zero_nl(positions, numbers, neighbor_list[1], neighbor_ptr, covalent_radii, r4r2, c6_reference,
                                                  coord_num_ref, cutoff_radii, rs6, s8, energy, forces, coord_num, virial, rs8, alpha, beta, k1,
                                                  k3, s6, s5_smoothing_on, s5_smoothing_off, batch_idx, cell, unit_shifts, compute_virial, None)
-        return (energy, forces, coord_num, virial) if compute_virial else (energy, forces, coord_num)
-    C.require_device(positions, numbers, neighbor_matrix, neighbor_list, neighbor_ptr, batch_idx)
-    scalars = zero_scalars(s6, s8, k1, k3, s5_smoothing_on, s5_smoothing_off)
-    tables = (covalent_radii, r4r2, c6_reference, coord_num_ref)
-    zero = (rs6, rs8, alpha, beta, cutoff_radii)
-    if use_matrix:
-        nm = C.i32(neighbor_matrix)
-        fill = n if fill_value is None else fill_value
-        packed = None
-        if nm is neighbor_matrix and cell is not None and neighbor_matrix_shifts is not None and int(fill) >= n:
-            from nvalchemiops.neighborlist import _engine as E
-
-            # exactly `dftd3`'s route: the companion and the search-side coordination numbers know nothing about the damping
-            packed = E.packed_companion(nm, neighbor_matrix_shifts, fill)
-            E.learn_dftd3_context(nm, numbers, covalent_radii, k1)
-        _launch(positions, numbers, nm, neighbor_matrix_shifts, None, nm.size(1), fill, cell,
-                batch_idx, num_systems, tables, scalars, compute_virial, energy, forces, coord_num, virial, packed=packed, zero=zero)
     else:
-        idx_j = C.i32(neighbor_list[1])
-        _launch(positions, numbers, idx_j, unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, num_systems, tables, scalars,
-                compute_virial, energy, forces, coord_num, virial, zero=zero)
-    return (energy, forces, coord_num, virial) if compute_virial else (energy, forces, coord_num)
+        C.require_device(positions, numbers, neighbor_matrix, neighbor_list, neighbor_ptr, batch_idx)
+        lists = K.list_args(positions.size(0), neighbor_matrix, neighbor_matrix_shifts, fill_value, neighbor_list, neighbor_ptr, unit_shifts)
+        _two_body(positions, numbers, lists, neighbor_matrix, cell, batch_idx, num_systems, (covalent_radii, r4r2, c6_reference, coord_num_ref),
+                  zero_scalars(s6, s8, k1, k3, s5_smoothing_on, s5_smoothing_off), k1, compute_virial, out,
+                  zero=(rs6, rs8, alpha, beta, cutoff_radii))
+    return K.select(out, compute_virial)
+
+
+def d3_scalars(a1, a2, s6, s8, k1, k3, on, off):
+    """The floats of `mi_d3_params`."""
+    return dict(a1=a1, a2=a2, s6=s6, s8=s8, k1=k1, k3=k3, s5_on=on, s5_off=off)
 
 
 def zero_scalars(s6, s8, k1, k3, on, off):
     """`mi_d3_params` scalars of a zero-damping call: a1 / a2 are not read."""
-    return dict(a1=0.0, a2=0.0, s6=s6, s8=s8, k1=k1, k3=k3, s5_on=on, s5_off=off)
+    return d3_scalars(0.0, 0.0, s6, s8, k1, k3, on, off)
 
 
 def atm_tile() -> int:
@@ -402,30 +286,18 @@ def _launch_atm(positions, numbers, idx, shifts, nptr, max_neighbors, fill_value
     """One `mi_d3_atm` call on the caller's arrays.  `want_visits`: return the per-centre triangle-visit counts the triple pass leaves in
     its workspace (a diagnostic for tools/atm_bench.py).  `zero`: None, or (rs9, cutoff_radii[nz,nz]) for the radii of the zero damping
     (`mi_d3_zero_atm`; scalars' a1 / a2 are then ignored)."""
-    dev = positions.device
     n = positions.shape[0]
-    pos = positions.detach().contiguous()
-    code = C.dtype_code(pos.dtype)
-    f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
-    rcov, r4r2, c6ab, cnref = (f32(t) for t in tables)
-    if c6ab.shape[-1] != 5 or c6ab.shape[-2] != 5:
-        raise ValueError("this build supports the standard 5x5 CN interpolation mesh only")
-    par = C.MiD3Params(rcov=rcov.data_ptr(), r4r2=r4r2.data_ptr(), c6ab=c6ab.data_ptr(), cn_ref=cnref.data_ptr(), nz=rcov.shape[0],
-                       **{k: float(v) for k, v in scalars.items()})
-    periodic = cell is not None and shifts is not None
-    cell_t = cell.detach().to(dtype=pos.dtype, device=dev).reshape(-1, 3, 3).contiguous() if periodic else None
-    sh = C.i32(shifts.to(dev)) if periodic else None
-    bi = None if batch_idx is None else C.i32(batch_idx)
+    pos, code, z, cell_t, sh, bi = K.prelude(positions, numbers, shifts, cell, batch_idx)
+    par, keep = K.d3_struct(pos.device, tables, scalars)
     L = C.lib()
     if not hasattr(L, "mi_d3_atm"):
         raise C.NativeLibraryError("libnvalchemiops_hip.so does not export mi_d3_atm: rebuild it (build_native.py)")
-    ws_bytes = int(L.mi_d3_atm_workspace_bytes(n, num_systems, rcov.shape[0]))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    z = C.i32(numbers)  # converted tensors stay referenced until the launch is enqueued
+    ws_bytes = int(L.mi_d3_atm_workspace_bytes(n, num_systems, par.nz))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos.device)
     if zero is not None:
         if not hasattr(L, "mi_d3_zero_atm"):
             raise C.NativeLibraryError("libnvalchemiops_hip.so does not export mi_d3_zero_atm: rebuild it (build_native.py)")
-        r0ab = f32(zero[1])
+        r0ab = K.f32_on(zero[1], pos.device)
         rc = L.mi_d3_zero_atm(C.ptr(pos), C.ptr(z), n, code, C.ptr(idx), C.ptr(sh), C.ptr(nptr), int(max_neighbors), int(fill_value), C.ptr(cell_t),
                               C.ptr(bi), int(num_systems), ctypes.byref(par), float(s9), float(alpha), float(three_body_cutoff), float(zero[0]),
                               C.ptr(r0ab), int(bool(compute_virial)), C.ptr(energy), C.ptr(forces), C.ptr(virial if compute_virial else None),
@@ -438,7 +310,7 @@ def _launch_atm(positions, numbers, idx, shifts, nptr, max_neighbors, fill_value
                          C.stream_of(pos))
         C.check(rc, "mi_d3_atm")
     if want_visits:
-        off = int(L.mi_d3_atm_visits_offset(n, num_systems, rcov.shape[0]))
+        off = int(L.mi_d3_atm_visits_offset(n, num_systems, par.nz))
         return ws[off:off + 4 * n].view(torch.int32).clone()
     return None
 
@@ -468,35 +340,17 @@ def dftd3_atm(positions: torch.Tensor, numbers: torch.Tensor, a1: float, a2: flo
     ``half_fill``) and its cutoff is at least ``three_body_cutoff``.  Entries beyond ``three_body_cutoff`` are part of no triple (they still
     count for the coordination numbers).  A periodic list may hold an atom's own images and several images of one neighbour: those are
     distinct vertices.  Argument names, parameter resolution, validation, ``num_systems`` inference and empty-input behaviour are `dftd3`'s."""
-    missing = None
     if a1 is None or a2 is None:
         missing = ("Functional parameters a1 and a2 must be provided. "
                    "These are functional-dependent parameters required for DFT-D3(BJ) calculations.")
-    elif three_body_cutoff is None:
-        missing = "three_body_cutoff must be provided: the distance below which all three sides of a triple must lie."
-    elif not three_body_cutoff > 0:
-        missing = f"three_body_cutoff must be positive, got {three_body_cutoff}"
-    elif not alpha > 0:
-        missing = f"alpha must be positive, got {alpha}"
-    use_matrix, use_list, tables = _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell,
-                                                      compute_virial, missing, d3_params, covalent_radii, r4r2, c6_reference, coord_num_ref,
-                                                      (positions, numbers, batch_idx, num_systems))
-    n, dev = positions.size(0), positions.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    if n == 0:
-        nsys = 1 if (batch_idx is None or batch_idx.numel() == 0) else int(batch_idx.max().item()) + 1
-        out = (torch.zeros(nsys, **f32), torch.zeros((0, 3), **f32))
-        return out + (torch.zeros((0, 3, 3), **f32),) if compute_virial else out
-    if num_systems is None:
-        if batch_idx is None:
-            num_systems = 1
-        elif cell is not None:
-            num_systems = cell.size(0)
-        else:
-            num_systems = int(batch_idx.max().item()) + 1
-    energy = torch.empty(num_systems, **f32)  # written for every system inside mi_d3_atm
-    forces = torch.empty((n, 3), **f32)
-    virial = torch.empty((num_systems, 3, 3), **f32) if compute_virial else torch.zeros((0, 3, 3), **f32)
+    else:
+        missing = K.three_body_missing(three_body_cutoff, alpha)
+    use_matrix, tables = _check_d3(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial, missing,
+                                   d3_params, covalent_radii, r4r2, c6_reference, coord_num_ref, positions, numbers, batch_idx, num_systems)
+    if positions.size(0) == 0:
+        return K.empty_result(positions, batch_idx, 0, compute_virial)
+    num_systems = K.infer_num_systems(num_systems, batch_idx, cell)
+    out = energy, forces, virial = K.allocate(positions, num_systems, 0, compute_virial)
     if C.tracing():
         if use_matrix:
             torch.ops.nvalchemiops.dftd3_atm_nm(positions, numbers, neighbor_matrix, tables[0], tables[1], tables[2], tables[3], a1, a2,
@@ -506,17 +360,12 @@ def dftd3_atm(positions: torch.Tensor, numbers: torch.Tensor, a1: float, a2: flo
             torch.ops.nvalchemiops.dftd3_atm_nl(positions, numbers, neighbor_list[1], neighbor_ptr, tables[0], tables[1], tables[2], tables[3],
                                                 a1, a2, three_body_cutoff, energy, forces, virial, s9, alpha, k1, k3, batch_idx, cell, unit_shifts,
                                                 compute_virial)
-        return (energy, forces, virial) if compute_virial else (energy, forces)
-    C.require_device(positions, numbers, neighbor_matrix, neighbor_list, neighbor_ptr, batch_idx)
-    scalars = atm_scalars(a1, a2, k1, k3)
-    if use_matrix:
-        nm = C.i32(neighbor_matrix)
-        _launch_atm(positions, numbers, nm, neighbor_matrix_shifts, None, nm.size(1), n if fill_value is None else fill_value, cell, batch_idx,
-                    num_systems, tables, scalars, s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial)
     else:
-        _launch_atm(positions, numbers, C.i32(neighbor_list[1]), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, num_systems, tables,
-                    scalars, s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial)
-    return (energy, forces, virial) if compute_virial else (energy, forces)
+        C.require_device(positions, numbers, neighbor_matrix, neighbor_list, neighbor_ptr, batch_idx)
+        lists = K.list_args(positions.size(0), neighbor_matrix, neighbor_matrix_shifts, fill_value, neighbor_list, neighbor_ptr, unit_shifts)
+        _launch_atm(positions, numbers, *lists, cell, batch_idx, num_systems, tables, atm_scalars(a1, a2, k1, k3), s9, alpha, three_body_cutoff,
+                    compute_virial, *out)
+    return K.select(out, compute_virial)
 
 
 @C.hybrid
@@ -533,35 +382,16 @@ def dftd3_zero_atm(positions: torch.Tensor, numbers: torch.Tensor, three_body_cu
     ``cutoff_radii`` is resolved as in `dftd3_zero` (explicit, or key ``"r0ab"`` of a ``d3_params`` dict); a triple with a pair whose entry
     is <= 0 contributes nothing.  The remaining arguments, the list requirements and the outputs -- ``(energy[num_systems], forces[N,3])``
     (+ ``virial[num_systems,3,3]``) of the three-body term alone, to be added to `dftd3_zero`'s -- are `dftd3_atm`'s."""
-    missing = None
-    if three_body_cutoff is None:
-        missing = "three_body_cutoff must be provided: the distance below which all three sides of a triple must lie."
-    elif not three_body_cutoff > 0:
-        missing = f"three_body_cutoff must be positive, got {three_body_cutoff}"
-    elif not alpha > 0:
-        missing = f"alpha must be positive, got {alpha}"
-    elif not rs9 > 0:
+    missing = K.three_body_missing(three_body_cutoff, alpha)
+    if missing is None and not rs9 > 0:
         missing = f"rs9 must be positive, got {rs9}"
-    use_matrix, use_list, tables = _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell,
-                                                      compute_virial, missing, d3_params, covalent_radii, r4r2, c6_reference, coord_num_ref,
-                                                      (positions, numbers, batch_idx, num_systems), cutoff_radii=cutoff_radii)
-    tables, cutoff_radii = tables[:4], tables[4]
-    n, dev = positions.size(0), positions.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    if n == 0:
-        nsys = 1 if (batch_idx is None or batch_idx.numel() == 0) else int(batch_idx.max().item()) + 1
-        out = (torch.zeros(nsys, **f32), torch.zeros((0, 3), **f32))
-        return out + (torch.zeros((0, 3, 3), **f32),) if compute_virial else out
-    if num_systems is None:
-        if batch_idx is None:
-            num_systems = 1
-        elif cell is not None:
-            num_systems = cell.size(0)
-        else:
-            num_systems = int(batch_idx.max().item()) + 1
-    energy = torch.empty(num_systems, **f32)  # written for every system inside mi_d3_zero_atm
-    forces = torch.empty((n, 3), **f32)
-    virial = torch.empty((num_systems, 3, 3), **f32) if compute_virial else torch.zeros((0, 3, 3), **f32)
+    use_matrix, tables, cutoff_radii = _check_d3(
+        neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial, missing, d3_params, covalent_radii,
+        r4r2, c6_reference, coord_num_ref, positions, numbers, batch_idx, num_systems, cutoff_radii=cutoff_radii)
+    if positions.size(0) == 0:
+        return K.empty_result(positions, batch_idx, 0, compute_virial)
+    num_systems = K.infer_num_systems(num_systems, batch_idx, cell)
+    out = energy, forces, virial = K.allocate(positions, num_systems, 0, compute_virial)
     if C.tracing():
         if use_matrix:
             torch.ops.nvalchemiops.dftd3_zero_atm_nm(positions, numbers, neighbor_matrix, tables[0], tables[1], tables[2], tables[3], cutoff_radii,
@@ -571,20 +401,14 @@ def dftd3_zero_atm(positions: torch.Tensor, numbers: torch.Tensor, three_body_cu
             torch.ops.nvalchemiops.dftd3_zero_atm_nl(positions, numbers, neighbor_list[1], neighbor_ptr, tables[0], tables[1], tables[2],
                                                      tables[3], cutoff_radii, three_body_cutoff, energy, forces, virial, rs9, s9, alpha, k1, k3,
                                                      batch_idx, cell, unit_shifts, compute_virial)
-        return (energy, forces, virial) if compute_virial else (energy, forces)
-    C.require_device(positions, numbers, neighbor_matrix, neighbor_list, neighbor_ptr, batch_idx)
-    scalars = atm_scalars(0.0, 0.0, k1, k3)
-    zero = (rs9, cutoff_radii)
-    if use_matrix:
-        nm = C.i32(neighbor_matrix)
-        _launch_atm(positions, numbers, nm, neighbor_matrix_shifts, None, nm.size(1), n if fill_value is None else fill_value, cell, batch_idx,
-                    num_systems, tables, scalars, s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial, zero=zero)
     else:
-        _launch_atm(positions, numbers, C.i32(neighbor_list[1]), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, num_systems, tables,
-                    scalars, s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial, zero=zero)
-    return (energy, forces, virial) if compute_virial else (energy, forces)
+        C.require_device(positions, numbers, neighbor_matrix, neighbor_list, neighbor_ptr, batch_idx)
+        lists = K.list_args(positions.size(0), neighbor_matrix, neighbor_matrix_shifts, fill_value, neighbor_list, neighbor_ptr, unit_shifts)
+        _launch_atm(positions, numbers, *lists, cell, batch_idx, num_systems, tables, atm_scalars(0.0, 0.0, k1, k3), s9, alpha, three_body_cutoff,
+                    compute_virial, *out, zero=(rs9, cutoff_radii))
+    return K.select(out, compute_virial)
 
 
 def atm_scalars(a1, a2, k1, k3):
     """`mi_d3_params` scalars of a three-body call: the two-body-only ones (s6, s8, the S5 window) are not read."""
-    return dict(a1=a1, a2=a2, s6=0.0, s8=0.0, k1=k1, k3=k3, s5_on=1e10, s5_off=1e10)
+    return d3_scalars(a1, a2, 0.0, 0.0, k1, k3, 1e10, 1e10)

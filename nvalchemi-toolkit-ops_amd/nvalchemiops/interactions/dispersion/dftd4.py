@@ -16,15 +16,13 @@ from dataclasses import dataclass
 import torch
 
 from nvalchemiops import _capi as C
-from nvalchemiops.interactions.dispersion.dftd3 import _check_and_resolve
+from nvalchemiops.interactions.dispersion import _call as K
 
-_FLOAT_TYPES = (torch.float32, torch.float64)
+_FLOAT_TYPES = K.FLOAT_TYPES
 _INT_TYPES = (torch.int32, torch.int64)
 N_REF = 7  # references per element the tables hold
 K4, K5, K6 = 4.10451, 19.08857, 2.0 * 11.28174 ** 2  # the electronegativity factor of the D4 covalent coordination number
-_FLOAT_TABLES = ("rcov", "en", "r4r2", "zeff", "gam", "cn_ref", "q_ref", "c6_ref")
-_INT_TABLES = ("n_ref", "ngw")
-_TABLES = ("rcov", "en", "r4r2", "zeff", "gam", "n_ref", "ngw", "cn_ref", "q_ref", "c6_ref")
+_INT_TABLES, _TABLES = K.D4_INT_TABLES, K.D4_TABLES
 
 
 @dataclass
@@ -101,26 +99,15 @@ def species_slots() -> int:
 def _launch(positions, numbers, charges, idx, shifts, nptr, max_neighbors, fill_value, cell, batch_idx, num_systems, tables, scalars, compute_virial,
             energy, forces, coord_num, charge_grad, virial) -> None:
     """One `mi_d4` call on the caller's arrays.  `tables`: the ten tensors in `D4Parameters` order; `scalars`: the floats of `mi_d4_params`."""
-    dev = positions.device
     n = positions.shape[0]
-    pos = positions.detach().contiguous()
-    code = C.dtype_code(pos.dtype)
-    f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
-    named = dict(zip(_TABLES, tables))
-    conv = {k: (C.i32(named[k].detach().to(dev)) if k in _INT_TABLES else f32(named[k])) for k in _TABLES}  # stay referenced until the launch is enqueued
+    pos, code, z, cell_t, sh, bi = K.prelude(positions, numbers, shifts, cell, batch_idx)
+    par, keep = K.d4_struct(pos.device, tables, scalars)
     L = C.lib()
     if not hasattr(L, "mi_d4"):
         raise C.NativeLibraryError("libnvalchemiops_hip.so does not export mi_d4: rebuild it (build_native.py)")
-    nz = conv["rcov"].shape[0]
-    par = C.MiD4Params(**{k: conv[k].data_ptr() for k in _TABLES}, nz=nz, **{k: float(v) for k, v in scalars.items()})
-    periodic = cell is not None and shifts is not None
-    cell_t = cell.detach().to(dtype=pos.dtype, device=dev).reshape(-1, 3, 3).contiguous() if periodic else None
-    sh = C.i32(shifts.to(dev)) if periodic else None
-    bi = None if batch_idx is None else C.i32(batch_idx)
-    q = f32(charges)
-    z = C.i32(numbers)
-    ws_bytes = int(L.mi_d4_workspace_bytes(n, int(num_systems), nz))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    q = K.f32_on(charges, pos.device)
+    ws_bytes = int(L.mi_d4_workspace_bytes(n, int(num_systems), par.nz))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos.device)
     rc = L.mi_d4(C.ptr(pos), C.ptr(z), n, code, C.ptr(idx), C.ptr(sh), C.ptr(nptr), int(max_neighbors),
                  ctypes.c_longlong(idx.shape[0] if nptr is not None else 0), int(fill_value), C.ptr(cell_t), C.ptr(bi), int(num_systems),
                  ctypes.byref(par), C.ptr(q), int(bool(compute_virial)), C.ptr(energy), C.ptr(forces), C.ptr(coord_num), C.ptr(charge_grad),
@@ -133,27 +120,21 @@ def d4_scalars(a1, a2, s6, s8, k_cn, wf, ga, gc, cn_cutoff):
     return dict(a1=a1, a2=a2, s6=s6, s8=s8, k_cn=k_cn, k4=K4, k5=K5, k6=K6, wf=wf, ga=ga, gc=gc, cn_cutoff=0.0 if cn_cutoff is None else cn_cutoff)
 
 
-class _D4Energy(torch.autograd.Function):
-    """`energy` with a hand-written first-order adjoint: d(sum_s g_s E_s)/d(positions) = -g[batch] forces, /d(charges) = g[batch] dE/dq."""
-
-    @staticmethod
-    def forward(ctx, positions, charges, batch_idx, run):
-        out = run()
-        energy, forces, _, charge_grad = out[:4]
-        ctx.save_for_backward(forces, charge_grad)
-        ctx.batch_idx = batch_idx
-        ctx.dtypes = (positions.dtype, charges.dtype)
-        ctx.mark_non_differentiable(*out[1:])
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g, *_unused):
-        forces, charge_grad = ctx.saved_tensors
-        ga = g.expand(forces.shape[0]) if ctx.batch_idx is None else g[ctx.batch_idx.long()]
-        gp = (-ga[:, None] * forces).to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None
-        gq = (ga * charge_grad).to(ctx.dtypes[1]) if ctx.needs_input_grad[1] else None
-        return gp, gq, None, None
+def _check_d4(d4_params, neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial, missing_functional,
+              positions, numbers, batch_idx, num_systems):
+    """Argument validation of `dftd4` / `dftd4_atm`, in the order a caller meets it: a `d4_params` dictionary goes through `D4Parameters`
+    first; then `dftd3`'s list-format checks; then the missing tables; then the per-atom / neighbour data.  Returns (use_matrix, the ten
+    tables in `D4Parameters` order)."""
+    if d4_params is not None and not isinstance(d4_params, D4Parameters):
+        d4_params = D4Parameters(**{k: d4_params[k] for k in _TABLES})
+    use_matrix = K.check_lists(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial,
+                               missing_functional)
+    if d4_params is None:
+        raise RuntimeError("DFT-D4 parameters must be explicitly provided: pass d4_params, a D4Parameters instance or a dictionary with its "
+                           "ten tables (rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref).")
+    K.check_atoms(positions, numbers, batch_idx, num_systems, neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts,
+                  cell)
+    return use_matrix, tuple(getattr(d4_params, k) for k in _TABLES)
 
 
 @C.hybrid
@@ -199,49 +180,20 @@ def dftd4(positions: torch.Tensor, numbers: torch.Tensor, charges: torch.Tensor,
     if a1 is None or a2 is None or s8 is None:
         missing = ("Functional parameters a1, a2, and s8 must be provided. "
                    "These are functional-dependent parameters required for DFT-D4 calculations.")
-    if d4_params is None:
-        tables = None
-    elif isinstance(d4_params, D4Parameters):
-        tables = tuple(getattr(d4_params, k) for k in _TABLES)
-    else:
-        checked = D4Parameters(**{k: d4_params[k] for k in _TABLES})
-        tables = tuple(getattr(checked, k) for k in _TABLES)
-    # `dftd3`'s checks in `dftd3`'s order; its four table slots take tensors of matching shapes (D4Parameters has validated the D4 tables)
-    atoms = (positions, numbers, batch_idx, num_systems)
-    if tables is None:  # the list checks come first, as in `dftd3`; then the missing tables are reported
-        try:
-            _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial, missing,
-                               None, None, None, None, None, atoms)
-        except RuntimeError:
-            pass
-        raise RuntimeError("DFT-D4 parameters must be explicitly provided: pass d4_params, a D4Parameters instance or a dictionary with its "
-                           "ten tables (rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref).")
-    use_matrix, use_list, _ = _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell,
-                                                 compute_virial, missing, None, tables[0], tables[2], tables[9], tables[9], atoms)
-    n, dev = positions.size(0), positions.device
+    use_matrix, tables = _check_d4(d4_params, neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial,
+                                   missing, positions, numbers, batch_idx, num_systems)
+    n = positions.size(0)
     if not isinstance(charges, torch.Tensor):
         raise TypeError(f"charges must be a torch.Tensor, got {type(charges)}")
     if charges.dtype not in _FLOAT_TYPES:
         raise TypeError(f"charges must be float32 or float64, got {charges.dtype}")
     if charges.dim() != 1 or charges.shape[0] != n:
         raise ValueError(f"charges must have one entry per atom: expected shape [{n}], got {tuple(charges.shape)}")
-    f32 = dict(dtype=torch.float32, device=dev)
     if n == 0:
-        nsys = 1 if (batch_idx is None or batch_idx.numel() == 0) else int(batch_idx.max().item()) + 1
-        out = (torch.zeros(nsys, **f32), torch.zeros((0, 3), **f32), torch.zeros((0,), **f32), torch.zeros((0,), **f32))
-        return out + (torch.zeros((0, 3, 3), **f32),) if compute_virial else out
-    if num_systems is None:
-        if batch_idx is None:
-            num_systems = 1
-        elif cell is not None:
-            num_systems = cell.size(0)
-        else:
-            num_systems = int(batch_idx.max().item()) + 1
-    energy = torch.empty(num_systems, **f32)  # written for every system inside mi_d4
-    forces = torch.empty((n, 3), **f32)
-    coord_num = torch.empty(n, **f32)
-    charge_grad = torch.empty(n, **f32)
-    virial = torch.empty((num_systems, 3, 3), **f32) if compute_virial else torch.zeros((0, 3, 3), **f32)
+        return K.empty_result(positions, batch_idx, 2, compute_virial)
+    num_systems = K.infer_num_systems(num_systems, batch_idx, cell)
+    out = energy, forces, coord_num, charge_grad, virial = K.allocate(positions, num_systems, 2, compute_virial)
+    result = K.select(out, compute_virial)
     if C.tracing():  # torch.compile: one mutating custom op per call, as for `dftd3`; no autograd on this path
         if use_matrix:
             torch.ops.nvalchemiops.dftd4_nm(positions, numbers, charges, neighbor_matrix, *tables, a1, a2, s8, energy, forces, coord_num,
@@ -251,22 +203,17 @@ def dftd4(positions: torch.Tensor, numbers: torch.Tensor, charges: torch.Tensor,
             torch.ops.nvalchemiops.dftd4_nl(positions, numbers, charges, neighbor_list[1], neighbor_ptr, *tables, a1, a2, s8, energy, forces,
                                             coord_num, charge_grad, virial, s6, cn_cutoff, wf, ga, gc, k_cn, batch_idx, cell, unit_shifts,
                                             compute_virial)
-        return (energy, forces, coord_num, charge_grad, virial) if compute_virial else (energy, forces, coord_num, charge_grad)
+        return result
     C.require_device(positions, numbers, charges, neighbor_matrix, neighbor_list, neighbor_ptr, batch_idx)
-    scalars = d4_scalars(a1, a2, s6, s8, k_cn, wf, ga, gc, cn_cutoff)
 
     def run():
-        if use_matrix:
-            nm = C.i32(neighbor_matrix)
-            _launch(positions, numbers, charges, nm, neighbor_matrix_shifts, None, nm.size(1), n if fill_value is None else fill_value, cell,
-                    batch_idx, num_systems, tables, scalars, compute_virial, energy, forces, coord_num, charge_grad, virial)
-        else:
-            _launch(positions, numbers, charges, C.i32(neighbor_list[1]), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, num_systems,
-                    tables, scalars, compute_virial, energy, forces, coord_num, charge_grad, virial)
-        return (energy, forces, coord_num, charge_grad, virial) if compute_virial else (energy, forces, coord_num, charge_grad)
+        lists = K.list_args(n, neighbor_matrix, neighbor_matrix_shifts, fill_value, neighbor_list, neighbor_ptr, unit_shifts)
+        _launch(positions, numbers, charges, *lists, cell, batch_idx, num_systems, tables, d4_scalars(a1, a2, s6, s8, k_cn, wf, ga, gc, cn_cutoff),
+                compute_virial, *out)
+        return result
 
     if torch.is_grad_enabled() and (positions.requires_grad or charges.requires_grad):
-        return _D4Energy.apply(positions, charges, batch_idx, run)
+        return K.EnergyAdjoint.apply(positions, charges, batch_idx, run)
     return run()
 
 
@@ -279,54 +226,23 @@ def _launch_atm(positions, numbers, idx, shifts, nptr, max_neighbors, fill_value
                 three_body_cutoff, compute_virial, energy, forces, virial, want_visits=False):
     """One `mi_d4_atm` call on the caller's arrays (`tables`, `scalars`: as for `_launch`; s6 / s8 are not read).  `want_visits`: return the
     per-centre triangle-visit counts the triple pass leaves in its workspace (a diagnostic for tools/d4_atm_bench.py)."""
-    dev = positions.device
     n = positions.shape[0]
-    pos = positions.detach().contiguous()
-    code = C.dtype_code(pos.dtype)
-    f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
-    named = dict(zip(_TABLES, tables))
-    conv = {k: (C.i32(named[k].detach().to(dev)) if k in _INT_TABLES else f32(named[k])) for k in _TABLES}  # stay referenced until the launch is enqueued
+    pos, code, z, cell_t, sh, bi = K.prelude(positions, numbers, shifts, cell, batch_idx)
+    par, keep = K.d4_struct(pos.device, tables, scalars)
     L = C.lib()
     if not hasattr(L, "mi_d4_atm"):
         raise C.NativeLibraryError("libnvalchemiops_hip.so does not export mi_d4_atm: rebuild it (build_native.py)")
-    nz = conv["rcov"].shape[0]
-    par = C.MiD4Params(**{k: conv[k].data_ptr() for k in _TABLES}, nz=nz, **{k: float(v) for k, v in scalars.items()})
-    periodic = cell is not None and shifts is not None
-    cell_t = cell.detach().to(dtype=pos.dtype, device=dev).reshape(-1, 3, 3).contiguous() if periodic else None
-    sh = C.i32(shifts.to(dev)) if periodic else None
-    bi = None if batch_idx is None else C.i32(batch_idx)
-    z = C.i32(numbers)
-    ws_bytes = int(L.mi_d4_atm_workspace_bytes(n, int(num_systems), nz))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws_bytes = int(L.mi_d4_atm_workspace_bytes(n, int(num_systems), par.nz))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=pos.device)
     rc = L.mi_d4_atm(C.ptr(pos), C.ptr(z), n, code, C.ptr(idx), C.ptr(sh), C.ptr(nptr), int(max_neighbors), int(fill_value), C.ptr(cell_t),
                      C.ptr(bi), int(num_systems), ctypes.byref(par), float(s9), float(alpha), float(three_body_cutoff), int(bool(compute_virial)),
                      C.ptr(energy), C.ptr(forces), C.ptr(virial if compute_virial else None), C.ptr(ws), ctypes.c_size_t(ws_bytes),
                      C.stream_of(pos))
     C.check(rc, "mi_d4_atm")
     if want_visits:
-        off = int(L.mi_d4_atm_visits_offset(n, int(num_systems), nz))
+        off = int(L.mi_d4_atm_visits_offset(n, int(num_systems), par.nz))
         return ws[off:off + 4 * n].view(torch.int32).clone()
     return None
-
-
-class _D4AtmEnergy(torch.autograd.Function):
-    """`energy` of `dftd4_atm` with `dftd4`'s hand-written first-order adjoint: d(sum_s g_s E_s)/d(positions) = -g[batch] forces."""
-
-    @staticmethod
-    def forward(ctx, positions, batch_idx, run):
-        out = run()
-        ctx.save_for_backward(out[1])
-        ctx.batch_idx = batch_idx
-        ctx.dtype = positions.dtype
-        ctx.mark_non_differentiable(*out[1:])
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g, *_unused):
-        (forces,) = ctx.saved_tensors
-        ga = g.expand(forces.shape[0]) if ctx.batch_idx is None else g[ctx.batch_idx.long()]
-        return (-ga[:, None] * forces).to(ctx.dtype), None, None
 
 
 @C.hybrid
@@ -365,51 +281,19 @@ def dftd4_atm(positions: torch.Tensor, numbers: torch.Tensor, a1: float, a2: flo
     (``nvalchemiops::dftd4_atm_nm`` / ``::dftd4_atm_nl``); there is no autograd on that path.
 
     Out of scope: a charge-dependent three-body C6 and its dE/dq, zero damping, the packed companion and element tables."""
-    missing = None
     if a1 is None or a2 is None:
         missing = ("Functional parameters a1 and a2 must be provided. "
                    "These are functional-dependent parameters required for DFT-D4 calculations.")
-    elif three_body_cutoff is None:
-        missing = "three_body_cutoff must be provided: the distance below which all three sides of a triple must lie."
-    elif not three_body_cutoff > 0:
-        missing = f"three_body_cutoff must be positive, got {three_body_cutoff}"
-    elif not alpha > 0:
-        missing = f"alpha must be positive, got {alpha}"
-    if d4_params is None:
-        tables = None
-    elif isinstance(d4_params, D4Parameters):
-        tables = tuple(getattr(d4_params, k) for k in _TABLES)
     else:
-        checked = D4Parameters(**{k: d4_params[k] for k in _TABLES})
-        tables = tuple(getattr(checked, k) for k in _TABLES)
-    atoms = (positions, numbers, batch_idx, num_systems)
-    if tables is None:  # the list checks come first, as in `dftd4`; then the missing tables are reported
-        try:
-            _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial, missing,
-                               None, None, None, None, None, atoms)
-        except RuntimeError:
-            pass
-        raise RuntimeError("DFT-D4 parameters must be explicitly provided: pass d4_params, a D4Parameters instance or a dictionary with its "
-                           "ten tables (rcov, en, r4r2, zeff, gam, n_ref, ngw, cn_ref, q_ref, c6_ref).")
-    use_matrix, use_list, _ = _check_and_resolve(neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell,
-                                                 compute_virial, missing, None, tables[0], tables[2], tables[9], tables[9], atoms)
-    n, dev = positions.size(0), positions.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    if n == 0:
-        nsys = 1 if (batch_idx is None or batch_idx.numel() == 0) else int(batch_idx.max().item()) + 1
-        out = (torch.zeros(nsys, **f32), torch.zeros((0, 3), **f32))
-        return out + (torch.zeros((0, 3, 3), **f32),) if compute_virial else out
-    if num_systems is None:
-        if batch_idx is None:
-            num_systems = 1
-        elif cell is not None:
-            num_systems = cell.size(0)
-        else:
-            num_systems = int(batch_idx.max().item()) + 1
-    energy = torch.empty(num_systems, **f32)  # written for every system inside mi_d4_atm
-    forces = torch.empty((n, 3), **f32)
-    virial = torch.empty((num_systems, 3, 3), **f32) if compute_virial else torch.zeros((0, 3, 3), **f32)
-    if C.tracing():  # torch.compile: one mutating custom op per call, as for `dftd4`; no autograd on this path
+        missing = K.three_body_missing(three_body_cutoff, alpha)
+    use_matrix, tables = _check_d4(d4_params, neighbor_matrix, neighbor_matrix_shifts, neighbor_list, neighbor_ptr, unit_shifts, cell, compute_virial,
+                                   missing, positions, numbers, batch_idx, num_systems)
+    if positions.size(0) == 0:
+        return K.empty_result(positions, batch_idx, 0, compute_virial)
+    num_systems = K.infer_num_systems(num_systems, batch_idx, cell)
+    out = energy, forces, virial = K.allocate(positions, num_systems, 0, compute_virial)
+    result = K.select(out, compute_virial)
+    if C.tracing():  # torch.compile: one mutating custom op per call, as for `dftd3`; no autograd on this path
         if use_matrix:
             torch.ops.nvalchemiops.dftd4_atm_nm(positions, numbers, neighbor_matrix, *tables, a1, a2, three_body_cutoff, energy, forces, virial,
                                                 s9, alpha, cn_cutoff, wf, ga, gc, k_cn, fill_value, batch_idx, cell, neighbor_matrix_shifts,
@@ -418,22 +302,17 @@ def dftd4_atm(positions: torch.Tensor, numbers: torch.Tensor, a1: float, a2: flo
             torch.ops.nvalchemiops.dftd4_atm_nl(positions, numbers, neighbor_list[1], neighbor_ptr, *tables, a1, a2, three_body_cutoff, energy,
                                                 forces, virial, s9, alpha, cn_cutoff, wf, ga, gc, k_cn, batch_idx, cell, unit_shifts,
                                                 compute_virial)
-        return (energy, forces, virial) if compute_virial else (energy, forces)
+        return result
     C.require_device(positions, numbers, neighbor_matrix, neighbor_list, neighbor_ptr, batch_idx)
-    scalars = d4_scalars(a1, a2, 0.0, 0.0, k_cn, wf, ga, gc, cn_cutoff)
 
     def run():
-        if use_matrix:
-            nm = C.i32(neighbor_matrix)
-            _launch_atm(positions, numbers, nm, neighbor_matrix_shifts, None, nm.size(1), n if fill_value is None else fill_value, cell,
-                        batch_idx, num_systems, tables, scalars, s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial)
-        else:
-            _launch_atm(positions, numbers, C.i32(neighbor_list[1]), unit_shifts, C.i32(neighbor_ptr), 0, 0, cell, batch_idx, num_systems,
-                        tables, scalars, s9, alpha, three_body_cutoff, compute_virial, energy, forces, virial)
-        return (energy, forces, virial) if compute_virial else (energy, forces)
+        lists = K.list_args(positions.size(0), neighbor_matrix, neighbor_matrix_shifts, fill_value, neighbor_list, neighbor_ptr, unit_shifts)
+        _launch_atm(positions, numbers, *lists, cell, batch_idx, num_systems, tables, d4_scalars(a1, a2, 0.0, 0.0, k_cn, wf, ga, gc, cn_cutoff),
+                    s9, alpha, three_body_cutoff, compute_virial, *out)
+        return result
 
     if torch.is_grad_enabled() and positions.requires_grad:
-        return _D4AtmEnergy.apply(positions, batch_idx, run)
+        return K.EnergyAdjoint.apply(positions, None, batch_idx, run)
     return run()
 
 

@@ -616,3 +616,22 @@ def test_full_list_record_validity_rules():
     import gc
     gc.collect()
     assert E.full_list_counts(nm, sh) is None                                                      # the counts tensor is gone
+
+
+def test_dispersion_seam_is_pinned():
+    """The seam of the dispersion family as it stood before the six wrappers moved onto one call layer (interactions/dispersion/_call.py):
+    the schema `torch.library.custom_op` infers for each of the twelve ops and the signature of each public function, as recorded in
+    tests/golden/dispersion_seam.json (its note says at which commit and how)."""
+    import inspect
+    import json
+
+    import nvalchemiops  # noqa: F401  (registers the ops)
+    from nvalchemiops.interactions import dispersion as D
+
+    want = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dispersion_seam.json")))
+    names = ["dftd3", "dftd3_zero", "dftd3_atm", "dftd3_zero_atm", "dftd4", "dftd4_atm"]
+    assert sorted(want["signatures"]) == sorted(names) and sorted(want["schemas"]) == sorted(f"{n}_{l}" for n in names for l in ("nm", "nl"))
+    for name, schema in want["schemas"].items():
+        assert str(getattr(torch.ops.nvalchemiops, name).default._schema) == schema, name
+    for name, sig in want["signatures"].items():
+        assert str(inspect.signature(getattr(D, name))) == sig, name
