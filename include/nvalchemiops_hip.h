@@ -190,6 +190,8 @@ int mi_nl_moved_beyond_skin(const void* reference_positions, const void* current
  * reference's pass 0 (materialised cartesian_shifts) is folded into the passes.  Outputs are float32
  * whatever `dtype` (the positions/cell dtype) is.  Layout selector: neighbor_ptr == NULL -> padded matrix
  * (entries >= fill_value are padding), else CSR (idx_j[neighbor_ptr[i]..neighbor_ptr[i+1])).
+ * Atoms with Z <= 0 or Z >= nz are padding, as a neighbour and as the owner of a row: part of no pair and of no coordination number, no
+ * table entry is read for them, and their force and coordination number are 0 (mi_d3, mi_d3_zero, mi_d3_atm, mi_d3_zero_atm alike).
  */
 typedef struct {
   const float* rcov;   /* [nz]            */

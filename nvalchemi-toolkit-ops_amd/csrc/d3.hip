@@ -545,12 +545,14 @@ __device__ __forceinline__ void d3_cn_body(D3_CN_PARAMS, int vblock /* the block
   }
   const typename Vec4<T>::type* __restrict__ arec = SORT ? acn : apos;
   const int zi = numbers[i];
-  const bool live = i0 < N && zi != 0;  // idle waves still take part in the block's lock-step barriers
+  // idle waves still take part in the block's lock-step barriers; an atom outside the tables (Z <= 0 or Z >= nz) is padding as a row
+  // owner exactly as it is as a neighbour (d3_pack_atoms_kernel gives it the radius -1): no row, and no table entry is read for it
+  const bool live = i0 < N && zi > 0 && zi < P.nz;
   const bool periodic = (cell != nullptr) && (ush != nullptr);
   T cm[9];
   if (periodic) { const T* c = cell + 9 * (size_t)(batch_idx ? batch_idx[i] : 0); for (int k = 0; k < 9; ++k) cm[k] = c[k]; }
   const T pix = pos[3 * (size_t)i], piy = pos[3 * (size_t)i + 1], piz = pos[3 * (size_t)i + 2];
-  const float rci = P.rcov[zi];
+  const float rci = P.rcov[live ? zi : 0];
   long long beg, end;
   d3_row<T, CSR>(i, M, nptr, beg, end);
   if (!live) end = beg;
@@ -639,12 +641,12 @@ __global__ __launch_bounds__(D3_LS_WAVES * MI_WAVE) void d3_cn_pre_kernel(D3_CN_
   if (adopt_sh) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) {
       const int z = numbers[i];
-      if (z == 0) continue;  // outputs of such atoms stay zero, as in the pass itself
+      if (z <= 0 || z >= P.nz) continue;  // outputs of such atoms stay zero, as in the pass itself
       const float c = cn_pre[i];
       cn[i] = c;
       aaux[i].x = c;
     }
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) d3_weights_atom(i, -1, numbers[i] == 0 ? 0.0f : cn_pre[i], aaux, W);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N; i += gridDim.x * blockDim.x) d3_weights_atom(i, -1, (numbers[i] <= 0 || numbers[i] >= P.nz) ? 0.0f : cn_pre[i], aaux, W);
     // the list's cutoff, for the grid of the spatial order (what the pass reports as the largest pair distance it met)
     if (rmax_bits && blockIdx.x == 0 && threadIdx.x == 0 && __int_as_float(cn_hdr[2]) > 0.0f) atomicMax(rmax_bits, cn_hdr[2]);
     return;
@@ -970,7 +972,7 @@ __device__ __forceinline__ void d3_energy_body(const T* __restrict__ pos, const 
   if (PK && inv) { apos = apos_s; aaux = aaux_s; aw = aw_s; }
   const int self = (PK && inv) ? k0 : i;  // where this atom's own records are (masked-out lanes gather them)
   const int zi = numbers[i];
-  if (zi == 0) return;
+  if (zi <= 0 || zi >= P.nz) return;  // padding: outside the tables (the species map and the c6 tables have nz rows)
   const bool periodic = (cell != nullptr) && (ush != nullptr);
   T cm[9];
   if (periodic) { const T* c = cell + 9 * (size_t)(batch_idx ? batch_idx[i] : 0); for (int k = 0; k < 9; ++k) cm[k] = d3_uni(c[k]); }
@@ -1237,12 +1239,12 @@ __device__ __forceinline__ void d3_chain_body(const T* __restrict__ pos, const i
   const float* __restrict__ drec = ordered ? dEdCN_s : dEdCN;
   const int self = (CREC ? inv != nullptr : ordered) ? k0 : i;
   const int zi = numbers[i];
-  const bool live = i0 < N && zi != 0;  // idle waves still take part in the block's lock-step barriers
+  const bool live = i0 < N && zi > 0 && zi < P.nz;  // idle waves still take part in the block's lock-step barriers; padding as in the CN pass
   const bool periodic = (cell != nullptr) && (ush != nullptr);
   T cm[9];
   if (periodic) { const T* c = cell + 9 * (size_t)(batch_idx ? batch_idx[i] : 0); for (int k = 0; k < 9; ++k) cm[k] = c[k]; }
   const T pix = pos[3 * (size_t)i], piy = pos[3 * (size_t)i + 1], piz = pos[3 * (size_t)i + 2];
-  const float rci = P.rcov[zi], di = dEdCN[i];
+  const float rci = P.rcov[live ? zi : 0], di = dEdCN[i];
   long long beg, end;
   d3_row<T, CSR>(i, M, nptr, beg, end);
   if (!live) end = beg;

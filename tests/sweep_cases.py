@@ -1,0 +1,611 @@
+"""Seeded sweep cases, boundary ladders and one-scalar variants of the five newer dispersion operators (`dftd3_atm`, `dftd3_zero`,
+`dftd3_zero_atm`, `dftd4`, `dftd4_atm`) and the inputs of the sweeps of `gaussian_charge_correction` and charge equilibration (last section),
+built on the float64 restatements tests/atm_reference.py, tests/d3_zero_reference.py,
+tests/d4_reference.py and tests/d4_atm_reference.py.  Importable without a GPU and without the native library (the two tile sizes are read
+lazily, by the ladder builders only).  The CPU suite asserts every condition a case must meet (tests/test_sweep_cases_cpu.py); the GPU
+modules tests/test_sweep_dispersion_gpu.py and tests/test_sweep_charges_gpu.py compare the kernels with the references made here.  Every reference is computed once
+(`functools.lru_cache`) and never modified.
+
+    case(op, seed)            seeded random case; everything is drawn from np.random.default_rng(BASE[op] + seed)
+    ladder_case(op, name)     one rung of a boundary ladder: "n64" ... (lane trips), "m255" ... (block trips and LDS tiles)
+    variant_case(op, name)    a fixed case with ONE model scalar moved off its default ("default": none moved)
+    references(kind, op, key) (float64 restatement, the same with float32 per-pair / per-atom / per-triple arithmetic), at the case's s9
+
+A case is a dict: pos, z, cell ([B,3,3] or None), batch_idx (None for one system), tables, r0ab (zero damping), q (`dftd4`), rc (list
+cutoff), rc3 (three-body ops), model (the scalars, in the restatements' names), margins (cutoff name -> smallest |distance - cutoff| of any
+pair of atom images), counts / widest (entries per row of the full list, from the float64 enumeration), lists (how the GPU module stores
+the list: int64, pad, foreign fill, permuted rows), and for three-body ops s9.
+
+CUTOFFS.  The restatements enumerate pairs in float64, the kernels in float32 (rounding at these distances: 2e-6 Bohr); a pair within
+rounding of a cutoff is counted by one and not by the other, which is no kernel error.  Each cutoff is therefore placed at the midpoint of
+the widest gap between image-pair distances inside a window of +-0.4 Bohr around its drawn target (`place_cutoff`); the CPU suite asserts a
+margin of 1e-3 Bohr for every case.
+
+S9.  Not drawn: `d4_atm_cases.lifted`'s rule applied to the case's own float64 reference -- the smallest power of ten at which energy,
+forces and (periodic) virial reach 500 x the bar the GPU comparison applies -- so a three-body case is never compared against nothing.
+
+GEOMETRY of a sweep case: one to three systems with sizes from {1, 2, 3, 7, 20, 45} (at most 70 atoms, at least one system of 7 or more),
+jittered lattices (`atm_reference.lattice_box`, spacing 3.6 - 4.6 Bohr, jitter 0.25; the first n sites of the smallest box that holds
+them) or `systems.molecule(min_dist=2.0)`: the distances of a condensed phase, for the reason the restatements' docstrings give.  Periodic
+in two seeds of three; in a third of those one system sits in a cell shorter than the list cutoff (rows hold the atom's own images), the
+other cells are at least half a Bohr higher than it.  Systems of one or two atoms of a periodic batch sit in a cube no image reaches
+across.  Positions are float64 in every fourth seed.  Species counts are scheduled over {1, 3, 6, 7, 16, 17, 20} (the thresholds of
+`D3_ATM_LDS_S`, `D4_SLOTS` and the 16-species D3 paths) with tables up to Z = 24; one seed in four puts a Z = 0 atom, one a Z > max_Z atom
+and one an element without references (`n_ref = 0`; for the D3 family an all-zero c6 block) into the middle of the largest system.
+
+RADII of `dftd3_zero_atm` seeds.  With the table of tests/test_d3_zero_gpu.py (radii from 3.5 Bohr) and rs9 down to 0.8 the nearest-neighbour
+triples are undamped (R0 = 2.8 Bohr below a contact of 3.5): triple terms of both signs, orders of magnitude above the sums they cancel
+to, whose float32 rounding -- not the kernel's evaluation order -- then decides the virial.  The restatement's own float32 deviation
+reached 2.9 of `dftd3`'s bar (seed 4; 1.3 on seed 10) with radii from 3.5 Bohr, 2.4 from 5, 1.0 from 5.5, 0.66 from 6 and 0.39 from
+6.5.  The sweep therefore draws that op's radii from [6.5, 9] Bohr (`ZERO_ATM_RADII_LO`), where the damping acts at contact distance;
+the CPU suite asserts the deviation below the bar for every seed.
+"""
+import functools
+
+import numpy as np
+import torch
+
+from tests import atm_reference as A
+from tests import d3_zero_reference as Z
+from tests import d4_atm_cases as K3
+from tests import d4_atm_reference as R3
+from tests import d4_cases as K
+from tests import d4_reference as R
+from tests import systems as S
+
+OPS = ("dftd3_atm", "dftd3_zero", "dftd3_zero_atm", "dftd4", "dftd4_atm")
+THREE_BODY = ("dftd3_atm", "dftd3_zero_atm", "dftd4_atm")
+D4_OPS = ("dftd4", "dftd4_atm")
+BASE = {"dftd3_atm": 7100, "dftd3_zero": 7200, "dftd3_zero_atm": 7300, "dftd4": 7400, "dftd4_atm": 7500}
+SEEDS = tuple(range(12))
+SIZES = (1, 2, 3, 7, 20, 45)
+SPECIES_COUNTS = (1, 3, 6, 7, 16, 17, 20)
+SPECIES_BY_SEED = (3, 6, 7, 16, 17, 20, 1, 7, 17, 6, 16, 3)  # every listed count at least once; the three-body thresholds twice
+Z_MAX = 24
+MARGIN = 1e-3
+WINDOW = 0.4
+ALPHAS = (13.5, 14.0, 15.2, 16.0)
+ZERO_ATM_RADII_LO = 6.5  # Bohr; see RADII in the module docstring
+DEFAULTS = {
+    "dftd3_atm": dict(a1=0.4, a2=4.0, alpha=16.0, k1=16.0, k3=-4.0),
+    "dftd3_zero": dict(rs6=1.217, s8=0.722, rs8=1.0, alpha=14.0, beta=0.0, k1=16.0, k3=-4.0, s6=1.0, s5_on=1e10, s5_off=1e10),
+    "dftd3_zero_atm": dict(rs9=4.0 / 3.0, alpha=16.0, k1=16.0, k3=-4.0),
+    "dftd4": dict(a1=0.4, a2=4.0, s8=0.8, s6=1.0, wf=6.0, ga=3.0, gc=2.0, k_cn=7.5, cn_cutoff=None),
+    "dftd4_atm": dict(a1=0.4, a2=4.0, alpha=16.0, wf=6.0, ga=3.0, gc=2.0, k_cn=7.5, cn_cutoff=None),
+}
+# the scalars a sweep seed draws, per op (the coverage test wants at least three distinct values of each over the twelve seeds)
+DRAWN = {
+    "dftd3_atm": ("a1", "a2", "alpha", "k1", "k3"),
+    "dftd3_zero": ("rs6", "s8", "rs8", "alpha", "beta", "k1", "k3", "s6"),
+    "dftd3_zero_atm": ("rs9", "alpha", "k1", "k3"),
+    "dftd4": ("a1", "a2", "s6", "s8", "wf", "ga", "gc", "k_cn"),
+    "dftd4_atm": ("a1", "a2", "alpha", "wf", "ga", "gc", "k_cn"),
+}
+TWO_VALUED = ("beta",)  # drawn from {0, 0.05}: two values, both required
+VARIANTS = {
+    "dftd4": (("s6", 0.8), ("s8", 0.0), ("a1", 0.52), ("a2", 5.0), ("wf", 4.5), ("ga", 2.4), ("gc", 1.6), ("k_cn", 6.5)),
+    "dftd4_atm": (("alpha", 14.0), ("alpha", 13.5), ("a1", 0.52), ("a2", 5.0), ("wf", 4.5), ("ga", 2.4), ("gc", 1.6), ("k_cn", 6.5)),
+    "dftd3_atm": (("k1", 15.0), ("k3", -3.5), ("a1", 0.52), ("a2", 5.0)),
+    "dftd3_zero_atm": (("k1", 15.0), ("k3", -3.5), ("rs9", 1.0)),
+}
+SEPARATION = 102.0  # a variant's float64 reference leaves the default's by this many bars: > 100 between the two kernel results, each within one
+LANE_RUNGS = ("n64", "n65", "n66", "n129")
+LANE_OPS = ("dftd4", "dftd3_zero")
+TILES = {"dftd4_atm": 288, "dftd3_atm": 320, "dftd3_zero_atm": 320}  # `D4_ATM_TILE` / `D3_ATM_TILE`; the CPU suite reads the #defines
+
+
+def tile_of(op):
+    """The LDS tile of the op's triple pass, from the library."""
+    if op == "dftd4_atm":
+        from nvalchemiops.interactions.dispersion.dftd4 import atm_tile
+    else:
+        from nvalchemiops.interactions.dispersion.dftd3 import atm_tile
+    return atm_tile()
+
+
+def tile_rungs(op, tile=None):
+    """Shell sizes of the block-trip / tile ladder: 255, 256, 257 (one stream trip short by one, exactly one, one plus one entry), then one
+    full tile, one tile plus one record and -- but for the zero-damping form, which runs the same triple pass -- exactly two tiles."""
+    tile = TILES[op] if tile is None else tile
+    return (255, 256, 257, tile, tile + 1, 2 * tile) if op != "dftd3_zero_atm" else (tile, tile + 1)
+
+
+# ---- cutoffs ------------------------------------------------------------------------------------------------------------------------------
+
+def image_distances(pos, cell, batch_idx, reach):
+    """Distances below `reach` of every pair of atom images (first atom in the home cell), all systems together; float64."""
+    pos = np.asarray(pos, np.float64)
+    bi = np.zeros(len(pos), np.int64) if batch_idx is None else np.asarray(batch_idx, np.int64)
+    out = []
+    for s in range(int(bi.max()) + 1 if len(pos) else 0):
+        sel = np.nonzero(bi == s)[0]
+        cs = None if cell is None else np.asarray(cell, np.float64).reshape(-1, 3, 3)[s]
+        i, j, sh = A.enumerate_pairs(pos[sel], cs, reach)
+        out.append(np.linalg.norm(A._np_vectors(pos[sel], cs, i, j, sh), axis=1))
+    return np.concatenate(out) if out else np.zeros(0)
+
+
+def place_cutoff(dist, target, window=WINDOW):
+    """The midpoint of the widest gap between the distances inside target +- window (the window's ends count as distances)."""
+    lo, hi = target - window, target + window
+    pts = np.concatenate([[lo], np.sort(dist[(dist > lo) & (dist < hi)]), [hi]])
+    k = int(np.argmax(np.diff(pts)))
+    return float(0.5 * (pts[k] + pts[k + 1]))
+
+
+def margin_of(dist, cutoff):
+    return float(np.abs(dist - cutoff).min()) if dist.size else float("inf")
+
+
+def row_counts(pos, cell, batch_idx, rc):
+    """Entries per row of the full list with cutoff rc (padding atoms have rows too: a neighbour search does not know the species)."""
+    pos = np.asarray(pos, np.float64)
+    bi = np.zeros(len(pos), np.int64) if batch_idx is None else np.asarray(batch_idx, np.int64)
+    counts = np.zeros(len(pos), np.int64)
+    for s in range(int(bi.max()) + 1):
+        sel = np.nonzero(bi == s)[0]
+        cs = None if cell is None else np.asarray(cell, np.float64).reshape(-1, 3, 3)[s]
+        i, _, _ = A.enumerate_pairs(pos[sel], cs, rc)
+        counts[sel] = np.bincount(i, minlength=len(sel))
+    return counts
+
+
+# ---- geometry of a sweep case ------------------------------------------------------------------------------------------------------------------
+
+_ORDINARY = {3: (3, 3, 3), 7: (3, 3, 3), 20: (3, 3, 3), 45: (3, 4, 4)}  # the first n sites are used
+_SHORT = {3: (3, 1, 1), 7: (4, 2, 1), 20: (5, 4, 1), 45: (9, 5, 1)}  # one lattice plane thick: a height of one spacing (<= 5.1 Bohr)
+
+
+def heights(cell):
+    return 1.0 / np.linalg.norm(np.linalg.inv(np.asarray(cell, np.float64).reshape(3, 3)), axis=0)
+
+
+def _sizes(g, need, single):
+    for _ in range(10_000):
+        sizes = [int(g.choice(SIZES)) for _ in range(1 if single else int(g.integers(1, 4)))]
+        if need <= sum(sizes) <= 70 and max(sizes) >= 7:
+            return sizes
+    raise AssertionError("no batch of sizes found")
+
+
+def _systems(g, seed, sizes, dtype, rc_target):
+    """(pos, cell or None, batch_idx or None, list-cutoff target, index of the short system or None)."""
+    periodic = seed % 3 != 2
+    short = seed in (1, 4, 7)  # three of the eight periodic seeds
+    short_sys = int(np.argmax(sizes)) if short else None
+    parts, cells = [], []
+    for k, n in enumerate(sizes):
+        sub = int(g.integers(1 << 30))
+        if not periodic:
+            parts.append(S.molecule(n, density=float(g.uniform(0.02, 0.03)), min_dist=2.0, seed=sub, dtype=dtype)[0])
+            continue
+        if n <= 2:  # no image within reach: a single atom is exactly zero, a pair has its one distance
+            p = np.array([[1.0, 2.0, 3.0], [1.0 + float(g.uniform(3.0, 5.0)), 2.5, 3.5]])[:n]
+            parts.append(p.astype(dtype))
+            cells.append((np.eye(3) * 2.5 * (rc_target + WINDOW)).astype(dtype))
+            continue
+        shape = (_SHORT if k == short_sys else _ORDINARY)[n]
+        p, c = A.lattice_box(shape, a=float(g.uniform(3.6, 4.6)), jitter=0.25, seed=sub, triclinic=bool(g.integers(2)), dtype=dtype)
+        parts.append(p[:n])
+        cells.append(c)
+    if periodic:  # ordinary cells stay at least half a Bohr above the list cutoff (window included)
+        for k, c in enumerate(cells):
+            if k != short_sys and sizes[k] > 2:
+                rc_target = min(rc_target, float(heights(c).min()) - 0.5 - WINDOW)
+    pos = np.concatenate(parts)
+    bi = None if len(sizes) == 1 else np.concatenate([np.full(n, k, np.int32) for k, n in enumerate(sizes)])
+    return pos, (np.stack(cells) if periodic else None), bi, rc_target, short_sys
+
+
+def _d3_tables(g, seed, dead):
+    t = {k: v.copy() for k, v in S.d3_test_tables(Z_MAX, seed=int(g.integers(1 << 30))).items()}
+    if seed % 5 == 1:  # reference CN that depends on the partner: the 25-term form (no factorised weights)
+        t["cn_ref"] *= (1.0 + 0.01 * np.arange(Z_MAX + 1, dtype=np.float32)[None, :, None, None])
+    if dead is not None:  # an element whose c6 block is zero: it is counted by its neighbours and is part of no pair energy
+        t["c6ab"][dead] = 0.0
+        t["c6ab"][:, dead] = 0.0
+    return t
+
+
+def _d4_tables(g, dead):
+    t = R.d4_test_tables(Z_MAX, seed=int(g.integers(1 << 30)))
+    if dead is not None:
+        t["n_ref"][dead] = 0
+        R.blank_unused(t)
+    return t
+
+
+def _species(g, op, seed, sizes):
+    """(z [N], kind of padding atom or None, its index or None, the element without references or None)."""
+    n = sum(sizes)
+    kind = (None, "z0", "beyond", "dead")[seed % 4]
+    count = SPECIES_BY_SEED[seed]
+    pool = g.permutation(np.arange(1, Z_MAX + 1))
+    dead = int(pool[-1]) if kind == "dead" else None
+    # a dead element is a species of its own for the D3 kernels (it takes part in the coordination numbers), padding for the D4 ones
+    regular = count - 1 if (dead is not None and op not in D4_OPS and count > 1) else count
+    sp = np.sort(pool[:regular])
+    start = int(np.sum(sizes[:int(np.argmax(sizes))]))
+    at = start + max(sizes) // 2 if kind is not None else None
+    z = np.zeros(n, np.int32)
+    others = np.array([i for i in range(n) if i != at])
+    z[others] = sp[g.permutation(len(others)) % regular]
+    if kind == "z0":
+        z[at] = 0
+    elif kind == "beyond":
+        z[at] = Z_MAX + 1 + int(g.integers(0, 3))
+    elif kind == "dead":
+        z[at] = dead
+    return z, kind, at, dead
+
+
+def _model(g, op, seed, rc):
+    a = int(g.integers(4))
+    draw = dict(a1=g.uniform(0.3, 0.6), a2=g.uniform(3.0, 5.5), s6=g.uniform(0.7, 1.0), s8=0.0 if seed == 5 else g.uniform(0.0, 2.5),
+                wf=g.uniform(4.0, 8.0), ga=g.uniform(2.0, 4.0), gc=g.uniform(1.5, 2.5), k_cn=g.uniform(6.0, 9.0), k1=g.uniform(14.0, 17.0),
+                k3=g.uniform(-5.0, -3.0), alpha=ALPHAS[seed] if seed < 4 else ALPHAS[a], rs6=g.uniform(0.8, 1.3),
+                rs8=g.uniform(0.8, 1.3), rs9=g.uniform(0.8, 1.3), beta=(0.0, 0.05)[seed % 2])
+    m = dict(DEFAULTS[op])
+    m.update({k: float(draw[k]) for k in DRAWN[op]})
+    if op == "dftd3_zero" and seed % 4 == 1:
+        m.update(s5_on=0.6 * rc, s5_off=0.95 * rc)
+    return m
+
+
+@functools.lru_cache(maxsize=None)
+def _sweep(op, seed):
+    g = np.random.default_rng(BASE[op] + seed)
+    dtype = np.float64 if seed % 4 == 3 else np.float32
+    sizes = _sizes(g, SPECIES_BY_SEED[seed] + 1, single=seed % 6 == 5)  # (one system: the unbatched search and call)
+    rc_target = float(g.uniform(7.5, 9.0))
+    pos, cell, bi, rc_target, short_sys = _systems(g, seed, sizes, dtype, rc_target)
+    z, kind, at, dead = _species(g, op, seed, sizes)
+    c = dict(op=op, pos=pos, z=z, cell=cell, batch_idx=bi, sizes=tuple(sizes), padding=kind, padding_atom=at, short_system=short_sys)
+    if op in D4_OPS:
+        c["tables"] = _d4_tables(g, dead)
+        c["q"] = g.uniform(-0.3, 0.3, len(pos)).astype(np.float32)
+    else:
+        c["tables"] = _d3_tables(g, seed, dead)
+        # three-body: radii from 6.5 Bohr (see RADII in the module docstring); two-body: the range of tests/test_d3_zero_gpu.py
+        c["r0ab"] = Z.synthetic_r0ab(Z_MAX + 1, seed=int(g.integers(1 << 30)), lo=ZERO_ATM_RADII_LO if op == "dftd3_zero_atm" else 3.5)
+    dist = image_distances(pos, cell, bi, rc_target + WINDOW + 0.1)
+    c["rc"] = place_cutoff(dist, rc_target)
+    c["margins"] = {"list": margin_of(dist, c["rc"])}
+    if op in THREE_BODY:
+        c["rc3"] = place_cutoff(dist, float(g.uniform(5.6, min(7.0, rc_target - 1.0))))
+        c["margins"]["three_body"] = margin_of(dist, c["rc3"])
+    c["model"] = _model(g, op, seed, c["rc"])
+    if op in D4_OPS and seed % 3 == 1:
+        c["model"]["cn_cutoff"] = place_cutoff(dist, float(g.uniform(4.8, 5.6)))
+        c["margins"]["cn"] = margin_of(dist, c["model"]["cn_cutoff"])
+    c["counts"] = row_counts(pos, cell, bi, c["rc"])
+    c["widest"] = int(c["counts"].max())
+    c["lists"] = dict(int64=seed % 4 == 2, pad=int(2 * g.integers(0, 5) + 1), foreign_fill=seed % 3 == 0, permuted=seed % 2 == 1)
+    return c
+
+
+# ---- ladders ------------------------------------------------------------------------------------------------------------------------------------
+
+def _fixed_tables(op):
+    c = {}
+    if op in D4_OPS:
+        c["tables"] = R.d4_test_tables(17)
+    else:
+        c["tables"] = S.d3_test_tables(17)
+        c["r0ab"] = Z.synthetic_r0ab(18)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def _ladder(op, name):
+    plain = dict(int64=False, pad=0, foreign_fill=False, permuted=False)
+    if name.startswith("n"):  # lane trips: a free cluster, every row holds the n - 1 others; the matrix is exactly that wide
+        n = int(name[1:])
+        pos = S.molecule(n, density=0.03, min_dist=2.0, seed=400 + n)[0]
+        z = np.random.default_rng(400 + n).choice(np.array((1, 6, 8, 17), np.int32), n)
+        dist = image_distances(pos, None, None, 1e9)
+        rc = 2.0 * float(dist.max())
+        c = dict(op=op, pos=pos, z=z, cell=None, batch_idx=None, rc=rc, margins={"list": margin_of(dist, rc)}, model=dict(DEFAULTS[op]), widest=n - 1, counts=np.full(n, n - 1),
+                 lists=plain, **_fixed_tables(op))
+        if op == "dftd4":
+            c["q"] = np.random.default_rng(477 + n).uniform(-0.3, 0.3, n).astype(np.float32)
+        return c
+    m = int(name[1:])  # block trips and LDS tiles: one row of m kept entries, every other row below one tile
+    # The cutoff sits in a window from half a Bohr above the shell radius (every centre-shell distance is below radius + 0.35) to two
+    # Bohr above it, far below the diameter.  Shell-shell distances near the radius R come m^2 / (4 R) to the Bohr: at R = 19 the widest gap
+    # of the two-tile shells (576, 640) leaves a margin of 0.7e-3 - 1.5e-3 over eight jitter seeds, so those two sit at R = 40.
+    radius = 19.0 if m < 500 else 40.0
+    pos = A.centre_and_shell(m, radius=radius)
+    z = np.random.default_rng(29).choice(np.array((1, 6, 8), np.int32), len(pos))
+    z[0] = 17  # the heaviest element of the tables at the centre: the triples of the long row weigh in the totals (C9 grows with Z)
+    dist = image_distances(pos, None, None, 1e9)
+    rc3 = place_cutoff(dist, radius + 1.25, 0.75)
+    rc = 2.0 * float(dist.max())
+    return dict(op=op, pos=pos, z=z, cell=None, batch_idx=None, rc=rc, rc3=rc3, margins={"list": margin_of(dist, rc), "three_body": margin_of(dist, rc3)},
+                model=dict(DEFAULTS[op]), widest=m, counts=np.full(m + 1, m), lists=plain, **_fixed_tables(op))
+
+
+# ---- variants -----------------------------------------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def _variant_base(op):
+    """`triclinic_f32` of tests/d4_cases.py for the D4 ops, the triclinic periodic box of tests/test_d3_atm_gpu.py for the D3 ones; the
+    cutoffs are the gap-rule values next to the ones those tests use (9 / 7 and 10 / 8.5)."""
+    if op in D4_OPS:
+        b = K.case("triclinic_f32")
+        c = dict(pos=b["pos"], z=b["z"], q=b["q"], tables=b["tables"], cell=np.asarray(b["cell"]).reshape(1, 3, 3))
+        rc_t, rc3_t = 9.0, 7.0
+    else:
+        pos, cell = A.lattice_box((5, 5, 6), seed=7, triclinic=True)
+        z = np.random.default_rng(7).choice(np.array((1, 6, 8, 17), np.int32), len(pos))
+        c = dict(pos=pos, z=z, cell=cell.reshape(1, 3, 3), **_fixed_tables(op))
+        rc_t, rc3_t = 10.0, 8.5
+    dist = image_distances(c["pos"], c["cell"], None, rc_t + WINDOW + 0.1)
+    c.update(op=op, batch_idx=None, rc=place_cutoff(dist, rc_t), lists=dict(int64=False, pad=8, foreign_fill=False, permuted=False))
+    c["margins"] = {"list": margin_of(dist, c["rc"])}
+    if op in THREE_BODY:
+        c["rc3"] = place_cutoff(dist, rc3_t)
+        c["margins"]["three_body"] = margin_of(dist, c["rc3"])
+    c["counts"] = row_counts(c["pos"], c["cell"], None, c["rc"])
+    c["widest"] = int(c["counts"].max())
+    return c
+
+
+def variant_names(op):
+    return tuple(f"{k}={v:g}" for k, v in VARIANTS[op])
+
+
+@functools.lru_cache(maxsize=None)
+def _variant(op, name):
+    c = dict(_variant_base(op))
+    c["model"] = dict(DEFAULTS[op])
+    if name != "default":
+        k, v = name.split("=")
+        assert k in c["model"], name
+        c["model"][k] = float(v)
+    return c
+
+
+# ---- references ---------------------------------------------------------------------------------------------------------------------------------
+
+def _geometry(kind, op, key):
+    return {"sweep": _sweep, "ladder": _ladder, "variant": _variant}[kind](op, key)
+
+
+def _zero_two_body(c, m, work_dtype):
+    """`d3_zero_reference.reference`, system by system: a system of one atom has no pair (the restatement's C6 interpolation wants at
+    least one), and is zero throughout."""
+    n = len(c["pos"])
+    bi = np.zeros(n, np.int64) if c["batch_idx"] is None else np.asarray(c["batch_idx"], np.int64)
+    nsys = int(bi.max()) + 1
+    out = dict(energy=np.zeros(nsys), forces=np.zeros((n, 3)), cn=np.zeros(n), virial=None if c["cell"] is None else np.zeros((nsys, 3, 3)),
+               triples=0)
+    for s in range(nsys):
+        sel = np.nonzero(bi == s)[0]
+        if len(sel) < 2:
+            continue
+        r = Z.reference(c["pos"][sel], c["z"][sel], c["tables"], c["r0ab"], m["rs6"], m["s8"], c["rc"], rs8=m["rs8"], alpha=m["alpha"], beta=m["beta"],
+                        k1=m["k1"], k3=m["k3"], s6=m["s6"], s5_on=m["s5_on"], s5_off=m["s5_off"], cell=None if c["cell"] is None else c["cell"][s],
+                        work_dtype=work_dtype)
+        out["energy"][s], out["forces"][sel], out["cn"][sel] = r["energy"][0], r["forces"], r["cn"]
+        if out["virial"] is not None:
+            out["virial"][s] = r["virial"][0]
+    return out
+
+
+def evaluate(c, work_dtype=torch.float64, s9=1.0, **override):
+    """The op's restatement on case c (model scalars overridden by `override`)."""
+    op, m = c["op"], dict(c["model"], **override)
+    common = dict(cell=c["cell"], batch_idx=c["batch_idx"], work_dtype=work_dtype)
+    pos, z, t = c["pos"], c["z"], c["tables"]
+    if op == "dftd3_atm":
+        return A.reference(pos, z, t, m["a1"], m["a2"], c["rc"], three_body_cutoff=c["rc3"], s9=s9, alpha=m["alpha"], k1=m["k1"], k3=m["k3"],
+                           term="atm", **common)
+    if op == "dftd3_zero":
+        return _zero_two_body(c, m, work_dtype)
+    if op == "dftd3_zero_atm":
+        return Z.reference(pos, z, t, c["r0ab"], None, None, c["rc"], three_body_cutoff=c["rc3"], rs9=m["rs9"], s9=s9, alpha=m["alpha"], k1=m["k1"],
+                           k3=m["k3"], term="atm", **common)
+    if op == "dftd4":
+        return R.reference(pos, z, c["q"], t, m["a1"], m["a2"], m["s8"], c["rc"], s6=m["s6"], cn_cutoff=m["cn_cutoff"], wf=m["wf"], ga=m["ga"],
+                           gc=m["gc"], k_cn=m["k_cn"], **common)
+    if op == "dftd4_atm":
+        return R3.reference(pos, z, t, m["a1"], m["a2"], c["rc"], three_body_cutoff=c["rc3"], s9=s9, alpha=m["alpha"], cn_cutoff=m["cn_cutoff"],
+                            wf=m["wf"], ga=m["ga"], gc=m["gc"], k_cn=m["k_cn"], **common)
+    raise ValueError(op)
+
+
+@functools.lru_cache(maxsize=None)
+def unit_references(kind, op, key):
+    """(float64, float32-arithmetic) restatement at s9 = 1."""
+    c = _geometry(kind, op, key)
+    return evaluate(c), evaluate(c, work_dtype=torch.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def s9_of(kind, op, key):
+    """1 for the two-body ops.  Three-body: the smallest power of ten that lifts the case (`d4_atm_cases.lifted`); a variant takes the s9 of
+    its default, so that the two calls differ in the one scalar only."""
+    if op not in THREE_BODY:
+        return 1.0
+    if kind == "variant" and key != "default":
+        return s9_of(kind, op, "default")
+    r64, _ = unit_references(kind, op, key)
+    s9 = 1.0
+    while not K3.lifted(r64, s9):
+        s9 *= 10.0
+        assert s9 <= 1e12, (kind, op, key)
+    return s9
+
+
+@functools.lru_cache(maxsize=None)
+def references(kind, op, key):
+    r64, r32 = unit_references(kind, op, key)
+    s9 = s9_of(kind, op, key)
+    return K3._scaled(r64, s9), K3._scaled(r32, s9)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(kind, op, key):
+    c = dict(_geometry(kind, op, key))
+    if op in THREE_BODY:
+        c["s9"] = s9_of(kind, op, key)
+    return c
+
+
+def case(op, seed):
+    return _charge_sweep(op, seed) if op in CHARGE_OPS else _case("sweep", op, seed)
+
+
+def ladder_case(op, name):
+    return _charge_ladder(name) if op in CHARGE_OPS else _case("ladder", op, name)
+
+
+def variant_case(op, name):
+    return _case("variant", op, name)
+
+
+# ---- bars ----------------------------------------------------------------------------------------------------------------------------------------
+
+EXTRA = {"energy": 0.0, "forces": 5e-6, "cn": 0.0, "charge_grad": 5e-6, "virial": 2e-7}  # as the ops' GPU modules have them
+OUTPUTS = {"dftd3_atm": ("energy", "forces", "virial"), "dftd3_zero": ("energy", "forces", "cn", "virial"),
+           "dftd3_zero_atm": ("energy", "forces", "virial"), "dftd4": ("energy", "forces", "cn", "charge_grad", "virial"),
+           "dftd4_atm": ("energy", "forces", "virial")}
+
+
+def d3_bar(ref, key):
+    """`dftd3`'s elementwise bar for a quantity with reference values `ref`."""
+    return 1e-6 + 1e-6 * np.abs(ref) + EXTRA[key] * (np.abs(ref).max() if ref.size else 0.0)
+
+
+def bar(r64, r32, key):
+    """The elementwise bar of the ops' GPU modules (`_judge` / `_bars`): 4 x the larger of the restatement's float32 deviation on this case
+    and `dftd3`'s bar."""
+    dev32 = np.abs(r32[key] - r64[key]).max() if r64[key].size else 0.0
+    return 4.0 * np.maximum(dev32, d3_bar(r64[key], key))
+
+
+def separation(op, name):
+    """By how many bars the variant's float64 reference leaves the default's, per output, largest first."""
+    r64, r32 = references("variant", op, name)
+    d64, _ = references("variant", op, "default")
+    out = {k: float((np.abs(r64[k] - d64[k]) / bar(r64, r32, k)).max()) for k in OUTPUTS[op] if r64[k] is not None}
+    return dict(sorted(out.items(), key=lambda kv: -kv[1]))
+
+
+# ---- Gaussian charges and charge equilibration ----------------------------------------------------------------------------------------------------
+# Inputs only: the references of these two ops are evaluated by the GPU modules on the entries actually stored (tests/gaussian_reference.py,
+# tests/qeq_reference.py), as tests/test_gaussian_charges_gpu.py and tests/test_qeq_gpu.py do, so no cutoff needs a margin here.  The recipe
+# is `_system` / `_abi_case` of those modules: uniform positions in a (triclinic or cubic) cell, sigma in [0.3, 0.8] with some exact zeros,
+# brute-force entries, a matrix widest row + an odd pad wide whose padding columns hold the mask value, -1 and n + 7, one emptied row.
+
+CHARGE_OPS = ("gaussian_charge_correction", "charge_equilibration")
+BASE.update(gaussian_charge_correction=7600, charge_equilibration=7700)
+CHARGE_SIZES = (1, 9, 60, 150)
+_BOX = {60: 9.0, 150: 12.0}  # 1 and 9 atoms: box 5 (shorter than the cutoff: own images) or 14 (a single atom then has no entry at all)
+UNROLLED_WIDTHS = (255, 256, 257, 335)
+COMPUTE_FLAGS = ("compute_forces", "compute_charge_gradients", "compute_sigma_gradients", "compute_virial")
+
+
+def charge_cell(box, triclinic=True):
+    return np.array([[box, 0, 0], [0.2 * box, 0.9 * box, 0], [0.1 * box, -0.15 * box, 1.1 * box]]) if triclinic else np.eye(3) * box
+
+
+def brute_force(pos, cell, cutoff, images):
+    """Every (i, j, S) with 1e-12 < |r_j - r_i + S . cell| < cutoff, S in [-images, images]^3, sorted by row: a full list (numpy; the
+    recipe of `gaussian_reference.brute_force_entries`).  `cell` None: free space."""
+    rng = np.arange(-images, images + 1) if cell is not None else np.zeros(1, np.int64)
+    S = np.array([(a, b, c) for a in rng for b in rng for c in rng])
+    d = pos[None, :, None, :] - pos[:, None, None, :] + (S @ (np.eye(3) if cell is None else cell))[None, None, :, :]
+    r = np.linalg.norm(d, axis=-1)
+    i, j, k = np.nonzero((r < cutoff) & (r > 1e-12))
+    return i, j, S[k]
+
+
+def charge_entries(c, s, images=None):
+    """The entries of system s of a charge case, with the system's own atom numbering."""
+    sel = np.nonzero(c["batch_idx"] == s)[0]
+    cell = None if c["cells"] is None else c["cells"][s]
+    return brute_force(c["pos"][sel], cell, c["cutoff"], c["images"][s] if images is None else images)
+
+
+def _with_entries(c):
+    ii, jj, ss, off = [], [], [], 0
+    for s in range(int(c["batch_idx"].max()) + 1):
+        i, j, S = charge_entries(c, s)
+        ii.append(i + off); jj.append(j + off); ss.append(S)
+        off += int((c["batch_idx"] == s).sum())
+    c["entries"] = (np.concatenate(ii), np.concatenate(jj), np.concatenate(ss))
+    c["widest"] = int(np.bincount(c["entries"][0], minlength=len(c["pos"])).max()) if len(c["entries"][0]) else 0
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def _charge_sweep(op, seed):
+    g = np.random.default_rng(BASE[op] + seed)
+    own = seed % 3 == 0  # the small systems sit in a cell shorter than the cutoff
+    while True:
+        sizes = tuple(int(v) for v in g.choice(CHARGE_SIZES, int(g.integers(1, 4))))
+        if max(sizes) >= 9:
+            break
+    cutoff = float(g.uniform(6.0, 7.0))
+    pos, cells, images = [], [], []
+    for n in sizes:
+        box = _BOX.get(n, 5.0 if own else 14.0)
+        cell = charge_cell(box, bool(g.integers(2)))
+        pos.append(g.uniform(0, 1, (n, 3)) @ cell)
+        cells.append(cell)
+        images.append(2 if box < cutoff else 1)
+    ntot = sum(sizes)
+    bi = np.concatenate([np.full(n, k, np.int32) for k, n in enumerate(sizes)])
+    q = g.normal(size=ntot)
+    neutral = seed % 2 == 1
+    if neutral:
+        for k in range(len(sizes)):
+            q[bi == k] -= q[bi == k].mean()
+    sigma = g.uniform(0.3, 0.8, ntot)
+    sigma[g.choice(ntot, min(3, max(1, ntot // 20)), replace=False)] = 0.0
+    big = int(np.argmax(sizes))
+    while True:  # (the clusters of the seed's solve; a lone atom carries its total charge and needs no solve)
+        clusters = tuple(int(v) for v in g.choice(CHARGE_SIZES, int(g.integers(1, 4))))
+        if max(clusters) >= 9:
+            break
+    c = dict(op=op, dtype="float64" if seed % 2 == 0 else "float32", sizes=sizes, pos=np.concatenate(pos), cells=np.stack(cells), batch_idx=bi,
+             cutoff=cutoff, images=tuple(images), q=q, neutral=neutral, sigma=sigma, pad=int(2 * g.integers(1, 5) + 1),
+             emptied_row=int(np.sum(sizes[:big])) + sizes[big] // 2, hard=g.uniform(0.5, 1.5, ntot), x=g.normal(size=ntot), y_in=g.normal(size=ntot),
+             alpha=g.uniform(0.3, 0.45, len(sizes)), flags={k: bool(g.integers(2)) for k in COMPUTE_FLAGS}, self_energy=bool(g.integers(2)),
+             background=bool(g.integers(2)), cluster_sizes=clusters,
+             cluster_seed=int(g.integers(1 << 30)), cluster_total=g.uniform(-1.5, 1.5, 3))
+    _with_entries(c)
+    i, j, S = c["entries"]
+    own_image = (i == j) & (np.abs(S).sum(1) > 0)
+    c["self_images"] = frozenset(int(v) for v in np.unique(bi[i[own_image]]))
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def _charge_ladder(name):
+    """Lane trips: a free cluster of n atoms without a cell, every pair stored: rows of n - 1 entries in a matrix exactly that wide."""
+    n = int(name[1:])
+    g = np.random.default_rng(7800 + n)
+    pos = S.molecule(n, density=0.05, min_dist=1.0, seed=500 + n, dtype=np.float64)[0]
+    sigma = g.uniform(0.3, 0.8, n)
+    sigma[g.choice(n, 2, replace=False)] = 0.0
+    c = dict(op="charges", dtype="float64", sizes=(n,), pos=pos, cells=None, batch_idx=np.zeros(n, np.int32), cutoff=1e9, images=(0,), q=g.normal(size=n),
+             sigma=sigma, pad=0, emptied_row=None, hard=g.uniform(0.5, 1.5, n), x=g.normal(size=n), y_in=g.normal(size=n), alpha=None)
+    return _with_entries(c)
+
+
+@functools.lru_cache(maxsize=None)
+def unrolled_case():
+    """`box150` of tests/test_qeq_gpu.py (the same draws) at cutoff 9.5: rows of about 300 entries, more than the 256 one pass of
+    `qeq_apply_kernel`'s four unrolled trips of 64 takes."""
+    g = np.random.default_rng(11)
+    n = 150
+    cell = charge_cell(12.0)
+    pos = g.uniform(0, 1, (n, 3)) @ cell
+    sigma = g.uniform(0.3, 0.8, n)
+    sigma[g.choice(n, 3, replace=False)] = 0.0
+    c = dict(op="charge_equilibration", dtype="float64", sizes=(n,), pos=pos, cells=cell[None], batch_idx=np.zeros(n, np.int32), cutoff=9.5, images=(1,),
+             sigma=sigma, pad=0, emptied_row=None, hard=g.uniform(0.5, 1.5, n), x=g.normal(size=n), y_in=g.normal(size=n), alpha=np.array([0.35]))
+    return _with_entries(c)
