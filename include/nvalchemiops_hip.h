@@ -481,6 +481,60 @@ int mi_gaussian_charges(const void* positions, const void* charges, const void* 
                         void* forces, double* charge_grads, double* sigma_grads, double* system_partial, void* scratch, size_t scratch_bytes,
                         void* stream);
 
+/* Point-dipole Ewald sum (csrc/dipole.hip; driver: nvalchemiops/interactions/electrostatics/dipole.py): what point dipoles mu_i (fixed in the
+ * laboratory frame) add to the periodic energy of point charges q_i -- the charge-charge part is NOT included, the result is added to an Ewald /
+ * PME energy.  Gaussian units, tin-foil boundary.  All arithmetic is fp64; only the pair vector and r^2 are formed in the positions dtype.  No
+ * floating-point atomics, plain stores, fixed summation orders: every output is bit-reproducible.
+ *
+ * mi_ewald_dipole_real: over the stored entries (i, j, S) of a FULL (symmetric) list -- padded matrix (neighbor_ptr == NULL; entries equal to
+ * mask_value or outside [0, n_atoms) are padding) or CSR -- with R = r_j - r_i + S . cell, r = |R|, a = alpha[system of i],
+ *     B0 = erfc(a r)/r,  B_n = [(2n - 1) B_{n-1} + (2 a^2)^n / (a sqrt(pi)) exp(-a^2 r^2)] / r^2,  c_i = mu_i.R, c_j = mu_j.R, d = mu_i.mu_j,
+ *     U = B1 (q_j c_i - q_i c_j + d) - B2 c_i c_j,        energies[i] = 1/2 sum_row U        (entries with r <= 1e-8 skipped, nothing else)
+ * weights [n_atoms] float64 or NULL (all ones): entry weight w = (g_i + g_j) / 2 -- the outputs are then the derivatives of
+ * L = sum_i g_i energies[i]:
+ *   MI_DP_FORCES       forces [n_atoms][3] (positions dtype) = -dL/dr_i  = sum_row w dU/dR,
+ *                      dU/dR = (-B2 (q_j c_i - q_i c_j + d) + B3 c_i c_j) R + (B1 q_j - B2 c_j) mu_i - (B1 q_i + B2 c_i) mu_j
+ *   MI_DP_CHARGE_GRAD  charge_grads [n_atoms] float64        = dL/dq_i   = -sum_row w B1 c_j
+ *   MI_DP_DIPOLE_GRAD  dipole_grads [n_atoms][3] float64     = dL/dmu_i  = sum_row w (B1 (q_j R + mu_j) - B2 c_j R)
+ *   MI_DP_VIRIAL       virial_partial [n_systems][mi_ewald_dipole_blocks()][9] float64 = block partials of W[a][b] = -1/2 sum_entries w (dU/dR)_a R_b,
+ *                      row-major and NOT symmetric (dU/dR is not along R); the caller sums the block dimension.  Needs unit_shifts.
+ * energies may be NULL (adjoint use).  unit_shifts NULL: all zero.  A half list is not detected.  n_systems > 1 needs batch_idx.
+ * scratch: mi_ewald_dipole_real_scratch_bytes(n_atoms, dtype) bytes ({x, y, z, q, mu} records + per-row virials), contents undefined.
+ *
+ * mi_ewald_dipole_structure_factors: table [n_systems][n_k][8] float64 = {Re S_q, Im S_q, Re M_x, Im M_x, Re M_y, Im M_y, Re M_z, Im M_z},
+ * S_q = sum_j g_j q_j exp(i k.r_j), M = sum_j g_j mu_j exp(i k.r_j) over the atoms [system_ptr[s], system_ptr[s + 1]) of each system
+ * (system_ptr NULL for one system), g = weights or 1 (NULL).  UNSCALED: the consumers apply G_k = (8 pi / V) exp(-k^2 / 4 a^2) / k^2
+ * (half-space k set; k^2 < 1e-10: 0).  k_vectors [n_systems][n_k][3] in the positions dtype; every entry of the table is written.
+ *
+ * mi_ewald_dipole_recip_gather: with S = S_q + i k.M and A_i = (q_i - i k.mu_i) exp(-i k.r_i),
+ *     energies[i] = 1/2 sum_k G_k { Re[A_i S] - q_i Re[exp(-i k.r_i) S_q] } - 2 a^3 / (3 sqrt(pi)) |mu_i|^2     (dipolar self term included)
+ * and forces (positions dtype), charge_grads, dipole_grads [n_atoms][3] (float64) = -d/dr_i, d/dq_i, d/dmu_i of sum_i energies[i]; any output
+ * may be NULL.  Adjoint form: table_g (the table summed with weights g) and weights together give the same derivatives of
+ * L = sum_i g_i energies[i], i.e. 1/2 sum_k G_k Re[dA_i/dtheta (g_i S + S^g)] minus the charge part, and the self term times g_i.
+ *
+ * mi_ewald_dipole_recip_virial: virial [n_systems][9] float64, row-major, -dE/d(strain) of the reciprocal sum under x -> (I + eps) x with the
+ * k set following the cell and the dipoles fixed (d(k.mu)/d eps_ab = -k_a mu_b):
+ *     W[a][b] = sum_k e_k (delta_ab - 2 (1/k^2 + 1/(4 a^2)) k_a k_b) + G_k k_a (Im S Re M_b - Re S Im M_b),  e_k = 1/2 G_k (|S|^2 - |S_q|^2). */
+#define MI_DP_FORCES 1
+#define MI_DP_CHARGE_GRAD 2
+#define MI_DP_DIPOLE_GRAD 4
+#define MI_DP_VIRIAL 8
+size_t mi_ewald_dipole_real_scratch_bytes(int n_atoms, int dtype);
+int mi_ewald_dipole_blocks(void);
+int mi_ewald_dipole_real(const void* positions, const void* charges, const void* dipoles, const void* cell /*[n_systems,3,3]*/,
+                         const void* alpha /*[n_systems]*/, const int32_t* batch_idx, const double* weights, int n_atoms, int n_systems, int dtype,
+                         const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors, int mask_value, int flags,
+                         double* energies, void* forces, double* charge_grads, double* dipole_grads, double* virial_partial, void* scratch,
+                         size_t scratch_bytes, void* stream);
+int mi_ewald_dipole_structure_factors(const void* positions, const void* charges, const void* dipoles, const double* weights, const void* k_vectors,
+                                      const int32_t* system_ptr, int n_atoms, int n_systems, int n_k, int dtype, double* table, void* stream);
+int mi_ewald_dipole_recip_gather(const void* positions, const void* charges, const void* dipoles, const void* k_vectors, const void* cell,
+                                 const void* alpha, const int32_t* batch_idx, const double* table, const double* table_g, const double* weights,
+                                 int n_atoms, int n_systems, int n_k, int dtype, double* energies, void* forces, double* charge_grads,
+                                 double* dipole_grads, void* stream);
+int mi_ewald_dipole_recip_virial(const double* table, const void* k_vectors, const void* cell, const void* alpha, int n_systems, int n_k, int dtype,
+                                 double* virial, void* stream);
+
 /* Charge equilibration (csrc/qeq.hip; driver: nvalchemiops/interactions/electrostatics/qeq.py): the real-space Hessian of the Gaussian-charge
  * electrostatic energy as a stored sparse operator over the caller's FULL list, its product, and the vector kernels of a batched projected
  * conjugate-gradient solve of  min_q sum chi_i q_i + 1/2 sum J_i q_i^2 + E_el(q),  sum_{i in s} q_i = Q_s.  All arithmetic is fp64; only the

@@ -32,6 +32,7 @@ SOURCES = {
     "d3.hip": ["-fno-hip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize"] + os.environ.get("MI_D3_EXTRA_FLAGS", "").split(),
     "ewald.hip": os.environ.get("MI_EWALD_EXTRA_FLAGS", "").split(),
     "gaussian.hip": [],  # Gaussian-smeared charge correction (mi_gaussian_charges): fp64 pair math with libm erfc
+    "dipole.hip": [],  # point-dipole Ewald sum (mi_ewald_dipole_*): fp64 pair math with libm erfc / exp, fp64 sincos phases
     "qeq.hip": [],  # charge equilibration (mi_qeq_*): stored pair operator, its product and the CG vector kernels, all fp64
     "d4.hip": [],  # DFT-D4 two-body dispersion (mi_d4): fp32 pair math with IEEE divide / sqrt and libm erff / expf, fp64 sums
     "pme.hip": os.environ.get("MI_PME_EXTRA_FLAGS", "").split(),

@@ -150,6 +150,19 @@ def lib() -> ctypes.CDLL:
         for name in ("mi_gaussian_charges_blocks", "mi_gaussian_charges_row_words"):
             getattr(L, name).restype = i
             getattr(L, name).argtypes = []
+        # point-dipole Ewald sum (nvalchemiops/interactions/electrostatics/dipole.py)
+        L.mi_ewald_dipole_real.restype = i
+        L.mi_ewald_dipole_real.argtypes = [vp] * 7 + [i, i, i, vp, vp, vp, i, i, i] + [vp] * 6 + [sz, vp]
+        L.mi_ewald_dipole_structure_factors.restype = i
+        L.mi_ewald_dipole_structure_factors.argtypes = [vp] * 6 + [i, i, i, i, vp, vp]
+        L.mi_ewald_dipole_recip_gather.restype = i
+        L.mi_ewald_dipole_recip_gather.argtypes = [vp] * 10 + [i, i, i, i] + [vp] * 5
+        L.mi_ewald_dipole_recip_virial.restype = i
+        L.mi_ewald_dipole_recip_virial.argtypes = [vp, vp, vp, vp, i, i, i, vp, vp]
+        L.mi_ewald_dipole_real_scratch_bytes.restype = sz
+        L.mi_ewald_dipole_real_scratch_bytes.argtypes = [i, i]
+        L.mi_ewald_dipole_blocks.restype = i
+        L.mi_ewald_dipole_blocks.argtypes = []
         # charge equilibration (nvalchemiops/interactions/electrostatics/qeq.py)
         L.mi_qeq_pair_coefficients.restype = i
         L.mi_qeq_pair_coefficients.argtypes = [vp] * 6 + [i, i, i, vp, vp, vp, i, i, vp, vp, vp, vp]
@@ -182,6 +195,12 @@ def fold_virial(partial: torch.Tensor) -> torch.Tensor:
     """[B, blocks, 6] float64 block partials {xx, yy, zz, xy, xz, yz} of a virial entry point -> symmetric [B, 3, 3] float64 (fixed-order sum)."""
     xx, yy, zz, xy, xz, yz = partial.sum(1).unbind(-1)
     return torch.stack((xx, xy, xz, xy, yy, yz, xz, yz, zz), dim=-1).reshape(-1, 3, 3)
+
+
+def fold_virial9(partial: torch.Tensor) -> torch.Tensor:
+    """[B, blocks, 9] float64 block partials (row-major, all nine components) -> [B, 3, 3] float64 (fixed-order sum).  For virials that are not
+    symmetric: dipoles fixed in the laboratory frame make dU/dR point away from R."""
+    return partial.sum(1).reshape(-1, 3, 3)
 
 
 def check(rc: int, what: str) -> None:

@@ -1583,7 +1583,144 @@ def _gaussian_backward(ctx, g_e, *g_explicit):
 gaussian_charge_correction_op = _op("_gaussian_charge_correction", _gaussian_fwd, _gaussian_fwd_fake, _gaussian_backward, _gaussian_setup)
 
 
-__all__ = ["gaussian_charge_correction_op", "gaussian_bwd_op", "spline_spread_op", "batch_spline_spread_op", "spline_gather_op", "batch_spline_gather_op", "spline_gather_vec3_op",
+# =====================================================================================================================================
+# point-dipole Ewald sum: one op per half (real / reciprocal space), optional tensors as for the Gaussian correction
+# =====================================================================================================================================
+# Outputs are always the five of the public functions; the ones not asked for are empty [0] tensors.  The energies are differentiable w.r.t.
+# positions, charges and dipoles: the backward ops run the forward kernels with the incoming gradient as per-atom weights.  Cell, alpha and
+# k-vector gradients are out of scope and refused (never a silent zero): the virial is the strain derivative.
+_DP_OUTPUTS = ("energies", "forces", "charge_gradients", "dipole_gradients", "virial")
+_DP_NO_GRAD = ("{op}: gradients w.r.t. {what} are not provided by the point-dipole Ewald term (out of scope); use compute_virial for the "
+               "strain derivative.")
+
+
+def _dp_fake(positions, nsys, forces, cgrads, dgrads, virial):
+    n = positions.shape[0]
+    empty = lambda: positions.new_empty((0,))  # noqa: E731
+    return (positions.new_empty((n,)), positions.new_empty((n, 3)) if forces else empty(), positions.new_empty((n,)) if cgrads else empty(),
+            positions.new_empty((n, 3)) if dgrads else empty(), positions.new_empty((nsys, 3, 3)) if virial else empty())
+
+
+def _dp_bwd_fake(positions):
+    n, f64 = positions.shape[0], dict(dtype=torch.float64)
+    return positions.new_empty((n, 3), **f64), positions.new_empty((n,), **f64), positions.new_empty((n, 3), **f64)
+
+
+def _dp_refuse_second_order(name):
+    def backward(ctx, *grads):
+        raise NotImplementedError(_SECOND_ORDER.format(op=name, what="gradient"))
+
+    return backward
+
+
+def _dp_backward(name, bwd_op, refused):
+    """Autograd of a dipole op: `refused` maps the positions of inputs without an adjoint (cell, alpha, k_vectors) to their names."""
+    def backward(ctx, g_e, *g_explicit):
+        for what, g in zip(_DP_OUTPUTS[1:], g_explicit):
+            if g is not None:
+                raise NotImplementedError(_SECOND_ORDER.format(op=name, what=what))
+        need = ctx.needs_input_grad
+        for k, what in refused.items():
+            if need[k]:
+                raise NotImplementedError(_DP_NO_GRAD.format(op=name, what=what))
+        if g_e is None:
+            return (None,) * len(need)
+        saved = ctx.saved_tensors
+        positions, charges, dipoles = saved[:3]
+        gpos, gq, gmu = bwd_op(*saved, *ctx.extra, g_e)
+        return (gpos.to(positions.dtype) if need[0] else None, gq.to(charges.dtype) if need[1] else None,
+                gmu.to(dipoles.dtype) if need[2] else None) + (None,) * (len(need) - 3)
+
+    return backward
+
+
+def _dp_real_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, cell: Tensor, alpha: Tensor, batch_idx: Optional[Tensor],
+                 neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
+                 neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int, compute_forces: bool,
+                 compute_charge_gradients: bool, compute_dipole_gradients: bool, compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from nvalchemiops.interactions.electrostatics.dipole import _real_forward
+
+    out = _real_forward(positions, charges, dipoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                        neighbor_matrix_shifts, int(mask_value), compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
+    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
+
+
+def _dp_real_fwd_fake(positions, charges, dipoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                      neighbor_matrix_shifts, mask_value, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial):
+    nsys = cell.reshape(-1, 3, 3).shape[0] if batch_idx is not None else 1
+    return _dp_fake(positions, nsys, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
+
+
+def _dp_real_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, cell: Tensor, alpha: Tensor, batch_idx: Optional[Tensor],
+                 neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
+                 neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int,
+                 grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor]:
+    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles) for L = sum_i g_i E_i."""
+    from nvalchemiops.interactions.electrostatics.dipole import _real_adjoint
+
+    return _real_adjoint(positions, charges, dipoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                         neighbor_matrix_shifts, int(mask_value), grad_energies)
+
+
+ewald_dipole_real_bwd_op = torch.library.custom_op("nvalchemiops::ewald_dipole_real_space_backward", _dp_real_bwd, mutates_args=())
+ewald_dipole_real_bwd_op.register_fake(lambda positions, *rest: _dp_bwd_fake(positions))
+ewald_dipole_real_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::ewald_dipole_real_space_backward"),
+                                           setup_context=lambda ctx, inputs, output: None)
+
+
+def _dp_real_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:11])
+    ctx.extra = (int(inputs[11]),)
+    ctx.set_materialize_grads(False)
+
+
+ewald_dipole_real_space_op = _op("_ewald_dipole_real_space", _dp_real_fwd, _dp_real_fwd_fake,
+                                 _dp_backward(f"{_NS}::_ewald_dipole_real_space", ewald_dipole_real_bwd_op, {3: "cell", 4: "alpha"}),
+                                 _dp_real_setup)
+
+
+def _dp_recip_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, cell: Tensor, k_vectors: Tensor, alpha: Tensor, batch_idx: Optional[Tensor],
+                  compute_forces: bool, compute_charge_gradients: bool, compute_dipole_gradients: bool,
+                  compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from nvalchemiops.interactions.electrostatics.dipole import _recip_forward
+
+    out = _recip_forward(positions, charges, dipoles, cell, k_vectors, alpha, batch_idx, compute_forces, compute_charge_gradients,
+                         compute_dipole_gradients, compute_virial)
+    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
+
+
+def _dp_recip_fwd_fake(positions, charges, dipoles, cell, k_vectors, alpha, batch_idx, compute_forces, compute_charge_gradients,
+                       compute_dipole_gradients, compute_virial):
+    return _dp_fake(positions, cell.reshape(-1, 3, 3).shape[0], compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
+
+
+def _dp_recip_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, cell: Tensor, k_vectors: Tensor, alpha: Tensor, batch_idx: Optional[Tensor],
+                  grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor]:
+    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles) for L = sum_i g_i E_i."""
+    from nvalchemiops.interactions.electrostatics.dipole import _recip_adjoint
+
+    return _recip_adjoint(positions, charges, dipoles, cell, k_vectors, alpha, batch_idx, grad_energies)
+
+
+ewald_dipole_recip_bwd_op = torch.library.custom_op("nvalchemiops::ewald_dipole_reciprocal_space_backward", _dp_recip_bwd, mutates_args=())
+ewald_dipole_recip_bwd_op.register_fake(lambda positions, *rest: _dp_bwd_fake(positions))
+ewald_dipole_recip_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::ewald_dipole_reciprocal_space_backward"),
+                                            setup_context=lambda ctx, inputs, output: None)
+
+
+def _dp_recip_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:7])
+    ctx.extra = ()
+    ctx.set_materialize_grads(False)
+
+
+ewald_dipole_reciprocal_space_op = _op("_ewald_dipole_reciprocal_space", _dp_recip_fwd, _dp_recip_fwd_fake,
+                                       _dp_backward(f"{_NS}::_ewald_dipole_reciprocal_space", ewald_dipole_recip_bwd_op,
+                                                    {3: "cell", 4: "k_vectors", 5: "alpha"}), _dp_recip_setup)
+
+
+__all__ = ["ewald_dipole_real_space_op", "ewald_dipole_reciprocal_space_op", "ewald_dipole_real_bwd_op", "ewald_dipole_recip_bwd_op",
+           "gaussian_charge_correction_op", "gaussian_bwd_op","spline_spread_op", "batch_spline_spread_op", "spline_gather_op", "batch_spline_gather_op", "spline_gather_vec3_op",
            "batch_spline_gather_vec3_op", "spline_gather_gradient_op", "batch_spline_gather_gradient_op", "pme_green_structure_factor_op",
            "batch_pme_green_structure_factor_op", "pme_energy_corrections_op", "batch_pme_energy_corrections_op",
            "pme_energy_corrections_with_charge_grad_op", "batch_pme_energy_corrections_with_charge_grad_op", "REAL_OPS", "real_space_op", "RECIPROCAL_OPS", "reciprocal_space_op", "COULOMB_OPS", "coulomb_op",
