@@ -885,6 +885,44 @@ int mi_pme_virial(const void* spec, const void* recip_cell, const void* alpha, c
                   int dtype, const void* k_vectors, const void* k_squared, int k_batched, const void* total_charge, double* partial, void* stream);
 int mi_pme_virial_blocks(void);
 
+/* Particle-mesh Ewald for point dipoles (csrc/pme.hip, last section; driver: nvalchemiops/interactions/electrostatics/pme_dipole.py): smooth PME
+ * with analytic spline derivatives.  With W_i(g) the order-p B-spline weight of atom i at mesh point g (as mi_spline_spread places it), grad the
+ * Cartesian gradient w.r.t. r_i (d W / d r_b = sum_a cit[a][b] n_a d W / d m_a, cit = cell_inv_t) and c = 2 alpha^3 / (3 sqrt(pi)):
+ *     rho_q = sum_i q_i W_i,  rho_mu = sum_i mu_i . grad W_i,  phi_X = the mesh solve of rho_X (mi_pme_solve* with_field = 0, or R2C ->
+ *     mi_pme_convolve -> C2R: linear, so the meshes are further systems of one batched call),  phi_t = phi_q + phi_mu,
+ *     E_i = q_i W_i.phi_mu + mu_i.grad W_i.phi_t - c |mu_i|^2
+ * order is 4, 5 or 6 (the plain order: MI_SPLINE_REFERENCE_ORDERS is refused), every mesh dimension >= order; positions, charges, dipoles
+ * [n_atoms][3], cell_inv_t, alpha and the meshes are in `dtype`; weights, where given, are float64 [n_atoms].
+ *
+ * mi_pme_dipole_spread: one pass over the atoms (order^2 threads each) adds q_i W_i into meshes[0] and mu_i . grad W_i into meshes[1], and with
+ * weights g also g_i q_i W_i into meshes[2] and g_i mu_i . grad W_i into meshes[3]: meshes [2 (weights NULL) | 4][n_systems][nx][ny][nz], ZEROED BY
+ * THIS CALL.  Floating-point atomic adds: a mesh is reproducible up to the arrival order of its adds only.
+ *
+ * mi_pme_dipole_gather: one read of mesh_a and mesh_b [n_systems][nx][ny][nz] per stencil point gives, per atom,
+ *     D_i = { dq: W_i.A,  dmu: grad W_i.B,  dr: q_i grad W_i.A + (mu_i . grad) grad W_i.B }
+ * and writes charge_grads[i] = s_i D_i.dq, dipole_grads[i] = s_i D_i.dmu - 2 c w_i mu_i, forces[i] = -s_i D_i.dr (positions dtype; the others
+ * float64), with s_i = 2, w_i = 1 (weights NULL: the forward call over (A, B) = (phi_mu, phi_t), every atom being source and probe) or
+ * s_i = w_i = weights[i] (the first launch of the adjoint of L = sum_i g_i E_i, same meshes).  accumulate = 1 (weights must be NULL): s_i = 1, no
+ * self term, and the three outputs are ADDED to what they hold -- the second launch of the adjoint, over (A, B) = (phi^g_mu, phi^g_q + phi^g_mu)
+ * of the weighted meshes.  energies[i] (float64) = q_i W_i.A + mu_i . grad W_i.B - c |mu_i|^2, never weighted or accumulated.  Any output may be
+ * NULL.  No atomics.
+ *
+ * mi_pme_dipole_virial: the k-space part of -dE/d(strain) from the two spectra [n_systems][nx][ny][nzr] (unscaled R2C of rho_q and rho_mu),
+ *     W[a][b] = sum_m h_m E_m (delta_ab - 2 (1/k^2 + 1/(4 alpha^2)) k_a k_b),  E_m = G(k_m) (2 Re[conj(spec_q) spec_mu] + |spec_mu|^2) / sf2_m,
+ * h as for mi_pme_virial.  Nine sums (row-major 3 x 3) per system and block: partial [n_systems][mi_pme_dipole_virial_blocks()][9] float64, every
+ * entry written, the caller folds the blocks AND adds the term of the dipoles' fractional components, which follow the strain while the dipoles
+ * stay fixed in the laboratory frame: sum_i (dE/dmu_i without its self term)[a] mu_i[b] per system (in this index order; it makes the virial
+ * non-symmetric). */
+int mi_pme_dipole_spread(const void* positions, const void* charges, const void* dipoles, const double* weights, const int32_t* batch_idx,
+                         const void* cell_inv_t, int n_atoms, int n_systems, int nx, int ny, int nz, int order, int dtype, void* meshes, void* stream);
+int mi_pme_dipole_gather(const void* positions, const void* charges, const void* dipoles, const double* weights, const int32_t* batch_idx,
+                         const void* cell_inv_t, const void* mesh_a, const void* mesh_b, const void* alpha /*[n_systems]*/, int n_atoms, int n_systems,
+                         int nx, int ny, int nz, int order, int dtype, int accumulate, double* energies, void* forces, double* charge_grads,
+                         double* dipole_grads, void* stream);
+int mi_pme_dipole_virial(const void* spec_q, const void* spec_mu, const void* recip_cell, const void* alpha, const void* volume, int n_systems, int nx,
+                         int ny, int nz, int order, int dtype, double* partial, void* stream);
+int mi_pme_dipole_virial_blocks(void);
+
 int mi_pme_gather_finish(const void* positions, const void* charges, const int32_t* batch_idx, const void* cell_inv_t,
                          const void* meshes /*[B,(1|4),nx,ny,nz] real*/, const void* alpha, const void* volume,
                          const void* total_charge /*[B]*/, int n_atoms, int n_systems, int nx, int ny, int nz,

@@ -2073,3 +2073,301 @@ int mi_segment_sum(const void* values, const int32_t* batch_idx, int n_atoms, in
 }
 
 }  // extern "C"
+
+// ==== particle-mesh Ewald for point dipoles (driver: nvalchemiops/interactions/electrostatics/pme_dipole.py) ================================
+// Smooth PME with analytic spline derivatives (Toukmaji, Sagui, Board, Darden): with W_i(g) the B-spline weight of atom i at mesh point g,
+//   rho_q = sum_i q_i W_i,  rho_mu = sum_i mu_i . grad W_i,  phi_X = the mesh solve of rho_X (mi_pme_solve* / mi_pme_convolve: linear, so the
+//   meshes are further "systems" of one batched call),  phi_t = phi_q + phi_mu,  c = 2 alpha^3 / (3 sqrt(pi)):
+//   E_i = q_i W_i.phi_mu + mu_i.grad W_i.phi_t - c |mu_i|^2,   dE/dq_i = 2 W_i.phi_mu,   dE/dmu_i = 2 grad W_i.phi_t - 2 c mu_i,
+//   F_i = -2 [q_i grad W_i.phi_mu + (mu_i.grad) grad W_i.phi_t]
+// grad is Cartesian: d W / d r_b = sum_a cit[a][b] n_a d W / d m_a, so the dipole enters as mu_frac = cit mu and the gather turns its
+// fractional sums into Cartesian ones with cit once, at the end.
+namespace {
+
+// M_p(u), M_p'(u) and M_p''(u) from ONE pass of the B-spline recursion: at level p - 2 it holds a_k = M_{p-2}(u - k), k = 0..2, and
+//   M_p'' = a_0 - 2 a_1 + a_2,   M_p' = b_0 - b_1 with b_k = M_{p-1}(u - k),   M_p = [u b_0 + (p - u) b_1] / (p - 1).
+// Order 4 goes through the recursion as well: the expanded cubics of `bspline_ref` cancel terms of size 48 into a value below 0.67, which in
+// float32 costs the dipole outputs a factor 3 in error against orders 5 and 6 (measured: 2.6e-6 vs 8e-7 of scale).
+template <class T, int ORDER> __device__ __forceinline__ void dipole_spline(T u, T& w, T& d, T& dd) {
+  w = d = dd = T(0);
+  if (!(u >= T(0) && u < T(ORDER))) return;
+  T m[ORDER];
+#pragma unroll
+  for (int k = 0; k < ORDER; ++k) { const T x = u - T(k); m[k] = (x >= T(0) && x < T(1)) ? T(1) : T(0); }
+#pragma unroll
+  for (int p = 2; p <= ORDER - 2; ++p) {
+    const T inv = T(1) / T(p - 1);
+#pragma unroll
+    for (int k = 0; k <= ORDER - p; ++k) { const T x = u - T(k); m[k] = (x * m[k] + (T(p) - x) * m[k + 1]) * inv; }
+  }
+  dd = m[0] - T(2) * m[1] + m[2];
+  const T inv = T(1) / T(ORDER - 2), x1 = u - T(1);
+  const T b0 = (u * m[0] + (T(ORDER - 1) - u) * m[1]) * inv, b1 = (x1 * m[1] + (T(ORDER - 1) - x1) * m[2]) * inv;
+  d = b0 - b1;
+  w = (u * b0 + (T(ORDER) - u) * b1) / T(ORDER - 1);
+}
+
+// 1-D weights and first derivatives (times the mesh dimension) of one atom, evaluated ONCE by 3 x ORDER threads of its group, in LDS
+template <class T, int ORDER> struct DipoleStencil { T w[3][ORDER], d[3][ORDER]; int gi[3][ORDER]; };
+
+// Spread: order^2 threads per atom (one (tx, ty) column each, z innermost), like spline_spread_kernel; one pass writes rho_q and rho_mu -- and
+// with per-atom weights g the two weighted meshes of the adjoint -- by atomic adds into meshes [2 | 4][B][nx][ny][nz] the entry point zeroed.
+template <class T, int ORDER>
+__global__ __launch_bounds__(256) void pme_dipole_spread_kernel(const T* __restrict__ pos, const T* __restrict__ charges, const T* __restrict__ dipoles,
+                                                                const double* __restrict__ weights, const int* __restrict__ batch_idx,
+                                                                const T* __restrict__ cit, int N, int B, int nx, int ny, int nz,
+                                                                T* __restrict__ meshes) {
+  constexpr int tpa = ORDER * ORDER, apb = 256 / tpa;
+  __shared__ DipoleStencil<T, ORDER> sten[apb];
+  const int la = threadIdx.x / tpa, col = threadIdx.x - la * tpa;
+  const int i = blockIdx.x * apb + la;
+  const bool active = la < apb && i < N;
+  const int s = active && batch_idx ? batch_idx[i] : 0;
+  if (active && col < 3 * ORDER) {
+    const Stencil<T> st = make_stencil(pos + 3 * (size_t)i, cit + 9 * (size_t)s, nx, ny, nz, ORDER);
+    const int d = col / ORDER, t = col - d * ORDER;
+    const int n = d == 0 ? nx : (d == 1 ? ny : nz);
+    const T u = (T)ORDER * T(0.5) + st.theta[d] - (T)(t + st.off0[d]);
+    T w1, d1, dd1;
+    dipole_spline<T, ORDER>(u, w1, d1, dd1);
+    sten[la].w[d][t] = w1;
+    sten[la].d[d][t] = d1 * (T)n;
+    sten[la].gi[d][t] = wrap_idx(st.base[d] + t + st.off0[d], n);
+  }
+  __syncthreads();
+  if (!active) return;
+  const DipoleStencil<T, ORDER>& k = sten[la];
+  const T* c = cit + 9 * (size_t)s;
+  const T mu[3] = {dipoles[3 * (size_t)i], dipoles[3 * (size_t)i + 1], dipoles[3 * (size_t)i + 2]};
+  T mf[3];
+  mat3_colvec(c, mu, mf);  // mu_frac = cit mu
+  const T q = charges[i];
+  const int tx = col / ORDER, ty = col - tx * ORDER;
+  const T wxy = k.w[0][tx] * k.w[1][ty];
+  const T dxy = mf[0] * (k.d[0][tx] * k.w[1][ty]) + mf[1] * (k.w[0][tx] * k.d[1][ty]);  // the x and y terms of mu . grad W, without their w_z
+  const T dz = mf[2] * wxy;
+  const size_t mesh = (size_t)B * nx * ny * nz;
+  T* row = meshes + (((size_t)s * nx + k.gi[0][tx]) * ny + k.gi[1][ty]) * nz;
+  const bool weighted = weights != nullptr;
+  const T g = weighted ? (T)weights[i] : T(0);
+#pragma unroll
+  for (int tz = 0; tz < ORDER; ++tz) {
+    const T vq = q * (wxy * k.w[2][tz]);
+    const T vm = dxy * k.w[2][tz] + dz * k.d[2][tz];
+    T* p = row + k.gi[2][tz];
+    if (vq != T(0)) atomicAdd(p, vq);
+    if (vm != T(0)) atomicAdd(p + mesh, vm);
+    if (weighted) {
+      if (g * vq != T(0)) atomicAdd(p + 2 * mesh, g * vq);
+      if (g * vm != T(0)) atomicAdd(p + 3 * mesh, g * vm);
+    }
+  }
+}
+
+// Gather: PG_LANES lanes per atom, one x-plane of the stencil each, shuffle fold -- the shape of pme_gather_finish_kernel.  One read of each
+// of the two meshes A and B [B][nx][ny][nz] per stencil point; thirteen sums in fractional coordinates:
+//   sA = W.A,  gA = grad W.A,  gB = grad W.B,  hB = (mu_frac . grad) grad W.B   (the six Hessian words contracted with mu_frac on the fly)
+// and with D_i = {dq: sA, dmu: cit^T gB, dr: q cit^T gA + cit^T hB} the outputs are s_i D_i, s_i = 2 (the forward call: each atom is source
+// and probe), g_i (weights) or 1 (accumulate: the second launch of the adjoint, added to what the first one wrote).  No atomics.
+template <class T, int ORDER>
+__global__ __launch_bounds__(256) void pme_dipole_gather_kernel(const T* __restrict__ pos, const T* __restrict__ charges, const T* __restrict__ dipoles,
+                                                                const double* __restrict__ weights, const int* __restrict__ batch_idx,
+                                                                const T* __restrict__ cit, const T* __restrict__ mesh_a, const T* __restrict__ mesh_b,
+                                                                const T* __restrict__ alpha, int N, int nx, int ny, int nz, int accumulate,
+                                                                double* __restrict__ energies, T* __restrict__ forces, double* __restrict__ cgrads,
+                                                                double* __restrict__ dgrads) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int i0 = t / PG_LANES, tx = t - i0 * PG_LANES;
+  const int i = i0 < N ? i0 : N - 1;  // surplus groups of the last block recompute the last atom and do not store
+  const int s = batch_idx ? batch_idx[i] : 0;
+  const T* c = cit + 9 * (size_t)s;
+  const Stencil<T> st = make_stencil(pos + 3 * (size_t)i, c, nx, ny, nz, ORDER);
+  const int dims[3] = {nx, ny, nz};
+  T w[2][ORDER], d[2][ORDER], dd[2][ORDER];  // the y and z axes; the lane's own x-plane below
+  int gi[2][ORDER];
+#pragma unroll
+  for (int a = 1; a < 3; ++a)
+#pragma unroll
+    for (int k = 0; k < ORDER; ++k) {
+      const T u = (T)ORDER * T(0.5) + st.theta[a] - (T)(k + st.off0[a]);
+      const T n = (T)dims[a];
+      T w1, d1, dd1;
+      dipole_spline<T, ORDER>(u, w1, d1, dd1);
+      w[a - 1][k] = w1;
+      d[a - 1][k] = d1 * n;
+      dd[a - 1][k] = dd1 * n * n;
+      gi[a - 1][k] = wrap_idx(st.base[a] + k + st.off0[a], dims[a]);
+    }
+  const T mu[3] = {dipoles[3 * (size_t)i], dipoles[3 * (size_t)i + 1], dipoles[3 * (size_t)i + 2]};
+  T mf[3];
+  mat3_colvec(c, mu, mf);
+  T sA = 0, gA[3] = {0, 0, 0}, gB[3] = {0, 0, 0}, hB[3] = {0, 0, 0};
+  if (tx < ORDER) {
+    const T u = (T)ORDER * T(0.5) + st.theta[0] - (T)(tx + st.off0[0]);
+    T wx, dx, ddx;
+    dipole_spline<T, ORDER>(u, wx, dx, ddx);
+    dx *= (T)nx;
+    ddx *= (T)nx * (T)nx;
+    const size_t m0 = ((size_t)s * nx + wrap_idx(st.base[0] + tx + st.off0[0], nx)) * ny;
+#pragma unroll
+    for (int ty = 0; ty < ORDER; ++ty) {
+      const size_t row = (m0 + gi[0][ty]) * nz;
+      const T wy = w[0][ty], dy = d[0][ty], ddy = dd[0][ty];
+#pragma unroll
+      for (int tz = 0; tz < ORDER; ++tz) {
+        const T a = mesh_a[row + gi[1][tz]], b = mesh_b[row + gi[1][tz]];
+        const T wz = w[1][tz], dz = d[1][tz], ddz = dd[1][tz];
+        const T W = wx * wy * wz, Gx = dx * wy * wz, Gy = wx * dy * wz, Gz = wx * wy * dz;
+        const T hxx = ddx * wy * wz, hyy = wx * ddy * wz, hzz = wx * wy * ddz, hxy = dx * dy * wz, hxz = dx * wy * dz, hyz = wx * dy * dz;
+        sA += a * W;
+        gA[0] += a * Gx; gA[1] += a * Gy; gA[2] += a * Gz;
+        gB[0] += b * Gx; gB[1] += b * Gy; gB[2] += b * Gz;
+        hB[0] += b * (mf[0] * hxx + mf[1] * hxy + mf[2] * hxz);
+        hB[1] += b * (mf[0] * hxy + mf[1] * hyy + mf[2] * hyz);
+        hB[2] += b * (mf[0] * hxz + mf[1] * hyz + mf[2] * hzz);
+      }
+    }
+  }
+#pragma unroll
+  for (int o = PG_LANES / 2; o > 0; o >>= 1) {
+    sA += __shfl_xor(sA, o, PG_LANES);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { gA[a] += __shfl_xor(gA[a], o, PG_LANES); gB[a] += __shfl_xor(gB[a], o, PG_LANES); hB[a] += __shfl_xor(hB[a], o, PG_LANES); }
+  }
+  if (tx != 0 || i0 >= N) return;
+  // fractional -> Cartesian: v_cart[b] = sum_a cit[a][b] v_frac[a], in double
+  const double q = (double)charges[i];
+  double cA[3], cB[3], cH[3];
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    cA[b] = (double)c[b] * (double)gA[0] + (double)c[3 + b] * (double)gA[1] + (double)c[6 + b] * (double)gA[2];
+    cB[b] = (double)c[b] * (double)gB[0] + (double)c[3 + b] * (double)gB[1] + (double)c[6 + b] * (double)gB[2];
+    cH[b] = (double)c[b] * (double)hB[0] + (double)c[3 + b] * (double)hB[1] + (double)c[6 + b] * (double)hB[2];
+  }
+  const double al = (double)alpha[s];
+  const double self = 2.0 * al * al * al / (3.0 * 1.7724538509055160273);  // 2 alpha^3 / (3 sqrt(pi))
+  const double m[3] = {(double)mu[0], (double)mu[1], (double)mu[2]};
+  const double gw = weights ? weights[i] : 1.0;
+  const double sc = accumulate ? 1.0 : (weights ? gw : 2.0);
+  if (energies) energies[i] = q * (double)sA + (m[0] * cB[0] + m[1] * cB[1] + m[2] * cB[2]) - self * (m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
+  if (cgrads) { const double v = sc * (double)sA; cgrads[i] = accumulate ? cgrads[i] + v : v; }
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    const size_t o = 3 * (size_t)i + b;
+    if (dgrads) { const double v = sc * cB[b]; dgrads[o] = accumulate ? dgrads[o] + v : v - 2.0 * self * gw * m[b]; }
+    if (forces) { const double v = -sc * (q * cA[b] + cH[b]); forces[o] = accumulate ? (T)((double)forces[o] + v) : (T)v; }
+  }
+}
+
+// k-space virial of the cross spectrum: pme_virial_kernel over the two spectra rho_hat_q, rho_hat_mu [B][nx][ny][nzr],
+//   W[a][b] = sum_m E_m (delta_ab - 2 (1/k^2 + 1/(4 alpha^2)) k_a k_b),  E_m = h_m G_m (2 Re[conj(rho_hat_q) rho_hat_mu] + |rho_hat_mu|^2) / sf2_m
+// (the cross form: never the difference of two quadratic forms).  Nine sums, row-major, per system and block; the caller adds the term of
+// the dipoles' fractional components, sum_i (dE/dmu_i without the self term)_a mu_i,b, which is what makes the virial non-symmetric.
+template <class T>
+__global__ __launch_bounds__(256) void pme_dipole_virial_kernel(const Cplx<T>* __restrict__ spec_q, const Cplx<T>* __restrict__ spec_mu,
+                                                                const T* __restrict__ recip, const T* __restrict__ alpha, const T* __restrict__ volume,
+                                                                int nx, int ny, int nz, int order, double* __restrict__ partial) {
+  const int b = blockIdx.y;
+  const int nzr = nz / 2 + 1;
+  const size_t per = (size_t)nx * ny * nzr;
+  const T* R = recip + 9 * (size_t)b;
+  const T al = alpha[b], vol = volume[b];
+  const double c4 = 1.0 / (4.0 * (double)al * (double)al);
+  double acc[6] = {0, 0, 0, 0, 0, 0};
+  for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x; r < per; r += (size_t)gridDim.x * blockDim.x) {
+    const int k = (int)(r % nzr), j = (int)((r / nzr) % ny), i = (int)(r / ((size_t)nzr * ny));
+    const int mx = miller_of(i, nx), my = miller_of(j, ny), mz = k;
+    const T m[3] = {(T)mx, (T)my, (T)mz};
+    T kv[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) kv[c] = m[0] * R[3 * c] + m[1] * R[3 * c + 1] + m[2] * R[3 * c + 2];
+    T k2 = kv[0] * kv[0] + kv[1] * kv[1] + kv[2] * kv[2];
+    if (!(k2 > T(1e-12))) k2 = T(1e-12);
+    const T G = green_of(k2, al, vol, i == 0 && j == 0 && k == 0);
+    if (G == T(0)) continue;
+    const T sf2 = sf_sq_of<T>(mx, my, mz, nx, ny, nz, order);
+    const Cplx<T> vq = spec_q[(size_t)b * per + r], vm = spec_mu[(size_t)b * per + r];
+    const double h = (k == 0 || (2 * k == nz)) ? 1.0 : 2.0;
+    const double cross = 2.0 * ((double)vq.re * (double)vm.re + (double)vq.im * (double)vm.im) + (double)vm.re * (double)vm.re + (double)vm.im * (double)vm.im;
+    const double e = h * cross * ((double)G / (double)sf2);
+    const double c = -2.0 * e * (1.0 / (double)k2 + c4);
+    const double kx = kv[0], ky = kv[1], kz = kv[2];
+    acc[0] += e + c * kx * kx; acc[1] += e + c * ky * ky; acc[2] += e + c * kz * kz;
+    acc[3] += c * kx * ky; acc[4] += c * kx * kz; acc[5] += c * ky * kz;
+  }
+  __shared__ double part[4][6];
+  const int lane = threadIdx.x & (MI_WAVE - 1), wave = threadIdx.x / MI_WAVE;
+#pragma unroll
+  for (int q = 0; q < 6; ++q) { const double t = wave_sum(acc[q]); if (lane == 0) part[wave][q] = t; }
+  __syncthreads();
+  if (threadIdx.x < 9) {
+    const int a = threadIdx.x / 3, bb = threadIdx.x - 3 * a;
+    const int q = a == bb ? a : (a + bb + 2);  // {xx, yy, zz, xy, xz, yz} -> row-major 3 x 3 (this part is symmetric)
+    partial[((size_t)b * gridDim.x + blockIdx.x) * 9 + threadIdx.x] = part[0][q] + part[1][q] + part[2][q] + part[3][q];
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi_pme_dipole_spread(const void* positions, const void* charges, const void* dipoles, const double* weights, const int32_t* batch_idx,
+                         const void* cell_inv_t, int n_atoms, int n_systems, int nx, int ny, int nz, int order, int dtype, void* meshes, void* stream) {
+  MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
+  MI_REQUIRE(order >= 4 && order <= MI_MAX_ORDER, "spline order must be 4..6 (the dipole terms need two continuous derivatives of the spline)");
+  MI_REQUIRE(n_systems >= 1 && nx >= order && ny >= order && nz >= order, "every mesh dimension must be at least the spline order");
+  MI_REQUIRE(n_atoms >= 0 && meshes && cell_inv_t, "null pointer");
+  MI_REQUIRE(n_atoms == 0 || (positions && charges && dipoles), "null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t mesh_bytes = (size_t)n_systems * nx * ny * nz * dtype_bytes(dtype);
+  mi_timing_begin("pme_dipole_spread", stream);
+  MI_HIP_CHECK(hipMemsetAsync(meshes, 0, (weights ? 4 : 2) * mesh_bytes, st));
+  if (n_atoms > 0) {
+    const int apb = 256 / (order * order);
+    MI_DISPATCH_ORDER(order, MI_DISPATCH_T(dtype, (pme_dipole_spread_kernel<T_, (O_ < 4 ? 4 : O_)><<<mi_blocks(n_atoms, apb), 256, 0, st>>>(
+                                 (const T_*)positions, (const T_*)charges, (const T_*)dipoles, weights, batch_idx, (const T_*)cell_inv_t, n_atoms,
+                                 n_systems, nx, ny, nz, (T_*)meshes))));
+  }
+  mi_timing_end(stream);
+  MI_LAUNCH_CHECK();
+  return MI_OK;
+}
+
+int mi_pme_dipole_gather(const void* positions, const void* charges, const void* dipoles, const double* weights, const int32_t* batch_idx,
+                         const void* cell_inv_t, const void* mesh_a, const void* mesh_b, const void* alpha, int n_atoms, int n_systems, int nx, int ny,
+                         int nz, int order, int dtype, int accumulate, double* energies, void* forces, double* charge_grads, double* dipole_grads,
+                         void* stream) {
+  MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
+  MI_REQUIRE(order >= 4 && order <= MI_MAX_ORDER, "spline order must be 4..6 (the dipole terms need two continuous derivatives of the spline)");
+  MI_REQUIRE(n_systems >= 1 && nx >= order && ny >= order && nz >= order, "every mesh dimension must be at least the spline order");
+  MI_REQUIRE(!(accumulate && weights), "accumulate (the second launch of the adjoint) takes no weights");
+  if (n_atoms <= 0) return MI_OK;
+  MI_REQUIRE(positions && charges && dipoles && cell_inv_t && mesh_a && mesh_b && alpha, "null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  mi_timing_begin("pme_dipole_gather", stream);
+  MI_DISPATCH_ORDER(order, MI_DISPATCH_T(dtype, (pme_dipole_gather_kernel<T_, (O_ < 4 ? 4 : O_)><<<mi_blocks((long long)n_atoms * PG_LANES, 256), 256, 0, st>>>(
+                               (const T_*)positions, (const T_*)charges, (const T_*)dipoles, weights, batch_idx, (const T_*)cell_inv_t, (const T_*)mesh_a,
+                               (const T_*)mesh_b, (const T_*)alpha, n_atoms, nx, ny, nz, accumulate, energies, (T_*)forces, charge_grads, dipole_grads))));
+  mi_timing_end(stream);
+  MI_LAUNCH_CHECK();
+  return MI_OK;
+}
+
+int mi_pme_dipole_virial(const void* spec_q, const void* spec_mu, const void* recip_cell, const void* alpha, const void* volume, int n_systems, int nx,
+                         int ny, int nz, int order, int dtype, double* partial /*[n_systems][mi_pme_dipole_virial_blocks()][9]*/, void* stream) {
+  MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
+  MI_REQUIRE(order >= 4 && order <= MI_MAX_ORDER, "spline order must be 4..6 (the dipole terms need two continuous derivatives of the spline)");
+  MI_REQUIRE(spec_q && spec_mu && recip_cell && alpha && volume && partial && n_systems >= 1 && n_systems <= 65535 && nx > 0 && ny > 0 && nz > 0,
+             "null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  mi_timing_begin("pme_dipole_virial", stream);
+  MI_DISPATCH_T(dtype, (pme_dipole_virial_kernel<T_><<<dim3(PME_VIR_BLOCKS, n_systems), 256, 0, st>>>(
+                           (const Cplx<T_>*)spec_q, (const Cplx<T_>*)spec_mu, (const T_*)recip_cell, (const T_*)alpha, (const T_*)volume, nx, ny, nz, order,
+                           partial)));
+  mi_timing_end(stream);
+  MI_LAUNCH_CHECK();
+  return MI_OK;
+}
+int mi_pme_dipole_virial_blocks(void) { return PME_VIR_BLOCKS; }
+
+}  // extern "C"

@@ -163,6 +163,15 @@ def lib() -> ctypes.CDLL:
         L.mi_ewald_dipole_real_scratch_bytes.argtypes = [i, i]
         L.mi_ewald_dipole_blocks.restype = i
         L.mi_ewald_dipole_blocks.argtypes = []
+        # particle-mesh Ewald for point dipoles (nvalchemiops/interactions/electrostatics/pme_dipole.py)
+        L.mi_pme_dipole_spread.restype = i
+        L.mi_pme_dipole_spread.argtypes = [vp] * 6 + [i] * 7 + [vp, vp]
+        L.mi_pme_dipole_gather.restype = i
+        L.mi_pme_dipole_gather.argtypes = [vp] * 9 + [i] * 8 + [vp] * 5
+        L.mi_pme_dipole_virial.restype = i
+        L.mi_pme_dipole_virial.argtypes = [vp] * 5 + [i] * 6 + [vp, vp]
+        L.mi_pme_dipole_virial_blocks.restype = i
+        L.mi_pme_dipole_virial_blocks.argtypes = []
         # charge equilibration (nvalchemiops/interactions/electrostatics/qeq.py)
         L.mi_qeq_pair_coefficients.restype = i
         L.mi_qeq_pair_coefficients.argtypes = [vp] * 6 + [i, i, i, vp, vp, vp, i, i, vp, vp, vp, vp]

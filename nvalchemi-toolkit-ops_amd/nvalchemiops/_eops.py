@@ -1719,7 +1719,50 @@ ewald_dipole_reciprocal_space_op = _op("_ewald_dipole_reciprocal_space", _dp_rec
                                                     {3: "cell", 4: "k_vectors", 5: "alpha"}), _dp_recip_setup)
 
 
-__all__ = ["ewald_dipole_real_space_op", "ewald_dipole_reciprocal_space_op", "ewald_dipole_real_bwd_op", "ewald_dipole_recip_bwd_op",
+
+# point-dipole PME, mesh half: the pattern of the two ops above (mesh dimensions and the spline order travel as plain integers)
+def _dp_pme_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, cell: Tensor, alpha: Tensor, batch_idx: Optional[Tensor], nx: int, ny: int,
+                nz: int, spline_order: int, compute_forces: bool, compute_charge_gradients: bool, compute_dipole_gradients: bool,
+                compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from nvalchemiops.interactions.electrostatics.pme_dipole import _recip_forward
+
+    out = _recip_forward(positions, charges, dipoles, cell, alpha, batch_idx, (int(nx), int(ny), int(nz)), int(spline_order), compute_forces,
+                         compute_charge_gradients, compute_dipole_gradients, compute_virial)
+    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
+
+
+def _dp_pme_fwd_fake(positions, charges, dipoles, cell, alpha, batch_idx, nx, ny, nz, spline_order, compute_forces, compute_charge_gradients,
+                     compute_dipole_gradients, compute_virial):
+    nsys = cell.reshape(-1, 3, 3).shape[0] if batch_idx is not None else 1
+    return _dp_fake(positions, nsys, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
+
+
+def _dp_pme_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, cell: Tensor, alpha: Tensor, batch_idx: Optional[Tensor], nx: int, ny: int,
+                nz: int, spline_order: int, grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor]:
+    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles) for L = sum_i g_i E_i."""
+    from nvalchemiops.interactions.electrostatics.pme_dipole import _recip_adjoint
+
+    return _recip_adjoint(positions, charges, dipoles, cell, alpha, batch_idx, (int(nx), int(ny), int(nz)), int(spline_order), grad_energies)
+
+
+pme_dipole_recip_bwd_op = torch.library.custom_op("nvalchemiops::pme_dipole_reciprocal_space_backward", _dp_pme_bwd, mutates_args=())
+pme_dipole_recip_bwd_op.register_fake(lambda positions, *rest: _dp_bwd_fake(positions))
+pme_dipole_recip_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::pme_dipole_reciprocal_space_backward"),
+                                          setup_context=lambda ctx, inputs, output: None)
+
+
+def _dp_pme_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:6])
+    ctx.extra = tuple(int(v) for v in inputs[6:10])
+    ctx.set_materialize_grads(False)
+
+
+pme_dipole_reciprocal_space_op = _op("_pme_dipole_reciprocal_space", _dp_pme_fwd, _dp_pme_fwd_fake,
+                                     _dp_backward(f"{_NS}::_pme_dipole_reciprocal_space", pme_dipole_recip_bwd_op, {3: "cell", 4: "alpha"}),
+                                     _dp_pme_setup)
+
+
+__all__ = ["pme_dipole_reciprocal_space_op", "pme_dipole_recip_bwd_op", "ewald_dipole_real_space_op", "ewald_dipole_reciprocal_space_op", "ewald_dipole_real_bwd_op", "ewald_dipole_recip_bwd_op",
            "gaussian_charge_correction_op", "gaussian_bwd_op","spline_spread_op", "batch_spline_spread_op", "spline_gather_op", "batch_spline_gather_op", "spline_gather_vec3_op",
            "batch_spline_gather_vec3_op", "spline_gather_gradient_op", "batch_spline_gather_gradient_op", "pme_green_structure_factor_op",
            "batch_pme_green_structure_factor_op", "pme_energy_corrections_op", "batch_pme_energy_corrections_op",

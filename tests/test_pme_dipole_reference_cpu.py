@@ -1,0 +1,141 @@
+"""The yardstick of tests/test_pme_dipole_gpu.py checked on its own: tests/pme_dipole_reference.py (mesh sum for point dipoles, restated from
+the definition) against the explicit reciprocal sum of tests/dipole_reference.py over a converged k set, against finite differences of its
+own energy, and against the symmetries of the model.  No device, no library.
+
+Relative errors are max |difference| of the per-atom energies over max |per-atom energy| of the explicit sum."""
+import functools
+import math
+
+import numpy as np
+import torch
+
+from tests import dipole_reference as D
+from tests import pme_dipole_reference as R
+from tests.gaussian_reference import brute_force_entries
+
+F64 = torch.float64
+CELL = np.array([[8.0, 0.0, 0.0], [0.7, 8.8, 0.0], [-0.4, 0.5, 7.2]])
+ALPHA = 0.35
+MESHES = ((16, 16, 16), (24, 24, 24))
+
+
+@functools.lru_cache(maxsize=None)
+def system():
+    g = np.random.default_rng(11)
+    pos = g.uniform(0, 1, (6, 3)) @ CELL
+    q = g.normal(size=6)
+    q -= q.mean()
+    mu = 0.5 * g.normal(size=(6, 3)) / math.sqrt(3.0)  # |mu| ~ 0.5
+    t = lambda a: torch.tensor(a, dtype=F64)  # noqa: E731
+    return t(pos), t(q), t(mu), t(CELL)
+
+
+def half_space_k(cell, index_max=10):
+    """k = 2 pi cell^-1 m over one half of the integer vectors with |m_d| <= index_max (m and -m counted once, m = 0 left out)."""
+    rng = np.arange(-index_max, index_max + 1)
+    m = np.stack(np.meshgrid(rng, rng, rng, indexing="ij"), axis=-1).reshape(-1, 3)
+    keep = (m[:, 0] > 0) | ((m[:, 0] == 0) & (m[:, 1] > 0)) | ((m[:, 0] == 0) & (m[:, 1] == 0) & (m[:, 2] > 0))
+    return torch.tensor(m[keep] @ (2.0 * np.pi * np.linalg.inv(cell)).T, dtype=F64)
+
+
+@functools.lru_cache(maxsize=None)
+def explicit(alpha=ALPHA):
+    pos, q, mu, cell = system()
+    return D.recip_energies(pos, q, mu, cell, half_space_k(CELL), alpha)
+
+
+@functools.lru_cache(maxsize=None)
+def mesh_error(order, dims, alpha=ALPHA):
+    """Relative error of the mesh energies against the converged explicit sum: THE number the bars of the GPU file are built on."""
+    pos, q, mu, cell = system()
+    ref = explicit(alpha)
+    e = R.energies(pos, q, mu, cell, alpha, dims, order).detach()
+    return float((e - ref).abs().max() / ref.abs().max())
+
+
+def total(pos, q, mu, cell, dims=(16, 16, 16), order=5, alpha=ALPHA):
+    return R.energies(pos, q, mu, cell, alpha, dims, order).sum().detach()
+
+
+def test_converges_to_the_explicit_sum():
+    errs = {(o, d): mesh_error(o, d) for o in (5, 6) for d in MESHES}
+    for key, err in errs.items():
+        print(f"order {key[0]} mesh {key[1]}: relative error {err:.2e}")
+    for o in (5, 6):
+        assert errs[(o, MESHES[1])] < errs[(o, MESHES[0])]
+    assert errs[(6, MESHES[1])] < 1e-5
+
+
+def test_zero_dipoles_give_exactly_zero():
+    pos, q, mu, cell = system()
+    e = R.energies(pos, q, torch.zeros_like(mu), cell, ALPHA, (16, 16, 16), 5)
+    assert torch.equal(e, torch.zeros_like(e))
+
+
+def test_bilinear_in_charges_and_dipoles():
+    pos, q, mu, cell = system()
+    e = lambda a, b: float(total(pos, a * q, b * mu, cell))  # noqa: E731  E(q, mu) = 2 C(q, mu) + D(mu, mu)
+    dd, full = e(0.0, 1.0), e(1.0, 1.0)
+    assert abs(e(0.0, 2.0) - 4.0 * dd) <= 1e-12 * abs(dd)
+    assert abs((e(-1.7, 1.0) - dd) - (-1.7) * (full - dd)) <= 1e-12 * abs(full)
+    assert abs((e(1.0, 3.0) - 9.0 * dd) - 3.0 * (full - dd)) <= 1e-12 * abs(full)
+    assert abs(full - dd) > 1e-3 * abs(dd)  # the charge-dipole part is there
+
+
+def test_lattice_translation_of_one_atom():
+    pos, q, mu, cell = system()
+    ref = R.energies(pos, q, mu, cell, ALPHA, (16, 16, 16), 5)
+    moved = pos.clone()
+    moved[2] += cell[0] - 2.0 * cell[1] + cell[2]
+    e = R.energies(moved, q, mu, cell, ALPHA, (16, 16, 16), 5)
+    assert float((e - ref).abs().max()) <= 1e-12 * float(ref.abs().max())
+
+
+def test_derivatives_against_central_differences():
+    pos, q, mu, cell = system()
+    dims, order, h = (12, 10, 16), 5, 1e-5
+    out = R.evaluate(pos, q, mu, cell, ALPHA, dims, order, virial=False)
+    f = lambda p, c, m: float(total(p, c, m, cell, dims, order))  # noqa: E731
+
+    def fd(which, idx):
+        args = [pos.clone(), q.clone(), mu.clone()]
+        args[which][idx] += h
+        up = f(*args)
+        args[which][idx] -= 2 * h
+        return (up - f(*args)) / (2 * h)
+
+    for i in range(6):
+        for a in range(3):
+            assert abs(-fd(0, (i, a)) - out["forces"][i, a]) <= 1e-8 * np.abs(out["forces"]).max()
+            assert abs(fd(2, (i, a)) - out["dipole_grads"][i, a]) <= 1e-8 * np.abs(out["dipole_grads"]).max()
+        assert abs(fd(1, i) - out["charge_grads"][i]) <= 1e-8 * np.abs(out["charge_grads"]).max()
+
+
+def test_virial_against_finite_strain():
+    pos, q, mu, cell = system()
+    dims, order, h = (12, 10, 16), 5, 1e-5
+    vir = R.evaluate(pos, q, mu, cell, ALPHA, dims, order)["virial"][0]
+
+    def strained(a, b, step):
+        defo = torch.eye(3, dtype=F64)
+        defo[a, b] += step
+        return float(total(pos @ defo.T, q, mu, cell @ defo.T, dims, order))
+
+    for a in range(3):
+        for b in range(3):
+            fd = -(strained(a, b, h) - strained(a, b, -h)) / (2 * h)
+            assert abs(fd - vir[a, b]) <= 1e-8 * np.abs(vir).max(), (a, b, fd, vir[a, b])
+    assert np.abs(vir - vir.T).max() > 1e-3 * np.abs(vir).max()  # dipoles fixed in the laboratory frame: not symmetric
+
+
+def test_real_plus_mesh_does_not_depend_on_alpha():
+    pos, q, mu, cell = system()
+    dims, order = MESHES[1], 6
+    i, j, S = brute_force_entries(pos.numpy(), CELL, 16.0, 3)  # erfc(0.35 x 16) = 2e-15: the real-space sum is converged
+    sums = []
+    for alpha in (0.35, 0.40):
+        sums.append((D.real_energies(pos, q, mu, cell, alpha, i, j, S) + R.energies(pos, q, mu, cell, alpha, dims, order)).detach())
+    bar = 2.0 * mesh_error(order, dims)
+    err = float((sums[0] - sums[1]).abs().max() / sums[0].abs().max())
+    print(f"alpha 0.35 vs 0.40: relative difference {err:.2e} (bar {bar:.2e})")
+    assert err <= bar
