@@ -9,7 +9,7 @@
 // Execution shape (csrc/d3.hip's): one wave64 per atom, lanes stride the row; only the row owner writes -- the list is full, so an owner
 // gets its force, dE/dCN_i and dE/dq_i from its own row alone (entry and mirror are equal by c6_ref[A,B,a,b] = c6_ref[B,A,b,a]; self-image
 // entries (i, i, +-S) come out right the same way).  No atomics anywhere; per-system sums are written per row and folded in a fixed order
-// (the scheme of gc_fold_kernel), so two identical calls give bit-identical outputs.  Pair math fp32 (the pair vector is formed in the
+// (mi_system_fold of pair_row.h), so two identical calls give bit-identical outputs.  Pair math fp32 (the pair vector is formed in the
 // positions dtype), accumulators fp64; the per-atom weights are evaluated in fp64 (O(N), seven references) and stored as fp32.
 //
 // Passes:  species (mark / compact / tables) -> pack -> CN -> weights -> energy -> chain -> fold -> finish.
@@ -25,12 +25,13 @@
 
 namespace {
 
+#include "pair_row.h"  // the fixed-order fold of d4_fold_kernel (MI_FOLD_BLOCKS, mi_system_fold)
+
 #define D4_REFS 7          // references per element
 #define D4_SLOTS 16        // species whose contracted vectors one wave holds in LDS
 #define D4_WAVES 4         // waves (atoms) per block
 #define D4_WREC 24         // floats per atom in the weight records: w[8], dw/dCN[8], dw/dq[8]
 #define D4_PAIR 8          // floats per species pair: {1 / (rcov_i + rcov_j), delta, Q, R0^6, R0^8, 0, 0, 0}
-#define D4_FOLD_BLOCKS 64
 #define D4_ROW_WORDS 13    // doubles per row: energy, 6 virial words of the energy pass, 6 of the chain pass {xx, yy, zz, xy, xz, yz}
 
 template <class T> struct D4Rec;
@@ -387,26 +388,13 @@ __global__ __launch_bounds__(D4_WAVES * MI_WAVE) void d4_chain_kernel(const D4Re
   }
 }
 
-// ---- fold: block (x, s) sums the rows x*256 + t + k*D4_FOLD_BLOCKS*256 of system s in a fixed order; plain stores ----------------------------
+// ---- fold: mi_system_fold of pair_row.h over the first `words` words of a row; all D4_ROW_WORDS are written (the others as zeros) ------------
 __global__ __launch_bounds__(256) void d4_fold_kernel(const double* __restrict__ row, const int* __restrict__ batch_idx, int N, int words,
                                                       double* __restrict__ partial) {
-  const int s = blockIdx.y;
-  double a[D4_ROW_WORDS];
-#pragma unroll
-  for (int k = 0; k < D4_ROW_WORDS; ++k) a[k] = 0.0;
-  for (long long r = (long long)blockIdx.x * 256 + threadIdx.x; r < N; r += (long long)D4_FOLD_BLOCKS * 256) {
-    if (batch_idx && batch_idx[r] != s) continue;
+  mi_system_fold<D4_ROW_WORDS, MI_FOLD_BLOCKS>(batch_idx, N, D4_ROW_WORDS, partial, [&](long long r, double* a) {
 #pragma unroll
     for (int k = 0; k < D4_ROW_WORDS; ++k) if (k < words) a[k] += row[D4_ROW_WORDS * r + k];
-  }
-  __shared__ double part[256 / MI_WAVE][D4_ROW_WORDS];
-  const int lane = threadIdx.x & (MI_WAVE - 1), wave = threadIdx.x / MI_WAVE;
-#pragma unroll
-  for (int k = 0; k < D4_ROW_WORDS; ++k) { const double x = wave_sum(a[k]); if (lane == 0) part[wave][k] = x; }
-  __syncthreads();
-  if ((int)threadIdx.x < D4_ROW_WORDS)
-    partial[((size_t)s * D4_FOLD_BLOCKS + blockIdx.x) * D4_ROW_WORDS + threadIdx.x] =
-        part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+  });
 }
 
 __global__ void d4_finish_kernel(const double* __restrict__ partial, int B, int want_virial, float* __restrict__ energy, float* __restrict__ virial) {
@@ -415,8 +403,8 @@ __global__ void d4_finish_kernel(const double* __restrict__ partial, int B, int 
   const int s = t / 7, k = t - 7 * s;
   if (k > 0 && !want_virial) return;
   double x = 0.0;
-  for (int q = 0; q < D4_FOLD_BLOCKS; ++q) {
-    const double* p = partial + ((size_t)s * D4_FOLD_BLOCKS + q) * D4_ROW_WORDS;
+  for (int q = 0; q < MI_FOLD_BLOCKS; ++q) {
+    const double* p = partial + ((size_t)s * MI_FOLD_BLOCKS + q) * D4_ROW_WORDS;
     x += k == 0 ? p[0] : p[k] + p[6 + k];
   }
   if (k == 0) { energy[s] = (float)x; return; }
@@ -444,7 +432,7 @@ D4Layout d4_layout(int N, int B, int nz) {
   L.dEdCN = take(sizeof(double) * n);
   L.fdir = take(sizeof(double) * 3 * n);
   L.row = take(sizeof(double) * D4_ROW_WORDS * n);
-  L.partial = take(sizeof(double) * D4_ROW_WORDS * D4_FOLD_BLOCKS * b);
+  L.partial = take(sizeof(double) * D4_ROW_WORDS * MI_FOLD_BLOCKS * b);
   L.present = take(sizeof(int) * z);
   L.smap = take(sizeof(int) * z);
   L.zlist = take(sizeof(int) * z);
@@ -494,7 +482,7 @@ int d4_impl(const T* positions, const int32_t* numbers, int N, const int32_t* id
   MI_TIMED("d4_chain", st, (d4_chain_kernel<T, CSR><<<rows, D4_WAVES * MI_WAVE, 0, st>>>(rec, N, idx, ush, nptr, M, fill_value, cell, bi, info, ptab, P,
                                                                                         want_virial, dEdCN, fdir, row, forces)));
   MI_TIMED("d4_fold", st, {
-    d4_fold_kernel<<<dim3(D4_FOLD_BLOCKS, B), 256, 0, st>>>(row, bi, N, want_virial ? D4_ROW_WORDS : 1, partial);
+    d4_fold_kernel<<<dim3(MI_FOLD_BLOCKS, B), 256, 0, st>>>(row, bi, N, want_virial ? D4_ROW_WORDS : 1, partial);
     d4_finish_kernel<<<mi_blocks(7ll * B, 256), 256, 0, st>>>(partial, B, want_virial, energy, virial);
   });
   MI_LAUNCH_CHECK();
@@ -506,7 +494,7 @@ int d4_impl(const T* positions, const int32_t* numbers, int N, const int32_t* id
 }  // namespace
 
 extern "C" int mi_d4_species_slots(void) { return D4_SLOTS; }
-extern "C" int mi_d4_fold_blocks(void) { return D4_FOLD_BLOCKS; }
+extern "C" int mi_d4_fold_blocks(void) { return MI_FOLD_BLOCKS; }
 
 extern "C" size_t mi_d4_workspace_bytes(int n_atoms, int n_systems, int nz) {
   if (n_atoms < 0 || nz < 1 || n_systems < 1) return 0;

@@ -343,7 +343,7 @@ int d4_atm_impl(const T* positions, const int32_t* numbers, int N, const int32_t
   MI_TIMED("d4_atm_chain", st, (d4_chain_kernel<T, CSR><<<rows, D4_WAVES * MI_WAVE, 0, st>>>(rec, N, idx, ush, nptr, M, fill_value, cell, bi, info, ptab, P,
                                                                                             want_virial, dEdCN, fdir, row, forces)));
   MI_TIMED("d4_atm_fold", st, {
-    d4_fold_kernel<<<dim3(D4_FOLD_BLOCKS, B), 256, 0, st>>>(row, bi, N, want_virial ? D4_ROW_WORDS : 1, partial);
+    d4_fold_kernel<<<dim3(MI_FOLD_BLOCKS, B), 256, 0, st>>>(row, bi, N, want_virial ? D4_ROW_WORDS : 1, partial);
     d4_finish_kernel<<<mi_blocks(7ll * B, 256), 256, 0, st>>>(partial, B, want_virial, energy, virial);
   });
   MI_LAUNCH_CHECK();

@@ -27,21 +27,15 @@
 
 namespace {
 
-#define DP_FOLD_BLOCKS 64
+#include "pair_row.h"  // the row walk of dp_pair_kernel, the pack kernel and the fixed-order folds
+
 #define DP_VIR_WORDS 9
 #define DP_SF_WORDS 8  // {Re S_q, Im S_q, Re M_x, Im M_x, Re M_y, Im M_y, Re M_z, Im M_z}
 
-template <class T> struct DpRec { T x, y, z, q, mx, my, mz, pad; };  // 32 / 64 bytes: two vector loads of one line
-
-template <class T>
-__global__ void dp_pack_kernel(const T* __restrict__ pos, const T* __restrict__ q, const T* __restrict__ mu, int N, DpRec<T>* __restrict__ rec) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  DpRec<T> r;
-  r.x = pos[3 * (size_t)i]; r.y = pos[3 * (size_t)i + 1]; r.z = pos[3 * (size_t)i + 2]; r.q = q[i];
-  r.mx = mu[3 * (size_t)i]; r.my = mu[3 * (size_t)i + 1]; r.mz = mu[3 * (size_t)i + 2]; r.pad = T(0);
-  rec[i] = r;
-}
+template <class T> struct DpRec {  // 32 / 64 bytes: two vector loads of one line
+  T x, y, z, q, mx, my, mz, pad;
+  __device__ __forceinline__ void set_tail(const T* __restrict__ mu, size_t i) { mx = mu[3 * i]; my = mu[3 * i + 1]; mz = mu[3 * i + 2]; pad = T(0); }
+};
 
 __device__ __forceinline__ double dp_volume(const double* cm) {
   return fabs(cm[0] * (cm[4] * cm[8] - cm[5] * cm[7]) - cm[1] * (cm[3] * cm[8] - cm[5] * cm[6]) + cm[2] * (cm[3] * cm[7] - cm[4] * cm[6]));
@@ -54,13 +48,12 @@ __global__ __launch_bounds__(256) void dp_pair_kernel(const DpRec<T>* __restrict
                                                       int mask_value, int flags, double* __restrict__ energies, T* __restrict__ forces,
                                                       double* __restrict__ cgrad, double* __restrict__ dgrad, double* __restrict__ trow) {
   const int lane = threadIdx.x & (MI_WAVE - 1);
-  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / MI_WAVE) + threadIdx.x / MI_WAVE);
+  const int i = pair_row_index();
   if (i >= N) return;
   const int s = batch_idx ? batch_idx[i] : 0;
   const bool shifted = ush != nullptr;
   T cm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  if (shifted)
-    for (int k = 0; k < 9; ++k) cm[k] = cell[9 * (size_t)s + k];
+  if (shifted) pair_row_cell(cell, s, cm);
   const double al = (double)alpha[s];
   const double ta = 2.0 * al * al, inv_a_sqrt_pi = 1.0 / (al * 1.7724538509055159);
   const DpRec<T> ri = rec[i];
@@ -69,18 +62,17 @@ __global__ __launch_bounds__(256) void dp_pair_kernel(const DpRec<T>* __restrict
   const bool wf = (flags & MI_DP_FORCES) != 0, wc = (flags & MI_DP_CHARGE_GRAD) != 0, wd = (flags & MI_DP_DIPOLE_GRAD) != 0;
   const bool wv = (flags & MI_DP_VIRIAL) != 0;
   long long beg, end;
-  if (CSR) { beg = nptr[i]; end = nptr[i + 1]; } else { beg = (long long)i * M; end = beg + M; }
+  pair_row_range<CSR>(nptr, i, M, beg, end);
   double eacc = 0.0, cgi = 0.0, fx = 0.0, fy = 0.0, fz = 0.0, dx_ = 0.0, dy_ = 0.0, dz_ = 0.0;
   double t[DP_VIR_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (long long e = beg + lane; e < end; e += MI_WAVE) {
     const int j = idx[e];
-    if ((!CSR && j == mask_value) || (unsigned)j >= (unsigned)N) continue;  // padding: mask_value, or any index outside [0, N)
+    if (pair_is_padding<CSR>(j, mask_value, N)) continue;
     const DpRec<T> rj = rec[j];
     T sx = rj.x - ri.x, sy = rj.y - ri.y, sz = rj.z - ri.z;
     if (shifted) {
-      const T fs[3] = {(T)ush[3 * e], (T)ush[3 * e + 1], (T)ush[3 * e + 2]};
       T sh[3];
-      rowvec_mat3(fs, cm, sh);
+      pair_separation(ush, e, cm, sh);
       sx += sh[0]; sy += sh[1]; sz += sh[2];
     }
     const T r2t = sx * sx + sy * sy + sz * sz;
@@ -136,28 +128,13 @@ __global__ __launch_bounds__(256) void dp_pair_kernel(const DpRec<T>* __restrict
   }
 }
 
-// wave sums of a[0..W) -> part[wave][0..W) -> the first W threads add the four wave partials in a fixed order into out[0..W)
-template <int W> __device__ __forceinline__ void dp_block_fold(double* a, double (*part)[W], double* __restrict__ out) {
-  const int lane = threadIdx.x & (MI_WAVE - 1), wave = threadIdx.x / MI_WAVE;
-#pragma unroll
-  for (int k = 0; k < W; ++k) { const double v = wave_sum(a[k]); if (lane == 0) part[wave][k] = v; }
-  __syncthreads();
-  if ((int)threadIdx.x < W) out[threadIdx.x] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
-}
-
-// per-system fold of the per-row virials: block (x, s) sums the rows x*256 + t + k*DP_FOLD_BLOCKS*256 of system s in a fixed order and writes
-// partial[s][x][0..9) with plain stores; the caller sums the DP_FOLD_BLOCKS rows.  No atomics.
+// per-system fold of the per-row virials: partial[s][x][0..9) with plain stores; the caller sums the MI_FOLD_BLOCKS rows.  No atomics.
 __global__ __launch_bounds__(256) void dp_fold_kernel(const double* __restrict__ trow, const int* __restrict__ batch_idx, int N,
                                                       double* __restrict__ partial) {
-  const int s = blockIdx.y;
-  double a[DP_VIR_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (long long r = (long long)blockIdx.x * 256 + threadIdx.x; r < N; r += (long long)DP_FOLD_BLOCKS * 256) {
-    if (batch_idx && batch_idx[r] != s) continue;
+  mi_system_fold<DP_VIR_WORDS, MI_FOLD_BLOCKS>(batch_idx, N, DP_VIR_WORDS, partial, [&](long long r, double* a) {
 #pragma unroll
     for (int k = 0; k < DP_VIR_WORDS; ++k) a[k] += trow[DP_VIR_WORDS * r + k];
-  }
-  __shared__ double part[256 / MI_WAVE][DP_VIR_WORDS];
-  dp_block_fold<DP_VIR_WORDS>(a, part, partial + ((size_t)s * DP_FOLD_BLOCKS + blockIdx.x) * DP_VIR_WORDS);
+  });
 }
 
 // table[b][k] = {S_q, M_x, M_y, M_z} = sum_j g_j {q_j, mu_j} exp(i k.r_j), unscaled (the consumers apply G_k).  Block (k, b): thread t takes
@@ -180,7 +157,7 @@ __global__ __launch_bounds__(256) void dp_sf_kernel(const T* __restrict__ pos, c
     a[0] += qj * cs; a[1] += qj * sn; a[2] += mx * cs; a[3] += mx * sn; a[4] += my * cs; a[5] += my * sn; a[6] += mz * cs; a[7] += mz * sn;
   }
   __shared__ double part[256 / MI_WAVE][DP_SF_WORDS];
-  dp_block_fold<DP_SF_WORDS>(a, part, table + DP_SF_WORDS * ((size_t)b * K + k));
+  mi_block_fold<DP_SF_WORDS>(a, part, table + DP_SF_WORDS * ((size_t)b * K + k), DP_SF_WORDS);
 }
 
 // One wave per atom, lanes stride k.  With X = table (no weights) or X = g_i table + table_g (adjoint; f = 1/2 then, 1 otherwise), D = i k.M^X,
@@ -279,14 +256,14 @@ __global__ __launch_bounds__(256) void dp_recip_virial_kernel(const double* __re
       for (int r = 0; r < 3; ++r) a[3 * p + r] += (p == r ? ek : 0.0) + c * kk[p] * kk[r] + green * kk[p] * (si * mre[r] - sr * mim[r]);
   }
   __shared__ double part[256 / MI_WAVE][DP_VIR_WORDS];
-  dp_block_fold<DP_VIR_WORDS>(a, part, virial + DP_VIR_WORDS * (size_t)b);
+  mi_block_fold<DP_VIR_WORDS>(a, part, virial + DP_VIR_WORDS * (size_t)b, DP_VIR_WORDS);
 }
 
 size_t dp_rec_bytes(int n_atoms, int dtype) { return mi_align((dtype == MI_F32 ? sizeof(DpRec<float>) : sizeof(DpRec<double>)) * (size_t)(n_atoms > 0 ? n_atoms : 0)); }
 
 }  // namespace
 
-extern "C" int mi_ewald_dipole_blocks(void) { return DP_FOLD_BLOCKS; }
+extern "C" int mi_ewald_dipole_blocks(void) { return MI_FOLD_BLOCKS; }
 extern "C" size_t mi_ewald_dipole_real_scratch_bytes(int n_atoms, int dtype) {
   return dp_rec_bytes(n_atoms, dtype) + mi_align(sizeof(double) * DP_VIR_WORDS * (size_t)(n_atoms > 0 ? n_atoms : 0));
 }
@@ -316,8 +293,8 @@ extern "C" int mi_ewald_dipole_real(const void* positions, const void* charges, 
   const int32_t* bi = n_systems > 1 ? batch_idx : nullptr;  // one system: every atom belongs to system 0 and the batch index is not read
 #define MI_DP(T_, CSR_)                                                                                                                          \
   do {                                                                                                                                           \
-    dp_pack_kernel<T_><<<mi_blocks(n_atoms, 256), 256, 0, st>>>((const T_*)positions, (const T_*)charges, (const T_*)dipoles, n_atoms,           \
-                                                                (DpRec<T_>*)scratch);                                                            \
+    pair_pack_kernel<<<mi_blocks(n_atoms, 256), 256, 0, st>>>((const T_*)positions, (const T_*)charges, (const T_*)dipoles, n_atoms,             \
+                                                              (DpRec<T_>*)scratch);                                                              \
     dp_pair_kernel<T_, CSR_><<<blocks, 256, 0, st>>>((const DpRec<T_>*)scratch, (const T_*)cell, (const T_*)alpha, bi, weights, n_atoms, idx_j,  \
                                                      unit_shifts, neighbor_ptr, max_neighbors, mask_value, flags, energies, (T_*)forces,         \
                                                      charge_grads, dipole_grads, trow);                                                          \
@@ -329,7 +306,7 @@ extern "C" int mi_ewald_dipole_real(const void* positions, const void* charges, 
 #undef MI_DP
   MI_LAUNCH_CHECK();
   if (virial) {
-    dp_fold_kernel<<<dim3(DP_FOLD_BLOCKS, n_systems), 256, 0, st>>>(trow, bi, n_atoms, virial_partial);
+    dp_fold_kernel<<<dim3(MI_FOLD_BLOCKS, n_systems), 256, 0, st>>>(trow, bi, n_atoms, virial_partial);
     MI_LAUNCH_CHECK();
   }
   return MI_OK;

@@ -18,6 +18,8 @@
 
 namespace {
 
+#include "pair_row.h"  // MiNewton::rcp, erfc_as_poly<Math> and the fixed-order fold of ew_virial_fold_kernel
+
 // 1/x and 1/sqrt(x) in fp64 from the hardware seeds (v_rcp_f64 / v_rsq_f64, ~26 bits) + two Newton steps: <= 1 ulp, ~7 / ~10 instructions
 // against ~25 for an IEEE divide and ~30 + 25 for sqrt followed by a divide.  The real-space pass is fp64-VALU-bound; results move in the
 // last bit only (the parity bar of this path is 1e-10 relative).  EW_IEEE_DIV=1 restores the IEEE forms (A/B).
@@ -28,12 +30,10 @@ __device__ __forceinline__ double ew_rcp(double x) {
 #if EW_IEEE_DIV
   return 1.0 / x;
 #else
-  double y = __builtin_amdgcn_rcp(x);
-  y = fma(fma(-x, y, 1.0), y, y);
-  y = fma(fma(-x, y, 1.0), y, y);
-  return y;
+  return MiNewton::rcp(x);
 #endif
 }
+struct EwMath { static __device__ __forceinline__ double rcp(double x) { return ew_rcp(x); } };
 __device__ __forceinline__ double ew_rsqrt(double x) {
   double y = __builtin_amdgcn_rsq(x);
   y = y * fma(-0.5 * x * y, y, 1.5);
@@ -51,14 +51,7 @@ template <class T> __device__ __forceinline__ void ew_dist(T sx, T sy, T sz, dou
     rinv = ew_rcp(dist);
   }
 }
-__device__ __forceinline__ double erfc_as_poly(double x, double e_neg_x2) {
-  // x >= 0 here (alpha * distance); constants verbatim from math/math.py:73-78
-  const double p = 0.3275911, a1 = 0.254829592, a2 = -0.284496736, a3 = 1.421413741, a4 = -1.453152027, a5 = 1.061405429;
-  const double t = ew_rcp(1.0 + p * x);
-  const double t2 = t * t, t3 = t2 * t, t4 = t3 * t, t5 = t4 * t;
-  const double poly = a1 * t + a2 * t2 + a3 * t3 + a4 * t4 + a5 * t5;
-  return poly * e_neg_x2;
-}
+__device__ __forceinline__ double erfc_as_poly(double x, double e_neg_x2) { return erfc_as_poly<EwMath>(x, e_neg_x2); }
 
 // Order-sensitive 64-bit mix of one stored entry: two independent 32-bit mixes of (a, b, S) side by side, summed per direction in 64 bits.
 // The list counts as symmetric iff the forward sum (entries as stored) equals the reverse sum (entries mirrored): a false "symmetric"
@@ -406,26 +399,14 @@ __global__ __launch_bounds__(EW_BWD_SLOTS) void ew_bwd_reduce_kernel(const doubl
   }
 }
 
-// per-system fold of the per-row virials of ewald_real_kernel<..., VIR = true>: block (x, s) sums the rows r = x*256 + t + k*EW_VIR_BLOCKS*256 of
-// system s in a fixed order and writes partial[s][x][0..5] with plain stores; the caller folds the EW_VIR_BLOCKS rows (deterministic, no atomics).
-// A batch reads batch_idx once per (row, system): n_systems * n_atoms int loads, L2-resident for the batches this is used with.
-#define EW_VIR_BLOCKS 64
+// per-system fold of the per-row virials of ewald_real_kernel<..., VIR = true>: partial[s][x][0..5] with plain stores; the caller folds the
+// MI_FOLD_BLOCKS rows (deterministic, no atomics).
 __global__ __launch_bounds__(256) void ew_virial_fold_kernel(const double* __restrict__ vrow, const int* __restrict__ batch_idx, int N,
                                                              double* __restrict__ partial) {
-  const int s = blockIdx.y;
-  double a[6] = {0, 0, 0, 0, 0, 0};
-  for (long long r = (long long)blockIdx.x * 256 + threadIdx.x; r < N; r += (long long)EW_VIR_BLOCKS * 256) {
-    if (batch_idx && batch_idx[r] != s) continue;
+  mi_system_fold<6, MI_FOLD_BLOCKS>(batch_idx, N, 6, partial, [&](long long r, double* a) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) a[k] += vrow[6 * r + k];
-  }
-  __shared__ double part[256 / MI_WAVE][6];
-  const int lane = threadIdx.x & (MI_WAVE - 1), wave = threadIdx.x / MI_WAVE;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) { const double t = wave_sum(a[k]); if (lane == 0) part[wave][k] = t; }
-  __syncthreads();
-  if (threadIdx.x < 6)
-    partial[((size_t)s * EW_VIR_BLOCKS + blockIdx.x) * 6 + threadIdx.x] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+  });
 }
 
 // general adjoint for lists that are not symmetric: entry (i -> j) belongs to E_i only, so it carries weight g_i to BOTH ends
@@ -1106,7 +1087,7 @@ extern "C" int mi_ewald_real_listed(const void* positions, const void* charges, 
                          energies, forces, charge_grads, scratch, scratch_bytes, search_num_neighbors, verify_stride, verify_phase, nullptr, stream);
 }
 
-extern "C" int mi_ewald_virial_blocks(void) { return EW_VIR_BLOCKS; }
+extern "C" int mi_ewald_virial_blocks(void) { return MI_FOLD_BLOCKS; }
 extern "C" int mi_ewald_real_virial(const void* positions, const void* charges, const void* cell, const void* alpha, const int32_t* batch_idx,
                                     int n_atoms, int n_systems, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
                                     const int32_t* neighbor_ptr, int max_neighbors, int mask_value, int flags, double* energies, void* forces,
@@ -1120,7 +1101,7 @@ extern "C" int mi_ewald_real_virial(const void* positions, const void* charges, 
                                  row_virial, stream);
   if (rc != MI_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  ew_virial_fold_kernel<<<dim3(EW_VIR_BLOCKS, n_systems), 256, 0, st>>>(row_virial, n_systems > 1 ? batch_idx : nullptr, n_atoms, virial_partial);
+  ew_virial_fold_kernel<<<dim3(MI_FOLD_BLOCKS, n_systems), 256, 0, st>>>(row_virial, n_systems > 1 ? batch_idx : nullptr, n_atoms, virial_partial);
   MI_LAUNCH_CHECK();
   return MI_OK;
 }

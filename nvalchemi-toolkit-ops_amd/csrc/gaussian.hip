@@ -24,27 +24,24 @@
 //     dL/dsigma_i  = -(4 / sqrt(pi)) q_i sigma_i sum_row w q_j exp(-x^2) / g_ij^3     (self-image entries (i, i, S) included correctly)
 //     per system   : MI_GC_VIRIAL     W[a][b]      = -sum_entries w fm r_a r_b   (-dE/d(strain); six components)
 //                    MI_GC_CELL_GRAD  dL/dcell[a][b] = sum_entries w fm S_a r_b  (nine components)
-// The per-system sums are written per row and folded in a fixed order by gc_fold_kernel (the scheme of ew_virial_fold_kernel).
+// The per-system sums are written per row and folded in a fixed order by gc_fold_kernel (mi_system_fold of pair_row.h, which also holds the
+// row walk of gc_pair_kernel and the pack kernel).
 #include "common.h"
 
 namespace {
 
-#define GC_FOLD_BLOCKS 64
+#include "pair_row.h"
+
 #define GC_ROW_WORDS 9  // doubles per row of the per-row tensor buffer (6 used by the virial, 9 by the cell gradient)
 
-template <class T> struct GcRec { T x, y, z, q, sg, pad0, pad1, pad2; };  // 32 / 64 bytes: two vector loads of one line
-
-template <class T>
-__global__ void gc_pack_kernel(const T* __restrict__ pos, const T* __restrict__ q, const T* __restrict__ sigma, int N, GcRec<T>* __restrict__ rec) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  GcRec<T> r;
-  r.x = pos[3 * (size_t)i]; r.y = pos[3 * (size_t)i + 1]; r.z = pos[3 * (size_t)i + 2]; r.q = q[i];
-  const T sg = sigma[i];
-  r.sg = sg > T(0) ? sg : T(0);  // (NaN -> 0 as well)
-  r.pad0 = r.pad1 = r.pad2 = T(0);
-  rec[i] = r;
-}
+template <class T> struct GcRec {  // 32 / 64 bytes: two vector loads of one line
+  T x, y, z, q, sg, pad0, pad1, pad2;
+  __device__ __forceinline__ void set_tail(const T* __restrict__ sigma, size_t i) {
+    const T s = sigma[i];
+    sg = s > T(0) ? s : T(0);  // (NaN -> 0 as well)
+    pad0 = pad1 = pad2 = T(0);
+  }
+};
 
 template <class T, bool CSR>
 __global__ __launch_bounds__(256) void gc_pair_kernel(const GcRec<T>* __restrict__ rec, const T* __restrict__ cell, const int* __restrict__ batch_idx,
@@ -53,14 +50,11 @@ __global__ __launch_bounds__(256) void gc_pair_kernel(const GcRec<T>* __restrict
                                                       T* __restrict__ forces, double* __restrict__ cgrad, double* __restrict__ sgrad,
                                                       double* __restrict__ trow) {
   const int lane = threadIdx.x & (MI_WAVE - 1);
-  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / MI_WAVE) + threadIdx.x / MI_WAVE);
+  const int i = pair_row_index();
   if (i >= N) return;
   const bool shifted = ush != nullptr && cell != nullptr;
   T cm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  if (shifted) {
-    const int s = batch_idx ? batch_idx[i] : 0;
-    for (int k = 0; k < 9; ++k) cm[k] = cell[9 * (size_t)s + k];
-  }
+  if (shifted) pair_row_cell(cell, batch_idx ? batch_idx[i] : 0, cm);
   const GcRec<T> ri = rec[i];
   const double qi = (double)ri.q, sgi = (double)ri.sg, si = sgi * sgi;
   const double gi = g ? g[i] : 1.0;
@@ -68,20 +62,18 @@ __global__ __launch_bounds__(256) void gc_pair_kernel(const GcRec<T>* __restrict
   const bool wv = (flags & MI_GC_VIRIAL) != 0, wg = (flags & MI_GC_CELL_GRAD) != 0 && !wv;
   const double two_over_sqrt_pi = 2.0 / 1.7724538509055159;
   long long beg, end;
-  if (CSR) { beg = nptr[i]; end = nptr[i + 1]; } else { beg = (long long)i * M; end = beg + M; }
+  pair_row_range<CSR>(nptr, i, M, beg, end);
   double eacc = 0.0, cgi = 0.0, sgacc = 0.0, fx = 0.0, fy = 0.0, fz = 0.0;
   double t[GC_ROW_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (long long e = beg + lane; e < end; e += MI_WAVE) {
     const int j = idx[e];
-    if ((!CSR && j == mask_value) || (unsigned)j >= (unsigned)N) continue;  // padding: mask_value, or any index outside [0, N)
+    if (pair_is_padding<CSR>(j, mask_value, N)) continue;
     const GcRec<T> rj = rec[j];
     T sx = rj.x - ri.x, sy = rj.y - ri.y, sz = rj.z - ri.z;
-    int S0 = 0, S1 = 0, S2 = 0;
+    int3 S = {0, 0, 0};
     if (shifted) {
-      S0 = ush[3 * e]; S1 = ush[3 * e + 1]; S2 = ush[3 * e + 2];
-      const T fs[3] = {(T)S0, (T)S1, (T)S2};
       T sh[3];
-      rowvec_mat3(fs, cm, sh);
+      S = pair_separation(ush, e, cm, sh);
       sx += sh[0]; sy += sh[1]; sz += sh[2];
     }
     const T r2t = sx * sx + sy * sy + sz * sz;
@@ -112,7 +104,7 @@ __global__ __launch_bounds__(256) void gc_pair_kernel(const GcRec<T>* __restrict
         t[3] -= fm * (dx * dy); t[4] -= fm * (dx * dz); t[5] -= fm * (dy * dz);
       }
       if (wg) {
-        const double a0 = fm * (double)S0, a1 = fm * (double)S1, a2 = fm * (double)S2;
+        const double a0 = fm * (double)S.x, a1 = fm * (double)S.y, a2 = fm * (double)S.z;
         t[0] += a0 * dx; t[1] += a0 * dy; t[2] += a0 * dz;
         t[3] += a1 * dx; t[4] += a1 * dy; t[5] += a1 * dz;
         t[6] += a2 * dx; t[7] += a2 * dy; t[8] += a2 * dz;
@@ -138,25 +130,13 @@ __global__ __launch_bounds__(256) void gc_pair_kernel(const GcRec<T>* __restrict
   }
 }
 
-// per-system fold of the per-row tensors: block (x, s) sums the rows x*256 + t + k*GC_FOLD_BLOCKS*256 of system s in a fixed order and
-// writes partial[s][x][0..words) with plain stores; the caller sums the GC_FOLD_BLOCKS rows.  No atomics.
+// per-system fold of the per-row tensors: partial[s][x][0..words) with plain stores; the caller sums the MI_FOLD_BLOCKS rows.  No atomics.
 __global__ __launch_bounds__(256) void gc_fold_kernel(const double* __restrict__ trow, const int* __restrict__ batch_idx, int N, int words,
                                                       double* __restrict__ partial) {
-  const int s = blockIdx.y;
-  double a[GC_ROW_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (long long r = (long long)blockIdx.x * 256 + threadIdx.x; r < N; r += (long long)GC_FOLD_BLOCKS * 256) {
-    if (batch_idx && batch_idx[r] != s) continue;
+  mi_system_fold<GC_ROW_WORDS, MI_FOLD_BLOCKS>(batch_idx, N, words, partial, [&](long long r, double* a) {
 #pragma unroll
     for (int k = 0; k < GC_ROW_WORDS; ++k) if (k < words) a[k] += trow[GC_ROW_WORDS * r + k];
-  }
-  __shared__ double part[256 / MI_WAVE][GC_ROW_WORDS];
-  const int lane = threadIdx.x & (MI_WAVE - 1), wave = threadIdx.x / MI_WAVE;
-#pragma unroll
-  for (int k = 0; k < GC_ROW_WORDS; ++k) { const double v = wave_sum(a[k]); if (lane == 0) part[wave][k] = v; }
-  __syncthreads();
-  if ((int)threadIdx.x < words)
-    partial[((size_t)s * GC_FOLD_BLOCKS + blockIdx.x) * GC_ROW_WORDS + threadIdx.x] =
-        part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+  });
 }
 
 // per-system sums of the O(N) background term, in the same fixed order: partial[s][x][0..2] = block partials of {q, q s, g q s} over the atoms
@@ -164,28 +144,18 @@ __global__ __launch_bounds__(256) void gc_fold_kernel(const double* __restrict__
 template <class T>
 __global__ __launch_bounds__(256) void gc_system_sums_kernel(const T* __restrict__ q, const T* __restrict__ sigma, const double* __restrict__ g,
                                                              const int* __restrict__ batch_idx, int N, double* __restrict__ partial) {
-  const int s = blockIdx.y;
-  double a[3] = {0, 0, 0};
-  for (long long r = (long long)blockIdx.x * 256 + threadIdx.x; r < N; r += (long long)GC_FOLD_BLOCKS * 256) {
-    if (batch_idx && batch_idx[r] != s) continue;
+  mi_system_fold<3, MI_FOLD_BLOCKS>(batch_idx, N, 3, partial, [&](long long r, double* a) {
     const double qr = (double)q[r], sg = (double)sigma[r];
     const double qs = sg > 0.0 ? qr * (sg * sg) : 0.0;
     a[0] += qr; a[1] += qs; a[2] += g ? g[r] * qs : qs;
-  }
-  __shared__ double part[256 / MI_WAVE][3];
-  const int lane = threadIdx.x & (MI_WAVE - 1), wave = threadIdx.x / MI_WAVE;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { const double v = wave_sum(a[k]); if (lane == 0) part[wave][k] = v; }
-  __syncthreads();
-  if (threadIdx.x < 3)
-    partial[((size_t)s * GC_FOLD_BLOCKS + blockIdx.x) * 3 + threadIdx.x] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+  });
 }
 
 size_t gc_rec_bytes(int n_atoms, int dtype) { return mi_align((dtype == MI_F32 ? sizeof(GcRec<float>) : sizeof(GcRec<double>)) * (size_t)(n_atoms > 0 ? n_atoms : 0)); }
 
 }  // namespace
 
-extern "C" int mi_gaussian_charges_blocks(void) { return GC_FOLD_BLOCKS; }
+extern "C" int mi_gaussian_charges_blocks(void) { return MI_FOLD_BLOCKS; }
 extern "C" int mi_gaussian_charges_row_words(void) { return GC_ROW_WORDS; }
 extern "C" size_t mi_gaussian_charges_scratch_bytes(int n_atoms, int dtype) {
   return gc_rec_bytes(n_atoms, dtype) + mi_align(sizeof(double) * GC_ROW_WORDS * (size_t)(n_atoms > 0 ? n_atoms : 0));
@@ -201,9 +171,9 @@ extern "C" int mi_gaussian_charges_system_sums(const void* charges, const void* 
   hipStream_t st = (hipStream_t)stream;
   const int32_t* bi = n_systems > 1 ? batch_idx : nullptr;
   if (dtype == MI_F32)
-    gc_system_sums_kernel<float><<<dim3(GC_FOLD_BLOCKS, n_systems), 256, 0, st>>>((const float*)charges, (const float*)sigma, weights, bi, n_atoms, partial);
+    gc_system_sums_kernel<float><<<dim3(MI_FOLD_BLOCKS, n_systems), 256, 0, st>>>((const float*)charges, (const float*)sigma, weights, bi, n_atoms, partial);
   else
-    gc_system_sums_kernel<double><<<dim3(GC_FOLD_BLOCKS, n_systems), 256, 0, st>>>((const double*)charges, (const double*)sigma, weights, bi, n_atoms, partial);
+    gc_system_sums_kernel<double><<<dim3(MI_FOLD_BLOCKS, n_systems), 256, 0, st>>>((const double*)charges, (const double*)sigma, weights, bi, n_atoms, partial);
   MI_LAUNCH_CHECK();
   return MI_OK;
 }
@@ -236,7 +206,7 @@ extern "C" int mi_gaussian_charges(const void* positions, const void* charges, c
   const int32_t* bi = n_systems > 1 ? batch_idx : nullptr;
 #define MI_GC(T_, CSR_)                                                                                                                        \
   do {                                                                                                                                         \
-    gc_pack_kernel<T_><<<mi_blocks(n_atoms, 256), 256, 0, st>>>((const T_*)positions, (const T_*)charges, (const T_*)sigma, n_atoms, (GcRec<T_>*)scratch); \
+    pair_pack_kernel<<<mi_blocks(n_atoms, 256), 256, 0, st>>>((const T_*)positions, (const T_*)charges, (const T_*)sigma, n_atoms, (GcRec<T_>*)scratch); \
     gc_pair_kernel<T_, CSR_><<<blocks, 256, 0, st>>>((const GcRec<T_>*)scratch, (const T_*)cell, bi, weights, n_atoms, idx_j, unit_shifts,     \
                                                      neighbor_ptr, max_neighbors, mask_value, flags, energies, (T_*)forces, charge_grads,      \
                                                      sigma_grads, trow);                                                                       \
@@ -248,7 +218,7 @@ extern "C" int mi_gaussian_charges(const void* positions, const void* charges, c
 #undef MI_GC
   MI_LAUNCH_CHECK();
   if (tensor) {
-    gc_fold_kernel<<<dim3(GC_FOLD_BLOCKS, n_systems), 256, 0, st>>>(trow, bi, n_atoms, (flags & MI_GC_VIRIAL) ? 6 : 9, system_partial);
+    gc_fold_kernel<<<dim3(MI_FOLD_BLOCKS, n_systems), 256, 0, st>>>(trow, bi, n_atoms, (flags & MI_GC_VIRIAL) ? 6 : 9, system_partial);
     MI_LAUNCH_CHECK();
   }
   return MI_OK;

@@ -5,7 +5,7 @@
 // the Gaussian-charge electrostatic energy of this package (point-charge Ewald / PME + gaussian_charge_correction, or erf(r/g)/r pairs without
 // a cell).  E_el is a quadratic form, and the geometry does not change during a solve, so the real-space part of its Hessian is a constant
 // sparse matrix over the caller's FULL neighbour list:
-//     c_e = [erfc_AS(a_s r) - erfc(r / g_ij)] / r      with a cell  (erfc_AS: the Abramowitz-Stegun polynomial of ewald.hip, restated below;
+//     c_e = [erfc_AS(a_s r) - erfc(r / g_ij)] / r      with a cell  (erfc_AS: the Abramowitz-Stegun polynomial ewald.hip uses, pair_row.h;
 //                                                                   erfc: the device library's, as in gaussian.hip)
 //     c_e = [1 - erfc(r / g_ij)] / r                   without one
 //     d_i = J_i + [sigma_i > 0] / (sqrt(pi) sigma_i)   hardness + Gaussian self term
@@ -19,35 +19,21 @@
 // index, so the product kernel gathers x[neighbors[e]] without a padding branch and without leaving [0, N).
 //
 // Kernels: qeq_coef_kernel (once per geometry), qeq_apply_kernel (y = y_in + d x + A x: one wave64 per row, nothing but two stream loads, one
-// 8-byte gather and one FMA per slot), qeq_fold_kernel (per-system block partials of sum y and x.y in a fixed order, the scheme of
-// gc_fold_kernel) and the two vector kernels of a CG iteration.  Every reduction is a wave reduction in a fixed order, every store a plain
+// 8-byte gather and one FMA per slot), qeq_fold_kernel (per-system block partials of sum y and x.y in a fixed order: mi_system_fold of
+// pair_row.h) and the two vector kernels of a CG iteration.  Every reduction is a wave reduction in a fixed order, every store a plain
 // vector store, there are no atomics: these kernels are bit-reproducible (a periodic solve as a whole is not: the reciprocal-space calls the
 // driver makes between them add with atomics in arrival order).
 //
-// The fold and CG kernels run on a grid (QEQ_FOLD_BLOCKS, n_systems), so n_systems <= 65535 (checked), and every block scans batch_idx once:
-// O(N n_systems) index reads per launch, as gc_fold_kernel.  Fine for a few large systems; thousands of small ones would want per-system
+// The fold and CG kernels run on a grid (MI_FOLD_BLOCKS, n_systems), so n_systems <= 65535 (checked), and every block scans batch_idx once:
+// O(N n_systems) index reads per launch, as every mi_system_fold.  Fine for a few large systems; thousands of small ones would want per-system
 // atom ranges (batch_idx sorted), which are not built.
 #include "common.h"
 
 namespace {
 
-#define QEQ_FOLD_BLOCKS 64  // block partials per system; == MI_WAVE, so one wave folds them with one wave_sum
-#define QEQ_STATE_WORDS 8   // doubles of solver state per system: {r.r, b.b, done, iterations, alpha, beta, 0, 0}
+#include "pair_row.h"  // the row walk of qeq_coef_kernel, the fixed-order fold, erfc_as_poly with the Newton reciprocal as ewald.hip runs it
 
-// 1/x from the hardware seed + two Newton steps and the A&S 7.1.26 polynomial exactly as ewald.hip evaluates them (ew_rcp, erfc_as_poly)
-__device__ __forceinline__ double qeq_rcp(double x) {
-  double y = __builtin_amdgcn_rcp(x);
-  y = fma(fma(-x, y, 1.0), y, y);
-  y = fma(fma(-x, y, 1.0), y, y);
-  return y;
-}
-__device__ __forceinline__ double qeq_erfc_as(double x, double e_neg_x2) {
-  const double p = 0.3275911, a1 = 0.254829592, a2 = -0.284496736, a3 = 1.421413741, a4 = -1.453152027, a5 = 1.061405429;
-  const double t = qeq_rcp(1.0 + p * x);
-  const double t2 = t * t, t3 = t2 * t, t4 = t3 * t, t5 = t4 * t;
-  const double poly = a1 * t + a2 * t2 + a3 * t3 + a4 * t4 + a5 * t5;
-  return poly * e_neg_x2;
-}
+#define QEQ_STATE_WORDS 8   // doubles of solver state per system: {r.r, b.b, done, iterations, alpha, beta, 0, 0}
 
 template <class T, bool CSR>
 __global__ __launch_bounds__(256) void qeq_coef_kernel(const T* __restrict__ pos, const T* __restrict__ sigma, const double* __restrict__ hardness,
@@ -56,7 +42,7 @@ __global__ __launch_bounds__(256) void qeq_coef_kernel(const T* __restrict__ pos
                                                        int M, int mask_value, double* __restrict__ coef, int* __restrict__ nbr,
                                                        double* __restrict__ diag) {
   const int lane = threadIdx.x & (MI_WAVE - 1);
-  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / MI_WAVE) + threadIdx.x / MI_WAVE);
+  const int i = pair_row_index();
   if (i >= N) return;
   const bool periodic = cell != nullptr;
   const bool shifted = periodic && ush != nullptr;
@@ -64,25 +50,24 @@ __global__ __launch_bounds__(256) void qeq_coef_kernel(const T* __restrict__ pos
   double al = 0.0;
   if (periodic) {
     const int s = batch_idx ? batch_idx[i] : 0;
-    for (int k = 0; k < 9; ++k) cm[k] = cell[9 * (size_t)s + k];
+    pair_row_cell(cell, s, cm);
     al = (double)alpha[s];
   }
   const T pix = pos[3 * (size_t)i], piy = pos[3 * (size_t)i + 1], piz = pos[3 * (size_t)i + 2];
   const T sgt = sigma[i];
-  const double sgi = sgt > T(0) ? (double)sgt : 0.0, si = sgi * sgi;  // (NaN -> point charge, as gc_pack_kernel)
+  const double sgi = sgt > T(0) ? (double)sgt : 0.0, si = sgi * sgi;  // (NaN -> point charge, as GcRec::set_tail)
   if (lane == 0) diag[i] = hardness[i] + (sgi > 0.0 ? 1.0 / (1.7724538509055159 * sgi) : 0.0);
   long long beg, end;
-  if (CSR) { beg = nptr[i]; end = nptr[i + 1]; } else { beg = (long long)i * M; end = beg + M; }
+  pair_row_range<CSR>(nptr, i, M, beg, end);
   for (long long e = beg + lane; e < end; e += MI_WAVE) {
     const int j = idx[e];
     double c = 0.0;
     int jj = i;  // padding and skipped entries: coefficient 0 on the row's own index
-    if (!((!CSR && j == mask_value) || (unsigned)j >= (unsigned)N)) {
+    if (!pair_is_padding<CSR>(j, mask_value, N)) {
       T sx = pos[3 * (size_t)j] - pix, sy = pos[3 * (size_t)j + 1] - piy, sz = pos[3 * (size_t)j + 2] - piz;
       if (shifted) {
-        const T fs[3] = {(T)ush[3 * e], (T)ush[3 * e + 1], (T)ush[3 * e + 2]};
         T sh[3];
-        rowvec_mat3(fs, cm, sh);
+        pair_separation(ush, e, cm, sh);
         sx += sh[0]; sy += sh[1]; sz += sh[2];
       }
       const T r2t = sx * sx + sy * sy + sz * sz;
@@ -92,7 +77,7 @@ __global__ __launch_bounds__(256) void qeq_coef_kernel(const T* __restrict__ pos
         double lr = 1.0;  // long-ranged factor: erfc_AS(a r) with a cell, 1 without
         if (periodic) {
           const double ar = al * dist;
-          lr = qeq_erfc_as(ar, exp(-(ar * ar)));
+          lr = erfc_as_poly<MiNewton>(ar, exp(-(ar * ar)));
         }
         const T sgj = sigma[j];
         const double sj = sgj > T(0) ? (double)sgj : 0.0;
@@ -115,10 +100,10 @@ __global__ __launch_bounds__(256) void qeq_apply_kernel(const double* __restrict
                                                         const double* __restrict__ x, const double* y_in /* may be y */, int N,
                                                         const int* __restrict__ nptr, int M, double* y) {
   const int lane = threadIdx.x & (MI_WAVE - 1);
-  const int i = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x / MI_WAVE) + threadIdx.x / MI_WAVE);
+  const int i = pair_row_index();
   if (i >= N) return;
   long long beg, end;
-  if (CSR) { beg = nptr[i]; end = nptr[i + 1]; } else { beg = (long long)i * M; end = beg + M; }
+  pair_row_range<CSR>(nptr, i, M, beg, end);
   double acc = 0.0;
   long long e = beg + lane;
   for (; e + 3 * MI_WAVE < end; e += 4 * MI_WAVE) {
@@ -132,29 +117,20 @@ __global__ __launch_bounds__(256) void qeq_apply_kernel(const double* __restrict
   if (lane == 0) y[i] = (y_in ? y_in[i] : 0.0) + fma(diag[i], x[i], acc);
 }
 
-// block (b, s) sums {y, x y} over the atoms b*256 + t + k*QEQ_FOLD_BLOCKS*256 of system s in a fixed order: partial[s][b][0..1], plain stores
+// block (b, s) sums {y, x y} over the atoms of system s in the fixed order of mi_system_fold: partial[s][b][0..1], plain stores
 __global__ __launch_bounds__(256) void qeq_fold_kernel(const double* __restrict__ y, const double* __restrict__ x, const int* __restrict__ batch_idx,
                                                        int N, double* __restrict__ partial) {
-  const int s = blockIdx.y;
-  double a0 = 0.0, a1 = 0.0;
-  for (long long r = (long long)blockIdx.x * 256 + threadIdx.x; r < N; r += (long long)QEQ_FOLD_BLOCKS * 256) {
-    if (batch_idx && batch_idx[r] != s) continue;
+  mi_system_fold<2, MI_FOLD_BLOCKS>(batch_idx, N, 2, partial, [&](long long r, double* a) {
     const double yr = y[r];
-    a0 += yr; a1 = fma(x[r], yr, a1);
-  }
-  __shared__ double part[256 / MI_WAVE][2];
-  const int lane = threadIdx.x & (MI_WAVE - 1), wave = threadIdx.x / MI_WAVE;
-  a0 = wave_sum(a0); a1 = wave_sum(a1);
-  if (lane == 0) { part[wave][0] = a0; part[wave][1] = a1; }
-  __syncthreads();
-  if (threadIdx.x < 2)
-    partial[((size_t)s * QEQ_FOLD_BLOCKS + blockIdx.x) * 2 + threadIdx.x] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+    a[0] += yr; a[1] = fma(x[r], yr, a[1]);
+  });
 }
 
-// the QEQ_FOLD_BLOCKS block partials of word k of system s, summed by the calling wave: every lane of every wave of every block gets the
+// the MI_FOLD_BLOCKS block partials of word k of system s, summed by the calling wave: every lane of every wave of every block gets the
 // same bits (a butterfly of commutative additions), so all blocks of a system derive identical scalars without talking to each other
 __device__ __forceinline__ double qeq_total(const double* __restrict__ partial, int s, int words, int k) {
-  return wave_sum(partial[((size_t)s * QEQ_FOLD_BLOCKS + (threadIdx.x & (MI_WAVE - 1))) * words + k]);
+  static_assert(MI_FOLD_BLOCKS == MI_WAVE, "one wave folds the block partials of a system with one wave_sum");
+  return wave_sum(partial[((size_t)s * MI_FOLD_BLOCKS + (threadIdx.x & (MI_WAVE - 1))) * words + k]);
 }
 
 // First half of a CG iteration.  From the partials {sum y, p.y} of y = H p:  w = y - mean_s(y) (the projection),  alpha_s = r.r / p.w
@@ -181,7 +157,7 @@ __global__ __launch_bounds__(256) void qeq_cg_update_kernel(const double* __rest
     else done = true;
   }
   double acc = 0.0;
-  for (long long a = (long long)blockIdx.x * 256 + threadIdx.x; a < N; a += (long long)QEQ_FOLD_BLOCKS * 256) {
+  for (long long a = (long long)blockIdx.x * 256 + threadIdx.x; a < N; a += (long long)MI_FOLD_BLOCKS * 256) {
     if (batch_idx && batch_idx[a] != s) continue;
     double ra = init ? 0.0 : r[a];
     if (alpha != 0.0) {
@@ -197,7 +173,7 @@ __global__ __launch_bounds__(256) void qeq_cg_update_kernel(const double* __rest
   if (lane == 0) part[wave] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {
-    partial_rr[(size_t)s * QEQ_FOLD_BLOCKS + blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+    partial_rr[(size_t)s * MI_FOLD_BLOCKS + blockIdx.x] = part[0] + part[1] + part[2] + part[3];
     if (blockIdx.x == 0) {
       double* so = state_out + QEQ_STATE_WORDS * (size_t)s;
       so[0] = st[0]; so[1] = st[1]; so[2] = done ? 1.0 : 0.0; so[3] = st[3]; so[4] = alpha; so[5] = st[5]; so[6] = 0.0; so[7] = 0.0;
@@ -220,7 +196,7 @@ __global__ __launch_bounds__(256) void qeq_cg_direction_kernel(const double* __r
   if (mode == 0 && !was_done) { beta = rr_new / st[0]; iters += 1.0; }
   const bool done = was_done || !(bb > 0.0) || rr_new <= tol2 * bb;
   if (!was_done) {
-    for (long long a = (long long)blockIdx.x * 256 + threadIdx.x; a < N; a += (long long)QEQ_FOLD_BLOCKS * 256) {
+    for (long long a = (long long)blockIdx.x * 256 + threadIdx.x; a < N; a += (long long)MI_FOLD_BLOCKS * 256) {
       if (batch_idx && batch_idx[a] != s) continue;
       p[a] = mode == 0 ? fma(beta, p[a], r[a]) : r[a];
     }
@@ -233,7 +209,7 @@ __global__ __launch_bounds__(256) void qeq_cg_direction_kernel(const double* __r
 
 }  // namespace
 
-extern "C" int mi_qeq_blocks(void) { return QEQ_FOLD_BLOCKS; }
+extern "C" int mi_qeq_blocks(void) { return MI_FOLD_BLOCKS; }
 extern "C" int mi_qeq_state_words(void) { return QEQ_STATE_WORDS; }
 
 extern "C" int mi_qeq_pair_coefficients(const void* positions, const void* sigma, const double* hardness, const void* cell, const void* alpha,
@@ -283,7 +259,7 @@ extern "C" int mi_qeq_apply(const double* coefficients, const int32_t* neighbors
     if (neighbor_ptr) qeq_apply_kernel<true><<<blocks, 256, 0, st>>>(coefficients, neighbors, diagonal, x, y_in, n_atoms, neighbor_ptr, 0, y);
     else qeq_apply_kernel<false><<<blocks, 256, 0, st>>>(coefficients, neighbors, diagonal, x, y_in, n_atoms, nullptr, max_neighbors, y);
   }
-  if (partial) qeq_fold_kernel<<<dim3(QEQ_FOLD_BLOCKS, n_systems), 256, 0, st>>>(y, x, n_systems > 1 ? batch_idx : nullptr, n_atoms, partial);
+  if (partial) qeq_fold_kernel<<<dim3(MI_FOLD_BLOCKS, n_systems), 256, 0, st>>>(y, x, n_systems > 1 ? batch_idx : nullptr, n_atoms, partial);
   mi_timing_end(stream);
   MI_LAUNCH_CHECK();
   return MI_OK;
@@ -301,7 +277,7 @@ extern "C" int mi_qeq_cg_update(const double* y, const double* partial_y, const 
   MI_REQUIRE(state_in != state_out, "state_in and state_out must differ");
   MI_REQUIRE(n_atoms == 0 || (y && r && (mode == 1 || (q && p))), "null pointer");
   mi_timing_begin("qeq_cg_update", stream);
-  qeq_cg_update_kernel<<<dim3(QEQ_FOLD_BLOCKS, n_systems), 256, 0, (hipStream_t)stream>>>(y, partial_y, counts, n_systems > 1 ? batch_idx : nullptr,
+  qeq_cg_update_kernel<<<dim3(MI_FOLD_BLOCKS, n_systems), 256, 0, (hipStream_t)stream>>>(y, partial_y, counts, n_systems > 1 ? batch_idx : nullptr,
                                                                                          n_atoms, mode, q, r, p, state_in, state_out, partial_rr);
   mi_timing_end(stream);
   MI_LAUNCH_CHECK();
@@ -320,7 +296,7 @@ extern "C" int mi_qeq_cg_direction(const double* partial_rr, const int32_t* batc
   MI_REQUIRE(state_in != state_out, "state_in and state_out must differ");
   MI_REQUIRE(n_atoms == 0 || (r && p), "null pointer");
   mi_timing_begin("qeq_cg_direction", stream);
-  qeq_cg_direction_kernel<<<dim3(QEQ_FOLD_BLOCKS, n_systems), 256, 0, (hipStream_t)stream>>>(partial_rr, n_systems > 1 ? batch_idx : nullptr, n_atoms,
+  qeq_cg_direction_kernel<<<dim3(MI_FOLD_BLOCKS, n_systems), 256, 0, (hipStream_t)stream>>>(partial_rr, n_systems > 1 ? batch_idx : nullptr, n_atoms,
                                                                                             mode, tolerance * tolerance, r, p, state_in, state_out);
   mi_timing_end(stream);
   MI_LAUNCH_CHECK();

@@ -18,10 +18,10 @@ import ctypes
 import torch
 
 from nvalchemiops import _capi as C
+from nvalchemiops.interactions.electrostatics import _pairs as P
 from nvalchemiops.interactions.electrostatics.ewald import _prepare_alpha, _prepare_cell
-from nvalchemiops.interactions.electrostatics.gaussian import _check as _check_lists
 
-DP_FORCES, DP_CHARGE_GRAD, DP_DIPOLE_GRAD, DP_VIRIAL = 1, 2, 4, 8
+DP_FORCES, DP_CHARGE_GRAD, DP_DIPOLE_GRAD, DP_VIRIAL = P.FORCES, P.CHARGE_GRAD, P.THIRD_GRAD, P.VIRIAL
 _TABLE_WORDS = 8  # {Re S_q, Im S_q, Re M_x, Im M_x, Re M_y, Im M_y, Re M_z, Im M_z}
 
 _MODEL = """With R = r_j - r_i + S . cell and r = |R| for every stored entry (i, j, S), B0 = erfc(alpha r) / r,
@@ -49,60 +49,9 @@ _RETURNS = """Returns ``energies`` [N], or a tuple holding only what was asked f
     surface (non-tin-foil) terms.  CPU tensors raise NativeLibraryError: there is no fallback."""
 
 
-def _check(positions, charges, dipoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx,
-           alpha, compute_virial):
-    """Every argument error of the real-space term, before anything is launched: `gaussian_charge_correction`'s checks and messages, plus the
-    dipole shape, the required cell and the shifts a virial needs."""
-    if cell is None:
-        raise ValueError("cell is required: the point-dipole Ewald sum is periodic (cell=None clusters are out of scope)")
-    _check_lists(positions, charges, 0.0, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx,
-                 compute_virial)
-    _check_dipoles(positions, dipoles)
-    if compute_virial and (neighbor_shifts if neighbor_list is not None else neighbor_matrix_shifts) is None:
-        raise ValueError("compute_virial needs the shifts of the list: pass neighbor_shifts with neighbor_list, neighbor_matrix_shifts with neighbor_matrix")
-    n_cells = cell.shape[0] if cell.dim() == 3 else 1
-    if isinstance(alpha, torch.Tensor) and alpha.numel() > 1 and alpha.numel() != n_cells:
-        raise ValueError(f"alpha has {alpha.numel()} values but there are {n_cells} systems")
-
-
-def _check_dipoles(positions, dipoles):
-    n = positions.shape[0]
-    if dipoles.dim() != 2 or tuple(dipoles.shape) != (n, 3):
-        raise ValueError(f"dipoles must have one vector per atom: expected shape [{n}, 3], got {tuple(dipoles.shape)}")
-
-
-def _num_systems(cell, batch_idx) -> int:
-    return cell.reshape(-1, 3, 3).shape[0] if batch_idx is not None else 1
-
-
-def _zeros(n, nsys, dt, dev):
-    return (torch.zeros(n, dtype=dt, device=dev), torch.zeros((n, 3), dtype=dt, device=dev), torch.zeros(n, dtype=dt, device=dev),
-            torch.zeros((n, 3), dtype=dt, device=dev), torch.zeros((nsys, 3, 3), dtype=dt, device=dev))
-
-
-def _select(res, want):
-    out = tuple(r for r, w in zip(res, want) if w)
-    return out if len(out) > 1 else out[0]
-
-
 # ---- real space ---------------------------------------------------------------------------------------------------------------------------
-def _real_inputs(positions, charges, dipoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                 neighbor_matrix_shifts):
-    """Detached, contiguous launch tensors (device check included; shapes were checked by `_check`)."""
-    dt = positions.dtype
-    C.require_device(positions, charges, dipoles, cell, alpha, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts,
-                     batch_idx)
-    if neighbor_list is not None:
-        idx, nptr, m, sh = C.i32(neighbor_list[1]), C.i32(neighbor_ptr), 0, neighbor_shifts
-        n_entries = idx.shape[0]
-    else:
-        idx, nptr, m, sh = C.i32(neighbor_matrix), None, neighbor_matrix.shape[1], neighbor_matrix_shifts
-        n_entries = idx.numel()
-    cells = cell.detach().to(dt).reshape(-1, 3, 3).contiguous()
-    batched = batch_idx is not None
-    return dict(pos=positions.detach().contiguous(), q=charges.detach().to(dt).contiguous(), mu=dipoles.detach().to(dt).contiguous(), cells=cells,
-                al=alpha.detach().to(dt).reshape(-1).contiguous(), bi=C.i32(batch_idx) if batched else None,
-                nsys=cells.shape[0] if batched else 1, idx=idx, nptr=nptr, m=m, sh=None if sh is None else C.i32(sh), n_entries=n_entries)
+def _real_inputs(positions, charges, dipoles, cell, alpha, batch_idx, *lists):
+    return P.launch_inputs(positions, charges, cell, batch_idx, lists, mu=dipoles, al=alpha.reshape(-1))
 
 
 def _real_launch(p, mask_value: int, flags: int, weights=None, energies: bool = True):
@@ -135,9 +84,9 @@ def _real_forward(positions, charges, dipoles, cell, alpha, batch_idx, neighbor_
                      neighbor_matrix_shifts)
     n, dev, dt = positions.shape[0], positions.device, positions.dtype
     if n == 0 or p["n_entries"] == 0:
-        res = _zeros(n, p["nsys"], dt, dev)
+        res = P.zeros(n, p["nsys"], dt, dev)
         return tuple(r if w else None for r, w in zip(res, (True, forces, cgrads, dgrads, virial)))
-    flags = (DP_FORCES if forces else 0) | (DP_CHARGE_GRAD if cgrads else 0) | (DP_DIPOLE_GRAD if dgrads else 0) | (DP_VIRIAL if virial else 0)
+    flags = P.flag_bits(forces, cgrads, dgrads, virial)
     e, f, cg, dg, part = _real_launch(p, mask_value, flags)
     return (e.to(dt), f, cg.to(dt) if cgrads else None, dg.to(dt) if dgrads else None, C.fold_virial9(part).to(dt) if virial else None)
 
@@ -173,22 +122,22 @@ def ewald_dipole_real_space(positions: torch.Tensor, charges: torch.Tensor, dipo
     [num_systems, 3, 3].
 
     RETURNS"""
-    _check(positions, charges, dipoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx,
-           alpha, compute_virial)
+    P.check_dipole_lists(positions, charges, dipoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts,
+                         batch_idx, alpha, compute_virial)
     n, dev, dt = positions.shape[0], positions.device, positions.dtype
     want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
     if n == 0:
-        return _select(_zeros(0, _num_systems(cell, batch_idx), dt, dev), want)
+        return P.select(P.zeros(0, P.num_systems(cell, batch_idx), dt, dev), want)
     alpha_t = _prepare_alpha(alpha, _prepare_cell(cell)[1], dt, dev)
     lists = (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
     flags = tuple(bool(w) for w in want[1:])
-    if C.tracing() or (torch.is_grad_enabled() and any(t.requires_grad for t in (positions, charges, dipoles, cell, alpha_t))):
+    if P.needs_op(positions, charges, dipoles, cell, alpha_t):
         from nvalchemiops import _eops
 
         res = _eops.ewald_dipole_real_space_op(positions, charges.to(dt), dipoles.to(dt), cell, alpha_t, batch_idx, *lists, int(mask_value), *flags)
     else:
         res = _real_forward(positions, charges, dipoles, cell, alpha_t, batch_idx, *lists, int(mask_value), *flags)
-    return _select(res, want)
+    return P.select(res, want)
 
 
 # ---- reciprocal space ---------------------------------------------------------------------------------------------------------------------
@@ -248,7 +197,7 @@ def _recip_forward(positions, charges, dipoles, cell, k_vectors, alpha, batch_id
     n, dev, dt = positions.shape[0], positions.device, positions.dtype
     want = (True, forces, cgrads, dgrads, virial)
     if n == 0:
-        return tuple(r if w else None for r, w in zip(_zeros(0, _prepare_cell(cell)[1], dt, dev), want))
+        return tuple(r if w else None for r, w in zip(P.zeros(0, _prepare_cell(cell)[1], dt, dev), want))
     p = _recip_inputs(positions, charges, dipoles, cell, k_vectors, alpha, batch_idx)
     table = _table(p)
     e, f, cg, dg = _gather(p, table, energies=True, forces=forces, cgrads=cgrads, dgrads=dgrads)
@@ -295,7 +244,7 @@ def ewald_dipole_reciprocal_space(positions: torch.Tensor, charges: torch.Tensor
         raise ValueError("cell is required: the point-dipole Ewald sum is periodic (cell=None clusters are out of scope)")
     C.dtype_code(positions.dtype)
     C.check_per_atom(positions.shape[0], charges=charges, batch_idx=batch_idx)
-    _check_dipoles(positions, dipoles)
+    P.check_dipoles(positions, dipoles)
     C.check_neighbor_data(positions.shape[0], cell=cell)
     n, dev, dt = positions.shape[0], positions.device, positions.dtype
     cells, n_sys = _prepare_cell(cell)
@@ -303,16 +252,16 @@ def ewald_dipole_reciprocal_space(positions: torch.Tensor, charges: torch.Tensor
         raise ValueError(f"k_vectors must have shape [K, 3] or [{n_sys}, K, 3], got {tuple(k_vectors.shape)}")
     want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
     if n == 0:
-        return _select(_zeros(0, n_sys, dt, dev), want)
+        return P.select(P.zeros(0, n_sys, dt, dev), want)
     alpha_t = _prepare_alpha(alpha, n_sys, dt, dev)
     flags = tuple(bool(w) for w in want[1:])
-    if C.tracing() or (torch.is_grad_enabled() and any(t.requires_grad for t in (positions, charges, dipoles, cell, k_vectors, alpha_t))):
+    if P.needs_op(positions, charges, dipoles, cell, k_vectors, alpha_t):
         from nvalchemiops import _eops
 
         res = _eops.ewald_dipole_reciprocal_space_op(positions, charges.to(dt), dipoles.to(dt), cells, k_vectors, alpha_t, batch_idx, *flags)
     else:
         res = _recip_forward(positions, charges, dipoles, cells, k_vectors, alpha_t, batch_idx, *flags)
-    return _select(res, want)
+    return P.select(res, want)
 
 
 @C.traceable
@@ -338,12 +287,12 @@ def ewald_dipole_correction(positions: torch.Tensor, charges: torch.Tensor, dipo
 
     if mask_value is None:
         mask_value = positions.shape[0]
-    _check(positions, charges, dipoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx,
-           alpha, compute_virial)
+    P.check_dipole_lists(positions, charges, dipoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts,
+                         batch_idx, alpha, compute_virial)
     cells, n_sys = _prepare_cell(cell)
     if positions.shape[0] == 0:
         want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
-        return _select(_zeros(0, _num_systems(cell, batch_idx), positions.dtype, positions.device), want)
+        return P.select(P.zeros(0, P.num_systems(cell, batch_idx), positions.dtype, positions.device), want)
     C.require_device(positions, charges, dipoles, cell, k_vectors, batch_idx)
     if alpha is None or (k_cutoff is None and k_vectors is None):
         params = estimate_ewald_parameters(positions, cells, batch_idx, accuracy)

@@ -19,31 +19,10 @@ import math
 import torch
 
 from nvalchemiops import _capi as C
+from nvalchemiops.interactions.electrostatics import _pairs as P
 
-GC_FORCES, GC_CHARGE_GRAD, GC_SIGMA_GRAD, GC_VIRIAL, GC_CELL_GRAD = 1, 2, 4, 8, 16
+GC_FORCES, GC_CHARGE_GRAD, GC_SIGMA_GRAD, GC_VIRIAL, GC_CELL_GRAD = P.FORCES, P.CHARGE_GRAD, P.THIRD_GRAD, P.VIRIAL, 16
 _SQRT_PI = math.sqrt(math.pi)
-
-
-def _check(positions, charges, sigma, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx,
-           compute_virial):
-    """Every argument error, before anything is launched: `ewald_real_space`'s messages for the same misuse, plus sigma and the cell-less rules."""
-    if neighbor_list is None and neighbor_matrix is None:
-        raise ValueError("Either neighbor_list or neighbor_matrix must be provided")
-    if neighbor_list is not None and neighbor_ptr is None:
-        raise ValueError("neighbor_ptr is required when using neighbor_list format")
-    C.dtype_code(positions.dtype)
-    if cell is None:
-        if neighbor_shifts is not None or neighbor_matrix_shifts is not None:
-            raise ValueError("neighbor shifts need a cell: pass cell, or a list without shifts for a non-periodic system")
-        if compute_virial:
-            raise ValueError("compute_virial needs a cell")
-    C.check_neighbor_data(positions.shape[0], neighbor_matrix=neighbor_matrix, neighbor_matrix_shifts=neighbor_matrix_shifts,
-                          neighbor_list=neighbor_list, neighbor_ptr=neighbor_ptr, neighbor_shifts=neighbor_shifts, cell=cell,
-                          charges=charges, batch_idx=batch_idx)
-    if isinstance(sigma, torch.Tensor) and sigma.dim() > 0:
-        C.check_per_atom(positions.shape[0], sigma=sigma)
-        if sigma.dim() != 1:
-            raise ValueError(f"sigma must have one entry per atom: expected shape [{positions.shape[0]}], got {tuple(sigma.shape)}")
 
 
 def _sigma_tensor(sigma, n: int, dtype, device) -> torch.Tensor:
@@ -53,21 +32,8 @@ def _sigma_tensor(sigma, n: int, dtype, device) -> torch.Tensor:
     return (sigma.expand(n) if sigma.dim() == 0 else sigma).to(dtype=dtype, device=device)
 
 
-def _inputs(positions, charges, sigma, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts):
-    """Detached, contiguous launch tensors (device check included; shapes were checked by `_check`)."""
-    dt = positions.dtype
-    C.require_device(positions, charges, sigma, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx)
-    if neighbor_list is not None:
-        idx, nptr, m, sh = C.i32(neighbor_list[1]), C.i32(neighbor_ptr), 0, neighbor_shifts
-        n_entries = idx.shape[0]
-    else:
-        idx, nptr, m, sh = C.i32(neighbor_matrix), None, neighbor_matrix.shape[1], neighbor_matrix_shifts
-        n_entries = idx.numel()
-    cells = None if cell is None else cell.detach().to(dt).reshape(-1, 3, 3).contiguous()
-    batched = batch_idx is not None and cells is not None
-    return dict(pos=positions.detach().contiguous(), q=charges.detach().to(dt).contiguous(), sigma=sigma.detach().to(dt).contiguous(), cells=cells,
-                bi=C.i32(batch_idx) if batched else None, nsys=cells.shape[0] if batched else 1, idx=idx, nptr=nptr, m=m,
-                sh=None if sh is None else C.i32(sh), n_entries=n_entries)
+def _inputs(positions, charges, sigma, cell, batch_idx, *lists):
+    return P.launch_inputs(positions, charges, cell, batch_idx, lists, sigma=sigma)
 
 
 def _launch(p, mask_value: int, flags: int, weights=None, energies: bool = True):
@@ -117,7 +83,7 @@ def _forward(positions, charges, sigma, cell, batch_idx, neighbor_list, neighbor
     p = _inputs(positions, charges, sigma, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
     n, dev, dt = positions.shape[0], positions.device, positions.dtype
     f64 = dict(dtype=torch.float64, device=dev)
-    flags = (GC_FORCES if forces else 0) | (GC_CHARGE_GRAD if cgrads else 0) | (GC_SIGMA_GRAD if sgrads else 0) | (GC_VIRIAL if virial else 0)
+    flags = P.flag_bits(forces, cgrads, sgrads, virial)
     if p["n_entries"] == 0:
         e = torch.zeros(n, **f64)
         f = torch.zeros((n, 3), dtype=dt, device=dev) if forces else None
@@ -220,28 +186,24 @@ def gaussian_charge_correction(positions: torch.Tensor, charges: torch.Tensor, s
     the `alchemiops::_gaussian_charge_correction` op, as it does under `torch.compile`.  Differentiating the explicit forces, gradients or
     virial raises NotImplementedError.  CPU tensors raise NativeLibraryError: there is no fallback."""
     n, dev, dt = positions.shape[0], positions.device, positions.dtype
-    _check(positions, charges, sigma, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx,
-           compute_virial)
+    P.check_lists(positions, charges, sigma, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx,
+                  compute_virial)
     want = (True, compute_forces, compute_charge_gradients, compute_sigma_gradients, compute_virial)
     nsys = cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1
     n_entries = neighbor_list.shape[1] if neighbor_list is not None else neighbor_matrix.numel()
     background = bool(neutralizing_background) and cell is not None
     if n == 0 or (n_entries == 0 and not self_energy and not background):
-        zeros = (torch.zeros(n, dtype=dt, device=dev), torch.zeros((n, 3), dtype=dt, device=dev), torch.zeros(n, dtype=dt, device=dev),
-                 torch.zeros(n, dtype=dt, device=dev), torch.zeros((nsys, 3, 3), dtype=dt, device=dev))
-        out = tuple(z for z, w in zip(zeros, want) if w)
-        return out if len(out) > 1 else out[0]
+        return P.select(P.zeros(n, nsys, dt, dev, third_is_vector=False), want)
     sig = _sigma_tensor(sigma, n, dt, dev)
     lists = (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
     flags = (bool(self_energy), background, bool(compute_forces), bool(compute_charge_gradients), bool(compute_sigma_gradients), bool(compute_virial))
-    if C.tracing() or (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (positions, charges, sig, cell))):
+    if P.needs_op(positions, charges, sig, cell):
         from nvalchemiops import _eops
 
         res = _eops.gaussian_charge_correction_op(positions, charges.to(dt), sig, cell, batch_idx, *lists, int(mask_value), *flags)
     else:
         res = _forward(positions, charges, sig, cell, batch_idx, *lists, int(mask_value), *flags)
-    out = tuple(r for r, w in zip(res, want) if w)
-    return out if len(out) > 1 else out[0]
+    return P.select(res, want)
 
 
 __all__ = ["gaussian_charge_correction"]

@@ -20,8 +20,9 @@ import math
 import torch
 
 from nvalchemiops import _capi as C
+from nvalchemiops.interactions.electrostatics import _pairs as P
 from nvalchemiops.interactions.electrostatics import pme as _pme
-from nvalchemiops.interactions.electrostatics.dipole import (_check, _check_dipoles, _num_systems, _select, _zeros, ewald_dipole_real_space)
+from nvalchemiops.interactions.electrostatics.dipole import ewald_dipole_real_space
 from nvalchemiops.interactions.electrostatics.pme import _prepare_alpha, _prepare_cell
 
 _MODEL = """Smooth PME with analytic spline derivatives (Toukmaji, Sagui, Board, Darden).  With frac = cell^-T r, mesh coordinate m_d = frac_d n_d,
@@ -82,7 +83,7 @@ def _check_recip(positions, charges, dipoles, cell, alpha, batch_idx):
         raise ValueError("cell is required: the point-dipole Ewald sum is periodic (cell=None clusters are out of scope)")
     C.dtype_code(positions.dtype)
     C.check_per_atom(positions.shape[0], charges=charges, batch_idx=batch_idx)
-    _check_dipoles(positions, dipoles)
+    P.check_dipoles(positions, dipoles)
     C.check_neighbor_data(positions.shape[0], cell=cell, alpha=alpha)
 
 
@@ -179,7 +180,7 @@ def _recip_forward(positions, charges, dipoles, cell, alpha, batch_idx, dims, or
     n, dev, dt = positions.shape[0], positions.device, positions.dtype
     want = (True, forces, cgrads, dgrads, virial)
     if n == 0:
-        return tuple(r if w else None for r, w in zip(_zeros(0, _num_systems(cell, batch_idx), dt, dev), want))
+        return tuple(r if w else None for r, w in zip(P.zeros(0, P.num_systems(cell, batch_idx), dt, dev), want))
     dims = tuple(int(v) for v in dims)
     p = _inputs(positions, charges, dipoles, cell, alpha, batch_idx)
     phi, spec = _solve(p, _spread(p, dims, order), dims, order, need_spec=virial)
@@ -243,16 +244,16 @@ def pme_dipole_reciprocal_space(positions: torch.Tensor, charges: torch.Tensor, 
     n, dev, dt = positions.shape[0], positions.device, positions.dtype
     want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
     if n == 0:
-        return _select(_zeros(0, _num_systems(cell, batch_idx), dt, dev), want)
+        return P.select(P.zeros(0, P.num_systems(cell, batch_idx), dt, dev), want)
     alpha_t = (_pme._traceable_alpha if C.tracing() else _prepare_alpha)(alpha, n_sys, dt, dev)
     flags = tuple(bool(w) for w in want[1:])
-    if C.tracing() or (torch.is_grad_enabled() and any(t.requires_grad for t in (positions, charges, dipoles, cell, alpha_t))):
+    if P.needs_op(positions, charges, dipoles, cell, alpha_t):
         from nvalchemiops import _eops
 
         res = _eops.pme_dipole_reciprocal_space_op(positions, charges.to(dt), dipoles.to(dt), cells, alpha_t, batch_idx, *dims, order, *flags)
     else:
         res = _recip_forward(positions, charges, dipoles, cells, alpha_t, batch_idx, dims, order, *flags)
-    return _select(res, want)
+    return P.select(res, want)
 
 
 @C.traceable
@@ -278,15 +279,15 @@ def pme_dipole_correction(positions: torch.Tensor, charges: torch.Tensor, dipole
         mask_value = positions.shape[0]
     if neighbor_list is not None and neighbor_matrix is not None:
         raise ValueError("pass the list in ONE format: neighbor_list (with neighbor_ptr) or neighbor_matrix, not both")
-    _check(positions, charges, dipoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx,
-           alpha, compute_virial)
+    P.check_dipole_lists(positions, charges, dipoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts,
+                         batch_idx, alpha, compute_virial)
     order = _check_order(spline_order)
     cells, n_sys = _prepare_cell(cell)
     if mesh_dimensions is not None:
         mesh_dimensions = _mesh_dims(cells, mesh_dimensions, None, order)
     if positions.shape[0] == 0:
         want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
-        return _select(_zeros(0, _num_systems(cell, batch_idx), positions.dtype, positions.device), want)
+        return P.select(P.zeros(0, P.num_systems(cell, batch_idx), positions.dtype, positions.device), want)
     C.require_device(positions, charges, dipoles, cell, batch_idx)
     if alpha is None:
         est = _pme.estimate_pme_parameters(positions, cells, batch_idx, accuracy)

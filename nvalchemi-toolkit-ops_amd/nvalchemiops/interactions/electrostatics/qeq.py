@@ -23,6 +23,7 @@ from collections import namedtuple
 import torch
 
 from nvalchemiops import _capi as C
+from nvalchemiops.interactions.electrostatics import _pairs as P
 from nvalchemiops.interactions.electrostatics import gaussian as G
 
 F64 = torch.float64
@@ -36,13 +37,13 @@ class ChargeEquilibrationError(RuntimeError):
 def _check(positions, electronegativity, hardness, sigma, cell, total_charge, batch_idx, num_systems, neighbor_list, neighbor_ptr, neighbor_shifts,
            neighbor_matrix, neighbor_matrix_shifts, reciprocal, alpha, mesh_dimensions, mesh_spacing, k_vectors, k_cutoff, tolerance,
            max_iterations, check_interval, initial_charges) -> int:
-    """Every argument error, before anything is launched (`gaussian._check` for the list, sigma and the cell-less rules).  Returns the number
+    """Every argument error, before anything is launched (`_pairs.check_lists` for the list, sigma and the cell-less rules).  Returns the number
     of systems: the cell count with a cell; otherwise `num_systems`, else the length of a `total_charge` tensor, else 1 -- never a host read
     of `batch_idx`."""
     n = positions.shape[0] if positions.dim() == 2 else -1
     if positions.dim() != 2 or positions.shape[1] != 3:
         raise ValueError(f"positions must have shape [num_atoms, 3], got {tuple(positions.shape)}")
-    G._check(positions, None, sigma, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx, False)
+    P.check_lists(positions, None, sigma, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx, False)
     for name, t in (("electronegativity", electronegativity), ("hardness", hardness), ("initial_charges", initial_charges)):
         if t is not None:
             C.check_per_atom(n, **{name: t})
@@ -107,16 +108,13 @@ class _Operator:
         self.kv_given = False
         if self.cells is not None:
             self._reciprocal_parameters(alpha, mesh_dimensions, mesh_spacing, k_vectors, k_cutoff, accuracy)
-        if neighbor_list is not None:
-            self.idx, self.nptr, self.m, sh = C.i32(neighbor_list[1]), C.i32(neighbor_ptr), 0, neighbor_shifts
-        else:
-            self.idx, self.nptr, self.m, sh = C.i32(neighbor_matrix), None, neighbor_matrix.shape[1], neighbor_matrix_shifts
-        slots = self.idx.numel()
+        ls = P.list_inputs(neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
+        self.idx, self.nptr, self.m, sh32, slots = ls["idx"], ls["nptr"], ls["m"], ls["sh"], ls["n_entries"]
         self.coef = torch.empty(slots, dtype=F64, device=dev)
         self.nbr = torch.empty(slots, dtype=torch.int32, device=dev)
         self.diag = torch.empty(n, dtype=F64, device=dev)
         self.blocks, self.words = int(C.lib().mi_qeq_blocks()), int(C.lib().mi_qeq_state_words())
-        hard64, sh32 = hardness.detach().to(F64).contiguous(), None if sh is None else C.i32(sh)
+        hard64 = hardness.detach().to(F64).contiguous()
         rc = C.lib().mi_qeq_pair_coefficients(C.ptr(self.pos), C.ptr(self.sigma), C.ptr(hard64), C.ptr(self.cells),
                                               C.ptr(self.alpha), C.ptr(self.bi if self.cells is not None else None), n, nsys, C.dtype_code(dt),
                                               C.ptr(self.idx), C.ptr(sh32), C.ptr(self.nptr), int(self.m),

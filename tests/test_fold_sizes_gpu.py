@@ -1,9 +1,11 @@
-"""Sizes beyond one trip of the per-system folds of `dftd4`, `dftd4_atm`, `gaussian_charge_correction` and `charge_equilibration`.
+"""Sizes beyond one trip of the per-system folds of `dftd4`, `dftd4_atm`, `gaussian_charge_correction`, `charge_equilibration`,
+`ewald_dipole_real_space` and `ewald_real_space_with_virial`.
 
-Every per-system sum of these ops is a fixed-order fold on a grid of (blocks, systems) blocks of 256 threads, each looping
-`r += blocks * 256` over ALL N rows and keeping those of its system: `d4_fold_kernel` (also `dftd4_atm`'s), `gc_fold_kernel`,
-`gc_system_sums_kernel`, `qeq_fold_kernel`, `qeq_cg_update_kernel`, `qeq_cg_direction_kernel`.  The parity modules stop at a few hundred
-atoms; the second trip of these loops (N > 256 * blocks = 16 384) and the batched form at that size are compared here.
+Every per-system sum of these ops is the fixed-order fold of csrc/pair_row.h (`mi_system_fold`) on a grid of (blocks, systems) blocks of
+256 threads, each looping `r += blocks * 256` over ALL N rows and keeping those of its system: `d4_fold_kernel` (also `dftd4_atm`'s),
+`gc_fold_kernel`, `gc_system_sums_kernel`, `qeq_fold_kernel`, `dp_fold_kernel`, `ew_virial_fold_kernel`; `qeq_cg_update_kernel` and
+`qeq_cg_direction_kernel` walk the same grid.  The parity modules stop at a few hundred atoms; the second trip of these loops
+(N > 256 * blocks = 16 384) and the batched form at that size are compared here.
 
 No large reference is needed.  These ops take the pairs from the list, so K copies of a small system with the small list repeated
 blockwise (indices + k n0, fill value N) are K independent systems, even at identical positions; the small call is judged against its
@@ -19,6 +21,12 @@ a third of the rows) and K n0 no multiple of 64.
   Gaussian background term: the per-system charge sum feeds every atom.  In (a) Q = K Q_small, so the expectation is the small call
       without background plus K x (K^2 x for the virial) the closed-form background part of the small system, compared with the
       module's rel = 1e-11 `_close`, as are the per-atom outputs of (b) with the background switched on.
+  ewald_dipole_real_space (nine-word virial) and ewald_real_space_with_virial (six words): (a) and (b) as above on the small systems of
+      `test_dipole_gpu._single()` (judged against tests/dipole_reference.py at that module's rel = 1e-11) and of
+      `test_electrostatic_virial_gpu._real_inputs` (judged against the strain derivative at that module's 1e-10).  The per-atom energies
+      and forces of `ewald_real_space_with_virial` are asserted bit-identical too: that held on the commit before the folds were shared
+      (the tiled list is a new tensor, so the big calls take the symmetry-checksum path while the small matrix call takes the trusted
+      one: same bits), so the module's looser rtol 1e-12 / atol 1e-14 of its scatter path is not needed.
   charge_equilibration (cluster): the operator is block-diagonal with identical blocks, so the exact solution is the small dense KKT
       solution tiled:  max|q - q_ref| <= sqrt(K) (10 tol ||b_small|| / lambda_min + 1e-14) for the single system (||b|| grows as sqrt(K)),
       without the sqrt(K) per system of the batch -- `_check_solution`'s bound with the small block's spectrum; tol = 1e-10.
@@ -31,6 +39,11 @@ bit-identical wherever that is asserted.  Worst |X_big - K X_small| / bar as ONE
              1e-11: energies 1.4e-16, forces 0, charge gradients 3.1e-16, sigma gradients 2.1e-16, virial 3.6e-16
 As a BATCH of K systems: every energy and virial of dftd4 and dftd4_atm EQUAL to the small call's (error 0), with K cells and with the
 stride-0 cell; gaussian virial 3.6e-15 and 5.3e-15 absolute (1.1e-9 and 1.8e-9 of the bar).
+  dipole real space  300 atoms (K 82, N 24 600): small call against the reference 6.0e-16 / 1.3e-15 / 1.3e-16 / 8.9e-16 / 1.8e-14
+             (energies / forces / charge / dipole gradients / virial, bar 1e-11); virial as one system 3.6e-12 (5.7e-10 of the bar), in the
+             batch 1.1e-13 (1.5e-9 of the bar) with K cells and with the stride-0 cell
+  ewald real space   160 atoms (K 155, N 24 800): virial as one system 2.3e-13 (1.5e-9 of the bar), in the batch 8.9e-16 (8.8e-10 of the
+             bar), both cell forms; energies and forces bit-identical, here and at the commit before the folds were shared
   charge_equilibration  60 atoms (K 410, N 24 600): max|q - q_ref| 2.9e-11 as one system (bar 1.3e-7) and in the worst system of the batch
              (bar 6.2e-9); 19 iterations in the small call, the single system and all 410 systems of the batch."""
 import math
@@ -44,6 +57,8 @@ from tests import d4_cases as K4
 from tests import qeq_reference as QR
 from tests import test_d4_atm_gpu as TD4A
 from tests import test_d4_gpu as TD4
+from tests import test_dipole_gpu as TDP
+from tests import test_electrostatic_virial_gpu as TV
 from tests import test_gaussian_charges_gpu as TG
 from tests import test_qeq_gpu as TQ
 
@@ -85,7 +100,8 @@ def _fold_close(big, small_times_k, scale, what):
 
 
 def _bitwise(big, small, k, what):
-    assert torch.equal(big, small.repeat((k,) + (1,) * (small.dim() - 1))), f"{what}: per-atom output differs from the tiled small call's"
+    tiled = small.repeat((k,) + (1,) * (small.dim() - 1))
+    assert torch.equal(big, tiled), f"{what}: per-atom output differs from the tiled small call's by up to {float((big - tiled).abs().max()):.3e}"
 
 
 # ---- dftd4 / dftd4_atm ---------------------------------------------------------------------------------------------------------------------
@@ -195,6 +211,74 @@ def test_gaussian_copies_as_one_system_and_as_a_batch(fmt):
         for i in range(4):
             TG._close(many[i], small[i].repeat((k,) + (1,) * (small[i].dim() - 1)), f"{label}, {TG.NAMES[i]}")
         _fold_close(many[4], small[4].expand_as(many[4]), small[4], f"{label}, virial")
+
+
+# ---- ewald_dipole_real_space / ewald_real_space_with_virial --------------------------------------------------------------------------------
+
+def _check_copies(label, small, one, many, k, per_atom, vir):
+    """`small`: the outputs of the small call; `one`: of its K copies as one system; `many`: [(tag, outputs)] of the copies as a batch."""
+    for i in per_atom:
+        _bitwise(one[i], small[i], k, f"{label} one system, output {i}")
+    _fold_close(one[vir], k * small[vir].double(), one[vir], f"{label} one system of {k * small[0].shape[0]} atoms, virial")
+    for tag, out in many:
+        for i in per_atom:
+            _bitwise(out[i], small[i], k, f"{label} batch{tag}, output {i}")
+        assert out[vir].shape[0] == k
+        _fold_close(out[vir], small[vir].expand_as(out[vir]), small[vir], f"{label} batch of {k}{tag}, virial")
+
+
+def _tiled_lists(fmt, nm, sh, nl, ptr, lsh, k, n):
+    if fmt == "matrix":
+        nm, sh = _tile_matrix(nm, sh, k)
+        return dict(neighbor_matrix=nm, neighbor_matrix_shifts=sh, mask_value=n)
+    lst, ptr, lsh = _tile_csr(nl, ptr, lsh, k)
+    return dict(neighbor_list=lst, neighbor_ptr=ptr, neighbor_shifts=lsh)
+
+
+@pytest.mark.parametrize("fmt", ["matrix", "list"])
+def test_dipole_real_space_copies_as_one_system_and_as_a_batch(fmt):
+    from nvalchemiops import _capi as C
+    from nvalchemiops.interactions.electrostatics import ewald_dipole_real_space as real
+
+    f = TDP._single()
+    n0, blocks = f["n"], int(C.lib().mi_ewald_dipole_blocks())
+    k = _copies(n0, blocks)
+    n = k * n0
+    assert n > 256 * blocks and n % 64 != 0
+    small = real(f["P"], f["Q"], f["M"], f["C"], f["A"], **TDP._fmt_kw(f, fmt), **TDP.ALL)
+    for name, o in zip(TDP.NAMES, small):
+        TDP._close(o, f["ref_real"][name], f"fold sizes dipole {fmt}: the small call, {name}")
+    P, Q, M = (f[x].repeat((k,) + (1,) * (f[x].dim() - 1)) for x in ("P", "Q", "M"))
+    big = _tiled_lists(fmt, f["nm"], f["sh"], f["nl"], f["ptr"], f["lsh"], k, n)
+    one = real(P, Q, M, f["C"], f["A"], **big, **TDP.ALL)
+    bi = torch.arange(k, device=DEV, dtype=torch.int32).repeat_interleave(n0)
+    many = [(tag, real(P, Q, M, cell, TDP.ALPHA, batch_idx=bi, **big, **TDP.ALL))
+            for tag, cell in (("", f["C"].repeat(k, 1, 1).contiguous()), (" (stride-0 cell)", f["C"][:1].expand(k, 3, 3)))]
+    _check_copies(f"dipole real space {fmt}", small, one, many, k, per_atom=(0, 1, 2, 3), vir=4)
+
+
+@pytest.mark.parametrize("kind", ["matrix", "csr"])
+def test_ewald_real_space_virial_copies_as_one_system_and_as_a_batch(kind):
+    from nvalchemiops import _capi as C
+    from nvalchemiops.interactions.electrostatics import ewald_real_space, ewald_real_space_with_virial as real
+
+    P0, Cc, Q0, nl = TV._real_inputs(kind)
+    n0, blocks = P0.shape[0], int(C.lib().mi_ewald_virial_blocks())
+    k = _copies(n0, blocks)
+    n = k * n0
+    assert n > 256 * blocks and n % 64 != 0
+    alpha = torch.tensor([0.35], dtype=F64, device=DEV)
+    small = real(P0, Q0, Cc[None], alpha, compute_forces=True, **nl)
+    TV._close(small[2], TV._strain_derivative(lambda p, c: ewald_real_space(p, Q0, c, alpha, **nl), P0, Cc), 1e-10,
+              f"fold sizes ewald {kind}: the small call, virial")
+    P, Q = P0.repeat(k, 1), Q0.repeat(k)
+    big = _tiled_lists(kind, nl.get("neighbor_matrix"), nl.get("neighbor_matrix_shifts"), nl.get("neighbor_list"), nl.get("neighbor_ptr"),
+                       nl.get("neighbor_shifts"), k, n)
+    one = real(P, Q, Cc[None], alpha, compute_forces=True, **big)
+    bi = torch.arange(k, device=DEV, dtype=torch.int32).repeat_interleave(n0)
+    many = [(tag, real(P, Q, cell, alpha.expand(k).contiguous(), batch_idx=bi, compute_forces=True, **big))
+            for tag, cell in (("", Cc[None].repeat(k, 1, 1).contiguous()), (" (stride-0 cell)", Cc[None].expand(k, 3, 3)))]
+    _check_copies(f"ewald real space {kind}", small, one, many, k, per_atom=(0, 1), vir=2)
 
 
 # ---- charge_equilibration ------------------------------------------------------------------------------------------------------------------
