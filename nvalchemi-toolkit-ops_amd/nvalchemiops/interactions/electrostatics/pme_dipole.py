@@ -9,8 +9,10 @@ Three HIP kernels (csrc/pme.hip, last section): `mi_pme_dipole_spread` (one pass
 `mi_pme_dipole_gather` (potential, gradient and Hessian of two meshes in one pass) and `mi_pme_dipole_virial` (the k-space virial of the
 cross spectrum).  Between them runs the mesh solve of the charge PME, `mi_pme_solve_tabled` or hipFFT plan -> `mi_pme_convolve` -> plan: the
 solve is linear, so the meshes of one call are further systems of one batched solve.  Forward and adjoint are the same launches without and
-with per-atom weights.  The spread adds with floating-point atomics: the meshes, and hence ALL outputs, are reproducible only up to the
-arrival order of these adds (differences in the last bits from run to run), as for the charge PME's small-system path.
+with per-atom weights.  The spread adds with floating-point atomics, always in float64: for float64 inputs the meshes, and hence ALL outputs,
+are reproducible only up to the arrival order of these adds (differences in the last bits from run to run), as for the charge PME's
+small-system path; for float32 inputs the float64 sums are rounded to float32 once, which makes the meshes and all outputs the same in every
+run (in float32 arrival order the forces moved by up to 1e-6 of their largest component from run to run).
 """
 from __future__ import annotations
 
@@ -47,10 +49,11 @@ _RETURNS = """Returns ``energies`` [N], or a tuple holding only what was asked f
     kernels run as their own adjoint); the call then goes through the `alchemiops::_pme_dipole_reciprocal_space` op, as it does under
     `torch.compile`.  Differentiating the explicit forces, gradients or virial raises NotImplementedError.  Gradients w.r.t. cell and alpha are
     out of scope (NotImplementedError at backward): use `compute_virial`.  Also out of scope: quadrupoles, a tile-owned spread, caller-supplied
-    k arrays, `cell=None` clusters, surface (non-tin-foil) terms.  The spread uses floating-point atomic adds: all outputs are reproducible
-    only up to the arrival order of these adds.  CPU tensors raise NativeLibraryError: there is no fallback."""
+    k arrays, `cell=None` clusters, surface (non-tin-foil) terms.  The spread uses float64 atomic adds: float64 outputs are reproducible only
+    up to the arrival order of these adds (last bits); float32 outputs are the same in every run.  CPU tensors raise NativeLibraryError: there is no fallback."""
 
 ORDERS = (4, 5, 6)
+_SPREAD_FLOAT32_IN_FLOAT64 = True  # float32 calls: the spread adds in float64 and rounds once (see `_spread`)
 
 
 def _check_order(spline_order) -> int:
@@ -110,6 +113,12 @@ def _inputs(positions, charges, dipoles, cells, alpha, batch_idx):
 def _spread(p, dims, order, weights=None):
     """[2 | 4, nsys, nx, ny, nz]: rho_q, rho_mu (and their g-weighted twins), zero-filled by the entry point."""
     pos = p["pos"]
+    if pos.dtype == torch.float32 and _SPREAD_FLOAT32_IN_FLOAT64:
+        # float32 atomic adds in arrival order move the last bits of the meshes from run to run, and the Hessian sums of the gather carry
+        # that into the forces at 1e-6 of their largest component.  Added in float64 and rounded once, the float32 meshes are the same
+        # in every run (but for a sum that lands on a rounding boundary of float32).
+        wide = {k: p[k].to(torch.float64) for k in ("pos", "q", "mu", "cit")}
+        return _spread(dict(p, code=C.dtype_code(torch.float64), **wide), dims, order, weights).to(torch.float32)
     meshes = torch.empty((4 if weights is not None else 2, p["nsys"]) + dims, dtype=pos.dtype, device=pos.device)
     rc = C.lib().mi_pme_dipole_spread(C.ptr(pos), C.ptr(p["q"]), C.ptr(p["mu"]), C.ptr(weights), C.ptr(p["bi"]), C.ptr(p["cit"]), pos.shape[0],
                                       int(p["nsys"]), *dims, int(order), p["code"], C.ptr(meshes), C.stream_of(pos))

@@ -1,5 +1,5 @@
-"""The fixtures of the layout sweeps of `dftd4`, `dftd4_atm`, `gaussian_charge_correction` and `charge_equilibration`
-(tests/test_arg_layouts_gpu.py), in one place and free of any device, so that the CPU suite can check on exactly these inputs the condition
+"""The fixtures of the layout sweeps of `dftd4`, `dftd4_atm`, `gaussian_charge_correction`, `charge_equilibration` and the two point-dipole
+operators (tests/test_arg_layouts_gpu.py), in one place and free of any device, so that the CPU suite can check on exactly these inputs the condition
 that makes such a sweep worth running (tests/test_layout_sensitivity_cpu.py): a tensor argument that the entry point misreads by one row
 must move the result far beyond the bar the sweep applies.  Every reference is computed once and never modified.
 
@@ -8,6 +8,7 @@ must move the result far beyond the bar the sweep applies.  Every reference is c
                                 a compact block of 130 atoms in a box of 22 for the table sweeps of `dftd4_atm`
     gaussian(dtype, batch)      130 atoms in the 12 Bohr box / 70 + 60 in boxes 12 and 11, widths in [0.3, 0.8], two point atoms per system
     qeq_cluster(), qeq_periodic()   two clusters (no cell) / two periodic systems with their own k-vectors and alpha
+    dipole(batch)               the Gaussian fixture's boxes with point dipoles, per-system alpha, a k set and a mesh: both dipole operators
 
 Why the D4 fixture is not the 12 Bohr box of the other sweeps: there the coordination numbers reach 18 while the `cn_ref` of
 `d4_test_tables` lie in [0, 1]; every Gaussian weight saturates on the reference nearest to 1, and rolling `ngw` by one row moves the
@@ -22,7 +23,9 @@ from tests import d4_atm_cases as K3
 from tests import d4_atm_reference as R3
 from tests import d4_cases as K
 from tests import d4_reference as R
+from tests import dipole_reference as DR
 from tests import gaussian_reference as GR
+from tests import pme_dipole_reference as PR
 from tests import qeq_reference as QR
 from tests import systems as S
 
@@ -229,3 +232,44 @@ def qeq_charge_bound(h, chi, total, bi, nsys, tol=QEQ_TOL):
         m = torch.nonzero(bi == s).flatten()
         out.append(10.0 * tol * float(b_norm[s]) / float(torch.linalg.eigvalsh(h[m][:, m]).min()) + 1e-14)
     return out
+
+
+# ---- ewald_dipole_correction and pme_dipole_correction -----------------------------------------------------------------------------------
+
+DP_ALPHA = (0.4, 0.375)
+DP_K_CUTOFF, DP_MESH, DP_ORDER = 2.2, (12, 10, 14), 5
+DP_NAMES = ("energies", "forces", "charge_grads", "dipole_grads", "virial")
+
+
+@functools.lru_cache(maxsize=None)
+def dipole(batch=False):
+    """The boxes of the Gaussian fixture (130 atoms in the 12 Bohr box / 70 + 60 in boxes 12 and 11, list cutoff `GC_RC`), charges
+    0.5 q + 0.125, dipoles 0.4 x normal with two zero rows per system, one alpha per system, and the package's half-space k set of cutoff
+    2.2 ([K, 3] / [B, K, 3]).  Every value is a float32 number -- the k-vectors too, rounded after they were generated: they are an input of
+    the kernels and of the restatement alike -- so float32 <-> float64 variants are equal-valued."""
+    from nvalchemiops.interactions.electrostatics import generate_k_vectors_ewald_summation
+
+    parts = [system(NA, 8, 12.0), system(NB, 9, 11.0)] if batch else [system(N, 7, 12.0)]
+    pos, cell, q, _, bi = _join(parts)
+    g = np.random.default_rng(27 + batch)
+    mu = (0.4 * g.normal(size=(len(pos), 3))).astype(np.float32)
+    off = 0
+    for p in parts:
+        mu[off + g.choice(len(p[0]), 2, replace=False)] = 0.0
+        off += len(p[0])
+    cells = torch.as_tensor(cell.astype(np.float64))
+    kv = generate_k_vectors_ewald_summation(cells if batch else cells[0], DP_K_CUTOFF).numpy().astype(np.float32)
+    return dict(pos=pos, cell=cell, q=(0.5 * q + 0.125).astype(np.float32), mu=mu, alpha=np.array(DP_ALPHA[:len(parts)], np.float32), kv=kv, batch_idx=bi)
+
+
+def dipole_reference(batch=False, op="ewald", dtype=F64, **replace):
+    """The restatement of `ewald_dipole_correction` (op "ewald": the full list of cutoff `GC_RC` and the fixture's k set; `dtype` float32 is
+    its float32-distance mode) or of `pme_dipole_reciprocal_space` (op "pme": mesh `DP_MESH`, order `DP_ORDER`; `dtype` float32 is its
+    float32 mode) on the fixture, with arguments replaced."""
+    c = {**dipole(batch), **replace}
+    t = lambda a: torch.as_tensor(np.asarray(a, np.float64))  # noqa: E731
+    bi = None if c["batch_idx"] is None else torch.as_tensor(c["batch_idx"])
+    if op == "pme":
+        return PR.evaluate(t(c["pos"]), t(c["q"]), t(c["mu"]), t(c["cell"]), t(c["alpha"]), DP_MESH, DP_ORDER, batch_idx=bi, dtype=dtype)
+    ent = _entries(c["pos"], c["cell"], c["batch_idx"], GC_RC)
+    return DR.evaluate(t(c["pos"]), t(c["q"]), t(c["mu"]), t(c["cell"]), t(c["alpha"]), ent, t(c["kv"]), batch_idx=bi, distance_dtype=dtype)

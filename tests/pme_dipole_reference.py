@@ -129,3 +129,20 @@ def evaluate(pos, q, mu, cell, alpha, dims, order, batch_idx=None, weights=None,
         es = energies(pos_e, q.detach(), mu.detach(), cell_e, alpha, dims, order, bi).sum()
         out["virial"] = -torch.autograd.grad(es, eps)[0]
     return {k: v.detach().to(F64).numpy() for k, v in out.items()}
+
+
+def half_spectrum_plane_virial(pos, q, mu, cell, alpha, dims, order, k):
+    """[3, 3] numpy: what plane k of the rfft half spectrum adds to the k-space virial of ONE system per unit of its Hermitian weight,
+        sum over the plane of (G / sf^2)(2 Re[conj(rho_q) rho_mu] + |rho_mu|^2)(delta_ab - 2 (1/k^2 + 1/(4 alpha^2)) k_a k_b).
+    On an odd axis the last plane k = (nz - 1) / 2 has weight 2; the test cases use this to make sure that plane is visible in the virial."""
+    dims = tuple(int(v) for v in dims)
+    nx, ny, _ = dims
+    rq = torch.fft.rfftn(_mesh(q, axis_weights(pos, cell, dims, order)))[:, :, k]
+    rm = torch.fft.rfftn(_spread_gradient(pos, mu, cell, dims, order).detach())[:, :, k]
+    e = _influence(cell, alpha, dims, order)[:, :, k] * (2.0 * (rq.conj() * rm).real + rm.abs() ** 2)
+    miller = lambda n: torch.tensor([i if i < (n + 1) // 2 else i - n for i in range(n)], dtype=cell.dtype)  # noqa: E731
+    m = torch.stack(torch.meshgrid(miller(nx), miller(ny), torch.tensor([float(k)], dtype=cell.dtype), indexing="ij"), dim=-1)[:, :, 0]
+    kv = torch.einsum("cd,xyd->xyc", 2.0 * math.pi * torch.linalg.inv(cell), m)
+    k2 = (kv * kv).sum(-1)
+    out = torch.eye(3, dtype=cell.dtype) * e.sum() - 2.0 * torch.einsum("xy,xya,xyb->ab", e * (1.0 / k2 + 0.25 / (alpha * alpha)), kv, kv)
+    return out.detach().numpy()

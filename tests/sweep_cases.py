@@ -1,5 +1,6 @@
 """Seeded sweep cases, boundary ladders and one-scalar variants of the five newer dispersion operators (`dftd3_atm`, `dftd3_zero`,
-`dftd3_zero_atm`, `dftd4`, `dftd4_atm`) and the inputs of the sweeps of `gaussian_charge_correction` and charge equilibration (last section),
+`dftd3_zero_atm`, `dftd4`, `dftd4_atm`) and the inputs of the sweeps of `gaussian_charge_correction`, charge equilibration and the two
+point-dipole operators (last two sections),
 built on the float64 restatements tests/atm_reference.py, tests/d3_zero_reference.py,
 tests/d4_reference.py and tests/d4_atm_reference.py.  Importable without a GPU and without the native library (the two tile sizes are read
 lazily, by the ladder builders only).  The CPU suite asserts every condition a case must meet (tests/test_sweep_cases_cpu.py); the GPU
@@ -51,6 +52,7 @@ from tests import d4_atm_cases as K3
 from tests import d4_atm_reference as R3
 from tests import d4_cases as K
 from tests import d4_reference as R
+from tests import pme_dipole_reference as PR
 from tests import systems as S
 
 OPS = ("dftd3_atm", "dftd3_zero", "dftd3_zero_atm", "dftd4", "dftd4_atm")
@@ -609,3 +611,277 @@ def unrolled_case():
     c = dict(op="charge_equilibration", dtype="float64", sizes=(n,), pos=pos, cells=cell[None], batch_idx=np.zeros(n, np.int32), cutoff=9.5, images=(1,),
              sigma=sigma, pad=0, emptied_row=None, hard=g.uniform(0.5, 1.5, n), x=g.normal(size=n), y_in=g.normal(size=n), alpha=np.array([0.35]))
     return _with_entries(c)
+
+
+# ---- point dipoles: ewald_dipole_correction and pme_dipole_correction -----------------------------------------------------------------------------
+# Inputs, and for the mesh term the restatement in both of its modes (it runs on the CPU); the explicit sum's restatement is evaluated by
+# the GPU module on the entries actually stored (tests/dipole_reference.py), as tests/test_dipole_gpu.py does.  The recipe is `_charge_sweep`
+# with three differences.  CONTACTS: positions are drawn by rejection so that no two atom images are closer than `MIN_CONTACT` -- the
+# real-space force goes as B3 ~ r^-7, and with uniform positions the float32 rounding of the distance of ONE close contact would decide the
+# whole float32 comparison.  SPECIAL SEEDS: `ZERO_DIPOLE_SEEDS` have all dipoles zero (every output but dipole_grads is then exactly 0);
+# `INTERLEAVED_SEEDS` have at least two systems and a seeded permutation `perm` of their atoms (`interleaved(c)` applies it: batch_idx is then
+# not sorted; for `pme_dipole_reciprocal_space` and the real-space half only); `EMPTY_SYSTEM_SEEDS` have three systems whose middle one has
+# no atom (sizes (a, 0, b), batch_idx holds 0 and 2, cells is [3, 3, 3]; both restatements accept such a batch).  MESH of a `pme_dipole` seed:
+# order 4, 5, 6 in turn, dimensions drawn from {order, order + 1, 9, 10, 11, 12, 13, 16}.
+
+DIPOLE_OPS = ("ewald_dipole", "pme_dipole")
+BASE.update(ewald_dipole=7900, pme_dipole=8070)  # 8070: the first of 8000, 8010, ... whose twelve seeds meet every condition of the CPU suite
+MIN_CONTACT = 1.0
+DIPOLE_FLAGS = ("compute_forces", "compute_charge_gradients", "compute_dipole_gradients", "compute_virial")
+DIPOLE_NAMES = ("energies", "forces", "charge_grads", "dipole_grads", "virial")
+ZERO_DIPOLE_SEEDS = (1, 6, 11)
+INTERLEAVED_SEEDS = (4, 8)   # even: float64, so that the interleaved and the sorted call are compared at the float64 bar of two device results
+EMPTY_SYSTEM_SEEDS = (5, 10)
+K_CUTOFF = 1.6               # of the sweep's explicit sums: up to 9 x 9 x 9 / 2 = 364 vectors per system
+K_RUNGS = (63, 64, 65, 255, 256, 257, 513)
+K_LADDER_CUTOFF = 3.0
+K_LADDER_ALPHA = 1.0
+ATOM_RUNGS = (255, 256, 257, 1)
+ATOM_LADDER_K_CUTOFF = 0.75
+SPREAD_MESH = (9, 10, 11)
+SPREAD_POOL_SEED = 8480
+BIG_MESH = (40, 36, 96)
+PME_ORDERS = (4, 5, 6)
+PG_ATOMS = 32                # atoms per block of `pme_dipole_gather_kernel`: 256 / PG_LANES; the CPU suite reads the #define
+
+
+def mesh_choices(order):
+    return (order, order + 1, 9, 10, 11, 12, 13, 16)
+
+
+def spread_atoms_per_block(order):
+    return 256 // (order * order)
+
+
+def spread_rungs(order):
+    apb = spread_atoms_per_block(order)
+    return tuple(sorted({apb - 1, apb, apb + 1, 2 * apb, PG_ATOMS - 1, PG_ATOMS, PG_ATOMS + 1}))
+
+
+def spaced_positions(g, n, cell, min_dist=MIN_CONTACT):
+    """n points uniform in the cell, drawn one by one and rejected when closer than min_dist to an image of an accepted one."""
+    rng = np.arange(-1, 2)
+    images = np.array([(a, b, c) for a in rng for b in rng for c in rng]) @ cell
+    pts = np.empty((0, 3))
+    while len(pts) < n:
+        p = g.uniform(0, 1, 3) @ cell
+        if len(pts) == 0 or np.linalg.norm(pts[:, None, :] + images[None] - p, axis=-1).min() >= min_dist + 1e-6:  # (the margin: the CPU suite asserts >= min_dist on distances formed another way)
+            pts = np.vstack([pts, p])
+    return pts
+
+
+def entry_distances(c):
+    """|r_j - r_i + S . cell| of every entry of the case, float64."""
+    i, j, S = c["entries"]
+    shift = 0.0 if c["cells"] is None else np.einsum("ea,eab->eb", S.astype(np.float64), c["cells"][c["batch_idx"][i]])
+    return np.linalg.norm(c["pos"][j] - c["pos"][i] + shift, axis=1)
+
+
+def stored_entries(c):
+    """(i, j, S) as the GPU module stores them: the emptied row taken out of the list from both ends."""
+    i, j, S = c["entries"]
+    if c["emptied_row"] is None:
+        return i, j, S
+    keep = (i != c["emptied_row"]) & (j != c["emptied_row"])
+    return i[keep], j[keep], S[keep]
+
+
+def interleaved(c):
+    """The case with its atoms in the order `perm` (new atom k is old atom perm[k]): every per-atom array, the entries and the emptied row."""
+    perm = c["perm"]
+    inv = np.empty_like(perm)
+    inv[perm] = np.arange(len(perm))
+    i, j, S = c["entries"]
+    ni, nj = inv[i], inv[j]
+    order = np.argsort(ni, kind="stable")
+    out = dict(c, perm=None, entries=(ni[order], nj[order], S[order]), emptied_row=None if c["emptied_row"] is None else int(inv[c["emptied_row"]]))
+    for k in ("pos", "q", "mu", "batch_idx", "weights"):
+        out[k] = c[k][perm]
+    return out
+
+
+def _dipoles(g, n, zero=False):
+    mu = 0.4 * g.normal(size=(n, 3))
+    mu[g.choice(n, min(3, max(1, n // 20)), replace=False)] = 0.0  # a few atoms without a dipole
+    return np.zeros((n, 3)) if zero else mu
+
+
+@functools.lru_cache(maxsize=None)
+def _dipole_sweep(op, seed):
+    g = np.random.default_rng(BASE[op] + seed)
+    own = seed % 3 == 0  # the small systems sit in a cell shorter than the cutoff
+    while True:
+        sizes = [int(v) for v in g.choice(CHARGE_SIZES, 3 if seed in EMPTY_SYSTEM_SEEDS else int(g.integers(2 if seed in INTERLEAVED_SEEDS else 1, 4)))]
+        if seed in EMPTY_SYSTEM_SEEDS:
+            sizes[1] = 0
+        if max(sizes) >= 9:
+            break
+    sizes = tuple(sizes)
+    cutoff = float(g.uniform(6.0, 7.0))
+    pos, cells, images = [], [], []
+    for n in sizes:
+        box = _BOX.get(n, 5.0 if own else 14.0)
+        cell = charge_cell(box, bool(g.integers(2)))
+        pos.append(spaced_positions(g, n, cell))
+        cells.append(cell)
+        images.append(2 if box < cutoff else 1)
+    ntot = sum(sizes)
+    bi = np.concatenate([np.full(n, k, np.int32) for k, n in enumerate(sizes)])
+    q = g.normal(size=ntot)
+    neutral = seed % 2 == 1
+    if neutral:
+        for k in range(len(sizes)):
+            if sizes[k]:
+                q[bi == k] -= q[bi == k].mean()
+    big = int(np.argmax(sizes))
+    order = PME_ORDERS[seed % 3]
+    c = dict(op=op, seed=seed, dtype="float64" if seed % 2 == 0 else "float32", sizes=sizes, pos=np.concatenate(pos), cells=np.stack(cells), batch_idx=bi,
+             cutoff=cutoff, images=tuple(images), q=q, neutral=neutral, mu=_dipoles(g, ntot, zero=seed in ZERO_DIPOLE_SEEDS),
+             zero_dipoles=seed in ZERO_DIPOLE_SEEDS, pad=int(2 * g.integers(1, 5) + 1), emptied_row=int(np.sum(sizes[:big])) + sizes[big] // 2,
+             alpha=g.uniform(0.3, 0.45, len(sizes)), flags={k: bool(g.integers(2)) for k in DIPOLE_FLAGS}, autograd=bool(g.integers(2)),
+             weights=g.uniform(0.2, 1.8, ntot), perm=g.permutation(ntot) if seed in INTERLEAVED_SEEDS else None,
+             empty_system=1 if seed in EMPTY_SYSTEM_SEEDS else None, k_cutoff=K_CUTOFF, order=order,
+             mesh=tuple(int(v) for v in g.choice(mesh_choices(order), 3)))
+    _with_entries(c)
+    i, j, S = c["entries"]
+    own_image = (i == j) & (np.abs(S).sum(1) > 0)
+    c["self_images"] = frozenset(int(v) for v in np.unique(bi[i[own_image]]))
+    c["min_dist"] = float(entry_distances(c).min())
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def _dipole_row_ladder(name):
+    """Lane trips of `dp_pair_kernel`: a cluster of n atoms (`systems.molecule`, no contact below 1) inside a cubic cell four cluster diameters
+    wide, every pair stored with a zero shift: rows of n - 1 entries, as a matrix exactly that wide and as CSR."""
+    n = int(name[1:])
+    g = np.random.default_rng(8100 + n)
+    pos = S.molecule(n, density=0.05, min_dist=MIN_CONTACT, seed=600 + n, dtype=np.float64)[0]
+    c = dict(op="ewald_dipole", dtype="float64", sizes=(n,), pos=pos, cells=None, batch_idx=np.zeros(n, np.int32), cutoff=1e9, images=(0,), q=g.normal(size=n),
+             mu=_dipoles(g, n), zero_dipoles=False, pad=0, emptied_row=None, alpha=np.array([0.35]), weights=g.uniform(0.2, 1.8, n), perm=None, empty_system=None)
+    _with_entries(c)
+    dist = entry_distances(c)
+    c["diameter"], c["min_dist"] = float(dist.max()), float(dist.min())
+    c["cells"] = (np.eye(3) * 4.0 * c["diameter"])[None]
+    return c
+
+
+def _one_system(seed, n, box, triclinic=True, alpha=0.4):
+    g = np.random.default_rng(seed)
+    cell = charge_cell(box, triclinic)
+    return g, dict(dtype="float64", sizes=(n,), pos=spaced_positions(g, n, cell), cells=cell[None], batch_idx=np.zeros(n, np.int32), q=g.normal(size=n) + 0.05,
+                   mu=_dipoles(g, n), zero_dipoles=False, alpha=np.array([alpha]), weights=g.uniform(0.2, 1.8, n), perm=None, empty_system=None)
+
+
+@functools.lru_cache(maxsize=None)
+def dipole_k_case():
+    """The K ladder of `dp_recip_gather_kernel` (64 k per trip) and `dp_recip_virial_kernel` (256): 60 atoms in the box of 9; the rungs are
+    the first K vectors of the package's half-space set of cutoff `K_LADDER_CUTOFF`.  alpha is 1.0, not an Ewald parameter one would use with
+    this set: at 0.4 the 513th vector carries 5e-17 of the largest Green weight and a kernel that skips it passes; at 1.0 every one of the 513
+    carries at least 2e-7 of it (the CPU suite asserts 1e-7: 1e4 bars)."""
+    _, c = _one_system(8200, 60, 9.0, alpha=K_LADDER_ALPHA)
+    return dict(c, op="ewald_dipole", k_cutoff=K_LADDER_CUTOFF)
+
+
+@functools.lru_cache(maxsize=None)
+def dipole_atom_case():
+    """The atom ladder of `dp_sf_kernel` (256 atoms per trip): one batch of 255, 256, 257 and 1 atoms in boxes of 14 to 15, about 65 k-vectors
+    per system; reciprocal half only."""
+    g = np.random.default_rng(8300)
+    boxes, tri = (14.0, 14.5, 15.0, 14.0), (True, False, True, False)
+    cells = np.stack([charge_cell(b, t) for b, t in zip(boxes, tri)])
+    pos = np.concatenate([spaced_positions(g, n, cell) for n, cell in zip(ATOM_RUNGS, cells)])
+    n = sum(ATOM_RUNGS)
+    return dict(op="ewald_dipole", dtype="float64", sizes=ATOM_RUNGS, pos=pos, cells=cells, batch_idx=np.repeat(np.arange(4, dtype=np.int32), ATOM_RUNGS),
+                q=g.normal(size=n) + 0.05, mu=_dipoles(g, n), zero_dipoles=False, alpha=g.uniform(0.3, 0.45, 4), weights=g.uniform(0.2, 1.8, n), perm=None,
+                empty_system=None, k_cutoff=ATOM_LADDER_K_CUTOFF)
+
+
+@functools.lru_cache(maxsize=None)
+def _spread_pool(order):
+    """33 atoms in the triclinic cell of tests/test_pme_dipole_gpu.py, fractional coordinates in [-0.2, 1.2]: stencils cross every face.
+    The pool was drawn anew twice (DESIGN.md 3.21 says why); the CPU suite asserts the restatement's float32 deviation below 1e-5 on every rung."""
+    g = np.random.default_rng(SPREAD_POOL_SEED + order)
+    cell = np.array([[8.0, 0.0, 0.0], [0.7, 8.8, 0.0], [-0.4, 0.5, 7.2]])
+    n = PG_ATOMS + 1
+    return dict(pos=g.uniform(-0.2, 1.2, (n, 3)) @ cell, cells=cell[None], q=g.normal(size=n) + 0.05, mu=0.5 * g.normal(size=(n, 3)) / np.sqrt(3.0),
+                weights=g.uniform(0.2, 1.8, n))
+
+
+@functools.lru_cache(maxsize=None)
+def dipole_spread_case(order, n):
+    """The first n atoms of the order's pool on mesh `SPREAD_MESH`: blocks of `pme_dipole_spread_kernel` (256 // order^2 atoms) and of
+    `pme_dipole_gather_kernel` (32 atoms) one atom short of full, full, and one atom into the next."""
+    p = _spread_pool(order)
+    return dict(op="pme_dipole", dtype=None, sizes=(n,), pos=p["pos"][:n], cells=p["cells"], batch_idx=np.zeros(n, np.int32), q=p["q"][:n], mu=p["mu"][:n],
+                zero_dipoles=False, alpha=np.array([0.35]), weights=p["weights"][:n], perm=None, empty_system=None, order=order, mesh=SPREAD_MESH)
+
+
+@functools.lru_cache(maxsize=None)
+def dipole_big_mesh_case():
+    """12 atoms on mesh (40, 36, 96): 40 x 36 x 49 = 70 560 half-spectrum points, more than the 256 x 256 one trip of
+    `pme_dipole_virial_kernel`'s grid-stride loop covers."""
+    _, c = _one_system(8500, 12, 9.0, alpha=0.35)
+    return dict(c, op="pme_dipole", order=5, mesh=BIG_MESH)
+
+
+def dipole_case(kind, key):
+    """kind: "sweep" (key: (op, seed)), "row" (rung name), "k", "atoms", "spread" (key: (order, n)), "big"."""
+    if kind == "sweep":
+        return _dipole_sweep(*key)
+    return {"row": _dipole_row_ladder, "k": lambda _: dipole_k_case(), "atoms": lambda _: dipole_atom_case(), "spread": lambda k: dipole_spread_case(*k),
+            "big": lambda _: dipole_big_mesh_case()}[kind](key)
+
+
+def dipole_tensors(c, dtype=torch.float64):
+    """(pos, q, mu, cells, alpha, batch_idx | None) of a dipole case as CPU tensors; batch_idx None for one system."""
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=dtype)  # noqa: E731
+    bi = torch.as_tensor(c["batch_idx"]) if len(c["sizes"]) > 1 else None
+    return t(c["pos"]), t(c["q"]), t(c["mu"]), t(c["cells"]), t(c["alpha"]), bi
+
+
+def dipole_k_vectors(c, dtype=torch.float64):
+    """The case's k set from the package's generator ([K, 3] for one system, [B, K, 3] for a batch), on the CPU."""
+    from nvalchemiops.interactions.electrostatics import generate_k_vectors_ewald_summation
+
+    cells = torch.as_tensor(c["cells"], dtype=dtype)
+    return generate_k_vectors_ewald_summation(cells if len(c["sizes"]) > 1 else cells[0], c["k_cutoff"])
+
+
+@functools.lru_cache(maxsize=None)
+def pme_dipole_reference(kind, key, mode="float64", weighted=False):
+    """`pme_dipole_reference.evaluate` on the case's mesh and order, in its float64 or its float32 mode; `weighted`: the derivatives are those
+    of L = sum_i w_i E_i with the case's weights (and no virial), else of the total energy."""
+    c = dipole_case(kind, key)
+    pos, q, mu, cells, alpha, bi = dipole_tensors(c)
+    return PR.evaluate(pos, q, mu, cells, alpha if bi is not None else float(alpha[0]), c["mesh"], c["order"], batch_idx=bi,
+                       weights=torch.as_tensor(c["weights"]) if weighted else None, dtype=torch.float64 if mode == "float64" else torch.float32,
+                       virial=not weighted)
+
+
+def pme_float32_deviation(kind, key, weighted=False):
+    """Per output: max |float32 mode - float64 mode| / max |float64 mode| of the restatement: a quarter of the float32 bar of the GPU test."""
+    r64, r32 = pme_dipole_reference(kind, key, "float64", weighted), pme_dipole_reference(kind, key, "float32", weighted)
+    return {k: float(np.abs(r32[k] - r64[k]).max() / np.abs(r64[k]).max()) for k in r64 if np.abs(r64[k]).max() > 0}
+
+
+def green_weights(c, k_vectors):
+    """G_k = (8 pi / V) exp(-k^2 / 4 alpha^2) / k^2 of the k-vectors of a one-system case (numpy)."""
+    k2 = (np.asarray(k_vectors, np.float64) ** 2).sum(-1)
+    return 8.0 * np.pi / abs(np.linalg.det(c["cells"][0])) * np.exp(-k2 / (4.0 * float(c["alpha"][0]) ** 2)) / k2
+
+
+def hermitian_plane_virial(kind, key):
+    """Per system [B, 3, 3]: what the plane k = (nz - 1) / 2 of the half spectrum of an odd-nz mesh adds to the k-space virial for one unit
+    of its Hermitian weight (`pme_dipole_reference.half_spectrum_plane_virial`).  A kernel that weighs this plane once instead of twice
+    (`k == nz / 2` for `2 * k == nz`) is off by exactly this much."""
+    c = dipole_case(kind, key)
+    assert c["mesh"][2] % 2 == 1
+    pos, q, mu, cells, alpha, bi = dipole_tensors(c)
+    sys_of = torch.zeros(len(pos), dtype=torch.long) if bi is None else bi.long()
+    out = np.zeros((len(cells), 3, 3))
+    for s, cell in enumerate(cells):
+        own = torch.nonzero(sys_of == s).reshape(-1)
+        if own.numel():
+            out[s] = PR.half_spectrum_plane_virial(pos[own], q[own], mu[own], cell, alpha[s], c["mesh"], c["order"], c["mesh"][2] // 2)
+    return out

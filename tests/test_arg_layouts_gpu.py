@@ -21,6 +21,8 @@ Which variant goes to which argument (no tensor argument of a listed entry point
     argument class                                   off col row  T   F   x0  i64 flt
     positions [N,3] (also reference/current, k-vectors, math points)
                                                       x   x   x   x   -   -   -   (math points, current_positions: x)
+    dipoles [N,3], k_vectors [K,3] / [B,K,3] of the
+      point-dipole operators                          x   x   x   x   -   -   -   x
     cell [3,3] / [B,3,3]                              x   -   x*  -   x   x*  -   x      (* batch forms)
     pbc [3] / [B,3] (bool)                            x   -   x*  -   -   x*  -   -
     charges, values, raw energies, alpha [B]          x   x   x   -   -   x*  -   x      (values [N,C] also T)
@@ -46,14 +48,20 @@ box).  A code path that ignored strides or dtype would read wrong values but sta
 out-of-bounds access, even against a broken library.  Everything that COULD go out of bounds is in tests/test_arg_contract_cpu.py, behind
 a launch guard.  Shapes: 130 atoms (more than two waves, no multiple of 64) in a triclinic cell of 12 Bohr, a batch of 70 + 60 atoms,
 cutoff 5 Bohr (20 - 60 neighbours), meshes (12, 10, 14) and (16, 8, 24), tables with 4 species present.  `dftd4`, `dftd4_atm`,
-`gaussian_charge_correction` and `charge_equilibration` have fixtures of their own (tests/layout_cases.py, which says why);
-tests/test_layout_sensitivity_cpu.py checks without a GPU that an argument of theirs read one row off moves the result by 100 bars.
+`gaussian_charge_correction`, `charge_equilibration` and the point-dipole operators have fixtures of their own (tests/layout_cases.py, which
+says why); tests/test_layout_sensitivity_cpu.py checks without a GPU that an argument of theirs read one row off moves the result by 100 bars.
 
 MEASURED on one MI355X for those four ops (variants run, all in one run; every sweep prints its line under `pytest -s`): dftd4 single
 system 69 (matrix, `D4Parameters`) + 73 (CSR, tables as a dict) + 11 (float64 positions), batch 75 + 78 + 12; dftd4_atm 65 + 69 + 11,
 44 + 44 (the tables on the compact block) and 71 + 74 + 12; gaussian_charge_correction 25 (matrix) + 29 (CSR) single, 31 + 34 batch, in float32 and in float64; charge_equilibration
 33 + 37 (cluster batch), 50 + 54 (periodic Ewald batch) + 1 (stride-0 cell).  Worst |variant - canonical| / bar: 0 in every sweep, the
-periodic solves included: every variant gave the bits of the canonical call."""
+periodic solves included: every variant gave the bits of the canonical call.
+
+Point-dipole operators, in float32 and in float64 alike (variants run; single system / batch): ewald_dipole_reciprocal_space 25 / 32,
+pme_dipole_reciprocal_space 20 / 27, ewald_dipole_real_space 30 (matrix) + 34 (CSR) / 37 + 39, ewald_dipole_correction 35 + 39 / 42 + 44,
+pme_dipole_correction 30 + 34 / 37 + 39: 1 088 variants.  The explicit sums gave the bits of the canonical call in every variant.  The mesh
+term stayed within 0.0015 of its 1e-12 bar in float64 (float64 atomic adds in the spread) and gave the bits of the canonical call in
+float32, where the spread adds in float64 and rounds once; so did `pme_dipole_correction` (0.0004 in float64).  DESIGN.md section 3.21."""
 import functools
 import re
 import types
@@ -72,8 +80,10 @@ from tests import test_d3_zero_atm_gpu as TZA
 from tests import test_d3_zero_gpu as TZ
 from tests import test_d4_atm_gpu as TD4A
 from tests import test_d4_gpu as TD4
+from tests import test_dipole_gpu as TDP
 from tests import test_gaussian_charges_gpu as TG
 from tests import test_math_gpu as TM
+from tests import test_pme_dipole_gpu as TPD
 from tests import test_pme_gpu as TP
 from tests import test_qeq_gpu as TQ
 
@@ -1019,6 +1029,114 @@ def test_charge_equilibration_periodic_ewald_batch(same_cell):
                ref=(out.charges, out.chemical_potential), shared=("cell",) if same_cell else ())
 
 
+# ---- point dipoles: explicit Ewald sum and particle-mesh Ewald ---------------------------------------------------------------------------------
+
+DIP = POS + " flt"  # dipoles [N, 3], k_vectors [K, 3] / [B, K, 3]
+
+
+@functools.lru_cache(maxsize=None)
+def _dfx(dtype_name, batch):
+    """The dipole fixture of tests/layout_cases.py on the device with both list layouts (cutoff 7 Bohr) and its restatements, computed once:
+    the explicit sum (total, real-space half, reciprocal half) on the stored entries and the fixture's k set, the mesh term in float64 and
+    -- for the float32 bar -- in the restatement's float32 mode."""
+    from nvalchemiops.neighborlist import batch_cell_list, cell_list
+
+    c, dt = LC.dipole(batch), np.dtype(dtype_name).type
+    f = types.SimpleNamespace(batch=batch, n=len(c["pos"]), tdtype=F32 if dt == np.float32 else F64)
+    f.P, f.C, f.Q, f.MU, f.AL, f.KV = (_t(c[k].astype(dt)) for k in ("pos", "cell", "q", "mu", "alpha", "kv"))
+    f.BI = None if not batch else _t(c["batch_idx"])
+    pbc = torch.ones((f.C.shape[0], 3), dtype=torch.bool, device=DEV)
+    if not batch:
+        f.nm, f.num, f.sh = cell_list(f.P, LC.GC_RC, f.C[0], pbc[0], max_neighbors=MG)
+        f.lst, f.ptr, f.lsh = cell_list(f.P, LC.GC_RC, f.C[0], pbc[0], max_neighbors=MG, return_neighbor_list=True)
+    else:
+        f.nm, f.num, f.sh = batch_cell_list(f.P, LC.GC_RC, f.C, pbc, f.BI, max_neighbors=MG)
+        f.lst, f.ptr, f.lsh = batch_cell_list(f.P, LC.GC_RC, f.C, pbc, f.BI, max_neighbors=MG, return_neighbor_list=True)
+    assert 64 < int(f.num.max()) <= MG and f.KV.shape[-2] > 256
+    f.rel = 1e-11 if dt == np.float64 else 1e-6  # tests/test_dipole_gpu.py: test_parity_fp64_matrix_and_csr / test_parity_fp32_inputs
+    ent = TDP.R.entries_from_matrix(f.nm, f.sh, f.n)
+    ev = lambda entries, kv: TDP.R.evaluate(f.P, f.Q, f.MU, f.C, f.AL, entries, kv, batch_idx=f.BI, distance_dtype=f.tdtype)  # noqa: E731
+    f.ref = dict(total=ev(ent, f.KV), real=ev(ent, None), recip=ev(None, f.KV), mesh=LC.dipole_reference(batch, "pme"))
+    if dt == np.float32:
+        low = LC.dipole_reference(batch, "pme", dtype=F32)
+        f.mesh_rel = {k: 4.0 * float(np.abs(low[k] - f.ref["mesh"][k]).max() / np.abs(f.ref["mesh"][k]).max()) for k in LC.DP_NAMES}  # tests/test_pme_dipole_gpu.py
+    else:
+        f.mesh_rel = {k: 1e-10 for k in LC.DP_NAMES}
+    f.two_runs = 1e-12 if dt == np.float64 else 1e-6  # two device results of the mesh term (float atomics in the spread)
+    return f
+
+
+def _close_two_runs(rel):
+    """|variant - canonical| <= rel x max |canonical| per output: the mesh term's spread adds with float atomics."""
+    def close(o, r, what, i):
+        err, scale = np.abs(o.detach().cpu().numpy().astype(np.float64) - r.astype(np.float64)).max(), np.abs(r).max()
+        if err / (rel * scale) > _WORST[0]:
+            _WORST[0] = float(err / (rel * scale))
+            print(f"    {what}: {_WORST[0]:.3g} of the bar")
+        assert err <= rel * scale, f"{what}: max err {err:.3e} > {rel * scale:.3e}"
+    return close
+
+
+@DTYPES
+@pytest.mark.parametrize("batch", [False, True])
+@_collecting
+def test_point_dipole_operators(dtype, batch):
+    """`ewald_dipole_correction`, `ewald_dipole_real_space`, `ewald_dipole_reciprocal_space`, `pme_dipole_reciprocal_space` and
+    `pme_dipole_correction`, all outputs.  The explicit sums use no atomics: every variant must give the BITS of the canonical call (the
+    `flt` variants too: every fixture value is a float32 number).  The mesh term, and the correction that contains it, within 1e-12
+    (float64) / 1e-6 (float32) of the largest canonical value per output."""
+    from nvalchemiops.interactions.electrostatics import (ewald_dipole_correction, ewald_dipole_real_space, ewald_dipole_reciprocal_space,
+                                                          pme_dipole_correction, pme_dipole_reciprocal_space)
+
+    f = _dfx(dtype, batch)
+    mesh = dict(mesh_dimensions=LC.DP_MESH, spline_order=LC.DP_ORDER)
+    two_runs = _close_two_runs(f.two_runs)
+    tag = f"{dtype}{' batch' if batch else ''}"
+    atoms = dict(positions=f.P, charges=f.Q, dipoles=f.MU, cell=f.C, alpha=f.AL)
+    aplan = dict(positions=POS, charges=VEC, dipoles=DIP, cell=CELLB if batch else CELL1, alpha=VEC)
+    if batch:
+        atoms["batch_idx"], aplan["batch_idx"] = f.BI, IDX
+    shared = ("cell", "alpha") if batch else ()
+
+    def against_restatement(out, ref, rel, what):
+        assert len(out) == 5
+        for name, o in zip(LC.DP_NAMES, out):
+            assert o.dtype == f.tdtype
+            if isinstance(rel, dict):
+                TPD._close(o.reshape(ref[name].shape), ref[name], f"{what} {name} vs the restatement", rel[name])
+            else:
+                TDP._close(o, ref[name], f"{what} {name} vs the restatement", rel)
+
+    # the halves that take no list
+    call = lambda **a: ewald_dipole_reciprocal_space(**a, **TDP.ALL)  # noqa: E731
+    kw = dict(atoms, k_vectors=f.KV)
+    ref = _tuple(call(**kw))
+    against_restatement(ref, f.ref["recip"], f.rel, f"ewald_dipole_reciprocal_space {tag}")
+    _swept(f"ewald_dipole_reciprocal_space {tag}", call, kw, dict(aplan, k_vectors=DIP), _exact, ref=ref, shared=shared)
+    call = lambda **a: pme_dipole_reciprocal_space(**a, **mesh, **TDP.ALL)  # noqa: E731
+    rec = _tuple(call(**atoms))
+    against_restatement(rec, f.ref["mesh"], f.mesh_rel, f"pme_dipole_reciprocal_space {tag}")
+    _swept(f"pme_dipole_reciprocal_space {tag}", call, atoms, aplan, two_runs, ref=rec, shared=shared)
+    # the entry points that take a list, in both list formats
+    for label, lists, lplan in (("matrix", dict(neighbor_matrix=f.nm, neighbor_matrix_shifts=f.sh, mask_value=f.n), dict(neighbor_matrix=MAT, neighbor_matrix_shifts=MAT)),
+                                ("csr", dict(neighbor_list=f.lst, neighbor_ptr=f.ptr, neighbor_shifts=f.lsh), dict(neighbor_list=MAT, neighbor_ptr=IDX, neighbor_shifts=MAT))):
+        sh = shared if label == "matrix" else ()
+        call = lambda **a: ewald_dipole_real_space(**a, **TDP.ALL)  # noqa: E731
+        real = _tuple(call(**atoms, **lists))
+        against_restatement(real, f.ref["real"], f.rel, f"ewald_dipole_real_space {tag} {label}")
+        _swept(f"ewald_dipole_real_space {tag} {label}", call, dict(atoms, **lists), dict(aplan, **lplan), _exact, ref=real, shared=sh)
+        call = lambda **a: ewald_dipole_correction(**a, **TDP.ALL)  # noqa: E731
+        kw = dict(atoms, k_vectors=f.KV, **lists)
+        ref = _tuple(call(**kw))
+        against_restatement(ref, f.ref["total"], f.rel, f"ewald_dipole_correction {tag} {label}")
+        _swept(f"ewald_dipole_correction {tag} {label}", call, kw, dict(aplan, k_vectors=DIP, **lplan), _exact, ref=ref, shared=sh)
+        call = lambda **a: pme_dipole_correction(**a, **mesh, **TDP.ALL)  # noqa: E731
+        ref = _tuple(call(**atoms, **lists))
+        for i, name in enumerate(LC.DP_NAMES):  # its halves were checked against their restatements above: the sum of the two canonical calls
+            two_runs(ref[i], (real[i] + rec[i]).cpu().numpy(), f"pme_dipole_correction {tag} {label} {name} vs real space + mesh", i)
+        _swept(f"pme_dipole_correction {tag} {label}", call, dict(atoms, **lists), dict(aplan, **lplan), two_runs, ref=ref, shared=sh)
+
+
 # ==== splines =============================================================================================================================
 
 MESH = "off col row T flt"
@@ -1236,6 +1354,32 @@ def test_gradient_layouts_of_the_dispersion_and_charge_ops(dtype):
             assert err <= rel[i] * scale[i], f"{what}: max err {err:.3e} on {scale[i]:.3e}"
 
         ops["charge_equilibration cluster batch"] = (solve, inputs, ("positions", "chi", "hardness", "sigma", "total_charge"), close_qeq)
+    _check_gradient_layouts(ops)
+
+
+@DTYPES
+def test_gradient_layouts_of_the_point_dipole_ops(dtype):
+    """The same for `ewald_dipole_correction` (matrix and CSR), `ewald_dipole_reciprocal_space` and `pme_dipole_reciprocal_space` on the single
+    system and the batch, with respect to positions, charges and dipoles.  The adjoints of the explicit sums are the forward kernels with
+    weights and use no atomics: equal bits.  The mesh term at the bar of two device results."""
+    from nvalchemiops.interactions.electrostatics import ewald_dipole_correction, ewald_dipole_reciprocal_space, pme_dipole_reciprocal_space
+
+    ops = {}
+    for batch in (False, True):
+        f = _dfx(dtype, batch)
+        bkw = dict(batch_idx=f.BI) if batch else {}
+        tag = " batch" if batch else ""
+        leaves, names = (f.P, f.Q, f.MU), ("positions", "charges", "dipoles")
+        ops[f"ewald_dipole_correction{tag}"] = (
+            lambda p, q, m, f=f, bkw=bkw: ewald_dipole_correction(p, q, m, f.C, f.AL, f.KV, neighbor_matrix=f.nm, neighbor_matrix_shifts=f.sh, mask_value=f.n, **bkw),
+            leaves, names, _exact)
+        ops[f"ewald_dipole_correction csr{tag}"] = (
+            lambda p, q, m, f=f, bkw=bkw: ewald_dipole_correction(p, q, m, f.C, f.AL, f.KV, neighbor_list=f.lst, neighbor_ptr=f.ptr, neighbor_shifts=f.lsh, **bkw),
+            leaves, names, _exact)
+        ops[f"ewald_dipole_reciprocal_space{tag}"] = (lambda p, q, m, f=f, bkw=bkw: ewald_dipole_reciprocal_space(p, q, m, f.C, f.KV, f.AL, **bkw), leaves, names, _exact)
+        ops[f"pme_dipole_reciprocal_space{tag}"] = (
+            lambda p, q, m, f=f, bkw=bkw: pme_dipole_reciprocal_space(p, q, m, f.C, f.AL, mesh_dimensions=LC.DP_MESH, spline_order=LC.DP_ORDER, **bkw),
+            leaves, names, _close_two_runs(f.two_runs))
     _check_gradient_layouts(ops)
 
 

@@ -103,3 +103,26 @@ def test_qeq_fixtures_rolled_electronegativity_hardness_and_widths(case):
         worst[arg] = float(((q - q_ref).abs() / (2.0 * bound)).max())
     print(f"[sensitivity qeq {case}] largest |moved - ref| / (2 x bound): " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
     assert all(v >= FACTOR for v in worst.values()), worst
+
+
+@pytest.mark.parametrize("op", ["ewald", "pme"])
+@pytest.mark.parametrize("batch", [False, True], ids=["single", "batch"])
+def test_dipole_fixture_rolled_dipoles_charges_and_alpha(batch, op):
+    """The widest bar the sweep applies to the canonical call is used: 1e-6 max|ref| (+ 1e-14) for the explicit sums (their float32 bar) and
+    4 x the restatement's own float32-against-float64 deviation for the mesh term (at most 4e-5 of max|ref|).  `alpha` holds one value per
+    system: on the single system rolling it changes nothing, so it is judged on the batch (0.4 and 0.375) only."""
+    c = L.dipole(batch)
+    ref = L.dipole_reference(batch, op)
+    assert abs(float(c["q"].sum())) > 1.0 and int((~c["mu"].any(axis=1)).sum()) == (4 if batch else 2)
+    if op == "ewald":
+        bars = {k: 1e-6 * np.abs(ref[k]).max() + 1e-14 for k in L.DP_NAMES}
+    else:
+        r32 = L.dipole_reference(batch, op, dtype=torch.float32)
+        bars = {k: 4.0 * np.abs(r32[k] - ref[k]).max() for k in L.DP_NAMES}
+        assert all(bars[k] <= 4e-5 * np.abs(ref[k]).max() for k in L.DP_NAMES)
+    worst = {}
+    for arg in ("mu", "q") + (("alpha",) if batch else ()):
+        moved = L.dipole_reference(batch, op, **{arg: _roll(c[arg])})
+        worst[arg] = max(_ratio(moved[k], ref[k], bars[k]) for k in L.DP_NAMES)
+    print(f"[sensitivity {op} dipole {'batch' if batch else 'single'}] largest |moved - ref| / bar: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+    assert all(v >= FACTOR for v in worst.values()), worst

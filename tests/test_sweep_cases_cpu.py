@@ -4,13 +4,16 @@ sit on its boundary, the separation of every variant from its default, the cover
 and the sensitivity of the reference-side numbers to four faults a kernel could have (DESIGN.md section 3.18 has the table)."""
 import os
 import re
+import time
 
 import numpy as np
 import pytest
+import torch
 
 from tests import atm_reference as A
 from tests import d4_atm_cases as K3
 from tests import d4_atm_reference as R3
+from tests import dipole_reference as DR
 from tests import sweep_cases as W
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "nvalchemi-toolkit-ops_amd", "csrc")
@@ -280,3 +283,224 @@ def test_qeq_unrolled_product_rung_rows():
     i2, _, _ = W.charge_entries(c, 0, images=2)
     assert len(i2) == len(i)
     assert W.UNROLLED_WIDTHS == (255, 256, 257, 335)
+
+
+# ---- point dipoles --------------------------------------------------------------------------------------------------------------------------------
+# The conditions of the cases of tests/test_sweep_dipoles_gpu.py.  COST: the restatement of a case is to stay below about a second; that is
+# asserted through what decides it (entries, atoms x k-vectors, atoms x mesh) and the time itself is only printed, so that a loaded machine
+# cannot fail the suite.  MEASURED here: 0.01 - 0.05 s per sweep seed for the explicit sum (up to 19 338 entries, 3 x 364 k-vectors), 0.03 -
+# 0.3 s for one evaluation of the mesh term; the float32 mode of the mesh restatement leaves its float64 mode by at most 2.6e-6 of
+# max |ref| over the twelve seeds, 3.3e-7 to 4.3e-6 on the spread / gather ladder and 2.8e-6 on the mesh of the two solve paths: all below
+# half of the 1e-5 asserted.
+
+FLOAT32_CAP = 1e-5  # of max |ref| per output: caps the float32 bar of the mesh term on the device at 4e-5
+
+
+def _tt(a):
+    return torch.as_tensor(np.ascontiguousarray(a))
+
+
+def _antisymmetric(v):
+    return float(np.linalg.norm(0.5 * (v - v.T)) / np.linalg.norm(v))
+
+
+def _nontrivial(c, ref, what):
+    """max |energies| > 0 (zero-dipole seeds: exactly 0 everywhere but dipole_grads, which exceed 1e-3), and a virial whose antisymmetric
+    part is above 1e-6 of its norm in every system with dipoles on two atoms or more (one dipole among its own images in a cubic cell has a
+    symmetric virial: there it must only be non-zero)."""
+    if c["zero_dipoles"]:
+        assert all(not ref[k].any() for k in ("energies", "forces", "charge_grads", "virial") if k in ref), what
+        assert np.abs(ref["dipole_grads"]).max() > 1e-3, what
+        return
+    assert np.abs(ref["energies"]).max() > 0.0, what
+    for s, v in enumerate(ref.get("virial", ())):
+        dipoles = int(c["mu"][c["batch_idx"] == s].any(axis=1).sum())
+        if dipoles >= 2:
+            assert _antisymmetric(v) > 1e-6, (what, s)
+        elif dipoles == 1:
+            assert v.any(), (what, s)
+        else:
+            assert not v.any(), (what, s, "a system without a dipole (or without atoms) has an exactly zero virial row")
+
+
+def _geometry_of_a_dipole_seed(c, seed):
+    n = len(c["pos"])
+    assert n == sum(c["sizes"]) == len(c["q"]) == len(c["mu"]) == len(c["batch_idx"]) == len(c["weights"])
+    assert 1 <= len(c["sizes"]) <= 3 and set(c["sizes"]) <= set(W.CHARGE_SIZES) | {0} and max(c["sizes"]) >= 9
+    assert c["min_dist"] >= W.MIN_CONTACT == 1.0 and c["min_dist"] == W.entry_distances(c).min()
+    assert 6.0 <= c["cutoff"] <= 7.0 and ((c["alpha"] >= 0.3) & (c["alpha"] <= 0.45)).all() and len(c["alpha"]) == len(c["sizes"]) == len(c["cells"])
+    assert c["dtype"] == ("float64", "float32")[seed % 2] and c["pad"] % 2 == 1 and 3 <= c["pad"] <= 9
+    for s, cell in enumerate(c["cells"]):
+        small = c["sizes"][s] in (0, 1, 9)
+        box = float(cell[0, 0])
+        assert box == (W._BOX[c["sizes"][s]] if not small else (5.0 if seed % 3 == 0 else 14.0))
+        i, j, S = W.charge_entries(c, s)
+        assert bool(((i == j) & (np.abs(S).sum(1) > 0)).any()) == (s in c["self_images"]) == (small and seed % 3 == 0 and c["sizes"][s] > 0)
+    i, j, S = W.stored_entries(c)
+    row = c["emptied_row"]
+    assert not (i == row).any() and not (j == row).any() and len(i) < len(c["entries"][0]), "one row emptied from both ends: the list stays full"
+    pairs = set(zip(i.tolist(), j.tolist(), map(tuple, S.tolist())))
+    assert all((b, a, (-s[0], -s[1], -s[2])) in pairs for a, b, s in list(pairs)[:2000]), "a full (symmetric) list"
+    assert c["zero_dipoles"] == (seed in W.ZERO_DIPOLE_SEEDS) == (not c["mu"].any())
+    zero_rows = int((~c["mu"].any(axis=1)).sum())
+    assert c["zero_dipoles"] or 1 <= zero_rows <= 3, "a few exact-zero rows"
+    if seed in W.INTERLEAVED_SEEDS:
+        p = W.interleaved(c)
+        assert len(c["sizes"]) >= 2 and (np.diff(p["batch_idx"]) < 0).any() and sorted(c["perm"].tolist()) == list(range(n))
+        assert np.array_equal(p["pos"], c["pos"][c["perm"]]) and np.isclose(W.entry_distances(p).min(), c["min_dist"], rtol=1e-12, atol=0.0)
+        assert np.array_equal(np.sort(W.entry_distances(p)), np.sort(W.entry_distances(c)))
+    else:
+        assert c["perm"] is None
+    if seed in W.EMPTY_SYSTEM_SEEDS:
+        assert len(c["sizes"]) == 3 and c["sizes"][1] == 0 and set(c["batch_idx"].tolist()) == {0, 2} and c["cells"].shape == (3, 3, 3) and c["empty_system"] == 1
+    else:
+        assert 0 not in c["sizes"] and c["empty_system"] is None
+
+
+def test_dipole_constants_are_the_kernels():
+    with open(os.path.join(CSRC, "pme.hip")) as f:
+        lanes = int(re.search(r"^#define PG_LANES\s+(\d+)", f.read(), re.M).group(1))
+    assert W.PG_ATOMS == 256 // lanes == 32
+    assert [W.spread_atoms_per_block(o) for o in W.PME_ORDERS] == [16, 10, 7]
+    assert W.spread_rungs(4) == (15, 16, 17, 31, 32, 33) and W.spread_rungs(5) == (9, 10, 11, 20, 31, 32, 33) and W.spread_rungs(6) == (6, 7, 8, 14, 31, 32, 33)
+    assert W.LANE_RUNGS == ("n64", "n65", "n66", "n129") and W.K_RUNGS == (63, 64, 65, 255, 256, 257, 513) and W.ATOM_RUNGS == (255, 256, 257, 1)
+    assert W.SPREAD_MESH == (9, 10, 11) and W.BIG_MESH == (40, 36, 96) and 40 * 36 * (96 // 2 + 1) > 256 * 256
+
+
+@pytest.mark.parametrize("seed", W.SEEDS)
+def test_ewald_dipole_seed_meets_its_conditions(seed):
+    c = W.dipole_case("sweep", ("ewald_dipole", seed))
+    _geometry_of_a_dipole_seed(c, seed)
+    pos, q, mu, cells, alpha, bi = W.dipole_tensors(c)
+    kv = W.dipole_k_vectors(c)
+    ent = tuple(_tt(e) for e in W.stored_entries(c))
+    assert len(ent[0]) <= 40_000 and len(pos) * kv.shape[-2] <= 200_000, "cost: the restatement of a sweep case stays far below a second"
+    t0 = time.perf_counter()
+    ref = DR.evaluate(pos, q, mu, cells, alpha, ent, kv, batch_idx=bi)
+    took = time.perf_counter() - t0
+    print(f"ewald_dipole {seed}: sizes {c['sizes']} {c['dtype']}, {len(ent[0])} entries, widest row {c['widest']}, K {kv.shape[-2]}, closest contact {c['min_dist']:.4f}, "
+          f"own images in {sorted(c['self_images'])}, max |E| {np.abs(ref['energies']).max():.3e}, restatement {took:.2f} s")
+    _nontrivial(c, ref, f"ewald_dipole {seed}")
+    if seed in W.INTERLEAVED_SEEDS:  # the real-space half on the interleaved batch is the sorted one's, atom by atom
+        p = W.interleaved(c)
+        a = DR.evaluate(*W.dipole_tensors(p)[:5], tuple(_tt(e) for e in W.stored_entries(p)), None, batch_idx=_tt(p["batch_idx"]))
+        b = DR.evaluate(pos, q, mu, cells, alpha, ent, None, batch_idx=bi)
+        assert np.abs(a["energies"] - b["energies"][c["perm"]]).max() <= 1e-12 * np.abs(b["energies"]).max()
+        assert np.abs(a["virial"] - b["virial"]).max() <= 1e-12 * np.abs(b["virial"]).max()
+
+
+@pytest.mark.parametrize("seed", W.SEEDS)
+def test_pme_dipole_seed_meets_its_conditions(seed):
+    c = W.dipole_case("sweep", ("pme_dipole", seed))
+    _geometry_of_a_dipole_seed(c, seed)
+    order, mesh = c["order"], c["mesh"]
+    assert order == W.PME_ORDERS[seed % 3] and set(mesh) <= set(W.mesh_choices(order)) and min(mesh) >= order
+    assert len(c["pos"]) * max(mesh) <= 10_000 and mesh[0] * mesh[1] * mesh[2] <= 4096, "cost: dense weights and one small mesh per system"
+    t0 = time.perf_counter()
+    ref = W.pme_dipole_reference("sweep", ("pme_dipole", seed))
+    took = time.perf_counter() - t0
+    _nontrivial(c, ref, f"pme_dipole {seed}")
+    dev = {**W.pme_float32_deviation("sweep", ("pme_dipole", seed)),
+           **{"weighted " + k: v for k, v in W.pme_float32_deviation("sweep", ("pme_dipole", seed), weighted=True).items() if k != "energies"}}
+    print(f"pme_dipole {seed}: sizes {c['sizes']} {c['dtype']}, order {order} mesh {mesh}, restatement {took:.2f} s, float32 mode against float64 mode: "
+          + ", ".join(f"{k} {v:.1e}" for k, v in dev.items()))
+    assert max(dev.values()) <= FLOAT32_CAP, dev
+    if mesh[2] % 2 == 1 and not c["zero_dipoles"]:
+        # the plane k = (nz - 1) / 2 has Hermitian weight 2 on an odd axis; a kernel that gives it 1 must be seen by the virial comparison
+        plane = np.abs(W.hermitian_plane_virial("sweep", ("pme_dipole", seed))).max() / np.abs(ref["virial"]).max()
+        bar = 1e-10 if c["dtype"] == "float64" else 4.0 * dev["virial"]
+        print(f"pme_dipole {seed}: the last plane of the odd axis holds {plane:.2e} of max |virial|: {plane / bar:.3g} bars")
+        assert plane >= 100.0 * bar, (plane, bar)
+    if seed in W.INTERLEAVED_SEEDS:  # the restatement needs no contiguous systems
+        p = W.interleaved(c)
+        pp, pq, pm, pc, pa, _ = W.dipole_tensors(p)
+        a = W.PR.evaluate(pp, pq, pm, pc, pa, mesh, order, batch_idx=_tt(p["batch_idx"]))
+        assert np.abs(a["energies"] - ref["energies"][c["perm"]]).max() <= 1e-12 * np.abs(ref["energies"]).max()
+        assert np.abs(a["virial"] - ref["virial"]).max() <= 1e-12 * np.abs(ref["virial"]).max()
+
+
+@pytest.mark.parametrize("op", W.DIPOLE_OPS)
+def test_dipole_seeds_cover_what_they_are_meant_to(op):
+    cases = [W.dipole_case("sweep", (op, s)) for s in W.SEEDS]
+    assert {c["dtype"] for c in cases} == {"float32", "float64"}
+    assert {n for c in cases for n in c["sizes"]} == set(W.CHARGE_SIZES) | {0} and {len(c["sizes"]) for c in cases} == {1, 2, 3}
+    assert any(c["self_images"] for c in cases) and any(not c["self_images"] for c in cases)
+    assert any(c["neutral"] for c in cases) and any(not c["neutral"] for c in cases)
+    assert sum(c["zero_dipoles"] for c in cases) == 3 == len(W.SEEDS) // 4 and {c["dtype"] for c in cases if c["zero_dipoles"]} == {"float32", "float64"}
+    assert sum(c["perm"] is not None for c in cases) == 2 and sum(c["empty_system"] is not None for c in cases) == 2
+    assert all(c["dtype"] == "float64" for c in cases if c["perm"] is not None)
+    assert not set(W.ZERO_DIPOLE_SEEDS) & set(W.INTERLEAVED_SEEDS + W.EMPTY_SYSTEM_SEEDS) and not set(W.INTERLEAVED_SEEDS) & set(W.EMPTY_SYSTEM_SEEDS)
+    assert any(np.allclose(c["cells"][s], np.diag(np.diag(c["cells"][s]))) for c in cases for s in range(len(c["sizes"])))
+    assert any(c["cells"][s][1, 0] != 0 for c in cases for s in range(len(c["sizes"])))
+    assert len({c["pad"] for c in cases}) >= 3
+    if op == "ewald_dipole":
+        flags = [tuple(sorted(k for k, v in c["flags"].items() if v)) for c in cases]
+        assert len(set(flags)) >= 6 and {c["autograd"] for c in cases} == {False, True}
+        assert all(any(c["flags"][k] for c in cases if not c["zero_dipoles"]) for k in W.DIPOLE_FLAGS)
+    else:
+        assert [c["order"] for c in cases] == [4, 5, 6] * 4
+        odd = [c["seed"] for c in cases if c["mesh"][2] % 2 == 1]
+        equal = [c["seed"] for c in cases if c["order"] in c["mesh"]]
+        print(f"pme_dipole: odd nz in seeds {odd}, a dimension equal to the order in seeds {equal}, meshes {[c['mesh'] for c in cases]}")
+        assert len(odd) >= 4 and len(equal) >= 2
+        assert any(not c["zero_dipoles"] for c in cases if c["seed"] in odd) and any(c["mesh"][2] % 2 == 0 and not c["zero_dipoles"] for c in cases)
+
+
+@pytest.mark.parametrize("name", W.LANE_RUNGS)
+def test_dipole_row_rung(name):
+    c = W.dipole_case("row", name)
+    n = len(c["pos"])
+    i, j, S = c["entries"]
+    d = np.linalg.norm(c["pos"][:, None] - c["pos"][None], axis=2)
+    off = d[~np.eye(n, dtype=bool)]
+    assert n == int(name[1:]) and n - 1 in (63, 64, 65, 128) and (np.bincount(i, minlength=n) == n - 1).all() and not S.any() and c["widest"] == n - 1
+    assert off.min() >= W.MIN_CONTACT and c["min_dist"] == pytest.approx(off.min()) and c["diameter"] == pytest.approx(off.max())
+    assert np.array_equal(c["cells"][0], np.eye(3) * 4.0 * c["diameter"]), "a cubic cell four cluster diameters wide: no image inside any cutoff"
+    pos, q, mu, cells, alpha, _ = W.dipole_tensors(c)
+    ref = DR.evaluate(pos, q, mu, cells, alpha, tuple(_tt(e) for e in c["entries"]), None)
+    _nontrivial(c, ref, name)
+
+
+def test_dipole_k_ladder_set_and_atom_ladder_batch():
+    c = W.dipole_case("k", None)
+    kv = W.dipole_k_vectors(c)
+    assert c["sizes"] == (60,) and c["cells"][0][0, 0] == 9.0 and kv.dim() == 2 and kv.shape[0] >= max(W.K_RUNGS) == 513
+    g = W.green_weights(c, kv[:513].numpy())
+    print(f"K ladder: smallest / largest Green weight of the first 513 vectors {g.min() / g.max():.1e}")
+    assert g.min() >= 1e-7 * g.max(), "every vector of every rung weighs: one skipped vector moves the sums by 1e4 bars or more"
+    pos, q, mu, cells, alpha, _ = W.dipole_tensors(c)
+    for k in W.K_RUNGS:
+        _nontrivial(c, DR.evaluate(pos, q, mu, cells, alpha, None, kv[:k]), f"K = {k}")
+    a = W.dipole_case("atoms", None)
+    ka = W.dipole_k_vectors(a)
+    print(f"K ladder: the set holds {kv.shape[0]} vectors; atom ladder: {ka.shape[1]} vectors per system")
+    assert a["sizes"] == (255, 256, 257, 1) and min(float(cl[0, 0]) for cl in a["cells"]) >= 14.0 and ka.shape[0] == 4 and 60 <= ka.shape[1] <= 70
+    assert np.array_equal(a["batch_idx"], np.repeat(np.arange(4), a["sizes"]))
+    pos, q, mu, cells, alpha, bi = W.dipole_tensors(a)
+    _nontrivial(a, DR.evaluate(pos, q, mu, cells, alpha, None, ka, batch_idx=bi), "atom ladder")
+
+
+@pytest.mark.parametrize("order", W.PME_ORDERS)
+def test_pme_dipole_ladders_float32_mode(order):
+    """The spread / gather ladder of this order, the mesh of tests/test_sweep_dipoles_gpu.py::test_both_solve_paths (the system of
+    tests/test_pme_dipole_gpu.py) and, at order 5, the big mesh: non-trivial, and the float32 mode within the cap."""
+    from tests import test_pme_dipole_gpu as TP
+
+    worst, lowest = 0.0, 1.0
+    for n in W.spread_rungs(order):
+        c = W.dipole_case("spread", (order, n))
+        assert len(c["pos"]) == n and c["mesh"] == W.SPREAD_MESH and c["order"] == order
+        frac = c["pos"] @ np.linalg.inv(c["cells"][0])
+        assert n < 9 or ((frac < 0).any() and (frac > 1).any()), "atoms outside the cell: stencils cross the faces"
+        _nontrivial(c, W.pme_dipole_reference("spread", (order, n)), f"order {order} N {n}")
+        dev = {**W.pme_float32_deviation("spread", (order, n)), **{"w " + k: v for k, v in W.pme_float32_deviation("spread", (order, n), weighted=True).items()}}
+        worst, lowest = max(worst, max(dev.values())), min(lowest, min(dev.values()))
+        assert max(dev.values()) <= FLOAT32_CAP, (n, dev)
+    r64, r32 = TP._reference(order, TP.MESH), TP._reference(order, TP.MESH, torch.float32)
+    solve = max(float(np.abs(r32[k] - r64[k]).max() / np.abs(r64[k]).max()) for k in r64)
+    print(f"order {order}: float32 mode against float64 mode, spread / gather ladder {lowest:.1e} to {worst:.1e}, mesh {TP.MESH} of the two solve paths {solve:.1e}")
+    assert solve <= FLOAT32_CAP
+    if order == 5:
+        c = W.dipole_case("big", None)
+        assert c["mesh"] == W.BIG_MESH and len(c["pos"]) == 12 and c["order"] == 5
+        _nontrivial(c, W.pme_dipole_reference("big", None), "big mesh")
