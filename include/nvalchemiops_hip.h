@@ -577,6 +577,54 @@ int mi_qeq_cg_update(const double* y, const double* partial_y, const double* cou
 int mi_qeq_cg_direction(const double* partial_rr, const int32_t* batch_idx, int n_atoms, int n_systems, int mode, double tolerance, const double* r,
                         double* p, const double* state_in, double* state_out, void* stream);
 
+/* Induced point dipoles (csrc/induced.hip; driver: nvalchemiops/interactions/electrostatics/induced.py): the real-space dipole-dipole operator
+ * of the point-dipole Ewald sum as a stored sparse operator of 3 x 3 blocks over the caller's FULL list, its product, and the vector kernels of
+ * a batched Jacobi-preconditioned conjugate-gradient solve of  H mu = b,  H = diag(1 / a) + T.  All arithmetic is fp64; only the pair vector
+ * and r are formed in the positions dtype.  No atomics anywhere: every per-system sum is a fixed-order fold into mi_induced_blocks() block
+ * partials that the next kernel sums itself, so these entry points are bit-reproducible.  Nothing synchronises with the host.
+ * n_systems <= 65535 wherever per-system sums are formed (one grid row per system; every block scans batch_idx).
+ * Solver vectors (x, y, y_in, r, p) are dense [n_atoms][3] float64.
+ *
+ * mi_induced_pair_tensors (once per geometry): for every slot e of the list layout -- padded matrix [n_atoms][max_neighbors]
+ *   (neighbor_ptr == NULL, n_slots = n_atoms * max_neighbors) or CSR (n_slots entries) -- with row i, neighbour j, unit shift S,
+ *   R = r_j - r_i + S . cell, r = |R|, formed as mi_ewald_dipole_real forms them (libm erfc / exp):
+ *     tensors[0][e] = B1, tensors[1][e] = B2, tensors[2..5)[e] = R      (five streams of n_slots float64: T_e = B1 I - B2 R R^T)
+ *     neighbors[e]  = j                                                  44 bytes per slot
+ *   r <= 1e-8: no contribution.  Padding (matrix entries equal to mask_value, any index outside [0, n_atoms)), entries without contribution
+ *   and entries with a non-polarisable atom at either end get zero coefficients and neighbors[e] = i, so neighbors[] is always safe to gather
+ *   with.  diagonal[i] = 1 / a_i, preconditioner[i] = a_i; an atom with a_i <= 0 or NaN is not polarisable: both are 1 and its row is empty.
+ *   polarizability, cell [n_systems,3,3], alpha [n_systems] in the positions dtype.  unit_shifts may be NULL (no translations).
+ * mi_induced_apply:  y[i] = (y_in ? y_in[i] : 0) + diagonal[i] x[i] + sum_{slots e of row i} (B1 x[j] - B2 (R . x[j]) R)   (one wave64 per row,
+ *   mi_induced_unroll_depth() trips in flight; y_in is added as given; x, y_in and y must not overlap).
+ *   partial (may be NULL): [n_systems][mi_induced_blocks()] block partials of sum_i x_i . y_i per system.  mi_induced_dot: those partials alone.
+ * State of a solve: [n_systems][mi_induced_state_words()] float64 = {r.z, b.b, done, iterations, alpha, beta, breakdown, r.r}; every kernel
+ *   reads state_in and writes state_out (two buffers used alternately; a fresh solve starts from zeros).
+ * mi_induced_cg_update(mode 0): from partial_y = the partials of y = H p:  alpha_s = r.z / p.y,  x += alpha p,  r -= alpha y,
+ *   partial_rr [n_systems][mi_induced_blocks()][2] = block partials of the new {r.r, r.z}, z = preconditioner * r.  A done system is not
+ *   touched.  A system that is not done and has p.y <= 0 or not finite is frozen (done = 1) with breakdown = 1: the operator is not positive
+ *   definite.  mode 1 (set-up): r = -y for y = H x0 - b; x, p and partial_y are not used.
+ * mi_induced_cg_direction(mode 0): beta_s = r.z_new / r.z_old,  p = z + beta p,  iterations += 1,  done = r.r_new <= tolerance^2 b.b; done
+ *   systems are frozen.  mode 1 (set-up): b.b = r.r, p = z, iterations = 0, done at once when b.b == 0.  mode 2 (restart): as mode 1 but b.b
+ *   is kept from state_in. */
+int mi_induced_blocks(void);
+int mi_induced_state_words(void);
+int mi_induced_tensor_words(void);
+int mi_induced_unroll_depth(void);
+int mi_induced_pair_tensors(const void* positions, const void* polarizability, const void* cell /*[n_systems,3,3]*/, const void* alpha /*[n_systems]*/,
+                            const int32_t* batch_idx, int n_atoms, int n_systems, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
+                            const int32_t* neighbor_ptr, int max_neighbors, int mask_value, long long n_slots, double* tensors, int32_t* neighbors,
+                            double* diagonal, double* preconditioner, void* stream);
+int mi_induced_apply(const double* tensors, const int32_t* neighbors, const double* diagonal, const double* x, const double* y_in,
+                     const int32_t* batch_idx, int n_atoms, int n_systems, const int32_t* neighbor_ptr, int max_neighbors, long long n_slots,
+                     double* y, double* partial, void* stream);
+int mi_induced_dot(const double* x, const double* y, const int32_t* batch_idx, int n_atoms, int n_systems, double* partial, void* stream);
+int mi_induced_cg_update(const double* y, const double* partial_y, const double* preconditioner, const int32_t* batch_idx, int n_atoms,
+                         int n_systems, int mode, double* x, double* r, const double* p, const double* state_in,
+                         double* state_out, double* partial_rr, void* stream);
+int mi_induced_cg_direction(const double* partial_rr, const double* preconditioner, const int32_t* batch_idx, int n_atoms, int n_systems,
+                            int mode, double tolerance, const double* r, double* p, const double* state_in, double* state_out,
+                            void* stream);
+
 /* Explicit-k reciprocal-space Ewald.  Replaces `alchemiops::_[batch_]ewald_reciprocal_space_energy[_forces
  * [_charge_grad]]` (ewald.py:1365-2318; kernels ewald_kernels.py:1496-2480).  Two passes, no [K,N] phase tables:
  *   mi_ewald_structure_factors : S[b][k] = 8pi/V exp(-k^2/4a^2)/k^2 * sum_j w_j exp(i k.r_j) (interleaved re,im; k^2<1e-10 -> 0)

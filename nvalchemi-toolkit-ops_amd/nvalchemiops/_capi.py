@@ -184,6 +184,21 @@ def lib() -> ctypes.CDLL:
         for name in ("mi_qeq_blocks", "mi_qeq_state_words"):
             getattr(L, name).restype = i
             getattr(L, name).argtypes = []
+        # induced point dipoles (nvalchemiops/interactions/electrostatics/induced.py)
+        ll = ctypes.c_longlong
+        L.mi_induced_pair_tensors.restype = i
+        L.mi_induced_pair_tensors.argtypes = [vp] * 5 + [i, i, i, vp, vp, vp, i, i, ll, vp, vp, vp, vp, vp]
+        L.mi_induced_apply.restype = i
+        L.mi_induced_apply.argtypes = [vp] * 6 + [i, i, vp, i, ll, vp, vp, vp]
+        L.mi_induced_dot.restype = i
+        L.mi_induced_dot.argtypes = [vp, vp, vp, i, i, vp, vp]
+        L.mi_induced_cg_update.restype = i
+        L.mi_induced_cg_update.argtypes = [vp] * 4 + [i, i, i] + [vp] * 7
+        L.mi_induced_cg_direction.restype = i
+        L.mi_induced_cg_direction.argtypes = [vp, vp, vp, i, i, i, dbl, vp, vp, vp, vp, vp]
+        for name in ("mi_induced_blocks", "mi_induced_state_words", "mi_induced_tensor_words", "mi_induced_unroll_depth"):
+            getattr(L, name).restype = i
+            getattr(L, name).argtypes = []
         _LIB = L
     return _LIB
 
