@@ -535,6 +535,31 @@ int mi_ewald_dipole_recip_gather(const void* positions, const void* charges, con
 int mi_ewald_dipole_recip_virial(const double* table, const void* k_vectors, const void* cell, const void* alpha, int n_systems, int n_k, int dtype,
                                  double* virial, void* stream);
 
+/* Thole damping of point dipoles, exponential form (the AMOEBA smearing; csrc/dipole.hip, the second radial kind of the pair kernel of
+ * mi_ewald_dipole_real; driver: nvalchemiops/interactions/electrostatics/thole.py): the short-ranged real-space correction that, ADDED to the
+ * energy of undamped point dipoles (mi_ewald_dipole_*, mi_pme_dipole_*), smears the charge-dipole and dipole-dipole terms.  Charge-charge terms
+ * are not touched, and nothing depends on an Ewald alpha.  Over the stored entries (i, j, S) of a FULL list, R = r_j - r_i + S . cell, r = |R|,
+ * a = polarizability [n_atoms] (positions dtype), E = thole_a r^3 / sqrt(a_i a_j):
+ *     D1 = -e^-E / r^3,  D2 = -3 (1 + E) e^-E / r^5,  D3 = -15 (1 + E + 3/5 E^2) e^-E / r^7
+ *     U = D1 (q_j c_i - q_i c_j + d) - D2 c_i c_j,        energies[i] = 1/2 sum_row U
+ * i.e. mi_ewald_dipole_real's expressions with D_n in place of B_n; arguments, weights (w = (g_i + g_j) / 2), flags, outputs, virial layout,
+ * arithmetic model (pair vector and r^2 in the positions dtype, the rest fp64, libm exp) and bit-reproducibility are those of
+ * mi_ewald_dipole_real.  An entry contributes exactly 0 when either end has a <= 0 or NaN (not polarisable: not damped), when r <= 1e-8, and
+ * when E >= 50 (it leaves before the exp; (1 + E + 0.6 E^2) e^-E < 4e-19 there).  Self-image entries (i, i, S != 0) are kept.
+ *   MI_DP_POLAR_GRAD   polarizability_grads [n_atoms] float64 = dL/da_i = -1 / (2 a_i) sum_row w E X,
+ *                      X = dU/dE at fixed R = (e^-E / r^3)(q_j c_i - q_i c_j + d) - (3 E e^-E / r^5) c_i c_j     (0 for a_i <= 0)
+ * cell may be NULL (a cluster: unit_shifts must be NULL too, no virial).  thole_a must be positive and finite.
+ * scratch: mi_thole_dipole_scratch_bytes(n_atoms, dtype) bytes ({x, y, z, q, mu, a} records + per-row virials), contents undefined.
+ * virial_partial is [n_systems][mi_thole_dipole_blocks()][9]. */
+#define MI_DP_POLAR_GRAD 16
+size_t mi_thole_dipole_scratch_bytes(int n_atoms, int dtype);
+int mi_thole_dipole_blocks(void);
+int mi_thole_dipole(const void* positions, const void* charges, const void* dipoles, const void* cell /*[n_systems,3,3] or NULL*/,
+                    const void* polarizability /*[n_atoms]*/, double thole_a, const int32_t* batch_idx, const double* weights, int n_atoms,
+                    int n_systems, int dtype, const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors,
+                    int mask_value, int flags, double* energies, void* forces, double* charge_grads, double* dipole_grads,
+                    double* polarizability_grads, double* virial_partial, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Charge equilibration (csrc/qeq.hip; driver: nvalchemiops/interactions/electrostatics/qeq.py): the real-space Hessian of the Gaussian-charge
  * electrostatic energy as a stored sparse operator over the caller's FULL list, its product, and the vector kernels of a batched projected
  * conjugate-gradient solve of  min_q sum chi_i q_i + 1/2 sum J_i q_i^2 + E_el(q),  sum_{i in s} q_i = Q_s.  All arithmetic is fp64; only the
@@ -594,6 +619,9 @@ int mi_qeq_cg_direction(const double* partial_rr, const int32_t* batch_idx, int 
  *   and entries with a non-polarisable atom at either end get zero coefficients and neighbors[e] = i, so neighbors[] is always safe to gather
  *   with.  diagonal[i] = 1 / a_i, preconditioner[i] = a_i; an atom with a_i <= 0 or NaN is not polarisable: both are 1 and its row is empty.
  *   polarizability, cell [n_systems,3,3], alpha [n_systems] in the positions dtype.  unit_shifts may be NULL (no translations).
+ * mi_thole_induced_pair_tensors: the same with exponential Thole damping of width thole_a (> 0, finite): tensors[0][e] = B1 + D1,
+ *   tensors[1][e] = B2 + D2 with the D_n and the E >= 50 exit of mi_thole_dipole, same streams and layout, so mi_induced_apply then gives
+ *   diagonal x + dE/dmu of mi_ewald_dipole_real + mi_thole_dipole at zero charges.  Everything else in this section is used unchanged.
  * mi_induced_apply:  y[i] = (y_in ? y_in[i] : 0) + diagonal[i] x[i] + sum_{slots e of row i} (B1 x[j] - B2 (R . x[j]) R)   (one wave64 per row,
  *   mi_induced_unroll_depth() trips in flight; y_in is added as given; x, y_in and y must not overlap).
  *   partial (may be NULL): [n_systems][mi_induced_blocks()] block partials of sum_i x_i . y_i per system.  mi_induced_dot: those partials alone.
@@ -614,6 +642,11 @@ int mi_induced_pair_tensors(const void* positions, const void* polarizability, c
                             const int32_t* batch_idx, int n_atoms, int n_systems, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
                             const int32_t* neighbor_ptr, int max_neighbors, int mask_value, long long n_slots, double* tensors, int32_t* neighbors,
                             double* diagonal, double* preconditioner, void* stream);
+int mi_thole_induced_pair_tensors(const void* positions, const void* polarizability, const void* cell /*[n_systems,3,3]*/,
+                                  const void* alpha /*[n_systems]*/, const int32_t* batch_idx, int n_atoms, int n_systems, int dtype,
+                                  const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors, int mask_value,
+                                  long long n_slots, double* tensors, int32_t* neighbors, double* diagonal, double* preconditioner,
+                                  double thole_a, void* stream);
 int mi_induced_apply(const double* tensors, const int32_t* neighbors, const double* diagonal, const double* x, const double* y_in,
                      const int32_t* batch_idx, int n_atoms, int n_systems, const int32_t* neighbor_ptr, int max_neighbors, long long n_slots,
                      double* y, double* partial, void* stream);

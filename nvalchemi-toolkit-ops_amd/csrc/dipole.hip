@@ -37,12 +37,44 @@ template <class T> struct DpRec {  // 32 / 64 bytes: two vector loads of one lin
   __device__ __forceinline__ void set_tail(const T* __restrict__ mu, size_t i) { mx = mu[3 * i]; my = mu[3 * i + 1]; mz = mu[3 * i + 2]; pad = T(0); }
 };
 
+// the record of the Thole kind: the polarisability rides in the word the Ewald kind leaves empty
+template <class T>
+__global__ void dp_thole_pack_kernel(const T* __restrict__ pos, const T* __restrict__ q, const T* __restrict__ mu, const T* __restrict__ polar,
+                                     int N, DpRec<T>* __restrict__ rec) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  DpRec<T> r;
+  r.x = pos[3 * (size_t)i]; r.y = pos[3 * (size_t)i + 1]; r.z = pos[3 * (size_t)i + 2]; r.q = q[i];
+  r.set_tail(mu, (size_t)i);
+  r.pad = polar[i];
+  rec[i] = r;
+}
+
 __device__ __forceinline__ double dp_volume(const double* cm) {
   return fabs(cm[0] * (cm[4] * cm[8] - cm[5] * cm[7]) - cm[1] * (cm[3] * cm[8] - cm[5] * cm[6]) + cm[2] * (cm[3] * cm[7] - cm[4] * cm[6]));
 }
 
-template <class T, bool CSR>
-__global__ __launch_bounds__(256) void dp_pair_kernel(const DpRec<T>* __restrict__ rec, const T* __restrict__ cell, const T* __restrict__ alpha,
+// The radial kind of dp_pair_kernel: what stands for B1, B2, B3 in the pair expressions above.  The kind's own launch arguments travel as one
+// struct in the place of the Ewald kernel's alpha pointer, so the Ewald instantiation keeps its argument block.
+//   DpEwald: B_n of the header, alpha per system.
+//   DpThole: the correction that ADDS exponential Thole smearing (the AMOEBA form) to undamped point dipoles.  With a_i, a_j the
+//     polarisabilities (the record's last word), a_T the Thole width and E = a_T r^3 / sqrt(a_i a_j):
+//       D1 = -e^-E / r^3,  D2 = -3 (1 + E) e^-E / r^5,  D3 = -15 (1 + E + 3/5 E^2) e^-E / r^7             (D_{n+1} = -(1/r) dD_n/dr, as for B_n)
+//     An entry with a_i <= 0 or a_j <= 0 (or NaN) is not damped, and one with E >= 50 leaves before the exp (its D_n are below 4e-19 of the
+//     undamped terms): both contribute exactly 0.  dL/da_i = -1 / (2 a_i) sum_row w E X,  X = dU/dE at fixed R = -D1 A - (3 E e^-E / r^5) c_i c_j.
+template <class T> struct DpEwald {
+  static constexpr bool thole = false;
+  const T* alpha;
+};
+template <class T> struct DpThole {
+  static constexpr bool thole = true;
+  double width;
+  double* __restrict__ pgrad;
+};
+#define DP_THOLE_EXIT 50.0
+
+template <class T, bool CSR, class Radial>
+__global__ __launch_bounds__(256) void dp_pair_kernel(const DpRec<T>* __restrict__ rec, const T* __restrict__ cell, const Radial rad,
                                                       const int* __restrict__ batch_idx, const double* __restrict__ g, int N,
                                                       const int* __restrict__ idx, const int* __restrict__ ush, const int* __restrict__ nptr, int M,
                                                       int mask_value, int flags, double* __restrict__ energies, T* __restrict__ forces,
@@ -54,8 +86,11 @@ __global__ __launch_bounds__(256) void dp_pair_kernel(const DpRec<T>* __restrict
   const bool shifted = ush != nullptr;
   T cm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (shifted) pair_row_cell(cell, s, cm);
-  const double al = (double)alpha[s];
-  const double ta = 2.0 * al * al, inv_a_sqrt_pi = 1.0 / (al * 1.7724538509055159);
+  double al = 0.0, ta = 0.0, inv_a_sqrt_pi = 0.0;
+  if constexpr (!Radial::thole) {
+    al = (double)rad.alpha[s];
+    ta = 2.0 * al * al; inv_a_sqrt_pi = 1.0 / (al * 1.7724538509055159);
+  }
   const DpRec<T> ri = rec[i];
   const double qi = (double)ri.q, mix = (double)ri.mx, miy = (double)ri.my, miz = (double)ri.mz;
   const double gi = g ? g[i] : 1.0;
@@ -65,6 +100,12 @@ __global__ __launch_bounds__(256) void dp_pair_kernel(const DpRec<T>* __restrict
   pair_row_range<CSR>(nptr, i, M, beg, end);
   double eacc = 0.0, cgi = 0.0, fx = 0.0, fy = 0.0, fz = 0.0, dx_ = 0.0, dy_ = 0.0, dz_ = 0.0;
   double t[DP_VIR_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  double pacc = 0.0;  // DpThole: sum_row w E X
+  const bool wp = Radial::thole && (flags & MI_DP_POLAR_GRAD) != 0;
+  const double ai = (double)ri.pad;
+  if constexpr (Radial::thole) {
+    if (!(ai > 0.0)) end = beg;  // row of an atom that is not polarisable: zeros
+  }
   for (long long e = beg + lane; e < end; e += MI_WAVE) {
     const int j = idx[e];
     if (pair_is_padding<CSR>(j, mask_value, N)) continue;
@@ -78,11 +119,28 @@ __global__ __launch_bounds__(256) void dp_pair_kernel(const DpRec<T>* __restrict
     const T r2t = sx * sx + sy * sy + sz * sz;
     const double dist = (double)sqrt(r2t);  // the distance is a quantity of the positions dtype
     if (!(dist > 1e-8)) continue;           // (NaN distances leave here too)
-    const double rinv = 1.0 / dist, rinv2 = rinv * rinv, ar = al * dist;
-    const double pre = exp(-(ar * ar)) * inv_a_sqrt_pi;
-    const double b0 = erfc(ar) * rinv;
-    const double b1 = (b0 + ta * pre) * rinv2;
-    const double b2 = (3.0 * b1 + ta * ta * pre) * rinv2;
+    double rinv2, pre, b1, b2;
+    double b3 = 0.0, xa = 0.0, xe = 0.0;  // DpThole: D3 and the two coefficients of E X = xa A - xe c_i c_j
+    if constexpr (!Radial::thole) {
+      const double rinv = 1.0 / dist, ar = al * dist;
+      rinv2 = rinv * rinv;
+      pre = exp(-(ar * ar)) * inv_a_sqrt_pi;
+      const double b0 = erfc(ar) * rinv;
+      b1 = (b0 + ta * pre) * rinv2;
+      b2 = (3.0 * b1 + ta * ta * pre) * rinv2;
+    } else {
+      const double aj = (double)rj.pad;
+      if (!(aj > 0.0)) continue;
+      const double big = rad.width * (dist * dist * dist) / sqrt(ai * aj);
+      if (!(big < DP_THOLE_EXIT)) continue;
+      const double rinv = 1.0 / dist, ex = exp(-big);
+      rinv2 = rinv * rinv; pre = 0.0;
+      const double d3 = ex * rinv * rinv2, d5 = 3.0 * d3 * rinv2;
+      b1 = -d3;
+      b2 = -(1.0 + big) * d5;
+      b3 = -5.0 * (1.0 + big + 0.6 * big * big) * d5 * rinv2;
+      xa = big * d3; xe = big * big * d5;
+    }
     const double rx = (double)sx, ry = (double)sy, rz = (double)sz;
     const double qj = (double)rj.q, mjx = (double)rj.mx, mjy = (double)rj.my, mjz = (double)rj.mz;
     const double ci = mix * rx + miy * ry + miz * rz, cj = mjx * rx + mjy * ry + mjz * rz;
@@ -95,8 +153,9 @@ __global__ __launch_bounds__(256) void dp_pair_kernel(const DpRec<T>* __restrict
       const double u = w * (b1 * qj - b2 * cj), v = w * b1;
       dx_ += u * rx + v * mjx; dy_ += u * ry + v * mjy; dz_ += u * rz + v * mjz;
     }
+    if (wp) pacc += w * (xa * a - xe * cc);
     if (wf || wv) {
-      const double b3 = (5.0 * b2 + ta * ta * ta * pre) * rinv2;
+      if constexpr (!Radial::thole) b3 = (5.0 * b2 + ta * ta * ta * pre) * rinv2;
       const double cr = w * (b3 * cc - b2 * a), cmi = w * (b1 * qj - b2 * cj), cmj = -w * (b1 * qi + b2 * ci);
       const double ux = cr * rx + cmi * mix + cmj * mjx, uy = cr * ry + cmi * miy + cmj * mjy, uz = cr * rz + cmi * miz + cmj * mjz;
       fx += ux; fy += uy; fz += uz;
@@ -116,6 +175,9 @@ __global__ __launch_bounds__(256) void dp_pair_kernel(const DpRec<T>* __restrict
   if (wd) {
     dx_ = wave_sum(dx_); dy_ = wave_sum(dy_); dz_ = wave_sum(dz_);
     if (lane == 0) { dgrad[3 * (size_t)i] = dx_; dgrad[3 * (size_t)i + 1] = dy_; dgrad[3 * (size_t)i + 2] = dz_; }
+  }
+  if constexpr (Radial::thole) {
+    if (wp) { pacc = wave_sum(pacc); if (lane == 0) rad.pgrad[i] = ai > 0.0 ? -0.5 * pacc / ai : 0.0; }
   }
   if (wv) {
 #pragma unroll
@@ -295,15 +357,66 @@ extern "C" int mi_ewald_dipole_real(const void* positions, const void* charges, 
   do {                                                                                                                                           \
     pair_pack_kernel<<<mi_blocks(n_atoms, 256), 256, 0, st>>>((const T_*)positions, (const T_*)charges, (const T_*)dipoles, n_atoms,             \
                                                               (DpRec<T_>*)scratch);                                                              \
-    dp_pair_kernel<T_, CSR_><<<blocks, 256, 0, st>>>((const DpRec<T_>*)scratch, (const T_*)cell, (const T_*)alpha, bi, weights, n_atoms, idx_j,  \
-                                                     unit_shifts, neighbor_ptr, max_neighbors, mask_value, flags, energies, (T_*)forces,         \
-                                                     charge_grads, dipole_grads, trow);                                                          \
+    dp_pair_kernel<T_, CSR_, DpEwald<T_>><<<blocks, 256, 0, st>>>((const DpRec<T_>*)scratch, (const T_*)cell, DpEwald<T_>{(const T_*)alpha}, bi,  \
+                                                                  weights, n_atoms, idx_j, unit_shifts, neighbor_ptr, max_neighbors, mask_value, \
+                                                                  flags, energies, (T_*)forces, charge_grads, dipole_grads, trow);               \
   } while (0)
   mi_timing_begin("ewald_dipole_real", stream);
   if (dtype == MI_F32) { if (neighbor_ptr) MI_DP(float, true); else MI_DP(float, false); }
   else { if (neighbor_ptr) MI_DP(double, true); else MI_DP(double, false); }
   mi_timing_end(stream);
 #undef MI_DP
+  MI_LAUNCH_CHECK();
+  if (virial) {
+    dp_fold_kernel<<<dim3(MI_FOLD_BLOCKS, n_systems), 256, 0, st>>>(trow, bi, n_atoms, virial_partial);
+    MI_LAUNCH_CHECK();
+  }
+  return MI_OK;
+}
+
+extern "C" int mi_thole_dipole_blocks(void) { return MI_FOLD_BLOCKS; }
+extern "C" size_t mi_thole_dipole_scratch_bytes(int n_atoms, int dtype) { return mi_ewald_dipole_real_scratch_bytes(n_atoms, dtype); }
+
+extern "C" int mi_thole_dipole(const void* positions, const void* charges, const void* dipoles, const void* cell, const void* polarizability,
+                               double thole_a, const int32_t* batch_idx, const double* weights, int n_atoms, int n_systems, int dtype,
+                               const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors, int mask_value,
+                               int flags, double* energies, void* forces, double* charge_grads, double* dipole_grads,
+                               double* polarizability_grads, double* virial_partial, void* scratch, size_t scratch_bytes, void* stream) {
+  MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
+  MI_REQUIRE(n_atoms >= 0, "n_atoms must not be negative");
+  MI_REQUIRE(n_systems >= 1 && n_systems <= 65535, "n_systems must be in [1, 65535]");
+  MI_REQUIRE(neighbor_ptr || max_neighbors >= 0, "max_neighbors must not be negative");
+  MI_REQUIRE(n_systems == 1 || batch_idx, "batch_idx is required for more than one system");
+  MI_REQUIRE(thole_a > 0.0 && thole_a < INFINITY, "thole_a must be positive and finite");
+  MI_REQUIRE(cell || !unit_shifts, "unit_shifts need a cell");
+  const bool virial = (flags & MI_DP_VIRIAL) != 0;
+  MI_REQUIRE(!virial || (unit_shifts && virial_partial), "the virial needs unit_shifts and virial_partial");
+  if (n_atoms == 0) return MI_OK;
+  MI_REQUIRE(positions && charges && dipoles && polarizability && idx_j, "null pointer");
+  MI_REQUIRE(energies || flags, "nothing to compute");
+  MI_REQUIRE(!(flags & MI_DP_FORCES) || forces, "forces output");
+  MI_REQUIRE(!(flags & MI_DP_CHARGE_GRAD) || charge_grads, "charge gradient output");
+  MI_REQUIRE(!(flags & MI_DP_DIPOLE_GRAD) || dipole_grads, "dipole gradient output");
+  MI_REQUIRE(!(flags & MI_DP_POLAR_GRAD) || polarizability_grads, "polarizability gradient output");
+  MI_REQUIRE(scratch && scratch_bytes >= mi_thole_dipole_scratch_bytes(n_atoms, dtype), "scratch smaller than mi_thole_dipole_scratch_bytes()");
+  hipStream_t st = (hipStream_t)stream;
+  double* trow = reinterpret_cast<double*>((char*)scratch + dp_rec_bytes(n_atoms, dtype));
+  const int blocks = mi_blocks(n_atoms, 256 / MI_WAVE);
+  const int32_t* bi = n_systems > 1 ? batch_idx : nullptr;
+#define MI_TH(T_, CSR_)                                                                                                                          \
+  do {                                                                                                                                           \
+    dp_thole_pack_kernel<<<mi_blocks(n_atoms, 256), 256, 0, st>>>((const T_*)positions, (const T_*)charges, (const T_*)dipoles,                  \
+                                                                  (const T_*)polarizability, n_atoms, (DpRec<T_>*)scratch);                      \
+    dp_pair_kernel<T_, CSR_, DpThole<T_>><<<blocks, 256, 0, st>>>((const DpRec<T_>*)scratch, (const T_*)cell,                                    \
+                                                                  DpThole<T_>{thole_a, polarizability_grads}, bi, weights, n_atoms, idx_j,       \
+                                                                  unit_shifts, neighbor_ptr, max_neighbors, mask_value, flags, energies,         \
+                                                                  (T_*)forces, charge_grads, dipole_grads, trow);                                \
+  } while (0)
+  mi_timing_begin("thole_dipole", stream);
+  if (dtype == MI_F32) { if (neighbor_ptr) MI_TH(float, true); else MI_TH(float, false); }
+  else { if (neighbor_ptr) MI_TH(double, true); else MI_TH(double, false); }
+  mi_timing_end(stream);
+#undef MI_TH
   MI_LAUNCH_CHECK();
   if (virial) {
     dp_fold_kernel<<<dim3(MI_FOLD_BLOCKS, n_systems), 256, 0, st>>>(trow, bi, n_atoms, virial_partial);

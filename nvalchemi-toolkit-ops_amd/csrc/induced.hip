@@ -34,12 +34,14 @@ namespace {
 #define IND_TENSOR_WORDS 5 // streams of the stored operator: {B1, B2, R_x, R_y, R_z}
 #define IND_DEPTH 4        // trips of a row in flight in ind_apply_kernel
 
-template <class T, bool CSR>
+// THOLE: the stored coefficients are B1 + D1 and B2 + D2 with the D_n of dp_pair_kernel's Thole kind (dipole.hip), E = thole_a r^3 / sqrt(a_i a_j)
+// and the same early exit at E >= 50, so sum_row T_e x_j is dE/dmu of mi_ewald_dipole_real + mi_thole_dipole for zero charges.
+template <class T, bool CSR, bool THOLE>
 __global__ __launch_bounds__(256) void ind_tensor_kernel(const T* __restrict__ pos, const T* __restrict__ polar, const T* __restrict__ cell,
                                                          const T* __restrict__ alpha, const int* __restrict__ batch_idx, int N,
                                                          const int* __restrict__ idx, const int* __restrict__ ush, const int* __restrict__ nptr,
                                                          int M, int mask_value, long long slots, double* __restrict__ ten, int* __restrict__ nbr,
-                                                         double* __restrict__ diag, double* __restrict__ precond) {
+                                                         double* __restrict__ diag, double* __restrict__ precond, double thole_a) {
   const int lane = threadIdx.x & (MI_WAVE - 1);
   const int i = pair_row_index();
   if (i >= N) return;
@@ -62,7 +64,8 @@ __global__ __launch_bounds__(256) void ind_tensor_kernel(const T* __restrict__ p
     const int j = idx[e];
     double b1 = 0.0, b2 = 0.0, rx = 0.0, ry = 0.0, rz = 0.0;
     int jj = i;  // padding and skipped entries: zero coefficients on the row's own index
-    if (pol_i && !pair_is_padding<CSR>(j, mask_value, N) && polar[j] > T(0)) {
+    T aj = T(0);
+    if (pol_i && !pair_is_padding<CSR>(j, mask_value, N) && (aj = polar[j]) > T(0)) {
       T sx = pos[3 * (size_t)j] - pix, sy = pos[3 * (size_t)j + 1] - piy, sz = pos[3 * (size_t)j + 2] - piz;
       if (shifted) {
         T sh[3];
@@ -77,6 +80,14 @@ __global__ __launch_bounds__(256) void ind_tensor_kernel(const T* __restrict__ p
         const double b0 = erfc(ar) * rinv;
         b1 = (b0 + ta * pre) * rinv2;
         b2 = (3.0 * b1 + ta * ta * pre) * rinv2;
+        if constexpr (THOLE) {
+          const double big = thole_a * (dist * dist * dist) / sqrt((double)ai * (double)aj);
+          if (big < 50.0) {
+            const double d3 = exp(-big) * rinv * rinv2;
+            b1 -= d3;
+            b2 -= 3.0 * (1.0 + big) * d3 * rinv2;
+          }
+        }
         rx = (double)sx; ry = (double)sy; rz = (double)sz;
         jj = j;
       }
@@ -257,11 +268,12 @@ extern "C" int mi_induced_state_words(void) { return IND_STATE_WORDS; }
 extern "C" int mi_induced_tensor_words(void) { return IND_TENSOR_WORDS; }
 extern "C" int mi_induced_unroll_depth(void) { return IND_DEPTH; }
 
-extern "C" int mi_induced_pair_tensors(const void* positions, const void* polarizability, const void* cell, const void* alpha,
-                                       const int32_t* batch_idx, int n_atoms, int n_systems, int dtype, const int32_t* idx_j,
-                                       const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors, int mask_value,
-                                       long long n_slots, double* tensors, int32_t* neighbors, double* diagonal, double* preconditioner,
-                                       void* stream) {
+namespace {
+
+int ind_pair_tensors(const void* positions, const void* polarizability, const void* cell, const void* alpha, const int32_t* batch_idx, int n_atoms,
+                     int n_systems, int dtype, const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors,
+                     int mask_value, long long n_slots, double* tensors, int32_t* neighbors, double* diagonal, double* preconditioner,
+                     bool thole, double thole_a, void* stream) {
   MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
   MI_REQUIRE(n_atoms >= 0, "n_atoms must not be negative");
   MI_REQUIRE(n_systems >= 1, "n_systems must be at least 1");
@@ -269,23 +281,49 @@ extern "C" int mi_induced_pair_tensors(const void* positions, const void* polari
   MI_REQUIRE(n_slots >= 0, "n_slots must not be negative");
   MI_REQUIRE(neighbor_ptr || n_slots == (long long)n_atoms * max_neighbors, "n_slots must be n_atoms * max_neighbors for a matrix");
   MI_REQUIRE(n_systems == 1 || batch_idx, "batch_idx is required for more than one system");
+  MI_REQUIRE(!thole || (thole_a > 0.0 && thole_a < INFINITY), "thole_a must be positive and finite");
   if (n_atoms == 0) return MI_OK;
   MI_REQUIRE(positions && polarizability && cell && alpha && diagonal && preconditioner, "null pointer");
   MI_REQUIRE(n_slots == 0 || (idx_j && tensors && neighbors), "null pointer");  // (a list may be empty)
   hipStream_t st = (hipStream_t)stream;
   const int blocks = mi_blocks(n_atoms, 256 / MI_WAVE);
   const int32_t* bi = n_systems > 1 ? batch_idx : nullptr;
-#define MI_IT(T_, CSR_)                                                                                                                       \
-  ind_tensor_kernel<T_, CSR_><<<blocks, 256, 0, st>>>((const T_*)positions, (const T_*)polarizability, (const T_*)cell, (const T_*)alpha, bi, \
-                                                      n_atoms, idx_j, unit_shifts, neighbor_ptr, max_neighbors, mask_value, n_slots, tensors, \
-                                                      neighbors, diagonal, preconditioner)
-  mi_timing_begin("induced_pair_tensors", stream);
-  if (dtype == MI_F32) { if (neighbor_ptr) MI_IT(float, true); else MI_IT(float, false); }
-  else { if (neighbor_ptr) MI_IT(double, true); else MI_IT(double, false); }
+#define MI_IT(T_, CSR_, THOLE_)                                                                                                                  \
+  ind_tensor_kernel<T_, CSR_, THOLE_><<<blocks, 256, 0, st>>>((const T_*)positions, (const T_*)polarizability, (const T_*)cell,                  \
+                                                              (const T_*)alpha, bi, n_atoms, idx_j, unit_shifts, neighbor_ptr, max_neighbors,    \
+                                                              mask_value, n_slots, tensors, neighbors, diagonal, preconditioner, thole_a)
+#define MI_IT_LAYOUT(T_)                                                                                                                         \
+  do {                                                                                                                                           \
+    if (thole) { if (neighbor_ptr) MI_IT(T_, true, true); else MI_IT(T_, false, true); }                                                         \
+    else { if (neighbor_ptr) MI_IT(T_, true, false); else MI_IT(T_, false, false); }                                                             \
+  } while (0)
+  mi_timing_begin(thole ? "thole_induced_pair_tensors" : "induced_pair_tensors", stream);
+  if (dtype == MI_F32) MI_IT_LAYOUT(float); else MI_IT_LAYOUT(double);
   mi_timing_end(stream);
+#undef MI_IT_LAYOUT
 #undef MI_IT
   MI_LAUNCH_CHECK();
   return MI_OK;
+}
+
+}  // namespace
+
+extern "C" int mi_induced_pair_tensors(const void* positions, const void* polarizability, const void* cell, const void* alpha,
+                                       const int32_t* batch_idx, int n_atoms, int n_systems, int dtype, const int32_t* idx_j,
+                                       const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors, int mask_value,
+                                       long long n_slots, double* tensors, int32_t* neighbors, double* diagonal, double* preconditioner,
+                                       void* stream) {
+  return ind_pair_tensors(positions, polarizability, cell, alpha, batch_idx, n_atoms, n_systems, dtype, idx_j, unit_shifts, neighbor_ptr,
+                          max_neighbors, mask_value, n_slots, tensors, neighbors, diagonal, preconditioner, false, 0.0, stream);
+}
+
+extern "C" int mi_thole_induced_pair_tensors(const void* positions, const void* polarizability, const void* cell, const void* alpha,
+                                             const int32_t* batch_idx, int n_atoms, int n_systems, int dtype, const int32_t* idx_j,
+                                             const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors, int mask_value,
+                                             long long n_slots, double* tensors, int32_t* neighbors, double* diagonal, double* preconditioner,
+                                             double thole_a, void* stream) {
+  return ind_pair_tensors(positions, polarizability, cell, alpha, batch_idx, n_atoms, n_systems, dtype, idx_j, unit_shifts, neighbor_ptr,
+                          max_neighbors, mask_value, n_slots, tensors, neighbors, diagonal, preconditioner, true, thole_a, stream);
 }
 
 extern "C" int mi_induced_apply(const double* tensors, const int32_t* neighbors, const double* diagonal, const double* x, const double* y_in,

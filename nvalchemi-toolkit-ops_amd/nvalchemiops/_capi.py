@@ -163,6 +163,13 @@ def lib() -> ctypes.CDLL:
         L.mi_ewald_dipole_real_scratch_bytes.argtypes = [i, i]
         L.mi_ewald_dipole_blocks.restype = i
         L.mi_ewald_dipole_blocks.argtypes = []
+        # Thole damping of point dipoles (nvalchemiops/interactions/electrostatics/thole.py)
+        L.mi_thole_dipole.restype = i
+        L.mi_thole_dipole.argtypes = [vp] * 5 + [ctypes.c_double, vp, vp, i, i, i, vp, vp, vp, i, i, i] + [vp] * 7 + [sz, vp]
+        L.mi_thole_dipole_scratch_bytes.restype = sz
+        L.mi_thole_dipole_scratch_bytes.argtypes = [i, i]
+        L.mi_thole_dipole_blocks.restype = i
+        L.mi_thole_dipole_blocks.argtypes = []
         # particle-mesh Ewald for point dipoles (nvalchemiops/interactions/electrostatics/pme_dipole.py)
         L.mi_pme_dipole_spread.restype = i
         L.mi_pme_dipole_spread.argtypes = [vp] * 6 + [i] * 7 + [vp, vp]
@@ -188,6 +195,8 @@ def lib() -> ctypes.CDLL:
         ll = ctypes.c_longlong
         L.mi_induced_pair_tensors.restype = i
         L.mi_induced_pair_tensors.argtypes = [vp] * 5 + [i, i, i, vp, vp, vp, i, i, ll, vp, vp, vp, vp, vp]
+        L.mi_thole_induced_pair_tensors.restype = i
+        L.mi_thole_induced_pair_tensors.argtypes = [vp] * 5 + [i, i, i, vp, vp, vp, i, i, ll, vp, vp, vp, vp, dbl, vp]
         L.mi_induced_apply.restype = i
         L.mi_induced_apply.argtypes = [vp] * 6 + [i, i, vp, i, ll, vp, vp, vp]
         L.mi_induced_dot.restype = i

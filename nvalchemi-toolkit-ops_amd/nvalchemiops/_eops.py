@@ -1762,7 +1762,87 @@ pme_dipole_reciprocal_space_op = _op("_pme_dipole_reciprocal_space", _dp_pme_fwd
                                      _dp_pme_setup)
 
 
-__all__ = ["pme_dipole_reciprocal_space_op", "pme_dipole_recip_bwd_op", "ewald_dipole_real_space_op", "ewald_dipole_reciprocal_space_op", "ewald_dipole_real_bwd_op", "ewald_dipole_recip_bwd_op",
+# Thole damping of point dipoles: the pattern of the real-space dipole op, with the polarisabilities as a fourth differentiable input, an
+# optional cell (clusters) and six outputs (polarizability_gradients before the virial).  The cell has no adjoint and is refused.
+_TH_NAME = f"{_NS}::_thole_dipole_correction"
+_TH_OUTPUTS = ("energies", "forces", "charge_gradients", "dipole_gradients", "polarizability_gradients", "virial")
+
+
+def _thole_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, polarizability: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor],
+               neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
+               neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int, thole: float, compute_forces: bool,
+               compute_charge_gradients: bool, compute_dipole_gradients: bool, compute_polarizability_gradients: bool,
+               compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from nvalchemiops.interactions.electrostatics.thole import _forward
+
+    out = _forward(positions, charges, dipoles, polarizability, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                   neighbor_matrix_shifts, int(mask_value), float(thole), compute_forces, compute_charge_gradients, compute_dipole_gradients,
+                   compute_polarizability_gradients, compute_virial)
+    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
+
+
+def _thole_fwd_fake(positions, charges, dipoles, polarizability, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                    neighbor_matrix_shifts, mask_value, thole, compute_forces, compute_charge_gradients, compute_dipole_gradients,
+                    compute_polarizability_gradients, compute_virial):
+    n = positions.shape[0]
+    nsys = cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1
+    empty = lambda: positions.new_empty((0,))  # noqa: E731
+    return (positions.new_empty((n,)), positions.new_empty((n, 3)) if compute_forces else empty(),
+            positions.new_empty((n,)) if compute_charge_gradients else empty(), positions.new_empty((n, 3)) if compute_dipole_gradients else empty(),
+            positions.new_empty((n,)) if compute_polarizability_gradients else empty(),
+            positions.new_empty((nsys, 3, 3)) if compute_virial else empty())
+
+
+def _thole_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, polarizability: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor],
+               neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
+               neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int, thole: float,
+               grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles, dL/dpolarizability) for L = sum_i g_i E_i."""
+    from nvalchemiops.interactions.electrostatics.thole import _adjoint
+
+    return _adjoint(positions, charges, dipoles, polarizability, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                    neighbor_matrix_shifts, int(mask_value), float(thole), grad_energies)
+
+
+def _thole_bwd_fake(positions, *rest):
+    n, f64 = positions.shape[0], dict(dtype=torch.float64)
+    return (positions.new_empty((n, 3), **f64), positions.new_empty((n,), **f64), positions.new_empty((n, 3), **f64),
+            positions.new_empty((n,), **f64))
+
+
+thole_dipole_bwd_op = torch.library.custom_op("nvalchemiops::thole_dipole_correction_backward", _thole_bwd, mutates_args=())
+thole_dipole_bwd_op.register_fake(_thole_bwd_fake)
+thole_dipole_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::thole_dipole_correction_backward"),
+                                      setup_context=lambda ctx, inputs, output: None)
+
+
+def _thole_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:11])
+    ctx.extra = (int(inputs[11]), float(inputs[12]))
+    ctx.set_materialize_grads(False)
+
+
+def _thole_backward(ctx, g_e, *g_explicit):
+    for what, g in zip(_TH_OUTPUTS[1:], g_explicit):
+        if g is not None:
+            raise NotImplementedError(_SECOND_ORDER.format(op=_TH_NAME, what=what))
+    need = ctx.needs_input_grad
+    if need[4]:
+        raise NotImplementedError(f"{_TH_NAME}: gradients w.r.t. cell are not provided by the Thole damping term (out of scope); use "
+                                  "compute_virial for the strain derivative.")
+    if g_e is None:
+        return (None,) * len(need)
+    saved = ctx.saved_tensors
+    positions, charges, dipoles, polar = saved[:4]
+    gpos, gq, gmu, gpol = thole_dipole_bwd_op(*saved, *ctx.extra, g_e)
+    return (gpos.to(positions.dtype) if need[0] else None, gq.to(charges.dtype) if need[1] else None,
+            gmu.to(dipoles.dtype) if need[2] else None, gpol.to(polar.dtype) if need[3] else None) + (None,) * (len(need) - 4)
+
+
+thole_dipole_correction_op = _op("_thole_dipole_correction", _thole_fwd, _thole_fwd_fake, _thole_backward, _thole_setup)
+
+
+__all__ = ["thole_dipole_correction_op", "thole_dipole_bwd_op", "pme_dipole_reciprocal_space_op", "pme_dipole_recip_bwd_op", "ewald_dipole_real_space_op", "ewald_dipole_reciprocal_space_op", "ewald_dipole_real_bwd_op", "ewald_dipole_recip_bwd_op",
            "gaussian_charge_correction_op", "gaussian_bwd_op","spline_spread_op", "batch_spline_spread_op", "spline_gather_op", "batch_spline_gather_op", "spline_gather_vec3_op",
            "batch_spline_gather_vec3_op", "spline_gather_gradient_op", "batch_spline_gather_gradient_op", "pme_green_structure_factor_op",
            "batch_pme_green_structure_factor_op", "pme_energy_corrections_op", "batch_pme_energy_corrections_op",

@@ -5,7 +5,9 @@ from nvalchemiops.interactions.electrostatics.ewald import (ewald_real_space, ew
 from nvalchemiops.interactions.electrostatics.dipole import ewald_dipole_correction, ewald_dipole_real_space, ewald_dipole_reciprocal_space
 from nvalchemiops.interactions.electrostatics.pme_dipole import pme_dipole_correction, pme_dipole_reciprocal_space
 from nvalchemiops.interactions.electrostatics.gaussian import gaussian_charge_correction
-from nvalchemiops.interactions.electrostatics.induced import InducedDipoleError, InducedDipoleResult, induced_dipoles
+from nvalchemiops.interactions.electrostatics.induced import (InducedDipoleError, InducedDipoleResult, induced_dipoles,
+                                                              thole_induced_dipoles)
+from nvalchemiops.interactions.electrostatics.thole import thole_dipole_correction
 from nvalchemiops.interactions.electrostatics.k_vectors import generate_k_vectors_ewald_summation, generate_k_vectors_pme
 from nvalchemiops.interactions.electrostatics.parameters import (EwaldParameters, PMEParameters, estimate_ewald_parameters,
                                                                  estimate_pme_mesh_dimensions, estimate_pme_parameters,
@@ -22,5 +24,5 @@ __all__ = [
     "ewald_real_space_with_virial", "pme_reciprocal_space_with_virial", "particle_mesh_ewald_with_virial", "ewald_reciprocal_space_with_virial",
     "ewald_summation_with_virial", "gaussian_charge_correction", "charge_equilibration", "ChargeEquilibrationError", "ChargeEquilibrationResult",
     "ewald_dipole_correction", "ewald_dipole_real_space", "ewald_dipole_reciprocal_space", "pme_dipole_correction", "pme_dipole_reciprocal_space",
-    "induced_dipoles", "InducedDipoleError", "InducedDipoleResult",
+    "induced_dipoles", "InducedDipoleError", "InducedDipoleResult", "thole_dipole_correction", "thole_induced_dipoles",
 ]

@@ -13,6 +13,9 @@ The geometry does not change during a solve, so the real-space part of T is a co
 `mi_induced_apply`, a sparse product of 3 x 3 blocks over 44 bytes per list slot, plus one reciprocal-space dipole-gradient call on the search
 direction.  The solver is Jacobi-preconditioned conjugate gradients (preconditioner diag(a)); all per-system scalars live on the device
 (`mi_induced_cg_update`, `mi_induced_cg_direction`) and every sum of these kernels is a fixed-order fold.
+
+In `thole_induced_dipoles` the energy is E_dip + `thole_dipole_correction` (exponential Thole damping, thole.py): `mi_thole_induced_pair_tensors` stores the
+damped coefficients in the same layout, and everything after the set-up is the same code.
 """
 from __future__ import annotations
 
@@ -24,6 +27,7 @@ from nvalchemiops import _capi as C
 from nvalchemiops.interactions.electrostatics import _pairs as P
 from nvalchemiops.interactions.electrostatics import dipole as D
 from nvalchemiops.interactions.electrostatics import pme_dipole as PD
+from nvalchemiops.interactions.electrostatics import thole as TH
 
 F64 = torch.float64
 InducedDipoleResult = namedtuple("InducedDipoleResult", ["dipoles", "polarization_energy", "iterations", "residual"])
@@ -36,7 +40,7 @@ class InducedDipoleError(RuntimeError):
 
 def _check(positions, charges, polarizability, cell, external_field, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
            neighbor_matrix_shifts, reciprocal, alpha, mesh_dimensions, mesh_spacing, spline_order, k_vectors, k_cutoff, tolerance, max_iterations,
-           check_interval, initial_dipoles) -> int:
+           check_interval, initial_dipoles, thole=None) -> int:
     """Every argument error, before anything is launched (`_pairs.check_dipole_lists` for the list and the required cell).  Returns the number
     of systems: the cell count."""
     if positions.dim() != 2 or positions.shape[1] != 3:
@@ -58,6 +62,8 @@ def _check(positions, charges, polarizability, cell, external_field, batch_idx, 
             raise ValueError(f"{name} must have one vector per atom: expected shape [{n}, 3], got {tuple(t.shape)}")
     if reciprocal not in ("pme", "ewald"):
         raise ValueError(f"reciprocal must be 'pme' or 'ewald', got {reciprocal!r}")
+    if thole is not None:
+        TH.check_thole(thole)
     nsys = cell.shape[0] if cell.dim() == 3 else 1
     C.check_neighbor_data(n, cell=cell, alpha=alpha)
     if reciprocal == "pme":
@@ -89,7 +95,7 @@ class _Operator:
     """H = diag(1 / a) + T of one geometry: the stored real-space tensors and the reciprocal-space dipole-gradient call."""
 
     def __init__(self, positions, polar, cell, batch_idx, nsys, lists, mask_value, reciprocal, alpha, mesh_dimensions, mesh_spacing, spline_order,
-                 k_vectors, k_cutoff, accuracy):
+                 k_vectors, k_cutoff, accuracy, thole=None):
         dt, dev, n = positions.dtype, positions.device, positions.shape[0]
         self.n, self.nsys, self.dt, self.dev = n, nsys, dt, dev
         self.pos = positions.detach().contiguous()
@@ -98,6 +104,7 @@ class _Operator:
         self.batch_idx = batch_idx if nsys > 1 else None
         self.cells = cell.detach().to(dt).reshape(-1, 3, 3).contiguous()
         self.reciprocal = reciprocal
+        self.thole = None if thole is None else float(thole)  # the Thole width: B_n + D_n in the stored operator, E_dip + E_thole in the energy
         self.alpha = self.kv = self.dims = self.order = None
         self._reciprocal_parameters(alpha, mesh_dimensions, mesh_spacing, spline_order, k_vectors, k_cutoff, accuracy)
         ls = P.list_inputs(*lists)
@@ -117,11 +124,13 @@ class _Operator:
             self.rp = D._recip_inputs(self.pos, zq, zmu, self.cells, self.kv, self.alpha, self.batch_idx)
 
     def pair_tensors(self):
-        rc = C.lib().mi_induced_pair_tensors(C.ptr(self.pos), C.ptr(self.polar), C.ptr(self.cells), C.ptr(self.alpha), C.ptr(self.bi), self.n,
-                                             self.nsys, C.dtype_code(self.dt), C.ptr(self.idx), C.ptr(self.sh), C.ptr(self.nptr), int(self.m),
-                                             self.mask_value, self.slots, C.ptr(self.tensors), C.ptr(self.nbr), C.ptr(self.diag),
-                                             C.ptr(self.precond), C.stream_of(self.pos))
-        C.check(rc, "mi_induced_pair_tensors")
+        args = (C.ptr(self.pos), C.ptr(self.polar), C.ptr(self.cells), C.ptr(self.alpha), C.ptr(self.bi), self.n, self.nsys, C.dtype_code(self.dt),
+                C.ptr(self.idx), C.ptr(self.sh), C.ptr(self.nptr), int(self.m), self.mask_value, self.slots, C.ptr(self.tensors), C.ptr(self.nbr),
+                C.ptr(self.diag), C.ptr(self.precond))
+        if self.thole is None:
+            C.check(C.lib().mi_induced_pair_tensors(*args, C.stream_of(self.pos)), "mi_induced_pair_tensors")
+        else:
+            C.check(C.lib().mi_thole_induced_pair_tensors(*args, C.cdouble(self.thole), C.stream_of(self.pos)), "mi_thole_induced_pair_tensors")
 
     def _reciprocal_parameters(self, alpha, mesh_dimensions, mesh_spacing, spline_order, k_vectors, k_cutoff, accuracy):
         """alpha, and the mesh or the k-vectors, as `pme_dipole_correction` / `ewald_dipole_correction` would choose them."""
@@ -201,6 +210,9 @@ class _Operator:
             else:
                 g = g + D.ewald_dipole_reciprocal_space(self.pos, q, mu0, self.cells, self.kv, self.alpha, batch_idx=self.batch_idx,
                                                         compute_dipole_gradients=True)[1].to(F64)
+            if self.thole is not None:
+                g = g + TH.thole_dipole_correction(self.pos, q, mu0, self.polar, self.cells, thole=self.thole, mask_value=mask_value,
+                                                   batch_idx=self.batch_idx, compute_dipole_gradients=True, **kw)[1].to(F64)
         b = -g if field is None else field.detach().to(F64) - g
         return (b * self.mask).contiguous()
 
@@ -264,21 +276,35 @@ def _info(state):
     return state[:, 3].to(torch.int64), torch.where(bb > 0, torch.sqrt(rr / torch.where(bb > 0, bb, torch.ones_like(bb))), torch.zeros_like(rr))
 
 
-def _dipole_energy(op: _Operator, positions, charges, dipoles, lists, mask_value):
-    """Total E_dip(charges, dipoles) from the differentiable public functions, alpha and the mesh / k-vectors of the solve held fixed."""
+def _thole_energy(op: _Operator, positions, charges, dipoles, polar, lists, mask_value):
+    """Total E_thole(charges, dipoles) of a damped solve from the differentiable public function (also w.r.t. the polarisabilities)."""
+    kw = dict(zip(("neighbor_list", "neighbor_ptr", "neighbor_shifts", "neighbor_matrix", "neighbor_matrix_shifts"), lists))
+    dt = positions.dtype
+    return TH.thole_dipole_correction(positions, charges.to(dt), dipoles.to(dt), polar.to(dt), op.cells, thole=op.thole, batch_idx=op.batch_idx,
+                                      mask_value=mask_value, **kw).sum()
+
+
+def _dipole_energy(op: _Operator, positions, charges, dipoles, lists, mask_value, polar=None):
+    """Total E_dip(charges, dipoles) from the differentiable public functions, alpha and the mesh / k-vectors of the solve held fixed; plus
+    E_thole of a damped solve (`polar` then gives the polarisabilities to differentiate; default: the operator's own)."""
     kw = dict(zip(("neighbor_list", "neighbor_ptr", "neighbor_shifts", "neighbor_matrix", "neighbor_matrix_shifts"), lists))
     q, mu = charges.to(positions.dtype), dipoles.to(positions.dtype)
     if op.reciprocal == "pme":
-        return PD.pme_dipole_correction(positions, q, mu, op.cells, alpha=op.alpha, mesh_dimensions=op.dims, spline_order=op.order,
-                                        batch_idx=op.batch_idx, mask_value=mask_value, **kw).sum()
-    return D.ewald_dipole_correction(positions, q, mu, op.cells, alpha=op.alpha, k_vectors=op.kv, batch_idx=op.batch_idx, mask_value=mask_value,
-                                     **kw).sum()
+        e = PD.pme_dipole_correction(positions, q, mu, op.cells, alpha=op.alpha, mesh_dimensions=op.dims, spline_order=op.order,
+                                     batch_idx=op.batch_idx, mask_value=mask_value, **kw).sum()
+    else:
+        e = D.ewald_dipole_correction(positions, q, mu, op.cells, alpha=op.alpha, k_vectors=op.kv, batch_idx=op.batch_idx, mask_value=mask_value,
+                                      **kw).sum()
+    if op.thole is None:
+        return e
+    return e + _thole_energy(op, positions, charges, dipoles, op.polar if polar is None else polar, lists, mask_value)
 
 
 class _InducedDipoles(torch.autograd.Function):
     """The solve under autograd: implicit differentiation of the stationarity condition, no new kernels.  With g = dL/dmu and z = H^-1 g (one
     more solve with the stored operator):  dL/dF = z,  dL/da_i = (z_i . mu_i) / a_i^2, and for theta in {positions, charges}
-    dL/dtheta = -1/2 d/dtheta [E_dip(q, mu + z) - E_dip(q, mu - z)]  with mu and z held fixed."""
+    dL/dtheta = -1/2 d/dtheta [E_dip(q, mu + z) - E_dip(q, mu - z)]  with mu and z held fixed.  A damped solve has E_dip + E_thole in that
+    difference, and E_thole depends on the polarisabilities: dL/da gains -1/2 d/da [E_thole(q, mu + z) - E_thole(q, mu - z)]."""
 
     @staticmethod
     def forward(ctx, positions, charges, polar, field, op, b, initial, lists, mask_value, solver):
@@ -308,16 +334,23 @@ class _InducedDipoles(torch.autograd.Function):
             g_polar = torch.where(ok, (z * mu).sum(1) / torch.where(ok, a * a, torch.ones_like(a)), torch.zeros_like(a)).to(polar.dtype)
         if need[3]:
             g_field = z.to(ctx.field_dtype)
-        if need[0] or need[1]:
+        damped_polar = need[2] and op.thole is not None
+        if need[0] or need[1] or damped_polar:
             with torch.enable_grad():
-                leaves = [positions.detach().requires_grad_(need[0]), charges.detach().requires_grad_(need[1])]
-                diff = (_dipole_energy(op, leaves[0], leaves[1], mu + z, ctx.lists, ctx.mask_value)
-                        - _dipole_energy(op, leaves[0], leaves[1], mu - z, ctx.lists, ctx.mask_value))
+                leaves = [positions.detach().requires_grad_(need[0]), charges.detach().requires_grad_(need[1]),
+                          polar.detach().requires_grad_(damped_polar)]
+                if need[0] or need[1]:
+                    energy = lambda d: _dipole_energy(op, leaves[0], leaves[1], d, ctx.lists, ctx.mask_value, leaves[2])  # noqa: E731
+                else:  # the polarisabilities alone: only E_thole depends on them
+                    energy = lambda d: _thole_energy(op, leaves[0], leaves[1], d, leaves[2], ctx.lists, ctx.mask_value)  # noqa: E731
+                diff = energy(mu + z) - energy(mu - z)
                 grads = list(torch.autograd.grad(-0.5 * diff, [t for t in leaves if t.requires_grad], allow_unused=True))
             if need[0]:
                 g_pos = grads.pop(0)
             if need[1]:
                 g_q = grads.pop(0)
+            if damped_polar:
+                g_polar = g_polar + grads.pop(0).to(polar.dtype)
         return g_pos, g_q, g_polar, g_field, None, None, None, None, None, None
 
 
@@ -367,14 +400,52 @@ def induced_dipoles(positions: torch.Tensor, charges: torch.Tensor, polarizabili
     have no cell adjoint, so `cell` is not differentiable).  Differentiating twice raises NotImplementedError, and so does tracing with
     torch.compile: the solve has a data-dependent trip count.  CPU tensors raise NativeLibraryError: there is no fallback.
 
-    Out of scope: Thole or other short-range damping, anisotropic polarisabilities, clusters without a cell, quadrupoles, a cell gradient,
-    an extended-Lagrangian or predictor scheme.  A damped permanent field can be passed through `external_field` with zero charges."""
+    These are undamped point dipoles.  `thole_induced_dipoles` is the same solve with exponential Thole damping, which keeps H positive
+    definite at the distances of bonded atoms.
+
+    Out of scope: anisotropic polarisabilities, clusters without a cell, quadrupoles, a cell gradient, an extended-Lagrangian or predictor
+    scheme.  A differently damped permanent field can be passed through `external_field` with zero charges."""
+    return _solve(None, positions, charges, polarizability, cell, external_field, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
+                  neighbor_matrix, neighbor_matrix_shifts, mask_value, reciprocal, alpha, mesh_dimensions, mesh_spacing, spline_order, k_vectors,
+                  k_cutoff, accuracy, tolerance, max_iterations, check_interval, initial_dipoles, return_info)
+
+
+def thole_induced_dipoles(positions: torch.Tensor, charges: torch.Tensor, polarizability, cell: torch.Tensor, *, thole: float | None = 0.39,
+                          external_field: torch.Tensor | None = None, batch_idx: torch.Tensor | None = None,
+                          neighbor_list: torch.Tensor | None = None, neighbor_ptr: torch.Tensor | None = None,
+                          neighbor_shifts: torch.Tensor | None = None, neighbor_matrix: torch.Tensor | None = None,
+                          neighbor_matrix_shifts: torch.Tensor | None = None, mask_value: int | None = None, reciprocal: str = "pme", alpha=None,
+                          mesh_dimensions: tuple[int, int, int] | None = None, mesh_spacing: float | None = None, spline_order: int = 5,
+                          k_vectors: torch.Tensor | None = None, k_cutoff: float | None = None, accuracy: float = 1e-6,
+                          tolerance: float = 1e-8, max_iterations: int = 200, check_interval: int = 4,
+                          initial_dipoles: torch.Tensor | None = None, return_info: bool = False):
+    """`induced_dipoles` with exponential Thole damping of width `thole` (AMOEBA uses 0.39): every argument, convention, return value and
+    error of `induced_dipoles`, with E_dip + `thole_dipole_correction` in the place of E_dip everywhere.  The stored operator holds B_n + D_n
+    (`mi_thole_induced_pair_tensors`: same layout, same product and CG kernels), the right-hand side and the implicit gradients include the
+    damped charge field, and dL/dpolarizability gains the derivative of E_thole.  The returned dipoles make
+    `dipole_grads(*_dipole_correction) + dipole_grads(thole_dipole_correction) + mu / a - F` vanish.  With damping H stays positive definite
+    at the distances of bonded atoms, where the undamped operator is not.  `thole=None` is `induced_dipoles` itself: the same launches and,
+    with reciprocal="ewald", the same bits.  `thole` that is not finite or not positive raises ValueError before anything is launched.
+
+    (`induced_dipoles` keeps its argument list as it is; the damped solve is this function of its own and not a keyword there.)
+
+    Out of scope: per-pair Thole widths, the linear Thole form and AMOEBA's separate direct-field damping and polarisation groups, and what
+    `induced_dipoles` leaves out."""
+    return _solve(thole, positions, charges, polarizability, cell, external_field, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
+                  neighbor_matrix, neighbor_matrix_shifts, mask_value, reciprocal, alpha, mesh_dimensions, mesh_spacing, spline_order, k_vectors,
+                  k_cutoff, accuracy, tolerance, max_iterations, check_interval, initial_dipoles, return_info)
+
+
+def _solve(thole, positions, charges, polarizability, cell, external_field, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
+           neighbor_matrix, neighbor_matrix_shifts, mask_value, reciprocal, alpha, mesh_dimensions, mesh_spacing, spline_order, k_vectors, k_cutoff,
+           accuracy, tolerance, max_iterations, check_interval, initial_dipoles, return_info):
+    """What `induced_dipoles` (thole None) and `thole_induced_dipoles` run."""
     if C.tracing():
         raise NotImplementedError("induced_dipoles cannot be traced by torch.compile: the solve iterates until a device-side convergence "
                                   "flag is set.  Call it outside the compiled region (torch.compiler.disable).")
     nsys = _check(positions, charges, polarizability, cell, external_field, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
                   neighbor_matrix_shifts, reciprocal, alpha, mesh_dimensions, mesh_spacing, spline_order, k_vectors, k_cutoff, tolerance,
-                  max_iterations, check_interval, initial_dipoles)
+                  max_iterations, check_interval, initial_dipoles, thole)
     n, dev, dt = positions.shape[0], positions.device, positions.dtype
     if mask_value is None:
         mask_value = n
@@ -390,7 +461,7 @@ def induced_dipoles(positions: torch.Tensor, charges: torch.Tensor, polarizabili
                  else torch.full((n,), float(polarizability), dtype=dt, device=dev))
         lists = (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
         op = _Operator(positions, polar, cell, batch_idx, nsys, lists, mask_value, reciprocal, alpha, mesh_dimensions, mesh_spacing, spline_order,
-                       k_vectors, k_cutoff, accuracy)
+                       k_vectors, k_cutoff, accuracy, thole)
         b = op.right_hand_side(charges, external_field, lists, int(mask_value))
         solver = (float(tolerance), int(max_iterations), int(check_interval))
         diff = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (positions, charges, polar, external_field))
@@ -406,4 +477,4 @@ def induced_dipoles(positions: torch.Tensor, charges: torch.Tensor, polarizabili
         return InducedDipoleResult(dipoles, (-0.5 * op.dot(mu64, b)).to(dt), iterations, residual.to(dt))
 
 
-__all__ = ["induced_dipoles", "InducedDipoleError", "InducedDipoleResult"]
+__all__ = ["induced_dipoles", "thole_induced_dipoles", "InducedDipoleError", "InducedDipoleResult"]
