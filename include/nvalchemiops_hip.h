@@ -535,6 +535,65 @@ int mi_ewald_dipole_recip_gather(const void* positions, const void* charges, con
 int mi_ewald_dipole_recip_virial(const double* table, const void* k_vectors, const void* cell, const void* alpha, int n_systems, int n_k, int dtype,
                                  double* virial, void* stream);
 
+/* Point-quadrupole Ewald sum (csrc/quadrupole.hip; driver: nvalchemiops/interactions/electrostatics/quadrupole.py): what point quadrupoles Q_i
+ * (symmetric Cartesian second Taylor coefficients 1/2 sum q d d, fixed in the laboratory frame; a traceless Stone quadrupole Theta is
+ * Q = Theta / 3) add to the periodic energy of point charges q_i and point dipoles mu_i -- the charge-quadrupole, dipole-quadrupole and
+ * quadrupole-quadrupole terms ONLY; the result is added to mi_ewald_dipole_* and an Ewald / PME energy.  quadrupoles is [n_atoms][3][3] in the
+ * positions dtype; 1/2 (Q + Q^T) is used, tracelessness is not required.  Arithmetic, reproducibility, list formats, weights
+ * (w = (g_i + g_j) / 2), scratch and virial layout are those of mi_ewald_dipole_*.
+ *
+ * mi_ewald_quadrupole_real: with B_n as for mi_ewald_dipole_real continued to B4 (B5 only for forces / virial), c = mu.R, t = tr Q, a = Q R,
+ * s = R.a, m_ij = mu_i.a_j, m_ji = mu_j.a_i, p = a_i.a_j, d = Q_i:Q_j,
+ *     C1 = -(q_i t_j + q_j t_i),  C2 = q_i s_j + q_j s_i + 2 (m_ji - m_ij) + t_i c_j - t_j c_i + t_i t_j + 2 d,
+ *     C3 = c_i s_j - c_j s_i - t_i s_j - t_j s_i - 4 p,  C4 = s_i s_j,
+ *     U = B1 C1 + B2 C2 + B3 C3 + B4 C4,        energies[i] = 1/2 sum_row U        (entries with r <= 1e-8 skipped, nothing else)
+ *   MI_QD_FORCES          forces [n_atoms][3] (positions dtype) = -dL/dr_i = sum_row w dU/dR (csrc/quadrupole.hip states dU/dR)
+ *   MI_QD_CHARGE_GRAD     charge_grads [n_atoms] float64       = dL/dq_i  = sum_row w (B2 s_j - B1 t_j)
+ *   MI_QD_DIPOLE_GRAD     dipole_grads [n_atoms][3] float64    = dL/dmu_i = sum_row w ((B3 s_j - B2 t_j) R - 2 B2 a_j)   (independent of every mu)
+ *   MI_QD_QUADRUPOLE_GRAD quadrupole_grads [n_atoms][3][3] float64, symmetric = dL/dQ_i
+ *                         = sum_row w (A0 I + A1 R R^T + B2 (mu_j R^T + R mu_j^T) - 2 B3 (R a_j^T + a_j R^T) + 2 B2 Q_j),
+ *                         A0 = -B1 q_j + B2 (c_j + t_j) - B3 s_j,  A1 = B2 q_j - B3 (c_j + t_j) + B4 s_j
+ *   MI_QD_VIRIAL          virial_partial [n_systems][mi_ewald_quadrupole_blocks()][9] float64, W[a][b] = -1/2 sum_entries w (dU/dR)_a R_b, row-major
+ *                         and NOT symmetric; the caller sums the block dimension.  Needs unit_shifts.
+ * scratch: mi_ewald_quadrupole_real_scratch_bytes(n_atoms, dtype) bytes (16-word records {x, y, z, q, mu, Q(6), -} + per-row virials).
+ *
+ * mi_ewald_quadrupole_structure_factors: table [n_systems][n_k][10] float64 = {Re, Im} of {S_q, M_x, M_y, M_z, T}, T = sum_j g_j (k.Q_j.k)
+ * exp(i k.r_j), S_q and M as for the dipole table; table_v [n_systems][n_k][6] = {Re, Im} of V = sum_j g_j (Q_j k) exp(i k.r_j), or NULL
+ * (only the virial reads it).  UNSCALED.
+ *
+ * mi_ewald_quadrupole_recip_gather: with S' = S_q + i k.M, tau_i = k.Q_i.k, e_i = exp(i k.r_i),
+ *     energies[i] = 1/2 sum_k G_k { tau_i Re[conj(e_i) (T - S')] - Re[conj((q_i + i k.mu_i) e_i) T] }
+ *                   + 4 a^3 / (3 sqrt(pi)) q_i tr Q_i - 4 a^5 / (5 sqrt(pi)) (2 Q_i:Q_i + (tr Q_i)^2)                  (self term included)
+ * and forces, charge_grads, dipole_grads, quadrupole_grads [n_atoms][3][3] as above; any output may be NULL; adjoint form as for
+ * mi_ewald_dipole_recip_gather.
+ *
+ * mi_ewald_quadrupole_recip_virial: virial [n_systems][9] float64, row-major, with d(k.mu)/d eps_ab = -k_a mu_b, d(k.Q.k)/d eps_ab = -2 k_a (Q k)_b:
+ *     W[a][b] = sum_k e_k (delta_ab - 2 (1/k^2 + 1/(4 a^2)) k_a k_b) + G_k k_a (2 Re[conj(T - S') V_b] - (Im T Re M_b - Re T Im M_b)),
+ *     e_k = 1/2 G_k (|T|^2 - 2 Re[conj(S') T]). */
+#define MI_QD_FORCES 1
+#define MI_QD_CHARGE_GRAD 2
+#define MI_QD_DIPOLE_GRAD 4
+#define MI_QD_VIRIAL 8
+#define MI_QD_QUADRUPOLE_GRAD 16
+size_t mi_ewald_quadrupole_real_scratch_bytes(int n_atoms, int dtype);
+int mi_ewald_quadrupole_blocks(void);
+int mi_ewald_quadrupole_real(const void* positions, const void* charges, const void* dipoles, const void* quadrupoles,
+                             const void* cell /*[n_systems,3,3]*/, const void* alpha /*[n_systems]*/, const int32_t* batch_idx,
+                             const double* weights, int n_atoms, int n_systems, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
+                             const int32_t* neighbor_ptr, int max_neighbors, int mask_value, int flags, double* energies, void* forces,
+                             double* charge_grads, double* dipole_grads, double* quadrupole_grads, double* virial_partial, void* scratch,
+                             size_t scratch_bytes, void* stream);
+int mi_ewald_quadrupole_structure_factors(const void* positions, const void* charges, const void* dipoles, const void* quadrupoles,
+                                          const double* weights, const void* k_vectors, const int32_t* system_ptr, int n_atoms, int n_systems,
+                                          int n_k, int dtype, double* table, double* table_v, void* stream);
+int mi_ewald_quadrupole_recip_gather(const void* positions, const void* charges, const void* dipoles, const void* quadrupoles,
+                                     const void* k_vectors, const void* cell, const void* alpha, const int32_t* batch_idx, const double* table,
+                                     const double* table_g, const double* weights, int n_atoms, int n_systems, int n_k, int dtype,
+                                     double* energies, void* forces, double* charge_grads, double* dipole_grads, double* quadrupole_grads,
+                                     void* stream);
+int mi_ewald_quadrupole_recip_virial(const double* table, const double* table_v, const void* k_vectors, const void* cell, const void* alpha,
+                                     int n_systems, int n_k, int dtype, double* virial, void* stream);
+
 /* Thole damping of point dipoles, exponential form (the AMOEBA smearing; csrc/dipole.hip, the second radial kind of the pair kernel of
  * mi_ewald_dipole_real; driver: nvalchemiops/interactions/electrostatics/thole.py): the short-ranged real-space correction that, ADDED to the
  * energy of undamped point dipoles (mi_ewald_dipole_*, mi_pme_dipole_*), smears the charge-dipole and dipole-dipole terms.  Charge-charge terms

@@ -33,6 +33,7 @@ SOURCES = {
     "ewald.hip": os.environ.get("MI_EWALD_EXTRA_FLAGS", "").split(),
     "gaussian.hip": [],  # Gaussian-smeared charge correction (mi_gaussian_charges): fp64 pair math with libm erfc
     "dipole.hip": [],  # point-dipole Ewald sum (mi_ewald_dipole_*): fp64 pair math with libm erfc / exp, fp64 sincos phases
+    "quadrupole.hip": [],  # point-quadrupole Ewald sum (mi_ewald_quadrupole_*): the arithmetic model of dipole.hip, B_n continued to B5
     "qeq.hip": [],  # charge equilibration (mi_qeq_*): stored pair operator, its product and the CG vector kernels, all fp64
     "induced.hip": [],  # induced point dipoles (mi_induced_*): stored 3 x 3 pair operator, its product and the PCG vector kernels, all fp64
     "d4.hip": [],  # DFT-D4 two-body dispersion (mi_d4): fp32 pair math with IEEE divide / sqrt and libm erff / expf, fp64 sums

@@ -163,6 +163,19 @@ def lib() -> ctypes.CDLL:
         L.mi_ewald_dipole_real_scratch_bytes.argtypes = [i, i]
         L.mi_ewald_dipole_blocks.restype = i
         L.mi_ewald_dipole_blocks.argtypes = []
+        # point-quadrupole Ewald sum (nvalchemiops/interactions/electrostatics/quadrupole.py)
+        L.mi_ewald_quadrupole_real.restype = i
+        L.mi_ewald_quadrupole_real.argtypes = [vp] * 8 + [i, i, i, vp, vp, vp, i, i, i] + [vp] * 7 + [sz, vp]
+        L.mi_ewald_quadrupole_structure_factors.restype = i
+        L.mi_ewald_quadrupole_structure_factors.argtypes = [vp] * 7 + [i, i, i, i, vp, vp, vp]
+        L.mi_ewald_quadrupole_recip_gather.restype = i
+        L.mi_ewald_quadrupole_recip_gather.argtypes = [vp] * 11 + [i, i, i, i] + [vp] * 6
+        L.mi_ewald_quadrupole_recip_virial.restype = i
+        L.mi_ewald_quadrupole_recip_virial.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp, vp]
+        L.mi_ewald_quadrupole_real_scratch_bytes.restype = sz
+        L.mi_ewald_quadrupole_real_scratch_bytes.argtypes = [i, i]
+        L.mi_ewald_quadrupole_blocks.restype = i
+        L.mi_ewald_quadrupole_blocks.argtypes = []
         # Thole damping of point dipoles (nvalchemiops/interactions/electrostatics/thole.py)
         L.mi_thole_dipole.restype = i
         L.mi_thole_dipole.argtypes = [vp] * 5 + [ctypes.c_double, vp, vp, i, i, i, vp, vp, vp, i, i, i] + [vp] * 7 + [sz, vp]

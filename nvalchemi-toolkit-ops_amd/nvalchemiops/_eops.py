@@ -1842,7 +1842,141 @@ def _thole_backward(ctx, g_e, *g_explicit):
 thole_dipole_correction_op = _op("_thole_dipole_correction", _thole_fwd, _thole_fwd_fake, _thole_backward, _thole_setup)
 
 
-__all__ = ["thole_dipole_correction_op", "thole_dipole_bwd_op", "pme_dipole_reciprocal_space_op", "pme_dipole_recip_bwd_op", "ewald_dipole_real_space_op", "ewald_dipole_reciprocal_space_op", "ewald_dipole_real_bwd_op", "ewald_dipole_recip_bwd_op",
+# point-quadrupole Ewald sum: the pattern of the two point-dipole Ewald ops, with the quadrupoles as a fourth differentiable input and six
+# outputs (quadrupole_gradients before the virial).  Cell, alpha and k-vector gradients are refused.
+_QD_OUTPUTS = ("energies", "forces", "charge_gradients", "dipole_gradients", "quadrupole_gradients", "virial")
+_QD_NO_GRAD = ("{op}: gradients w.r.t. {what} are not provided by the point-quadrupole Ewald term (out of scope); use compute_virial for the "
+               "strain derivative.")
+
+
+def _qd_fake(positions, nsys, forces, cgrads, dgrads, qgrads, virial):
+    n = positions.shape[0]
+    empty = lambda: positions.new_empty((0,))  # noqa: E731
+    return (positions.new_empty((n,)), positions.new_empty((n, 3)) if forces else empty(), positions.new_empty((n,)) if cgrads else empty(),
+            positions.new_empty((n, 3)) if dgrads else empty(), positions.new_empty((n, 3, 3)) if qgrads else empty(),
+            positions.new_empty((nsys, 3, 3)) if virial else empty())
+
+
+def _qd_bwd_fake(positions, *rest):
+    n, f64 = positions.shape[0], dict(dtype=torch.float64)
+    return (positions.new_empty((n, 3), **f64), positions.new_empty((n,), **f64), positions.new_empty((n, 3), **f64),
+            positions.new_empty((n, 3, 3), **f64))
+
+
+def _qd_backward(name, bwd_op, refused):
+    """Autograd of a quadrupole op: `refused` maps the positions of inputs without an adjoint (cell, alpha, k_vectors) to their names."""
+    def backward(ctx, g_e, *g_explicit):
+        for what, g in zip(_QD_OUTPUTS[1:], g_explicit):
+            if g is not None:
+                raise NotImplementedError(_SECOND_ORDER.format(op=name, what=what))
+        need = ctx.needs_input_grad
+        for k, what in refused.items():
+            if need[k]:
+                raise NotImplementedError(_QD_NO_GRAD.format(op=name, what=what))
+        if g_e is None:
+            return (None,) * len(need)
+        saved = ctx.saved_tensors
+        positions, charges, dipoles, quadrupoles = saved[:4]
+        gpos, gq, gmu, gqd = bwd_op(*saved, *ctx.extra, g_e)
+        return (gpos.to(positions.dtype) if need[0] else None, gq.to(charges.dtype) if need[1] else None,
+                gmu.to(dipoles.dtype) if need[2] else None, gqd.to(quadrupoles.dtype) if need[3] else None) + (None,) * (len(need) - 4)
+
+    return backward
+
+
+def _qd_real_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, quadrupoles: Tensor, cell: Tensor, alpha: Tensor,
+                 batch_idx: Optional[Tensor], neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
+                 neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int, compute_forces: bool,
+                 compute_charge_gradients: bool, compute_dipole_gradients: bool, compute_quadrupole_gradients: bool,
+                 compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from nvalchemiops.interactions.electrostatics.quadrupole import _real_forward
+
+    out = _real_forward(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
+                        neighbor_matrix, neighbor_matrix_shifts, int(mask_value), compute_forces, compute_charge_gradients,
+                        compute_dipole_gradients, compute_quadrupole_gradients, compute_virial)
+    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
+
+
+def _qd_real_fwd_fake(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
+                      neighbor_matrix, neighbor_matrix_shifts, mask_value, compute_forces, compute_charge_gradients, compute_dipole_gradients,
+                      compute_quadrupole_gradients, compute_virial):
+    nsys = cell.reshape(-1, 3, 3).shape[0] if batch_idx is not None else 1
+    return _qd_fake(positions, nsys, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_quadrupole_gradients,
+                    compute_virial)
+
+
+def _qd_real_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, quadrupoles: Tensor, cell: Tensor, alpha: Tensor,
+                 batch_idx: Optional[Tensor], neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
+                 neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int,
+                 grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles, dL/dquadrupoles) for L = sum_i g_i E_i."""
+    from nvalchemiops.interactions.electrostatics.quadrupole import _real_adjoint
+
+    return _real_adjoint(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
+                         neighbor_matrix, neighbor_matrix_shifts, int(mask_value), grad_energies)
+
+
+ewald_quadrupole_real_bwd_op = torch.library.custom_op("nvalchemiops::ewald_quadrupole_real_space_backward", _qd_real_bwd, mutates_args=())
+ewald_quadrupole_real_bwd_op.register_fake(_qd_bwd_fake)
+ewald_quadrupole_real_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::ewald_quadrupole_real_space_backward"),
+                                               setup_context=lambda ctx, inputs, output: None)
+
+
+def _qd_real_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:12])
+    ctx.extra = (int(inputs[12]),)
+    ctx.set_materialize_grads(False)
+
+
+ewald_quadrupole_real_space_op = _op("_ewald_quadrupole_real_space", _qd_real_fwd, _qd_real_fwd_fake,
+                                     _qd_backward(f"{_NS}::_ewald_quadrupole_real_space", ewald_quadrupole_real_bwd_op, {4: "cell", 5: "alpha"}),
+                                     _qd_real_setup)
+
+
+def _qd_recip_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, quadrupoles: Tensor, cell: Tensor, k_vectors: Tensor, alpha: Tensor,
+                  batch_idx: Optional[Tensor], compute_forces: bool, compute_charge_gradients: bool, compute_dipole_gradients: bool,
+                  compute_quadrupole_gradients: bool, compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from nvalchemiops.interactions.electrostatics.quadrupole import _recip_forward
+
+    out = _recip_forward(positions, charges, dipoles, quadrupoles, cell, k_vectors, alpha, batch_idx, compute_forces, compute_charge_gradients,
+                         compute_dipole_gradients, compute_quadrupole_gradients, compute_virial)
+    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
+
+
+def _qd_recip_fwd_fake(positions, charges, dipoles, quadrupoles, cell, k_vectors, alpha, batch_idx, compute_forces, compute_charge_gradients,
+                       compute_dipole_gradients, compute_quadrupole_gradients, compute_virial):
+    return _qd_fake(positions, cell.reshape(-1, 3, 3).shape[0], compute_forces, compute_charge_gradients, compute_dipole_gradients,
+                    compute_quadrupole_gradients, compute_virial)
+
+
+def _qd_recip_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, quadrupoles: Tensor, cell: Tensor, k_vectors: Tensor, alpha: Tensor,
+                  batch_idx: Optional[Tensor], grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles, dL/dquadrupoles) for L = sum_i g_i E_i."""
+    from nvalchemiops.interactions.electrostatics.quadrupole import _recip_adjoint
+
+    return _recip_adjoint(positions, charges, dipoles, quadrupoles, cell, k_vectors, alpha, batch_idx, grad_energies)
+
+
+ewald_quadrupole_recip_bwd_op = torch.library.custom_op("nvalchemiops::ewald_quadrupole_reciprocal_space_backward", _qd_recip_bwd,
+                                                        mutates_args=())
+ewald_quadrupole_recip_bwd_op.register_fake(_qd_bwd_fake)
+ewald_quadrupole_recip_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::ewald_quadrupole_reciprocal_space_backward"),
+                                                setup_context=lambda ctx, inputs, output: None)
+
+
+def _qd_recip_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:8])
+    ctx.extra = ()
+    ctx.set_materialize_grads(False)
+
+
+ewald_quadrupole_reciprocal_space_op = _op("_ewald_quadrupole_reciprocal_space", _qd_recip_fwd, _qd_recip_fwd_fake,
+                                           _qd_backward(f"{_NS}::_ewald_quadrupole_reciprocal_space", ewald_quadrupole_recip_bwd_op,
+                                                        {4: "cell", 5: "k_vectors", 6: "alpha"}), _qd_recip_setup)
+
+
+__all__ = ["ewald_quadrupole_real_space_op", "ewald_quadrupole_reciprocal_space_op", "ewald_quadrupole_real_bwd_op",
+           "ewald_quadrupole_recip_bwd_op", "thole_dipole_correction_op", "thole_dipole_bwd_op", "pme_dipole_reciprocal_space_op", "pme_dipole_recip_bwd_op", "ewald_dipole_real_space_op", "ewald_dipole_reciprocal_space_op", "ewald_dipole_real_bwd_op", "ewald_dipole_recip_bwd_op",
            "gaussian_charge_correction_op", "gaussian_bwd_op","spline_spread_op", "batch_spline_spread_op", "spline_gather_op", "batch_spline_gather_op", "spline_gather_vec3_op",
            "batch_spline_gather_vec3_op", "spline_gather_gradient_op", "batch_spline_gather_gradient_op", "pme_green_structure_factor_op",
            "batch_pme_green_structure_factor_op", "pme_energy_corrections_op", "batch_pme_energy_corrections_op",

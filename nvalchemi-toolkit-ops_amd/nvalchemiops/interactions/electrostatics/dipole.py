@@ -45,7 +45,7 @@ _RETURNS = """Returns ``energies`` [N], or a tuple holding only what was asked f
     Energies are differentiable once w.r.t. positions, charges and dipoles, for any upstream gradient on the per-atom energies (the same
     kernels run as their own adjoint); the call then goes through an `alchemiops::_ewald_dipole_*` op, as it does under `torch.compile`.
     Differentiating the explicit forces, gradients or virial raises NotImplementedError.  Gradients w.r.t. cell and alpha are out of scope
-    (NotImplementedError at backward): use `compute_virial`.  Also out of scope: quadrupoles, `cell=None` clusters,
+    (NotImplementedError at backward): use `compute_virial`.  Also out of scope: quadrupoles (`ewald_quadrupole_correction` adds them), `cell=None` clusters,
     surface (non-tin-foil) terms.  CPU tensors raise NativeLibraryError: there is no fallback."""
 
 
