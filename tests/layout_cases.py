@@ -1,5 +1,5 @@
-"""The fixtures of the layout sweeps of `dftd4`, `dftd4_atm`, `gaussian_charge_correction`, `charge_equilibration` and the two point-dipole
-operators (tests/test_arg_layouts_gpu.py), in one place and free of any device, so that the CPU suite can check on exactly these inputs the condition
+"""The fixtures of the layout sweeps of `dftd4`, `dftd4_atm`, `gaussian_charge_correction`, `charge_equilibration`, the two point-dipole
+operators, `ewald_quadrupole_correction`, `thole_dipole_correction` and the induced-dipole solves (tests/test_arg_layouts_gpu.py), in one place and free of any device, so that the CPU suite can check on exactly these inputs the condition
 that makes such a sweep worth running (tests/test_layout_sensitivity_cpu.py): a tensor argument that the entry point misreads by one row
 must move the result far beyond the bar the sweep applies.  Every reference is computed once and never modified.
 
@@ -9,6 +9,10 @@ must move the result far beyond the bar the sweep applies.  Every reference is c
     gaussian(dtype, batch)      130 atoms in the 12 Bohr box / 70 + 60 in boxes 12 and 11, widths in [0.3, 0.8], two point atoms per system
     qeq_cluster(), qeq_periodic()   two clusters (no cell) / two periodic systems with their own k-vectors and alpha
     dipole(batch)               the Gaussian fixture's boxes with point dipoles, per-system alpha, a k set and a mesh: both dipole operators
+    quadrupole(batch)           `dipole(batch)` plus quadrupoles (two zero rows and four unsymmetric rows per system)
+    thole(batch)                `dipole(batch)` plus polarisabilities in [2, 8] (two non-polarisable atoms per system), width 0.39
+    induced(batch)              an `induced_cases` lattice (l64 / l27 + l64) in float32 numbers with its full list, k set, an external field and
+                                a warm start; polarisabilities for the undamped and for the damped solve
 
 Why the D4 fixture is not the 12 Bohr box of the other sweeps: there the coordination numbers reach 18 while the `cn_ref` of
 `d4_test_tables` lie in [0, 1]; every Gaussian weight saturates on the reference nearest to 1, and rolling `ngw` by one row moves the
@@ -25,9 +29,13 @@ from tests import d4_cases as K
 from tests import d4_reference as R
 from tests import dipole_reference as DR
 from tests import gaussian_reference as GR
+from tests import induced_cases as IC
+from tests import induced_reference as IR
 from tests import pme_dipole_reference as PR
 from tests import qeq_reference as QR
+from tests import quadrupole_reference as XR
 from tests import systems as S
+from tests import thole_reference as TR
 
 N, NA, NB = 130, 70, 60
 F64 = torch.float64
@@ -273,3 +281,138 @@ def dipole_reference(batch=False, op="ewald", dtype=F64, **replace):
         return PR.evaluate(t(c["pos"]), t(c["q"]), t(c["mu"]), t(c["cell"]), t(c["alpha"]), DP_MESH, DP_ORDER, batch_idx=bi, dtype=dtype)
     ent = _entries(c["pos"], c["cell"], c["batch_idx"], GC_RC)
     return DR.evaluate(t(c["pos"]), t(c["q"]), t(c["mu"]), t(c["cell"]), t(c["alpha"]), ent, t(c["kv"]), batch_idx=bi, distance_dtype=dtype)
+
+
+# ---- ewald_quadrupole_correction and thole_dipole_correction -----------------------------------------------------------------------------
+
+QD_NAMES = ("energies", "forces", "charge_grads", "dipole_grads", "quadrupole_grads", "virial")
+TH_NAMES = ("energies", "forces", "charge_grads", "dipole_grads", "polar_grads", "virial")
+THOLE = 0.39
+
+
+def _per_system_rows(g, sizes, count):
+    """`count` distinct rows of every system, as indices into the joined arrays."""
+    off, rows = 0, []
+    for n in sizes:
+        rows.append(off + g.choice(n, count, replace=False))
+        off += n
+    return rows
+
+
+@functools.lru_cache(maxsize=None)
+def quadrupole(batch=False):
+    """`dipole(batch)` plus quadrupoles 0.3 x normal, symmetrised; per system two zero rows and four rows with an added antisymmetric part
+    (1/2 (Q + Q^T) is what counts: a sweep that reads Q transposed must still agree).  Float32 numbers."""
+    c = dict(dipole(batch))
+    g = np.random.default_rng(37 + batch)
+    qd = 0.3 * g.normal(size=(len(c["pos"]), 3, 3))
+    qd = 0.5 * (qd + qd.transpose(0, 2, 1))
+    for rows in _per_system_rows(g, (NA, NB) if batch else (N,), 6):
+        qd[rows[:2]] = 0.0
+        skew = 0.1 * g.normal(size=(4, 3, 3))
+        qd[rows[2:]] += skew - skew.transpose(0, 2, 1)
+    c["qd"] = qd.astype(np.float32)
+    return c
+
+
+def quadrupole_reference(batch=False, part="total", dtype=F64, **replace):
+    """The restatement of `ewald_quadrupole_correction` ("total"), its real-space half ("real") or its reciprocal half ("recip") on the
+    fixture: the full list of cutoff `GC_RC` (brute-force entries) and the fixture's k set; `dtype` float32 is the float32-distance mode."""
+    c = {**quadrupole(batch), **replace}
+    t = lambda a: torch.as_tensor(np.asarray(a, np.float64))  # noqa: E731
+    bi = None if c["batch_idx"] is None else torch.as_tensor(c["batch_idx"])
+    ent = _entries(c["pos"], c["cell"], c["batch_idx"], GC_RC) if part != "recip" else None
+    return XR.evaluate(t(c["pos"]), t(c["q"]), t(c["mu"]), t(c["qd"]), t(c["cell"]), t(c["alpha"]), ent, t(c["kv"]) if part != "real" else None,
+                       batch_idx=bi, distance_dtype=dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def thole(batch=False):
+    """`dipole(batch)` plus polarisabilities uniform in [2, 8] with two non-polarisable atoms (0) per system; width `THOLE`.  At these values
+    E = a_T r^3 / sqrt(a_i a_j) is 0.5 - 2 on the nearest neighbours (distance 2.1) and passes 50 inside the list cutoff for the smallest
+    polarisabilities, so both sides of the kernel's early exit are present."""
+    c = dict(dipole(batch))
+    g = np.random.default_rng(37 + batch)
+    polar = g.uniform(2.0, 8.0, len(c["pos"]))
+    for rows in _per_system_rows(g, (NA, NB) if batch else (N,), 2):
+        polar[rows] = 0.0
+    c["polar"] = polar.astype(np.float32)
+    return c
+
+
+def thole_reference(batch=False, dtype=F64, **replace):
+    """The restatement of `thole_dipole_correction` on the fixture (brute-force entries of cutoff `GC_RC`)."""
+    c = {**thole(batch), **replace}
+    t = lambda a: torch.as_tensor(np.asarray(a, np.float64))  # noqa: E731
+    bi = None if c["batch_idx"] is None else torch.as_tensor(c["batch_idx"])
+    ent = _entries(c["pos"], c["cell"], c["batch_idx"], GC_RC)
+    return TR.evaluate(t(c["pos"]), t(c["q"]), t(c["mu"]), t(c["polar"]), t(c["cell"]), THOLE, ent, batch_idx=bi, distance_dtype=dtype)
+
+
+# ---- induced_dipoles and thole_induced_dipoles -------------------------------------------------------------------------------------------
+
+IND_TOL = 1e-10
+
+
+@functools.lru_cache(maxsize=None)
+def induced(batch=False):
+    """The lattices of tests/induced_cases.py rounded to float32: l64 as one system / l27 + l64 as a batch with their own cells and alpha
+    (l64: 0.45, l27: 0.625), the full list of every image within the cases' cutoff 11, the package's k set of the cases' k_cutoff per
+    system (rounded to float32 after it was generated), an external field and a warm start drawn once.  At 0.625 the k sum of cutoff 3.2 is
+    truncated at exp(-k^2 / 4 alpha^2) = 1.4e-3, on purpose: device and dense restatement sum the same terms, and with two converged
+    parameter sets (0.45 and 0.4375) the operator would not depend on which alpha a system is given -- rolled `alpha` then moved the dense
+    solution by 1.25 x (2 x bound) only, where tests/test_layout_sensitivity_cpu.py demands 100.  `polar` are the cases'
+    polarisabilities (the undamped solve); `polar_thole` are those of the damped solve, drawn as the Thole fixture's: uniform in [2, 8] --
+    of the order of d_min^3 = 8, where the undamped operator is indefinite -- with two non-polarisable atoms (0) per system."""
+    from nvalchemiops.interactions.electrostatics import generate_k_vectors_ewald_summation
+
+    names = ("l27", "l64") if batch else ("l64",)
+    parts = [IC.lattice(k) for k in names]
+    pos = _f32(np.concatenate([p["pos"] for p in parts]))
+    cells = _f32(np.stack([p["cell"] for p in parts]))
+    sizes = [p["n"] for p in parts]
+    bi = None if not batch else np.repeat(np.arange(len(parts), dtype=np.int32), sizes)
+    off, ii, jj, ss = 0, [], [], []
+    for p, cell in zip(parts, cells):
+        i, j, sh = GR.brute_force_entries(pos[off:off + p["n"]], cell, IC.EWALD["cutoff"], 2)
+        ii.append(i + off); jj.append(j + off); ss.append(sh)  # noqa: E702
+        off += p["n"]
+    ent = (torch.cat(ii), torch.cat(jj), torch.cat(ss))
+    g = np.random.default_rng(37 + batch)
+    n = len(pos)
+    kv = generate_k_vectors_ewald_summation(torch.as_tensor(cells), IC.EWALD["k_cutoff"]).numpy().astype(np.float32).astype(np.float64)
+    polar = _f32(np.concatenate([p["polar"] for p in parts]))
+    field, start = _f32(0.1 * g.normal(size=(n, 3))), _f32(0.05 * g.normal(size=(n, 3)))
+    polar_thole = g.uniform(2.0, 8.0, n)
+    for rows in _per_system_rows(g, sizes, 2):
+        polar_thole[rows] = 0.0
+    return dict(n=n, nsys=len(parts), pos=pos, cell=cells, q=_f32(np.concatenate([p["q"] for p in parts])), polar=polar, polar_thole=_f32(polar_thole),
+                alpha=_f32([0.625, 0.45][-len(parts):]), kv=kv if batch else kv.reshape(-1, 3), batch_idx=bi, ent=ent, field=field, start=start,
+                width=int(torch.bincount(ent[0]).max()) + 3)
+
+
+def induced_dense(c, thole=None, device="cpu", **replace):
+    """dict(H, b, polar, bi) of the dense float64 restatement of an induced-dipole fixture on `device`: undamped with `polar`, damped
+    (`thole`) with `polar_thole`; arguments replaced by name (`polar` replaces whichever of the two is in use)."""
+    c = {**c, **replace}
+    t = lambda a: None if a is None else torch.as_tensor(np.asarray(a), device=device)  # noqa: E731
+    ent = tuple(e.to(device) for e in c["ent"])
+    polar = t(c["polar"] if thole is None or "polar" in replace else c["polar_thole"])
+    bi = t(c["batch_idx"])
+    if thole is None:
+        T, lin = IR.dipole_operator(t(c["pos"]), t(c["q"]), t(c["cell"]), t(c["alpha"]), ent, t(c["kv"]), batch_idx=bi)
+    else:
+        T, lin = TR.damped_operator(t(c["pos"]), t(c["q"]), polar, t(c["cell"]), t(c["alpha"]), thole, ent, t(c["kv"]), batch_idx=bi)
+    return dict(H=IR.system_matrix(T, polar), b=IR.right_hand_side(lin, polar, t(c["field"])), polar=polar, bi=bi)
+
+
+def induced_bound(d, nsys, tol=IND_TOL):
+    """Per system: the bound `_check_solution` of tests/test_induced_gpu.py derives from the dense operator for |mu - mu_ref|,
+    10 tol ||b|| / lambda_min + 1e-14."""
+    n = d["b"].shape[0] // 3
+    sys_of = (torch.zeros(n, dtype=torch.long, device=d["b"].device) if d["bi"] is None else d["bi"].long()).repeat_interleave(3)
+    out = []
+    for s in range(nsys):
+        m = torch.nonzero(sys_of == s).flatten()
+        out.append(10.0 * tol * float(d["b"][m].norm()) / float(torch.linalg.eigvalsh(d["H"][m][:, m]).min()) + 1e-14)
+    return out

@@ -1,6 +1,6 @@
 """Seeded sweep cases, boundary ladders and one-scalar variants of the five newer dispersion operators (`dftd3_atm`, `dftd3_zero`,
-`dftd3_zero_atm`, `dftd4`, `dftd4_atm`) and the inputs of the sweeps of `gaussian_charge_correction`, charge equilibration and the two
-point-dipole operators (last two sections),
+`dftd3_zero_atm`, `dftd4`, `dftd4_atm`) and the inputs of the sweeps of `gaussian_charge_correction`, charge equilibration, the two
+point-dipole operators, `ewald_quadrupole_correction`, `thole_dipole_correction` and `induced_dipoles` (last three sections),
 built on the float64 restatements tests/atm_reference.py, tests/d3_zero_reference.py,
 tests/d4_reference.py and tests/d4_atm_reference.py.  Importable without a GPU and without the native library (the two tile sizes are read
 lazily, by the ladder builders only).  The CPU suite asserts every condition a case must meet (tests/test_sweep_cases_cpu.py); the GPU
@@ -885,3 +885,183 @@ def hermitian_plane_virial(kind, key):
         if own.numel():
             out[s] = PR.half_spectrum_plane_virial(pos[own], q[own], mu[own], cell, alpha[s], c["mesh"], c["order"], c["mesh"][2] // 2)
     return out
+
+
+# ---- point quadrupoles and Thole damping: ewald_quadrupole_correction and thole_dipole_correction ------------------------------------------------
+# Inputs only; both restatements (tests/quadrupole_reference.py, tests/thole_reference.py) are evaluated by the GPU module on the entries
+# actually stored.  A seed is the dipole recipe above under the operator's own BASE (geometry with spaced positions, charges, weights, the
+# emptied row, the interleaving permutation, the system without atoms, alpha) with dipoles on EVERY seed -- the dipole section's zero-dipole
+# seeds get dipoles here: without them the Thole correction and the dipole-quadrupole term vanish -- plus quadrupoles 0.3 x normal,
+# symmetrised, a few zero rows and a few rows with an antisymmetric part, or polarisabilities uniform in [0.5, 4] with a few non-polarisable
+# atoms (0).  With contacts from 1 to the cutoff of 6 - 7, E = a_T r^3 / sqrt(a_i a_j) runs from 0.1 to beyond the kernel's exit at 50.
+# `ZERO_MULTIPOLE_SEEDS`: all quadrupoles zero (every output but quadrupole_grads exactly 0) / every atom non-polarisable (every output
+# exactly 0).  `SINGLE_FLAG_SEEDS`: seed k of them asks for flag k alone; the other seeds draw a subset.
+
+MULTIPOLE_OPS = ("ewald_quadrupole", "thole")
+BASE.update(ewald_quadrupole=8600, thole=8700)
+QUADRUPOLE_FLAGS = ("compute_forces", "compute_charge_gradients", "compute_dipole_gradients", "compute_quadrupole_gradients", "compute_virial")
+QUADRUPOLE_NAMES = ("energies", "forces", "charge_grads", "dipole_grads", "quadrupole_grads", "virial")
+THOLE_FLAGS = ("compute_forces", "compute_charge_gradients", "compute_dipole_gradients", "compute_polarizability_gradients", "compute_virial")
+THOLE_NAMES = ("energies", "forces", "charge_grads", "dipole_grads", "polar_grads", "virial")
+MULTIPOLE_FLAGS = {"ewald_quadrupole": QUADRUPOLE_FLAGS, "thole": THOLE_FLAGS}
+MULTIPOLE_NAMES = {"ewald_quadrupole": QUADRUPOLE_NAMES, "thole": THOLE_NAMES}
+ZERO_MULTIPOLE_SEEDS = ZERO_DIPOLE_SEEDS
+SINGLE_FLAG_SEEDS = (0, 2, 3, 7, 9)  # the seeds with no other designation
+THOLE = 0.39
+THOLE_EXIT = 50.0            # `thole_dipole_correction` skips entries with E >= 50
+THOLE_ROWS = (0, 1, 63, 64, 65, 128, 129)
+
+
+def _quadrupoles(g, n, zero=False):
+    qd = 0.3 * g.normal(size=(n, 3, 3))
+    qd = 0.5 * (qd + qd.transpose(0, 2, 1))
+    pick = g.permutation(n)
+    few = min(3, max(1, n // 20))
+    qd[pick[:few]] = 0.0  # a few atoms without a quadrupole
+    if n > 2 * few:
+        skew = 0.1 * g.normal(size=(few, 3, 3))
+        qd[pick[few:2 * few]] += skew - skew.transpose(0, 2, 1)  # 1/2 (Q + Q^T) is what counts
+    return np.zeros((n, 3, 3)) if zero else qd
+
+
+def _polarisabilities(g, n, zero=False, lo=0.5, hi=4.0):
+    a = g.uniform(lo, hi, n)
+    if n > 3:
+        a[g.choice(n, min(3, max(1, n // 20)), replace=False)] = 0.0  # a few non-polarisable atoms
+    return np.zeros(n) if zero else a
+
+
+@functools.lru_cache(maxsize=None)
+def _multipole_sweep(op, seed):
+    c = dict(_dipole_sweep(op, seed))
+    g = np.random.default_rng(BASE[op] + 500 + seed)
+    n = len(c["pos"])
+    if c["zero_dipoles"]:
+        c.update(mu=_dipoles(g, n), zero_dipoles=False)
+    names = MULTIPOLE_FLAGS[op]
+    if seed in SINGLE_FLAG_SEEDS:
+        c["flags"] = {k: k == names[SINGLE_FLAG_SEEDS.index(seed)] for k in names}
+    else:
+        c["flags"] = {k: bool(g.integers(2)) for k in names}
+    c["zero"] = seed in ZERO_MULTIPOLE_SEEDS
+    if op == "ewald_quadrupole":
+        c["qd"] = _quadrupoles(g, n, c["zero"])
+    else:
+        c["polar"] = _polarisabilities(g, n, c["zero"])
+    return c
+
+
+def multipole_interleaved(c):
+    """`interleaved(c)` with the quadrupoles / polarisabilities in the new atom order too."""
+    out = interleaved(c)
+    for k in ("qd", "polar"):
+        if k in c:
+            out[k] = c[k][c["perm"]]
+    return out
+
+
+def thole_exponents(c, entries=None):
+    """E = a_T r^3 / sqrt(a_i a_j) of the entries whose two atoms are polarisable, and the rows they belong to."""
+    i, j, _ = c["entries"] if entries is None else entries
+    r = entry_distances(c if entries is None else dict(c, entries=entries))
+    ok = (c["polar"][i] > 0) & (c["polar"][j] > 0)
+    return THOLE * r[ok] ** 3 / np.sqrt(c["polar"][i][ok] * c["polar"][j][ok]), i[ok]
+
+
+@functools.lru_cache(maxsize=None)
+def quadrupole_atom_case():
+    """`dipole_atom_case()` (systems of 255, 256, 257 and 1 atoms in one batch, about 65 k-vectors per system) with quadrupoles: the 256-atom
+    trips of `qd_sf_kernel` and its `sptr`; reciprocal half only."""
+    c = dict(dipole_atom_case(), op="ewald_quadrupole")
+    c["qd"] = _quadrupoles(np.random.default_rng(8610), len(c["pos"]))
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def quadrupole_no_shift_case():
+    """The 65-atom row rung of the dipole section (a cluster inside a cubic cell four diameters wide, every pair stored with a zero shift:
+    rows of 64 entries) with quadrupoles: the list is passed with zero shifts and without shifts (`ush == nullptr` in `qd_pair_kernel`)."""
+    c = dict(_dipole_row_ladder("n65"), op="ewald_quadrupole")
+    c["qd"] = _quadrupoles(np.random.default_rng(8620), len(c["pos"]))
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def quadrupole_shared_k_case():
+    """Two systems of 60 and 9 atoms in the SAME triclinic cell of edge 9 with one alpha: one k set [1, K, 3] serves both."""
+    g = np.random.default_rng(8630)
+    cell = charge_cell(9.0)
+    sizes = (60, 9)
+    n = sum(sizes)
+    pos = np.concatenate([spaced_positions(g, m, cell) for m in sizes])
+    return dict(op="ewald_quadrupole", dtype="float64", sizes=sizes, pos=pos, cells=np.stack([cell, cell]), batch_idx=np.repeat(np.arange(2, dtype=np.int32), sizes),
+                q=g.normal(size=n) + 0.05, mu=_dipoles(g, n), qd=_quadrupoles(g, n), zero_dipoles=False, alpha=np.array([0.4, 0.4]),
+                weights=g.uniform(0.2, 1.8, n), perm=None, empty_system=None, k_cutoff=K_CUTOFF)
+
+
+@functools.lru_cache(maxsize=None)
+def thole_row_ladder(periodic=True):
+    """Rows of exactly 0, 1, 63, 64, 65, 128 and 129 entries in a FULL list built by hand, as `_ladder` of tests/test_quadrupole_gpu.py
+    builds it: ladder atom t is paired with that many distinct (filler atom, shift) combinations and the filler rows hold the reversed
+    entries (j, i, -S).  periodic: 40 fillers in a triclinic box of edge 6, shifts in [-1, 1]^3 (entry distances 1 - 15).  Not periodic: a
+    cluster of 130 fillers without a cell (`cell=None`), every shift zero.  The row of one entry holds the ladder atom's NEAREST partner,
+    so that it lies inside the exit; polarisabilities uniform in [0.5, 2] put E = 50 at r = 4 - 6.3, inside the span of every longer row."""
+    n_fill = 40 if periodic else 130
+    n = len(THOLE_ROWS) + n_fill
+    g = np.random.default_rng(8700 + n_fill)
+    if periodic:
+        cell = charge_cell(6.0)
+        pos = spaced_positions(g, n, cell)
+        shifts = np.array([(a, b, c) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1)])
+    else:
+        cell, pos, shifts = None, S.molecule(n, density=0.05, min_dist=MIN_CONTACT, seed=700, dtype=np.float64)[0], np.zeros((1, 3), np.int64)
+    combos = [(f, s) for f in range(len(THOLE_ROWS), n) for s in range(len(shifts))]
+    ei, ej, eS = [], [], []
+    for t, length in enumerate(THOLE_ROWS):
+        if length == 1:
+            d = [np.linalg.norm(pos[f] - pos[t] + (shifts[s] @ cell if periodic else 0.0)) for f, s in combos]
+            chosen = [int(np.argmin(d))]
+        else:
+            chosen = g.choice(len(combos), length, replace=False)
+        for k in chosen:
+            f, s = combos[k]
+            ei += [t, f]; ej += [f, t]; eS += [shifts[s], -shifts[s]]  # noqa: E702
+    ei, ej, eS = np.array(ei), np.array(ej), np.array(eS).reshape(-1, 3)
+    order = np.argsort(ei, kind="stable")
+    polar = g.uniform(0.5, 2.0, n)
+    polar[g.choice(np.arange(len(THOLE_ROWS), n), 2, replace=False)] = 0.0  # two non-polarisable fillers
+    c = dict(op="thole", dtype="float64", sizes=(n,), pos=pos, cells=None if cell is None else cell[None], batch_idx=np.zeros(n, np.int32), q=g.normal(size=n) + 0.05,
+             mu=_dipoles(g, n), polar=polar, zero_dipoles=False, weights=g.uniform(0.2, 1.8, n), perm=None, empty_system=None, pad=0, emptied_row=None,
+             entries=(ei[order], ej[order], eS[order]))
+    c["widest"] = int(np.bincount(c["entries"][0], minlength=n).max())
+    c["min_dist"] = float(entry_distances(c).min())
+    return c
+
+
+def multipole_case(kind, key=None):
+    """kind: "sweep" (key: (op, seed)), "atoms", "no_shifts", "shared_k", "thole_rows" (key: periodic)."""
+    if kind == "sweep":
+        return _multipole_sweep(*key)
+    return {"atoms": lambda _: quadrupole_atom_case(), "no_shifts": lambda _: quadrupole_no_shift_case(), "shared_k": lambda _: quadrupole_shared_k_case(),
+            "thole_rows": lambda k: thole_row_ladder(bool(k))}[kind](key)
+
+
+@functools.lru_cache(maxsize=None)
+def induced_idle_systems_case():
+    """A batch of three cells for `induced_dipoles`: system 0 is the 27-atom lattice of tests/induced_cases.py (it iterates), system 1 has NO
+    atoms, system 2 has nine charged atoms of which NONE is polarisable (a = 0): its right-hand side is zero on every atom."""
+    from tests import induced_cases as IC
+
+    a = IC.lattice("l27")
+    g = np.random.default_rng(8800)
+    cell2 = charge_cell(7.0)
+    pos2 = spaced_positions(g, 9, cell2)
+    i0, j0, S0 = (e.numpy() for e in IC.entries("l27"))
+    i2, j2, S2 = brute_force(pos2, cell2, 6.0, 2)
+    n = 36
+    c = dict(sizes=(27, 0, 9), pos=np.concatenate([a["pos"], pos2]), cells=np.stack([a["cell"], charge_cell(8.0, False), cell2]),
+             batch_idx=np.repeat(np.array([0, 2], np.int32), (27, 9)), q=np.concatenate([a["q"], g.normal(size=9)]),
+             polar=np.concatenate([a["polar"], np.zeros(9)]), alpha=np.array([IC.EWALD["alpha"], 0.4, 0.5]), k_cutoff=IC.EWALD["k_cutoff"],
+             entries=(np.concatenate([i0, i2 + 27]), np.concatenate([j0, j2 + 27]), np.concatenate([S0, S2])), pad=3, emptied_row=None)
+    c["widest"] = int(np.bincount(c["entries"][0], minlength=n).max())
+    return c

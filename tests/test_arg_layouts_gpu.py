@@ -23,6 +23,10 @@ Which variant goes to which argument (no tensor argument of a listed entry point
                                                       x   x   x   x   -   -   -   (math points, current_positions: x)
     dipoles [N,3], k_vectors [K,3] / [B,K,3] of the
       point-dipole operators                          x   x   x   x   -   -   -   x
+    quadrupoles [N,3,3]                               x   x   x   x   x   -   -   x      (T: the atom axis stored last; F: the two tensor
+                                                                                          axes swapped in storage)
+    k_vectors [B,K,3] of a batch in ONE cell          also as [1,K,3], as an offset view of that, and as x0
+    external_field, initial_dipoles [N,3]             x   x   x   x   -   -   -   x
     cell [3,3] / [B,3,3]                              x   -   x*  -   x   x*  -   x      (* batch forms)
     pbc [3] / [B,3] (bool)                            x   -   x*  -   -   x*  -   -
     charges, values, raw energies, alpha [B]          x   x   x   -   -   x*  -   x      (values [N,C] also T)
@@ -35,8 +39,8 @@ Which variant goes to which argument (no tensor argument of a listed entry point
     D4 tables rcov, en, r4r2, zeff, gam, cn_ref,
       q_ref, c6_ref                                   x   x   x   T(cn_ref, q_ref, c6_ref) -   -   -   x
     D4 tables n_ref, ngw                              x   x   x   T(ngw)  -   -   x   -
-    sigma, electronegativity, hardness,
-      initial_charges, total_charge [B]               x   x   x   -   -   -   -   x
+    sigma, electronegativity, hardness, polarizability,
+      initial_charges, total_charge [B]               x   x   x   -   -   -   -   x      (polarizability also as a Python number)
     meshes, k_squared                                 x   x   x   x   -   -   -   x*     (* not k_squared)
 
 `flt` goes to every float argument but the one whose dtype IS the dtype of the call and of its outputs: positions, and where there are
@@ -61,7 +65,19 @@ Point-dipole operators, in float32 and in float64 alike (variants run; single sy
 pme_dipole_reciprocal_space 20 / 27, ewald_dipole_real_space 30 (matrix) + 34 (CSR) / 37 + 39, ewald_dipole_correction 35 + 39 / 42 + 44,
 pme_dipole_correction 30 + 34 / 37 + 39: 1 088 variants.  The explicit sums gave the bits of the canonical call in every variant.  The mesh
 term stayed within 0.0015 of its 1e-12 bar in float64 (float64 atomic adds in the spread) and gave the bits of the canonical call in
-float32, where the spread adds in float64 and rounds once; so did `pme_dipole_correction` (0.0004 in float64).  DESIGN.md section 3.21."""
+float32, where the spread adds in float64 and rounds once; so did `pme_dipole_correction` (0.0004 in float64).  DESIGN.md section 3.21.
+
+Point quadrupoles, Thole damping and induced dipoles (fixtures `quadrupole`, `thole`, `induced` of tests/layout_cases.py; variants run,
+single system / batch).  In float32 and in float64 alike: ewald_quadrupole_reciprocal_space 31 / 38 (+ 2 stride-0 and 2 [1, K, 3] forms on
+the batch in one cell), ewald_quadrupole_real_space 36 (matrix) + 40 (CSR) / 43 + 45, ewald_quadrupole_correction 41 + 45 / 48 + 50,
+thole_dipole_correction 30 + 34 / 36 + 39 (+ a Python number against a constant tensor in each): 1 120 variants.  In float64:
+induced_dipoles and thole_induced_dipoles, each 44 + 48 / 49 + 53 with reciprocal="ewald" and 39 / 44 with reciprocal="pme": 554
+variants.  Every variant of the explicit sums and of the "ewald" solves gave the BITS of the canonical call (dipoles and iteration
+counts), and so did the "pme" solves, whose bar is twice `_check_solution`'s bound.  Gradient layouts: 10 ops in float32 and 14 in float64
+(the four solves are float64 only), four grad-output layouts each, every gradient bit-identical to the contiguous backward.  With the
+`.contiguous()` of `quadrupoles` taken out of the real-space launch (a patched `launch_inputs`, not committed) the col, row and T variants
+of `ewald_quadrupole_real_space` and `ewald_quadrupole_correction` fail in every sweep; F does not and cannot: it hands the kernel Q
+transposed, and 1/2 (Q + Q^T) is what the kernel uses.  DESIGN.md section 3.25."""
 import functools
 import re
 import types
@@ -82,10 +98,13 @@ from tests import test_d4_atm_gpu as TD4A
 from tests import test_d4_gpu as TD4
 from tests import test_dipole_gpu as TDP
 from tests import test_gaussian_charges_gpu as TG
+from tests import test_induced_gpu as TI
 from tests import test_math_gpu as TM
 from tests import test_pme_dipole_gpu as TPD
 from tests import test_pme_gpu as TP
 from tests import test_qeq_gpu as TQ
+from tests import test_quadrupole_gpu as TQD
+from tests import test_thole_gpu as TTH
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -1137,6 +1156,170 @@ def test_point_dipole_operators(dtype, batch):
         _swept(f"pme_dipole_correction {tag} {label}", call, dict(atoms, **lists), dict(aplan, **lplan), two_runs, ref=ref, shared=sh)
 
 
+# ---- point quadrupoles, Thole damping, induced dipoles -------------------------------------------------------------------------------------
+
+QUAD = "off col row T F flt"  # quadrupoles [N, 3, 3]: col = a view of a wider last dimension, T = the atom axis stored last, F = the two tensor axes swapped in storage
+
+
+@functools.lru_cache(maxsize=None)
+def _mfx(dtype_name, batch):
+    """The dipole fixture on the device (`_dfx`: positions, charges, dipoles, cells, alpha, k set, both list layouts) with the quadrupoles and
+    polarisabilities of tests/layout_cases.py, and the restatements of the quadrupole term (real-space half, reciprocal half, their sum) and
+    of the Thole correction on the stored entries, computed once."""
+    d, dt = _dfx(dtype_name, batch), np.dtype(dtype_name).type
+    f = types.SimpleNamespace(**vars(d))
+    f.QD, f.POL = _t(LC.quadrupole(batch)["qd"].astype(dt)), _t(LC.thole(batch)["polar"].astype(dt))
+    ent = TDP.R.entries_from_matrix(f.nm, f.sh, f.n)
+    ev = lambda entries, kv: TQD.R.evaluate(f.P, f.Q, f.MU, f.QD, f.C, f.AL, entries, kv, batch_idx=f.BI, distance_dtype=f.tdtype)  # noqa: E731
+    f.qref = dict(real=ev(ent, None), recip=ev(None, f.KV))
+    f.qref["total"] = TQD._sum(f.qref["real"], f.qref["recip"])
+    f.tref = TTH.TR.evaluate(f.P, f.Q, f.MU, f.POL, f.C, LC.THOLE, ent, batch_idx=f.BI, distance_dtype=f.tdtype)
+    return f
+
+
+def _list_forms(f):
+    return (("matrix", dict(neighbor_matrix=f.nm, neighbor_matrix_shifts=f.sh, mask_value=f.n), dict(neighbor_matrix=MAT, neighbor_matrix_shifts=MAT)),
+            ("csr", dict(neighbor_list=f.lst, neighbor_ptr=f.ptr, neighbor_shifts=f.lsh), dict(neighbor_list=MAT, neighbor_ptr=IDX, neighbor_shifts=MAT)))
+
+
+@DTYPES
+@pytest.mark.parametrize("batch", [False, True])
+@_collecting
+def test_point_quadrupole_operators(dtype, batch):
+    """`ewald_quadrupole_reciprocal_space`, `ewald_quadrupole_real_space` and `ewald_quadrupole_correction`, all six outputs: the canonical
+    call against the restatement at the bars of tests/test_quadrupole_gpu.py, every variant against the BITS of the canonical call (nothing in
+    csrc/quadrupole.hip adds with atomics; the `flt` variants too, every fixture value being a float32 number).  On the batch the reciprocal
+    half is run once more with both systems in the cell of the first: `k_vectors` as [1, K, 3] and as a stride-0 expansion must give the
+    bits of the contiguous [B, K, 3] set."""
+    from nvalchemiops.interactions.electrostatics import ewald_quadrupole_correction, ewald_quadrupole_real_space, ewald_quadrupole_reciprocal_space
+
+    f = _mfx(dtype, batch)
+    tag = f"{dtype}{' batch' if batch else ''}"
+    atoms = dict(positions=f.P, charges=f.Q, dipoles=f.MU, quadrupoles=f.QD, cell=f.C, alpha=f.AL)
+    aplan = dict(positions=POS, charges=VEC, dipoles=DIP, quadrupoles=QUAD, cell=CELLB if batch else CELL1, alpha=VEC)
+    if batch:
+        atoms["batch_idx"], aplan["batch_idx"] = f.BI, IDX
+    shared = ("cell", "alpha") if batch else ()
+
+    def against_restatement(out, ref, what):
+        assert len(out) == 6
+        for name, o in zip(TQD.NAMES, out):
+            assert o.dtype == f.tdtype
+            TQD._close(o, ref[name], f"{what} {name} vs the restatement", f.rel)
+
+    call = lambda **a: ewald_quadrupole_reciprocal_space(**a, **TQD.ALL)  # noqa: E731
+    kw = dict(atoms, k_vectors=f.KV)
+    ref = _tuple(call(**kw))
+    against_restatement(ref, f.qref["recip"], f"ewald_quadrupole_reciprocal_space {tag}")
+    _swept(f"ewald_quadrupole_reciprocal_space {tag}", call, kw, dict(aplan, k_vectors=DIP), _exact, ref=ref, shared=shared)
+    if batch:  # one cell and one k set for both systems
+        same = dict(kw, cell=f.C[:1].repeat(2, 1, 1).contiguous(), k_vectors=f.KV[:1].repeat(2, 1, 1).contiguous())
+        ref = _swept(f"ewald_quadrupole_reciprocal_space {tag} x0", call, same, {}, _exact, shared=("cell", "k_vectors"))
+        assert not torch.equal(ref[0], _tuple(call(**kw))[0])
+        _compare(_tuple(call(**dict(same, k_vectors=f.KV[:1]))), ref, _exact, "ewald_quadrupole_reciprocal_space[k_vectors:[1, K, 3]]")
+        _compare(_tuple(call(**dict(same, k_vectors=_variant(f.KV[:1], "off")))), ref, _exact, "ewald_quadrupole_reciprocal_space[k_vectors:[1, K, 3] off]")
+    for label, lists, lplan in _list_forms(f):
+        sh = shared if label == "matrix" else ()
+        call = lambda **a: ewald_quadrupole_real_space(**a, **TQD.ALL)  # noqa: E731
+        ref = _tuple(call(**atoms, **lists))
+        against_restatement(ref, f.qref["real"], f"ewald_quadrupole_real_space {tag} {label}")
+        _swept(f"ewald_quadrupole_real_space {tag} {label}", call, dict(atoms, **lists), dict(aplan, **lplan), _exact, ref=ref, shared=sh)
+        call = lambda **a: ewald_quadrupole_correction(**a, **TQD.ALL)  # noqa: E731
+        kw = dict(atoms, k_vectors=f.KV, **lists)
+        ref = _tuple(call(**kw))
+        against_restatement(ref, f.qref["total"], f"ewald_quadrupole_correction {tag} {label}")
+        _swept(f"ewald_quadrupole_correction {tag} {label}", call, kw, dict(aplan, k_vectors=DIP, **lplan), _exact, ref=ref, shared=sh)
+
+
+@DTYPES
+@pytest.mark.parametrize("batch", [False, True])
+@_collecting
+def test_thole_dipole_correction(dtype, batch):
+    """All six outputs; `polarizability` gets the plan of `sigma`.  One kernel, no atomics: every variant gives the bits of the canonical call,
+    and a Python number gives the bits of a constant tensor."""
+    from nvalchemiops.interactions.electrostatics import thole_dipole_correction as th
+
+    f = _mfx(dtype, batch)
+    tag = f"thole_dipole_correction {dtype}{' batch' if batch else ''}"
+    call = lambda **a: th(**a, thole=LC.THOLE, **TTH.ALL)  # noqa: E731
+    atoms = dict(positions=f.P, charges=f.Q, dipoles=f.MU, polarizability=f.POL, cell=f.C)
+    aplan = dict(positions=POS, charges=VEC, dipoles=DIP, polarizability=VEC, cell=CELLB if batch else CELL1)
+    if batch:
+        atoms["batch_idx"], aplan["batch_idx"] = f.BI, IDX
+    for label, lists, lplan in _list_forms(f):
+        ref = _tuple(call(**atoms, **lists))
+        assert len(ref) == 6
+        for name, o in zip(TTH.NAMES, ref):
+            assert o.dtype == f.tdtype
+            TTH._close(o, f.tref[name], f"{tag} {label} {name} vs the restatement", f.rel)
+        _swept(f"{tag} {label}", call, dict(atoms, **lists), dict(aplan, **lplan), _exact, ref=ref, shared=("cell",) if batch and label == "matrix" else ())
+        number = _tuple(call(**dict(atoms, polarizability=2.5), **lists))
+        _compare(_tuple(call(**dict(atoms, polarizability=torch.full_like(f.POL, 2.5)), **lists)), number, _exact, f"{tag} {label}[polarizability: number]")
+        assert not torch.equal(number[0], ref[0])
+
+
+@functools.lru_cache(maxsize=None)
+def _ifx(batch):
+    """An induced-dipole fixture of tests/layout_cases.py on the device (float64 arrays of float32 numbers) with both list layouts and the
+    dense restatements, undamped and damped, computed once."""
+    c = LC.induced(batch)
+    f = types.SimpleNamespace(batch=batch, n=c["n"], nsys=c["nsys"], c=c)
+    f.P, f.Q, f.C, f.AL, f.KV, f.F, f.X0 = (_t(c[k]) for k in ("pos", "q", "cell", "alpha", "kv", "field", "start"))
+    f.BI = None if not batch else _t(c["batch_idx"])
+    f.nm, f.sh = TQ._lists(*c["ent"], c["n"], c["width"], c["n"])
+    f.lst, f.ptr, f.lsh = TQ._csr(f.nm, f.sh, c["n"])
+    f.dense = {th: LC.induced_dense(c, th, DEV) for th in (None, LC.THOLE)}
+    return f
+
+
+def _within_twice_the_bound(bound_per_row):
+    def close(o, r, what, i):
+        err = np.abs(o.detach().cpu().numpy() - r)
+        _WORST[0] = max(_WORST[0], float((err / bound_per_row).max()))
+        assert (err <= bound_per_row).all(), f"{what}: max err {err.max():.3e}, worst err / (2 x bound) {(err / bound_per_row).max():.3g}"
+    return close
+
+
+@pytest.mark.parametrize("damped", [False, True], ids=["undamped", "thole"])
+@pytest.mark.parametrize("batch", [False, True])
+@_collecting
+def test_induced_dipoles_explicit_ewald_and_pme(batch, damped):
+    """`induced_dipoles` / `thole_induced_dipoles` with reciprocal="ewald", given k-vectors, one alpha per system, an external field and a warm
+    start: the canonical call against the dense solve by `_check_solution`, and every variant against the BITS of the canonical dipoles and
+    iteration counts, as the docstring of `induced_dipoles` promises for this path.  Then one pass with reciprocal="pme" (matrix list), whose
+    mesh spread adds with atomics: each variant within TWICE `_check_solution`'s bound of the canonical pme call (each of the two converged
+    solves is within once of the exact solution of its operator)."""
+    from nvalchemiops.interactions.electrostatics import induced_dipoles, thole_induced_dipoles
+
+    f = _ifx(batch)
+    thole = LC.THOLE if damped else None
+    d = f.dense[thole]
+    extra = dict(thole=thole) if damped else {}
+    fn = thole_induced_dipoles if damped else induced_dipoles
+    tag = f"{'thole_' if damped else ''}induced_dipoles{' batch' if batch else ''}"
+
+    def call(positions, charges, polarizability, cell, **a):
+        out = fn(positions, charges, polarizability, cell, tolerance=LC.IND_TOL, return_info=True, **extra, **a)
+        return out.dipoles, out.iterations
+
+    atoms = dict(positions=f.P, charges=f.Q, polarizability=d["polar"], cell=f.C, alpha=f.AL, external_field=f.F, initial_dipoles=f.X0)
+    aplan = dict(positions=POS, charges=VEC, polarizability=VEC, cell=CELLB if batch else CELL1, alpha=VEC, external_field=DIP, initial_dipoles=DIP)
+    if batch:
+        atoms["batch_idx"], aplan["batch_idx"] = f.BI, IDX
+    for label, lists, lplan in _list_forms(f):
+        kw = dict(atoms, reciprocal="ewald", k_vectors=f.KV, **lists)
+        a = {k: v for k, v in kw.items() if k not in ("positions", "charges", "polarizability", "cell")}
+        out = fn(f.P, f.Q, d["polar"], f.C, tolerance=LC.IND_TOL, return_info=True, **extra, **a)
+        TI._check_solution(out, d["H"], d["b"], d["polar"], f.BI, f.nsys, LC.IND_TOL, f"layouts {tag} {label}", x0=f.X0)
+        assert int(out.iterations.min()) > 0
+        _swept(f"{tag} ewald {label}", call, kw, dict(aplan, k_vectors=DIP, **lplan), _exact, ref=(out.dipoles, out.iterations))
+    label, lists, lplan = _list_forms(f)[0]
+    bound = np.asarray(LC.induced_bound(d, f.nsys))
+    rows = 2.0 * bound[np.zeros(f.n, np.int64) if f.BI is None else f.c["batch_idx"]][:, None]
+    kw = dict(atoms, reciprocal="pme", mesh_dimensions=(32, 32, 32), spline_order=5, **lists)
+    _swept(f"{tag} pme {label}", lambda **a: call(**a)[:1], kw, dict(aplan, **lplan), _within_twice_the_bound(rows))
+
+
 # ==== splines =============================================================================================================================
 
 MESH = "off col row T flt"
@@ -1381,6 +1564,43 @@ def test_gradient_layouts_of_the_point_dipole_ops(dtype):
             lambda p, q, m, f=f, bkw=bkw: pme_dipole_reciprocal_space(p, q, m, f.C, f.AL, mesh_dimensions=LC.DP_MESH, spline_order=LC.DP_ORDER, **bkw),
             leaves, names, _close_two_runs(f.two_runs))
     _check_gradient_layouts(ops)
+
+
+@DTYPES
+def test_gradient_layouts_of_the_quadrupole_thole_and_induced_dipole_ops(dtype):
+    """The same for `ewald_quadrupole_correction` (matrix and CSR) and `ewald_quadrupole_reciprocal_space` with respect to positions, charges,
+    dipoles and quadrupoles, `thole_dipole_correction` with respect to positions, charges, dipoles and polarizability -- on the single system
+    and the batch -- and the dipoles of `induced_dipoles` / `thole_induced_dipoles` (reciprocal="ewald", float64 only) with respect to
+    positions, charges, polarizability and the external field.  The adjoints are the forward kernels with weights; the backward of the solve
+    is one more solve with the stored operator and two calls of the public energy functions: no atomics anywhere, equal bits."""
+    from nvalchemiops.interactions.electrostatics import (ewald_quadrupole_correction, ewald_quadrupole_reciprocal_space, induced_dipoles,
+                                                          thole_dipole_correction, thole_induced_dipoles)
+
+    ops = {}
+    for batch in (False, True):
+        f = _mfx(dtype, batch)
+        bkw = dict(batch_idx=f.BI) if batch else {}
+        tag = " batch" if batch else ""
+        leaves, names = (f.P, f.Q, f.MU, f.QD), ("positions", "charges", "dipoles", "quadrupoles")
+        for label, lists, _ in _list_forms(f):
+            ops[f"ewald_quadrupole_correction {label}{tag}"] = (
+                lambda p, q, m, t, f=f, bkw=bkw, lists=lists: ewald_quadrupole_correction(p, q, m, t, f.C, f.AL, f.KV, **lists, **bkw), leaves, names, _exact)
+            ops[f"thole_dipole_correction {label}{tag}"] = (
+                lambda p, q, m, a, f=f, bkw=bkw, lists=lists: thole_dipole_correction(p, q, m, a, f.C, thole=LC.THOLE, **lists, **bkw),
+                (f.P, f.Q, f.MU, f.POL), ("positions", "charges", "dipoles", "polarizability"), _exact)
+        ops[f"ewald_quadrupole_reciprocal_space{tag}"] = (
+            lambda p, q, m, t, f=f, bkw=bkw: ewald_quadrupole_reciprocal_space(p, q, m, t, f.C, f.KV, f.AL, **bkw), leaves, names, _exact)
+        if dtype == "float64":
+            g = _ifx(batch)
+            gkw = dict(batch_idx=g.BI) if batch else {}
+            common = dict(reciprocal="ewald", alpha=g.AL, k_vectors=g.KV, tolerance=1e-12, neighbor_matrix=g.nm, neighbor_matrix_shifts=g.sh, mask_value=g.n)
+            ops[f"induced_dipoles{tag}"] = (lambda p, q, a, e, g=g, gkw=gkw, common=common: induced_dipoles(p, q, a, g.C, external_field=e, **common, **gkw),
+                                           (g.P, g.Q, g.dense[None]["polar"], g.F), ("positions", "charges", "polarizability", "external_field"), _exact)
+            ops[f"thole_induced_dipoles{tag}"] = (
+                lambda p, q, a, e, g=g, gkw=gkw, common=common: thole_induced_dipoles(p, q, a, g.C, thole=LC.THOLE, external_field=e, **common, **gkw),
+                (g.P, g.Q, g.dense[LC.THOLE]["polar"], g.F), ("positions", "charges", "polarizability", "external_field"), _exact)
+    _check_gradient_layouts(ops)
+    print(f"[layouts] gradient layouts {dtype}: {len(ops)} ops x 4 grad-output layouts, every gradient bit-identical to the contiguous backward")
 
 
 # ==== caller-owned output buffers =========================================================================================================

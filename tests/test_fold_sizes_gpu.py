@@ -1,10 +1,12 @@
 """Sizes beyond one trip of the per-system folds of `dftd4`, `dftd4_atm`, `gaussian_charge_correction`, `charge_equilibration`,
-`ewald_dipole_real_space` and `ewald_real_space_with_virial`.
+`ewald_dipole_real_space`, `ewald_real_space_with_virial`, `ewald_quadrupole_real_space`, `thole_dipole_correction`, `induced_dipoles`
+and `thole_induced_dipoles`.
 
 Every per-system sum of these ops is the fixed-order fold of csrc/pair_row.h (`mi_system_fold`) on a grid of (blocks, systems) blocks of
 256 threads, each looping `r += blocks * 256` over ALL N rows and keeping those of its system: `d4_fold_kernel` (also `dftd4_atm`'s),
-`gc_fold_kernel`, `gc_system_sums_kernel`, `qeq_fold_kernel`, `dp_fold_kernel`, `ew_virial_fold_kernel`; `qeq_cg_update_kernel` and
-`qeq_cg_direction_kernel` walk the same grid.  The parity modules stop at a few hundred atoms; the second trip of these loops
+`gc_fold_kernel`, `gc_system_sums_kernel`, `qeq_fold_kernel`, `dp_fold_kernel` (also as `mi_thole_dipole` launches it),
+`ew_virial_fold_kernel`, `qd_fold_kernel`, `ind_dot_kernel`; `qeq_cg_update_kernel`, `qeq_cg_direction_kernel`, `ind_cg_update_kernel` and
+`ind_cg_direction_kernel` walk the same grid.  The parity modules stop at a few hundred atoms; the second trip of these loops
 (N > 256 * blocks = 16 384) and the batched form at that size are compared here.
 
 No large reference is needed.  These ops take the pairs from the list, so K copies of a small system with the small list repeated
@@ -30,6 +32,14 @@ a third of the rows) and K n0 no multiple of 64.
   charge_equilibration (cluster): the operator is block-diagonal with identical blocks, so the exact solution is the small dense KKT
       solution tiled:  max|q - q_ref| <= sqrt(K) (10 tol ||b_small|| / lambda_min + 1e-14) for the single system (||b|| grows as sqrt(K)),
       without the sqrt(K) per system of the batch -- `_check_solution`'s bound with the small block's spectrum; tol = 1e-10.
+  ewald_quadrupole_real_space and thole_dipole_correction: (a) and (b) on `test_quadrupole_gpu._single()` (300 atoms) and on the single
+      periodic case of tests/test_thole_gpu.py (27 atoms, rows of about 210 entries, its three non-polarisable atoms; the list padded
+      with the mask value alone), every flag, both formats, the small call judged against its restatement at the module's 1e-11.
+  induced_dipoles and thole_induced_dipoles: reciprocal="ewald" with an EMPTY k set -- `k_vectors` [0, 3] is accepted, as
+      `ewald_dipole_reciprocal_space` accepts it, and leaves the self term alone, so the copies do not couple -- on the 27-atom lattice
+      with a list cutoff of 6 (`thole_cases.fold_case()`; tests/test_induced_reference_cpu.py asserts that this truncated H is positive
+      definite).  The bound is the QEq one, with `_check_solution` of tests/test_induced_gpu.py for the small call.  `mi_induced_dot` and
+      the `partial` output of `mi_induced_apply` on K n0 random rows against float64 torch sums per system, at the fold bar.
 
 MEASURED on one MI355X (each test prints its figures under `pytest -s`; matrix and CSR agree to the digits shown).  Per-atom outputs:
 bit-identical wherever that is asserted.  Worst |X_big - K X_small| / bar as ONE system:
@@ -45,7 +55,19 @@ stride-0 cell; gaussian virial 3.6e-15 and 5.3e-15 absolute (1.1e-9 and 1.8e-9 o
   ewald real space   160 atoms (K 155, N 24 800): virial as one system 2.3e-13 (1.5e-9 of the bar), in the batch 8.9e-16 (8.8e-10 of the
              bar), both cell forms; energies and forces bit-identical, here and at the commit before the folds were shared
   charge_equilibration  60 atoms (K 410, N 24 600): max|q - q_ref| 2.9e-11 as one system (bar 1.3e-7) and in the worst system of the batch
-             (bar 6.2e-9); 19 iterations in the small call, the single system and all 410 systems of the batch."""
+             (bar 6.2e-9); 19 iterations in the small call, the single system and all 410 systems of the batch.
+  quadrupole real space  300 atoms (K 82, N 24 600): small call against the reference 1.4e-15 / 1.3e-15 / 3.7e-16 / 7.1e-16 / 6.6e-16 /
+             6.0e-14 (energies / forces / charge / dipole / quadrupole gradients / virial, bar 1e-11); virial as one system 2.3e-10
+             (3.7e-10 of the bar), in the batch 7.3e-12 (9.6e-10 of the bar) with K cells and with the stride-0 cell.  With
+             `qd_fold_kernel` cut to its first trip (a scratch build) the one-system virial is off by 2.1e6 bars, and
+             tests/test_quadrupole_gpu.py still passes.
+  thole      27 atoms (K 911, N 24 597): small call 1.1e-15 at worst (bar 1e-11); virial as one system 2.8e-14 (6.2e-10 of the bar), in
+             the batch 2.8e-17 (5.5e-10 of the bar), both cell forms
+  induced_dipoles  27 atoms (K 911, N 24 597), empty k set: max|mu - mu_ref| 3.0e-12 undamped and 1.0e-12 damped, as one system (bars
+             2.1e-8 and 1.9e-8) and in the worst system of the batch (bars 6.9e-10 and 6.2e-10), both cell forms; 10 iterations in the
+             small call, the single system and all 911 systems of the batch (reference PCG: 10)
+  mi_induced_dot / mi_induced_apply partial  24 597 random rows: 1.2e-9 / 0 of the bar as one system, 8.8e-10 / 1.2e-9 as 911 systems
+Matrix and CSR agree to the digits shown; per-atom outputs bit-identical wherever that is asserted."""
 import math
 
 import numpy as np
@@ -60,7 +82,11 @@ from tests import test_d4_gpu as TD4
 from tests import test_dipole_gpu as TDP
 from tests import test_electrostatic_virial_gpu as TV
 from tests import test_gaussian_charges_gpu as TG
+from tests import test_induced_gpu as TI
 from tests import test_qeq_gpu as TQ
+from tests import test_quadrupole_gpu as TQD
+from tests import test_thole_gpu as TTH
+from tests import thole_cases as TC
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -322,3 +348,146 @@ def test_charge_equilibration_copies_as_one_system_and_as_a_batch(fmt):
           f"{int(many.iterations.max())}")
     assert bool((err <= dq).all())
     assert bool(((many.charges.reshape(k, n0).sum(1) - total).abs() <= 1e-12 * n0).all()) and bool((many.iterations <= max_iterations).all())
+
+
+# ---- ewald_quadrupole_real_space / thole_dipole_correction ---------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("fmt", ["matrix", "list"])
+def test_quadrupole_real_space_copies_as_one_system_and_as_a_batch(fmt):
+    from nvalchemiops import _capi as C
+    from nvalchemiops.interactions.electrostatics import ewald_quadrupole_real_space as real
+
+    f = TQD._single()
+    n0, blocks = f["n"], int(C.lib().mi_ewald_quadrupole_blocks())
+    k = _copies(n0, blocks)
+    n = k * n0
+    assert n > 256 * blocks and n % 64 != 0
+    small = real(f["P"], f["Q"], f["M"], f["T"], f["C"], f["A"], **TQD._fmt_kw(f, fmt), **TQD.ALL)
+    for name, o in zip(TQD.NAMES, small):
+        TQD._close(o, f["ref_real"][name], f"fold sizes quadrupole {fmt}: the small call, {name}")
+    P, Q, M, T = (f[x].repeat((k,) + (1,) * (f[x].dim() - 1)) for x in ("P", "Q", "M", "T"))
+    big = _tiled_lists(fmt, f["nm"], f["sh"], f["nl"], f["ptr"], f["lsh"], k, n)
+    one = real(P, Q, M, T, f["C"], f["A"], **big, **TQD.ALL)
+    bi = torch.arange(k, device=DEV, dtype=torch.int32).repeat_interleave(n0)
+    many = [(tag, real(P, Q, M, T, cell, TQD.ALPHA, batch_idx=bi, **big, **TQD.ALL))
+            for tag, cell in (("", f["C"].repeat(k, 1, 1).contiguous()), (" (stride-0 cell)", f["C"][:1].expand(k, 3, 3)))]
+    _check_copies(f"quadrupole real space {fmt}", small, one, many, k, per_atom=(0, 1, 2, 3, 4), vir=5)
+
+
+@pytest.mark.parametrize("fmt", ["matrix", "list"])
+def test_thole_dipole_correction_copies_as_one_system_and_as_a_batch(fmt):
+    """The single periodic case of tests/test_thole_gpu.py (27 atoms, rows of about 210 entries, atoms with a = 0, a < 0 and a = NaN) over a
+    list padded with the mask value alone: the other two kinds of padding of that case (-1, N + 7) would turn into indices of other copies
+    when the list is tiled."""
+    from nvalchemiops import _capi as C
+    from nvalchemiops.interactions.electrostatics import thole_dipole_correction as th
+
+    c = TTH._abi_case("single")
+    n0, blocks = c["n"], int(C.lib().mi_thole_dipole_blocks())
+    f = TTH._lists(*c["ent"], n0)
+    k = _copies(n0, blocks)
+    n = k * n0
+    assert n > 256 * blocks and n % 64 != 0
+    p0, q0, m0, a0, cell = (TTH._t(c[x]) for x in ("pos", "q", "mu", "polar", "cells"))
+    small = th(p0, q0, m0, a0, cell, **TTH._kw(f, fmt), **TTH.ALL)
+    ref = TTH._abi_reference("single", F64)
+    for name, o in zip(TTH.NAMES, small):
+        TTH._close(o, ref[name], f"fold sizes thole {fmt}: the small call, {name}", 1e-11)
+    P, Q, M, A = (x.repeat((k,) + (1,) * (x.dim() - 1)) for x in (p0, q0, m0, a0))
+    big = _tiled_lists(fmt, f["nm"], f["sh"], f["nl"], f["ptr"], f["lsh"], k, n)
+    one = th(P, Q, M, A, cell, **big, **TTH.ALL)
+    bi = torch.arange(k, device=DEV, dtype=torch.int32).repeat_interleave(n0)
+    many = [(tag, th(P, Q, M, A, cells, batch_idx=bi, **big, **TTH.ALL))
+            for tag, cells in (("", cell.repeat(k, 1, 1).contiguous()), (" (stride-0 cell)", cell[:1].expand(k, 3, 3)))]
+    _check_copies(f"thole {fmt}", small, one, many, k, per_atom=(0, 1, 2, 3, 4), vir=5)
+
+
+# ---- induced_dipoles / thole_induced_dipoles -----------------------------------------------------------------------------------------------
+
+def _induced_copies():
+    """(case, small lists, K, blocks) of `thole_cases.fold_case()`: 27 atoms, so K = 911 and N = 24 597."""
+    from nvalchemiops import _capi as C
+
+    case = TC.fold_case()
+    blocks = int(C.lib().mi_induced_blocks())
+    k = _copies(case["n"], blocks)
+    assert k * case["n"] > 256 * blocks and (k * case["n"]) % 64 != 0
+    return case, TTH._lists(*case["entries"], case["n"]), k, blocks
+
+
+@pytest.mark.parametrize("thole", [None, TC.THOLE], ids=["undamped", "thole"])
+@pytest.mark.parametrize("fmt", ["matrix", "list"])
+def test_induced_dipoles_copies_as_one_system_and_as_a_batch(fmt, thole):
+    """reciprocal="ewald" with an EMPTY k set: the reciprocal term is the self term alone, the operator of the copies is block-diagonal with
+    identical blocks and the exact solution is the small dense solution tiled.  `_check_solution`'s bound with the small block's spectrum:
+    max|mu - mu_ref| <= 10 tol ||b_small|| / lambda_min + 1e-14 per system of the batch, times sqrt(K) for the single system (||b|| grows as
+    sqrt(K)), as for `charge_equilibration` above."""
+    from nvalchemiops.interactions.electrostatics import induced_dipoles, thole_induced_dipoles
+
+    tol = 1e-10
+    case, f, k, _ = _induced_copies()
+    n0, n = case["n"], k * case["n"]
+    d = TC.dense(case, thole, DEV)
+    assert d["kv"].shape == (0, 3)
+    solve = induced_dipoles if thole is None else (lambda *a, **kw: thole_induced_dipoles(*a, thole=thole, **kw))
+    common = dict(reciprocal="ewald", k_vectors=d["kv"], tolerance=tol, return_info=True)
+    p0, q0, cell = TTH._t(case["pos"]), TTH._t(case["q"]), TTH._t(case["cell"]).reshape(1, 3, 3)
+    label = f"{'induced' if thole is None else 'thole induced'} {fmt}"
+    out = solve(p0, q0, d["polar"], cell, alpha=case["alpha"], **common, **TTH._kw(f, fmt))
+    mu_ref = TI._check_solution(out, d["H"], d["b"], d["polar"], None, 1, tol, f"fold sizes {label}: the small call")
+    dmu = 10.0 * tol * float(d["b"].norm()) / float(torch.linalg.eigvalsh(d["H"]).min()) + 1e-14
+    P, Q, A = p0.repeat(k, 1), q0.repeat(k), d["polar"].repeat(k)
+    big = _tiled_lists(fmt, f["nm"], f["sh"], f["nl"], f["ptr"], f["lsh"], k, n)
+    want = mu_ref.repeat(k, 1)
+    # one system of K n0 atoms
+    one = solve(P, Q, A, cell, alpha=case["alpha"], **common, **big)
+    err = float((one.dipoles - want).abs().max())
+    print(f"[fold] {label} one system of {n} atoms: max|mu - mu_ref| {err:.3e}  bar {math.sqrt(k) * dmu:.3e}  iterations {one.iterations.tolist()} "
+          f"(small call {out.iterations.tolist()})")
+    assert err <= math.sqrt(k) * dmu and float(one.residual[0]) <= tol
+    # a batch of K systems: K cells, and one cell as a stride-0 expansion
+    bi = torch.arange(k, device=DEV, dtype=torch.int32).repeat_interleave(n0)
+    for tag, cells in (("", cell.repeat(k, 1, 1).contiguous()), (" (stride-0 cell)", cell[:1].expand(k, 3, 3))):
+        many = solve(P, Q, A, cells, alpha=torch.full((k,), case["alpha"], dtype=F64, device=DEV), batch_idx=bi, **common, **big)
+        err = (many.dipoles - want).abs().reshape(k, -1).max(1).values
+        print(f"[fold] {label} batch of {k}{tag}: worst system max|mu - mu_ref| {float(err.max()):.3e}  bar {dmu:.3e}  iterations "
+              f"{int(many.iterations.min())} - {int(many.iterations.max())}")
+        assert bool((err <= dmu).all()) and bool((many.residual <= tol).all())
+        energy = many.polarization_energy
+        assert bool(((energy - out.polarization_energy).abs() <= 100.0 * tol * out.polarization_energy.abs() + 1e-14).all())
+
+
+@pytest.mark.parametrize("fmt", ["matrix", "csr"])
+def test_induced_dot_and_apply_partials_beyond_one_trip(fmt):
+    """`mi_induced_dot` and the `partial` output of `mi_induced_apply` on K n0 random rows against float64 torch sums per system, as one
+    system and as a batch of K; the products themselves equal the tiled small product bit for bit."""
+    from nvalchemiops import _capi as C
+
+    case, f, k, blocks = _induced_copies()
+    n0, n = case["n"], k * case["n"]
+    g = torch.Generator(device="cpu").manual_seed(41)
+    x, y = (torch.randn((n, 3), dtype=F64, generator=g).to(DEV) for _ in range(2))
+    bi = torch.arange(k, device=DEV, dtype=torch.int32).repeat_interleave(n0)
+    p0, a0, cell, al = TTH._t(case["pos"]), TTH._t(case["polar"]), TTH._t(case["cell"]).reshape(1, 3, 3), TTH._t(np.array([case["alpha"]]))
+    if fmt == "matrix":
+        nm, sh = _tile_matrix(f["nm"], f["sh"], k)
+        idx, nptr, m = nm, None, nm.shape[1]
+        small_lay = (f["nm"], f["sh"], None, f["nm"].shape[1])
+    else:
+        lst, nptr, sh = _tile_csr(f["nl"], f["ptr"], f["lsh"], k)
+        idx, m = lst[1].contiguous(), 0
+        small_lay = (f["nl"][1].contiguous(), f["lsh"], f["ptr"], 0)
+    ten0, nbr0, diag0, _ = TI._tensors(p0, a0, cell, al, None, 1, *small_lay, n0)
+    P, A = p0.repeat(k, 1), a0.repeat(k)
+    for label, b, nsys, cells, alpha in (("one system", None, 1, cell, al), (f"batch of {k}", bi, k, cell.repeat(k, 1, 1).contiguous(), al.repeat(k))):
+        part = torch.full((nsys, blocks), float("nan"), dtype=F64, device=DEV)
+        C.check(C.lib().mi_induced_dot(C.ptr(x), C.ptr(y), C.ptr(b), n, nsys, C.ptr(part), C.stream_of(x)), "mi_induced_dot")
+        want = (x * y).sum(1).reshape(nsys, -1).sum(1)
+        _fold_close(part.sum(1), want, want, f"mi_induced_dot {label} of {n} rows")
+        ten, nbr, diag, _ = TI._tensors(P, A, cells, alpha, b, nsys, idx, sh, nptr, m, n)
+        hx, part = TI._apply(ten, nbr, diag, x, None, b, nsys, nptr, m)
+        want = (x * hx).sum(1).reshape(nsys, -1).sum(1)
+        _fold_close(part.sum(1), want, want, f"mi_induced_apply {fmt} partial, {label}")
+        for s in (0, k // 2, k - 1):  # the product of a copy is the small product on that copy's rows
+            rows = slice(s * n0, (s + 1) * n0)
+            assert torch.equal(hx[rows], TI._apply(ten0, nbr0, diag0, x[rows].contiguous(), None, None, 1, small_lay[2], small_lay[3], want_partial=False)[0])

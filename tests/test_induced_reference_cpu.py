@@ -66,6 +66,33 @@ def test_solution_minimises_the_energy_and_pcg_agrees_with_the_dense_solve(name)
     assert 0 < its < 40 and float((x - mu).abs().max()) <= 10 * 1e-10 * float(b.norm()) / lam
 
 
+@pytest.mark.parametrize("thole", [None, 0.39], ids=["undamped", "thole"])
+def test_fold_case_truncated_operator_with_the_self_term_alone_is_positive_definite(thole):
+    """The problem tests/test_fold_sizes_gpu.py tiles: the real-space sum cut at 6 and an empty k set.  Measured: spectrum of D^1/2 H D^1/2 in
+    [0.631, 1.215] undamped, [0.698, 1.150] damped; rows of 29 - 36 entries; dense PCG to 1e-10 in 10 iterations both."""
+    from tests import thole_cases as TC
+
+    case = TC.fold_case()
+    d = TC.dense(case, thole)
+    assert d["kv"].shape == (0, 3)
+    ev = R.scaled_spectrum(d["H"], d["polar"])
+    _, its = R.pcg(d["H"], d["b"], R.preconditioner(d["polar"]), 1e-10)
+    rows = torch.bincount(case["entries"][0], minlength=case["n"])
+    print(f"fold case {'undamped' if thole is None else 'thole'}: spectrum of D^1/2 H D^1/2 in [{float(ev.min()):.3f}, {float(ev.max()):.3f}], "
+          f"rows of {int(rows.min())} - {int(rows.max())} entries (mean {float(rows.double().mean()):.1f}), dense PCG to 1e-10 in {its} iterations")
+    assert float((d["H"] - d["H"].T).abs().max()) <= 1e-15
+    assert float(ev.min()) > 0.5 and float(torch.linalg.eigvalsh(d["H"]).min()) > 0  # a condition on the inputs, not a measurement
+    assert float(d["b"].abs().max()) > 0 and 0 < its < 40
+    # the self term is all that the empty k set leaves: H differs from the real-space operator by -(4 alpha^3 / 3 sqrt(pi)) on the diagonal
+    pos, q, cell = _t(case["pos"]), _t(case["q"]), _t(case["cell"])
+    if thole is None:
+        t_real, _ = R.dipole_operator(pos, q, cell, case["alpha"], case["entries"])
+    else:
+        t_real, _ = TC.TR.damped_operator(pos, q, d["polar"], cell, case["alpha"], thole, case["entries"])
+    self_term = 4.0 * case["alpha"] ** 3 / (3.0 * torch.pi ** 0.5)
+    assert float((d["T"] - t_real + self_term * torch.eye(3 * case["n"], dtype=F64)).abs().max()) <= 1e-14
+
+
 def test_non_polarisable_atoms_are_inert():
     c = IC.lattice("l27")
     f = _problem("l27")

@@ -8,7 +8,16 @@ pairs only.  With the 70 + 60 atoms of the batch taken as the FIRST sites of the
 `dftd4` restatement by 0.45 bars and `dftd4_atm`'s by 0.05 (rolled `rcov`: 54): the batch is therefore built of compact blocks.  On the
 130-atom single system `en` moves `dftd4` by 881 bars but the three-body term by 66 only, so the table sweeps of `dftd4_atm` run on a
 compact 130-atom block as well, where every table is asserted; on the single system itself the figures of `dftd4_atm` are printed
-and its `s9` rule is asserted.  Every test prints its table (`pytest -s`)."""
+and its `s9` rule is asserted.  Every test prints its table (`pytest -s`).
+
+Quadrupole, Thole and induced-dipole fixtures, measured here (largest |moved - ref| / bar, single / batch): quadrupole restatement --
+quadrupoles 2.3e6 / 1.7e6, dipoles 1.1e6 / 9.5e5, charges 9.7e5 / 1.1e6, alpha (batch) 738; Thole restatement -- polarisabilities 8.3e5 /
+6.0e5, dipoles 1.9e6 / 2.8e6, charges 1.5e6 / 1.6e6, E between 0.27 and 60; dense induced-dipole solution against 2 x `_check_solution`'s
+bound -- polarisabilities, charges and external field 1e7 - 1e8 in all four fixtures, alpha (batch) 3.5e3 undamped and 1.9e4 damped.  The
+alpha of the induced batch is why its 27-atom lattice runs at alpha 0.625 with a truncated k sum: with two converged parameter sets the
+operator does not depend on alpha and a rolled `alpha` moved the solution by 1.25 x (2 x bound).  Smallest eigenvalue of D^1/2 H D^1/2:
+0.717 (single) and 0.653, 0.717 (batch) undamped; 0.475 and 0.481, 0.472 damped at polarisabilities in [2, 8], where the undamped H is
+indefinite (asserted)."""
 import numpy as np
 import pytest
 import torch
@@ -125,4 +134,83 @@ def test_dipole_fixture_rolled_dipoles_charges_and_alpha(batch, op):
         moved = L.dipole_reference(batch, op, **{arg: _roll(c[arg])})
         worst[arg] = max(_ratio(moved[k], ref[k], bars[k]) for k in L.DP_NAMES)
     print(f"[sensitivity {op} dipole {'batch' if batch else 'single'}] largest |moved - ref| / bar: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+    assert all(v >= FACTOR for v in worst.values()), worst
+
+
+@pytest.mark.parametrize("batch", [False, True], ids=["single", "batch"])
+def test_quadrupole_fixture_rolled_quadrupoles_dipoles_charges_and_alpha(batch):
+    """The widest bar the sweep applies to the canonical call: 1e-6 max|ref| (+ 1e-14), the float32 bar of tests/test_quadrupole_gpu.py.
+    `alpha` is judged on the batch (0.4 and 0.375) only.  Also the properties the fixture promises: two zero rows and four unsymmetric rows
+    per system, and that reading Q transposed changes nothing in the restatement (1/2 (Q + Q^T) is what counts) while Q itself is not
+    symmetric -- so a T variant whose storage was read untransposed agrees, and one read with a wrong stride does not."""
+    c = L.quadrupole(batch)
+    ref = L.quadrupole_reference(batch)
+    nsys = 2 if batch else 1
+    assert int((~c["qd"].any(axis=(1, 2))).sum()) == 2 * nsys
+    assert int((np.abs(c["qd"] - c["qd"].transpose(0, 2, 1)).max(axis=(1, 2)) > 1e-3).sum()) == 4 * nsys
+    bars = {k: 1e-6 * np.abs(ref[k]).max() + 1e-14 for k in L.QD_NAMES}
+    flipped = L.quadrupole_reference(batch, qd=np.ascontiguousarray(c["qd"].transpose(0, 2, 1)))
+    assert all(_ratio(flipped[k], ref[k], bars[k]) <= 1e-3 for k in L.QD_NAMES)
+    worst = {}
+    for arg in ("qd", "mu", "q") + (("alpha",) if batch else ()):
+        moved = L.quadrupole_reference(batch, **{arg: _roll(c[arg])})
+        worst[arg] = max(_ratio(moved[k], ref[k], bars[k]) for k in L.QD_NAMES)
+    print(f"[sensitivity quadrupole {'batch' if batch else 'single'}] largest |moved - ref| / bar: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+    assert all(v >= FACTOR for v in worst.values()), worst
+
+
+@pytest.mark.parametrize("batch", [False, True], ids=["single", "batch"])
+def test_thole_fixture_rolled_polarisabilities_dipoles_and_charges(batch):
+    """The widest bar of the sweep: 1e-6 max|ref| (+ 1e-14), the float32 bar of tests/test_thole_gpu.py.  The correction does not depend on
+    alpha.  Both sides of the kernel's exit at E = 50 are present among the stored entries."""
+    c = L.thole(batch)
+    ref = L.thole_reference(batch)
+    assert int((c["polar"] == 0).sum()) == (4 if batch else 2) and float(c["polar"][c["polar"] > 0].min()) >= 2.0 and float(c["polar"].max()) <= 8.0
+    i, j, S = L._entries(c["pos"], c["cell"], c["batch_idx"], L.GC_RC)
+    bi = np.zeros(len(c["pos"]), np.int64) if c["batch_idx"] is None else c["batch_idx"]
+    r = np.linalg.norm(c["pos"][j] - c["pos"][i] + np.einsum("ea,eab->eb", S.numpy().astype(np.float64), c["cell"][bi[i]].astype(np.float64)), axis=1)
+    ok = (c["polar"][i] > 0) & (c["polar"][j] > 0)
+    E = L.THOLE * r[ok] ** 3 / np.sqrt(c["polar"][i][ok].astype(np.float64) * c["polar"][j][ok])
+    assert (E < 1.0).any() and (E >= 50.0).any()
+    bars = {k: 1e-6 * np.abs(ref[k]).max() + 1e-14 for k in L.TH_NAMES}
+    worst = {}
+    for arg in ("polar", "mu", "q"):
+        moved = L.thole_reference(batch, **{arg: _roll(c[arg])})
+        worst[arg] = max(_ratio(moved[k], ref[k], bars[k]) for k in L.TH_NAMES)
+    print(f"[sensitivity thole {'batch' if batch else 'single'}] E in [{E.min():.3g}, {E.max():.3g}]; largest |moved - ref| / bar: "
+          + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+    assert all(v >= FACTOR for v in worst.values()), worst
+
+
+@pytest.mark.parametrize("damped", [False, True], ids=["undamped", "thole"])
+@pytest.mark.parametrize("batch", [False, True], ids=["single", "batch"])
+def test_induced_fixtures_are_positive_definite_and_rolled_arguments_move_the_dipoles(batch, damped):
+    """The sweep of the solves compares the canonical call with the dense solution at `_check_solution`'s bound and variants by their bits;
+    the one `reciprocal="pme"` pass is held to twice that bound, which is the widest bar: a rolled `polarizability`, `charges`,
+    `external_field` or (batch) `alpha` must move the dense solution by 100 x (2 x bound).  The smallest eigenvalue of D^1/2 H D^1/2 is
+    positive for every system: undamped at the cases' polarisabilities, damped at polarisabilities drawn as the Thole fixture's (uniform in
+    [2, 8], where the undamped operator is NOT positive definite, which is asserted too: the damping is what the damped fixture tests)."""
+    thole = L.THOLE if damped else None
+    c = L.induced(batch)
+    d = L.induced_dense(c, thole)
+    nsys = c["nsys"]
+    sys_of = (torch.zeros(c["n"], dtype=torch.long) if d["bi"] is None else d["bi"].long()).repeat_interleave(3)
+    low = []
+    for s in range(nsys):
+        m = torch.nonzero(sys_of == s).flatten()
+        ev = L.IR.scaled_spectrum(d["H"][m][:, m], d["polar"][m[::3] // 3])
+        low.append(float(ev.min()))
+    assert min(low) > 0, low
+    if damped:
+        assert int((c["polar_thole"] == 0).sum()) == 2 * nsys
+        plain = L.induced_dense(c, None, polar=c["polar_thole"])
+        assert float(torch.linalg.eigvalsh(plain["H"]).min()) < 0, "without damping these polarisabilities must be beyond the polarisation catastrophe"
+    bound = torch.tensor(L.induced_bound(d, nsys))[sys_of].reshape(-1, 3)
+    mu_ref = L.IR.solve(d["H"], d["b"], d["bi"], nsys)
+    worst = {}
+    for arg in ("polar", "q", "field") + (("alpha",) if batch else ()):
+        m = L.induced_dense(c, thole, **{arg: _roll(c["polar_thole" if damped and arg == "polar" else arg])})
+        worst[arg] = float(((L.IR.solve(m["H"], m["b"], m["bi"], nsys) - mu_ref).abs() / (2.0 * bound)).max())
+    print(f"[sensitivity induced {'batch' if batch else 'single'} {'thole' if damped else 'undamped'}] smallest eigenvalue of D^1/2 H D^1/2 per system "
+          f"{[round(v, 3) for v in low]}; largest |moved - ref| / (2 x bound): " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
     assert all(v >= FACTOR for v in worst.values()), worst

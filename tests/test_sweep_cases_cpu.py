@@ -14,7 +14,9 @@ from tests import atm_reference as A
 from tests import d4_atm_cases as K3
 from tests import d4_atm_reference as R3
 from tests import dipole_reference as DR
+from tests import quadrupole_reference as XR
 from tests import sweep_cases as W
+from tests import thole_reference as TR
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "nvalchemi-toolkit-ops_amd", "csrc")
 
@@ -504,3 +506,140 @@ def test_pme_dipole_ladders_float32_mode(order):
         c = W.dipole_case("big", None)
         assert c["mesh"] == W.BIG_MESH and len(c["pos"]) == 12 and c["order"] == 5
         _nontrivial(c, W.pme_dipole_reference("big", None), "big mesh")
+
+
+# ---- point quadrupoles and Thole damping ----------------------------------------------------------------------------------------------------------
+# The conditions of the cases of tests/test_sweep_multipoles_gpu.py.  A seed is the dipole recipe under the operator's own BASE, so its
+# geometry is held to `_geometry_of_a_dipole_seed`; what the multipole section adds is asserted here.  MEASURED here: the restatement of a
+# quadrupole seed (nested autograd over up to 33 000 entries) takes 0.05 - 2 s -- the interleaved seed 4 evaluates three and takes 5 - 7 s
+# in all --, that of a Thole seed below 0.1 s.
+
+
+def _multipole_reference(c, entries, kv=None):
+    pos, q, mu, cells, alpha, bi = W.dipole_tensors(c)
+    ent = tuple(_tt(e) for e in entries)
+    if "qd" in c:
+        return XR.evaluate(pos, q, mu, _tt(c["qd"]), cells, alpha, ent, kv, batch_idx=bi)
+    return TR.evaluate(pos, q, mu, _tt(c["polar"]), cells, W.THOLE, ent, batch_idx=bi)
+
+
+@pytest.mark.parametrize("seed", W.SEEDS)
+@pytest.mark.parametrize("op", W.MULTIPOLE_OPS)
+def test_multipole_seed_meets_its_conditions(op, seed):
+    base, c = W._dipole_sweep(op, seed), W.multipole_case("sweep", (op, seed))
+    _geometry_of_a_dipole_seed(base, seed)
+    n = len(c["pos"])
+    for k in ("pos", "q", "batch_idx", "weights", "cells", "alpha"):
+        assert np.array_equal(c[k], base[k]), k
+    assert c["entries"] is base["entries"] and c["emptied_row"] == base["emptied_row"] and c["min_dist"] >= W.MIN_CONTACT
+    assert W.entry_distances(c).min() >= W.MIN_CONTACT, "no contact below 1: one close pair must not decide a float32 comparison"
+    assert not c["zero_dipoles"] and c["mu"].any() and 1 <= int((~c["mu"].any(axis=1)).sum()) <= 3, "dipoles on every seed"
+    assert c["zero"] == (seed in W.ZERO_MULTIPOLE_SEEDS) and set(c["flags"]) == set(W.MULTIPOLE_FLAGS[op])
+    if seed in W.SINGLE_FLAG_SEEDS:
+        assert [k for k, v in c["flags"].items() if v] == [W.MULTIPOLE_FLAGS[op][W.SINGLE_FLAG_SEEDS.index(seed)]]
+    ent = W.stored_entries(c)
+    kv = W.dipole_k_vectors(c) if op == "ewald_quadrupole" else None
+    assert len(ent[0]) <= 40_000 and (kv is None or n * kv.shape[-2] <= 200_000), "cost"
+    t0 = time.perf_counter()
+    ref = _multipole_reference(c, ent, kv)
+    took = time.perf_counter() - t0
+    if op == "ewald_quadrupole":
+        assert c["qd"].shape == (n, 3, 3) and (not c["qd"].any()) == c["zero"]
+        if c["zero"]:  # what the parity module asserts as exact zeros is exactly zero in the restatement, and the field gradient is not
+            assert all(not ref[k].any() for k in ("energies", "forces", "charge_grads", "dipole_grads", "virial")) and np.abs(ref["quadrupole_grads"]).max() > 1e-3
+        else:
+            zero_rows = int((~c["qd"].any(axis=(1, 2))).sum())
+            assert 1 <= zero_rows <= 3 and np.abs(ref["energies"]).max() > 0
+            if n > 6:
+                assert np.abs(c["qd"] - c["qd"].transpose(0, 2, 1)).max() > 1e-3, "a few unsymmetric rows"
+    else:
+        assert c["polar"].shape == (n,) and (not c["polar"].any()) == c["zero"] and c["polar"].min() >= 0.0 and c["polar"].max() <= 4.0
+        if c["zero"]:
+            assert all(not v.any() for v in ref.values()), "every atom non-polarisable: every output exactly 0"
+        else:
+            E, _ = W.thole_exponents(c, ent)
+            assert (n <= 3 or (c["polar"] == 0).any()) and np.abs(ref["energies"]).max() > 0
+            if max(c["sizes"]) >= 60:
+                assert (E < 1.0).any() and (E >= W.THOLE_EXIT).any(), "both sides of the exit at E = 50"
+    if seed in W.INTERLEAVED_SEEDS:  # the real-space sums on the interleaved batch are the sorted ones, atom by atom
+        p = W.multipole_interleaved(c)
+        a = _multipole_reference(p, W.stored_entries(p))
+        b = _multipole_reference(c, ent)
+        assert np.abs(a["energies"] - b["energies"][c["perm"]]).max() <= 1e-12 * np.abs(b["energies"]).max()
+        assert np.abs(a["virial"] - b["virial"]).max() <= 1e-12 * np.abs(b["virial"]).max()
+    print(f"{op} {seed}: sizes {c['sizes']} {c['dtype']}, {len(ent[0])} entries, widest row {c['widest']}, flags {[k[8:] for k, v in c['flags'].items() if v]}, "
+          f"max |E| {np.abs(ref['energies']).max():.3e}, restatement {took:.2f} s")
+
+
+@pytest.mark.parametrize("op", W.MULTIPOLE_OPS)
+def test_multipole_seeds_cover_what_they_are_meant_to(op):
+    cases = [W.multipole_case("sweep", (op, s)) for s in W.SEEDS]
+    assert {c["dtype"] for c in cases} == {"float32", "float64"} and all(c["dtype"] == ("float64", "float32")[c["seed"] % 2] for c in cases)
+    assert {n for c in cases for n in c["sizes"]} == set(W.CHARGE_SIZES) | {0} and {len(c["sizes"]) for c in cases} == {1, 2, 3}
+    assert any(c["self_images"] for c in cases) and any(not c["self_images"] for c in cases)
+    assert any(np.allclose(c["cells"][s], np.diag(np.diag(c["cells"][s]))) for c in cases for s in range(len(c["sizes"])))
+    assert any(c["cells"][s][1, 0] != 0 for c in cases for s in range(len(c["sizes"])))
+    assert sum(c["zero"] for c in cases) == 3 and {c["dtype"] for c in cases if c["zero"]} == {"float32", "float64"}
+    assert sum(c["perm"] is not None for c in cases) == 2 and sum(c["empty_system"] is not None for c in cases) == 2
+    assert all(c["dtype"] == "float64" for c in cases if c["perm"] is not None)
+    designated = set(W.ZERO_MULTIPOLE_SEEDS) | set(W.INTERLEAVED_SEEDS) | set(W.EMPTY_SYSTEM_SEEDS)
+    assert len(designated) == 7 and set(W.SINGLE_FLAG_SEEDS) == set(W.SEEDS) - designated
+    alone = [tuple(k for k, v in c["flags"].items() if v) for c in cases if not c["zero"]]
+    assert all((k,) in alone for k in W.MULTIPOLE_FLAGS[op]), "every flag alone at least once, on a seed with quadrupoles / polarisabilities"
+    assert len(set(alone)) >= 7 and {c["autograd"] for c in cases} == {False, True}
+    assert max(c["widest"] for c in cases) > 64 and sum(c["widest"] > 64 for c in cases) >= 6, "rows longer than one trip of the wave"
+
+
+def test_multipole_ladders():
+    a = W.multipole_case("atoms")
+    assert a["sizes"] == W.ATOM_RUNGS == (255, 256, 257, 1) and a["qd"].shape == (769, 3, 3) and np.array_equal(a["pos"], W.dipole_atom_case()["pos"])
+    ka = W.dipole_k_vectors(a)
+    assert ka.shape[0] == 4 and 60 <= ka.shape[1] <= 70
+    pos, q, mu, cells, alpha, bi = W.dipole_tensors(a)
+    ref = XR.evaluate(pos, q, mu, _tt(a["qd"]), cells, alpha, None, ka, batch_idx=bi)
+    assert all(np.abs(ref["energies"][bi.numpy() == s]).max() > 0 for s in range(4)) and all(_antisymmetric(v) > 1e-6 for v in ref["virial"][:3])
+    c = W.multipole_case("no_shifts")
+    i, j, S = c["entries"]
+    assert len(c["pos"]) == 65 and (np.bincount(i, minlength=65) == 64).all() and not S.any() and c["min_dist"] >= W.MIN_CONTACT
+    assert np.array_equal(c["cells"][0], np.eye(3) * 4.0 * c["diameter"]), "no image inside any cutoff: zero shifts are the whole list"
+    s = W.multipole_case("shared_k")
+    assert s["sizes"] == (60, 9) and np.array_equal(s["cells"][0], s["cells"][1]) and s["alpha"][0] == s["alpha"][1]
+    ks = W.dipole_k_vectors(s)
+    assert ks.shape[0] == 2 and torch.equal(ks[0], ks[1]) and ks.shape[1] > 64, "one k set serves both systems"
+    for k in (0, 1):
+        p = s["pos"][s["batch_idx"] == k]
+        assert (np.linalg.norm(p[:, None] - p[None], axis=-1) + 9.0 * np.eye(len(p))).min() >= W.MIN_CONTACT
+
+
+@pytest.mark.parametrize("periodic", [True, False], ids=["periodic", "cluster"])
+def test_thole_row_ladder_rows_straddle_the_exit(periodic):
+    c = W.multipole_case("thole_rows", periodic)
+    i, j, S = c["entries"]
+    n = len(c["pos"])
+    counts = np.bincount(i, minlength=n)
+    assert tuple(counts[:len(W.THOLE_ROWS)]) == W.THOLE_ROWS == (0, 1, 63, 64, 65, 128, 129) and n == 7 + (40 if periodic else 130)
+    assert (c["cells"] is None) == (not periodic) and (periodic or not S.any()) and c["min_dist"] >= W.MIN_CONTACT
+    pairs = set(zip(i.tolist(), j.tolist(), map(tuple, S.tolist())))
+    assert len(pairs) == len(i) and all((b, a, (-s[0], -s[1], -s[2])) in pairs for a, b, s in pairs), "distinct entries, a full (symmetric) list"
+    assert (c["polar"][:7] > 0).all() and int((c["polar"] == 0).sum()) == 2
+    E, rows = W.thole_exponents(c)
+    inside = [int((E[rows == t] < W.THOLE_EXIT).sum()) for t in range(7)]
+    beyond = [int((E[rows == t] >= W.THOLE_EXIT).sum()) for t in range(7)]
+    print(f"thole row ladder ({'periodic' if periodic else 'cluster'}): entries inside / beyond the exit per ladder row {list(zip(inside, beyond))}")
+    assert inside[1] == 1, "the row of one entry lies inside the exit: it contributes"
+    assert all(inside[t] >= 3 and beyond[t] >= 3 for t in range(2, 7)), "every longer row has entries on both sides of E = 50"
+    ref = TR.evaluate(_tt(c["pos"]), _tt(c["q"]), _tt(c["mu"]), _tt(c["polar"]), _tt(c["cells"]) if periodic else None, W.THOLE,
+                      tuple(_tt(e) for e in c["entries"]))
+    assert not ref["energies"][0] and all(abs(ref["energies"][t]) > 0 for t in range(1, 7))
+
+
+def test_induced_idle_systems_case():
+    from tests import thole_cases as TC
+
+    c = W.induced_idle_systems_case()
+    assert c["sizes"] == (27, 0, 9) and set(c["batch_idx"].tolist()) == {0, 2} and c["cells"].shape == (3, 3, 3)
+    assert (c["polar"][:27] > 0).all() and not c["polar"][27:].any() and np.abs(c["q"][27:]).min() > 0
+    i, j, S = c["entries"]
+    assert ((i < 27) == (j < 27)).all() and (np.bincount(i, minlength=36)[27:] > 0).all(), "no entry joins two systems; the idle atoms do have neighbours"
+    d = TC.dense(TC.lattice("l27"), None)
+    assert float(torch.linalg.eigvalsh(d["H"]).min()) > 0 and float(d["b"].abs().max()) > 0, "system 0 has a solve to do"

@@ -47,12 +47,27 @@ def lattice(name, large=False):
                 entries=IC.entries(name), k_cutoff=IC.EWALD["k_cutoff"])
 
 
+FOLD_CUTOFF = 6.0
+
+
+@functools.lru_cache(maxsize=None)
+def fold_case(name="l27"):
+    """The lattice the fold-size tests of the solvers tile (tests/test_fold_sizes_gpu.py): list cutoff `FOLD_CUTOFF` (29 - 36 entries per
+    row, so that the stored operator of 911 copies stays small) and an EMPTY k set (`k_cutoff=None`): of the reciprocal term only the self
+    term -(2 alpha^3 / 3 sqrt(pi)) |mu|^2 is left, which does not couple the copies.  tests/test_induced_reference_cpu.py asserts that this
+    truncated H is positive definite, undamped and damped."""
+    c = IC.lattice(name)
+    return dict(n=c["n"], pos=c["pos"], cell=c["cell"], q=c["q"], polar=c["polar"], alpha=IC.EWALD["alpha"],
+                entries=IC.entries(name, FOLD_CUTOFF, 1), k_cutoff=None)
+
+
 def dense(case, thole, device="cpu", field=None):
-    """dict(T, c, H, b, polar) of a case on `device`: the undamped operator for `thole=None`, E_dip + E_thole otherwise."""
+    """dict(T, c, H, b, polar) of a case on `device`: the undamped operator for `thole=None`, E_dip + E_thole otherwise.  A case with
+    `k_cutoff=None` has an empty k set [0, 3]."""
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=F64, device=device)  # noqa: E731
     pos, q, polar, cell = t(case["pos"]), t(case["q"]), t(case["polar"]), t(case["cell"])
     ent = tuple(e.to(device) for e in case["entries"])
-    kv = IC.k_vectors(case["cell"], case["k_cutoff"]).to(device)
+    kv = torch.zeros((0, 3), dtype=F64, device=device) if case["k_cutoff"] is None else IC.k_vectors(case["cell"], case["k_cutoff"]).to(device)
     if thole is None:
         T, c = IR.dipole_operator(pos, q, cell, case["alpha"], ent, kv)
     else:
