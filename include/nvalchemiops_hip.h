@@ -1063,6 +1063,40 @@ int mi_pme_dipole_virial(const void* spec_q, const void* spec_mu, const void* re
                          int ny, int nz, int order, int dtype, double* partial, void* stream);
 int mi_pme_dipole_virial_blocks(void);
 
+/* Particle-mesh Ewald for point quadrupoles (csrc/pme.hip, last section; driver: nvalchemiops/interactions/electrostatics/pme_quadrupole.py): the
+ * dipole section continued by one multipole order.  quadrupoles [n_atoms][3][3] in `dtype`, 1/2 (Q + Q^T) of it is used; l_i = q_i + mu_i . grad,
+ * Theta_i = Q_i : grad grad, c3 = 4 alpha^3 / (3 sqrt(pi)), c5 = 4 alpha^5 / (5 sqrt(pi)):
+ *     rho_l = sum_i l_i W_i,  rho_T = sum_i Theta_i W_i,  phi_T = the mesh solve of rho_T,  phi_L = the mesh solve of rho_l, plus phi_T,
+ *     E_i = l_i W_i.phi_T + Theta_i W_i.phi_L + c3 q_i tr Q_i - c5 (2 Q_i:Q_i + (tr Q_i)^2)
+ * order is 5 or 6 (the forces need the third derivative of the spline, which is not continuous at order 4); everything else as for mi_pme_dipole_*.
+ *
+ * mi_pme_quadrupole_spread: one pass over the atoms adds l_i W_i into meshes[0] and Theta_i W_i into meshes[1], and with weights g their g-weighted
+ * twins into meshes[2] and meshes[3]: meshes [2 (weights NULL) | 4][n_systems][nx][ny][nz], ZEROED BY THIS CALL.  Floating-point atomic adds; a
+ * value that is exactly zero is not added, so zero quadrupoles leave meshes[1] exactly zero.
+ *
+ * mi_pme_quadrupole_gather: one read of mesh_a and mesh_b per stencil point gives, per atom,
+ *     D_i = { dq: W_i.A,  dmu: grad W_i.A,  dQ: grad grad W_i.B,  dr: q_i grad W_i.A + (mu_i . grad) grad W_i.A + (Q_i : grad grad) grad W_i.B }
+ * and writes charge_grads[i] = s_i D_i.dq + w_i c3 tr Q_i, dipole_grads[i] = s_i D_i.dmu, quadrupole_grads[i] (3 x 3, symmetric) = s_i D_i.dQ +
+ * w_i (c3 q_i I - c5 (4 Q_i + 2 tr Q_i I)), forces[i] = -s_i D_i.dr (positions dtype; the others float64), with s_i and w_i as for
+ * mi_pme_dipole_gather: 2 and 1 for the forward call over (A, B) = (phi_T, phi_L); weights[i] for the first launch of the adjoint; accumulate = 1
+ * (weights NULL): s_i = 1, no self terms, outputs ADDED to what they hold -- the second launch of the adjoint, over (phi^g_T, phi^g_l + phi^g_T).
+ * energies[i] (float64) = l_i W_i.A + Theta_i W_i.B + the self terms, never weighted or accumulated.  Any output may be NULL; the third-derivative
+ * work is compiled only into the variant that runs when forces is given.  No atomics.
+ *
+ * mi_pme_quadrupole_virial: mi_pme_dipole_virial over the spectra of (rho_l, rho_T), E_m = G(k_m) (2 Re[conj(spec_l) spec_t] + |spec_t|^2) / sf2_m:
+ * partial [n_systems][mi_pme_quadrupole_virial_blocks()][9] float64.  The caller folds the blocks and adds the terms of the multipoles' fractional
+ * components, sum_i (dE/dmu_i)[a] mu_i[b] + 2 sum_i (G_i Q_i)[a][b] per system, G_i = dE/dQ_i without its self terms. */
+int mi_pme_quadrupole_spread(const void* positions, const void* charges, const void* dipoles, const void* quadrupoles, const double* weights,
+                             const int32_t* batch_idx, const void* cell_inv_t, int n_atoms, int n_systems, int nx, int ny, int nz, int order, int dtype,
+                             void* meshes, void* stream);
+int mi_pme_quadrupole_gather(const void* positions, const void* charges, const void* dipoles, const void* quadrupoles, const double* weights,
+                             const int32_t* batch_idx, const void* cell_inv_t, const void* mesh_a, const void* mesh_b, const void* alpha /*[n_systems]*/,
+                             int n_atoms, int n_systems, int nx, int ny, int nz, int order, int dtype, int accumulate, double* energies, void* forces,
+                             double* charge_grads, double* dipole_grads, double* quadrupole_grads, void* stream);
+int mi_pme_quadrupole_virial(const void* spec_l, const void* spec_t, const void* recip_cell, const void* alpha, const void* volume, int n_systems,
+                             int nx, int ny, int nz, int order, int dtype, double* partial, void* stream);
+int mi_pme_quadrupole_virial_blocks(void);
+
 int mi_pme_gather_finish(const void* positions, const void* charges, const int32_t* batch_idx, const void* cell_inv_t,
                          const void* meshes /*[B,(1|4),nx,ny,nz] real*/, const void* alpha, const void* volume,
                          const void* total_charge /*[B]*/, int n_atoms, int n_systems, int nx, int ny, int nz,

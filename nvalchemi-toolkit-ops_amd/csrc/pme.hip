@@ -2371,3 +2371,360 @@ int mi_pme_dipole_virial(const void* spec_q, const void* spec_mu, const void* re
 int mi_pme_dipole_virial_blocks(void) { return PME_VIR_BLOCKS; }
 
 }  // extern "C"
+
+// ==== particle-mesh Ewald for point quadrupoles (driver: nvalchemiops/interactions/electrostatics/pme_quadrupole.py) ========================
+// The section above continued by one multipole order.  With l_i = q_i + mu_i . grad and Theta_i = Q_i : grad grad (Q_i symmetric):
+//   rho_l = sum_i l_i W_i,  rho_T = sum_i Theta_i W_i,  phi_T = solve(rho_T),  phi_L = solve(rho_l) + phi_T,
+//   c3 = 4 alpha^3 / (3 sqrt(pi)),  c5 = 4 alpha^5 / (5 sqrt(pi)):
+//   E_i = l_i W_i.phi_T + Theta_i W_i.phi_L + c3 q_i tr Q_i - c5 (2 Q_i:Q_i + (tr Q_i)^2)
+//   dE/dq_i = 2 W_i.phi_T + c3 tr Q_i,   dE/dmu_i = 2 grad W_i.phi_T,   dE/dQ_i = 2 grad grad W_i.phi_L + c3 q_i I - c5 (4 Q_i + 2 tr Q_i I)
+//   F_i = -2 [q_i grad W_i.phi_T + (mu_i.grad) grad W_i.phi_T + (Q_i:grad grad) grad W_i.phi_L]
+// In mesh coordinates Q : grad grad W = sum_aa' Qf[a][a'] d2 W / dm_a dm_a' with Qf = cit Q cit^T; the factors n_a of d / dm_a live in the 1-D
+// tables (M' n, M'' n^2, M''' n^3), and Qf travels as six words {xx, yy, zz, 2 xy, 2 xz, 2 yz}.
+namespace {
+
+// `dipole_spline` with M_p''' as well, from the same single pass of the recursion: at level p - 3 it holds c_k = M_{p-3}(u - k), k = 0..3, and
+//   M_p''' = c_0 - 3 c_1 + 3 c_2 - c_3.   ORDER is 5 or 6 (at order 4 level p - 3 is the indicator function: M_4''' is not continuous).
+template <class T, int ORDER> __device__ __forceinline__ void quadrupole_spline(T u, T& w, T& d, T& dd, T& ddd) {
+  static_assert(ORDER >= 5, "the third derivative needs order 5 or 6");
+  w = d = dd = ddd = T(0);
+  if (!(u >= T(0) && u < T(ORDER))) return;
+  T m[ORDER];
+#pragma unroll
+  for (int k = 0; k < ORDER; ++k) { const T x = u - T(k); m[k] = (x >= T(0) && x < T(1)) ? T(1) : T(0); }
+#pragma unroll
+  for (int p = 2; p <= ORDER - 3; ++p) {
+    const T inv = T(1) / T(p - 1);
+#pragma unroll
+    for (int k = 0; k <= ORDER - p; ++k) { const T x = u - T(k); m[k] = (x * m[k] + (T(p) - x) * m[k + 1]) * inv; }
+  }
+  ddd = m[0] - T(3) * m[1] + T(3) * m[2] - m[3];
+  {
+    const T inv = T(1) / T(ORDER - 3);
+#pragma unroll
+    for (int k = 0; k <= 2; ++k) { const T x = u - T(k); m[k] = (x * m[k] + (T(ORDER - 2) - x) * m[k + 1]) * inv; }
+  }
+  dd = m[0] - T(2) * m[1] + m[2];
+  const T inv = T(1) / T(ORDER - 2), x1 = u - T(1);
+  const T b0 = (u * m[0] + (T(ORDER - 1) - u) * m[1]) * inv, b1 = (x1 * m[1] + (T(ORDER - 1) - x1) * m[2]) * inv;
+  d = b0 - b1;
+  w = (u * b0 + (T(ORDER) - u) * b1) / T(ORDER - 1);
+}
+
+// Qf = cit Qs cit^T of Qs = 1/2 (Q + Q^T), as six words {xx, yy, zz, 2 xy, 2 xz, 2 yz}: Q : grad grad W = sum_w qf[w] H[w] over the six
+// distinct second derivatives of W in mesh coordinates
+template <class T> __device__ __forceinline__ void quadrupole_frac(const T* __restrict__ c, const T* __restrict__ Q9, T qf[6]) {
+  T qs[3][3], cq[3][3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) qs[a][b] = T(0.5) * (Q9[3 * a + b] + Q9[3 * b + a]);
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) cq[a][b] = c[3 * a] * qs[0][b] + c[3 * a + 1] * qs[1][b] + c[3 * a + 2] * qs[2][b];
+  auto f = [&](int a, int b) { return cq[a][0] * c[3 * b] + cq[a][1] * c[3 * b + 1] + cq[a][2] * c[3 * b + 2]; };
+  qf[0] = f(0, 0); qf[1] = f(1, 1); qf[2] = f(2, 2);
+  qf[3] = T(2) * f(0, 1); qf[4] = T(2) * f(0, 2); qf[5] = T(2) * f(1, 2);
+}
+
+// 1-D values, first and second derivatives (times n, n^2) of one atom, evaluated ONCE by 3 x ORDER threads of its group, in LDS
+template <class T, int ORDER> struct QuadrupoleStencil { T w[3][ORDER], d[3][ORDER], dd[3][ORDER]; int gi[3][ORDER]; };
+
+// Spread: pme_dipole_spread_kernel with a second-derivative table.  One pass adds l_i W_i into meshes[0] and Theta_i W_i into meshes[1] -- and
+// with per-atom weights g their weighted twins into meshes[2], meshes[3] -- by atomic adds into [2 | 4][B][nx][ny][nz] the entry point zeroed.
+// A value that is exactly zero is not added: zero quadrupoles leave meshes[1] exactly zero.
+template <class T, int ORDER>
+__global__ __launch_bounds__(256) void pme_quadrupole_spread_kernel(const T* __restrict__ pos, const T* __restrict__ charges, const T* __restrict__ dipoles,
+                                                                    const T* __restrict__ quadrupoles, const double* __restrict__ weights,
+                                                                    const int* __restrict__ batch_idx, const T* __restrict__ cit, int N, int B, int nx,
+                                                                    int ny, int nz, T* __restrict__ meshes) {
+  constexpr int tpa = ORDER * ORDER, apb = 256 / tpa;
+  __shared__ QuadrupoleStencil<T, ORDER> sten[apb];
+  const int la = threadIdx.x / tpa, col = threadIdx.x - la * tpa;
+  const int i = blockIdx.x * apb + la;
+  const bool active = la < apb && i < N;
+  const int s = active && batch_idx ? batch_idx[i] : 0;
+  if (active && col < 3 * ORDER) {
+    const Stencil<T> st = make_stencil(pos + 3 * (size_t)i, cit + 9 * (size_t)s, nx, ny, nz, ORDER);
+    const int d = col / ORDER, t = col - d * ORDER;
+    const int n = d == 0 ? nx : (d == 1 ? ny : nz);
+    const T u = (T)ORDER * T(0.5) + st.theta[d] - (T)(t + st.off0[d]);
+    T w1, d1, dd1, ddd1;
+    quadrupole_spline<T, ORDER>(u, w1, d1, dd1, ddd1);
+    sten[la].w[d][t] = w1;
+    sten[la].d[d][t] = d1 * (T)n;
+    sten[la].dd[d][t] = dd1 * (T)n * (T)n;
+    sten[la].gi[d][t] = wrap_idx(st.base[d] + t + st.off0[d], n);
+  }
+  __syncthreads();
+  if (!active) return;
+  const QuadrupoleStencil<T, ORDER>& k = sten[la];
+  const T* c = cit + 9 * (size_t)s;
+  const T mu[3] = {dipoles[3 * (size_t)i], dipoles[3 * (size_t)i + 1], dipoles[3 * (size_t)i + 2]};
+  T mf[3], qf[6];
+  mat3_colvec(c, mu, mf);  // mu_frac = cit mu
+  quadrupole_frac(c, quadrupoles + 9 * (size_t)i, qf);
+  const T q = charges[i];
+  const int tx = col / ORDER, ty = col - tx * ORDER;
+  const T wx = k.w[0][tx], dx = k.d[0][tx], ddx = k.dd[0][tx], wy = k.w[1][ty], dy = k.d[1][ty], ddy = k.dd[1][ty];
+  // per column: the coefficients of w_z, w_z' and w_z'' of the two densities
+  const T l0 = q * (wx * wy) + mf[0] * (dx * wy) + mf[1] * (wx * dy), l1 = mf[2] * (wx * wy);
+  const T t0 = qf[0] * (ddx * wy) + qf[1] * (wx * ddy) + qf[3] * (dx * dy), t1 = qf[4] * (dx * wy) + qf[5] * (wx * dy), t2 = qf[2] * (wx * wy);
+  const size_t mesh = (size_t)B * nx * ny * nz;
+  T* row = meshes + (((size_t)s * nx + k.gi[0][tx]) * ny + k.gi[1][ty]) * nz;
+  const bool weighted = weights != nullptr;
+  const T g = weighted ? (T)weights[i] : T(0);
+#pragma unroll
+  for (int tz = 0; tz < ORDER; ++tz) {
+    const T vl = l0 * k.w[2][tz] + l1 * k.d[2][tz];
+    const T vt = t0 * k.w[2][tz] + t1 * k.d[2][tz] + t2 * k.dd[2][tz];
+    T* p = row + k.gi[2][tz];
+    if (vl != T(0)) atomicAdd(p, vl);
+    if (vt != T(0)) atomicAdd(p + mesh, vt);
+    if (weighted) {
+      if (g * vl != T(0)) atomicAdd(p + 2 * mesh, g * vl);
+      if (g * vt != T(0)) atomicAdd(p + 3 * mesh, g * vt);
+    }
+  }
+}
+
+// Gather: PG_LANES lanes per atom, one x-plane of the stencil each, shuffle fold, no atomics -- the shape of pme_dipole_gather_kernel.  One read
+// of each of the two meshes A and B per stencil point.  The sums are taken axis by axis: the z-contractions of a mesh row with w_z .. w_z''',
+// then those with the y table, and once per lane with the lane's x values, which gives every mixed derivative up to the order needed:
+//   sA = W.A,  gA = grad W.A,  hA = (mu_frac . grad) grad W.A (FV only),  HB = the six Hessian words of B,  tB = (Qf : grad grad) grad W.B (FV only)
+// With D_i = {dq: sA, dmu: cit^T gA, dQ: cit^T HB cit, dr: cit^T (q gA + hA + tB)} the outputs are s_i D_i, s_i = 2 (the forward call), g_i
+// (weights) or 1 (accumulate: the second launch of the adjoint, added to what the first one wrote); the self terms ride with the first launch.
+// FV (forces wanted) is a compile-time split: the third-derivative tables and the Hessian of A exist only where the forces are asked for.
+template <class T, int ORDER, bool FV>
+__global__ __launch_bounds__(256) void pme_quadrupole_gather_kernel(const T* __restrict__ pos, const T* __restrict__ charges, const T* __restrict__ dipoles,
+                                                                    const T* __restrict__ quadrupoles, const double* __restrict__ weights,
+                                                                    const int* __restrict__ batch_idx, const T* __restrict__ cit,
+                                                                    const T* __restrict__ mesh_a, const T* __restrict__ mesh_b, const T* __restrict__ alpha,
+                                                                    int N, int nx, int ny, int nz, int accumulate, double* __restrict__ energies,
+                                                                    T* __restrict__ forces, double* __restrict__ cgrads, double* __restrict__ dgrads,
+                                                                    double* __restrict__ qgrads) {
+  constexpr int D = FV ? 4 : 3;  // derivative orders held per axis
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int i0 = t / PG_LANES, tx = t - i0 * PG_LANES;
+  const int i = i0 < N ? i0 : N - 1;  // surplus groups of the last block recompute the last atom and do not store
+  const int s = batch_idx ? batch_idx[i] : 0;
+  const T* c = cit + 9 * (size_t)s;
+  const Stencil<T> st = make_stencil(pos + 3 * (size_t)i, c, nx, ny, nz, ORDER);
+  const int dims[3] = {nx, ny, nz};
+  T tab[2][D][ORDER];  // the y and z axes: M, M' n, M'' n^2 (, M''' n^3); the lane's own x-plane below
+  int gi[2][ORDER];
+#pragma unroll
+  for (int a = 1; a < 3; ++a)
+#pragma unroll
+    for (int k = 0; k < ORDER; ++k) {
+      const T u = (T)ORDER * T(0.5) + st.theta[a] - (T)(k + st.off0[a]);
+      const T n = (T)dims[a];
+      T v[4];
+      quadrupole_spline<T, ORDER>(u, v[0], v[1], v[2], v[3]);
+      T f = T(1);
+#pragma unroll
+      for (int o = 0; o < D; ++o) { tab[a - 1][o][k] = v[o] * f; f *= n; }
+      gi[a - 1][k] = wrap_idx(st.base[a] + k + st.off0[a], dims[a]);
+    }
+  const T mu[3] = {dipoles[3 * (size_t)i], dipoles[3 * (size_t)i + 1], dipoles[3 * (size_t)i + 2]};
+  T mf[3], qf[6];
+  mat3_colvec(c, mu, mf);
+  quadrupole_frac(c, quadrupoles + 9 * (size_t)i, qf);
+  T sA = 0, gA[3] = {0, 0, 0}, hA[3] = {0, 0, 0}, HB[6] = {0, 0, 0, 0, 0, 0}, tB[3] = {0, 0, 0};
+  if (tx < ORDER) {
+    const T u = (T)ORDER * T(0.5) + st.theta[0] - (T)(tx + st.off0[0]);
+    T X[4];
+    quadrupole_spline<T, ORDER>(u, X[0], X[1], X[2], X[3]);
+    X[1] *= (T)nx;
+    X[2] *= (T)nx * (T)nx;
+    X[3] *= (T)nx * (T)nx * (T)nx;
+    const size_t m0 = ((size_t)s * nx + wrap_idx(st.base[0] + tx + st.off0[0], nx)) * ny;
+    // P[j][k] = sum over the lane's plane of (d/dm_y)^j (d/dm_z)^k of the weights times the mesh, j + k < D (A: j + k < D - 1)
+    T PA[D - 1][D - 1], PB[D][D];
+#pragma unroll
+    for (int j = 0; j < D; ++j)
+#pragma unroll
+      for (int k = 0; k < D; ++k) { PB[j][k] = T(0); if (j < D - 1 && k < D - 1) PA[j][k] = T(0); }
+#pragma unroll
+    for (int ty = 0; ty < ORDER; ++ty) {
+      const size_t row = (m0 + gi[0][ty]) * nz;
+      T za[D - 1], zb[D];
+#pragma unroll
+      for (int k = 0; k < D; ++k) { zb[k] = T(0); if (k < D - 1) za[k] = T(0); }
+#pragma unroll
+      for (int tz = 0; tz < ORDER; ++tz) {
+        const T a = mesh_a[row + gi[1][tz]], b = mesh_b[row + gi[1][tz]];
+#pragma unroll
+        for (int k = 0; k < D; ++k) { zb[k] += b * tab[1][k][tz]; if (k < D - 1) za[k] += a * tab[1][k][tz]; }
+      }
+#pragma unroll
+      for (int j = 0; j < D; ++j)
+#pragma unroll
+        for (int k = 0; k + j < D; ++k) {
+          PB[j][k] += tab[0][j][ty] * zb[k];
+          if (j + k < D - 1) PA[j][k] += tab[0][j][ty] * za[k];
+        }
+    }
+    sA = X[0] * PA[0][0];
+    gA[0] = X[1] * PA[0][0]; gA[1] = X[0] * PA[1][0]; gA[2] = X[0] * PA[0][1];
+    HB[0] = X[2] * PB[0][0]; HB[1] = X[0] * PB[2][0]; HB[2] = X[0] * PB[0][2];
+    HB[3] = X[1] * PB[1][0]; HB[4] = X[1] * PB[0][1]; HB[5] = X[0] * PB[1][1];
+    if constexpr (FV) {
+      const T axx = X[2] * PA[0][0], ayy = X[0] * PA[2][0], azz = X[0] * PA[0][2], axy = X[1] * PA[1][0], axz = X[1] * PA[0][1], ayz = X[0] * PA[1][1];
+      hA[0] = mf[0] * axx + mf[1] * axy + mf[2] * axz;
+      hA[1] = mf[0] * axy + mf[1] * ayy + mf[2] * ayz;
+      hA[2] = mf[0] * axz + mf[1] * ayz + mf[2] * azz;
+      const T xxx = X[3] * PB[0][0], xxy = X[2] * PB[1][0], xxz = X[2] * PB[0][1], xyy = X[1] * PB[2][0], xyz = X[1] * PB[1][1], xzz = X[1] * PB[0][2];
+      const T yyy = X[0] * PB[3][0], yyz = X[0] * PB[2][1], yzz = X[0] * PB[1][2], zzz = X[0] * PB[0][3];
+      tB[0] = qf[0] * xxx + qf[1] * xyy + qf[2] * xzz + qf[3] * xxy + qf[4] * xxz + qf[5] * xyz;
+      tB[1] = qf[0] * xxy + qf[1] * yyy + qf[2] * yzz + qf[3] * xyy + qf[4] * xyz + qf[5] * yyz;
+      tB[2] = qf[0] * xxz + qf[1] * yyz + qf[2] * zzz + qf[3] * xyz + qf[4] * xzz + qf[5] * yzz;
+    }
+  }
+#pragma unroll
+  for (int o = PG_LANES / 2; o > 0; o >>= 1) {
+    sA += __shfl_xor(sA, o, PG_LANES);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      gA[a] += __shfl_xor(gA[a], o, PG_LANES);
+      if constexpr (FV) { hA[a] += __shfl_xor(hA[a], o, PG_LANES); tB[a] += __shfl_xor(tB[a], o, PG_LANES); }
+    }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) HB[a] += __shfl_xor(HB[a], o, PG_LANES);
+  }
+  if (tx != 0 || i0 >= N) return;
+  // fractional -> Cartesian, in double: v_cart[b] = sum_a cit[a][b] v_frac[a],  H_cart[b][b'] = sum_aa' cit[a][b] cit[a'][b'] H_frac[a][a']
+  double cd[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) cd[k] = (double)c[k];
+  const double q = (double)charges[i];
+  double cA[3], cF[3];
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    cA[b] = cd[b] * (double)gA[0] + cd[3 + b] * (double)gA[1] + cd[6 + b] * (double)gA[2];
+    cF[b] = cd[b] * ((double)hA[0] + (double)tB[0]) + cd[3 + b] * ((double)hA[1] + (double)tB[1]) + cd[6 + b] * ((double)hA[2] + (double)tB[2]);
+  }
+  const double hf[3][3] = {{(double)HB[0], (double)HB[3], (double)HB[4]}, {(double)HB[3], (double)HB[1], (double)HB[5]}, {(double)HB[4], (double)HB[5], (double)HB[2]}};
+  double hc[3][3], half[3][3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) half[a][b] = hf[a][0] * cd[b] + hf[a][1] * cd[3 + b] + hf[a][2] * cd[6 + b];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = a; b < 3; ++b) hc[a][b] = hc[b][a] = cd[a] * half[0][b] + cd[3 + a] * half[1][b] + cd[6 + a] * half[2][b];  // symmetric to the bit
+  double Q[3][3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) Q[a][b] = 0.5 * ((double)quadrupoles[9 * (size_t)i + 3 * a + b] + (double)quadrupoles[9 * (size_t)i + 3 * b + a]);
+  const double al = (double)alpha[s], al3 = al * al * al;
+  const double c3 = 4.0 * al3 / (3.0 * 1.7724538509055160273), c5 = 4.0 * al3 * al * al / (5.0 * 1.7724538509055160273);
+  const double tr = Q[0][0] + Q[1][1] + Q[2][2];
+  const double m[3] = {(double)mu[0], (double)mu[1], (double)mu[2]};
+  const double gw = weights ? weights[i] : 1.0;
+  const double sc = accumulate ? 1.0 : (weights ? gw : 2.0);
+  if (energies) {
+    double qq = 0.0, qh = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) { qq += Q[a][b] * Q[a][b]; qh += Q[a][b] * hc[a][b]; }
+    energies[i] = q * (double)sA + (m[0] * cA[0] + m[1] * cA[1] + m[2] * cA[2]) + qh + c3 * q * tr - c5 * (2.0 * qq + tr * tr);
+  }
+  if (cgrads) { const double v = sc * (double)sA; cgrads[i] = accumulate ? cgrads[i] + v : v + gw * c3 * tr; }
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    const size_t o = 3 * (size_t)i + b;
+    if (dgrads) { const double v = sc * cA[b]; dgrads[o] = accumulate ? dgrads[o] + v : v; }
+    if constexpr (FV) { const double v = -sc * (q * cA[b] + cF[b]); forces[o] = accumulate ? (T)((double)forces[o] + v) : (T)v; }
+  }
+  if (qgrads) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        const size_t o = 9 * (size_t)i + 3 * a + b;
+        const double v = sc * hc[a][b];
+        qgrads[o] = accumulate ? qgrads[o] + v : v + gw * ((a == b ? c3 * q - 2.0 * c5 * tr : 0.0) - 4.0 * c5 * Q[a][b]);
+      }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi_pme_quadrupole_spread(const void* positions, const void* charges, const void* dipoles, const void* quadrupoles, const double* weights,
+                             const int32_t* batch_idx, const void* cell_inv_t, int n_atoms, int n_systems, int nx, int ny, int nz, int order, int dtype,
+                             void* meshes, void* stream) {
+  MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
+  MI_REQUIRE(order >= 5 && order <= MI_MAX_ORDER, "spline order must be 5 or 6 (the quadrupole terms need three continuous derivatives of the spline)");
+  MI_REQUIRE(n_systems >= 1 && nx >= order && ny >= order && nz >= order, "every mesh dimension must be at least the spline order");
+  MI_REQUIRE(n_atoms >= 0 && meshes && cell_inv_t, "null pointer");
+  MI_REQUIRE(n_atoms == 0 || (positions && charges && dipoles && quadrupoles), "null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t mesh_bytes = (size_t)n_systems * nx * ny * nz * dtype_bytes(dtype);
+  mi_timing_begin("pme_quadrupole_spread", stream);
+  MI_HIP_CHECK(hipMemsetAsync(meshes, 0, (weights ? 4 : 2) * mesh_bytes, st));
+  if (n_atoms > 0) {
+    const int apb = 256 / (order * order);
+    MI_DISPATCH_ORDER(order, MI_DISPATCH_T(dtype, (pme_quadrupole_spread_kernel<T_, (O_ < 5 ? 5 : O_)><<<mi_blocks(n_atoms, apb), 256, 0, st>>>(
+                                 (const T_*)positions, (const T_*)charges, (const T_*)dipoles, (const T_*)quadrupoles, weights, batch_idx,
+                                 (const T_*)cell_inv_t, n_atoms, n_systems, nx, ny, nz, (T_*)meshes))));
+  }
+  mi_timing_end(stream);
+  MI_LAUNCH_CHECK();
+  return MI_OK;
+}
+
+#define MI_PME_QUADRUPOLE_GATHER(FV_)                                                                                                                  \
+  MI_DISPATCH_ORDER(order, MI_DISPATCH_T(dtype, (pme_quadrupole_gather_kernel<T_, (O_ < 5 ? 5 : O_), FV_><<<mi_blocks((long long)n_atoms * PG_LANES, 256), 256, 0, st>>>( \
+                               (const T_*)positions, (const T_*)charges, (const T_*)dipoles, (const T_*)quadrupoles, weights, batch_idx,                \
+                               (const T_*)cell_inv_t, (const T_*)mesh_a, (const T_*)mesh_b, (const T_*)alpha, n_atoms, nx, ny, nz, accumulate, energies, \
+                               (T_*)forces, charge_grads, dipole_grads, quadrupole_grads))))
+
+int mi_pme_quadrupole_gather(const void* positions, const void* charges, const void* dipoles, const void* quadrupoles, const double* weights,
+                             const int32_t* batch_idx, const void* cell_inv_t, const void* mesh_a, const void* mesh_b, const void* alpha, int n_atoms,
+                             int n_systems, int nx, int ny, int nz, int order, int dtype, int accumulate, double* energies, void* forces,
+                             double* charge_grads, double* dipole_grads, double* quadrupole_grads, void* stream) {
+  MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
+  MI_REQUIRE(order >= 5 && order <= MI_MAX_ORDER, "spline order must be 5 or 6 (the quadrupole terms need three continuous derivatives of the spline)");
+  MI_REQUIRE(n_systems >= 1 && nx >= order && ny >= order && nz >= order, "every mesh dimension must be at least the spline order");
+  MI_REQUIRE(!(accumulate && weights), "accumulate (the second launch of the adjoint) takes no weights");
+  if (n_atoms <= 0) return MI_OK;
+  MI_REQUIRE(positions && charges && dipoles && quadrupoles && cell_inv_t && mesh_a && mesh_b && alpha, "null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  mi_timing_begin("pme_quadrupole_gather", stream);
+  if (forces) MI_PME_QUADRUPOLE_GATHER(true);
+  else MI_PME_QUADRUPOLE_GATHER(false);
+  mi_timing_end(stream);
+  MI_LAUNCH_CHECK();
+  return MI_OK;
+}
+#undef MI_PME_QUADRUPOLE_GATHER
+
+// The k-space virial is the cross form of the dipole section with (rho_l, rho_T) in the places of (rho_q, rho_mu):
+//   E_m = h_m G_m (2 Re[conj(rho_l) rho_T] + |rho_T|^2) / sf2_m -- the same kernel.  The caller adds the two terms of the multipoles' fractional
+// components, sum_i (dE/dmu_i)_a mu_i,b + 2 sum_i (G_i Q_i)_ab with G_i = dE/dQ_i without its self terms.
+int mi_pme_quadrupole_virial(const void* spec_l, const void* spec_t, const void* recip_cell, const void* alpha, const void* volume, int n_systems,
+                             int nx, int ny, int nz, int order, int dtype, double* partial /*[n_systems][mi_pme_quadrupole_virial_blocks()][9]*/,
+                             void* stream) {
+  MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
+  MI_REQUIRE(order >= 5 && order <= MI_MAX_ORDER, "spline order must be 5 or 6 (the quadrupole terms need three continuous derivatives of the spline)");
+  MI_REQUIRE(spec_l && spec_t && recip_cell && alpha && volume && partial && n_systems >= 1 && n_systems <= 65535 && nx > 0 && ny > 0 && nz > 0,
+             "null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  mi_timing_begin("pme_quadrupole_virial", stream);
+  MI_DISPATCH_T(dtype, (pme_dipole_virial_kernel<T_><<<dim3(PME_VIR_BLOCKS, n_systems), 256, 0, st>>>(
+                           (const Cplx<T_>*)spec_l, (const Cplx<T_>*)spec_t, (const T_*)recip_cell, (const T_*)alpha, (const T_*)volume, nx, ny, nz, order,
+                           partial)));
+  mi_timing_end(stream);
+  MI_LAUNCH_CHECK();
+  return MI_OK;
+}
+int mi_pme_quadrupole_virial_blocks(void) { return PME_VIR_BLOCKS; }
+
+}  // extern "C"

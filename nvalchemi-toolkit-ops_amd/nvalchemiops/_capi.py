@@ -192,6 +192,15 @@ def lib() -> ctypes.CDLL:
         L.mi_pme_dipole_virial.argtypes = [vp] * 5 + [i] * 6 + [vp, vp]
         L.mi_pme_dipole_virial_blocks.restype = i
         L.mi_pme_dipole_virial_blocks.argtypes = []
+        # particle-mesh Ewald for point quadrupoles (nvalchemiops/interactions/electrostatics/pme_quadrupole.py)
+        L.mi_pme_quadrupole_spread.restype = i
+        L.mi_pme_quadrupole_spread.argtypes = [vp] * 7 + [i] * 7 + [vp, vp]
+        L.mi_pme_quadrupole_gather.restype = i
+        L.mi_pme_quadrupole_gather.argtypes = [vp] * 10 + [i] * 8 + [vp] * 6
+        L.mi_pme_quadrupole_virial.restype = i
+        L.mi_pme_quadrupole_virial.argtypes = [vp] * 5 + [i] * 6 + [vp, vp]
+        L.mi_pme_quadrupole_virial_blocks.restype = i
+        L.mi_pme_quadrupole_virial_blocks.argtypes = []
         # charge equilibration (nvalchemiops/interactions/electrostatics/qeq.py)
         L.mi_qeq_pair_coefficients.restype = i
         L.mi_qeq_pair_coefficients.argtypes = [vp] * 6 + [i, i, i, vp, vp, vp, i, i, vp, vp, vp, vp]

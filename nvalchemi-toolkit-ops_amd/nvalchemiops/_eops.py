@@ -1975,7 +1975,52 @@ ewald_quadrupole_reciprocal_space_op = _op("_ewald_quadrupole_reciprocal_space",
                                                         {4: "cell", 5: "k_vectors", 6: "alpha"}), _qd_recip_setup)
 
 
-__all__ = ["ewald_quadrupole_real_space_op", "ewald_quadrupole_reciprocal_space_op", "ewald_quadrupole_real_bwd_op",
+# point-quadrupole PME, mesh half: the pattern of the point-dipole PME op with the quadrupoles as a fourth differentiable input and six outputs
+def _qd_pme_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, quadrupoles: Tensor, cell: Tensor, alpha: Tensor, batch_idx: Optional[Tensor],
+                nx: int, ny: int, nz: int, spline_order: int, compute_forces: bool, compute_charge_gradients: bool, compute_dipole_gradients: bool,
+                compute_quadrupole_gradients: bool, compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from nvalchemiops.interactions.electrostatics.pme_quadrupole import _recip_forward
+
+    out = _recip_forward(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, (int(nx), int(ny), int(nz)), int(spline_order),
+                         compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_quadrupole_gradients, compute_virial)
+    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
+
+
+def _qd_pme_fwd_fake(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, nx, ny, nz, spline_order, compute_forces,
+                     compute_charge_gradients, compute_dipole_gradients, compute_quadrupole_gradients, compute_virial):
+    nsys = cell.reshape(-1, 3, 3).shape[0] if batch_idx is not None else 1
+    return _qd_fake(positions, nsys, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_quadrupole_gradients,
+                    compute_virial)
+
+
+def _qd_pme_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, quadrupoles: Tensor, cell: Tensor, alpha: Tensor, batch_idx: Optional[Tensor],
+                nx: int, ny: int, nz: int, spline_order: int, grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles, dL/dquadrupoles) for L = sum_i g_i E_i."""
+    from nvalchemiops.interactions.electrostatics.pme_quadrupole import _recip_adjoint
+
+    return _recip_adjoint(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, (int(nx), int(ny), int(nz)), int(spline_order),
+                          grad_energies)
+
+
+pme_quadrupole_recip_bwd_op = torch.library.custom_op("nvalchemiops::pme_quadrupole_reciprocal_space_backward", _qd_pme_bwd, mutates_args=())
+pme_quadrupole_recip_bwd_op.register_fake(_qd_bwd_fake)
+pme_quadrupole_recip_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::pme_quadrupole_reciprocal_space_backward"),
+                                              setup_context=lambda ctx, inputs, output: None)
+
+
+def _qd_pme_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:7])
+    ctx.extra = tuple(int(v) for v in inputs[7:11])
+    ctx.set_materialize_grads(False)
+
+
+pme_quadrupole_reciprocal_space_op = _op("_pme_quadrupole_reciprocal_space", _qd_pme_fwd, _qd_pme_fwd_fake,
+                                         _qd_backward(f"{_NS}::_pme_quadrupole_reciprocal_space", pme_quadrupole_recip_bwd_op,
+                                                      {4: "cell", 5: "alpha"}), _qd_pme_setup)
+
+
+__all__ = ["pme_quadrupole_reciprocal_space_op", "pme_quadrupole_recip_bwd_op",
+           "ewald_quadrupole_real_space_op", "ewald_quadrupole_reciprocal_space_op", "ewald_quadrupole_real_bwd_op",
            "ewald_quadrupole_recip_bwd_op", "thole_dipole_correction_op", "thole_dipole_bwd_op", "pme_dipole_reciprocal_space_op", "pme_dipole_recip_bwd_op", "ewald_dipole_real_space_op", "ewald_dipole_reciprocal_space_op", "ewald_dipole_real_bwd_op", "ewald_dipole_recip_bwd_op",
            "gaussian_charge_correction_op", "gaussian_bwd_op","spline_spread_op", "batch_spline_spread_op", "spline_gather_op", "batch_spline_gather_op", "spline_gather_vec3_op",
            "batch_spline_gather_vec3_op", "spline_gather_gradient_op", "batch_spline_gather_gradient_op", "pme_green_structure_factor_op",

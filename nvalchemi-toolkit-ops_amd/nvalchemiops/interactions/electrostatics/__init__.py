@@ -6,6 +6,7 @@ from nvalchemiops.interactions.electrostatics.dipole import ewald_dipole_correct
 from nvalchemiops.interactions.electrostatics.pme_dipole import pme_dipole_correction, pme_dipole_reciprocal_space
 from nvalchemiops.interactions.electrostatics.quadrupole import (ewald_quadrupole_correction, ewald_quadrupole_real_space,
                                                                  ewald_quadrupole_reciprocal_space)
+from nvalchemiops.interactions.electrostatics.pme_quadrupole import pme_quadrupole_correction, pme_quadrupole_reciprocal_space
 from nvalchemiops.interactions.electrostatics.gaussian import gaussian_charge_correction
 from nvalchemiops.interactions.electrostatics.induced import (InducedDipoleError, InducedDipoleResult, induced_dipoles,
                                                               thole_induced_dipoles)
@@ -28,4 +29,5 @@ __all__ = [
     "ewald_dipole_correction", "ewald_dipole_real_space", "ewald_dipole_reciprocal_space", "pme_dipole_correction", "pme_dipole_reciprocal_space",
     "induced_dipoles", "InducedDipoleError", "InducedDipoleResult", "thole_dipole_correction", "thole_induced_dipoles",
     "ewald_quadrupole_correction", "ewald_quadrupole_real_space", "ewald_quadrupole_reciprocal_space",
+    "pme_quadrupole_correction", "pme_quadrupole_reciprocal_space",
 ]

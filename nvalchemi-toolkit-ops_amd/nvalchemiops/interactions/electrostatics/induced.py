@@ -405,7 +405,7 @@ def induced_dipoles(positions: torch.Tensor, charges: torch.Tensor, polarizabili
 
     Out of scope: anisotropic polarisabilities, clusters without a cell, quadrupoles, a cell gradient, an extended-Lagrangian or predictor
     scheme.  A differently damped permanent field can be passed through `external_field` with zero charges; the field of permanent quadrupoles
-    is minus the `dipole_grads` of `ewald_quadrupole_correction`, passed the same way."""
+    is minus the `dipole_grads` of `ewald_quadrupole_correction` (or, on the mesh, of `pme_quadrupole_correction`), passed the same way."""
     return _solve(None, positions, charges, polarizability, cell, external_field, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
                   neighbor_matrix, neighbor_matrix_shifts, mask_value, reciprocal, alpha, mesh_dimensions, mesh_spacing, spline_order, k_vectors,
                   k_cutoff, accuracy, tolerance, max_iterations, check_interval, initial_dipoles, return_info)

@@ -48,8 +48,8 @@ _RETURNS = """Returns ``energies`` [N], or a tuple holding only what was asked f
     Energies are differentiable once w.r.t. positions, charges and dipoles, for any upstream gradient on the per-atom energies (the same
     kernels run as their own adjoint); the call then goes through the `alchemiops::_pme_dipole_reciprocal_space` op, as it does under
     `torch.compile`.  Differentiating the explicit forces, gradients or virial raises NotImplementedError.  Gradients w.r.t. cell and alpha are
-    out of scope (NotImplementedError at backward): use `compute_virial`.  Also out of scope: quadrupoles (on the mesh; `ewald_quadrupole_correction` adds them by
-    explicit Ewald summation), a tile-owned spread, caller-supplied
+    out of scope (NotImplementedError at backward): use `compute_virial`.  Also out of scope: quadrupoles (`pme_quadrupole_correction` adds them
+    on the mesh, `ewald_quadrupole_correction` by explicit Ewald summation), a tile-owned spread, caller-supplied
     k arrays, `cell=None` clusters, surface (non-tin-foil) terms.  The spread uses float64 atomic adds: float64 outputs are reproducible only
     up to the arrival order of these adds (last bits); float32 outputs are the same in every run.  CPU tensors raise NativeLibraryError: there is no fallback."""
 

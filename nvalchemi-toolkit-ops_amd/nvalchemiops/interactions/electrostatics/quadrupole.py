@@ -55,7 +55,7 @@ _RETURNS = """Returns ``energies`` [N], or a tuple holding only what was asked f
     Energies are differentiable once w.r.t. positions, charges, dipoles and quadrupoles, for any upstream gradient on the per-atom energies
     (the same kernels run as their own adjoint); the call then goes through an `alchemiops::_ewald_quadrupole_*` op, as it does under
     `torch.compile`.  Differentiating the explicit forces, gradients or virial raises NotImplementedError.  Gradients w.r.t. cell and alpha
-    are out of scope (NotImplementedError at backward): use `compute_virial`.  Also out of scope: quadrupoles on the mesh, `cell=None`
+    are out of scope (NotImplementedError at backward): use `compute_virial`.  Also out of scope: quadrupoles on the mesh (`pme_quadrupole_correction` is the mesh counterpart of this routine), `cell=None`
     clusters, octupoles, spherical-tensor input, surface (non-tin-foil) terms.  CPU tensors raise NativeLibraryError: there is no fallback."""
 
 
