@@ -2510,7 +2510,16 @@ __global__ __launch_bounds__(256) void pme_quadrupole_gather_kernel(const T* __r
   const int i = i0 < N ? i0 : N - 1;  // surplus groups of the last block recompute the last atom and do not store
   const int s = batch_idx ? batch_idx[i] : 0;
   const T* c = cit + 9 * (size_t)s;
-  const Stencil<T> st = make_stencil(pos + 3 * (size_t)i, c, nx, ny, nz, ORDER);
+  // The stencil and the 1-D tables are formed in double from the caller's values and rounded once: a float32 call spreads in double
+  // (`_spread`), so its meshes hold the weights of the unrounded mesh coordinate.  Tables from a float32 coordinate (off by up to 1e-6 of
+  // a mesh spacing) are those of a slightly displaced atom, on which its own density then pulls: a force of float32-rounding size that
+  // does not shrink with the net force.  In a float64 call every operation below is what it was.
+  double p3[3], c9[9];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) p3[k] = (double)pos[3 * (size_t)i + k];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) c9[k] = (double)c[k];
+  const Stencil<double> st = make_stencil<double>(p3, c9, nx, ny, nz, ORDER);
   const int dims[3] = {nx, ny, nz};
   T tab[2][D][ORDER];  // the y and z axes: M, M' n, M'' n^2 (, M''' n^3); the lane's own x-plane below
   int gi[2][ORDER];
@@ -2518,13 +2527,13 @@ __global__ __launch_bounds__(256) void pme_quadrupole_gather_kernel(const T* __r
   for (int a = 1; a < 3; ++a)
 #pragma unroll
     for (int k = 0; k < ORDER; ++k) {
-      const T u = (T)ORDER * T(0.5) + st.theta[a] - (T)(k + st.off0[a]);
-      const T n = (T)dims[a];
-      T v[4];
-      quadrupole_spline<T, ORDER>(u, v[0], v[1], v[2], v[3]);
-      T f = T(1);
+      const double u = (double)ORDER * 0.5 + st.theta[a] - (double)(k + st.off0[a]);
+      const double n = (double)dims[a];
+      double v[4];
+      quadrupole_spline<double, ORDER>(u, v[0], v[1], v[2], v[3]);
+      double f = 1.0;
 #pragma unroll
-      for (int o = 0; o < D; ++o) { tab[a - 1][o][k] = v[o] * f; f *= n; }
+      for (int o = 0; o < D; ++o) { tab[a - 1][o][k] = (T)(v[o] * f); f *= n; }
       gi[a - 1][k] = wrap_idx(st.base[a] + k + st.off0[a], dims[a]);
     }
   const T mu[3] = {dipoles[3 * (size_t)i], dipoles[3 * (size_t)i + 1], dipoles[3 * (size_t)i + 2]};
@@ -2533,12 +2542,13 @@ __global__ __launch_bounds__(256) void pme_quadrupole_gather_kernel(const T* __r
   quadrupole_frac(c, quadrupoles + 9 * (size_t)i, qf);
   T sA = 0, gA[3] = {0, 0, 0}, hA[3] = {0, 0, 0}, HB[6] = {0, 0, 0, 0, 0, 0}, tB[3] = {0, 0, 0};
   if (tx < ORDER) {
-    const T u = (T)ORDER * T(0.5) + st.theta[0] - (T)(tx + st.off0[0]);
-    T X[4];
-    quadrupole_spline<T, ORDER>(u, X[0], X[1], X[2], X[3]);
-    X[1] *= (T)nx;
-    X[2] *= (T)nx * (T)nx;
-    X[3] *= (T)nx * (T)nx * (T)nx;
+    const double u = (double)ORDER * 0.5 + st.theta[0] - (double)(tx + st.off0[0]);
+    double Xd[4];
+    quadrupole_spline<double, ORDER>(u, Xd[0], Xd[1], Xd[2], Xd[3]);
+    Xd[1] *= (double)nx;
+    Xd[2] *= (double)nx * (double)nx;
+    Xd[3] *= (double)nx * (double)nx * (double)nx;
+    const T X[4] = {(T)Xd[0], (T)Xd[1], (T)Xd[2], (T)Xd[3]};
     const size_t m0 = ((size_t)s * nx + wrap_idx(st.base[0] + tx + st.off0[0], nx)) * ny;
     // P[j][k] = sum over the lane's plane of (d/dm_y)^j (d/dm_z)^k of the weights times the mesh, j + k < D (A: j + k < D - 1)
     T PA[D - 1][D - 1], PB[D][D];

@@ -54,7 +54,7 @@ _RETURNS = """Returns ``energies`` [N], or a tuple holding only what was asked f
     up to the arrival order of these adds (last bits); float32 outputs are the same in every run.  CPU tensors raise NativeLibraryError: there is no fallback."""
 
 ORDERS = (4, 5, 6)
-_SPREAD_FLOAT32_IN_FLOAT64 = True  # float32 calls: the spread adds in float64 and rounds once (see `_spread`)
+_SPREAD_FLOAT32_IN_FLOAT64 = True  # float32 calls: the spread adds in float64 and rounds once (see `_spread`); the dipole term only -- `pme_quadrupole._spread` always does, its gather depends on it
 
 
 def _check_order(spline_order) -> int:

@@ -11,7 +11,8 @@ quadrupole mesh), `mi_pme_quadrupole_gather` (potential, gradient, Hessian and -
 in one pass) and `mi_pme_quadrupole_virial` (the k-space virial of the cross spectrum).  Between them runs the mesh solve of the charge PME,
 through `_solve` of `pme_dipole.py`.  Forward and adjoint are the same launches without and with per-atom weights.  The spread adds with
 floating-point atomics, always in float64, with the consequences `pme_dipole.py` describes: float64 outputs are reproducible up to the arrival
-order of these adds, float32 outputs are the same in every run.
+order of these adds, float32 outputs are the same in every run.  The gather forms its stencil and spline tables in float64 whatever the
+dtype and rounds them once, so that a float32 call gathers with the weights it spread with.
 """
 from __future__ import annotations
 
@@ -95,9 +96,10 @@ def _inputs(positions, charges, dipoles, quadrupoles, cells, alpha, batch_idx):
 
 def _spread(p, dims, order, weights=None):
     """[2 | 4, nsys, nx, ny, nz]: rho_l, rho_T (and their g-weighted twins), zero-filled by the entry point.  float32 calls add in float64 and
-    round once, the policy of `pme_dipole._spread`."""
+    round once, the policy of `pme_dipole._spread` -- here without its switch (`pme_dipole._SPREAD_FLOAT32_IN_FLOAT64`): the gather forms
+    its stencil in float64 whatever the dtype, and a spread from float32 stencils would not be the one it is the adjoint of."""
     pos = p["pos"]
-    if pos.dtype == torch.float32 and _pd._SPREAD_FLOAT32_IN_FLOAT64:
+    if pos.dtype == torch.float32:
         wide = {k: p[k].to(torch.float64) for k in ("pos", "q", "mu", "qd", "cit")}
         return _spread(dict(p, code=C.dtype_code(torch.float64), **wide), dims, order, weights).to(torch.float32)
     meshes = torch.empty((4 if weights is not None else 2, p["nsys"]) + dims, dtype=pos.dtype, device=pos.device)

@@ -10,6 +10,7 @@ must move the result far beyond the bar the sweep applies.  Every reference is c
     qeq_cluster(), qeq_periodic()   two clusters (no cell) / two periodic systems with their own k-vectors and alpha
     dipole(batch)               the Gaussian fixture's boxes with point dipoles, per-system alpha, a k set and a mesh: both dipole operators
     quadrupole(batch)           `dipole(batch)` plus quadrupoles (two zero rows and four unsymmetric rows per system)
+    pme_quadrupole(batch)       `quadrupole(batch)` on mesh `DP_MESH` at order 6 (the dipole fixture covers order 5): `pme_quadrupole_correction`
     thole(batch)                `dipole(batch)` plus polarisabilities in [2, 8] (two non-polarisable atoms per system), width 0.39
     induced(batch)              an `induced_cases` lattice (l64 / l27 + l64) in float32 numbers with its full list, k set, an external field and
                                 a warm start; polarisabilities for the undamped and for the damped solve
@@ -32,6 +33,7 @@ from tests import gaussian_reference as GR
 from tests import induced_cases as IC
 from tests import induced_reference as IR
 from tests import pme_dipole_reference as PR
+from tests import pme_quadrupole_reference as PQR
 from tests import qeq_reference as QR
 from tests import quadrupole_reference as XR
 from tests import systems as S
@@ -324,6 +326,28 @@ def quadrupole_reference(batch=False, part="total", dtype=F64, **replace):
     ent = _entries(c["pos"], c["cell"], c["batch_idx"], GC_RC) if part != "recip" else None
     return XR.evaluate(t(c["pos"]), t(c["q"]), t(c["mu"]), t(c["qd"]), t(c["cell"]), t(c["alpha"]), ent, t(c["kv"]) if part != "real" else None,
                        batch_idx=bi, distance_dtype=dtype)
+
+
+PQ_ORDER = 6
+
+
+def pme_quadrupole(batch=False):
+    """`quadrupole(batch)`: the mesh operator takes the same inputs, on mesh `DP_MESH` at order `PQ_ORDER`."""
+    return quadrupole(batch)
+
+
+def pme_quadrupole_reference(batch=False, dtype=F64, **replace):
+    """The restatement of `pme_quadrupole_reciprocal_space` (tests/pme_quadrupole_reference.py) on the fixture, mesh `DP_MESH`, order
+    `PQ_ORDER`; `dtype` float32 is its float32 mode."""
+    c = {**pme_quadrupole(batch), **replace}
+    t = lambda a: torch.as_tensor(np.asarray(a, np.float64))  # noqa: E731
+    bi = None if c["batch_idx"] is None else torch.as_tensor(c["batch_idx"])
+    return PQR.evaluate(t(c["pos"]), t(c["q"]), t(c["mu"]), t(c["qd"]), t(c["cell"]), t(c["alpha"]), DP_MESH, PQ_ORDER, batch_idx=bi, dtype=dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def pme_quadrupole_references(batch=False):
+    return pme_quadrupole_reference(batch), pme_quadrupole_reference(batch, torch.float32)
 
 
 @functools.lru_cache(maxsize=None)

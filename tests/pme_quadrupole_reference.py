@@ -144,3 +144,22 @@ def closed_virial(pos, q, mu, Q, cell, alpha, dims, order):
     gq = _sym(gq)
     out = out + torch.einsum("ia,ib->ab", gmu, mu.detach()) + 2.0 * torch.einsum("iac,icb->ab", gq, Qs.detach())
     return out.detach().numpy()
+
+
+def half_spectrum_plane_virial(pos, q, mu, Q, cell, alpha, dims, order, k):
+    """[3, 3] numpy: what plane k of the rfft half spectrum adds to the k-space virial of ONE system per unit of its Hermitian weight,
+        sum over the plane of (G / sf^2)(2 Re[conj(rho_l) rho_T] + |rho_T|^2)(delta_ab - 2 (1/k^2 + 1/(4 alpha^2)) k_a k_b),
+    the first sum of `closed_virial` restricted to one plane (the twin of `pme_dipole_reference.half_spectrum_plane_virial`).  On an odd axis
+    the last plane k = (nz - 1) / 2 has weight 2; the test cases use this to make sure that plane is visible in the virial."""
+    dims = tuple(int(v) for v in dims)
+    nx, ny, _ = dims
+    rho_l, rho_t = densities(pos, q, mu, _sym(Q), cell, dims, order)
+    sl, st = torch.fft.rfftn(rho_l.detach())[:, :, k], torch.fft.rfftn(rho_t.detach())[:, :, k]
+    e = _influence(cell, alpha, dims, order)[:, :, k] * (2.0 * (sl.conj() * st).real + st.abs() ** 2)
+    miller = lambda n: torch.tensor([i if i < (n + 1) // 2 else i - n for i in range(n)], dtype=cell.dtype)  # noqa: E731
+    m = torch.stack(torch.meshgrid(miller(nx), miller(ny), torch.tensor([float(k)], dtype=cell.dtype), indexing="ij"), dim=-1)[:, :, 0]
+    kv = torch.einsum("cd,xyd->xyc", 2.0 * math.pi * torch.linalg.inv(cell), m)
+    k2 = (kv * kv).sum(-1)
+    k2 = torch.where(k2 < 1e-10, torch.ones_like(k2), k2)  # e is 0 there
+    out = torch.eye(3, dtype=cell.dtype) * e.sum() - 2.0 * torch.einsum("xy,xya,xyb->ab", e * (1.0 / k2 + 0.25 / (alpha * alpha)), kv, kv)
+    return out.detach().numpy()

@@ -1,6 +1,6 @@
 """Seeded sweep cases, boundary ladders and one-scalar variants of the five newer dispersion operators (`dftd3_atm`, `dftd3_zero`,
 `dftd3_zero_atm`, `dftd4`, `dftd4_atm`) and the inputs of the sweeps of `gaussian_charge_correction`, charge equilibration, the two
-point-dipole operators, `ewald_quadrupole_correction`, `thole_dipole_correction` and `induced_dipoles` (last three sections),
+point-dipole operators, `ewald_quadrupole_correction`, `thole_dipole_correction`, `induced_dipoles` and `pme_quadrupole_correction` (last four sections),
 built on the float64 restatements tests/atm_reference.py, tests/d3_zero_reference.py,
 tests/d4_reference.py and tests/d4_atm_reference.py.  Importable without a GPU and without the native library (the two tile sizes are read
 lazily, by the ladder builders only).  The CPU suite asserts every condition a case must meet (tests/test_sweep_cases_cpu.py); the GPU
@@ -1065,3 +1065,203 @@ def induced_idle_systems_case():
              entries=(np.concatenate([i0, i2 + 27]), np.concatenate([j0, j2 + 27]), np.concatenate([S0, S2])), pad=3, emptied_row=None)
     c["widest"] = int(np.bincount(c["entries"][0], minlength=n).max())
     return c
+
+
+# ---- point quadrupoles on the mesh: pme_quadrupole_correction ---------------------------------------------------------------------------------------
+# Inputs and the restatement (tests/pme_quadrupole_reference.py, on the CPU, on the same mesh and order) in both of its modes.  A seed is the
+# dipole recipe above under its own BASE (geometry with spaced positions, one to three systems with their own cells and alpha, weights, the
+# emptied row of the stored list, the interleaving permutation, the system without atoms) with dipoles on every seed but `NO_DIPOLE_SEED`
+# (there the call passes `dipoles=None`; the seed is an empty-system seed, so it has two systems with atoms), quadrupoles as in the
+# `ewald_quadrupole` sweep and that sweep's flags.  ORDER 5 and 6 in turn, two seeds each ((seed // 2) % 2): the dtype alternates with the
+# seed, so every order meets both dtypes.  MESH: three draws from `mesh_choices(order)`.  The ladder, the knot cases and the big mesh follow
+# the seeds.  tests/test_sweep_cases_cpu.py asserts the conditions; tests/test_sweep_pme_quadrupole_gpu.py runs the kernels on them.
+
+BASE.update(pme_quadrupole=8920)  # 8920: the first of 8900, 8910, ... whose twelve seeds meet every condition of the CPU suite
+PMEQ_ORDERS = (5, 6)
+NO_DIPOLE_SEED = 5
+PMEQ_POOL_SEED = 8990        # of the ladder's pool, + order: the first of 8980, 8990, ... whose rungs are within the float32 cap (rung 1: but for `PMEQ_LONE_ATOM_EXEMPT`) and whose first atom has a dipole and a quadrupole
+PMEQ_LONE_ATOM_EXEMPT = ("forces", "dipole_grads")  # of rung 1 in float32: see `pmeq_spread_case`
+PMEQ_KNOT_SEED = 8960
+PMEQ_KNOT_CASES = ((5, (16, 16, 16)), (6, (16, 16, 16)), (6, (6, 8, 16)), (5, (5, 8, 16)))
+PMEQ_KNOT_SHIFTS = ((0, 0, -3), (1, 1, 2), (2, 2, 1))  # (atom, axis, whole cells) of the lattice-translation check
+PMEQ_GRADS = ("forces", "charge_grads", "dipole_grads", "quadrupole_grads")
+
+
+def pmeq_spread_rungs(order):
+    return (1,) + spread_rungs(order)
+
+
+@functools.lru_cache(maxsize=None)
+def _pmeq_sweep(seed):
+    c = dict(_dipole_sweep("pme_quadrupole", seed))
+    g = np.random.default_rng(BASE["pme_quadrupole"] + 500 + seed)
+    n = len(c["pos"])
+    if c["zero_dipoles"]:
+        c.update(mu=_dipoles(g, n), zero_dipoles=False)
+    if seed == NO_DIPOLE_SEED:
+        c.update(mu=np.zeros((n, 3)))
+    c["no_dipoles"] = seed == NO_DIPOLE_SEED
+    if seed in SINGLE_FLAG_SEEDS:
+        c["flags"] = {k: k == QUADRUPOLE_FLAGS[SINGLE_FLAG_SEEDS.index(seed)] for k in QUADRUPOLE_FLAGS}
+    else:
+        c["flags"] = {k: bool(g.integers(2)) for k in QUADRUPOLE_FLAGS}
+    c["zero"] = seed in ZERO_MULTIPOLE_SEEDS
+    c["qd"] = _quadrupoles(g, n, c["zero"])
+    c["order"] = PMEQ_ORDERS[(seed // 2) % 2]
+    c["mesh"] = tuple(int(v) for v in g.choice(mesh_choices(c["order"]), 3))
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def _pmeq_pool(order):
+    """`_spread_pool` with quadrupoles: 33 atoms in the triclinic cell of tests/test_pme_quadrupole_gpu.py, fractional coordinates in
+    [-0.2, 1.2]; charges, dipoles, quadrupoles and weights."""
+    g = np.random.default_rng(PMEQ_POOL_SEED + order)
+    cell = np.array([[8.0, 0.0, 0.0], [0.7, 8.8, 0.0], [-0.4, 0.5, 7.2]])
+    n = PG_ATOMS + 1
+    return dict(pos=g.uniform(-0.2, 1.2, (n, 3)) @ cell, cells=cell[None], q=g.normal(size=n) + 0.05, mu=0.5 * g.normal(size=(n, 3)) / np.sqrt(3.0),
+                qd=_quadrupoles(g, n), weights=g.uniform(0.2, 1.8, n))
+
+
+def _pmeq_one(pos, q, mu, qd, weights, cells, order, mesh, alpha=0.35):
+    n = len(pos)
+    return dict(op="pme_quadrupole", dtype=None, sizes=(n,), pos=pos, cells=cells, batch_idx=np.zeros(n, np.int32), q=q, mu=mu, qd=qd, zero=False,
+                zero_dipoles=False, no_dipoles=False, alpha=np.array([alpha]), weights=weights, perm=None, empty_system=None, order=order, mesh=tuple(mesh))
+
+
+@functools.lru_cache(maxsize=None)
+def pmeq_spread_case(order, n):
+    """The first n atoms of the order's pool on `SPREAD_MESH`: blocks of `pme_quadrupole_spread_kernel` (256 // order^2 atoms: 10 and 7) and of
+    `pme_quadrupole_gather_kernel` (32) one atom short of full, full, one atom into the next, two blocks; and one atom as a call of its own.
+    RUNG 1: one atom among its own images feels no net force and no net field but for the mesh's own anisotropy: forces and dipole_grads
+    are what is left of terms that cancel, and the restatement's float32 mode deviates from its float64 mode there by 5e-5 - 7.5e-3 of the
+    output's maximum (this pool: forces 7.3e-5 / 8.9e-4, dipole_grads 5.4e-5 / 7.5e-3 at orders 5 / 6; above the cap in every draw tried).
+    In float32 these two outputs -- `PMEQ_LONE_ATOM_EXEMPT`, forward and weighted backward -- are only required to be finite.  Energies,
+    charge_grads, quadrupole_grads and virial of the lone atom are within the cap on this pool (4e-7 - 3e-6) and are held to the float32
+    bar like every other rung; in float64 all six outputs are."""
+    p = _pmeq_pool(order)
+    return _pmeq_one(p["pos"][:n], p["q"][:n], p["mu"][:n], p["qd"][:n], p["weights"][:n], p["cells"], order, SPREAD_MESH)
+
+
+def _f32(a):
+    return np.asarray(a, np.float32).astype(np.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def pmeq_knot_case(order, mesh):
+    """12 atoms in the cubic cell of edge 8 whose MESH coordinates u = n x / 8 sit on spline knots: integers for the first six atoms (at
+    order 6 theta = 0 and one stencil point at u = 0), integers + 1/2 for the last six (at order 5 theta - 3/2 = -1 exactly), drawn from
+    [-3, n + 3].  Atom 0 is at (0, 0, 0), atom 1 at (nx, ny, nz) (base = n, wrapped), atom 2 at (-1, ny, 1/2); atoms 3, 6 and 7 have one
+    generic axis each (x, y, z).  Every position is a float32 number, so both dtypes see the same inputs; on an axis of 8 or 16 points the mesh
+    coordinate is then exact in both dtypes, on the axes of 5 and 6 points it is a knot up to the rounding of x (|du| <= 4e-7), on either
+    side of it.  The restatement is continuous there (the CPU suite measures by how much +-1e-7 moves it), so it is a valid yardstick."""
+    g = np.random.default_rng(PMEQ_KNOT_SEED + 10 * order + mesh[0])
+    dims = np.array(mesh)
+    u = np.stack([g.integers(-3, dims + 4) for _ in range(12)]).astype(np.float64)
+    u[6:] = np.stack([g.integers(-3, dims + 3) for _ in range(6)]) + 0.5
+    u[0], u[1], u[2] = 0.0, dims, (-1.0, mesh[1], 0.5)
+    for atom, axis in ((3, 0), (6, 1), (7, 2)):
+        u[atom, axis] = g.uniform(-3.0, mesh[axis] + 3.0)
+    pos = _f32(u / dims * 8.0)
+    c = _pmeq_one(pos, _f32(g.normal(size=12) + 0.05), _f32(0.5 * g.normal(size=(12, 3)) / np.sqrt(3.0)), _f32(_quadrupoles(g, 12)),
+                  _f32(g.uniform(0.2, 1.8, 12)), (np.eye(3) * 8.0)[None], order, mesh)
+    c["mesh_coordinates"] = u
+    return c
+
+
+def pmeq_translated(c):
+    """The knot case with three atoms moved by whole lattice vectors (`PMEQ_KNOT_SHIFTS`): the same periodic system."""
+    pos = c["pos"].copy()
+    for atom, axis, cells in PMEQ_KNOT_SHIFTS:
+        pos[atom] += cells * c["cells"][0][axis]
+    return dict(c, pos=pos)
+
+
+@functools.lru_cache(maxsize=None)
+def pmeq_big_mesh_case():
+    """The atoms of `dipole_big_mesh_case()` with quadrupoles on mesh (40, 36, 96), order 5: 70 560 half-spectrum points, the second trip of
+    `pme_quadrupole_virial_kernel`'s grid-stride loop.  Float64 only: the restatement's float32 mode deviates by 4.6e-4 in the forces and
+    1.3e-4 in the virial on this mesh (the factor n^3 of the third derivative); four times that is no bar."""
+    c = dipole_big_mesh_case()
+    n = len(c["pos"])
+    return _pmeq_one(c["pos"], c["q"], c["mu"], _quadrupoles(np.random.default_rng(8950), n), c["weights"], c["cells"], 5, BIG_MESH, alpha=float(c["alpha"][0]))
+
+
+def pmeq_case(kind, key=None):
+    """kind: "sweep" (key: seed), "spread" (key: (order, n)), "knots" (key: (order, mesh)), "big"."""
+    return {"sweep": _pmeq_sweep, "spread": lambda k: pmeq_spread_case(*k), "knots": lambda k: pmeq_knot_case(*k), "big": lambda _: pmeq_big_mesh_case()}[kind](key)
+
+
+def pmeq_tensors(c, dtype=torch.float64):
+    """(pos, q, mu, qd, cells, alpha, batch_idx | None) of a case as CPU tensors; batch_idx None for one system."""
+    pos, q, mu, cells, alpha, bi = dipole_tensors(c, dtype)
+    return pos, q, mu, torch.as_tensor(np.ascontiguousarray(c["qd"]), dtype=dtype), cells, alpha, bi
+
+
+def pmeq_evaluate(c, mode="float64", weighted=False):
+    from tests import pme_quadrupole_reference as QR
+
+    pos, q, mu, qd, cells, alpha, bi = pmeq_tensors(c)
+    return QR.evaluate(pos, q, mu, qd, cells, alpha if bi is not None else float(alpha[0]), c["mesh"], c["order"], batch_idx=bi,
+                       weights=torch.as_tensor(c["weights"]) if weighted else None, dtype=torch.float64 if mode == "float64" else torch.float32,
+                       virial=not weighted)
+
+
+@functools.lru_cache(maxsize=None)
+def pme_quadrupole_reference(kind, key, mode="float64", weighted=False):
+    """`pme_quadrupole_reference.evaluate` on the case's mesh and order, in its float64 or its float32 mode; `weighted`: the derivatives are
+    those of L = sum_i w_i E_i with the case's weights (and no virial), else of the total energy."""
+    return pmeq_evaluate(pmeq_case(kind, key), mode, weighted)
+
+
+def pmeq_float32_deviation(kind, key, weighted=False):
+    """Per output: max |float32 mode - float64 mode| / max |float64 mode| of the restatement: a quarter of the float32 bar of the GPU test."""
+    r64, r32 = pme_quadrupole_reference(kind, key, "float64", weighted), pme_quadrupole_reference(kind, key, "float32", weighted)
+    return {k: float(np.abs(r32[k] - r64[k]).max() / np.abs(r64[k]).max()) for k in r64 if np.abs(r64[k]).max() > 0}
+
+
+def pmeq_plane_virial(kind, key):
+    """Per system [B, 3, 3]: what the plane k = (nz - 1) / 2 of the half spectrum of an odd-nz mesh adds to the k-space virial of the cross
+    spectrum for one unit of its Hermitian weight (`pme_quadrupole_reference.half_spectrum_plane_virial`)."""
+    from tests import pme_quadrupole_reference as QR
+
+    c = pmeq_case(kind, key)
+    assert c["mesh"][2] % 2 == 1
+    pos, q, mu, qd, cells, alpha, bi = pmeq_tensors(c)
+    sys_of = torch.zeros(len(pos), dtype=torch.long) if bi is None else bi.long()
+    out = np.zeros((len(cells), 3, 3))
+    for s, cell in enumerate(cells):
+        own = torch.nonzero(sys_of == s).reshape(-1)
+        if own.numel():
+            out[s] = QR.half_spectrum_plane_virial(pos[own], q[own], mu[own], qd[own], cell, alpha[s], c["mesh"], c["order"], c["mesh"][2] // 2)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def pmeq_convergence():
+    """Per output: the relative difference (max |difference| / max |explicit|) between the restatement of the mesh term at order 6 on 32^3
+    and the explicit reciprocal sum of tests/quadrupole_reference.py on the converged k set (cutoff 4.5: exp(-k^2 / 4 alpha^2) = 1e-18), both
+    on the 37-atom system of tests/test_pme_quadrupole_gpu.py.  Ten times these are the bars of
+    tests/test_sweep_pme_quadrupole_gpu.py::test_mesh_term_converges_to_the_explicit_sum_in_every_output: numbers of the two restatements."""
+    from nvalchemiops.interactions.electrostatics import generate_k_vectors_ewald_summation
+    from tests import pme_quadrupole_reference as QR
+    from tests import quadrupole_reference as XR
+    from tests import test_pme_quadrupole_gpu as TPQ
+
+    t = lambda a: torch.tensor(a, dtype=torch.float64)  # noqa: E731
+    pos, q, mu, qd = (t(a) for a in TPQ._system())
+    cell = t(TPQ.CELL).reshape(1, 3, 3)
+    mesh = QR.evaluate(pos, q, mu, qd, cell, TPQ.ALPHA, (32, 32, 32), 6)
+    explicit = XR.evaluate(pos, q, mu, qd, cell, t([TPQ.ALPHA]), None, generate_k_vectors_ewald_summation(cell[0], 4.5))
+    return {k: float(np.abs(mesh[k] - explicit[k]).max() / np.abs(explicit[k]).max()) for k in QUADRUPOLE_NAMES}
+
+
+@functools.lru_cache(maxsize=None)
+def pmeq_batch_seed():
+    """The first seed with three systems with atoms, quadrupoles and dipoles, not interleaved: the batch of
+    test_batch_systems_equal_single_calls_forward_and_backward, which runs in both dtypes."""
+    for s in SEEDS:
+        c = _pmeq_sweep(s)
+        if len(c["sizes"]) == 3 and min(c["sizes"]) > 0 and not c["zero"] and not c["no_dipoles"] and c["perm"] is None:
+            return s
+    raise AssertionError("no seed with three systems with atoms")

@@ -77,7 +77,13 @@ counts), and so did the "pme" solves, whose bar is twice `_check_solution`'s bou
 (the four solves are float64 only), four grad-output layouts each, every gradient bit-identical to the contiguous backward.  With the
 `.contiguous()` of `quadrupoles` taken out of the real-space launch (a patched `launch_inputs`, not committed) the col, row and T variants
 of `ewald_quadrupole_real_space` and `ewald_quadrupole_correction` fail in every sweep; F does not and cannot: it hands the kernel Q
-transposed, and 1/2 (Q + Q^T) is what the kernel uses.  DESIGN.md section 3.25."""
+transposed, and 1/2 (Q + Q^T) is what the kernel uses.  DESIGN.md section 3.25.
+
+Point quadrupoles on the mesh (fixture `pme_quadrupole`: the quadrupole fixture on mesh (12, 10, 14) at order 6; variants run, single system /
+batch, in float32 and in float64 alike): pme_quadrupole_reciprocal_space 26 (+ 4 forms with a [3, 3] cell, a 0-d alpha and a Python number) /
+33, pme_quadrupole_correction 36 (matrix) + 40 (CSR) (+ 2) / 43 + 45: 446 variants and 12 forms.  In float32 every variant gave the BITS of the
+canonical call (the spread adds in float64 and rounds once); in float64 they stayed within 0.0034 of the 1e-12 bar of two runs.  Gradient
+layouts of both entry points: bit-identical in float32, within that bar in float64.  DESIGN.md section 3.28."""
 import functools
 import re
 import types
@@ -1234,6 +1240,53 @@ def test_point_quadrupole_operators(dtype, batch):
 @DTYPES
 @pytest.mark.parametrize("batch", [False, True])
 @_collecting
+def test_pme_quadrupole_operators(dtype, batch):
+    """`pme_quadrupole_reciprocal_space` and `pme_quadrupole_correction` (matrix and CSR lists) on the fixture `pme_quadrupole` of
+    tests/layout_cases.py (mesh (12, 10, 14), order 6), all six outputs.  The canonical call of the mesh half against the restatement at the
+    bars of tests/test_pme_quadrupole_gpu.py (1e-10 of max |ref| in float64, 4 x the restatement's float32-mode deviation in float32), the
+    canonical correction against real-space half + mesh half.  Variants: in float32 the BITS of the canonical call (the spread adds in float64
+    and rounds once; every fixture value is a float32 number), in float64 the 1e-12 bar of two runs (float64 atomic adds in the spread).
+    On the single system also the forms no plan holds: a [3, 3] cell, alpha as a 0-d tensor and as a Python number; [B] alpha and an int64
+    `batch_idx` are in the plans."""
+    from nvalchemiops.interactions.electrostatics import ewald_quadrupole_real_space, pme_quadrupole_correction, pme_quadrupole_reciprocal_space
+
+    f = _mfx(dtype, batch)
+    mesh = dict(mesh_dimensions=LC.DP_MESH, spline_order=LC.PQ_ORDER)
+    close = _exact if dtype == "float32" else _close_two_runs(1e-12)
+    tag = f"{dtype}{' batch' if batch else ''}"
+    atoms = dict(positions=f.P, charges=f.Q, dipoles=f.MU, quadrupoles=f.QD, cell=f.C, alpha=f.AL)
+    aplan = dict(positions=POS, charges=VEC, dipoles=DIP, quadrupoles=QUAD, cell=CELLB if batch else CELL1, alpha=VEC)
+    if batch:
+        atoms["batch_idx"], aplan["batch_idx"] = f.BI, IDX
+    shared = ("cell", "alpha") if batch else ()
+    r64, r32 = LC.pme_quadrupole_references(batch)
+    call = lambda **a: pme_quadrupole_reciprocal_space(**a, **mesh, **TQD.ALL)  # noqa: E731
+    rec = _tuple(call(**atoms))
+    assert len(rec) == 6
+    for name, o in zip(LC.QD_NAMES, rec):
+        assert o.dtype == f.tdtype
+        rel = 1e-10 if dtype == "float64" else 4.0 * float(np.abs(r32[name] - r64[name]).max() / np.abs(r64[name]).max())
+        TPD._close(o.reshape(r64[name].shape), r64[name], f"pme_quadrupole_reciprocal_space {tag} {name} vs the restatement", rel)
+    _swept(f"pme_quadrupole_reciprocal_space {tag}", call, atoms, aplan, close, ref=rec, shared=shared)
+    if not batch:
+        for what, form in (("cell:[3, 3]", dict(cell=f.C[0])), ("alpha:0-d", dict(alpha=f.AL[0])), ("alpha:number", dict(alpha=float(f.AL[0]))),
+                           ("cell:[3, 3] alpha:number", dict(cell=f.C[0], alpha=float(f.AL[0])))):
+            _compare(_tuple(call(**dict(atoms, **form))), rec, close, f"pme_quadrupole_reciprocal_space[{what}]")
+    for label, lists, lplan in _list_forms(f):
+        sh = shared if label == "matrix" else ()
+        real = _tuple(ewald_quadrupole_real_space(**atoms, **lists, **TQD.ALL))
+        call = lambda **a: pme_quadrupole_correction(**a, **mesh, **TQD.ALL)  # noqa: E731
+        ref = _tuple(call(**atoms, **lists))
+        for i, name in enumerate(LC.QD_NAMES):  # the real-space half has its own sweep and restatement above: the sum of the two canonical calls
+            close(ref[i], (real[i] + rec[i]).cpu().numpy(), f"pme_quadrupole_correction {tag} {label} {name} vs real space + mesh", i)
+        _swept(f"pme_quadrupole_correction {tag} {label}", call, dict(atoms, **lists), dict(aplan, **lplan), close, ref=ref, shared=sh)
+        if not batch:
+            _compare(_tuple(call(**dict(atoms, cell=f.C[0], alpha=float(f.AL[0])), **lists)), ref, close, f"pme_quadrupole_correction {label}[cell:[3, 3] alpha:number]")
+
+
+@DTYPES
+@pytest.mark.parametrize("batch", [False, True])
+@_collecting
 def test_thole_dipole_correction(dtype, batch):
     """All six outputs; `polarizability` gets the plan of `sigma`.  One kernel, no atomics: every variant gives the bits of the canonical call,
     and a Python number gives the bits of a constant tensor."""
@@ -1572,9 +1625,16 @@ def test_gradient_layouts_of_the_quadrupole_thole_and_induced_dipole_ops(dtype):
     dipoles and quadrupoles, `thole_dipole_correction` with respect to positions, charges, dipoles and polarizability -- on the single system
     and the batch -- and the dipoles of `induced_dipoles` / `thole_induced_dipoles` (reciprocal="ewald", float64 only) with respect to
     positions, charges, polarizability and the external field.  The adjoints are the forward kernels with weights; the backward of the solve
-    is one more solve with the stored operator and two calls of the public energy functions: no atomics anywhere, equal bits."""
+    is one more solve with the stored operator and two calls of the public energy functions: no atomics anywhere, equal bits.  And
+    `pme_quadrupole_reciprocal_space` / `pme_quadrupole_correction` (mesh (12, 10, 14), order 6) with respect to positions, charges, dipoles
+    and quadrupoles: the four-mesh adjoint adds with float64 atomics in the spread, so equal bits in float32 (rounded once) and the bar of
+    two runs, 1e-12 of the largest component, in float64."""
     from nvalchemiops.interactions.electrostatics import (ewald_quadrupole_correction, ewald_quadrupole_reciprocal_space, induced_dipoles,
-                                                          thole_dipole_correction, thole_induced_dipoles)
+                                                          pme_quadrupole_correction, pme_quadrupole_reciprocal_space, thole_dipole_correction,
+                                                          thole_induced_dipoles)
+
+    mesh = dict(mesh_dimensions=LC.DP_MESH, spline_order=LC.PQ_ORDER)
+    mesh_close = _exact if dtype == "float32" else _close_two_runs(1e-12)
 
     ops = {}
     for batch in (False, True):
@@ -1590,6 +1650,11 @@ def test_gradient_layouts_of_the_quadrupole_thole_and_induced_dipole_ops(dtype):
                 (f.P, f.Q, f.MU, f.POL), ("positions", "charges", "dipoles", "polarizability"), _exact)
         ops[f"ewald_quadrupole_reciprocal_space{tag}"] = (
             lambda p, q, m, t, f=f, bkw=bkw: ewald_quadrupole_reciprocal_space(p, q, m, t, f.C, f.KV, f.AL, **bkw), leaves, names, _exact)
+        ops[f"pme_quadrupole_reciprocal_space{tag}"] = (
+            lambda p, q, m, t, f=f, bkw=bkw: pme_quadrupole_reciprocal_space(p, q, m, t, f.C, f.AL, **mesh, **bkw), leaves, names, mesh_close)
+        lists = _list_forms(f)[int(batch)][1]  # the matrix on the single system, CSR on the batch
+        ops[f"pme_quadrupole_correction{tag}"] = (
+            lambda p, q, m, t, f=f, bkw=bkw, lists=lists: pme_quadrupole_correction(p, q, m, t, f.C, f.AL, **mesh, **lists, **bkw), leaves, names, mesh_close)
         if dtype == "float64":
             g = _ifx(batch)
             gkw = dict(batch_idx=g.BI) if batch else {}
@@ -1600,7 +1665,8 @@ def test_gradient_layouts_of_the_quadrupole_thole_and_induced_dipole_ops(dtype):
                 lambda p, q, a, e, g=g, gkw=gkw, common=common: thole_induced_dipoles(p, q, a, g.C, thole=LC.THOLE, external_field=e, **common, **gkw),
                 (g.P, g.Q, g.dense[LC.THOLE]["polar"], g.F), ("positions", "charges", "polarizability", "external_field"), _exact)
     _check_gradient_layouts(ops)
-    print(f"[layouts] gradient layouts {dtype}: {len(ops)} ops x 4 grad-output layouts, every gradient bit-identical to the contiguous backward")
+    print(f"[layouts] gradient layouts {dtype}: {len(ops)} ops x 4 grad-output layouts, every gradient bit-identical to the contiguous backward"
+          + (" (the four mesh ops: within the bar of two runs)" if dtype == "float64" else ""))
 
 
 # ==== caller-owned output buffers =========================================================================================================

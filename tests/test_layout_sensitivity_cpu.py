@@ -214,3 +214,28 @@ def test_induced_fixtures_are_positive_definite_and_rolled_arguments_move_the_di
     print(f"[sensitivity induced {'batch' if batch else 'single'} {'thole' if damped else 'undamped'}] smallest eigenvalue of D^1/2 H D^1/2 per system "
           f"{[round(v, 3) for v in low]}; largest |moved - ref| / (2 x bound): " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
     assert all(v >= FACTOR for v in worst.values()), worst
+
+
+@pytest.mark.parametrize("batch", [False, True], ids=["single", "batch"])
+def test_pme_quadrupole_fixture_rolled_arguments_and_a_transposed_cell(batch):
+    """The widest bar the sweep applies to the canonical call of `pme_quadrupole_reciprocal_space`: 4 x the restatement's own
+    float32-against-float64 deviation (at most 1e-4 of max |ref|), mesh (12, 10, 14), order 6.  A rolled `positions`, `charges`, `dipoles`,
+    `quadrupoles`, (batch) `alpha` or `batch_idx`, or a transposed cell, must move the restatement by 100 bars.  A transposed `quadrupoles`
+    must NOT move it: 1/2 (Q + Q^T) is what counts, so a variant that hands the kernel Q^T agrees by construction (the `F` variant of the
+    sweep), and only one read with a wrong stride differs.  Measured (single / batch): positions 3.2e5 / 3.9e5, charges 2.3e5 / 2.5e5,
+    dipoles 1.8e5 / 2.4e5, quadrupoles 3.0e5 / 3.2e5, cell 2.3e5 / 2.4e5, alpha (batch) 6.0e4, batch_idx (batch) 1.3e5."""
+    c = L.pme_quadrupole(batch)
+    ref, r32 = L.pme_quadrupole_references(batch)
+    bars = {k: 4.0 * np.abs(r32[k] - ref[k]).max() for k in L.QD_NAMES}
+    assert all(0.0 < bars[k] <= 1e-4 * np.abs(ref[k]).max() for k in L.QD_NAMES), {k: bars[k] / np.abs(ref[k]).max() for k in L.QD_NAMES}
+    assert np.abs(c["qd"] - c["qd"].transpose(0, 2, 1)).max() > 1e-3 and np.abs(c["cell"] - c["cell"].transpose(0, 2, 1)).max() > 1.0
+    flipped = L.pme_quadrupole_reference(batch, qd=np.ascontiguousarray(c["qd"].transpose(0, 2, 1)))
+    assert all(_ratio(flipped[k], ref[k], bars[k]) <= 1e-3 for k in L.QD_NAMES), "Q transposed: the same symmetric part"
+    worst = {}
+    for arg in ("pos", "q", "mu", "qd") + (("alpha", "batch_idx") if batch else ()):
+        moved = L.pme_quadrupole_reference(batch, **{arg: _roll(c[arg])})
+        worst[arg] = max(_ratio(moved[k], ref[k], bars[k]) for k in L.QD_NAMES)
+    moved = L.pme_quadrupole_reference(batch, cell=np.ascontiguousarray(c["cell"].transpose(0, 2, 1)))
+    worst["cell transposed"] = max(_ratio(moved[k], ref[k], bars[k]) for k in L.QD_NAMES)
+    print(f"[sensitivity pme_quadrupole {'batch' if batch else 'single'}] largest |moved - ref| / bar: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+    assert all(v >= FACTOR for v in worst.values()), worst

@@ -10,7 +10,7 @@ Shapes: the 37-atom triclinic system of tests/test_pme_dipole_gpu.py (same const
 periodic face; at order 5 a spread block holds 10 atoms and at order 6 it holds 7 with idle threads, both with a partial last block; the
 gather's 8-lane groups do not fill a wave) with Q = 0.3 normal, four of them unsymmetric, one atom without a dipole and three without a
 quadrupole.  Meshes: (12, 10, 16) takes the fused solve, (14, 12, 16) the FFT plans, (12, 10, 15) has an odd axis without a Nyquist plane,
-and (5, 6, 7) at order 5 has an axis equal to the order, so that the stencil wraps onto the whole axis.  A batch of 7 + 1 + 12 atoms with
+and (5, 6, 7) at order 5 and (6, 7, 8) at order 6 have an axis equal to the order, so that the stencil wraps onto the whole axis.  A batch of 7 + 1 + 12 atoms with
 different cells and per-system alpha.
 
 The fp64 parity cases and the weighted-loss case run a second time on poisoned scratch (tests/poison.py): a mesh or a partial table that a
@@ -32,7 +32,8 @@ ALL = dict(compute_forces=True, compute_charge_gradients=True, compute_dipole_gr
 CELL = np.array([[8.0, 0.0, 0.0], [0.7, 8.8, 0.0], [-0.4, 0.5, 7.2]])
 ALPHA = 0.35
 MESH, MESH_PLAN, MESH_ODD, MESH_WRAP = (12, 10, 16), (14, 12, 16), (12, 10, 15), (5, 6, 7)
-CASES = [(order, dims) for dims in (MESH, MESH_PLAN, MESH_ODD) for order in (5, 6)] + [(5, MESH_WRAP)]
+MESH_WRAP6 = (6, 7, 8)
+CASES = [(order, dims) for dims in (MESH, MESH_PLAN, MESH_ODD) for order in (5, 6)] + [(5, MESH_WRAP), (6, MESH_WRAP6)]
 N = 37
 
 

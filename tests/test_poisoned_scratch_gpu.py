@@ -20,7 +20,9 @@ TEST allocates with `torch.zeros` (`test_qeq_gpu.py::test_coefficients_and_produ
 `test_fold_sizes_gpu.py::test_induced_dot_and_apply_partials_beyond_one_trip`); the same kernels run on the package's own `torch.empty`
 blocks in the solve tests below.  `test_dense_row_needs_more_than_one_lds_tile` of the two D3 three-body modules is left out for its time
 (9 - 11 s, nearly all of it the reference on the CPU); `test_row_of_three_lds_tiles_runs_every_tile_pair_once` takes the same multi-tile path
-in 3 s.  A device error ends the session (tests/poison.py `device_guard`)."""
+in 3 s.  Of tests/test_sweep_pme_quadrupole_gpu.py the sweep, the knot cases, the batch test and the ladder rungs 1, apb + 1 and 33 of each
+order are here (the four-mesh memset of the adjoint and its `accumulate` launch run in each): every one makes poisoned allocations and
+none left the list; the restatements of the sweep seeds are evaluated by a module-scoped fixture before the poison starts.  A device error ends the session (tests/poison.py `device_guard`)."""
 import types
 
 import pytest
@@ -51,6 +53,7 @@ from tests import test_quadrupole_gpu as TQD
 from tests import test_search_cn_gpu as TS
 from tests import test_spline_channels_gpu as TCH
 from tests import test_sweep_multipoles_gpu as TSM
+from tests import test_sweep_pme_quadrupole_gpu as TSQ
 from tests import test_thole_gpu as TTH
 from tests.test_search_cn_gpu import engine  # noqa: F401  (requested by name; tests/test_packed_companion_gpu.py has the same fixture)
 
@@ -253,6 +256,30 @@ _take("quadrupole", TQD, """parity_fp64_matrix_and_csr parity_fp32_inputs self_i
       row_length_ladder k_count_ladder empty_k_set_is_the_self_term_alone batch_equals_single_calls_and_reference
       autograd_matches_reference_and_explicit_outputs autograd_fp32_only_quadrupoles_and_batch
       virial_is_the_strain_derivative_and_not_symmetric""")
+
+# the quadrupole mesh term: the four-mesh memset of the adjoint (`weights ? 4 : 2`) and its `accumulate` launch run in every one of these
+@pytest.fixture(scope="module")
+def pme_quadrupole_references():
+    """The restatements of the sweep seeds, evaluated BEFORE the poison starts (a module-scoped fixture is set up before the autouse one): on
+    poisoned CPU allocations an evaluation takes twice as long -- the float32 seeds 3, 7, 9 and 11 took 5.1 - 7.5 s that way --, and the
+    references are the home module's, computed once for both (`functools.lru_cache`)."""
+    W = TSQ.W
+    for seed in W.SEEDS:
+        both = W.pmeq_case("sweep", seed)["dtype"] == "float32" or seed == W.pmeq_batch_seed()
+        for mode in ("float64", "float32") if both else ("float64",):
+            for weighted in (False, True):
+                W.pme_quadrupole_reference("sweep", seed, mode, weighted)
+
+
+_take("pme_quadrupole", TSQ, "atoms_on_spline_knots")
+_take("pme_quadrupole", TSQ, "sweep batch_systems_equal_single_calls_forward_and_backward", "pme_quadrupole_references")
+
+
+@pytest.mark.parametrize("dt", [TSQ.F64, TSQ.F32], ids=["float64", "float32"])
+@pytest.mark.parametrize("order,n", [(o, n) for o in TSQ.W.PMEQ_ORDERS for n in (1, TSQ.W.spread_atoms_per_block(o) + 1, TSQ.W.PG_ATOMS + 1)])
+def test_pme_quadrupole__spread_gather_ladder(order, n, dt):
+    TSQ.test_spread_gather_ladder(order, n, dt)
+
 
 # ---- nvalchemiops.math: the closed forms ----------------------------------------------------------------------------------------------------------
 

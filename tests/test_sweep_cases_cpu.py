@@ -643,3 +643,197 @@ def test_induced_idle_systems_case():
     assert ((i < 27) == (j < 27)).all() and (np.bincount(i, minlength=36)[27:] > 0).all(), "no entry joins two systems; the idle atoms do have neighbours"
     d = TC.dense(TC.lattice("l27"), None)
     assert float(torch.linalg.eigvalsh(d["H"]).min()) > 0 and float(d["b"].abs().max()) > 0, "system 0 has a solve to do"
+
+
+# ---- point quadrupoles on the mesh -------------------------------------------------------------------------------------------------------------
+# The conditions of the cases of tests/test_sweep_pme_quadrupole_gpu.py.  A seed is the dipole recipe under the operator's own BASE, so its
+# geometry is held to `_geometry_of_a_dipole_seed`.  MEASURED here: one evaluation of the restatement takes 0.3 - 1.6 s on a seed (the
+# seeds with 150-atom systems are the slow ones), below 0.2 s on a rung or a knot case, 1 s on the big mesh.
+
+PMEQ_FLOAT32_CAP = 2.5e-5  # of max |ref| per output: caps the float32 bar of the quadrupole mesh term on the device at 1e-4
+PMEQ_ZERO = ("energies", "forces", "charge_grads", "dipole_grads", "virial")
+
+
+def _pmeq_nontrivial(c, ref, what):
+    """Every compared output is non-trivial: max |.| > 0 for each, and in every system with quadrupoles on two atoms or more a virial whose
+    antisymmetric part is above 1e-6 of its norm (the mesh virial is NOT symmetric; a symmetrised one must fail); zero-quadrupole seeds:
+    exactly 0 everywhere but quadrupole_grads, which exceed 1e-3; a system without atoms has an exactly zero virial row."""
+    if c["zero"]:
+        assert all(not ref[k].any() for k in PMEQ_ZERO if k in ref), what
+        assert np.abs(ref["quadrupole_grads"]).max() > 1e-3, what
+        return
+    for k, v in ref.items():
+        assert np.abs(v).max() > 0.0, (what, k)
+    for s, v in enumerate(ref.get("virial", ())):
+        quadrupoles = int(c["qd"][c["batch_idx"] == s].any(axis=(1, 2)).sum())
+        if quadrupoles >= 2:
+            assert _antisymmetric(v) > 1e-6, (what, s)
+        elif quadrupoles == 0:
+            assert not v.any(), (what, s)
+
+
+def _pmeq_deviation(kind, key):
+    """The float32 mode against the float64 mode, forward and weighted backward, every output."""
+    return {**W.pmeq_float32_deviation(kind, key), **{"weighted " + k: v for k, v in W.pmeq_float32_deviation(kind, key, weighted=True).items() if k != "energies"}}
+
+
+@pytest.mark.parametrize("seed", W.SEEDS)
+def test_pme_quadrupole_seed_meets_its_conditions(seed):
+    base, c = W._dipole_sweep("pme_quadrupole", seed), W.pmeq_case("sweep", seed)
+    _geometry_of_a_dipole_seed(base, seed)
+    n = len(c["pos"])
+    for k in ("pos", "q", "batch_idx", "weights", "cells", "alpha"):
+        assert np.array_equal(c[k], base[k]), k
+    assert c["entries"] is base["entries"] and c["emptied_row"] == base["emptied_row"]
+    order, mesh = c["order"], c["mesh"]
+    assert order == W.PMEQ_ORDERS[(seed // 2) % 2] and set(mesh) <= set(W.mesh_choices(order)) and min(mesh) >= order
+    assert n * max(mesh) <= 10_000 and mesh[0] * mesh[1] * mesh[2] <= 4096, "cost: dense weights and one small mesh per system"
+    assert c["no_dipoles"] == (seed == W.NO_DIPOLE_SEED) == (not c["mu"].any())
+    if c["no_dipoles"]:
+        assert sum(s > 0 for s in c["sizes"]) >= 2, "dipoles=None in a batch of at least two systems with atoms"
+    else:
+        assert 1 <= int((~c["mu"].any(axis=1)).sum()) <= 3, "dipoles on every other seed, a few zero rows"
+    assert c["zero"] == (seed in W.ZERO_MULTIPOLE_SEEDS) == (not c["qd"].any()) and c["qd"].shape == (n, 3, 3) and set(c["flags"]) == set(W.QUADRUPOLE_FLAGS)
+    if seed in W.SINGLE_FLAG_SEEDS:
+        assert [k for k, v in c["flags"].items() if v] == [W.QUADRUPOLE_FLAGS[W.SINGLE_FLAG_SEEDS.index(seed)]]
+    if not c["zero"]:
+        assert 1 <= int((~c["qd"].any(axis=(1, 2))).sum()) <= 3, "a few atoms without a quadrupole"
+        assert n <= 6 or np.abs(c["qd"] - c["qd"].transpose(0, 2, 1)).max() > 1e-3, "a few unsymmetric rows"
+    t0 = time.perf_counter()
+    ref = W.pme_quadrupole_reference("sweep", seed)
+    took = time.perf_counter() - t0
+    _pmeq_nontrivial(c, ref, f"pme_quadrupole {seed}")
+    _pmeq_nontrivial(c, W.pme_quadrupole_reference("sweep", seed, "float64", True), f"pme_quadrupole {seed} weighted")
+    dev = _pmeq_deviation("sweep", seed)
+    print(f"pme_quadrupole {seed}: sizes {c['sizes']} {c['dtype']}, order {order} mesh {mesh}, flags {[k[8:] for k, v in c['flags'].items() if v]}, "
+          f"restatement {took:.2f} s, float32 mode against float64 mode: " + ", ".join(f"{k} {v:.1e}" for k, v in dev.items()))
+    if c["dtype"] == "float32" or seed == W.pmeq_batch_seed():
+        assert max(dev.values()) <= PMEQ_FLOAT32_CAP, dev
+    if mesh[2] % 2 == 1 and not c["zero"]:
+        # the plane k = (nz - 1) / 2 has Hermitian weight 2 on an odd axis; a kernel that gives it 1 must be seen by the virial comparison
+        plane = np.abs(W.pmeq_plane_virial("sweep", seed)).max() / np.abs(ref["virial"]).max()
+        print(f"pme_quadrupole {seed}: the last plane of the odd axis holds {plane:.2e} of max |virial|: {plane / 1e-10:.3g} float64 bars")
+        assert plane >= 100.0 * 1e-10, plane
+    if seed in W.INTERLEAVED_SEEDS:  # the restatement needs no contiguous systems
+        p = W.multipole_interleaved(c)
+        a = W.pmeq_evaluate(p)
+        assert np.abs(a["energies"] - ref["energies"][c["perm"]]).max() <= 1e-12 * np.abs(ref["energies"]).max()
+        assert np.abs(a["virial"] - ref["virial"]).max() <= 1e-12 * np.abs(ref["virial"]).max()
+
+
+def test_pme_quadrupole_seeds_cover_what_they_are_meant_to():
+    cases = [W.pmeq_case("sweep", s) for s in W.SEEDS]
+    assert all(c["dtype"] == ("float64", "float32")[c["seed"] % 2] for c in cases) and {len(c["sizes"]) for c in cases} == {1, 2, 3}
+    assert [c["order"] for c in cases] == [5, 5, 6, 6] * 3 and {(c["order"], c["dtype"]) for c in cases} == {(o, d) for o in (5, 6) for d in ("float32", "float64")}
+    assert sum(c["zero"] for c in cases) == 3 and {c["dtype"] for c in cases if c["zero"]} == {"float32", "float64"}
+    assert sum(c["perm"] is not None for c in cases) == 2 and sum(c["empty_system"] is not None for c in cases) == 2
+    assert all(c["dtype"] == "float64" and len(c["sizes"]) >= 2 for c in cases if c["perm"] is not None)
+    assert W.NO_DIPOLE_SEED in W.EMPTY_SYSTEM_SEEDS and sum(c["no_dipoles"] for c in cases) == 1
+    assert any(c["dtype"] == "float32" and sum(s > 0 for s in c["sizes"]) >= 2 for c in cases), "a float32 batch"
+    designated = set(W.ZERO_MULTIPOLE_SEEDS) | set(W.INTERLEAVED_SEEDS) | set(W.EMPTY_SYSTEM_SEEDS)
+    assert len(designated) == 7 and set(W.SINGLE_FLAG_SEEDS) == set(W.SEEDS) - designated
+    alone = [tuple(k for k, v in c["flags"].items() if v) for c in cases if not c["zero"]]
+    assert all((k,) in alone for k in W.QUADRUPOLE_FLAGS), "every flag alone at least once, on a seed with quadrupoles"
+    assert any(np.allclose(c["cells"][s], np.diag(np.diag(c["cells"][s]))) for c in cases for s in range(len(c["sizes"])))
+    assert any(c["cells"][s][1, 0] != 0 for c in cases for s in range(len(c["sizes"])))
+    odd = [c["seed"] for c in cases if c["mesh"][2] % 2 == 1]
+    equal = {o: [c["seed"] for c in cases if c["order"] == o and o in c["mesh"]] for o in W.PMEQ_ORDERS}
+    print(f"pme_quadrupole: odd nz in seeds {odd}, an axis equal to the order in seeds {equal}, meshes {[c['mesh'] for c in cases]}, batch seed {W.pmeq_batch_seed()}")
+    assert len(odd) >= 2 and sum(not cases[s]["zero"] for s in odd) >= 2, "odd nz on at least two seeds with quadrupoles (the Hermitian weight of the last plane)"
+    assert all(any(not cases[s]["zero"] for s in equal[o]) for o in W.PMEQ_ORDERS), "an axis equal to the order, for each order, on a seed with quadrupoles"
+    b = cases[W.pmeq_batch_seed()]
+    assert len(b["sizes"]) == 3 and min(b["sizes"]) > 0 and not b["zero"] and not b["no_dipoles"] and b["perm"] is None
+
+
+def test_pme_quadrupole_constants_are_the_kernels():
+    with open(os.path.join(CSRC, "pme.hip")) as f:
+        src = f.read()
+    assert re.search(r"pme_quadrupole_spread_kernel.*?constexpr int tpa = ORDER \* ORDER, apb = 256 / tpa;", src, re.S)
+    assert [W.spread_atoms_per_block(o) for o in W.PMEQ_ORDERS] == [10, 7]
+    assert W.pmeq_spread_rungs(5) == (1, 9, 10, 11, 20, 31, 32, 33) and W.pmeq_spread_rungs(6) == (1, 6, 7, 8, 14, 31, 32, 33)
+
+
+@pytest.mark.parametrize("order", W.PMEQ_ORDERS)
+def test_pme_quadrupole_ladder_and_big_mesh(order):
+    """The spread / gather ladder of this order and, at order 5, the big mesh: non-trivial, every rung within the float32 cap in every
+    output.  Rung 1 (`sweep_cases.pmeq_spread_case`): within the cap in energies, charge_grads, quadrupole_grads, virial and the weighted
+    charge and quadrupole gradients; forces and dipole_grads, forward and weighted, are the two exempt outputs, and each must really be over
+    the cap -- an exemption that the figures do not call for fails here."""
+    worst, lowest = 0.0, 1.0
+    for n in W.pmeq_spread_rungs(order):
+        c = W.pmeq_case("spread", (order, n))
+        assert len(c["pos"]) == n and c["mesh"] == W.SPREAD_MESH and c["order"] == order and c["qd"].shape == (n, 3, 3)
+        frac = c["pos"] @ np.linalg.inv(c["cells"][0])
+        assert frac.min() >= -0.2 and frac.max() <= 1.2 and (n < 9 or ((frac < 0).any() and (frac > 1).any())), "atoms outside the cell: stencils cross the faces"
+        t0 = time.perf_counter()
+        ref = W.pme_quadrupole_reference("spread", (order, n))
+        took = time.perf_counter() - t0
+        assert all(np.abs(v).max() > 0 for v in ref.values()) and (n == 1 or _antisymmetric(ref["virial"][0]) > 1e-6), n
+        dev = _pmeq_deviation("spread", (order, n))
+        print(f"order {order} N {n}: restatement {took:.2f} s, float32 mode against float64 mode " + ", ".join(f"{k} {v:.1e}" for k, v in dev.items()))
+        if n == 1:
+            exempt = {k: v for k, v in dev.items() if k.replace("weighted ", "") in W.PMEQ_LONE_ATOM_EXEMPT}
+            held = {k: v for k, v in dev.items() if k not in exempt}
+            assert c["qd"].any() and c["mu"].any() and len(exempt) == 4 and len(held) == 6
+            assert max(held.values()) <= PMEQ_FLOAT32_CAP, ("one atom alone: four outputs and their weighted gradients are within the cap", held)
+            assert min(exempt.values()) > PMEQ_FLOAT32_CAP, ("one atom alone: forces and dipole_grads are exempt because they are over the cap", exempt)
+            continue
+        worst, lowest = max(worst, max(dev.values())), min(lowest, min(dev.values()))
+        assert max(dev.values()) <= PMEQ_FLOAT32_CAP, (n, dev)
+    print(f"order {order}: float32 mode against float64 mode on the spread / gather ladder from 6 atoms on {lowest:.1e} to {worst:.1e}")
+    if order == 5:
+        c = W.pmeq_case("big")
+        assert c["mesh"] == W.BIG_MESH and len(c["pos"]) == 12 and c["order"] == 5 and np.array_equal(c["pos"], W.dipole_big_mesh_case()["pos"])
+        t0 = time.perf_counter()
+        ref = W.pme_quadrupole_reference("big", None)
+        print(f"big mesh {W.BIG_MESH}: restatement {time.perf_counter() - t0:.2f} s")
+        assert all(np.abs(v).max() > 0 for v in ref.values()) and _antisymmetric(ref["virial"][0]) > 1e-6
+
+
+@pytest.mark.parametrize("order,mesh", W.PMEQ_KNOT_CASES)
+def test_pme_quadrupole_knot_case(order, mesh):
+    """The construction (which atoms sit on which knots), the float32 cap, and that the restatement is CONTINUOUS across the knots: moving
+    every atom by +1e-7 or by -1e-7 along (1, 1, 1) moves every output by a small amount (measured: at most 5.3e-8 of its maximum) that
+    shrinks tenfold with the displacement, and is the same for both signs wherever the output is differentiable at the knot (a jump at a knot
+    would show as a move that does not shrink)."""
+    c = W.pmeq_case("knots", (order, mesh))
+    u, dims = c["mesh_coordinates"], np.array(mesh)
+    assert np.array_equal(c["cells"][0], np.eye(3) * 8.0) and len(c["pos"]) == 12 and np.array_equal(c["pos"], c["pos"].astype(np.float32).astype(np.float64))
+    assert u.min() >= -3.0 and (u <= dims + 3).all()
+    assert np.array_equal(u[0], np.zeros(3)) and np.array_equal(u[1], dims) and np.array_equal(u[2], (-1.0, mesh[1], 0.5))
+    generic = {(3, 0), (6, 1), (7, 2)}
+    for i in range(12):
+        for d in range(3):
+            if (i, d) in generic:
+                assert abs(2.0 * u[i, d] - round(2.0 * u[i, d])) > 1e-3, "a generic axis"
+            elif (i, d) != (2, 2):
+                assert (u[i, d] == np.floor(u[i, d])) if i < 6 else (u[i, d] - 0.5 == np.floor(u[i, d])), (i, d)
+    on_mesh = c["pos"] / 8.0 * dims  # what the kernels form, in float64
+    knots = np.array([[(i, d) not in generic for d in range(3)] for i in range(12)])
+    assert np.abs(on_mesh - u)[knots].max() <= 4e-7
+    for d in range(3):
+        if mesh[d] in (8, 16):
+            exact = [i for i in range(12) if (i, d) not in generic]
+            assert np.array_equal(on_mesh[exact, d], u[exact, d]), "on axes of 8 and 16 points the float32 position IS the knot"
+    moved = W.pmeq_translated(c)
+    assert np.array_equal(moved["pos"], moved["pos"].astype(np.float32).astype(np.float64)) and np.abs(moved["pos"] - c["pos"]).max() == 24.0
+    ref = W.pme_quadrupole_reference("knots", (order, mesh))
+    assert all(np.abs(v).max() > 0 and np.isfinite(v).all() for v in ref.values())
+    dev = _pmeq_deviation("knots", (order, mesh))
+    print(f"knots order {order} mesh {mesh}: float32 mode against float64 mode " + ", ".join(f"{k} {v:.1e}" for k, v in dev.items()))
+    assert max(dev.values()) <= PMEQ_FLOAT32_CAP, dev
+    moves = {h: [W.pmeq_evaluate(dict(c, pos=c["pos"] + s * h)) for s in (1.0, -1.0)] for h in (1e-7, 1e-8)}
+    for k, v in ref.items():
+        (a, b), (a8, b8) = ([np.abs(m[k] - v).max() / np.abs(v).max() for m in moves[h]] for h in (1e-7, 1e-8))
+        print(f"knots order {order} mesh {mesh}: {k:16s} moves by {a:.2e} (+1e-7) and {b:.2e} (-1e-7), by {a8:.2e} and {b8:.2e} (+-1e-8) of its maximum")
+        assert max(a, b) <= 1e-6 and max(a8, b8) <= 0.2 * max(a, b) + 1e-12, (k, "a jump at a knot does not shrink with the displacement")
+        if order == 6 or k not in ("forces", "virial"):  # (order 5: the fourth derivative of M_5 jumps at a knot, so the third derivatives have a kink there: continuous, two slopes)
+            assert abs(a - b) <= 0.05 * max(a, b) + 1e-12, (k, "the same move for both signs")
+
+
+def test_pme_quadrupole_convergence_bars():
+    """The per-output differences between the mesh restatement at order 6 on 32^3 and the explicit restatement on the converged k set, on
+    the 37-atom system: ten times these are the bars of test_mesh_term_converges_to_the_explicit_sum_in_every_output."""
+    d = W.pmeq_convergence()
+    print("pme_quadrupole, order 6 on 32^3 against the explicit sum: " + ", ".join(f"{k} {v:.2e}" for k, v in d.items()))
+    assert set(d) == set(W.QUADRUPOLE_NAMES) and all(0.0 < v < 1e-3 for v in d.values())
