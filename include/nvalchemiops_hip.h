@@ -619,6 +619,36 @@ int mi_thole_dipole(const void* positions, const void* charges, const void* dipo
                     int mask_value, int flags, double* energies, void* forces, double* charge_grads, double* dipole_grads,
                     double* polarizability_grads, double* virial_partial, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Cluster point multipoles: the bare (undamped, 1/r) multipole pair sums (csrc/dipole.hip and csrc/quadrupole.hip, one more radial kind of the
+ * pair kernels of mi_ewald_dipole_real / mi_ewald_quadrupole_real; driver: nvalchemiops/interactions/electrostatics/cluster.py).  The radial
+ * factors are the alpha -> 0 limit of the Ewald B_n:
+ *     B1 = 1 / r^3,  B_{n+1} = (2n + 1) B_n / r^2:  B2 = 3 / r^5,  B3 = 15 / r^7,  B4 = 105 / r^9,  B5 = 945 / r^11
+ * with no erfc and no exp.  Everything else -- the pair expressions U, dU/dR, dU/dq, dU/dmu, dU/dQ, arguments, weights (w = (g_i + g_j) / 2),
+ * flags (MI_DP_* / MI_QD_*), outputs, virial layout, list formats, padding, the r <= 1e-8 skip, kept self-image entries, the arithmetic model
+ * (pair vector and r^2 in the positions dtype, the rest fp64) and bit-reproducibility -- is that of mi_ewald_dipole_real and
+ * mi_ewald_quadrupole_real, without their alpha argument.
+ * mi_coulomb_dipole: the charge-dipole and dipole-dipole energy over the stored entries of a FULL list; added to a bare charge-charge sum.
+ * mi_coulomb_quadrupole: the terms with at least one quadrupole; added to mi_coulomb_dipole.
+ * cell may be NULL (a cluster: unit_shifts must be NULL too, no virial); with a cell and unit_shifts the sum runs over the listed images (a
+ * cut-off sum: the list is the cutoff).  An unknown flag bit is an argument error.
+ * scratch: mi_coulomb_dipole_scratch_bytes / mi_coulomb_quadrupole_scratch_bytes(n_atoms, dtype) bytes (records + per-row virials), contents
+ * undefined.  virial_partial is [n_systems][mi_coulomb_dipole_blocks() / mi_coulomb_quadrupole_blocks()][9]. */
+size_t mi_coulomb_dipole_scratch_bytes(int n_atoms, int dtype);
+int mi_coulomb_dipole_blocks(void);
+int mi_coulomb_dipole(const void* positions, const void* charges, const void* dipoles, const void* cell /*[n_systems,3,3] or NULL*/,
+                      const int32_t* batch_idx, const double* weights, int n_atoms, int n_systems, int dtype, const int32_t* idx_j,
+                      const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors, int mask_value, int flags, double* energies,
+                      void* forces, double* charge_grads, double* dipole_grads, double* virial_partial, void* scratch, size_t scratch_bytes,
+                      void* stream);
+size_t mi_coulomb_quadrupole_scratch_bytes(int n_atoms, int dtype);
+int mi_coulomb_quadrupole_blocks(void);
+int mi_coulomb_quadrupole(const void* positions, const void* charges, const void* dipoles, const void* quadrupoles,
+                          const void* cell /*[n_systems,3,3] or NULL*/, const int32_t* batch_idx, const double* weights, int n_atoms,
+                          int n_systems, int dtype, const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr,
+                          int max_neighbors, int mask_value, int flags, double* energies, void* forces, double* charge_grads,
+                          double* dipole_grads, double* quadrupole_grads, double* virial_partial, void* scratch, size_t scratch_bytes,
+                          void* stream);
+
 /* Charge equilibration (csrc/qeq.hip; driver: nvalchemiops/interactions/electrostatics/qeq.py): the real-space Hessian of the Gaussian-charge
  * electrostatic energy as a stored sparse operator over the caller's FULL list, its product, and the vector kernels of a batched projected
  * conjugate-gradient solve of  min_q sum chi_i q_i + 1/2 sum J_i q_i^2 + E_el(q),  sum_{i in s} q_i = Q_s.  All arithmetic is fp64; only the
@@ -681,6 +711,11 @@ int mi_qeq_cg_direction(const double* partial_rr, const int32_t* batch_idx, int 
  * mi_thole_induced_pair_tensors: the same with exponential Thole damping of width thole_a (> 0, finite): tensors[0][e] = B1 + D1,
  *   tensors[1][e] = B2 + D2 with the D_n and the E >= 50 exit of mi_thole_dipole, same streams and layout, so mi_induced_apply then gives
  *   diagonal x + dE/dmu of mi_ewald_dipole_real + mi_thole_dipole at zero charges.  Everything else in this section is used unchanged.
+ * mi_cluster_induced_pair_tensors: the operator of a cluster without a cell -- no cell, no alpha, no shifts, no batch_idx (the list confines
+ *   pairs to systems): tensors[0][e] = 1 / r^3, tensors[1][e] = 3 / r^5 (the alpha -> 0 limit of B1, B2) for thole_a == 0, and those plus
+ *   D1, D2 of mi_thole_dipole (with its E >= 50 exit) for a finite thole_a > 0; any other thole_a is an argument error.  Same streams, layout,
+ *   padding and non-polarisable rules, so mi_induced_apply then gives diagonal x + dE/dmu of mi_coulomb_dipole (+ mi_thole_dipole) at zero
+ *   charges, and the product and CG entry points of this section are used unchanged.
  * mi_induced_apply:  y[i] = (y_in ? y_in[i] : 0) + diagonal[i] x[i] + sum_{slots e of row i} (B1 x[j] - B2 (R . x[j]) R)   (one wave64 per row,
  *   mi_induced_unroll_depth() trips in flight; y_in is added as given; x, y_in and y must not overlap).
  *   partial (may be NULL): [n_systems][mi_induced_blocks()] block partials of sum_i x_i . y_i per system.  mi_induced_dot: those partials alone.
@@ -706,6 +741,9 @@ int mi_thole_induced_pair_tensors(const void* positions, const void* polarizabil
                                   const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors, int mask_value,
                                   long long n_slots, double* tensors, int32_t* neighbors, double* diagonal, double* preconditioner,
                                   double thole_a, void* stream);
+int mi_cluster_induced_pair_tensors(const void* positions, const void* polarizability, int n_atoms, int dtype, const int32_t* idx_j,
+                                    const int32_t* neighbor_ptr, int max_neighbors, int mask_value, long long n_slots, double* tensors,
+                                    int32_t* neighbors, double* diagonal, double* preconditioner, double thole_a, void* stream);
 int mi_induced_apply(const double* tensors, const int32_t* neighbors, const double* diagonal, const double* x, const double* y_in,
                      const int32_t* batch_idx, int n_atoms, int n_systems, const int32_t* neighbor_ptr, int max_neighbors, long long n_slots,
                      double* y, double* partial, void* stream);

@@ -23,6 +23,9 @@
 //
 // Every kernel is its own adjoint: with per-atom weights g (NULL: all ones) an entry weighs w = (g_i + g_j) / 2, the table is summed with
 // g_j on every atom, and the owner sums become the derivatives of L = sum_i g_i E_i (the contract of mi_gaussian_charges).
+//
+// The real-space pair kernel has two more radial kinds beside the Ewald one (below): Thole damping (mi_thole_dipole) and the bare 1 / r
+// interaction of clusters and cut-off sums (mi_coulomb_dipole: the alpha -> 0 limit, B1 = 1 / r^3, B_{n+1} = (2n + 1) B_n / r^2).
 #include "common.h"
 
 namespace {
@@ -62,12 +65,18 @@ __device__ __forceinline__ double dp_volume(const double* cm) {
 //       D1 = -e^-E / r^3,  D2 = -3 (1 + E) e^-E / r^5,  D3 = -15 (1 + E + 3/5 E^2) e^-E / r^7             (D_{n+1} = -(1/r) dD_n/dr, as for B_n)
 //     An entry with a_i <= 0 or a_j <= 0 (or NaN) is not damped, and one with E >= 50 leaves before the exp (its D_n are below 4e-19 of the
 //     undamped terms): both contribute exactly 0.  dL/da_i = -1 / (2 a_i) sum_row w E X,  X = dU/dE at fixed R = -D1 A - (3 E e^-E / r^5) c_i c_j.
+//   DpBare: the undamped 1/r interaction of a cluster or a cut-off sum, the alpha -> 0 limit of the B_n: B1 = 1 / r^3, B2 = 3 / r^5,
+//     B3 = 15 / r^7 (B_{n+1} = (2n + 1) B_n / r^2).  No erfc, no exp, no launch argument of its own (the word it carries is not read).
 template <class T> struct DpEwald {
-  static constexpr bool thole = false;
+  static constexpr bool thole = false, bare = false;
   const T* alpha;
 };
+template <class T> struct DpBare {
+  static constexpr bool thole = false, bare = true;
+  int unused;
+};
 template <class T> struct DpThole {
-  static constexpr bool thole = true;
+  static constexpr bool thole = true, bare = false;
   double width;
   double* __restrict__ pgrad;
 };
@@ -87,7 +96,7 @@ __global__ __launch_bounds__(256) void dp_pair_kernel(const DpRec<T>* __restrict
   T cm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (shifted) pair_row_cell(cell, s, cm);
   double al = 0.0, ta = 0.0, inv_a_sqrt_pi = 0.0;
-  if constexpr (!Radial::thole) {
+  if constexpr (!Radial::thole && !Radial::bare) {
     al = (double)rad.alpha[s];
     ta = 2.0 * al * al; inv_a_sqrt_pi = 1.0 / (al * 1.7724538509055159);
   }
@@ -121,7 +130,12 @@ __global__ __launch_bounds__(256) void dp_pair_kernel(const DpRec<T>* __restrict
     if (!(dist > 1e-8)) continue;           // (NaN distances leave here too)
     double rinv2, pre, b1, b2;
     double b3 = 0.0, xa = 0.0, xe = 0.0;  // DpThole: D3 and the two coefficients of E X = xa A - xe c_i c_j
-    if constexpr (!Radial::thole) {
+    if constexpr (Radial::bare) {
+      const double rinv = 1.0 / dist;
+      rinv2 = rinv * rinv; pre = 0.0;
+      b1 = rinv * rinv2;
+      b2 = 3.0 * b1 * rinv2;
+    } else if constexpr (!Radial::thole) {
       const double rinv = 1.0 / dist, ar = al * dist;
       rinv2 = rinv * rinv;
       pre = exp(-(ar * ar)) * inv_a_sqrt_pi;
@@ -155,7 +169,8 @@ __global__ __launch_bounds__(256) void dp_pair_kernel(const DpRec<T>* __restrict
     }
     if (wp) pacc += w * (xa * a - xe * cc);
     if (wf || wv) {
-      if constexpr (!Radial::thole) b3 = (5.0 * b2 + ta * ta * ta * pre) * rinv2;
+      if constexpr (Radial::bare) b3 = 5.0 * b2 * rinv2;
+      else if constexpr (!Radial::thole) b3 = (5.0 * b2 + ta * ta * ta * pre) * rinv2;
       const double cr = w * (b3 * cc - b2 * a), cmi = w * (b1 * qj - b2 * cj), cmj = -w * (b1 * qi + b2 * ci);
       const double ux = cr * rx + cmi * mix + cmj * mjx, uy = cr * ry + cmi * miy + cmj * mjy, uz = cr * rz + cmi * miz + cmj * mjz;
       fx += ux; fy += uy; fz += uz;
@@ -417,6 +432,55 @@ extern "C" int mi_thole_dipole(const void* positions, const void* charges, const
   else { if (neighbor_ptr) MI_TH(double, true); else MI_TH(double, false); }
   mi_timing_end(stream);
 #undef MI_TH
+  MI_LAUNCH_CHECK();
+  if (virial) {
+    dp_fold_kernel<<<dim3(MI_FOLD_BLOCKS, n_systems), 256, 0, st>>>(trow, bi, n_atoms, virial_partial);
+    MI_LAUNCH_CHECK();
+  }
+  return MI_OK;
+}
+
+extern "C" int mi_coulomb_dipole_blocks(void) { return MI_FOLD_BLOCKS; }
+extern "C" size_t mi_coulomb_dipole_scratch_bytes(int n_atoms, int dtype) { return mi_ewald_dipole_real_scratch_bytes(n_atoms, dtype); }
+
+extern "C" int mi_coulomb_dipole(const void* positions, const void* charges, const void* dipoles, const void* cell, const int32_t* batch_idx,
+                                 const double* weights, int n_atoms, int n_systems, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
+                                 const int32_t* neighbor_ptr, int max_neighbors, int mask_value, int flags, double* energies, void* forces,
+                                 double* charge_grads, double* dipole_grads, double* virial_partial, void* scratch, size_t scratch_bytes,
+                                 void* stream) {
+  MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
+  MI_REQUIRE(n_atoms >= 0, "n_atoms must not be negative");
+  MI_REQUIRE(n_systems >= 1 && n_systems <= 65535, "n_systems must be in [1, 65535]");
+  MI_REQUIRE(neighbor_ptr || max_neighbors >= 0, "max_neighbors must not be negative");
+  MI_REQUIRE(n_systems == 1 || batch_idx, "batch_idx is required for more than one system");
+  MI_REQUIRE(!(flags & ~(MI_DP_FORCES | MI_DP_CHARGE_GRAD | MI_DP_DIPOLE_GRAD | MI_DP_VIRIAL)), "unknown flag");
+  MI_REQUIRE(cell || !unit_shifts, "unit_shifts need a cell");
+  const bool virial = (flags & MI_DP_VIRIAL) != 0;
+  MI_REQUIRE(!virial || (unit_shifts && virial_partial), "the virial needs unit_shifts and virial_partial");
+  if (n_atoms == 0) return MI_OK;
+  MI_REQUIRE(positions && charges && dipoles && idx_j, "null pointer");
+  MI_REQUIRE(energies || flags, "nothing to compute");
+  MI_REQUIRE(!(flags & MI_DP_FORCES) || forces, "forces output");
+  MI_REQUIRE(!(flags & MI_DP_CHARGE_GRAD) || charge_grads, "charge gradient output");
+  MI_REQUIRE(!(flags & MI_DP_DIPOLE_GRAD) || dipole_grads, "dipole gradient output");
+  MI_REQUIRE(scratch && scratch_bytes >= mi_coulomb_dipole_scratch_bytes(n_atoms, dtype), "scratch smaller than mi_coulomb_dipole_scratch_bytes()");
+  hipStream_t st = (hipStream_t)stream;
+  double* trow = reinterpret_cast<double*>((char*)scratch + dp_rec_bytes(n_atoms, dtype));
+  const int blocks = mi_blocks(n_atoms, 256 / MI_WAVE);
+  const int32_t* bi = n_systems > 1 ? batch_idx : nullptr;
+#define MI_CD(T_, CSR_)                                                                                                                          \
+  do {                                                                                                                                           \
+    pair_pack_kernel<<<mi_blocks(n_atoms, 256), 256, 0, st>>>((const T_*)positions, (const T_*)charges, (const T_*)dipoles, n_atoms,             \
+                                                              (DpRec<T_>*)scratch);                                                              \
+    dp_pair_kernel<T_, CSR_, DpBare<T_>><<<blocks, 256, 0, st>>>((const DpRec<T_>*)scratch, (const T_*)cell, DpBare<T_>{0}, bi, weights,         \
+                                                                 n_atoms, idx_j, unit_shifts, neighbor_ptr, max_neighbors, mask_value, flags,    \
+                                                                 energies, (T_*)forces, charge_grads, dipole_grads, trow);                       \
+  } while (0)
+  mi_timing_begin("coulomb_dipole", stream);
+  if (dtype == MI_F32) { if (neighbor_ptr) MI_CD(float, true); else MI_CD(float, false); }
+  else { if (neighbor_ptr) MI_CD(double, true); else MI_CD(double, false); }
+  mi_timing_end(stream);
+#undef MI_CD
   MI_LAUNCH_CHECK();
   if (virial) {
     dp_fold_kernel<<<dim3(MI_FOLD_BLOCKS, n_systems), 256, 0, st>>>(trow, bi, n_atoms, virial_partial);

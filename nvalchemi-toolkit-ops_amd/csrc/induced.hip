@@ -22,6 +22,9 @@
 // x . y: mi_system_fold of pair_row.h) and the two vector kernels of a CG iteration.  Every reduction runs in a fixed order, every store is a
 // plain vector store, there are no atomics: these kernels are bit-reproducible.
 //
+// mi_cluster_induced_pair_tensors stores the operator of a cluster without a cell in the same layout: B1 = 1 / r^3, B2 = 3 / r^5 (the alpha -> 0
+// limit), optionally Thole-damped; product and CG kernels do not know the difference.
+//
 // The fold and CG kernels run on a grid (MI_FOLD_BLOCKS, n_systems), so n_systems <= 65535 (checked), and every block scans batch_idx once:
 // O(N n_systems) index reads per launch, as every mi_system_fold.
 #include "common.h"
@@ -36,7 +39,9 @@ namespace {
 
 // THOLE: the stored coefficients are B1 + D1 and B2 + D2 with the D_n of dp_pair_kernel's Thole kind (dipole.hip), E = thole_a r^3 / sqrt(a_i a_j)
 // and the same early exit at E >= 50, so sum_row T_e x_j is dE/dmu of mi_ewald_dipole_real + mi_thole_dipole for zero charges.
-template <class T, bool CSR, bool THOLE>
+// BARE: the undamped 1/r operator of a cluster, B1 = 1 / r^3 and B2 = 3 / r^5 (the alpha -> 0 limit; no erfc, no exp): cell, alpha, batch_idx and
+// ush are not read (NULL).  With THOLE the D_n are added as above, so sum_row T_e x_j is dE/dmu of mi_coulomb_dipole (+ mi_thole_dipole).
+template <class T, bool CSR, bool THOLE, bool BARE = false>
 __global__ __launch_bounds__(256) void ind_tensor_kernel(const T* __restrict__ pos, const T* __restrict__ polar, const T* __restrict__ cell,
                                                          const T* __restrict__ alpha, const int* __restrict__ batch_idx, int N,
                                                          const int* __restrict__ idx, const int* __restrict__ ush, const int* __restrict__ nptr,
@@ -49,8 +54,8 @@ __global__ __launch_bounds__(256) void ind_tensor_kernel(const T* __restrict__ p
   const bool shifted = ush != nullptr;
   T cm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (shifted) pair_row_cell(cell, s, cm);
-  const double al = (double)alpha[s];
-  const double ta = 2.0 * al * al, inv_a_sqrt_pi = 1.0 / (al * 1.7724538509055159);
+  const double al = BARE ? 0.0 : (double)alpha[s];
+  const double ta = 2.0 * al * al, inv_a_sqrt_pi = 1.0 / (al * 1.7724538509055159);  // (BARE: not used)
   const T pix = pos[3 * (size_t)i], piy = pos[3 * (size_t)i + 1], piz = pos[3 * (size_t)i + 2];
   const T ai = polar[i];
   const bool pol_i = ai > T(0);  // (NaN: not polarisable)
@@ -76,10 +81,15 @@ __global__ __launch_bounds__(256) void ind_tensor_kernel(const T* __restrict__ p
       const double dist = (double)sqrt(r2t);  // the distance is a quantity of the positions dtype
       if (dist > 1e-8) {                      // (NaN fails)
         const double rinv = 1.0 / dist, rinv2 = rinv * rinv, ar = al * dist;
-        const double pre = exp(-(ar * ar)) * inv_a_sqrt_pi;
-        const double b0 = erfc(ar) * rinv;
-        b1 = (b0 + ta * pre) * rinv2;
-        b2 = (3.0 * b1 + ta * ta * pre) * rinv2;
+        if constexpr (BARE) {
+          b1 = rinv * rinv2;
+          b2 = 3.0 * b1 * rinv2;
+        } else {
+          const double pre = exp(-(ar * ar)) * inv_a_sqrt_pi;
+          const double b0 = erfc(ar) * rinv;
+          b1 = (b0 + ta * pre) * rinv2;
+          b2 = (3.0 * b1 + ta * ta * pre) * rinv2;
+        }
         if constexpr (THOLE) {
           const double big = thole_a * (dist * dist * dist) / sqrt((double)ai * (double)aj);
           if (big < 50.0) {
@@ -324,6 +334,41 @@ extern "C" int mi_thole_induced_pair_tensors(const void* positions, const void* 
                                              double thole_a, void* stream) {
   return ind_pair_tensors(positions, polarizability, cell, alpha, batch_idx, n_atoms, n_systems, dtype, idx_j, unit_shifts, neighbor_ptr,
                           max_neighbors, mask_value, n_slots, tensors, neighbors, diagonal, preconditioner, true, thole_a, stream);
+}
+
+extern "C" int mi_cluster_induced_pair_tensors(const void* positions, const void* polarizability, int n_atoms, int dtype, const int32_t* idx_j,
+                                               const int32_t* neighbor_ptr, int max_neighbors, int mask_value, long long n_slots,
+                                               double* tensors, int32_t* neighbors, double* diagonal, double* preconditioner, double thole_a,
+                                               void* stream) {
+  MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
+  MI_REQUIRE(n_atoms >= 0, "n_atoms must not be negative");
+  MI_REQUIRE(neighbor_ptr || max_neighbors >= 0, "max_neighbors must not be negative");
+  MI_REQUIRE(n_slots >= 0, "n_slots must not be negative");
+  MI_REQUIRE(neighbor_ptr || n_slots == (long long)n_atoms * max_neighbors, "n_slots must be n_atoms * max_neighbors for a matrix");
+  MI_REQUIRE(thole_a >= 0.0 && thole_a < INFINITY, "thole_a must be 0 (undamped) or positive and finite");
+  if (n_atoms == 0) return MI_OK;
+  MI_REQUIRE(positions && polarizability && diagonal && preconditioner, "null pointer");
+  MI_REQUIRE(n_slots == 0 || (idx_j && tensors && neighbors), "null pointer");  // (a list may be empty)
+  hipStream_t st = (hipStream_t)stream;
+  const int blocks = mi_blocks(n_atoms, 256 / MI_WAVE);
+  const bool thole = thole_a > 0.0;
+#define MI_CT(T_, CSR_, THOLE_)                                                                                                                  \
+  ind_tensor_kernel<T_, CSR_, THOLE_, true><<<blocks, 256, 0, st>>>((const T_*)positions, (const T_*)polarizability, (const T_*)nullptr,         \
+                                                                    (const T_*)nullptr, nullptr, n_atoms, idx_j, nullptr, neighbor_ptr,          \
+                                                                    max_neighbors, mask_value, n_slots, tensors, neighbors, diagonal,            \
+                                                                    preconditioner, thole_a)
+#define MI_CT_LAYOUT(T_)                                                                                                                         \
+  do {                                                                                                                                           \
+    if (thole) { if (neighbor_ptr) MI_CT(T_, true, true); else MI_CT(T_, false, true); }                                                         \
+    else { if (neighbor_ptr) MI_CT(T_, true, false); else MI_CT(T_, false, false); }                                                             \
+  } while (0)
+  mi_timing_begin("cluster_induced_pair_tensors", stream);
+  if (dtype == MI_F32) MI_CT_LAYOUT(float); else MI_CT_LAYOUT(double);
+  mi_timing_end(stream);
+#undef MI_CT_LAYOUT
+#undef MI_CT
+  MI_LAUNCH_CHECK();
+  return MI_OK;
 }
 
 extern "C" int mi_induced_apply(const double* tensors, const int32_t* neighbors, const double* diagonal, const double* x, const double* y_in,

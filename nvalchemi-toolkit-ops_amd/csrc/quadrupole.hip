@@ -38,6 +38,9 @@
 //
 // Every kernel is its own adjoint under the contract of dipole.hip: with per-atom weights g (NULL: all ones) an entry weighs
 // w = (g_i + g_j) / 2, the table is summed with g_j on every atom, and the owner sums become the derivatives of L = sum_i g_i E_i.
+//
+// The real-space pair kernel has a second radial kind, the bare 1 / r interaction of clusters and cut-off sums (mi_coulomb_quadrupole: the
+// alpha -> 0 limit, B1 = 1 / r^3, B_{n+1} = (2n + 1) B_n / r^2, with C1 ... C4, dU/dR, dU/dq, dU/dmu and dU/dQ exactly as above).
 #include "common.h"
 
 namespace {
@@ -89,7 +92,9 @@ __device__ __forceinline__ double qd_volume(const double* cm) {
 // FV: forces or virial are wanted (B5 and the four extra matrix-vector products are compiled in only then).  The fp64 variant without FV is
 // asked for three waves per SIMD: it fits 167 VGPRs without scratch (174 when not asked).  The same request spills in the fp32 variant and
 // in any FV variant, so those keep two waves: no instantiation may use scratch.
-template <class T, bool CSR, bool FV>
+// BARE: the undamped 1/r interaction of a cluster or a cut-off sum, the alpha -> 0 limit: B1 = 1 / r^3, B_{n+1} = (2n + 1) B_n / r^2; no erfc,
+// no exp, alpha is not read (NULL).
+template <class T, bool CSR, bool FV, bool BARE = false>
 __global__ __launch_bounds__(256, (FV || sizeof(T) == 4) ? 2 : 3) void qd_pair_kernel(const QdRec<T>* __restrict__ rec, const T* __restrict__ cell, const T* __restrict__ alpha,
                                                       const int* __restrict__ batch_idx, const double* __restrict__ g, int N,
                                                       const int* __restrict__ idx, const int* __restrict__ ush, const int* __restrict__ nptr, int M,
@@ -103,8 +108,9 @@ __global__ __launch_bounds__(256, (FV || sizeof(T) == 4) ? 2 : 3) void qd_pair_k
   const bool shifted = ush != nullptr;
   T cm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (shifted) pair_row_cell(cell, s, cm);
-  const double al = (double)alpha[s];
-  const double ta = 2.0 * al * al, inv_a_sqrt_pi = 1.0 / (al * QD_SQRT_PI);
+  double al = 0.0;
+  if constexpr (!BARE) al = (double)alpha[s];
+  const double ta = 2.0 * al * al, inv_a_sqrt_pi = BARE ? 0.0 : 1.0 / (al * QD_SQRT_PI);
   const QdRec<T> ri = rec[i];
   const double qi = (double)ri.q, mix = (double)ri.mx, miy = (double)ri.my, miz = (double)ri.mz;
   const double Qi[6] = {(double)ri.xx, (double)ri.xy, (double)ri.xz, (double)ri.yy, (double)ri.yz, (double)ri.zz};
@@ -131,13 +137,21 @@ __global__ __launch_bounds__(256, (FV || sizeof(T) == 4) ? 2 : 3) void qd_pair_k
     const double dist = (double)sqrt(r2t);  // the distance is a quantity of the positions dtype
     if (!(dist > 1e-8)) continue;           // (NaN distances leave here too)
     const double rinv = 1.0 / dist, ar = al * dist, rinv2 = rinv * rinv;
-    const double pre = exp(-(ar * ar)) * inv_a_sqrt_pi;
     const double ta2 = ta * ta;
-    const double b0 = erfc(ar) * rinv;
-    const double b1 = (b0 + ta * pre) * rinv2;
-    const double b2 = (3.0 * b1 + ta2 * pre) * rinv2;
-    const double b3 = (5.0 * b2 + ta2 * ta * pre) * rinv2;
-    const double b4 = (7.0 * b3 + ta2 * ta2 * pre) * rinv2;
+    double pre = 0.0, b1, b2, b3, b4;
+    if constexpr (BARE) {
+      b1 = rinv * rinv2;
+      b2 = 3.0 * b1 * rinv2;
+      b3 = 5.0 * b2 * rinv2;
+      b4 = 7.0 * b3 * rinv2;
+    } else {
+      pre = exp(-(ar * ar)) * inv_a_sqrt_pi;
+      const double b0 = erfc(ar) * rinv;
+      b1 = (b0 + ta * pre) * rinv2;
+      b2 = (3.0 * b1 + ta2 * pre) * rinv2;
+      b3 = (5.0 * b2 + ta2 * ta * pre) * rinv2;
+      b4 = (7.0 * b3 + ta2 * ta2 * pre) * rinv2;
+    }
     const double rx = (double)sx, ry = (double)sy, rz = (double)sz;
     const double qj = (double)rj.q, mjx = (double)rj.mx, mjy = (double)rj.my, mjz = (double)rj.mz;
     const double Qj[6] = {(double)rj.xx, (double)rj.xy, (double)rj.xz, (double)rj.yy, (double)rj.yz, (double)rj.zz};
@@ -174,7 +188,7 @@ __global__ __launch_bounds__(256, (FV || sizeof(T) == 4) ? 2 : 3) void qd_pair_k
     }
     if constexpr (FV) {
       if (wf || wv) {
-        const double b5 = (9.0 * b4 + ta2 * ta2 * ta * pre) * rinv2;
+        const double b5 = BARE ? 9.0 * b4 * rinv2 : (9.0 * b4 + ta2 * ta2 * ta * pre) * rinv2;
         const double cr = -w * (b2 * c1 + b3 * c2 + b4 * c3 + b5 * c4);
         const double cai = 2.0 * w * a1, caj = 2.0 * w * (b2 * qi + b3 * (ci - ti) + b4 * si);
         const double cmi = w * (b3 * sj - b2 * tj), cmj = w * (b2 * ti - b3 * si);
@@ -454,6 +468,61 @@ extern "C" int mi_ewald_quadrupole_real(const void* positions, const void* charg
   mi_timing_end(stream);
 #undef MI_QD
 #undef MI_QD_ARGS
+  MI_LAUNCH_CHECK();
+  if (virial) {
+    qd_fold_kernel<<<dim3(MI_FOLD_BLOCKS, n_systems), 256, 0, st>>>(trow, bi, n_atoms, virial_partial);
+    MI_LAUNCH_CHECK();
+  }
+  return MI_OK;
+}
+
+extern "C" int mi_coulomb_quadrupole_blocks(void) { return MI_FOLD_BLOCKS; }
+extern "C" size_t mi_coulomb_quadrupole_scratch_bytes(int n_atoms, int dtype) { return mi_ewald_quadrupole_real_scratch_bytes(n_atoms, dtype); }
+
+extern "C" int mi_coulomb_quadrupole(const void* positions, const void* charges, const void* dipoles, const void* quadrupoles, const void* cell,
+                                     const int32_t* batch_idx, const double* weights, int n_atoms, int n_systems, int dtype, const int32_t* idx_j,
+                                     const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors, int mask_value, int flags,
+                                     double* energies, void* forces, double* charge_grads, double* dipole_grads, double* quadrupole_grads,
+                                     double* virial_partial, void* scratch, size_t scratch_bytes, void* stream) {
+  MI_REQUIRE(dtype == MI_F32 || dtype == MI_F64, "dtype");
+  MI_REQUIRE(n_atoms >= 0, "n_atoms must not be negative");
+  MI_REQUIRE(n_systems >= 1 && n_systems <= 65535, "n_systems must be in [1, 65535]");
+  MI_REQUIRE(neighbor_ptr || max_neighbors >= 0, "max_neighbors must not be negative");
+  MI_REQUIRE(n_systems == 1 || batch_idx, "batch_idx is required for more than one system");
+  MI_REQUIRE(!(flags & ~(MI_QD_FORCES | MI_QD_CHARGE_GRAD | MI_QD_DIPOLE_GRAD | MI_QD_VIRIAL | MI_QD_QUADRUPOLE_GRAD)), "unknown flag");
+  MI_REQUIRE(cell || !unit_shifts, "unit_shifts need a cell");
+  const bool virial = (flags & MI_QD_VIRIAL) != 0;
+  MI_REQUIRE(!virial || (unit_shifts && virial_partial), "the virial needs unit_shifts and virial_partial");
+  if (n_atoms == 0) return MI_OK;
+  MI_REQUIRE(positions && charges && dipoles && quadrupoles && idx_j, "null pointer");
+  MI_REQUIRE(energies || flags, "nothing to compute");
+  MI_REQUIRE(!(flags & MI_QD_FORCES) || forces, "forces output");
+  MI_REQUIRE(!(flags & MI_QD_CHARGE_GRAD) || charge_grads, "charge gradient output");
+  MI_REQUIRE(!(flags & MI_QD_DIPOLE_GRAD) || dipole_grads, "dipole gradient output");
+  MI_REQUIRE(!(flags & MI_QD_QUADRUPOLE_GRAD) || quadrupole_grads, "quadrupole gradient output");
+  MI_REQUIRE(scratch && scratch_bytes >= mi_coulomb_quadrupole_scratch_bytes(n_atoms, dtype),
+             "scratch smaller than mi_coulomb_quadrupole_scratch_bytes()");
+  hipStream_t st = (hipStream_t)stream;
+  double* trow = reinterpret_cast<double*>((char*)scratch + qd_rec_bytes(n_atoms, dtype));
+  const int blocks = mi_blocks(n_atoms, 256 / MI_WAVE);
+  const int32_t* bi = n_systems > 1 ? batch_idx : nullptr;
+  const bool fv = (flags & (MI_QD_FORCES | MI_QD_VIRIAL)) != 0;
+#define MI_CQ_ARGS(T_)                                                                                                                        \
+  (const QdRec<T_>*)scratch, (const T_*)cell, (const T_*)nullptr, bi, weights, n_atoms, idx_j, unit_shifts, neighbor_ptr, max_neighbors,     \
+      mask_value, flags, energies, (T_*)forces, charge_grads, dipole_grads, quadrupole_grads, trow
+#define MI_CQ(T_, CSR_)                                                                                                                       \
+  do {                                                                                                                                        \
+    qd_pack_kernel<T_><<<mi_blocks(n_atoms, 256), 256, 0, st>>>((const T_*)positions, (const T_*)charges, (const T_*)dipoles,                 \
+                                                                (const T_*)quadrupoles, n_atoms, (QdRec<T_>*)scratch);                        \
+    if (fv) qd_pair_kernel<T_, CSR_, true, true><<<blocks, 256, 0, st>>>(MI_CQ_ARGS(T_));                                                     \
+    else qd_pair_kernel<T_, CSR_, false, true><<<blocks, 256, 0, st>>>(MI_CQ_ARGS(T_));                                                       \
+  } while (0)
+  mi_timing_begin("coulomb_quadrupole", stream);
+  if (dtype == MI_F32) { if (neighbor_ptr) MI_CQ(float, true); else MI_CQ(float, false); }
+  else { if (neighbor_ptr) MI_CQ(double, true); else MI_CQ(double, false); }
+  mi_timing_end(stream);
+#undef MI_CQ
+#undef MI_CQ_ARGS
   MI_LAUNCH_CHECK();
   if (virial) {
     qd_fold_kernel<<<dim3(MI_FOLD_BLOCKS, n_systems), 256, 0, st>>>(trow, bi, n_atoms, virial_partial);

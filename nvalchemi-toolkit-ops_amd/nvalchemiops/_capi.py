@@ -183,6 +183,16 @@ def lib() -> ctypes.CDLL:
         L.mi_thole_dipole_scratch_bytes.argtypes = [i, i]
         L.mi_thole_dipole_blocks.restype = i
         L.mi_thole_dipole_blocks.argtypes = []
+        # cluster point multipoles: the bare pair sums (nvalchemiops/interactions/electrostatics/cluster.py)
+        L.mi_coulomb_dipole.restype = i
+        L.mi_coulomb_dipole.argtypes = [vp] * 6 + [i, i, i, vp, vp, vp, i, i, i] + [vp] * 6 + [sz, vp]
+        L.mi_coulomb_quadrupole.restype = i
+        L.mi_coulomb_quadrupole.argtypes = [vp] * 7 + [i, i, i, vp, vp, vp, i, i, i] + [vp] * 7 + [sz, vp]
+        for name in ("mi_coulomb_dipole", "mi_coulomb_quadrupole"):
+            getattr(L, name + "_scratch_bytes").restype = sz
+            getattr(L, name + "_scratch_bytes").argtypes = [i, i]
+            getattr(L, name + "_blocks").restype = i
+            getattr(L, name + "_blocks").argtypes = []
         # particle-mesh Ewald for point dipoles (nvalchemiops/interactions/electrostatics/pme_dipole.py)
         L.mi_pme_dipole_spread.restype = i
         L.mi_pme_dipole_spread.argtypes = [vp] * 6 + [i] * 7 + [vp, vp]
@@ -219,6 +229,8 @@ def lib() -> ctypes.CDLL:
         L.mi_induced_pair_tensors.argtypes = [vp] * 5 + [i, i, i, vp, vp, vp, i, i, ll, vp, vp, vp, vp, vp]
         L.mi_thole_induced_pair_tensors.restype = i
         L.mi_thole_induced_pair_tensors.argtypes = [vp] * 5 + [i, i, i, vp, vp, vp, i, i, ll, vp, vp, vp, vp, dbl, vp]
+        L.mi_cluster_induced_pair_tensors.restype = i
+        L.mi_cluster_induced_pair_tensors.argtypes = [vp, vp, i, i, vp, vp, i, i, ll, vp, vp, vp, vp, dbl, vp]
         L.mi_induced_apply.restype = i
         L.mi_induced_apply.argtypes = [vp] * 6 + [i, i, vp, i, ll, vp, vp, vp]
         L.mi_induced_dot.restype = i

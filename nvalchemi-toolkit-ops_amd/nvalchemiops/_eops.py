@@ -2019,7 +2019,127 @@ pme_quadrupole_reciprocal_space_op = _op("_pme_quadrupole_reciprocal_space", _qd
                                                       {4: "cell", 5: "alpha"}), _qd_pme_setup)
 
 
-__all__ = ["pme_quadrupole_reciprocal_space_op", "pme_quadrupole_recip_bwd_op",
+# cluster point multipoles (the bare dipole and quadrupole pair sums): the pattern of the Thole op -- an optional cell (clusters) that has no
+# adjoint and is refused, the outputs of the real-space dipole / quadrupole ops.
+_CL_NO_GRAD = ("{op}: gradients w.r.t. cell are not provided by the bare multipole pair sums (out of scope); use compute_virial for the strain "
+               "derivative.")
+
+
+def _cl_nsys(cell, batch_idx):
+    return cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1
+
+
+def _cl_backward(name, bwd_op, outputs, n_diff):
+    """Autograd of a cluster op: the first `n_diff` inputs are differentiable, the cell follows them."""
+    def backward(ctx, g_e, *g_explicit):
+        for what, g in zip(outputs[1:], g_explicit):
+            if g is not None:
+                raise NotImplementedError(_SECOND_ORDER.format(op=name, what=what))
+        need = ctx.needs_input_grad
+        if need[n_diff]:
+            raise NotImplementedError(_CL_NO_GRAD.format(op=name))
+        if g_e is None:
+            return (None,) * len(need)
+        saved = ctx.saved_tensors
+        grads = bwd_op(*saved, *ctx.extra, g_e)
+        return tuple(g.to(t.dtype) if w else None for g, t, w in zip(grads, saved[:n_diff], need[:n_diff])) + (None,) * (len(need) - n_diff)
+
+    return backward
+
+
+def _cl_dp_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor],
+               neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
+               neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int, compute_forces: bool,
+               compute_charge_gradients: bool, compute_dipole_gradients: bool, compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from nvalchemiops.interactions.electrostatics.cluster import _dipole_forward
+
+    out = _dipole_forward(positions, charges, dipoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                          neighbor_matrix_shifts, int(mask_value), compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
+    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
+
+
+def _cl_dp_fwd_fake(positions, charges, dipoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                    neighbor_matrix_shifts, mask_value, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial):
+    return _dp_fake(positions, _cl_nsys(cell, batch_idx), compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
+
+
+def _cl_dp_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor],
+               neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
+               neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int,
+               grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor]:
+    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles) for L = sum_i g_i E_i."""
+    from nvalchemiops.interactions.electrostatics.cluster import _dipole_adjoint
+
+    return _dipole_adjoint(positions, charges, dipoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                           neighbor_matrix_shifts, int(mask_value), grad_energies)
+
+
+coulomb_dipole_bwd_op = torch.library.custom_op("nvalchemiops::coulomb_dipole_correction_backward", _cl_dp_bwd, mutates_args=())
+coulomb_dipole_bwd_op.register_fake(lambda positions, *rest: _dp_bwd_fake(positions))
+coulomb_dipole_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::coulomb_dipole_correction_backward"),
+                                        setup_context=lambda ctx, inputs, output: None)
+
+
+def _cl_dp_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:10])
+    ctx.extra = (int(inputs[10]),)
+    ctx.set_materialize_grads(False)
+
+
+coulomb_dipole_correction_op = _op("_coulomb_dipole_correction", _cl_dp_fwd, _cl_dp_fwd_fake,
+                                   _cl_backward(f"{_NS}::_coulomb_dipole_correction", coulomb_dipole_bwd_op, _DP_OUTPUTS, 3), _cl_dp_setup)
+
+
+def _cl_qd_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, quadrupoles: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor],
+               neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
+               neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int, compute_forces: bool,
+               compute_charge_gradients: bool, compute_dipole_gradients: bool, compute_quadrupole_gradients: bool,
+               compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    from nvalchemiops.interactions.electrostatics.cluster import _quadrupole_forward
+
+    out = _quadrupole_forward(positions, charges, dipoles, quadrupoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
+                              neighbor_matrix, neighbor_matrix_shifts, int(mask_value), compute_forces, compute_charge_gradients,
+                              compute_dipole_gradients, compute_quadrupole_gradients, compute_virial)
+    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
+
+
+def _cl_qd_fwd_fake(positions, charges, dipoles, quadrupoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                    neighbor_matrix_shifts, mask_value, compute_forces, compute_charge_gradients, compute_dipole_gradients,
+                    compute_quadrupole_gradients, compute_virial):
+    return _qd_fake(positions, _cl_nsys(cell, batch_idx), compute_forces, compute_charge_gradients, compute_dipole_gradients,
+                    compute_quadrupole_gradients, compute_virial)
+
+
+def _cl_qd_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, quadrupoles: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor],
+               neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
+               neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int,
+               grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles, dL/dquadrupoles) for L = sum_i g_i E_i."""
+    from nvalchemiops.interactions.electrostatics.cluster import _quadrupole_adjoint
+
+    return _quadrupole_adjoint(positions, charges, dipoles, quadrupoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
+                               neighbor_matrix, neighbor_matrix_shifts, int(mask_value), grad_energies)
+
+
+coulomb_quadrupole_bwd_op = torch.library.custom_op("nvalchemiops::coulomb_quadrupole_correction_backward", _cl_qd_bwd, mutates_args=())
+coulomb_quadrupole_bwd_op.register_fake(_qd_bwd_fake)
+coulomb_quadrupole_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::coulomb_quadrupole_correction_backward"),
+                                            setup_context=lambda ctx, inputs, output: None)
+
+
+def _cl_qd_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:11])
+    ctx.extra = (int(inputs[11]),)
+    ctx.set_materialize_grads(False)
+
+
+coulomb_quadrupole_correction_op = _op("_coulomb_quadrupole_correction", _cl_qd_fwd, _cl_qd_fwd_fake,
+                                       _cl_backward(f"{_NS}::_coulomb_quadrupole_correction", coulomb_quadrupole_bwd_op, _QD_OUTPUTS, 4),
+                                       _cl_qd_setup)
+
+
+__all__ = ["coulomb_dipole_correction_op", "coulomb_dipole_bwd_op", "coulomb_quadrupole_correction_op", "coulomb_quadrupole_bwd_op",
+           "pme_quadrupole_reciprocal_space_op", "pme_quadrupole_recip_bwd_op",
            "ewald_quadrupole_real_space_op", "ewald_quadrupole_reciprocal_space_op", "ewald_quadrupole_real_bwd_op",
            "ewald_quadrupole_recip_bwd_op", "thole_dipole_correction_op", "thole_dipole_bwd_op", "pme_dipole_reciprocal_space_op", "pme_dipole_recip_bwd_op", "ewald_dipole_real_space_op", "ewald_dipole_reciprocal_space_op", "ewald_dipole_real_bwd_op", "ewald_dipole_recip_bwd_op",
            "gaussian_charge_correction_op", "gaussian_bwd_op","spline_spread_op", "batch_spline_spread_op", "spline_gather_op", "batch_spline_gather_op", "spline_gather_vec3_op",

@@ -11,6 +11,8 @@ from nvalchemiops.interactions.electrostatics.gaussian import gaussian_charge_co
 from nvalchemiops.interactions.electrostatics.induced import (InducedDipoleError, InducedDipoleResult, induced_dipoles,
                                                               thole_induced_dipoles)
 from nvalchemiops.interactions.electrostatics.thole import thole_dipole_correction
+from nvalchemiops.interactions.electrostatics.cluster import (cluster_induced_dipoles, coulomb_dipole_correction,
+                                                              coulomb_quadrupole_correction)
 from nvalchemiops.interactions.electrostatics.k_vectors import generate_k_vectors_ewald_summation, generate_k_vectors_pme
 from nvalchemiops.interactions.electrostatics.parameters import (EwaldParameters, PMEParameters, estimate_ewald_parameters,
                                                                  estimate_pme_mesh_dimensions, estimate_pme_parameters,
@@ -30,4 +32,5 @@ __all__ = [
     "induced_dipoles", "InducedDipoleError", "InducedDipoleResult", "thole_dipole_correction", "thole_induced_dipoles",
     "ewald_quadrupole_correction", "ewald_quadrupole_real_space", "ewald_quadrupole_reciprocal_space",
     "pme_quadrupole_correction", "pme_quadrupole_reciprocal_space",
+    "coulomb_dipole_correction", "coulomb_quadrupole_correction", "cluster_induced_dipoles",
 ]

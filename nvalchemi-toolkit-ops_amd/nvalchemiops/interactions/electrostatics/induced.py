@@ -92,7 +92,11 @@ def _check(positions, charges, polarizability, cell, external_field, batch_idx, 
 
 
 class _Operator:
-    """H = diag(1 / a) + T of one geometry: the stored real-space tensors and the reciprocal-space dipole-gradient call."""
+    """H = diag(1 / a) + T of one geometry: the stored real-space tensors and the reciprocal-space dipole-gradient call.  `reciprocal=None`
+    is the mode without a reciprocal part (`cluster_induced_dipoles`: no cell, no alpha, no shifts): the stored operator holds the bare
+    1 / r^3, 3 / r^5 coefficients, H x is the stored-operator product alone, and the energy is `coulomb_dipole_correction`."""
+
+    name = "induced_dipoles"  # the public function in error messages
 
     def __init__(self, positions, polar, cell, batch_idx, nsys, lists, mask_value, reciprocal, alpha, mesh_dimensions, mesh_spacing, spline_order,
                  k_vectors, k_cutoff, accuracy, thole=None):
@@ -102,11 +106,12 @@ class _Operator:
         self.polar = polar.detach().to(dt).contiguous()
         self.bi = C.i32(batch_idx) if nsys > 1 else None
         self.batch_idx = batch_idx if nsys > 1 else None
-        self.cells = cell.detach().to(dt).reshape(-1, 3, 3).contiguous()
+        self.cells = None if cell is None else cell.detach().to(dt).reshape(-1, 3, 3).contiguous()
         self.reciprocal = reciprocal
         self.thole = None if thole is None else float(thole)  # the Thole width: B_n + D_n in the stored operator, E_dip + E_thole in the energy
         self.alpha = self.kv = self.dims = self.order = None
-        self._reciprocal_parameters(alpha, mesh_dimensions, mesh_spacing, spline_order, k_vectors, k_cutoff, accuracy)
+        if reciprocal is not None:
+            self._reciprocal_parameters(alpha, mesh_dimensions, mesh_spacing, spline_order, k_vectors, k_cutoff, accuracy)
         ls = P.list_inputs(*lists)
         self.idx, self.nptr, self.m, self.sh, self.slots = ls["idx"], ls["nptr"], ls["m"], ls["sh"], ls["n_entries"]
         L = C.lib()
@@ -120,10 +125,17 @@ class _Operator:
         zq, zmu = torch.zeros(n, dtype=dt, device=dev), torch.zeros((n, 3), dtype=dt, device=dev)
         if reciprocal == "pme":  # launch tensors of the reciprocal call, made once: only the dipoles change between iterations
             self.rp = PD._inputs(self.pos, zq, zmu, self.cells, self.alpha, self.batch_idx)
-        else:
+        elif reciprocal == "ewald":
             self.rp = D._recip_inputs(self.pos, zq, zmu, self.cells, self.kv, self.alpha, self.batch_idx)
 
     def pair_tensors(self):
+        if self.reciprocal is None:
+            rc = C.lib().mi_cluster_induced_pair_tensors(C.ptr(self.pos), C.ptr(self.polar), self.n, C.dtype_code(self.dt), C.ptr(self.idx),
+                                                         C.ptr(self.nptr), int(self.m), self.mask_value, self.slots, C.ptr(self.tensors),
+                                                         C.ptr(self.nbr), C.ptr(self.diag), C.ptr(self.precond),
+                                                         C.cdouble(0.0 if self.thole is None else self.thole), C.stream_of(self.pos))
+            C.check(rc, "mi_cluster_induced_pair_tensors")
+            return
         args = (C.ptr(self.pos), C.ptr(self.polar), C.ptr(self.cells), C.ptr(self.alpha), C.ptr(self.bi), self.n, self.nsys, C.dtype_code(self.dt),
                 C.ptr(self.idx), C.ptr(self.sh), C.ptr(self.nptr), int(self.m), self.mask_value, self.slots, C.ptr(self.tensors), C.ptr(self.nbr),
                 C.ptr(self.diag), C.ptr(self.precond))
@@ -165,7 +177,10 @@ class _Operator:
     # ---- the pieces of H x ----------------------------------------------------------------------------------------------------------------
     def reciprocal_gradient(self, x):
         """float64 [N, 3] dE_recip/dmu at zero charges and the dipoles x (linear in x), projected onto the polarisable atoms: the dipole
-        gradient of the public reciprocal-space function -- same launches, the energies skipped, the same rounding to the positions dtype."""
+        gradient of the public reciprocal-space function -- same launches, the energies skipped, the same rounding to the positions dtype.
+        None without a reciprocal part."""
+        if self.reciprocal is None:
+            return None
         with torch.no_grad():
             p = dict(self.rp, mu=x.to(self.dt).contiguous())
             if self.reciprocal == "pme":
@@ -202,12 +217,17 @@ class _Operator:
         q = charges.detach().to(self.dt)
         mu0 = torch.zeros((self.n, 3), dtype=self.dt, device=self.dev)
         with torch.no_grad():
-            g = D.ewald_dipole_real_space(self.pos, q, mu0, self.cells, self.alpha, mask_value=mask_value, batch_idx=self.batch_idx,
-                                          compute_dipole_gradients=True, **kw)[1].to(F64)
+            if self.reciprocal is None:
+                from nvalchemiops.interactions.electrostatics.cluster import coulomb_dipole_correction
+
+                g = coulomb_dipole_correction(self.pos, q, mu0, mask_value=mask_value, compute_dipole_gradients=True, **kw)[1].to(F64)
+            else:
+                g = D.ewald_dipole_real_space(self.pos, q, mu0, self.cells, self.alpha, mask_value=mask_value, batch_idx=self.batch_idx,
+                                              compute_dipole_gradients=True, **kw)[1].to(F64)
             if self.reciprocal == "pme":
                 g = g + PD.pme_dipole_reciprocal_space(self.pos, q, mu0, self.cells, self.alpha, mesh_dimensions=self.dims, spline_order=self.order,
                                                        batch_idx=self.batch_idx, compute_dipole_gradients=True)[1].to(F64)
-            else:
+            elif self.reciprocal == "ewald":
                 g = g + D.ewald_dipole_reciprocal_space(self.pos, q, mu0, self.cells, self.kv, self.alpha, batch_idx=self.batch_idx,
                                                         compute_dipole_gradients=True)[1].to(F64)
             if self.thole is not None:
@@ -289,7 +309,11 @@ def _dipole_energy(op: _Operator, positions, charges, dipoles, lists, mask_value
     E_thole of a damped solve (`polar` then gives the polarisabilities to differentiate; default: the operator's own)."""
     kw = dict(zip(("neighbor_list", "neighbor_ptr", "neighbor_shifts", "neighbor_matrix", "neighbor_matrix_shifts"), lists))
     q, mu = charges.to(positions.dtype), dipoles.to(positions.dtype)
-    if op.reciprocal == "pme":
+    if op.reciprocal is None:
+        from nvalchemiops.interactions.electrostatics.cluster import coulomb_dipole_correction
+
+        e = coulomb_dipole_correction(positions, q, mu, mask_value=mask_value, **kw).sum()
+    elif op.reciprocal == "pme":
         e = PD.pme_dipole_correction(positions, q, mu, op.cells, alpha=op.alpha, mesh_dimensions=op.dims, spline_order=op.order,
                                      batch_idx=op.batch_idx, mask_value=mask_value, **kw).sum()
     else:
@@ -308,7 +332,7 @@ class _InducedDipoles(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, positions, charges, polar, field, op, b, initial, lists, mask_value, solver):
-        x, state = _conjugate_gradients(op, b, initial, *solver, "induced_dipoles")
+        x, state = _conjugate_gradients(op, b, initial, *solver, op.name)
         mu = x
         ctx.save_for_backward(positions, charges, polar, mu)
         ctx.op, ctx.lists, ctx.mask_value, ctx.solver = op, lists, mask_value, solver
@@ -320,13 +344,13 @@ class _InducedDipoles(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _g_state):
         if torch.is_grad_enabled():
-            raise NotImplementedError("induced_dipoles: second derivatives are not supported (the backward pass is itself a linear solve and is "
+            raise NotImplementedError(f"{ctx.op.name}: second derivatives are not supported (the backward pass is itself a linear solve and is "
                                       "not recorded)")
         positions, charges, polar, mu = ctx.saved_tensors
         op, need = ctx.op, ctx.needs_input_grad
         if g is None:
             return (None,) * 10
-        z, _ = _conjugate_gradients(op, (g.detach().to(F64) * op.mask).contiguous(), None, *ctx.solver, "induced_dipoles (backward)")
+        z, _ = _conjugate_gradients(op, (g.detach().to(F64) * op.mask).contiguous(), None, *ctx.solver, f"{op.name} (backward)")
         g_pos = g_q = g_polar = g_field = None
         if need[2]:
             a = polar.detach().to(F64)
@@ -437,6 +461,29 @@ def thole_induced_dipoles(positions: torch.Tensor, charges: torch.Tensor, polari
                   k_cutoff, accuracy, tolerance, max_iterations, check_interval, initial_dipoles, return_info)
 
 
+def _empty_result(nsys, dt, dev, return_info):
+    empty = torch.zeros((0, 3), dtype=dt, device=dev)
+    zeros = torch.zeros(nsys, dtype=dt, device=dev)
+    return InducedDipoleResult(empty, zeros, torch.zeros(nsys, dtype=torch.int64, device=dev), zeros.clone()) if return_info else empty
+
+
+def _run(op: _Operator, positions, charges, polar, external_field, lists, mask_value, solver, initial_dipoles, return_info):
+    """The solve on a built operator, with or without autograd, and its result: what every public solver function ends in."""
+    dt = positions.dtype
+    b = op.right_hand_side(charges, external_field, lists, mask_value)
+    diff = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (positions, charges, polar, external_field))
+    if diff:
+        dipoles, state = _InducedDipoles.apply(positions, charges, polar, external_field, op, b, initial_dipoles, lists, mask_value, solver)
+        mu64 = dipoles.detach().to(F64).contiguous()
+    else:
+        mu64, state = _conjugate_gradients(op, b, initial_dipoles, *solver, op.name)
+        dipoles = mu64.to(dt)
+    if not return_info:
+        return dipoles
+    iterations, residual = _info(state)
+    return InducedDipoleResult(dipoles, (-0.5 * op.dot(mu64, b)).to(dt), iterations, residual.to(dt))
+
+
 def _solve(thole, positions, charges, polarizability, cell, external_field, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
            neighbor_matrix, neighbor_matrix_shifts, mask_value, reciprocal, alpha, mesh_dimensions, mesh_spacing, spline_order, k_vectors, k_cutoff,
            accuracy, tolerance, max_iterations, check_interval, initial_dipoles, return_info):
@@ -452,9 +499,7 @@ def _solve(thole, positions, charges, polarizability, cell, external_field, batc
         mask_value = n
     per_atom_polar = isinstance(polarizability, torch.Tensor) and polarizability.dim() > 0
     if n == 0:
-        empty = torch.zeros((0, 3), dtype=dt, device=dev)
-        zeros = torch.zeros(nsys, dtype=dt, device=dev)
-        return InducedDipoleResult(empty, zeros, torch.zeros(nsys, dtype=torch.int64, device=dev), zeros.clone()) if return_info else empty
+        return _empty_result(nsys, dt, dev, return_info)
     C.require_device(positions, charges, polarizability if per_atom_polar else None, cell, external_field, batch_idx, neighbor_list, neighbor_ptr,
                      neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, k_vectors, initial_dipoles)
     with torch.cuda.device(dev):
@@ -463,19 +508,8 @@ def _solve(thole, positions, charges, polarizability, cell, external_field, batc
         lists = (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
         op = _Operator(positions, polar, cell, batch_idx, nsys, lists, mask_value, reciprocal, alpha, mesh_dimensions, mesh_spacing, spline_order,
                        k_vectors, k_cutoff, accuracy, thole)
-        b = op.right_hand_side(charges, external_field, lists, int(mask_value))
-        solver = (float(tolerance), int(max_iterations), int(check_interval))
-        diff = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (positions, charges, polar, external_field))
-        if diff:
-            dipoles, state = _InducedDipoles.apply(positions, charges, polar, external_field, op, b, initial_dipoles, lists, int(mask_value), solver)
-            mu64 = dipoles.detach().to(F64).contiguous()
-        else:
-            mu64, state = _conjugate_gradients(op, b, initial_dipoles, *solver, "induced_dipoles")
-            dipoles = mu64.to(dt)
-        if not return_info:
-            return dipoles
-        iterations, residual = _info(state)
-        return InducedDipoleResult(dipoles, (-0.5 * op.dot(mu64, b)).to(dt), iterations, residual.to(dt))
+        return _run(op, positions, charges, polar, external_field, lists, int(mask_value),
+                    (float(tolerance), int(max_iterations), int(check_interval)), initial_dipoles, return_info)
 
 
 __all__ = ["induced_dipoles", "thole_induced_dipoles", "InducedDipoleError", "InducedDipoleResult"]
