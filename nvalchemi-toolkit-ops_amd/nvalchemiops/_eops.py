@@ -22,6 +22,7 @@ being traced; otherwise they take the direct ctypes path (no dispatcher overhead
 from __future__ import annotations
 
 import ctypes
+import importlib
 import math
 from typing import Optional
 
@@ -1584,558 +1585,135 @@ gaussian_charge_correction_op = _op("_gaussian_charge_correction", _gaussian_fwd
 
 
 # =====================================================================================================================================
-# point-dipole Ewald sum: one op per half (real / reciprocal space), optional tensors as for the Gaussian correction
+# point multipoles: nine operator halves, one forward / backward op pair each, built from one table
 # =====================================================================================================================================
-# Outputs are always the five of the public functions; the ones not asked for are empty [0] tensors.  The energies are differentiable w.r.t.
-# positions, charges and dipoles: the backward ops run the forward kernels with the incoming gradient as per-atom weights.  Cell, alpha and
-# k-vector gradients are out of scope and refused (never a silent zero): the virial is the strain derivative.
-_DP_OUTPUTS = ("energies", "forces", "charge_gradients", "dipole_gradients", "virial")
+# Outputs are always those of the public function (energies, forces, charge_gradients, dipole_gradients, the row's extra output, virial); the
+# ones not asked for are empty [0] tensors.  The energies are differentiable w.r.t. the row's first inputs: the backward op runs the forward
+# kernels with the incoming gradient as per-atom weights and returns float64 gradients.  Gradients of inputs without an adjoint (cell, alpha,
+# k-vectors) are refused, never a silent zero: the virial is the strain derivative.  The ops are registered with an explicit schema string, so
+# the implementations take *args in schema order.
 _DP_NO_GRAD = ("{op}: gradients w.r.t. {what} are not provided by the point-dipole Ewald term (out of scope); use compute_virial for the "
                "strain derivative.")
-
-
-def _dp_fake(positions, nsys, forces, cgrads, dgrads, virial):
-    n = positions.shape[0]
-    empty = lambda: positions.new_empty((0,))  # noqa: E731
-    return (positions.new_empty((n,)), positions.new_empty((n, 3)) if forces else empty(), positions.new_empty((n,)) if cgrads else empty(),
-            positions.new_empty((n, 3)) if dgrads else empty(), positions.new_empty((nsys, 3, 3)) if virial else empty())
-
-
-def _dp_bwd_fake(positions):
-    n, f64 = positions.shape[0], dict(dtype=torch.float64)
-    return positions.new_empty((n, 3), **f64), positions.new_empty((n,), **f64), positions.new_empty((n, 3), **f64)
-
-
-def _dp_refuse_second_order(name):
-    def backward(ctx, *grads):
-        raise NotImplementedError(_SECOND_ORDER.format(op=name, what="gradient"))
-
-    return backward
-
-
-def _dp_backward(name, bwd_op, refused):
-    """Autograd of a dipole op: `refused` maps the positions of inputs without an adjoint (cell, alpha, k_vectors) to their names."""
-    def backward(ctx, g_e, *g_explicit):
-        for what, g in zip(_DP_OUTPUTS[1:], g_explicit):
-            if g is not None:
-                raise NotImplementedError(_SECOND_ORDER.format(op=name, what=what))
-        need = ctx.needs_input_grad
-        for k, what in refused.items():
-            if need[k]:
-                raise NotImplementedError(_DP_NO_GRAD.format(op=name, what=what))
-        if g_e is None:
-            return (None,) * len(need)
-        saved = ctx.saved_tensors
-        positions, charges, dipoles = saved[:3]
-        gpos, gq, gmu = bwd_op(*saved, *ctx.extra, g_e)
-        return (gpos.to(positions.dtype) if need[0] else None, gq.to(charges.dtype) if need[1] else None,
-                gmu.to(dipoles.dtype) if need[2] else None) + (None,) * (len(need) - 3)
-
-    return backward
-
-
-def _dp_real_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, cell: Tensor, alpha: Tensor, batch_idx: Optional[Tensor],
-                 neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
-                 neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int, compute_forces: bool,
-                 compute_charge_gradients: bool, compute_dipole_gradients: bool, compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    from nvalchemiops.interactions.electrostatics.dipole import _real_forward
-
-    out = _real_forward(positions, charges, dipoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                        neighbor_matrix_shifts, int(mask_value), compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
-    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
-
-
-def _dp_real_fwd_fake(positions, charges, dipoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                      neighbor_matrix_shifts, mask_value, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial):
-    nsys = cell.reshape(-1, 3, 3).shape[0] if batch_idx is not None else 1
-    return _dp_fake(positions, nsys, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
-
-
-def _dp_real_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, cell: Tensor, alpha: Tensor, batch_idx: Optional[Tensor],
-                 neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
-                 neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int,
-                 grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor]:
-    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles) for L = sum_i g_i E_i."""
-    from nvalchemiops.interactions.electrostatics.dipole import _real_adjoint
-
-    return _real_adjoint(positions, charges, dipoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                         neighbor_matrix_shifts, int(mask_value), grad_energies)
-
-
-ewald_dipole_real_bwd_op = torch.library.custom_op("nvalchemiops::ewald_dipole_real_space_backward", _dp_real_bwd, mutates_args=())
-ewald_dipole_real_bwd_op.register_fake(lambda positions, *rest: _dp_bwd_fake(positions))
-ewald_dipole_real_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::ewald_dipole_real_space_backward"),
-                                           setup_context=lambda ctx, inputs, output: None)
-
-
-def _dp_real_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs[:11])
-    ctx.extra = (int(inputs[11]),)
-    ctx.set_materialize_grads(False)
-
-
-ewald_dipole_real_space_op = _op("_ewald_dipole_real_space", _dp_real_fwd, _dp_real_fwd_fake,
-                                 _dp_backward(f"{_NS}::_ewald_dipole_real_space", ewald_dipole_real_bwd_op, {3: "cell", 4: "alpha"}),
-                                 _dp_real_setup)
-
-
-def _dp_recip_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, cell: Tensor, k_vectors: Tensor, alpha: Tensor, batch_idx: Optional[Tensor],
-                  compute_forces: bool, compute_charge_gradients: bool, compute_dipole_gradients: bool,
-                  compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    from nvalchemiops.interactions.electrostatics.dipole import _recip_forward
-
-    out = _recip_forward(positions, charges, dipoles, cell, k_vectors, alpha, batch_idx, compute_forces, compute_charge_gradients,
-                         compute_dipole_gradients, compute_virial)
-    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
-
-
-def _dp_recip_fwd_fake(positions, charges, dipoles, cell, k_vectors, alpha, batch_idx, compute_forces, compute_charge_gradients,
-                       compute_dipole_gradients, compute_virial):
-    return _dp_fake(positions, cell.reshape(-1, 3, 3).shape[0], compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
-
-
-def _dp_recip_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, cell: Tensor, k_vectors: Tensor, alpha: Tensor, batch_idx: Optional[Tensor],
-                  grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor]:
-    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles) for L = sum_i g_i E_i."""
-    from nvalchemiops.interactions.electrostatics.dipole import _recip_adjoint
-
-    return _recip_adjoint(positions, charges, dipoles, cell, k_vectors, alpha, batch_idx, grad_energies)
-
-
-ewald_dipole_recip_bwd_op = torch.library.custom_op("nvalchemiops::ewald_dipole_reciprocal_space_backward", _dp_recip_bwd, mutates_args=())
-ewald_dipole_recip_bwd_op.register_fake(lambda positions, *rest: _dp_bwd_fake(positions))
-ewald_dipole_recip_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::ewald_dipole_reciprocal_space_backward"),
-                                            setup_context=lambda ctx, inputs, output: None)
-
-
-def _dp_recip_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs[:7])
-    ctx.extra = ()
-    ctx.set_materialize_grads(False)
-
-
-ewald_dipole_reciprocal_space_op = _op("_ewald_dipole_reciprocal_space", _dp_recip_fwd, _dp_recip_fwd_fake,
-                                       _dp_backward(f"{_NS}::_ewald_dipole_reciprocal_space", ewald_dipole_recip_bwd_op,
-                                                    {3: "cell", 4: "k_vectors", 5: "alpha"}), _dp_recip_setup)
-
-
-
-# point-dipole PME, mesh half: the pattern of the two ops above (mesh dimensions and the spline order travel as plain integers)
-def _dp_pme_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, cell: Tensor, alpha: Tensor, batch_idx: Optional[Tensor], nx: int, ny: int,
-                nz: int, spline_order: int, compute_forces: bool, compute_charge_gradients: bool, compute_dipole_gradients: bool,
-                compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    from nvalchemiops.interactions.electrostatics.pme_dipole import _recip_forward
-
-    out = _recip_forward(positions, charges, dipoles, cell, alpha, batch_idx, (int(nx), int(ny), int(nz)), int(spline_order), compute_forces,
-                         compute_charge_gradients, compute_dipole_gradients, compute_virial)
-    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
-
-
-def _dp_pme_fwd_fake(positions, charges, dipoles, cell, alpha, batch_idx, nx, ny, nz, spline_order, compute_forces, compute_charge_gradients,
-                     compute_dipole_gradients, compute_virial):
-    nsys = cell.reshape(-1, 3, 3).shape[0] if batch_idx is not None else 1
-    return _dp_fake(positions, nsys, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
-
-
-def _dp_pme_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, cell: Tensor, alpha: Tensor, batch_idx: Optional[Tensor], nx: int, ny: int,
-                nz: int, spline_order: int, grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor]:
-    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles) for L = sum_i g_i E_i."""
-    from nvalchemiops.interactions.electrostatics.pme_dipole import _recip_adjoint
-
-    return _recip_adjoint(positions, charges, dipoles, cell, alpha, batch_idx, (int(nx), int(ny), int(nz)), int(spline_order), grad_energies)
-
-
-pme_dipole_recip_bwd_op = torch.library.custom_op("nvalchemiops::pme_dipole_reciprocal_space_backward", _dp_pme_bwd, mutates_args=())
-pme_dipole_recip_bwd_op.register_fake(lambda positions, *rest: _dp_bwd_fake(positions))
-pme_dipole_recip_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::pme_dipole_reciprocal_space_backward"),
-                                          setup_context=lambda ctx, inputs, output: None)
-
-
-def _dp_pme_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs[:6])
-    ctx.extra = tuple(int(v) for v in inputs[6:10])
-    ctx.set_materialize_grads(False)
-
-
-pme_dipole_reciprocal_space_op = _op("_pme_dipole_reciprocal_space", _dp_pme_fwd, _dp_pme_fwd_fake,
-                                     _dp_backward(f"{_NS}::_pme_dipole_reciprocal_space", pme_dipole_recip_bwd_op, {3: "cell", 4: "alpha"}),
-                                     _dp_pme_setup)
-
-
-# Thole damping of point dipoles: the pattern of the real-space dipole op, with the polarisabilities as a fourth differentiable input, an
-# optional cell (clusters) and six outputs (polarizability_gradients before the virial).  The cell has no adjoint and is refused.
-_TH_NAME = f"{_NS}::_thole_dipole_correction"
-_TH_OUTPUTS = ("energies", "forces", "charge_gradients", "dipole_gradients", "polarizability_gradients", "virial")
-
-
-def _thole_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, polarizability: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor],
-               neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
-               neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int, thole: float, compute_forces: bool,
-               compute_charge_gradients: bool, compute_dipole_gradients: bool, compute_polarizability_gradients: bool,
-               compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
-    from nvalchemiops.interactions.electrostatics.thole import _forward
-
-    out = _forward(positions, charges, dipoles, polarizability, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                   neighbor_matrix_shifts, int(mask_value), float(thole), compute_forces, compute_charge_gradients, compute_dipole_gradients,
-                   compute_polarizability_gradients, compute_virial)
-    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
-
-
-def _thole_fwd_fake(positions, charges, dipoles, polarizability, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                    neighbor_matrix_shifts, mask_value, thole, compute_forces, compute_charge_gradients, compute_dipole_gradients,
-                    compute_polarizability_gradients, compute_virial):
-    n = positions.shape[0]
-    nsys = cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1
-    empty = lambda: positions.new_empty((0,))  # noqa: E731
-    return (positions.new_empty((n,)), positions.new_empty((n, 3)) if compute_forces else empty(),
-            positions.new_empty((n,)) if compute_charge_gradients else empty(), positions.new_empty((n, 3)) if compute_dipole_gradients else empty(),
-            positions.new_empty((n,)) if compute_polarizability_gradients else empty(),
-            positions.new_empty((nsys, 3, 3)) if compute_virial else empty())
-
-
-def _thole_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, polarizability: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor],
-               neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
-               neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int, thole: float,
-               grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor]:
-    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles, dL/dpolarizability) for L = sum_i g_i E_i."""
-    from nvalchemiops.interactions.electrostatics.thole import _adjoint
-
-    return _adjoint(positions, charges, dipoles, polarizability, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                    neighbor_matrix_shifts, int(mask_value), float(thole), grad_energies)
-
-
-def _thole_bwd_fake(positions, *rest):
-    n, f64 = positions.shape[0], dict(dtype=torch.float64)
-    return (positions.new_empty((n, 3), **f64), positions.new_empty((n,), **f64), positions.new_empty((n, 3), **f64),
-            positions.new_empty((n,), **f64))
-
-
-thole_dipole_bwd_op = torch.library.custom_op("nvalchemiops::thole_dipole_correction_backward", _thole_bwd, mutates_args=())
-thole_dipole_bwd_op.register_fake(_thole_bwd_fake)
-thole_dipole_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::thole_dipole_correction_backward"),
-                                      setup_context=lambda ctx, inputs, output: None)
-
-
-def _thole_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs[:11])
-    ctx.extra = (int(inputs[11]), float(inputs[12]))
-    ctx.set_materialize_grads(False)
-
-
-def _thole_backward(ctx, g_e, *g_explicit):
-    for what, g in zip(_TH_OUTPUTS[1:], g_explicit):
-        if g is not None:
-            raise NotImplementedError(_SECOND_ORDER.format(op=_TH_NAME, what=what))
-    need = ctx.needs_input_grad
-    if need[4]:
-        raise NotImplementedError(f"{_TH_NAME}: gradients w.r.t. cell are not provided by the Thole damping term (out of scope); use "
-                                  "compute_virial for the strain derivative.")
-    if g_e is None:
-        return (None,) * len(need)
-    saved = ctx.saved_tensors
-    positions, charges, dipoles, polar = saved[:4]
-    gpos, gq, gmu, gpol = thole_dipole_bwd_op(*saved, *ctx.extra, g_e)
-    return (gpos.to(positions.dtype) if need[0] else None, gq.to(charges.dtype) if need[1] else None,
-            gmu.to(dipoles.dtype) if need[2] else None, gpol.to(polar.dtype) if need[3] else None) + (None,) * (len(need) - 4)
-
-
-thole_dipole_correction_op = _op("_thole_dipole_correction", _thole_fwd, _thole_fwd_fake, _thole_backward, _thole_setup)
-
-
-# point-quadrupole Ewald sum: the pattern of the two point-dipole Ewald ops, with the quadrupoles as a fourth differentiable input and six
-# outputs (quadrupole_gradients before the virial).  Cell, alpha and k-vector gradients are refused.
-_QD_OUTPUTS = ("energies", "forces", "charge_gradients", "dipole_gradients", "quadrupole_gradients", "virial")
 _QD_NO_GRAD = ("{op}: gradients w.r.t. {what} are not provided by the point-quadrupole Ewald term (out of scope); use compute_virial for the "
                "strain derivative.")
-
-
-def _qd_fake(positions, nsys, forces, cgrads, dgrads, qgrads, virial):
-    n = positions.shape[0]
-    empty = lambda: positions.new_empty((0,))  # noqa: E731
-    return (positions.new_empty((n,)), positions.new_empty((n, 3)) if forces else empty(), positions.new_empty((n,)) if cgrads else empty(),
-            positions.new_empty((n, 3)) if dgrads else empty(), positions.new_empty((n, 3, 3)) if qgrads else empty(),
-            positions.new_empty((nsys, 3, 3)) if virial else empty())
-
-
-def _qd_bwd_fake(positions, *rest):
-    n, f64 = positions.shape[0], dict(dtype=torch.float64)
-    return (positions.new_empty((n, 3), **f64), positions.new_empty((n,), **f64), positions.new_empty((n, 3), **f64),
-            positions.new_empty((n, 3, 3), **f64))
-
-
-def _qd_backward(name, bwd_op, refused):
-    """Autograd of a quadrupole op: `refused` maps the positions of inputs without an adjoint (cell, alpha, k_vectors) to their names."""
-    def backward(ctx, g_e, *g_explicit):
-        for what, g in zip(_QD_OUTPUTS[1:], g_explicit):
-            if g is not None:
-                raise NotImplementedError(_SECOND_ORDER.format(op=name, what=what))
-        need = ctx.needs_input_grad
-        for k, what in refused.items():
-            if need[k]:
-                raise NotImplementedError(_QD_NO_GRAD.format(op=name, what=what))
-        if g_e is None:
-            return (None,) * len(need)
-        saved = ctx.saved_tensors
-        positions, charges, dipoles, quadrupoles = saved[:4]
-        gpos, gq, gmu, gqd = bwd_op(*saved, *ctx.extra, g_e)
-        return (gpos.to(positions.dtype) if need[0] else None, gq.to(charges.dtype) if need[1] else None,
-                gmu.to(dipoles.dtype) if need[2] else None, gqd.to(quadrupoles.dtype) if need[3] else None) + (None,) * (len(need) - 4)
-
-    return backward
-
-
-def _qd_real_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, quadrupoles: Tensor, cell: Tensor, alpha: Tensor,
-                 batch_idx: Optional[Tensor], neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
-                 neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int, compute_forces: bool,
-                 compute_charge_gradients: bool, compute_dipole_gradients: bool, compute_quadrupole_gradients: bool,
-                 compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
-    from nvalchemiops.interactions.electrostatics.quadrupole import _real_forward
-
-    out = _real_forward(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
-                        neighbor_matrix, neighbor_matrix_shifts, int(mask_value), compute_forces, compute_charge_gradients,
-                        compute_dipole_gradients, compute_quadrupole_gradients, compute_virial)
-    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
-
-
-def _qd_real_fwd_fake(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
-                      neighbor_matrix, neighbor_matrix_shifts, mask_value, compute_forces, compute_charge_gradients, compute_dipole_gradients,
-                      compute_quadrupole_gradients, compute_virial):
-    nsys = cell.reshape(-1, 3, 3).shape[0] if batch_idx is not None else 1
-    return _qd_fake(positions, nsys, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_quadrupole_gradients,
-                    compute_virial)
-
-
-def _qd_real_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, quadrupoles: Tensor, cell: Tensor, alpha: Tensor,
-                 batch_idx: Optional[Tensor], neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
-                 neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int,
-                 grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor]:
-    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles, dL/dquadrupoles) for L = sum_i g_i E_i."""
-    from nvalchemiops.interactions.electrostatics.quadrupole import _real_adjoint
-
-    return _real_adjoint(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
-                         neighbor_matrix, neighbor_matrix_shifts, int(mask_value), grad_energies)
-
-
-ewald_quadrupole_real_bwd_op = torch.library.custom_op("nvalchemiops::ewald_quadrupole_real_space_backward", _qd_real_bwd, mutates_args=())
-ewald_quadrupole_real_bwd_op.register_fake(_qd_bwd_fake)
-ewald_quadrupole_real_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::ewald_quadrupole_real_space_backward"),
-                                               setup_context=lambda ctx, inputs, output: None)
-
-
-def _qd_real_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs[:12])
-    ctx.extra = (int(inputs[12]),)
-    ctx.set_materialize_grads(False)
-
-
-ewald_quadrupole_real_space_op = _op("_ewald_quadrupole_real_space", _qd_real_fwd, _qd_real_fwd_fake,
-                                     _qd_backward(f"{_NS}::_ewald_quadrupole_real_space", ewald_quadrupole_real_bwd_op, {4: "cell", 5: "alpha"}),
-                                     _qd_real_setup)
-
-
-def _qd_recip_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, quadrupoles: Tensor, cell: Tensor, k_vectors: Tensor, alpha: Tensor,
-                  batch_idx: Optional[Tensor], compute_forces: bool, compute_charge_gradients: bool, compute_dipole_gradients: bool,
-                  compute_quadrupole_gradients: bool, compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
-    from nvalchemiops.interactions.electrostatics.quadrupole import _recip_forward
-
-    out = _recip_forward(positions, charges, dipoles, quadrupoles, cell, k_vectors, alpha, batch_idx, compute_forces, compute_charge_gradients,
-                         compute_dipole_gradients, compute_quadrupole_gradients, compute_virial)
-    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
-
-
-def _qd_recip_fwd_fake(positions, charges, dipoles, quadrupoles, cell, k_vectors, alpha, batch_idx, compute_forces, compute_charge_gradients,
-                       compute_dipole_gradients, compute_quadrupole_gradients, compute_virial):
-    return _qd_fake(positions, cell.reshape(-1, 3, 3).shape[0], compute_forces, compute_charge_gradients, compute_dipole_gradients,
-                    compute_quadrupole_gradients, compute_virial)
-
-
-def _qd_recip_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, quadrupoles: Tensor, cell: Tensor, k_vectors: Tensor, alpha: Tensor,
-                  batch_idx: Optional[Tensor], grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor]:
-    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles, dL/dquadrupoles) for L = sum_i g_i E_i."""
-    from nvalchemiops.interactions.electrostatics.quadrupole import _recip_adjoint
-
-    return _recip_adjoint(positions, charges, dipoles, quadrupoles, cell, k_vectors, alpha, batch_idx, grad_energies)
-
-
-ewald_quadrupole_recip_bwd_op = torch.library.custom_op("nvalchemiops::ewald_quadrupole_reciprocal_space_backward", _qd_recip_bwd,
-                                                        mutates_args=())
-ewald_quadrupole_recip_bwd_op.register_fake(_qd_bwd_fake)
-ewald_quadrupole_recip_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::ewald_quadrupole_reciprocal_space_backward"),
-                                                setup_context=lambda ctx, inputs, output: None)
-
-
-def _qd_recip_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs[:8])
-    ctx.extra = ()
-    ctx.set_materialize_grads(False)
-
-
-ewald_quadrupole_reciprocal_space_op = _op("_ewald_quadrupole_reciprocal_space", _qd_recip_fwd, _qd_recip_fwd_fake,
-                                           _qd_backward(f"{_NS}::_ewald_quadrupole_reciprocal_space", ewald_quadrupole_recip_bwd_op,
-                                                        {4: "cell", 5: "k_vectors", 6: "alpha"}), _qd_recip_setup)
-
-
-# point-quadrupole PME, mesh half: the pattern of the point-dipole PME op with the quadrupoles as a fourth differentiable input and six outputs
-def _qd_pme_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, quadrupoles: Tensor, cell: Tensor, alpha: Tensor, batch_idx: Optional[Tensor],
-                nx: int, ny: int, nz: int, spline_order: int, compute_forces: bool, compute_charge_gradients: bool, compute_dipole_gradients: bool,
-                compute_quadrupole_gradients: bool, compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
-    from nvalchemiops.interactions.electrostatics.pme_quadrupole import _recip_forward
-
-    out = _recip_forward(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, (int(nx), int(ny), int(nz)), int(spline_order),
-                         compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_quadrupole_gradients, compute_virial)
-    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
-
-
-def _qd_pme_fwd_fake(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, nx, ny, nz, spline_order, compute_forces,
-                     compute_charge_gradients, compute_dipole_gradients, compute_quadrupole_gradients, compute_virial):
-    nsys = cell.reshape(-1, 3, 3).shape[0] if batch_idx is not None else 1
-    return _qd_fake(positions, nsys, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_quadrupole_gradients,
-                    compute_virial)
-
-
-def _qd_pme_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, quadrupoles: Tensor, cell: Tensor, alpha: Tensor, batch_idx: Optional[Tensor],
-                nx: int, ny: int, nz: int, spline_order: int, grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor]:
-    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles, dL/dquadrupoles) for L = sum_i g_i E_i."""
-    from nvalchemiops.interactions.electrostatics.pme_quadrupole import _recip_adjoint
-
-    return _recip_adjoint(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, (int(nx), int(ny), int(nz)), int(spline_order),
-                          grad_energies)
-
-
-pme_quadrupole_recip_bwd_op = torch.library.custom_op("nvalchemiops::pme_quadrupole_reciprocal_space_backward", _qd_pme_bwd, mutates_args=())
-pme_quadrupole_recip_bwd_op.register_fake(_qd_bwd_fake)
-pme_quadrupole_recip_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::pme_quadrupole_reciprocal_space_backward"),
-                                              setup_context=lambda ctx, inputs, output: None)
-
-
-def _qd_pme_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs[:7])
-    ctx.extra = tuple(int(v) for v in inputs[7:11])
-    ctx.set_materialize_grads(False)
-
-
-pme_quadrupole_reciprocal_space_op = _op("_pme_quadrupole_reciprocal_space", _qd_pme_fwd, _qd_pme_fwd_fake,
-                                         _qd_backward(f"{_NS}::_pme_quadrupole_reciprocal_space", pme_quadrupole_recip_bwd_op,
-                                                      {4: "cell", 5: "alpha"}), _qd_pme_setup)
-
-
-# cluster point multipoles (the bare dipole and quadrupole pair sums): the pattern of the Thole op -- an optional cell (clusters) that has no
-# adjoint and is refused, the outputs of the real-space dipole / quadrupole ops.
+_TH_NO_GRAD = ("{op}: gradients w.r.t. cell are not provided by the Thole damping term (out of scope); use "
+               "compute_virial for the strain derivative.")
 _CL_NO_GRAD = ("{op}: gradients w.r.t. cell are not provided by the bare multipole pair sums (out of scope); use compute_virial for the strain "
                "derivative.")
+_PER_ATOM = {"positions": (3,), "charges": (), "dipoles": (3,), "quadrupoles": (3, 3), "polarizability": ()}  # shapes after [n]
+_SCALARS = {"SymInt": int, "float": float}  # schema type of a plain scalar -> the conversion `ctx.extra` and the launch functions get
+_SYSTEMS = {  # the fake's number of systems, from (cell, batch_idx)
+    "batch": lambda cell, batch_idx: cell.reshape(-1, 3, 3).shape[0] if batch_idx is not None else 1,
+    "optional cell": lambda cell, batch_idx: cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1,
+    "cell rows": lambda cell, batch_idx: cell.reshape(-1, 3, 3).shape[0],
+}
+_DP, _QD, _TH = ("positions", "charges", "dipoles"), ("positions", "charges", "dipoles", "quadrupoles"), ("positions", "charges", "dipoles",
+                                                                                                            "polarizability")
+_QG, _PG = ("quadrupole_gradients", (3, 3)), ("polarizability_gradients", ())
+_LISTS = ("Tensor? batch_idx, Tensor? neighbor_list, Tensor? neighbor_ptr, Tensor? neighbor_shifts, Tensor? neighbor_matrix, "
+          "Tensor? neighbor_matrix_shifts, SymInt mask_value")
+_MESH = "Tensor cell, Tensor alpha, Tensor? batch_idx, SymInt nx, SymInt ny, SymInt nz, SymInt spline_order"
+_KSUM = "Tensor cell, Tensor k_vectors, Tensor alpha, Tensor? batch_idx"
+# op name: (module under interactions/electrostatics, its forward, its adjoint, differentiable inputs, middle arguments (a `Tensor` is saved
+# for backward, a scalar travels in ctx.extra), extra output | None, system-count rule, inputs without an adjoint, refusal text)
+_MULTIPOLE_OPS = {
+    "ewald_dipole_real_space": ("dipole", "_real_forward", "_real_adjoint", _DP, f"Tensor cell, Tensor alpha, {_LISTS}", None, "batch",
+                                ("cell", "alpha"), _DP_NO_GRAD),
+    "ewald_dipole_reciprocal_space": ("dipole", "_recip_forward", "_recip_adjoint", _DP, _KSUM, None, "cell rows",
+                                      ("cell", "k_vectors", "alpha"), _DP_NO_GRAD),
+    "pme_dipole_reciprocal_space": ("pme_dipole", "_recip_forward", "_recip_adjoint", _DP, _MESH, None, "batch", ("cell", "alpha"), _DP_NO_GRAD),
+    "thole_dipole_correction": ("thole", "_forward", "_adjoint", _TH, f"Tensor? cell, {_LISTS}, float thole", _PG, "optional cell", ("cell",),
+                                _TH_NO_GRAD),
+    "ewald_quadrupole_real_space": ("quadrupole", "_real_forward", "_real_adjoint", _QD, f"Tensor cell, Tensor alpha, {_LISTS}", _QG, "batch",
+                                    ("cell", "alpha"), _QD_NO_GRAD),
+    "ewald_quadrupole_reciprocal_space": ("quadrupole", "_recip_forward", "_recip_adjoint", _QD, _KSUM, _QG, "cell rows",
+                                          ("cell", "k_vectors", "alpha"), _QD_NO_GRAD),
+    "pme_quadrupole_reciprocal_space": ("pme_quadrupole", "_recip_forward", "_recip_adjoint", _QD, _MESH, _QG, "batch", ("cell", "alpha"),
+                                        _QD_NO_GRAD),
+    "coulomb_dipole_correction": ("cluster", "_dipole_forward", "_dipole_adjoint", _DP, f"Tensor? cell, {_LISTS}", None, "optional cell",
+                                  ("cell",), _CL_NO_GRAD),
+    "coulomb_quadrupole_correction": ("cluster", "_quadrupole_forward", "_quadrupole_adjoint", _QD, f"Tensor? cell, {_LISTS}", _QG,
+                                      "optional cell", ("cell",), _CL_NO_GRAD),
+}
 
 
-def _cl_nsys(cell, batch_idx):
-    return cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1
+def _multipole_ops(name, module, forward, adjoint, diff, middle, extra, systems, no_adjoint, refusal):
+    """(forward op `alchemiops::_<name>`, backward op `nvalchemiops::<name>_backward`) of one row of `_MULTIPOLE_OPS`, with their fakes, the
+    second-order refusal on the backward op and the forward op's autograd."""
+    fwd_name, bwd_name = f"{_NS}::_{name}", f"nvalchemiops::{name}_backward"
+    mid = [a.split() for a in middle.split(", ")]  # [schema type, argument name]
+    names = list(diff) + [a[1] for a in mid]
+    n_diff, n_in = len(diff), len(names)
+    k = n_diff + sum(t.startswith("Tensor") for t, _ in mid)  # the tensors lead, the plain scalars trail
+    convert = [_SCALARS[t] for t, _ in mid[k - n_diff:]]
+    outputs = (("energies", ()), ("forces", (3,)), ("charge_gradients", ()), ("dipole_gradients", (3,))) + ((extra,) if extra else ())
+    i_cell, i_batch, nsys_of = names.index("cell"), names.index("batch_idx"), _SYSTEMS[systems]
+    refused = {names.index(what): what for what in no_adjoint}
+    inputs = ", ".join([f"Tensor {d}" for d in diff] + [middle])
+    flags = ", ".join(f"bool compute_{o}" for o, _ in outputs[1:]) + ", bool compute_virial"
 
+    def run(fn_name, args, tail):
+        fn = getattr(importlib.import_module(f"nvalchemiops.interactions.electrostatics.{module}"), fn_name)
+        return fn(*args[:k], *[c(v) for c, v in zip(convert, args[k:n_in])], *tail)
 
-def _cl_backward(name, bwd_op, outputs, n_diff):
-    """Autograd of a cluster op: the first `n_diff` inputs are differentiable, the cell follows them."""
+    def fwd(*args):
+        return tuple(args[0].new_empty((0,)) if o is None else o for o in run(forward, args, args[n_in:]))
+
+    def fwd_fake(*args):
+        positions, want = args[0], (True,) + tuple(args[n_in:])
+        shapes = [(positions.shape[0],) + s for _, s in outputs] + [(nsys_of(args[i_cell], args[i_batch]), 3, 3)]
+        return tuple(positions.new_empty(s if w else (0,)) for s, w in zip(shapes, want))
+
+    def bwd(*args):
+        return run(adjoint, args, (args[n_in],))
+
+    def bwd_fake(positions, *rest):
+        return tuple(positions.new_empty((positions.shape[0],) + _PER_ATOM[d], dtype=torch.float64) for d in diff)
+
+    def refuse_second_order(ctx, *grads):
+        raise NotImplementedError(_SECOND_ORDER.format(op=bwd_name, what="gradient"))
+
+    bwd_op = torch.library.custom_op(bwd_name, bwd, mutates_args=(),
+                                     schema=f"({inputs}, Tensor grad_energies) -> ({', '.join(['Tensor'] * n_diff)})")
+    bwd_op.register_fake(bwd_fake)
+    bwd_op.register_autograd(refuse_second_order, setup_context=lambda ctx, inputs, output: None)
+
+    def setup(ctx, inputs, output):
+        ctx.save_for_backward(*inputs[:k])
+        ctx.extra = tuple(c(v) for c, v in zip(convert, inputs[k:n_in]))
+        ctx.set_materialize_grads(False)
+
     def backward(ctx, g_e, *g_explicit):
-        for what, g in zip(outputs[1:], g_explicit):
+        for (what, _), g in zip(outputs[1:] + (("virial", None),), g_explicit):
             if g is not None:
-                raise NotImplementedError(_SECOND_ORDER.format(op=name, what=what))
+                raise NotImplementedError(_SECOND_ORDER.format(op=fwd_name, what=what))
         need = ctx.needs_input_grad
-        if need[n_diff]:
-            raise NotImplementedError(_CL_NO_GRAD.format(op=name))
+        for i, what in refused.items():
+            if need[i]:
+                raise NotImplementedError(refusal.format(op=fwd_name, what=what))
         if g_e is None:
             return (None,) * len(need)
         saved = ctx.saved_tensors
         grads = bwd_op(*saved, *ctx.extra, g_e)
         return tuple(g.to(t.dtype) if w else None for g, t, w in zip(grads, saved[:n_diff], need[:n_diff])) + (None,) * (len(need) - n_diff)
 
-    return backward
+    fwd_op = torch.library.custom_op(fwd_name, fwd, mutates_args=(),
+                                     schema=f"({inputs}, {flags}) -> ({', '.join(['Tensor'] * (len(outputs) + 1))})")
+    fwd_op.register_fake(fwd_fake)
+    fwd_op.register_autograd(backward, setup_context=setup)
+    return fwd_op, bwd_op
 
 
-def _cl_dp_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor],
-               neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
-               neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int, compute_forces: bool,
-               compute_charge_gradients: bool, compute_dipole_gradients: bool, compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    from nvalchemiops.interactions.electrostatics.cluster import _dipole_forward
-
-    out = _dipole_forward(positions, charges, dipoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                          neighbor_matrix_shifts, int(mask_value), compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
-    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
-
-
-def _cl_dp_fwd_fake(positions, charges, dipoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                    neighbor_matrix_shifts, mask_value, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial):
-    return _dp_fake(positions, _cl_nsys(cell, batch_idx), compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
-
-
-def _cl_dp_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor],
-               neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
-               neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int,
-               grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor]:
-    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles) for L = sum_i g_i E_i."""
-    from nvalchemiops.interactions.electrostatics.cluster import _dipole_adjoint
-
-    return _dipole_adjoint(positions, charges, dipoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                           neighbor_matrix_shifts, int(mask_value), grad_energies)
-
-
-coulomb_dipole_bwd_op = torch.library.custom_op("nvalchemiops::coulomb_dipole_correction_backward", _cl_dp_bwd, mutates_args=())
-coulomb_dipole_bwd_op.register_fake(lambda positions, *rest: _dp_bwd_fake(positions))
-coulomb_dipole_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::coulomb_dipole_correction_backward"),
-                                        setup_context=lambda ctx, inputs, output: None)
-
-
-def _cl_dp_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs[:10])
-    ctx.extra = (int(inputs[10]),)
-    ctx.set_materialize_grads(False)
-
-
-coulomb_dipole_correction_op = _op("_coulomb_dipole_correction", _cl_dp_fwd, _cl_dp_fwd_fake,
-                                   _cl_backward(f"{_NS}::_coulomb_dipole_correction", coulomb_dipole_bwd_op, _DP_OUTPUTS, 3), _cl_dp_setup)
-
-
-def _cl_qd_fwd(positions: Tensor, charges: Tensor, dipoles: Tensor, quadrupoles: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor],
-               neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
-               neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int, compute_forces: bool,
-               compute_charge_gradients: bool, compute_dipole_gradients: bool, compute_quadrupole_gradients: bool,
-               compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
-    from nvalchemiops.interactions.electrostatics.cluster import _quadrupole_forward
-
-    out = _quadrupole_forward(positions, charges, dipoles, quadrupoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
-                              neighbor_matrix, neighbor_matrix_shifts, int(mask_value), compute_forces, compute_charge_gradients,
-                              compute_dipole_gradients, compute_quadrupole_gradients, compute_virial)
-    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
-
-
-def _cl_qd_fwd_fake(positions, charges, dipoles, quadrupoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                    neighbor_matrix_shifts, mask_value, compute_forces, compute_charge_gradients, compute_dipole_gradients,
-                    compute_quadrupole_gradients, compute_virial):
-    return _qd_fake(positions, _cl_nsys(cell, batch_idx), compute_forces, compute_charge_gradients, compute_dipole_gradients,
-                    compute_quadrupole_gradients, compute_virial)
-
-
-def _cl_qd_bwd(positions: Tensor, charges: Tensor, dipoles: Tensor, quadrupoles: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor],
-               neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
-               neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int,
-               grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor]:
-    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles, dL/dquadrupoles) for L = sum_i g_i E_i."""
-    from nvalchemiops.interactions.electrostatics.cluster import _quadrupole_adjoint
-
-    return _quadrupole_adjoint(positions, charges, dipoles, quadrupoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
-                               neighbor_matrix, neighbor_matrix_shifts, int(mask_value), grad_energies)
-
-
-coulomb_quadrupole_bwd_op = torch.library.custom_op("nvalchemiops::coulomb_quadrupole_correction_backward", _cl_qd_bwd, mutates_args=())
-coulomb_quadrupole_bwd_op.register_fake(_qd_bwd_fake)
-coulomb_quadrupole_bwd_op.register_autograd(_dp_refuse_second_order("nvalchemiops::coulomb_quadrupole_correction_backward"),
-                                            setup_context=lambda ctx, inputs, output: None)
-
-
-def _cl_qd_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs[:11])
-    ctx.extra = (int(inputs[11]),)
-    ctx.set_materialize_grads(False)
-
-
-coulomb_quadrupole_correction_op = _op("_coulomb_quadrupole_correction", _cl_qd_fwd, _cl_qd_fwd_fake,
-                                       _cl_backward(f"{_NS}::_coulomb_quadrupole_correction", coulomb_quadrupole_bwd_op, _QD_OUTPUTS, 4),
-                                       _cl_qd_setup)
+_MP = {name: _multipole_ops(name, *row) for name, row in _MULTIPOLE_OPS.items()}
+ewald_dipole_real_space_op, ewald_dipole_real_bwd_op = _MP["ewald_dipole_real_space"]
+ewald_dipole_reciprocal_space_op, ewald_dipole_recip_bwd_op = _MP["ewald_dipole_reciprocal_space"]
+pme_dipole_reciprocal_space_op, pme_dipole_recip_bwd_op = _MP["pme_dipole_reciprocal_space"]
+thole_dipole_correction_op, thole_dipole_bwd_op = _MP["thole_dipole_correction"]
+ewald_quadrupole_real_space_op, ewald_quadrupole_real_bwd_op = _MP["ewald_quadrupole_real_space"]
+ewald_quadrupole_reciprocal_space_op, ewald_quadrupole_recip_bwd_op = _MP["ewald_quadrupole_reciprocal_space"]
+pme_quadrupole_reciprocal_space_op, pme_quadrupole_recip_bwd_op = _MP["pme_quadrupole_reciprocal_space"]
+coulomb_dipole_correction_op, coulomb_dipole_bwd_op = _MP["coulomb_dipole_correction"]
+coulomb_quadrupole_correction_op, coulomb_quadrupole_bwd_op = _MP["coulomb_quadrupole_correction"]
 
 
 __all__ = ["coulomb_dipole_correction_op", "coulomb_dipole_bwd_op", "coulomb_quadrupole_correction_op", "coulomb_quadrupole_bwd_op",

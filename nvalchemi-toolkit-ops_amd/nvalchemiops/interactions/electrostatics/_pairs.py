@@ -7,7 +7,8 @@ import torch
 
 from nvalchemiops import _capi as C
 
-FORCES, CHARGE_GRAD, THIRD_GRAD, VIRIAL = 1, 2, 4, 8  # MI_GC_* / MI_DP_*: the third gradient is dE/dsigma or dE/dmu
+# MI_GC_* / MI_DP_* / MI_QD_*: the third gradient is dE/dsigma or dE/dmu, the fourth dE/dQ (MI_QD_QUADRUPOLE_GRAD) or dE/da (MI_DP_POLAR_GRAD)
+FORCES, CHARGE_GRAD, THIRD_GRAD, VIRIAL, FOURTH_GRAD = 1, 2, 4, 8, 16
 
 
 def check_lists(positions, charges, sigma, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx,
@@ -66,20 +67,23 @@ def list_inputs(neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, n
     return dict(idx=idx, nptr=nptr, m=m, sh=None if sh is None else C.i32(sh), n_entries=idx.numel())
 
 
-def launch_inputs(positions, charges, cell, batch_idx, lists, **per_atom):
+def launch_inputs(positions, charges, cell, batch_idx, lists, mask=None, **per_atom):
     """Detached, contiguous launch tensors in the positions dtype (device check included; shapes were checked before): `list_inputs(*lists)`
-    plus pos, q, cells | None, bi | None (int32, only with a cell), nsys, and the caller's own arrays under their keywords."""
+    plus pos, q, cells | None, bi | None (int32, only with a cell), nsys, the caller's own arrays under their keywords, and `mask`, the
+    list's padding value as the operators that keep it in this dict pass it."""
     dt = positions.dtype
     C.require_device(positions, charges, *per_atom.values(), cell, *lists, batch_idx)
     conv = lambda t: t.detach().to(dt).contiguous()  # noqa: E731
     cells = None if cell is None else conv(cell.reshape(-1, 3, 3))
     batched = batch_idx is not None and cells is not None
     return dict(pos=positions.detach().contiguous(), q=conv(charges), cells=cells, bi=C.i32(batch_idx) if batched else None,
-                nsys=cells.shape[0] if batched else 1, **{k: conv(v) for k, v in per_atom.items()}, **list_inputs(*lists))
+                nsys=cells.shape[0] if batched else 1, mask=mask, **{k: conv(v) for k, v in per_atom.items()}, **list_inputs(*lists))
 
 
-def flag_bits(forces, charge_grads, third_grads, virial) -> int:
-    return (FORCES if forces else 0) | (CHARGE_GRAD if charge_grads else 0) | (THIRD_GRAD if third_grads else 0) | (VIRIAL if virial else 0)
+def flag_bits(want) -> int:
+    """The flag word of a pair kernel for `want` = (energies, forces, charge gradient, third gradient[, fourth gradient], virial)."""
+    bits = (FORCES if want[1] else 0) | (CHARGE_GRAD if want[2] else 0) | (THIRD_GRAD if want[3] else 0) | (VIRIAL if want[-1] else 0)
+    return bits | FOURTH_GRAD if len(want) == 6 and want[4] else bits
 
 
 def needs_op(*tensors) -> bool:
@@ -87,10 +91,11 @@ def needs_op(*tensors) -> bool:
     return C.tracing() or (torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors))
 
 
-def zeros(n, nsys, dt, dev, third_is_vector: bool = True):
-    """All five outputs of an operator as zeros: energies, forces, charge_grads, the third gradient ([n, 3] dipole or [n] sigma), virial."""
+def zeros(n, nsys, dt, dev, *grads):
+    """All outputs of an operator as zeros: energies, forces, one gradient per per-atom shape in `grads` (() charges or sigma, (3,) dipoles,
+    (3, 3) quadrupoles), virial."""
     z = lambda *shape: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
-    return z(n), z(n, 3), z(n), z(n, 3) if third_is_vector else z(n), z(nsys, 3, 3)
+    return (z(n), z(n, 3)) + tuple(z(n, *s) for s in grads) + (z(nsys, 3, 3),)
 
 
 def select(res, want):

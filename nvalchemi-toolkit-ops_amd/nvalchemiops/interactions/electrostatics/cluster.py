@@ -25,6 +25,7 @@ import ctypes
 import torch
 
 from nvalchemiops import _capi as C
+from nvalchemiops.interactions.electrostatics import _multipoles as M
 from nvalchemiops.interactions.electrostatics import _pairs as P
 from nvalchemiops.interactions.electrostatics import induced as I
 from nvalchemiops.interactions.electrostatics import quadrupole as Q
@@ -41,42 +42,30 @@ _LISTS = """THE LIST MUST BE FULL (symmetric: every pair stored from both ends),
 
 def _check(positions, charges, dipoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx,
            compute_virial):
-    """Every argument error, before anything is launched: `_pairs.check_dipole_lists` with a cell, the cell-less rules of `_pairs.check_lists`
-    without one."""
-    if positions.dim() != 2 or positions.shape[1] != 3:
-        raise ValueError(f"positions must have shape [num_atoms, 3], got {tuple(positions.shape)}")
-    if neighbor_list is not None and neighbor_matrix is not None:
-        raise ValueError("pass the list in ONE format: neighbor_list (with neighbor_ptr) or neighbor_matrix, not both")
-    if cell is None:
-        P.check_lists(positions, charges, 0.0, None, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx,
-                      compute_virial)
-        P.check_dipoles(positions, dipoles)
-    else:
-        P.check_dipole_lists(positions, charges, dipoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts,
-                             batch_idx, None, compute_virial)
-
-
-def _num_systems(cell, batch_idx) -> int:
-    return cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1
+    """Every argument error, before anything is launched."""
+    M.check_positions_and_format(positions, neighbor_list, neighbor_matrix)
+    M.check_optional_cell_lists(positions, charges, dipoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                                neighbor_matrix_shifts, batch_idx, compute_virial)
 
 
 # ---- dipoles ------------------------------------------------------------------------------------------------------------------------------
-def _dipole_launch(p, mask_value: int, flags: int, weights=None, energies: bool = True):
+def _dipole_inputs(positions, charges, dipoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                   neighbor_matrix_shifts, mask_value):
+    lists = (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
+    return P.launch_inputs(positions, charges, cell, batch_idx, lists, int(mask_value), mu=dipoles)
+
+
+def _dipole_launch(p, flags: int, weights=None, energies: bool = True):
     """One `mi_coulomb_dipole` launch: float64 (energies | None, forces in the positions dtype | None, charge sums | None, dipole sums | None,
     virial block partials [nsys, blocks, 9] | None)."""
     pos = p["pos"]
-    n, dev, dt = pos.shape[0], pos.device, pos.dtype
+    n, dt = pos.shape[0], pos.dtype
     L = C.lib()
-    f64 = dict(dtype=torch.float64, device=dev)
-    e = torch.empty(n, **f64) if energies else None
-    f = torch.empty((n, 3), dtype=dt, device=dev) if flags & P.FORCES else None
-    cg = torch.empty(n, **f64) if flags & P.CHARGE_GRAD else None
-    dg = torch.empty((n, 3), **f64) if flags & P.THIRD_GRAD else None
-    part = torch.empty((p["nsys"], int(L.mi_coulomb_dipole_blocks()), 9), **f64) if flags & P.VIRIAL else None
+    e, f, cg, dg = M.allocate(pos, M.DIPOLE, (energies, flags & P.FORCES, flags & P.CHARGE_GRAD, flags & P.THIRD_GRAD))
     nbytes = int(L.mi_coulomb_dipole_scratch_bytes(n, C.dtype_code(dt)))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    part, scratch = M.pair_scratch(p, flags, int(L.mi_coulomb_dipole_blocks()), nbytes)
     rc = L.mi_coulomb_dipole(C.ptr(pos), C.ptr(p["q"]), C.ptr(p["mu"]), C.ptr(p["cells"]), C.ptr(p["bi"]), C.ptr(weights), n, int(p["nsys"]),
-                             C.dtype_code(dt), C.ptr(p["idx"]), C.ptr(p["sh"]), C.ptr(p["nptr"]), int(p["m"]), int(mask_value), int(flags),
+                             C.dtype_code(dt), C.ptr(p["idx"]), C.ptr(p["sh"]), C.ptr(p["nptr"]), int(p["m"]), p["mask"], int(flags),
                              C.ptr(e), C.ptr(f), C.ptr(cg), C.ptr(dg), C.ptr(part), C.ptr(scratch), ctypes.c_size_t(nbytes), C.stream_of(pos))
     C.check(rc, "mi_coulomb_dipole")
     return e, f, cg, dg, part
@@ -86,28 +75,17 @@ def _dipole_forward(positions, charges, dipoles, cell, batch_idx, neighbor_list,
                     neighbor_matrix_shifts, mask_value, forces, cgrads, dgrads, virial):
     """(energies, forces | None, charge_grads | None, dipole_grads | None, virial | None) in the positions dtype, no autograd graph: what the
     eager call and the `alchemiops::_coulomb_dipole_correction` op both run."""
-    p = P.launch_inputs(positions, charges, cell, batch_idx, (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts),
-                        mu=dipoles)
-    n, dev, dt = positions.shape[0], positions.device, positions.dtype
-    if n == 0 or p["n_entries"] == 0:
-        res = P.zeros(n, p["nsys"], dt, dev)
-        return tuple(r if w else None for r, w in zip(res, (True, forces, cgrads, dgrads, virial)))
-    e, f, cg, dg, part = _dipole_launch(p, mask_value, P.flag_bits(forces, cgrads, dgrads, virial))
-    return (e.to(dt), f, cg.to(dt) if cgrads else None, dg.to(dt) if dgrads else None, C.fold_virial9(part).to(dt) if virial else None)
+    p = _dipole_inputs(positions, charges, dipoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                       neighbor_matrix_shifts, mask_value)
+    return M.pair_forward(p, _dipole_launch, M.DIPOLE, (True, forces, cgrads, dgrads, virial))
 
 
 def _dipole_adjoint(positions, charges, dipoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
                     neighbor_matrix_shifts, mask_value, grad_energies):
     """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles) of L = sum_i g_i E_i: the forward kernel with weights."""
-    p = P.launch_inputs(positions, charges, cell, batch_idx, (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts),
-                        mu=dipoles)
-    n, dev = positions.shape[0], positions.device
-    f64 = dict(dtype=torch.float64, device=dev)
-    if n == 0 or p["n_entries"] == 0:
-        return torch.zeros((n, 3), **f64), torch.zeros(n, **f64), torch.zeros((n, 3), **f64)
-    g = grad_energies.detach().to(torch.float64).contiguous()
-    _, f, gq, gmu, _ = _dipole_launch(p, mask_value, P.FORCES | P.CHARGE_GRAD | P.THIRD_GRAD, weights=g, energies=False)
-    return -f.to(torch.float64), gq, gmu
+    p = _dipole_inputs(positions, charges, dipoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                       neighbor_matrix_shifts, mask_value)
+    return M.pair_adjoint(p, _dipole_launch, M.DIPOLE, grad_energies)
 
 
 @C.traceable
@@ -142,44 +120,33 @@ def coulomb_dipole_correction(positions: torch.Tensor, charges: torch.Tensor, di
     field, octupoles.  CPU tensors raise NativeLibraryError: there is no fallback."""
     _check(positions, charges, dipoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx,
            compute_virial)
-    n, dev, dt = positions.shape[0], positions.device, positions.dtype
     want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
-    if n == 0:
-        return P.select(P.zeros(0, _num_systems(cell, batch_idx), dt, dev), want)
-    lists = (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
-    flags = tuple(bool(w) for w in want[1:])
-    if P.needs_op(positions, charges, dipoles, cell):
-        from nvalchemiops import _eops
-
-        res = _eops.coulomb_dipole_correction_op(positions, charges.to(dt), dipoles.to(dt), cell, batch_idx, *lists, int(mask_value), *flags)
-    else:
-        res = _dipole_forward(positions, charges, dipoles, cell, batch_idx, *lists, int(mask_value), *flags)
-    return P.select(res, want)
+    if positions.shape[0] == 0:
+        return M.no_atoms(positions, M.num_systems(cell, batch_idx), M.DIPOLE, want)
+    return M.dispatch("coulomb_dipole_correction_op", _dipole_forward, (positions, charges, dipoles), (cell,),
+                      (batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, int(mask_value)), want)
 
 
 # ---- quadrupoles --------------------------------------------------------------------------------------------------------------------------
-def _quadrupole_inputs(positions, charges, dipoles, quadrupoles, cell, batch_idx, *lists):
-    return P.launch_inputs(positions, charges, cell, batch_idx, lists, mu=dipoles, qd=quadrupoles)
+def _quadrupole_inputs(positions, charges, dipoles, quadrupoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                       neighbor_matrix_shifts, mask_value):
+    lists = (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
+    return P.launch_inputs(positions, charges, cell, batch_idx, lists, int(mask_value), mu=dipoles, qd=quadrupoles)
 
 
-def _quadrupole_launch(p, mask_value: int, flags: int, weights=None, energies: bool = True):
+def _quadrupole_launch(p, flags: int, weights=None, energies: bool = True):
     """One `mi_coulomb_quadrupole` launch: float64 (energies | None, forces in the positions dtype | None, charge sums | None, dipole sums |
     None, quadrupole sums [n, 3, 3] | None, virial block partials [nsys, blocks, 9] | None)."""
     pos = p["pos"]
-    n, dev, dt = pos.shape[0], pos.device, pos.dtype
+    n, dt = pos.shape[0], pos.dtype
     L = C.lib()
-    f64 = dict(dtype=torch.float64, device=dev)
-    e = torch.empty(n, **f64) if energies else None
-    f = torch.empty((n, 3), dtype=dt, device=dev) if flags & Q.QD_FORCES else None
-    cg = torch.empty(n, **f64) if flags & Q.QD_CHARGE_GRAD else None
-    dg = torch.empty((n, 3), **f64) if flags & Q.QD_DIPOLE_GRAD else None
-    qg = torch.empty((n, 3, 3), **f64) if flags & Q.QD_QUADRUPOLE_GRAD else None
-    part = torch.empty((p["nsys"], int(L.mi_coulomb_quadrupole_blocks()), 9), **f64) if flags & Q.QD_VIRIAL else None
+    e, f, cg, dg, qg = M.allocate(pos, M.QUADRUPOLE, (energies, flags & P.FORCES, flags & P.CHARGE_GRAD, flags & P.THIRD_GRAD,
+                                                      flags & P.FOURTH_GRAD))
     nbytes = int(L.mi_coulomb_quadrupole_scratch_bytes(n, C.dtype_code(dt)))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    part, scratch = M.pair_scratch(p, flags, int(L.mi_coulomb_quadrupole_blocks()), nbytes)
     rc = L.mi_coulomb_quadrupole(C.ptr(pos), C.ptr(p["q"]), C.ptr(p["mu"]), C.ptr(p["qd"]), C.ptr(p["cells"]), C.ptr(p["bi"]), C.ptr(weights), n,
                                  int(p["nsys"]), C.dtype_code(dt), C.ptr(p["idx"]), C.ptr(p["sh"]), C.ptr(p["nptr"]), int(p["m"]),
-                                 int(mask_value), int(flags), C.ptr(e), C.ptr(f), C.ptr(cg), C.ptr(dg), C.ptr(qg), C.ptr(part), C.ptr(scratch),
+                                 p["mask"], int(flags), C.ptr(e), C.ptr(f), C.ptr(cg), C.ptr(dg), C.ptr(qg), C.ptr(part), C.ptr(scratch),
                                  ctypes.c_size_t(nbytes), C.stream_of(pos))
     C.check(rc, "mi_coulomb_quadrupole")
     return e, f, cg, dg, qg, part
@@ -190,29 +157,16 @@ def _quadrupole_forward(positions, charges, dipoles, quadrupoles, cell, batch_id
     """(energies, forces | None, charge_grads | None, dipole_grads | None, quadrupole_grads | None, virial | None) in the positions dtype, no
     autograd graph: what the eager call and the `alchemiops::_coulomb_quadrupole_correction` op both run."""
     p = _quadrupole_inputs(positions, charges, dipoles, quadrupoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
-                           neighbor_matrix, neighbor_matrix_shifts)
-    n, dev, dt = positions.shape[0], positions.device, positions.dtype
-    want = (True, forces, cgrads, dgrads, qgrads, virial)
-    if n == 0 or p["n_entries"] == 0:
-        return tuple(r if w else None for r, w in zip(Q._zeros(n, p["nsys"], dt, dev), want))
-    e, f, cg, dg, qg, part = _quadrupole_launch(p, mask_value, Q._flag_bits(forces, cgrads, dgrads, qgrads, virial))
-    return (e.to(dt), f, cg.to(dt) if cgrads else None, dg.to(dt) if dgrads else None, qg.to(dt) if qgrads else None,
-            C.fold_virial9(part).to(dt) if virial else None)
+                           neighbor_matrix, neighbor_matrix_shifts, mask_value)
+    return M.pair_forward(p, _quadrupole_launch, M.QUADRUPOLE, (True, forces, cgrads, dgrads, qgrads, virial))
 
 
 def _quadrupole_adjoint(positions, charges, dipoles, quadrupoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
                         neighbor_matrix_shifts, mask_value, grad_energies):
     """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles, dL/dquadrupoles) of L = sum_i g_i E_i: the forward kernel with weights."""
     p = _quadrupole_inputs(positions, charges, dipoles, quadrupoles, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
-                           neighbor_matrix, neighbor_matrix_shifts)
-    n, dev = positions.shape[0], positions.device
-    f64 = dict(dtype=torch.float64, device=dev)
-    if n == 0 or p["n_entries"] == 0:
-        return torch.zeros((n, 3), **f64), torch.zeros(n, **f64), torch.zeros((n, 3), **f64), torch.zeros((n, 3, 3), **f64)
-    g = grad_energies.detach().to(torch.float64).contiguous()
-    _, f, gq, gmu, gqd, _ = _quadrupole_launch(p, mask_value, Q.QD_FORCES | Q.QD_CHARGE_GRAD | Q.QD_DIPOLE_GRAD | Q.QD_QUADRUPOLE_GRAD,
-                                               weights=g, energies=False)
-    return -f.to(torch.float64), gq, gmu, gqd
+                           neighbor_matrix, neighbor_matrix_shifts, mask_value)
+    return M.pair_adjoint(p, _quadrupole_launch, M.QUADRUPOLE, grad_energies)
 
 
 @C.traceable
@@ -254,20 +208,11 @@ def coulomb_quadrupole_correction(positions: torch.Tensor, charges: torch.Tensor
     _check(positions, charges, dipoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx,
            compute_virial)
     Q.check_quadrupoles(positions, quadrupoles)
-    n, dev, dt = positions.shape[0], positions.device, positions.dtype
     want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_quadrupole_gradients, compute_virial)
-    if n == 0:
-        return P.select(Q._zeros(0, _num_systems(cell, batch_idx), dt, dev), want)
-    lists = (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
-    flags = tuple(bool(w) for w in want[1:])
-    if P.needs_op(positions, charges, dipoles, quadrupoles, cell):
-        from nvalchemiops import _eops
-
-        res = _eops.coulomb_quadrupole_correction_op(positions, charges.to(dt), dipoles.to(dt), quadrupoles.to(dt), cell, batch_idx, *lists,
-                                                     int(mask_value), *flags)
-    else:
-        res = _quadrupole_forward(positions, charges, dipoles, quadrupoles, cell, batch_idx, *lists, int(mask_value), *flags)
-    return P.select(res, want)
+    if positions.shape[0] == 0:
+        return M.no_atoms(positions, M.num_systems(cell, batch_idx), M.QUADRUPOLE, want)
+    return M.dispatch("coulomb_quadrupole_correction_op", _quadrupole_forward, (positions, charges, dipoles, quadrupoles), (cell,),
+                      (batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, int(mask_value)), want)
 
 
 for _fn in (coulomb_dipole_correction, coulomb_quadrupole_correction):

@@ -18,10 +18,10 @@ import ctypes
 import torch
 
 from nvalchemiops import _capi as C
+from nvalchemiops.interactions.electrostatics import _multipoles as M
 from nvalchemiops.interactions.electrostatics import _pairs as P
 from nvalchemiops.interactions.electrostatics.ewald import _prepare_alpha, _prepare_cell
 
-DP_FORCES, DP_CHARGE_GRAD, DP_DIPOLE_GRAD, DP_VIRIAL = P.FORCES, P.CHARGE_GRAD, P.THIRD_GRAD, P.VIRIAL
 _TABLE_WORDS = 8  # {Re S_q, Im S_q, Re M_x, Im M_x, Re M_y, Im M_y, Re M_z, Im M_z}
 
 _MODEL = """With R = r_j - r_i + S . cell and r = |R| for every stored entry (i, j, S), B0 = erfc(alpha r) / r,
@@ -50,26 +50,23 @@ _RETURNS = """Returns ``energies`` [N], or a tuple holding only what was asked f
 
 
 # ---- real space ---------------------------------------------------------------------------------------------------------------------------
-def _real_inputs(positions, charges, dipoles, cell, alpha, batch_idx, *lists):
-    return P.launch_inputs(positions, charges, cell, batch_idx, lists, mu=dipoles, al=alpha.reshape(-1))
+def _real_inputs(positions, charges, dipoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                 neighbor_matrix_shifts, mask_value):
+    lists = (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
+    return P.launch_inputs(positions, charges, cell, batch_idx, lists, int(mask_value), mu=dipoles, al=alpha.reshape(-1))
 
 
-def _real_launch(p, mask_value: int, flags: int, weights=None, energies: bool = True):
+def _real_launch(p, flags: int, weights=None, energies: bool = True):
     """One `mi_ewald_dipole_real` launch: float64 (energies | None, forces in the positions dtype | None, charge sums | None, dipole sums | None,
     virial block partials [nsys, blocks, 9] | None)."""
     pos = p["pos"]
-    n, dev, dt = pos.shape[0], pos.device, pos.dtype
+    n, dt = pos.shape[0], pos.dtype
     L = C.lib()
-    f64 = dict(dtype=torch.float64, device=dev)
-    e = torch.empty(n, **f64) if energies else None
-    f = torch.empty((n, 3), dtype=dt, device=dev) if flags & DP_FORCES else None
-    cg = torch.empty(n, **f64) if flags & DP_CHARGE_GRAD else None
-    dg = torch.empty((n, 3), **f64) if flags & DP_DIPOLE_GRAD else None
-    part = torch.empty((p["nsys"], int(L.mi_ewald_dipole_blocks()), 9), **f64) if flags & DP_VIRIAL else None
+    e, f, cg, dg = M.allocate(pos, M.DIPOLE, (energies, flags & P.FORCES, flags & P.CHARGE_GRAD, flags & P.THIRD_GRAD))
     nbytes = int(L.mi_ewald_dipole_real_scratch_bytes(n, C.dtype_code(dt)))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    part, scratch = M.pair_scratch(p, flags, int(L.mi_ewald_dipole_blocks()), nbytes)
     rc = L.mi_ewald_dipole_real(C.ptr(pos), C.ptr(p["q"]), C.ptr(p["mu"]), C.ptr(p["cells"]), C.ptr(p["al"]), C.ptr(p["bi"]), C.ptr(weights), n,
-                                int(p["nsys"]), C.dtype_code(dt), C.ptr(p["idx"]), C.ptr(p["sh"]), C.ptr(p["nptr"]), int(p["m"]), int(mask_value),
+                                int(p["nsys"]), C.dtype_code(dt), C.ptr(p["idx"]), C.ptr(p["sh"]), C.ptr(p["nptr"]), int(p["m"]), p["mask"],
                                 int(flags), C.ptr(e), C.ptr(f), C.ptr(cg), C.ptr(dg), C.ptr(part), C.ptr(scratch), ctypes.c_size_t(nbytes),
                                 C.stream_of(pos))
     C.check(rc, "mi_ewald_dipole_real")
@@ -81,28 +78,16 @@ def _real_forward(positions, charges, dipoles, cell, alpha, batch_idx, neighbor_
     """(energies, forces | None, charge_grads | None, dipole_grads | None, virial | None) in the positions dtype, no autograd graph: what the
     eager call and the `alchemiops::_ewald_dipole_real_space` op both run."""
     p = _real_inputs(positions, charges, dipoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                     neighbor_matrix_shifts)
-    n, dev, dt = positions.shape[0], positions.device, positions.dtype
-    if n == 0 or p["n_entries"] == 0:
-        res = P.zeros(n, p["nsys"], dt, dev)
-        return tuple(r if w else None for r, w in zip(res, (True, forces, cgrads, dgrads, virial)))
-    flags = P.flag_bits(forces, cgrads, dgrads, virial)
-    e, f, cg, dg, part = _real_launch(p, mask_value, flags)
-    return (e.to(dt), f, cg.to(dt) if cgrads else None, dg.to(dt) if dgrads else None, C.fold_virial9(part).to(dt) if virial else None)
+                     neighbor_matrix_shifts, mask_value)
+    return M.pair_forward(p, _real_launch, M.DIPOLE, (True, forces, cgrads, dgrads, virial))
 
 
 def _real_adjoint(positions, charges, dipoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
                   neighbor_matrix_shifts, mask_value, grad_energies):
     """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles) of L = sum_i g_i E_i: the forward kernel with weights."""
     p = _real_inputs(positions, charges, dipoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                     neighbor_matrix_shifts)
-    n, dev = positions.shape[0], positions.device
-    f64 = dict(dtype=torch.float64, device=dev)
-    if n == 0 or p["n_entries"] == 0:
-        return torch.zeros((n, 3), **f64), torch.zeros(n, **f64), torch.zeros((n, 3), **f64)
-    g = grad_energies.detach().to(torch.float64).contiguous()
-    _, f, gq, gmu, _ = _real_launch(p, mask_value, DP_FORCES | DP_CHARGE_GRAD | DP_DIPOLE_GRAD, weights=g, energies=False)
-    return -f.to(torch.float64), gq, gmu
+                     neighbor_matrix_shifts, mask_value)
+    return M.pair_adjoint(p, _real_launch, M.DIPOLE, grad_energies)
 
 
 @C.traceable
@@ -124,20 +109,13 @@ def ewald_dipole_real_space(positions: torch.Tensor, charges: torch.Tensor, dipo
     RETURNS"""
     P.check_dipole_lists(positions, charges, dipoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts,
                          batch_idx, alpha, compute_virial)
-    n, dev, dt = positions.shape[0], positions.device, positions.dtype
     want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
-    if n == 0:
-        return P.select(P.zeros(0, P.num_systems(cell, batch_idx), dt, dev), want)
-    alpha_t = _prepare_alpha(alpha, _prepare_cell(cell)[1], dt, dev)
-    lists = (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
-    flags = tuple(bool(w) for w in want[1:])
-    if P.needs_op(positions, charges, dipoles, cell, alpha_t):
-        from nvalchemiops import _eops
-
-        res = _eops.ewald_dipole_real_space_op(positions, charges.to(dt), dipoles.to(dt), cell, alpha_t, batch_idx, *lists, int(mask_value), *flags)
-    else:
-        res = _real_forward(positions, charges, dipoles, cell, alpha_t, batch_idx, *lists, int(mask_value), *flags)
-    return P.select(res, want)
+    if positions.shape[0] == 0:
+        return M.no_atoms(positions, P.num_systems(cell, batch_idx), M.DIPOLE, want)
+    alpha_t = _prepare_alpha(alpha, _prepare_cell(cell)[1], positions.dtype, positions.device)
+    return M.dispatch("ewald_dipole_real_space_op", _real_forward, (positions, charges, dipoles), (cell, alpha_t),
+                      (batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts,
+                       int(mask_value)), want)
 
 
 # ---- reciprocal space ---------------------------------------------------------------------------------------------------------------------
@@ -175,14 +153,11 @@ def _table(p, weights=None):
     return table
 
 
-def _gather(p, table, table_g=None, weights=None, energies=False, forces=False, cgrads=False, dgrads=False):
+def _gather(p, table, want, table_g=None, weights=None):
+    """`want` = (energies, forces, charge sums, dipole sums), as `_multipoles.allocate` takes it."""
     pos = p["pos"]
-    n, dev = pos.shape[0], pos.device
-    f64 = dict(dtype=torch.float64, device=dev)
-    e = torch.empty(n, **f64) if energies else None
-    f = torch.empty((n, 3), dtype=pos.dtype, device=dev) if forces else None
-    cg = torch.empty(n, **f64) if cgrads else None
-    dg = torch.empty((n, 3), **f64) if dgrads else None
+    n = pos.shape[0]
+    e, f, cg, dg = M.allocate(pos, M.DIPOLE, want)
     adjoint = weights is not None and table_g is not None
     rc = C.lib().mi_ewald_dipole_recip_gather(C.ptr(pos), C.ptr(p["q"]), C.ptr(p["mu"]), C.ptr(p["kv"]) if p["n_k"] else None, C.ptr(p["cells"]),
                                               C.ptr(p["al"]), C.ptr(p["bi"]), C.ptr(table), C.ptr(table_g) if adjoint else None,
@@ -197,34 +172,33 @@ def _recip_forward(positions, charges, dipoles, cell, k_vectors, alpha, batch_id
     n, dev, dt = positions.shape[0], positions.device, positions.dtype
     want = (True, forces, cgrads, dgrads, virial)
     if n == 0:
-        return tuple(r if w else None for r, w in zip(P.zeros(0, _prepare_cell(cell)[1], dt, dev), want))
+        return M.if_wanted(P.zeros(0, _prepare_cell(cell)[1], dt, dev, *M.DIPOLE), want)
     p = _recip_inputs(positions, charges, dipoles, cell, k_vectors, alpha, batch_idx)
     table = _table(p)
-    e, f, cg, dg = _gather(p, table, energies=True, forces=forces, cgrads=cgrads, dgrads=dgrads)
+    sums = _gather(p, table, want[:-1])
     vir = None
     if virial:
         vir = torch.empty((p["nsys"], 9), dtype=torch.float64, device=dev)
         rc = C.lib().mi_ewald_dipole_recip_virial(C.ptr(table), C.ptr(p["kv"]) if p["n_k"] else None, C.ptr(p["cells"]), C.ptr(p["al"]),
                                                   int(p["nsys"]), int(p["n_k"]), C.dtype_code(dt), C.ptr(vir), C.stream_of(p["pos"]))
         C.check(rc, "mi_ewald_dipole_recip_virial")
-        vir = vir.reshape(-1, 3, 3).to(dt)
-    return e.to(dt), f, cg.to(dt) if cgrads else None, dg.to(dt) if dgrads else None, vir
+        vir = vir.reshape(-1, 3, 3)
+    return M.finish(sums, vir, want, dt)
 
 
 def _recip_adjoint(positions, charges, dipoles, cell, k_vectors, alpha, batch_idx, grad_energies):
     """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles) of L = sum_i g_i E_i: a second table summed with the weights g, and the gather in its
     adjoint form (dL/dtheta_i = 1/2 sum_k G_k Re[dA_i/dtheta (g_i S + S^g)] minus the charge part, self term times g_i)."""
     n, dev = positions.shape[0], positions.device
-    f64 = dict(dtype=torch.float64, device=dev)
     if n == 0:
-        return torch.zeros((0, 3), **f64), torch.zeros(0, **f64), torch.zeros((0, 3), **f64)
+        return M.zero_gradients(0, dev, M.DIPOLE)
     p = _recip_inputs(positions, charges, dipoles, cell, k_vectors, alpha, batch_idx)
-    g = grad_energies.detach().to(torch.float64).contiguous()
+    g = M.weights_of(grad_energies)
     table = _table(p)
     if table is None:  # no k-vectors: the self term alone, -g_i 4 alpha^3 / (3 sqrt(pi)) mu_i, which is g_i times the plain dipole gradient
-        _, _, _, dg = _gather(p, None, dgrads=True)
-        return torch.zeros((n, 3), **f64), torch.zeros(n, **f64), g.unsqueeze(1) * dg
-    _, f, gq, gmu = _gather(p, table, table_g=_table(p, weights=g), weights=g, forces=True, cgrads=True, dgrads=True)
+        dg = _gather(p, None, (False, False, False, True))[3]
+        return M.zero_gradients(n, dev, M.DIPOLE[:1]) + (g.unsqueeze(1) * dg,)
+    _, f, gq, gmu = _gather(p, table, (False, True, True, True), table_g=_table(p, weights=g), weights=g)
     return -f.to(torch.float64), gq, gmu
 
 
@@ -252,16 +226,9 @@ def ewald_dipole_reciprocal_space(positions: torch.Tensor, charges: torch.Tensor
         raise ValueError(f"k_vectors must have shape [K, 3] or [{n_sys}, K, 3], got {tuple(k_vectors.shape)}")
     want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
     if n == 0:
-        return P.select(P.zeros(0, n_sys, dt, dev), want)
-    alpha_t = _prepare_alpha(alpha, n_sys, dt, dev)
-    flags = tuple(bool(w) for w in want[1:])
-    if P.needs_op(positions, charges, dipoles, cell, k_vectors, alpha_t):
-        from nvalchemiops import _eops
-
-        res = _eops.ewald_dipole_reciprocal_space_op(positions, charges.to(dt), dipoles.to(dt), cells, k_vectors, alpha_t, batch_idx, *flags)
-    else:
-        res = _recip_forward(positions, charges, dipoles, cells, k_vectors, alpha_t, batch_idx, *flags)
-    return P.select(res, want)
+        return M.no_atoms(positions, n_sys, M.DIPOLE, want)
+    return M.dispatch("ewald_dipole_reciprocal_space_op", _recip_forward, (positions, charges, dipoles),
+                      (cells, k_vectors, _prepare_alpha(alpha, n_sys, dt, dev)), (batch_idx,), want)
 
 
 @C.traceable
@@ -282,37 +249,17 @@ def ewald_dipole_correction(positions: torch.Tensor, charges: torch.Tensor, dipo
     truncated list is not detected.  A matrix entry equal to `mask_value` (default: N) or outside [0, N) is padding.
 
     RETURNS"""
-    from nvalchemiops.interactions.electrostatics.k_vectors import generate_k_vectors_ewald_summation
-    from nvalchemiops.interactions.electrostatics.parameters import estimate_ewald_parameters
-
     if mask_value is None:
         mask_value = positions.shape[0]
     P.check_dipole_lists(positions, charges, dipoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts,
                          batch_idx, alpha, compute_virial)
-    cells, n_sys = _prepare_cell(cell)
-    if positions.shape[0] == 0:
-        want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
-        return P.select(P.zeros(0, P.num_systems(cell, batch_idx), positions.dtype, positions.device), want)
-    C.require_device(positions, charges, dipoles, cell, k_vectors, batch_idx)
-    if alpha is None or (k_cutoff is None and k_vectors is None):
-        params = estimate_ewald_parameters(positions, cells, batch_idx, accuracy)
-        if alpha is None:
-            alpha = params.alpha
-        if k_cutoff is None:
-            k_cutoff = params.reciprocal_space_cutoff
-    alpha_t = _prepare_alpha(alpha, n_sys, positions.dtype, positions.device)
-    if k_vectors is None:
-        k_vectors = generate_k_vectors_ewald_summation(cells, k_cutoff)
-    flags = dict(compute_forces=compute_forces, compute_charge_gradients=compute_charge_gradients,
-                 compute_dipole_gradients=compute_dipole_gradients, compute_virial=compute_virial)
-    rs = ewald_dipole_real_space(positions, charges, dipoles, cells, alpha_t, neighbor_list=neighbor_list, neighbor_ptr=neighbor_ptr,
-                                 neighbor_shifts=neighbor_shifts, neighbor_matrix=neighbor_matrix, neighbor_matrix_shifts=neighbor_matrix_shifts,
-                                 mask_value=mask_value, batch_idx=batch_idx, **flags)
-    rec = ewald_dipole_reciprocal_space(positions, charges, dipoles, cells, k_vectors, alpha_t, batch_idx=batch_idx, **flags)
-    if isinstance(rs, tuple):
-        return tuple(a + b for a, b in zip(rs, rec))
-    return rs + rec
+    return M.ewald_correction(_EWALD, (positions, charges, dipoles), cell, alpha, k_vectors, k_cutoff, batch_idx,
+                              (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts), mask_value,
+                              (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial), accuracy)
 
+
+FLAGS = ("compute_forces", "compute_charge_gradients", "compute_dipole_gradients", "compute_virial")
+_EWALD = dict(grads=M.DIPOLE, flags=FLAGS, real=ewald_dipole_real_space, recip=ewald_dipole_reciprocal_space)
 
 for _fn in (ewald_dipole_real_space, ewald_dipole_reciprocal_space, ewald_dipole_correction):
     _fn.__doc__ = _fn.__doc__.replace("MODEL", _MODEL).replace("RETURNS", _RETURNS)

@@ -83,7 +83,7 @@ def _forward(positions, charges, sigma, cell, batch_idx, neighbor_list, neighbor
     p = _inputs(positions, charges, sigma, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
     n, dev, dt = positions.shape[0], positions.device, positions.dtype
     f64 = dict(dtype=torch.float64, device=dev)
-    flags = P.flag_bits(forces, cgrads, sgrads, virial)
+    flags = P.flag_bits((True, forces, cgrads, sgrads, virial))
     if p["n_entries"] == 0:
         e = torch.zeros(n, **f64)
         f = torch.zeros((n, 3), dtype=dt, device=dev) if forces else None
@@ -193,7 +193,7 @@ def gaussian_charge_correction(positions: torch.Tensor, charges: torch.Tensor, s
     n_entries = neighbor_list.shape[1] if neighbor_list is not None else neighbor_matrix.numel()
     background = bool(neutralizing_background) and cell is not None
     if n == 0 or (n_entries == 0 and not self_energy and not background):
-        return P.select(P.zeros(n, nsys, dt, dev, third_is_vector=False), want)
+        return P.select(P.zeros(n, nsys, dt, dev, (), ()), want)
     sig = _sigma_tensor(sigma, n, dt, dev)
     lists = (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
     flags = (bool(self_energy), background, bool(compute_forces), bool(compute_charge_gradients), bool(compute_sigma_gradients), bool(compute_virial))

@@ -24,6 +24,7 @@ from collections import namedtuple
 import torch
 
 from nvalchemiops import _capi as C
+from nvalchemiops.interactions.electrostatics import _multipoles as M
 from nvalchemiops.interactions.electrostatics import _pairs as P
 from nvalchemiops.interactions.electrostatics import dipole as D
 from nvalchemiops.interactions.electrostatics import pme_dipole as PD
@@ -73,7 +74,7 @@ def _check(positions, charges, polarizability, cell, external_field, batch_idx, 
             raise ValueError("k_vectors belong to reciprocal='ewald'")
         order = PD._check_order(spline_order)
         if mesh_dimensions is not None:
-            PD._mesh_dims(cell.reshape(-1, 3, 3), mesh_dimensions, None, order)
+            M.mesh_dims(cell.reshape(-1, 3, 3), mesh_dimensions, None, order)
     else:
         if mesh_dimensions is not None or mesh_spacing is not None:
             raise ValueError("mesh_dimensions / mesh_spacing belong to reciprocal='pme'")
@@ -124,7 +125,7 @@ class _Operator:
         self.mask = (self.polar > 0).to(F64).unsqueeze(1)  # the projector onto the polarisable atoms
         zq, zmu = torch.zeros(n, dtype=dt, device=dev), torch.zeros((n, 3), dtype=dt, device=dev)
         if reciprocal == "pme":  # launch tensors of the reciprocal call, made once: only the dipoles change between iterations
-            self.rp = PD._inputs(self.pos, zq, zmu, self.cells, self.alpha, self.batch_idx)
+            self.rp = M.mesh_inputs(self.pos, zq, zmu, self.cells, self.alpha, self.batch_idx)
         elif reciprocal == "ewald":
             self.rp = D._recip_inputs(self.pos, zq, zmu, self.cells, self.kv, self.alpha, self.batch_idx)
 
@@ -162,7 +163,7 @@ class _Operator:
             if mesh_dimensions is None:
                 mesh_dimensions = (PME.mesh_spacing_to_dimensions(cells, mesh_spacing) if mesh_spacing is not None
                                    else PME.estimate_pme_mesh_dimensions(cells, self.alpha, accuracy))
-            self.dims = PD._mesh_dims(cells, mesh_dimensions, None, self.order)
+            self.dims = M.mesh_dims(cells, mesh_dimensions, None, self.order)
         else:
             if alpha is None or (k_cutoff is None and k_vectors is None):
                 params = estimate_ewald_parameters(self.pos, cells, self.batch_idx, accuracy)
@@ -184,11 +185,11 @@ class _Operator:
         with torch.no_grad():
             p = dict(self.rp, mu=x.to(self.dt).contiguous())
             if self.reciprocal == "pme":
-                phi, _ = PD._solve(p, PD._spread(p, self.dims, self.order), self.dims, self.order, need_spec=False)
+                phi, _ = M.mesh_solve(p, PD._spread(p, self.dims, self.order), self.dims, self.order, need_spec=False)
                 phi[0] += phi[1]
-                dg = PD._gather(p, self.dims, self.order, phi[1], phi[0], dgrads=True)[3]
+                dg = PD._gather(p, self.dims, self.order, phi[1], phi[0], (False, False, False, True))[3]
             else:
-                dg = D._gather(p, D._table(p), dgrads=True)[3]
+                dg = D._gather(p, D._table(p), (False, False, False, True))[3]
         return (dg.to(self.dt).to(F64) * self.mask).contiguous()
 
     def apply(self, x, y_in=None, partial=None):

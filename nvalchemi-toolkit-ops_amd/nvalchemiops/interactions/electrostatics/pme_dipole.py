@@ -16,16 +16,14 @@ run (in float32 arrival order the forces moved by up to 1e-6 of their largest co
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
 
 from nvalchemiops import _capi as C
+from nvalchemiops.interactions.electrostatics import _multipoles as M
 from nvalchemiops.interactions.electrostatics import _pairs as P
-from nvalchemiops.interactions.electrostatics import pme as _pme
-from nvalchemiops.interactions.electrostatics.dipole import ewald_dipole_real_space
-from nvalchemiops.interactions.electrostatics.pme import _prepare_alpha, _prepare_cell
+from nvalchemiops.interactions.electrostatics.dipole import FLAGS, ewald_dipole_real_space
 
 _MODEL = """Smooth PME with analytic spline derivatives (Toukmaji, Sagui, Board, Darden).  With frac = cell^-T r, mesh coordinate m_d = frac_d n_d,
     W_i(g) = prod_d M_p(p/2 + m_d - g_d) the order-p B-spline weight of atom i at mesh point g and grad the Cartesian gradient w.r.t. r_i:
@@ -58,28 +56,7 @@ _SPREAD_FLOAT32_IN_FLOAT64 = True  # float32 calls: the spread adds in float64 a
 
 
 def _check_order(spline_order) -> int:
-    order = C.plain_spline_order(spline_order)
-    if order not in ORDERS:
-        raise ValueError(f"spline_order must be 4, 5 or 6 for the dipole mesh sum (the forces need a continuous second derivative of the spline), "
-                         f"got {order}")
-    if int(spline_order) & C.SPLINE_REFERENCE_ORDERS or (not int(spline_order) & C.SPLINE_RESOLVED and not C.tracing()
-                                                          and C.reference_spline_orders_active()):
-        raise ValueError("the dipole mesh sum has no reference evaluation of the spline orders (reference_spline_orders): the reference package has "
-                         "no dipole term")
-    return order
-
-
-def _mesh_dims(cells, mesh_dimensions, mesh_spacing, order):
-    if mesh_dimensions is None:
-        if mesh_spacing is None:
-            raise ValueError("Either mesh_dimensions or mesh_spacing must be provided")
-        mesh_dimensions = _pme.mesh_spacing_to_dimensions(cells, mesh_spacing)
-    dims = tuple(int(v) for v in mesh_dimensions)
-    if len(dims) != 3:
-        raise ValueError(f"mesh_dimensions must hold three integers, got {mesh_dimensions}")
-    if min(dims) < order:
-        raise ValueError(f"every mesh dimension must be at least the spline order {order}, got {dims}")
-    return dims
+    return M.check_order(spline_order, ORDERS, "dipole", "the forces need a continuous second derivative of the spline")
 
 
 def _check_recip(positions, charges, dipoles, cell, alpha, batch_idx):
@@ -92,88 +69,26 @@ def _check_recip(positions, charges, dipoles, cell, alpha, batch_idx):
 
 
 # ---- launches -----------------------------------------------------------------------------------------------------------------------------
-def _inputs(positions, charges, dipoles, cells, alpha, batch_idx):
-    """Detached contiguous launch tensors plus the cell geometry (cell^-T, 2 pi cell^-1, volume) of `mi_pme_prepare`."""
-    dt, dev, n = positions.dtype, positions.device, positions.shape[0]
-    C.require_device(positions, charges, dipoles, cells, alpha, batch_idx)
-    code = C.dtype_code(dt)
-    batched = batch_idx is not None
-    cc = cells.detach().to(dt).reshape(-1, 3, 3).contiguous()
-    nsys = cc.shape[0] if batched else 1
-    cc = cc[:nsys].contiguous()
-    p = dict(pos=positions.detach().contiguous(), q=charges.detach().to(dt).contiguous(), mu=dipoles.detach().to(dt).contiguous(),
-             al=alpha.detach().to(dt).reshape(-1)[:nsys].contiguous(), bi=C.i32(batch_idx) if batched else None, nsys=nsys, code=code, cells=cc)
-    cit, recip = torch.empty_like(cc), torch.empty_like(cc)
-    vol, qtot = torch.empty(nsys, dtype=dt, device=dev), torch.empty(nsys, dtype=dt, device=dev)
-    C.check(C.lib().mi_pme_prepare(C.ptr(cc), C.ptr(p["q"]), C.ptr(p["bi"]), n, nsys, code, C.ptr(cit), C.ptr(recip), C.ptr(vol), C.ptr(qtot),
-                                   C.stream_of(positions)), "mi_pme_prepare")
-    p.update(cit=cit, recip=recip, vol=vol)
-    return p
+def _spread_launch(p, dims, order, weights, meshes):
+    pos = p["pos"]
+    rc = C.lib().mi_pme_dipole_spread(C.ptr(pos), C.ptr(p["q"]), C.ptr(p["mu"]), C.ptr(weights), C.ptr(p["bi"]), C.ptr(p["cit"]), pos.shape[0],
+                                      int(p["nsys"]), *dims, int(order), p["code"], C.ptr(meshes), C.stream_of(pos))
+    C.check(rc, "mi_pme_dipole_spread")
 
 
 def _spread(p, dims, order, weights=None):
     """[2 | 4, nsys, nx, ny, nz]: rho_q, rho_mu (and their g-weighted twins), zero-filled by the entry point."""
-    pos = p["pos"]
-    if pos.dtype == torch.float32 and _SPREAD_FLOAT32_IN_FLOAT64:
-        # float32 atomic adds in arrival order move the last bits of the meshes from run to run, and the Hessian sums of the gather carry
-        # that into the forces at 1e-6 of their largest component.  Added in float64 and rounded once, the float32 meshes are the same
-        # in every run (but for a sum that lands on a rounding boundary of float32).
-        wide = {k: p[k].to(torch.float64) for k in ("pos", "q", "mu", "cit")}
-        return _spread(dict(p, code=C.dtype_code(torch.float64), **wide), dims, order, weights).to(torch.float32)
-    meshes = torch.empty((4 if weights is not None else 2, p["nsys"]) + dims, dtype=pos.dtype, device=pos.device)
-    rc = C.lib().mi_pme_dipole_spread(C.ptr(pos), C.ptr(p["q"]), C.ptr(p["mu"]), C.ptr(weights), C.ptr(p["bi"]), C.ptr(p["cit"]), pos.shape[0],
-                                      int(p["nsys"]), *dims, int(order), p["code"], C.ptr(meshes), C.stream_of(pos))
-    C.check(rc, "mi_pme_dipole_spread")
-    return meshes
+    return M.mesh_spread(p, dims, order, _spread_launch, _SPREAD_FLOAT32_IN_FLOAT64, weights)
 
 
-def _solve(p, meshes, dims, order, need_spec):
-    """phi_X = IFFT[G FFT(rho_X) / sf^2] of every mesh of `meshes` [M, nsys, nx, ny, nz] in ONE batched call: the M x nsys meshes are systems
-    of the charge PME's solve, with the cell, alpha and volume rows repeated.  Returns (potentials, like `meshes`; spectra [M, nsys, nx, ny, nzr]
-    or None).  The fused in-LDS solve where it is supported, hipFFT plan -> `mi_pme_convolve` -> plan otherwise, as `_reciprocal_front` does."""
-    nx, ny, nz = dims
-    m, nsys = meshes.shape[0], p["nsys"]
-    b = m * nsys
-    dt, dev, code = meshes.dtype, meshes.device, p["code"]
-    st = C.stream_of(meshes)
-    recip, al, vol = p["recip"].repeat(m, 1, 1), p["al"].repeat(m), p["vol"].repeat(m)
-    cdt = torch.complex64 if dt == torch.float32 else torch.complex128
-    L = C.lib()
-    if _pme._MESH_SOLVE is not False and L.mi_pme_solve_supported(b, nx, ny, nz, code):
-        nbytes = int(L.mi_pme_solve_scratch_bytes(b, nx, ny, nz, 1, code))
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        real = torch.empty((m, nsys, nx, ny, nz), dtype=dt, device=dev)
-        spec = torch.empty((m, nsys, nx, ny, nz // 2 + 1), dtype=cdt, device=dev) if need_spec else None
-        rc = L.mi_pme_solve_tabled(C.ptr(meshes), C.ptr(recip), C.ptr(al), C.ptr(vol), b, nx, ny, nz, int(order), 0, code, C.ptr(scratch),
-                                   ctypes.c_size_t(nbytes), C.ptr(real), C.ptr(spec), C.ptr(_pme._solve_tables(dev, dims, code)), st)
-        C.check(rc, "mi_pme_solve_tabled")
-        return real, spec
-    spec = torch.empty((m, nsys, nx, ny, nz // 2 + 1), dtype=cdt, device=dev)
-    _pme._fft_plan(dev, dims, b, code, False)(meshes, spec)
-    conv = torch.empty_like(spec)
-    rc = L.mi_pme_convolve(C.ptr(spec), C.ptr(recip), C.ptr(al), C.ptr(vol), b, nx, ny, nz, int(order), 0, code, None, None, 0, C.ptr(conv), st)
-    C.check(rc, "mi_pme_convolve")
-    real = torch.empty((m, nsys, nx, ny, nz), dtype=dt, device=dev)
-    _pme._fft_plan(dev, dims, b, code, True)(conv, real)
-    return real, spec
-
-
-def _gather(p, dims, order, mesh_a, mesh_b, weights=None, accumulate=False, out=None, energies=False, forces=False, cgrads=False, dgrads=False):
+def _gather(p, dims, order, mesh_a, mesh_b, want, weights=None, out=None):
     """One `mi_pme_dipole_gather` launch over (A, B): float64 (energies | None, forces in the positions dtype | None, charge sums | None,
-    dipole sums | None); `accumulate` adds to the tensors of `out`."""
+    dipole sums | None) as `want` asks for them; with `out` the launch adds to its tensors."""
     pos = p["pos"]
-    n, dev = pos.shape[0], pos.device
-    f64 = dict(dtype=torch.float64, device=dev)
-    if accumulate:
-        e, f, cg, dg = out
-    else:
-        e = torch.empty(n, **f64) if energies else None
-        f = torch.empty((n, 3), dtype=pos.dtype, device=dev) if forces else None
-        cg = torch.empty(n, **f64) if cgrads else None
-        dg = torch.empty((n, 3), **f64) if dgrads else None
+    e, f, cg, dg = M.allocate(pos, M.DIPOLE, want) if out is None else out
     rc = C.lib().mi_pme_dipole_gather(C.ptr(pos), C.ptr(p["q"]), C.ptr(p["mu"]), C.ptr(weights), C.ptr(p["bi"]), C.ptr(p["cit"]), C.ptr(mesh_a),
-                                      C.ptr(mesh_b), C.ptr(p["al"]), n, int(p["nsys"]), *dims, int(order), p["code"], int(accumulate), C.ptr(e),
-                                      C.ptr(f), C.ptr(cg), C.ptr(dg), C.stream_of(pos))
+                                      C.ptr(mesh_b), C.ptr(p["al"]), pos.shape[0], int(p["nsys"]), *dims, int(order), p["code"],
+                                      int(out is not None), C.ptr(e), C.ptr(f), C.ptr(cg), C.ptr(dg), C.stream_of(pos))
     C.check(rc, "mi_pme_dipole_gather")
     return e, f, cg, dg
 
@@ -181,57 +96,32 @@ def _gather(p, dims, order, mesh_a, mesh_b, weights=None, accumulate=False, out=
 def _self_coefficient(p):
     """2 alpha^3 / (3 sqrt(pi)) per atom, float64."""
     c = 2.0 * p["al"].to(torch.float64) ** 3 / (3.0 * math.sqrt(math.pi))
-    return c[p["bi"].long()] if p["bi"] is not None else c.expand(p["pos"].shape[0])
+    return M.per_atom(p, c)
 
 
-def _recip_forward(positions, charges, dipoles, cell, alpha, batch_idx, dims, order, forces, cgrads, dgrads, virial):
+def _virial(p, spec, sums, dims, order):
+    """Float64 [nsys, 3, 3]: the k-space virial of the cross spectrum plus the term of the dipoles that follow the strain."""
+    L = C.lib()
+    part = torch.empty((p["nsys"], int(L.mi_pme_dipole_virial_blocks()), 9), dtype=torch.float64, device=p["pos"].device)
+    rc = L.mi_pme_dipole_virial(C.ptr(spec[0]), C.ptr(spec[1]), C.ptr(p["recip"]), C.ptr(p["al"]), C.ptr(p["vol"]), int(p["nsys"]), *dims,
+                                int(order), p["code"], C.ptr(part), C.stream_of(p["pos"]))
+    C.check(rc, "mi_pme_dipole_virial")
+    # the dipoles' fractional components follow the strain: + sum_i (dE/dmu_i without its self term)_a mu_i,b per system (index order matters)
+    mu64 = p["mu"].to(torch.float64)
+    outer = (sums[3] + 2.0 * _self_coefficient(p).unsqueeze(1) * mu64).unsqueeze(2) * mu64.unsqueeze(1)
+    return M.strained_multipole_virial(p, part, outer)
+
+
+def _recip_forward(positions, charges, dipoles, cell, alpha, batch_idx, nx, ny, nz, order, *flags):
     """(energies, forces | None, charge_grads | None, dipole_grads | None, virial | None) in the positions dtype, no autograd graph: what the
     eager call and the `alchemiops::_pme_dipole_reciprocal_space` op both run."""
-    n, dev, dt = positions.shape[0], positions.device, positions.dtype
-    want = (True, forces, cgrads, dgrads, virial)
-    if n == 0:
-        return tuple(r if w else None for r, w in zip(P.zeros(0, P.num_systems(cell, batch_idx), dt, dev), want))
-    dims = tuple(int(v) for v in dims)
-    p = _inputs(positions, charges, dipoles, cell, alpha, batch_idx)
-    phi, spec = _solve(p, _spread(p, dims, order), dims, order, need_spec=virial)
-    phi[0] += phi[1]  # phi_t = phi_q + phi_mu: the gather reads (A, B) = (phi_mu, phi_t)
-    e, f, cg, dg = _gather(p, dims, order, phi[1], phi[0], energies=True, forces=forces, cgrads=cgrads, dgrads=dgrads or virial)
-    vir = None
-    if virial:
-        L = C.lib()
-        part = torch.empty((p["nsys"], int(L.mi_pme_dipole_virial_blocks()), 9), dtype=torch.float64, device=dev)
-        rc = L.mi_pme_dipole_virial(C.ptr(spec[0]), C.ptr(spec[1]), C.ptr(p["recip"]), C.ptr(p["al"]), C.ptr(p["vol"]), int(p["nsys"]), *dims,
-                                    int(order), p["code"], C.ptr(part), C.stream_of(positions))
-        C.check(rc, "mi_pme_dipole_virial")
-        # the dipoles' fractional components follow the strain: + sum_i (dE/dmu_i without its self term)_a mu_i,b per system (index order matters)
-        mu64 = p["mu"].to(torch.float64)
-        outer = (dg + 2.0 * _self_coefficient(p).unsqueeze(1) * mu64).unsqueeze(2) * mu64.unsqueeze(1)
-        vir = C.fold_virial9(part)
-        if p["bi"] is not None:
-            vir = vir.index_add(0, p["bi"].long(), outer)
-        else:
-            vir = vir + outer.sum(0, keepdim=True)
-        vir = vir.to(dt)
-    return e.to(dt), f, cg.to(dt) if cgrads else None, dg.to(dt) if dgrads else None, vir
+    return M.mesh_forward(MESH, (positions, charges, dipoles, cell, alpha, batch_idx), (nx, ny, nz), order, (True,) + flags)
 
 
-def _recip_adjoint(positions, charges, dipoles, cell, alpha, batch_idx, dims, order, grad_energies):
-    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles) of L = sum_i g_i E_i.  The gather is its own adjoint: the g-weighted meshes ride in
-    the same spread and the same batched solve (four meshes), and
-        dL/dtheta_i = g_i x [gather over (phi_mu, phi_t)] + [gather over (phi^g_mu, phi^g_q + phi^g_mu)],   self term -c g_i |mu_i|^2."""
-    n, dev = positions.shape[0], positions.device
-    f64 = dict(dtype=torch.float64, device=dev)
-    if n == 0:
-        return torch.zeros((0, 3), **f64), torch.zeros(0, **f64), torch.zeros((0, 3), **f64)
-    dims = tuple(int(v) for v in dims)
-    p = _inputs(positions, charges, dipoles, cell, alpha, batch_idx)
-    g = grad_energies.detach().to(torch.float64).contiguous()
-    phi, _ = _solve(p, _spread(p, dims, order, weights=g), dims, order, need_spec=False)
-    phi[0] += phi[1]
-    phi[2] += phi[3]
-    out = _gather(p, dims, order, phi[1], phi[0], weights=g, forces=True, cgrads=True, dgrads=True)
-    _, f, gq, gmu = _gather(p, dims, order, phi[3], phi[2], accumulate=True, out=out)
-    return -f.to(torch.float64), gq, gmu
+def _recip_adjoint(positions, charges, dipoles, cell, alpha, batch_idx, nx, ny, nz, order, grad_energies):
+    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles) of L = sum_i g_i E_i, over (phi_mu, phi_t) and (phi^g_mu, phi^g_q + phi^g_mu); the self
+    term is -c g_i |mu_i|^2."""
+    return M.mesh_adjoint(MESH, (positions, charges, dipoles, cell, alpha, batch_idx), (nx, ny, nz), order, grad_energies)
 
 
 # ---- public -------------------------------------------------------------------------------------------------------------------------------
@@ -248,22 +138,8 @@ def pme_dipole_reciprocal_space(positions: torch.Tensor, charges: torch.Tensor, 
 
     RETURNS"""
     _check_recip(positions, charges, dipoles, cell, alpha, batch_idx)
-    order = _check_order(spline_order)
-    cells, n_sys = _prepare_cell(cell)
-    dims = _mesh_dims(cells, mesh_dimensions, mesh_spacing, order)
-    n, dev, dt = positions.shape[0], positions.device, positions.dtype
-    want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
-    if n == 0:
-        return P.select(P.zeros(0, P.num_systems(cell, batch_idx), dt, dev), want)
-    alpha_t = (_pme._traceable_alpha if C.tracing() else _prepare_alpha)(alpha, n_sys, dt, dev)
-    flags = tuple(bool(w) for w in want[1:])
-    if P.needs_op(positions, charges, dipoles, cell, alpha_t):
-        from nvalchemiops import _eops
-
-        res = _eops.pme_dipole_reciprocal_space_op(positions, charges.to(dt), dipoles.to(dt), cells, alpha_t, batch_idx, *dims, order, *flags)
-    else:
-        res = _recip_forward(positions, charges, dipoles, cells, alpha_t, batch_idx, dims, order, *flags)
-    return P.select(res, want)
+    return M.mesh_reciprocal_space(MESH, (positions, charges, dipoles), cell, alpha, mesh_dimensions, mesh_spacing, spline_order, batch_idx,
+                                   (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial))
 
 
 @C.traceable
@@ -291,35 +167,15 @@ def pme_dipole_correction(positions: torch.Tensor, charges: torch.Tensor, dipole
         raise ValueError("pass the list in ONE format: neighbor_list (with neighbor_ptr) or neighbor_matrix, not both")
     P.check_dipole_lists(positions, charges, dipoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts,
                          batch_idx, alpha, compute_virial)
-    order = _check_order(spline_order)
-    cells, n_sys = _prepare_cell(cell)
-    if mesh_dimensions is not None:
-        mesh_dimensions = _mesh_dims(cells, mesh_dimensions, None, order)
-    if positions.shape[0] == 0:
-        want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial)
-        return P.select(P.zeros(0, P.num_systems(cell, batch_idx), positions.dtype, positions.device), want)
-    C.require_device(positions, charges, dipoles, cell, batch_idx)
-    if alpha is None:
-        est = _pme.estimate_pme_parameters(positions, cells, batch_idx, accuracy)
-        alpha = est.alpha
-        if mesh_dimensions is None and mesh_spacing is None:
-            mesh_dimensions = tuple(est.mesh_dimensions)
-    alpha_t = (_pme._traceable_alpha if C.tracing() else _prepare_alpha)(alpha, n_sys, positions.dtype, positions.device)
-    if mesh_dimensions is None:
-        mesh_dimensions = (_pme.mesh_spacing_to_dimensions(cells, mesh_spacing) if mesh_spacing is not None
-                           else _pme.estimate_pme_mesh_dimensions(cells, alpha_t, accuracy))
-    mesh_dimensions = _mesh_dims(cells, mesh_dimensions, None, order)
-    flags = dict(compute_forces=compute_forces, compute_charge_gradients=compute_charge_gradients,
-                 compute_dipole_gradients=compute_dipole_gradients, compute_virial=compute_virial)
-    rs = ewald_dipole_real_space(positions, charges, dipoles, cells, alpha_t, neighbor_list=neighbor_list, neighbor_ptr=neighbor_ptr,
-                                 neighbor_shifts=neighbor_shifts, neighbor_matrix=neighbor_matrix, neighbor_matrix_shifts=neighbor_matrix_shifts,
-                                 mask_value=mask_value, batch_idx=batch_idx, **flags)
-    rec = pme_dipole_reciprocal_space(positions, charges, dipoles, cells, alpha_t, mesh_dimensions=mesh_dimensions, spline_order=order,
-                                      batch_idx=batch_idx, **flags)
-    if isinstance(rs, tuple):
-        return tuple(a + b for a, b in zip(rs, rec))
-    return rs + rec
+    return M.mesh_correction(MESH, (positions, charges, dipoles), cell, alpha, mesh_spacing, mesh_dimensions, spline_order, batch_idx,
+                             (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts), mask_value,
+                             (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_virial), accuracy)
 
+
+# what `_multipoles.mesh_*` run for this operator.  The functions are bound here, at import: rebinding `_spread`, `_gather`, `_virial` or
+# `_recip_forward` on the module afterwards does not reach them (only `_SPREAD_FLOAT32_IN_FLOAT64` is read at call time).
+MESH = dict(grads=M.DIPOLE, flags=FLAGS, check_order=_check_order, spread=_spread, gather=_gather, virial=_virial, forward=_recip_forward,
+            op="pme_dipole_reciprocal_space_op", real=ewald_dipole_real_space, recip=pme_dipole_reciprocal_space)
 
 for _fn in (pme_dipole_reciprocal_space, pme_dipole_correction):
     _fn.__doc__ = _fn.__doc__.replace("MODEL", _MODEL).replace("RETURNS", _RETURNS)

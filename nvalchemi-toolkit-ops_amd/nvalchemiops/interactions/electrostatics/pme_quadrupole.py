@@ -21,14 +21,9 @@ import math
 import torch
 
 from nvalchemiops import _capi as C
-from nvalchemiops.interactions.electrostatics import _pairs as P
-from nvalchemiops.interactions.electrostatics import pme as _pme
+from nvalchemiops.interactions.electrostatics import _multipoles as M
 from nvalchemiops.interactions.electrostatics import pme_dipole as _pd
-from nvalchemiops.interactions.electrostatics.pme import _prepare_alpha, _prepare_cell
-from nvalchemiops.interactions.electrostatics.pme_dipole import _inputs as _dipole_inputs
-from nvalchemiops.interactions.electrostatics.pme_dipole import _mesh_dims, _solve
-from nvalchemiops.interactions.electrostatics.quadrupole import (_check_real, _dipoles_or_zeros, _zeros, check_quadrupoles,
-                                                                 ewald_quadrupole_real_space)
+from nvalchemiops.interactions.electrostatics.quadrupole import FLAGS, _check_real, _dipoles_or_zeros, check_quadrupoles, ewald_quadrupole_real_space
 
 _MODEL = """Smooth PME with analytic spline derivatives, one multipole order beyond `pme_dipole_correction`.  Atom i carries q_i, mu_i and a
     symmetric Cartesian quadrupole Q_i, `quadrupoles` [N, 3, 3] (the second Taylor coefficient 1/2 sum q d d; a traceless AMOEBA / Stone
@@ -69,15 +64,8 @@ ORDERS = (5, 6)
 
 
 def _check_order(spline_order) -> int:
-    order = C.plain_spline_order(spline_order)
-    if order not in ORDERS:
-        raise ValueError(f"spline_order must be 5 or 6 for the quadrupole mesh sum (the forces need the third derivative of the spline, which is "
-                         f"discontinuous at order 4, where the second derivative the energy needs is only continuous), got {order}")
-    if int(spline_order) & C.SPLINE_REFERENCE_ORDERS or (not int(spline_order) & C.SPLINE_RESOLVED and not C.tracing()
-                                                          and C.reference_spline_orders_active()):
-        raise ValueError("the quadrupole mesh sum has no reference evaluation of the spline orders (reference_spline_orders): the reference "
-                         "package has no quadrupole term")
-    return order
+    return M.check_order(spline_order, ORDERS, "quadrupole", "the forces need the third derivative of the spline, which is discontinuous at "
+                         "order 4, where the second derivative the energy needs is only continuous")
 
 
 def _check_recip(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx):
@@ -86,113 +74,66 @@ def _check_recip(positions, charges, dipoles, quadrupoles, cell, alpha, batch_id
 
 
 # ---- launches -----------------------------------------------------------------------------------------------------------------------------
-def _inputs(positions, charges, dipoles, quadrupoles, cells, alpha, batch_idx):
-    """`_inputs` of `pme_dipole.py` plus the quadrupoles (detached, contiguous, in the positions dtype)."""
-    C.require_device(quadrupoles)
-    p = _dipole_inputs(positions, charges, dipoles, cells, alpha, batch_idx)
-    p["qd"] = quadrupoles.detach().to(positions.dtype).contiguous()
-    return p
+def _spread_launch(p, dims, order, weights, meshes):
+    pos = p["pos"]
+    rc = C.lib().mi_pme_quadrupole_spread(C.ptr(pos), C.ptr(p["q"]), C.ptr(p["mu"]), C.ptr(p["qd"]), C.ptr(weights), C.ptr(p["bi"]),
+                                          C.ptr(p["cit"]), pos.shape[0], int(p["nsys"]), *dims, int(order), p["code"], C.ptr(meshes),
+                                          C.stream_of(pos))
+    C.check(rc, "mi_pme_quadrupole_spread")
 
 
 def _spread(p, dims, order, weights=None):
     """[2 | 4, nsys, nx, ny, nz]: rho_l, rho_T (and their g-weighted twins), zero-filled by the entry point.  float32 calls add in float64 and
     round once, the policy of `pme_dipole._spread` -- here without its switch (`pme_dipole._SPREAD_FLOAT32_IN_FLOAT64`): the gather forms
     its stencil in float64 whatever the dtype, and a spread from float32 stencils would not be the one it is the adjoint of."""
-    pos = p["pos"]
-    if pos.dtype == torch.float32:
-        wide = {k: p[k].to(torch.float64) for k in ("pos", "q", "mu", "qd", "cit")}
-        return _spread(dict(p, code=C.dtype_code(torch.float64), **wide), dims, order, weights).to(torch.float32)
-    meshes = torch.empty((4 if weights is not None else 2, p["nsys"]) + dims, dtype=pos.dtype, device=pos.device)
-    rc = C.lib().mi_pme_quadrupole_spread(C.ptr(pos), C.ptr(p["q"]), C.ptr(p["mu"]), C.ptr(p["qd"]), C.ptr(weights), C.ptr(p["bi"]),
-                                          C.ptr(p["cit"]), pos.shape[0], int(p["nsys"]), *dims, int(order), p["code"], C.ptr(meshes),
-                                          C.stream_of(pos))
-    C.check(rc, "mi_pme_quadrupole_spread")
-    return meshes
+    return M.mesh_spread(p, dims, order, _spread_launch, True, weights)
 
 
-def _gather(p, dims, order, mesh_a, mesh_b, weights=None, accumulate=False, out=None, energies=False, forces=False, cgrads=False, dgrads=False,
-            qgrads=False):
+def _gather(p, dims, order, mesh_a, mesh_b, want, weights=None, out=None):
     """One `mi_pme_quadrupole_gather` launch over (A, B): float64 (energies | None, forces in the positions dtype | None, charge sums | None,
-    dipole sums | None, quadrupole sums [n, 3, 3] | None); `accumulate` adds to the tensors of `out`."""
+    dipole sums | None, quadrupole sums [n, 3, 3] | None) as `want` asks for them; with `out` the launch adds to its tensors."""
     pos = p["pos"]
-    n, dev = pos.shape[0], pos.device
-    f64 = dict(dtype=torch.float64, device=dev)
-    if accumulate:
-        e, f, cg, dg, qg = out
-    else:
-        e = torch.empty(n, **f64) if energies else None
-        f = torch.empty((n, 3), dtype=pos.dtype, device=dev) if forces else None
-        cg = torch.empty(n, **f64) if cgrads else None
-        dg = torch.empty((n, 3), **f64) if dgrads else None
-        qg = torch.empty((n, 3, 3), **f64) if qgrads else None
+    e, f, cg, dg, qg = M.allocate(pos, M.QUADRUPOLE, want) if out is None else out
     rc = C.lib().mi_pme_quadrupole_gather(C.ptr(pos), C.ptr(p["q"]), C.ptr(p["mu"]), C.ptr(p["qd"]), C.ptr(weights), C.ptr(p["bi"]),
-                                          C.ptr(p["cit"]), C.ptr(mesh_a), C.ptr(mesh_b), C.ptr(p["al"]), n, int(p["nsys"]), *dims, int(order),
-                                          p["code"], int(accumulate), C.ptr(e), C.ptr(f), C.ptr(cg), C.ptr(dg), C.ptr(qg), C.stream_of(pos))
+                                          C.ptr(p["cit"]), C.ptr(mesh_a), C.ptr(mesh_b), C.ptr(p["al"]), pos.shape[0], int(p["nsys"]), *dims,
+                                          int(order), p["code"], int(out is not None), C.ptr(e), C.ptr(f), C.ptr(cg), C.ptr(dg), C.ptr(qg),
+                                          C.stream_of(pos))
     C.check(rc, "mi_pme_quadrupole_gather")
     return e, f, cg, dg, qg
 
 
-def _per_atom(p, values):
-    return values[p["bi"].long()] if p["bi"] is not None else values.expand(p["pos"].shape[0])
+def _virial(p, spec, sums, dims, order):
+    """Float64 [nsys, 3, 3]: the k-space virial of the cross spectrum plus the term of the multipoles that follow the strain."""
+    L = C.lib()
+    dev, dg, qg = p["pos"].device, sums[3], sums[4]
+    part = torch.empty((p["nsys"], int(L.mi_pme_quadrupole_virial_blocks()), 9), dtype=torch.float64, device=dev)
+    rc = L.mi_pme_quadrupole_virial(C.ptr(spec[0]), C.ptr(spec[1]), C.ptr(p["recip"]), C.ptr(p["al"]), C.ptr(p["vol"]), int(p["nsys"]), *dims,
+                                    int(order), p["code"], C.ptr(part), C.stream_of(p["pos"]))
+    C.check(rc, "mi_pme_quadrupole_virial")
+    # the multipoles' fractional components follow the strain: + sum_i (dE/dmu_i)_a mu_i,b + 2 sum_i (G_i Q_i)_ab per system, G_i = dE/dQ_i
+    # without its self terms (index order and the factor 2 matter: the virial is not symmetric)
+    al = M.per_atom(p, p["al"].to(torch.float64))
+    c3 = (4.0 * al**3 / (3.0 * math.sqrt(math.pi))).reshape(-1, 1, 1)
+    c5 = (4.0 * al**5 / (5.0 * math.sqrt(math.pi))).reshape(-1, 1, 1)
+    mu64, q64, qd64 = p["mu"].to(torch.float64), p["q"].to(torch.float64).reshape(-1, 1, 1), p["qd"].to(torch.float64)
+    qd64 = 0.5 * (qd64 + qd64.transpose(1, 2))
+    eye = torch.eye(3, dtype=torch.float64, device=dev)
+    tr = qd64.diagonal(dim1=1, dim2=2).sum(-1).reshape(-1, 1, 1)
+    bare = qg - c3 * q64 * eye + c5 * (4.0 * qd64 + 2.0 * tr * eye)
+    outer = dg.unsqueeze(2) * mu64.unsqueeze(1) + 2.0 * bare @ qd64
+    return M.strained_multipole_virial(p, part, outer)
 
 
-def _recip_forward(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, dims, order, forces, cgrads, dgrads, qgrads, virial):
+def _recip_forward(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, nx, ny, nz, order, *flags):
     """(energies, forces | None, charge_grads | None, dipole_grads | None, quadrupole_grads | None, virial | None) in the positions dtype, no
     autograd graph: what the eager call and the `alchemiops::_pme_quadrupole_reciprocal_space` op both run."""
-    n, dev, dt = positions.shape[0], positions.device, positions.dtype
-    want = (True, forces, cgrads, dgrads, qgrads, virial)
-    if n == 0:
-        return tuple(r if w else None for r, w in zip(_zeros(0, P.num_systems(cell, batch_idx), dt, dev), want))
-    dims = tuple(int(v) for v in dims)
-    p = _inputs(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx)
-    phi, spec = _solve(p, _spread(p, dims, order), dims, order, need_spec=virial)
-    phi[0] += phi[1]  # phi_L = phi_l + phi_T: the gather reads (A, B) = (phi_T, phi_L)
-    e, f, cg, dg, qg = _gather(p, dims, order, phi[1], phi[0], energies=True, forces=forces, cgrads=cgrads, dgrads=dgrads or virial,
-                               qgrads=qgrads or virial)
-    vir = None
-    if virial:
-        L = C.lib()
-        part = torch.empty((p["nsys"], int(L.mi_pme_quadrupole_virial_blocks()), 9), dtype=torch.float64, device=dev)
-        rc = L.mi_pme_quadrupole_virial(C.ptr(spec[0]), C.ptr(spec[1]), C.ptr(p["recip"]), C.ptr(p["al"]), C.ptr(p["vol"]), int(p["nsys"]), *dims,
-                                        int(order), p["code"], C.ptr(part), C.stream_of(positions))
-        C.check(rc, "mi_pme_quadrupole_virial")
-        # the multipoles' fractional components follow the strain: + sum_i (dE/dmu_i)_a mu_i,b + 2 sum_i (G_i Q_i)_ab per system, G_i = dE/dQ_i
-        # without its self terms (index order and the factor 2 matter: the virial is not symmetric)
-        al = _per_atom(p, p["al"].to(torch.float64))
-        c3 = (4.0 * al**3 / (3.0 * math.sqrt(math.pi))).reshape(-1, 1, 1)
-        c5 = (4.0 * al**5 / (5.0 * math.sqrt(math.pi))).reshape(-1, 1, 1)
-        mu64, q64, qd64 = p["mu"].to(torch.float64), p["q"].to(torch.float64).reshape(-1, 1, 1), p["qd"].to(torch.float64)
-        qd64 = 0.5 * (qd64 + qd64.transpose(1, 2))
-        eye = torch.eye(3, dtype=torch.float64, device=dev)
-        tr = qd64.diagonal(dim1=1, dim2=2).sum(-1).reshape(-1, 1, 1)
-        bare = qg - c3 * q64 * eye + c5 * (4.0 * qd64 + 2.0 * tr * eye)
-        outer = dg.unsqueeze(2) * mu64.unsqueeze(1) + 2.0 * bare @ qd64
-        vir = C.fold_virial9(part)
-        if p["bi"] is not None:
-            vir = vir.index_add(0, p["bi"].long(), outer)
-        else:
-            vir = vir + outer.sum(0, keepdim=True)
-        vir = vir.to(dt)
-    return e.to(dt), f, cg.to(dt) if cgrads else None, dg.to(dt) if dgrads else None, qg.to(dt) if qgrads else None, vir
+    return M.mesh_forward(MESH, (positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx), (nx, ny, nz), order, (True,) + flags)
 
 
-def _recip_adjoint(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, dims, order, grad_energies):
-    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles, dL/dquadrupoles) of L = sum_i g_i E_i.  The gather is its own adjoint: the g-weighted
-    meshes ride in the same spread and the same batched solve (four meshes), and
-        dL/dtheta_i = g_i x [gather over (phi_T, phi_L)] + [gather over (phi^g_T, phi^g_l + phi^g_T)],   self terms x g_i."""
-    n, dev = positions.shape[0], positions.device
-    f64 = dict(dtype=torch.float64, device=dev)
-    if n == 0:
-        return torch.zeros((0, 3), **f64), torch.zeros(0, **f64), torch.zeros((0, 3), **f64), torch.zeros((0, 3, 3), **f64)
-    dims = tuple(int(v) for v in dims)
-    p = _inputs(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx)
-    g = grad_energies.detach().to(torch.float64).contiguous()
-    phi, _ = _solve(p, _spread(p, dims, order, weights=g), dims, order, need_spec=False)
-    phi[0] += phi[1]
-    phi[2] += phi[3]
-    out = _gather(p, dims, order, phi[1], phi[0], weights=g, forces=True, cgrads=True, dgrads=True, qgrads=True)
-    _, f, gq, gmu, gqd = _gather(p, dims, order, phi[3], phi[2], accumulate=True, out=out)
-    return -f.to(torch.float64), gq, gmu, gqd
+def _recip_adjoint(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, nx, ny, nz, order, grad_energies):
+    """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles, dL/dquadrupoles) of L = sum_i g_i E_i, over (phi_T, phi_L) and (phi^g_T, phi^g_l +
+    phi^g_T); the self terms x g_i."""
+    return M.mesh_adjoint(MESH, (positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx), (nx, ny, nz), order, grad_energies)
 
 
 # ---- public -------------------------------------------------------------------------------------------------------------------------------
@@ -213,23 +154,9 @@ def pme_quadrupole_reciprocal_space(positions: torch.Tensor, charges: torch.Tens
     RETURNS"""
     dipoles = _dipoles_or_zeros(positions, dipoles)
     _check_recip(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx)
-    order = _check_order(spline_order)
-    cells, n_sys = _prepare_cell(cell)
-    dims = _mesh_dims(cells, mesh_dimensions, mesh_spacing, order)
-    n, dev, dt = positions.shape[0], positions.device, positions.dtype
     want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_quadrupole_gradients, compute_virial)
-    if n == 0:
-        return P.select(_zeros(0, P.num_systems(cell, batch_idx), dt, dev), want)
-    alpha_t = (_pme._traceable_alpha if C.tracing() else _prepare_alpha)(alpha, n_sys, dt, dev)
-    flags = tuple(bool(w) for w in want[1:])
-    if P.needs_op(positions, charges, dipoles, quadrupoles, cell, alpha_t):
-        from nvalchemiops import _eops
-
-        res = _eops.pme_quadrupole_reciprocal_space_op(positions, charges.to(dt), dipoles.to(dt), quadrupoles.to(dt), cells, alpha_t, batch_idx,
-                                                       *dims, order, *flags)
-    else:
-        res = _recip_forward(positions, charges, dipoles, quadrupoles, cells, alpha_t, batch_idx, dims, order, *flags)
-    return P.select(res, want)
+    return M.mesh_reciprocal_space(MESH, (positions, charges, dipoles, quadrupoles), cell, alpha, mesh_dimensions, mesh_spacing, spline_order,
+                                   batch_idx, want)
 
 
 @C.traceable
@@ -259,36 +186,14 @@ def pme_quadrupole_correction(positions: torch.Tensor, charges: torch.Tensor, di
     dipoles = _dipoles_or_zeros(positions, dipoles)
     _check_real(positions, charges, dipoles, quadrupoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
                 neighbor_matrix_shifts, batch_idx, alpha, compute_virial)
-    order = _check_order(spline_order)
-    cells, n_sys = _prepare_cell(cell)
-    if mesh_dimensions is not None:
-        mesh_dimensions = _mesh_dims(cells, mesh_dimensions, None, order)
-    if positions.shape[0] == 0:
-        want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_quadrupole_gradients, compute_virial)
-        return P.select(_zeros(0, P.num_systems(cell, batch_idx), positions.dtype, positions.device), want)
-    C.require_device(positions, charges, dipoles, quadrupoles, cell, batch_idx)
-    if alpha is None:
-        est = _pme.estimate_pme_parameters(positions, cells, batch_idx, accuracy)
-        alpha = est.alpha
-        if mesh_dimensions is None and mesh_spacing is None:
-            mesh_dimensions = tuple(est.mesh_dimensions)
-    alpha_t = (_pme._traceable_alpha if C.tracing() else _prepare_alpha)(alpha, n_sys, positions.dtype, positions.device)
-    if mesh_dimensions is None:
-        mesh_dimensions = (_pme.mesh_spacing_to_dimensions(cells, mesh_spacing) if mesh_spacing is not None
-                           else _pme.estimate_pme_mesh_dimensions(cells, alpha_t, accuracy))
-    mesh_dimensions = _mesh_dims(cells, mesh_dimensions, None, order)
-    flags = dict(compute_forces=compute_forces, compute_charge_gradients=compute_charge_gradients,
-                 compute_dipole_gradients=compute_dipole_gradients, compute_quadrupole_gradients=compute_quadrupole_gradients,
-                 compute_virial=compute_virial)
-    rs = ewald_quadrupole_real_space(positions, charges, dipoles, quadrupoles, cells, alpha_t, neighbor_list=neighbor_list,
-                                     neighbor_ptr=neighbor_ptr, neighbor_shifts=neighbor_shifts, neighbor_matrix=neighbor_matrix,
-                                     neighbor_matrix_shifts=neighbor_matrix_shifts, mask_value=mask_value, batch_idx=batch_idx, **flags)
-    rec = pme_quadrupole_reciprocal_space(positions, charges, dipoles, quadrupoles, cells, alpha_t, mesh_dimensions=mesh_dimensions,
-                                          spline_order=order, batch_idx=batch_idx, **flags)
-    if isinstance(rs, tuple):
-        return tuple(a + b for a, b in zip(rs, rec))
-    return rs + rec
+    want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_quadrupole_gradients, compute_virial)
+    return M.mesh_correction(MESH, (positions, charges, dipoles, quadrupoles), cell, alpha, mesh_spacing, mesh_dimensions, spline_order, batch_idx,
+                             (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts), mask_value, want, accuracy)
 
+
+# what `_multipoles.mesh_*` run for this operator, bound here at import (see `pme_dipole.MESH`)
+MESH = dict(grads=M.QUADRUPOLE, flags=FLAGS, check_order=_check_order, spread=_spread, gather=_gather, virial=_virial, forward=_recip_forward,
+            op="pme_quadrupole_reciprocal_space_op", real=ewald_quadrupole_real_space, recip=pme_quadrupole_reciprocal_space)
 
 for _fn in (pme_quadrupole_reciprocal_space, pme_quadrupole_correction):
     _fn.__doc__ = _fn.__doc__.replace("MODEL", _MODEL).replace("RETURNS", _RETURNS)

@@ -18,10 +18,10 @@ import ctypes
 import torch
 
 from nvalchemiops import _capi as C
+from nvalchemiops.interactions.electrostatics import _multipoles as M
 from nvalchemiops.interactions.electrostatics import _pairs as P
 from nvalchemiops.interactions.electrostatics.ewald import _prepare_alpha, _prepare_cell
 
-QD_FORCES, QD_CHARGE_GRAD, QD_DIPOLE_GRAD, QD_VIRIAL, QD_QUADRUPOLE_GRAD = P.FORCES, P.CHARGE_GRAD, P.THIRD_GRAD, P.VIRIAL, 16  # MI_QD_*
 _TABLE_WORDS, _V_WORDS = 10, 6  # {Re, Im} of {S_q, M_x, M_y, M_z, T}; {Re, Im} of V = sum_j (Q_j k) e^{i k.r_j} (virial only)
 
 _MODEL = """Atom i carries q_i, mu_i and a symmetric Cartesian quadrupole Q_i, `quadrupoles` [N, 3, 3]: the second Taylor coefficient
@@ -70,38 +70,26 @@ def _dipoles_or_zeros(positions, dipoles):
     return torch.zeros((positions.shape[0], 3), dtype=positions.dtype, device=positions.device) if dipoles is None else dipoles
 
 
-def _zeros(n, nsys, dt, dev):
-    z = lambda *shape: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
-    return z(n), z(n, 3), z(n), z(n, 3), z(n, 3, 3), z(nsys, 3, 3)
-
-
-def _flag_bits(forces, cgrads, dgrads, qgrads, virial) -> int:
-    return P.flag_bits(forces, cgrads, dgrads, virial) | (QD_QUADRUPOLE_GRAD if qgrads else 0)
-
-
 # ---- real space ---------------------------------------------------------------------------------------------------------------------------
-def _real_inputs(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, *lists):
-    return P.launch_inputs(positions, charges, cell, batch_idx, lists, mu=dipoles, qd=quadrupoles, al=alpha.reshape(-1))
+def _real_inputs(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                 neighbor_matrix_shifts, mask_value):
+    lists = (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
+    return P.launch_inputs(positions, charges, cell, batch_idx, lists, int(mask_value), mu=dipoles, qd=quadrupoles, al=alpha.reshape(-1))
 
 
-def _real_launch(p, mask_value: int, flags: int, weights=None, energies: bool = True):
+def _real_launch(p, flags: int, weights=None, energies: bool = True):
     """One `mi_ewald_quadrupole_real` launch: float64 (energies | None, forces in the positions dtype | None, charge sums | None, dipole sums |
     None, quadrupole sums [n, 3, 3] | None, virial block partials [nsys, blocks, 9] | None)."""
     pos = p["pos"]
-    n, dev, dt = pos.shape[0], pos.device, pos.dtype
+    n, dt = pos.shape[0], pos.dtype
     L = C.lib()
-    f64 = dict(dtype=torch.float64, device=dev)
-    e = torch.empty(n, **f64) if energies else None
-    f = torch.empty((n, 3), dtype=dt, device=dev) if flags & QD_FORCES else None
-    cg = torch.empty(n, **f64) if flags & QD_CHARGE_GRAD else None
-    dg = torch.empty((n, 3), **f64) if flags & QD_DIPOLE_GRAD else None
-    qg = torch.empty((n, 3, 3), **f64) if flags & QD_QUADRUPOLE_GRAD else None
-    part = torch.empty((p["nsys"], int(L.mi_ewald_quadrupole_blocks()), 9), **f64) if flags & QD_VIRIAL else None
+    e, f, cg, dg, qg = M.allocate(pos, M.QUADRUPOLE, (energies, flags & P.FORCES, flags & P.CHARGE_GRAD, flags & P.THIRD_GRAD,
+                                                      flags & P.FOURTH_GRAD))
     nbytes = int(L.mi_ewald_quadrupole_real_scratch_bytes(n, C.dtype_code(dt)))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    part, scratch = M.pair_scratch(p, flags, int(L.mi_ewald_quadrupole_blocks()), nbytes)
     rc = L.mi_ewald_quadrupole_real(C.ptr(pos), C.ptr(p["q"]), C.ptr(p["mu"]), C.ptr(p["qd"]), C.ptr(p["cells"]), C.ptr(p["al"]), C.ptr(p["bi"]),
                                     C.ptr(weights), n, int(p["nsys"]), C.dtype_code(dt), C.ptr(p["idx"]), C.ptr(p["sh"]), C.ptr(p["nptr"]),
-                                    int(p["m"]), int(mask_value), int(flags), C.ptr(e), C.ptr(f), C.ptr(cg), C.ptr(dg), C.ptr(qg), C.ptr(part),
+                                    int(p["m"]), p["mask"], int(flags), C.ptr(e), C.ptr(f), C.ptr(cg), C.ptr(dg), C.ptr(qg), C.ptr(part),
                                     C.ptr(scratch), ctypes.c_size_t(nbytes), C.stream_of(pos))
     C.check(rc, "mi_ewald_quadrupole_real")
     return e, f, cg, dg, qg, part
@@ -112,28 +100,16 @@ def _real_forward(positions, charges, dipoles, quadrupoles, cell, alpha, batch_i
     """(energies, forces | None, charge_grads | None, dipole_grads | None, quadrupole_grads | None, virial | None) in the positions dtype, no
     autograd graph: what the eager call and the `alchemiops::_ewald_quadrupole_real_space` op both run."""
     p = _real_inputs(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
-                     neighbor_matrix, neighbor_matrix_shifts)
-    n, dev, dt = positions.shape[0], positions.device, positions.dtype
-    want = (True, forces, cgrads, dgrads, qgrads, virial)
-    if n == 0 or p["n_entries"] == 0:
-        return tuple(r if w else None for r, w in zip(_zeros(n, p["nsys"], dt, dev), want))
-    e, f, cg, dg, qg, part = _real_launch(p, mask_value, _flag_bits(forces, cgrads, dgrads, qgrads, virial))
-    return (e.to(dt), f, cg.to(dt) if cgrads else None, dg.to(dt) if dgrads else None, qg.to(dt) if qgrads else None,
-            C.fold_virial9(part).to(dt) if virial else None)
+                     neighbor_matrix, neighbor_matrix_shifts, mask_value)
+    return M.pair_forward(p, _real_launch, M.QUADRUPOLE, (True, forces, cgrads, dgrads, qgrads, virial))
 
 
 def _real_adjoint(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
                   neighbor_matrix_shifts, mask_value, grad_energies):
     """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles, dL/dquadrupoles) of L = sum_i g_i E_i: the forward kernel with weights."""
     p = _real_inputs(positions, charges, dipoles, quadrupoles, cell, alpha, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
-                     neighbor_matrix, neighbor_matrix_shifts)
-    n, dev = positions.shape[0], positions.device
-    f64 = dict(dtype=torch.float64, device=dev)
-    if n == 0 or p["n_entries"] == 0:
-        return torch.zeros((n, 3), **f64), torch.zeros(n, **f64), torch.zeros((n, 3), **f64), torch.zeros((n, 3, 3), **f64)
-    g = grad_energies.detach().to(torch.float64).contiguous()
-    _, f, gq, gmu, gqd, _ = _real_launch(p, mask_value, QD_FORCES | QD_CHARGE_GRAD | QD_DIPOLE_GRAD | QD_QUADRUPOLE_GRAD, weights=g, energies=False)
-    return -f.to(torch.float64), gq, gmu, gqd
+                     neighbor_matrix, neighbor_matrix_shifts, mask_value)
+    return M.pair_adjoint(p, _real_launch, M.QUADRUPOLE, grad_energies)
 
 
 def _check_real(positions, charges, dipoles, quadrupoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
@@ -164,21 +140,13 @@ def ewald_quadrupole_real_space(positions: torch.Tensor, charges: torch.Tensor, 
     dipoles = _dipoles_or_zeros(positions, dipoles)
     _check_real(positions, charges, dipoles, quadrupoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
                 neighbor_matrix_shifts, batch_idx, alpha, compute_virial)
-    n, dev, dt = positions.shape[0], positions.device, positions.dtype
     want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_quadrupole_gradients, compute_virial)
-    if n == 0:
-        return P.select(_zeros(0, P.num_systems(cell, batch_idx), dt, dev), want)
-    alpha_t = _prepare_alpha(alpha, _prepare_cell(cell)[1], dt, dev)
-    lists = (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
-    flags = tuple(bool(w) for w in want[1:])
-    if P.needs_op(positions, charges, dipoles, quadrupoles, cell, alpha_t):
-        from nvalchemiops import _eops
-
-        res = _eops.ewald_quadrupole_real_space_op(positions, charges.to(dt), dipoles.to(dt), quadrupoles.to(dt), cell, alpha_t, batch_idx, *lists,
-                                                   int(mask_value), *flags)
-    else:
-        res = _real_forward(positions, charges, dipoles, quadrupoles, cell, alpha_t, batch_idx, *lists, int(mask_value), *flags)
-    return P.select(res, want)
+    if positions.shape[0] == 0:
+        return M.no_atoms(positions, P.num_systems(cell, batch_idx), M.QUADRUPOLE, want)
+    alpha_t = _prepare_alpha(alpha, _prepare_cell(cell)[1], positions.dtype, positions.device)
+    return M.dispatch("ewald_quadrupole_real_space_op", _real_forward, (positions, charges, dipoles, quadrupoles), (cell, alpha_t),
+                      (batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts,
+                       int(mask_value)), want)
 
 
 # ---- reciprocal space ---------------------------------------------------------------------------------------------------------------------
@@ -207,15 +175,11 @@ def _table(p, weights=None, with_v: bool = False):
     return table, table_v
 
 
-def _gather(p, table, table_g=None, weights=None, energies=False, forces=False, cgrads=False, dgrads=False, qgrads=False):
+def _gather(p, table, want, table_g=None, weights=None):
+    """`want` = (energies, forces, charge sums, dipole sums, quadrupole sums), as `_multipoles.allocate` takes it."""
     pos = p["pos"]
-    n, dev = pos.shape[0], pos.device
-    f64 = dict(dtype=torch.float64, device=dev)
-    e = torch.empty(n, **f64) if energies else None
-    f = torch.empty((n, 3), dtype=pos.dtype, device=dev) if forces else None
-    cg = torch.empty(n, **f64) if cgrads else None
-    dg = torch.empty((n, 3), **f64) if dgrads else None
-    qg = torch.empty((n, 3, 3), **f64) if qgrads else None
+    n = pos.shape[0]
+    e, f, cg, dg, qg = M.allocate(pos, M.QUADRUPOLE, want)
     adjoint = weights is not None and table_g is not None
     rc = C.lib().mi_ewald_quadrupole_recip_gather(C.ptr(pos), C.ptr(p["q"]), C.ptr(p["mu"]), C.ptr(p["qd"]), C.ptr(p["kv"]) if p["n_k"] else None,
                                                   C.ptr(p["cells"]), C.ptr(p["al"]), C.ptr(p["bi"]), C.ptr(table),
@@ -232,10 +196,10 @@ def _recip_forward(positions, charges, dipoles, quadrupoles, cell, k_vectors, al
     n, dev, dt = positions.shape[0], positions.device, positions.dtype
     want = (True, forces, cgrads, dgrads, qgrads, virial)
     if n == 0:
-        return tuple(r if w else None for r, w in zip(_zeros(0, _prepare_cell(cell)[1], dt, dev), want))
+        return M.if_wanted(P.zeros(0, _prepare_cell(cell)[1], dt, dev, *M.QUADRUPOLE), want)
     p = _recip_inputs(positions, charges, dipoles, quadrupoles, cell, k_vectors, alpha, batch_idx)
     table, table_v = _table(p, with_v=bool(virial))
-    e, f, cg, dg, qg = _gather(p, table, energies=True, forces=forces, cgrads=cgrads, dgrads=dgrads, qgrads=qgrads)
+    sums = _gather(p, table, want[:-1])
     vir = None
     if virial:
         vir = torch.empty((p["nsys"], 9), dtype=torch.float64, device=dev)
@@ -243,24 +207,24 @@ def _recip_forward(positions, charges, dipoles, quadrupoles, cell, k_vectors, al
                                                       C.ptr(p["al"]), int(p["nsys"]), int(p["n_k"]), C.dtype_code(dt), C.ptr(vir),
                                                       C.stream_of(p["pos"]))
         C.check(rc, "mi_ewald_quadrupole_recip_virial")
-        vir = vir.reshape(-1, 3, 3).to(dt)
-    return e.to(dt), f, cg.to(dt) if cgrads else None, dg.to(dt) if dgrads else None, qg.to(dt) if qgrads else None, vir
+        vir = vir.reshape(-1, 3, 3)
+    return M.finish(sums, vir, want, dt)
 
 
 def _recip_adjoint(positions, charges, dipoles, quadrupoles, cell, k_vectors, alpha, batch_idx, grad_energies):
     """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles, dL/dquadrupoles) of L = sum_i g_i E_i: a second table summed with the weights g, and
     the gather in its adjoint form (the bilinear form of atom i's factor with g_i S + S^g, halved; self term times g_i)."""
     n, dev = positions.shape[0], positions.device
-    f64 = dict(dtype=torch.float64, device=dev)
     if n == 0:
-        return torch.zeros((0, 3), **f64), torch.zeros(0, **f64), torch.zeros((0, 3), **f64), torch.zeros((0, 3, 3), **f64)
+        return M.zero_gradients(0, dev, M.QUADRUPOLE)
     p = _recip_inputs(positions, charges, dipoles, quadrupoles, cell, k_vectors, alpha, batch_idx)
-    g = grad_energies.detach().to(torch.float64).contiguous()
+    g = M.weights_of(grad_energies)
     table, _ = _table(p)
     if table is None:  # no k-vectors: the self term alone, whose gradients are g_i times the plain ones
-        _, _, cg, _, qg = _gather(p, None, cgrads=True, qgrads=True)
-        return torch.zeros((n, 3), **f64), g * cg, torch.zeros((n, 3), **f64), g.reshape(-1, 1, 1) * qg
-    _, f, gq, gmu, gqd = _gather(p, table, table_g=_table(p, weights=g)[0], weights=g, forces=True, cgrads=True, dgrads=True, qgrads=True)
+        _, _, cg, _, qg = _gather(p, None, (False, False, True, False, True))
+        no_force, no_dipole_gradient = M.zero_gradients(n, dev, ((3,),))
+        return no_force, g * cg, no_dipole_gradient, g.reshape(-1, 1, 1) * qg
+    _, f, gq, gmu, gqd = _gather(p, table, (False, True, True, True, True), table_g=_table(p, weights=g)[0], weights=g)
     return -f.to(torch.float64), gq, gmu, gqd
 
 
@@ -293,17 +257,9 @@ def ewald_quadrupole_reciprocal_space(positions: torch.Tensor, charges: torch.Te
         raise ValueError(f"k_vectors must have shape [K, 3] or [{n_sys}, K, 3], got {tuple(k_vectors.shape)}")
     want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_quadrupole_gradients, compute_virial)
     if n == 0:
-        return P.select(_zeros(0, n_sys, dt, dev), want)
-    alpha_t = _prepare_alpha(alpha, n_sys, dt, dev)
-    flags = tuple(bool(w) for w in want[1:])
-    if P.needs_op(positions, charges, dipoles, quadrupoles, cell, k_vectors, alpha_t):
-        from nvalchemiops import _eops
-
-        res = _eops.ewald_quadrupole_reciprocal_space_op(positions, charges.to(dt), dipoles.to(dt), quadrupoles.to(dt), cells, k_vectors, alpha_t,
-                                                         batch_idx, *flags)
-    else:
-        res = _recip_forward(positions, charges, dipoles, quadrupoles, cells, k_vectors, alpha_t, batch_idx, *flags)
-    return P.select(res, want)
+        return M.no_atoms(positions, n_sys, M.QUADRUPOLE, want)
+    return M.dispatch("ewald_quadrupole_reciprocal_space_op", _recip_forward, (positions, charges, dipoles, quadrupoles),
+                      (cells, k_vectors, _prepare_alpha(alpha, n_sys, dt, dev)), (batch_idx,), want)
 
 
 @C.traceable
@@ -326,39 +282,18 @@ def ewald_quadrupole_correction(positions: torch.Tensor, charges: torch.Tensor, 
     truncated list is not detected.  A matrix entry equal to `mask_value` (default: N) or outside [0, N) is padding.
 
     RETURNS"""
-    from nvalchemiops.interactions.electrostatics.k_vectors import generate_k_vectors_ewald_summation
-    from nvalchemiops.interactions.electrostatics.parameters import estimate_ewald_parameters
-
     if mask_value is None:
         mask_value = positions.shape[0]
     dipoles = _dipoles_or_zeros(positions, dipoles)
     _check_real(positions, charges, dipoles, quadrupoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
                 neighbor_matrix_shifts, batch_idx, alpha, compute_virial)
-    cells, n_sys = _prepare_cell(cell)
-    if positions.shape[0] == 0:
-        want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_quadrupole_gradients, compute_virial)
-        return P.select(_zeros(0, P.num_systems(cell, batch_idx), positions.dtype, positions.device), want)
-    C.require_device(positions, charges, dipoles, quadrupoles, cell, k_vectors, batch_idx)
-    if alpha is None or (k_cutoff is None and k_vectors is None):
-        params = estimate_ewald_parameters(positions, cells, batch_idx, accuracy)
-        if alpha is None:
-            alpha = params.alpha
-        if k_cutoff is None:
-            k_cutoff = params.reciprocal_space_cutoff
-    alpha_t = _prepare_alpha(alpha, n_sys, positions.dtype, positions.device)
-    if k_vectors is None:
-        k_vectors = generate_k_vectors_ewald_summation(cells, k_cutoff)
-    flags = dict(compute_forces=compute_forces, compute_charge_gradients=compute_charge_gradients,
-                 compute_dipole_gradients=compute_dipole_gradients, compute_quadrupole_gradients=compute_quadrupole_gradients,
-                 compute_virial=compute_virial)
-    rs = ewald_quadrupole_real_space(positions, charges, dipoles, quadrupoles, cells, alpha_t, neighbor_list=neighbor_list,
-                                     neighbor_ptr=neighbor_ptr, neighbor_shifts=neighbor_shifts, neighbor_matrix=neighbor_matrix,
-                                     neighbor_matrix_shifts=neighbor_matrix_shifts, mask_value=mask_value, batch_idx=batch_idx, **flags)
-    rec = ewald_quadrupole_reciprocal_space(positions, charges, dipoles, quadrupoles, cells, k_vectors, alpha_t, batch_idx=batch_idx, **flags)
-    if isinstance(rs, tuple):
-        return tuple(a + b for a, b in zip(rs, rec))
-    return rs + rec
+    want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_quadrupole_gradients, compute_virial)
+    return M.ewald_correction(_EWALD, (positions, charges, dipoles, quadrupoles), cell, alpha, k_vectors, k_cutoff, batch_idx,
+                              (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts), mask_value, want, accuracy)
 
+
+FLAGS = ("compute_forces", "compute_charge_gradients", "compute_dipole_gradients", "compute_quadrupole_gradients", "compute_virial")
+_EWALD = dict(grads=M.QUADRUPOLE, flags=FLAGS, real=ewald_quadrupole_real_space, recip=ewald_quadrupole_reciprocal_space)
 
 for _fn in (ewald_quadrupole_real_space, ewald_quadrupole_reciprocal_space, ewald_quadrupole_correction):
     _fn.__doc__ = _fn.__doc__.replace("MODEL", _MODEL).replace("RETURNS", _RETURNS)

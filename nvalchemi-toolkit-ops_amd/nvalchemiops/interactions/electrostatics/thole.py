@@ -19,9 +19,9 @@ import math
 import torch
 
 from nvalchemiops import _capi as C
+from nvalchemiops.interactions.electrostatics import _multipoles as M
 from nvalchemiops.interactions.electrostatics import _pairs as P
 
-TH_POLAR_GRAD = 16  # MI_DP_POLAR_GRAD, beside the MI_DP_* bits of _pairs
 DEFAULT_THOLE = 0.39
 
 
@@ -47,18 +47,10 @@ def _check(positions, charges, dipoles, polarizability, cell, thole, neighbor_li
            neighbor_matrix_shifts, batch_idx, compute_virial) -> float:
     """Every argument error, before anything is launched: `_pairs.check_dipole_lists` with a cell, the cell-less rules of `_pairs.check_lists`
     without one, plus the polarisabilities and the Thole width."""
-    if positions.dim() != 2 or positions.shape[1] != 3:
-        raise ValueError(f"positions must have shape [num_atoms, 3], got {tuple(positions.shape)}")
-    if neighbor_list is not None and neighbor_matrix is not None:
-        raise ValueError("pass the list in ONE format: neighbor_list (with neighbor_ptr) or neighbor_matrix, not both")
+    M.check_positions_and_format(positions, neighbor_list, neighbor_matrix)
     thole = check_thole(thole)
-    if cell is None:
-        P.check_lists(positions, charges, 0.0, None, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, batch_idx,
-                      compute_virial)
-        P.check_dipoles(positions, dipoles)
-    else:
-        P.check_dipole_lists(positions, charges, dipoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts,
-                             batch_idx, None, compute_virial)
+    M.check_optional_cell_lists(positions, charges, dipoles, cell, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+                                neighbor_matrix_shifts, batch_idx, compute_virial)
     check_polarizability(positions.shape[0], polarizability)
     return thole
 
@@ -69,33 +61,26 @@ def _polar_tensor(polarizability, n, dt, dev):
     return torch.full((n,), float(polarizability), dtype=dt, device=dev)
 
 
-def _inputs(positions, charges, dipoles, polar, cell, batch_idx, *lists):
-    return P.launch_inputs(positions, charges, cell, batch_idx, lists, mu=dipoles, pol=polar)
+def _inputs(positions, charges, dipoles, polar, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
+            neighbor_matrix_shifts, mask_value, thole):
+    lists = (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
+    p = P.launch_inputs(positions, charges, cell, batch_idx, lists, int(mask_value), mu=dipoles, pol=polar)
+    p["thole"] = thole
+    return p
 
 
-def _zeros(n, nsys, dt, dev):
-    z = lambda *shape: torch.zeros(shape, dtype=dt, device=dev)  # noqa: E731
-    return z(n), z(n, 3), z(n), z(n, 3), z(n), z(nsys, 3, 3)
-
-
-def _launch(p, thole: float, mask_value: int, flags: int, weights=None, energies: bool = True):
+def _launch(p, flags: int, weights=None, energies: bool = True):
     """One `mi_thole_dipole` launch: float64 (energies | None, forces in the positions dtype | None, charge sums | None, dipole sums | None,
     polarisability sums | None, virial block partials [nsys, blocks, 9] | None)."""
     pos = p["pos"]
-    n, dev, dt = pos.shape[0], pos.device, pos.dtype
+    n, dt = pos.shape[0], pos.dtype
     L = C.lib()
-    f64 = dict(dtype=torch.float64, device=dev)
-    e = torch.empty(n, **f64) if energies else None
-    f = torch.empty((n, 3), dtype=dt, device=dev) if flags & P.FORCES else None
-    cg = torch.empty(n, **f64) if flags & P.CHARGE_GRAD else None
-    dg = torch.empty((n, 3), **f64) if flags & P.THIRD_GRAD else None
-    pg = torch.empty(n, **f64) if flags & TH_POLAR_GRAD else None
-    part = torch.empty((p["nsys"], int(L.mi_thole_dipole_blocks()), 9), **f64) if flags & P.VIRIAL else None
+    e, f, cg, dg, pg = M.allocate(pos, M.THOLE, (energies, flags & P.FORCES, flags & P.CHARGE_GRAD, flags & P.THIRD_GRAD, flags & P.FOURTH_GRAD))
     nbytes = int(L.mi_thole_dipole_scratch_bytes(n, C.dtype_code(dt)))
-    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    rc = L.mi_thole_dipole(C.ptr(pos), C.ptr(p["q"]), C.ptr(p["mu"]), C.ptr(p["cells"]), C.ptr(p["pol"]), C.cdouble(thole), C.ptr(p["bi"]),
+    part, scratch = M.pair_scratch(p, flags, int(L.mi_thole_dipole_blocks()), nbytes)
+    rc = L.mi_thole_dipole(C.ptr(pos), C.ptr(p["q"]), C.ptr(p["mu"]), C.ptr(p["cells"]), C.ptr(p["pol"]), C.cdouble(p["thole"]), C.ptr(p["bi"]),
                            C.ptr(weights), n, int(p["nsys"]), C.dtype_code(dt), C.ptr(p["idx"]), C.ptr(p["sh"]), C.ptr(p["nptr"]), int(p["m"]),
-                           int(mask_value), int(flags), C.ptr(e), C.ptr(f), C.ptr(cg), C.ptr(dg), C.ptr(pg), C.ptr(part), C.ptr(scratch),
+                           p["mask"], int(flags), C.ptr(e), C.ptr(f), C.ptr(cg), C.ptr(dg), C.ptr(pg), C.ptr(part), C.ptr(scratch),
                            ctypes.c_size_t(nbytes), C.stream_of(pos))
     C.check(rc, "mi_thole_dipole")
     return e, f, cg, dg, pg, part
@@ -106,29 +91,16 @@ def _forward(positions, charges, dipoles, polar, cell, batch_idx, neighbor_list,
     """(energies, forces | None, charge_grads | None, dipole_grads | None, polarizability_grads | None, virial | None) in the positions dtype, no
     autograd graph: what the eager call and the `alchemiops::_thole_dipole_correction` op both run."""
     p = _inputs(positions, charges, dipoles, polar, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                neighbor_matrix_shifts)
-    n, dev, dt = positions.shape[0], positions.device, positions.dtype
-    want = (True, forces, cgrads, dgrads, pgrads, virial)
-    if n == 0 or p["n_entries"] == 0:
-        return tuple(r if w else None for r, w in zip(_zeros(n, p["nsys"], dt, dev), want))
-    flags = P.flag_bits(forces, cgrads, dgrads, virial) | (TH_POLAR_GRAD if pgrads else 0)
-    e, f, cg, dg, pg, part = _launch(p, thole, mask_value, flags)
-    return (e.to(dt), f, cg.to(dt) if cgrads else None, dg.to(dt) if dgrads else None, pg.to(dt) if pgrads else None,
-            C.fold_virial9(part).to(dt) if virial else None)
+                neighbor_matrix_shifts, mask_value, thole)
+    return M.pair_forward(p, _launch, M.THOLE, (True, forces, cgrads, dgrads, pgrads, virial))
 
 
 def _adjoint(positions, charges, dipoles, polar, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
              neighbor_matrix_shifts, mask_value, thole, grad_energies):
     """Float64 (dL/dpositions, dL/dcharges, dL/ddipoles, dL/dpolarizability) of L = sum_i g_i E_i: the forward kernel with weights."""
     p = _inputs(positions, charges, dipoles, polar, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                neighbor_matrix_shifts)
-    n, dev = positions.shape[0], positions.device
-    f64 = dict(dtype=torch.float64, device=dev)
-    if n == 0 or p["n_entries"] == 0:
-        return torch.zeros((n, 3), **f64), torch.zeros(n, **f64), torch.zeros((n, 3), **f64), torch.zeros(n, **f64)
-    g = grad_energies.detach().to(torch.float64).contiguous()
-    _, f, gq, gmu, gpol, _ = _launch(p, thole, mask_value, P.FORCES | P.CHARGE_GRAD | P.THIRD_GRAD | TH_POLAR_GRAD, weights=g, energies=False)
-    return -f.to(torch.float64), gq, gmu, gpol
+                neighbor_matrix_shifts, mask_value, thole)
+    return M.pair_adjoint(p, _launch, M.THOLE, grad_energies)
 
 
 @C.traceable
@@ -173,20 +145,11 @@ def thole_dipole_correction(positions: torch.Tensor, charges: torch.Tensor, dipo
                    neighbor_matrix_shifts, batch_idx, compute_virial)
     n, dev, dt = positions.shape[0], positions.device, positions.dtype
     want = (True, compute_forces, compute_charge_gradients, compute_dipole_gradients, compute_polarizability_gradients, compute_virial)
-    nsys = cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1
     if n == 0:
-        return P.select(_zeros(0, nsys, dt, dev), want)
-    polar = _polar_tensor(polarizability, n, dt, dev)
-    lists = (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
-    flags = tuple(bool(w) for w in want[1:])
-    if P.needs_op(positions, charges, dipoles, polar, cell):
-        from nvalchemiops import _eops
-
-        res = _eops.thole_dipole_correction_op(positions, charges.to(dt), dipoles.to(dt), polar.to(dt), cell, batch_idx, *lists, int(mask_value),
-                                               thole, *flags)
-    else:
-        res = _forward(positions, charges, dipoles, polar, cell, batch_idx, *lists, int(mask_value), thole, *flags)
-    return P.select(res, want)
+        return M.no_atoms(positions, M.num_systems(cell, batch_idx), M.THOLE, want)
+    return M.dispatch("thole_dipole_correction_op", _forward, (positions, charges, dipoles, _polar_tensor(polarizability, n, dt, dev)), (cell,),
+                      (batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, int(mask_value),
+                       thole), want)
 
 
 __all__ = ["thole_dipole_correction"]

@@ -635,3 +635,29 @@ def test_dispersion_seam_is_pinned():
         assert str(getattr(torch.ops.nvalchemiops, name).default._schema) == schema, name
     for name, sig in want["signatures"].items():
         assert str(inspect.signature(getattr(D, name))) == sig, name
+
+
+def test_multipole_seam_is_pinned():
+    """The seam of the point-multipole family as it stood before its nine op pairs were generated from one table (nvalchemiops/_eops.py) and
+    its wrappers moved onto one call layer (interactions/electrostatics/_multipoles.py): the full schema of each of the eighteen ops and the
+    signature of each of the thirteen public functions, as recorded in tests/golden/multipole_seam.json (its note says at which commit and
+    how)."""
+    import inspect
+    import json
+
+    import nvalchemiops  # noqa: F401
+    from nvalchemiops import _eops  # noqa: F401  (registers the ops)
+    from nvalchemiops.interactions import electrostatics as E
+
+    want = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "multipole_seam.json")))
+    halves = ["ewald_dipole_real_space", "ewald_dipole_reciprocal_space", "pme_dipole_reciprocal_space", "thole_dipole_correction",
+              "ewald_quadrupole_real_space", "ewald_quadrupole_reciprocal_space", "pme_quadrupole_reciprocal_space",
+              "coulomb_dipole_correction", "coulomb_quadrupole_correction"]
+    composites = ["ewald_dipole_correction", "ewald_quadrupole_correction", "pme_dipole_correction", "pme_quadrupole_correction"]
+    assert sorted(want["signatures"]) == sorted(halves + composites)
+    assert sorted(want["schemas"]) == sorted([f"alchemiops::_{h}" for h in halves] + [f"nvalchemiops::{h}_backward" for h in halves])
+    for name, schema in want["schemas"].items():
+        namespace, op = name.split("::")
+        assert str(getattr(getattr(torch.ops, namespace), op).default._schema) == schema, name
+    for name, sig in want["signatures"].items():
+        assert str(inspect.signature(getattr(E, name))) == sig, name
