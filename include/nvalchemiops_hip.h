@@ -1151,6 +1151,44 @@ int mi_pme_corrections(const void* raw, const void* charges, const int32_t* batc
 /* per-system sum of charges (charges.sum() / scatter_add_, pme.py:1225,1241-1244); out zeroed by caller */
 int mi_segment_sum(const void* values, const int32_t* batch_idx, int n_atoms, int dtype, void* out /*[B]*/, void* stream);
 
+/* ---- local-frame multipoles (csrc/frames.hip; driver: nvalchemiops/interactions/electrostatics/frames.py) ---------------------------------
+ * Per-atom local dipoles [n_atoms][3] and quadrupoles [n_atoms][3][3] (1/2 (Q + Q^T) of it is used) rotated into the laboratory frame,
+ * mu = R mu_loc, Q = R Q_loc R^T, and the adjoint of that map: the torque forces on the frame-defining atoms.  frame_atoms [n_atoms][3] names
+ * the (z, x, y) atoms of every atom, a slot outside [0, n_atoms) names nobody; frame_kinds [n_atoms] is 0 NONE (R = I), 1 Z_ONLY, 2 Z_THEN_X,
+ * 3 BISECTOR, 4 Z_BISECT, 5 THREE_FOLD (Tinker / OpenMM's axis types; csrc/frames.hip states them), any other value is NONE.  d_a = r_a - r_i is
+ * the minimum image when cell [n_systems][3][3] is given (rows are lattice vectors; batch_idx [n_atoms] selects the row, NULL: system 0), the
+ * plain difference when cell is NULL.  Z_THEN_X with a y atom mirrors the local y axis when d_y . (d_z x d_x) < 0.  positions, the local
+ * multipoles, cell and the incoming gradients are in `dtype`; all arithmetic is float64 and every output is rounded once.  One thread per atom,
+ * mi_frame_block_threads() threads per block, no atomics: every output is bit-reproducible.  A zero or collinear pair of frame vectors gives
+ * non-finite values for that atom (and, after the gather, the atoms it names) only.
+ *
+ * mi_frame_rotate: dipoles [n_atoms][3] and quadrupoles [n_atoms][3][3] (exactly symmetric) in `dtype`; each is written exactly when its local
+ * input is given.
+ *
+ * mi_frame_adjoint: from dipole_grads = dL/dmu and quadrupole_grads = dL/dQ (either NULL: zero; 1/2 (g + g^T) is used) writes, per atom, the
+ * record records[i] = {-sum_a dL/dd_a, dL/dd_z, dL/dd_x, dL/dd_y} ([n_atoms][4][3] float64, every word written, zeros for slots the kind does
+ * not use), and when asked local_dipole_grads[i] = R^T dL/dmu, local_quadrupole_grads[i] = R^T 1/2 (g + g^T) R (float64, the mirrored
+ * components with their sign) and virial_rows[i][p][q] = -sum_a (dL/dd_a)[p] d_a[q] ([n_atoms][9] float64; needs a cell): minus the strain
+ * derivative of L under x -> (I + eps) x with the local multipoles held fixed.
+ *
+ * mi_frame_gather: out[i] = sign * (records[i][0] + sum of records[e / 4][e % 4] over e = inverse_slots[inverse_ptr[i] .. inverse_ptr[i + 1])),
+ * in the stored order ([n_atoms][3] in `dtype`, which need not be the dtype of the adjoint call): sign = +1 gives dL/dr, sign = -1 the torque
+ * forces.  inverse_slots [n_entries] holds, for every atom, the codes 4 * j + 1 + slot of the (atom j, slot) pairs that name it; a code outside
+ * [0, 4 n_atoms) is skipped.  With virial_rows, virial_partial [n_systems][mi_frame_blocks()][9] float64 receives the fixed-order per-system
+ * fold of the rows (every entry written; the caller sums the blocks). */
+int mi_frame_rotate(const void* positions, const void* local_dipoles, const void* local_quadrupoles, const int32_t* frame_atoms,
+                    const int32_t* frame_kinds, const void* cell, const int32_t* batch_idx, int n_atoms, int n_systems, int dtype, void* dipoles,
+                    void* quadrupoles, void* stream);
+int mi_frame_adjoint(const void* positions, const void* local_dipoles, const void* local_quadrupoles, const int32_t* frame_atoms,
+                     const int32_t* frame_kinds, const void* cell, const int32_t* batch_idx, const void* dipole_grads,
+                     const void* quadrupole_grads, int n_atoms, int n_systems, int dtype, double* records, double* local_dipole_grads,
+                     double* local_quadrupole_grads, double* virial_rows, void* stream);
+int mi_frame_gather(const double* records, const int32_t* inverse_ptr, const int32_t* inverse_slots, long long n_entries,
+                    const double* virial_rows, const int32_t* batch_idx, int n_atoms, int n_systems, int dtype, double sign, void* out,
+                    double* virial_partial, void* stream);
+int mi_frame_blocks(void);
+int mi_frame_block_threads(void);
+
 /* ---- multi-GPU: the one collective of the path (csrc/comm.cpp) ------------------------------------------------------------
  * The reference has no multi-GPU code; the path shards at SYSTEM granularity -- no pair crosses systems
  * (batch_cell_list.py:448-457, dftd3.py:823,1126, spline.py:809) -- so every rank runs the kernels above on its own contiguous range of

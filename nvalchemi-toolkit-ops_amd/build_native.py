@@ -40,6 +40,7 @@ SOURCES = {
     "pme.hip": os.environ.get("MI_PME_EXTRA_FLAGS", "").split(),
     "dft.hip": [],  # dense DFT of any mesh size: the transform of last resort behind the self-tested hipFFT plans
     "calib.hip": [],
+    "frames.hip": [],  # local-frame multipoles (mi_frame_*): rotation to the laboratory frame, its adjoint and the torque-force gather, all fp64
     "multipole.hip": [],  # spherical harmonics / Gaussian multipole basis (nvalchemiops.math): fp64 elementwise kernels
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]

@@ -242,6 +242,16 @@ def lib() -> ctypes.CDLL:
         for name in ("mi_induced_blocks", "mi_induced_state_words", "mi_induced_tensor_words", "mi_induced_unroll_depth"):
             getattr(L, name).restype = i
             getattr(L, name).argtypes = []
+        # local-frame multipoles (nvalchemiops/interactions/electrostatics/frames.py)
+        L.mi_frame_rotate.restype = i
+        L.mi_frame_rotate.argtypes = [vp] * 7 + [i, i, i, vp, vp, vp]
+        L.mi_frame_adjoint.restype = i
+        L.mi_frame_adjoint.argtypes = [vp] * 9 + [i, i, i] + [vp] * 5
+        L.mi_frame_gather.restype = i
+        L.mi_frame_gather.argtypes = [vp, vp, vp, ll, vp, vp, i, i, i, dbl, vp, vp, vp]
+        for name in ("mi_frame_blocks", "mi_frame_block_threads"):
+            getattr(L, name).restype = i
+            getattr(L, name).argtypes = []
         _LIB = L
     return _LIB
 

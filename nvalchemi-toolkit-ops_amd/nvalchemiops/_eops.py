@@ -1716,7 +1716,84 @@ coulomb_dipole_correction_op, coulomb_dipole_bwd_op = _MP["coulomb_dipole_correc
 coulomb_quadrupole_correction_op, coulomb_quadrupole_bwd_op = _MP["coulomb_quadrupole_correction"]
 
 
-__all__ = ["coulomb_dipole_correction_op", "coulomb_dipole_bwd_op", "coulomb_quadrupole_correction_op", "coulomb_quadrupole_bwd_op",
+# =====================================================================================================================================
+# local-frame multipoles: mu = R mu_loc, Q = R Q_loc R^T (nvalchemiops/interactions/electrostatics/frames.py)
+# =====================================================================================================================================
+# Both outputs are differentiable w.r.t. positions and the local multipoles; the backward op runs `mi_frame_adjoint` + `mi_frame_gather` and
+# returns float64 gradients.  An output whose local input is None is an empty [0] tensor, and so is the gradient of an input that is None.
+_FR_NO_GRAD = ("{op}: gradients w.r.t. cell are not provided by the local-frame rotation (out of scope); use compute_virial of "
+               "multipole_frame_forces for the strain derivative.")
+_FR_NAME = f"{_NS}::_rotate_multipoles"
+_FR_INPUTS = ("Tensor positions, Tensor? local_dipoles, Tensor? local_quadrupoles, Tensor? cell, Tensor? batch_idx, Tensor frame_atoms, "
+              "Tensor frame_kinds")
+
+
+def _frames():
+    return importlib.import_module("nvalchemiops.interactions.electrostatics.frames")
+
+
+def _rotate_fwd(positions, local_dipoles, local_quadrupoles, cell, batch_idx, frame_atoms, frame_kinds, inverse_ptr, inverse_slots):
+    mu, qd = _frames()._forward(positions, local_dipoles, local_quadrupoles, cell, batch_idx, frame_atoms, frame_kinds)
+    return tuple(positions.new_empty((0,)) if o is None else o for o in (mu, qd))
+
+
+def _rotate_fwd_fake(positions, local_dipoles, local_quadrupoles, cell, batch_idx, frame_atoms, frame_kinds, inverse_ptr, inverse_slots):
+    n = positions.shape[0]
+    return (positions.new_empty((n, 3) if local_dipoles is not None else (0,)),
+            positions.new_empty((n, 3, 3) if local_quadrupoles is not None else (0,)))
+
+
+def _rotate_bwd(positions, local_dipoles, local_quadrupoles, cell, batch_idx, frame_atoms, frame_kinds, inverse_ptr, inverse_slots, grad_dipoles,
+                grad_quadrupoles):
+    return _frames()._adjoint(positions, local_dipoles, local_quadrupoles, cell, batch_idx, frame_atoms, frame_kinds, inverse_ptr, inverse_slots,
+                              grad_dipoles, grad_quadrupoles)
+
+
+def _rotate_bwd_fake(positions, local_dipoles, local_quadrupoles, cell, batch_idx, frame_atoms, frame_kinds, inverse_ptr, inverse_slots,
+                     grad_dipoles, grad_quadrupoles):
+    n = positions.shape[0]
+    f64 = lambda shape: positions.new_empty(shape, dtype=torch.float64)  # noqa: E731
+    return f64((n, 3)), f64((n, 3) if local_dipoles is not None else (0,)), f64((n, 3, 3) if local_quadrupoles is not None else (0,))
+
+
+def _rotate_refuse_second_order(ctx, *grads):
+    raise NotImplementedError(_SECOND_ORDER.format(op="nvalchemiops::rotate_multipoles_backward", what="gradient"))
+
+
+rotate_multipoles_bwd_op = torch.library.custom_op(
+    "nvalchemiops::rotate_multipoles_backward", _rotate_bwd, mutates_args=(),
+    schema=f"({_FR_INPUTS}, Tensor inverse_ptr, Tensor inverse_slots, Tensor? grad_dipoles, Tensor? grad_quadrupoles) -> (Tensor, Tensor, Tensor)")
+rotate_multipoles_bwd_op.register_fake(_rotate_bwd_fake)
+rotate_multipoles_bwd_op.register_autograd(_rotate_refuse_second_order, setup_context=lambda ctx, inputs, output: None)
+
+
+def _rotate_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+    ctx.set_materialize_grads(False)
+
+
+def _rotate_backward(ctx, g_mu, g_qd):
+    need = ctx.needs_input_grad
+    if need[3]:
+        raise NotImplementedError(_FR_NO_GRAD.format(op=_FR_NAME))
+    saved = ctx.saved_tensors
+    if g_mu is not None and saved[1] is None:
+        g_mu = None
+    if g_qd is not None and saved[2] is None:
+        g_qd = None
+    if g_mu is None and g_qd is None:
+        return (None,) * len(need)
+    grads = rotate_multipoles_bwd_op(*saved, g_mu, g_qd)
+    return tuple(g.to(t.dtype) if w else None for g, t, w in zip(grads, saved[:3], need[:3])) + (None,) * (len(need) - 3)
+
+
+rotate_multipoles_op = torch.library.custom_op(_FR_NAME, _rotate_fwd, mutates_args=(),
+                                               schema=f"({_FR_INPUTS}, Tensor inverse_ptr, Tensor inverse_slots) -> (Tensor, Tensor)")
+rotate_multipoles_op.register_fake(_rotate_fwd_fake)
+rotate_multipoles_op.register_autograd(_rotate_backward, setup_context=_rotate_setup)
+
+
+__all__ = ["rotate_multipoles_op", "rotate_multipoles_bwd_op", "coulomb_dipole_correction_op", "coulomb_dipole_bwd_op", "coulomb_quadrupole_correction_op", "coulomb_quadrupole_bwd_op",
            "pme_quadrupole_reciprocal_space_op", "pme_quadrupole_recip_bwd_op",
            "ewald_quadrupole_real_space_op", "ewald_quadrupole_reciprocal_space_op", "ewald_quadrupole_real_bwd_op",
            "ewald_quadrupole_recip_bwd_op", "thole_dipole_correction_op", "thole_dipole_bwd_op", "pme_dipole_reciprocal_space_op", "pme_dipole_recip_bwd_op", "ewald_dipole_real_space_op", "ewald_dipole_reciprocal_space_op", "ewald_dipole_real_bwd_op", "ewald_dipole_recip_bwd_op",

@@ -40,7 +40,9 @@ _RETURNS = """Returns ``energies`` [N], or a tuple holding only what was asked f
     dipole_grads [N, 3], virial [num_systems, 3, 3]; all in the positions dtype (sums in float64).  forces = -dE/dr, charge_grads = dE/dq,
     dipole_grads = dE/dmu of the total E = sum_i E_i: dipole_grads is minus the electric field at the atom (it does not vanish for zero
     dipoles), and the torque on a dipole is mu x (-dipole_grads).  virial = -dE/d(strain) under x -> (I + eps) x with the dipoles held fixed in
-    the laboratory frame: dU/dR is then not parallel to R, so the virial has nine independent components and is NOT symmetric.
+    the laboratory frame: dU/dR is then not parallel to R, so the virial has nine independent components and is NOT symmetric.  For dipoles
+    defined in local frames (`rotate_multipoles`), `multipole_frame_forces` turns that torque into forces on the frame atoms and returns the
+    term the virial lacks.
 
     Energies are differentiable once w.r.t. positions, charges and dipoles, for any upstream gradient on the per-atom energies (the same
     kernels run as their own adjoint); the call then goes through an `alchemiops::_ewald_dipole_*` op, as it does under `torch.compile`.

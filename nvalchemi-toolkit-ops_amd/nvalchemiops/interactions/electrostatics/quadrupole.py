@@ -50,7 +50,8 @@ _RETURNS = """Returns ``energies`` [N], or a tuple holding only what was asked f
     this correction does not depend on the dipoles (the dipole-quadrupole term is linear in mu): minus dipole_grads is the electric field of
     the quadrupoles at each atom, which is what `induced_dipoles(external_field=...)` takes.  virial = -dE/d(strain) under x -> (I + eps) x
     with the multipoles held fixed in the laboratory frame: dU/dR is then not parallel to R, so the virial has nine independent components and
-    is NOT symmetric.
+    is NOT symmetric.  For multipoles defined in local frames (`rotate_multipoles`), `multipole_frame_forces` turns the torques on them into
+    forces on the frame atoms and returns the term the virial lacks.
 
     Energies are differentiable once w.r.t. positions, charges, dipoles and quadrupoles, for any upstream gradient on the per-atom energies
     (the same kernels run as their own adjoint); the call then goes through an `alchemiops::_ewald_quadrupole_*` op, as it does under
