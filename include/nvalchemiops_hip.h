@@ -649,6 +649,31 @@ int mi_coulomb_quadrupole(const void* positions, const void* charges, const void
                           double* dipole_grads, double* quadrupole_grads, double* virial_partial, void* scratch, size_t scratch_bytes,
                           void* stream);
 
+/* Scaled bonded pairs of point multipoles (csrc/pair_scale.hip; driver: nvalchemiops/interactions/electrostatics/pair_scale.py).  Every
+ * stored entry e = (i, j, S) of a FULL list carries a scale pair_scales[e] (float64, laid out like idx_j: [n_atoms][max_neighbors] or
+ * [nnz]; symmetric, s_ij = s_ji, which is not checked).  Returned is what has to be ADDED to an unscaled total so that every listed pair
+ * carries its scale:
+ *     E_i = 1/2 sum_{row i} (s_e - 1) U_ij,   U_ij = L_i L_j (1 / r)
+ * the complete bare pair energy of charges, dipoles and quadrupoles: the charge-charge term B0 q_i q_j plus the pair expressions of
+ * mi_coulomb_dipole and mi_coulomb_quadrupole (B0 = 1 / r, B1 = 1 / r^3, B_{n+1} = (2n + 1) B_n / r^2), with their gradients.  s_e = 0 is an
+ * exclusion; an entry with s_e = 1 is skipped before any arithmetic and contributes exactly 0.  dipoles and quadrupoles may be NULL (none).
+ * One group of 8 lanes per row (8 rows per wave64), butterfly sums inside the group, no atomics: bit-reproducible.
+ * Arguments, weights (an entry weighs (g_i + g_j) / 2 . (s_e - 1)), flags (MI_QD_*), outputs, virial layout, list formats, padding (the scale
+ * of a padding slot is not looked at), the r <= 1e-8 skip and the arithmetic model are those of mi_coulomb_quadrupole.  minimum_image != 0
+ * (needs a cell, excludes unit_shifts): the difference r_j - r_i of every entry is reduced to its minimum image in fp64 (rint of the
+ * fractional components) and rounded once to the positions dtype; the virial then uses the reduced vector.  An unknown flag bit,
+ * minimum_image without a cell and unit_shifts together with minimum_image are argument errors; the virial needs unit_shifts or
+ * minimum_image.
+ * scratch: mi_pair_scale_scratch_bytes(n_atoms, dtype) bytes (records + per-row virials), contents undefined.  virial_partial is
+ * [n_systems][mi_pair_scale_blocks()][9]. */
+size_t mi_pair_scale_scratch_bytes(int n_atoms, int dtype);
+int mi_pair_scale_blocks(void);
+int mi_pair_scale(const void* positions, const void* charges, const void* dipoles /*or NULL*/, const void* quadrupoles /*or NULL*/,
+                  const void* cell /*[n_systems,3,3] or NULL*/, const int32_t* batch_idx, const double* weights, const double* pair_scales,
+                  int n_atoms, int n_systems, int dtype, const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr,
+                  int max_neighbors, int mask_value, int minimum_image, int flags, double* energies, void* forces, double* charge_grads,
+                  double* dipole_grads, double* quadrupole_grads, double* virial_partial, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Charge equilibration (csrc/qeq.hip; driver: nvalchemiops/interactions/electrostatics/qeq.py): the real-space Hessian of the Gaussian-charge
  * electrostatic energy as a stored sparse operator over the caller's FULL list, its product, and the vector kernels of a batched projected
  * conjugate-gradient solve of  min_q sum chi_i q_i + 1/2 sum J_i q_i^2 + E_el(q),  sum_{i in s} q_i = Q_s.  All arithmetic is fp64; only the

@@ -34,6 +34,7 @@ SOURCES = {
     "gaussian.hip": [],  # Gaussian-smeared charge correction (mi_gaussian_charges): fp64 pair math with libm erfc
     "dipole.hip": [],  # point-dipole Ewald sum (mi_ewald_dipole_*): fp64 pair math with libm erfc / exp, fp64 sincos phases
     "quadrupole.hip": [],  # point-quadrupole Ewald sum (mi_ewald_quadrupole_*): the arithmetic model of dipole.hip, B_n continued to B5
+    "pair_scale.hip": [],  # scaled bonded pairs of point multipoles (mi_pair_scale): 8 lanes per row, the arithmetic model of quadrupole.hip
     "qeq.hip": [],  # charge equilibration (mi_qeq_*): stored pair operator, its product and the CG vector kernels, all fp64
     "induced.hip": [],  # induced point dipoles (mi_induced_*): stored 3 x 3 pair operator, its product and the PCG vector kernels, all fp64
     "d4.hip": [],  # DFT-D4 two-body dispersion (mi_d4): fp32 pair math with IEEE divide / sqrt and libm erff / expf, fp64 sums

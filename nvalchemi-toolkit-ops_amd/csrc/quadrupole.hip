@@ -46,15 +46,12 @@
 namespace {
 
 #include "pair_row.h"
+#include "qd_record.h"  // QdRec, qd_matvec, qd_pack_kernel (shared with pair_scale.hip)
 
 #define QD_VIR_WORDS 9
 #define QD_SF_WORDS 10  // {Re, Im} of S_q, M_x, M_y, M_z, T
 #define QD_V_WORDS 6    // {Re, Im} of V_x, V_y, V_z
 #define QD_SQRT_PI 1.7724538509055159
-
-template <class T> struct QdRec {  // 64 / 128 bytes: one line
-  T x, y, z, q, mx, my, mz, xx, xy, xz, yy, yz, zz, pad[3];
-};
 
 // the six unique words of 1/2 (Q + Q^T) of atom i, in fp64: {xx, xy, xz, yy, yz, zz}
 template <class T> __device__ __forceinline__ void qd_sym(const T* __restrict__ quad, size_t i, double s[6]) {
@@ -62,29 +59,6 @@ template <class T> __device__ __forceinline__ void qd_sym(const T* __restrict__ 
   s[0] = (double)m[0]; s[3] = (double)m[4]; s[5] = (double)m[8];
   s[1] = 0.5 * ((double)m[1] + (double)m[3]); s[2] = 0.5 * ((double)m[2] + (double)m[6]); s[4] = 0.5 * ((double)m[5] + (double)m[7]);
 }
-// o = Q v for the six words of a symmetric Q
-__device__ __forceinline__ void qd_matvec(const double s[6], double vx, double vy, double vz, double& ox, double& oy, double& oz) {
-  ox = s[0] * vx + s[1] * vy + s[2] * vz;
-  oy = s[1] * vx + s[3] * vy + s[4] * vz;
-  oz = s[2] * vx + s[4] * vy + s[5] * vz;
-}
-
-template <class T>
-__global__ void qd_pack_kernel(const T* __restrict__ pos, const T* __restrict__ q, const T* __restrict__ mu, const T* __restrict__ quad, int N,
-                               QdRec<T>* __restrict__ rec) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  const size_t n = (size_t)i;
-  const T* m = quad + 9 * n;
-  QdRec<T> r;
-  r.x = pos[3 * n]; r.y = pos[3 * n + 1]; r.z = pos[3 * n + 2]; r.q = q[i];
-  r.mx = mu[3 * n]; r.my = mu[3 * n + 1]; r.mz = mu[3 * n + 2];
-  r.xx = m[0]; r.yy = m[4]; r.zz = m[8];
-  r.xy = T(0.5) * (m[1] + m[3]); r.xz = T(0.5) * (m[2] + m[6]); r.yz = T(0.5) * (m[5] + m[7]);
-  r.pad[0] = r.pad[1] = r.pad[2] = T(0);
-  rec[i] = r;
-}
-
 __device__ __forceinline__ double qd_volume(const double* cm) {
   return fabs(cm[0] * (cm[4] * cm[8] - cm[5] * cm[7]) - cm[1] * (cm[3] * cm[8] - cm[5] * cm[6]) + cm[2] * (cm[3] * cm[7] - cm[4] * cm[6]));
 }

@@ -188,7 +188,10 @@ def lib() -> ctypes.CDLL:
         L.mi_coulomb_dipole.argtypes = [vp] * 6 + [i, i, i, vp, vp, vp, i, i, i] + [vp] * 6 + [sz, vp]
         L.mi_coulomb_quadrupole.restype = i
         L.mi_coulomb_quadrupole.argtypes = [vp] * 7 + [i, i, i, vp, vp, vp, i, i, i] + [vp] * 7 + [sz, vp]
-        for name in ("mi_coulomb_dipole", "mi_coulomb_quadrupole"):
+        # scaled bonded pairs of point multipoles (nvalchemiops/interactions/electrostatics/pair_scale.py)
+        L.mi_pair_scale.restype = i
+        L.mi_pair_scale.argtypes = [vp] * 8 + [i, i, i, vp, vp, vp, i, i, i, i] + [vp] * 7 + [sz, vp]
+        for name in ("mi_coulomb_dipole", "mi_coulomb_quadrupole", "mi_pair_scale"):
             getattr(L, name + "_scratch_bytes").restype = sz
             getattr(L, name + "_scratch_bytes").argtypes = [i, i]
             getattr(L, name + "_blocks").restype = i

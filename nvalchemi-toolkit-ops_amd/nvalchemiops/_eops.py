@@ -1585,7 +1585,7 @@ gaussian_charge_correction_op = _op("_gaussian_charge_correction", _gaussian_fwd
 
 
 # =====================================================================================================================================
-# point multipoles: nine operator halves, one forward / backward op pair each, built from one table
+# point multipoles: nine operator halves and the bonded-pair scaling, one forward / backward op pair each, built from one table
 # =====================================================================================================================================
 # Outputs are always those of the public function (energies, forces, charge_gradients, dipole_gradients, the row's extra output, virial); the
 # ones not asked for are empty [0] tensors.  The energies are differentiable w.r.t. the row's first inputs: the backward op runs the forward
@@ -1601,7 +1601,7 @@ _TH_NO_GRAD = ("{op}: gradients w.r.t. cell are not provided by the Thole dampin
 _CL_NO_GRAD = ("{op}: gradients w.r.t. cell are not provided by the bare multipole pair sums (out of scope); use compute_virial for the strain "
                "derivative.")
 _PER_ATOM = {"positions": (3,), "charges": (), "dipoles": (3,), "quadrupoles": (3, 3), "polarizability": ()}  # shapes after [n]
-_SCALARS = {"SymInt": int, "float": float}  # schema type of a plain scalar -> the conversion `ctx.extra` and the launch functions get
+_SCALARS = {"SymInt": int, "float": float, "bool": bool}  # schema type of a plain scalar -> the conversion `ctx.extra` and the launch functions get
 _SYSTEMS = {  # the fake's number of systems, from (cell, batch_idx)
     "batch": lambda cell, batch_idx: cell.reshape(-1, 3, 3).shape[0] if batch_idx is not None else 1,
     "optional cell": lambda cell, batch_idx: cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1,
@@ -1634,6 +1634,8 @@ _MULTIPOLE_OPS = {
                                   ("cell",), _CL_NO_GRAD),
     "coulomb_quadrupole_correction": ("cluster", "_quadrupole_forward", "_quadrupole_adjoint", _QD, f"Tensor? cell, {_LISTS}", _QG,
                                       "optional cell", ("cell",), _CL_NO_GRAD),
+    "pair_scale_correction": ("pair_scale", "_forward", "_adjoint", _QD, f"Tensor pair_scales, Tensor? cell, {_LISTS}, bool minimum_image", _QG,
+                              "optional cell", ("cell",), _CL_NO_GRAD),
 }
 
 
@@ -1714,6 +1716,7 @@ ewald_quadrupole_reciprocal_space_op, ewald_quadrupole_recip_bwd_op = _MP["ewald
 pme_quadrupole_reciprocal_space_op, pme_quadrupole_recip_bwd_op = _MP["pme_quadrupole_reciprocal_space"]
 coulomb_dipole_correction_op, coulomb_dipole_bwd_op = _MP["coulomb_dipole_correction"]
 coulomb_quadrupole_correction_op, coulomb_quadrupole_bwd_op = _MP["coulomb_quadrupole_correction"]
+pair_scale_correction_op, pair_scale_bwd_op = _MP["pair_scale_correction"]
 
 
 # =====================================================================================================================================
@@ -1793,7 +1796,7 @@ rotate_multipoles_op.register_fake(_rotate_fwd_fake)
 rotate_multipoles_op.register_autograd(_rotate_backward, setup_context=_rotate_setup)
 
 
-__all__ = ["rotate_multipoles_op", "rotate_multipoles_bwd_op", "coulomb_dipole_correction_op", "coulomb_dipole_bwd_op", "coulomb_quadrupole_correction_op", "coulomb_quadrupole_bwd_op",
+__all__ = ["pair_scale_correction_op", "pair_scale_bwd_op", "rotate_multipoles_op", "rotate_multipoles_bwd_op", "coulomb_dipole_correction_op", "coulomb_dipole_bwd_op", "coulomb_quadrupole_correction_op", "coulomb_quadrupole_bwd_op",
            "pme_quadrupole_reciprocal_space_op", "pme_quadrupole_recip_bwd_op",
            "ewald_quadrupole_real_space_op", "ewald_quadrupole_reciprocal_space_op", "ewald_quadrupole_real_bwd_op",
            "ewald_quadrupole_recip_bwd_op", "thole_dipole_correction_op", "thole_dipole_bwd_op", "pme_dipole_reciprocal_space_op", "pme_dipole_recip_bwd_op", "ewald_dipole_real_space_op", "ewald_dipole_reciprocal_space_op", "ewald_dipole_real_bwd_op", "ewald_dipole_recip_bwd_op",

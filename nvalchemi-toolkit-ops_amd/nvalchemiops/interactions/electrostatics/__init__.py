@@ -13,6 +13,7 @@ from nvalchemiops.interactions.electrostatics.induced import (InducedDipoleError
 from nvalchemiops.interactions.electrostatics.thole import thole_dipole_correction
 from nvalchemiops.interactions.electrostatics.cluster import (cluster_induced_dipoles, coulomb_dipole_correction,
                                                               coulomb_quadrupole_correction)
+from nvalchemiops.interactions.electrostatics.pair_scale import BondedPairScales, bonded_pair_scales, pair_scale_correction
 from nvalchemiops.interactions.electrostatics.frames import (FRAME_BISECTOR, FRAME_NONE, FRAME_THREE_FOLD, FRAME_Z_BISECT, FRAME_Z_ONLY,
                                                              FRAME_Z_THEN_X, LocalFrames, multipole_frame_forces, rotate_multipoles)
 from nvalchemiops.interactions.electrostatics.k_vectors import generate_k_vectors_ewald_summation, generate_k_vectors_pme
@@ -37,4 +38,5 @@ __all__ = [
     "coulomb_dipole_correction", "coulomb_quadrupole_correction", "cluster_induced_dipoles",
     "LocalFrames", "rotate_multipoles", "multipole_frame_forces", "FRAME_NONE", "FRAME_Z_ONLY", "FRAME_Z_THEN_X", "FRAME_BISECTOR",
     "FRAME_Z_BISECT", "FRAME_THREE_FOLD",
+    "pair_scale_correction", "bonded_pair_scales", "BondedPairScales",
 ]
