@@ -1,5 +1,6 @@
 """The fixtures of the layout sweeps of `dftd4`, `dftd4_atm`, `gaussian_charge_correction`, `charge_equilibration`, the two point-dipole
-operators, `ewald_quadrupole_correction`, `thole_dipole_correction` and the induced-dipole solves (tests/test_arg_layouts_gpu.py), in one place and free of any device, so that the CPU suite can check on exactly these inputs the condition
+operators, `ewald_quadrupole_correction`, `thole_dipole_correction`, the induced-dipole solves, `pair_scale_correction`, the local-frame functions and
+`cluster_induced_dipoles` (tests/test_arg_layouts_gpu.py), in one place and free of any device, so that the CPU suite can check on exactly these inputs the condition
 that makes such a sweep worth running (tests/test_layout_sensitivity_cpu.py): a tensor argument that the entry point misreads by one row
 must move the result far beyond the bar the sweep applies.  Every reference is computed once and never modified.
 
@@ -14,6 +15,9 @@ must move the result far beyond the bar the sweep applies.  Every reference is c
     thole(batch)                `dipole(batch)` plus polarisabilities in [2, 8] (two non-polarisable atoms per system), width 0.39
     induced(batch)              an `induced_cases` lattice (l64 / l27 + l64) in float32 numbers with its full list, k set, an external field and
                                 a warm start; polarisabilities for the undamped and for the damped solve
+    pair_scale(batch)           `quadrupole(batch)` with its brute-force list and one scale per entry by distance class (0, 0.375, 1, 0.75)
+    frames(batch)               a local-frame topology of every kind over 130 / 70 + 60 atoms, wrapped into the boxes of `system`
+    cluster_induced()           the three clusters of tests/cluster_multipole_reference.py in float32 numbers, a field and a warm start
 
 Why the D4 fixture is not the 12 Bohr box of the other sweeps: there the coordination numbers reach 18 while the `cn_ref` of
 `d4_test_tables` lie in [0, 1]; every Gaussian weight saturates on the reference nearest to 1, and rolling `ngw` by one row moves the
@@ -440,3 +444,170 @@ def induced_bound(d, nsys, tol=IND_TOL):
         m = torch.nonzero(sys_of == s).flatten()
         out.append(10.0 * tol * float(d["b"][m].norm()) / float(torch.linalg.eigvalsh(d["H"][m][:, m]).min()) + 1e-14)
     return out
+
+
+# ---- pair_scale_correction -----------------------------------------------------------------------------------------------------------------
+
+PS_EDGES, PS_SCALES = (3.3, 4.5, 5.85), (0.0, 0.375, 1.0, 0.75)  # float32 numbers, as every value of these fixtures; the edges lie between neighbour shells of the lattice (3.0 | 3.7, 4.2 | 4.7, 5.6 | 6.0)
+PS_IMAGE_MARGIN = 0.45                                        # largest |fractional component| of a pair kept for the `minimum_image` calls
+
+
+def pair_vectors(pos, cells, batch_idx, i, j, S):
+    """[E, 3] float64 torch: (r_j - r_i) + S . cell, formed so that the mirror entry (j, i, -S) gives exactly the negative; and the same
+    vectors in fractional coordinates."""
+    pos, cells = pos.to(F64), cells.to(F64).reshape(-1, 3, 3)
+    c = cells[torch.zeros_like(i) if batch_idx is None else batch_idx.long()[i]]
+    d = (pos[j] - pos[i]) + torch.einsum("ea,eab->eb", S.to(F64), c)
+    return d, torch.einsum("ea,eab->eb", d, torch.linalg.inv(c))
+
+
+def distance_class_scales(pos, cells, batch_idx, i, j, S):
+    """One scale per stored entry from its distance class (`PS_EDGES`, `PS_SCALES`): symmetric by construction, the third class is exactly 1."""
+    r = pair_vectors(pos, cells, batch_idx, i, j, S)[0].norm(dim=1)
+    return torch.tensor(PS_SCALES, dtype=F64, device=r.device)[torch.bucketize(r, torch.tensor(PS_EDGES, dtype=F64, device=r.device))]
+
+
+def minimum_image_entries(pos, cells, batch_idx, i, j, S):
+    """Mask of the entries whose stored shift already is the minimum image, with every fractional component at most `PS_IMAGE_MARGIN`:
+    an entry and its mirror are kept or dropped together."""
+    return (pair_vectors(pos, cells, batch_idx, i, j, S)[1].abs() <= PS_IMAGE_MARGIN).all(dim=1)
+
+
+@functools.lru_cache(maxsize=None)
+def pair_scale(batch=False):
+    """`quadrupole(batch)` with the full list of cutoff `GC_RC` (brute-force entries `ent`) and one scale per entry by distance class."""
+    c = dict(quadrupole(batch))
+    c["ent"] = _entries(c["pos"], c["cell"], c["batch_idx"], GC_RC)
+    bi = None if c["batch_idx"] is None else torch.as_tensor(c["batch_idx"])
+    c["scales"] = distance_class_scales(torch.as_tensor(c["pos"]), torch.as_tensor(c["cell"]), bi, *c["ent"]).numpy()
+    return c
+
+
+def pair_scale_reference(batch=False, dtype=F64, **replace):
+    """The restatement of `pair_scale_correction` (tests/pair_scale_reference.py) on the fixture with explicit shifts."""
+    from tests import pair_scale_reference as PSR
+
+    c = {**pair_scale(batch), **replace}
+    t = lambda a: torch.as_tensor(np.asarray(a, np.float64))  # noqa: E731
+    bi = None if c["batch_idx"] is None else torch.as_tensor(c["batch_idx"])
+    return PSR.evaluate(t(c["pos"]), t(c["q"]), t(c["mu"]), t(c["qd"]), t(c["scales"]), c["ent"], cell=t(c["cell"]), batch_idx=bi, distance_dtype=dtype)
+
+
+# ---- LocalFrames, rotate_multipoles, multipole_frame_forces ----------------------------------------------------------------------------------
+
+FR_NAMES = ("dipoles", "quadrupoles", "positions_grad", "local_dipole_grads", "local_quadrupole_grads", "virial")
+FR_MOLECULES = ("none", "z_only", "z_only_y", "water", "ammonia", "z_bisect", "chiral", "mirror")
+
+
+def frame_conditions(pos, atoms, kinds, cell=None, batch_idx=None):
+    """What the bars of tests/test_local_frames_gpu.py assume of a geometry, measured: dict(bond=(min, max) length of a frame vector,
+    angle=(min, max) in degrees between two frame vectors of an atom, z_only=smallest | |e_z . x| - 0.866 | of a Z_ONLY atom, chiral=smallest
+    |d_y . (d_z x d_x)| / (|d_y| |d_z| |d_x|) of a Z_THEN_X atom with a y atom, image=largest |fractional component| of a frame vector (with a
+    cell: the distance of the minimum-image rounding from a flip is 0.5 minus this)).  float64 torch on the CPU."""
+    from tests import local_frames_reference as LR
+
+    pos, atoms, kinds = pos.to(F64), atoms.long(), kinds.long()
+    cells = None if cell is None else cell.to(F64).reshape(-1, 3, 3)
+    out = dict(bond=[np.inf, 0.0], angle=[180.0, 0.0], z_only=np.inf, chiral=np.inf, image=0.0)
+    idx = torch.arange(pos.shape[0])
+    vec = {}
+    for slot in range(3):
+        rows = idx[atoms[:, slot] >= 0]
+        if rows.numel() == 0:
+            continue
+        d = LR.frame_vectors(pos, atoms, rows, slot, cells, batch_idx)
+        vec[slot] = (rows, d)
+        length = d.norm(dim=1)
+        out["bond"] = [min(out["bond"][0], float(length.min())), max(out["bond"][1], float(length.max()))]
+        if cells is not None:
+            c = cells[batch_idx.long()[rows]] if batch_idx is not None else cells[:1].expand(rows.shape[0], 3, 3)
+            out["image"] = max(out["image"], float(torch.einsum("na,nab->nb", d, torch.linalg.inv(c)).abs().max()))
+    full = {s: torch.full((pos.shape[0], 3), float("nan"), dtype=F64).index_copy(0, r, d) for s, (r, d) in vec.items()}
+    for a, b in ((0, 1), (0, 2), (1, 2)):
+        if a in full and b in full:
+            cos = (full[a] * full[b]).sum(1) / (full[a].norm(dim=1) * full[b].norm(dim=1))
+            ang = torch.rad2deg(torch.acos(cos[~torch.isnan(cos)].clamp(-1.0, 1.0)))
+            if ang.numel():
+                out["angle"] = [min(out["angle"][0], float(ang.min())), max(out["angle"][1], float(ang.max()))]
+    z_only = kinds == LR.Z_ONLY
+    if bool(z_only.any()):
+        ez = full[0][z_only]
+        out["z_only"] = float(((ez[:, 0] / ez.norm(dim=1)).abs() - LR.Z_ONLY_SWITCH).abs().min())
+    chiral = (kinds == LR.Z_THEN_X) & (atoms[:, 2] >= 0)
+    if bool(chiral.any()):
+        dz, dx, dy = (full[s][chiral] for s in range(3))
+        out["chiral"] = float(((dy * torch.linalg.cross(dz, dx)).sum(1).abs() / (dy.norm(dim=1) * dz.norm(dim=1) * dx.norm(dim=1))).min())
+    return out
+
+
+def _frame_box(box):
+    return torch.tensor([[box, 0.0, 0.0], [0.25 * box, 0.9 * box, 0.0], [0.1 * box, -0.2 * box, 1.1 * box]], dtype=F64).float().double()
+
+
+@functools.lru_cache(maxsize=None)
+def frames(batch=False):
+    """A topology over the 130 / 70 + 60 atoms of the layout sweeps that uses every kind: the eight molecules of
+    tests/local_frames_reference.py (25 atoms: every kind, Z_ONLY on both sides of its switch, Z_THEN_X with and without a y atom, both
+    chiralities) and randomly rotated waters, wrapped into the triclinic boxes of `system` (12 / 12 and 11; molecules straddle faces);
+    the batch's second system is a z-bisect centre, an ammonia and 17 waters.  Local multipoles and the caller gradients `w_mu`, `w_q` are
+    drawn once.  Every value is a float32 number; tests/test_layout_sensitivity_cpu.py asserts the geometry conditions on these numbers."""
+    from tests import local_frames_reference as LR
+
+    mols = [LR.molecule(m) for m in FR_MOLECULES]
+    if batch:
+        parts = [LR.join(mols + [LR.waters(NA - 25, seed=32)[:3]])[:3], LR.join([LR.molecule("z_bisect"), LR.molecule("ammonia"), LR.waters(NB - 9, seed=33)[:3]])[:3]]
+        cells = torch.stack([_frame_box(12.0), _frame_box(11.0)])
+    else:
+        parts = [LR.join(mols + [LR.waters(N - 25, seed=31)[:3]])[:3]]
+        cells = _frame_box(12.0)[None]
+    wrapped = []
+    for (p, a, k), cell in zip(parts, cells):
+        p = p + torch.tensor([5.7, 0.3, 6.1], dtype=F64)  # the molecules at the origin land on a face of the box
+        frac = p @ torch.linalg.inv(cell)
+        wrapped.append(((frac - torch.floor(frac)) @ cell, a, k))
+    pos, atoms, kinds, sys_of = LR.join(wrapped)
+    n = pos.shape[0]
+    assert n == (NA + NB if batch else N) and sorted(set(kinds.tolist())) == list(range(6))
+    mu, quad = LR.local_multipoles(n, 41 + batch)
+    gen = torch.Generator().manual_seed(43 + batch)
+    f32 = lambda t: t.float().double().numpy()  # noqa: E731
+    return dict(n=n, pos=f32(pos), atoms=atoms.numpy(), kinds=kinds.numpy(), cell=f32(cells), batch_idx=sys_of.to(torch.int32).numpy() if batch else None,
+                mu=f32(mu), quad=f32(quad), w_mu=f32(torch.randn((n, 3), dtype=F64, generator=gen)), w_q=f32(torch.randn((n, 3, 3), dtype=F64, generator=gen)))
+
+
+def frames_reference(batch=False, **replace):
+    """dict of float64 numpy arrays (`FR_NAMES`) of the restatement tests/local_frames_reference.py on the fixture, arguments replaced."""
+    from tests import local_frames_reference as LR
+
+    c = {**frames(batch), **replace}
+    t = lambda a: torch.as_tensor(np.asarray(a, np.float64))  # noqa: E731
+    bi = None if c["batch_idx"] is None else torch.as_tensor(c["batch_idx"])
+    out = LR.evaluate(t(c["pos"]), t(c["mu"]), t(c["quad"]), torch.as_tensor(c["atoms"]), torch.as_tensor(c["kinds"]), t(c["w_mu"]), t(c["w_q"]),
+                      cell=t(c["cell"]), batch_idx=bi)
+    return {k: out[k].detach().numpy() for k in FR_NAMES}
+
+
+# ---- cluster_induced_dipoles ---------------------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def cluster_induced():
+    """The batch of three clusters (70, 2 and 1 atoms) of tests/cluster_multipole_reference.py rounded to float32 numbers, with an external
+    field and a warm start; `polar` for the undamped solve, four times those (`polar_thole`) with `thole=0.39`, as in
+    tests/test_cluster_multipole_gpu.py."""
+    from tests import cluster_multipole_reference as CR
+
+    p = dict(CR.problem("batch"))
+    for k in ("pos", "q", "polar", "field"):
+        p[k] = _f32(p[k])
+    p["polar_thole"] = _f32(4.0 * p["polar"])
+    p["start"] = _f32(0.05 * np.random.default_rng(53).normal(size=(p["n"], 3)))
+    return p
+
+
+def cluster_induced_dense(thole=None, device="cpu"):
+    """dict(H, b, polar, bi) of the dense float64 restatement of `cluster_induced()`."""
+    from tests import cluster_multipole_reference as CR
+
+    p = cluster_induced()
+    H, b, _, polar = CR.dense_problem(dict(p, polar=p["polar"] if thole is None else p["polar_thole"]), thole, device)
+    return dict(H=H, b=b, polar=polar, bi=torch.as_tensor(p["batch_idx"], device=device))

@@ -1,6 +1,7 @@
 """Seeded sweep cases, boundary ladders and one-scalar variants of the five newer dispersion operators (`dftd3_atm`, `dftd3_zero`,
 `dftd3_zero_atm`, `dftd4`, `dftd4_atm`) and the inputs of the sweeps of `gaussian_charge_correction`, charge equilibration, the two
-point-dipole operators, `ewald_quadrupole_correction`, `thole_dipole_correction`, `induced_dipoles` and `pme_quadrupole_correction` (last four sections),
+point-dipole operators, `ewald_quadrupole_correction`, `thole_dipole_correction`, `induced_dipoles`, `pme_quadrupole_correction` and the cluster, pair-scale and
+local-frame operators (last five sections),
 built on the float64 restatements tests/atm_reference.py, tests/d3_zero_reference.py,
 tests/d4_reference.py and tests/d4_atm_reference.py.  Importable without a GPU and without the native library (the two tile sizes are read
 lazily, by the ladder builders only).  The CPU suite asserts every condition a case must meet (tests/test_sweep_cases_cpu.py); the GPU
@@ -1265,3 +1266,269 @@ def pmeq_batch_seed():
         if len(c["sizes"]) == 3 and min(c["sizes"]) > 0 and not c["zero"] and not c["no_dipoles"] and c["perm"] is None:
             return s
     raise AssertionError("no seed with three systems with atoms")
+
+
+# ---- cluster multipoles, scaled pairs, local frames: coulomb_dipole_correction, coulomb_quadrupole_correction, pair_scale_correction,
+#      rotate_multipoles / multipole_frame_forces -------------------------------------------------------------------------------------------------
+# Inputs only; the restatements (tests/cluster_multipole_reference.py, tests/pair_scale_reference.py, tests/local_frames_reference.py) are
+# evaluated by the GPU module on the entries actually stored.  A PAIR seed: 1 - 4 systems with sizes from {1, 2, 9, 60, 150} (and one system
+# of 0 atoms on `EMPTY_SYSTEM_SEEDS`), `spaced_positions` at `CLUSTER_D_MIN` = the 1.3 of tests/cluster_multipole_reference.py so that family's
+# bars apply, as clusters (all pairs of every system) or in triclinic cells (`CLUSTER_PERIODIC_SEEDS`: every image within a cutoff of 4 - 5,
+# the small systems in a cell of 4.5 with their own images).  `padded_matrix` stores a list as a matrix with all three kinds of padding and,
+# on every other row, one padding slot BETWEEN live entries.  The designations are the quadrupole section's: `ZERO_MULTIPOLE_SEEDS` (zero
+# dipoles / zero quadrupoles / for `pair_scale` unit scales: every output exactly 0), `INTERLEAVED_SEEDS`, `EMPTY_SYSTEM_SEEDS`,
+# `SINGLE_FLAG_SEEDS`.  `pair_scale` only: scales from the symmetric hash of tests/pair_scale_cases.py (0, 0.4, 0.8, 1), float32 scales on
+# `PS_F32_SCALE_SEEDS`, `minimum_image` on `PS_MIN_IMAGE_SEEDS` (periodic seeds whose list is cut to the pairs whose stored shift is the
+# minimum image with every fractional component at most 0.45, and given without shifts: a topology list), `dipoles=None` /
+# `quadrupoles=None` on one seed each, and on `PS_COINCIDENT_SEED` two atoms at the same point listed both ways (r <= 1e-8: skipped).
+
+CLUSTER_OPS = ("coulomb_dipole", "coulomb_quadrupole", "pair_scale")
+BASE.update(coulomb_dipole=9100, coulomb_quadrupole=9200, pair_scale=9300, frames=9400)
+CLUSTER_D_MIN = 1.3
+CLUSTER_SIZES = (1, 2, 9, 60, 150)
+CLUSTER_PERIODIC_SEEDS = (0, 1, 4, 5, 6, 8, 11)
+CLUSTER_FLAGS = {"coulomb_dipole": DIPOLE_FLAGS, "coulomb_quadrupole": QUADRUPOLE_FLAGS, "pair_scale": QUADRUPOLE_FLAGS}
+CLUSTER_NAMES = {"coulomb_dipole": DIPOLE_NAMES, "coulomb_quadrupole": QUADRUPOLE_NAMES, "pair_scale": QUADRUPOLE_NAMES}
+PS_F32_SCALE_SEEDS = (3, 6)
+PS_MIN_IMAGE_SEEDS = (1, 8)
+PS_NO_DIPOLE_SEED, PS_NO_QUADRUPOLE_SEED, PS_COINCIDENT_SEED = 2, 7, 9
+PS_IMAGE_MARGIN = 0.45
+PS_LADDER = (255, 256, 257, 1)
+
+
+def hash_scale(i, j):
+    """The symmetric hash of tests/pair_scale_cases.py on arrays: the classes 0, 0.4, 0.8 and 1."""
+    return np.array([0.0, 0.4, 0.8, 1.0, 0.4])[(i * j + i + j) % 5]
+
+
+def fractional_pair_vectors(c, entries=None):
+    """r_j - r_i + S . cell of every entry in fractional coordinates of its system's cell."""
+    i, j, S = c["entries"] if entries is None else entries
+    cells = c["cells"][c["batch_idx"][i]]
+    d = c["pos"][j] - c["pos"][i] + np.einsum("ea,eab->eb", S.astype(np.float64), cells)
+    return np.einsum("ea,eab->eb", d, np.linalg.inv(cells))
+
+
+def padded_matrix(entries, n, values=None):
+    """(neighbor_matrix [n, M], shifts [n, M, 3], values [n, M] with NaN on padding | None) of entries sorted by row, their order kept.  Rows are
+    seven columns wider than the longest; padding is the mask value n, with -1 in the last column and n + 7 in every other row of the one
+    before; on every other row that holds at least two entries the second entry onwards is moved one slot to the right, which leaves one
+    padding slot between live entries."""
+    i, j, S = entries
+    counts = np.bincount(i, minlength=n) if len(i) else np.zeros(n, np.int64)
+    m = int(counts.max() if n else 0) + 8
+    col = np.arange(len(i)) - (np.cumsum(counts) - counts)[i]
+    col = col + ((col >= 1) & (i % 2 == 1) & (counts[i] >= 2))
+    nm = np.full((n, m), n, np.int32)
+    sh = np.zeros((n, m, 3), np.int32)
+    nm[i, col], sh[i, col] = j, S
+    nm[:, -1] = -1
+    nm[::2, -2] = n + 7
+    val = None
+    if values is not None:
+        val = np.full((n, m), np.nan)
+        val[i, col] = values
+    return nm, sh, val
+
+
+@functools.lru_cache(maxsize=None)
+def _cluster_sweep(op, seed):
+    g = np.random.default_rng(BASE[op] + seed)
+    periodic = seed in CLUSTER_PERIODIC_SEEDS
+    while True:
+        sizes = [int(v) for v in g.choice(CLUSTER_SIZES, 3 if seed in EMPTY_SYSTEM_SEEDS else int(g.integers(2 if seed in INTERLEAVED_SEEDS else 1, 5)))]
+        if seed in EMPTY_SYSTEM_SEEDS:
+            sizes[1] = 0
+        if max(sizes) >= 9 and sum(sizes) <= 320:
+            break
+    sizes = tuple(sizes)
+    cutoff = float(g.uniform(4.0, 5.0))
+    pos, cells, images = [], [], []
+    for n in sizes:
+        box = _BOX.get(n, 4.5)
+        cell = charge_cell(box, True)
+        pos.append(spaced_positions(g, n, cell, CLUSTER_D_MIN))
+        cells.append(cell)
+        images.append(2 if box < cutoff else 1)
+    ntot = sum(sizes)
+    bi = np.concatenate([np.full(n, k, np.int32) for k, n in enumerate(sizes)])
+    zero = seed in ZERO_MULTIPOLE_SEEDS
+    names = CLUSTER_FLAGS[op]
+    if seed in SINGLE_FLAG_SEEDS:  # the periodic one of these seeds (0) asks for the virial alone; a cluster that would be asked for it gives the forces
+        alone = names[(SINGLE_FLAG_SEEDS.index(seed) - 1) % len(names)]
+        alone = names[0] if alone == "compute_virial" and not periodic else alone
+        flags = {k: k == alone for k in names}
+    else:
+        flags = {k: bool(g.integers(2)) for k in names}
+    c = dict(op=op, seed=seed, dtype="float64" if seed % 2 == 0 else "float32", sizes=sizes, periodic=periodic, pos=np.concatenate(pos),
+             cells=np.stack(cells) if periodic else None, batch_idx=bi, cutoff=cutoff if periodic else 1e9, images=tuple(images), q=g.normal(size=ntot) + 0.05,
+             mu=_dipoles(g, ntot, zero=zero and op == "coulomb_dipole"), qd=_quadrupoles(g, ntot, zero=zero and op == "coulomb_quadrupole"), zero=zero,
+             flags=flags, autograd=bool(g.integers(2)), weights=g.uniform(0.2, 1.8, ntot), perm=g.permutation(ntot) if seed in INTERLEAVED_SEEDS else None,
+             empty_system=1 if seed in EMPTY_SYSTEM_SEEDS else None, emptied_row=None, minimum_image=False, coincident=None, no_dipoles=False,
+             no_quadrupoles=False, scale_dtype="float64")
+    if not periodic:
+        c["flags"]["compute_virial"] = False  # a cluster has no virial
+    if op == "pair_scale" and seed == PS_COINCIDENT_SEED:
+        big = int(np.argmax(sizes))
+        a = int(np.sum(sizes[:big]))
+        c["pos"][a + 1] = c["pos"][a]
+        c["coincident"] = (a, a + 1)
+    _with_entries(c)
+    if op == "pair_scale":
+        i, j, S = c["entries"]
+        if c["coincident"] is not None:  # the brute-force list leaves r = 0 out: the coincident pair is listed both ways by hand
+            a, b = c["coincident"]
+            i, j, S = np.append(i, [a, b]), np.append(j, [b, a]), np.vstack([S, np.zeros((2, 3), S.dtype)])
+            order = np.lexsort((j, i))
+            c["entries"] = (i[order], j[order], S[order])
+        if seed in PS_MIN_IMAGE_SEEDS:
+            keep = (np.abs(fractional_pair_vectors(c)) <= PS_IMAGE_MARGIN).all(axis=1)
+            c["entries"] = tuple(e[keep] for e in c["entries"])
+            c["minimum_image"] = True
+        i, j, S = c["entries"]
+        c["scales"] = np.ones(len(i)) if zero else hash_scale(i.astype(np.int64), j.astype(np.int64))
+        c["scale_dtype"] = "float32" if seed in PS_F32_SCALE_SEEDS else "float64"
+        c["no_dipoles"], c["no_quadrupoles"] = seed == PS_NO_DIPOLE_SEED, seed == PS_NO_QUADRUPOLE_SEED
+    return c
+
+
+def cluster_interleaved(c):
+    """`interleaved(c)` with the quadrupoles in the new atom order and the scales in the new entry order too."""
+    perm = c["perm"]
+    inv = np.empty_like(perm)
+    inv[perm] = np.arange(len(perm))
+    i, j, S = c["entries"]
+    ni, nj = inv[i], inv[j]
+    order = np.argsort(ni, kind="stable")
+    out = dict(c, perm=None, entries=(ni[order], nj[order], S[order]))
+    for k in ("pos", "q", "mu", "qd", "batch_idx", "weights"):
+        out[k] = c[k][perm]
+    if "scales" in c:
+        out["scales"] = c["scales"][order]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def pair_scale_ladder():
+    """255, 256, 257 and 1 atoms per system in one batch under `minimum_image`, rows of 0 - 9 entries: the group-of-8 kernel gives a wave 8
+    rows, so system boundaries fall inside waves and inside blocks.  Atoms on a jittered grid of spacing 2 in cubic-ish triclinic cells of
+    16; row r of a system names its (r mod 10) nearest atoms under the minimum image and is named by them: a full list whose rows hold 0 - 9
+    entries before the mirror entries are added (the CPU suite asserts that empty rows and rows of 9 and more both occur)."""
+    g = np.random.default_rng(BASE["pair_scale"] + 100)
+    pos, cells, pairs, off = [], [], set(), 0
+    for n in PS_LADDER:
+        cell = charge_cell(16.0, True)
+        grid = np.stack(np.meshgrid(*[np.arange(7)] * 3, indexing="ij"), -1).reshape(-1, 3)[:n] * 2.0 + 1.0
+        frac = (grid + g.uniform(-0.3, 0.3, grid.shape)) / 16.0
+        pos.append(frac @ cell)
+        cells.append(cell)
+        d = frac[None, :, :] - frac[:, None, :]
+        dist = np.linalg.norm((d - np.rint(d)) @ cell, axis=-1) + np.eye(n) * 1e9
+        for r in range(n):  # row r names its r mod 10 nearest atoms (minimum image), and is named by them
+            for b in np.argsort(dist[r], kind="stable")[:min(r % 10, n - 1)]:
+                pairs.add((off + r, off + int(b))); pairs.add((off + int(b), off + r))
+        off += n
+    keys = sorted(pairs)
+    i, j = np.array([k[0] for k in keys], np.int64), np.array([k[1] for k in keys], np.int64)
+    ntot = off
+    c = dict(op="pair_scale", seed=None, dtype="float64", sizes=PS_LADDER, periodic=True, pos=np.concatenate(pos), cells=np.stack(cells),
+             batch_idx=np.concatenate([np.full(n, k, np.int32) for k, n in enumerate(PS_LADDER)]), q=g.normal(size=ntot) + 0.05, mu=_dipoles(g, ntot),
+             qd=_quadrupoles(g, ntot), entries=(i, j, np.zeros((len(i), 3), np.int64)), scales=hash_scale(i, j), minimum_image=True,
+             weights=g.uniform(0.2, 1.8, ntot))
+    return c
+
+
+# Local frames.  A seed draws molecules of every kind (tests/local_frames_reference.py: the eight smallest molecules, so Z_THEN_X comes with
+# and without a y atom and in both chiralities), rotates each at random, places them on a grid of spacing 4 with NONE atoms scattered
+# between them up to the seed's total, and then PERMUTES THE ATOM ORDER at random: frame atoms lie above and below their owner and, from 257
+# atoms on, in another block of 256 threads.  Forms: a cluster, one triclinic cell with wrapped positions, a batch of two or three cells,
+# the batch interleaved (`FRAME_INTERLEAVED_SEEDS`) or with a system without atoms (`FRAME_EMPTY_SEEDS`).  One input None on
+# `FRAME_NO_DIPOLE_SEED` / `FRAME_NO_QUADRUPOLE_SEED`.  `FRAME_SEED_OFFSET` is the first of 0, 100, ... under which all twelve seeds meet
+# the conditions of the CPU suite: no case is dropped.  A molecule's rotation is drawn again while it leaves a Z_ONLY axis within 0.07 of its
+# switch at 0.866 (a uniform axis does so with probability 0.14, so no offset could clear fifty such atoms at once).
+FRAME_TOTALS = (1, 2, 63, 64, 65, 257, 600)
+FRAME_TOTAL_BY_SEED = (257, 65, 600, 1, 64, 63, 600, 2, 257, 65, 64, 600)
+FRAME_FORMS = ("cluster", "cell", "batch")
+FRAME_INTERLEAVED_SEEDS = (2, 8)
+FRAME_EMPTY_SEEDS = (5, 11)
+FRAME_NO_DIPOLE_SEED, FRAME_NO_QUADRUPOLE_SEED = 4, 9
+FRAME_MOLECULES = ("z_only", "z_only_y", "water", "ammonia", "z_bisect", "chiral", "mirror")
+FRAME_SEED_OFFSET = 0
+FRAME_SWITCH_MARGIN = 0.06
+
+
+@functools.lru_cache(maxsize=None)
+def _frame_sweep(seed):
+    from tests import local_frames_reference as LR
+
+    gen = torch.Generator().manual_seed(BASE["frames"] + FRAME_SEED_OFFSET + seed)
+    g = np.random.default_rng(BASE["frames"] + FRAME_SEED_OFFSET + seed)
+    total = FRAME_TOTAL_BY_SEED[seed]
+    form = "batch" if seed in FRAME_INTERLEAVED_SEEDS + FRAME_EMPTY_SEEDS else FRAME_FORMS[seed % 3]
+    if total < 9:
+        form = "cluster" if seed % 2 else "cell"
+    nsys = 1 if form != "batch" else 3
+    sizes = [total] if nsys == 1 else [total - 2 * (total // 3), total // 3, total // 3]
+    if seed in FRAME_EMPTY_SEEDS:
+        sizes = [sizes[0] + sizes[1], 0, sizes[2]]
+    parts, sys_of, cells = [], [], []
+    for s, n in enumerate(sizes):
+        side, used, m = 14.0, 0, 0
+        mols = []
+        while True:  # molecules of every kind in turn, starting at a seeded one, while they fit
+            p, a, k = LR.molecule(FRAME_MOLECULES[(m + seed + s) % len(FRAME_MOLECULES)])
+            if used + p.shape[0] > n:
+                break
+            centre = torch.tensor([m % 3, (m // 3) % 3, (m // 9) % 3], dtype=torch.float64) * 4.0 + torch.rand(3, dtype=torch.float64, generator=gen)
+            while True:  # a rotation is drawn again while it leaves a Z_ONLY axis within `FRAME_SWITCH_MARGIN` of the 0.866 switch (as `spaced_positions` rejects)
+                rot = (p - p.mean(0)) @ LR.random_rotation(gen).T
+                z = torch.nonzero(k == LR.Z_ONLY).reshape(-1)
+                ez = rot[a[z, 0].long()] - rot[z]
+                if z.numel() == 0 or float(((ez[:, 0] / ez.norm(dim=1)).abs() - LR.Z_ONLY_SWITCH).abs().min()) > FRAME_SWITCH_MARGIN + 0.01:
+                    break
+            mols.append((rot + centre + 27.0 * (m // 27), a, k))
+            used += p.shape[0]
+            m += 1
+            if m >= 150:
+                break
+        for _ in range(n - used):  # NONE atoms scattered between the molecules
+            mols.append((torch.rand((1, 3), dtype=torch.float64, generator=gen) * 12.0, torch.full((1, 3), -1, dtype=torch.int32),
+                         torch.zeros(1, dtype=torch.int32)))
+        parts += mols
+        sys_of += [s] * n
+        cells.append(torch.tensor(charge_cell(side + s, True)).float().double())
+    if parts:
+        pos, atoms, kinds, _ = LR.join(parts)
+    sys_of = torch.tensor(sys_of, dtype=torch.int64)
+    cells = torch.stack(cells)
+    if form != "cluster":  # wrapped positions: molecules straddle faces
+        frac = torch.einsum("na,nab->nb", pos, torch.linalg.inv(cells)[sys_of])
+        pos = torch.einsum("na,nab->nb", frac - torch.floor(frac), cells[sys_of])
+    pos = pos.float().double()  # float32 numbers, like the cells, the local multipoles and the weights below: wrapped coordinates reach 16, where
+    # one float32 rounding of a position is 5e-7 of a bond; with inputs that ARE float32 numbers the float32 calls see the float64 calls' geometry
+    n = pos.shape[0]
+    # the random atom order: within each system unless the seed interleaves the batch
+    if seed in FRAME_INTERLEAVED_SEEDS:
+        perm = torch.as_tensor(g.permutation(n))
+    else:
+        perm = torch.cat([torch.nonzero(sys_of == s).reshape(-1)[torch.as_tensor(g.permutation(k), dtype=torch.int64)] for s, k in enumerate(sizes)]) if n else torch.zeros(0, dtype=torch.int64)
+    inv = torch.empty_like(perm)
+    inv[perm] = torch.arange(n)
+    atoms = torch.where(atoms >= 0, inv[atoms.long().clamp(min=0)].to(torch.int32), atoms)[perm]
+    pos, kinds, sys_of = pos[perm], kinds[perm], sys_of[perm]
+    mu, quad = (t.float().double() for t in LR.local_multipoles(n, BASE["frames"] + 50 + seed))
+    return dict(seed=seed, dtype="float64" if seed % 2 == 0 else "float32", form=form, n=n, sizes=tuple(sizes), pos=pos, atoms=atoms.contiguous(), kinds=kinds,
+                cells=None if form == "cluster" else (cells if form == "batch" else cells[0]), batch_idx=sys_of.to(torch.int32) if form == "batch" else None,
+                mu=None if seed == FRAME_NO_DIPOLE_SEED else mu, quad=None if seed == FRAME_NO_QUADRUPOLE_SEED else quad,
+                w_mu=torch.randn((n, 3), dtype=torch.float64, generator=gen).float().double(),
+                w_q=torch.randn((n, 3, 3), dtype=torch.float64, generator=gen).float().double(), empty_system=1 if seed in FRAME_EMPTY_SEEDS else None)
+
+
+def cluster_case(kind, key=None):
+    if kind == "sweep":
+        return _cluster_sweep(*key)
+    if kind == "ps_ladder":
+        return pair_scale_ladder()
+    if kind == "frames":
+        return _frame_sweep(key)
+    raise KeyError(kind)

@@ -42,6 +42,12 @@ Which variant goes to which argument (no tensor argument of a listed entry point
     sigma, electronegativity, hardness, polarizability,
       initial_charges, total_charge [B]               x   x   x   -   -   -   -   x      (polarizability also as a Python number)
     meshes, k_squared                                 x   x   x   x   -   -   -   x*     (* not k_squared)
+    pair_scales [N,M] beside a matrix                 x   x   x   x   -   -   -   x      (float32 or float64 WHATEVER the positions dtype:
+    pair_scales [nnz] beside a list                   x   x   x   -   -   -   -   x       flt is the dtype the positions do not have)
+    frame_atoms [N,3] (through `LocalFrames`)         x   x   x   x   -   -   x   -
+    frame_kinds [N] (through `LocalFrames`)           x   x   x   -   -   -   x   -
+    local_dipoles, dipole_grads [N,3]                 x   x   x   x   -   -   -   x      (the caller's gradients of `multipole_frame_forces`
+    local_quadrupoles, quadrupole_grads [N,3,3]       x   x   x   x   x   -   -   x       are of any float dtype and layout)
 
 `flt` goes to every float argument but the one whose dtype IS the dtype of the call and of its outputs: positions, and where there are
 none `k_squared` (pme_green_structure_factor) and `raw_energies` (pme_energy_corrections_with_charge_grad).
@@ -83,7 +89,23 @@ Point quadrupoles on the mesh (fixture `pme_quadrupole`: the quadrupole fixture 
 batch, in float32 and in float64 alike): pme_quadrupole_reciprocal_space 26 (+ 4 forms with a [3, 3] cell, a 0-d alpha and a Python number) /
 33, pme_quadrupole_correction 36 (matrix) + 40 (CSR) (+ 2) / 43 + 45: 446 variants and 12 forms.  In float32 every variant gave the BITS of the
 canonical call (the spread adds in float64 and rounds once); in float64 they stayed within 0.0034 of the 1e-12 bar of two runs.  Gradient
-layouts of both entry points: bit-identical in float32, within that bar in float64.  DESIGN.md section 3.28."""
+layouts of both entry points: bit-identical in float32, within that bar in float64.  DESIGN.md section 3.28.
+
+Cluster multipoles, scaled pairs and local frames (fixtures `pair_scale`, `frames`, `cluster_induced` of tests/layout_cases.py; variants run,
+single system / batch, in float32 and in float64 alike): coulomb_dipole_correction 26 (matrix) + 30 (CSR) + 18 (`cell=None`: the first
+system as a cluster, a matrix without shifts whose rows hold padding between live entries) / 32 + 35 + 18, coulomb_quadrupole_correction
+32 + 36 + 24 / 38 + 41 + 24, pair_scale_correction 37 + 40 with shifts and 32 + 35 under `minimum_image` / 43 + 45 and 37 + 40 (+ three
+`None` forms per list against zero tensors), LocalFrames + rotate_multipoles + multipole_frame_forces 38 / 43 (+ `LocalFrames.to()`);
+cluster_induced_dipoles (float64, cluster batch, undamped and Thole) 31 + 35 each (+ a Python number against a constant tensor): 1 620
+variants, every one the BITS of the canonical call -- for the frames also `torch.equal` tables, for the solves dipoles and iteration counts.
+Gradient layouts: 14 ops (the two cluster corrections and pair_scale_correction in both list forms, rotate_multipoles with both outputs;
+single system and batch) x 4 grad-output layouts in each dtype, every gradient bit-identical to the contiguous backward.
+With the `.contiguous()` of `pair_scales` taken out of `pair_scale._inputs` and the one of `dipole_grads` out of
+`frames._adjoint_launch` (patched in a scratch run, not committed) all eight sweeps of `test_pair_scale_correction` and `test_local_frames`
+fail: `pair_scales` col and row (both list forms) and T (matrix) in float64, where `.to(float64)` is the tensor itself, and T alone in
+float32, where `.to()` copies a strided view into contiguous storage but keeps the strides of a dense transposed one; `dipole_grads` col,
+row and T in both dtypes (the torque forces move by about 10).  `off` and `flt` do not and cannot fail: an offset view is contiguous from
+its own pointer, and a dtype change copies.  DESIGN.md section 3.33."""
 import functools
 import re
 import types
@@ -1373,6 +1395,236 @@ def test_induced_dipoles_explicit_ewald_and_pme(batch, damped):
     _swept(f"{tag} pme {label}", lambda **a: call(**a)[:1], kw, dict(aplan, **lplan), _within_twice_the_bound(rows))
 
 
+# ---- cluster multipoles, scaled pairs, local frames ------------------------------------------------------------------------------------------
+
+def _cluster_lists(f):
+    """The first system of the fixture as a cluster: its rows of the stored matrix with every entry that carries a shift, or that lies in
+    another system, turned into padding -- padding BETWEEN live entries -- and no shifts."""
+    n1 = f.n if f.BI is None else int((f.BI == 0).sum())
+    nm = f.nm[:n1].clone()
+    nm[(f.sh[:n1] != 0).any(-1) | (nm >= n1)] = n1
+    return n1, nm.contiguous()
+
+
+@DTYPES
+@pytest.mark.parametrize("batch", [False, True])
+@_collecting
+def test_cluster_multipole_corrections(dtype, batch):
+    """`coulomb_dipole_correction` and `coulomb_quadrupole_correction`, every output: as periodic cut-off sums on the quadrupole fixture
+    (both list forms, a stride-0 cell on the batch's matrix form) and once more with `cell=None` on the first system as a cluster, a matrix
+    without shifts whose rows hold padding between live entries.  The canonical call against tests/cluster_multipole_reference.py on the
+    stored entries at the bars of tests/test_cluster_multipole_gpu.py, every variant against the BITS of the canonical call."""
+    from nvalchemiops.interactions.electrostatics import coulomb_dipole_correction, coulomb_quadrupole_correction
+    from tests import cluster_multipole_reference as CR
+    from tests import test_cluster_multipole_gpu as TCM
+
+    f = _mfx(dtype, batch)
+    tag = f"{dtype}{' batch' if batch else ''}"
+    ent = TDP.R.entries_from_matrix(f.nm, f.sh, f.n)
+    n1, nm1 = _cluster_lists(f)
+    ent1 = TDP.R.entries_from_matrix(nm1, torch.zeros(tuple(nm1.shape) + (3,), dtype=I32, device=DEV), n1)
+    assert 0 < ent1[0].shape[0] < ent[0].shape[0] and bool(((nm1 == n1)[:, :-1] & (nm1 != n1)[:, 1:]).any()), "padding between live entries"
+    for which, fn, evaluate, extra, eplan in (("dipole", coulomb_dipole_correction, CR.dipole_evaluate, {}, {}),
+                                              ("quadrupole", coulomb_quadrupole_correction, CR.quadrupole_evaluate, dict(quadrupoles=f.QD), dict(quadrupoles=QUAD))):
+        call = lambda fn=fn, which=which, **a: fn(**a, **{k: v for k, v in TCM.ALL[which].items() if a.get("cell") is not None or k != "compute_virial"})  # noqa: E731
+        atoms = dict(positions=f.P, charges=f.Q, dipoles=f.MU, **extra, cell=f.C)
+        aplan = dict(positions=POS, charges=VEC, dipoles=DIP, **eplan, cell=CELLB if batch else CELL1)
+        if batch:
+            atoms["batch_idx"], aplan["batch_idx"] = f.BI, IDX
+        ref64 = evaluate(*[atoms[k] for k in ("positions", "charges", "dipoles") + tuple(extra)], ent, cell=f.C, batch_idx=f.BI, distance_dtype=f.tdtype)
+        for label, lists, lplan in _list_forms(f):
+            ref = _tuple(call(**atoms, **lists))
+            assert len(ref) == len(TCM.NAMES[which])
+            for name, o in zip(TCM.NAMES[which], ref):
+                assert o.dtype == f.tdtype
+                TCM._close(o, ref64[name], f"coulomb_{which}_correction {tag} {label} {name} vs the restatement", f.rel)
+            _swept(f"coulomb_{which}_correction {tag} {label}", call, dict(atoms, **lists), dict(aplan, **lplan), _exact, ref=ref,
+                   shared=("cell",) if batch and label == "matrix" else ())
+        # the first system as a cluster
+        catoms = {k: (v[:n1].contiguous() if k != "cell" else None) for k, v in atoms.items() if k != "batch_idx"}
+        cplan = {k: v for k, v in aplan.items() if k not in ("cell", "batch_idx")}
+        lists = dict(neighbor_matrix=nm1, mask_value=n1)
+        ref = _tuple(call(**catoms, **lists))
+        ref64 = evaluate(*[catoms[k] for k in ("positions", "charges", "dipoles") + tuple(extra)], ent1, distance_dtype=f.tdtype)
+        for name, o in zip([k for k in TCM.NAMES[which] if k != "virial"], ref):
+            TCM._close(o, ref64[name], f"coulomb_{which}_correction {tag} cluster {name} vs the restatement", f.rel)
+        _swept(f"coulomb_{which}_correction {tag} cluster", call, dict(catoms, **lists), dict(cplan, neighbor_matrix=MAT), _exact, ref=ref)
+
+
+SCL_M = "off col row T flt"   # pair_scales [N, M]: float32 or float64 whatever the positions dtype
+SCL_L = "off col row flt"     # pair_scales [nnz]
+
+
+def _matrix_of(entries, values, n, fill):
+    """Padded [n, M] matrix (+ shifts and per-slot values, 0.5 on padding) of entries sorted by row."""
+    i, j, S = entries
+    counts = torch.bincount(i, minlength=n)
+    col = torch.arange(i.shape[0], device=DEV) - (torch.cumsum(counts, 0) - counts)[i]
+    m = int(counts.max()) + 2
+    nm = torch.full((n, m), fill, dtype=I32, device=DEV)
+    sh = torch.zeros((n, m, 3), dtype=I32, device=DEV)
+    val = torch.full((n, m), 0.5, dtype=values.dtype, device=DEV)
+    nm[i, col], sh[i, col], val[i, col] = j.to(I32), S.to(I32), values
+    ptr = torch.zeros(n + 1, dtype=I32, device=DEV)
+    ptr[1:] = torch.cumsum(counts, 0)
+    return nm, sh, val, torch.stack([i, j]).to(I32).contiguous(), ptr, S.to(I32).contiguous()
+
+
+def _stored_pair_scales(f):
+    """(pair_scales [N, M] beside the stored matrix with 0.5 on its padding, pair_scales [nnz] beside the stored CSR list) in the positions dtype."""
+    live = (f.nm >= 0) & (f.nm < f.n)
+    snm = torch.full(tuple(f.nm.shape), 0.5, dtype=f.tdtype, device=DEV)
+    snm[live] = LC.distance_class_scales(f.P, f.C, f.BI, *TDP.R.entries_from_matrix(f.nm, f.sh, f.n)).to(f.tdtype)
+    scsr = LC.distance_class_scales(f.P, f.C, f.BI, f.lst[0].long(), f.lst[1].long(), f.lsh.long()).to(f.tdtype)
+    return snm.contiguous(), scsr.contiguous()
+
+
+@DTYPES
+@pytest.mark.parametrize("batch", [False, True])
+@_collecting
+def test_pair_scale_correction(dtype, batch):
+    """All six outputs on the quadrupole fixture with one scale per stored entry from its distance class (tests/layout_cases.py: symmetric by
+    construction, one class exactly 1, 0.5 on the padding of the matrix).  `pair_scales` is an argument class of its own: [N, M] beside a
+    matrix, [nnz] beside a list, float32 or float64 whatever the positions dtype, so `flt` is the float dtype the positions do NOT have.
+    With shifts; then with `minimum_image=True` on the sub-list of the pairs whose stored shift already is the minimum image (fractional
+    components at most 0.45), without shifts, where the call with shifts and the call without meet the same restatement; then
+    `dipoles=None`, `quadrupoles=None` and both against the bits of zero tensors."""
+    from nvalchemiops.interactions.electrostatics import pair_scale_correction
+    from tests import pair_scale_reference as PSR
+    from tests import test_pair_scale_gpu as TPS
+
+    f = _mfx(dtype, batch)
+    tag = f"pair_scale_correction {dtype}{' batch' if batch else ''}"
+    ent = TDP.R.entries_from_matrix(f.nm, f.sh, f.n)
+    scales = LC.distance_class_scales(f.P, f.C, f.BI, *ent)
+    assert sorted(set(scales.tolist())) == sorted(LC.PS_SCALES)
+    call = lambda **a: pair_scale_correction(**a, **TPS.ALL)  # noqa: E731
+    atoms = dict(positions=f.P, charges=f.Q, dipoles=f.MU, quadrupoles=f.QD, cell=f.C)
+    aplan = dict(positions=POS, charges=VEC, dipoles=DIP, quadrupoles=QUAD, cell=CELLB if batch else CELL1)
+    if batch:
+        atoms["batch_idx"], aplan["batch_idx"] = f.BI, IDX
+
+    def against_restatement(out, ref, what):
+        assert len(out) == 6
+        for name, o in zip(TPS.NAMES, out):
+            assert o.dtype == f.tdtype
+            TPS._close(o, ref[name], f"{what} {name} vs the restatement", f.rel)
+
+    # the whole list, explicit shifts; the stored matrix and the stored CSR list hold the same entries in the same row order
+    ref64 = PSR.evaluate(f.P, f.Q, f.MU, f.QD, scales, ent, cell=f.C, batch_idx=f.BI, distance_dtype=f.tdtype)
+    snm, scsr = _stored_pair_scales(f)
+    for (label, lists, lplan), s, splan in zip(_list_forms(f), (snm, scsr), (SCL_M, SCL_L)):
+        kw = dict(atoms, pair_scales=s, **lists)
+        ref = _tuple(call(**kw))
+        against_restatement(ref, ref64, f"{tag} {label}")
+        _swept(f"{tag} {label}", call, kw, dict(aplan, pair_scales=splan, **lplan), _exact, ref=ref, shared=("cell",) if batch and label == "matrix" else ())
+        for absent in (("dipoles",), ("quadrupoles",), ("dipoles", "quadrupoles")):
+            none = _tuple(call(**dict(kw, **{k: None for k in absent})))
+            _compare(_tuple(call(**dict(kw, **{k: torch.zeros_like(kw[k]) for k in absent}))), none, _exact, f"{tag} {label}[{' '.join(absent)}: None]")
+            assert not torch.equal(none[0], ref[0])
+    # minimum image on the pairs whose stored shift already is the minimum image
+    keep = LC.minimum_image_entries(f.P, f.C, f.BI, *ent)
+    sub = tuple(e[keep] for e in ent)
+    assert 0 < int(keep.sum()) < keep.shape[0] and bool((sub[2] != 0).any())
+    ref64 = PSR.evaluate(f.P, f.Q, f.MU, f.QD, scales[keep], sub, cell=f.C, batch_idx=f.BI, distance_dtype=f.tdtype, minimum_image=True)
+    nm, sh, snm, lst, ptr, lsh = _matrix_of(sub, scales[keep].to(f.tdtype), f.n, f.n)
+    for label, lists, shifts, s, lplan, splan in (
+            ("matrix", dict(neighbor_matrix=nm, mask_value=f.n), dict(neighbor_matrix_shifts=sh), snm, dict(neighbor_matrix=MAT), SCL_M),
+            ("csr", dict(neighbor_list=lst, neighbor_ptr=ptr), dict(neighbor_shifts=lsh), scales[keep].to(f.tdtype).contiguous(),
+             dict(neighbor_list=MAT, neighbor_ptr=IDX), SCL_L)):
+        against_restatement(_tuple(call(**atoms, pair_scales=s, **lists, **shifts)), ref64, f"{tag} {label} sub-list with shifts")
+        kw = dict(atoms, pair_scales=s, **lists)
+        mcall = lambda **a: pair_scale_correction(**a, minimum_image=True, **TPS.ALL)  # noqa: E731
+        ref = _tuple(mcall(**kw))
+        against_restatement(ref, ref64, f"{tag} {label} minimum image")
+        _swept(f"{tag} {label} minimum image", mcall, kw, dict(aplan, pair_scales=splan, **lplan), _exact, ref=ref)
+
+
+@functools.lru_cache(maxsize=None)
+def _ffx(dtype_name, batch):
+    c, dt = LC.frames(batch), np.dtype(dtype_name).type
+    f = types.SimpleNamespace(batch=batch, n=c["n"], c=c, tdtype=F32 if dt == np.float32 else F64, rel=1e-11 if dt == np.float64 else 1e-6)
+    f.P, f.MU, f.QD, f.WMU, f.WQ, f.C = (_t(c[k].astype(dt)) for k in ("pos", "mu", "quad", "w_mu", "w_q", "cell"))
+    f.ATOMS, f.KINDS = _t(c["atoms"]), _t(c["kinds"])
+    f.BI = None if not batch else _t(c["batch_idx"])
+    f.ref = LC.frames_reference(batch)
+    return f
+
+
+@DTYPES
+@pytest.mark.parametrize("batch", [False, True])
+@_collecting
+def test_local_frames(dtype, batch):
+    """`LocalFrames`, `rotate_multipoles` and `multipole_frame_forces(compute_local_gradients=True, compute_virial=True)` on the fixture
+    `frames` of tests/layout_cases.py.  `frame_atoms` and `frame_kinds` go through the constructor in every layout and as int64; the four
+    tensors of the resulting object must equal the canonical object's.  The local multipoles and the caller's gradients get the plans of
+    dipoles and quadrupoles, `flt` included (`multipole_frame_forces` takes gradients of any float dtype).  The canonical call against
+    tests/local_frames_reference.py at the bars of tests/test_local_frames_gpu.py, every variant against the BITS of the canonical call.  A
+    `LocalFrames` built on the CPU and moved with `.to()` gives the bits of the device-built one."""
+    from nvalchemiops.interactions.electrostatics import LocalFrames, multipole_frame_forces, rotate_multipoles
+    from tests import test_local_frames_gpu as TLF
+
+    f = _ffx(dtype, batch)
+    tag = f"local frames {dtype}{' batch' if batch else ''}"
+
+    def run(fr, positions, local_dipoles, local_quadrupoles, dipole_grads, quadrupole_grads, cell, batch_idx=None):
+        mu, qd = rotate_multipoles(positions, local_dipoles, local_quadrupoles, fr, cell, batch_idx=batch_idx)
+        out = multipole_frame_forces(positions, local_dipoles, local_quadrupoles, fr, dipole_grads, quadrupole_grads, cell, batch_idx=batch_idx,
+                                     compute_local_gradients=True, compute_virial=True)
+        return (mu, qd) + tuple(out) + (fr.frame_atoms, fr.frame_kinds, fr.inverse_ptr, fr.inverse_slots)
+
+    def call(frame_atoms, frame_kinds, **a):
+        return run(LocalFrames(frame_atoms, frame_kinds, batch_idx=a.get("batch_idx")), **a)
+
+    kw = dict(frame_atoms=f.ATOMS, frame_kinds=f.KINDS, positions=f.P, local_dipoles=f.MU, local_quadrupoles=f.QD, dipole_grads=f.WMU,
+              quadrupole_grads=f.WQ, cell=f.C)
+    plan = dict(frame_atoms=MAT, frame_kinds=IDX, positions=POS, local_dipoles=DIP, local_quadrupoles=QUAD, dipole_grads=DIP, quadrupole_grads=QUAD,
+                cell=CELLB if batch else CELL1)
+    if batch:
+        kw["batch_idx"], plan["batch_idx"] = f.BI, IDX
+    ref = call(**kw)
+    assert len(ref) == 10 and all(o.dtype == f.tdtype for o in ref[:6]) and all(o.dtype == I32 for o in ref[6:])
+    for name, o, sign in zip(LC.FR_NAMES, ref, (1.0, 1.0, -1.0, 1.0, 1.0, 1.0)):  # the third output is the torque force, -dL/dr
+        TLF._close(sign * o, f.ref[name], f"{tag} {name} vs the restatement", f.rel)
+    _swept(tag, call, kw, plan, _exact, ref=ref)
+    moved = LocalFrames(f.ATOMS.cpu(), f.KINDS.cpu(), batch_idx=None if f.BI is None else f.BI.cpu()).to(DEV)
+    _compare(run(moved, **{k: v for k, v in kw.items() if not k.startswith("frame_")}), ref, _exact, f"{tag}[LocalFrames.to()]")
+
+
+@pytest.mark.parametrize("damped", [False, True], ids=["undamped", "thole"])
+@_collecting
+def test_cluster_induced_dipoles(damped):
+    """`cluster_induced_dipoles` on the batch of three clusters of tests/layout_cases.py (`cluster_induced`), an external field and a warm
+    start, float64: the canonical call against the dense solve by `_check_solution` of tests/test_induced_gpu.py, every variant against
+    the BITS of the canonical dipoles and iteration counts; a Python number for the polarisability against a constant tensor."""
+    from nvalchemiops.interactions.electrostatics import cluster_induced_dipoles
+    from tests import test_cluster_multipole_gpu as TCM
+
+    c = LC.cluster_induced()
+    thole = LC.THOLE if damped else None
+    d = LC.cluster_induced_dense(thole, DEV)
+    lf = TCM._lists(*c["entries"], c["n"], False)
+    tag = f"cluster_induced_dipoles {'thole' if damped else 'undamped'}"
+
+    def call(**a):
+        out = cluster_induced_dipoles(thole=thole, num_systems=c["nsys"], tolerance=LC.IND_TOL, return_info=True, **a)
+        return out.dipoles, out.iterations
+
+    atoms = dict(positions=_t(c["pos"]), charges=_t(c["q"]), polarizability=d["polar"], external_field=_t(c["field"]), initial_dipoles=_t(c["start"]),
+                 batch_idx=_t(c["batch_idx"]))
+    aplan = dict(positions=POS, charges=VEC, polarizability=VEC, external_field=DIP, initial_dipoles=DIP, batch_idx=IDX)
+    for label, lists, lplan in (("matrix", dict(neighbor_matrix=lf["nm"], mask_value=c["n"]), dict(neighbor_matrix=MAT)),
+                                ("csr", dict(neighbor_list=lf["nl"], neighbor_ptr=lf["ptr"]), dict(neighbor_list=MAT, neighbor_ptr=IDX))):
+        kw = dict(atoms, **lists)
+        out = cluster_induced_dipoles(thole=thole, num_systems=c["nsys"], tolerance=LC.IND_TOL, return_info=True, **kw)
+        TI._check_solution(out, d["H"], d["b"], d["polar"], atoms["batch_idx"], c["nsys"], LC.IND_TOL, f"layouts {tag} {label}", x0=atoms["initial_dipoles"])
+        assert int(out.iterations.max()) > 0
+        _swept(f"{tag} {label}", call, kw, dict(aplan, **lplan), _exact, ref=(out.dipoles, out.iterations))
+        number = call(**dict(kw, polarizability=0.0625))
+        _compare(call(**dict(kw, polarizability=torch.full_like(d["polar"], 0.0625))), number, _exact, f"{tag} {label}[polarizability: number]")
+        assert not torch.equal(number[0], out.dipoles)
+
+
 # ==== splines =============================================================================================================================
 
 MESH = "off col row T flt"
@@ -1667,6 +1919,36 @@ def test_gradient_layouts_of_the_quadrupole_thole_and_induced_dipole_ops(dtype):
     _check_gradient_layouts(ops)
     print(f"[layouts] gradient layouts {dtype}: {len(ops)} ops x 4 grad-output layouts, every gradient bit-identical to the contiguous backward"
           + (" (the four mesh ops: within the bar of two runs)" if dtype == "float64" else ""))
+
+
+@DTYPES
+def test_gradient_layouts_of_the_cluster_pair_scale_and_local_frame_ops(dtype):
+    """The same for `coulomb_dipole_correction`, `coulomb_quadrupole_correction` and `pair_scale_correction` (matrix and CSR, periodic cut-off
+    sums on the quadrupole fixture) with respect to positions, charges, dipoles and quadrupoles, and for BOTH outputs of `rotate_multipoles`
+    on the fixture `frames` with respect to positions and the local multipoles, on the single system and the batch.  Every adjoint is the
+    forward kernel with weights, or `mi_frame_adjoint` + `mi_frame_gather`: no atomics, equal bits."""
+    from nvalchemiops.interactions.electrostatics import (LocalFrames, coulomb_dipole_correction, coulomb_quadrupole_correction, pair_scale_correction,
+                                                          rotate_multipoles)
+
+    ops = {}
+    for batch in (False, True):
+        f = _mfx(dtype, batch)
+        bkw = dict(batch_idx=f.BI) if batch else {}
+        tag = " batch" if batch else ""
+        leaves, names = (f.P, f.Q, f.MU, f.QD), ("positions", "charges", "dipoles", "quadrupoles")
+        for (label, lists, _), s in zip(_list_forms(f), _stored_pair_scales(f)):
+            ops[f"coulomb_dipole_correction {label}{tag}"] = (
+                lambda p, q, m, f=f, bkw=bkw, lists=lists: coulomb_dipole_correction(p, q, m, f.C, **lists, **bkw), leaves[:3], names[:3], _exact)
+            ops[f"coulomb_quadrupole_correction {label}{tag}"] = (
+                lambda p, q, m, t, f=f, bkw=bkw, lists=lists: coulomb_quadrupole_correction(p, q, m, t, f.C, **lists, **bkw), leaves, names, _exact)
+            ops[f"pair_scale_correction {label}{tag}"] = (
+                lambda p, q, m, t, f=f, bkw=bkw, lists=lists, s=s: pair_scale_correction(p, q, m, t, s, f.C, **lists, **bkw), leaves, names, _exact)
+        g = _ffx(dtype, batch)
+        fr = LocalFrames(g.ATOMS, g.KINDS, batch_idx=g.BI)
+        ops[f"rotate_multipoles{tag}"] = (lambda p, m, t, g=g, fr=fr: rotate_multipoles(p, m, t, fr, g.C, batch_idx=g.BI), (g.P, g.MU, g.QD),
+                                          ("positions", "local_dipoles", "local_quadrupoles"), _exact)
+    _check_gradient_layouts(ops)
+    print(f"[layouts] gradient layouts {dtype}: {len(ops)} ops x 4 grad-output layouts, every gradient bit-identical to the contiguous backward")
 
 
 # ==== caller-owned output buffers =========================================================================================================

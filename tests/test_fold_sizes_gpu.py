@@ -1,11 +1,13 @@
 """Sizes beyond one trip of the per-system folds of `dftd4`, `dftd4_atm`, `gaussian_charge_correction`, `charge_equilibration`,
-`ewald_dipole_real_space`, `ewald_real_space_with_virial`, `ewald_quadrupole_real_space`, `thole_dipole_correction`, `induced_dipoles`
-and `thole_induced_dipoles`.
+`ewald_dipole_real_space`, `ewald_real_space_with_virial`, `ewald_quadrupole_real_space`, `thole_dipole_correction`, `induced_dipoles`,
+`thole_induced_dipoles`, `pair_scale_correction`, `rotate_multipoles` / `multipole_frame_forces`, `coulomb_dipole_correction`,
+`coulomb_quadrupole_correction` (as periodic cut-off sums) and `cluster_induced_dipoles`.
 
 Every per-system sum of these ops is the fixed-order fold of csrc/pair_row.h (`mi_system_fold`) on a grid of (blocks, systems) blocks of
 256 threads, each looping `r += blocks * 256` over ALL N rows and keeping those of its system: `d4_fold_kernel` (also `dftd4_atm`'s),
 `gc_fold_kernel`, `gc_system_sums_kernel`, `qeq_fold_kernel`, `dp_fold_kernel` (also as `mi_thole_dipole` launches it),
-`ew_virial_fold_kernel`, `qd_fold_kernel`, `ind_dot_kernel`; `qeq_cg_update_kernel`, `qeq_cg_direction_kernel`, `ind_cg_update_kernel` and
+`ew_virial_fold_kernel`, `qd_fold_kernel`, `ind_dot_kernel`, `ps_fold_kernel`, `fr_fold_kernel` (and `dp_fold_kernel` / `qd_fold_kernel` once
+more as `mi_coulomb_dipole` / `mi_coulomb_quadrupole` launch them from their own scratch layout); `qeq_cg_update_kernel`, `qeq_cg_direction_kernel`, `ind_cg_update_kernel` and
 `ind_cg_direction_kernel` walk the same grid.  The parity modules stop at a few hundred atoms; the second trip of these loops
 (N > 256 * blocks = 16 384) and the batched form at that size are compared here.
 
@@ -40,6 +42,18 @@ a third of the rows) and K n0 no multiple of 64.
       with a list cutoff of 6 (`thole_cases.fold_case()`; tests/test_induced_reference_cpu.py asserts that this truncated H is positive
       definite).  The bound is the QEq one, with `_check_solution` of tests/test_induced_gpu.py for the small call.  `mi_induced_dot` and
       the `partial` output of `mi_induced_apply` on K n0 random rows against float64 torch sums per system, at the fold bar.
+  pair_scale_correction: with explicit shifts (the `MIN = false` kernels) on the 24-atom triclinic box of tests/pair_scale_cases.py, and
+      with `minimum_image=True` (the `MIN = true` kernels) on its three wrapped molecules -- (b) is their batch of three cells tiled to
+      3 K systems, (a) the 9-atom chain alone in its cell -- every flag, both formats.  The matrices keep all three kinds of padding
+      (`_tile_padded_matrix`: a -1 slot stays -1) and NaN scales on the padding; `pair_scales` is tiled like the shifts.
+  rotate_multipoles + multipole_frame_forces(compute_local_gradients, compute_virial): the "triclinic" case of
+      tests/test_local_frames_gpu.py (25 atoms, every kind, wrapped positions); `LocalFrames` is built from the tiled tables.  Dipoles,
+      quadrupoles, torque forces and both local gradients bit for bit; the virial term of `fr_fold_kernel` at the fold bar.
+  coulomb_dipole_correction / coulomb_quadrupole_correction with a cell: the periodic problem of tests/cluster_multipole_reference.py
+      (96 atoms) with its list cut to the entries within 7.0 plus every self image (the shortest lattice vector is 8.87, so a plain cutoff
+      below it would hold none): rows of 130 - 145 entries, 3.4 M entries tiled.  The first periodic BATCH of the bare kind.
+  cluster_induced_dipoles: K copies of the 150-atom cluster over its all-pairs list (3.7 M entries), undamped and thole = 0.39, as one
+      system and with num_systems = K; the bound of the induced-dipole test above, and the iteration count equal to the small call's.
 
 MEASURED on one MI355X (each test prints its figures under `pytest -s`; matrix and CSR agree to the digits shown).  Per-atom outputs:
 bit-identical wherever that is asserted.  Worst |X_big - K X_small| / bar as ONE system:
@@ -67,22 +81,43 @@ stride-0 cell; gaussian virial 3.6e-15 and 5.3e-15 absolute (1.1e-9 and 1.8e-9 o
              2.1e-8 and 1.9e-8) and in the worst system of the batch (bars 6.9e-10 and 6.2e-10), both cell forms; 10 iterations in the
              small call, the single system and all 911 systems of the batch (reference PCG: 10)
   mi_induced_dot / mi_induced_apply partial  24 597 random rows: 1.2e-9 / 0 of the bar as one system, 8.8e-10 / 1.2e-9 as 911 systems
+  pair_scale  24 atoms (K 1025, N 24 600), shifts: small call 1.1e-15 at worst (bar 1e-11); virial as one system 1.8e-12 (8.8e-10 of the
+             bar), in the batch 1.8e-15 (8.8e-10 of the bar), both cell forms.  Minimum image: the batch of 17 atoms in three cells (K 1446,
+             4338 systems, N 24 582) small call 1.3e-15, every system's virial 1.8e-15 (9.0e-10 of the bar); the chain (K 2731, N 24 579) as
+             one system 3.6e-12 (6.8e-10 of the bar).  With `ps_fold_kernel` cut to its first trip (a scratch build, all reads in range) the
+             one-system virial is off by 2.1e6 bars and the virials of the minimum-image batch by 4.2e6 bars -- all four tests fail -- and
+             tests/test_pair_scale_gpu.py still passes (35 tests).
+  local frames  25 atoms (K 984, N 24 600): virial term as one system 3.6e-12 (7.0e-10 of the bar), in the batch 3.6e-15 (6.8e-10 of the
+             bar), both cell forms.  With `fr_fold_kernel` cut to its first trip the one-system virial term is off by 2.1e6 bars, and
+             tests/test_local_frames_gpu.py still passes (45 tests).
+  cluster dipole / quadrupole, periodic  96 atoms (K 257, N 24 672, 3.4 M entries): small call 2.7e-15 / 3.7e-15 at worst (bar 1e-11);
+             virial as one system 2.3e-13 / 4.5e-13 (6.9e-10 / 6.2e-10 of the bar), in the batch 8.9e-16 / 2.7e-15 (6.9e-10 / 9.3e-10 of
+             the bar), both cell forms
+  cluster_induced_dipoles  150 atoms (K 164, N 24 600): max|mu - mu_ref| 6.1e-12 undamped and 2.7e-11 damped, as one system (bars 1.4e-7)
+             and in the worst system of the batch (bars 1.1e-8); 8 / 15 iterations in the small call, the single system and all 164
+             systems of the batch (reference PCG: 8 / 15)
 Matrix and CSR agree to the digits shown; per-atom outputs bit-identical wherever that is asserted."""
+import functools
 import math
 
 import numpy as np
 import pytest
 import torch
 
+from tests import cluster_multipole_reference as CR
 from tests import d4_atm_cases as K3
 from tests import d4_cases as K4
+from tests import pair_scale_reference as PR
 from tests import qeq_reference as QR
+from tests import test_cluster_multipole_gpu as TCM
 from tests import test_d4_atm_gpu as TD4A
 from tests import test_d4_gpu as TD4
 from tests import test_dipole_gpu as TDP
 from tests import test_electrostatic_virial_gpu as TV
 from tests import test_gaussian_charges_gpu as TG
 from tests import test_induced_gpu as TI
+from tests import test_local_frames_gpu as TLF
+from tests import test_pair_scale_gpu as TPS
 from tests import test_qeq_gpu as TQ
 from tests import test_quadrupole_gpu as TQD
 from tests import test_thole_gpu as TTH
@@ -108,6 +143,15 @@ def _tile_matrix(nm, sh, k):
     off = (torch.arange(k, device=nm.device, dtype=nm.dtype) * n0)[:, None, None]
     big = torch.where(nm[None] == n0, torch.full_like(nm[None], k * n0), nm[None] + off).reshape(k * n0, -1).contiguous()
     return big, None if sh is None else sh.repeat(k, 1, 1).contiguous()
+
+
+def _tile_padded_matrix(nm, k):
+    """`_tile_matrix` for a matrix that holds all three kinds of padding (the mask value n0, -1 and n0 + 7): a -1 slot stays -1, a value
+    >= n0 moves up by (k - 1) n0, so the mask value becomes k n0 and n0 + 7 becomes k n0 + 7, outside [0, k n0) again."""
+    n0 = nm.shape[0]
+    off = (torch.arange(k, device=nm.device, dtype=nm.dtype) * n0)[:, None, None]
+    pad = torch.where(nm < 0, nm, nm + (k - 1) * n0)
+    return torch.where(((nm >= 0) & (nm < n0))[None], nm[None] + off, pad[None]).reshape(k * n0, -1).contiguous()
 
 
 def _tile_csr(lst, ptr, lsh, k):
@@ -491,3 +535,220 @@ def test_induced_dot_and_apply_partials_beyond_one_trip(fmt):
         for s in (0, k // 2, k - 1):  # the product of a copy is the small product on that copy's rows
             rows = slice(s * n0, (s + 1) * n0)
             assert torch.equal(hx[rows], TI._apply(ten0, nbr0, diag0, x[rows].contiguous(), None, None, 1, small_lay[2], small_lay[3], want_partial=False)[0])
+
+
+# ---- pair_scale_correction -----------------------------------------------------------------------------------------------------------------
+
+def _pair_scale_copies(n0):
+    from nvalchemiops import _capi as C
+
+    blocks = int(C.lib().mi_pair_scale_blocks())
+    k = _copies(n0, blocks)
+    assert k * n0 > 256 * blocks and (k * n0) % 64 != 0
+    return k
+
+
+def _tiled_scaled_lists(f, fmt, k, shifts):
+    """The lists of `test_pair_scale_gpu._lists` (matrix: all three kinds of padding, NaN scales on the padding) repeated blockwise, the scales
+    and the shifts tiled alike."""
+    if fmt == "matrix":
+        return dict(pair_scales=f["snm"].repeat(k, 1), neighbor_matrix=_tile_padded_matrix(f["nm"], k),
+                    neighbor_matrix_shifts=f["sh"].repeat(k, 1, 1).contiguous() if shifts else None, mask_value=k * f["n"])
+    lst, ptr, lsh = _tile_csr(f["nl"], f["ptr"], f["lsh"] if shifts else None, k)
+    return dict(pair_scales=f["scsr"].repeat(k), neighbor_list=lst, neighbor_ptr=ptr, neighbor_shifts=lsh)
+
+
+def _tiled_atoms(args, k):
+    return [a.repeat((k,) + (1,) * (a.dim() - 1)) for a in args]
+
+
+@pytest.mark.parametrize("fmt", ["matrix", "list"])
+def test_pair_scale_copies_as_one_system_and_as_a_batch(fmt):
+    """Explicit shifts (the `MIN = false` kernels and `ps_fold_kernel`): the 24-atom triclinic box of tests/pair_scale_cases.py, every flag."""
+    fn, f = TPS._fn(), TPS._case("periodic")
+    n0 = f["n"]
+    k = _pair_scale_copies(n0)
+    args, cell, ref = TPS._inputs(f), TPS._cells(f), TPS._reference("periodic")
+    small = fn(*args, cell=cell, **TPS._kw(f, fmt), **TPS.ALL)
+    for name, o in zip(TPS.NAMES, small):
+        TPS._close(o, ref[name], f"fold sizes pair scale {fmt}: the small call, {name}", 1e-11)
+    big_args, big = _tiled_atoms(args, k), _tiled_scaled_lists(f, fmt, k, True)
+    one = fn(*big_args, cell=cell, **big, **TPS.ALL)
+    bi = torch.arange(k, device=DEV, dtype=torch.int32).repeat_interleave(n0)
+    many = [(tag, fn(*big_args, cell=cells, batch_idx=bi, **big, **TPS.ALL))
+            for tag, cells in (("", cell.repeat(k, 1, 1).contiguous()), (" (stride-0 cell)", cell[:1].expand(k, 3, 3)))]
+    _check_copies(f"pair scale {fmt}", small, one, many, k, per_atom=(0, 1, 2, 3, 4), vir=5)
+
+
+@pytest.mark.parametrize("fmt", ["matrix", "list"])
+def test_pair_scale_minimum_image_copies_as_one_system_and_as_a_batch(fmt):
+    """`minimum_image=True` on a list without shifts (the `MIN = true` kernels): the three wrapped molecules of tests/pair_scale_cases.py,
+    their batch of three cells tiled to 3 K systems (the cells repeated; 3 K stays below the 65 535 of the grid), and the 9-atom chain alone
+    in its cell as one system of K copies."""
+    fn, f = TPS._fn(), TPS._case("molecules")
+    args, cells, ref = TPS._inputs(f), TPS._cells(f), TPS._reference("molecules")
+    # (b) the batch of three systems, K times
+    n0 = f["n"]
+    k = _pair_scale_copies(n0)
+    assert 3 * k <= 65535
+    small = fn(*args, cell=cells, batch_idx=f["bi"], minimum_image=True, **TPS._kw(f, fmt, shifts=False), **TPS.ALL)
+    for name, o in zip(TPS.NAMES, small):
+        TPS._close(o, ref[name], f"fold sizes pair scale minimum image {fmt}: the small batch, {name}", 1e-11)
+    bi = (3 * torch.arange(k, device=DEV, dtype=torch.int32)[:, None] + f["bi"][None, :].to(torch.int32)).reshape(-1).contiguous()
+    many = fn(*_tiled_atoms(args, k), cell=cells.repeat(k, 1, 1).contiguous(), batch_idx=bi, minimum_image=True,
+              **_tiled_scaled_lists(f, fmt, k, False), **TPS.ALL)
+    for i in range(5):
+        _bitwise(many[i], small[i], k, f"pair scale minimum image {fmt} batch, output {i}")
+    assert many[5].shape[0] == 3 * k
+    _fold_close(many[5], small[5].repeat(k, 1, 1), small[5], f"pair scale minimum image {fmt} batch of {3 * k}, virial")
+    # (a) the chain alone in its cell: one system of K copies
+    p = f["problem"]
+    sel = p["entries"][0] < 9
+    assert bool((p["entries"][1][sel] < 9).all())
+    c = TPS._lists(tuple(e[sel] for e in p["entries"]), p["scales"][sel.numpy()], 9, True)
+    k = _pair_scale_copies(9)
+    chain, cell = [a[:9].contiguous() for a in args], cells[:1].contiguous()
+    small = fn(*chain, cell=cell, minimum_image=True, **TPS._kw(c, fmt, shifts=False), **TPS.ALL)
+    ref = PR.evaluate(*chain, c["s"], c["ent"], cell=cell, minimum_image=True)
+    for name, o in zip(TPS.NAMES, small):
+        TPS._close(o, ref[name], f"fold sizes pair scale minimum image {fmt}: the chain, {name}", 1e-11)
+    one = fn(*_tiled_atoms(chain, k), cell=cell, minimum_image=True, **_tiled_scaled_lists(c, fmt, k, False), **TPS.ALL)
+    _check_copies(f"pair scale minimum image {fmt}", small, one, [], k, per_atom=(0, 1, 2, 3, 4), vir=5)
+
+
+# ---- rotate_multipoles / multipole_frame_forces --------------------------------------------------------------------------------------------
+
+def test_local_frames_copies_as_one_system_and_as_a_batch():
+    """The "triclinic" case of tests/test_local_frames_gpu.py (every kind, wrapped positions, molecules that straddle faces); `LocalFrames` is
+    built from the tiled tables (indices + k n0, a -1 slot stays -1).  Dipoles, quadrupoles, torque forces and both local gradients bit for
+    bit, the virial term of `fr_fold_kernel` at the fold bar."""
+    from nvalchemiops import _capi as C
+
+    LocalFrames, rotate, frame_forces = TLF._api()
+    c = TLF._case("triclinic")
+    n0, blocks = c["n"], int(C.lib().mi_frame_blocks())
+    k = _copies(n0, blocks)
+    n = k * n0
+    assert n > 256 * blocks and n % 64 != 0
+    small = TLF._check_all("triclinic", F64)  # (forces, local_dipole_grads, local_quadrupole_grads, virial), judged against the reference
+    d = TLF._device_inputs(c, F64)
+    small = tuple(rotate(d["pos"], d["mu"], d["quad"], d["frames"], d["cell"])) + tuple(small)
+    P, MU, QD, WMU, WQ = _tiled_atoms([d[x] for x in ("pos", "mu", "quad", "w_mu", "w_q")], k)
+    off = (torch.arange(k, dtype=torch.int32) * n0)[:, None, None]
+    atoms = torch.where(c["atoms"][None] >= 0, c["atoms"][None] + off, c["atoms"][None]).reshape(n, 3).to(DEV)
+    kinds = c["kinds"].repeat(k).to(DEV)
+    assert int(atoms.min()) == -1 and int(atoms.max()) < n
+
+    def run(frames, cell, bi):
+        out = frame_forces(P, MU, QD, frames, WMU, WQ, cell, batch_idx=bi, compute_local_gradients=True, compute_virial=True)
+        return tuple(rotate(P, MU, QD, frames, cell, batch_idx=bi)) + tuple(out)
+
+    one = run(LocalFrames(atoms, kinds), d["cell"], None)
+    bi = torch.arange(k, device=DEV, dtype=torch.int32).repeat_interleave(n0)
+    frames = LocalFrames(atoms, kinds, batch_idx=bi)
+    many = [(tag, run(frames, cells, bi))
+            for tag, cells in (("", d["cell"][None].repeat(k, 1, 1).contiguous()), (" (stride-0 cell)", d["cell"][None].expand(k, 3, 3)))]
+    _check_copies("local frames", small, one, many, k, per_atom=(0, 1, 2, 3, 4), vir=5)
+
+
+# ---- coulomb_dipole_correction / coulomb_quadrupole_correction as periodic cut-off sums ---------------------------------------------------------
+
+CLUSTER_FOLD_CUTOFF = 7.0
+
+
+@functools.lru_cache(maxsize=None)
+def _cluster_periodic_case():
+    """The periodic problem of tests/cluster_multipole_reference.py (96 atoms, cutoff 9.0, rows of about 290 entries) with its list cut to
+    the entries within `CLUSTER_FOLD_CUTOFF` plus every self image (i, i, S != 0) it holds: K = 257 copies then store about 3.4 M entries
+    where the full list would store 7.2 M.  The shortest lattice vector is 8.87 long, so a plain cutoff that short would hold no self image;
+    the cut list is still full (an entry and its mirror have the same length) and rows still hold more than 64 entries."""
+    p = CR.periodic_problem()
+    i, j, S = p["entries"]
+    pos, cell = torch.as_tensor(p["pos"]), torch.as_tensor(p["cell"])
+    r = (pos[j] + S.to(F64) @ cell - pos[i]).norm(dim=1)
+    keep = (r < CLUSTER_FOLD_CUTOFF) | (i == j)
+    i, j, S = i[keep], j[keep], S[keep]
+    counts = torch.bincount(i, minlength=p["n"])
+    assert int(counts.min()) > 64 and bool((counts % 64 != 0).any()) and bool(((i == j) & (S != 0).any(-1)).any())
+    f = TCM._lists(i, j, S, p["n"], True)
+    f.update(cells=p["cell"][None], **{x: p[x] for x in ("pos", "q", "mu", "Q")})
+    return f
+
+
+@pytest.mark.parametrize("fmt", ["matrix", "list"])
+@pytest.mark.parametrize("which", ["dipole", "quadrupole"])
+def test_cluster_corrections_periodic_copies_as_one_system_and_as_a_batch(which, fmt):
+    """`mi_coulomb_dipole` / `mi_coulomb_quadrupole` launch the shared `dp_fold_kernel` / `qd_fold_kernel` from their own scratch layout; this
+    is the second trip of those launches and the first periodic BATCH of the bare kind, every flag."""
+    from nvalchemiops import _capi as C
+
+    fn, f = TCM._api(which), _cluster_periodic_case()
+    n0, blocks = f["n"], int(getattr(C.lib(), f"mi_coulomb_{which}_blocks")())
+    k = _copies(n0, blocks)
+    n = k * n0
+    assert n > 256 * blocks and n % 64 != 0 and k * f["nl"].shape[1] <= 4_200_000
+    args, cell = [TCM._t(f[x]) for x in TCM.INPUTS[which]], TCM._t(f["cells"])
+    small = fn(*args, cell, **TCM._kw(f, fmt), **TCM.ALL[which])
+    evaluate = CR.dipole_evaluate if which == "dipole" else CR.quadrupole_evaluate
+    ref = evaluate(*args, f["ent"], cell=cell)
+    for name, o in zip(TCM.NAMES[which], small):
+        TCM._close(o, ref[name], f"fold sizes cluster {which} {fmt}: the small call, {name}", 1e-11)
+    if fmt == "matrix":
+        big = dict(neighbor_matrix=_tile_padded_matrix(f["nm"], k), neighbor_matrix_shifts=f["sh"].repeat(k, 1, 1).contiguous(), mask_value=n)
+    else:
+        lst, ptr, lsh = _tile_csr(f["nl"], f["ptr"], f["lsh"], k)
+        big = dict(neighbor_list=lst, neighbor_ptr=ptr, neighbor_shifts=lsh)
+    big_args = _tiled_atoms(args, k)
+    one = fn(*big_args, cell, **big, **TCM.ALL[which])
+    bi = torch.arange(k, device=DEV, dtype=torch.int32).repeat_interleave(n0)
+    many = [(tag, fn(*big_args, cells, batch_idx=bi, **big, **TCM.ALL[which]))
+            for tag, cells in (("", cell.repeat(k, 1, 1).contiguous()), (" (stride-0 cell)", cell[:1].expand(k, 3, 3)))]
+    last = len(small) - 1
+    _check_copies(f"cluster {which} periodic {fmt}", small, one, many, k, per_atom=tuple(range(last)), vir=last)
+
+
+# ---- cluster_induced_dipoles ---------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("damped", [False, True], ids=["undamped", "thole"])
+@pytest.mark.parametrize("fmt", ["matrix", "list"])
+def test_cluster_induced_dipoles_copies_as_one_system_and_as_a_batch(fmt, damped):
+    """K copies of the 150-atom cluster of tests/cluster_multipole_reference.py over its all-pairs list repeated blockwise: the operator is
+    block-diagonal with identical blocks, so the exact solution is the small dense solution tiled.  The bound of the induced-dipole fold
+    test above with the small block's spectrum; the iteration count is the small call's."""
+    from nvalchemiops import _capi as C
+
+    solve = TCM._api()[0]
+    f, tol = TCM._solver_case("c150", damped), 1e-10
+    n0, blocks = f["n"], int(C.lib().mi_induced_blocks())
+    k = _copies(n0, blocks)
+    n = k * n0
+    assert n > 256 * blocks and n % 64 != 0
+    p0, q0, a0, field = TCM._t(f["pos"]), TCM._t(f["q"]), f["polar"], f["field"]
+    label = f"cluster induced {'thole' if damped else 'undamped'} {fmt}"
+    common = dict(thole=f["thole"], tolerance=tol, return_info=True)
+    lists = dict(neighbor_matrix=f["nm"]) if fmt == "matrix" else dict(neighbor_list=f["nl"], neighbor_ptr=f["ptr"])
+    out = solve(p0, q0, a0, external_field=field, **common, **lists)
+    mu_ref = TCM._check_solution(out, f["H"], f["b"], a0, f["bi"], 1, tol, f"fold sizes {label}: the small call")
+    dmu = 10.0 * tol * float(f["b"].norm()) / float(torch.linalg.eigvalsh(f["H"]).min()) + 1e-14
+    if fmt == "matrix":
+        big = dict(neighbor_matrix=_tile_padded_matrix(f["nm"], k))
+    else:
+        lst, ptr, _ = _tile_csr(f["nl"], f["ptr"], None, k)
+        big = dict(neighbor_list=lst, neighbor_ptr=ptr)
+    P, Q, A, F = _tiled_atoms([p0, q0, a0, field], k)
+    want = mu_ref.reshape(n0, 3).repeat(k, 1)
+    one = solve(P, Q, A, external_field=F, **common, **big)
+    err = float((one.dipoles - want).abs().max())
+    print(f"[fold] {label} one system of {n} atoms: max|mu - mu_ref| {err:.3e}  bar {math.sqrt(k) * dmu:.3e}  iterations {one.iterations.tolist()} "
+          f"(small call {out.iterations.tolist()})")
+    assert err <= math.sqrt(k) * dmu and float(one.residual[0]) <= tol
+    assert one.iterations.tolist() == out.iterations.tolist()
+    bi = torch.arange(k, device=DEV, dtype=torch.int32).repeat_interleave(n0)
+    many = solve(P, Q, A, external_field=F, batch_idx=bi, num_systems=k, **common, **big)
+    err = (many.dipoles - want).abs().reshape(k, -1).max(1).values
+    print(f"[fold] {label} batch of {k}: worst system max|mu - mu_ref| {float(err.max()):.3e}  bar {dmu:.3e}  iterations "
+          f"{int(many.iterations.min())} - {int(many.iterations.max())}")
+    assert bool((err <= dmu).all()) and bool((many.residual <= tol).all())
+    assert many.iterations.tolist() == out.iterations.tolist() * k
+    energy = many.polarization_energy
+    assert bool(((energy - out.polarization_energy).abs() <= 100.0 * tol * out.polarization_energy.abs() + 1e-14).all())

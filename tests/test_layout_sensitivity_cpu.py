@@ -17,7 +17,11 @@ bound -- polarisabilities, charges and external field 1e7 - 1e8 in all four fixt
 alpha of the induced batch is why its 27-atom lattice runs at alpha 0.625 with a truncated k sum: with two converged parameter sets the
 operator does not depend on alpha and a rolled `alpha` moved the solution by 1.25 x (2 x bound).  Smallest eigenvalue of D^1/2 H D^1/2:
 0.717 (single) and 0.653, 0.717 (batch) undamped; 0.475 and 0.481, 0.472 damped at polarisabilities in [2, 8], where the undamped H is
-indefinite (asserted)."""
+indefinite (asserted).
+
+Pair-scale and local-frame fixtures, measured here (single / batch): rolled `pair_scales` 4.5e5 / 9.8e5 bars; rolled `frame_atoms` 1.8e6 /
+2.0e6, `local_quadrupoles` 1.4e6 / 1.3e6, `quadrupole_grads` 1.7e6 / 1.9e6.  Geometry of the frame fixture: bonds 0.957 - 1.446, angles
+42.0 - 131.1 degrees, Z_ONLY axes 0.053 from the switch, chiral triple products >= 0.47, fractional components of frame vectors <= 0.145."""
 import numpy as np
 import pytest
 import torch
@@ -238,4 +242,61 @@ def test_pme_quadrupole_fixture_rolled_arguments_and_a_transposed_cell(batch):
     moved = L.pme_quadrupole_reference(batch, cell=np.ascontiguousarray(c["cell"].transpose(0, 2, 1)))
     worst["cell transposed"] = max(_ratio(moved[k], ref[k], bars[k]) for k in L.QD_NAMES)
     print(f"[sensitivity pme_quadrupole {'batch' if batch else 'single'}] largest |moved - ref| / bar: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+    assert all(v >= FACTOR for v in worst.values()), worst
+
+
+@pytest.mark.parametrize("batch", [False, True], ids=["single", "batch"])
+def test_pair_scale_fixture_rolled_scales(batch):
+    """`pair_scales` is the one argument class `pair_scale_correction` adds: one value per stored entry.  Rolled by one entry it must move the
+    restatement by 100 x the widest bar of the sweep, 1e-6 max|ref| (+ 1e-14), the float32 bar of tests/test_pair_scale_gpu.py.  Also what the
+    fixture promises: the four classes are present, the scales are symmetric, every listed distance is at least the 1.3 the bars assume,
+    and the sub-list of the `minimum_image` calls is full, holds shifted entries and is not the whole list."""
+    from tests.cluster_multipole_reference import D_MIN
+
+    c = L.pair_scale(batch)
+    i, j, S = c["ent"]
+    t = torch.as_tensor
+    bi = None if c["batch_idx"] is None else t(c["batch_idx"])
+    d, _ = L.pair_vectors(t(c["pos"]), t(c["cell"]), bi, i, j, S)
+    assert float(d.norm(dim=1).min()) >= D_MIN and sorted(set(c["scales"].tolist())) == sorted(L.PS_SCALES)
+    by_pair = {(a, b, tuple(s)): v for a, b, s, v in zip(i.tolist(), j.tolist(), S.tolist(), c["scales"].tolist())}
+    assert all(by_pair[(b, a, tuple(-x for x in s))] == v for (a, b, s), v in by_pair.items()), "s_ij = s_ji"
+    keep = L.minimum_image_entries(t(c["pos"]), t(c["cell"]), bi, i, j, S)
+    kept = {(a, b) for a, b in zip(i[keep].tolist(), j[keep].tolist())}
+    assert 0 < len(kept) == int(keep.sum()) < keep.shape[0] and all((b, a) in kept for a, b in kept) and bool((S[keep] != 0).any())
+    ref = L.pair_scale_reference(batch)
+    bars = {k: 1e-6 * np.abs(ref[k]).max() + 1e-14 for k in L.QD_NAMES}
+    moved = L.pair_scale_reference(batch, scales=_roll(c["scales"]))
+    worst = max(_ratio(moved[k], ref[k], bars[k]) for k in L.QD_NAMES)
+    print(f"[sensitivity pair_scale {'batch' if batch else 'single'}] largest |moved - ref| / bar: pair_scales {worst:.3g}; minimum-image sub-list "
+          f"{int(keep.sum())} of {keep.shape[0]} entries")
+    assert worst >= FACTOR
+
+
+@pytest.mark.parametrize("batch", [False, True], ids=["single", "batch"])
+def test_frames_fixture_geometry_and_rolled_tables_multipoles_and_gradients(batch):
+    """The geometry conditions behind the bars of tests/test_local_frames_gpu.py on the float32 numbers of the fixture: bond lengths in
+    [0.9, 1.6], angles between frame vectors in [40, 140] degrees, Z_ONLY axes at least 0.05 from the switch, chiral triple products above 0.2,
+    every fractional component of a frame vector at least 0.05 away from +-0.5.  Then `frame_atoms`, `local_quadrupoles` and
+    `quadrupole_grads` rolled by one row: each must move the restatement by 100 x the widest bar of the sweep, 1e-6 max|ref| (+ 1e-14).
+    A rolled `frame_atoms` makes some atoms name themselves (non-finite values there): the figure is taken over the finite entries and
+    the number of non-finite ones is printed."""
+    c = L.frames(batch)
+    t = torch.as_tensor
+    cond = L.frame_conditions(t(c["pos"]), t(c["atoms"]), t(c["kinds"]), t(c["cell"]), None if c["batch_idx"] is None else t(c["batch_idx"]))
+    assert 0.9 <= cond["bond"][0] and cond["bond"][1] <= 1.6 and 40.0 <= cond["angle"][0] and cond["angle"][1] <= 140.0, cond
+    assert cond["z_only"] > 0.05 and cond["chiral"] > 0.2 and cond["image"] <= 0.45, cond
+    assert sorted(set(c["kinds"].tolist())) == list(range(6))
+    chiral = (c["kinds"] == 2) & (c["atoms"][:, 2] >= 0)
+    assert chiral.any() and ((c["kinds"] == 2) & ~chiral).any(), "Z_THEN_X with and without a y atom"
+    ref = L.frames_reference(batch)
+    bars = {k: 1e-6 * np.abs(ref[k]).max() + 1e-14 for k in L.FR_NAMES}
+    worst, lost = {}, 0
+    for arg in ("atoms", "quad", "w_q"):
+        moved = L.frames_reference(batch, **{arg: _roll(c[arg])})
+        finite = {k: np.isfinite(moved[k]) for k in L.FR_NAMES}
+        lost = max(lost, sum(int((~m).sum()) for m in finite.values()))
+        worst[arg] = max(_ratio(moved[k][finite[k]], ref[k][finite[k]], bars[k]) for k in L.FR_NAMES if finite[k].any())
+    print(f"[sensitivity frames {'batch' if batch else 'single'}] {cond}; largest |moved - ref| / bar: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items())
+          + f"; non-finite entries under rolled frame_atoms: {lost}")
     assert all(v >= FACTOR for v in worst.values()), worst

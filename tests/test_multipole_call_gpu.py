@@ -1,12 +1,15 @@
-"""The call layer of the nine point-multipole operator halves (interactions/electrostatics/_multipoles.py and the op table of _eops.py): the
-eager path against the custom op, and the op's backward against the operator's adjoint function.
+"""The call layer of the ten point-multipole operator halves (interactions/electrostatics/_multipoles.py and the op table of _eops.py) and of
+`rotate_multipoles`, whose op is written out beside that table: the eager path against the custom op, and the op's backward against the
+operator's adjoint function.
 
 Both sides of every comparison reach the same launches, so everything but the float64 mesh outputs must agree bit for bit (the float64
 spread adds in arrival order; those agree to the relative 1e-12 of tests/test_pme_quadrupole_gpu.py).  What can differ is the wiring: an
 argument in the wrong slot of the generated forward / setup_context / backward, a saved tensor taken for a scalar, a flag dropped.  The input
 is the batch of tests/test_dispersion_call_gpu.py (two triclinic cells of 10 + 14 atoms, self-images in the first, an empty row in the
 second) on a full list as a matrix 44 wide with an explicit mask value above N and as CSR with shifts, two different alphas, a (8, 10, 12)
-mesh, and for the operators that take `cell=None` the first system alone as a cluster.
+mesh, and for the operators that take `cell=None` the first system alone as a cluster.  `pair_scales` is a symmetric hash of the two atom
+indices (the classes 0, 0.4, 0.8 and 1 of tests/pair_scale_cases.py, whatever the image) on every slot of that list.  `rotate_multipoles`
+runs on the batch of three cells of tests/test_local_frames_gpu.py.
 """
 import functools
 
@@ -40,11 +43,24 @@ OPERATORS = {
     "pme_quadrupole_reciprocal_space": ("pme_quadrupole", "_recip_adjoint", QD, MESH, "quadrupole_gradients", ("cell", "alpha"), False, (5, 6)),
     "coulomb_dipole_correction": ("cluster", "_dipole_adjoint", DP, ("cell",) + LISTS, None, ("cell",), True, None),
     "coulomb_quadrupole_correction": ("cluster", "_quadrupole_adjoint", QD, ("cell",) + LISTS, "quadrupole_gradients", ("cell",), True, None),
+    "pair_scale_correction": ("pair_scale", "_adjoint", QD, ("pair_scales", "cell") + LISTS + ("minimum_image",), "quadrupole_gradients", ("cell",),
+                              True, None),
 }
 
 
 def _t(a):
     return torch.as_tensor(np.ascontiguousarray(a), device=DEV)
+
+
+def _pair_scales(i, j, dtype):
+    """One scale per slot, symmetric in (i, j) whatever the image; a padding slot gets a value that is not looked at."""
+    table = torch.tensor([0.0, 0.4, 0.8, 1.0, 0.4], dtype=dtype, device=DEV)
+    i, j = i.long(), j.long()
+    return table[(i * j + i + j) % 5].contiguous()
+
+
+def _row_of(nm):
+    return torch.arange(nm.shape[0], device=nm.device)[:, None].expand_as(nm)
 
 
 @functools.lru_cache(maxsize=None)
@@ -70,8 +86,12 @@ def inputs(tag):
     common = dict(cell=tc, alpha=torch.tensor([0.30, 0.36], dtype=dtype, device=DEV), batch_idx=tb, thole=0.39,
                   k_vectors=generate_k_vectors_ewald_summation(tc, 1.1), nx=MESH_DIMS[0], ny=MESH_DIMS[1], nz=MESH_DIMS[2])
     assert common["k_vectors"].shape[0] == 2 and 8 <= common["k_vectors"].shape[1] <= 400
-    batch = {"matrix": dict(atoms, **common, **dict(none, neighbor_matrix=nm.clone(), neighbor_matrix_shifts=sh.clone()), mask_value=n + 7),
-             "csr": dict(atoms, **common, **dict(none, neighbor_list=nl, neighbor_ptr=nptr, neighbor_shifts=ush), mask_value=-1)}
+    common["minimum_image"] = False
+    batch = {"matrix": dict(atoms, **common, **dict(none, neighbor_matrix=nm.clone(), neighbor_matrix_shifts=sh.clone()), mask_value=n + 7,
+                            pair_scales=_pair_scales(_row_of(nm), nm, dtype)),
+             "csr": dict(atoms, **common, **dict(none, neighbor_list=nl, neighbor_ptr=nptr, neighbor_shifts=ush), mask_value=-1,
+                         pair_scales=_pair_scales(nl[0], nl[1], dtype))}
+    assert {0.0, 0.4, 0.8, 1.0} == {round(float(v), 6) for v in batch["csr"]["pair_scales"].unique()}
     first = np.flatnonzero(bi == 0)
     d = np.linalg.norm(pos[first, None, :].astype(np.float64) - pos[None, first, :], axis=-1)
     rows = [np.flatnonzero((d[i] < RC) & (np.arange(len(first)) != i)) for i in range(len(first))]
@@ -82,6 +102,7 @@ def inputs(tag):
     cluster = dict({k: v[: len(first)].contiguous() for k, v in atoms.items()}, **none, cell=None, batch_idx=None, thole=0.39,
                    mask_value=len(first) + 3)
     cluster["neighbor_matrix"] = _t(cm)
+    cluster.update(pair_scales=_pair_scales(_row_of(cluster["neighbor_matrix"]), cluster["neighbor_matrix"], dtype), minimum_image=False)
     return dict(batch=batch, cluster=dict(matrix=cluster))
 
 
@@ -193,3 +214,55 @@ def test_refusals_come_from_the_table(name):
         with pytest.raises(NotImplementedError) as err:
             torch.autograd.grad(o.sum(), positions, retain_graph=True)
         assert f"alchemiops::_{name}: derivatives of the '{what}' output are second derivatives of the pair kernels" in str(err.value)
+
+
+def test_pair_scales_that_require_a_gradient_are_refused():
+    """The one refusal of `pair_scale_correction` that is not a row of the table: it is raised by the public function, before the op."""
+    for label, a in cases("pair_scale_correction"):
+        args = dict(a, pair_scales=a["pair_scales"].clone().requires_grad_(True))
+        with pytest.raises(NotImplementedError, match="pair_scales is not differentiable"):
+            call_public("pair_scale_correction", args, {})
+
+
+# ---- rotate_multipoles: its op is written out beside the table (two differentiable outputs, a frame table) -----------------------------------
+@pytest.mark.parametrize("tag", sorted(DTYPES))
+def test_rotate_multipoles_eager_matches_op_and_backward_matches_adjoint(tag):
+    from nvalchemiops import _eops
+    from nvalchemiops.interactions.electrostatics import frames as FR
+    from nvalchemiops.interactions.electrostatics import rotate_multipoles
+    from tests import test_local_frames_gpu as TLF
+
+    dtype = DTYPES[tag]
+    d = TLF._device_inputs(TLF._case("batch"), dtype)
+    fr = d["frames"]
+    tables = (fr.frame_atoms, fr.frame_kinds, fr.inverse_ptr, fr.inverse_slots)
+    op = torch.ops.alchemiops._rotate_multipoles
+    eager = FR._forward(d["pos"], d["mu"], d["quad"], d["cell"], d["batch"], fr.frame_atoms, fr.frame_kinds)
+    public = rotate_multipoles(d["pos"], d["mu"], d["quad"], fr, d["cell"], batch_idx=d["batch"])
+    direct = op(d["pos"], d["mu"], d["quad"], d["cell"], d["batch"], *tables)
+    for what, e, p, o in zip(("dipoles", "quadrupoles"), eager, public, direct):
+        same(e, o, f"rotate_multipoles {tag} {what}, eager against the op", True)
+        same(p, o, f"rotate_multipoles {tag} {what}, public against the op", True)
+        assert float(o.abs().max()) > 0
+    # an input that is None: an empty [0] tensor in its place, the other output unchanged
+    only = op(d["pos"], d["mu"], None, d["cell"], d["batch"], *tables)
+    assert tuple(only[1].shape) == (0,) and torch.equal(only[0], direct[0])
+    only = op(d["pos"], None, d["quad"], d["cell"], d["batch"], *tables)
+    assert tuple(only[0].shape) == (0,) and torch.equal(only[1], direct[1])
+    # the op's backward against the adjoint function, both outputs weighted, and each output alone
+    for g_mu, g_qd in ((d["w_mu"], d["w_q"]), (d["w_mu"], None), (None, d["w_q"])):
+        leaves = [d[k].clone().requires_grad_(True) for k in ("pos", "mu", "quad")]
+        out = op(*leaves, d["cell"], d["batch"], *tables)
+        used = [(o, g) for o, g in zip(out, (g_mu, g_qd)) if g is not None]
+        grads = torch.autograd.grad([o for o, _ in used], leaves, grad_outputs=[g for _, g in used], allow_unused=True)
+        ref = FR._adjoint(d["pos"], d["mu"], d["quad"], d["cell"], d["batch"], *tables, g_mu, g_qd)
+        for what, got, r, leaf in zip(("positions", "local_dipoles", "local_quadrupoles"), grads, ref, leaves):
+            assert r.dtype == torch.float64
+            if got is None:  # an output that was not used sends nothing to its own local input
+                assert float(r.abs().max()) == 0.0, what
+                continue
+            same(got, r.to(leaf.dtype), f"rotate_multipoles {tag} d/d{what}", True)
+    pos, cell = d["pos"].clone().requires_grad_(True), d["cell"].clone().requires_grad_(True)
+    with pytest.raises(NotImplementedError) as err:
+        op(pos, d["mu"], d["quad"], cell, d["batch"], *tables)[0].sum().backward()
+    assert "alchemiops::_rotate_multipoles: gradients w.r.t. cell are not provided by the local-frame rotation" in str(err.value)

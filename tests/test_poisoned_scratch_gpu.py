@@ -291,4 +291,7 @@ _take("math", TM, """spherical_harmonics_against_closed_forms harmonic_gradients
 _take("fold", TFS, """d4_copies_as_one_system_and_as_a_batch gaussian_copies_as_one_system_and_as_a_batch
       dipole_real_space_copies_as_one_system_and_as_a_batch ewald_real_space_virial_copies_as_one_system_and_as_a_batch
       charge_equilibration_copies_as_one_system_and_as_a_batch quadrupole_real_space_copies_as_one_system_and_as_a_batch
-      thole_dipole_correction_copies_as_one_system_and_as_a_batch induced_dipoles_copies_as_one_system_and_as_a_batch""")
+      thole_dipole_correction_copies_as_one_system_and_as_a_batch induced_dipoles_copies_as_one_system_and_as_a_batch
+      pair_scale_copies_as_one_system_and_as_a_batch pair_scale_minimum_image_copies_as_one_system_and_as_a_batch
+      local_frames_copies_as_one_system_and_as_a_batch cluster_corrections_periodic_copies_as_one_system_and_as_a_batch
+      cluster_induced_dipoles_copies_as_one_system_and_as_a_batch""")

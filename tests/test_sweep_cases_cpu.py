@@ -1,7 +1,8 @@
 """The conditions every case of tests/sweep_cases.py must meet before it is worth a GPU run, checked without a GPU from the float64
 restatements alone: the margin of every cutoff, the lifting rule and the float32 model of the three-body cases, the counts that make a rung
 sit on its boundary, the separation of every variant from its default, the coverage of the twelve seeds of each op, a bound on the cost,
-and the sensitivity of the reference-side numbers to four faults a kernel could have (DESIGN.md section 3.18 has the table)."""
+and the sensitivity of the reference-side numbers to four faults a kernel could have (DESIGN.md section 3.18 has the table).  Last section:
+the conditions of the cluster, pair-scale and local-frame sweeps of tests/test_sweep_cluster_frames_gpu.py."""
 import os
 import re
 import time
@@ -837,3 +838,130 @@ def test_pme_quadrupole_convergence_bars():
     d = W.pmeq_convergence()
     print("pme_quadrupole, order 6 on 32^3 against the explicit sum: " + ", ".join(f"{k} {v:.2e}" for k, v in d.items()))
     assert set(d) == set(W.QUADRUPOLE_NAMES) and all(0.0 < v < 1e-3 for v in d.values())
+
+
+# ---- cluster multipoles, scaled pairs, local frames ----------------------------------------------------------------------------------------------
+
+def _mirrored(i, j, S):
+    keys = {(int(a), int(b)) + tuple(int(x) for x in s) for a, b, s in zip(i, j, S)}
+    return all((b, a, -x, -y, -z) in keys for a, b, x, y, z in keys)
+
+
+@pytest.mark.parametrize("seed", W.SEEDS)
+@pytest.mark.parametrize("op", W.CLUSTER_OPS)
+def test_cluster_seed_meets_its_conditions(op, seed):
+    """Every stored distance at or above the 1.3 of tests/cluster_multipole_reference.py (but for the one coincident pair, at exactly 0), a
+    full list, symmetric scales of the four classes, minimum-image pairs at least 0.05 from a flip, and a matrix that holds all three kinds
+    of padding, a padding slot between live entries, and the entries in their order."""
+    from tests.cluster_multipole_reference import D_MIN
+
+    c = W.cluster_case("sweep", (op, seed))
+    i, j, S = c["entries"]
+    n = len(c["pos"])
+    assert W.CLUSTER_D_MIN == D_MIN and c["dtype"] == ("float64" if seed % 2 == 0 else "float32")
+    assert 1 <= len(c["sizes"]) <= 4 and set(c["sizes"]) <= set(W.CLUSTER_SIZES) | {0} and (0 in c["sizes"]) == (seed in W.EMPTY_SYSTEM_SEEDS)
+    assert c["periodic"] == (seed in W.CLUSTER_PERIODIC_SEEDS) and (c["cells"] is None) == (not c["periodic"])
+    r = W.entry_distances(c) if not c["minimum_image"] else np.linalg.norm(
+        np.einsum("ea,eab->eb", (lambda f: f - np.rint(f))(W.fractional_pair_vectors(c)), c["cells"][c["batch_idx"][i]]), axis=1)
+    live = np.ones(len(i), bool)
+    if c["coincident"] is not None:
+        a, b = c["coincident"]
+        live = ~(((i == a) & (j == b)) | ((i == b) & (j == a)))
+        assert int((~live).sum()) == 2 and float(r[~live].max()) == 0.0 and not c["periodic"]
+    assert float(r[live].min()) >= D_MIN and _mirrored(i, j, S)
+    if not c["periodic"]:
+        assert not S.any() and len(i) == sum(k * (k - 1) for k in c["sizes"]) and not c["flags"]["compute_virial"]
+    if c["minimum_image"]:
+        f = W.fractional_pair_vectors(c)
+        assert c["periodic"] and float(np.abs(f).max()) <= W.PS_IMAGE_MARGIN and bool(S.any()) and bool((np.rint(f) == 0).all())
+    if op == "pair_scale":
+        s = c["scales"]
+        by = {(int(a), int(b)) + tuple(int(x) for x in sh): v for a, b, sh, v in zip(i, j, S, s)}
+        assert all(by[(b, a, -x, -y, -z)] == v for (a, b, x, y, z), v in by.items())
+        assert (set(s.tolist()) == {1.0}) if c["zero"] else (set(s.tolist()) == {0.0, 0.4, 0.8, 1.0})
+        assert c["scale_dtype"] == ("float32" if seed in W.PS_F32_SCALE_SEEDS else "float64") and c["minimum_image"] == (seed in W.PS_MIN_IMAGE_SEEDS)
+    else:
+        zero = c["mu"] if op == "coulomb_dipole" else c["qd"]
+        assert (not zero.any()) == c["zero"]
+    nm, sh, val = W.padded_matrix(c["entries"], n, c.get("scales"))
+    ok = (nm >= 0) & (nm < n)
+    assert (nm == n).any() and (nm == -1).any() and (nm == n + 7).any()
+    assert np.array_equal(np.nonzero(ok)[0], i) and np.array_equal(nm[ok], j) and np.array_equal(sh[ok], S)
+    assert bool((~ok[:, :-1] & ok[:, 1:]).any()), "a padding slot between live entries"
+    if val is not None:
+        assert np.array_equal(val[ok], c["scales"]) and np.isnan(val[~ok]).all()
+    if c["perm"] is not None:
+        ci = W.cluster_interleaved(c)
+        assert len(c["sizes"]) >= 2 and bool((np.diff(ci["batch_idx"]) < 0).any()) and np.array_equal(ci["pos"], c["pos"][c["perm"]])
+
+
+@pytest.mark.parametrize("op", W.CLUSTER_OPS)
+def test_cluster_seeds_cover_what_they_are_meant_to(op):
+    cases = [W.cluster_case("sweep", (op, s)) for s in W.SEEDS]
+    alone = {k for c in cases if sum(c["flags"].values()) == 1 for k, v in c["flags"].items() if v}
+    assert alone == set(W.CLUSTER_FLAGS[op]), "each compute flag alone"
+    assert any(c["dtype"] == "float32" and sum(c["flags"].values()) == 1 and not (c["flags"]["compute_forces"] or c["flags"]["compute_virial"]) for c in cases)
+    assert {c["periodic"] for c in cases} == {True, False} and {n for c in cases for n in c["sizes"]} >= set(W.CLUSTER_SIZES)
+    assert all(cases[s]["periodic"] and cases[s]["perm"] is not None for s in W.INTERLEAVED_SEEDS) and any(cases[s]["periodic"] for s in W.EMPTY_SYSTEM_SEEDS)
+    if op == "pair_scale":
+        assert cases[W.PS_NO_DIPOLE_SEED]["no_dipoles"] and cases[W.PS_NO_QUADRUPOLE_SEED]["no_quadrupoles"] and cases[W.PS_COINCIDENT_SEED]["coincident"]
+        assert any(len(cases[s]["sizes"]) > 1 for s in W.PS_MIN_IMAGE_SEEDS)
+
+
+def test_pair_scale_ladder_case():
+    c = W.cluster_case("ps_ladder")
+    i, j, S = c["entries"]
+    f = W.fractional_pair_vectors(c)
+    red = f - np.rint(f)
+    r = np.linalg.norm(np.einsum("ea,eab->eb", red, c["cells"][c["batch_idx"][i]]), axis=1)
+    counts = np.bincount(i, minlength=len(c["pos"]))
+    assert c["sizes"] == (255, 256, 257, 1) and not S.any() and _mirrored(i, j, S) and bool((c["batch_idx"][i] == c["batch_idx"][j]).all())
+    assert float(r.min()) >= W.CLUSTER_D_MIN and float(np.abs(red).max()) <= W.PS_IMAGE_MARGIN and bool((np.rint(f) != 0).any())
+    assert counts.min() == 0 and counts.max() >= 9 and counts[-1] == 0
+    assert set(c["scales"].tolist()) == {0.0, 0.4, 0.8, 1.0}
+
+
+@pytest.mark.parametrize("seed", W.SEEDS)
+def test_frame_seed_meets_its_conditions(seed):
+    """Bond lengths in [0.9, 1.6], angles between frame vectors in [40, 140] degrees, Z_ONLY axes more than 0.06 from the switch, chiral triple
+    products above 0.2, under a cell every fractional component of a frame vector at least 0.05 from +-0.5, and the restatement's own change
+    under float32 rounding of its inputs at most 1e-7 of max|ref| per output (the figure tests/test_local_frames_gpu.py states)."""
+    from tests import layout_cases as LC
+    from tests import local_frames_reference as LR
+
+    c = W.cluster_case("frames", seed)
+    n = c["n"]
+    assert n == W.FRAME_TOTAL_BY_SEED[seed] and sum(c["sizes"]) == n and (0 in c["sizes"]) == (seed in W.FRAME_EMPTY_SEEDS)
+    cond = LC.frame_conditions(c["pos"], c["atoms"], c["kinds"], c["cells"], None if c["batch_idx"] is None else c["batch_idx"].long())
+    named = c["atoms"] >= 0
+    if bool(named.any()):
+        assert 0.9 <= cond["bond"][0] and cond["bond"][1] <= 1.6 and cond["z_only"] > W.FRAME_SWITCH_MARGIN and cond["chiral"] > 0.2 and cond["image"] <= 0.45, cond
+        if bool((named.sum(1) >= 2).any()):
+            assert 40.0 <= cond["angle"][0] and cond["angle"][1] <= 140.0, cond
+    if n >= 63:
+        owner = torch.arange(n)[:, None].expand(n, 3)
+        assert sorted(set(c["kinds"].tolist())) == list(range(6))
+        assert bool((c["atoms"][named] > owner[named]).any()) and bool((c["atoms"][named] < owner[named]).any()), "frame atoms above and below their owner"
+        chiral = (c["kinds"] == LR.Z_THEN_X) & (c["atoms"][:, 2] >= 0)
+        assert bool(chiral.any()) and bool(((c["kinds"] == LR.Z_THEN_X) & ~chiral).any())
+    if n >= 257:
+        assert bool(((c["atoms"][named].long() // 256) != (owner[named] // 256)).any()), "a frame atom in another block of 256"
+    if c["batch_idx"] is not None:
+        used = torch.where(named, c["atoms"].long(), torch.arange(n)[:, None].expand(n, 3))
+        assert bool((c["batch_idx"][used] == c["batch_idx"][:, None]).all())
+        assert (seed in W.FRAME_INTERLEAVED_SEEDS) == bool((torch.diff(c["batch_idx"]) < 0).any())
+    rnd = lambda x: None if x is None else x.float().double()  # noqa: E731
+    args = lambda f: (f(c["pos"]), f(c["mu"]), f(c["quad"]), c["atoms"], c["kinds"], f(c["w_mu"]), f(c["w_q"]))  # noqa: E731
+    kw = lambda f: dict(cell=f(c["cells"]), batch_idx=c["batch_idx"])  # noqa: E731
+    ref, low = LR.evaluate(*args(lambda x: x), **kw(lambda x: x)), LR.evaluate(*args(rnd), **kw(rnd))
+    for k, v in ref.items():
+        if v is not None and v.numel() and float(v.abs().max()) > 0:
+            assert float((low[k] - v).abs().max()) <= 1e-7 * float(v.abs().max()), (k, float((low[k] - v).abs().max()) / float(v.abs().max()))
+
+
+def test_frame_seeds_cover_what_they_are_meant_to():
+    cases = [W.cluster_case("frames", s) for s in W.SEEDS]
+    assert {c["n"] for c in cases} == set(W.FRAME_TOTALS) and {c["form"] for c in cases} == set(W.FRAME_FORMS)
+    assert cases[W.FRAME_NO_DIPOLE_SEED]["mu"] is None and cases[W.FRAME_NO_QUADRUPOLE_SEED]["quad"] is None
+    assert all(cases[s]["form"] == "batch" for s in W.FRAME_INTERLEAVED_SEEDS + W.FRAME_EMPTY_SEEDS)
+    assert {c["dtype"] for c in cases if c["form"] == "batch"} == {"float64", "float32"}
