@@ -674,6 +674,41 @@ int mi_pair_scale(const void* positions, const void* charges, const void* dipole
                   int max_neighbors, int mask_value, int minimum_image, int flags, double* energies, void* forces, double* charge_grads,
                   double* dipole_grads, double* quadrupole_grads, double* virial_partial, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Scaled, Thole-damped bonded pairs of point dipoles (csrc/dipole_scale.hip; driver: nvalchemiops/interactions/electrostatics/dipole_scale.py).
+ * Every stored entry e = (i, j, S) of a FULL list carries a direct scale s^d_e on its charge-dipole term and a mutual scale s^m_e on its
+ * dipole-dipole term (float64 streams laid out like idx_j; either may be NULL = all 1, not both; symmetric, which is not checked).  With
+ * A_q = q_j c_i - q_i c_j, c = mu . R, B1 = 1 / r^3, B2 = 3 / r^5 and l3, l5 the damping factors of mi_thole_dipole (1 when thole_a == 0, when
+ * either end has a <= 0 or NaN, and for E >= 50):
+ *     E_i = 1/2 sum_{row i} [(s^d_e - 1) l3 B1 A_q + (s^m_e - 1) (l3 B1 mu_i . mu_j - l5 B2 c_i c_j)]
+ * what has to be ADDED to mi_coulomb_dipole / mi_ewald_dipole_* (+ mi_thole_dipole) so that every listed pair carries s^d l on its
+ * charge-dipole and s^m l on its dipole-dipole term.  An entry with both scales 1 is skipped before any arithmetic.  polarizability may be
+ * NULL when thole_a == 0 (polarizability_grads are then zeros).  One group of 8 lanes per row, butterfly sums, no atomics: bit-reproducible.
+ * weights, flags (MI_DP_*, MI_DP_POLAR_GRAD included), outputs, list formats, padding, the r <= 1e-8 skip, minimum_image, the virial layout
+ * and the argument errors are those of mi_pair_scale.  scratch: mi_dipole_scale_scratch_bytes(n_atoms, dtype) bytes (8-word records +
+ * per-row virials), contents undefined.  virial_partial is [n_systems][mi_dipole_scale_blocks()][9]. */
+size_t mi_dipole_scale_scratch_bytes(int n_atoms, int dtype);
+int mi_dipole_scale_blocks(void);
+int mi_dipole_scale(const void* positions, const void* charges, const void* dipoles, const void* polarizability /*or NULL*/,
+                    const void* cell /*[n_systems,3,3] or NULL*/, const int32_t* batch_idx, const double* weights,
+                    const double* direct_scales /*or NULL*/, const double* mutual_scales /*or NULL*/, double thole_a, int n_atoms, int n_systems,
+                    int dtype, const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors, int mask_value,
+                    int minimum_image, int flags, double* energies, void* forces, double* charge_grads, double* dipole_grads,
+                    double* polarizability_grads, double* virial_partial, void* scratch, size_t scratch_bytes, void* stream);
+
+/* The mutual part of the same pairs as a stored operator beside the one of mi_induced_pair_tensors, over a bonded MATRIX list
+ * [n_atoms][max_neighbors] (n_slots = n_atoms * max_neighbors).  mi_scaled_dipole_tensors (once per geometry) stores, per slot,
+ *     tensors[0..5)[n_slots] = {(s^m - 1) l3 B1, (s^m - 1) l5 B2, R_x, R_y, R_z} (fp64) and neighbors[n_slots] = j
+ * with R the minimum image of r_j - r_i when a cell is given (reduced in fp64, rounded once to the positions dtype) and the bare difference
+ * when cell == NULL; padding, entries with r <= 1e-8, s^m == 1 and entries with a non-polarisable end (a <= 0 or NaN) hold zeros and the
+ * row's own index.  thole_a == 0: undamped.  mi_scaled_dipole_apply: y_i = y_in,i (or 0) + sum_row (c1 x_j - c2 (R . x_j) R), fp64, 8 lanes
+ * per row, no transcendental, no atomics, bit-reproducible; y is the y_in of mi_induced_apply.  x, y_in and y must not overlap. */
+int mi_scaled_dipole_tensor_words(void);
+int mi_scaled_dipole_tensors(const void* positions, const void* polarizability, const void* cell /*or NULL*/, const int32_t* batch_idx,
+                             const double* mutual_scales, double thole_a, int n_atoms, int n_systems, int dtype, const int32_t* idx_j,
+                             int max_neighbors, int mask_value, long long n_slots, double* tensors, int32_t* neighbors, void* stream);
+int mi_scaled_dipole_apply(const double* tensors, const int32_t* neighbors, const double* x, const double* y_in /*or NULL*/, int n_atoms,
+                           int max_neighbors, long long n_slots, double* y, void* stream);
+
 /* Charge equilibration (csrc/qeq.hip; driver: nvalchemiops/interactions/electrostatics/qeq.py): the real-space Hessian of the Gaussian-charge
  * electrostatic energy as a stored sparse operator over the caller's FULL list, its product, and the vector kernels of a batched projected
  * conjugate-gradient solve of  min_q sum chi_i q_i + 1/2 sum J_i q_i^2 + E_el(q),  sum_{i in s} q_i = Q_s.  All arithmetic is fp64; only the

@@ -191,7 +191,16 @@ def lib() -> ctypes.CDLL:
         # scaled bonded pairs of point multipoles (nvalchemiops/interactions/electrostatics/pair_scale.py)
         L.mi_pair_scale.restype = i
         L.mi_pair_scale.argtypes = [vp] * 8 + [i, i, i, vp, vp, vp, i, i, i, i] + [vp] * 7 + [sz, vp]
-        for name in ("mi_coulomb_dipole", "mi_coulomb_quadrupole", "mi_pair_scale"):
+        # scaled, Thole-damped bonded dipole pairs and their stored operator (nvalchemiops/interactions/electrostatics/dipole_scale.py)
+        L.mi_dipole_scale.restype = i
+        L.mi_dipole_scale.argtypes = [vp] * 9 + [dbl, i, i, i, vp, vp, vp, i, i, i, i] + [vp] * 7 + [sz, vp]
+        L.mi_scaled_dipole_tensor_words.restype = i
+        L.mi_scaled_dipole_tensor_words.argtypes = []
+        L.mi_scaled_dipole_tensors.restype = i
+        L.mi_scaled_dipole_tensors.argtypes = [vp] * 5 + [dbl, i, i, i, vp, i, i, ctypes.c_longlong, vp, vp, vp]
+        L.mi_scaled_dipole_apply.restype = i
+        L.mi_scaled_dipole_apply.argtypes = [vp] * 4 + [i, i, ctypes.c_longlong, vp, vp]
+        for name in ("mi_coulomb_dipole", "mi_coulomb_quadrupole", "mi_pair_scale", "mi_dipole_scale"):
             getattr(L, name + "_scratch_bytes").restype = sz
             getattr(L, name + "_scratch_bytes").argtypes = [i, i]
             getattr(L, name + "_blocks").restype = i

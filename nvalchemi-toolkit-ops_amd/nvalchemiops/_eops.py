@@ -1585,7 +1585,7 @@ gaussian_charge_correction_op = _op("_gaussian_charge_correction", _gaussian_fwd
 
 
 # =====================================================================================================================================
-# point multipoles: nine operator halves and the bonded-pair scaling, one forward / backward op pair each, built from one table
+# point multipoles: nine operator halves and the two bonded-pair scalings, one forward / backward op pair each, built from one table
 # =====================================================================================================================================
 # Outputs are always those of the public function (energies, forces, charge_gradients, dipole_gradients, the row's extra output, virial); the
 # ones not asked for are empty [0] tensors.  The energies are differentiable w.r.t. the row's first inputs: the backward op runs the forward
@@ -1636,6 +1636,9 @@ _MULTIPOLE_OPS = {
                                       "optional cell", ("cell",), _CL_NO_GRAD),
     "pair_scale_correction": ("pair_scale", "_forward", "_adjoint", _QD, f"Tensor pair_scales, Tensor? cell, {_LISTS}, bool minimum_image", _QG,
                               "optional cell", ("cell",), _CL_NO_GRAD),
+    "dipole_pair_scale_correction": ("dipole_scale", "_forward", "_adjoint", _TH,
+                                     f"Tensor? direct_scales, Tensor? mutual_scales, Tensor? cell, {_LISTS}, bool minimum_image, float thole", _PG,
+                                     "optional cell", ("cell",), _CL_NO_GRAD),
 }
 
 
@@ -1717,6 +1720,7 @@ pme_quadrupole_reciprocal_space_op, pme_quadrupole_recip_bwd_op = _MP["pme_quadr
 coulomb_dipole_correction_op, coulomb_dipole_bwd_op = _MP["coulomb_dipole_correction"]
 coulomb_quadrupole_correction_op, coulomb_quadrupole_bwd_op = _MP["coulomb_quadrupole_correction"]
 pair_scale_correction_op, pair_scale_bwd_op = _MP["pair_scale_correction"]
+dipole_pair_scale_correction_op, dipole_pair_scale_bwd_op = _MP["dipole_pair_scale_correction"]
 
 
 # =====================================================================================================================================
@@ -1796,7 +1800,7 @@ rotate_multipoles_op.register_fake(_rotate_fwd_fake)
 rotate_multipoles_op.register_autograd(_rotate_backward, setup_context=_rotate_setup)
 
 
-__all__ = ["pair_scale_correction_op", "pair_scale_bwd_op", "rotate_multipoles_op", "rotate_multipoles_bwd_op", "coulomb_dipole_correction_op", "coulomb_dipole_bwd_op", "coulomb_quadrupole_correction_op", "coulomb_quadrupole_bwd_op",
+__all__ = ["pair_scale_correction_op", "pair_scale_bwd_op", "dipole_pair_scale_correction_op", "dipole_pair_scale_bwd_op", "rotate_multipoles_op", "rotate_multipoles_bwd_op", "coulomb_dipole_correction_op", "coulomb_dipole_bwd_op", "coulomb_quadrupole_correction_op", "coulomb_quadrupole_bwd_op",
            "pme_quadrupole_reciprocal_space_op", "pme_quadrupole_recip_bwd_op",
            "ewald_quadrupole_real_space_op", "ewald_quadrupole_reciprocal_space_op", "ewald_quadrupole_real_bwd_op",
            "ewald_quadrupole_recip_bwd_op", "thole_dipole_correction_op", "thole_dipole_bwd_op", "pme_dipole_reciprocal_space_op", "pme_dipole_recip_bwd_op", "ewald_dipole_real_space_op", "ewald_dipole_reciprocal_space_op", "ewald_dipole_real_bwd_op", "ewald_dipole_recip_bwd_op",

@@ -9,11 +9,12 @@ from nvalchemiops.interactions.electrostatics.quadrupole import (ewald_quadrupol
 from nvalchemiops.interactions.electrostatics.pme_quadrupole import pme_quadrupole_correction, pme_quadrupole_reciprocal_space
 from nvalchemiops.interactions.electrostatics.gaussian import gaussian_charge_correction
 from nvalchemiops.interactions.electrostatics.induced import (InducedDipoleError, InducedDipoleResult, induced_dipoles,
-                                                              thole_induced_dipoles)
+                                                              scaled_induced_dipoles, thole_induced_dipoles)
 from nvalchemiops.interactions.electrostatics.thole import thole_dipole_correction
 from nvalchemiops.interactions.electrostatics.cluster import (cluster_induced_dipoles, coulomb_dipole_correction,
                                                               coulomb_quadrupole_correction)
 from nvalchemiops.interactions.electrostatics.pair_scale import BondedPairScales, bonded_pair_scales, pair_scale_correction
+from nvalchemiops.interactions.electrostatics.dipole_scale import PolarizationPairScales, dipole_pair_scale_correction
 from nvalchemiops.interactions.electrostatics.frames import (FRAME_BISECTOR, FRAME_NONE, FRAME_THREE_FOLD, FRAME_Z_BISECT, FRAME_Z_ONLY,
                                                              FRAME_Z_THEN_X, LocalFrames, multipole_frame_forces, rotate_multipoles)
 from nvalchemiops.interactions.electrostatics.k_vectors import generate_k_vectors_ewald_summation, generate_k_vectors_pme
@@ -38,5 +39,5 @@ __all__ = [
     "coulomb_dipole_correction", "coulomb_quadrupole_correction", "cluster_induced_dipoles",
     "LocalFrames", "rotate_multipoles", "multipole_frame_forces", "FRAME_NONE", "FRAME_Z_ONLY", "FRAME_Z_THEN_X", "FRAME_BISECTOR",
     "FRAME_Z_BISECT", "FRAME_THREE_FOLD",
-    "pair_scale_correction", "bonded_pair_scales", "BondedPairScales",
+    "pair_scale_correction", "bonded_pair_scales", "BondedPairScales", "dipole_pair_scale_correction", "PolarizationPairScales", "scaled_induced_dipoles",
 ]

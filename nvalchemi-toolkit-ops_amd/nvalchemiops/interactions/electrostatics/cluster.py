@@ -284,6 +284,9 @@ def cluster_induced_dipoles(positions: torch.Tensor, charges: torch.Tensor, pola
     is never read on the host); `batch_idx` [N] is required when it exceeds 1.  The systems of a batch converge, and are reported,
     separately.
 
+    `scaled_induced_dipoles` (without a cell) is this solve with scale factors on the bonded pairs: two bonded atoms with a >= r^3 / 2,
+    which this function refuses as not positive definite, solve there with a mutual scale of 0.
+
     Solver, `tolerance`, `max_iterations`, `check_interval`, `initial_dipoles` (warm start) and `InducedDipoleError` with both of its
     messages -- no convergence, and "not positive definite" when a search direction p with p.Hp <= 0 is met (the polarisation catastrophe
     of undamped point dipoles: two atoms at distance r are beyond it for a > r^3 / 2) -- are those of `induced_dipoles`.  All solver
@@ -299,12 +302,24 @@ def cluster_induced_dipoles(positions: torch.Tensor, charges: torch.Tensor, pola
 
     Out of scope: a cell (use `induced_dipoles`), anisotropic polarisabilities, per-pair Thole widths, AMOEBA's separate direct-field damping
     and polarisation groups, a cutoff switching function or reaction field."""
+    return _cluster_solve(positions, charges, polarizability, thole=thole, external_field=external_field, batch_idx=batch_idx,
+                          num_systems=num_systems, neighbor_list=neighbor_list, neighbor_ptr=neighbor_ptr, neighbor_matrix=neighbor_matrix,
+                          mask_value=mask_value, tolerance=tolerance, max_iterations=max_iterations, check_interval=check_interval,
+                          initial_dipoles=initial_dipoles, return_info=return_info)
+
+
+def _cluster_solve(positions, charges, polarizability, *, thole=None, external_field=None, batch_idx=None, num_systems=None, neighbor_list=None,
+                   neighbor_ptr=None, neighbor_matrix=None, mask_value=None, tolerance=1e-8, max_iterations=200, check_interval=4,
+                   initial_dipoles=None, return_info=False, scaled_pairs=None):
+    """What `cluster_induced_dipoles` and, with `scaled_pairs`, `scaled_induced_dipoles` run."""
     if C.tracing():
         raise NotImplementedError("cluster_induced_dipoles cannot be traced by torch.compile: the solve iterates until a device-side "
                                   "convergence flag is set.  Call it outside the compiled region (torch.compiler.disable).")
     nsys = _check_solve(positions, charges, polarizability, external_field, batch_idx, num_systems, neighbor_list, neighbor_ptr, neighbor_matrix,
                         tolerance, max_iterations, check_interval, initial_dipoles, thole)
     n, dev, dt = positions.shape[0], positions.device, positions.dtype
+    if scaled_pairs is not None:
+        I.DS.check_scaled_pairs(scaled_pairs, n)
     if mask_value is None:
         mask_value = n
     per_atom_polar = isinstance(polarizability, torch.Tensor) and polarizability.dim() > 0
@@ -315,7 +330,7 @@ def cluster_induced_dipoles(positions: torch.Tensor, charges: torch.Tensor, pola
     with torch.cuda.device(dev):
         polar = TH._polar_tensor(polarizability, n, dt, dev)
         lists = (neighbor_list, neighbor_ptr, None, neighbor_matrix, None)
-        op = I._Operator(positions, polar, None, batch_idx, nsys, lists, mask_value, None, None, None, None, None, None, None, None, thole)
+        op = I._Operator(positions, polar, None, batch_idx, nsys, lists, mask_value, None, None, None, None, None, None, None, None, thole, scaled_pairs)
         op.name = "cluster_induced_dipoles"
         return I._run(op, positions, charges, polar, external_field, lists, int(mask_value), (float(tolerance), int(max_iterations),
                                                                                                int(check_interval)), initial_dipoles, return_info)

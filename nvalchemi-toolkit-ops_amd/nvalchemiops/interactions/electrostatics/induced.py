@@ -19,6 +19,7 @@ damped coefficients in the same layout, and everything after the set-up is the s
 """
 from __future__ import annotations
 
+import inspect
 from collections import namedtuple
 
 import torch
@@ -27,6 +28,7 @@ from nvalchemiops import _capi as C
 from nvalchemiops.interactions.electrostatics import _multipoles as M
 from nvalchemiops.interactions.electrostatics import _pairs as P
 from nvalchemiops.interactions.electrostatics import dipole as D
+from nvalchemiops.interactions.electrostatics import dipole_scale as DS
 from nvalchemiops.interactions.electrostatics import pme_dipole as PD
 from nvalchemiops.interactions.electrostatics import thole as TH
 
@@ -100,7 +102,7 @@ class _Operator:
     name = "induced_dipoles"  # the public function in error messages
 
     def __init__(self, positions, polar, cell, batch_idx, nsys, lists, mask_value, reciprocal, alpha, mesh_dimensions, mesh_spacing, spline_order,
-                 k_vectors, k_cutoff, accuracy, thole=None):
+                 k_vectors, k_cutoff, accuracy, thole=None, scaled_pairs=None):
         dt, dev, n = positions.dtype, positions.device, positions.shape[0]
         self.n, self.nsys, self.dt, self.dev = n, nsys, dt, dev
         self.pos = positions.detach().contiguous()
@@ -122,6 +124,8 @@ class _Operator:
         self.diag, self.precond = torch.empty(n, dtype=F64, device=dev), torch.empty(n, dtype=F64, device=dev)
         self.mask_value = int(mask_value)
         self.pair_tensors()
+        # the bonded pairs of `scaled_induced_dipoles`: a second small stored operator whose product is handed to `mi_induced_apply` as y_in
+        self.scaled = None if scaled_pairs is None else DS.ScaledOperator(scaled_pairs, self.pos, self.polar, self.cells, self.bi, nsys, self.thole)
         self.mask = (self.polar > 0).to(F64).unsqueeze(1)  # the projector onto the polarisable atoms
         zq, zmu = torch.zeros(n, dtype=dt, device=dev), torch.zeros((n, 3), dtype=dt, device=dev)
         if reciprocal == "pme":  # launch tensors of the reciprocal call, made once: only the dipoles change between iterations
@@ -194,6 +198,8 @@ class _Operator:
 
     def apply(self, x, y_in=None, partial=None):
         """y = y_in + x / a + T_real x (`mi_induced_apply`), and the per-system block partials of x . y when asked for."""
+        if self.scaled is not None:
+            y_in = self.scaled.apply(x, y_in)
         y = torch.empty((self.n, 3), dtype=F64, device=self.dev)
         rc = C.lib().mi_induced_apply(C.ptr(self.tensors), C.ptr(self.nbr), C.ptr(self.diag), C.ptr(x), C.ptr(y_in), C.ptr(self.bi), self.n,
                                       self.nsys, C.ptr(self.nptr), int(self.m), self.slots, C.ptr(y), C.ptr(partial), C.stream_of(x))
@@ -234,6 +240,8 @@ class _Operator:
             if self.thole is not None:
                 g = g + TH.thole_dipole_correction(self.pos, q, mu0, self.polar, self.cells, thole=self.thole, mask_value=mask_value,
                                                    batch_idx=self.batch_idx, compute_dipole_gradients=True, **kw)[1].to(F64)
+            if self.scaled is not None and self.scaled.direct is not None:  # the direct scales on the (damped) charge field
+                g = g + _scaled_energy(self, self.pos, q, mu0, self.polar, compute_dipole_gradients=True)[1].to(F64)
         b = -g if field is None else field.detach().to(F64) - g
         return (b * self.mask).contiguous()
 
@@ -297,12 +305,23 @@ def _info(state):
     return state[:, 3].to(torch.int64), torch.where(bb > 0, torch.sqrt(rr / torch.where(bb > 0, bb, torch.ones_like(bb))), torch.zeros_like(rr))
 
 
+def _scaled_energy(op: _Operator, positions, charges, dipoles, polar, **compute):
+    """`dipole_pair_scale_correction` over the bonded pairs of the solve: minimum images with a cell, bare differences without one."""
+    sp, dt = op.scaled, positions.dtype
+    return DS.dipole_pair_scale_correction(positions, charges.to(dt), dipoles.to(dt), sp.direct, sp.mutual, op.cells,
+                                           polarizability=polar.to(dt), thole=op.thole, neighbor_matrix=sp.matrix, mask_value=op.n,
+                                           batch_idx=op.batch_idx if op.cells is not None else None, minimum_image=op.cells is not None,
+                                           **compute)
+
+
 def _thole_energy(op: _Operator, positions, charges, dipoles, polar, lists, mask_value):
-    """Total E_thole(charges, dipoles) of a damped solve from the differentiable public function (also w.r.t. the polarisabilities)."""
+    """Total E_thole(charges, dipoles) of a damped solve from the differentiable public function (also w.r.t. the polarisabilities); with
+    `scaled_pairs`, plus their term, which depends on the polarisabilities through the same damping."""
     kw = dict(zip(("neighbor_list", "neighbor_ptr", "neighbor_shifts", "neighbor_matrix", "neighbor_matrix_shifts"), lists))
     dt = positions.dtype
-    return TH.thole_dipole_correction(positions, charges.to(dt), dipoles.to(dt), polar.to(dt), op.cells, thole=op.thole, batch_idx=op.batch_idx,
-                                      mask_value=mask_value, **kw).sum()
+    e = TH.thole_dipole_correction(positions, charges.to(dt), dipoles.to(dt), polar.to(dt), op.cells, thole=op.thole, batch_idx=op.batch_idx,
+                                   mask_value=mask_value, **kw).sum()
+    return e if op.scaled is None else e + _scaled_energy(op, positions, charges, dipoles, polar).sum()
 
 
 def _dipole_energy(op: _Operator, positions, charges, dipoles, lists, mask_value, polar=None):
@@ -321,7 +340,7 @@ def _dipole_energy(op: _Operator, positions, charges, dipoles, lists, mask_value
         e = D.ewald_dipole_correction(positions, q, mu, op.cells, alpha=op.alpha, k_vectors=op.kv, batch_idx=op.batch_idx, mask_value=mask_value,
                                       **kw).sum()
     if op.thole is None:
-        return e
+        return e if op.scaled is None else e + _scaled_energy(op, positions, charges, dipoles, op.polar).sum()
     return e + _thole_energy(op, positions, charges, dipoles, op.polar if polar is None else polar, lists, mask_value)
 
 
@@ -426,7 +445,7 @@ def induced_dipoles(positions: torch.Tensor, charges: torch.Tensor, polarizabili
     torch.compile: the solve has a data-dependent trip count.  CPU tensors raise NativeLibraryError: there is no fallback.
 
     These are undamped point dipoles.  `thole_induced_dipoles` is the same solve with exponential Thole damping, which keeps H positive
-    definite at the distances of bonded atoms.
+    definite at the distances of bonded atoms; `scaled_induced_dipoles` is either solve with scale factors on the bonded pairs.
 
     Out of scope: anisotropic polarisabilities, clusters without a cell, quadrupoles, a cell gradient, an extended-Lagrangian or predictor
     scheme.  A differently damped permanent field can be passed through `external_field` with zero charges; the field of permanent quadrupoles
@@ -462,6 +481,40 @@ def thole_induced_dipoles(positions: torch.Tensor, charges: torch.Tensor, polari
                   k_cutoff, accuracy, tolerance, max_iterations, check_interval, initial_dipoles, return_info)
 
 
+def scaled_induced_dipoles(positions: torch.Tensor, charges: torch.Tensor, polarizability, cell: torch.Tensor | None = None, *,
+                           scaled_pairs: DS.PolarizationPairScales, thole: float | None = None, **solver_arguments):
+    """The induced-dipole solves with scale factors on the bonded pairs of the model.  With a cell this is `thole_induced_dipoles`
+    (`thole=None`: `induced_dipoles`), without one `cluster_induced_dipoles`; `solver_arguments` are the keywords of that function (lists,
+    external_field, batch_idx, tolerance, return_info, ...) with their meanings, defaults, errors and return values.  Those three keep their
+    argument lists as they are, as `induced_dipoles` did when the damped solve became a function of its own.
+
+    `scaled_pairs=PolarizationPairScales(neighbor_matrix, direct_scales, mutual_scales)` (matrix format, as `bonded_pair_scales` produces it;
+    its docstring has the recipe from a topology) gives every listed pair its direct and mutual factor: the energy of the solve gains
+    `dipole_pair_scale_correction` over that list -- minimum images of the entries with a cell, bare differences without one, Thole-damped
+    when `thole` is given -- so H gains a second small stored operator (`mi_scaled_dipole_tensors` once, one `mi_scaled_dipole_apply` per
+    product, its output the `y_in` of `mi_induced_apply`), b the scaled damped direct field, and the polarisation energy, the stationarity
+    relation and the implicit gradients (dE/da included when damped) that term.  The returned dipoles make the `dipole_grads` of the
+    existing corrections plus those of `dipole_pair_scale_correction`, plus mu / a - F, vanish; the forces of a step are those corrections
+    plus `dipole_pair_scale_correction(compute_forces=True)` at the returned dipoles.  Mutual scales of 0 on 1-2 / 1-3 pairs keep H positive
+    definite where undamped bonded dipoles are not: two atoms at distance d with a >= d^3 / 2, which `cluster_induced_dipoles` refuses as
+    not positive definite, solve.  With all scales 1 the dipoles are bit-identical to those of the unscaled function (reciprocal="ewald" or
+    no cell).
+
+    Out of scope: CSR bonded lists, per-pair Thole widths, separate p / d dipole sets, dE/ds."""
+    if cell is None:
+        from nvalchemiops.interactions.electrostatics import cluster as CL
+
+        return CL._cluster_solve(positions, charges, polarizability, thole=thole, scaled_pairs=scaled_pairs, **solver_arguments)
+    order = ("external_field", "batch_idx", "neighbor_list", "neighbor_ptr", "neighbor_shifts", "neighbor_matrix", "neighbor_matrix_shifts",
+             "mask_value", "reciprocal", "alpha", "mesh_dimensions", "mesh_spacing", "spline_order", "k_vectors", "k_cutoff", "accuracy",
+             "tolerance", "max_iterations", "check_interval", "initial_dipoles", "return_info")
+    unknown = sorted(set(solver_arguments) - set(order))
+    if unknown:
+        raise TypeError(f"scaled_induced_dipoles got unexpected keyword arguments {unknown}: with a cell it takes those of thole_induced_dipoles")
+    defaults = {k: v.default for k, v in inspect.signature(induced_dipoles).parameters.items()}
+    return _solve(thole, positions, charges, polarizability, cell, *[solver_arguments.get(k, defaults[k]) for k in order], scaled_pairs)
+
+
 def _empty_result(nsys, dt, dev, return_info):
     empty = torch.zeros((0, 3), dtype=dt, device=dev)
     zeros = torch.zeros(nsys, dtype=dt, device=dev)
@@ -487,7 +540,7 @@ def _run(op: _Operator, positions, charges, polar, external_field, lists, mask_v
 
 def _solve(thole, positions, charges, polarizability, cell, external_field, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts,
            neighbor_matrix, neighbor_matrix_shifts, mask_value, reciprocal, alpha, mesh_dimensions, mesh_spacing, spline_order, k_vectors, k_cutoff,
-           accuracy, tolerance, max_iterations, check_interval, initial_dipoles, return_info):
+           accuracy, tolerance, max_iterations, check_interval, initial_dipoles, return_info, scaled_pairs=None):
     """What `induced_dipoles` (thole None) and `thole_induced_dipoles` run."""
     if C.tracing():
         raise NotImplementedError("induced_dipoles cannot be traced by torch.compile: the solve iterates until a device-side convergence "
@@ -496,6 +549,8 @@ def _solve(thole, positions, charges, polarizability, cell, external_field, batc
                   neighbor_matrix_shifts, reciprocal, alpha, mesh_dimensions, mesh_spacing, spline_order, k_vectors, k_cutoff, tolerance,
                   max_iterations, check_interval, initial_dipoles, thole)
     n, dev, dt = positions.shape[0], positions.device, positions.dtype
+    if scaled_pairs is not None:
+        DS.check_scaled_pairs(scaled_pairs, n)
     if mask_value is None:
         mask_value = n
     per_atom_polar = isinstance(polarizability, torch.Tensor) and polarizability.dim() > 0
@@ -508,9 +563,9 @@ def _solve(thole, positions, charges, polarizability, cell, external_field, batc
                  else torch.full((n,), float(polarizability), dtype=dt, device=dev))
         lists = (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
         op = _Operator(positions, polar, cell, batch_idx, nsys, lists, mask_value, reciprocal, alpha, mesh_dimensions, mesh_spacing, spline_order,
-                       k_vectors, k_cutoff, accuracy, thole)
+                       k_vectors, k_cutoff, accuracy, thole, scaled_pairs)
         return _run(op, positions, charges, polar, external_field, lists, int(mask_value),
                     (float(tolerance), int(max_iterations), int(check_interval)), initial_dipoles, return_info)
 
 
-__all__ = ["induced_dipoles", "thole_induced_dipoles", "InducedDipoleError", "InducedDipoleResult"]
+__all__ = ["induced_dipoles", "thole_induced_dipoles", "scaled_induced_dipoles", "InducedDipoleError", "InducedDipoleResult"]

@@ -153,9 +153,9 @@ def pair_scale_correction(positions: torch.Tensor, charges: torch.Tensor, dipole
     Energies are differentiable once w.r.t. positions, charges, dipoles and quadrupoles, for any upstream gradient on the per-atom energies
     (the same kernel runs as its own adjoint: an entry weighs (g_i + g_j) / 2 . (s_e - 1)); the call then goes through the
     `alchemiops::_pair_scale_correction` op, as it does under `torch.compile`.  Differentiating the explicit forces, gradients or virial
-    raises NotImplementedError, and so does a gradient w.r.t. cell: use `compute_virial`.  Out of scope: scale factors inside the stored mutual
-    operator of `induced_dipoles`, Thole-damped scaled pairs, polarisation groups, dE/ds.  CPU tensors raise NativeLibraryError: there is no
-    fallback."""
+    raises NotImplementedError, and so does a gradient w.r.t. cell: use `compute_virial`.  Separate direct and mutual factors and Thole-damped
+    scaled pairs are `dipole_pair_scale_correction`; the scaled mutual operator of `induced_dipoles` and its
+    siblings is `scaled_induced_dipoles` (polarisation groups on the direct field are direct scales there).  Out of scope: dE/ds.  CPU tensors raise NativeLibraryError: there is no fallback."""
     M.check_positions_and_format(positions, neighbor_list, neighbor_matrix)
     n = positions.shape[0]
     dipoles = Q._dipoles_or_zeros(positions, dipoles)
