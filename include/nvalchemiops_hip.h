@@ -1249,6 +1249,53 @@ int mi_frame_gather(const double* records, const int32_t* inverse_ptr, const int
 int mi_frame_blocks(void);
 int mi_frame_block_threads(void);
 
+/* Van der Waals pair potentials between reduced sites (csrc/vdw.hip; driver: nvalchemiops/interactions/vdw/pair.py): Halgren's buffered 14-7
+ * and Lennard-Jones over the stored entries (i, j, S) of a FULL (symmetric) list -- padded matrix (neighbor_ptr == NULL; entries equal to
+ * mask_value or outside [0, n_atoms) are padding) or CSR.  With d = site_j - site_i + S . cell, r = |d|, rho = r / R_ij:
+ *     energies[i] = 1/2 sum_{entries of row i} s_e T(r) U_ij(r)
+ *     MI_VDW_BUFFERED_14_7   U = eps_ij ((1 + delta) / (rho + delta))^7 ((1 + gamma) / (rho^7 + gamma) - 2)
+ *     MI_VDW_LENNARD_JONES   U = eps_ij (rho^-12 - 2 rho^-6)                  (delta, gamma not read)
+ * radii are minimum-energy distances (R_min, not sigma) for both kinds: U(R_ij) = -eps_ij.  Combining rules: R_ij = (R_i + R_j) / 2,
+ * sqrt(R_i R_j) or (R_i^3 + R_j^3) / (R_i^2 + R_j^2); eps_ij = sqrt(eps_i eps_j) or 4 eps_i eps_j / (sqrt(eps_i) + sqrt(eps_j))^2.  An atom
+ * with R <= 0, eps <= 0 or NaN has no site: its entries are skipped from both ends.  T = 1 - 10 t^3 + 15 t^4 - 6 t^5 with
+ * t = (r - taper_on) / (cutoff - taper_on) for r > taper_on (taper_on < 0: plain truncation).  Entries with r^2 >= cutoff^2 or r <= 1e-8
+ * contribute nothing.  pair_scales (NULL: ones): s_e, one value per slot of idx_j, float32 or float64 (pair_scales_dtype), symmetric.
+ * Sites: parent == NULL: sites are atoms.  Otherwise parent [n_atoms] (own index or outside [0, n_atoms): not reduced), reduction [n_atoms]
+ * (positions dtype) and the inverse CSR child_ptr [n_atoms + 1] / child_idx [n_children] (children of every atom, ascending):
+ * site_i = r_i - (1 - reduction_i) (r_i - r_p), r_i - r_p the minimum image when a cell is given (the site stays at the atom's own image).  The list is the caller's atom list; the cutoff
+ * applies to site distances.  Pair vector and r^2 in the positions dtype, everything else fp64; the row owner writes every output (no
+ * atomics, deterministic).  weights [n_atoms] float64 or NULL (all ones): entry weight w = (g_i + g_j) / 2 -- the outputs are then the
+ * derivatives of L = sum_i g_i energies[i]:
+ *   MI_VDW_FORCES        forces [n_atoms][3] (positions dtype) = -dL/dr on ATOMS: atom a receives reduction_a F_a + sum_children (1 - reduction_c) F_c
+ *                        of the site forces F_i = sum_row w s (T U)' d / r
+ *   MI_VDW_RADIUS_GRAD   radius_grads [n_atoms] float64  = dL/dR_i
+ *   MI_VDW_EPSILON_GRAD  epsilon_grads [n_atoms] float64 = dL/deps_i
+ *   MI_VDW_VIRIAL        system_partial [n_systems][mi_vdw_blocks()][mi_vdw_row_words()] float64 = block partials of
+ *                        -1/2 sum_entries w s (T U)' d_a d_b / r, {xx, yy, zz, xy, xz, yz}; the caller sums the block dimension (needs a cell)
+ * energies may be NULL (adjoint use).  cell NULL: non-periodic, unit_shifts must be NULL too.  unit_shifts NULL with a cell: all zero.
+ * scratch: mi_vdw_scratch_bytes(n_atoms, dtype, with_sites) bytes (records, per-row virial words, fp64 site forces), contents undefined. */
+#define MI_VDW_BUFFERED_14_7 0
+#define MI_VDW_LENNARD_JONES 1
+#define MI_VDW_RADIUS_ARITHMETIC 0
+#define MI_VDW_RADIUS_GEOMETRIC 1
+#define MI_VDW_RADIUS_CUBIC_MEAN 2
+#define MI_VDW_EPSILON_GEOMETRIC 0
+#define MI_VDW_EPSILON_HHG 1
+#define MI_VDW_FORCES 1
+#define MI_VDW_RADIUS_GRAD 2
+#define MI_VDW_EPSILON_GRAD 4
+#define MI_VDW_VIRIAL 8
+size_t mi_vdw_scratch_bytes(int n_atoms, int dtype, int with_sites);
+int mi_vdw_blocks(void);
+int mi_vdw_row_words(void);
+int mi_vdw(const void* positions, const void* radii, const void* epsilons, const void* cell /*[n_systems,3,3] or NULL*/, const int32_t* batch_idx,
+           const double* weights, const int32_t* parent, const void* reduction, const int32_t* child_ptr, const int32_t* child_idx,
+           long long n_children, const void* pair_scales, int pair_scales_dtype, int n_atoms, int n_systems, int dtype, int kind,
+           int radius_rule, int epsilon_rule, double delta, double gamma, double cutoff, double taper_on, const int32_t* idx_j,
+           const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors, int mask_value, int flags, double* energies,
+           void* forces, double* radius_grads, double* epsilon_grads, double* system_partial, void* scratch, size_t scratch_bytes,
+           void* stream);
+
 /* ---- multi-GPU: the one collective of the path (csrc/comm.cpp) ------------------------------------------------------------
  * The reference has no multi-GPU code; the path shards at SYSTEM granularity -- no pair crosses systems
  * (batch_cell_list.py:448-457, dftd3.py:823,1126, spline.py:809) -- so every rank runs the kernels above on its own contiguous range of

@@ -45,6 +45,9 @@ SOURCES = {
     "dft.hip": [],  # dense DFT of any mesh size: the transform of last resort behind the self-tested hipFFT plans
     "calib.hip": [],
     "frames.hip": [],  # local-frame multipoles (mi_frame_*): rotation to the laboratory frame, its adjoint and the torque-force gather, all fp64
+    # van der Waals pair potentials between reduced sites (mi_vdw): buffered 14-7 and Lennard-Jones, fp64 pair math; the float32 pair vector
+    # is formed with scalar ops only, as in dipole_scale.hip
+    "vdw.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "multipole.hip": [],  # spherical harmonics / Gaussian multipole basis (nvalchemiops.math): fp64 elementwise kernels
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]

@@ -264,6 +264,14 @@ def lib() -> ctypes.CDLL:
         for name in ("mi_frame_blocks", "mi_frame_block_threads"):
             getattr(L, name).restype = i
             getattr(L, name).argtypes = []
+        # van der Waals pair potentials between reduced sites (nvalchemiops/interactions/vdw/pair.py)
+        L.mi_vdw.restype = i
+        L.mi_vdw.argtypes = [vp] * 10 + [ll, vp, i, i, i, i, i, i, i, dbl, dbl, dbl, dbl, vp, vp, vp, i, i, i] + [vp] * 6 + [sz, vp]
+        L.mi_vdw_scratch_bytes.restype = sz
+        L.mi_vdw_scratch_bytes.argtypes = [i, i, i]
+        for name in ("mi_vdw_blocks", "mi_vdw_row_words"):
+            getattr(L, name).restype = i
+            getattr(L, name).argtypes = []
         _LIB = L
     return _LIB
 

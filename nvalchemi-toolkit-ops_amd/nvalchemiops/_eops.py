@@ -1800,7 +1800,91 @@ rotate_multipoles_op.register_fake(_rotate_fwd_fake)
 rotate_multipoles_op.register_autograd(_rotate_backward, setup_context=_rotate_setup)
 
 
-__all__ = ["pair_scale_correction_op", "pair_scale_bwd_op", "dipole_pair_scale_correction_op", "dipole_pair_scale_bwd_op", "rotate_multipoles_op", "rotate_multipoles_bwd_op", "coulomb_dipole_correction_op", "coulomb_dipole_bwd_op", "coulomb_quadrupole_correction_op", "coulomb_quadrupole_bwd_op",
+# =====================================================================================================================================
+# van der Waals pair potentials (buffered 14-7, Lennard-Jones): one forward / backward op pair per kind, written as the Gaussian op above
+# =====================================================================================================================================
+# Outputs are always the five of the public functions; the ones not asked for are empty [0] tensors.  The energies are differentiable w.r.t.
+# positions, radii and epsilons: the backward op runs the forward kernels with the incoming gradient as per-atom weights.  The site tables,
+# the pair scales and the cell have no gradient (the virial is the strain derivative).
+_VDW_OUTPUTS = ("energies", "forces", "radius_gradients", "epsilon_gradients", "virial")
+_VDW_TENSORS = 15  # positions ... neighbor_matrix_shifts
+
+
+def _make_vdw_ops(kind: int, name: str):
+    fwd_name, bwd_name = f"{_NS}::_{name}", f"nvalchemiops::{name}_backward"
+
+    def fwd(positions: Tensor, radii: Tensor, epsilons: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor], parent: Optional[Tensor],
+            reduction: Optional[Tensor], child_ptr: Optional[Tensor], child_idx: Optional[Tensor], pair_scales: Optional[Tensor],
+            neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor], neighbor_matrix: Optional[Tensor],
+            neighbor_matrix_shifts: Optional[Tensor], mask_value: int, cutoff: float, taper: float, delta: float, gamma: float, radius_rule: int,
+            epsilon_rule: int, compute_forces: bool, compute_radius_gradients: bool, compute_epsilon_gradients: bool,
+            compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+        from nvalchemiops.interactions.vdw.pair import _forward
+
+        out = _forward(kind, positions, radii, epsilons, cell, batch_idx, parent, reduction, child_ptr, child_idx, pair_scales, neighbor_list,
+                       neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, int(mask_value), cutoff, taper, delta, gamma,
+                       int(radius_rule), int(epsilon_rule), compute_forces, compute_radius_gradients, compute_epsilon_gradients, compute_virial)
+        return tuple(positions.new_empty((0,)) if o is None else o for o in out)
+
+    def fwd_fake(positions, radii, epsilons, cell, batch_idx, parent, reduction, child_ptr, child_idx, pair_scales, neighbor_list, neighbor_ptr,
+                 neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, mask_value, cutoff, taper, delta, gamma, radius_rule, epsilon_rule,
+                 compute_forces, compute_radius_gradients, compute_epsilon_gradients, compute_virial):
+        n = positions.shape[0]
+        nsys = cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1
+        empty = lambda: positions.new_empty((0,))  # noqa: E731
+        return (positions.new_empty((n,)), positions.new_empty((n, 3)) if compute_forces else empty(),
+                positions.new_empty((n,)) if compute_radius_gradients else empty(), positions.new_empty((n,)) if compute_epsilon_gradients else empty(),
+                positions.new_empty((nsys, 3, 3)) if compute_virial else empty())
+
+    def bwd(positions: Tensor, radii: Tensor, epsilons: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor], parent: Optional[Tensor],
+            reduction: Optional[Tensor], child_ptr: Optional[Tensor], child_idx: Optional[Tensor], pair_scales: Optional[Tensor],
+            neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor], neighbor_matrix: Optional[Tensor],
+            neighbor_matrix_shifts: Optional[Tensor], mask_value: int, cutoff: float, taper: float, delta: float, gamma: float, radius_rule: int,
+            epsilon_rule: int, grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor]:
+        """Float64 (dL/dpositions, dL/dradii, dL/depsilons) for L = sum_i g_i E_i."""
+        from nvalchemiops.interactions.vdw.pair import _adjoint
+
+        return _adjoint(kind, positions, radii, epsilons, cell, batch_idx, parent, reduction, child_ptr, child_idx, pair_scales, neighbor_list,
+                        neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, int(mask_value), cutoff, taper, delta, gamma,
+                        int(radius_rule), int(epsilon_rule), grad_energies)
+
+    def bwd_fake(positions, *rest):
+        n, f64 = positions.shape[0], dict(dtype=torch.float64)
+        return positions.new_empty((n, 3), **f64), positions.new_empty((n,), **f64), positions.new_empty((n,), **f64)
+
+    bwd_op = torch.library.custom_op(bwd_name, bwd, mutates_args=())
+    bwd_op.register_fake(bwd_fake)
+    bwd_op.register_autograd(lambda ctx, *g: (_ for _ in ()).throw(NotImplementedError(_SECOND_ORDER.format(op=bwd_name, what="gradient"))),
+                             setup_context=lambda ctx, inputs, output: None)
+
+    def setup(ctx, inputs, output):
+        ctx.save_for_backward(*inputs[:_VDW_TENSORS])
+        ctx.model = inputs[_VDW_TENSORS:_VDW_TENSORS + 7]
+        ctx.set_materialize_grads(False)
+
+    def backward(ctx, g_e, *g_explicit):
+        for what, g in zip(_VDW_OUTPUTS[1:], g_explicit):
+            if g is not None:
+                raise NotImplementedError(_SECOND_ORDER.format(op=fwd_name, what=what))
+        need = ctx.needs_input_grad
+        if g_e is None:
+            return (None,) * len(need)
+        saved = ctx.saved_tensors
+        mask, cutoff, taper, delta, gamma, rrule, erule = ctx.model
+        gpos, gr, ge = bwd_op(*saved, int(mask), float(cutoff), float(taper), float(delta), float(gamma), int(rrule), int(erule), g_e)
+        return (gpos.to(saved[0].dtype) if need[0] else None, gr.to(saved[1].dtype) if need[1] else None,
+                ge.to(saved[2].dtype) if need[2] else None) + (None,) * (len(need) - 3)
+
+    return _op(f"_{name}", fwd, fwd_fake, backward, setup), bwd_op
+
+
+buffered_14_7_op, buffered_14_7_bwd_op = _make_vdw_ops(0, "buffered_14_7")
+lennard_jones_op, lennard_jones_bwd_op = _make_vdw_ops(1, "lennard_jones")
+VDW_OPS = (buffered_14_7_op, lennard_jones_op)  # by MI_VDW_BUFFERED_14_7 / MI_VDW_LENNARD_JONES
+
+
+__all__ = ["buffered_14_7_op", "buffered_14_7_bwd_op", "lennard_jones_op", "lennard_jones_bwd_op", "VDW_OPS",
+           "pair_scale_correction_op", "pair_scale_bwd_op", "dipole_pair_scale_correction_op", "dipole_pair_scale_bwd_op", "rotate_multipoles_op", "rotate_multipoles_bwd_op", "coulomb_dipole_correction_op", "coulomb_dipole_bwd_op", "coulomb_quadrupole_correction_op", "coulomb_quadrupole_bwd_op",
            "pme_quadrupole_reciprocal_space_op", "pme_quadrupole_recip_bwd_op",
            "ewald_quadrupole_real_space_op", "ewald_quadrupole_reciprocal_space_op", "ewald_quadrupole_real_bwd_op",
            "ewald_quadrupole_recip_bwd_op", "thole_dipole_correction_op", "thole_dipole_bwd_op", "pme_dipole_reciprocal_space_op", "pme_dipole_recip_bwd_op", "ewald_dipole_real_space_op", "ewald_dipole_reciprocal_space_op", "ewald_dipole_real_bwd_op", "ewald_dipole_recip_bwd_op",

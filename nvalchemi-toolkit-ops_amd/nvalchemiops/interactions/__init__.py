@@ -1,1 +1,11 @@
-"""Neighbour-driven interactions of the MI355X hot path: dispersion (DFT-D3) and electrostatics (PME)."""
+"""Neighbour-driven interactions of the MI355X hot path: dispersion (DFT-D3), electrostatics (PME) and van der Waals pair potentials."""
+__all__ = ["buffered_14_7", "lennard_jones", "ReducedSites"]
+
+
+def __getattr__(name):
+    """The vdW exports, imported on first use: importing a subpackage does not pull in the others."""
+    if name in __all__:
+        from nvalchemiops.interactions import vdw
+
+        return getattr(vdw, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
