@@ -1296,6 +1296,61 @@ int mi_vdw(const void* positions, const void* radii, const void* epsilons, const
            void* forces, double* radius_grads, double* epsilon_grads, double* system_partial, void* scratch, size_t scratch_bytes,
            void* stream);
 
+/* Dispersion Ewald sum (csrc/dispersion_ewald.hip; driver: nvalchemiops/interactions/vdw/ewald.py): the lattice sum of the r^-6 energy
+ *     E = -1/2 sum'_{i, j, n} c_i c_j / |r_j - r_i + n|^6,      C6_ij = c_i c_j,
+ * by explicit Ewald summation.  With beta = alpha [n_systems] (positions dtype), a = beta r, g(a) = exp(-a^2) (1 + a^2 + a^4 / 2),
+ * b = |k| / (2 beta), f(b) = (1 - 2 b^2) exp(-b^2) + 2 sqrt(pi) b^3 erfc(b), S(k) = sum_j c_j e^{i k.r_j}:
+ *     real space    energies[i] = -1/2 sum_{entries of row i} c_i c_j (g(beta r) - T_c(r)) / r^6
+ *     reciprocal    energies[i] = -(pi^1.5 beta^3 / (3 V)) sum_{k in half space} f(b) c_i Re[e^{-i k.r_i} S(k)]
+ *                                 - (pi^1.5 beta^3 / (6 V)) c_i sum_j c_j + (beta^6 / 12) c_i^2
+ * mi_ewald_dispersion_real walks the stored entries (i, j, S) of a FULL (symmetric) list -- padded matrix (neighbor_ptr == NULL; entries
+ * equal to mask_value or outside [0, n_atoms) are padding) or CSR -- as mi_vdw does: pair vector and r^2 in the positions dtype, the rest
+ * fp64, the row owner writes alone (no atomics, deterministic); entries with r <= 1e-8 contribute nothing, the list is the cutoff.
+ * counted_cutoff > 0: T_c is the quintic switch of csrc/vdw.hip between counted_taper (negative: none) and counted_cutoff -- 1 below the
+ * taper, 0 from the cutoff on: the part a truncated mi_vdw Lennard-Jones call has already summed -- else T_c = 0.  weights [n_atoms] float64
+ * or NULL (all ones): entry weight w = (g_i + g_j) / 2, the outputs are then the derivatives of L = sum_i g_i energies[i]:
+ *   MI_DE_FORCES            forces [n_atoms][3] (positions dtype) = -dL/dr
+ *   MI_DE_COEFFICIENT_GRAD  coefficient_grads [n_atoms] float64 = dL/dc
+ *   MI_DE_VIRIAL            virial_partial [n_systems][mi_ewald_dispersion_blocks()][mi_ewald_dispersion_row_words()] float64: block partials
+ *                           of -dE/d(strain), {xx, yy, zz, xy, xz, yz}; the caller sums the block dimension (needs unit_shifts)
+ * energies may be NULL (adjoint use).  scratch: mi_ewald_dispersion_real_scratch_bytes(n_atoms, dtype) bytes, contents undefined.
+ *
+ * Reciprocal space.  Atoms of one system are contiguous (system_ptr [n_systems + 1] / a monotonic batch_idx; NULL for one system);
+ * k_vectors [n_systems][n_k][3] (positions dtype) is a half-space set, a vector with |k|^2 < 1e-10 weighs nothing.  Every per-k array has
+ * n_k + 1 slots per system: slot n_k is k = 0, which the library adds itself.
+ *   mi_ewald_dispersion_structure_factors   table [n_systems][n_k + 1][2] float64 = {Re, Im} of sum_j g_j c_j e^{i k.r_j} (weights g, NULL:
+ *       ones) and, unless NULL, records [n_systems][n_k + 1][mi_ewald_dispersion_record_words()] float64 = {k_x, k_y, k_z, w_k Re S, w_k Im S},
+ *       w_k = -(pi^1.5 beta^3 / (3 V)) f(b), half of that with f = 1 in slot n_k (needs cell and alpha).  A thread owns one k and walks LDS
+ *       tiles of mi_ewald_dispersion_atom_tile() atoms; the tile partials in scratch (mi_ewald_dispersion_sf_scratch_bytes) are added in index order.
+ *   mi_ewald_dispersion_recip_gather        a thread owns one atom and walks LDS tiles of mi_ewald_dispersion_k_tile() records: energies
+ *       [n_atoms] float64 (k = 0 and self terms included), forces [n_atoms][3] (positions dtype), coefficient_grads [n_atoms] float64; any may
+ *       be NULL.  With records_g (the records of the g-weighted table) and weights g: the derivatives of L = sum_i g_i energies[i].
+ *   mi_ewald_dispersion_recip_virial        virial [n_systems][6] float64 = -dE/d(strain), {xx, yy, zz, xy, xz, yz}, from the unweighted table,
+ *       the k set following the cell. */
+#define MI_DE_FORCES 1
+#define MI_DE_COEFFICIENT_GRAD 2
+#define MI_DE_VIRIAL 8
+int mi_ewald_dispersion_blocks(void);
+int mi_ewald_dispersion_row_words(void);
+int mi_ewald_dispersion_atom_tile(void);
+int mi_ewald_dispersion_k_tile(void);
+int mi_ewald_dispersion_record_words(void);
+size_t mi_ewald_dispersion_real_scratch_bytes(int n_atoms, int dtype);
+size_t mi_ewald_dispersion_sf_scratch_bytes(int n_atoms, int n_systems, int n_k);
+int mi_ewald_dispersion_real(const void* positions, const void* coefficients, const void* cell /*[n_systems,3,3]*/, const void* alpha,
+                             const int32_t* batch_idx, const double* weights, int n_atoms, int n_systems, int dtype, double counted_cutoff,
+                             double counted_taper, const int32_t* idx_j, const int32_t* unit_shifts, const int32_t* neighbor_ptr,
+                             int max_neighbors, int mask_value, int flags, double* energies, void* forces, double* coefficient_grads,
+                             double* virial_partial, void* scratch, size_t scratch_bytes, void* stream);
+int mi_ewald_dispersion_structure_factors(const void* positions, const void* coefficients, const double* weights, const void* k_vectors,
+                                          const void* cell, const void* alpha, const int32_t* system_ptr, int n_atoms, int n_systems, int n_k,
+                                          int dtype, double* table, double* records, void* scratch, size_t scratch_bytes, void* stream);
+int mi_ewald_dispersion_recip_gather(const void* positions, const void* coefficients, const void* alpha, const int32_t* batch_idx,
+                                     const double* records, const double* records_g, const double* weights, int n_atoms, int n_systems, int n_k,
+                                     int dtype, double* energies, void* forces, double* coefficient_grads, void* stream);
+int mi_ewald_dispersion_recip_virial(const double* table, const void* k_vectors, const void* cell, const void* alpha, int n_systems, int n_k,
+                                     int dtype, double* virial, void* stream);
+
 /* ---- multi-GPU: the one collective of the path (csrc/comm.cpp) ------------------------------------------------------------
  * The reference has no multi-GPU code; the path shards at SYSTEM granularity -- no pair crosses systems
  * (batch_cell_list.py:448-457, dftd3.py:823,1126, spline.py:809) -- so every rank runs the kernels above on its own contiguous range of

@@ -48,6 +48,9 @@ SOURCES = {
     # van der Waals pair potentials between reduced sites (mi_vdw): buffered 14-7 and Lennard-Jones, fp64 pair math; the float32 pair vector
     # is formed with scalar ops only, as in dipole_scale.hip
     "vdw.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # dispersion Ewald sum (mi_ewald_dispersion_*): fp64 pair math with libm exp, fp64 sincos phases and erfc once per k; the float32 pair
+    # vector is formed with scalar ops only, as in vdw.hip
+    "dispersion_ewald.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "multipole.hip": [],  # spherical harmonics / Gaussian multipole basis (nvalchemiops.math): fp64 elementwise kernels
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]

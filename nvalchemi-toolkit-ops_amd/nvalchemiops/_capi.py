@@ -272,6 +272,22 @@ def lib() -> ctypes.CDLL:
         for name in ("mi_vdw_blocks", "mi_vdw_row_words"):
             getattr(L, name).restype = i
             getattr(L, name).argtypes = []
+        # dispersion Ewald sum (nvalchemiops/interactions/vdw/ewald.py)
+        L.mi_ewald_dispersion_real.restype = i
+        L.mi_ewald_dispersion_real.argtypes = [vp] * 6 + [i, i, i, dbl, dbl, vp, vp, vp, i, i, i] + [vp] * 5 + [sz, vp]
+        L.mi_ewald_dispersion_structure_factors.restype = i
+        L.mi_ewald_dispersion_structure_factors.argtypes = [vp] * 7 + [i, i, i, i, vp, vp, vp, sz, vp]
+        L.mi_ewald_dispersion_recip_gather.restype = i
+        L.mi_ewald_dispersion_recip_gather.argtypes = [vp] * 7 + [i, i, i, i] + [vp] * 4
+        L.mi_ewald_dispersion_recip_virial.restype = i
+        L.mi_ewald_dispersion_recip_virial.argtypes = [vp] * 4 + [i, i, i, vp, vp]
+        L.mi_ewald_dispersion_real_scratch_bytes.restype = sz
+        L.mi_ewald_dispersion_real_scratch_bytes.argtypes = [i, i]
+        L.mi_ewald_dispersion_sf_scratch_bytes.restype = sz
+        L.mi_ewald_dispersion_sf_scratch_bytes.argtypes = [i, i, i]
+        for name in ("blocks", "row_words", "atom_tile", "k_tile", "record_words"):
+            getattr(L, "mi_ewald_dispersion_" + name).restype = i
+            getattr(L, "mi_ewald_dispersion_" + name).argtypes = []
         _LIB = L
     return _LIB
 

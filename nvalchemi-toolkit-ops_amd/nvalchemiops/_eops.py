@@ -1883,7 +1883,91 @@ lennard_jones_op, lennard_jones_bwd_op = _make_vdw_ops(1, "lennard_jones")
 VDW_OPS = (buffered_14_7_op, lennard_jones_op)  # by MI_VDW_BUFFERED_14_7 / MI_VDW_LENNARD_JONES
 
 
-__all__ = ["buffered_14_7_op", "buffered_14_7_bwd_op", "lennard_jones_op", "lennard_jones_bwd_op", "VDW_OPS",
+# =====================================================================================================================================
+# dispersion Ewald sum (nvalchemiops/interactions/vdw/ewald.py): one forward / backward op pair per half, from one maker
+# =====================================================================================================================================
+# Outputs are always (energies, forces, coefficient_gradients, virial); the ones not asked for are empty [0] tensors.  The energies are
+# differentiable w.r.t. positions and coefficients: the backward op runs the forward kernels with the incoming gradient as per-atom weights
+# and returns float64 gradients.  Gradients w.r.t. cell, k-vectors and alpha are refused, never a silent zero: the virial is the strain
+# derivative.  The ops are registered with an explicit schema string, so the implementations take *args in schema order.
+_DE_NO_GRAD = ("{op}: gradients w.r.t. {what} are not provided by the dispersion Ewald sum (out of scope); use compute_virial for the strain "
+               "derivative.")
+_DE_OUTPUTS = ("forces", "coefficient_gradients", "virial")
+
+
+def _dispersion_ewald_ops(name, forward, adjoint, middle, n_tensors, refused):
+    """(forward op `alchemiops::_<name>`, backward op `nvalchemiops::<name>_backward`).  `middle`: the schema of the arguments between the two
+    differentiable inputs and the flags, its first `n_tensors` tensors (saved for backward), the rest plain scalars; `refused`: argument
+    index -> name of the inputs without an adjoint."""
+    fwd_name, bwd_name = f"{_NS}::_{name}", f"nvalchemiops::{name}_backward"
+    mid = [a.split() for a in middle.split(", ")]
+    k, n_in = 2 + n_tensors, 2 + len(mid)
+    convert = [_SCALARS[t] for t, _ in mid[n_tensors:]]
+    i_cell, i_batch = 2, 2 + [a[1] for a in mid].index("batch_idx")
+    inputs = f"Tensor positions, Tensor coefficients, {middle}"
+
+    def run(fn_name, args, tail):
+        fn = getattr(importlib.import_module("nvalchemiops.interactions.vdw.ewald"), fn_name)
+        return fn(*args[:k], *[c(v) for c, v in zip(convert, args[k:n_in])], *tail)
+
+    def fwd(*args):
+        return tuple(args[0].new_empty((0,)) if o is None else o for o in run(forward, args, args[n_in:]))
+
+    def fwd_fake(*args):
+        positions, want = args[0], (True,) + tuple(args[n_in:])
+        n, cell = positions.shape[0], args[i_cell]
+        nsys = cell.reshape(-1, 3, 3).shape[0] if (args[i_batch] is not None or name.endswith("reciprocal_space")) else 1
+        return tuple(positions.new_empty(s if w else (0,)) for s, w in zip(((n,), (n, 3), (n,), (nsys, 3, 3)), want))
+
+    def bwd(*args):
+        return run(adjoint, args, (args[n_in],))
+
+    def bwd_fake(positions, *rest):
+        n = positions.shape[0]
+        return positions.new_empty((n, 3), dtype=torch.float64), positions.new_empty((n,), dtype=torch.float64)
+
+    def refuse_second_order(ctx, *grads):
+        raise NotImplementedError(_SECOND_ORDER.format(op=bwd_name, what="gradient"))
+
+    bwd_op = torch.library.custom_op(bwd_name, bwd, mutates_args=(), schema=f"({inputs}, Tensor grad_energies) -> (Tensor, Tensor)")
+    bwd_op.register_fake(bwd_fake)
+    bwd_op.register_autograd(refuse_second_order, setup_context=lambda ctx, inputs, output: None)
+
+    def setup(ctx, inputs, output):
+        ctx.save_for_backward(*inputs[:k])
+        ctx.extra = tuple(c(v) for c, v in zip(convert, inputs[k:n_in]))
+        ctx.set_materialize_grads(False)
+
+    def backward(ctx, g_e, *g_explicit):
+        for what, g in zip(_DE_OUTPUTS, g_explicit):
+            if g is not None:
+                raise NotImplementedError(_SECOND_ORDER.format(op=fwd_name, what=what))
+        need = ctx.needs_input_grad
+        for i, what in refused.items():
+            if need[i]:
+                raise NotImplementedError(_DE_NO_GRAD.format(op=fwd_name, what=what))
+        if g_e is None:
+            return (None,) * len(need)
+        saved = ctx.saved_tensors
+        gpos, gc = bwd_op(*saved, *ctx.extra, g_e)
+        return (gpos.to(saved[0].dtype) if need[0] else None, gc.to(saved[1].dtype) if need[1] else None) + (None,) * (len(need) - 2)
+
+    flags = "bool compute_forces, bool compute_coefficient_gradients, bool compute_virial"
+    fwd_op = torch.library.custom_op(fwd_name, fwd, mutates_args=(), schema=f"({inputs}, {flags}) -> (Tensor, Tensor, Tensor, Tensor)")
+    fwd_op.register_fake(fwd_fake)
+    fwd_op.register_autograd(backward, setup_context=setup)
+    return fwd_op, bwd_op
+
+
+ewald_dispersion_real_space_op, ewald_dispersion_real_bwd_op = _dispersion_ewald_ops(
+    "ewald_dispersion_real_space", "_real_forward", "_real_adjoint",
+    f"Tensor cell, Tensor alpha, {_LISTS}, float counted_cutoff, float counted_taper", 8, {2: "cell", 3: "alpha"})
+ewald_dispersion_reciprocal_space_op, ewald_dispersion_recip_bwd_op = _dispersion_ewald_ops(
+    "ewald_dispersion_reciprocal_space", "_recip_forward", "_recip_adjoint", _KSUM, 4, {2: "cell", 3: "k_vectors", 4: "alpha"})
+
+
+__all__ = ["ewald_dispersion_real_space_op", "ewald_dispersion_real_bwd_op", "ewald_dispersion_reciprocal_space_op", "ewald_dispersion_recip_bwd_op",
+           "buffered_14_7_op", "buffered_14_7_bwd_op", "lennard_jones_op", "lennard_jones_bwd_op", "VDW_OPS",
            "pair_scale_correction_op", "pair_scale_bwd_op", "dipole_pair_scale_correction_op", "dipole_pair_scale_bwd_op", "rotate_multipoles_op", "rotate_multipoles_bwd_op", "coulomb_dipole_correction_op", "coulomb_dipole_bwd_op", "coulomb_quadrupole_correction_op", "coulomb_quadrupole_bwd_op",
            "pme_quadrupole_reciprocal_space_op", "pme_quadrupole_recip_bwd_op",
            "ewald_quadrupole_real_space_op", "ewald_quadrupole_reciprocal_space_op", "ewald_quadrupole_real_bwd_op",
