@@ -6,8 +6,8 @@
                             - (pi^1.5 beta^3 / (6 V)) c_i sum_j c_j + (beta^6 / 12) c_i^2
                       f(b) = (1 - 2 b^2) exp(-b^2) + 2 sqrt(pi) b^3 erfc(b),   S(k) = sum_j c_j e^{i k.r_j}
 
-T_c is Tinker's quintic switch of the part `lennard_jones(cutoff=, taper=)` has already summed (1 below the taper, 0 from the cutoff on), 0 by
-default.  Derivatives come from autograd; the virial is the strain derivative with positions, cell and k-vectors strained together.
+T_c is Tinker's quintic switch of the part `lennard_jones(cutoff=, taper=)` has already summed (1 below the taper, 0 from the cutoff on; without
+a taper 1 below the cutoff), 0 by default.  A caller's k-vector with |k|^2 < 1e-10 weighs nothing, as the k = 0 slot of a full set would.  Derivatives come from autograd; the virial is the strain derivative with positions, cell and k-vectors strained together.
 `distance_dtype=float32` rounds pair vector and r^2 to float32 as the kernel does; `nudge_r2` moves every float32 r^2 by one ulp: what the
 float32 real-space bars of tests/test_dispersion_ewald_gpu.py are measured with."""
 import math
@@ -102,7 +102,9 @@ def real_energies(pos, c, cell, alpha, i, j, S, batch_idx=None, counted=None, di
     if counted is None:
         kernel = 1.0 - one_minus_g(a2)
     else:
-        kernel = one_minus_switch(torch.sqrt(r2), *counted) - one_minus_g(a2)  # g - T = (1 - T) - (1 - g)
+        # g - T = (1 - T) - (1 - g); without a taper 1 - T is the step at the cutoff, taken on r^2 as the kernel takes it
+        outside = (r2 >= counted[0] * counted[0]).to(F64) if counted[1] is None else one_minus_switch(torch.sqrt(r2), *counted)
+        kernel = outside - one_minus_g(a2)
     pair = -0.5 * c[i] * c[j] * kernel / r2 ** 3
     return torch.zeros(pos.shape[0], dtype=F64, device=pos.device).index_add(0, i, torch.where(keep, pair, torch.zeros_like(pair)))
 

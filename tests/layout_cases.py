@@ -18,6 +18,9 @@ must move the result far beyond the bar the sweep applies.  Every reference is c
     pair_scale(batch)           `quadrupole(batch)` with its brute-force list and one scale per entry by distance class (0, 0.375, 1, 0.75)
     frames(batch)               a local-frame topology of every kind over 130 / 70 + 60 atoms, wrapped into the boxes of `system`
     cluster_induced()           the three clusters of tests/cluster_multipole_reference.py in float32 numbers, a field and a warm start
+    vdw(batch, kind)            a sweep case of tests/sweep_cases.py (one cell of 60 atoms / 60 + 2 + 9 atoms in three cells) with reduced sites and scales
+    dispersion_ewald(batch)     a dispersion sweep case (60 atoms / 150 + 60 + 2 in three cells), alpha and k-vectors per system
+    dipole_scale(batch)         the periodic box / the three wrapped molecules of tests/dipole_scale_cases.py
 
 Why the D4 fixture is not the 12 Bohr box of the other sweeps: there the coordination numbers reach 18 while the `cn_ref` of
 `d4_test_tables` lie in [0, 1]; every Gaussian weight saturates on the reference nearest to 1, and rolling `ngw` by one row moves the
@@ -611,3 +614,75 @@ def cluster_induced_dense(thole=None, device="cpu"):
     p = cluster_induced()
     H, b, _, polar = CR.dense_problem(dict(p, polar=p["polar"] if thole is None else p["polar_thole"]), thole, device)
     return dict(H=H, b=b, polar=polar, bi=torch.as_tensor(p["batch_idx"], device=device))
+
+
+# ---- van der Waals pairs, dispersion Ewald, scaled dipole pairs ------------------------------------------------------------------------------
+
+VDW_SEED = {False: 0, True: 4}   # tests/sweep_cases.py: one triclinic cell of 60 atoms / a batch of 60 + 2 + 9 atoms in three cells of their own
+DE_SEED = {False: 0, True: 2}    # one cell of 60 atoms, no counted part / 150 + 60 + 2 atoms, counted (rc, None), k-vectors [3, K, 3] per cell
+
+
+@functools.lru_cache(maxsize=None)
+def vdw(batch=False, kind="buffered_14_7"):
+    """A sweep case of tests/sweep_cases.py (reduced sites with several children per parent, a tapered cutoff, the full list by brute force)
+    in float32 numbers, with one scale per entry from the symmetric hash of its atom pair.  Arguments of `vdw_reference`."""
+    from tests import sweep_cases as W
+
+    c = dict(W.vdw_case("sweep", (kind, VDW_SEED[batch])))
+    assert c["periodic"] and c["parent"] is not None and c["taper"] is not None and (len(c["sizes"]) > 1) == batch
+    for k in ("pos", "radii", "eps", "kappa", "cells"):
+        c[k] = _f32(c[k])
+    i, j, _ = c["entries"]
+    c.update(scales=_f32(W.hash_scale(i, j)), scale_dtype="float64")  # (rounded to float32 numbers, still symmetric)
+    return c
+
+
+def vdw_reference(batch=False, kind="buffered_14_7", dtype=F64, **replace):
+    from tests import sweep_cases as W
+
+    return W.vdw_reference(dict(vdw(batch, kind), **replace), kind, dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def dispersion_ewald(batch=False):
+    """A dispersion sweep case in float32 numbers: per-system alpha, some c = 0 atoms, k-vectors [B, K, 3] of every system's own cell."""
+    from tests import sweep_cases as W
+
+    c = dict(W.dispersion_case("sweep", DE_SEED[batch]))
+    assert (len(c["sizes"]) > 1) == batch and c["k_vectors"].shape[1] > 8
+    for k in ("pos", "c", "cells", "alpha"):
+        c[k] = _f32(c[k])
+    c["k_vectors"] = c["k_vectors"].to(torch.float32).to(F64)
+    return c
+
+
+def dispersion_ewald_reference(batch=False, half="sum", dtype=F64, **replace):
+    from tests import sweep_cases as W
+
+    return W.dispersion_reference(dict(dispersion_ewald(batch), **replace), half, dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def dipole_scale(batch=False):
+    """The periodic problem of tests/dipole_scale_cases.py (one triclinic box, explicit shifts) / its batch of three wrapped molecules, in
+    float32 numbers: pos, q, mu, polar (one 0, one NaN), sd, sm [entries], entries, cell, batch_idx."""
+    from tests import dipole_scale_cases as SC
+
+    p = dict(SC.problem("molecules" if batch else "periodic"))
+    if batch:
+        p["pos"] = p["pos_wrapped"]
+    assert p["cell"] is not None and (p["batch_idx"] is not None) == batch
+    for k in ("pos", "q", "mu", "polar", "sd", "sm", "cell"):
+        p[k] = _f32(np.asarray(p[k], dtype=np.float64))
+    return p
+
+
+def dipole_scale_reference(batch=False, thole=0.39, dtype=F64, **replace):
+    from tests import dipole_scale_reference as SR
+
+    p = dict(dipole_scale(batch), **replace)
+    t = lambda k: torch.as_tensor(np.asarray(p[k]), dtype=F64)  # noqa: E731
+    bi = None if p["batch_idx"] is None else torch.as_tensor(np.asarray(p["batch_idx"])).long()
+    return SR.evaluate(t("pos").to(dtype), t("q").to(dtype), t("mu").to(dtype), t("polar").to(dtype), t("sd"), t("sm"),
+                       tuple(torch.as_tensor(np.asarray(e)).long() for e in p["entries"]), thole=thole, batch_idx=bi, cell=t("cell").to(dtype),
+                       distance_dtype=dtype)

@@ -1532,3 +1532,473 @@ def cluster_case(kind, key=None):
     if kind == "frames":
         return _frame_sweep(key)
     raise KeyError(kind)
+
+
+# ---- van der Waals pair potentials and the dispersion Ewald sum: buffered_14_7, lennard_jones, ewald_dispersion_* ------------------------------
+# Inputs only; the restatements (tests/vdw_reference.py, tests/dispersion_ewald_reference.py) are evaluated by the GPU modules on the entries
+# actually stored.  A seed: a cluster, one cell, or a batch of two or three systems (`VDW_FORMS`), sizes from {1, 2, 9, 60, 150}, and EVERY
+# SYSTEM OF A BATCH IN A CELL OF ITS OWN SHAPE (`sweep_cell`: drawn tilts and edge ratios, on `VDW_ROTATED_SEEDS` times a drawn rotation, so
+# that all nine components are non-zero): a kernel that read system 0's cell, volume or k-vectors for every system would be wrong on every
+# batch seed.  The dispersion seeds generate each system's k-vectors from its own cell and cut them to the shortest set.  vdW: atoms at
+# `VDW_D_MIN` = 2 with R in [1.4, 1.7], so that every site pair keeps rho >= 0.8 (the condition of tests/test_vdw_gpu.py's float32 bars);
+# reduced sites on a drawn eighth of the atoms as parents with one to three of their nearest neighbours (minimum image, so bonds cross cell
+# faces) as children, a parent with eps = 0, a child with R = 0, the other atoms their own parent or -1 in turn; rules `VDW_RULES[seed % 6]`,
+# no taper on `VDW_NO_TAPER_SEEDS`, scales none / float32 / float64 by seed % 3 from `hash_scale`.  Designations as above:
+# `INTERLEAVED_SEEDS`, `EMPTY_SYSTEM_SEEDS` (the system in the middle), `SINGLE_FLAG_SEEDS`, and no flag at all on `VDW_NO_FLAG_SEED`.  The
+# cutoff of a seed is moved in steps of 1e-3 until no stored r^2 lies within `VDW_MARGIN` of its square: a float32 kernel and the
+# restatement's float32 mode may differ by an ulp of r^2, and without a taper the potential jumps there.
+VDW_KINDS = ("buffered_14_7", "lennard_jones")
+BASE.update(buffered_14_7=9500, lennard_jones=9600, dispersion_ewald=9700)
+VDW_SIZES = CLUSTER_SIZES
+VDW_BOX = {60: 11.0, 150: 15.0}  # 0, 1, 2 and 9 atoms: a box of 6, shorter than the list: own images
+VDW_FORMS = ("cell", "batch", "cluster", "cell", "batch", "batch", "cluster", "batch", "batch", "cell", "batch", "cluster")
+VDW_FLAGS = ("compute_forces", "compute_radius_gradients", "compute_epsilon_gradients", "compute_virial")
+VDW_NAMES = ("energies", "forces", "radius_grads", "epsilon_grads", "virial")
+VDW_RULES = tuple((r, e) for r in ("arithmetic", "geometric", "cubic-mean") for e in ("geometric", "hhg"))
+VDW_NO_TAPER_SEEDS = (1, 5, 9)
+VDW_NO_FLAG_SEED = 6
+VDW_ROTATED_SEEDS = (1, 4, 10)
+VDW_D_MIN = 2.0
+VDW_BOND_MAX = 2.6
+VDW_MARGIN = 2e-6
+VDW_ROWS = THOLE_ROWS
+DE_FLAGS = ("compute_forces", "compute_coefficient_gradients", "compute_virial")
+DE_NAMES = ("energies", "forces", "coefficient_grads", "virial")
+DE_NO_K_SEED = 7
+DE_D_MIN = 1.5
+DE_TILES = {"atom": 256, "k": 256}  # `DE_ATOM_TILE` / `DE_K_TILE`; the CPU suite reads the #defines
+DE_MIXED_SIZES = (3, 1, 0, 300, 7)  # one gather block spans four systems, the fourth system spans two atom tiles
+# Largest change of each output, relative to its largest |value|, when every float32 r^2 of the restatement moves by one ulp (`nudge_r2`):
+# the largest over the float32 (odd) seeds, on the edge case and on the row ladder, in the order of the NAMES.  Measured on the CPU from the
+# restatement alone by `measured_f32_figures`; tests/test_sweep_cases_cpu.py measures them again.  The edge case's are larger because its
+# seven atoms hold one pair at rho = 0.8 and little else.
+VDW_F32_FIGURE = {
+    "buffered_14_7": {"sweep": (3.23e-07, 3.73e-07, 2.78e-07, 3.05e-07, 3.58e-07), "edge": (1.35e-06, 1.01e-06, 8.88e-07, 2.53e-06, 1.01e-06),
+                      "rows": (3.18e-07, 3.66e-07, 3.05e-07, 3.18e-07, 3.64e-07)},
+    "lennard_jones": {"sweep": (2.87e-07, 3.78e-07, 2.59e-07, 2.92e-07, 3.46e-07), "edge": (1.53e-06, 1.09e-06, 9.73e-07, 2.55e-06, 1.09e-06),
+                      "rows": (2.83e-07, 3.35e-07, 2.64e-07, 2.83e-07, 3.31e-07)}}
+DE_F32_FIGURE = {"sweep": (5.2e-07, 1.65e-06, 4.27e-07, 2.46e-06), "edge": (3.93e-07, 4.29e-07, 3.81e-07, 3.92e-07)}
+
+
+def sweep_cell(g, box, rotated=False):
+    """A triclinic cell of a drawn shape: lower triangular with tilts up to a quarter of the edge and edge ratios 0.85 - 1.15; `rotated`: times
+    a drawn proper rotation, every component non-zero."""
+    t = g.uniform(-0.25, 0.25, 3)
+    cell = np.array([[box, 0, 0], [t[0] * box, g.uniform(0.85, 1.0) * box, 0], [t[1] * box, t[2] * box, g.uniform(1.0, 1.15) * box]])
+    if rotated:
+        q, r = np.linalg.qr(g.normal(size=(3, 3)))
+        q = q * np.sign(np.diag(r))
+        if np.linalg.det(q) < 0:
+            q[:, 0] = -q[:, 0]
+        cell = cell @ q
+    return cell
+
+
+def _distinct_cells(g, sizes, rotated, box_of):
+    """One cell per system, drawn again until any two differ by more than 5 % of the larger one's largest component somewhere."""
+    while True:
+        cells = [sweep_cell(g, box_of(n), rotated) for n in sizes]
+        if all(np.abs(a - b).max() > 0.05 * max(np.abs(a).max(), np.abs(b).max()) for k, a in enumerate(cells) for b in cells[k + 1:]):
+            return cells
+
+
+def _batch_sizes(g, seed, form):
+    """One system of 60 or 150; a batch: the first of 60 or 150, the last of 1, 2 or 9 in turn, and with three systems the middle one drawn
+    from all five, or without atoms on `EMPTY_SYSTEM_SEEDS`."""
+    if form != "batch":
+        return (int(g.choice((60, 150))),)
+    k = 3 if seed in EMPTY_SYSTEM_SEEDS else int(g.integers(2, 4))
+    sizes = [int(g.choice((60, 150)))] + ([int(g.choice(VDW_SIZES[:4]))] if k == 3 else []) + [(1, 2, 9)[(seed // 2) % 3]]
+    if seed in EMPTY_SYSTEM_SEEDS:
+        sizes[1] = 0
+    return tuple(sizes)
+
+
+def _single_flags(g, seed, names, periodic, none_seed):
+    if seed in SINGLE_FLAG_SEEDS:
+        alone = names[(SINGLE_FLAG_SEEDS.index(seed) - 1) % len(names)]
+        alone = names[0] if alone == "compute_virial" and not periodic else alone
+        return {k: k == alone for k in names}
+    flags = {k: seed != none_seed and bool(g.integers(2)) for k in names}
+    if not periodic:
+        flags["compute_virial"] = False
+    return flags
+
+
+def _vdw_sites(g, pos, cell, n, kappa_lo=0.88):
+    """(parent, reduction, parents with children) of one system: -1 and the atom's own index in turn, then n // 8 drawn parents with one to
+    three children each, their nearest free neighbours under the minimum image within `VDW_BOND_MAX`, every fractional component of the bond
+    at most 0.45 (0.05 from a minimum-image flip)."""
+    parent = np.where(np.arange(n) % 2 == 0, -1, np.arange(n))
+    kappa = g.uniform(kappa_lo, 0.95, n)
+    if n < 9:
+        return parent, kappa, []
+    d = pos[None, :, :] - pos[:, None, :]
+    ok = np.ones((n, n), bool)
+    if cell is not None:
+        f = d @ np.linalg.inv(cell)
+        red = f - np.rint(f)
+        ok = (np.abs(red) <= 0.45).all(-1)
+        d = red @ cell
+    dist = np.linalg.norm(d, axis=-1) + np.eye(n) * 1e9
+    free, parents = np.ones(n, bool), []
+    for p in g.permutation(n)[:max(1, n // 8)]:
+        if not free[p]:
+            continue
+        want = int(g.integers(1, 4))
+        kids = [int(k) for k in np.argsort(dist[p], kind="stable") if free[k] and k != p and dist[p, k] <= VDW_BOND_MAX and ok[p, k]][:want]
+        if not kids:
+            continue
+        free[p] = False
+        for k in kids:
+            parent[k], free[k] = p, False
+        parents.append(int(p))
+    return parent, kappa, parents
+
+
+def vdw_reduced(c):
+    own = np.arange(len(c["parent"]))
+    return (c["parent"] >= 0) & (c["parent"] < len(own)) & (c["parent"] != own)
+
+
+def vdw_bonds(c):
+    """(children, r_child - r_parent under the minimum image, its fractional components before the image is taken off | None)."""
+    kids = np.nonzero(vdw_reduced(c))[0]
+    d = c["pos"][kids] - c["pos"][c["parent"][kids]]
+    if c["cells"] is None:
+        return kids, d, None
+    cells = c["cells"][c["batch_idx"][kids]]
+    f = np.einsum("ea,eab->eb", d, np.linalg.inv(cells))
+    return kids, d - np.einsum("ea,eab->eb", np.rint(f), cells), f
+
+
+def vdw_site_positions(c):
+    kids, d, _ = vdw_bonds(c)
+    site = c["pos"].copy()
+    site[kids] -= (1.0 - c["kappa"][kids])[:, None] * d
+    return site
+
+
+def vdw_site_distances(c):
+    """Site distance of every stored entry."""
+    i, j, S = c["entries"]
+    site = vdw_site_positions(c)
+    shift = 0.0 if c["cells"] is None else np.einsum("ea,eab->eb", S.astype(np.float64), c["cells"][c["batch_idx"][i]])
+    return np.linalg.norm(site[j] - site[i] + shift, axis=1)
+
+
+def _list_all(pos, cells, sizes, reach):
+    """Full lists of every system by `brute_force` to `reach`, joined, and the image range of each system."""
+    ii, jj, ss, off, images = [], [], [], 0, []
+    for s, n in enumerate(sizes):
+        cell = None if cells is None else cells[s]
+        images.append(0 if cell is None else int(np.ceil(reach / heights(cell).min())))
+        i, j, S = brute_force(pos[off:off + n], cell, reach, images[-1])
+        ii.append(i + off); jj.append(j + off); ss.append(S.reshape(-1, 3))  # noqa: E702
+        off += n
+    return (np.concatenate(ii), np.concatenate(jj), np.concatenate(ss).astype(np.int64)), tuple(images)
+
+
+def _clear_of(r, cutoff):
+    """The first of cutoff, cutoff + 1e-3, ... with no r^2 within `VDW_MARGIN` (relative) of its square."""
+    while len(r) and float(np.abs(r * r / (cutoff * cutoff) - 1.0).min()) < VDW_MARGIN:
+        cutoff += 1e-3
+    return cutoff
+
+
+def _sibling_order(perm, parent, reduced):
+    """`perm` with the new places of every parent's children in their old order: the gather sums a parent's children in index order, so
+    only then is an interleaved call's force on a parent the sorted call's bit for bit."""
+    inv = np.empty_like(perm)
+    inv[perm] = np.arange(len(perm))
+    for p in np.unique(parent[reduced]):
+        kids = np.nonzero(reduced & (parent == p))[0]
+        inv[kids] = np.sort(inv[kids])
+    out = np.empty_like(perm)
+    out[inv] = np.arange(len(perm))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _vdw_sweep(kind, seed):
+    g = np.random.default_rng(BASE[kind] + seed)
+    form = VDW_FORMS[seed]
+    periodic = form != "cluster"
+    sizes = _batch_sizes(g, seed, form)
+    cells = _distinct_cells(g, sizes, seed in VDW_ROTATED_SEEDS, lambda n: VDW_BOX.get(n, 6.0))
+    pos = [spaced_positions(g, n, cell, VDW_D_MIN) for n, cell in zip(sizes, cells)]
+    ntot = sum(sizes)
+    radii, eps = g.uniform(1.4, 1.7, ntot), g.uniform(0.05, 0.3, ntot)
+    parent, kappa, parents, off = [], [], [], 0
+    for n, p, cell in zip(sizes, pos, cells):
+        par, kap, heads = _vdw_sites(g, p, cell if periodic else None, n)
+        parent.append(np.where(par >= 0, par + off, -1)); kappa.append(kap); parents.append([h + off for h in heads])  # noqa: E702
+        off += n
+    parent, kappa = np.concatenate(parent), np.concatenate(kappa)
+    heads = parents[int(np.argmax(sizes))]
+    lost = int(np.nonzero((parent == heads[1]) & (np.arange(ntot) != heads[1]))[0][0])
+    eps[heads[0]], radii[lost] = 0.0, 0.0  # a parent without a site that has children, and a child without a site
+    cutoff = float(g.uniform(4.0, 5.0))
+    taper = None if seed in VDW_NO_TAPER_SEEDS else float(g.uniform(0.8, 0.92)) * cutoff
+    c = dict(op=kind, seed=seed, dtype="float64" if seed % 2 == 0 else "float32", form=form, sizes=sizes, periodic=periodic, pos=np.concatenate(pos),
+             cells=np.stack(cells) if periodic else None, batch_idx=np.concatenate([np.full(n, k, np.int32) for k, n in enumerate(sizes)]),
+             radii=radii, eps=eps, parent=parent, kappa=kappa, no_site=(heads[0], lost), taper=taper,
+             rules=VDW_RULES[seed % 6], delta=float(g.uniform(0.05, 0.1)), gamma=float(g.uniform(0.08, 0.16)),
+             flags=_single_flags(g, seed, VDW_FLAGS, periodic, VDW_NO_FLAG_SEED), autograd=bool(g.integers(2)), weights=g.uniform(0.2, 1.8, ntot),
+             empty_system=1 if seed in EMPTY_SYSTEM_SEEDS else None, scale_dtype=(None, "float32", "float64")[seed % 3])
+    kids, bond, _ = vdw_bonds(c)
+    c["reach"] = cutoff + 0.01 + 2.0 * float(((1.0 - kappa[kids]) * np.linalg.norm(bond, axis=1)).max()) + 0.05
+    c["entries"], c["images"] = _list_all(c["pos"], c["cells"], sizes, c["reach"])
+    c["cutoff"] = _clear_of(vdw_site_distances(c), cutoff)
+    i, j, _ = c["entries"]
+    c["scales"] = None if c["scale_dtype"] is None else hash_scale(i, j)
+    c["perm"] = _sibling_order(g.permutation(ntot), parent, vdw_reduced(c)) if seed in INTERLEAVED_SEEDS else None
+    return c
+
+
+def vdw_interleaved(c):
+    """The case with its atoms in the order `perm`: per-atom arrays, the parent table renumbered, entries and scales sorted by their new row."""
+    perm = c["perm"]
+    inv = np.empty_like(perm)
+    inv[perm] = np.arange(len(perm))
+    i, j, S = c["entries"]
+    ni, nj = inv[i], inv[j]
+    order = np.argsort(ni, kind="stable")
+    out = dict(c, perm=None, entries=(ni[order], nj[order], S[order]), scales=None if c["scales"] is None else c["scales"][order])
+    for k in ("pos", "radii", "eps", "kappa", "batch_idx", "weights"):
+        out[k] = c[k][perm]
+    old = c["parent"][perm]
+    out["parent"] = np.where(old >= 0, inv[np.clip(old, 0, None)], -1)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def vdw_edge_case():
+    """Hand-placed float32-exact coordinates in a cubic cell of 32 with every shift zero (S . cell adds an exact 0), cutoff 3 and taper 2.5.
+    From atom 0: atom 1 at r^2 == cutoff^2 exactly; atom 2 at r = the float32 below 3, whose r^2 is the float32 below 9 (exact in float64,
+    rounded once in float32 whether or not the sum of squares is contracted: the other two terms are 0); atom 3 at r == taper; atom 4 at
+    r = 2; atoms 0 and 3 also list themselves (r = 0).  Atoms 5 and 6 list only each other, at the cutoff: exact zeros.  All pairs of atoms
+    0 - 4 are listed, most of them beyond the cutoff.  `padded_matrix` leaves a padding slot between live entries on rows 1 and 3."""
+    x = float(np.nextafter(np.float32(3.0), np.float32(0.0)))
+    pos = np.array([[0, 0, 0], [3, 0, 0], [-x, 0, 0], [0, 2.5, 0], [0, 0, -2], [10, 10, 10], [13, 10, 10]], np.float64)
+    pairs = [(a, b) for a in range(5) for b in range(5) if a != b] + [(0, 0), (3, 3), (5, 6), (6, 5)]
+    i, j = (np.array(v, np.int64) for v in zip(*sorted(pairs)))
+    n = len(pos)
+    return dict(op=None, seed=None, dtype=None, form="cell", sizes=(n,), periodic=True, pos=pos, cells=np.eye(3)[None] * 32.0, batch_idx=np.zeros(n, np.int32),
+                radii=np.array([2.25, 2.0, 2.5, 2.125, 2.375, 2.0, 2.25]), eps=np.array([0.25, 0.125, 0.1875, 0.3125, 0.0625, 0.25, 0.125]),
+                parent=None, kappa=None, taper=2.5, cutoff=3.0, rules=None, delta=0.07, gamma=0.12, flags={k: True for k in VDW_FLAGS}, scales=None,
+                scale_dtype=None, entries=(i, j, np.zeros((len(i), 3), np.int64)), perm=None, empty_system=None, at_cutoff=(5, 6))
+
+
+@functools.lru_cache(maxsize=None)
+def vdw_row_ladder():
+    """Rows of exactly 0, 1, 63, 64, 65, 128 and 129 entries WITH SITES, in a full list built as `thole_row_ladder` builds it: ladder atom t
+    holds its that many nearest (filler, shift) combinations and the fillers hold the reversed entries.  40 fillers in a drawn cell of 12,
+    shifts in [-2, 2]^3, cutoff 9 and taper 8, so that the long rows end beyond the cutoff.  The ladder atoms of 63 and 65 entries are the
+    children of their nearest filler, the one of 64 the parent of its nearest filler (kappa 0.93 - 0.95: the bonds are up to 4 long)."""
+    g = np.random.default_rng(BASE["buffered_14_7"] + 100)
+    n = len(VDW_ROWS) + 40
+    cell = sweep_cell(g, 12.0, True)
+    pos = spaced_positions(g, n, cell, VDW_D_MIN)
+    rng = np.arange(-2, 3)
+    shifts = np.array([(a, b, c) for a in rng for b in rng for c in rng])
+    parent = np.where(np.arange(n) % 2 == 0, -1, np.arange(n))
+    ei, ej, eS = [], [], []
+    for t, length in enumerate(VDW_ROWS):
+        d = np.linalg.norm(pos[len(VDW_ROWS):, None, :] - pos[t] + (shifts @ cell)[None, :, :], axis=-1)  # [filler, shift]
+        for k in np.argsort(d.reshape(-1), kind="stable")[:length]:
+            f, s = len(VDW_ROWS) + int(k) // len(shifts), int(k) % len(shifts)
+            ei += [t, f]; ej += [f, t]; eS += [shifts[s], -shifts[s]]  # noqa: E702
+        nearest = len(VDW_ROWS) + int(np.argmin(d.min(axis=1)))
+        if length in (63, 65):
+            parent[t] = nearest
+        elif length == 64:
+            parent[nearest] = t
+    ei, ej, eS = np.array(ei), np.array(ej), np.array(eS).reshape(-1, 3)
+    order = np.argsort(ei, kind="stable")
+    c = dict(op=None, seed=None, dtype=None, form="cell", sizes=(n,), periodic=True, pos=pos, cells=cell[None], batch_idx=np.zeros(n, np.int32),
+             radii=g.uniform(1.4, 1.7, n), eps=g.uniform(0.05, 0.3, n), parent=parent, kappa=g.uniform(0.93, 0.95, n), taper=8.0, rules=None, delta=0.07,
+             gamma=0.12, flags={k: True for k in VDW_FLAGS}, scale_dtype="float64", entries=(ei[order], ej[order], eS[order].astype(np.int64)), perm=None,
+             empty_system=None)
+    c["cutoff"] = _clear_of(vdw_site_distances(c), 9.0)
+    c["scales"] = hash_scale(c["entries"][0], c["entries"][1])
+    return c
+
+
+def vdw_case(kind, key=None):
+    """kind: "sweep" (key: (op, seed)), "edge", "rows"."""
+    if kind == "sweep":
+        return _vdw_sweep(*key)
+    return {"edge": vdw_edge_case, "rows": vdw_row_ladder}[kind]()
+
+
+def _own_k_vectors(cells, k_cutoff, n_k=None):
+    """([B, K, 3] float64 torch, the K of every system before the cut): the half-space set of EACH system's own cell, cut to the shortest
+    (or to n_k)."""
+    from nvalchemiops.interactions.electrostatics.k_vectors import generate_k_vectors_ewald_summation
+
+    sets = [generate_k_vectors_ewald_summation(torch.as_tensor(cell, dtype=torch.float64), k_cutoff) for cell in cells]
+    counts = tuple(int(k.shape[0]) for k in sets)
+    keep = min(counts) if n_k is None else n_k
+    assert keep <= min(counts)
+    return torch.stack([k[:keep] for k in sets]), counts
+
+
+@functools.lru_cache(maxsize=None)
+def _dispersion_sweep(seed):
+    """The frame of `_vdw_sweep` for the three `ewald_dispersion_*` functions: always periodic, one cell on seeds 0, 3, 6, 9 and a batch
+    otherwise; alpha per system, `counted` none / (rc, rt) / (rc, None) by seed % 3, a tenth of the atoms with c = 0, the list by
+    `brute_force` to 5.5 - 6.5, k-vectors of every system's own cell at `K_CUTOFF` cut to the shortest set, none on `DE_NO_K_SEED`."""
+    g = np.random.default_rng(BASE["dispersion_ewald"] + seed)
+    form = "cell" if seed % 3 == 0 else "batch"
+    sizes = _batch_sizes(g, seed, form)
+    cells = _distinct_cells(g, sizes, seed in VDW_ROTATED_SEEDS, lambda n: VDW_BOX.get(n, 6.0))
+    pos = np.concatenate([spaced_positions(g, n, cell, DE_D_MIN) for n, cell in zip(sizes, cells)])
+    ntot = sum(sizes)
+    coeff = g.uniform(2.0, 5.0, ntot)
+    coeff[g.choice(ntot, max(1, ntot // 10), replace=False)] = 0.0
+    rc = float(g.uniform(4.0, 5.0))
+    c = dict(op="dispersion_ewald", seed=seed, dtype="float64" if seed % 2 == 0 else "float32", form=form, sizes=sizes, periodic=True, pos=pos,
+             cells=np.stack(cells), batch_idx=np.concatenate([np.full(n, k, np.int32) for k, n in enumerate(sizes)]), c=coeff,
+             alpha=g.uniform(0.25, 0.45, len(sizes)), flags=_single_flags(g, seed, DE_FLAGS, True, VDW_NO_FLAG_SEED), autograd=bool(g.integers(2)),
+             weights=g.uniform(0.2, 1.8, ntot), empty_system=1 if seed in EMPTY_SYSTEM_SEEDS else None, reach=float(g.uniform(5.5, 6.5)))
+    c["entries"], c["images"] = _list_all(pos, c["cells"], sizes, c["reach"])
+    rc = _clear_of(entry_distances(c), rc)
+    c["counted"] = (None, (rc, 0.9 * rc), (rc, None))[seed % 3]
+    c["k_vectors"], c["k_counts"] = _own_k_vectors(cells, K_CUTOFF, 0 if seed == DE_NO_K_SEED else None)
+    c["perm"] = g.permutation(ntot) if seed in INTERLEAVED_SEEDS else None
+    return c
+
+
+def dispersion_interleaved(c):
+    """The case with its atoms in the order `perm` (for the real half only: the reciprocal half documents contiguous systems)."""
+    perm = c["perm"]
+    inv = np.empty_like(perm)
+    inv[perm] = np.arange(len(perm))
+    i, j, S = c["entries"]
+    ni, nj = inv[i], inv[j]
+    order = np.argsort(ni, kind="stable")
+    out = dict(c, perm=None, entries=(ni[order], nj[order], S[order]))
+    for k in ("pos", "c", "batch_idx", "weights"):
+        out[k] = c[k][perm]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def dispersion_edge_case():
+    """Hand-placed float32-exact coordinates in a cubic cell of 32, every shift zero, alpha = 0.25, counted (5, 4.5).  From atom 0: atom 1 at
+    r = 4, a^2 == 1 exactly (the switch between the series and the difference); atoms 2 and 3 at the float32 numbers below and above 4,
+    whose squares round once to floats below and above 16; atom 4 at r^2 == counted_cutoff^2 = 9 + 16; atom 5 at r == counted_taper;
+    atoms 0 and 5 list themselves (r = 0).  Atom 6 has c = 0.  All pairs are listed.  `k_vectors`: the cell's set at 0.7, and `k_tiny`: the
+    same set with (1e-6, 0, 0) appended, |k|^2 = 1e-12 < 1e-10."""
+    lo, hi = (float(np.nextafter(np.float32(4.0), np.float32(v))) for v in (0.0, 8.0))
+    pos = np.array([[0, 0, 0], [4, 0, 0], [0, -lo, 0], [0, 0, hi], [-3, 4, 0], [0, 0, -4.5], [2, 2, 2]], np.float64)
+    n = len(pos)
+    pairs = [(a, b) for a in range(n) for b in range(n) if a != b] + [(0, 0), (5, 5)]
+    i, j = (np.array(v, np.int64) for v in zip(*sorted(pairs)))
+    cells = np.eye(3)[None] * 32.0
+    kv, counts = _own_k_vectors(cells, 0.7)
+    return dict(op="dispersion_ewald", seed=None, dtype=None, form="cell", sizes=(n,), periodic=True, pos=pos, cells=cells, batch_idx=np.zeros(n, np.int32),
+                c=np.array([2.5, 3.0, 2.0, 4.5, 3.5, 2.25, 0.0]), alpha=np.array([0.25]), counted=(5.0, 4.5), flags={k: True for k in DE_FLAGS},
+                entries=(i, j, np.zeros((len(i), 3), np.int64)), k_vectors=kv, k_counts=counts, perm=None, empty_system=None,
+                k_tiny=torch.cat([kv, torch.tensor([[[1e-6, 0.0, 0.0]]], dtype=torch.float64)], dim=1))
+
+
+@functools.lru_cache(maxsize=None)
+def dispersion_recip_case(sizes, n_k):
+    """Systems of `sizes` atoms uniform in cells of their own shape (edges 9, 9.7, ...), the first n_k vectors of each system's OWN half-space
+    set at 4.6, alpha 1.1, 1.3, ... (f(b) of order one): the reciprocal ladders of tests/test_dispersion_ewald_gpu.py on distinct cells."""
+    g = np.random.default_rng(BASE["dispersion_ewald"] + 100 + sum(sizes) + n_k)
+    cells = [sweep_cell(g, 9.0 + 0.7 * s, s % 2 == 1) for s in range(len(sizes))]
+    pos = np.concatenate([g.uniform(0, 1, (n, 3)) @ cell for n, cell in zip(sizes, cells)])
+    kv, counts = _own_k_vectors(cells, 4.6, n_k)
+    ntot = sum(sizes)
+    return dict(op="dispersion_ewald", seed=None, dtype=None, form="batch", sizes=tuple(sizes), periodic=True, pos=pos, cells=np.stack(cells),
+                batch_idx=np.concatenate([np.full(n, k, np.int32) for k, n in enumerate(sizes)]), c=g.uniform(1.0, 2.0, ntot),
+                alpha=1.1 + 0.2 * np.arange(len(sizes)), counted=None, flags={k: True for k in DE_FLAGS}, entries=None, k_vectors=kv, k_counts=counts,
+                perm=None, empty_system=sizes.index(0) if 0 in sizes else None)
+
+
+def dispersion_recip_rungs(atom_tile=None, k_tile=None):
+    """(sizes, n_k) of the reciprocal ladders: the first system at the atom tile - 1, + 0, + 1 and twice + 3 beside a second of 5; the k tile
+    likewise beside systems of tile + 1 and 9 atoms; and `DE_MIXED_SIZES`."""
+    ta, tk = atom_tile or DE_TILES["atom"], k_tile or DE_TILES["k"]
+    return ([((n, 5), tk + 1) for n in (1, ta - 1, ta, ta + 1, 2 * ta + 3)] + [((ta + 1, 9), k) for k in (0, 1, tk - 1, tk, 2 * tk + 3)]
+            + [(DE_MIXED_SIZES, tk + 1)])
+
+
+def dispersion_case(kind, key=None):
+    """kind: "sweep" (key: seed), "edge", "recip" (key: (sizes, n_k))."""
+    if kind == "sweep":
+        return _dispersion_sweep(key)
+    if kind == "edge":
+        return dispersion_edge_case()
+    return dispersion_recip_case(*key)
+
+
+def _tt(a, device, dtype=None):
+    return torch.as_tensor(np.ascontiguousarray(a), device=device, dtype=dtype)
+
+
+def vdw_model(c, kind):
+    """The keyword arguments of the model, the same for the operator and for tests/vdw_reference.py (a case without rules: the kind's defaults)."""
+    rules = c["rules"] or (("cubic-mean", "hhg") if kind == "buffered_14_7" else ("arithmetic", "geometric"))
+    kw = dict(cutoff=c["cutoff"], taper=c["taper"], radius_rule=rules[0], epsilon_rule=rules[1])
+    if kind == "buffered_14_7":
+        kw.update(delta=c["delta"], gamma=c["gamma"])
+    return kw
+
+
+def vdw_reference(c, kind, dtype, device="cpu", nudge=False):
+    """tests/vdw_reference.py at the inputs rounded to `dtype` (the scales to theirs), on the stored entries; `nudge`: every float32 r^2 one ulp up."""
+    from tests import vdw_reference as VR
+
+    pos, radii, eps = (_tt(c[k], device, dtype) for k in ("pos", "radii", "eps"))
+    i, j, S = (_tt(e, device).long() for e in c["entries"])
+    scales = None if c["scales"] is None else _tt(c["scales"], device, torch.float32 if c["scale_dtype"] == "float32" else torch.float64).to(torch.float64)
+    sites = None if c["parent"] is None else (_tt(c["parent"], device), _tt(c["kappa"], device, dtype))
+    return VR.evaluate(kind, pos, radii, eps, _tt(c["cells"], device, dtype) if c["periodic"] else None, i, j, S, scales,
+                       batch_idx=_tt(c["batch_idx"], device) if c["periodic"] else None, distance_dtype=dtype, nudge_r2=nudge, sites=sites, **vdw_model(c, kind))
+
+
+def dispersion_reference(c, half, dtype, device="cpu", nudge=False):
+    """tests/dispersion_ewald_reference.py at the inputs rounded to `dtype`; half: "real" (the stored entries), "recip" (the k-vectors) or "sum"."""
+    from tests import dispersion_ewald_reference as ER
+
+    pos, coeff, cell, alpha = (_tt(c[k], device, dtype) for k in ("pos", "c", "cells", "alpha"))
+    entries = None if half == "recip" else tuple(_tt(e, device).long() for e in c["entries"])
+    kv = None if half == "real" else c["k_vectors"].to(device).to(dtype)
+    kw = {} if entries is None else dict(counted=c["counted"], distance_dtype=dtype, nudge_r2=nudge)
+    return ER.evaluate(pos, coeff, cell, alpha, entries, kv, batch_idx=_tt(c["batch_idx"], device), **kw)
+
+
+def f32_figures(ref, nudged, names):
+    """Per output: the largest change between the two float32-mode restatements relative to the largest |value| (0 for an output that is None or zero)."""
+    out = []
+    for k in names:
+        scale = 0.0 if ref[k] is None or not ref[k].numel() else float(ref[k].abs().max())
+        out.append(float((nudged[k] - ref[k]).abs().max()) / scale if scale > 0 else 0.0)
+    return tuple(out)
+
+
+def vdw_f32_cases(kind):
+    return {"sweep": [_vdw_sweep(kind, s) for s in SEEDS if s % 2 == 1], "edge": [vdw_edge_case()], "rows": [vdw_row_ladder()]}
+
+
+def dispersion_f32_cases():
+    return {"sweep": [_dispersion_sweep(s) for s in SEEDS if s % 2 == 1], "edge": [dispersion_edge_case()]}
+
+
+def measured_f32_figures(family, kind=None):
+    """{group: figures}: the largest `f32_figures` over the group's cases, from the restatement alone (CPU), to three digits."""
+    out = {}
+    for group, cases in (vdw_f32_cases(kind) if family == "vdw" else dispersion_f32_cases()).items():
+        worst = np.zeros(5 if family == "vdw" else 4)
+        for c in cases:
+            if family == "vdw":
+                pair = [vdw_reference(c, kind, torch.float32, nudge=v) for v in (False, True)]
+            else:
+                pair = [dispersion_reference(c, "real", torch.float32, nudge=v) for v in (False, True)]
+            worst = np.maximum(worst, f32_figures(*pair, VDW_NAMES if family == "vdw" else DE_NAMES))
+        out[group] = tuple(float(f"{v:.3g}") for v in worst)
+    return out

@@ -536,3 +536,155 @@ def test_well_formed_cpu_arguments_stop_at_the_device_check():
     for call in calls:
         with pytest.raises(C.NativeLibraryError, match="ROCm devices only"):
             call()
+
+
+# ---- van der Waals pairs, dispersion Ewald, scaled dipole pairs: `mi_vdw*`, `mi_ewald_dispersion_*`, `mi_dipole_scale*` are never reached -----
+
+def _vdw_calls():
+    from nvalchemiops.interactions import buffered_14_7, lennard_jones
+
+    every = dict(compute_forces=True, compute_radius_gradients=True, compute_epsilon_gradients=True)
+    return {"buffered_14_7": lambda *a, **k: buffered_14_7(*a, cutoff=3.0, taper=2.5, **k),
+            "lennard_jones": lambda *a, **k: lennard_jones(*a, cutoff=3.0, **k),
+            "buffered_14_7_all_outputs": lambda *a, **k: buffered_14_7(*a, cutoff=3.0, **every, **k),
+            "lennard_jones_autograd": lambda pos, r, *a, **k: lennard_jones(pos.clone().requires_grad_(True), r.clone().requires_grad_(True), *a, cutoff=3.0, **k)}
+
+
+@pytest.mark.parametrize("entry", ["buffered_14_7", "lennard_jones", "buffered_14_7_all_outputs", "lennard_jones_autograd"])
+def test_vdw_inputs_are_checked_against_each_other(entry):
+    from nvalchemiops.interactions import ReducedSites
+
+    call = _vdw_calls()[entry]
+    pos, cell, _, bi = _geometry()
+    r, e = torch.rand(N) + 1.0, torch.rand(N)
+    nm, nsh, lst, ptr, lsh = _neighbour_inputs()
+    cells = cell[None]
+    good = dict(neighbor_matrix=nm, neighbor_matrix_shifts=nsh)
+    for match, kw in _periodic_list_cases("neighbor_shifts"):
+        with pytest.raises(ValueError, match=match):
+            call(pos, r, e, cells, **kw)
+    for lists, width in ((good, (N, M)), (dict(neighbor_list=lst, neighbor_ptr=ptr, neighbor_shifts=lsh), (7,))):
+        with pytest.raises(ValueError, match="radii"):
+            call(pos, r[:-1], e, cells, **lists)
+        with pytest.raises(ValueError, match="epsilons"):
+            call(pos, r, e[:, None].expand(N, 2), cells, **lists)
+        with pytest.raises(ValueError, match="batch_idx"):
+            call(pos, r, e, cells.repeat(B, 1, 1), batch_idx=bi[:-1], **lists)
+        with pytest.raises(ValueError, match="cell must have shape"):
+            call(pos, r, e, torch.zeros(3, 2), **lists)
+        for bad in (torch.rand(*width[:-1], width[-1] + 1), torch.rand(*width)[..., :-1], torch.rand(2, *width)):
+            with pytest.raises(ValueError, match="pair_scales must have the shape of the index array"):
+                call(pos, r, e, cells, pair_scales=bad, **lists)
+        with pytest.raises(ValueError, match="pair_scales must be float32 or float64"):
+            call(pos, r, e, cells, pair_scales=torch.ones(width, dtype=torch.float16), **lists)
+        with pytest.raises(ValueError, match=f"sites describes {N - 1} atoms"):  # a table for another number of atoms: `parent` would be read past its end
+            call(pos, r, e, cells, sites=ReducedSites(torch.full((N - 1,), -1, dtype=I32), torch.ones(N - 1)), **lists)
+    with pytest.raises(ValueError, match="positions must have shape"):
+        call(pos[:, :2], r, e, cells, **good)
+
+
+def _dispersion_ewald_calls():
+    from nvalchemiops.interactions import ewald_dispersion_correction, ewald_dispersion_real_space
+
+    every = dict(compute_forces=True, compute_coefficient_gradients=True, compute_virial=True)
+    kv = torch.rand(6, 3)
+    return {"real_space": ewald_dispersion_real_space, "real_space_all_outputs": lambda *a, **k: ewald_dispersion_real_space(*a, counted_cutoff=3.0, **every, **k),
+            "correction": lambda *a, **k: ewald_dispersion_correction(*a, k_vectors=kv, **k),
+            "correction_autograd": lambda pos, c, *a, **k: ewald_dispersion_correction(pos.clone().requires_grad_(True), c.clone().requires_grad_(True), *a, k_cutoff=1.0, **k)}
+
+
+@pytest.mark.parametrize("entry", ["real_space", "real_space_all_outputs", "correction", "correction_autograd"])
+def test_dispersion_ewald_inputs_are_checked_against_each_other(entry):
+    call = _dispersion_ewald_calls()[entry]
+    pos, cell, _, bi = _geometry()
+    c = torch.rand(N)
+    nm, nsh, lst, ptr, lsh = _neighbour_inputs()
+    cells = cell[None]
+    for match, kw in _periodic_list_cases("neighbor_shifts"):
+        with pytest.raises(ValueError, match=match):
+            call(pos, c, cells, 0.3, **kw)
+    for lists in (dict(neighbor_matrix=nm, neighbor_matrix_shifts=nsh), dict(neighbor_list=lst, neighbor_ptr=ptr, neighbor_shifts=lsh)):
+        with pytest.raises(ValueError, match="coefficients"):
+            call(pos, c[:-1], cells, 0.3, **lists)
+        with pytest.raises(ValueError, match="batch_idx"):
+            call(pos, c, cells.repeat(B, 1, 1), 0.3, batch_idx=bi[:-1], **lists)
+        with pytest.raises(ValueError, match="alpha has 3 values but there are 2 systems"):
+            call(pos, c, cells.repeat(B, 1, 1), torch.tensor([0.3, 0.3, 0.3]), batch_idx=bi, **lists)
+
+
+def test_dispersion_ewald_reciprocal_inputs_are_checked_against_each_other():
+    from nvalchemiops.interactions import ewald_dispersion_reciprocal_space as recip
+
+    pos, cell, _, bi = _geometry()
+    c, cellb = torch.rand(N), cell[None].repeat(B, 1, 1)
+    for bad in (torch.rand(6, 2), torch.rand(6), torch.rand(3, 6, 3), torch.rand(1, 2, 6, 3)):  # [3, K, 3] beside two systems: system 2 would read past the end
+        with pytest.raises(ValueError, match="k_vectors must have shape"):
+            recip(pos, c, cellb, bad, torch.tensor([0.3, 0.3]), batch_idx=bi)
+    with pytest.raises(ValueError, match="coefficients"):
+        recip(pos, c[:-1], cellb, torch.rand(2, 6, 3), 0.3, batch_idx=bi)
+    with pytest.raises(ValueError, match="batch_idx"):
+        recip(pos, c, cellb, torch.rand(2, 6, 3), 0.3, batch_idx=bi[:-1])
+    with pytest.raises(ValueError, match="alpha has 3 values but there are 2 systems"):
+        recip(pos, c, cellb, torch.rand(2, 6, 3), torch.tensor([0.3, 0.3, 0.3]), batch_idx=bi)
+
+
+@pytest.mark.parametrize("entry", ["energies", "all_outputs", "autograd"])
+def test_dipole_pair_scale_correction_inputs_are_checked_against_each_other(entry):
+    from nvalchemiops.interactions.electrostatics import dipole_pair_scale_correction as dps
+
+    every = dict(compute_forces=True, compute_charge_gradients=True, compute_dipole_gradients=True, compute_polarizability_gradients=True)
+    call = {"energies": dps, "all_outputs": lambda *a, **k: dps(*a, **every, **k),
+            "autograd": lambda pos, q, *a, **k: dps(pos.clone().requires_grad_(True), q.clone().requires_grad_(True), *a, **k)}[entry]
+    pos, cell, _, bi = _geometry()
+    q, mu, pol = torch.rand(N), torch.rand(N, 3), torch.rand(N) + 0.5
+    nm, nsh, lst, ptr, lsh = _neighbour_inputs()
+    cells = cell[None]
+    for lists, width in ((dict(neighbor_matrix=nm, neighbor_matrix_shifts=nsh), (N, M)), (dict(neighbor_list=lst, neighbor_ptr=ptr, neighbor_shifts=lsh), (7,))):
+        s = torch.rand(width)
+        for name, args in (("direct_scales", (torch.rand(*width[:-1], width[-1] + 1), s)), ("mutual_scales", (s, torch.rand(*width)[..., :-1])),
+                           ("direct_scales", (torch.rand(2, *width), None)), ("mutual_scales", (None, torch.ones(width, dtype=torch.float16)))):
+            with pytest.raises(ValueError, match=name):
+                call(pos, q, mu, *args, cells, **lists)
+        with pytest.raises(ValueError, match="both None"):
+            call(pos, q, mu, None, None, cells, **lists)
+        with pytest.raises(ValueError, match="charges"):
+            call(pos, q[:-1], mu, s, s, cells, **lists)
+        with pytest.raises(ValueError, match="dipoles"):
+            call(pos, q, mu[:-1], s, s, cells, **lists)
+        with pytest.raises(ValueError, match="polarizability"):
+            call(pos, q, mu, s, s, cells, polarizability=pol[:-1], thole=0.39, **lists)
+        with pytest.raises(ValueError, match="thole needs the polarizability"):
+            call(pos, q, mu, s, s, cells, thole=0.39, **lists)
+        with pytest.raises(ValueError, match="batch_idx"):
+            call(pos, q, mu, s, s, cells.repeat(B, 1, 1), batch_idx=bi[:-1], **lists)
+        with pytest.raises(ValueError, match="minimum_image takes a list without shifts"):
+            call(pos, q, mu, s, s, cells, minimum_image=True, **lists)
+    with pytest.raises(ValueError, match="neighbor_matrix"):
+        call(pos, q, mu, torch.rand(N - 1, M), None, cells, neighbor_matrix=nm[:-1], neighbor_matrix_shifts=nsh[:-1])
+    with pytest.raises(ValueError, match="neighbor_ptr"):
+        call(pos, q, mu, torch.rand(7), None, cells, neighbor_list=lst, neighbor_ptr=ptr[:-1], neighbor_shifts=lsh)
+    with pytest.raises(ValueError, match="minimum_image needs a cell"):
+        call(pos, q, mu, torch.rand(N, M), None, neighbor_matrix=nm, minimum_image=True)
+
+
+def test_well_formed_cpu_arguments_of_the_three_newest_families_stop_at_the_device_check():
+    """The control of the four tests above."""
+    from nvalchemiops import _capi as C
+    from nvalchemiops.interactions import ReducedSites, ewald_dispersion_reciprocal_space
+    from nvalchemiops.interactions.electrostatics import dipole_pair_scale_correction as dps
+
+    pos, cell, _, bi = _geometry()
+    nm, nsh, lst, ptr, lsh = _neighbour_inputs()
+    r, e, mu = torch.rand(N) + 1.0, torch.rand(N), torch.rand(N, 3)
+    cellb = cell[None].repeat(B, 1, 1)
+    sites = ReducedSites(torch.tensor([-1, 0, 0, -1, 3], dtype=I32), torch.full((N,), 0.9), batch_idx=bi)
+    matrix, csr = dict(neighbor_matrix=nm, neighbor_matrix_shifts=nsh), dict(neighbor_list=lst, neighbor_ptr=ptr, neighbor_shifts=lsh)
+    calls = [lambda c=c: c(pos, r, e, cellb, batch_idx=bi, sites=sites, pair_scales=torch.rand(N, M), **matrix) for c in _vdw_calls().values()]
+    calls += [lambda c=c: c(pos, r, e, cellb, batch_idx=bi, sites=sites, pair_scales=torch.rand(7, dtype=torch.float64), **csr) for c in _vdw_calls().values()]
+    calls += [lambda c=c, lists=lists: c(pos, e, cellb, torch.tensor([0.3, 0.4]), batch_idx=bi, **lists) for c in _dispersion_ewald_calls().values() for lists in (matrix, csr)]
+    calls.append(lambda: ewald_dispersion_reciprocal_space(pos, e, cellb, torch.rand(2, 6, 3), torch.tensor([0.3, 0.4]), batch_idx=bi, compute_virial=True))
+    calls.append(lambda: dps(pos, e, mu, torch.rand(N, M), torch.rand(N, M), cellb, polarizability=r, thole=0.39, batch_idx=bi, **matrix))
+    calls.append(lambda: dps(pos, e, mu, None, torch.rand(7), cellb, batch_idx=bi, compute_forces=True, **csr))
+    for call in calls:
+        with pytest.raises(C.NativeLibraryError, match="ROCm devices only"):
+            call()

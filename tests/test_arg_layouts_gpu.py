@@ -105,7 +105,14 @@ With the `.contiguous()` of `pair_scales` taken out of `pair_scale._inputs` and 
 fail: `pair_scales` col and row (both list forms) and T (matrix) in float64, where `.to(float64)` is the tensor itself, and T alone in
 float32, where `.to()` copies a strided view into contiguous storage but keeps the strides of a dense transposed one; `dipole_grads` col,
 row and T in both dtypes (the torque forces move by about 10).  `off` and `flt` do not and cannot fail: an offset view is contiguous from
-its own pointer, and a dtype change copies.  DESIGN.md section 3.33."""
+its own pointer, and a dtype change copies.  DESIGN.md section 3.33.
+
+Van der Waals pairs, dispersion Ewald and scaled dipole pairs (fixtures `vdw`, `dispersion_ewald`, `dipole_scale` of tests/layout_cases.py;
+single system and batch, float32 and float64): buffered_14_7 and lennard_jones 38 (matrix) + 41 (CSR) / 43 + 46 each, with `parent` and
+`reduction` through the `ReducedSites` constructor; ewald_dispersion_real_space 23 + 27 / 30 + 34, ewald_dispersion_correction 28 + 32 / 35 + 39,
+ewald_dispersion_reciprocal_space 18 / 25; dipole_pair_scale_correction 40 + 42 / 45 + 47: 1 602 variants, plus the [3, 3] cell, the
+number / 0-dim alpha, [K, 3] / [1, K, 3] / stride-0 k-vectors, `None` forms and `ReducedSites.to()`.  MEASURED on one MI355X: every variant
+the BITS of the canonical call; 10 ops x 4 grad-output layouts bit-identical in each dtype.  DESIGN.md section 3.37."""
 import functools
 import re
 import types
@@ -2057,3 +2064,251 @@ def test_illegal_outputs_are_refused_and_left_untouched(batch):
                         assert bool((b == SENTINEL).all()), f"{name}: {names[i]} was written although {names[bad]} ({kind}) was refused"
                 _guarded(one, f"{name} {names[bad]} {kind}", fails)
     assert not fails, "\n".join(fails)
+
+
+# ==== van der Waals pairs, dispersion Ewald, scaled dipole pairs (fixtures `vdw`, `dispersion_ewald`, `dipole_scale` of tests/layout_cases.py) ==
+# Every variant against the BITS of the canonical call (forward and adjoint are one launch without atomics).  The canonical call is judged
+# against the restatement first: 1e-11 in float64; in float32 four times the restatement's own sensitivity to one ulp of every float32 r^2,
+# computed on the CPU from the restatement alone on this fixture (`nudge=True`), 1e-6 for the reciprocal half and for the scaled dipole pairs.
+
+def _judge(out, ref, names, bars, what):
+    assert len(out) == len(names)
+    for name, o in zip(names, out):
+        r = torch.as_tensor(np.asarray(ref[name]), dtype=F64)
+        scale, err = float(r.abs().max()), float((o.detach().cpu().to(F64) - r).abs().max())
+        assert err <= bars[name] * scale + 1e-14, f"{what} {name} vs the restatement: max err {err:.3e} > {bars[name] * scale + 1e-14:.3e}"
+
+
+def _stored_lists(c, scales=None, sdt=F64):
+    """((label, list keywords, plan, pair_scales | None, its plan), ...) of a case of tests/sweep_cases.py: the padded matrix and CSR."""
+    from tests import sweep_cases as W
+
+    i, j, S = c["entries"]
+    n = len(c["pos"])
+    nm, sh, val = W.padded_matrix(c["entries"], n, scales)
+    ptr = np.zeros(n + 1, np.int32)
+    ptr[1:] = np.cumsum(np.bincount(i, minlength=n))
+    return (("matrix", dict(neighbor_matrix=_t(nm, I32), neighbor_matrix_shifts=_t(sh, I32), mask_value=n), dict(neighbor_matrix=MAT, neighbor_matrix_shifts=MAT),
+             None if scales is None else _t(val, sdt), SCL_M),
+            ("csr", dict(neighbor_list=_t(np.stack([i, j]), I32), neighbor_ptr=_t(ptr), neighbor_shifts=_t(S, I32)),
+             dict(neighbor_list=MAT, neighbor_ptr=IDX, neighbor_shifts=MAT), None if scales is None else _t(scales, sdt), SCL_L))
+
+
+def _two_copies(c):
+    """The single-system case twice, as a batch of two systems in the same cell (for the stride-0 forms)."""
+    n, (i, j, S) = len(c["pos"]), c["entries"]
+    d = dict(c, entries=(np.concatenate([i, i + n]), np.concatenate([j, j + n]), np.concatenate([S, S])), batch_idx=np.repeat(np.arange(2, dtype=np.int32), n),
+             cells=np.concatenate([c["cells"], c["cells"]]), sizes=(n, n))
+    for k in ("pos", "radii", "eps", "kappa", "c", "scales"):
+        if c.get(k) is not None:
+            d[k] = np.concatenate([c[k], c[k]])
+    if c.get("parent") is not None:
+        d["parent"] = np.concatenate([c["parent"], np.where(c["parent"] >= 0, c["parent"] + n, -1)])
+    if "alpha" in c:
+        d["alpha"] = np.concatenate([c["alpha"], c["alpha"]])
+    return d
+
+
+@DTYPES
+@pytest.mark.parametrize("batch", [False, True])
+@pytest.mark.parametrize("kind", ["buffered_14_7", "lennard_jones"])
+@_collecting
+def test_vdw_pair_potentials(kind, batch, dtype):
+    """`radii`, `epsilons`, `pair_scales` (in the float dtype the positions do NOT have, [N, M] and [nnz]), `parent` and `reduction` through the
+    `ReducedSites` constructor, `ReducedSites.to()`, the cell as [3, 3] / [1, 3, 3] / stride-0, `pair_scales=None` and `sites=None`."""
+    from nvalchemiops import interactions as IA
+    from tests import sweep_cases as W
+
+    c = LC.vdw(batch, kind)
+    tdt = F32 if dtype == "float32" else F64
+    sdt = F64 if tdt == F32 else F32
+    c = dict(c, scale_dtype="float32" if sdt == F32 else "float64")
+    flags = {f: True for f in W.VDW_FLAGS}
+    ref = W.vdw_reference(c, kind, tdt)
+    bars = dict.fromkeys(W.VDW_NAMES, 1e-11) if tdt == F64 else {
+        k: 4.0 * v for k, v in zip(W.VDW_NAMES, W.f32_figures(ref, W.vdw_reference(c, kind, tdt, nudge=True), W.VDW_NAMES))}
+    tag = f"{kind} {dtype}{' batch' if batch else ''}"
+
+    def call(parent, reduction, **a):
+        sites = IA.ReducedSites(parent, reduction, batch_idx=a.get("batch_idx"))
+        return getattr(IA, kind)(**a, sites=sites, **W.vdw_model(c, kind), **flags)
+
+    def atoms_of(c):
+        a = dict(positions=_t(c["pos"], tdt), radii=_t(c["radii"], tdt), epsilons=_t(c["eps"], tdt), cell=_t(c["cells"], tdt), parent=_t(c["parent"], I32),
+                 reduction=_t(c["kappa"], tdt))
+        if len(c["sizes"]) > 1:
+            a["batch_idx"] = _t(c["batch_idx"], I32)
+        return a
+
+    atoms = atoms_of(c)
+    aplan = dict(positions=POS, radii=VEC, epsilons=VEC, cell=CELLB if batch else CELL1, parent=IDX, reduction=VEC)
+    if batch:
+        aplan["batch_idx"] = IDX
+    for label, lists, lplan, s, splan in _stored_lists(c, c["scales"], sdt):
+        kw = dict(atoms, pair_scales=s, **lists)
+        out = _tuple(call(**kw))
+        _judge(out, ref, W.VDW_NAMES, bars, f"{tag} {label}")
+        _swept(f"{tag} {label}", call, kw, dict(aplan, pair_scales=splan, **lplan), _exact, ref=out)
+        if not batch:  # one cell as [3, 3]
+            _compare(_tuple(call(**dict(kw, cell=kw["cell"][0]))), out, _exact, f"{tag} {label}[cell: [3, 3]]")
+        # None inputs against what they stand for: unit scales, a table of -1
+        ones = torch.where(torch.isnan(s), s, torch.ones_like(s))
+        _compare(_tuple(call(**dict(kw, pair_scales=None))), _tuple(call(**dict(kw, pair_scales=ones))), _exact, f"{tag} {label}[pair_scales: None]")
+        free = dict(kw)
+        del free["parent"], free["reduction"]
+        nosites = _tuple(getattr(IA, kind)(**free, sites=None, **W.vdw_model(c, kind), **flags))
+        _compare(nosites, _tuple(call(**dict(kw, parent=torch.full_like(kw["parent"], -1)))), _exact, f"{tag} {label}[sites: None]")
+        assert not torch.equal(nosites[0], out[0])
+        # a table built on the host and moved
+        host = IA.ReducedSites(kw["parent"].cpu(), kw["reduction"].cpu(), batch_idx=None if not batch else kw["batch_idx"].cpu()).to(DEV)
+        _compare(_tuple(getattr(IA, kind)(**free, sites=host, **W.vdw_model(c, kind), **flags)), out, _exact, f"{tag} {label}[ReducedSites.to()]")
+    if not batch:  # the same cell for two systems: a stride-0 expansion against the repeated cell
+        c2 = _two_copies(c)
+        label, lists, _, s, _ = _stored_lists(c2, c2["scales"], sdt)[0]
+        _sweep_shared(f"{tag} two copies", call, dict(atoms_of(c2), pair_scales=s, **lists), ("cell",), _exact)
+
+
+@DTYPES
+@pytest.mark.parametrize("batch", [False, True])
+@_collecting
+def test_dispersion_ewald(batch, dtype):
+    """`coefficients`, `k_vectors` as [K, 3] / [1, K, 3] / [B, K, 3], `alpha` as a number, a 0-dim tensor and a [B] tensor, the cell as [3, 3] /
+    [1, 3, 3] / stride-0, `k_vectors=None` against an empty set, for the three `ewald_dispersion_*` functions."""
+    from nvalchemiops import interactions as IA
+    from tests import sweep_cases as W
+
+    c = LC.dispersion_ewald(batch)
+    tdt = F32 if dtype == "float32" else F64
+    flags = {f: True for f in W.DE_FLAGS}
+    tag = f"ewald_dispersion {dtype}{' batch' if batch else ''}"
+    counted = {} if c["counted"] is None else dict(counted_cutoff=c["counted"][0], counted_taper=c["counted"][1])
+    refs = {h: W.dispersion_reference(c, h, tdt) for h in ("real", "recip", "sum")}
+    real_bar = dict.fromkeys(W.DE_NAMES, 1e-11) if tdt == F64 else {
+        k: 4.0 * v for k, v in zip(W.DE_NAMES, W.f32_figures(refs["real"], W.dispersion_reference(c, "real", tdt, nudge=True), W.DE_NAMES))}
+    recip_bar = dict.fromkeys(W.DE_NAMES, 1e-11 if tdt == F64 else 1e-6)
+    sum_bar = {k: max(real_bar[k], recip_bar[k]) for k in W.DE_NAMES}
+
+    def atoms_of(c):
+        a = dict(positions=_t(c["pos"], tdt), coefficients=_t(c["c"], tdt), cell=_t(c["cells"], tdt), alpha=_t(c["alpha"], tdt))
+        if len(c["sizes"]) > 1:
+            a["batch_idx"] = _t(c["batch_idx"], I32)
+        return a
+
+    atoms, kv = atoms_of(c), c["k_vectors"].to(DEV).to(tdt).contiguous()
+    aplan = dict(positions=POS, coefficients=VEC, cell=CELLB if batch else CELL1, alpha=VEC if batch else "off flt")
+    if batch:
+        aplan["batch_idx"] = IDX
+    real = lambda **a: IA.ewald_dispersion_real_space(**a, **counted, **flags)  # noqa: E731
+    recip = lambda **a: IA.ewald_dispersion_reciprocal_space(**a, **flags)  # noqa: E731
+    both = lambda **a: IA.ewald_dispersion_correction(**a, **counted, **flags)  # noqa: E731
+    for label, lists, lplan, _, _ in _stored_lists(c):
+        for name, fn, extra, xplan, half, bars in (("real_space", real, {}, {}, "real", real_bar), ("correction", both, dict(k_vectors=kv), dict(k_vectors=DIP), "sum", sum_bar)):
+            kw = dict(atoms, **lists, **extra)
+            out = _tuple(fn(**kw))
+            _judge(out, refs[half], W.DE_NAMES, bars, f"{tag} {name} {label}")
+            _swept(f"{tag} {name} {label}", fn, kw, dict(aplan, **lplan, **xplan), _exact, ref=out)
+    kw = dict(atoms, k_vectors=kv)
+    out = _tuple(recip(**kw))
+    _judge(out, refs["recip"], W.DE_NAMES, recip_bar, f"{tag} reciprocal_space")
+    _swept(f"{tag} reciprocal_space", recip, kw, dict(aplan, k_vectors=DIP), _exact, ref=out)
+    empty = _tuple(recip(**dict(kw, k_vectors=kv[:, :0])))
+    _compare(_tuple(recip(**dict(kw, k_vectors=None))), empty, _exact, f"{tag} reciprocal_space[k_vectors: None]")
+    assert not torch.equal(empty[0], out[0])
+    if not batch:
+        a0 = float(c["alpha"][0])
+        for what, form in (("cell: [3, 3]", dict(cell=kw["cell"][0])), ("k_vectors: [K, 3]", dict(k_vectors=kv[0])), ("k_vectors: [K, 3] offset", dict(k_vectors=_variant(kv[0], "off"))),
+                           ("alpha: number", dict(alpha=a0)), ("alpha: 0-dim", dict(alpha=torch.tensor(a0, dtype=tdt, device=DEV)))):
+            _compare(_tuple(recip(**dict(kw, **form))), out, _exact, f"{tag} reciprocal_space[{what}]")
+        label, lists, _, _, _ = _stored_lists(c)[1]
+        rout = _tuple(real(**atoms, **lists))
+        for what, form in (("cell: [3, 3]", dict(cell=kw["cell"][0])), ("alpha: number", dict(alpha=a0)), ("alpha: 0-dim", dict(alpha=torch.tensor(a0, dtype=tdt, device=DEV)))):
+            _compare(_tuple(real(**dict(atoms, **lists, **form))), rout, _exact, f"{tag} real_space[{what}]")
+        # two systems in one cell: stride-0 cell and alpha, k_vectors [1, K, 3] and its stride-0 expansion against the repeated [2, K, 3]
+        c2 = _two_copies(c)
+        a2, kv2 = atoms_of(c2), kv.repeat(2, 1, 1).contiguous()
+        _sweep_shared(f"{tag} real_space two copies", real, dict(a2, **_stored_lists(c2)[0][1]), ("cell", "alpha"), _exact)
+        _sweep_shared(f"{tag} reciprocal_space two copies", recip, dict(a2, k_vectors=kv2), ("cell", "alpha", "k_vectors"), _exact)
+        _compare(_tuple(recip(**dict(a2, k_vectors=kv))), _tuple(recip(**dict(a2, k_vectors=kv2))), _exact, f"{tag} reciprocal_space two copies[k_vectors: [1, K, 3]]")
+        _compare(_tuple(recip(**dict(a2, alpha=a0, k_vectors=kv2))), _tuple(recip(**dict(a2, k_vectors=kv2))), _exact, f"{tag} reciprocal_space two copies[alpha: number]")
+
+
+@DTYPES
+@pytest.mark.parametrize("batch", [False, True])
+@_collecting
+def test_dipole_pair_scale_correction(batch, dtype):
+    """`direct_scales` and `mutual_scales` ([N, M] and [nnz], in the float dtype the positions do not have), `polarizability`, the dipoles and the
+    lists of `dipole_pair_scale_correction`, Thole-damped; a scale array that is None against unit scales."""
+    from nvalchemiops.interactions.electrostatics import dipole_pair_scale_correction
+    from tests import dipole_scale_cases as SC
+    from tests import test_dipole_scale_gpu as TDS
+
+    p = LC.dipole_scale(batch)
+    tdt = F32 if dtype == "float32" else F64
+    sdt = F64 if tdt == F32 else F32
+    ref = LC.dipole_scale_reference(batch, SC.A_T, tdt)
+    bars = dict.fromkeys(TDS.NAMES, 1e-11 if tdt == F64 else 1e-6)
+    n, (i, j, S) = p["n"], p["entries"]
+    sd, sm = torch.as_tensor(p["sd"]), torch.as_tensor(p["sm"])
+    nm, sh, dnm, mnm = SC.matrix(i, j, n, int(torch.bincount(i, minlength=n).max()) + 3, (S, sd, sm), fill=0.5)
+    ptr = torch.zeros(n + 1, dtype=I32)
+    ptr[1:] = torch.cumsum(torch.bincount(i, minlength=n), 0)
+    d = lambda t, dt=None: t.to(DEV).to(dt or t.dtype).contiguous()  # noqa: E731
+    atoms = dict(positions=_t(p["pos"], tdt), charges=_t(p["q"], tdt), dipoles=_t(p["mu"], tdt), polarizability=_t(p["polar"], tdt), cell=_t(p["cell"], tdt))
+    aplan = dict(positions=POS, charges=VEC, dipoles=DIP, polarizability=VEC, cell=CELLB if batch else CELL1)
+    if batch:
+        atoms["batch_idx"], aplan["batch_idx"] = _t(p["batch_idx"], I32), IDX
+    call = lambda **a: dipole_pair_scale_correction(**a, thole=SC.A_T, compute_virial=True, **TDS.ALL)  # noqa: E731
+    tag = f"dipole_pair_scale_correction {dtype}{' batch' if batch else ''}"
+    for label, lists, lplan, scales, splan in (
+            ("matrix", dict(neighbor_matrix=d(nm, I32), neighbor_matrix_shifts=d(sh, I32), mask_value=n), dict(neighbor_matrix=MAT, neighbor_matrix_shifts=MAT),
+             (d(dnm, sdt), d(mnm, sdt)), SCL_M),
+            ("csr", dict(neighbor_list=d(torch.stack([i, j]), I32), neighbor_ptr=d(ptr), neighbor_shifts=d(S, I32)),
+             dict(neighbor_list=MAT, neighbor_ptr=IDX, neighbor_shifts=MAT), (d(sd, sdt), d(sm, sdt)), SCL_L)):
+        kw = dict(atoms, direct_scales=scales[0], mutual_scales=scales[1], **lists)
+        out = _tuple(call(**kw))
+        _judge(out, ref, TDS.NAMES, bars, f"{tag} {label}")
+        _swept(f"{tag} {label}", call, kw, dict(aplan, direct_scales=splan, mutual_scales=splan, **lplan), _exact, ref=out)
+        for absent in ("direct_scales", "mutual_scales"):
+            _compare(_tuple(call(**dict(kw, **{absent: None}))), _tuple(call(**dict(kw, **{absent: torch.ones_like(kw[absent])}))), _exact, f"{tag} {label}[{absent}: None]")
+        if not batch:
+            _compare(_tuple(call(**dict(kw, cell=kw["cell"][0]))), out, _exact, f"{tag} {label}[cell: [3, 3]]")
+
+
+@DTYPES
+def test_gradient_layouts_of_the_vdw_dispersion_ewald_and_dipole_scale_ops(dtype):
+    """Caller gradients of the autograd ops of the three families on the batch fixtures: every grad-output layout against the bits of the contiguous backward."""
+    from nvalchemiops import interactions as IA
+    from nvalchemiops.interactions.electrostatics import dipole_pair_scale_correction
+    from tests import dipole_scale_cases as SC
+    from tests import sweep_cases as W
+
+    tdt = F32 if dtype == "float32" else F64
+    ops = {}
+    for kind in ("buffered_14_7", "lennard_jones"):
+        c = LC.vdw(True, kind)
+        bi = _t(c["batch_idx"], I32)
+        sites = IA.ReducedSites(_t(c["parent"], I32), _t(c["kappa"], tdt), batch_idx=bi)
+        for label, lists, _, s, _ in _stored_lists(c, c["scales"], F64):
+            ops[f"{kind} {label}"] = (lambda p, r, e, kind=kind, c=c, bi=bi, sites=sites, lists=lists, s=s: getattr(IA, kind)(
+                p, r, e, _t(c["cells"], tdt), sites=sites, pair_scales=s, batch_idx=bi, **lists, **W.vdw_model(c, kind)),
+                (_t(c["pos"], tdt), _t(c["radii"], tdt), _t(c["eps"], tdt)), ("positions", "radii", "epsilons"), _exact)
+    c = LC.dispersion_ewald(True)
+    bi, cell, al, kv = _t(c["batch_idx"], I32), _t(c["cells"], tdt), _t(c["alpha"], tdt), c["k_vectors"].to(DEV).to(tdt)
+    leaves, names = (_t(c["pos"], tdt), _t(c["c"], tdt)), ("positions", "coefficients")
+    counted = dict(counted_cutoff=c["counted"][0], counted_taper=c["counted"][1])
+    for label, lists, _, _, _ in _stored_lists(c):
+        ops[f"ewald_dispersion_real_space {label}"] = (lambda p, q, lists=lists: IA.ewald_dispersion_real_space(p, q, cell, al, batch_idx=bi, **lists, **counted), leaves, names, _exact)
+        ops[f"ewald_dispersion_correction {label}"] = (lambda p, q, lists=lists: IA.ewald_dispersion_correction(p, q, cell, al, k_vectors=kv, batch_idx=bi, **lists, **counted),
+                                                       leaves, names, _exact)
+    ops["ewald_dispersion_reciprocal_space"] = (lambda p, q: IA.ewald_dispersion_reciprocal_space(p, q, cell, kv, al, batch_idx=bi), leaves, names, _exact)
+    p = LC.dipole_scale(True)
+    i, j, S = p["entries"]
+    ptr = torch.zeros(p["n"] + 1, dtype=I32)
+    ptr[1:] = torch.cumsum(torch.bincount(i, minlength=p["n"]), 0)
+    lists = dict(neighbor_list=torch.stack([i, j]).to(DEV).int().contiguous(), neighbor_ptr=ptr.to(DEV), neighbor_shifts=S.to(DEV).int().contiguous())
+    sd, sm, pbi, pcell = _t(p["sd"], F64), _t(p["sm"], F64), _t(p["batch_idx"], I32), _t(p["cell"], tdt)
+    polar = np.where(np.isnan(p["polar"]), 0.0, p["polar"])  # (a NaN polarisability has a NaN gradient slot: no layout question)
+    ops["dipole_pair_scale_correction csr"] = (lambda x, q, m, a: dipole_pair_scale_correction(x, q, m, sd, sm, pcell, polarizability=a, thole=SC.A_T, batch_idx=pbi, **lists),
+                                               (_t(p["pos"], tdt), _t(p["q"], tdt), _t(p["mu"], tdt), _t(polar, tdt)), ("positions", "charges", "dipoles", "polarizability"), _exact)
+    _check_gradient_layouts(ops)
+    print(f"[layouts] gradient layouts {dtype}: {len(ops)} ops x 4 grad-output layouts, every gradient bit-identical to the contiguous backward")

@@ -128,3 +128,69 @@ def test_eager_call_and_custom_op_are_bit_identical(name, layout, dtype):
         assert torch.isfinite(a).all(), f"output {i} of the eager call is not finite"
         assert torch.equal(a.view(torch.int32), b.view(torch.int32)), f"output {i}: eager call and custom op differ by {(a - b).abs().max().item():.3e}"
     assert float(eager[0].abs().min()) > 0 and float(eager[-1].abs().max()) > 0  # both systems have an energy, and there is a virial
+
+
+# ---- van der Waals pairs and the dispersion Ewald sum: the `VDW_OPS` and `ewald_dispersion_*_op` rows of _eops.py -------------------------------
+# Their ops are written as the dispersion ops above are (one forward / backward pair, outputs not asked for as empty [0] tensors), so they are
+# compared here: the eager `_forward` against the op, bit for bit, and the op's backward against the adjoint function.  The input is the batch
+# fixture of tests/layout_cases.py (three cells of their own, reduced sites, scales, per-system alpha and k-vectors).
+def _family_args(family, dtype, fmt):
+    """(public function, op, forward, adjoint, number of differentiable inputs, the op's arguments before the flags, the number of flags)."""
+    import importlib
+
+    from nvalchemiops import _eops
+    from nvalchemiops import interactions as IA
+    from tests import layout_cases as LC
+    from tests import sweep_cases as W
+
+    t = lambda a, dt=None: torch.as_tensor(np.ascontiguousarray(a), device=DEV, dtype=dt)  # noqa: E731
+    vdw = family in W.VDW_KINDS
+    c = LC.vdw(True, family) if vdw else LC.dispersion_ewald(True)
+    i, j, S = c["entries"]
+    n = len(c["pos"])
+    bi = t(c["batch_idx"], torch.int32)
+    if fmt == "matrix":
+        nm, sh, val = W.padded_matrix(c["entries"], n, c["scales"] if vdw else None)
+        lists, mask, scales = (None, None, None, t(nm, torch.int32), t(sh, torch.int32)), n, val
+    else:
+        ptr = np.zeros(n + 1, np.int32)
+        ptr[1:] = np.cumsum(np.bincount(i, minlength=n))
+        lists, mask, scales = (t(np.stack([i, j]), torch.int32), t(ptr), t(S, torch.int32), None, None), -1, c["scales"] if vdw else None
+    if vdw:
+        kind = W.VDW_KINDS.index(family)
+        pair = importlib.import_module("nvalchemiops.interactions.vdw.pair")
+        sites = IA.ReducedSites(t(c["parent"], torch.int32), t(c["kappa"], dtype), batch_idx=bi)
+        m = W.vdw_model(c, family)
+        args = (t(c["pos"], dtype), t(c["radii"], dtype), t(c["eps"], dtype), t(c["cells"], dtype), bi, sites.parent, sites.reduction, sites.child_ptr,
+                sites.child_idx, t(scales, torch.float64), *lists, mask, float(m["cutoff"]), float(m["taper"]), float(m.get("delta", 1.0)),
+                float(m.get("gamma", 1.0)), pair.RADIUS_RULES[m["radius_rule"]], pair.EPSILON_RULES[m["epsilon_rule"]])
+        return (_eops.VDW_OPS[kind], functools.partial(pair._forward, kind), functools.partial(pair._adjoint, kind), 3, args, 4)
+    ew = importlib.import_module("nvalchemiops.interactions.vdw.ewald")
+    head = (t(c["pos"], dtype), t(c["c"], dtype), t(c["cells"], dtype))
+    alpha = t(c["alpha"], dtype)
+    if family == "ewald_dispersion_real_space":
+        return (_eops.ewald_dispersion_real_space_op, ew._real_forward, ew._real_adjoint, 2,
+                (*head, alpha, bi, *lists, mask, float(c["counted"][0]), -1.0 if c["counted"][1] is None else float(c["counted"][1])), 3)
+    return (_eops.ewald_dispersion_reciprocal_space_op, ew._recip_forward, ew._recip_adjoint, 2, (*head, c["k_vectors"].to(DEV).to(dtype), alpha, bi), 3)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("family,fmt", [(f, m) for f in ("buffered_14_7", "lennard_jones", "ewald_dispersion_real_space") for m in ("matrix", "csr")]
+                         + [("ewald_dispersion_reciprocal_space", "none")])
+def test_vdw_and_dispersion_ewald_ops_match_the_eager_path_and_the_adjoint(family, fmt, dtype):
+    op, forward, adjoint, n_diff, args, n_flags = _family_args(family, dtype, fmt)
+    for flags in ((True,) * n_flags, (False,) * n_flags, (False,) * (n_flags - 1) + (True,)):
+        eager, direct = forward(*args, *flags), op(*args, *flags)
+        assert len(eager) == len(direct) == n_flags + 1
+        for k, (e, d, want) in enumerate(zip(eager, direct, (True,) + flags)):
+            if not want:
+                assert e is None and tuple(d.shape) == (0,), f"{family} output {k}: not asked for"
+                continue
+            assert e.dtype == d.dtype == dtype and float(e.abs().max()) > 0 and torch.equal(e, d), f"{family} {fmt} flags {flags}: output {k} differs"
+    leaves = [a.clone().requires_grad_(True) for a in args[:n_diff]]
+    g = torch.as_tensor(np.random.default_rng(5).normal(size=leaves[0].shape[0]), device=DEV).to(dtype)
+    grads = torch.autograd.grad(op(*leaves, *args[n_diff:], *(False,) * n_flags)[0], leaves, grad_outputs=g)
+    ref = adjoint(*args, g)
+    assert len(grads) == len(ref) == n_diff
+    for k, (got, r) in enumerate(zip(grads, ref)):
+        assert r.dtype == torch.float64 and float(r.abs().max()) > 0 and torch.equal(got, r.to(dtype)), f"{family} {fmt}: gradient {k} differs from the adjoint's"

@@ -65,3 +65,32 @@ def test_series_and_direct_branch_of_one_minus_g_agree_across_the_threshold():
     assert abs(float(below - above)) <= 4.0 * torch.finfo(F64).eps
     tiny = torch.tensor([1e-4], dtype=F64)
     assert abs(float(R.one_minus_g(tiny)) / (1e-12 / 6.0 * (1.0 - 0.75e-4)) - 1.0) <= 1e-7  # a^6 / 6 (1 - 3 a^2 / 4 + ...)
+
+
+def test_counted_cutoff_without_a_taper_is_the_limit_of_a_narrow_one():
+    """counted = (rc, None): the step at rc, what a taper window of 1e-9 gives on entries outside it; and not the plain sum."""
+    from tests import sweep_cases as W
+
+    c = W.dispersion_case("sweep", 5)
+    rc = c["counted"][0]
+    assert c["counted"][1] is None
+    a = W.dispersion_reference(c, "real", torch.float64)
+    b = W.dispersion_reference(dict(c, counted=(rc, rc - 1e-9)), "real", torch.float64)
+    plain = W.dispersion_reference(dict(c, counted=None), "real", torch.float64)
+    for k in W.DE_NAMES:
+        assert torch.equal(a[k], b[k]) and not torch.equal(a[k], plain[k]), k
+
+
+def test_a_k_vector_below_the_threshold_weighs_nothing():
+    """|k|^2 < 1e-10: the restatement on the edge case's set with (1e-6, 0, 0) appended is the restatement on the set without it, every output;
+    a vector just above the threshold does weigh."""
+    from tests import sweep_cases as W
+
+    c = W.dispersion_case("edge")
+    plain = W.dispersion_reference(c, "recip", torch.float64)
+    tiny = W.dispersion_reference(dict(c, k_vectors=c["k_tiny"]), "recip", torch.float64)
+    above = torch.cat([c["k_vectors"], torch.tensor([[[2e-5, 0.0, 0.0]]], dtype=torch.float64)], dim=1)
+    heavy = W.dispersion_reference(dict(c, k_vectors=above), "recip", torch.float64)
+    for k in W.DE_NAMES:
+        assert torch.equal(plain[k], tiny[k]), k
+    assert not torch.equal(plain["energies"], heavy["energies"])

@@ -1,7 +1,8 @@
 """Sizes beyond one trip of the per-system folds of `dftd4`, `dftd4_atm`, `gaussian_charge_correction`, `charge_equilibration`,
 `ewald_dipole_real_space`, `ewald_real_space_with_virial`, `ewald_quadrupole_real_space`, `thole_dipole_correction`, `induced_dipoles`,
 `thole_induced_dipoles`, `pair_scale_correction`, `rotate_multipoles` / `multipole_frame_forces`, `coulomb_dipole_correction`,
-`coulomb_quadrupole_correction` (as periodic cut-off sums) and `cluster_induced_dipoles`.
+`coulomb_quadrupole_correction` (as periodic cut-off sums), `cluster_induced_dipoles`, `buffered_14_7`, `lennard_jones`,
+`ewald_dispersion_real_space`, `ewald_dispersion_reciprocal_space` and `dipole_pair_scale_correction`.
 
 Every per-system sum of these ops is the fixed-order fold of csrc/pair_row.h (`mi_system_fold`) on a grid of (blocks, systems) blocks of
 256 threads, each looping `r += blocks * 256` over ALL N rows and keeping those of its system: `d4_fold_kernel` (also `dftd4_atm`'s),
@@ -96,6 +97,18 @@ stride-0 cell; gaussian virial 3.6e-15 and 5.3e-15 absolute (1.1e-9 and 1.8e-9 o
   cluster_induced_dipoles  150 atoms (K 164, N 24 600): max|mu - mu_ref| 6.1e-12 undamped and 2.7e-11 damped, as one system (bars 1.4e-7)
              and in the worst system of the batch (bars 1.1e-8); 8 / 15 iterations in the small call, the single system and all 164
              systems of the batch (reference PCG: 8 / 15)
+  vdw        60 atoms with sites and scales (K 410, N 24 600): small call at the 1e-11 of tests/test_vdw_gpu.py; virial as one system
+             2.3e-13 / 7.1e-15 (14-7 / LJ: 1.7e-10 / 4.9e-12 of the bar), in the batch 1.8e-15 / 3.6e-15 (5.3e-10 / 1.0e-9 of the bar), both
+             cell forms.  With `vdw_fold_kernel` and `de_fold_kernel` cut to their first trip (a scratch build, all reads in range) the
+             one-system virials of both kinds and of the dispersion real half are off by 2.1e6 bars -- six tests fail -- and
+             tests/test_vdw_gpu.py and tests/test_dispersion_ewald_gpu.py still pass (17 tests).
+  dispersion real space, counted (4.0, 3.6)  60 atoms listed to 4.5 (K 410, N 24 600): virial as one system 2.8e-14 (2.5e-10 of the bar),
+             in the batch 2.2e-16 (8.1e-10 of the bar), both cell forms
+  dispersion reciprocal space  410 systems of 60 atoms, 7 k-vectors, four or five systems per atom tile over 97 tiles: against the small
+             call relative to max|small| (bar 1e-11) energies 8.7e-16, forces 1.2e-15, coefficient gradients 6.4e-16, virial 7.6e-16,
+             both cell forms
+  dipole pair scale  24 atoms (K 1025, N 24 600): virial as one system 2.3e-13 bare / 1.1e-13 damped (1.1e-9 / 7.6e-10 of the bar), in
+             the batch 1.1e-16 / 2.2e-16 (5.3e-10 / 1.5e-9 of the bar), both cell forms
 Matrix and CSR agree to the digits shown; per-atom outputs bit-identical wherever that is asserted."""
 import functools
 import math
@@ -109,10 +122,13 @@ from tests import d4_atm_cases as K3
 from tests import d4_cases as K4
 from tests import pair_scale_reference as PR
 from tests import qeq_reference as QR
+from tests import sweep_cases as W
 from tests import test_cluster_multipole_gpu as TCM
 from tests import test_d4_atm_gpu as TD4A
 from tests import test_d4_gpu as TD4
 from tests import test_dipole_gpu as TDP
+from tests import test_dipole_scale_gpu as TDS
+from tests import test_dispersion_ewald_gpu as TDE
 from tests import test_electrostatic_virial_gpu as TV
 from tests import test_gaussian_charges_gpu as TG
 from tests import test_induced_gpu as TI
@@ -121,6 +137,7 @@ from tests import test_pair_scale_gpu as TPS
 from tests import test_qeq_gpu as TQ
 from tests import test_quadrupole_gpu as TQD
 from tests import test_thole_gpu as TTH
+from tests import test_vdw_gpu as TVW
 from tests import thole_cases as TC
 
 pytestmark = pytest.mark.gpu
@@ -752,3 +769,141 @@ def test_cluster_induced_dipoles_copies_as_one_system_and_as_a_batch(fmt, damped
     assert many.iterations.tolist() == out.iterations.tolist() * k
     energy = many.polarization_energy
     assert bool(((energy - out.polarization_energy).abs() <= 100.0 * tol * out.polarization_energy.abs() + 1e-14).all())
+
+
+# ---- buffered_14_7 / lennard_jones / ewald_dispersion_* -----------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("fmt", ["matrix", "list"])
+@pytest.mark.parametrize("kind", TVW.R.KINDS)
+def test_vdw_copies_as_one_system_and_as_a_batch(kind, fmt):
+    """`vdw_fold_kernel`: the 60-atom periodic box of tests/test_vdw_gpu.py with its reduced sites and scales, every flag; the parent table is
+    tiled with the atoms (a parent of -1 stays -1)."""
+    from nvalchemiops import _capi as C
+    from nvalchemiops.interactions import ReducedSites
+
+    f = TVW.periodic()
+    n0, blocks = f["n"], int(C.lib().mi_vdw_blocks())
+    k = _copies(n0, blocks)
+    n = k * n0
+    assert n > 256 * blocks and n % 64 != 0
+    small = TVW._compare(f, kind, F64, "matrix" if fmt == "matrix" else "csr", True, f"fold sizes vdw {fmt}: the small call")  # at its 1e-11
+    pos, radii, eps = _tiled_atoms([TVW._t(f[x], F64) for x in ("pos", "radii", "eps")], k)
+    par = TVW._t(f["sites"][0]).long()
+    off = torch.arange(k, device=DEV)[:, None] * n0
+    parent = torch.where(par[None] >= 0, par[None] + off, torch.full_like(par[None], -1)).reshape(-1).to(torch.int32)
+    kappa = TVW._t(f["sites"][1], F64).repeat(k)
+    if fmt == "matrix":
+        nm, sh = _tile_matrix(TVW._t(f["nm"]), f["sh"], k)
+        lists = dict(neighbor_matrix=nm, neighbor_matrix_shifts=sh, mask_value=n, pair_scales=TVW._t(f["ms"], F64).repeat(k, 1))
+    else:
+        lst, ptr, lsh = _tile_csr(TVW._t(f["nl"]), f["ptr"], f["lsh"], k)
+        lists = dict(neighbor_list=lst, neighbor_ptr=ptr, neighbor_shifts=lsh, pair_scales=TVW._t(f["ls"], F64).repeat(k))
+    flags = dict(compute_forces=True, compute_radius_gradients=True, compute_epsilon_gradients=True, compute_virial=True)
+
+    def call(cell, bi):
+        return TVW.FN[kind](pos, radii, eps, cell, cutoff=f["cutoff"], taper=f["taper"], sites=ReducedSites(parent, kappa, batch_idx=bi), batch_idx=bi, **lists, **flags)
+
+    bi = torch.arange(k, device=DEV, dtype=torch.int32).repeat_interleave(n0)
+    many = [(tag, call(cells, bi)) for tag, cells in (("", f["cell"].repeat(k, 1, 1).contiguous()), (" (stride-0 cell)", f["cell"][:1].expand(k, 3, 3)))]
+    _check_copies(f"vdw {kind} {fmt}", small, call(f["cell"], None), many, k, per_atom=(0, 1, 2, 3), vir=4)
+
+
+def _dispersion_box():
+    """The 60-atom box of tests/test_dispersion_ewald_gpu.py listed to 4.5, its entries sorted by row: (positions, coefficients, cell [1, 3, 3]) on
+    the device and the entries as numpy arrays."""
+    pos, c, (i, j, S) = TDE._box(11, 4.5)
+    order = torch.argsort(i, stable=True)
+    return pos.to(DEV), c.to(DEV), TDE.CELL.to(DEV)[None], tuple(e[order].numpy() for e in (i, j, S))
+
+
+@pytest.mark.parametrize("fmt", ["matrix", "list"])
+def test_dispersion_real_space_copies_as_one_system_and_as_a_batch(fmt):
+    """`de_fold_kernel`, counted kind (cutoff 4.0, taper 3.6), every flag; the matrix keeps all three kinds of padding (`_tile_padded_matrix`)."""
+    from nvalchemiops import _capi as C
+    from nvalchemiops.interactions import ewald_dispersion_real_space as real
+
+    pos, c, cell, entries = _dispersion_box()
+    n0, blocks = pos.shape[0], int(C.lib().mi_ewald_dispersion_blocks())
+    k = _copies(n0, blocks)
+    n = k * n0
+    assert n > 256 * blocks and n % 64 != 0
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=DEV)  # noqa: E731
+    if fmt == "matrix":
+        nm, sh, _ = W.padded_matrix(entries, n0)
+        lists = dict(neighbor_matrix=t(nm), neighbor_matrix_shifts=t(sh), mask_value=n0)
+        big = dict(neighbor_matrix=_tile_padded_matrix(t(nm), k), neighbor_matrix_shifts=t(sh).repeat(k, 1, 1).contiguous(), mask_value=n)
+    else:
+        ptr = np.zeros(n0 + 1, np.int32)
+        ptr[1:] = np.cumsum(np.bincount(entries[0], minlength=n0))
+        lists = dict(neighbor_list=t(np.stack(entries[:2]).astype(np.int32)), neighbor_ptr=t(ptr), neighbor_shifts=t(entries[2].astype(np.int32)))
+        lst, bptr, lsh = _tile_csr(lists["neighbor_list"], lists["neighbor_ptr"], lists["neighbor_shifts"], k)
+        big = dict(neighbor_list=lst, neighbor_ptr=bptr, neighbor_shifts=lsh)
+    kw = dict(counted_cutoff=4.0, counted_taper=3.6, **TDE.ALL)
+    small = real(pos, c, cell, 0.3, **lists, **kw)
+    ref = TDE.R.evaluate(pos, c, cell, 0.3, tuple(t(e).long() for e in entries), counted=(4.0, 3.6))
+    for name, o in zip(TDE.NAMES, small):
+        TDE._close(o, ref[name], f"fold sizes dispersion real space {fmt}: the small call, {name}", 1e-11)
+    P, Cf = _tiled_atoms([pos, c], k)
+    bi = torch.arange(k, device=DEV, dtype=torch.int32).repeat_interleave(n0)
+    many = [(tag, real(P, Cf, cells, 0.3, batch_idx=bi, **big, **kw))
+            for tag, cells in (("", cell.repeat(k, 1, 1).contiguous()), (" (stride-0 cell)", cell[:1].expand(k, 3, 3)))]
+    _check_copies(f"dispersion real space {fmt}", small, real(P, Cf, cell, 0.3, **big, **kw), many, k, per_atom=(0, 1, 2), vir=3)
+
+
+def test_dispersion_reciprocal_space_copies_as_a_batch():
+    """The `tile + b` partial slots of `de_sf_kernel` and the system loop of `de_gather_kernel`: K systems of 60 atoms, so four or five systems
+    share every atom tile of 256 over 97 tiles, with seven k-vectors.  Not bit for bit: a system split across two tiles sums its two partials,
+    the small call one.  Every system's per-atom outputs and virial within the float64 bar of the small call's."""
+    from nvalchemiops import _capi as C
+    from nvalchemiops.interactions import ewald_dispersion_reciprocal_space as recip
+
+    pos, c, cell, _ = _dispersion_box()
+    n0, tile = pos.shape[0], int(C.lib().mi_ewald_dispersion_atom_tile())
+    k = _copies(n0, int(C.lib().mi_ewald_dispersion_blocks()))
+    assert tile // n0 >= 4 and k * n0 > 90 * tile
+    kv = TDE.generate_k_vectors_ewald_summation(cell[0], 2.2)[:7]
+    small = recip(pos, c, cell, kv, 1.1, **TDE.ALL)
+    ref = TDE.R.evaluate(pos, c, cell, 1.1, None, kv)
+    for name, o in zip(TDE.NAMES, small):
+        TDE._close(o, ref[name], f"fold sizes dispersion reciprocal space: the small call, {name}", 1e-11)
+    P, Cf = _tiled_atoms([pos, c], k)
+    bi = torch.arange(k, device=DEV, dtype=torch.int32).repeat_interleave(n0)
+    for tag, cells in (("", cell.repeat(k, 1, 1).contiguous()), (" (stride-0 cell)", cell[:1].expand(k, 3, 3))):
+        out = recip(P, Cf, cells, kv, 1.1, batch_idx=bi, **TDE.ALL)
+        for name, o, s in zip(TDE.NAMES, out, small):
+            want = s.expand(k, 3, 3) if name == "virial" else s.repeat((k,) + (1,) * (s.dim() - 1))
+            TDE._close(o, want, f"[fold] dispersion reciprocal space batch of {k}{tag}, {name}", 1e-11)
+
+
+# ---- dipole_pair_scale_correction ------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("thole", [None, TDS.SC.A_T], ids=["bare", "thole"])
+@pytest.mark.parametrize("fmt", ["matrix", "csr"])
+def test_dipole_pair_scale_copies_as_one_system_and_as_a_batch(fmt, thole):
+    """The fold of csrc/dipole_scale.hip: the periodic problem of tests/dipole_scale_cases.py (24 atoms), every flag, both scale arrays tiled
+    like the shifts; the matrix keeps its three kinds of padding and NaN scales on it."""
+    from nvalchemiops import _capi as C
+
+    fn, f = TDS._api().dipole_pair_scale_correction, TDS._case("periodic")
+    n0 = f["n"]
+    k = _copies(n0, int(C.lib().mi_dipole_scale_blocks()))
+    n = k * n0
+    assert n > 256 * int(C.lib().mi_dipole_scale_blocks()) and n % 64 != 0 and f["bi"] is None
+    small = TDS._call(f, fmt, thole, compute_virial=True, **TDS.ALL)
+    for name, o in zip(TDS.NAMES, small):
+        TDS._close(o, TDS._reference("periodic", thole)[name], f"fold sizes dipole pair scale {fmt}: the small call, {name}", 1e-11)
+    pos, q, mu, polar = _tiled_atoms(f["arrays"], k)
+    sd, sm = f["scales"][fmt]
+    if fmt == "matrix":
+        big = dict(neighbor_matrix=_tile_padded_matrix(f["matrix"]["neighbor_matrix"], k), mask_value=n,
+                   neighbor_matrix_shifts=f["matrix"]["neighbor_matrix_shifts"].repeat(k, 1, 1).contiguous())
+        sd, sm = sd.repeat(k, 1), sm.repeat(k, 1)
+    else:
+        lst, ptr, lsh = _tile_csr(f["csr"]["neighbor_list"], f["csr"]["neighbor_ptr"], f["csr"]["neighbor_shifts"], k)
+        big = dict(neighbor_list=lst, neighbor_ptr=ptr, neighbor_shifts=lsh)
+        sd, sm = sd.repeat(k), sm.repeat(k)
+    call = lambda cell, bi: fn(pos, q, mu, sd, sm, cell, polarizability=polar, thole=thole, batch_idx=bi, compute_virial=True, **big, **TDS.ALL)  # noqa: E731
+    cell = f["cell"].reshape(-1, 3, 3)
+    bi = torch.arange(k, device=DEV, dtype=torch.int32).repeat_interleave(n0)
+    many = [(tag, call(cells, bi)) for tag, cells in (("", cell.repeat(k, 1, 1).contiguous()), (" (stride-0 cell)", cell[:1].expand(k, 3, 3)))]
+    _check_copies(f"dipole pair scale {fmt} {'thole' if thole else 'bare'}", small, call(cell, None), many, k, per_atom=(0, 1, 2, 3, 4), vir=5)

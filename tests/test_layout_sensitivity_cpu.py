@@ -300,3 +300,52 @@ def test_frames_fixture_geometry_and_rolled_tables_multipoles_and_gradients(batc
     print(f"[sensitivity frames {'batch' if batch else 'single'}] {cond}; largest |moved - ref| / bar: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items())
           + f"; non-finite entries under rolled frame_atoms: {lost}")
     assert all(v >= FACTOR for v in worst.values()), worst
+
+
+# ---- van der Waals pairs, dispersion Ewald, scaled dipole pairs ------------------------------------------------------------------------------
+
+def _moved_by(ref, moved, rel=1e-11):
+    """Largest |moved - ref| over the outputs, in units of the float64 bar of the sweeps (rel x the largest |value| of the output + 1e-14)."""
+    worst = 0.0
+    for k, r in ref.items():
+        r, m = np.asarray(r, dtype=np.float64), np.asarray(moved[k], dtype=np.float64)
+        worst = max(worst, _ratio(m, r, rel * np.abs(r).max() + 1e-14))
+    return worst
+
+
+@pytest.mark.parametrize("kind", ["buffered_14_7", "lennard_jones"])
+@pytest.mark.parametrize("batch", [False, True], ids=["single", "batch"])
+def test_vdw_fixture_rolled_parameters_scales_and_site_tables(kind, batch):
+    c, ref = L.vdw(batch, kind), L.vdw_reference(batch, kind)
+    worst = {arg: _moved_by(ref, L.vdw_reference(batch, kind, **{arg: _roll(c[arg])})) for arg in ("radii", "eps", "scales", "parent", "kappa")}
+    print(f"[sensitivity {kind} {'batch' if batch else 'single'}] largest |moved - ref| / bar: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+    assert all(v >= FACTOR for v in worst.values()), worst
+
+
+@pytest.mark.parametrize("batch", [False, True], ids=["single", "batch"])
+def test_dispersion_ewald_fixture_rolled_coefficients_k_vectors_and_alpha(batch):
+    c = L.dispersion_ewald(batch)
+    worst = {}
+    for half in ("real", "recip"):
+        ref = L.dispersion_ewald_reference(batch, half)
+        worst[f"c ({half})"] = _moved_by(ref, L.dispersion_ewald_reference(batch, half, c=_roll(c["c"])))
+        if batch:
+            worst[f"alpha ({half})"] = _moved_by(ref, L.dispersion_ewald_reference(batch, half, alpha=_roll(c["alpha"])))
+    ref = L.dispersion_ewald_reference(batch, "recip")
+    kv = c["k_vectors"]
+    # misread k-vectors: the [K, 3] rows of every system read one component off (a rolled flat buffer), and for a batch system 0's set for all
+    flat = torch.roll(kv.reshape(kv.shape[0], -1), 1, dims=1).reshape(kv.shape)
+    worst["k_vectors (one component off)"] = _moved_by(ref, L.dispersion_ewald_reference(batch, "recip", k_vectors=flat))
+    if batch:
+        worst["k_vectors (rolled by a system)"] = _moved_by(ref, L.dispersion_ewald_reference(batch, "recip", k_vectors=torch.roll(kv, 1, dims=0)))
+    print(f"[sensitivity ewald_dispersion {'batch' if batch else 'single'}] largest |moved - ref| / bar: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+    assert all(v >= FACTOR for v in worst.values()), worst
+
+
+@pytest.mark.parametrize("batch", [False, True], ids=["single", "batch"])
+def test_dipole_scale_fixture_rolled_scales_and_polarisabilities(batch):
+    p, ref = L.dipole_scale(batch), L.dipole_scale_reference(batch)
+    worst = {arg: _moved_by(ref, L.dipole_scale_reference(batch, **{arg: _roll(p[arg])})) for arg in ("sd", "sm", "polar", "mu", "q")}
+    print(f"[sensitivity dipole_pair_scale_correction {'batch' if batch else 'single'}] largest |moved - ref| / bar: "
+          + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()))
+    assert all(v >= FACTOR for v in worst.values()), worst

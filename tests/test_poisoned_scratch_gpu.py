@@ -38,6 +38,8 @@ from tests import test_d3_zero_gpu as TZ
 from tests import test_d4_atm_gpu as TD4A
 from tests import test_d4_gpu as TD4
 from tests import test_dipole_gpu as TDP
+from tests import test_dipole_scale_gpu as TDS
+from tests import test_dispersion_ewald_gpu as TDE
 from tests import test_electrostatic_virial_gpu as TV
 from tests import test_ewald_full_list_gpu as TF
 from tests import test_fold_sizes_gpu as TFS
@@ -52,9 +54,12 @@ from tests import test_qeq_gpu as TQ
 from tests import test_quadrupole_gpu as TQD
 from tests import test_search_cn_gpu as TS
 from tests import test_spline_channels_gpu as TCH
+from tests import test_sweep_dispersion_ewald_gpu as TSD
 from tests import test_sweep_multipoles_gpu as TSM
 from tests import test_sweep_pme_quadrupole_gpu as TSQ
+from tests import test_sweep_vdw_gpu as TSV
 from tests import test_thole_gpu as TTH
+from tests import test_vdw_gpu as TVW
 from tests.test_search_cn_gpu import engine  # noqa: F401  (requested by name; tests/test_packed_companion_gpu.py has the same fixture)
 
 pytestmark = pytest.mark.gpu
@@ -257,6 +262,26 @@ _take("quadrupole", TQD, """parity_fp64_matrix_and_csr parity_fp32_inputs self_i
       autograd_matches_reference_and_explicit_outputs autograd_fp32_only_quadrupoles_and_batch
       virial_is_the_strain_derivative_and_not_symmetric""")
 
+# ---- van der Waals, the dispersion Ewald sum, scaled bonded dipole pairs: the parity tests, the edge cases, the seeds with a system without atoms
+_take("vdw", TVW, "parity_across_the_wave_stride_and_in_periodic_boxes")
+_take("vdw", TSV, "vdw_entries_on_the_cutoff_the_taper_and_r_zero")
+_take("dispersion_ewald", TDE, "real_space_and_the_sum_of_both_halves reciprocal_space_around_the_tile_edges")
+_take("dispersion_ewald", TSD, """dispersion_entries_on_the_series_switch_the_counted_edges_and_r_zero a_k_vector_below_the_threshold_weighs_nothing""")
+_take("dipole_scale", TDS, """every_output_against_the_yardstick unit_scales_give_exact_zeros_and_one_sided_scales_select_their_term
+      minimum_image_of_wrapped_atoms_is_the_unwrapped_molecule""")
+
+
+@pytest.mark.parametrize("seed", TSV.W.EMPTY_SYSTEM_SEEDS)
+@pytest.mark.parametrize("kind", TSV.W.VDW_KINDS)
+def test_vdw__vdw_sweep_with_a_system_without_atoms(kind, seed):
+    TSV.test_vdw_sweep(kind, seed)
+
+
+@pytest.mark.parametrize("seed", TSD.W.EMPTY_SYSTEM_SEEDS)
+def test_dispersion_ewald__dispersion_sweep_with_a_system_without_atoms(seed):
+    TSD.test_dispersion_sweep(seed)
+
+
 # the quadrupole mesh term: the four-mesh memset of the adjoint (`weights ? 4 : 2`) and its `accumulate` launch run in every one of these
 @pytest.fixture(scope="module")
 def pme_quadrupole_references():
@@ -294,4 +319,6 @@ _take("fold", TFS, """d4_copies_as_one_system_and_as_a_batch gaussian_copies_as_
       thole_dipole_correction_copies_as_one_system_and_as_a_batch induced_dipoles_copies_as_one_system_and_as_a_batch
       pair_scale_copies_as_one_system_and_as_a_batch pair_scale_minimum_image_copies_as_one_system_and_as_a_batch
       local_frames_copies_as_one_system_and_as_a_batch cluster_corrections_periodic_copies_as_one_system_and_as_a_batch
-      cluster_induced_dipoles_copies_as_one_system_and_as_a_batch""")
+      cluster_induced_dipoles_copies_as_one_system_and_as_a_batch vdw_copies_as_one_system_and_as_a_batch
+      dispersion_real_space_copies_as_one_system_and_as_a_batch dispersion_reciprocal_space_copies_as_a_batch
+      dipole_pair_scale_copies_as_one_system_and_as_a_batch""")

@@ -965,3 +965,246 @@ def test_frame_seeds_cover_what_they_are_meant_to():
     assert cases[W.FRAME_NO_DIPOLE_SEED]["mu"] is None and cases[W.FRAME_NO_QUADRUPOLE_SEED]["quad"] is None
     assert all(cases[s]["form"] == "batch" for s in W.FRAME_INTERLEAVED_SEEDS + W.FRAME_EMPTY_SEEDS)
     assert {c["dtype"] for c in cases if c["form"] == "batch"} == {"float64", "float32"}
+
+
+# ---- van der Waals pair potentials and the dispersion Ewald sum ------------------------------------------------------
+
+def _cells_differ(cells):
+    return all(np.abs(a - b).max() > 0.05 * max(np.abs(a).max(), np.abs(b).max()) for k, a in enumerate(cells) for b in cells[k + 1:])
+
+
+def _matrix_holds(c, n):
+    nm, sh, val = W.padded_matrix(c["entries"], n, c.get("scales"))
+    i, j, S = c["entries"]
+    ok = (nm >= 0) & (nm < n)
+    assert (nm == n).any() and (nm == -1).any() and (nm == n + 7).any()
+    assert np.array_equal(np.nonzero(ok)[0], i) and np.array_equal(nm[ok], j) and np.array_equal(sh[ok], S)
+    assert bool((~ok[:, :-1] & ok[:, 1:]).any()), "a padding slot between live entries"
+    if val is not None:
+        assert np.array_equal(val[ok], c["scales"]) and np.isnan(val[~ok]).all()
+
+
+def _symmetric_scales(c):
+    i, j, S = c["entries"]
+    by = {(int(a), int(b)) + tuple(int(x) for x in sh): v for a, b, sh, v in zip(i, j, S, c["scales"])}
+    return all(by[(b, a, -x, -y, -z)] == v for (a, b, x, y, z), v in by.items())
+
+
+def _rho_min(c, r):
+    """Smallest r / max(R_i, R_j) over the site pairs inside the cutoff: every radius rule gives a mean of the two radii, so a lower bound of rho."""
+    i, j, _ = c["entries"]
+    valid = (c["radii"] > 0) & (c["eps"] > 0)
+    live = valid[i] & valid[j] & (r < c["cutoff"]) & (r > 0)
+    return float((r[live] / np.maximum(c["radii"][i], c["radii"][j])[live]).min())
+
+
+@pytest.mark.parametrize("seed", W.SEEDS)
+@pytest.mark.parametrize("kind", W.VDW_KINDS)
+def test_vdw_seed_meets_its_conditions(kind, seed):
+    """A full, symmetric list that reaches the cutoff plus twice the largest site displacement, symmetric scales, rho >= 0.8 for every site
+    pair, every bond at least 0.05 (fractional) from a minimum-image flip, entries on both sides of the taper and beyond the cutoff, no
+    r^2 within the margin of the cutoff's, distinct cells in a batch, and the atoms without a site where the sweep means them to be."""
+    c = W.vdw_case("sweep", (kind, seed))
+    i, j, S = c["entries"]
+    n = len(c["pos"])
+    assert c["dtype"] == ("float64" if seed % 2 == 0 else "float32") and c["form"] == W.VDW_FORMS[seed] and c["periodic"] == (c["form"] != "cluster")
+    assert set(c["sizes"]) <= set(W.VDW_SIZES) | {0} and (0 in c["sizes"]) == (seed in W.EMPTY_SYSTEM_SEEDS) and (len(c["sizes"]) > 1) == (c["form"] == "batch")
+    assert (c["taper"] is None) == (seed in W.VDW_NO_TAPER_SEEDS) and c["rules"] == W.VDW_RULES[seed % 6]
+    assert _mirrored(i, j, S) and bool((c["batch_idx"][i] == c["batch_idx"][j]).all())
+    kids, bond, frac = W.vdw_bonds(c)
+    reduced = W.vdw_reduced(c)
+    displacement = float(((1.0 - c["kappa"][kids]) * np.linalg.norm(bond, axis=1)).max())
+    assert c["reach"] >= c["cutoff"] + 2.0 * displacement and float(np.linalg.norm(bond, axis=1).max()) <= W.VDW_BOND_MAX
+    full, _ = W._list_all(c["pos"], c["cells"], c["sizes"], c["reach"])  # noqa: SLF001
+    assert all(np.array_equal(a, b) for a, b in zip(full, c["entries"])), "the list is every image within its reach"
+    if c["periodic"]:
+        assert float(np.abs(frac - np.rint(frac)).max()) <= 0.45, "a bond within 0.05 of a minimum-image flip"
+        assert all(m >= c["reach"] / W.heights(cell).min() for m, cell in zip(c["images"], c["cells"]))
+    else:
+        assert c["cells"] is None and not S.any() and not c["flags"]["compute_virial"]
+    if c["scales"] is not None:
+        assert _symmetric_scales(c) and set(c["scales"].tolist()) == {0.0, 0.4, 0.8, 1.0}
+    assert (c["scales"] is None) == (seed % 3 == 0) and c["scale_dtype"] == (None, "float32", "float64")[seed % 3]
+    r = W.vdw_site_distances(c)
+    assert _rho_min(c, r) >= 0.8, "the float32 bars are measured for rho >= 0.8"
+    lo = c["cutoff"] if c["taper"] is None else c["taper"]
+    assert bool((r < lo).any()) and bool((r > c["cutoff"]).any()) and (c["taper"] is None or bool(((r > lo) & (r < c["cutoff"])).any()))
+    assert float(np.abs(r * r / c["cutoff"] ** 2 - 1.0).min()) >= W.VDW_MARGIN and float(r.min()) > 1.0
+    if c["form"] == "batch":
+        assert _cells_differ(list(c["cells"])), "every system of a batch has a cell of its own"
+    head, child = c["no_site"]
+    assert c["eps"][head] == 0.0 and not reduced[head] and int((reduced & (c["parent"] == head)).sum()) >= 1, "a parent with eps = 0 that has children"
+    assert c["radii"][child] == 0.0 and reduced[child] and c["eps"][c["parent"][child]] > 0, "a child with R = 0"
+    assert bool((c["parent"] == -1).any()) and bool((c["parent"] == np.arange(n)).any()) and int(np.bincount(c["parent"][reduced]).max()) >= 2
+    assert not reduced[c["parent"][reduced]].any() and bool((c["batch_idx"][c["parent"][reduced]] == c["batch_idx"][reduced]).all())
+    _matrix_holds(c, n)
+    if c["perm"] is not None:
+        ci = W.vdw_interleaved(c)
+        assert bool((np.diff(ci["batch_idx"]) < 0).any()) and np.array_equal(ci["pos"], c["pos"][c["perm"]]) and _mirrored(*ci["entries"])
+        inv = np.argsort(c["perm"])
+        for p in np.unique(c["parent"][reduced]):
+            old = np.nonzero(reduced & (c["parent"] == p))[0]
+            assert bool((np.diff(inv[old]) > 0).all()), "children of one parent keep their order"
+            assert np.array_equal(np.nonzero(ci["parent"] == inv[p])[0][np.nonzero(ci["parent"] == inv[p])[0] != inv[p]], inv[old])
+        assert np.allclose(W.vdw_site_positions(ci), W.vdw_site_positions(c)[c["perm"]], rtol=0, atol=1e-12)
+
+
+@pytest.mark.parametrize("kind", W.VDW_KINDS)
+def test_vdw_seeds_cover_what_they_are_meant_to(kind):
+    cases = [W.vdw_case("sweep", (kind, s)) for s in W.SEEDS]
+    alone = {k for c in cases if sum(c["flags"].values()) == 1 for k, v in c["flags"].items() if v}
+    assert alone == set(W.VDW_FLAGS), "each compute flag alone"
+    assert any(c["flags"] == {k: k == "compute_virial" for k in W.VDW_FLAGS} and W.vdw_reduced(c).any() for c in cases), "the virial alone, with sites"
+    assert not any(cases[W.VDW_NO_FLAG_SEED]["flags"].values()), "energies alone"
+    assert {c["rules"] for c in cases} == set(W.VDW_RULES) and sum(c["taper"] is None for c in cases) >= 3
+    assert {c["scale_dtype"] for c in cases} == {None, "float32", "float64"} and {c["form"] for c in cases} == {"cluster", "cell", "batch"}
+    assert {n for c in cases for n in c["sizes"]} >= set(W.VDW_SIZES)
+    assert all(cases[s]["form"] == "batch" and cases[s]["perm"] is not None and cases[s]["dtype"] == "float64" for s in W.INTERLEAVED_SEEDS)
+    assert all(cases[s]["form"] == "batch" and cases[s]["sizes"][1] == 0 for s in W.EMPTY_SYSTEM_SEEDS)
+    assert any(bool(np.rint(W.vdw_bonds(c)[2]).any()) for c in cases if c["periodic"]), "children bonded across a cell face"
+    for s in W.VDW_ROTATED_SEEDS:  # row order matters: the transposed matrix is another lattice, and no component is zero
+        cell = cases[s]["cells"][0]
+        assert cases[s]["form"] == "batch" and float(np.abs(cell).min()) > 1e-3 * float(np.abs(cell).max()) and float(np.abs(cell - cell.T).max()) > 0.05 * float(np.abs(cell).max())
+
+
+def test_vdw_edge_case_sits_on_its_edges_in_both_precisions():
+    c = W.vdw_case("edge")
+    i, j, S = c["entries"]
+    for k in ("pos", "radii", "eps", "cells"):
+        assert np.array_equal(c[k].astype(np.float32).astype(np.float64), c[k]), f"{k} is not float32-exact"
+    d32 = c["pos"].astype(np.float32)[j] - c["pos"].astype(np.float32)[i]
+    r2_32 = ((d32[:, 0] * d32[:, 0] + d32[:, 1] * d32[:, 1]) + d32[:, 2] * d32[:, 2]).astype(np.float64)
+    r2_64 = ((c["pos"][j] - c["pos"][i]) ** 2).sum(1)
+    at = lambda a, b: int(np.nonzero((i == a) & (j == b))[0][0])  # noqa: E731
+    cut2 = c["cutoff"] ** 2
+    assert r2_32[at(0, 1)] == cut2 == r2_64[at(0, 1)], "r^2 == cutoff^2 exactly"
+    assert r2_32[at(0, 2)] == float(np.nextafter(np.float32(cut2), np.float32(0))) and r2_64[at(0, 2)] < cut2, "one float32 ulp inside"
+    assert abs(r2_32[at(0, 2)] - r2_64[at(0, 2)]) < 1e-6 and np.count_nonzero(d32[at(0, 2)]) == 1, "along an axis: one rounding, contracted or not"
+    assert np.sqrt(r2_32[at(0, 3)]) == c["taper"] == np.sqrt(r2_64[at(0, 3)]), "r == taper"
+    assert r2_32[at(0, 0)] == 0.0 and r2_32[at(3, 3)] == 0.0 and r2_32[at(0, 4)] == 4.0
+    for a, b in (c["at_cutoff"], c["at_cutoff"][::-1]):
+        assert np.array_equal(j[i == a], [b]) and r2_32[at(a, b)] == cut2 == r2_64[at(a, b)], "an atom whose only entry sits at the cutoff"
+    assert _mirrored(i, j, S) and not S.any() and bool((r2_64 > cut2).any())
+    assert _rho_min(c, np.sqrt(r2_64)) >= 0.8
+    _matrix_holds(c, len(c["pos"]))
+
+
+def test_vdw_row_ladder_case():
+    c = W.vdw_case("rows")
+    i, j, S = c["entries"]
+    n, rows = len(c["pos"]), len(W.VDW_ROWS)
+    reduced = W.vdw_reduced(c)
+    assert tuple(np.bincount(i, minlength=n)[:rows]) == W.VDW_ROWS == (0, 1, 63, 64, 65, 128, 129) and _mirrored(i, j, S) and _symmetric_scales(c)
+    assert reduced[W.VDW_ROWS.index(63)] and reduced[W.VDW_ROWS.index(65)] and int(((c["parent"] == W.VDW_ROWS.index(64)) & reduced).sum()) == 1
+    assert not reduced[c["parent"][reduced]].any()
+    _, _, frac = W.vdw_bonds(c)
+    r = W.vdw_site_distances(c)
+    assert float(np.abs(frac - np.rint(frac)).max()) <= 0.45 and _rho_min(c, r) >= 0.8
+    assert bool((r > c["cutoff"]).any()) and bool(((r > c["taper"]) & (r < c["cutoff"])).any()) and float(np.abs(r * r / c["cutoff"] ** 2 - 1.0).min()) >= W.VDW_MARGIN
+    cell = c["cells"][0]
+    assert float(np.abs(cell).min()) > 0.01 * float(np.abs(cell).max())
+
+
+def _reciprocal_of(kv, cell):
+    """Largest distance of k . cell^T / 2 pi from whole numbers: 0 for reciprocal vectors of `cell`."""
+    m = kv.numpy() @ cell.T / (2.0 * np.pi)
+    return float(np.abs(m - np.rint(m)).max()) if m.size else 0.0
+
+
+@pytest.mark.parametrize("seed", W.SEEDS)
+def test_dispersion_seed_meets_its_conditions(seed):
+    """A full symmetric list, distinct cells, k-vectors that are each system's OWN reciprocal vectors (and not another system's), cut to the
+    shortest of sets of different lengths, no r^2 within the margin of the counted cutoff's, entries in the series branch and in the taper
+    window."""
+    c = W.dispersion_case("sweep", seed)
+    i, j, S = c["entries"]
+    n, nsys = len(c["pos"]), len(c["sizes"])
+    assert c["dtype"] == ("float64" if seed % 2 == 0 else "float32") and (nsys == 1) == (seed % 3 == 0) and (0 in c["sizes"]) == (seed in W.EMPTY_SYSTEM_SEEDS)
+    assert _mirrored(i, j, S) and bool((c["batch_idx"][i] == c["batch_idx"][j]).all())
+    full, _ = W._list_all(c["pos"], c["cells"], c["sizes"], c["reach"])  # noqa: SLF001
+    assert all(np.array_equal(a, b) for a, b in zip(full, c["entries"]))
+    r = W.entry_distances(c)
+    assert float(r.min()) >= W.DE_D_MIN and bool((c["c"] == 0).any()) and bool((c["c"] > 0).any()) and c["alpha"].shape == (nsys,)
+    assert bool(((c["alpha"][c["batch_idx"][i]] * r) ** 2 < 1.0).any()) and bool(((c["alpha"][c["batch_idx"][i]] * r) ** 2 > 1.0).any())
+    assert (c["counted"] is None) == (seed % 3 == 0) and (c["counted"] is None or (c["counted"][1] is None) == (seed % 3 == 2))
+    if c["counted"] is not None:
+        rc, rt = c["counted"]
+        assert float(np.abs(r * r / rc ** 2 - 1.0).min()) >= W.VDW_MARGIN and bool((r > rc).any()) and bool((r < rc).any())
+        assert rt is None or bool(((r > rt) & (r < rc)).any())
+    kv = c["k_vectors"]
+    assert tuple(kv.shape) == (nsys, 0 if seed == W.DE_NO_K_SEED else min(c["k_counts"]), 3)
+    if nsys > 1:
+        assert _cells_differ(list(c["cells"])) and len(set(c["k_counts"])) > 1, "the K differ before the cut"
+    for s in range(nsys):
+        assert _reciprocal_of(kv[s], c["cells"][s]) < 1e-9
+        assert all(kv.shape[1] == 0 or _reciprocal_of(kv[s], c["cells"][t]) > 1e-3 for t in range(nsys) if t != s), "another system's k-vectors would do"
+    _matrix_holds(c, n)
+    if c["perm"] is not None:
+        ci = W.dispersion_interleaved(c)
+        assert bool((np.diff(ci["batch_idx"]) < 0).any()) and np.array_equal(ci["c"], c["c"][c["perm"]]) and _mirrored(*ci["entries"])
+
+
+def test_dispersion_seeds_cover_what_they_are_meant_to():
+    cases = [W.dispersion_case("sweep", s) for s in W.SEEDS]
+    alone = {k for c in cases if sum(c["flags"].values()) == 1 for k, v in c["flags"].items() if v}
+    assert alone == set(W.DE_FLAGS) and not any(cases[W.VDW_NO_FLAG_SEED]["flags"].values())
+    assert cases[W.DE_NO_K_SEED]["k_vectors"].shape[1] == 0 and all(cases[s]["sizes"][1] == 0 and len(cases[s]["sizes"]) == 3 for s in W.EMPTY_SYSTEM_SEEDS)
+    assert all(cases[s]["perm"] is not None and len(cases[s]["sizes"]) > 1 and cases[s]["dtype"] == "float64" for s in W.INTERLEAVED_SEEDS)
+    assert {n for c in cases for n in c["sizes"]} >= set(W.VDW_SIZES)
+    assert any(float(np.abs(c["cells"][0]).min()) > 0 for c in cases if len(c["sizes"]) > 1), "a batch in rotated cells"
+
+
+def test_dispersion_edge_case_sits_on_its_edges_in_both_precisions():
+    c = W.dispersion_case("edge")
+    i, j, S = c["entries"]
+    for k in ("pos", "c", "cells", "alpha"):
+        assert np.array_equal(c[k].astype(np.float32).astype(np.float64), c[k]), f"{k} is not float32-exact"
+    d32 = c["pos"].astype(np.float32)[j] - c["pos"].astype(np.float32)[i]
+    r2_32 = ((d32[:, 0] * d32[:, 0] + d32[:, 1] * d32[:, 1]) + d32[:, 2] * d32[:, 2]).astype(np.float64)
+    r2_64 = ((c["pos"][j] - c["pos"][i]) ** 2).sum(1)
+    at = lambda a, b: int(np.nonzero((i == a) & (j == b))[0][0])  # noqa: E731
+    a2 = float(c["alpha"][0]) ** 2
+    assert a2 * r2_32[at(0, 1)] == 1.0 == a2 * r2_64[at(0, 1)], "a^2 == 1 exactly"
+    assert a2 * r2_32[at(0, 2)] < 1.0 < a2 * r2_32[at(0, 3)] and a2 * r2_64[at(0, 2)] < 1.0 < a2 * r2_64[at(0, 3)]
+    below = np.nextafter(np.float32(4), np.float32(0))
+    assert r2_32[at(0, 2)] == float(below * below), "the square of the float32 below 4, rounded once"
+    assert all(np.count_nonzero(d32[at(0, b)]) == 1 for b in (1, 2, 3))
+    rc, rt = c["counted"]
+    assert r2_32[at(0, 4)] == rc * rc == r2_64[at(0, 4)] and np.sqrt(r2_32[at(0, 5)]) == rt == np.sqrt(r2_64[at(0, 5)])
+    assert r2_32[at(0, 0)] == 0.0 and r2_32[at(5, 5)] == 0.0 and c["c"][6] == 0.0 and _mirrored(i, j, S) and not S.any()
+    tiny = c["k_tiny"]
+    assert tiny.shape[1] == c["k_vectors"].shape[1] + 1 and torch.equal(tiny[:, :-1], c["k_vectors"]) and float((tiny[0, -1] ** 2).sum()) < 1e-10
+    assert float((c["k_vectors"] ** 2).sum(-1).min()) > 1e-3 and (tiny.shape[1] - 1) // W.DE_TILES["k"] == tiny.shape[1] // W.DE_TILES["k"], "the same k tiles"
+    _matrix_holds(c, len(c["pos"]))
+
+
+def test_dispersion_reciprocal_ladders():
+    with open(os.path.join(CSRC, "dispersion_ewald.hip")) as f:
+        text = f.read()
+    assert W.DE_TILES == {"atom": int(re.search(r"#define DE_ATOM_TILE (\d+)", text).group(1)), "k": int(re.search(r"#define DE_K_TILE (\d+)", text).group(1))}
+    ta, tk = W.DE_TILES["atom"], W.DE_TILES["k"]
+    rungs = W.dispersion_recip_rungs()
+    assert {s[0] for s, k in rungs if k == tk + 1} >= {1, ta - 1, ta, ta + 1, 2 * ta + 3} and {k for s, k in rungs} == {0, 1, tk - 1, tk, tk + 1, 2 * tk + 3}
+    assert max(sum(s) for s, _ in rungs) <= 2 * ta + 3 + 5 and max(k for _, k in rungs) <= 2 * tk + 3
+    for sizes, n_k in rungs:
+        c = W.dispersion_case("recip", (sizes, n_k))
+        assert len(sizes) >= 2 and _cells_differ(list(c["cells"])) and tuple(c["k_vectors"].shape) == (len(sizes), n_k, 3)
+        for s in range(len(sizes)):
+            assert _reciprocal_of(c["k_vectors"][s], c["cells"][s]) < 1e-9
+            assert n_k == 0 or all(_reciprocal_of(c["k_vectors"][s], c["cells"][t]) > 1e-3 for t in range(len(sizes)) if t != s)
+    sizes = W.DE_MIXED_SIZES
+    starts = np.cumsum((0,) + sizes)
+    assert sizes == (3, 1, 0, 300, 7) and len({int(a) // ta for a in starts[:4]}) == 1 and starts[3] // ta != (starts[4] - 1) // ta
+
+
+def test_float32_figures_are_the_restatements_own():
+    """The float32 bars of tests/test_sweep_vdw_gpu.py and tests/test_sweep_dispersion_ewald_gpu.py are four times these figures: measured
+    here again, on the CPU, from the restatements alone (every float32 r^2 moved by one ulp).  Within 5 %: another math library may move a
+    last bit of the float32 mode, and the bars are four times the figure."""
+    pairs = [(W.measured_f32_figures("vdw", kind), W.VDW_F32_FIGURE[kind], kind) for kind in W.VDW_KINDS]
+    pairs.append((W.measured_f32_figures("dispersion"), W.DE_F32_FIGURE, "dispersion"))
+    for got, want, what in pairs:
+        print(what, got)
+        assert got.keys() == want.keys()
+        for group in want:
+            assert all(abs(a - b) <= 0.05 * b for a, b in zip(got[group], want[group])), (what, group, got[group], want[group])
