@@ -1351,6 +1351,29 @@ int mi_ewald_dispersion_recip_gather(const void* positions, const void* coeffici
 int mi_ewald_dispersion_recip_virial(const double* table, const void* k_vectors, const void* cell, const void* alpha, int n_systems, int n_k,
                                      int dtype, double* virial, void* stream);
 
+/* ---- dispersion lattice sum on a mesh, LJ-PME (csrc/dispersion_pme.hip; driver: nvalchemiops/interactions/vdw/pme.py) --------------------
+ * The reciprocal half above on a mesh.  With W_i(g) the order-p B-spline weight (p = 4, 5, 6; every mesh dimension >= p):
+ *     rho = sum_i c_i W_i,   phi = IFFT_unscaled[D FFT(rho)],   D(m) = -(pi^1.5 beta^3 / (6 V)) f(b_m) / sf^2(m),   b_m = |k_m| / (2 beta)
+ *     energies[i] = c_i W_i.phi + (beta^6 / 12) c_i^2
+ * over the FULL spectrum: f(0) = 1, so D(0) is the k = 0 term.  sf^2 is the squared sinc product to the power p, clamped at 1e-10, as
+ * mi_pme_convolve forms it.  rho comes from mi_spline_spread and the transforms from mi_fft_lds or the plans.
+ *   mi_pme_dispersion_convolve   out = D spec for the n_meshes (1, or 2: the adjoint's g-weighted mesh second) natural-order half spectra
+ *       [n_meshes][n_systems][nx][ny][nz/2+1] complex of the dtype; out may be spec.  recip_cell (2 pi cell^-1), alpha, volume: [n_systems]
+ *       rows in the dtype, as mi_pme_prepare writes them.  One launch for all systems; exp, erfc and sf^2 once per mesh point in fp64.
+ *       virial_partial (NULL: not computed) [n_systems][mi_pme_dispersion_virial_blocks()][6] float64: block partials of -dE/d(strain) of
+ *       mesh 0 under x -> (I + eps) x at fixed fractional coordinates, mesh and beta, {xx, yy, zz, xy, xz, yz}; the caller sums the block
+ *       dimension.  Every partial is written; fixed summation order, no atomics.
+ *   mi_pme_dispersion_gather     8 lanes per atom over its p^3 stencil of phi [n_systems][nx][ny][nz] (the dtype): energies [n_atoms]
+ *       float64 (self term included), forces [n_atoms][3] (the dtype) = -dE/dr, coefficient_grads [n_atoms] float64 = dE/dc of the total
+ *       energy; any may be NULL.  With weights g [n_atoms] float64 and phi_g, the potential of the mesh spread from g_i c_i (both or
+ *       neither): the derivatives of L = sum_i g_i energies[i].  Stencil and weights are fp64 for both dtypes. */
+int mi_pme_dispersion_virial_blocks(void);
+int mi_pme_dispersion_convolve(const void* spec, const void* recip_cell, const void* alpha, const void* volume, int n_systems, int n_meshes,
+                               int nx, int ny, int nz, int order, int dtype, void* out, double* virial_partial, void* stream);
+int mi_pme_dispersion_gather(const void* positions, const void* coefficients, const double* weights, const int32_t* batch_idx,
+                             const void* cell_inv_t, const void* phi, const void* phi_g, const void* alpha, int n_atoms, int n_systems, int nx,
+                             int ny, int nz, int order, int dtype, double* energies, void* forces, double* coefficient_grads, void* stream);
+
 /* ---- multi-GPU: the one collective of the path (csrc/comm.cpp) ------------------------------------------------------------
  * The reference has no multi-GPU code; the path shards at SYSTEM granularity -- no pair crosses systems
  * (batch_cell_list.py:448-457, dftd3.py:823,1126, spline.py:809) -- so every rank runs the kernels above on its own contiguous range of

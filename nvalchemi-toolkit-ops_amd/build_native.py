@@ -51,6 +51,9 @@ SOURCES = {
     # dispersion Ewald sum (mi_ewald_dispersion_*): fp64 pair math with libm exp, fp64 sincos phases and erfc once per k; the float32 pair
     # vector is formed with scalar ops only, as in vdw.hip
     "dispersion_ewald.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # dispersion lattice sum on a mesh (mi_pme_dispersion_*): the r^-6 k-space operator (fp64 exp / erfc once per mesh point) and the
+    # 8-lanes-per-atom gather with fp64 stencils
+    "dispersion_pme.hip": [],
     "multipole.hip": [],  # spherical harmonics / Gaussian multipole basis (nvalchemiops.math): fp64 elementwise kernels
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]

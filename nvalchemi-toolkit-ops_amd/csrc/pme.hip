@@ -1058,12 +1058,7 @@ __global__ __launch_bounds__(256) void pme_gather_box_kernel(const T* __restrict
 }
 
 // ---- k-space --------------------------------------------------------------------------------------------
-template <class T> __device__ __forceinline__ T sinc_pi(T x) {
-  if (fabs(x) < T(1e-6)) return T(1);
-  const T px = T(3.14159265358979323846) * x;
-  return sin(px) / px;
-}
-__device__ __forceinline__ int miller_of(int i, int n) { return i < (n + 1) / 2 ? i : i - n; }  // fftfreq(n, 1/n)
+#include "pme_kspace.h"  // sinc_pi, miller_of, sf_sq_of
 
 template <class T> __device__ __forceinline__ T green_of(T k2, T alpha, T volume, bool origin) {
   // pme_kernels.py:194-206: 2 pi exp(-k^2 / 4 a^2) / (k^2 V), 0 for k^2 < 1e-10 and at index (0,0,0)
@@ -1071,17 +1066,6 @@ template <class T> __device__ __forceinline__ T green_of(T k2, T alpha, T volume
   const T ef = exp(-(T(1) / (T(4) * alpha * alpha)) * k2) / k2;
   return T(6.283185307179586) * ef / volume;
 }
-template <class T> __device__ __forceinline__ T sf_sq_of(int mx, int my, int mz, int nx, int ny, int nz, int expo) {
-  // pme_kernels.py:208-225: (sinc sinc sinc)^expo, clamped at 1e-10, squared.  The reference caps the exponent at
-  // min(order, 4); the caller passes that for orders <= 4 and the mathematically right `order` for the
-  // true order-5/6 splines of this build.
-  const T sp = sinc_pi((T)mx / (T)nx) * sinc_pi((T)my / (T)ny) * sinc_pi((T)mz / (T)nz);
-  T sf = sp;
-  for (int t = 1; t < expo; ++t) sf = sf * sp;
-  if (sf < T(1e-10)) sf = T(1e-10);
-  return sf * sf;
-}
-
 template <class T>
 __global__ void pme_green_sf_kernel(const T* __restrict__ k2, const T* __restrict__ alpha, const T* __restrict__ volume, int B, int nx, int ny,
                                     int nz, int order, T* __restrict__ G, T* __restrict__ sf2) {

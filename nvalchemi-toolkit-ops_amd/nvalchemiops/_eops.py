@@ -1601,7 +1601,7 @@ _TH_NO_GRAD = ("{op}: gradients w.r.t. cell are not provided by the Thole dampin
 _CL_NO_GRAD = ("{op}: gradients w.r.t. cell are not provided by the bare multipole pair sums (out of scope); use compute_virial for the strain "
                "derivative.")
 _PER_ATOM = {"positions": (3,), "charges": (), "dipoles": (3,), "quadrupoles": (3, 3), "polarizability": ()}  # shapes after [n]
-_SCALARS = {"SymInt": int, "float": float, "bool": bool}  # schema type of a plain scalar -> the conversion `ctx.extra` and the launch functions get
+_SCALARS = {"SymInt": int, "int": int, "float": float, "bool": bool}  # schema type of a plain scalar -> the conversion `ctx.extra` and the launch functions get
 _SYSTEMS = {  # the fake's number of systems, from (cell, batch_idx)
     "batch": lambda cell, batch_idx: cell.reshape(-1, 3, 3).shape[0] if batch_idx is not None else 1,
     "optional cell": lambda cell, batch_idx: cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1,
@@ -1895,10 +1895,10 @@ _DE_NO_GRAD = ("{op}: gradients w.r.t. {what} are not provided by the dispersion
 _DE_OUTPUTS = ("forces", "coefficient_gradients", "virial")
 
 
-def _dispersion_ewald_ops(name, forward, adjoint, middle, n_tensors, refused):
+def _dispersion_ewald_ops(name, forward, adjoint, middle, n_tensors, refused, module="nvalchemiops.interactions.vdw.ewald"):
     """(forward op `alchemiops::_<name>`, backward op `nvalchemiops::<name>_backward`).  `middle`: the schema of the arguments between the two
     differentiable inputs and the flags, its first `n_tensors` tensors (saved for backward), the rest plain scalars; `refused`: argument
-    index -> name of the inputs without an adjoint."""
+    index -> name of the inputs without an adjoint; `module` holds `forward` and `adjoint`."""
     fwd_name, bwd_name = f"{_NS}::_{name}", f"nvalchemiops::{name}_backward"
     mid = [a.split() for a in middle.split(", ")]
     k, n_in = 2 + n_tensors, 2 + len(mid)
@@ -1907,7 +1907,7 @@ def _dispersion_ewald_ops(name, forward, adjoint, middle, n_tensors, refused):
     inputs = f"Tensor positions, Tensor coefficients, {middle}"
 
     def run(fn_name, args, tail):
-        fn = getattr(importlib.import_module("nvalchemiops.interactions.vdw.ewald"), fn_name)
+        fn = getattr(importlib.import_module(module), fn_name)
         return fn(*args[:k], *[c(v) for c, v in zip(convert, args[k:n_in])], *tail)
 
     def fwd(*args):
@@ -1964,9 +1964,14 @@ ewald_dispersion_real_space_op, ewald_dispersion_real_bwd_op = _dispersion_ewald
     f"Tensor cell, Tensor alpha, {_LISTS}, float counted_cutoff, float counted_taper", 8, {2: "cell", 3: "alpha"})
 ewald_dispersion_reciprocal_space_op, ewald_dispersion_recip_bwd_op = _dispersion_ewald_ops(
     "ewald_dispersion_reciprocal_space", "_recip_forward", "_recip_adjoint", _KSUM, 4, {2: "cell", 3: "k_vectors", 4: "alpha"})
+# the mesh half (nvalchemiops/interactions/vdw/pme.py): the mesh dimensions and the spline order travel as plain ints
+pme_dispersion_reciprocal_space_op, pme_dispersion_recip_bwd_op = _dispersion_ewald_ops(
+    "pme_dispersion_reciprocal_space", "_recip_forward", "_recip_adjoint",
+    "Tensor cell, Tensor alpha, Tensor? batch_idx, int nx, int ny, int nz, int order", 3, {2: "cell", 3: "alpha"},
+    module="nvalchemiops.interactions.vdw.pme")
 
 
-__all__ = ["ewald_dispersion_real_space_op", "ewald_dispersion_real_bwd_op", "ewald_dispersion_reciprocal_space_op", "ewald_dispersion_recip_bwd_op",
+__all__ = ["pme_dispersion_reciprocal_space_op", "pme_dispersion_recip_bwd_op", "ewald_dispersion_real_space_op", "ewald_dispersion_real_bwd_op", "ewald_dispersion_reciprocal_space_op", "ewald_dispersion_recip_bwd_op",
            "buffered_14_7_op", "buffered_14_7_bwd_op", "lennard_jones_op", "lennard_jones_bwd_op", "VDW_OPS",
            "pair_scale_correction_op", "pair_scale_bwd_op", "dipole_pair_scale_correction_op", "dipole_pair_scale_bwd_op", "rotate_multipoles_op", "rotate_multipoles_bwd_op", "coulomb_dipole_correction_op", "coulomb_dipole_bwd_op", "coulomb_quadrupole_correction_op", "coulomb_quadrupole_bwd_op",
            "pme_quadrupole_reciprocal_space_op", "pme_quadrupole_recip_bwd_op",

@@ -42,8 +42,8 @@ _RETURNS = """Returns ``energies`` [N], or a tuple holding only what was asked f
     Energies are differentiable once w.r.t. positions and coefficients, for any upstream gradient on the per-atom energies (the same kernels
     run as their own adjoint); the call then goes through an `alchemiops::_ewald_dispersion_*` op, as it does under `torch.compile`.
     Differentiating the explicit forces, gradients or virial raises NotImplementedError.  Gradients w.r.t. cell, k-vectors and alpha are out of
-    scope (NotImplementedError at backward): use `compute_virial`.  Also out of scope: the mesh form, an alpha / k_cutoff estimator, `cell=None`
-    clusters.  CPU tensors raise NativeLibraryError: there is no fallback."""
+    scope (NotImplementedError at backward): use `compute_virial`.  Also out of scope: an alpha / k_cutoff estimator, `cell=None` clusters
+    (the mesh form is `pme_dispersion_correction`).  CPU tensors raise NativeLibraryError: there is no fallback."""
 
 _NO_CELL = "cell is required: the dispersion Ewald sum is periodic (cell=None clusters are out of scope)"
 _NONE4 = (None, None, None, None)
