@@ -1374,6 +1374,49 @@ int mi_pme_dispersion_gather(const void* positions, const void* coefficients, co
                              const void* cell_inv_t, const void* phi, const void* phi_g, const void* alpha, int n_atoms, int n_systems, int nx,
                              int ny, int nz, int order, int dtype, double* energies, void* forces, double* coefficient_grads, void* stream);
 
+/* ---- valence terms (csrc/valence.hip; driver: nvalchemiops/interactions/valence) ---------------------------------------------------------------
+ * The bonded terms of a force field, Tinker's definitions (angles in radians, no 1/2 in front of a force constant).  atoms [n_terms][A] names
+ * the atoms of every term, parameters [n_terms][n_params] (positions dtype) its constants:
+ *   MI_VALENCE_BOND          A = 2 (a, b)        {k, r0}                   k D^2 (1 + cubic D + quartic D^2),  D = |r_a - r_b| - r0
+ *   MI_VALENCE_ANGLE         A = 3 (a, b, c)     {k, theta0}               k D^2 (1 + cubic D + ... + sextic D^4),  D = angle(a, b, c) - theta0
+ *   MI_VALENCE_STRETCH_BEND  A = 3 (a, b, c)     {k1, k2, r1, r2, theta0}  (k1 (|r_a - r_b| - r1) + k2 (|r_c - r_b| - r2)) (angle - theta0)
+ *   MI_VALENCE_OUT_OF_PLANE  A = 4 (a, b, c, d)  {k}                       k X^2 (1 + cubic X + ... + sextic X^4), X = asin(|V| / sqrt(cc |w|^2)),
+ *                            u = r_a - r_b, v = r_c - r_b, w = r_d - r_b, V = w . (u x v), cc = |u x v|^2 (MI_VALENCE_PLANE_WDC) or
+ *                            |(u - w) x (v - w)|^2 (MI_VALENCE_PLANE_ALLINGER); a term with V == 0 has exactly zero gradients
+ *   MI_VALENCE_TORSION       A = 4 (a, b, c, d)  {V_1..V_F, gamma_1..gamma_F}, n_params = 2 F, F in 1..6
+ *                            sum_n V_n (1 + cos(n phi - gamma_n)), phi the IUPAC dihedral (trans = pi)
+ * Difference vectors are minimum images when cell [n_systems][3][3] is given (rows are lattice vectors; batch_idx [n_atoms] of the term's first
+ * atom selects the row, NULL: system 0).  All arithmetic is float64, outputs are rounded once, no atomics: bit-reproducible.  A term that names
+ * an atom outside [0, n_atoms) contributes exact zeros everywhere.  slot_ptr [n_atoms + 1] / slot_idx [n_slots]: a CSR over atoms of the slots
+ * t A + p that name each atom; the sums over an atom's slots run in the stored order, a slot outside [0, n_terms A) is skipped.
+ * weights [n_atoms] float64 or NULL (all ones): every derivative of term t is scaled by w_t = (1 / A) sum_{a in t} weights[a] -- the outputs
+ * are then the derivatives of L = sum_i weights_i energies[i].
+ *   energies [n_atoms] (positions dtype; NULL ok)             atom shares sum_{t containing i} E_t / A
+ *   MI_VALENCE_FORCES          forces [n_atoms][3] (positions dtype) = -dL/dr
+ *   MI_VALENCE_PARAMETER_GRAD  parameter_grads [n_terms][n_params] float64 = dL/dparameters
+ *   MI_VALENCE_VIRIAL          virial_partial [n_systems][mi_valence_blocks()][9] float64: block partials of -sum_v dL/dv (x) v over the
+ *                              difference vectors, row-major; the caller sums the block dimension (needs a cell)
+ *   MI_VALENCE_TERM_MAJOR      a measurement aid: the gradient record in scratch is laid out [n_terms][A][3] and not as planes [A][3][n_terms]
+ * scratch: mi_valence_scratch_bytes(kind, n_terms, flags) bytes, contents undefined (every word read has been written by the same call). */
+#define MI_VALENCE_BOND 0
+#define MI_VALENCE_ANGLE 1
+#define MI_VALENCE_STRETCH_BEND 2
+#define MI_VALENCE_OUT_OF_PLANE 3
+#define MI_VALENCE_TORSION 4
+#define MI_VALENCE_PLANE_WDC 0
+#define MI_VALENCE_PLANE_ALLINGER 1
+#define MI_VALENCE_FORCES 1
+#define MI_VALENCE_PARAMETER_GRAD 2
+#define MI_VALENCE_VIRIAL 4
+#define MI_VALENCE_TERM_MAJOR 8
+size_t mi_valence_scratch_bytes(int kind, int n_terms, int flags);
+int mi_valence_blocks(void);
+int mi_valence_arity(int kind);
+int mi_valence(int kind, const void* positions, const int32_t* atoms, const void* parameters, int n_params, const void* cell,
+               const int32_t* batch_idx, const double* weights, const int32_t* slot_ptr, const int32_t* slot_idx, long long n_slots, int n_atoms,
+               int n_terms, int n_systems, int dtype, double cubic, double quartic, double pentic, double sextic, int plane, int flags,
+               void* energies, void* forces, double* parameter_grads, double* virial_partial, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- multi-GPU: the one collective of the path (csrc/comm.cpp) ------------------------------------------------------------
  * The reference has no multi-GPU code; the path shards at SYSTEM granularity -- no pair crosses systems
  * (batch_cell_list.py:448-457, dftd3.py:823,1126, spline.py:809) -- so every rank runs the kernels above on its own contiguous range of

@@ -272,6 +272,15 @@ def lib() -> ctypes.CDLL:
         for name in ("mi_vdw_blocks", "mi_vdw_row_words"):
             getattr(L, name).restype = i
             getattr(L, name).argtypes = []
+        # valence terms (nvalchemiops/interactions/valence)
+        L.mi_valence.restype = i
+        L.mi_valence.argtypes = [i] + [vp] * 3 + [i] + [vp] * 5 + [ll, i, i, i, i, dbl, dbl, dbl, dbl, i, i] + [vp] * 5 + [sz, vp]
+        L.mi_valence_scratch_bytes.restype = sz
+        L.mi_valence_scratch_bytes.argtypes = [i, i, i]
+        L.mi_valence_blocks.restype = i
+        L.mi_valence_blocks.argtypes = []
+        L.mi_valence_arity.restype = i
+        L.mi_valence_arity.argtypes = [i]
         # dispersion Ewald sum (nvalchemiops/interactions/vdw/ewald.py)
         L.mi_ewald_dispersion_real.restype = i
         L.mi_ewald_dispersion_real.argtypes = [vp] * 6 + [i, i, i, dbl, dbl, vp, vp, vp, i, i, i] + [vp] * 5 + [sz, vp]

@@ -1884,6 +1884,79 @@ VDW_OPS = (buffered_14_7_op, lennard_jones_op)  # by MI_VDW_BUFFERED_14_7 / MI_V
 
 
 # =====================================================================================================================================
+# valence terms (nvalchemiops/interactions/valence): one forward / backward op pair per kind, written as the vdW ops above
+# =====================================================================================================================================
+# Outputs are always (energies, forces, parameter_gradients, virial); the ones not asked for are empty [0] tensors.  The energies are
+# differentiable w.r.t. positions and parameters: the backward op runs the forward kernels with the incoming gradient as per-atom weights.
+# The term tables and the cell have no gradient (the virial is the strain derivative).
+_VALENCE_OUTPUTS = ("energies", "forces", "parameter_gradients", "virial")
+_VALENCE_TENSORS = 7  # positions ... slot_idx
+
+
+def _make_valence_ops(kind: int, name: str):
+    fwd_name, bwd_name = f"{_NS}::_{name}", f"nvalchemiops::{name}_backward"
+
+    def fwd(positions: Tensor, parameters: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor], atoms: Tensor, slot_ptr: Tensor,
+            slot_idx: Tensor, cubic: float, quartic: float, pentic: float, sextic: float, plane: int, compute_forces: bool,
+            compute_parameter_gradients: bool, compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+        from nvalchemiops.interactions.valence.functions import _forward
+
+        out = _forward(kind, positions, parameters, cell, batch_idx, atoms, slot_ptr, slot_idx, cubic, quartic, pentic, sextic, int(plane),
+                       compute_forces, compute_parameter_gradients, compute_virial)
+        return tuple(positions.new_empty((0,)) if o is None else o for o in out)
+
+    def fwd_fake(positions, parameters, cell, batch_idx, atoms, slot_ptr, slot_idx, cubic, quartic, pentic, sextic, plane, compute_forces,
+                 compute_parameter_gradients, compute_virial):
+        n = positions.shape[0]
+        nsys = cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1
+        empty = lambda: positions.new_empty((0,))  # noqa: E731
+        return (positions.new_empty((n,)), positions.new_empty((n, 3)) if compute_forces else empty(),
+                positions.new_empty(parameters.shape) if compute_parameter_gradients else empty(),
+                positions.new_empty((nsys, 3, 3)) if compute_virial else empty())
+
+    def bwd(positions: Tensor, parameters: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor], atoms: Tensor, slot_ptr: Tensor,
+            slot_idx: Tensor, cubic: float, quartic: float, pentic: float, sextic: float, plane: int,
+            grad_energies: Tensor) -> tuple[Tensor, Tensor]:
+        """Float64 (dL/dpositions, dL/dparameters) for L = sum_i g_i E_i."""
+        from nvalchemiops.interactions.valence.functions import _adjoint
+
+        return _adjoint(kind, positions, parameters, cell, batch_idx, atoms, slot_ptr, slot_idx, cubic, quartic, pentic, sextic, int(plane),
+                        grad_energies)
+
+    def bwd_fake(positions, parameters, *rest):
+        f64 = dict(dtype=torch.float64)
+        return positions.new_empty((positions.shape[0], 3), **f64), positions.new_empty(parameters.shape, **f64)
+
+    bwd_op = torch.library.custom_op(bwd_name, bwd, mutates_args=())
+    bwd_op.register_fake(bwd_fake)
+    bwd_op.register_autograd(lambda ctx, *g: (_ for _ in ()).throw(NotImplementedError(_SECOND_ORDER.format(op=bwd_name, what="gradient"))),
+                             setup_context=lambda ctx, inputs, output: None)
+
+    def setup(ctx, inputs, output):
+        ctx.save_for_backward(*inputs[:_VALENCE_TENSORS])
+        ctx.model = inputs[_VALENCE_TENSORS:_VALENCE_TENSORS + 5]
+        ctx.set_materialize_grads(False)
+
+    def backward(ctx, g_e, *g_explicit):
+        for what, g in zip(_VALENCE_OUTPUTS[1:], g_explicit):
+            if g is not None:
+                raise NotImplementedError(_SECOND_ORDER.format(op=fwd_name, what=what))
+        need = ctx.needs_input_grad
+        if g_e is None:
+            return (None,) * len(need)
+        saved = ctx.saved_tensors
+        cubic, quartic, pentic, sextic, plane = ctx.model
+        gpos, gpar = bwd_op(*saved, float(cubic), float(quartic), float(pentic), float(sextic), int(plane), g_e)
+        return (gpos.to(saved[0].dtype) if need[0] else None, gpar.to(saved[1].dtype) if need[1] else None) + (None,) * (len(need) - 2)
+
+    return _op(f"_{name}", fwd, fwd_fake, backward, setup), bwd_op
+
+
+VALENCE_OPS, VALENCE_BWD_OPS = zip(*(_make_valence_ops(_kind, _name) for _kind, _name in enumerate(  # by MI_VALENCE_BOND .. MI_VALENCE_TORSION
+    ("bond_stretch", "angle_bend", "stretch_bend", "out_of_plane_bend", "torsion"))))
+
+
+# =====================================================================================================================================
 # dispersion Ewald sum (nvalchemiops/interactions/vdw/ewald.py): one forward / backward op pair per half, from one maker
 # =====================================================================================================================================
 # Outputs are always (energies, forces, coefficient_gradients, virial); the ones not asked for are empty [0] tensors.  The energies are
