@@ -1503,95 +1503,21 @@ pme_recip_virial_op.register_autograd(_virial_no_adjoint("nvalchemiops::pme_reci
 
 
 # =====================================================================================================================================
-# Gaussian-smeared charge correction: one op with optional tensors (single / batch, list / matrix, with / without a cell)
+# energy op pairs: a forward op `alchemiops::_<name>` and a backward op `nvalchemiops::<name>_backward` per row of one table, built by
+# one maker
 # =====================================================================================================================================
-# Outputs are always the five of the public function; the ones not asked for are empty [0] tensors.  The energies are differentiable w.r.t.
-# positions, charges, sigma and cell: the backward op runs the forward kernel with the incoming gradient as per-atom weights.
-_GC_NAME = f"{_NS}::_gaussian_charge_correction"
-_GC_OUTPUTS = ("energies", "forces", "charge_gradients", "sigma_gradients", "virial")
-
-
-def _gaussian_fwd(positions: Tensor, charges: Tensor, sigma: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor],
-                  neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
-                  neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int, self_energy: bool,
-                  neutralizing_background: bool, compute_forces: bool, compute_charge_gradients: bool, compute_sigma_gradients: bool,
-                  compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-    from nvalchemiops.interactions.electrostatics.gaussian import _forward
-
-    out = _forward(positions, charges, sigma, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts,
-                   int(mask_value), self_energy, neutralizing_background, compute_forces, compute_charge_gradients, compute_sigma_gradients,
-                   compute_virial)
-    return tuple(positions.new_empty((0,)) if o is None else o for o in out)
-
-
-def _gaussian_fwd_fake(positions, charges, sigma, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                       neighbor_matrix_shifts, mask_value, self_energy, neutralizing_background, compute_forces, compute_charge_gradients,
-                       compute_sigma_gradients, compute_virial):
-    n = positions.shape[0]
-    nsys = cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1
-    empty = lambda: positions.new_empty((0,))  # noqa: E731
-    return (positions.new_empty((n,)), positions.new_empty((n, 3)) if compute_forces else empty(),
-            positions.new_empty((n,)) if compute_charge_gradients else empty(), positions.new_empty((n,)) if compute_sigma_gradients else empty(),
-            positions.new_empty((nsys, 3, 3)) if compute_virial else empty())
-
-
-def _gaussian_bwd(positions: Tensor, charges: Tensor, sigma: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor],
-                  neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor],
-                  neighbor_matrix: Optional[Tensor], neighbor_matrix_shifts: Optional[Tensor], mask_value: int, self_energy: bool,
-                  neutralizing_background: bool, grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor, Tensor]:
-    """Float64 (dL/dpositions, dL/dcharges, dL/dsigma, dL/dcell [B,3,3] or [0]) for L = sum_i g_i E_i."""
-    from nvalchemiops.interactions.electrostatics.gaussian import _adjoint
-
-    gpos, gq, gs, gcell = _adjoint(positions, charges, sigma, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                                   neighbor_matrix_shifts, int(mask_value), self_energy, neutralizing_background, grad_energies)
-    return gpos, gq, gs, (gcell if gcell is not None else gpos.new_empty((0,)))
-
-
-def _gaussian_bwd_fake(positions, charges, sigma, cell, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
-                       neighbor_matrix_shifts, mask_value, self_energy, neutralizing_background, grad_energies):
-    n, f64 = positions.shape[0], dict(dtype=torch.float64)
-    nsys = cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1
-    return (positions.new_empty((n, 3), **f64), positions.new_empty((n,), **f64), positions.new_empty((n,), **f64),
-            positions.new_empty((nsys, 3, 3), **f64) if cell is not None else positions.new_empty((0,), **f64))
-
-
-gaussian_bwd_op = torch.library.custom_op("nvalchemiops::gaussian_charge_correction_backward", _gaussian_bwd, mutates_args=())
-gaussian_bwd_op.register_fake(_gaussian_bwd_fake)
-gaussian_bwd_op.register_autograd(lambda ctx, *g: (_ for _ in ()).throw(NotImplementedError(_SECOND_ORDER.format(
-    op="nvalchemiops::gaussian_charge_correction_backward", what="gradient"))), setup_context=lambda ctx, inputs, output: None)
-
-
-def _gaussian_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs[:10])
-    ctx.mask, ctx.self_energy, ctx.background = inputs[10], inputs[11], inputs[12]
-    ctx.set_materialize_grads(False)
-
-
-def _gaussian_backward(ctx, g_e, *g_explicit):
-    for what, g in zip(_GC_OUTPUTS[1:], g_explicit):
-        if g is not None:
-            raise NotImplementedError(_SECOND_ORDER.format(op=_GC_NAME, what=what))
-    need = ctx.needs_input_grad
-    if g_e is None:
-        return (None,) * len(need)
-    saved = ctx.saved_tensors
-    positions, charges, sigma, cell = saved[:4]
-    gpos, gq, gs, gcell = gaussian_bwd_op(*saved, int(ctx.mask), bool(ctx.self_energy), bool(ctx.background), g_e)
-    return (gpos.to(positions.dtype) if need[0] else None, gq.to(charges.dtype) if need[1] else None, gs.to(sigma.dtype) if need[2] else None,
-            gcell.reshape(cell.shape).to(cell.dtype) if (cell is not None and need[3]) else None) + (None,) * (len(need) - 4)
-
-
-gaussian_charge_correction_op = _op("_gaussian_charge_correction", _gaussian_fwd, _gaussian_fwd_fake, _gaussian_backward, _gaussian_setup)
-
-
-# =====================================================================================================================================
-# point multipoles: nine operator halves and the two bonded-pair scalings, one forward / backward op pair each, built from one table (DESIGN §3.30)
-# =====================================================================================================================================
-# Outputs are always those of the public function (energies, forces, charge_gradients, dipole_gradients, the row's extra output, virial); the
-# ones not asked for are empty [0] tensors.  The energies are differentiable w.r.t. the row's first inputs: the backward op runs the forward
-# kernels with the incoming gradient as per-atom weights and returns float64 gradients.  Gradients of inputs without an adjoint (cell, alpha,
-# k-vectors) are refused, never a silent zero: the virial is the strain derivative.  The ops are registered with an explicit schema string, so
-# the implementations take *args in schema order.
+# The contract of a pair.  The forward op returns the energies, one output per `compute_*` flag and the virial; the ones not asked for are
+# empty [0] tensors, and the fake returns the true dtype.  The energies are differentiable w.r.t. the row's first inputs: the backward op runs
+# the forward kernels with the incoming gradient as per-atom weights and returns float64 gradients, which the autograd formula casts to the
+# input dtypes.  Gradients of the explicit outputs are refused (second derivatives), and so are gradients of the row's `refused` inputs, never
+# a silent zero: the virial is the strain derivative.  The backward op refuses to be differentiated again.  The ops are registered with an
+# explicit schema string, so the implementations take *args in schema order.
+#   point multipoles, bonded-pair scalings: differentiable w.r.t. positions, charges, dipoles and quadrupoles / polarizability; cell, alpha
+#     and k-vectors are refused.
+#   Gaussian charges: w.r.t. positions, charges, sigma and the cell (one gradient per system, None without a cell).
+#   van der Waals pairs: w.r.t. positions, radii and epsilons; the site tables, the pair scales and the cell have no gradient.
+#   valence terms: w.r.t. positions and parameters; the term tables and the cell have no gradient.
+#   dispersion Ewald sums: w.r.t. positions and coefficients; cell, alpha and k-vectors are refused.
 _DP_NO_GRAD = ("{op}: gradients w.r.t. {what} are not provided by the point-dipole Ewald term (out of scope); use compute_virial for the "
                "strain derivative.")
 _QD_NO_GRAD = ("{op}: gradients w.r.t. {what} are not provided by the point-quadrupole Ewald term (out of scope); use compute_virial for the "
@@ -1600,80 +1526,129 @@ _TH_NO_GRAD = ("{op}: gradients w.r.t. cell are not provided by the Thole dampin
                "compute_virial for the strain derivative.")
 _CL_NO_GRAD = ("{op}: gradients w.r.t. cell are not provided by the bare multipole pair sums (out of scope); use compute_virial for the strain "
                "derivative.")
-_PER_ATOM = {"positions": (3,), "charges": (), "dipoles": (3,), "quadrupoles": (3, 3), "polarizability": ()}  # shapes after [n]
+_DE_NO_GRAD = ("{op}: gradients w.r.t. {what} are not provided by the dispersion Ewald sum (out of scope); use compute_virial for the strain "
+               "derivative.")
 _SCALARS = {"SymInt": int, "int": int, "float": float, "bool": bool}  # schema type of a plain scalar -> the conversion `ctx.extra` and the launch functions get
 _SYSTEMS = {  # the fake's number of systems, from (cell, batch_idx)
     "batch": lambda cell, batch_idx: cell.reshape(-1, 3, 3).shape[0] if batch_idx is not None else 1,
     "optional cell": lambda cell, batch_idx: cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1,
     "cell rows": lambda cell, batch_idx: cell.reshape(-1, 3, 3).shape[0],
 }
-_DP, _QD, _TH = ("positions", "charges", "dipoles"), ("positions", "charges", "dipoles", "quadrupoles"), ("positions", "charges", "dipoles",
-                                                                                                            "polarizability")
-_QG, _PG = ("quadrupole_gradients", (3, 3)), ("polarizability_gradients", ())
-_LISTS = ("Tensor? batch_idx, Tensor? neighbor_list, Tensor? neighbor_ptr, Tensor? neighbor_shifts, Tensor? neighbor_matrix, "
-          "Tensor? neighbor_matrix_shifts, SymInt mask_value")
+_EL, _VW, _VL = "nvalchemiops.interactions.electrostatics.", "nvalchemiops.interactions.vdw.", "nvalchemiops.interactions.valence.functions"
+_DP = "Tensor positions, Tensor charges, Tensor dipoles"
+_QD, _TH = f"{_DP}, Tensor quadrupoles", f"{_DP}, Tensor polarizability"
+_NEIGHBORS = ("Tensor? neighbor_list, Tensor? neighbor_ptr, Tensor? neighbor_shifts, Tensor? neighbor_matrix, Tensor? neighbor_matrix_shifts, "
+              "SymInt mask_value")
+_LISTS = f"Tensor? batch_idx, {_NEIGHBORS}"
 _MESH = "Tensor cell, Tensor alpha, Tensor? batch_idx, SymInt nx, SymInt ny, SymInt nz, SymInt spline_order"
 _KSUM = "Tensor cell, Tensor k_vectors, Tensor alpha, Tensor? batch_idx"
-# op name: (module under interactions/electrostatics, its forward, its adjoint, differentiable inputs, middle arguments (a `Tensor` is saved
-# for backward, a scalar travels in ctx.extra), extra output | None, system-count rule, inputs without an adjoint, refusal text)
-_MULTIPOLE_OPS = {
-    "ewald_dipole_real_space": ("dipole", "_real_forward", "_real_adjoint", _DP, f"Tensor cell, Tensor alpha, {_LISTS}", None, "batch",
-                                ("cell", "alpha"), _DP_NO_GRAD),
-    "ewald_dipole_reciprocal_space": ("dipole", "_recip_forward", "_recip_adjoint", _DP, _KSUM, None, "cell rows",
-                                      ("cell", "k_vectors", "alpha"), _DP_NO_GRAD),
-    "pme_dipole_reciprocal_space": ("pme_dipole", "_recip_forward", "_recip_adjoint", _DP, _MESH, None, "batch", ("cell", "alpha"), _DP_NO_GRAD),
-    "thole_dipole_correction": ("thole", "_forward", "_adjoint", _TH, f"Tensor? cell, {_LISTS}, float thole", _PG, "optional cell", ("cell",),
-                                _TH_NO_GRAD),
-    "ewald_quadrupole_real_space": ("quadrupole", "_real_forward", "_real_adjoint", _QD, f"Tensor cell, Tensor alpha, {_LISTS}", _QG, "batch",
-                                    ("cell", "alpha"), _QD_NO_GRAD),
-    "ewald_quadrupole_reciprocal_space": ("quadrupole", "_recip_forward", "_recip_adjoint", _QD, _KSUM, _QG, "cell rows",
-                                          ("cell", "k_vectors", "alpha"), _QD_NO_GRAD),
-    "pme_quadrupole_reciprocal_space": ("pme_quadrupole", "_recip_forward", "_recip_adjoint", _QD, _MESH, _QG, "batch", ("cell", "alpha"),
-                                        _QD_NO_GRAD),
-    "coulomb_dipole_correction": ("cluster", "_dipole_forward", "_dipole_adjoint", _DP, f"Tensor? cell, {_LISTS}", None, "optional cell",
-                                  ("cell",), _CL_NO_GRAD),
-    "coulomb_quadrupole_correction": ("cluster", "_quadrupole_forward", "_quadrupole_adjoint", _QD, f"Tensor? cell, {_LISTS}", _QG,
-                                      "optional cell", ("cell",), _CL_NO_GRAD),
-    "pair_scale_correction": ("pair_scale", "_forward", "_adjoint", _QD, f"Tensor pair_scales, Tensor? cell, {_LISTS}, bool minimum_image", _QG,
-                              "optional cell", ("cell",), _CL_NO_GRAD),
-    "dipole_pair_scale_correction": ("dipole_scale", "_forward", "_adjoint", _TH,
-                                     f"Tensor? direct_scales, Tensor? mutual_scales, Tensor? cell, {_LISTS}, bool minimum_image, float thole", _PG,
-                                     "optional cell", ("cell",), _CL_NO_GRAD),
+# an explicit output: (its name, which gives the flag `compute_<name>`; the input whose shape it has)
+_F, _CG = ("forces", "positions"), ("charge_gradients", "charges")
+_DP_OUT = (_F, _CG, ("dipole_gradients", "dipoles"))
+_QD_OUT, _TH_OUT = _DP_OUT + (("quadrupole_gradients", "quadrupoles"),), _DP_OUT + (("polarizability_gradients", "polarizability"),)
+_VDW = dict(module=_VW + "pair", forward="_forward", adjoint="_adjoint", diff="Tensor positions, Tensor radii, Tensor epsilons",
+            middle=("Tensor? cell, Tensor? batch_idx, Tensor? parent, Tensor? reduction, Tensor? child_ptr, Tensor? child_idx, Tensor? pair_scales, "
+                    f"{_NEIGHBORS}, float cutoff, float taper, float delta, float gamma, SymInt radius_rule, SymInt epsilon_rule"),
+            outputs=(_F, ("radius_gradients", "radii"), ("epsilon_gradients", "epsilons")), systems="optional cell")
+_VALENCE = dict(module=_VL, forward="_forward", adjoint="_adjoint", diff="Tensor positions, Tensor parameters",
+                middle=("Tensor? cell, Tensor? batch_idx, Tensor atoms, Tensor slot_ptr, Tensor slot_idx, float cubic, float quartic, float pentic, "
+                        "float sextic, SymInt plane"),
+                outputs=(_F, ("parameter_gradients", "parameters")), systems="optional cell")
+_VALENCE_KINDS = ("bond_stretch", "angle_bend", "stretch_bend", "out_of_plane_bend", "torsion")  # by MI_VALENCE_BOND .. MI_VALENCE_TORSION
+_DE = dict(module=_VW + "ewald", diff="Tensor positions, Tensor coefficients", outputs=(_F, ("coefficient_gradients", "coefficients")),
+           refusal=_DE_NO_GRAD)
+_REAL, _RECIP = dict(forward="_real_forward", adjoint="_real_adjoint"), dict(forward="_recip_forward", adjoint="_recip_adjoint")
+# op name: the keywords of `_energy_ops`.  module, forward, adjoint: where the two launch functions live (imported at call time); bound: their
+# leading arguments that are not the op's (the kind); diff: the differentiable inputs; middle: the arguments between them and the flags;
+# outputs: the explicit outputs between the energies and the virial; systems: the fake's rule in `_SYSTEMS`; refused, refusal: the inputs
+# whose gradient is refused, and the text; per_system: the differentiable inputs whose gradient comes back as [nsys, 3, 3].
+_ENERGY_OPS = {
+    "gaussian_charge_correction": dict(module=_EL + "gaussian", forward="_forward", adjoint="_adjoint",
+                                       diff="Tensor positions, Tensor charges, Tensor sigma, Tensor? cell",
+                                       middle=f"{_LISTS}, bool self_energy, bool neutralizing_background",
+                                       outputs=(_F, _CG, ("sigma_gradients", "sigma")), systems="optional cell", per_system=("cell",)),
+    "ewald_dipole_real_space": dict(_REAL, module=_EL + "dipole", diff=_DP, middle=f"Tensor cell, Tensor alpha, {_LISTS}", outputs=_DP_OUT,
+                                    systems="batch", refused=("cell", "alpha"), refusal=_DP_NO_GRAD),
+    "ewald_dipole_reciprocal_space": dict(_RECIP, module=_EL + "dipole", diff=_DP, middle=_KSUM, outputs=_DP_OUT, systems="cell rows",
+                                          refused=("cell", "k_vectors", "alpha"), refusal=_DP_NO_GRAD),
+    "pme_dipole_reciprocal_space": dict(_RECIP, module=_EL + "pme_dipole", diff=_DP, middle=_MESH, outputs=_DP_OUT, systems="batch",
+                                        refused=("cell", "alpha"), refusal=_DP_NO_GRAD),
+    "thole_dipole_correction": dict(module=_EL + "thole", forward="_forward", adjoint="_adjoint", diff=_TH,
+                                    middle=f"Tensor? cell, {_LISTS}, float thole", outputs=_TH_OUT, systems="optional cell", refused=("cell",),
+                                    refusal=_TH_NO_GRAD),
+    "ewald_quadrupole_real_space": dict(_REAL, module=_EL + "quadrupole", diff=_QD, middle=f"Tensor cell, Tensor alpha, {_LISTS}",
+                                        outputs=_QD_OUT, systems="batch", refused=("cell", "alpha"), refusal=_QD_NO_GRAD),
+    "ewald_quadrupole_reciprocal_space": dict(_RECIP, module=_EL + "quadrupole", diff=_QD, middle=_KSUM, outputs=_QD_OUT, systems="cell rows",
+                                              refused=("cell", "k_vectors", "alpha"), refusal=_QD_NO_GRAD),
+    "pme_quadrupole_reciprocal_space": dict(_RECIP, module=_EL + "pme_quadrupole", diff=_QD, middle=_MESH, outputs=_QD_OUT, systems="batch",
+                                            refused=("cell", "alpha"), refusal=_QD_NO_GRAD),
+    "coulomb_dipole_correction": dict(module=_EL + "cluster", forward="_dipole_forward", adjoint="_dipole_adjoint", diff=_DP,
+                                      middle=f"Tensor? cell, {_LISTS}", outputs=_DP_OUT, systems="optional cell", refused=("cell",),
+                                      refusal=_CL_NO_GRAD),
+    "coulomb_quadrupole_correction": dict(module=_EL + "cluster", forward="_quadrupole_forward", adjoint="_quadrupole_adjoint", diff=_QD,
+                                          middle=f"Tensor? cell, {_LISTS}", outputs=_QD_OUT, systems="optional cell", refused=("cell",),
+                                          refusal=_CL_NO_GRAD),
+    "pair_scale_correction": dict(module=_EL + "pair_scale", forward="_forward", adjoint="_adjoint", diff=_QD,
+                                  middle=f"Tensor pair_scales, Tensor? cell, {_LISTS}, bool minimum_image", outputs=_QD_OUT,
+                                  systems="optional cell", refused=("cell",), refusal=_CL_NO_GRAD),
+    "dipole_pair_scale_correction": dict(module=_EL + "dipole_scale", forward="_forward", adjoint="_adjoint", diff=_TH,
+                                         middle=(f"Tensor? direct_scales, Tensor? mutual_scales, Tensor? cell, {_LISTS}, bool minimum_image, "
+                                                 "float thole"),
+                                         outputs=_TH_OUT, systems="optional cell", refused=("cell",), refusal=_CL_NO_GRAD),
+    "buffered_14_7": dict(_VDW, bound=(0,)),  # MI_VDW_BUFFERED_14_7
+    "lennard_jones": dict(_VDW, bound=(1,)),  # MI_VDW_LENNARD_JONES
+    **{name: dict(_VALENCE, bound=(kind,)) for kind, name in enumerate(_VALENCE_KINDS)},
+    "ewald_dispersion_real_space": dict(_DE, **_REAL, middle=f"Tensor cell, Tensor alpha, {_LISTS}, float counted_cutoff, float counted_taper",
+                                        systems="batch", refused=("cell", "alpha")),
+    "ewald_dispersion_reciprocal_space": dict(_DE, **_RECIP, middle=_KSUM, systems="cell rows", refused=("cell", "k_vectors", "alpha")),
+    # the mesh half: the mesh dimensions and the spline order travel as plain ints
+    "pme_dispersion_reciprocal_space": dict(_DE, **_RECIP, module=_VW + "pme",
+                                            middle="Tensor cell, Tensor alpha, Tensor? batch_idx, int nx, int ny, int nz, int order",
+                                            systems="batch", refused=("cell", "alpha")),
 }
 
 
-def _multipole_ops(name, module, forward, adjoint, diff, middle, extra, systems, no_adjoint, refusal):
-    """(forward op `alchemiops::_<name>`, backward op `nvalchemiops::<name>_backward`) of one row of `_MULTIPOLE_OPS`, with their fakes, the
+def _energy_ops(name, module, forward, adjoint, diff, middle, outputs, systems, refused=(), refusal=None, bound=(), per_system=()):
+    """(forward op `alchemiops::_<name>`, backward op `nvalchemiops::<name>_backward`) of one row of `_ENERGY_OPS`, with their fakes, the
     second-order refusal on the backward op and the forward op's autograd."""
     fwd_name, bwd_name = f"{_NS}::_{name}", f"nvalchemiops::{name}_backward"
-    mid = [a.split() for a in middle.split(", ")]  # [schema type, argument name]
-    names = list(diff) + [a[1] for a in mid]
-    n_diff, n_in = len(diff), len(names)
-    k = n_diff + sum(t.startswith("Tensor") for t, _ in mid)  # the tensors lead, the plain scalars trail
-    convert = [_SCALARS[t] for t, _ in mid[k - n_diff:]]
-    outputs = (("energies", ()), ("forces", (3,)), ("charge_gradients", ()), ("dipole_gradients", (3,))) + ((extra,) if extra else ())
+    inputs = f"{diff}, {middle}"
+    typed = [a.split() for a in inputs.split(", ")]  # [schema type, argument name]
+    names = [a[1] for a in typed]
+    n_diff, n_in = len(diff.split(", ")), len(names)
+    k = sum(t.startswith("Tensor") for t, _ in typed)  # the tensors lead and are saved for backward, the plain scalars trail
+    convert = [_SCALARS[t] for t, _ in typed[k:]]
+    whats = [o for o, _ in outputs] + ["virial"]
+    like = [names.index(src) for _, src in outputs]
     i_cell, i_batch, nsys_of = names.index("cell"), names.index("batch_idx"), _SYSTEMS[systems]
-    refused = {names.index(what): what for what in no_adjoint}
-    inputs = ", ".join([f"Tensor {d}" for d in diff] + [middle])
-    flags = ", ".join(f"bool compute_{o}" for o, _ in outputs[1:]) + ", bool compute_virial"
+    refused = {names.index(what): what for what in refused}
+    optional = any(t == "Tensor?" for t, _ in typed[:n_diff])  # a differentiable input that may be None: its gradient is then [0]
+    reshaped = [names.index(d) for d in per_system]  # a per-system gradient is returned in the shape of its input
+    flags =", ".join(f"bool compute_{o}" for o in whats)
 
     def run(fn_name, args, tail):
-        fn = getattr(importlib.import_module(f"nvalchemiops.interactions.electrostatics.{module}"), fn_name)
-        return fn(*args[:k], *[c(v) for c, v in zip(convert, args[k:n_in])], *tail)
+        # `from module import fn_name` at call time.  Not importlib.import_module: on a loaded module that takes the import lock, 10 us a
+        # call against under 2 us (Python 3.10), twice per forward + backward
+        fn = getattr(__import__(module, fromlist=(fn_name,)), fn_name)
+        return fn(*bound, *args[:k], *[c(v) for c, v in zip(convert, args[k:n_in])], *tail)
 
     def fwd(*args):
         return tuple(args[0].new_empty((0,)) if o is None else o for o in run(forward, args, args[n_in:]))
 
     def fwd_fake(*args):
         positions, want = args[0], (True,) + tuple(args[n_in:])
-        shapes = [(positions.shape[0],) + s for _, s in outputs] + [(nsys_of(args[i_cell], args[i_batch]), 3, 3)]
+        shapes = [(positions.shape[0],)] + [args[i].shape for i in like] + [(nsys_of(args[i_cell], args[i_batch]), 3, 3)]
         return tuple(positions.new_empty(s if w else (0,)) for s, w in zip(shapes, want))
 
     def bwd(*args):
-        return run(adjoint, args, (args[n_in],))
+        grads = run(adjoint, args, (args[n_in],))
+        return tuple(args[0].new_empty((0,), dtype=torch.float64) if g is None else g for g in grads) if optional else grads
 
-    def bwd_fake(positions, *rest):
-        return tuple(positions.new_empty((positions.shape[0],) + _PER_ATOM[d], dtype=torch.float64) for d in diff)
+    def bwd_fake(*args):
+        """A gradient has the shape of its input; a `per_system` one is [nsys, 3, 3]; that of an input that is None is [0]."""
+        shapes = [(0,) if a is None else (nsys_of(args[i_cell], args[i_batch]), 3, 3) if d in per_system else a.shape
+                  for d, a in zip(names, args[:n_diff])]
+        return tuple(args[0].new_empty(s, dtype=torch.float64) for s in shapes)
 
     def refuse_second_order(ctx, *grads):
         raise NotImplementedError(_SECOND_ORDER.format(op=bwd_name, what="gradient"))
@@ -1689,7 +1664,7 @@ def _multipole_ops(name, module, forward, adjoint, diff, middle, extra, systems,
         ctx.set_materialize_grads(False)
 
     def backward(ctx, g_e, *g_explicit):
-        for (what, _), g in zip(outputs[1:] + (("virial", None),), g_explicit):
+        for what, g in zip(whats, g_explicit):
             if g is not None:
                 raise NotImplementedError(_SECOND_ORDER.format(op=fwd_name, what=what))
         need = ctx.needs_input_grad
@@ -1699,28 +1674,40 @@ def _multipole_ops(name, module, forward, adjoint, diff, middle, extra, systems,
         if g_e is None:
             return (None,) * len(need)
         saved = ctx.saved_tensors
-        grads = bwd_op(*saved, *ctx.extra, g_e)
-        return tuple(g.to(t.dtype) if w else None for g, t, w in zip(grads, saved[:n_diff], need[:n_diff])) + (None,) * (len(need) - n_diff)
+        grads = list(bwd_op(*saved, *ctx.extra, g_e))
+        for i in reshaped:
+            if need[i]:
+                grads[i] = grads[i].reshape(saved[i].shape)
+        cast = tuple(g.to(t.dtype) if w else None for g, t, w in zip(grads, saved[:n_diff], need[:n_diff]))
+        return cast + (None,) * (len(need) - n_diff)
 
     fwd_op = torch.library.custom_op(fwd_name, fwd, mutates_args=(),
-                                     schema=f"({inputs}, {flags}) -> ({', '.join(['Tensor'] * (len(outputs) + 1))})")
+                                     schema=f"({inputs}, {flags}) -> ({', '.join(['Tensor'] * (len(whats) + 1))})")
     fwd_op.register_fake(fwd_fake)
     fwd_op.register_autograd(backward, setup_context=setup)
     return fwd_op, bwd_op
 
 
-_MP = {name: _multipole_ops(name, *row) for name, row in _MULTIPOLE_OPS.items()}
-ewald_dipole_real_space_op, ewald_dipole_real_bwd_op = _MP["ewald_dipole_real_space"]
-ewald_dipole_reciprocal_space_op, ewald_dipole_recip_bwd_op = _MP["ewald_dipole_reciprocal_space"]
-pme_dipole_reciprocal_space_op, pme_dipole_recip_bwd_op = _MP["pme_dipole_reciprocal_space"]
-thole_dipole_correction_op, thole_dipole_bwd_op = _MP["thole_dipole_correction"]
-ewald_quadrupole_real_space_op, ewald_quadrupole_real_bwd_op = _MP["ewald_quadrupole_real_space"]
-ewald_quadrupole_reciprocal_space_op, ewald_quadrupole_recip_bwd_op = _MP["ewald_quadrupole_reciprocal_space"]
-pme_quadrupole_reciprocal_space_op, pme_quadrupole_recip_bwd_op = _MP["pme_quadrupole_reciprocal_space"]
-coulomb_dipole_correction_op, coulomb_dipole_bwd_op = _MP["coulomb_dipole_correction"]
-coulomb_quadrupole_correction_op, coulomb_quadrupole_bwd_op = _MP["coulomb_quadrupole_correction"]
-pair_scale_correction_op, pair_scale_bwd_op = _MP["pair_scale_correction"]
-dipole_pair_scale_correction_op, dipole_pair_scale_bwd_op = _MP["dipole_pair_scale_correction"]
+_EO = {name: _energy_ops(name, **row) for name, row in _ENERGY_OPS.items()}
+gaussian_charge_correction_op, gaussian_bwd_op = _EO["gaussian_charge_correction"]
+ewald_dipole_real_space_op, ewald_dipole_real_bwd_op = _EO["ewald_dipole_real_space"]
+ewald_dipole_reciprocal_space_op, ewald_dipole_recip_bwd_op = _EO["ewald_dipole_reciprocal_space"]
+pme_dipole_reciprocal_space_op, pme_dipole_recip_bwd_op = _EO["pme_dipole_reciprocal_space"]
+thole_dipole_correction_op, thole_dipole_bwd_op = _EO["thole_dipole_correction"]
+ewald_quadrupole_real_space_op, ewald_quadrupole_real_bwd_op = _EO["ewald_quadrupole_real_space"]
+ewald_quadrupole_reciprocal_space_op, ewald_quadrupole_recip_bwd_op = _EO["ewald_quadrupole_reciprocal_space"]
+pme_quadrupole_reciprocal_space_op, pme_quadrupole_recip_bwd_op = _EO["pme_quadrupole_reciprocal_space"]
+coulomb_dipole_correction_op, coulomb_dipole_bwd_op = _EO["coulomb_dipole_correction"]
+coulomb_quadrupole_correction_op, coulomb_quadrupole_bwd_op = _EO["coulomb_quadrupole_correction"]
+pair_scale_correction_op, pair_scale_bwd_op = _EO["pair_scale_correction"]
+dipole_pair_scale_correction_op, dipole_pair_scale_bwd_op = _EO["dipole_pair_scale_correction"]
+buffered_14_7_op, buffered_14_7_bwd_op = _EO["buffered_14_7"]
+lennard_jones_op, lennard_jones_bwd_op = _EO["lennard_jones"]
+VDW_OPS = (buffered_14_7_op, lennard_jones_op)  # by MI_VDW_BUFFERED_14_7 / MI_VDW_LENNARD_JONES
+VALENCE_OPS, VALENCE_BWD_OPS = zip(*(_EO[name] for name in _VALENCE_KINDS))
+ewald_dispersion_real_space_op, ewald_dispersion_real_bwd_op = _EO["ewald_dispersion_real_space"]
+ewald_dispersion_reciprocal_space_op, ewald_dispersion_recip_bwd_op = _EO["ewald_dispersion_reciprocal_space"]
+pme_dispersion_reciprocal_space_op, pme_dispersion_recip_bwd_op = _EO["pme_dispersion_reciprocal_space"]
 
 
 # =====================================================================================================================================
@@ -1800,258 +1787,17 @@ rotate_multipoles_op.register_fake(_rotate_fwd_fake)
 rotate_multipoles_op.register_autograd(_rotate_backward, setup_context=_rotate_setup)
 
 
-# =====================================================================================================================================
-# van der Waals pair potentials (buffered 14-7, Lennard-Jones): one forward / backward op pair per kind, written as the Gaussian op above
-# =====================================================================================================================================
-# Outputs are always the five of the public functions; the ones not asked for are empty [0] tensors.  The energies are differentiable w.r.t.
-# positions, radii and epsilons: the backward op runs the forward kernels with the incoming gradient as per-atom weights.  The site tables,
-# the pair scales and the cell have no gradient (the virial is the strain derivative).
-_VDW_OUTPUTS = ("energies", "forces", "radius_gradients", "epsilon_gradients", "virial")
-_VDW_TENSORS = 15  # positions ... neighbor_matrix_shifts
-
-
-def _make_vdw_ops(kind: int, name: str):
-    fwd_name, bwd_name = f"{_NS}::_{name}", f"nvalchemiops::{name}_backward"
-
-    def fwd(positions: Tensor, radii: Tensor, epsilons: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor], parent: Optional[Tensor],
-            reduction: Optional[Tensor], child_ptr: Optional[Tensor], child_idx: Optional[Tensor], pair_scales: Optional[Tensor],
-            neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor], neighbor_matrix: Optional[Tensor],
-            neighbor_matrix_shifts: Optional[Tensor], mask_value: int, cutoff: float, taper: float, delta: float, gamma: float, radius_rule: int,
-            epsilon_rule: int, compute_forces: bool, compute_radius_gradients: bool, compute_epsilon_gradients: bool,
-            compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
-        from nvalchemiops.interactions.vdw.pair import _forward
-
-        out = _forward(kind, positions, radii, epsilons, cell, batch_idx, parent, reduction, child_ptr, child_idx, pair_scales, neighbor_list,
-                       neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, int(mask_value), cutoff, taper, delta, gamma,
-                       int(radius_rule), int(epsilon_rule), compute_forces, compute_radius_gradients, compute_epsilon_gradients, compute_virial)
-        return tuple(positions.new_empty((0,)) if o is None else o for o in out)
-
-    def fwd_fake(positions, radii, epsilons, cell, batch_idx, parent, reduction, child_ptr, child_idx, pair_scales, neighbor_list, neighbor_ptr,
-                 neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, mask_value, cutoff, taper, delta, gamma, radius_rule, epsilon_rule,
-                 compute_forces, compute_radius_gradients, compute_epsilon_gradients, compute_virial):
-        n = positions.shape[0]
-        nsys = cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1
-        empty = lambda: positions.new_empty((0,))  # noqa: E731
-        return (positions.new_empty((n,)), positions.new_empty((n, 3)) if compute_forces else empty(),
-                positions.new_empty((n,)) if compute_radius_gradients else empty(), positions.new_empty((n,)) if compute_epsilon_gradients else empty(),
-                positions.new_empty((nsys, 3, 3)) if compute_virial else empty())
-
-    def bwd(positions: Tensor, radii: Tensor, epsilons: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor], parent: Optional[Tensor],
-            reduction: Optional[Tensor], child_ptr: Optional[Tensor], child_idx: Optional[Tensor], pair_scales: Optional[Tensor],
-            neighbor_list: Optional[Tensor], neighbor_ptr: Optional[Tensor], neighbor_shifts: Optional[Tensor], neighbor_matrix: Optional[Tensor],
-            neighbor_matrix_shifts: Optional[Tensor], mask_value: int, cutoff: float, taper: float, delta: float, gamma: float, radius_rule: int,
-            epsilon_rule: int, grad_energies: Tensor) -> tuple[Tensor, Tensor, Tensor]:
-        """Float64 (dL/dpositions, dL/dradii, dL/depsilons) for L = sum_i g_i E_i."""
-        from nvalchemiops.interactions.vdw.pair import _adjoint
-
-        return _adjoint(kind, positions, radii, epsilons, cell, batch_idx, parent, reduction, child_ptr, child_idx, pair_scales, neighbor_list,
-                        neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts, int(mask_value), cutoff, taper, delta, gamma,
-                        int(radius_rule), int(epsilon_rule), grad_energies)
-
-    def bwd_fake(positions, *rest):
-        n, f64 = positions.shape[0], dict(dtype=torch.float64)
-        return positions.new_empty((n, 3), **f64), positions.new_empty((n,), **f64), positions.new_empty((n,), **f64)
-
-    bwd_op = torch.library.custom_op(bwd_name, bwd, mutates_args=())
-    bwd_op.register_fake(bwd_fake)
-    bwd_op.register_autograd(lambda ctx, *g: (_ for _ in ()).throw(NotImplementedError(_SECOND_ORDER.format(op=bwd_name, what="gradient"))),
-                             setup_context=lambda ctx, inputs, output: None)
-
-    def setup(ctx, inputs, output):
-        ctx.save_for_backward(*inputs[:_VDW_TENSORS])
-        ctx.model = inputs[_VDW_TENSORS:_VDW_TENSORS + 7]
-        ctx.set_materialize_grads(False)
-
-    def backward(ctx, g_e, *g_explicit):
-        for what, g in zip(_VDW_OUTPUTS[1:], g_explicit):
-            if g is not None:
-                raise NotImplementedError(_SECOND_ORDER.format(op=fwd_name, what=what))
-        need = ctx.needs_input_grad
-        if g_e is None:
-            return (None,) * len(need)
-        saved = ctx.saved_tensors
-        mask, cutoff, taper, delta, gamma, rrule, erule = ctx.model
-        gpos, gr, ge = bwd_op(*saved, int(mask), float(cutoff), float(taper), float(delta), float(gamma), int(rrule), int(erule), g_e)
-        return (gpos.to(saved[0].dtype) if need[0] else None, gr.to(saved[1].dtype) if need[1] else None,
-                ge.to(saved[2].dtype) if need[2] else None) + (None,) * (len(need) - 3)
-
-    return _op(f"_{name}", fwd, fwd_fake, backward, setup), bwd_op
-
-
-buffered_14_7_op, buffered_14_7_bwd_op = _make_vdw_ops(0, "buffered_14_7")
-lennard_jones_op, lennard_jones_bwd_op = _make_vdw_ops(1, "lennard_jones")
-VDW_OPS = (buffered_14_7_op, lennard_jones_op)  # by MI_VDW_BUFFERED_14_7 / MI_VDW_LENNARD_JONES
-
-
-# =====================================================================================================================================
-# valence terms (nvalchemiops/interactions/valence): one forward / backward op pair per kind, written as the vdW ops above
-# =====================================================================================================================================
-# Outputs are always (energies, forces, parameter_gradients, virial); the ones not asked for are empty [0] tensors.  The energies are
-# differentiable w.r.t. positions and parameters: the backward op runs the forward kernels with the incoming gradient as per-atom weights.
-# The term tables and the cell have no gradient (the virial is the strain derivative).
-_VALENCE_OUTPUTS = ("energies", "forces", "parameter_gradients", "virial")
-_VALENCE_TENSORS = 7  # positions ... slot_idx
-
-
-def _make_valence_ops(kind: int, name: str):
-    fwd_name, bwd_name = f"{_NS}::_{name}", f"nvalchemiops::{name}_backward"
-
-    def fwd(positions: Tensor, parameters: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor], atoms: Tensor, slot_ptr: Tensor,
-            slot_idx: Tensor, cubic: float, quartic: float, pentic: float, sextic: float, plane: int, compute_forces: bool,
-            compute_parameter_gradients: bool, compute_virial: bool) -> tuple[Tensor, Tensor, Tensor, Tensor]:
-        from nvalchemiops.interactions.valence.functions import _forward
-
-        out = _forward(kind, positions, parameters, cell, batch_idx, atoms, slot_ptr, slot_idx, cubic, quartic, pentic, sextic, int(plane),
-                       compute_forces, compute_parameter_gradients, compute_virial)
-        return tuple(positions.new_empty((0,)) if o is None else o for o in out)
-
-    def fwd_fake(positions, parameters, cell, batch_idx, atoms, slot_ptr, slot_idx, cubic, quartic, pentic, sextic, plane, compute_forces,
-                 compute_parameter_gradients, compute_virial):
-        n = positions.shape[0]
-        nsys = cell.reshape(-1, 3, 3).shape[0] if (cell is not None and batch_idx is not None) else 1
-        empty = lambda: positions.new_empty((0,))  # noqa: E731
-        return (positions.new_empty((n,)), positions.new_empty((n, 3)) if compute_forces else empty(),
-                positions.new_empty(parameters.shape) if compute_parameter_gradients else empty(),
-                positions.new_empty((nsys, 3, 3)) if compute_virial else empty())
-
-    def bwd(positions: Tensor, parameters: Tensor, cell: Optional[Tensor], batch_idx: Optional[Tensor], atoms: Tensor, slot_ptr: Tensor,
-            slot_idx: Tensor, cubic: float, quartic: float, pentic: float, sextic: float, plane: int,
-            grad_energies: Tensor) -> tuple[Tensor, Tensor]:
-        """Float64 (dL/dpositions, dL/dparameters) for L = sum_i g_i E_i."""
-        from nvalchemiops.interactions.valence.functions import _adjoint
-
-        return _adjoint(kind, positions, parameters, cell, batch_idx, atoms, slot_ptr, slot_idx, cubic, quartic, pentic, sextic, int(plane),
-                        grad_energies)
-
-    def bwd_fake(positions, parameters, *rest):
-        f64 = dict(dtype=torch.float64)
-        return positions.new_empty((positions.shape[0], 3), **f64), positions.new_empty(parameters.shape, **f64)
-
-    bwd_op = torch.library.custom_op(bwd_name, bwd, mutates_args=())
-    bwd_op.register_fake(bwd_fake)
-    bwd_op.register_autograd(lambda ctx, *g: (_ for _ in ()).throw(NotImplementedError(_SECOND_ORDER.format(op=bwd_name, what="gradient"))),
-                             setup_context=lambda ctx, inputs, output: None)
-
-    def setup(ctx, inputs, output):
-        ctx.save_for_backward(*inputs[:_VALENCE_TENSORS])
-        ctx.model = inputs[_VALENCE_TENSORS:_VALENCE_TENSORS + 5]
-        ctx.set_materialize_grads(False)
-
-    def backward(ctx, g_e, *g_explicit):
-        for what, g in zip(_VALENCE_OUTPUTS[1:], g_explicit):
-            if g is not None:
-                raise NotImplementedError(_SECOND_ORDER.format(op=fwd_name, what=what))
-        need = ctx.needs_input_grad
-        if g_e is None:
-            return (None,) * len(need)
-        saved = ctx.saved_tensors
-        cubic, quartic, pentic, sextic, plane = ctx.model
-        gpos, gpar = bwd_op(*saved, float(cubic), float(quartic), float(pentic), float(sextic), int(plane), g_e)
-        return (gpos.to(saved[0].dtype) if need[0] else None, gpar.to(saved[1].dtype) if need[1] else None) + (None,) * (len(need) - 2)
-
-    return _op(f"_{name}", fwd, fwd_fake, backward, setup), bwd_op
-
-
-VALENCE_OPS, VALENCE_BWD_OPS = zip(*(_make_valence_ops(_kind, _name) for _kind, _name in enumerate(  # by MI_VALENCE_BOND .. MI_VALENCE_TORSION
-    ("bond_stretch", "angle_bend", "stretch_bend", "out_of_plane_bend", "torsion"))))
-
-
-# =====================================================================================================================================
-# dispersion Ewald sum (nvalchemiops/interactions/vdw/ewald.py): one forward / backward op pair per half, from one maker
-# =====================================================================================================================================
-# Outputs are always (energies, forces, coefficient_gradients, virial); the ones not asked for are empty [0] tensors.  The energies are
-# differentiable w.r.t. positions and coefficients: the backward op runs the forward kernels with the incoming gradient as per-atom weights
-# and returns float64 gradients.  Gradients w.r.t. cell, k-vectors and alpha are refused, never a silent zero: the virial is the strain
-# derivative.  The ops are registered with an explicit schema string, so the implementations take *args in schema order.
-_DE_NO_GRAD = ("{op}: gradients w.r.t. {what} are not provided by the dispersion Ewald sum (out of scope); use compute_virial for the strain "
-               "derivative.")
-_DE_OUTPUTS = ("forces", "coefficient_gradients", "virial")
-
-
-def _dispersion_ewald_ops(name, forward, adjoint, middle, n_tensors, refused, module="nvalchemiops.interactions.vdw.ewald"):
-    """(forward op `alchemiops::_<name>`, backward op `nvalchemiops::<name>_backward`).  `middle`: the schema of the arguments between the two
-    differentiable inputs and the flags, its first `n_tensors` tensors (saved for backward), the rest plain scalars; `refused`: argument
-    index -> name of the inputs without an adjoint; `module` holds `forward` and `adjoint`."""
-    fwd_name, bwd_name = f"{_NS}::_{name}", f"nvalchemiops::{name}_backward"
-    mid = [a.split() for a in middle.split(", ")]
-    k, n_in = 2 + n_tensors, 2 + len(mid)
-    convert = [_SCALARS[t] for t, _ in mid[n_tensors:]]
-    i_cell, i_batch = 2, 2 + [a[1] for a in mid].index("batch_idx")
-    inputs = f"Tensor positions, Tensor coefficients, {middle}"
-
-    def run(fn_name, args, tail):
-        fn = getattr(importlib.import_module(module), fn_name)
-        return fn(*args[:k], *[c(v) for c, v in zip(convert, args[k:n_in])], *tail)
-
-    def fwd(*args):
-        return tuple(args[0].new_empty((0,)) if o is None else o for o in run(forward, args, args[n_in:]))
-
-    def fwd_fake(*args):
-        positions, want = args[0], (True,) + tuple(args[n_in:])
-        n, cell = positions.shape[0], args[i_cell]
-        nsys = cell.reshape(-1, 3, 3).shape[0] if (args[i_batch] is not None or name.endswith("reciprocal_space")) else 1
-        return tuple(positions.new_empty(s if w else (0,)) for s, w in zip(((n,), (n, 3), (n,), (nsys, 3, 3)), want))
-
-    def bwd(*args):
-        return run(adjoint, args, (args[n_in],))
-
-    def bwd_fake(positions, *rest):
-        n = positions.shape[0]
-        return positions.new_empty((n, 3), dtype=torch.float64), positions.new_empty((n,), dtype=torch.float64)
-
-    def refuse_second_order(ctx, *grads):
-        raise NotImplementedError(_SECOND_ORDER.format(op=bwd_name, what="gradient"))
-
-    bwd_op = torch.library.custom_op(bwd_name, bwd, mutates_args=(), schema=f"({inputs}, Tensor grad_energies) -> (Tensor, Tensor)")
-    bwd_op.register_fake(bwd_fake)
-    bwd_op.register_autograd(refuse_second_order, setup_context=lambda ctx, inputs, output: None)
-
-    def setup(ctx, inputs, output):
-        ctx.save_for_backward(*inputs[:k])
-        ctx.extra = tuple(c(v) for c, v in zip(convert, inputs[k:n_in]))
-        ctx.set_materialize_grads(False)
-
-    def backward(ctx, g_e, *g_explicit):
-        for what, g in zip(_DE_OUTPUTS, g_explicit):
-            if g is not None:
-                raise NotImplementedError(_SECOND_ORDER.format(op=fwd_name, what=what))
-        need = ctx.needs_input_grad
-        for i, what in refused.items():
-            if need[i]:
-                raise NotImplementedError(_DE_NO_GRAD.format(op=fwd_name, what=what))
-        if g_e is None:
-            return (None,) * len(need)
-        saved = ctx.saved_tensors
-        gpos, gc = bwd_op(*saved, *ctx.extra, g_e)
-        return (gpos.to(saved[0].dtype) if need[0] else None, gc.to(saved[1].dtype) if need[1] else None) + (None,) * (len(need) - 2)
-
-    flags = "bool compute_forces, bool compute_coefficient_gradients, bool compute_virial"
-    fwd_op = torch.library.custom_op(fwd_name, fwd, mutates_args=(), schema=f"({inputs}, {flags}) -> (Tensor, Tensor, Tensor, Tensor)")
-    fwd_op.register_fake(fwd_fake)
-    fwd_op.register_autograd(backward, setup_context=setup)
-    return fwd_op, bwd_op
-
-
-ewald_dispersion_real_space_op, ewald_dispersion_real_bwd_op = _dispersion_ewald_ops(
-    "ewald_dispersion_real_space", "_real_forward", "_real_adjoint",
-    f"Tensor cell, Tensor alpha, {_LISTS}, float counted_cutoff, float counted_taper", 8, {2: "cell", 3: "alpha"})
-ewald_dispersion_reciprocal_space_op, ewald_dispersion_recip_bwd_op = _dispersion_ewald_ops(
-    "ewald_dispersion_reciprocal_space", "_recip_forward", "_recip_adjoint", _KSUM, 4, {2: "cell", 3: "k_vectors", 4: "alpha"})
-# the mesh half (nvalchemiops/interactions/vdw/pme.py): the mesh dimensions and the spline order travel as plain ints
-pme_dispersion_reciprocal_space_op, pme_dispersion_recip_bwd_op = _dispersion_ewald_ops(
-    "pme_dispersion_reciprocal_space", "_recip_forward", "_recip_adjoint",
-    "Tensor cell, Tensor alpha, Tensor? batch_idx, int nx, int ny, int nz, int order", 3, {2: "cell", 3: "alpha"},
-    module="nvalchemiops.interactions.vdw.pme")
-
-
-__all__ = ["pme_dispersion_reciprocal_space_op", "pme_dispersion_recip_bwd_op", "ewald_dispersion_real_space_op", "ewald_dispersion_real_bwd_op", "ewald_dispersion_reciprocal_space_op", "ewald_dispersion_recip_bwd_op",
-           "buffered_14_7_op", "buffered_14_7_bwd_op", "lennard_jones_op", "lennard_jones_bwd_op", "VDW_OPS",
-           "pair_scale_correction_op", "pair_scale_bwd_op", "dipole_pair_scale_correction_op", "dipole_pair_scale_bwd_op", "rotate_multipoles_op", "rotate_multipoles_bwd_op", "coulomb_dipole_correction_op", "coulomb_dipole_bwd_op", "coulomb_quadrupole_correction_op", "coulomb_quadrupole_bwd_op",
-           "pme_quadrupole_reciprocal_space_op", "pme_quadrupole_recip_bwd_op",
-           "ewald_quadrupole_real_space_op", "ewald_quadrupole_reciprocal_space_op", "ewald_quadrupole_real_bwd_op",
-           "ewald_quadrupole_recip_bwd_op", "thole_dipole_correction_op", "thole_dipole_bwd_op", "pme_dipole_reciprocal_space_op", "pme_dipole_recip_bwd_op", "ewald_dipole_real_space_op", "ewald_dipole_reciprocal_space_op", "ewald_dipole_real_bwd_op", "ewald_dipole_recip_bwd_op",
-           "gaussian_charge_correction_op", "gaussian_bwd_op","spline_spread_op", "batch_spline_spread_op", "spline_gather_op", "batch_spline_gather_op", "spline_gather_vec3_op",
-           "batch_spline_gather_vec3_op", "spline_gather_gradient_op", "batch_spline_gather_gradient_op", "pme_green_structure_factor_op",
-           "batch_pme_green_structure_factor_op", "pme_energy_corrections_op", "batch_pme_energy_corrections_op",
-           "pme_energy_corrections_with_charge_grad_op", "batch_pme_energy_corrections_with_charge_grad_op", "REAL_OPS", "real_space_op", "RECIPROCAL_OPS", "reciprocal_space_op", "COULOMB_OPS", "coulomb_op",
-           "ewald_real_virial_op", "ewald_recip_virial_op", "pme_recip_virial_op"]
+__all__ = ["pme_dispersion_reciprocal_space_op", "pme_dispersion_recip_bwd_op", "ewald_dispersion_real_space_op", "ewald_dispersion_real_bwd_op",
+           "ewald_dispersion_reciprocal_space_op", "ewald_dispersion_recip_bwd_op", "buffered_14_7_op", "buffered_14_7_bwd_op", "lennard_jones_op",
+           "lennard_jones_bwd_op", "VDW_OPS", "pair_scale_correction_op", "pair_scale_bwd_op", "dipole_pair_scale_correction_op",
+           "dipole_pair_scale_bwd_op", "rotate_multipoles_op", "rotate_multipoles_bwd_op", "coulomb_dipole_correction_op", "coulomb_dipole_bwd_op",
+           "coulomb_quadrupole_correction_op", "coulomb_quadrupole_bwd_op", "pme_quadrupole_reciprocal_space_op", "pme_quadrupole_recip_bwd_op",
+           "ewald_quadrupole_real_space_op", "ewald_quadrupole_reciprocal_space_op", "ewald_quadrupole_real_bwd_op", "ewald_quadrupole_recip_bwd_op",
+           "thole_dipole_correction_op", "thole_dipole_bwd_op", "pme_dipole_reciprocal_space_op", "pme_dipole_recip_bwd_op",
+           "ewald_dipole_real_space_op", "ewald_dipole_reciprocal_space_op", "ewald_dipole_real_bwd_op", "ewald_dipole_recip_bwd_op",
+           "gaussian_charge_correction_op", "gaussian_bwd_op", "spline_spread_op", "batch_spline_spread_op", "spline_gather_op",
+           "batch_spline_gather_op", "spline_gather_vec3_op", "batch_spline_gather_vec3_op", "spline_gather_gradient_op",
+           "batch_spline_gather_gradient_op", "pme_green_structure_factor_op", "batch_pme_green_structure_factor_op", "pme_energy_corrections_op",
+           "batch_pme_energy_corrections_op", "pme_energy_corrections_with_charge_grad_op", "batch_pme_energy_corrections_with_charge_grad_op",
+           "REAL_OPS", "real_space_op", "RECIPROCAL_OPS", "reciprocal_space_op", "COULOMB_OPS", "coulomb_op", "ewald_real_virial_op",
+           "ewald_recip_virial_op", "pme_recip_virial_op"]

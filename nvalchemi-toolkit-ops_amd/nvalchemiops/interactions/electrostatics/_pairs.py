@@ -91,6 +91,19 @@ def needs_op(*tensors) -> bool:
     return C.tracing() or (torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors))
 
 
+def dispatch(op, forward, args, tensors, want, kind=None):
+    """The tail of a public function: when `needs_op(*tensors)`, through the op that `nvalchemiops._eops` holds under the name `op` (with a
+    `kind`: the tuple of a family's ops, indexed by it), else straight to `forward`; both take `args`.  Then the outputs that were asked for."""
+    if needs_op(*tensors):
+        from nvalchemiops import _eops
+
+        op = getattr(_eops, op)
+        res = (op if kind is None else op[kind])(*args)
+    else:
+        res = forward(*args)
+    return select(res, want)
+
+
 def zeros(n, nsys, dt, dev, *grads):
     """All outputs of an operator as zeros: energies, forces, one gradient per per-atom shape in `grads` (() charges or sigma, (3,) dipoles,
     (3, 3) quadrupoles), virial."""

@@ -197,13 +197,8 @@ def gaussian_charge_correction(positions: torch.Tensor, charges: torch.Tensor, s
     sig = _sigma_tensor(sigma, n, dt, dev)
     lists = (neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix, neighbor_matrix_shifts)
     flags = (bool(self_energy), background, bool(compute_forces), bool(compute_charge_gradients), bool(compute_sigma_gradients), bool(compute_virial))
-    if P.needs_op(positions, charges, sig, cell):
-        from nvalchemiops import _eops
-
-        res = _eops.gaussian_charge_correction_op(positions, charges.to(dt), sig, cell, batch_idx, *lists, int(mask_value), *flags)
-    else:
-        res = _forward(positions, charges, sig, cell, batch_idx, *lists, int(mask_value), *flags)
-    return P.select(res, want)
+    args = (positions, charges.to(dt), sig, cell, batch_idx, *lists, int(mask_value), *flags)
+    return P.dispatch("gaussian_charge_correction_op", _forward, args, (positions, charges, sig, cell), want)
 
 
 __all__ = ["gaussian_charge_correction"]

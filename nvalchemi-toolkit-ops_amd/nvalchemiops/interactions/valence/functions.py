@@ -9,6 +9,7 @@ reference package has no counterpart."""
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import torch
 
@@ -129,13 +130,7 @@ def _call(kind, positions, terms, parameters, cell, consts, plane, batch_idx, co
         return P.select((z(n), z(n, 3), z(*parameters.shape), z(nsys, 3, 3)), want)
     args = (positions, parameters.to(dt), cell, batch_idx, terms.atoms, terms.slot_ptr, terms.slot_idx, *(float(c) for c in consts), int(plane),
             bool(compute_forces), bool(compute_parameter_gradients), bool(compute_virial))
-    if P.needs_op(positions, parameters):
-        from nvalchemiops import _eops
-
-        res = _eops.VALENCE_OPS[kind](*args)
-    else:
-        res = _forward(kind, *args)
-    return P.select(res, want)
+    return P.dispatch("VALENCE_OPS", functools.partial(_forward, kind), args, (positions, parameters), want, kind)
 
 
 @C.traceable

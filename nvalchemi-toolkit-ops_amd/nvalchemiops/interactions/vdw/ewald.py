@@ -80,23 +80,8 @@ def _check_counted(counted_cutoff, counted_taper):
     return float(counted_cutoff), -1.0 if counted_taper is None else float(counted_taper)
 
 
-def _select(res, want):
-    return P.select(res, want)
-
-
 def _zeros(n, nsys, dt, dev, want):
     return tuple(r if w else None for r, w in zip(P.zeros(n, nsys, dt, dev, ()), want))
-
-
-def _dispatch(op, forward, args, tensors, want):
-    """Through the `_eops` op under torch.compile or when autograd has to record the call, else straight to `forward`."""
-    if P.needs_op(*tensors):
-        from nvalchemiops import _eops
-
-        res = getattr(_eops, op)(*args)
-    else:
-        res = forward(*args)
-    return _select(res, want)
 
 
 # ---- real space ---------------------------------------------------------------------------------------------------------------------------
@@ -182,11 +167,11 @@ def ewald_dispersion_real_space(positions: torch.Tensor, coefficients: torch.Ten
     want = (True, compute_forces, compute_coefficient_gradients, compute_virial)
     n, dt, dev = positions.shape[0], positions.dtype, positions.device
     if n == 0:
-        return _select(P.zeros(0, P.num_systems(cell, batch_idx), dt, dev, ()), want)
+        return P.select(P.zeros(0, P.num_systems(cell, batch_idx), dt, dev, ()), want)
     alpha_t = _prepare_alpha(alpha, _prepare_cell(cell)[1], dt, dev)
     args = (positions, coefficients.to(dt), cell, alpha_t, batch_idx, neighbor_list, neighbor_ptr, neighbor_shifts, neighbor_matrix,
             neighbor_matrix_shifts, int(mask_value), *counted, bool(compute_forces), bool(compute_coefficient_gradients), bool(compute_virial))
-    return _dispatch("ewald_dispersion_real_space_op", _real_forward, args, (positions, coefficients, cell, alpha_t), want)
+    return P.dispatch("ewald_dispersion_real_space_op", _real_forward, args, (positions, coefficients, cell, alpha_t), want)
 
 
 # ---- reciprocal space ---------------------------------------------------------------------------------------------------------------------
@@ -293,11 +278,11 @@ def ewald_dispersion_reciprocal_space(positions: torch.Tensor, coefficients: tor
         raise ValueError(f"k_vectors must have shape [K, 3] or [{n_sys}, K, 3], got {tuple(k_vectors.shape)}")
     want = (True, compute_forces, compute_coefficient_gradients, compute_virial)
     if n == 0:
-        return _select(P.zeros(0, n_sys, dt, dev, ()), want)
+        return P.select(P.zeros(0, n_sys, dt, dev, ()), want)
     alpha_t = _prepare_alpha(alpha, n_sys, dt, dev)
     args = (positions, coefficients.to(dt), cells, k_vectors, alpha_t, batch_idx, bool(compute_forces), bool(compute_coefficient_gradients),
             bool(compute_virial))
-    return _dispatch("ewald_dispersion_reciprocal_space_op", _recip_forward, args, (positions, coefficients, cells, k_vectors, alpha_t), want)
+    return P.dispatch("ewald_dispersion_reciprocal_space_op", _recip_forward, args, (positions, coefficients, cells, k_vectors, alpha_t), want)
 
 
 @C.traceable

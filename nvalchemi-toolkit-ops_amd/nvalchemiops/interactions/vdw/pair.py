@@ -9,6 +9,7 @@ and without per-atom weights, so every output is bit-reproducible.  The referenc
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import torch
 
@@ -175,13 +176,7 @@ def _call(kind, positions, radii, epsilons, cell, cutoff, taper, sites, pair_sca
     args = (positions, radii.to(dt), epsilons.to(dt), cell, batch_idx, *tables, pair_scales, neighbor_list, neighbor_ptr, neighbor_shifts,
             neighbor_matrix, neighbor_matrix_shifts, int(mask_value), float(cutoff), -1.0 if taper is None else float(taper), float(delta),
             float(gamma), rrule, erule, bool(compute_forces), bool(compute_radius_gradients), bool(compute_epsilon_gradients), bool(compute_virial))
-    if P.needs_op(positions, radii, epsilons):
-        from nvalchemiops import _eops
-
-        res = _eops.VDW_OPS[kind](*args)
-    else:
-        res = _forward(kind, *args)
-    return P.select(res, want)
+    return P.dispatch("VDW_OPS", functools.partial(_forward, kind), args, (positions, radii, epsilons), want, kind)
 
 
 @C.traceable

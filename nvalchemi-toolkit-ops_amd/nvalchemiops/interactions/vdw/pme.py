@@ -173,7 +173,7 @@ def pme_dispersion_reciprocal_space(positions: torch.Tensor, coefficients: torch
     alpha_t = M._mesh_alpha(alpha, n_sys, positions)
     args = (positions, coefficients.to(dt), cells, alpha_t, batch_idx, *dims, order, bool(compute_forces), bool(compute_coefficient_gradients),
             bool(compute_virial))
-    return E._dispatch("pme_dispersion_reciprocal_space_op", _recip_forward, args, (positions, coefficients, cells, alpha_t), want)
+    return P.dispatch("pme_dispersion_reciprocal_space_op", _recip_forward, args, (positions, coefficients, cells, alpha_t), want)
 
 
 @C.traceable

@@ -130,12 +130,48 @@ def test_eager_call_and_custom_op_are_bit_identical(name, layout, dtype):
     assert float(eager[0].abs().min()) > 0 and float(eager[-1].abs().max()) > 0  # both systems have an energy, and there is a virial
 
 
-# ---- van der Waals pairs and the dispersion Ewald sum: the `VDW_OPS` and `ewald_dispersion_*_op` rows of _eops.py -------------------------------
-# Their ops are written as the dispersion ops above are (one forward / backward pair, outputs not asked for as empty [0] tensors), so they are
-# compared here: the eager `_forward` against the op, bit for bit, and the op's backward against the adjoint function.  The input is the batch
-# fixture of tests/layout_cases.py (three cells of their own, reduced sites, scales, per-system alpha and k-vectors).
+# ---- the energy op pairs of _eops.py outside tests/test_multipole_call_gpu.py: van der Waals pairs, the dispersion Ewald sum and its mesh half,
+# ---- Gaussian charges, scaled dipole pairs, the five valence kinds -----------------------------------------------------------------------------
+# Every pair is a row of one table built by one maker (one forward / backward pair, outputs not asked for as empty [0] tensors), so they are
+# compared here: the eager `_forward` against the op, bit for bit, and the op's backward against the adjoint function.  The inputs are the
+# batch fixtures of tests/layout_cases.py (cells of their own, reduced sites, scales, per-system alpha and k-vectors, an (8, 10, 12) mesh) and
+# the "batch" case of tests/test_valence_gpu.py (three cells, the middle system empty): tens of atoms in 2 - 3 systems, the smallest input
+# that tells an argument in the wrong slot, a scalar taken for a saved tensor, a dropped flag and a per-system mix-up apart.
+VALENCE_KINDS = ("bond_stretch", "angle_bend", "stretch_bend", "out_of_plane_bend", "torsion")
+MESH_DIMS, MESH_ORDER = (8, 10, 12), 5
+# family: (the op's outputs after the energies, the inputs whose gradient the op refuses)
+FAMILIES = {
+    "buffered_14_7": (("forces", "radius_gradients", "epsilon_gradients", "virial"), ()),
+    "lennard_jones": (("forces", "radius_gradients", "epsilon_gradients", "virial"), ()),
+    "ewald_dispersion_real_space": (("forces", "coefficient_gradients", "virial"), ("cell", "alpha")),
+    "ewald_dispersion_reciprocal_space": (("forces", "coefficient_gradients", "virial"), ("cell", "k_vectors", "alpha")),
+    "pme_dispersion_reciprocal_space": (("forces", "coefficient_gradients", "virial"), ("cell", "alpha")),
+    "gaussian_charge_correction": (("forces", "charge_gradients", "sigma_gradients", "virial"), ()),
+    "dipole_pair_scale_correction": (("forces", "charge_gradients", "dipole_gradients", "polarizability_gradients", "virial"), ("cell",)),
+    **{k: (("forces", "parameter_gradients", "virial"), ()) for k in VALENCE_KINDS},
+}
+CASES = ([(f, m) for f in ("buffered_14_7", "lennard_jones", "ewald_dispersion_real_space", "gaussian_charge_correction") for m in ("matrix", "csr")]
+         + [("dipole_pair_scale_correction", "csr")]
+         + [(f, "none") for f in ("ewald_dispersion_reciprocal_space", "pme_dispersion_reciprocal_space") + VALENCE_KINDS])
+
+
+def _stored(entries, n, fmt, values=None):
+    """(the five list arguments, mask value, `values` per slot | None) of row-sorted entries (i, j, S) as a padded matrix or as CSR."""
+    from tests import sweep_cases as W
+
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=DEV, dtype=torch.int32)  # noqa: E731
+    i, j, S = (np.asarray(e) for e in entries)
+    assert (np.diff(i) >= 0).all()
+    if fmt == "matrix":
+        nm, sh, val = W.padded_matrix((i, j, S), n, values)
+        return (None, None, None, t(nm), t(sh)), n, val
+    ptr = np.zeros(n + 1, np.int32)
+    ptr[1:] = np.cumsum(np.bincount(i, minlength=n))
+    return (t(np.stack([i, j])), t(ptr), t(S), None, None), -1, values
+
+
 def _family_args(family, dtype, fmt):
-    """(public function, op, forward, adjoint, number of differentiable inputs, the op's arguments before the flags, the number of flags)."""
+    """(op, forward, adjoint, number of differentiable inputs, the op's arguments before the flags by name) of one family."""
     import importlib
 
     from nvalchemiops import _eops
@@ -144,41 +180,92 @@ def _family_args(family, dtype, fmt):
     from tests import sweep_cases as W
 
     t = lambda a, dt=None: torch.as_tensor(np.ascontiguousarray(a), device=DEV, dtype=dt)  # noqa: E731
+    lists = ("neighbor_list", "neighbor_ptr", "neighbor_shifts", "neighbor_matrix", "neighbor_matrix_shifts")
+    named = lambda names, values: dict(zip(names, values, strict=True))  # noqa: E731
+    if family in VALENCE_KINDS:
+        from nvalchemiops.interactions import valence as V
+        from tests import test_valence_gpu as TV
+
+        kind = VALENCE_KINDS.index(family)
+        fn = importlib.import_module("nvalchemiops.interactions.valence.functions")
+        c = TV._case(family, "batch")
+        bi = c["batch"].to(DEV)
+        terms = V.ValenceTerms(c["atoms"].to(DEV), c["pos"].shape[0], batch_idx=bi)
+        args = named(("positions", "parameters", "cell", "batch_idx", "atoms", "slot_ptr", "slot_idx", "cubic", "quartic", "pentic", "sextic", "plane"),
+                     (c["pos"].to(DEV, dtype), c["par"].to(DEV, dtype), c["cell"].to(DEV, dtype), bi, terms.atoms, terms.slot_ptr, terms.slot_idx,
+                      *TV._model(family)[0]["consts"], fn.PLANES["wdc"]))
+        return _eops.VALENCE_OPS[kind], functools.partial(fn._forward, kind), functools.partial(fn._adjoint, kind), 2, args
+    if family == "gaussian_charge_correction":
+        ga = importlib.import_module("nvalchemiops.interactions.electrostatics.gaussian")
+        c = LC.gaussian(True)
+        i, j, S = (e.numpy() for e in LC._entries(c["pos"], c["cell"], c["batch_idx"], LC.GC_RC))
+        order = np.argsort(i, kind="stable")
+        stored, mask, _ = _stored((i[order], j[order], S[order]), len(c["pos"]), fmt)
+        args = named(("positions", "charges", "sigma", "cell", "batch_idx") + lists + ("mask_value", "self_energy", "neutralizing_background"),
+                     (t(c["pos"], dtype), t(c["q"], dtype), t(c["sigma"], dtype), t(c["cell"], dtype), t(c["batch_idx"], torch.int32), *stored, mask,
+                      True, True))
+        return _eops.gaussian_charge_correction_op, ga._forward, ga._adjoint, 4, args
+    if family == "dipole_pair_scale_correction":
+        from tests import dipole_scale_cases as SC
+
+        ds = importlib.import_module("nvalchemiops.interactions.electrostatics.dipole_scale")
+        p = LC.dipole_scale(True)
+        stored, mask, _ = _stored(p["entries"], p["n"], fmt)
+        polar = np.where(np.isnan(p["polar"]), 0.0, p["polar"])  # (a NaN polarisability has a NaN gradient slot, which equals nothing)
+        args = named(("positions", "charges", "dipoles", "polarizability", "direct_scales", "mutual_scales", "cell", "batch_idx") + lists
+                     + ("mask_value", "minimum_image", "thole"),
+                     (t(p["pos"], dtype), t(p["q"], dtype), t(p["mu"], dtype), t(polar, dtype), t(p["sd"], torch.float64), t(p["sm"], torch.float64),
+                      t(p["cell"], dtype), t(p["batch_idx"], torch.int32), *stored, mask, False, SC.A_T))
+        return _eops.dipole_pair_scale_correction_op, ds._forward, ds._adjoint, 4, args
     vdw = family in W.VDW_KINDS
     c = LC.vdw(True, family) if vdw else LC.dispersion_ewald(True)
-    i, j, S = c["entries"]
     n = len(c["pos"])
     bi = t(c["batch_idx"], torch.int32)
-    if fmt == "matrix":
-        nm, sh, val = W.padded_matrix(c["entries"], n, c["scales"] if vdw else None)
-        lists, mask, scales = (None, None, None, t(nm, torch.int32), t(sh, torch.int32)), n, val
-    else:
-        ptr = np.zeros(n + 1, np.int32)
-        ptr[1:] = np.cumsum(np.bincount(i, minlength=n))
-        lists, mask, scales = (t(np.stack([i, j]), torch.int32), t(ptr), t(S, torch.int32), None, None), -1, c["scales"] if vdw else None
     if vdw:
+        stored, mask, scales = _stored(c["entries"], n, fmt, c["scales"])
         kind = W.VDW_KINDS.index(family)
         pair = importlib.import_module("nvalchemiops.interactions.vdw.pair")
         sites = IA.ReducedSites(t(c["parent"], torch.int32), t(c["kappa"], dtype), batch_idx=bi)
         m = W.vdw_model(c, family)
-        args = (t(c["pos"], dtype), t(c["radii"], dtype), t(c["eps"], dtype), t(c["cells"], dtype), bi, sites.parent, sites.reduction, sites.child_ptr,
-                sites.child_idx, t(scales, torch.float64), *lists, mask, float(m["cutoff"]), float(m["taper"]), float(m.get("delta", 1.0)),
-                float(m.get("gamma", 1.0)), pair.RADIUS_RULES[m["radius_rule"]], pair.EPSILON_RULES[m["epsilon_rule"]])
-        return (_eops.VDW_OPS[kind], functools.partial(pair._forward, kind), functools.partial(pair._adjoint, kind), 3, args, 4)
+        args = named(("positions", "radii", "epsilons", "cell", "batch_idx", "parent", "reduction", "child_ptr", "child_idx", "pair_scales") + lists
+                     + ("mask_value", "cutoff", "taper", "delta", "gamma", "radius_rule", "epsilon_rule"),
+                     (t(c["pos"], dtype), t(c["radii"], dtype), t(c["eps"], dtype), t(c["cells"], dtype), bi, sites.parent, sites.reduction,
+                      sites.child_ptr, sites.child_idx, t(scales, torch.float64), *stored, mask, float(m["cutoff"]), float(m["taper"]),
+                      float(m.get("delta", 1.0)), float(m.get("gamma", 1.0)), pair.RADIUS_RULES[m["radius_rule"]], pair.EPSILON_RULES[m["epsilon_rule"]]))
+        return _eops.VDW_OPS[kind], functools.partial(pair._forward, kind), functools.partial(pair._adjoint, kind), 3, args
     ew = importlib.import_module("nvalchemiops.interactions.vdw.ewald")
-    head = (t(c["pos"], dtype), t(c["c"], dtype), t(c["cells"], dtype))
+    head = dict(positions=t(c["pos"], dtype), coefficients=t(c["c"], dtype), cell=t(c["cells"], dtype))
     alpha = t(c["alpha"], dtype)
     if family == "ewald_dispersion_real_space":
-        return (_eops.ewald_dispersion_real_space_op, ew._real_forward, ew._real_adjoint, 2,
-                (*head, alpha, bi, *lists, mask, float(c["counted"][0]), -1.0 if c["counted"][1] is None else float(c["counted"][1])), 3)
-    return (_eops.ewald_dispersion_reciprocal_space_op, ew._recip_forward, ew._recip_adjoint, 2, (*head, c["k_vectors"].to(DEV).to(dtype), alpha, bi), 3)
+        stored, mask, _ = _stored(c["entries"], n, fmt)
+        args = dict(head, alpha=alpha, batch_idx=bi, **named(lists, stored), mask_value=mask, counted_cutoff=float(c["counted"][0]),
+                    counted_taper=-1.0 if c["counted"][1] is None else float(c["counted"][1]))
+        return _eops.ewald_dispersion_real_space_op, ew._real_forward, ew._real_adjoint, 2, args
+    if family == "pme_dispersion_reciprocal_space":
+        pme = importlib.import_module("nvalchemiops.interactions.vdw.pme")
+        args = dict(head, alpha=alpha, batch_idx=bi, nx=MESH_DIMS[0], ny=MESH_DIMS[1], nz=MESH_DIMS[2], order=MESH_ORDER)
+        return _eops.pme_dispersion_reciprocal_space_op, pme._recip_forward, pme._recip_adjoint, 2, args
+    args = dict(head, k_vectors=c["k_vectors"].to(DEV).to(dtype), alpha=alpha, batch_idx=bi)
+    return _eops.ewald_dispersion_reciprocal_space_op, ew._recip_forward, ew._recip_adjoint, 2, args
+
+
+def _same(got, ref, exact, what):
+    """Bit for bit, but for the float64 outputs of the mesh half: its float64 spread adds in arrival order, and they get the relative 1e-12
+    tests/test_multipole_call_gpu.py grants float64 mesh outputs."""
+    assert got.shape == ref.shape and got.dtype == ref.dtype, what
+    if exact:
+        assert torch.equal(got, ref), f"{what}: max difference {(got - ref).abs().max().item():.3e}"
+    else:
+        scale, err = ref.abs().max().item(), (got - ref).abs().max().item()
+        assert err <= 1e-12 * scale, f"{what}: max err {err:.3e} > 1e-12 x {scale:.3e}"
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
-@pytest.mark.parametrize("family,fmt", [(f, m) for f in ("buffered_14_7", "lennard_jones", "ewald_dispersion_real_space") for m in ("matrix", "csr")]
-                         + [("ewald_dispersion_reciprocal_space", "none")])
+@pytest.mark.parametrize("family,fmt", CASES)
 def test_vdw_and_dispersion_ewald_ops_match_the_eager_path_and_the_adjoint(family, fmt, dtype):
-    op, forward, adjoint, n_diff, args, n_flags = _family_args(family, dtype, fmt)
+    op, forward, adjoint, n_diff, named = _family_args(family, dtype, fmt)
+    args, n_flags = tuple(named.values()), len(FAMILIES[family][0])
+    exact = not (family == "pme_dispersion_reciprocal_space" and dtype == torch.float64)
     for flags in ((True,) * n_flags, (False,) * n_flags, (False,) * (n_flags - 1) + (True,)):
         eager, direct = forward(*args, *flags), op(*args, *flags)
         assert len(eager) == len(direct) == n_flags + 1
@@ -186,11 +273,41 @@ def test_vdw_and_dispersion_ewald_ops_match_the_eager_path_and_the_adjoint(famil
             if not want:
                 assert e is None and tuple(d.shape) == (0,), f"{family} output {k}: not asked for"
                 continue
-            assert e.dtype == d.dtype == dtype and float(e.abs().max()) > 0 and torch.equal(e, d), f"{family} {fmt} flags {flags}: output {k} differs"
-    leaves = [a.clone().requires_grad_(True) for a in args[:n_diff]]
+            assert e.dtype == dtype and float(e.abs().max()) > 0, f"{family} {fmt} flags {flags}: output {k}"
+            _same(d, e, exact, f"{family} {fmt} flags {flags}: output {k}")
+    leaves = [a.clone().requires_grad_(True) for a in args[:n_diff]]  # (for the Gaussian op the fourth is the cell)
     g = torch.as_tensor(np.random.default_rng(5).normal(size=leaves[0].shape[0]), device=DEV).to(dtype)
     grads = torch.autograd.grad(op(*leaves, *args[n_diff:], *(False,) * n_flags)[0], leaves, grad_outputs=g)
     ref = adjoint(*args, g)
     assert len(grads) == len(ref) == n_diff
     for k, (got, r) in enumerate(zip(grads, ref)):
-        assert r.dtype == torch.float64 and float(r.abs().max()) > 0 and torch.equal(got, r.to(dtype)), f"{family} {fmt}: gradient {k} differs from the adjoint's"
+        assert r.dtype == torch.float64 and float(r.abs().max()) > 0, f"{family} {fmt}: gradient {k}"
+        _same(got, r.reshape(got.shape).to(dtype), exact, f"{family} {fmt}: gradient {k} against the adjoint's")
+
+
+@pytest.mark.parametrize("family,fmt", [(f, m) for f, m in CASES if m != "matrix"])
+def test_refusals_and_silent_nones_of_the_energy_ops(family, fmt):
+    """A gradient of an explicit output raises the second-order text with the op's name; an input without an adjoint that requires a gradient
+    raises its refusal where the family has one (dispersion sums: cell, alpha, k-vectors; scaled dipole pairs: cell).  The van der Waals and
+    valence ops have none: their cell gets no gradient (None), silently, while the other gradients arrive."""
+    op, _, _, n_diff, named = _family_args(family, torch.float64, fmt)
+    outputs, refused = FAMILIES[family]
+    name = f"alchemiops::_{family}"
+    for what in refused:
+        a = dict(named, positions=named["positions"].clone().requires_grad_(True))
+        a[what] = named[what].clone().requires_grad_(True)
+        with pytest.raises(NotImplementedError) as err:
+            op(*a.values(), *[False] * len(outputs))[0].sum().backward()
+        assert f"{name}: gradients w.r.t. {what} are not provided by the " in str(err.value)
+        if family != "dipole_pair_scale_correction":
+            assert "not provided by the dispersion Ewald sum (out of scope); use compute_virial for the strain derivative." in str(err.value)
+    positions = named["positions"].clone().requires_grad_(True)
+    out = op(positions, *list(named.values())[1:], *[True] * len(outputs))
+    for what, o in zip(outputs, out[1:]):
+        with pytest.raises(NotImplementedError) as err:
+            torch.autograd.grad(o.sum(), positions, retain_graph=True)
+        assert f"{name}: derivatives of the '{what}' output are second derivatives of the pair kernels" in str(err.value)
+    if family in VALENCE_KINDS or family in ("buffered_14_7", "lennard_jones"):
+        a = dict(named, positions=named["positions"].clone().requires_grad_(True), cell=named["cell"].clone().requires_grad_(True))
+        op(*a.values(), *[False] * len(outputs))[0].sum().backward()
+        assert a["cell"].grad is None and float(a["positions"].grad.abs().max()) > 0

@@ -661,3 +661,22 @@ def test_multipole_seam_is_pinned():
         assert str(getattr(getattr(torch.ops, namespace), op).default._schema) == schema, name
     for name, sig in want["signatures"].items():
         assert str(inspect.signature(getattr(E, name))) == sig, name
+
+
+def test_energy_ops_seam_is_pinned():
+    """The seam of the energy op pairs outside tests/golden/multipole_seam.json as it stood before all of them were built from one table
+    by one maker (nvalchemiops/_eops.py): the full schema of both ops of each pair, string for string, as recorded in
+    tests/golden/energy_ops_seam.json (its note says at which commit and how)."""
+    import json
+
+    import nvalchemiops  # noqa: F401
+    from nvalchemiops import _eops  # noqa: F401  (registers the ops)
+
+    want = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "energy_ops_seam.json")))
+    pairs = ["gaussian_charge_correction", "pair_scale_correction", "dipole_pair_scale_correction", "buffered_14_7", "lennard_jones",
+             "bond_stretch", "angle_bend", "stretch_bend", "out_of_plane_bend", "torsion", "ewald_dispersion_real_space",
+             "ewald_dispersion_reciprocal_space", "pme_dispersion_reciprocal_space", "rotate_multipoles"]
+    assert sorted(want["schemas"]) == sorted([f"alchemiops::_{p}" for p in pairs] + [f"nvalchemiops::{p}_backward" for p in pairs])
+    for name, schema in want["schemas"].items():
+        namespace, op = name.split("::")
+        assert str(getattr(getattr(torch.ops, namespace), op).default._schema) == schema, name
