@@ -1385,6 +1385,13 @@ int mi_pme_dispersion_gather(const void* positions, const void* coefficients, co
  *                            |(u - w) x (v - w)|^2 (MI_VALENCE_PLANE_ALLINGER); a term with V == 0 has exactly zero gradients
  *   MI_VALENCE_TORSION       A = 4 (a, b, c, d)  {V_1..V_F, gamma_1..gamma_F}, n_params = 2 F, F in 1..6
  *                            sum_n V_n (1 + cos(n phi - gamma_n)), phi the IUPAC dihedral (trans = pi)
+ *   MI_VALENCE_STRETCH_TORSION  A = 4 (a, b, c, d)  {k_11 k_12 k_13 k_21 .. k_33, r0_1 r0_2 r0_3, gamma_1 gamma_2 gamma_3}, n_params = 15
+ *                            sum_{m=1..3} (r_m - r0_m) sum_{n=1..3} k_mn (1 + cos(n phi - gamma_n)),  r_1 = |b - a|, r_2 = |c - b|, r_3 = |d - c|
+ *   MI_VALENCE_ANGLE_TORSION    A = 4 (a, b, c, d)  {k_11 .. k_23, theta0_1 theta0_2, gamma_1 gamma_2 gamma_3}, n_params = 11
+ *                            sum_{m=1,2} (theta_m - theta0_m) sum_{n=1..3} k_mn (1 + cos(n phi - gamma_n)),  theta_1 = angle(a, b, c), theta_2 = angle(b, c, d)
+ *   MI_VALENCE_PI_TORSION       A = 6 (a, b, c, d, e, f)  {k}: c - d is the bond, a and b are bonded to c, e and f to d
+ *                            k (1 - cos 2 phi), phi the dihedral of (c + p, c, d, d + q), p = (r_a - r_d) x (r_b - r_d), q = (r_e - r_c) x (r_f - r_c);
+ *                            its difference vectors are r_a - r_d, r_b - r_d, r_e - r_c, r_f - r_c and r_d - r_c
  * Difference vectors are minimum images when cell [n_systems][3][3] is given (rows are lattice vectors; batch_idx [n_atoms] of the term's first
  * atom selects the row, NULL: system 0).  All arithmetic is float64, outputs are rounded once, no atomics: bit-reproducible.  A term that names
  * an atom outside [0, n_atoms) contributes exact zeros everywhere.  slot_ptr [n_atoms + 1] / slot_idx [n_slots]: a CSR over atoms of the slots
@@ -1403,6 +1410,9 @@ int mi_pme_dispersion_gather(const void* positions, const void* coefficients, co
 #define MI_VALENCE_STRETCH_BEND 2
 #define MI_VALENCE_OUT_OF_PLANE 3
 #define MI_VALENCE_TORSION 4
+#define MI_VALENCE_STRETCH_TORSION 5
+#define MI_VALENCE_ANGLE_TORSION 6
+#define MI_VALENCE_PI_TORSION 7
 #define MI_VALENCE_PLANE_WDC 0
 #define MI_VALENCE_PLANE_ALLINGER 1
 #define MI_VALENCE_FORCES 1
@@ -1416,6 +1426,18 @@ int mi_valence(int kind, const void* positions, const int32_t* atoms, const void
                const int32_t* batch_idx, const double* weights, const int32_t* slot_ptr, const int32_t* slot_idx, long long n_slots, int n_atoms,
                int n_terms, int n_systems, int dtype, double cubic, double quartic, double pentic, double sextic, int plane, int flags,
                void* energies, void* forces, double* parameter_grads, double* virial_partial, void* scratch, size_t scratch_bytes, void* stream);
+/* Torsion-torsion (CMAP) terms over atoms [n_terms][5] = (a, b, c, d, e): E_t = F_m(s phi_1, s phi_2) with phi_1 = dihedral(a, b, c, d),
+ * phi_2 = dihedral(b, c, d, e), m = map_index[t] and s = signs[t] = +-1 (float64).  F_m is the bicubic patch (tensor-product cubic Hermite,
+ * the Numerical Recipes bcuint construction) of map m on a uniform periodic grid over [-pi, pi)^2: nodes [n_maps][n1][n2][4] float64 holds
+ * one 32-byte record (f, df/dx, df/dy, d2f/dxdy) per node, node (i, j) at (-pi + 2 pi i / n1, -pi + 2 pi j / n2).  The cell index is reduced
+ * modulo n, so phi = pi and every edge land in a valid cell.  Everything else is mi_valence's contract with A = 5 and no parameters: minimum
+ * images, weights, slots, outputs, the flags MI_VALENCE_FORCES / _VIRIAL / _TERM_MAJOR, exact zeros for a term that names an atom outside
+ * [0, n_atoms) or a map outside [0, n_maps).  The four corner records of a term's cell are read in place, through the cache. */
+size_t mi_torsion_torsion_scratch_bytes(int n_terms, int flags);
+int mi_torsion_torsion(const void* positions, const int32_t* atoms, const double* nodes, const int32_t* map_index, const double* signs, int n_maps,
+                       int n1, int n2, const void* cell, const int32_t* batch_idx, const double* weights, const int32_t* slot_ptr,
+                       const int32_t* slot_idx, long long n_slots, int n_atoms, int n_terms, int n_systems, int dtype, int flags, void* energies,
+                       void* forces, double* virial_partial, void* scratch, size_t scratch_bytes, void* stream);
 
 /* ---- multi-GPU: the one collective of the path (csrc/comm.cpp) ------------------------------------------------------------
  * The reference has no multi-GPU code; the path shards at SYSTEM granularity -- no pair crosses systems

@@ -54,7 +54,9 @@ SOURCES = {
     # dispersion lattice sum on a mesh (mi_pme_dispersion_*): the r^-6 k-space operator (fp64 exp / erfc once per mesh point) and the
     # 8-lanes-per-atom gather with fp64 stencils
     "dispersion_pme.hip": [],
-    "valence.hip": [],  # valence terms (mi_valence): bonds, angles, stretch-bend, out-of-plane bends and torsions, one thread per term, all fp64
+    # valence terms (mi_valence, mi_torsion_torsion): bonds, angles, stretch-bend, out-of-plane bends, torsions and the coupled torsion terms,
+    # one thread per term, all fp64
+    "valence.hip": [],
     "multipole.hip": [],  # spherical harmonics / Gaussian multipole basis (nvalchemiops.math): fp64 elementwise kernels
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]

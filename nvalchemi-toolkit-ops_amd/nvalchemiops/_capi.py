@@ -281,6 +281,10 @@ def lib() -> ctypes.CDLL:
         L.mi_valence_blocks.argtypes = []
         L.mi_valence_arity.restype = i
         L.mi_valence_arity.argtypes = [i]
+        L.mi_torsion_torsion.restype = i
+        L.mi_torsion_torsion.argtypes = [vp] * 5 + [i] * 3 + [vp] * 5 + [ll] + [i] * 5 + [vp] * 4 + [sz, vp]
+        L.mi_torsion_torsion_scratch_bytes.restype = sz
+        L.mi_torsion_torsion_scratch_bytes.argtypes = [i, i]
         # dispersion Ewald sum (nvalchemiops/interactions/vdw/ewald.py)
         L.mi_ewald_dispersion_real.restype = i
         L.mi_ewald_dispersion_real.argtypes = [vp] * 6 + [i, i, i, dbl, dbl, vp, vp, vp, i, i, i] + [vp] * 5 + [sz, vp]

@@ -1516,7 +1516,8 @@ pme_recip_virial_op.register_autograd(_virial_no_adjoint("nvalchemiops::pme_reci
 #     and k-vectors are refused.
 #   Gaussian charges: w.r.t. positions, charges, sigma and the cell (one gradient per system, None without a cell).
 #   van der Waals pairs: w.r.t. positions, radii and epsilons; the site tables, the pair scales and the cell have no gradient.
-#   valence terms: w.r.t. positions and parameters; the term tables and the cell have no gradient.
+#   valence terms: w.r.t. positions and parameters; the term tables and the cell have no gradient.  Torsion-torsion terms: w.r.t. positions
+#     only (one differentiable input: its backward op returns a tensor, not a tuple); the maps have no gradient.
 #   dispersion Ewald sums: w.r.t. positions and coefficients; cell, alpha and k-vectors are refused.
 _DP_NO_GRAD = ("{op}: gradients w.r.t. {what} are not provided by the point-dipole Ewald term (out of scope); use compute_virial for the "
                "strain derivative.")
@@ -1554,7 +1555,8 @@ _VALENCE = dict(module=_VL, forward="_forward", adjoint="_adjoint", diff="Tensor
                 middle=("Tensor? cell, Tensor? batch_idx, Tensor atoms, Tensor slot_ptr, Tensor slot_idx, float cubic, float quartic, float pentic, "
                         "float sextic, SymInt plane"),
                 outputs=(_F, ("parameter_gradients", "parameters")), systems="optional cell")
-_VALENCE_KINDS = ("bond_stretch", "angle_bend", "stretch_bend", "out_of_plane_bend", "torsion")  # by MI_VALENCE_BOND .. MI_VALENCE_TORSION
+_VALENCE_KINDS = ("bond_stretch", "angle_bend", "stretch_bend", "out_of_plane_bend", "torsion", "stretch_torsion", "angle_torsion",
+                  "pi_torsion")  # by MI_VALENCE_BOND .. MI_VALENCE_PI_TORSION
 _DE = dict(module=_VW + "ewald", diff="Tensor positions, Tensor coefficients", outputs=(_F, ("coefficient_gradients", "coefficients")),
            refusal=_DE_NO_GRAD)
 _REAL, _RECIP = dict(forward="_real_forward", adjoint="_real_adjoint"), dict(forward="_recip_forward", adjoint="_recip_adjoint")
@@ -1598,6 +1600,11 @@ _ENERGY_OPS = {
     "buffered_14_7": dict(_VDW, bound=(0,)),  # MI_VDW_BUFFERED_14_7
     "lennard_jones": dict(_VDW, bound=(1,)),  # MI_VDW_LENNARD_JONES
     **{name: dict(_VALENCE, bound=(kind,)) for kind, name in enumerate(_VALENCE_KINDS)},
+    "torsion_torsion": dict(module="nvalchemiops.interactions.valence.tortor", forward="_forward", adjoint="_adjoint",
+                            diff="Tensor positions",
+                            middle=("Tensor? cell, Tensor? batch_idx, Tensor atoms, Tensor slot_ptr, Tensor slot_idx, Tensor nodes, Tensor map_index, "
+                                    "Tensor signs"),
+                            outputs=(_F,), systems="optional cell"),
     "ewald_dispersion_real_space": dict(_DE, **_REAL, middle=f"Tensor cell, Tensor alpha, {_LISTS}, float counted_cutoff, float counted_taper",
                                         systems="batch", refused=("cell", "alpha")),
     "ewald_dispersion_reciprocal_space": dict(_DE, **_RECIP, middle=_KSUM, systems="cell rows", refused=("cell", "k_vectors", "alpha")),
@@ -1642,13 +1649,16 @@ def _energy_ops(name, module, forward, adjoint, diff, middle, outputs, systems, 
 
     def bwd(*args):
         grads = run(adjoint, args, (args[n_in],))
+        if n_diff == 1:
+            return grads
         return tuple(args[0].new_empty((0,), dtype=torch.float64) if g is None else g for g in grads) if optional else grads
 
     def bwd_fake(*args):
         """A gradient has the shape of its input; a `per_system` one is [nsys, 3, 3]; that of an input that is None is [0]."""
         shapes = [(0,) if a is None else (nsys_of(args[i_cell], args[i_batch]), 3, 3) if d in per_system else a.shape
                   for d, a in zip(names, args[:n_diff])]
-        return tuple(args[0].new_empty(s, dtype=torch.float64) for s in shapes)
+        out = tuple(args[0].new_empty(s, dtype=torch.float64) for s in shapes)
+        return out[0] if n_diff == 1 else out
 
     def refuse_second_order(ctx, *grads):
         raise NotImplementedError(_SECOND_ORDER.format(op=bwd_name, what="gradient"))
@@ -1674,7 +1684,7 @@ def _energy_ops(name, module, forward, adjoint, diff, middle, outputs, systems, 
         if g_e is None:
             return (None,) * len(need)
         saved = ctx.saved_tensors
-        grads = list(bwd_op(*saved, *ctx.extra, g_e))
+        grads = [bwd_op(*saved, *ctx.extra, g_e)] if n_diff == 1 else list(bwd_op(*saved, *ctx.extra, g_e))
         for i in reshaped:
             if need[i]:
                 grads[i] = grads[i].reshape(saved[i].shape)
@@ -1705,6 +1715,7 @@ buffered_14_7_op, buffered_14_7_bwd_op = _EO["buffered_14_7"]
 lennard_jones_op, lennard_jones_bwd_op = _EO["lennard_jones"]
 VDW_OPS = (buffered_14_7_op, lennard_jones_op)  # by MI_VDW_BUFFERED_14_7 / MI_VDW_LENNARD_JONES
 VALENCE_OPS, VALENCE_BWD_OPS = zip(*(_EO[name] for name in _VALENCE_KINDS))
+torsion_torsion_op, torsion_torsion_bwd_op = _EO["torsion_torsion"]
 ewald_dispersion_real_space_op, ewald_dispersion_real_bwd_op = _EO["ewald_dispersion_real_space"]
 ewald_dispersion_reciprocal_space_op, ewald_dispersion_recip_bwd_op = _EO["ewald_dispersion_reciprocal_space"]
 pme_dispersion_reciprocal_space_op, pme_dispersion_recip_bwd_op = _EO["pme_dispersion_reciprocal_space"]
@@ -1787,7 +1798,7 @@ rotate_multipoles_op.register_fake(_rotate_fwd_fake)
 rotate_multipoles_op.register_autograd(_rotate_backward, setup_context=_rotate_setup)
 
 
-__all__ = ["pme_dispersion_reciprocal_space_op", "pme_dispersion_recip_bwd_op", "ewald_dispersion_real_space_op", "ewald_dispersion_real_bwd_op",
+__all__ = ["torsion_torsion_op", "torsion_torsion_bwd_op", "pme_dispersion_reciprocal_space_op", "pme_dispersion_recip_bwd_op", "ewald_dispersion_real_space_op", "ewald_dispersion_real_bwd_op",
            "ewald_dispersion_reciprocal_space_op", "ewald_dispersion_recip_bwd_op", "buffered_14_7_op", "buffered_14_7_bwd_op", "lennard_jones_op",
            "lennard_jones_bwd_op", "VDW_OPS", "pair_scale_correction_op", "pair_scale_bwd_op", "dipole_pair_scale_correction_op",
            "dipole_pair_scale_bwd_op", "rotate_multipoles_op", "rotate_multipoles_bwd_op", "coulomb_dipole_correction_op", "coulomb_dipole_bwd_op",

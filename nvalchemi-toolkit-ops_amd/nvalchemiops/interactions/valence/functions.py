@@ -1,7 +1,8 @@
-"""The valence (bonded) terms of a force field: bond stretch, angle bend, stretch-bend, out-of-plane bend and Fourier torsion.
+"""The valence (bonded) terms of a force field: bond stretch, angle bend, stretch-bend, out-of-plane bend and Fourier torsion, and the
+coupled torsion terms stretch-torsion, angle-torsion and pi-torsion (torsion-torsion: tortor.py).
 
 The electrostatics and vdw packages cover every non-bonded term of an AMOEBA-class model; this module is the bonded energy.  The definitions
-are Tinker's (angles in radians, no 1/2 in front of a force constant).  All five functions run on one HIP kernel family (csrc/valence.hip,
+are Tinker's (angles in radians, no 1/2 in front of a force constant).  All functions run on one HIP kernel family (csrc/valence.hip,
 `mi_valence`): a term pass with one thread per term writes the term energy, a gradient record, the parameter gradients and the virial words;
 a gather pass with one thread per atom sums the atom's slots in a fixed order.  All arithmetic is float64 whatever the positions dtype, there
 are no atomics, and forward and adjoint are the same launch without and with per-atom weights, so every output is bit-reproducible.  The
@@ -17,12 +18,12 @@ from nvalchemiops import _capi as C
 from nvalchemiops.interactions.electrostatics import _pairs as P
 from nvalchemiops.interactions.valence.terms import ValenceTerms
 
-BOND, ANGLE, STRETCH_BEND, OUT_OF_PLANE, TORSION = 0, 1, 2, 3, 4
+BOND, ANGLE, STRETCH_BEND, OUT_OF_PLANE, TORSION, STRETCH_TORSION, ANGLE_TORSION, PI_TORSION = range(8)
 PLANES = {"wdc": 0, "allinger": 1}
 VALENCE_FORCES, VALENCE_PARAMETER_GRAD, VALENCE_VIRIAL, VALENCE_TERM_MAJOR = 1, 2, 4, 8
-_NAMES = ("bond_stretch", "angle_bend", "stretch_bend", "out_of_plane_bend", "torsion")
-_ARITY = (2, 3, 3, 4, 4)
-_PARAMS = (2, 2, 5, 1, None)  # columns of `parameters`; a torsion takes 2 F, F in 1..6
+_NAMES = ("bond_stretch", "angle_bend", "stretch_bend", "out_of_plane_bend", "torsion", "stretch_torsion", "angle_torsion", "pi_torsion")
+_ARITY = (2, 3, 3, 4, 4, 4, 4, 6)
+_PARAMS = (2, 2, 5, 1, None, 15, 11, 1)  # columns of `parameters`; a torsion takes 2 F, F in 1..6
 
 _COMMON_DOC = """`terms` is a `ValenceTerms` built once from the atom tuples; `parameters` [T, P] holds one row per term, float32 or float64, converted to
     the positions dtype.  With `cell` ([3, 3], or [num_systems, 3, 3] with `batch_idx`; rows are lattice vectors) every difference vector is
@@ -41,8 +42,8 @@ _COMMON_DOC = """`terms` is a `ValenceTerms` built once from the atom tuples; `p
 
 
 def _check(kind, positions, terms, parameters, cell, batch_idx, compute_virial):
-    """Every argument error, before anything is launched.  Returns the number of systems."""
-    name = _NAMES[kind]
+    """Every argument error, before anything is launched.  Returns the number of systems.  `kind` None: a table without parameters, whose
+    type the caller has checked (torsion_torsion)."""
     if positions.dim() != 2 or positions.shape[1] != 3:
         raise ValueError(f"positions must have shape [num_atoms, 3], got {tuple(positions.shape)}")
     C.dtype_code(positions.dtype)
@@ -51,6 +52,23 @@ def _check(kind, positions, terms, parameters, cell, batch_idx, compute_virial):
         raise TypeError(f"terms must be a ValenceTerms, got {type(terms)}")
     if terms.num_atoms != n:
         raise ValueError(f"terms describes {terms.num_atoms} atoms but positions has {n}")
+    if kind is not None:
+        _check_parameters(kind, terms, parameters)
+    C.check_per_atom(n, batch_idx=batch_idx)
+    if cell is None:
+        if compute_virial:
+            raise ValueError("compute_virial needs a cell")
+        return 1
+    if cell.dim() not in (2, 3) or tuple(cell.shape[-2:]) != (3, 3):
+        raise ValueError(f"cell must have shape [3, 3] or [num_systems, 3, 3], got {tuple(cell.shape)}")
+    n_cells = cell.shape[0] if cell.dim() == 3 else 1
+    if batch_idx is None and n_cells != 1:
+        raise ValueError(f"cell holds {n_cells} systems: batch_idx is required")
+    return n_cells if batch_idx is not None else 1
+
+
+def _check_parameters(kind, terms, parameters):
+    name = _NAMES[kind]
     if terms.arity != _ARITY[kind]:
         raise ValueError(f"{name} takes terms of {_ARITY[kind]} atoms, got a table of {terms.arity}")
     if not isinstance(parameters, torch.Tensor) or parameters.dim() != 2 or parameters.shape[0] != terms.num_terms:
@@ -63,17 +81,6 @@ def _check(kind, positions, terms, parameters, cell, batch_idx, compute_virial):
             raise ValueError(f"torsion parameters hold V_1..V_F and gamma_1..gamma_F: P = 2 F with F in 1..6, got P = {p}")
     elif p != _PARAMS[kind]:
         raise ValueError(f"{name} takes {_PARAMS[kind]} parameters per term, got P = {p}")
-    C.check_per_atom(n, batch_idx=batch_idx)
-    if cell is None:
-        if compute_virial:
-            raise ValueError("compute_virial needs a cell")
-        return 1
-    if cell.dim() not in (2, 3) or tuple(cell.shape[-2:]) != (3, 3):
-        raise ValueError(f"cell must have shape [3, 3] or [num_systems, 3, 3], got {tuple(cell.shape)}")
-    n_cells = cell.shape[0] if cell.dim() == 3 else 1
-    if batch_idx is None and n_cells != 1:
-        raise ValueError(f"cell holds {n_cells} systems: batch_idx is required")
-    return n_cells if batch_idx is not None else 1
 
 
 def _launch(kind, positions, parameters, cell, batch_idx, atoms, slot_ptr, slot_idx, consts, plane, flags, weights=None, energies=True):
@@ -213,8 +220,56 @@ def torsion(positions: torch.Tensor, terms: ValenceTerms, parameters: torch.Tens
     return _call(TORSION, positions, terms, parameters, cell, (0.0,) * 4, 0, batch_idx, compute_forces, compute_parameter_gradients, compute_virial)
 
 
-for _fn in (bond_stretch, angle_bend, stretch_bend, out_of_plane_bend, torsion):
+@C.traceable
+def stretch_torsion(positions: torch.Tensor, terms: ValenceTerms, parameters: torch.Tensor, cell: torch.Tensor | None = None, *,
+                    batch_idx: torch.Tensor | None = None, compute_forces: bool = False, compute_parameter_gradients: bool = False,
+                    compute_virial: bool = False):
+    """Stretch-torsion coupling over the terms (a, b, c, d), `parameters` [T, 15] = (k_11 k_12 k_13 k_21 .. k_33, r0_1 r0_2 r0_3,
+    gamma_1 gamma_2 gamma_3), radians:
+
+        E_t = sum_{m = 1..3} (r_m - r0_m) sum_{n = 1..3} k_mn (1 + cos(n phi - gamma_n))
+
+    with r_1 = |r_b - r_a|, r_2 = |r_c - r_b|, r_3 = |r_d - r_c| and phi the dihedral of `torsion`.  AMOEBA's term has gamma = (0, pi, 0); a
+    force field that couples the central bond only leaves the rows m = 1 and 3 zero.
+
+    COMMON"""
+    return _call(STRETCH_TORSION, positions, terms, parameters, cell, (0.0,) * 4, 0, batch_idx, compute_forces, compute_parameter_gradients,
+                 compute_virial)
+
+
+@C.traceable
+def angle_torsion(positions: torch.Tensor, terms: ValenceTerms, parameters: torch.Tensor, cell: torch.Tensor | None = None, *,
+                  batch_idx: torch.Tensor | None = None, compute_forces: bool = False, compute_parameter_gradients: bool = False,
+                  compute_virial: bool = False):
+    """Angle-torsion coupling over the terms (a, b, c, d), `parameters` [T, 11] = (k_11 k_12 k_13 k_21 k_22 k_23, theta0_1 theta0_2,
+    gamma_1 gamma_2 gamma_3), radians:
+
+        E_t = sum_{m = 1, 2} (theta_m - theta0_m) sum_{n = 1..3} k_mn (1 + cos(n phi - gamma_n))
+
+    with theta_1 = angle(a, b, c), theta_2 = angle(b, c, d) and phi the dihedral of `torsion`.  A straight angle has no defined gradient.
+
+    COMMON"""
+    return _call(ANGLE_TORSION, positions, terms, parameters, cell, (0.0,) * 4, 0, batch_idx, compute_forces, compute_parameter_gradients,
+                 compute_virial)
+
+
+@C.traceable
+def pi_torsion(positions: torch.Tensor, terms: ValenceTerms, parameters: torch.Tensor, cell: torch.Tensor | None = None, *,
+               batch_idx: torch.Tensor | None = None, compute_forces: bool = False, compute_parameter_gradients: bool = False,
+               compute_virial: bool = False):
+    """Pi-orbital torsions about the bond c-d of two trigonal centres over the terms (a, b, c, d, e, f) of a `WideValenceTerms`, a and b
+    bonded to c, e and f bonded to d, `parameters` [T, 1] = (k):
+
+        E_t = k (1 - cos 2 phi),    phi = dihedral of the points (c + p, c, d, d + q),  p = (r_a - r_d) x (r_b - r_d),  q = (r_e - r_c) x (r_f - r_c)
+
+    The minimum-imaged vectors are r_a - r_d, r_b - r_d, r_e - r_c, r_f - r_c and r_d - r_c, and the virial is the sum over these five.
+
+    COMMON"""
+    return _call(PI_TORSION, positions, terms, parameters, cell, (0.0,) * 4, 0, batch_idx, compute_forces, compute_parameter_gradients, compute_virial)
+
+
+for _fn in (bond_stretch, angle_bend, stretch_bend, out_of_plane_bend, torsion, stretch_torsion, angle_torsion, pi_torsion):
     _fn.__doc__ = _fn.__doc__.replace("COMMON", _COMMON_DOC)
 del _fn
 
-__all__ = ["bond_stretch", "angle_bend", "stretch_bend", "out_of_plane_bend", "torsion"]
+__all__ = ["bond_stretch", "angle_bend", "stretch_bend", "out_of_plane_bend", "torsion", "stretch_torsion", "angle_torsion", "pi_torsion"]
