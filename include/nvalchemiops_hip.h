@@ -481,6 +481,46 @@ int mi_gaussian_charges(const void* positions, const void* charges, const void* 
                         void* forces, double* charge_grads, double* sigma_grads, double* system_partial, void* scratch, size_t scratch_bytes,
                         void* stream);
 
+/* Generalized Born implicit solvent (csrc/born.hip; driver: nvalchemiops/interactions/electrostatics/born.py): Hawkins-Cramer-Truhlar
+ * descreening, Onufriev-Bashford-Case Born radii, the Still pair function and an ACE-type surface term over the stored entries (i, j, S) of a
+ * FULL (symmetric) list -- padded matrix (neighbor_ptr == NULL; entries equal to mask_value or outside [0, n_atoms) are padding) or CSR; the
+ * list is the sum, with a cell (r = r_j - r_i + S . cell) or without one.  rho_i = R_i - offset, S_j = screening_j rho_j:
+ *     I(r; rho, S) = 0 if r + S <= rho, else with L = max(rho, |r - S|), U = r + S
+ *                    1/2 [1/L - 1/U + (r/4)(1/U^2 - 1/L^2) + ln(L/U)/(2r) + (S^2/(4r))(1/L^2 - 1/U^2)]  (+ 1/rho - 1/L if rho < S - r)
+ *     Psi_i = rho_i sum_row I(r; rho_i, S_j),   1/B_i = 1/rho_i - tanh(a Psi - b Psi^2 + c Psi^3) / R_i
+ *     energies[i] = C [q_i^2/B_i + sum_row q_i q_j / f] + surf (R_i + probe)^2 (R_i/B_i)^6,   f^2 = r^2 + B_i B_j exp(-r^2/(4 B_i B_j))
+ * params [MI_BORN_PARAMS] host doubles {offset, a, b, c, C = -1/2 k (1/eps_in - 1/eps_out), surf = 4 pi gamma_sa (0: no surface term), probe}.
+ * Entries with r <= 1e-8 are skipped.  Pair vector and r^2 in the positions dtype, everything else fp64.  The row owner writes every output:
+ * no atomics, fixed summation order, bit-reproducible.  A half list is not detected.  rho_i <= 0 is the caller's error (not checked here).
+ * The three calls share one scratch of mi_born_scratch_bytes(n_atoms, dtype) bytes and must see the same list, params and flags:
+ *   mi_born_radii   packs the per-atom records and writes born_radii [n_atoms] float64 (with MI_GB_FORCES or MI_GB_VIRIAL also dB/dPsi
+ *                   to the scratch);
+ *   mi_born_energy  energies [n_atoms] float64 (may be NULL) and, with MI_GB_CHARGE_GRAD, charge_grads [n_atoms] float64 = dL/dq_i at fixed
+ *                   positions; with MI_GB_FORCES or MI_GB_VIRIAL the direct force, the virial partial and dL/dB_i go to the scratch.  weights
+ *                   [n_atoms] float64 or NULL (all ones): a listed pair carries (g_i + g_j) / 2, self and surface terms g_i, so the outputs are
+ *                   derivatives of L = sum_i g_i energies[i];
+ *   mi_born_chain   (only with MI_GB_FORCES or MI_GB_VIRIAL) adds the path through the Born radii: forces [n_atoms][3] (positions dtype)
+ *                   = -dL/dr_i, and with MI_GB_VIRIAL system_partial [n_systems][mi_born_blocks()][mi_born_row_words()] float64 = block
+ *                   partials of -dL/d(strain) {xx, yy, zz, xy, xz, yz}; the caller sums the block dimension.  The virial needs a cell.
+ * idx_j may be NULL only for a matrix with max_neighbors == 0.  cell NULL: unit_shifts must be NULL too.  n_systems > 1 needs batch_idx. */
+#define MI_GB_FORCES 1
+#define MI_GB_CHARGE_GRAD 2
+#define MI_GB_VIRIAL 8
+#define MI_BORN_PARAMS 7
+size_t mi_born_scratch_bytes(int n_atoms, int dtype);
+int mi_born_blocks(void);
+int mi_born_row_words(void);
+int mi_born_radii(const void* positions, const void* charges, const void* radii, const void* screening, const void* cell /*[n_systems,3,3] or NULL*/,
+                  const int32_t* batch_idx, int n_atoms, int n_systems, int dtype, const int32_t* idx_j, const int32_t* unit_shifts,
+                  const int32_t* neighbor_ptr, int max_neighbors, int mask_value, const double* params, int flags, double* born_radii,
+                  void* scratch, size_t scratch_bytes, void* stream);
+int mi_born_energy(const void* cell, const int32_t* batch_idx, const double* weights, int n_atoms, int n_systems, int dtype, const int32_t* idx_j,
+                   const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors, int mask_value, const double* params, int flags,
+                   const double* born_radii, double* energies, double* charge_grads, void* scratch, size_t scratch_bytes, void* stream);
+int mi_born_chain(const void* cell, const int32_t* batch_idx, int n_atoms, int n_systems, int dtype, const int32_t* idx_j,
+                  const int32_t* unit_shifts, const int32_t* neighbor_ptr, int max_neighbors, int mask_value, const double* params, int flags,
+                  void* forces, double* system_partial, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Point-dipole Ewald sum (csrc/dipole.hip; driver: nvalchemiops/interactions/electrostatics/dipole.py): what point dipoles mu_i (fixed in the
  * laboratory frame) add to the periodic energy of point charges q_i -- the charge-charge part is NOT included, the result is added to an Ewald /
  * PME energy.  Gaussian units, tin-foil boundary.  All arithmetic is fp64; only the pair vector and r^2 are formed in the positions dtype.  No

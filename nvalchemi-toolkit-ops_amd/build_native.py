@@ -32,6 +32,8 @@ SOURCES = {
     "d3.hip": ["-fno-hip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize"] + os.environ.get("MI_D3_EXTRA_FLAGS", "").split(),
     "ewald.hip": os.environ.get("MI_EWALD_EXTRA_FLAGS", "").split(),
     "gaussian.hip": [],  # Gaussian-smeared charge correction (mi_gaussian_charges): fp64 pair math with libm erfc
+    # generalized Born implicit solvent (mi_born_*): fp64 pair math with libm log / exp / tanh, reciprocals and rsqrt by Newton steps
+    "born.hip": [],
     "dipole.hip": [],  # point-dipole Ewald sum (mi_ewald_dipole_*): fp64 pair math with libm erfc / exp, fp64 sincos phases
     "quadrupole.hip": [],  # point-quadrupole Ewald sum (mi_ewald_quadrupole_*): the arithmetic model of dipole.hip, B_n continued to B5
     "pair_scale.hip": [],  # scaled bonded pairs of point multipoles (mi_pair_scale): 8 lanes per row, the arithmetic model of quadrupole.hip

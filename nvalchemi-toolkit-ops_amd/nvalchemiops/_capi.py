@@ -150,6 +150,17 @@ def lib() -> ctypes.CDLL:
         for name in ("mi_gaussian_charges_blocks", "mi_gaussian_charges_row_words"):
             getattr(L, name).restype = i
             getattr(L, name).argtypes = []
+        # generalized Born implicit solvent (nvalchemiops/interactions/electrostatics/born.py)
+        lists = [i, i, i, vp, vp, vp, i, i, vp, i]  # n_atoms, n_systems, dtype, idx_j, unit_shifts, neighbor_ptr, max_neighbors, mask_value, params, flags
+        for name, args in (("mi_born_radii", [vp] * 6 + lists + [vp, vp, sz, vp]), ("mi_born_energy", [vp] * 3 + lists + [vp] * 4 + [sz, vp]),
+                           ("mi_born_chain", [vp] * 2 + lists + [vp] * 3 + [sz, vp])):
+            getattr(L, name).restype = i
+            getattr(L, name).argtypes = args
+        L.mi_born_scratch_bytes.restype = sz
+        L.mi_born_scratch_bytes.argtypes = [i, i]
+        for name in ("mi_born_blocks", "mi_born_row_words"):
+            getattr(L, name).restype = i
+            getattr(L, name).argtypes = []
         # point-dipole Ewald sum (nvalchemiops/interactions/electrostatics/dipole.py)
         L.mi_ewald_dipole_real.restype = i
         L.mi_ewald_dipole_real.argtypes = [vp] * 7 + [i, i, i, vp, vp, vp, i, i, i] + [vp] * 6 + [sz, vp]

@@ -1529,6 +1529,8 @@ _CL_NO_GRAD = ("{op}: gradients w.r.t. cell are not provided by the bare multipo
                "derivative.")
 _DE_NO_GRAD = ("{op}: gradients w.r.t. {what} are not provided by the dispersion Ewald sum (out of scope); use compute_virial for the strain "
                "derivative.")
+_GB_NO_GRAD = ("{op}: gradients w.r.t. {what} are not provided by the generalized Born term (out of scope: dE/dR, dE/dscreening and a cell "
+               "gradient); use compute_virial for the strain derivative.")
 _SCALARS = {"SymInt": int, "int": int, "float": float, "bool": bool}  # schema type of a plain scalar -> the conversion `ctx.extra` and the launch functions get
 _SYSTEMS = {  # the fake's number of systems, from (cell, batch_idx)
     "batch": lambda cell, batch_idx: cell.reshape(-1, 3, 3).shape[0] if batch_idx is not None else 1,
@@ -1569,6 +1571,12 @@ _ENERGY_OPS = {
                                        diff="Tensor positions, Tensor charges, Tensor sigma, Tensor? cell",
                                        middle=f"{_LISTS}, bool self_energy, bool neutralizing_background",
                                        outputs=(_F, _CG, ("sigma_gradients", "sigma")), systems="optional cell", per_system=("cell",)),
+    "generalized_born": dict(module=_EL + "born", forward="_forward", adjoint="_adjoint", diff="Tensor positions, Tensor charges",
+                             middle=(f"Tensor radii, Tensor screening, Tensor? cell, {_LISTS}, float solute_dielectric, float solvent_dielectric, "
+                                     "float coulomb_constant, float offset, float obc_alpha, float obc_beta, float obc_gamma, float surface_tension, "
+                                     "float probe_radius"),
+                             outputs=(_F, _CG, ("born_radii", "radii")), systems="optional cell", refused=("radii", "screening", "cell"),
+                             refusal=_GB_NO_GRAD),
     "ewald_dipole_real_space": dict(_REAL, module=_EL + "dipole", diff=_DP, middle=f"Tensor cell, Tensor alpha, {_LISTS}", outputs=_DP_OUT,
                                     systems="batch", refused=("cell", "alpha"), refusal=_DP_NO_GRAD),
     "ewald_dipole_reciprocal_space": dict(_RECIP, module=_EL + "dipole", diff=_DP, middle=_KSUM, outputs=_DP_OUT, systems="cell rows",
@@ -1700,6 +1708,7 @@ def _energy_ops(name, module, forward, adjoint, diff, middle, outputs, systems, 
 
 _EO = {name: _energy_ops(name, **row) for name, row in _ENERGY_OPS.items()}
 gaussian_charge_correction_op, gaussian_bwd_op = _EO["gaussian_charge_correction"]
+generalized_born_op, generalized_born_bwd_op = _EO["generalized_born"]
 ewald_dipole_real_space_op, ewald_dipole_real_bwd_op = _EO["ewald_dipole_real_space"]
 ewald_dipole_reciprocal_space_op, ewald_dipole_recip_bwd_op = _EO["ewald_dipole_reciprocal_space"]
 pme_dipole_reciprocal_space_op, pme_dipole_recip_bwd_op = _EO["pme_dipole_reciprocal_space"]
@@ -1798,7 +1807,7 @@ rotate_multipoles_op.register_fake(_rotate_fwd_fake)
 rotate_multipoles_op.register_autograd(_rotate_backward, setup_context=_rotate_setup)
 
 
-__all__ = ["torsion_torsion_op", "torsion_torsion_bwd_op", "pme_dispersion_reciprocal_space_op", "pme_dispersion_recip_bwd_op", "ewald_dispersion_real_space_op", "ewald_dispersion_real_bwd_op",
+__all__ = ["generalized_born_op", "generalized_born_bwd_op", "torsion_torsion_op", "torsion_torsion_bwd_op", "pme_dispersion_reciprocal_space_op", "pme_dispersion_recip_bwd_op", "ewald_dispersion_real_space_op", "ewald_dispersion_real_bwd_op",
            "ewald_dispersion_reciprocal_space_op", "ewald_dispersion_recip_bwd_op", "buffered_14_7_op", "buffered_14_7_bwd_op", "lennard_jones_op",
            "lennard_jones_bwd_op", "VDW_OPS", "pair_scale_correction_op", "pair_scale_bwd_op", "dipole_pair_scale_correction_op",
            "dipole_pair_scale_bwd_op", "rotate_multipoles_op", "rotate_multipoles_bwd_op", "coulomb_dipole_correction_op", "coulomb_dipole_bwd_op",

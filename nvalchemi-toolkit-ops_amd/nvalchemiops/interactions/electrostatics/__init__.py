@@ -8,6 +8,7 @@ from nvalchemiops.interactions.electrostatics.quadrupole import (ewald_quadrupol
                                                                  ewald_quadrupole_reciprocal_space)
 from nvalchemiops.interactions.electrostatics.pme_quadrupole import pme_quadrupole_correction, pme_quadrupole_reciprocal_space
 from nvalchemiops.interactions.electrostatics.gaussian import gaussian_charge_correction
+from nvalchemiops.interactions.electrostatics.born import generalized_born
 from nvalchemiops.interactions.electrostatics.induced import (InducedDipoleError, InducedDipoleResult, induced_dipoles,
                                                               scaled_induced_dipoles, thole_induced_dipoles)
 from nvalchemiops.interactions.electrostatics.thole import thole_dipole_correction
@@ -40,4 +41,5 @@ __all__ = [
     "LocalFrames", "rotate_multipoles", "multipole_frame_forces", "FRAME_NONE", "FRAME_Z_ONLY", "FRAME_Z_THEN_X", "FRAME_BISECTOR",
     "FRAME_Z_BISECT", "FRAME_THREE_FOLD",
     "pair_scale_correction", "bonded_pair_scales", "BondedPairScales", "dipole_pair_scale_correction", "PolarizationPairScales", "scaled_induced_dipoles",
+    "generalized_born",
 ]
